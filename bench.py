@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the HOMMX micro-cell hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config C2|C5]
+    python bench.py --gpus N --steps K --warmup W [--config C2|C5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic input.
@@ -15,15 +15,20 @@ A "step" is one pass of the hot path over one batch of synthetic input.
   rotated-fibre theta.  The 24,576 cells are block-partitioned over the N ranks (STRONG scaling); every rank samples only its
   own shard (two phase values + M per cell; the fibre mask once), solves it and the C_H field is all-gathered over RCCL.
 
-Prints ONE JSON line on rank 0 (contract: metric/value/unit/..., plus `roofline` and `cpu_baseline`).
+Prints ONE JSON line on rank 0 (contract: metric/value/unit/..., plus `roofline` from the timed steps' own HIP events).
+`--dump-outputs DIR` writes what the last timed step computed (the effective-tensor field and rank 0's info flags) as DIR/<name>.npy
+in float64; the inputs are synthetic and deterministic, so two builds given the same arguments can be compared output for output.
 
 `value` is the device-resident rate the bench contract asks for (inputs in HBM when the timed region starts; equal to
-`value_device_resident`).  SURVEY 8(d) defines the unit of work WITH the transfers ("H2D of inputs and D2H of A_eff included"): that
-figure is `value_survey_8d` -- the C-ABI call `hommx_solve_batch_two_phase` on HOST arrays, C2's own coefficient shape (a 2 KB phase
-mask + two values per macro cell in, A_H + info out, one synchronisation) -- and `value_host_boundary` is the generic 134 MB element
-stream through `hommx_solve_batch` (PCIe-bound).  The default C2 line also carries a nested `"c5"` record (BASELINE config 5: the 3D
-stratified-elasticity path on the nested-dissection route, all 24,576 cells, `--c5-steps` timed passes with the workspace reserved
-outside the timed region) with its own `roofline` and `cpu_baseline`; `--no-c5` leaves it out.
+`value_device_resident`).  A plain run measures only that: set-up, warm-up, the timed steps, the line.  `--full` adds everything
+else the benchmark measures, each in runs of its own after the timed steps: the measured fp64 peak (calibration kernels), the
+CPU baselines with their parity sample (`cpu_baseline`, `cpu_baseline_optimized`), and for C2 SURVEY 8(d)'s unit of work WITH the
+transfers ("H2D of inputs and D2H of A_eff included"): `value_survey_8d` -- the C-ABI call `hommx_solve_batch_two_phase` on HOST
+arrays, C2's own coefficient shape (a 2 KB phase mask + two values per macro cell in, A_H + info out, one synchronisation) -- and
+`value_host_boundary`, the generic 134 MB element stream through `hommx_solve_batch` (PCIe-bound), plus a nested `"c5"` record
+(BASELINE config 5: the 3D stratified-elasticity path on the nested-dissection route, all 24,576 cells, `--c5-steps` timed passes
+with the workspace reserved outside the timed region) with its own `roofline` and `cpu_baseline`.  `--no-c5`, `--no-host-boundary`
+and `--no-cpu-baseline` leave parts of `--full` out.
 """
 
 from __future__ import annotations
@@ -42,6 +47,21 @@ sys.path.insert(0, HERE)
 FP64_PEAK_DATASHEET = 78.6e12  # FLOP/s, AMD MI355X datasheet: FP64 vector == FP64 matrix (absent from the local guide)
 PMC_SUMMARY = os.path.join("profiles", "r04_c2_pmc_summary.json")
 MF_PMC_SUMMARY = os.path.join("profiles", "r04_mf_pmc_summary.json")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every {name: array} as out_dir/<name>.npy in float64.  When the arrays exceed DUMP_LIMIT_BYTES in all, each
+    keeps a fixed, seeded sample of its leading axis (the macro cells), written beside it as <name>_sample_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:  # half the budget for the samples: their indices take at most as much again
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, a.shape[0] * (DUMP_LIMIT_BYTES // 2) // total), replace=False))
+            a = a[idx]
+            np.save(os.path.join(out_dir, f"{name}_sample_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def flop_model(n: int, b: int | None = None) -> float:
@@ -351,11 +371,14 @@ def main():
     ap.add_argument("--macro", type=int, default=64, help="C2: macro cells per side (64)")
     ap.add_argument("--micro", type=int, default=None, help="micro cells per side (C2: 32, C5: 16)")
     ap.add_argument("--c5-shape", type=int, nargs=3, default=(32, 16, 8), help="C5: macro box (32 16 8 = 24,576 tets)")
-    ap.add_argument("--no-c5", action="store_true", help="C2: leave the nested C5 record (3D elasticity path) out of the line")
-    ap.add_argument("--c5-steps", type=int, default=2, help="C2: timed passes over all 24,576 C5 cells in the nested record (about 9 s each on one GPU)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: nested C5 record, fp64 "
+                    "calibration, host-boundary and two-phase figures, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-c5", action="store_true", help="C2 --full: leave the nested C5 record (3D elasticity path) out of the line")
+    ap.add_argument("--c5-steps", type=int, default=2, help="C2 --full: timed passes over all 24,576 C5 cells in the nested record (about 9 s each on one GPU)")
     ap.add_argument("--c5-warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-boundary", action="store_true", help="skip the host-boundary and two-phase figures")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-host-boundary", action="store_true", help="C2 --full: skip the host-boundary and two-phase figures")
     ap.add_argument("--cpu-cores", type=int, default=0, help="host cores for the CPU baseline (0: min(16, available))")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU work per core")
     ap.add_argument("--cpu-worker", type=int, nargs=2, metavar=("START", "COUNT"), help=argparse.SUPPRESS)
@@ -420,7 +443,7 @@ def main():
     stream = torch.cuda.current_stream()
     if args.config == "C5":
         rec = run_c5(args, torch, dist, use_dist, dev, rank, local_rank, world, MicroCellPlan, workloads, all_gather_field,
-                     shard_range, stream)
+                     shard_range, stream, dump_dir=args.dump_outputs)
         if rank == 0:
             emit(rec)
         if use_dist:
@@ -451,10 +474,12 @@ def main():
 
     dt, kern_ms, ag_ms, field = timed_steps(step, args.steps, args.warmup, use_dist, dist, dev, torch)
     n_bad = int((info != 0).sum().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"effective_tensor": field.cpu().numpy(), "info": info.cpu().numpy()})
 
     # nested record of BASELINE config 5 (the 3D elasticity path): every rank takes part (strong scaling of the 24,576 cells)
     c5 = None
-    if not args.no_c5:
+    if args.full and not args.no_c5:
         try:
             c5 = run_c5(args, torch, dist, use_dist, dev, rank, local_rank, world, MicroCellPlan, workloads, all_gather_field,
                         shard_range, stream, steps=args.c5_steps, warmup=args.c5_warmup, n=16)
@@ -530,27 +555,28 @@ def main():
                 rec["roofline"]["traffic_algorithmic"] = algorithmic_bytes(n, False) * nc
         except Exception:
             pass
-        # fp64 calibration (the local guide lists no f64 peak): best of the MFMA and the FMA loop over 2 and 4 waves per SIMD --
-        # both instructions share one fp64 pipe, so the larger is the measured peak a kernel mixing them is priced against
-        try:
-            import ctypes
+        if args.full:
+            # fp64 calibration (a measured peak beside the datasheet's): best of the MFMA and the FMA loop over 2 and 4 waves per SIMD --
+            # both instructions share one fp64 pipe, so the larger is the measured peak a kernel mixing them is priced against
+            try:
+                import ctypes
 
-            from hommx_amd import _lib
+                from hommx_amd import _lib
 
-            fm, ff, fl = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
-            _lib.check(_lib.load().hommx_calibrate_fp64_detail(local_rank, ctypes.byref(fm), ctypes.byref(ff), ctypes.byref(fl)), "calibrate")
-            peak_m = max(fm.value, ff.value, fl.value)
-            rec["roofline"]["peak_measured_mfma_f64"] = fm.value / 1e12  # dependency-free pure-MFMA loop (clocks down under its own load)
-            rec["roofline"]["peak_measured_mfma_lds_fed_f64"] = fl.value / 1e12  # the MFMA fed from LDS like a GEMM: what a real kernel can hold
-            rec["roofline"]["peak_measured_fma_f64"] = ff.value / 1e12
-            rec["roofline"]["peak_measured_f64"] = peak_m / 1e12
-            rec["roofline"]["frac_of_measured_peak"] = achieved / peak_m
-            rec["roofline"]["frac_executed_of_measured_peak"] = flops_executed_fused2d(n) * nc / (kern_ms * 1e-3) / peak_m
-        except Exception as e:  # pragma: no cover
-            rec["roofline"]["peak_measured_f64"] = None
-            print(f"[bench] calibration failed: {e}", file=sys.stderr)
+                fm, ff, fl = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+                _lib.check(_lib.load().hommx_calibrate_fp64_detail(local_rank, ctypes.byref(fm), ctypes.byref(ff), ctypes.byref(fl)), "calibrate")
+                peak_m = max(fm.value, ff.value, fl.value)
+                rec["roofline"]["peak_measured_mfma_f64"] = fm.value / 1e12  # dependency-free pure-MFMA loop (clocks down under its own load)
+                rec["roofline"]["peak_measured_mfma_lds_fed_f64"] = fl.value / 1e12  # the MFMA fed from LDS like a GEMM: what a real kernel can hold
+                rec["roofline"]["peak_measured_fma_f64"] = ff.value / 1e12
+                rec["roofline"]["peak_measured_f64"] = peak_m / 1e12
+                rec["roofline"]["frac_of_measured_peak"] = achieved / peak_m
+                rec["roofline"]["frac_executed_of_measured_peak"] = flops_executed_fused2d(n) * nc / (kern_ms * 1e-3) / peak_m
+            except Exception as e:  # pragma: no cover
+                rec["roofline"]["peak_measured_f64"] = None
+                print(f"[bench] calibration failed: {e}", file=sys.stderr)
 
-        if world == 1 and not args.no_host_boundary:
+        if args.full and world == 1 and not args.no_host_boundary:
             # SURVEY 8(d)'s unit of work with the transfers in it: pageable NumPy arrays through hommx_solve_batch
             reps = 5
             plan.solve(coef_h)  # staging buffers allocated
@@ -589,7 +615,7 @@ def main():
             rec["two_phase_over_kernel"] = tp * 1e3 / kern_ms
             rec["two_phase_bitwise_equal_to_stream"] = bool(np.array_equal(A_tp, A_host))
 
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import hommx_oracle as O
 
             X = msh.cell_vertices()
@@ -644,11 +670,11 @@ def main():
 
 
 def run_c5(args, torch, dist, use_dist, dev, rank, local_rank, world, MicroCellPlan, workloads, all_gather_field, shard_range,
-           stream, steps=None, warmup=None, n=None):
+           stream, steps=None, warmup=None, n=None, dump_dir=None):
     """BASELINE config 5: strong scaling of the 24,576 stratified 3D elasticity cells over the ranks.  Returns the record on rank 0
-    (None elsewhere).  Under a process group the ranks agree that every one of them got through its set-up (plan, workspace, inputs)
-    BEFORE the first collective of the timed loop: a rank that failed there makes all of them raise instead of leaving the others
-    waiting in an all-gather."""
+    (None elsewhere); with ``dump_dir`` rank 0 writes the last timed step's C_H field and its own info flags there.  Under a process
+    group the ranks agree that every one of them got through its set-up (plan, workspace, inputs) BEFORE the first collective of the
+    timed loop: a rank that failed there makes all of them raise instead of leaving the others waiting in an all-gather."""
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     n = args.micro if n is None else n
@@ -703,6 +729,10 @@ def run_c5(args, torch, dist, use_dist, dev, rank, local_rank, world, MicroCellP
         n_bad = int(nb.item())
     if rank != 0:
         return None
+    if dump_dir:
+        from hommx_amd.dist import _unpad_index
+
+        dump_outputs(dump_dir, {"effective_tensor": field.cpu().numpy()[_unpad_index(ntot, per, world)], "info": info[:nloc].cpu().numpy()})
     bdim = 3 * n * n
     F = flop_model(n, bdim)
     fr = flops_ref(3, n, 3, 6)
@@ -711,7 +741,7 @@ def run_c5(args, torch, dist, use_dist, dev, rank, local_rank, world, MicroCellP
     C = field[:nloc].cpu().numpy()
     sym = float(np.abs(C - np.transpose(C, (0, 2, 1))).max() / np.abs(C).max())
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         avail = usable_cores()
         n_sample = max(1, min(8, avail, ntot))
         rate, done, slowest = cpu_baseline_c5_multicore(args, n_sample, n)
