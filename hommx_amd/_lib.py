@@ -28,6 +28,9 @@ EXPORTED_SYMBOLS = (
     "hommx_plan_kernel_name",
     "hommx_plan_route_detail",
     "hommx_plan_flops_per_solve",
+    "hommx_mesh_analyze",
+    "hommx_plan_create_mesh",
+    "hommx_plan_front_width",
     "hommx_solve_batch",
     "hommx_solve_batch_device",
     "hommx_solve_batch_correctors",
@@ -55,6 +58,7 @@ KIND_ELASTICITY_ISO = 2
 KIND_ELASTICITY_VOIGT = 3
 SAMPLER_AFFINE = 0
 SAMPLER_RECIPROCAL = 1
+MESH_MAX_FRONT = 192  # HOMMX_MESH_MAX_FRONT
 
 
 class PlanDesc(C.Structure):
@@ -65,6 +69,21 @@ class PlanDesc(C.Structure):
         ("device", C.c_int32),
         ("flags", C.c_int32),
         ("reserved", C.c_int32 * 3),
+    ]
+
+
+class MeshDesc(C.Structure):
+    _fields_ = [
+        ("dim", C.c_int32),
+        ("kind", C.c_int32),
+        ("device", C.c_int32),
+        ("flags", C.c_int32),
+        ("n_nodes", C.c_int64),
+        ("n_el", C.c_int64),
+        ("el_nodes", C.c_void_p),
+        ("el_x", C.c_void_p),
+        ("order", C.c_void_p),
+        ("reserved", C.c_int32 * 4),
     ]
 
 
@@ -119,6 +138,12 @@ def load():
     lib.hommx_device_count.argtypes = []
     lib.hommx_plan_create.restype = C.c_int
     lib.hommx_plan_create.argtypes = [C.POINTER(vp), C.POINTER(PlanDesc)]
+    lib.hommx_mesh_analyze.restype = C.c_int
+    lib.hommx_mesh_analyze.argtypes = [C.POINTER(MeshDesc), C.POINTER(i32), dp]
+    lib.hommx_plan_create_mesh.restype = C.c_int
+    lib.hommx_plan_create_mesh.argtypes = [C.POINTER(vp), C.POINTER(MeshDesc)]
+    lib.hommx_plan_front_width.restype = i32
+    lib.hommx_plan_front_width.argtypes = [vp]
     lib.hommx_plan_reserve.restype = C.c_int
     lib.hommx_plan_reserve.argtypes = [vp, i64]
     lib.hommx_plan_destroy.restype = C.c_int

@@ -21,6 +21,39 @@ KINDS = {
 }
 
 
+def mesh_desc(msh, kind: str, device: int = 0, order=None, constraint=None):
+    """hommx_mesh_desc of a unit-cell mesh: periodic node of every element vertex + unfolded coordinates.  Returns (desc, arrays the
+    descriptor points into -- keep them alive while it is used)."""
+    from . import fem
+    from .cell_problem import create_periodic_boundary_conditions
+
+    if constraint is None:
+        constraint = create_periodic_boundary_conditions(fem.FunctionSpace(msh, 1))
+    d = msh.topology.dim
+    to_periodic = np.asarray(constraint.to_periodic, dtype=np.int64)
+    keep = {
+        "to_periodic": to_periodic,
+        "el_nodes": np.ascontiguousarray(to_periodic[msh.cells], dtype=np.int32),
+        "el_x": np.ascontiguousarray(msh.geometry.x[msh.cells][:, :, :d], dtype=np.float64),
+    }
+    if order is not None:
+        keep["order"] = np.ascontiguousarray(order, dtype=np.int32)
+    desc = _lib.MeshDesc(d, KINDS[kind], int(device), 0, int(constraint.num_independent), int(msh.cells.shape[0]),
+                         keep["el_nodes"].ctypes.data, keep["el_x"].ctypes.data,
+                         keep["order"].ctypes.data if order is not None else None)
+    return desc, keep
+
+
+def mesh_analyze(msh, kind: str = "poisson", order=None, constraint=None) -> tuple[int, float]:
+    """(front width in unknowns, flops per solve) of the mesh route for this mesh and order -- host only, no GPU
+    (hommx_mesh_analyze).  Raises HommxLibraryError (code -1, HOMMX_EINVAL) with the reason for a mesh the route cannot take."""
+    desc, keep = mesh_desc(msh, kind, 0, order, constraint)
+    lib = _lib.load()
+    w, fl = C.c_int32(0), C.c_double(0.0)
+    _lib.check(lib.hommx_mesh_analyze(C.byref(desc), C.byref(w), C.byref(fl)), "hommx_mesh_analyze")
+    return int(w.value), float(fl.value)
+
+
 class MicroCellPlan:
     """Everything batch-independent for one (dim, n_micro, kind): kernel choice + device scratch.
 
@@ -42,6 +75,37 @@ class MicroCellPlan:
         self.kernel = self._lib.hommx_plan_kernel_name(h).decode()
         self.route_detail = self._lib.hommx_plan_route_detail(h).decode()  # what that route launches for this plan (reports)
         self.flops_per_solve = float(self._lib.hommx_plan_flops_per_solve(h))  # dense flops of the route, by its own model
+        self.n_nodes = self.n_micro**self.dim  # periodic nodes (correctors: dof = node * bs + component)
+        self.front_width = 0
+        self.to_periodic = None
+
+    @classmethod
+    def from_mesh(cls, msh, kind: str = "poisson", device: int = 0, order=None, constraint=None) -> "MicroCellPlan":
+        """Plan of the mesh route for ANY periodic simplicial mesh of the unit cell (include/hommx_hip.h, hommx_plan_create_mesh).
+
+        The periodic nodes are those of ``create_periodic_boundary_conditions`` (or of ``constraint``, when given); ``to_periodic``
+        maps every mesh vertex to its periodic node, and correctors are indexed by periodic node.  ``order``: elimination order of
+        the periodic nodes (default: the library's reverse Cuthill-McKee).  coef[cell][el] follows the mesh's cell order.
+        ``n_micro`` is None, ``front_width`` the width of the frontal elimination in unknowns."""
+        if kind not in KINDS:
+            raise ValueError(f"unknown kind {kind!r}; expected one of {sorted(KINDS)}")
+        desc, keep = mesh_desc(msh, kind, device, order, constraint)
+        self = cls.__new__(cls)
+        self._lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(self._lib.hommx_plan_create_mesh(C.byref(h), C.byref(desc)), "hommx_plan_create_mesh")
+        self._h = h
+        self.dim, self.n_micro, self.kind, self.device = int(desc.dim), None, kind, int(device)
+        self.n_el = int(self._lib.hommx_plan_num_elements(h))
+        self.n_comp = int(self._lib.hommx_plan_coef_components(h))
+        self.t = int(self._lib.hommx_plan_tensor_size(h))
+        self.kernel = self._lib.hommx_plan_kernel_name(h).decode()
+        self.route_detail = self._lib.hommx_plan_route_detail(h).decode()
+        self.flops_per_solve = float(self._lib.hommx_plan_flops_per_solve(h))
+        self.n_nodes = int(desc.n_nodes)
+        self.front_width = int(self._lib.hommx_plan_front_width(h))
+        self.to_periodic = keep["to_periodic"]
+        return self
 
     def reserve(self, n_cells: int):
         """Allocate the device workspace for batches of up to ``n_cells`` now (otherwise the first solve does it)."""
@@ -82,7 +146,7 @@ class MicroCellPlan:
         info = np.zeros(nc, dtype=np.int32)
         if return_correctors:
             bs = 1 if self.kind.startswith("poisson") else self.dim
-            corr = np.empty((nc, self.t, self.n_micro**self.dim * bs), dtype=np.float64)
+            corr = np.empty((nc, self.t, self.n_nodes * bs), dtype=np.float64)
             if nc:
                 _lib.check(
                     self._lib.hommx_solve_batch_correctors(

@@ -54,7 +54,10 @@ def create_periodic_boundary_conditions(function_space: fem.FunctionSpace, bcs=N
         raise ValueError("Periodic boundary conditions in 1d not implemented.")  # cell_problem.py:27-28
     if d not in (2, 3):
         raise ValueError(f"Unkown topology dimension. {d=} is something unexpected")
-    n = micro_cells_per_side(msh)
+    try:
+        n = micro_cells_per_side(msh)
+    except ValueError:
+        return _match_periodic(function_space)
     x = msh.geometry.x[:, :d]
     lo, hi = x.min(axis=0), x.max(axis=0)
     on_max = np.isclose(x, hi)
@@ -66,6 +69,34 @@ def create_periodic_boundary_conditions(function_space: fem.FunctionSpace, bcs=N
     masters = gm @ stride
     to_periodic = (g % n) @ (n ** np.arange(d))
     return PeriodicConstraint(function_space, slaves, masters, to_periodic, n**d)
+
+
+def _match_periodic(function_space: fem.FunctionSpace) -> PeriodicConstraint:
+    """Any simplicial mesh of the unit cell: every node on a max face is matched geometrically with its image on the min faces, all
+    coordinates on a max face folded at once (edges and corners land on the one independent node of their class).  The independent
+    nodes are the nodes on no max face, numbered in mesh order."""
+    from scipy.spatial import cKDTree
+
+    msh: Mesh = function_space.mesh
+    d = msh.topology.dim
+    x = msh.geometry.x[:, :d]
+    lo, hi = x.min(axis=0), x.max(axis=0)
+    tol = 1e-8 * float((hi - lo).max())
+    on_max = np.abs(x - hi) <= tol
+    slaves = np.nonzero(on_max.any(axis=1))[0]
+    indep = np.nonzero(~on_max.any(axis=1))[0]
+    y = x[slaves].copy()
+    y[on_max[slaves]] = np.broadcast_to(lo, y.shape)[on_max[slaves]]
+    dist, j = cKDTree(x[indep]).query(y, distance_upper_bound=tol)
+    miss = np.nonzero(~np.isfinite(dist))[0]
+    if miss.size:
+        s = int(slaves[miss[0]])
+        raise ValueError(f"micro mesh is not periodic: node {s} at {x[s].tolist()} has no image on the min faces")
+    masters = indep[j]
+    to_periodic = np.empty(x.shape[0], dtype=np.int64)
+    to_periodic[indep] = np.arange(indep.size)
+    to_periodic[slaves] = j
+    return PeriodicConstraint(function_space, slaves, masters, to_periodic, int(indep.size))
 
 
 class PeriodicLinearProblem:
@@ -89,10 +120,15 @@ class PeriodicLinearProblem:
         self._kind = kind
         msh = mpc.function_space.mesh
         self._dim = msh.topology.dim
-        self._n = micro_cells_per_side(msh)
         self._coef = np.asarray(coef, dtype=float)[None]
         self._M = None if M is None else np.asarray(M, dtype=float)[None]
-        self._plan = MicroCellPlan(self._dim, self._n, kind, device=device)
+        try:
+            self._n = micro_cells_per_side(msh)
+        except ValueError:  # unstructured (or nx != ny) micro mesh: the mesh route, on the constraint's periodic numbering
+            self._n = None
+            self._plan = MicroCellPlan.from_mesh(msh, kind, device=device, constraint=mpc)
+        else:
+            self._plan = MicroCellPlan(self._dim, self._n, kind, device=device)
         self.effective_tensor: np.ndarray | None = None
         self.info: int | None = None
 

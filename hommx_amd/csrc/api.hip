@@ -13,6 +13,7 @@
 
 #include "../../include/hommx_hip.h"
 #include "kernels.h"
+#include "mesh_front.h"
 
 namespace {
 
@@ -36,7 +37,7 @@ int fail(int code, const char* fmt, ...) {
                   hipGetErrorString(e__));                                                     \
   } while (0)
 
-enum Family { FAM_FUSED2D = 0, FAM_BLOCKED = 1 };
+enum Family { FAM_FUSED2D = 0, FAM_BLOCKED = 1, FAM_MESH = 2 };
 
 }  // namespace
 
@@ -78,6 +79,7 @@ struct hommx_plan {
   int32_t* d_info = nullptr;
   int64_t cap_cells = 0;
   hommx::BlockedWorkspace* ws = nullptr;
+  hommx::MeshPlan* mesh = nullptr;  // FAM_MESH: symbolic phase + device tables of the unstructured micro mesh
   double* d_expand = nullptr;  // two-phase media on the blocked family: expanded element stream
   int64_t cap_expand = 0;
   // plan-owned staging of the sampler entry points (two-phase / separable, host pointers): grown on demand, never per call
@@ -148,6 +150,7 @@ int hommx_plan_destroy(hommx_plan* p) {
   if (p->d_out) hipFree(p->d_out);
   if (p->d_info) hipFree(p->d_info);
   if (p->ws) hommx::blocked_workspace_destroy(p->ws);
+  if (p->mesh) hommx::mesh_destroy(p->mesh);
   if (p->d_expand) hipFree(p->d_expand);
   for (hommx_plan::Buf* b : {&p->st_mask, &p->st_values, &p->st_table, &p->st_w, &p->st_M, &p->st_out, &p->st_info, &p->dev_in, &p->dev_out})
     if (b->p) hipFree(b->p);
@@ -176,6 +179,10 @@ int hommx_plan_reserve(hommx_plan* p, int64_t n_cells) {
   if (n_cells < 0) return fail(HOMMX_EINVAL, "negative n_cells");
   if (p->family == FAM_FUSED2D || n_cells == 0) return HOMMX_OK;  // the fused 2D family keeps no scratch
   HIP_TRY(hipSetDevice(p->desc.device));
+  if (p->family == FAM_MESH) {
+    int rc = hommx::mesh_reserve(p->mesh, n_cells);
+    return rc ? fail(rc, "mesh route: %s", hommx::mesh_last_error()) : HOMMX_OK;
+  }
   int rc = hommx::blocked_reserve(p->ws, n_cells);
   if (rc != 0) return fail(rc, "blocked path: %s", hommx::blocked_last_error());
   return HOMMX_OK;
@@ -187,10 +194,12 @@ double hommx_plan_flops_per_solve(const hommx_plan* p) {
     const double n = p->desc.n_micro;
     return (6.0 * (n - 1) + 2.0) * n * n * n;
   }
+  if (p->family == FAM_MESH) return hommx::mesh_flops_per_cell(p->mesh);
   return hommx::blocked_flops_per_cell(p->ws);
 }
 const char* hommx_plan_kernel_name(const hommx_plan* p) {
   if (!p) return "";
+  if (p->family == FAM_MESH) return "mesh_front";
   return p->family == FAM_FUSED2D ? "fused2d" : hommx::blocked_route_name(p->ws);
 }
 
@@ -199,8 +208,73 @@ const char* hommx_plan_route_detail(hommx_plan* p) {
   if (p->family == FAM_FUSED2D)
     return p->desc.n_micro > 16 ? "fused2d: k_poisson2d_fused<32>, one wavefront per macro cell, every matrix in the f64 MFMA accumulator layout"
                                 : "fused2d: k_poisson2d_fused<16>, one wavefront per macro cell, every matrix in the f64 MFMA accumulator layout";
+  if (p->family == FAM_MESH) return hommx::mesh_route_detail(p->mesh);
   return hommx::blocked_route_detail(p->ws);
 }
+
+}  // extern "C"
+
+namespace {
+// an element stream on the device through the plan's blocked or mesh route
+int solve_stream(hommx_plan* p, int64_t n_cells, const double* d_coef, const double* d_M, double* d_A_eff, int32_t* d_info, hipStream_t st) {
+  if (p->family == FAM_MESH) {
+    int rc = hommx::mesh_solve(p->mesh, n_cells, d_coef, d_M, d_A_eff, d_info, st);
+    return rc ? fail(rc, "mesh route: %s", hommx::mesh_last_error()) : HOMMX_OK;
+  }
+  int rc = hommx::blocked_solve(p->ws, n_cells, d_coef, d_M, d_A_eff, d_info, st);
+  return rc ? fail(rc, "blocked path: %s", hommx::blocked_last_error()) : HOMMX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int hommx_mesh_analyze(const hommx_mesh_desc* d, int32_t* front_width, double* flops_per_solve) {
+  int rc = hommx::mesh_analyze(d, nullptr, front_width, flops_per_solve);
+  return rc ? fail(rc, "%s", hommx::mesh_last_error()) : HOMMX_OK;
+}
+
+int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d) {
+  if (!out || !d) return fail(HOMMX_EINVAL, "null argument");
+  *out = nullptr;
+  hommx::MeshPlan* m = nullptr;
+  int rc = hommx::mesh_analyze(d, &m, nullptr, nullptr);  // every argument check runs before the device is touched
+  if (rc) return fail(rc, "%s", hommx::mesh_last_error());
+  int ndev = hommx_device_count();
+  if (ndev <= 0 || d->device < 0 || d->device >= ndev) {
+    hommx::mesh_destroy(m);
+    return ndev <= 0 ? fail(HOMMX_ENODEV, "no HIP device visible") : fail(HOMMX_EINVAL, "device %d out of range [0,%d)", d->device, ndev);
+  }
+  hommx_plan* p = new (std::nothrow) hommx_plan();
+  if (!p) {
+    hommx::mesh_destroy(m);
+    return fail(HOMMX_ENOMEM, "host allocation failed");
+  }
+  p->desc.dim = d->dim;
+  p->desc.n_micro = 0;
+  p->desc.kind = d->kind;
+  p->desc.device = d->device;
+  p->desc.flags = d->flags;
+  p->family = FAM_MESH;
+  p->mesh = m;
+  p->n_el = d->n_el;
+  const int dim = d->dim, te = dim * (dim + 1) / 2;
+  switch (d->kind) {
+    case HOMMX_KIND_POISSON_SCALAR: p->n_comp = 1; p->t = dim; break;
+    case HOMMX_KIND_POISSON_MATRIX: p->n_comp = te; p->t = dim; break;
+    case HOMMX_KIND_ELASTICITY_ISO: p->n_comp = 2; p->t = te; break;
+    default: p->n_comp = te * (te + 1) / 2; p->t = te; break;
+  }
+  p->h2d_overlap = getenv("HOMMX_NO_H2D_OVERLAP") == nullptr;
+  if (hipSetDevice(d->device) != hipSuccess || (rc = hommx::mesh_upload(m)) != 0) {
+    const std::string msg = rc ? hommx::mesh_last_error() : "hipSetDevice failed";
+    hommx_plan_destroy(p);
+    return fail(rc ? rc : HOMMX_EHIP, "mesh route: %s", msg.c_str());
+  }
+  *out = p;
+  return HOMMX_OK;
+}
+
+int32_t hommx_plan_front_width(const hommx_plan* p) { return p && p->family == FAM_MESH ? hommx::mesh_front_width(p->mesh) : 0; }
 
 int hommx_solve_batch_device(hommx_plan* p, int64_t n_cells, const double* d_coef, const double* d_M,
                              double* d_A_eff, int32_t* d_info, void* stream) {
@@ -215,9 +289,7 @@ int hommx_solve_batch_device(hommx_plan* p, int64_t n_cells, const double* d_coe
     HIP_TRY(hommx::launch_poisson2d_fused(d_coef, d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st));
     return HOMMX_OK;
   }
-  int rc = hommx::blocked_solve(p->ws, n_cells, d_coef, d_M, d_A_eff, d_info, st);
-  if (rc != 0) return fail(rc, "blocked path: %s", hommx::blocked_last_error());
-  return HOMMX_OK;
+  return solve_stream(p, n_cells, d_coef, d_M, d_A_eff, d_info, st);
 }
 
 int hommx_solve_batch(hommx_plan* p, int64_t n_cells, const double* coef, const double* M, double* A_eff,
@@ -299,7 +371,7 @@ int hommx_solve_batch_two_phase_device(hommx_plan* p, int64_t n_cells, const uin
     HIP_TRY(hommx::launch_poisson2d_fused(d_values, d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st, src));
     return HOMMX_OK;
   }
-  // blocked family: expand on the device, chunk by chunk of at most 1 GiB of element stream
+  // blocked and mesh families: expand on the device, chunk by chunk of at most 1 GiB of element stream
   const int64_t per = p->n_el * p->n_comp;
   int64_t chunk = (int64_t)((1ll << 27) / (per > 0 ? per : 1));
   if (chunk < 1) chunk = 1;
@@ -315,9 +387,8 @@ int hommx_solve_batch_two_phase_device(hommx_plan* p, int64_t n_cells, const uin
   for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
     const int64_t nc = (n_cells - c0 < chunk) ? n_cells - c0 : chunk;
     HIP_TRY(hommx::launch_expand_two_phase(d_mask, d_values + c0 * 2 * p->n_comp, p->d_expand, p->n_el, p->n_comp, nc, st));
-    int rc = hommx::blocked_solve(p->ws, nc, p->d_expand, d_M ? d_M + c0 * d * d : nullptr, d_A_eff + c0 * t * t,
-                                  d_info ? d_info + c0 : nullptr, st);
-    if (rc != 0) return fail(rc, "blocked path: %s", hommx::blocked_last_error());
+    int rc = solve_stream(p, nc, p->d_expand, d_M ? d_M + c0 * d * d : nullptr, d_A_eff + c0 * t * t, d_info ? d_info + c0 : nullptr, st);
+    if (rc != HOMMX_OK) return rc;
   }
   return HOMMX_OK;
 }
@@ -384,7 +455,7 @@ int hommx_solve_batch_separable_device(hommx_plan* p, int64_t n_cells, int32_t f
     HIP_TRY(hommx::launch_poisson2d_fused(d_params, d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st, src));
     return HOMMX_OK;
   }
-  // blocked family: expand on the device, chunk by chunk of at most 1 GiB of element stream
+  // blocked and mesh families: expand on the device, chunk by chunk of at most 1 GiB of element stream
   const int64_t per = p->n_el * p->n_comp;
   int64_t chunk = (int64_t)((1ll << 27) / (per > 0 ? per : 1));
   if (chunk < 1) chunk = 1;
@@ -400,9 +471,8 @@ int hommx_solve_batch_separable_device(hommx_plan* p, int64_t n_cells, int32_t f
   for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
     const int64_t nc = (n_cells - c0 < chunk) ? n_cells - c0 : chunk;
     HIP_TRY(hommx::launch_expand_separable(src, d_params + 2 * p->n_comp * c0, p->d_expand, p->n_el, p->n_comp, nc, st));
-    int rc = hommx::blocked_solve(p->ws, nc, p->d_expand, d_M ? d_M + c0 * d * d : nullptr, d_A_eff + c0 * t * t,
-                                  d_info ? d_info + c0 : nullptr, st);
-    if (rc != 0) return fail(rc, "blocked path: %s", hommx::blocked_last_error());
+    int rc = solve_stream(p, nc, p->d_expand, d_M ? d_M + c0 * d * d : nullptr, d_A_eff + c0 * t * t, d_info ? d_info + c0 : nullptr, st);
+    if (rc != HOMMX_OK) return rc;
   }
   return HOMMX_OK;
 }
@@ -448,14 +518,17 @@ int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* c
   if (n_cells == 0) return HOMMX_OK;
   if (!coef || !A_eff || !correctors) return fail(HOMMX_EINVAL, "null coef / A_eff / correctors");
   HIP_TRY(hipSetDevice(p->desc.device));
-  if (!p->ws) {
+  if (p->family != FAM_MESH && !p->ws) {
     int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
     if (rc != 0) return fail(rc, "blocked path: %s", hommx::blocked_last_error());
   }
   const int d = p->desc.dim, t = p->t;
   const int bs = (p->desc.kind >= HOMMX_KIND_ELASTICITY_ISO) ? d : 1;
   long long nn = 1;
-  for (int k = 0; k < d; ++k) nn *= p->desc.n_micro;
+  if (p->family == FAM_MESH)
+    nn = hommx::mesh_num_nodes(p->mesh);
+  else
+    for (int k = 0; k < d; ++k) nn *= p->desc.n_micro;
   double *d_coef = nullptr, *d_M = nullptr, *d_out = nullptr, *d_corr = nullptr;
   int32_t* d_info = nullptr;
   auto cleanup = [&]() {
@@ -484,10 +557,11 @@ int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* c
     HIP_TRY_C(hipMalloc(&d_M, sizeof(double) * n_cells * d * d));
     HIP_TRY_C(hipMemcpy(d_M, M, sizeof(double) * n_cells * d * d, hipMemcpyHostToDevice));
   }
-  int rc = hommx::blocked_solve(p->ws, n_cells, d_coef, d_M, d_out, d_info, nullptr, d_corr);
+  int rc = p->family == FAM_MESH ? hommx::mesh_solve(p->mesh, n_cells, d_coef, d_M, d_out, d_info, nullptr, d_corr)
+                                 : hommx::blocked_solve(p->ws, n_cells, d_coef, d_M, d_out, d_info, nullptr, d_corr);
   if (rc != 0) {
     cleanup();
-    return fail(rc, "blocked path: %s", hommx::blocked_last_error());
+    return fail(rc, "%s", p->family == FAM_MESH ? hommx::mesh_last_error() : hommx::blocked_last_error());
   }
   HIP_TRY_C(hipDeviceSynchronize());
   HIP_TRY_C(hipMemcpy(A_eff, d_out, sizeof(double) * n_cells * t * t, hipMemcpyDeviceToHost));

@@ -1,0 +1,36 @@
+// mesh_front.h -- internal interface of the mesh route (mesh_front.hip): cell problems on an unstructured periodic micro mesh,
+// eliminated by a batched frontal method.
+//
+// The symbolic phase (validation, elimination order, front slots, assembly groups) is plain host code: hommx_mesh_analyze and the
+// argument checks of hommx_plan_create_mesh run it without a GPU.  mesh_upload moves its tables to the device.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/hommx_hip.h"
+
+namespace hommx {
+
+struct MeshPlan;
+
+// Validates the descriptor and runs the symbolic phase.  out == nullptr: analysis only (hommx_mesh_analyze).  Returns 0 or HOMMX_EINVAL /
+// HOMMX_ENOMEM with the message in mesh_last_error().
+int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width, double* flops_per_solve);
+// device tables of the plan (after mesh_analyze with out != nullptr; the caller has selected the plan's device)
+int mesh_upload(MeshPlan* m);
+void mesh_destroy(MeshPlan* m);
+const char* mesh_last_error();
+
+int32_t mesh_front_width(const MeshPlan* m);
+double mesh_flops_per_cell(const MeshPlan* m);
+int64_t mesh_num_nodes(const MeshPlan* m);
+const char* mesh_route_detail(MeshPlan* m);
+// allocate the corrector arena for batches of up to n_cells now (the effective-tensor path keeps no workspace)
+int mesh_reserve(MeshPlan* m, long long n_cells);
+
+// coef[cell][el][n_comp] (caller's element order), M[cell][d][d] or null -> out[cell][t][t], info[cell] (may be null);
+// d_corr != null: also the correctors [cell][t][n_nodes * bs] (mean-free), by back substitution over the factor arena
+int mesh_solve(MeshPlan* m, long long ncells, const double* d_coef, const double* d_M, double* d_out, int32_t* d_info, hipStream_t stream,
+               double* d_corr = nullptr);
+
+}  // namespace hommx

@@ -249,7 +249,10 @@ class BaseHMM(ABC):
             raise ValueError("Topological dimension is different from geometrical dimension for micro mesh.")
         if self._tdim != msh_micro.topology.dim:
             raise ValueError("Micro and macro mesh should have the same dimensionality.")  # hmm.py:114-115
-        self._n_micro = micro_cells_per_side(msh_micro)
+        try:
+            self._n_micro = micro_cells_per_side(msh_micro)
+        except ValueError:  # any other periodic unit-cell mesh: the mesh route (MicroCellPlan.from_mesh)
+            self._n_micro = None
         self._cell_mesh_area = float(msh_micro.cell_volumes().sum())  # hmm.py:101
         if isinstance(A, TwoPhase) and quadrature_degree not in (None, 0, 1):
             raise ValueError("a TwoPhase coefficient is piecewise constant in y (UFL: degree 0, centroid rule); "
@@ -494,7 +497,10 @@ class BaseHMM(ABC):
                 from .dist import default_device
 
                 self._device = default_device()
-            self._plan = MicroCellPlan(self._tdim, self._n_micro, kind, device=self._device)
+            if self._n_micro is None:
+                self._plan = MicroCellPlan.from_mesh(self._cell_mesh, kind, device=self._device)
+            else:
+                self._plan = MicroCellPlan(self._tdim, self._n_micro, kind, device=self._device)
             self._reserved_cells = 0
         if n_cells and n_cells > getattr(self, "_reserved_cells", 0) and hasattr(self._plan, "reserve"):
             self._plan.reserve(int(n_cells))
@@ -632,6 +638,12 @@ class BaseHMM(ABC):
 
     def _periodic_to_micro_nodes(self) -> np.ndarray:
         """Micro-mesh node -> periodic unknown (the slave -> master map of cell_problem.py:38-300 on the torus)."""
+        if self._n_micro is None:
+            if self._plan is not None and self._plan.to_periodic is not None:
+                return self._plan.to_periodic
+            from .cell_problem import create_periodic_boundary_conditions
+
+            return create_periodic_boundary_conditions(fem.FunctionSpace(self._cell_mesh, 1)).to_periodic
         n, d = self._n_micro, self._tdim
         g = np.rint(self._cell_mesh.geometry.x[:, :d] * n).astype(np.int64) % n
         return g @ (n ** np.arange(d))

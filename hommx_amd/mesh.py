@@ -105,6 +105,32 @@ def create_unit_cube(nx: int, ny: int, nz: int, comm=None) -> Mesh:
     return create_box([(0.0, 0.0, 0.0), (1.0, 1.0, 1.0)], (nx, ny, nz), comm)
 
 
+def create_mesh(cells, x, comm=None) -> Mesh:
+    """Unstructured P1 simplicial mesh from its cells [n_cells, dim+1] and vertex coordinates x [n_vertices, gdim] (dolfinx's
+    ``mesh.create_mesh(comm, cells, x, element)`` without the communicator and the element).  ``shape == ()``: the micro solver
+    takes the mesh route (``MicroCellPlan.from_mesh``) for it."""
+    cells = np.asarray(cells)
+    x = np.asarray(x, dtype=float)
+    if cells.ndim != 2 or cells.shape[1] not in (3, 4):
+        raise ValueError(f"cells must have shape (n_cells, 3) or (n_cells, 4), got {cells.shape}")
+    if cells.shape[0] == 0:
+        raise ValueError("the mesh has no cells")
+    if not np.issubdtype(cells.dtype, np.integer):
+        raise ValueError(f"cells must be integers, got {cells.dtype}")
+    d = cells.shape[1] - 1
+    if x.ndim != 2 or not (d <= x.shape[1] <= 3):
+        raise ValueError(f"x must have shape (n_vertices, {d}..3) for {d}D cells, got {x.shape}")
+    if not np.isfinite(x).all():
+        raise ValueError("x holds non-finite coordinates")
+    if cells.min() < 0 or cells.max() >= x.shape[0]:
+        raise ValueError(f"cells reference vertices outside [0, {x.shape[0]})")
+    if (np.sort(cells, axis=1)[:, 1:] == np.sort(cells, axis=1)[:, :-1]).any():
+        raise ValueError("a cell repeats a vertex")
+    x3 = np.zeros((x.shape[0], 3))
+    x3[:, : x.shape[1]] = x
+    return Mesh(Geometry(x3, d), Topology(d), cells.astype(np.int32), (), comm)
+
+
 def micro_cells_per_side(msh: Mesh) -> int:
     """n of a unit-cell mesh built by create_unit_square(n, n) / create_unit_cube(n, n, n)."""
     if not msh.shape or len(set(msh.shape)) != 1:

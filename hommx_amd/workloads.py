@@ -164,3 +164,77 @@ def c5_rotated_fibres(shape=(32, 16, 8), n=16):
     c = msh.cell_midpoints()
     coef = fibre_lame(c, n, np.full(c.shape[0], 100.0))
     return msh, coef, c5_theta_transpose(c)  # M[i][j] = d theta_j / d x_i (hmm.py:741)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# unstructured periodic micro meshes (the mesh route, MicroCellPlan.from_mesh); seeded, periodic-compatible by construction: only
+# interior vertices move, so the boundary vertices of opposite faces keep matching
+# --------------------------------------------------------------------------------------------------------------------------------
+
+
+def _positive(cells: np.ndarray, x: np.ndarray, dim: int) -> np.ndarray:
+    """Cells reoriented to a positive signed volume; asserts that no cell is flat."""
+    X = x[cells][:, :, :dim]
+    det = np.linalg.det(X[:, 1:, :] - X[:, :1, :])
+    cells = cells.copy()
+    neg = det < 0
+    cells[neg, 0], cells[neg, 1] = cells[neg, 1], cells[neg, 0].copy()
+    vol = np.abs(det) / (2.0 if dim == 2 else 6.0)
+    assert (vol > 1e-3 * vol.mean()).all(), f"degenerate element: smallest volume {vol.min():.3g}"
+    return cells
+
+
+def _jitter_interior(x: np.ndarray, dim: int, h: np.ndarray, amount: float, rng) -> np.ndarray:
+    x = x.copy()
+    inner = np.all((x[:, :dim] > 1e-12) & (x[:, :dim] < 1.0 - 1e-12), axis=1)
+    x[inner, :dim] += rng.uniform(-amount, amount, size=(int(inner.sum()), dim)) * h
+    return x
+
+
+def jittered_unit_square(nx: int, ny: int, jitter: float = 0.25, seed: int = 0) -> _mesh.Mesh:
+    """create_unit_square(nx, ny) with every interior vertex moved by up to ``jitter`` cell widths and a random diagonal in every
+    square: an unstructured periodic mesh of the unit square."""
+    rng = np.random.default_rng(seed)
+    base = _mesh.create_unit_square(nx, ny)
+    x = _jitter_interior(base.geometry.x, 2, np.array([1.0 / nx, 1.0 / ny]), jitter, rng)
+    c = base.cells.reshape(-1, 2, 3)  # (v0, v1, v3), (v0, v2, v3) per square
+    v0, v1, v3, v2 = c[:, 0, 0], c[:, 0, 1], c[:, 0, 2], c[:, 1, 1]
+    flip = rng.random(len(c)) < 0.5
+    t1 = np.where(flip[:, None], np.stack([v0, v1, v2], 1), np.stack([v0, v1, v3], 1))
+    t2 = np.where(flip[:, None], np.stack([v1, v3, v2], 1), np.stack([v0, v2, v3], 1))
+    cells = np.stack([t1, t2], 1).reshape(-1, 3)
+    return _mesh.create_mesh(_positive(cells, x, 2), x[:, :2])
+
+
+def layered_unit_square(interfaces, nx: int = 16, ny: int = 16, seed: int = 0) -> _mesh.Mesh:
+    """A mesh of the unit square graded to conform to the horizontal layer interfaces y = interfaces[i]: the rows of the grid are
+    the union of ny uniform rows and the interfaces (uniform rows closer than a third of a row to an interface dropped), the interior
+    vertices off the interfaces move in x by up to a quarter cell, and every square takes a random diagonal."""
+    rng = np.random.default_rng(seed)
+    yi = np.asarray(sorted(float(v) for v in interfaces if 0.0 < float(v) < 1.0))
+    yu = np.linspace(0.0, 1.0, ny + 1)
+    keep = np.array([np.all(np.abs(yi - v) > 1.0 / (3 * ny)) or v in (0.0, 1.0) for v in yu]) if yi.size else np.ones(ny + 1, bool)
+    ys = np.unique(np.concatenate([yu[keep], yi]))
+    xs = np.linspace(0.0, 1.0, nx + 1)
+    X, Y = np.meshgrid(xs, ys, indexing="xy")
+    x = np.stack([X.ravel(), Y.ravel()], 1)
+    inner = (x[:, 0] > 0) & (x[:, 0] < 1) & (x[:, 1] > 0) & (x[:, 1] < 1)
+    x[inner, 0] += rng.uniform(-0.25, 0.25, int(inner.sum())) / nx
+    nxv, nrow = nx + 1, len(ys) - 1
+    ci, cj = np.meshgrid(np.arange(nx), np.arange(nrow), indexing="xy")
+    v0 = (cj * nxv + ci).ravel()
+    v1, v2 = v0 + 1, v0 + nxv
+    v3 = v1 + nxv
+    flip = rng.random(v0.size) < 0.5
+    t1 = np.where(flip[:, None], np.stack([v0, v1, v2], 1), np.stack([v0, v1, v3], 1))
+    t2 = np.where(flip[:, None], np.stack([v1, v3, v2], 1), np.stack([v0, v2, v3], 1))
+    cells = np.stack([t1, t2], 1).reshape(-1, 3)
+    return _mesh.create_mesh(_positive(cells, x, 2), x)
+
+
+def jittered_unit_cube(nx: int, ny: int, nz: int, jitter: float = 0.15, seed: int = 0) -> _mesh.Mesh:
+    """create_unit_cube(nx, ny, nz) with every interior vertex moved by up to ``jitter`` cell widths."""
+    rng = np.random.default_rng(seed)
+    base = _mesh.create_unit_cube(nx, ny, nz)
+    x = _jitter_interior(base.geometry.x, 3, np.array([1.0 / nx, 1.0 / ny, 1.0 / nz]), jitter, rng)
+    return _mesh.create_mesh(_positive(base.cells, x, 3), x)

@@ -196,6 +196,42 @@ int hommx_solve_batch_correctors(hommx_plan* plan, int64_t n_cells, const double
                                  double* A_eff, double* correctors, int32_t* info);
 
 /*
+ * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
+ * periodic: the caller folds the mesh vertices into n_nodes independent (periodic) nodes -- cell_problem.py:38-300's slave -> master
+ * map -- and passes, per element, the periodic node of every vertex and the UNFOLDED vertex coordinates (gradients and volumes).
+ * The plan is a hommx_plan of its own route ("mesh_front": batched frontal elimination, one workgroup per macro cell, the front in
+ * LDS); hommx_solve_batch[_device], _two_phase[_device], _separable[_device], _correctors, hommx_plan_reserve, the accessors and
+ * hommx_plan_destroy take it unchanged (hommx_plan_n_micro is 0).  hommx_solve_batch_multi[_device] refuses it (HOMMX_EINVAL).
+ *
+ *   coef[cell][el]    follows the element order of the descriptor
+ *   gauge             the last node of the elimination order is pinned (its bs unknowns dropped), as on the structured routes
+ *   correctors        [n_cells][t][n_nodes * bs], dof = node * bs + component in the caller's node ids, mean-free per component
+ *   info[cell]        k > 0: the k-th pivot (counted from 1 in elimination order) was non-positive or not finite
+ *   flops_per_solve   sum over the pivots of f^2 + 2 f t, f = unknowns in the front at that pivot (itself included)
+ */
+#define HOMMX_MESH_MAX_FRONT 192  /* largest front, in unknowns: the packed front of t + 192 rows fills the 160 KiB LDS of a CU */
+
+typedef struct hommx_mesh_desc {
+  int32_t dim, kind, device, flags;   /* as hommx_plan_desc; flags normally 0                                     */
+  int64_t n_nodes;                    /* independent (periodic) nodes                                             */
+  int64_t n_el;                       /* micro elements; coef[cell][el] follows THIS order                        */
+  const int32_t* el_nodes;            /* [n_el][dim+1]  periodic node of each vertex                              */
+  const double* el_x;                 /* [n_el][dim+1][dim] vertex coordinates, NOT folded: gradients and volumes */
+  const int32_t* order;               /* [n_nodes] elimination order, or NULL: the library's own (narrowest of reverse Cuthill-McKee and coordinate sweeps) */
+  int32_t reserved[4];
+} hommx_mesh_desc;
+
+/* Validation and symbolic phase only, no GPU: node range, every node used, no repeated node in an element, non-degenerate elements,
+ * element volumes summing to 1 (the unit cell), a connected mesh, `order` a permutation, front width <= HOMMX_MESH_MAX_FRONT.  Any
+ * failure returns HOMMX_EINVAL with the reason (the measured width and the limit for a front that is too wide).  Either output may
+ * be NULL. */
+int hommx_mesh_analyze(const hommx_mesh_desc* d, int32_t* front_width, double* flops_per_solve);
+/* The same checks, then the plan on d->device. */
+int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d);
+/* Front width of a mesh plan in unknowns; 0 for the structured routes. */
+int32_t hommx_plan_front_width(const hommx_plan* plan);
+
+/*
  * Multi-GPU from ONE process: the macro cells are block-partitioned over the devices of a communicator --
  * the reference's MPI partition of the cell loop (hmm.py:307-310) -- and ONE RCCL all-gather over xGMI returns the whole
  * effective-tensor field (with the per-cell info flags riding in the same buffer) to every device, where the reference merges
