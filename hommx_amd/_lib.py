@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "hommx_plan_route_detail",
     "hommx_plan_flops_per_solve",
     "hommx_mesh_analyze",
+    "hommx_mesh_analyze_tree",
     "hommx_plan_create_mesh",
     "hommx_plan_front_width",
     "hommx_solve_batch",
@@ -59,6 +60,7 @@ KIND_ELASTICITY_VOIGT = 3
 SAMPLER_AFFINE = 0
 SAMPLER_RECIPROCAL = 1
 MESH_MAX_FRONT = 192  # HOMMX_MESH_MAX_FRONT
+MESH_FLAG_TREE = 1  # HOMMX_MESH_FLAG_TREE
 
 
 class PlanDesc(C.Structure):
@@ -140,6 +142,8 @@ def load():
     lib.hommx_plan_create.argtypes = [C.POINTER(vp), C.POINTER(PlanDesc)]
     lib.hommx_mesh_analyze.restype = C.c_int
     lib.hommx_mesh_analyze.argtypes = [C.POINTER(MeshDesc), C.POINTER(i32), dp]
+    lib.hommx_mesh_analyze_tree.restype = C.c_int
+    lib.hommx_mesh_analyze_tree.argtypes = [C.POINTER(MeshDesc), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), dp, vp, vp]
     lib.hommx_plan_create_mesh.restype = C.c_int
     lib.hommx_plan_create_mesh.argtypes = [C.POINTER(vp), C.POINTER(MeshDesc)]
     lib.hommx_plan_front_width.restype = i32

@@ -21,7 +21,7 @@ KINDS = {
 }
 
 
-def mesh_desc(msh, kind: str, device: int = 0, order=None, constraint=None):
+def mesh_desc(msh, kind: str, device: int = 0, order=None, constraint=None, flags: int = 0):
     """hommx_mesh_desc of a unit-cell mesh: periodic node of every element vertex + unfolded coordinates.  Returns (desc, arrays the
     descriptor points into -- keep them alive while it is used)."""
     from . import fem
@@ -38,7 +38,7 @@ def mesh_desc(msh, kind: str, device: int = 0, order=None, constraint=None):
     }
     if order is not None:
         keep["order"] = np.ascontiguousarray(order, dtype=np.int32)
-    desc = _lib.MeshDesc(d, KINDS[kind], int(device), 0, int(constraint.num_independent), int(msh.cells.shape[0]),
+    desc = _lib.MeshDesc(d, KINDS[kind], int(device), int(flags), int(constraint.num_independent), int(msh.cells.shape[0]),
                          keep["el_nodes"].ctypes.data, keep["el_x"].ctypes.data,
                          keep["order"].ctypes.data if order is not None else None)
     return desc, keep
@@ -52,6 +52,22 @@ def mesh_analyze(msh, kind: str = "poisson", order=None, constraint=None) -> tup
     w, fl = C.c_int32(0), C.c_double(0.0)
     _lib.check(lib.hommx_mesh_analyze(C.byref(desc), C.byref(w), C.byref(fl)), "hommx_mesh_analyze")
     return int(w.value), float(fl.value)
+
+
+def mesh_analyze_tree(msh, kind: str = "poisson", constraint=None) -> dict:
+    """The tree route's symbolic phase for this mesh (hommx_mesh_analyze_tree) -- host only, no GPU.  Returns n_fronts, n_groups,
+    max_front (largest front, unknowns), flops_per_solve (multifrontal model), supernode_of_node[n_nodes] and parent[n_fronts] (supernodes
+    in elimination order, children first, parent -1 at the root).  Raises HommxLibraryError (HOMMX_EINVAL) for a mesh it cannot take."""
+    desc, keep = mesh_desc(msh, kind, 0, None, constraint)
+    lib = _lib.load()
+    nf, ng, mx, fl = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+    sn = np.empty(int(desc.n_nodes), dtype=np.int32)
+    _lib.check(lib.hommx_mesh_analyze_tree(C.byref(desc), C.byref(nf), C.byref(ng), C.byref(mx), C.byref(fl), sn.ctypes.data, None),
+               "hommx_mesh_analyze_tree")
+    parent = np.empty(int(nf.value), dtype=np.int32)
+    _lib.check(lib.hommx_mesh_analyze_tree(C.byref(desc), None, None, None, None, None, parent.ctypes.data), "hommx_mesh_analyze_tree")
+    return {"n_fronts": int(nf.value), "n_groups": int(ng.value), "max_front": int(mx.value), "flops_per_solve": float(fl.value),
+            "supernode_of_node": sn, "parent": parent}
 
 
 class MicroCellPlan:
@@ -80,18 +96,26 @@ class MicroCellPlan:
         self.to_periodic = None
 
     @classmethod
-    def from_mesh(cls, msh, kind: str = "poisson", device: int = 0, order=None, constraint=None) -> "MicroCellPlan":
+    def from_mesh(cls, msh, kind: str = "poisson", device: int = 0, order=None, constraint=None, route: str | None = None) -> "MicroCellPlan":
         """Plan of the mesh route for ANY periodic simplicial mesh of the unit cell (include/hommx_hip.h, hommx_plan_create_mesh).
 
         The periodic nodes are those of ``create_periodic_boundary_conditions`` (or of ``constraint``, when given); ``to_periodic``
         maps every mesh vertex to its periodic node, and correctors are indexed by periodic node.  ``order``: elimination order of
         the periodic nodes (default: the library's reverse Cuthill-McKee).  coef[cell][el] follows the mesh's cell order.
-        ``n_micro`` is None, ``front_width`` the width of the frontal elimination in unknowns."""
+        ``n_micro`` is None, ``front_width`` the width of the frontal elimination in unknowns (0 on the tree route).
+
+        ``route``: None lets the library choose (the frontal route "mesh_front" up to a front of 192 unknowns, the nested-dissection route
+        "mesh_multifrontal" beyond); "front" insists on the frontal route (HOMMX_EINVAL for a mesh too wide for it); "tree" takes the
+        nested-dissection route for any mesh (``order`` is then ignored)."""
         if kind not in KINDS:
             raise ValueError(f"unknown kind {kind!r}; expected one of {sorted(KINDS)}")
-        desc, keep = mesh_desc(msh, kind, device, order, constraint)
+        if route not in (None, "front", "tree"):
+            raise ValueError(f"unknown route {route!r}; expected None, 'front' or 'tree'")
+        desc, keep = mesh_desc(msh, kind, device, order, constraint, flags=_lib.MESH_FLAG_TREE if route == "tree" else 0)
         self = cls.__new__(cls)
         self._lib = _lib.load()
+        if route == "front":  # the frontal route's own analysis: its error (front too wide) instead of the tree route
+            _lib.check(self._lib.hommx_mesh_analyze(C.byref(desc), None, None), "hommx_mesh_analyze")
         h = C.c_void_p()
         _lib.check(self._lib.hommx_plan_create_mesh(C.byref(h), C.byref(desc)), "hommx_plan_create_mesh")
         self._h = h

@@ -14,6 +14,7 @@
 #include "../../include/hommx_hip.h"
 #include "kernels.h"
 #include "mesh_front.h"
+#include "mesh_tree.h"
 
 namespace {
 
@@ -37,7 +38,7 @@ int fail(int code, const char* fmt, ...) {
                   hipGetErrorString(e__));                                                     \
   } while (0)
 
-enum Family { FAM_FUSED2D = 0, FAM_BLOCKED = 1, FAM_MESH = 2 };
+enum Family { FAM_FUSED2D = 0, FAM_BLOCKED = 1, FAM_MESH = 2, FAM_MESH_TREE = 3 };
 
 }  // namespace
 
@@ -80,6 +81,7 @@ struct hommx_plan {
   int64_t cap_cells = 0;
   hommx::BlockedWorkspace* ws = nullptr;
   hommx::MeshPlan* mesh = nullptr;  // FAM_MESH: symbolic phase + device tables of the unstructured micro mesh
+  hommx::MeshTreePlan* mtree = nullptr;  // FAM_MESH_TREE: the same mesh on the nested-dissection engine (meshes wider than the LDS front)
   double* d_expand = nullptr;  // two-phase media on the blocked family: expanded element stream
   int64_t cap_expand = 0;
   // plan-owned staging of the sampler entry points (two-phase / separable, host pointers): grown on demand, never per call
@@ -151,6 +153,7 @@ int hommx_plan_destroy(hommx_plan* p) {
   if (p->d_info) hipFree(p->d_info);
   if (p->ws) hommx::blocked_workspace_destroy(p->ws);
   if (p->mesh) hommx::mesh_destroy(p->mesh);
+  if (p->mtree) hommx::mesh_tree_destroy(p->mtree);
   if (p->d_expand) hipFree(p->d_expand);
   for (hommx_plan::Buf* b : {&p->st_mask, &p->st_values, &p->st_table, &p->st_w, &p->st_M, &p->st_out, &p->st_info, &p->dev_in, &p->dev_out})
     if (b->p) hipFree(b->p);
@@ -179,8 +182,8 @@ int hommx_plan_reserve(hommx_plan* p, int64_t n_cells) {
   if (n_cells < 0) return fail(HOMMX_EINVAL, "negative n_cells");
   if (p->family == FAM_FUSED2D || n_cells == 0) return HOMMX_OK;  // the fused 2D family keeps no scratch
   HIP_TRY(hipSetDevice(p->desc.device));
-  if (p->family == FAM_MESH) {
-    int rc = hommx::mesh_reserve(p->mesh, n_cells);
+  if (p->family == FAM_MESH || p->family == FAM_MESH_TREE) {
+    int rc = p->family == FAM_MESH ? hommx::mesh_reserve(p->mesh, n_cells) : hommx::mesh_tree_reserve(p->mtree, n_cells);
     return rc ? fail(rc, "mesh route: %s", hommx::mesh_last_error()) : HOMMX_OK;
   }
   int rc = hommx::blocked_reserve(p->ws, n_cells);
@@ -195,11 +198,13 @@ double hommx_plan_flops_per_solve(const hommx_plan* p) {
     return (6.0 * (n - 1) + 2.0) * n * n * n;
   }
   if (p->family == FAM_MESH) return hommx::mesh_flops_per_cell(p->mesh);
+  if (p->family == FAM_MESH_TREE) return hommx::mesh_tree_flops_per_cell(p->mtree);
   return hommx::blocked_flops_per_cell(p->ws);
 }
 const char* hommx_plan_kernel_name(const hommx_plan* p) {
   if (!p) return "";
   if (p->family == FAM_MESH) return "mesh_front";
+  if (p->family == FAM_MESH_TREE) return "mesh_multifrontal";
   return p->family == FAM_FUSED2D ? "fused2d" : hommx::blocked_route_name(p->ws);
 }
 
@@ -209,6 +214,7 @@ const char* hommx_plan_route_detail(hommx_plan* p) {
     return p->desc.n_micro > 16 ? "fused2d: k_poisson2d_fused<32>, one wavefront per macro cell, every matrix in the f64 MFMA accumulator layout"
                                 : "fused2d: k_poisson2d_fused<16>, one wavefront per macro cell, every matrix in the f64 MFMA accumulator layout";
   if (p->family == FAM_MESH) return hommx::mesh_route_detail(p->mesh);
+  if (p->family == FAM_MESH_TREE) return hommx::mesh_tree_route_detail(p->mtree);
   return hommx::blocked_route_detail(p->ws);
 }
 
@@ -219,6 +225,10 @@ namespace {
 int solve_stream(hommx_plan* p, int64_t n_cells, const double* d_coef, const double* d_M, double* d_A_eff, int32_t* d_info, hipStream_t st) {
   if (p->family == FAM_MESH) {
     int rc = hommx::mesh_solve(p->mesh, n_cells, d_coef, d_M, d_A_eff, d_info, st);
+    return rc ? fail(rc, "mesh route: %s", hommx::mesh_last_error()) : HOMMX_OK;
+  }
+  if (p->family == FAM_MESH_TREE) {
+    int rc = hommx::mesh_tree_solve(p->mtree, n_cells, d_coef, d_M, d_A_eff, d_info, st);
     return rc ? fail(rc, "mesh route: %s", hommx::mesh_last_error()) : HOMMX_OK;
   }
   int rc = hommx::blocked_solve(p->ws, n_cells, d_coef, d_M, d_A_eff, d_info, st);
@@ -233,20 +243,44 @@ int hommx_mesh_analyze(const hommx_mesh_desc* d, int32_t* front_width, double* f
   return rc ? fail(rc, "%s", hommx::mesh_last_error()) : HOMMX_OK;
 }
 
+int hommx_mesh_analyze_tree(const hommx_mesh_desc* d, int32_t* n_fronts, int32_t* n_groups, int32_t* max_front, double* flops_per_solve,
+                            int32_t* supernode_of_node, int32_t* parent) {
+  hommx::MeshTreeInfo info{};
+  int rc = hommx::mesh_tree_analyze(d, nullptr, &info, supernode_of_node, parent);
+  if (rc) return fail(rc, "%s", hommx::mesh_last_error());
+  if (n_fronts) *n_fronts = info.n_fronts;
+  if (n_groups) *n_groups = info.n_groups;
+  if (max_front) *max_front = info.max_front;
+  if (flops_per_solve) *flops_per_solve = info.flops;
+  return HOMMX_OK;
+}
+
 int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d) {
   if (!out || !d) return fail(HOMMX_EINVAL, "null argument");
   *out = nullptr;
+  // every argument check runs before the device is touched.  The frontal route takes what fits its LDS front; wider meshes, and any mesh
+  // with HOMMX_MESH_FLAG_TREE, take the tree route
   hommx::MeshPlan* m = nullptr;
-  int rc = hommx::mesh_analyze(d, &m, nullptr, nullptr);  // every argument check runs before the device is touched
-  if (rc) return fail(rc, "%s", hommx::mesh_last_error());
+  hommx::MeshTreePlan* mt = nullptr;
+  int rc = 0;
+  if (!(d->flags & HOMMX_MESH_FLAG_TREE)) {
+    int32_t width = 0;
+    rc = hommx::mesh_analyze(d, &m, &width, nullptr);
+    if (rc && !(rc == HOMMX_EINVAL && width > HOMMX_MESH_MAX_FRONT)) return fail(rc, "%s", hommx::mesh_last_error());
+  }
+  if (!m && (rc = hommx::mesh_tree_analyze(d, &mt, nullptr, nullptr, nullptr)) != 0) return fail(rc, "%s", hommx::mesh_last_error());
+  auto drop = [&]() {
+    hommx::mesh_destroy(m);
+    hommx::mesh_tree_destroy(mt);
+  };
   int ndev = hommx_device_count();
   if (ndev <= 0 || d->device < 0 || d->device >= ndev) {
-    hommx::mesh_destroy(m);
+    drop();
     return ndev <= 0 ? fail(HOMMX_ENODEV, "no HIP device visible") : fail(HOMMX_EINVAL, "device %d out of range [0,%d)", d->device, ndev);
   }
   hommx_plan* p = new (std::nothrow) hommx_plan();
   if (!p) {
-    hommx::mesh_destroy(m);
+    drop();
     return fail(HOMMX_ENOMEM, "host allocation failed");
   }
   p->desc.dim = d->dim;
@@ -254,8 +288,9 @@ int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d) {
   p->desc.kind = d->kind;
   p->desc.device = d->device;
   p->desc.flags = d->flags;
-  p->family = FAM_MESH;
+  p->family = m ? FAM_MESH : FAM_MESH_TREE;
   p->mesh = m;
+  p->mtree = mt;
   p->n_el = d->n_el;
   const int dim = d->dim, te = dim * (dim + 1) / 2;
   switch (d->kind) {
@@ -265,7 +300,7 @@ int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d) {
     default: p->n_comp = te * (te + 1) / 2; p->t = te; break;
   }
   p->h2d_overlap = getenv("HOMMX_NO_H2D_OVERLAP") == nullptr;
-  if (hipSetDevice(d->device) != hipSuccess || (rc = hommx::mesh_upload(m)) != 0) {
+  if (hipSetDevice(d->device) != hipSuccess || (rc = m ? hommx::mesh_upload(m) : hommx::mesh_tree_upload(mt)) != 0) {
     const std::string msg = rc ? hommx::mesh_last_error() : "hipSetDevice failed";
     hommx_plan_destroy(p);
     return fail(rc ? rc : HOMMX_EHIP, "mesh route: %s", msg.c_str());
@@ -518,7 +553,7 @@ int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* c
   if (n_cells == 0) return HOMMX_OK;
   if (!coef || !A_eff || !correctors) return fail(HOMMX_EINVAL, "null coef / A_eff / correctors");
   HIP_TRY(hipSetDevice(p->desc.device));
-  if (p->family != FAM_MESH && !p->ws) {
+  if (p->family != FAM_MESH && p->family != FAM_MESH_TREE && !p->ws) {
     int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
     if (rc != 0) return fail(rc, "blocked path: %s", hommx::blocked_last_error());
   }
@@ -527,6 +562,8 @@ int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* c
   long long nn = 1;
   if (p->family == FAM_MESH)
     nn = hommx::mesh_num_nodes(p->mesh);
+  else if (p->family == FAM_MESH_TREE)
+    nn = hommx::mesh_tree_num_nodes(p->mtree);
   else
     for (int k = 0; k < d; ++k) nn *= p->desc.n_micro;
   double *d_coef = nullptr, *d_M = nullptr, *d_out = nullptr, *d_corr = nullptr;
@@ -557,11 +594,13 @@ int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* c
     HIP_TRY_C(hipMalloc(&d_M, sizeof(double) * n_cells * d * d));
     HIP_TRY_C(hipMemcpy(d_M, M, sizeof(double) * n_cells * d * d, hipMemcpyHostToDevice));
   }
-  int rc = p->family == FAM_MESH ? hommx::mesh_solve(p->mesh, n_cells, d_coef, d_M, d_out, d_info, nullptr, d_corr)
-                                 : hommx::blocked_solve(p->ws, n_cells, d_coef, d_M, d_out, d_info, nullptr, d_corr);
+  const bool mesh = p->family == FAM_MESH || p->family == FAM_MESH_TREE;
+  int rc = p->family == FAM_MESH        ? hommx::mesh_solve(p->mesh, n_cells, d_coef, d_M, d_out, d_info, nullptr, d_corr)
+           : p->family == FAM_MESH_TREE ? hommx::mesh_tree_solve(p->mtree, n_cells, d_coef, d_M, d_out, d_info, nullptr, d_corr)
+                                        : hommx::blocked_solve(p->ws, n_cells, d_coef, d_M, d_out, d_info, nullptr, d_corr);
   if (rc != 0) {
     cleanup();
-    return fail(rc, "%s", p->family == FAM_MESH ? hommx::mesh_last_error() : hommx::blocked_last_error());
+    return fail(rc, "%s", mesh ? hommx::mesh_last_error() : hommx::blocked_last_error());
   }
   HIP_TRY_C(hipDeviceSynchronize());
   HIP_TRY_C(hipMemcpy(A_eff, d_out, sizeof(double) * n_cells * t * t, hipMemcpyDeviceToHost));

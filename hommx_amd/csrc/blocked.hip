@@ -921,6 +921,21 @@ static void fill_tables(Geo& G) {
   }
 }
 
+// development knobs of a workspace (include/hommx_hip.h), read once when it is created
+static void ws_read_knobs(BlockedWorkspace* ws) {
+  if (const char* e = getenv("HOMMX_BLOCKED_MEM_GB")) ws->budget_gb_env = atof(e);
+  if (const char* e = getenv("HOMMX_GEMM128_MIN")) ws->gemm128_min = atoi(e);
+  ws->sparse_v1 = getenv("HOMMX_SPARSE_V1") != nullptr;
+  ws->leaf32 = getenv("HOMMX_LEAF32") != nullptr;
+  ws->split64 = getenv("HOMMX_NO_SPLIT64") == nullptr;
+  ws->small_fused = getenv("HOMMX_NO_SMALL_FUSED") == nullptr;
+  if (const char* e = getenv("HOMMX_SMALL_WAVES")) ws->small_waves = atoi(e);
+  if (const char* e = getenv("HOMMX_MF_G128_MIN_K")) ws->mf_gather128_min_k = atoi(e);
+  ws->mf_no_border_split = getenv("HOMMX_MF_NO_BORDER_SPLIT") != nullptr;
+  if (const char* e = getenv("HOMMX_MF_CORR")) ws->mf_corr = atoi(e) != 0;
+  if (const char* e = getenv("HOMMX_TILE_SB")) ws->tile_sb = atoi(e);
+}
+
 int blocked_workspace_create(BlockedWorkspace** out, int dim, int n, int kind) {
   *out = nullptr;
   BlockedWorkspace* ws = new BlockedWorkspace();
@@ -943,13 +958,7 @@ int blocked_workspace_create(BlockedWorkspace** out, int dim, int n, int kind) {
   G.ncode = dim == 2 ? 9 : 27;
   G.n_el = G.nsub * G.nn;
   fill_tables(G);
-  if (const char* e = getenv("HOMMX_BLOCKED_MEM_GB")) ws->budget_gb_env = atof(e);
-  if (const char* e = getenv("HOMMX_GEMM128_MIN")) ws->gemm128_min = atoi(e);
-  ws->sparse_v1 = getenv("HOMMX_SPARSE_V1") != nullptr;
-  ws->leaf32 = getenv("HOMMX_LEAF32") != nullptr;
-  ws->split64 = getenv("HOMMX_NO_SPLIT64") == nullptr;
-  ws->small_fused = getenv("HOMMX_NO_SMALL_FUSED") == nullptr;
-  if (const char* e = getenv("HOMMX_SMALL_WAVES")) ws->small_waves = atoi(e);
+  ws_read_knobs(ws);
   // route: nested dissection (multifrontal.hip) wherever it beats the plane elimination (profiles/r03_kinds_routes.txt) -- every plane
   // block b > 64, i.e. everything the one-launch kernels do not take: 2D scalar n = 80: +51 %, 2D elasticity n = 36: +92 %, 3D elasticity
   // n = 5: +68 %, n = 16: +76 %, scalar 3D n = 9: +18 % (it lost 10 % there before the build kernel batched its loads and the route ran on
@@ -963,10 +972,6 @@ int blocked_workspace_create(BlockedWorkspace** out, int dim, int n, int kind) {
     ws->mf_min_b = atoi(e);
     mf_env = true;
   }
-  if (const char* e = getenv("HOMMX_MF_G128_MIN_K")) ws->mf_gather128_min_k = atoi(e);
-  ws->mf_no_border_split = getenv("HOMMX_MF_NO_BORDER_SPLIT") != nullptr;
-  if (const char* e = getenv("HOMMX_MF_CORR")) ws->mf_corr = atoi(e) != 0;
-  if (const char* e = getenv("HOMMX_TILE_SB")) ws->tile_sb = atoi(e);
   // (a threshold from the environment below 65 takes effect only together with HOMMX_NO_SMALL_FUSED: A/B runs)
   if (ws->mf_min_b > 0 && G.b >= ws->mf_min_b && (G.b > 64 || !ws->small_fused || (!mf_env && G.b > 48))) {
     if (int rc = mf_plan_create(&ws->mf, G)) {
@@ -977,6 +982,17 @@ int blocked_workspace_create(BlockedWorkspace** out, int dim, int n, int kind) {
     // per CU) are never slower than the 128 x 128 ones any more -- C4 +2 %, 3D elasticity 20^3 +2 %, scalar 24^3 -1.5 %
     if (!getenv("HOMMX_GEMM128_MIN")) ws->gemm128_min = 1 << 30;
   }
+  *out = ws;
+  return 0;
+}
+
+int blocked_workspace_create_mesh(BlockedWorkspace** out, const Geo& G, MfPlan* mf) {
+  *out = nullptr;
+  BlockedWorkspace* ws = new BlockedWorkspace();
+  ws->G = G;
+  ws_read_knobs(ws);
+  ws->mf = mf;  // owned by the workspace from here on
+  if (!getenv("HOMMX_GEMM128_MIN")) ws->gemm128_min = 1 << 30;  // as for the structured multifrontal plans (blocked_workspace_create)
   *out = ws;
   return 0;
 }

@@ -7,6 +7,7 @@
 
 #include <map>
 #include <string>
+#include <vector>
 
 #include "geo.h"
 
@@ -95,8 +96,35 @@ void invert(const Ctx& c, double* S, int off, int size, double* tmp);
 
 extern thread_local std::string g_berr;
 
+// Symbolic input of a nested-dissection plan, from either source (the box dissection of the n^d torus, or the coordinate bisection of an
+// unstructured mesh: mesh_tree.hip): the supernode tree and the coupling graph.  Nothing in it is geometric.
+struct MfTree {
+  std::vector<std::vector<int>> sn_nodes;     // nodes of every supernode; children come before their parent, the root is the last
+  std::vector<std::vector<int>> sn_children;  // at most two per supernode (MfChild has two slots)
+  std::vector<int> nb_ptr, nb_node, nb_code;  // CSR over nodes v: every node w coupled with v (v included) and the code of (row w, column v)
+};
+// supernode tree of the n^d torus (TreeBuilder: two planes per periodic direction, one per open one) with its stencil couplings
+void mf_tree_structured(const Geo& G, MfTree* T);
+// leaf size and ring-split depth of both tree builders (HOMMX_MF_LEAF, HOMMX_MF_SPLIT_DEPTH)
+int mf_leaf_max(int dim, int bs);
+int mf_split_depth();
+
 // multifrontal.hip
 int mf_plan_create(MfPlan** out, const Geo& G, bool keep = false);
+// host half of mf_plan_create on any tree: boundaries, heights, groups, arena, flop model and the index tables (no GPU); the gauge is the node of
+// highest elimination rank in the root.  G supplies nn, bs, ncode.  mf_plan_upload moves the tables to the current device.
+int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep);
+int mf_plan_upload(MfPlan* P);
+// what the host analysis found: fronts, groups, the largest front (s + r, unknowns), the largest (s, r) pair, arena doubles per cell, groups on
+// k_mf_front
+struct MfStats {
+  int nfronts, ngroups, max_front, max_s, max_r, front_groups;
+  long long arena_per_cell;
+  double flops;
+};
+MfStats mf_stats(const MfPlan* p);
+struct MeshAsm;
+void mf_set_mesh(MfPlan* p, const MeshAsm* a);  // K1 of the plan: the mesh assembly on these tables (mesh_tree.hip)
 void mf_plan_destroy(MfPlan* p);
 double mf_flops_per_cell(const MfPlan* p);
 std::string mf_describe(const BlockedWorkspace* ws, const MfPlan* p);  // one line: tree, stages, streams, tile sizes of the dense kernels
@@ -104,6 +132,9 @@ int mf_reserve(BlockedWorkspace* ws, MfPlan* P, long long ncells, bool ahead);
 // effective tensors, and with the corrector plan (keep = true) and d_corr != nullptr the correctors [cell][t][n^d bs] as well
 int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
              hipStream_t st, double* d_corr = nullptr);
+// mesh_tree.hip: K1 of a mesh plan -- Kst, Brhs and C0 of `nc` cells in the layout launch_assembly writes, from the element stream
+void launch_mesh_assembly(const MeshAsm& a, const double* coef, const double* Mm, long long nc, hipStream_t st, double* Kst, double* Brhs,
+                          double* C0);
 // remove the mean of every component of nc x t corrector fields (blocked.hip)
 void launch_center_corr(BlockedWorkspace* ws, double* corr, long long nc, hipStream_t st);
 // K1 of the blocked family (stencil rows, loads, C0 of `nc` cells into the given buffers), shared by both eliminations: each route owns

@@ -55,6 +55,11 @@ namespace hommx {
 // blocked.hip: generic block-cyclic path (any dim / kind / n); host-orchestrated batched kernels.
 struct BlockedWorkspace;
 int blocked_workspace_create(BlockedWorkspace** out, int dim, int n, int kind);
+// workspace of a mesh plan of the tree route (mesh_tree.hip): its Geo (nn = n_nodes, ncode = most coupling codes of a node, n unused) and its
+// multifrontal plan, which the workspace then owns; the same development knobs as blocked_workspace_create
+struct Geo;
+struct MfPlan;
+int blocked_workspace_create_mesh(BlockedWorkspace** out, const Geo& G, MfPlan* mf);
 void blocked_workspace_destroy(BlockedWorkspace* ws);
 int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, const double* d_M,
                   double* d_out, int32_t* d_info, hipStream_t stream, double* d_corr = nullptr);

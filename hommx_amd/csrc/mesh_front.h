@@ -7,11 +7,22 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+#include <vector>
+
 #include "../../include/hommx_hip.h"
 
 namespace hommx {
 
 struct MeshPlan;
+
+// what both mesh routes take from a validated descriptor
+struct MeshGeom {
+  std::vector<double> grads, vol;  // [n_el][dim+1][dim] P1 gradients, [n_el] volumes (from the unfolded coordinates)
+  std::vector<int> ptr, adj;       // node graph: CSR, neighbours sorted ascending, the node itself not included
+};
+// Every check of hommx_mesh_analyze but the front width, in the same order and with the same messages (mesh_last_error()).
+int mesh_check(const hommx_mesh_desc* d, MeshGeom* g);
 
 // Validates the descriptor and runs the symbolic phase.  out == nullptr: analysis only (hommx_mesh_analyze).  Returns 0 or HOMMX_EINVAL /
 // HOMMX_ENOMEM with the message in mesh_last_error().
@@ -20,6 +31,7 @@ int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width,
 int mesh_upload(MeshPlan* m);
 void mesh_destroy(MeshPlan* m);
 const char* mesh_last_error();
+int mesh_error(int code, const std::string& msg);  // sets the message mesh_last_error() returns
 
 int32_t mesh_front_width(const MeshPlan* m);
 double mesh_flops_per_cell(const MeshPlan* m);

@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "mesh_elem.h"
 #include "mesh_front.h"
 
 namespace hommx {
@@ -52,6 +53,10 @@ constexpr int kRed = 21;  // t (t + 1) / 2 for t <= 6: the C0 partial sums
 }  // namespace
 
 const char* mesh_last_error() { return g_merr.c_str(); }
+int mesh_error(int code, const std::string& msg) {
+  g_merr = msg;
+  return code;
+}
 
 // device view of the symbolic phase (all arrays on the plan's device)
 struct MeshDev {
@@ -92,73 +97,6 @@ struct MeshPlan {
 // ------------------------------------------------------------------------------------------------------------------------------
 
 __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // packed lower triangle, i >= j
-
-// Material matrix C (t x t) of an element in the basis of the canonical loads (Poisson: A; elasticity: E^m : A : E^n).
-template <int DIM, int KIND>
-__device__ __forceinline__ void material(const double* __restrict__ c, double (&C)[KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM][KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM]) {
-  constexpr int T = KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM;
-  if constexpr (KIND == HOMMX_KIND_POISSON_SCALAR) {
-    const double a = c[0];
-#pragma unroll
-    for (int m = 0; m < T; ++m)
-#pragma unroll
-      for (int n = 0; n < T; ++n) C[m][n] = m == n ? a : 0.0;
-  } else if constexpr (KIND == HOMMX_KIND_POISSON_MATRIX) {
-    // (00, 11, [22,] 01 [, 02, 12])
-#pragma unroll
-    for (int m = 0; m < DIM; ++m) C[m][m] = c[m];
-    C[0][1] = C[1][0] = c[DIM];
-    if constexpr (DIM == 3) {
-      C[0][2] = C[2][0] = c[4];
-      C[1][2] = C[2][1] = c[5];
-    }
-  } else if constexpr (KIND == HOMMX_KIND_ELASTICITY_ISO) {
-    const double lam = c[0], mu = c[1];
-#pragma unroll
-    for (int m = 0; m < T; ++m)
-#pragma unroll
-      for (int n = 0; n < T; ++n) C[m][n] = (m < DIM && n < DIM ? lam : 0.0) + (m == n ? (m < DIM ? 2.0 * mu : mu) : 0.0);
-  } else {
-    // upper triangle of the t x t matrix, row-major
-    int q = 0;
-#pragma unroll
-    for (int m = 0; m < T; ++m)
-#pragma unroll
-      for (int n = m; n < T; ++n, ++q) C[m][n] = C[n][m] = c[q];
-  }
-}
-
-// strain of local dof r = a * bs + alpha in the basis of the canonical loads: Poisson M g_a; elasticity sym(e_alpha (x) M g_a) with
-// the off-diagonal components doubled (E^m, m = (k, l), k != l, has 1/2 at kl and lk)
-template <int DIM, int KIND>
-__device__ __forceinline__ void strain(const double* __restrict__ g, const double* __restrict__ M, int alpha,
-                                       double (&s)[KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM]) {
-  double gt[DIM];
-#pragma unroll
-  for (int i = 0; i < DIM; ++i) {
-    if (M) {
-      double v = 0.0;
-#pragma unroll
-      for (int k = 0; k < DIM; ++k) v += M[i * DIM + k] * g[k];
-      gt[i] = v;
-    } else {
-      gt[i] = g[i];
-    }
-  }
-  if constexpr (KIND < 2) {
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) s[i] = gt[i];
-  } else {
-#pragma unroll
-    for (int m = 0; m < DIM; ++m) s[m] = alpha == m ? gt[m] : 0.0;
-    constexpr int PK[3] = {0, 0, 1}, PL[3] = {1, 2, 2};  // Voigt pairs 01, 02, 12
-#pragma unroll
-    for (int o = 0; o < DIM * (DIM - 1) / 2; ++o) {
-      const int k = PK[o], l = PL[o];
-      s[DIM + o] = (alpha == k ? gt[l] : 0.0) + (alpha == l ? gt[k] : 0.0);
-    }
-  }
-}
 
 template <int DIM, int KIND>
 __global__ void __launch_bounds__(kThreads) k_mesh_front(MeshDev G, const double* __restrict__ coef, const double* __restrict__ Mall,
@@ -482,30 +420,15 @@ std::vector<int> sweep_order(const hommx_mesh_desc* d, int axis) {
 
 }  // namespace
 
-int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width, double* flops_per_solve) {
-  if (out) *out = nullptr;
+int mesh_check(const hommx_mesh_desc* d, MeshGeom* g) {
   if (!d) return mfail(HOMMX_EINVAL, "null descriptor");
   if (d->dim != 2 && d->dim != 3) return mfail(HOMMX_EINVAL, "dim must be 2 or 3, got %d", d->dim);
   if (d->kind < 0 || d->kind > 3) return mfail(HOMMX_EINVAL, "unknown kind %d", d->kind);
   if (d->n_nodes < 2 || d->n_nodes > 0x3fffffffll) return mfail(HOMMX_EINVAL, "n_nodes must be in [2, 2^30), got %lld", (long long)d->n_nodes);
   if (d->n_el < 1 || d->n_el > 0x3fffffffll) return mfail(HOMMX_EINVAL, "n_el must be in [1, 2^30), got %lld", (long long)d->n_el);
   if (!d->el_nodes || !d->el_x) return mfail(HOMMX_EINVAL, "null el_nodes / el_x");
-  MeshPlan* m = new (std::nothrow) MeshPlan();
-  if (!m) return mfail(HOMMX_ENOMEM, "host allocation failed");
-  struct Guard {
-    MeshPlan*& p;
-    ~Guard() { delete p; }
-  } guard{m};
   const int dim = d->dim, nv = dim + 1;
   const int n = (int)d->n_nodes, ne = (int)d->n_el;
-  m->dim = dim;
-  m->kind = d->kind;
-  m->bs = d->kind >= HOMMX_KIND_ELASTICITY_ISO ? dim : 1;
-  m->t = d->kind >= HOMMX_KIND_ELASTICITY_ISO ? dim * (dim + 1) / 2 : dim;
-  m->n_comp = d->kind == 0 ? 1 : d->kind == 1 ? dim * (dim + 1) / 2 : d->kind == 2 ? 2 : m->t * (m->t + 1) / 2;
-  m->n_nodes = n;
-  m->n_el = ne;
-  const int bs = m->bs, t = m->t;
 
   // topology
   std::vector<int> used(n, 0);
@@ -522,8 +445,8 @@ int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width,
     if (!used[v]) return mfail(HOMMX_EINVAL, "node %d belongs to no element", v);
 
   // geometry: P1 gradients and volumes from the unfolded coordinates
-  m->grads.assign((size_t)ne * nv * dim, 0.0);
-  m->vol.assign(ne, 0.0);
+  g->grads.assign((size_t)ne * nv * dim, 0.0);
+  g->vol.assign(ne, 0.0);
   double vsum = 0.0;
   for (int e = 0; e < ne; ++e) {
     const double* X = d->el_x + (size_t)e * nv * dim;
@@ -548,21 +471,24 @@ int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width,
     }
     const double v = std::fabs(det) / (dim == 2 ? 2.0 : 6.0);
     if (!(v > 1e-10 / ne) || !std::isfinite(v)) return mfail(HOMMX_EINVAL, "element %d is degenerate (volume %.3g)", e, v);
-    m->vol[e] = v;
+    g->vol[e] = v;
     vsum += v;
     // grad phi_a = column a - 1 of J^-1 (a >= 1), grad phi_0 = -sum of the others
-    double* g = m->grads.data() + (size_t)e * nv * dim;
+    double* gr = g->grads.data() + (size_t)e * nv * dim;
     for (int a = 1; a < nv; ++a)
       for (int c = 0; c < dim; ++c) {
-        g[a * dim + c] = Ji[c][a - 1];
-        g[c] -= Ji[c][a - 1];
+        gr[a * dim + c] = Ji[c][a - 1];
+        gr[c] -= Ji[c][a - 1];
       }
   }
   if (!(std::fabs(vsum - 1.0) <= 1e-10))
     return mfail(HOMMX_EINVAL, "element volumes sum to %.15g, expected 1 (the unit cell)", vsum);
 
   // node graph (for the order and the connectivity check)
-  std::vector<int> ptr(n + 1, 0), adj;
+  std::vector<int>& ptr = g->ptr;
+  std::vector<int>& adj = g->adj;
+  ptr.assign(n + 1, 0);
+  adj.clear();
   {
     std::vector<std::vector<int>> nb(n);
     for (int e = 0; e < ne; ++e)
@@ -589,13 +515,42 @@ int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width,
     if ((int)q.size() != n) return mfail(HOMMX_EINVAL, "the mesh is not connected (%d of %d nodes reachable from node 0)", (int)q.size(), n);
   }
   if (d->order) {
-    m->order.assign(d->order, d->order + n);
     std::vector<char> seen(n, 0);
     for (int k = 0; k < n; ++k) {
-      const int v = m->order[k];
+      const int v = d->order[k];
       if (v < 0 || v >= n || seen[v]) return mfail(HOMMX_EINVAL, "order is not a permutation of [0, %d): entry %d is %d", n, k, v);
       seen[v] = 1;
     }
+  }
+  return HOMMX_OK;
+}
+
+int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width, double* flops_per_solve) {
+  if (out) *out = nullptr;
+  MeshGeom geo;
+  if (int rc = mesh_check(d, &geo)) return rc;
+  MeshPlan* m = new (std::nothrow) MeshPlan();
+  if (!m) return mfail(HOMMX_ENOMEM, "host allocation failed");
+  struct Guard {
+    MeshPlan*& p;
+    ~Guard() { delete p; }
+  } guard{m};
+  const int dim = d->dim, nv = dim + 1;
+  const int n = (int)d->n_nodes, ne = (int)d->n_el;
+  m->dim = dim;
+  m->kind = d->kind;
+  m->bs = d->kind >= HOMMX_KIND_ELASTICITY_ISO ? dim : 1;
+  m->t = d->kind >= HOMMX_KIND_ELASTICITY_ISO ? dim * (dim + 1) / 2 : dim;
+  m->n_comp = d->kind == 0 ? 1 : d->kind == 1 ? dim * (dim + 1) / 2 : d->kind == 2 ? 2 : m->t * (m->t + 1) / 2;
+  m->n_nodes = n;
+  m->n_el = ne;
+  const int bs = m->bs, t = m->t;
+  m->grads.swap(geo.grads);
+  m->vol.swap(geo.vol);
+  const std::vector<int>& ptr = geo.ptr;
+  const std::vector<int>& adj = geo.adj;
+  if (d->order) {
+    m->order.assign(d->order, d->order + n);
   } else {
     // the narrowest of reverse Cuthill-McKee and the coordinate sweeps along every axis
     m->order = rcm_order(n, ptr, adj);

@@ -231,7 +231,7 @@ namespace {
 int check_plans(const hommx_comm* c, hommx_plan* const* plans) {
   for (int i = 0; i < c->ndev; ++i) {
     if (!plans[i]) return fail(HOMMX_EINVAL, "null plan for device slot %d", i);
-    if (hommx_plan_front_width(plans[i]) > 0)
+    if (hommx_plan_front_width(plans[i]) > 0 || hommx_plan_n_micro(plans[i]) == 0)
       return fail(HOMMX_EINVAL, "plan %d is a mesh plan: single-process multi-GPU solves take the structured routes only", i);
     if (hommx_plan_device(plans[i]) != c->devs[i])
       return fail(HOMMX_EINVAL, "plan %d lives on device %d, the communicator's slot %d is device %d", i, hommx_plan_device(plans[i]), i, c->devs[i]);

@@ -24,7 +24,10 @@
 //     are written by k_mf_build: stencil entries + the children's entries, every entry exactly once -- no memset, no atomics.
 //   * Nodes are numbered in elimination order everywhere, so child -> parent maps are monotone and only lower triangles are ever needed.
 //   * Every chunk of cells runs as two to four pieces side by side on as many streams (the caller's and plan-owned ones, mf_solve).
-// Gauge: the last node is pinned in the root front (cell_problem.py:349-361).
+// Gauge: the node of highest elimination rank is pinned in the root front -- node nn - 1 on the torus (cell_problem.py:349-361).
+// The numeric phase never looks at geometry: mf_plan_build takes the supernode tree and the coupling graph (MfTree) from either source, the
+// box dissection of the torus (mf_tree_structured) or the coordinate bisection of an unstructured mesh (mesh_tree.hip, whose plans carry
+// their own K1, launch_mesh_assembly).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -72,6 +75,11 @@ struct MfGroup {
   int32_t* d_upos = nullptr;        // [nf][2][16 T]  unknown of the front -> unknown of the child's update matrix, -1: none
   uint16_t* d_tilemap = nullptr;    // [ntiles]       a << 8 | b
   bool has_children = false;
+  // the same tables on the host (mf_plan_build), until mf_plan_upload
+  std::vector<int32_t> h_nodes, h_cpos, h_dpos, h_upos;
+  std::vector<int8_t> h_code;
+  std::vector<MfChild> h_child;
+  std::vector<uint16_t> h_tilemap;
 };
 
 struct MfPlan {
@@ -93,6 +101,8 @@ struct MfPlan {
   int streams = 4;
   hipStream_t side[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
+  // plans of an unstructured mesh (mesh_tree.hip): K1 is the mesh assembly on these tables instead of the structured stencil kernel
+  const MeshAsm* mesh = nullptr;
 };
 
 constexpr int MF_BORDER = 8;  // load rows per front (t <= 6)
@@ -212,6 +222,7 @@ int upload(T** dst, const std::vector<T>& src) {
 }  // namespace
 
 double mf_flops_per_cell(const MfPlan* p) { return p ? p->flops_per_cell : 0.0; }
+void mf_set_mesh(MfPlan* p, const MeshAsm* a) { p->mesh = a; }
 
 std::string mf_describe(const BlockedWorkspace* ws, const MfPlan* p) {
   if (!p) return "";
@@ -262,25 +273,27 @@ void mf_plan_destroy(MfPlan* p) {
   delete p;
 }
 
-int mf_plan_create(MfPlan** out, const Geo& G, bool keep) {
-  *out = nullptr;
-  MfPlan* P = new MfPlan();
-  P->G = G;
-  P->keep = keep;
-  const int dim = G.dim, n = G.n, bs = G.bs, nn = G.nn;
-  TreeBuilder tb;
-  tb.dim = dim;
-  tb.n = n;
+int mf_leaf_max(int dim, int bs) {
   // leaves of about 64 - 81 unknowns (a leaf front pads its eliminated block to a multiple of 32): 27 nodes x 3 unknowns for 3D elasticity
   // (12 and 64 nodes measure the same within 1 %), 64 nodes for scalar 3D problems (16^3: +10 % over 9-node leaves), 32 for two unknowns
   // per node (16: the same); scalar 2D: 25 (against 64: 80^2 +10 %, 96^2 +6 %, 128^2 +3 %; 16: -30 %)
-  tb.leaf_max = bs >= 3 ? 27 : bs == 2 ? 32 : dim == 2 ? 25 : 64;
-  if (const char* e = getenv("HOMMX_MF_LEAF")) tb.leaf_max = std::max(1, atoi(e));
-  if (const char* e = getenv("HOMMX_MF_SPLIT_DEPTH")) tb.split_depth = atoi(e);
-  if (const char* e = getenv("HOMMX_MF_STAGE")) P->stage = atoi(e);
-  if (const char* e = getenv("HOMMX_MF_STREAMS")) P->streams = atoi(e);
-  if (const char* e = getenv("HOMMX_MF_FRONT")) P->front_max_t = std::max(0, std::min(MFF_MAX_T, atoi(e)));
-  if (keep) P->front_max_t = 0;  // the back substitution reads N_i and X_i of every front: the corrector plan keeps them in HBM
+  int leaf_max = bs >= 3 ? 27 : bs == 2 ? 32 : dim == 2 ? 25 : 64;
+  if (const char* e = getenv("HOMMX_MF_LEAF")) leaf_max = std::max(1, atoi(e));
+  return leaf_max;
+}
+
+int mf_split_depth() {
+  const char* e = getenv("HOMMX_MF_SPLIT_DEPTH");
+  return e ? atoi(e) : 0;
+}
+
+void mf_tree_structured(const Geo& G, MfTree* T) {
+  const int dim = G.dim, n = G.n, nn = G.nn;
+  TreeBuilder tb;
+  tb.dim = dim;
+  tb.n = n;
+  tb.leaf_max = mf_leaf_max(dim, G.bs);
+  tb.split_depth = mf_split_depth();
   {
     std::vector<int> all(nn);
     for (int i = 0; i < nn; ++i) all[i] = i;
@@ -288,22 +301,14 @@ int mf_plan_create(MfPlan** out, const Geo& G, bool keep) {
     const bool per[3] = {true, true, dim == 3};
     tb.rec(all, lo, hi, per);
   }
-  std::vector<SN>& sn = tb.sn;
-  const int nsn = (int)sn.size();
-  // elimination rank of every node: supernodes in list order (children before parents), ascending node id inside
-  std::vector<int> rank(nn, -1), owner(nn, -1);
-  {
-    int r = 0;
-    for (int k = 0; k < nsn; ++k) {
-      std::sort(sn[k].nodes.begin(), sn[k].nodes.end());
-      for (int v : sn[k].nodes) {
-        rank[v] = r++;
-        owner[v] = k;
-      }
-    }
+  T->sn_nodes.clear();
+  T->sn_children.clear();
+  for (SN& s : tb.sn) {
+    T->sn_nodes.push_back(std::move(s.nodes));
+    T->sn_children.push_back(std::move(s.children));
   }
   // stencil offsets: code = sum (d_k + 1) 3^k; the periodic P1 stencil couples along the cube's main-diagonal tetrahedra only
-  // (offsets whose components all have one sign), but the table keeps every code the assembly kernel writes (zeros included)
+  // (offsets whose components all have one sign), but Kst keeps every code the assembly kernel writes (zeros included)
   const int ncode = G.ncode;
   auto neighbour = [&](int v, int code) {
     int out = 0, mul = 1, vv = v, cc = code;
@@ -327,15 +332,83 @@ int mf_plan_create(MfPlan** out, const Geo& G, bool keep) {
     }
     return !(pos && neg);
   };
+  // node w = v + off(c) couples with v; the code of (row w, column v) is the opposite offset
+  T->nb_ptr.assign(nn + 1, 0);
+  T->nb_node.clear();
+  T->nb_code.clear();
+  for (int v = 0; v < nn; ++v) {
+    for (int c = 0; c < ncode; ++c)
+      if (coupled(c)) {
+        T->nb_node.push_back(neighbour(v, c));
+        T->nb_code.push_back(ncode - 1 - c);
+      }
+    T->nb_ptr[v + 1] = (int)T->nb_node.size();
+  }
+}
+
+int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep) {
+  *out = nullptr;
+  MfPlan* P = new MfPlan();
+  P->G = G;
+  P->keep = keep;
+  const int bs = G.bs, nn = G.nn;
+  if (const char* e = getenv("HOMMX_MF_STAGE")) P->stage = atoi(e);
+  if (const char* e = getenv("HOMMX_MF_STREAMS")) P->streams = atoi(e);
+  if (const char* e = getenv("HOMMX_MF_FRONT")) P->front_max_t = std::max(0, std::min(MFF_MAX_T, atoi(e)));
+  if (keep) P->front_max_t = 0;  // the back substitution reads N_i and X_i of every front: the corrector plan keeps them in HBM
+  const int nsn = (int)T.sn_nodes.size();
+  if (nsn == 0 || T.sn_nodes.back().empty()) {
+    g_berr = "multifrontal plan: empty tree or empty root front";
+    delete P;
+    return HOMMX_EINVAL;
+  }
+  std::vector<SN> sn(nsn);
+  for (int k = 0; k < nsn; ++k) {
+    sn[k].nodes = T.sn_nodes[k];
+    sn[k].children = T.sn_children[k];
+    if (sn[k].children.size() > 2) {
+      g_berr = "multifrontal plan: more than two children";
+      delete P;
+      return HOMMX_EINVAL;
+    }
+    for (int c : sn[k].children)
+      if (c < 0 || c >= k) {
+        g_berr = "multifrontal plan: a child does not come before its parent";
+        delete P;
+        return HOMMX_EINVAL;
+      }
+  }
+  // elimination rank of every node: supernodes in list order (children before parents), ascending node id inside
+  std::vector<int> rank(nn, -1), owner(nn, -1);
+  {
+    int r = 0;
+    for (int k = 0; k < nsn; ++k) {
+      std::sort(sn[k].nodes.begin(), sn[k].nodes.end());
+      for (int v : sn[k].nodes) {
+        if (v < 0 || v >= nn || owner[v] >= 0) {
+          g_berr = "multifrontal plan: the supernodes do not partition the nodes";
+          delete P;
+          return HOMMX_EINVAL;
+        }
+        rank[v] = r++;
+        owner[v] = k;
+      }
+    }
+    if (r != nn) {
+      g_berr = "multifrontal plan: the supernodes do not partition the nodes";
+      delete P;
+      return HOMMX_EINVAL;
+    }
+  }
+  // gauge: the node of highest elimination rank, in the root (structured trees: node nn - 1)
+  const int gauge = sn[nsn - 1].nodes.back();
   // boundaries (symbolic elimination on the supernode tree) and heights
   {
     std::vector<char> mark(nn, 0);
     for (int k = 0; k < nsn; ++k) {
       SN& s = sn[k];
       std::vector<int> cand;
-      for (int v : s.nodes)
-        for (int code = 0; code < ncode; ++code)
-          if (coupled(code)) cand.push_back(neighbour(v, code));
+      for (int v : s.nodes) cand.insert(cand.end(), T.nb_node.begin() + T.nb_ptr[v], T.nb_node.begin() + T.nb_ptr[v + 1]);
       for (int c : s.children) {
         cand.insert(cand.end(), sn[c].bnd.begin(), sn[c].bnd.end());
         s.height = std::max(s.height, sn[c].height + 1);
@@ -348,11 +421,6 @@ int mf_plan_create(MfPlan** out, const Geo& G, bool keep) {
       for (int v : s.bnd) mark[v] = 0;
       std::sort(s.bnd.begin(), s.bnd.end(), [&](int a, int b) { return rank[a] < rank[b]; });
     }
-  }
-  if (owner[nn - 1] != nsn - 1) {
-    g_berr = "multifrontal plan: the gauge node is not in the root front";
-    delete P;
-    return HOMMX_EINVAL;
   }
   // groups: fronts of equal (height, ns, nr)
   std::map<std::tuple<int, int, int>, int> gid;
@@ -453,30 +521,36 @@ int mf_plan_create(MfPlan** out, const Geo& G, bool keep) {
     }
     P->arena_per_cell = peak;
   }
-  // device tables
+  // index tables (host; mf_plan_upload moves them to the device)
   std::vector<int> local(nn, -1);
   for (int t = 0; t < ng; ++t) {
     const int g = order[t];
     MfGroup& mg = P->groups[t];
     const int nloc = mg.ns + mg.nr;
-    std::vector<int32_t> nodes((size_t)mg.nf * nloc), cpos((size_t)mg.nf * 2 * nloc, -1), dpos((size_t)mg.nf * 2 * mg.rp, -1);
-    std::vector<int8_t> code((size_t)mg.nf * nloc * mg.ns + 4, (int8_t)-1);  // + 4: k_mf_front stages the tables word by word
-    std::vector<MfChild> child((size_t)mg.nf * 2);
+    std::vector<int32_t>& nodes = mg.h_nodes;
+    std::vector<int32_t>& cpos = mg.h_cpos;
+    std::vector<int32_t>& dpos = mg.h_dpos;
+    std::vector<int8_t>& code = mg.h_code;
+    std::vector<MfChild>& child = mg.h_child;
+    std::vector<int32_t>& upos = mg.h_upos;
+    nodes.assign((size_t)mg.nf * nloc, 0);
+    cpos.assign((size_t)mg.nf * 2 * nloc, -1);
+    dpos.assign((size_t)mg.nf * 2 * mg.rp, -1);
+    code.assign((size_t)mg.nf * nloc * mg.ns + 4, (int8_t)-1);  // + 4: k_mf_front stages the tables word by word
+    child.assign((size_t)mg.nf * 2, MfChild{});
     const int NUf = 16 * mg.T;
-    std::vector<int32_t> upos(mg.front ? (size_t)mg.nf * 2 * NUf : 0, -1);
+    upos.assign(mg.front ? (size_t)mg.nf * 2 * NUf : 0, -1);
     for (int f = 0; f < mg.nf; ++f) {
       const SN& s = sn[members[g][f]];
       int32_t* nd = &nodes[(size_t)f * nloc];
       for (int i = 0; i < mg.ns; ++i) nd[i] = s.nodes[i];
       for (int i = 0; i < mg.nr; ++i) nd[mg.ns + i] = s.bnd[i];
       for (int i = 0; i < nloc; ++i) local[nd[i]] = i;
-      for (int j = 0; j < mg.ns; ++j)  // column node j: its stencil neighbours i = j + off(code'), stored as the code of (i -> j)
-        for (int c = 0; c < ncode; ++c) {
-          if (!coupled(c)) continue;
-          const int v = neighbour(nd[j], c);  // v = node_j + off(c)  =>  node_j = v + off(opposite code)
-          const int i = local[v];
+      for (int j = 0; j < mg.ns; ++j)  // column node j: the nodes w it couples with, stored as the code of (w -> node_j)
+        for (int e = T.nb_ptr[nd[j]]; e < T.nb_ptr[nd[j] + 1]; ++e) {
+          const int i = local[T.nb_node[e]];
           if (i < 0) continue;  // eliminated earlier: that coupling sits in an earlier front
-          code[((size_t)f * nloc + i) * mg.ns + j] = (int8_t)(ncode - 1 - c);  // opposite offset: code of (node_i -> node_j)
+          code[((size_t)f * nloc + i) * mg.ns + j] = (int8_t)T.nb_code[e];
         }
       for (int slot = 0; slot < 2; ++slot) {
         MfChild& ch = child[(size_t)f * 2 + slot];
@@ -515,33 +589,69 @@ int mf_plan_create(MfPlan** out, const Geo& G, bool keep) {
           for (int p = 0; p < mg.rb + MF_BORDER; ++p) up[mg.s16 + p] = dp[p];
         }
       }
-      if (s.children.size() > 2) {
-        g_berr = "multifrontal plan: more than two children";
-        mf_plan_destroy(P);
-        return HOMMX_EINVAL;
-      }
-      if (members[g][f] == nsn - 1) mg.pinpos = local[nn - 1];
+      if (members[g][f] == nsn - 1) mg.pinpos = local[gauge];
       for (int i = 0; i < nloc; ++i) local[nd[i]] = -1;
     }
-    std::vector<uint16_t> tilemap;
+    mg.h_tilemap.clear();
     if (mg.front)
       for (int a = mg.R0; a < mg.T; ++a)   // row by row: the tiles with eliminated rows (a < P) come first (mf_front_kernel.h; the one-wave variants,
-        for (int b = a; b < mg.T; ++b) tilemap.push_back((uint16_t)(a << 8 | b));  // T <= 6, number their tiles column by column without a table)
-    if (upload(&mg.d_nodes, nodes) || upload(&mg.d_code, code) || upload(&mg.d_cpos, cpos) || upload(&mg.d_dpos, dpos) ||
-        upload(&mg.d_child, child) || upload(&mg.d_upos, upos) || upload(&mg.d_tilemap, tilemap)) {
-      mf_plan_destroy(P);
-      return HOMMX_EHIP;
-    }
+        for (int b = a; b < mg.T; ++b) mg.h_tilemap.push_back((uint16_t)(a << 8 | b));  // T <= 6, number their tiles column by column without a table)
   }
   if (getenv("HOMMX_MF_VERBOSE")) {
-    fprintf(stderr, "[hommx multifrontal] n = %d, bs = %d: %d fronts in %d groups, arena %.1f MB + scratch %.1f MB per cell, %.2f GFLOP per cell\n",
-            n, bs, nsn, ng, 8e-6 * P->arena_per_cell, 8e-6 * P->scratch_per_cell, 1e-9 * P->flops_per_cell);
+    if (G.n > 0)
+      fprintf(stderr, "[hommx multifrontal] n = %d, bs = %d: %d fronts in %d groups, arena %.1f MB + scratch %.1f MB per cell, %.2f GFLOP per cell\n",
+              G.n, bs, nsn, ng, 8e-6 * P->arena_per_cell, 8e-6 * P->scratch_per_cell, 1e-9 * P->flops_per_cell);
+    else
+      fprintf(stderr, "[hommx multifrontal] mesh of %d nodes, bs = %d: %d fronts in %d groups, arena %.1f MB + scratch %.1f MB per cell, %.2f GFLOP per cell\n",
+              nn, bs, nsn, ng, 8e-6 * P->arena_per_cell, 8e-6 * P->scratch_per_cell, 1e-9 * P->flops_per_cell);
     for (const MfGroup& mg : P->groups)
       fprintf(stderr, "   height %d: %3d fronts  s = %4d (%4d)  r = %4d (%4d)%s\n", mg.height, mg.nf, mg.ns * bs, mg.sp, mg.rb, mg.rp,
               mg.front ? "  [k_mf_front]" : "");
   }
   *out = P;
   return 0;
+}
+
+int mf_plan_upload(MfPlan* P) {
+  for (MfGroup& mg : P->groups)
+    if (upload(&mg.d_nodes, mg.h_nodes) || upload(&mg.d_code, mg.h_code) || upload(&mg.d_cpos, mg.h_cpos) || upload(&mg.d_dpos, mg.h_dpos) ||
+        upload(&mg.d_child, mg.h_child) || upload(&mg.d_upos, mg.h_upos) || upload(&mg.d_tilemap, mg.h_tilemap))
+      return HOMMX_EHIP;
+  return 0;
+}
+
+int mf_plan_create(MfPlan** out, const Geo& G, bool keep) {
+  *out = nullptr;
+  MfTree T;
+  mf_tree_structured(G, &T);
+  MfPlan* P = nullptr;
+  if (int rc = mf_plan_build(&P, G, T, keep)) return rc;
+  if (int rc = mf_plan_upload(P)) {
+    mf_plan_destroy(P);
+    return rc;
+  }
+  *out = P;
+  return 0;
+}
+
+MfStats mf_stats(const MfPlan* p) {
+  MfStats s{};
+  if (!p) return s;
+  const int bs = p->G.bs;
+  s.nfronts = p->nfronts;
+  s.ngroups = (int)p->groups.size();
+  for (const MfGroup& mg : p->groups) {
+    const int L = (mg.ns + mg.nr) * bs;
+    if (L > s.max_front) {
+      s.max_front = L;
+      s.max_s = mg.ns * bs;
+      s.max_r = mg.rb;
+    }
+    if (mg.front) ++s.front_groups;
+  }
+  s.arena_per_cell = p->arena_per_cell;
+  s.flops = p->flops_per_cell;
+  return s;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1001,8 +1111,11 @@ int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_
     }
     for (int k = 0; k < nh; ++k) {
       const MfHalf& h = halves[k];
-      launch_assembly(ws, d_coef + h.c0 * G.n_el * G.ncomp, d_M ? d_M + h.c0 * G.dim * G.dim : nullptr, h.nc, h.st,
-                      P->Kst + h.base * G.ncode * bs * bs * G.nn, P->Brhs + h.base * G.t * bs * G.nn, P->C0 + h.base * 36);
+      const double* coef = d_coef + h.c0 * G.n_el * G.ncomp;
+      const double* Mm = d_M ? d_M + h.c0 * G.dim * G.dim : nullptr;
+      double *Kst = P->Kst + h.base * G.ncode * bs * bs * G.nn, *Brhs = P->Brhs + h.base * G.t * bs * G.nn, *C0 = P->C0 + h.base * 36;
+      if (P->mesh) launch_mesh_assembly(*P->mesh, coef, Mm, h.nc, h.st, Kst, Brhs, C0);  // the only launch that knows the geometry
+      else launch_assembly(ws, coef, Mm, h.nc, h.st, Kst, Brhs, C0);
     }
     int gi = 0;
     for (const MfGroup& mg : P->groups) {  // launches of the pieces interleaved: all queues fill at the same pace

@@ -98,7 +98,8 @@ int hommx_plan_reserve(hommx_plan* plan, int64_t n_cells);
  * t = size of the effective tensor (d for Poisson, d(d+1)/2 for elasticity), the descriptor fields, and the name of the
  * kernel route the plan's effective-tensor solves take: "fused2d" (2D scalar Poisson, n <= 32), "small_wave" (plane block
  * b <= 48: one wavefront per cell), "small_fused" (3D meshes with 48 < b <= 64: LDS), "multifrontal" (plane blocks b > 64 and 2D meshes with b > 48, e.g. 3D elasticity
- * from 5^3 micro cells: nested dissection, batched fronts) or "blocked" (everything else: plane elimination; also the corrector entry point of plans whose tensors take a one-launch route). */
+ * from 5^3 micro cells: nested dissection, batched fronts) or "blocked" (everything else: plane elimination; also the corrector entry point of plans whose tensors take a one-launch route);
+ * mesh plans: "mesh_front" or "mesh_multifrontal". */
 int32_t hommx_plan_dim(const hommx_plan* plan);
 int32_t hommx_plan_device(const hommx_plan* plan);
 int32_t hommx_plan_n_micro(const hommx_plan* plan);
@@ -199,25 +200,32 @@ int hommx_solve_batch_correctors(hommx_plan* plan, int64_t n_cells, const double
  * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
  * periodic: the caller folds the mesh vertices into n_nodes independent (periodic) nodes -- cell_problem.py:38-300's slave -> master
  * map -- and passes, per element, the periodic node of every vertex and the UNFOLDED vertex coordinates (gradients and volumes).
- * The plan is a hommx_plan of its own route ("mesh_front": batched frontal elimination, one workgroup per macro cell, the front in
- * LDS); hommx_solve_batch[_device], _two_phase[_device], _separable[_device], _correctors, hommx_plan_reserve, the accessors and
- * hommx_plan_destroy take it unchanged (hommx_plan_n_micro is 0).  hommx_solve_batch_multi[_device] refuses it (HOMMX_EINVAL).
+ * The plan is a hommx_plan of one of two routes: "mesh_front" (batched frontal elimination, one workgroup per macro cell, the front in
+ * LDS) for meshes whose frontal width is at most HOMMX_MESH_MAX_FRONT, and "mesh_multifrontal" (nested
+ * dissection of the mesh by coordinate bisection, eliminated by the multifrontal engine of the structured routes) for wider meshes and
+ * for any mesh with HOMMX_MESH_FLAG_TREE.  hommx_solve_batch[_device], _two_phase[_device], _separable[_device], _correctors,
+ * hommx_plan_reserve, the accessors and hommx_plan_destroy take either unchanged (hommx_plan_n_micro is 0).
+ * hommx_solve_batch_multi[_device] refuses both (HOMMX_EINVAL).
  *
  *   coef[cell][el]    follows the element order of the descriptor
- *   gauge             the last node of the elimination order is pinned (its bs unknowns dropped), as on the structured routes
+ *   gauge             the last node of the elimination order is pinned (its bs unknowns dropped), as on the structured routes; on
+ *                     the tree route the node of highest elimination rank in the root front (A_H does not depend on the choice)
  *   correctors        [n_cells][t][n_nodes * bs], dof = node * bs + component in the caller's node ids, mean-free per component
  *   info[cell]        k > 0: the k-th pivot (counted from 1 in elimination order) was non-positive or not finite
- *   flops_per_solve   sum over the pivots of f^2 + 2 f t, f = unknowns in the front at that pivot (itself included)
+ *   flops_per_solve   sum over the pivots of f^2 + 2 f t, f = unknowns in the front at that pivot (itself included); on the tree
+ *                     route the dense flops of the multifrontal model (padded fronts, as hommx_plan_flops_per_solve of the structured
+ *                     multifrontal route)
  */
 #define HOMMX_MESH_MAX_FRONT 192  /* largest front, in unknowns: the packed front of t + 192 rows fills the 160 KiB LDS of a CU */
+#define HOMMX_MESH_FLAG_TREE 1    /* hommx_mesh_desc.flags: take the tree route whatever the frontal width                   */
 
 typedef struct hommx_mesh_desc {
-  int32_t dim, kind, device, flags;   /* as hommx_plan_desc; flags normally 0                                     */
+  int32_t dim, kind, device, flags;   /* as hommx_plan_desc; flags: 0 or HOMMX_MESH_FLAG_TREE                     */
   int64_t n_nodes;                    /* independent (periodic) nodes                                             */
   int64_t n_el;                       /* micro elements; coef[cell][el] follows THIS order                        */
   const int32_t* el_nodes;            /* [n_el][dim+1]  periodic node of each vertex                              */
   const double* el_x;                 /* [n_el][dim+1][dim] vertex coordinates, NOT folded: gradients and volumes */
-  const int32_t* order;               /* [n_nodes] elimination order, or NULL: the library's own (narrowest of reverse Cuthill-McKee and coordinate sweeps) */
+  const int32_t* order;               /* [n_nodes] elimination order, or NULL: the library's own (narrowest of reverse Cuthill-McKee and coordinate sweeps); the tree route checks it and ignores it */
   int32_t reserved[4];
 } hommx_mesh_desc;
 
@@ -226,9 +234,17 @@ typedef struct hommx_mesh_desc {
  * failure returns HOMMX_EINVAL with the reason (the measured width and the limit for a front that is too wide).  Either output may
  * be NULL. */
 int hommx_mesh_analyze(const hommx_mesh_desc* d, int32_t* front_width, double* flops_per_solve);
-/* The same checks, then the plan on d->device. */
+/* The tree route's analysis, host only: the same checks but the front width, then the dissection.  Supernodes (fronts) are numbered in
+ * elimination order, children before their parent, the root last; parent[root] = -1, no front has more than two children, and the gauge
+ * is the root's node of highest id.  max_front: the largest front (eliminated + boundary unknowns); flops_per_solve: the multifrontal
+ * model.  A node with more than 127 coupling codes (neighbours + itself) is refused with HOMMX_EINVAL.  Every output may be NULL;
+ * parent needs n_fronts entries (a first call without it tells how many). */
+int hommx_mesh_analyze_tree(const hommx_mesh_desc* d, int32_t* n_fronts, int32_t* n_groups, int32_t* max_front, double* flops_per_solve,
+                            int32_t* supernode_of_node /*[n_nodes] or NULL*/, int32_t* parent /*[n_fronts] or NULL*/);
+/* The same checks, then the plan on d->device: the frontal route when its width is at most HOMMX_MESH_MAX_FRONT and the flag is not
+ * set, the tree route otherwise (a front too wide is then no error). */
 int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d);
-/* Front width of a mesh plan in unknowns; 0 for the structured routes. */
+/* Front width of a frontal mesh plan in unknowns; 0 for the structured routes and for the tree route. */
 int32_t hommx_plan_front_width(const hommx_plan* plan);
 
 /*
