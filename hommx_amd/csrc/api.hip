@@ -4,6 +4,7 @@
 // _compute_local_stiffness (hmm.py:334-369) once per cell.  Here: one call per batch of cells.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +13,7 @@
 #include <string>
 
 #include "../../include/hommx_hip.h"
+#include "blocked_internal.h"
 #include "kernels.h"
 #include "mesh_front.h"
 #include "mesh_tree.h"
@@ -38,65 +40,135 @@ int fail(int code, const char* fmt, ...) {
                   hipGetErrorString(e__));                                                     \
   } while (0)
 
-enum Family { FAM_FUSED2D = 0, FAM_BLOCKED = 1, FAM_MESH = 2, FAM_MESH_TREE = 3 };
+// FAM_BLOCKED: structured plans beyond the fused 2D kernel, and the mesh plans of the tree route (their workspace carries the mesh)
+enum Family { FAM_FUSED2D = 0, FAM_BLOCKED = 1, FAM_MESH = 2 };
 
-}  // namespace
+// a device (or, pinned, page-locked host) buffer, grown on demand
+struct Buf {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool pinned = false;
+  void release() {
+    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    cap = 0;
+  }
+};
 
-struct hommx_plan;
-namespace {
-template <typename B>
-int grow_pinned(B& b, size_t bytes) {
+int grow(Buf& b, size_t bytes) {
   if (bytes <= b.cap) return HOMMX_OK;
-  if (b.p) (void)hipHostFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  HIP_TRY(hipHostMalloc(&b.p, bytes, hipHostMallocDefault));
+  b.release();
+  if (b.pinned)
+    HIP_TRY(hipHostMalloc(&b.p, bytes, hipHostMallocDefault));
+  else
+    HIP_TRY(hipMalloc(&b.p, bytes));
   b.cap = bytes;
   return HOMMX_OK;
 }
 
-template <typename B>
-int grow(B& b, size_t bytes) {
-  if (bytes <= b.cap) return HOMMX_OK;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  HIP_TRY(hipMalloc(&b.p, bytes));
-  b.cap = bytes;
-  return HOMMX_OK;
-}
 }  // namespace
 
 struct hommx_plan {
   hommx_plan_desc desc;
   Family family;
   int64_t n_el;
-  int32_t n_comp;
-  int32_t t;
-  // staging buffers for the host-pointer entry point (grown on demand)
-  double* d_coef = nullptr;
-  double* d_M = nullptr;
-  double* d_out = nullptr;
-  int32_t* d_info = nullptr;
-  int64_t cap_cells = 0;
-  hommx::BlockedWorkspace* ws = nullptr;
-  hommx::MeshPlan* mesh = nullptr;  // FAM_MESH: symbolic phase + device tables of the unstructured micro mesh
-  hommx::MeshTreePlan* mtree = nullptr;  // FAM_MESH_TREE: the same mesh on the nested-dissection engine (meshes wider than the LDS front)
-  double* d_expand = nullptr;  // two-phase media on the blocked family: expanded element stream
-  int64_t cap_expand = 0;
-  // plan-owned staging of the sampler entry points (two-phase / separable, host pointers): grown on demand, never per call
-  struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-  };
-  Buf st_mask, st_values, st_table, st_w, st_M, st_out, st_info;
-  // pinned host mirrors of the small sampler inputs / outputs: one asynchronous H2D, the kernel, one asynchronous D2H, ONE synchronisation
-  Buf pin_in, pin_out, dev_in, dev_out;
-  // host-pointer entry point of the fused family: coefficient chunks stream in on s_copy while s_comp solves the previous one
+  hommx::KindSizes ks;
+  hommx::BlockedWorkspace* ws = nullptr;  // FAM_BLOCKED, and a FAM_FUSED2D plan once it has served correctors
+  hommx::MeshPlan* mesh = nullptr;        // FAM_MESH: symbolic phase + device tables of the unstructured micro mesh
+  // plan-owned staging, grown on demand, never per call: the plain host entry point's buffers, the expanded element stream of the sampler
+  // entry points, and the packed blocks of the sampler host entry points (pinned host mirrors + device)
+  Buf coef, M, out, info, expand, dev_in, dev_out, pin_in{nullptr, 0, true}, pin_out{nullptr, 0, true};
+  // host-pointer entry point: coefficient chunks stream in on s_copy while s_comp solves the previous one
   hipStream_t s_copy = nullptr, s_comp = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
-  bool h2d_overlap = true;  // HOMMX_NO_H2D_OVERLAP (dev knob, read when the plan is created) switches the pipelining off
 };
+
+namespace {
+
+// what opens a batch entry point, in this order: the plan, the batch size, the pointers (`names` lists them), the limit of one launch (device
+// entry points); then the plan's device is made current.  GO, or what the call returns: an error, HOMMX_OK for an empty batch
+constexpr int GO = 1;
+int open_call(const hommx_plan* p, int64_t n_cells, bool ptrs_ok = true, const char* names = "", bool one_launch = false) {
+  if (!p) return fail(HOMMX_EINVAL, "null plan");
+  if (n_cells < 0) return fail(HOMMX_EINVAL, "negative n_cells");
+  if (n_cells == 0) return HOMMX_OK;
+  if (!ptrs_ok) return fail(HOMMX_EINVAL, "null %s", names);
+  if (one_launch && n_cells > 0x7fffffffll) return fail(HOMMX_EINVAL, "n_cells too large for one launch");
+  HIP_TRY(hipSetDevice(p->desc.device));
+  return GO;
+}
+
+// a failed call into the plan's route, under the route's name
+int route_fail(const hommx_plan* p, int rc) {
+  if (p->family == FAM_MESH) return fail(rc, "mesh route: %s", hommx::mesh_last_error());
+  return fail(rc, "%s: %s", p->desc.n_micro ? "blocked path" : "mesh route", hommx::blocked_last_error());
+}
+
+// an element stream on the device through the plan's mesh_front or blocked route; d_corr: the correctors as well
+int route_solve(hommx_plan* p, int64_t n_cells, const double* d_coef, const double* d_M, double* d_A_eff, int32_t* d_info, hipStream_t st,
+                double* d_corr = nullptr) {
+  const int rc = p->family == FAM_MESH ? hommx::mesh_solve(p->mesh, n_cells, d_coef, d_M, d_A_eff, d_info, st, d_corr)
+                                       : hommx::blocked_solve(p->ws, n_cells, d_coef, d_M, d_A_eff, d_info, st, d_corr);
+  return rc ? route_fail(p, rc) : HOMMX_OK;
+}
+
+// the sampler device entry points on the blocked and mesh families: expand(c0, nc, dst) launches the expansion of cells [c0, c0 + nc) into
+// the plan's element stream, which is solved chunk by chunk of at most 1 GiB
+template <typename Expand>
+int expand_and_solve(hommx_plan* p, int64_t n_cells, const double* d_M, double* d_A_eff, int32_t* d_info, hipStream_t st, Expand expand) {
+  const int64_t per = p->n_el * p->ks.n_comp;
+  const int64_t chunk = std::clamp<int64_t>((1ll << 27) / std::max<int64_t>(per, 1), 1, n_cells);
+  if (int rc = grow(p->expand, sizeof(double) * chunk * per)) return rc;
+  double* dst = static_cast<double*>(p->expand.p);
+  const int d = p->desc.dim, t = p->ks.t;
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    const int64_t nc = (n_cells - c0 < chunk) ? n_cells - c0 : chunk;
+    HIP_TRY(expand(c0, nc, dst));
+    int rc = route_solve(p, nc, dst, d_M ? d_M + c0 * d * d : nullptr, d_A_eff + c0 * t * t, d_info ? d_info + c0 : nullptr, st);
+    if (rc != HOMMX_OK) return rc;
+  }
+  return HOMMX_OK;
+}
+
+// The sampler host entry points: their inputs are small, so they are packed into ONE pinned block owned by the plan and travel in one
+// asynchronous copy; the outputs come back the same way, and the call synchronises once.  No hipMalloc / hipFree per call.  in[k]: a host
+// input (a null one takes no room); run(d_in, d_A_eff, d_info) calls the device entry point with d_in[k] the device copy of in[k] (or null).
+struct HostIn {
+  const void* src;
+  size_t bytes;
+};
+template <size_t N, typename Run>
+int staged_call(hommx_plan* p, int64_t n_cells, const HostIn (&in)[N], double* A_eff, int32_t* info, Run run) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  size_t off[N], in_bytes = 0;
+  for (size_t k = 0; k < N; ++k) {
+    off[k] = in_bytes;
+    if (in[k].src) in_bytes += up(in[k].bytes);
+  }
+  const size_t a_bytes = sizeof(double) * n_cells * p->ks.t * p->ks.t, o_info = up(a_bytes), out_bytes = o_info + up(sizeof(int32_t) * n_cells);
+  if (int rc = grow(p->pin_in, in_bytes)) return rc;
+  if (int rc = grow(p->pin_out, out_bytes)) return rc;
+  if (int rc = grow(p->dev_in, in_bytes)) return rc;
+  if (int rc = grow(p->dev_out, out_bytes)) return rc;
+  char* hin = static_cast<char*>(p->pin_in.p);
+  char* din = static_cast<char*>(p->dev_in.p);
+  char* dout = static_cast<char*>(p->dev_out.p);
+  const void* d_in[N];
+  for (size_t k = 0; k < N; ++k) {
+    d_in[k] = in[k].src ? din + off[k] : nullptr;
+    if (in[k].src) memcpy(hin + off[k], in[k].src, in[k].bytes);
+  }
+  HIP_TRY(hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, nullptr));
+  if (int rc = run(d_in, reinterpret_cast<double*>(dout), reinterpret_cast<int32_t*>(dout + o_info))) return rc;
+  HIP_TRY(hipMemcpyAsync(p->pin_out.p, dout, out_bytes, hipMemcpyDeviceToHost, nullptr));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  const char* hout = static_cast<const char*>(p->pin_out.p);
+  memcpy(A_eff, hout, a_bytes);
+  if (info) memcpy(info, hout + o_info, sizeof(int32_t) * n_cells);
+  return HOMMX_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -123,16 +195,9 @@ int hommx_plan_create(hommx_plan** out, const hommx_plan_desc* d) {
   p->desc = *d;
   const int dim = d->dim, n = d->n_micro;
   p->n_el = (dim == 2) ? 2ll * n * n : 6ll * n * n * n;
-  const int tp = dim;                    // Poisson tensor size
-  const int te = dim * (dim + 1) / 2;    // elasticity (Voigt) tensor size
-  switch (d->kind) {
-    case HOMMX_KIND_POISSON_SCALAR: p->n_comp = 1; p->t = tp; break;
-    case HOMMX_KIND_POISSON_MATRIX: p->n_comp = dim * (dim + 1) / 2; p->t = tp; break;
-    case HOMMX_KIND_ELASTICITY_ISO: p->n_comp = 2; p->t = te; break;
-    default: p->n_comp = te * (te + 1) / 2; p->t = te; break;
-  }
-  p->h2d_overlap = getenv("HOMMX_NO_H2D_OVERLAP") == nullptr;
-  p->family = (dim == 2 && d->kind == HOMMX_KIND_POISSON_SCALAR && n <= 32 && !(d->flags & 1)) ? FAM_FUSED2D : FAM_BLOCKED;
+  p->ks = hommx::kind_sizes(dim, d->kind);
+  const bool fused = dim == 2 && d->kind == HOMMX_KIND_POISSON_SCALAR && n <= 32 && !(d->flags & HOMMX_FLAG_FORCE_BLOCKED);
+  p->family = fused ? FAM_FUSED2D : FAM_BLOCKED;
   if (p->family == FAM_BLOCKED) {
     int rc = hommx::blocked_workspace_create(&p->ws, dim, n, d->kind);
     if (rc != 0) {
@@ -147,18 +212,9 @@ int hommx_plan_create(hommx_plan** out, const hommx_plan_desc* d) {
 int hommx_plan_destroy(hommx_plan* p) {
   if (!p) return HOMMX_OK;
   hipSetDevice(p->desc.device);
-  if (p->d_coef) hipFree(p->d_coef);
-  if (p->d_M) hipFree(p->d_M);
-  if (p->d_out) hipFree(p->d_out);
-  if (p->d_info) hipFree(p->d_info);
   if (p->ws) hommx::blocked_workspace_destroy(p->ws);
   if (p->mesh) hommx::mesh_destroy(p->mesh);
-  if (p->mtree) hommx::mesh_tree_destroy(p->mtree);
-  if (p->d_expand) hipFree(p->d_expand);
-  for (hommx_plan::Buf* b : {&p->st_mask, &p->st_values, &p->st_table, &p->st_w, &p->st_M, &p->st_out, &p->st_info, &p->dev_in, &p->dev_out})
-    if (b->p) hipFree(b->p);
-  for (hommx_plan::Buf* b : {&p->pin_in, &p->pin_out})
-    if (b->p) hipHostFree(b->p);
+  for (Buf* b : {&p->coef, &p->M, &p->out, &p->info, &p->expand, &p->dev_in, &p->dev_out, &p->pin_in, &p->pin_out}) b->release();
   if (p->s_copy) hipStreamDestroy(p->s_copy);
   if (p->s_comp) hipStreamDestroy(p->s_comp);
   for (hipEvent_t e : p->ev)
@@ -175,68 +231,46 @@ int32_t hommx_plan_device(const hommx_plan* p) { return p ? p->desc.device : -1;
 int32_t hommx_plan_n_micro(const hommx_plan* p) { return p ? p->desc.n_micro : 0; }
 int32_t hommx_plan_kind(const hommx_plan* p) { return p ? p->desc.kind : -1; }
 int64_t hommx_plan_num_elements(const hommx_plan* p) { return p ? p->n_el : 0; }
-int32_t hommx_plan_coef_components(const hommx_plan* p) { return p ? p->n_comp : 0; }
-int32_t hommx_plan_tensor_size(const hommx_plan* p) { return p ? p->t : 0; }
+int32_t hommx_plan_coef_components(const hommx_plan* p) { return p ? p->ks.n_comp : 0; }
+int32_t hommx_plan_tensor_size(const hommx_plan* p) { return p ? p->ks.t : 0; }
 int hommx_plan_reserve(hommx_plan* p, int64_t n_cells) {
-  if (!p) return fail(HOMMX_EINVAL, "null plan");
-  if (n_cells < 0) return fail(HOMMX_EINVAL, "negative n_cells");
-  if (p->family == FAM_FUSED2D || n_cells == 0) return HOMMX_OK;  // the fused 2D family keeps no scratch
-  HIP_TRY(hipSetDevice(p->desc.device));
-  if (p->family == FAM_MESH || p->family == FAM_MESH_TREE) {
-    int rc = p->family == FAM_MESH ? hommx::mesh_reserve(p->mesh, n_cells) : hommx::mesh_tree_reserve(p->mtree, n_cells);
-    return rc ? fail(rc, "mesh route: %s", hommx::mesh_last_error()) : HOMMX_OK;
-  }
-  int rc = hommx::blocked_reserve(p->ws, n_cells);
-  if (rc != 0) return fail(rc, "blocked path: %s", hommx::blocked_last_error());
-  return HOMMX_OK;
+  if (int rc = open_call(p, n_cells); rc != GO) return rc;
+  if (p->family == FAM_FUSED2D) return HOMMX_OK;  // the fused 2D family keeps no scratch
+  const int rc = p->family == FAM_MESH ? hommx::mesh_reserve(p->mesh, n_cells) : hommx::blocked_reserve(p->ws, n_cells);
+  return rc ? route_fail(p, rc) : HOMMX_OK;
 }
 
 double hommx_plan_flops_per_solve(const hommx_plan* p) {
   if (!p) return 0.0;
-  if (p->family == FAM_FUSED2D) {
-    const double n = p->desc.n_micro;
-    return (6.0 * (n - 1) + 2.0) * n * n * n;
+  switch (p->family) {
+    case FAM_FUSED2D: {
+      const double n = p->desc.n_micro;
+      return (6.0 * (n - 1) + 2.0) * n * n * n;
+    }
+    case FAM_MESH: return hommx::mesh_flops_per_cell(p->mesh);
+    default: return hommx::blocked_flops_per_cell(p->ws);
   }
-  if (p->family == FAM_MESH) return hommx::mesh_flops_per_cell(p->mesh);
-  if (p->family == FAM_MESH_TREE) return hommx::mesh_tree_flops_per_cell(p->mtree);
-  return hommx::blocked_flops_per_cell(p->ws);
 }
+
 const char* hommx_plan_kernel_name(const hommx_plan* p) {
   if (!p) return "";
-  if (p->family == FAM_MESH) return "mesh_front";
-  if (p->family == FAM_MESH_TREE) return "mesh_multifrontal";
-  return p->family == FAM_FUSED2D ? "fused2d" : hommx::blocked_route_name(p->ws);
+  switch (p->family) {
+    case FAM_FUSED2D: return "fused2d";
+    case FAM_MESH: return "mesh_front";
+    default: return hommx::blocked_route_name(p->ws);
+  }
 }
 
 const char* hommx_plan_route_detail(hommx_plan* p) {
   if (!p) return "";
-  if (p->family == FAM_FUSED2D)
-    return p->desc.n_micro > 16 ? "fused2d: k_poisson2d_fused<32>, one wavefront per macro cell, every matrix in the f64 MFMA accumulator layout"
-                                : "fused2d: k_poisson2d_fused<16>, one wavefront per macro cell, every matrix in the f64 MFMA accumulator layout";
-  if (p->family == FAM_MESH) return hommx::mesh_route_detail(p->mesh);
-  if (p->family == FAM_MESH_TREE) return hommx::mesh_tree_route_detail(p->mtree);
-  return hommx::blocked_route_detail(p->ws);
-}
-
-}  // extern "C"
-
-namespace {
-// an element stream on the device through the plan's blocked or mesh route
-int solve_stream(hommx_plan* p, int64_t n_cells, const double* d_coef, const double* d_M, double* d_A_eff, int32_t* d_info, hipStream_t st) {
-  if (p->family == FAM_MESH) {
-    int rc = hommx::mesh_solve(p->mesh, n_cells, d_coef, d_M, d_A_eff, d_info, st);
-    return rc ? fail(rc, "mesh route: %s", hommx::mesh_last_error()) : HOMMX_OK;
+  switch (p->family) {
+    case FAM_FUSED2D:
+      return p->desc.n_micro > 16 ? "fused2d: k_poisson2d_fused<32>, one wavefront per macro cell, every matrix in the f64 MFMA accumulator layout"
+                                  : "fused2d: k_poisson2d_fused<16>, one wavefront per macro cell, every matrix in the f64 MFMA accumulator layout";
+    case FAM_MESH: return hommx::mesh_route_detail(p->mesh);
+    default: return hommx::blocked_route_detail(p->ws);
   }
-  if (p->family == FAM_MESH_TREE) {
-    int rc = hommx::mesh_tree_solve(p->mtree, n_cells, d_coef, d_M, d_A_eff, d_info, st);
-    return rc ? fail(rc, "mesh route: %s", hommx::mesh_last_error()) : HOMMX_OK;
-  }
-  int rc = hommx::blocked_solve(p->ws, n_cells, d_coef, d_M, d_A_eff, d_info, st);
-  return rc ? fail(rc, "blocked path: %s", hommx::blocked_last_error()) : HOMMX_OK;
 }
-}  // namespace
-
-extern "C" {
 
 int hommx_mesh_analyze(const hommx_mesh_desc* d, int32_t* front_width, double* flops_per_solve) {
   int rc = hommx::mesh_analyze(d, nullptr, front_width, flops_per_solve);
@@ -288,19 +322,14 @@ int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d) {
   p->desc.kind = d->kind;
   p->desc.device = d->device;
   p->desc.flags = d->flags;
-  p->family = m ? FAM_MESH : FAM_MESH_TREE;
+  p->family = m ? FAM_MESH : FAM_BLOCKED;
   p->mesh = m;
-  p->mtree = mt;
   p->n_el = d->n_el;
-  const int dim = d->dim, te = dim * (dim + 1) / 2;
-  switch (d->kind) {
-    case HOMMX_KIND_POISSON_SCALAR: p->n_comp = 1; p->t = dim; break;
-    case HOMMX_KIND_POISSON_MATRIX: p->n_comp = te; p->t = dim; break;
-    case HOMMX_KIND_ELASTICITY_ISO: p->n_comp = 2; p->t = te; break;
-    default: p->n_comp = te * (te + 1) / 2; p->t = te; break;
-  }
-  p->h2d_overlap = getenv("HOMMX_NO_H2D_OVERLAP") == nullptr;
-  if (hipSetDevice(d->device) != hipSuccess || (rc = m ? hommx::mesh_upload(m) : hommx::mesh_tree_upload(mt)) != 0) {
+  p->ks = hommx::kind_sizes(d->dim, d->kind);
+  const bool dev_ok = hipSetDevice(d->device) == hipSuccess;
+  if (dev_ok) rc = m ? hommx::mesh_upload(m) : hommx::mesh_tree_workspace(mt, &p->ws);
+  hommx::mesh_tree_destroy(mt);  // host analysis only: the workspace holds what the tree route needs
+  if (!dev_ok || rc) {
     const std::string msg = rc ? hommx::mesh_last_error() : "hipSetDevice failed";
     hommx_plan_destroy(p);
     return fail(rc ? rc : HOMMX_EHIP, "mesh route: %s", msg.c_str());
@@ -313,52 +342,33 @@ int32_t hommx_plan_front_width(const hommx_plan* p) { return p && p->family == F
 
 int hommx_solve_batch_device(hommx_plan* p, int64_t n_cells, const double* d_coef, const double* d_M,
                              double* d_A_eff, int32_t* d_info, void* stream) {
-  if (!p) return fail(HOMMX_EINVAL, "null plan");
-  if (n_cells < 0) return fail(HOMMX_EINVAL, "negative n_cells");
-  if (n_cells == 0) return HOMMX_OK;
-  if (!d_coef || !d_A_eff) return fail(HOMMX_EINVAL, "null coef / A_eff");
-  if (n_cells > 0x7fffffffll) return fail(HOMMX_EINVAL, "n_cells too large for one launch");
-  HIP_TRY(hipSetDevice(p->desc.device));
+  if (int rc = open_call(p, n_cells, d_coef && d_A_eff, "coef / A_eff", true); rc != GO) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (p->family == FAM_FUSED2D) {
     HIP_TRY(hommx::launch_poisson2d_fused(d_coef, d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st));
     return HOMMX_OK;
   }
-  return solve_stream(p, n_cells, d_coef, d_M, d_A_eff, d_info, st);
+  return route_solve(p, n_cells, d_coef, d_M, d_A_eff, d_info, st);
 }
 
 int hommx_solve_batch(hommx_plan* p, int64_t n_cells, const double* coef, const double* M, double* A_eff,
                       int32_t* info) {
-  if (!p) return fail(HOMMX_EINVAL, "null plan");
-  if (n_cells < 0) return fail(HOMMX_EINVAL, "negative n_cells");
-  if (n_cells == 0) return HOMMX_OK;
-  if (!coef || !A_eff) return fail(HOMMX_EINVAL, "null coef / A_eff");
-  HIP_TRY(hipSetDevice(p->desc.device));
-  const int d = p->desc.dim, t = p->t;
-  if (n_cells > p->cap_cells) {
-    if (p->d_coef) hipFree(p->d_coef);
-    if (p->d_M) hipFree(p->d_M);
-    if (p->d_out) hipFree(p->d_out);
-    if (p->d_info) hipFree(p->d_info);
-    p->d_coef = p->d_M = p->d_out = nullptr;
-    p->d_info = nullptr;
-    p->cap_cells = 0;
-    HIP_TRY(hipMalloc(&p->d_coef, sizeof(double) * n_cells * p->n_el * p->n_comp));
-    HIP_TRY(hipMalloc(&p->d_M, sizeof(double) * n_cells * d * d));
-    HIP_TRY(hipMalloc(&p->d_out, sizeof(double) * n_cells * t * t));
-    HIP_TRY(hipMalloc(&p->d_info, sizeof(int32_t) * n_cells));
-    p->cap_cells = n_cells;
-  }
-  if (M) HIP_TRY(hipMemcpy(p->d_M, M, sizeof(double) * n_cells * d * d, hipMemcpyHostToDevice));
-  const int64_t per = p->n_el * p->n_comp;
+  if (int rc = open_call(p, n_cells, coef && A_eff, "coef / A_eff"); rc != GO) return rc;
+  const int d = p->desc.dim, t = p->ks.t;
+  const int64_t per = p->n_el * p->ks.n_comp;
+  if (int rc = grow(p->coef, sizeof(double) * n_cells * per)) return rc;
+  if (int rc = grow(p->M, sizeof(double) * n_cells * d * d)) return rc;
+  if (int rc = grow(p->out, sizeof(double) * n_cells * t * t)) return rc;
+  if (int rc = grow(p->info, sizeof(int32_t) * n_cells)) return rc;
+  double* d_coef = static_cast<double*>(p->coef.p);
+  double* d_M = M ? static_cast<double*>(p->M.p) : nullptr;
+  double* d_out = static_cast<double*>(p->out.p);
+  int32_t* d_info = static_cast<int32_t*>(p->info.p);
+  if (M) HIP_TRY(hipMemcpy(d_M, M, sizeof(double) * n_cells * d * d, hipMemcpyHostToDevice));
   // cells per chunk of the pipelined copy.  Fused 2D kernel: one wave per cell fills the 256 CUs x 8 wave slots exactly once; blocked
   // family: about 256 MB of coefficient stream, at least 256 cells (from there its throughput is flat: C4 / C5 393 KB per cell -> 682)
-  int64_t CH = 2048;
-  if (p->family != FAM_FUSED2D) {
-    CH = (int64_t)((256ll << 20) / (8 * (per > 0 ? per : 1)));
-    CH = CH < 256 ? 256 : CH > 4096 ? 4096 : CH;
-  }
-  if (n_cells >= 2 * CH && p->h2d_overlap) {
+  const int64_t CH = p->family == FAM_FUSED2D ? 2048 : std::clamp<int64_t>((256ll << 20) / (8 * std::max<int64_t>(per, 1)), 256, 4096);
+  if (n_cells >= 2 * CH) {
     // The coefficient stream (16 KiB per 2D cell, 393 KB per 16^3 elasticity cell) costs PCIe time -- more than the fused kernel costs GPU
     // time, 4 - 8 % of the 3D solves: pipeline it.  The copies are issued from pageable memory, so each blocks this thread -- while the
     // kernels of the previous chunk, already queued on the other stream, run.
@@ -371,33 +381,27 @@ int hommx_solve_batch(hommx_plan* p, int64_t n_cells, const double* coef, const 
     int k = 0;
     for (int64_t c0 = 0; c0 < n_cells; c0 += CH, k ^= 1) {
       const int64_t nc = (n_cells - c0 < CH) ? n_cells - c0 : CH;
-      HIP_TRY(hipMemcpyAsync(p->d_coef + c0 * per, coef + c0 * per, sizeof(double) * nc * per, hipMemcpyHostToDevice, p->s_copy));
+      HIP_TRY(hipMemcpyAsync(d_coef + c0 * per, coef + c0 * per, sizeof(double) * nc * per, hipMemcpyHostToDevice, p->s_copy));
       HIP_TRY(hipEventRecord(p->ev[k], p->s_copy));
       HIP_TRY(hipStreamWaitEvent(p->s_comp, p->ev[k], 0));
-      int rc = hommx_solve_batch_device(p, nc, p->d_coef + c0 * per, M ? p->d_M + c0 * d * d : nullptr, p->d_out + c0 * t * t,
-                                        p->d_info + c0, p->s_comp);
+      int rc = hommx_solve_batch_device(p, nc, d_coef + c0 * per, M ? d_M + c0 * d * d : nullptr, d_out + c0 * t * t, d_info + c0, p->s_comp);
       if (rc != HOMMX_OK) return rc;
     }
     HIP_TRY(hipStreamSynchronize(p->s_comp));
-  } else {
-    HIP_TRY(hipMemcpy(p->d_coef, coef, sizeof(double) * n_cells * per, hipMemcpyHostToDevice));
-    int rc = hommx_solve_batch_device(p, n_cells, p->d_coef, M ? p->d_M : nullptr, p->d_out, p->d_info, nullptr);
+  } else {  // batches below two chunks: one copy in front of the kernels
+    HIP_TRY(hipMemcpy(d_coef, coef, sizeof(double) * n_cells * per, hipMemcpyHostToDevice));
+    int rc = hommx_solve_batch_device(p, n_cells, d_coef, d_M, d_out, d_info, nullptr);
     if (rc != HOMMX_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
   }
-  HIP_TRY(hipMemcpy(A_eff, p->d_out, sizeof(double) * n_cells * t * t, hipMemcpyDeviceToHost));
-  if (info) HIP_TRY(hipMemcpy(info, p->d_info, sizeof(int32_t) * n_cells, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(A_eff, d_out, sizeof(double) * n_cells * t * t, hipMemcpyDeviceToHost));
+  if (info) HIP_TRY(hipMemcpy(info, d_info, sizeof(int32_t) * n_cells, hipMemcpyDeviceToHost));
   return HOMMX_OK;
 }
 
 int hommx_solve_batch_two_phase_device(hommx_plan* p, int64_t n_cells, const uint8_t* d_mask, const double* d_values,
                                        const double* d_M, double* d_A_eff, int32_t* d_info, void* stream) {
-  if (!p) return fail(HOMMX_EINVAL, "null plan");
-  if (n_cells < 0) return fail(HOMMX_EINVAL, "negative n_cells");
-  if (n_cells == 0) return HOMMX_OK;
-  if (!d_mask || !d_values || !d_A_eff) return fail(HOMMX_EINVAL, "null mask / values / A_eff");
-  if (n_cells > 0x7fffffffll) return fail(HOMMX_EINVAL, "n_cells too large for one launch");
-  HIP_TRY(hipSetDevice(p->desc.device));
+  if (int rc = open_call(p, n_cells, d_mask && d_values && d_A_eff, "mask / values / A_eff", true); rc != GO) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (p->family == FAM_FUSED2D) {
     hommx::CoefSource src;
@@ -406,71 +410,27 @@ int hommx_solve_batch_two_phase_device(hommx_plan* p, int64_t n_cells, const uin
     HIP_TRY(hommx::launch_poisson2d_fused(d_values, d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st, src));
     return HOMMX_OK;
   }
-  // blocked and mesh families: expand on the device, chunk by chunk of at most 1 GiB of element stream
-  const int64_t per = p->n_el * p->n_comp;
-  int64_t chunk = (int64_t)((1ll << 27) / (per > 0 ? per : 1));
-  if (chunk < 1) chunk = 1;
-  if (chunk > n_cells) chunk = n_cells;
-  if (chunk > p->cap_expand) {
-    if (p->d_expand) hipFree(p->d_expand);
-    p->d_expand = nullptr;
-    p->cap_expand = 0;
-    HIP_TRY(hipMalloc(&p->d_expand, sizeof(double) * chunk * per));
-    p->cap_expand = chunk;
-  }
-  const int d = p->desc.dim, t = p->t;
-  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
-    const int64_t nc = (n_cells - c0 < chunk) ? n_cells - c0 : chunk;
-    HIP_TRY(hommx::launch_expand_two_phase(d_mask, d_values + c0 * 2 * p->n_comp, p->d_expand, p->n_el, p->n_comp, nc, st));
-    int rc = solve_stream(p, nc, p->d_expand, d_M ? d_M + c0 * d * d : nullptr, d_A_eff + c0 * t * t, d_info ? d_info + c0 : nullptr, st);
-    if (rc != HOMMX_OK) return rc;
-  }
-  return HOMMX_OK;
+  const int n_comp = p->ks.n_comp;
+  return expand_and_solve(p, n_cells, d_M, d_A_eff, d_info, st, [&](int64_t c0, int64_t nc, double* dst) {
+    return hommx::launch_expand_two_phase(d_mask, d_values + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st);
+  });
 }
 
 int hommx_solve_batch_two_phase(hommx_plan* p, int64_t n_cells, const uint8_t* mask, const double* values,
                                 const double* M, double* A_eff, int32_t* info) {
-  if (!p) return fail(HOMMX_EINVAL, "null plan");
-  if (n_cells < 0) return fail(HOMMX_EINVAL, "negative n_cells");
-  if (n_cells == 0) return HOMMX_OK;
-  if (!mask || !values || !A_eff) return fail(HOMMX_EINVAL, "null mask / values / A_eff");
-  HIP_TRY(hipSetDevice(p->desc.device));
-  const int d = p->desc.dim, t = p->t;
-  // The inputs are small (a mask + two values per cell): they are packed into ONE pinned block owned by the plan and travel in one
-  // asynchronous copy; the outputs come back the same way, and the call synchronises once.  No hipMalloc / hipFree per call.
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t o_mask = 0, o_val = up((size_t)p->n_el), o_M = o_val + up(sizeof(double) * n_cells * 2 * p->n_comp);
-  const size_t in_bytes = o_M + (M ? up(sizeof(double) * n_cells * d * d) : 0);
-  const size_t o_info = up(sizeof(double) * n_cells * t * t), out_bytes = o_info + up(sizeof(int32_t) * n_cells);
-  if (int rc = grow_pinned(p->pin_in, in_bytes)) return rc;
-  if (int rc = grow_pinned(p->pin_out, out_bytes)) return rc;
-  if (int rc = grow(p->dev_in, in_bytes)) return rc;
-  if (int rc = grow(p->dev_out, out_bytes)) return rc;
-  char* hin = static_cast<char*>(p->pin_in.p);
-  char* din = static_cast<char*>(p->dev_in.p);
-  char* dout = static_cast<char*>(p->dev_out.p);
-  memcpy(hin + o_mask, mask, (size_t)p->n_el);
-  memcpy(hin + o_val, values, sizeof(double) * n_cells * 2 * p->n_comp);
-  if (M) memcpy(hin + o_M, M, sizeof(double) * n_cells * d * d);
-  HIP_TRY(hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, nullptr));
-  int rc = hommx_solve_batch_two_phase_device(p, n_cells, reinterpret_cast<const uint8_t*>(din + o_mask), reinterpret_cast<const double*>(din + o_val),
-                                              M ? reinterpret_cast<const double*>(din + o_M) : nullptr, reinterpret_cast<double*>(dout),
-                                              reinterpret_cast<int32_t*>(dout + o_info), nullptr);
-  if (rc != HOMMX_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(p->pin_out.p, dout, out_bytes, hipMemcpyDeviceToHost, nullptr));
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  const char* hout = static_cast<const char*>(p->pin_out.p);
-  memcpy(A_eff, hout, sizeof(double) * n_cells * t * t);
-  if (info) memcpy(info, hout + o_info, sizeof(int32_t) * n_cells);
-  return HOMMX_OK;
+  if (int rc = open_call(p, n_cells, mask && values && A_eff, "mask / values / A_eff"); rc != GO) return rc;
+  const int d = p->desc.dim;
+  const HostIn in[] = {{mask, (size_t)p->n_el}, {values, sizeof(double) * n_cells * 2 * p->ks.n_comp}, {M, sizeof(double) * n_cells * d * d}};
+  return staged_call(p, n_cells, in, A_eff, info, [&](const void* const* d_in, double* d_A_eff, int32_t* d_info) {
+    return hommx_solve_batch_two_phase_device(p, n_cells, static_cast<const uint8_t*>(d_in[0]), static_cast<const double*>(d_in[1]),
+                                              static_cast<const double*>(d_in[2]), d_A_eff, d_info, nullptr);
+  });
 }
 
 int hommx_solve_batch_separable_device(hommx_plan* p, int64_t n_cells, int32_t family, int32_t n_q, const double* d_table,
                                        const double* d_weights, const double* d_params, const double* d_M, double* d_A_eff,
                                        int32_t* d_info, void* stream) {
-  if (!p) return fail(HOMMX_EINVAL, "null plan");
-  if (n_cells < 0) return fail(HOMMX_EINVAL, "negative n_cells");
-  if (n_cells == 0) return HOMMX_OK;
+  if (int rc = open_call(p, n_cells); rc != GO) return rc;
   if (p->desc.kind != HOMMX_KIND_POISSON_SCALAR && p->desc.kind != HOMMX_KIND_ELASTICITY_ISO)
     return fail(HOMMX_EINVAL, "separable samplers are defined for the scalar Poisson and the isotropic elasticity kinds");
   if (p->desc.kind == HOMMX_KIND_ELASTICITY_ISO && family != HOMMX_SAMPLER_AFFINE)
@@ -479,7 +439,6 @@ int hommx_solve_batch_separable_device(hommx_plan* p, int64_t n_cells, int32_t f
   if (!d_table || !d_params || !d_A_eff) return fail(HOMMX_EINVAL, "null table / params / A_eff");
   if (family == HOMMX_SAMPLER_RECIPROCAL && (n_q < 1 || !d_weights)) return fail(HOMMX_EINVAL, "reciprocal sampler needs n_q >= 1 and weights");
   if (n_cells > 0x7fffffffll) return fail(HOMMX_EINVAL, "n_cells too large for one launch");
-  HIP_TRY(hipSetDevice(p->desc.device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hommx::CoefSource src;
   src.mode = family == HOMMX_SAMPLER_AFFINE ? hommx::COEF_AFFINE : hommx::COEF_RECIPROCAL;
@@ -490,124 +449,62 @@ int hommx_solve_batch_separable_device(hommx_plan* p, int64_t n_cells, int32_t f
     HIP_TRY(hommx::launch_poisson2d_fused(d_params, d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st, src));
     return HOMMX_OK;
   }
-  // blocked and mesh families: expand on the device, chunk by chunk of at most 1 GiB of element stream
-  const int64_t per = p->n_el * p->n_comp;
-  int64_t chunk = (int64_t)((1ll << 27) / (per > 0 ? per : 1));
-  if (chunk < 1) chunk = 1;
-  if (chunk > n_cells) chunk = n_cells;
-  if (chunk > p->cap_expand) {
-    if (p->d_expand) hipFree(p->d_expand);
-    p->d_expand = nullptr;
-    p->cap_expand = 0;
-    HIP_TRY(hipMalloc(&p->d_expand, sizeof(double) * chunk * per));
-    p->cap_expand = chunk;
-  }
-  const int d = p->desc.dim, t = p->t;
-  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
-    const int64_t nc = (n_cells - c0 < chunk) ? n_cells - c0 : chunk;
-    HIP_TRY(hommx::launch_expand_separable(src, d_params + 2 * p->n_comp * c0, p->d_expand, p->n_el, p->n_comp, nc, st));
-    int rc = solve_stream(p, nc, p->d_expand, d_M ? d_M + c0 * d * d : nullptr, d_A_eff + c0 * t * t, d_info ? d_info + c0 : nullptr, st);
-    if (rc != HOMMX_OK) return rc;
-  }
-  return HOMMX_OK;
+  const int n_comp = p->ks.n_comp;
+  return expand_and_solve(p, n_cells, d_M, d_A_eff, d_info, st, [&](int64_t c0, int64_t nc, double* dst) {
+    return hommx::launch_expand_separable(src, d_params + 2 * n_comp * c0, dst, p->n_el, n_comp, nc, st);
+  });
 }
 
 int hommx_solve_batch_separable(hommx_plan* p, int64_t n_cells, int32_t family, int32_t n_q, const double* table,
                                 const double* weights, const double* params, const double* M, double* A_eff, int32_t* info) {
-  if (!p) return fail(HOMMX_EINVAL, "null plan");
-  if (n_cells < 0) return fail(HOMMX_EINVAL, "negative n_cells");
-  if (n_cells == 0) return HOMMX_OK;
-  if (!table || !params || !A_eff) return fail(HOMMX_EINVAL, "null table / params / A_eff");
+  if (int rc = open_call(p, n_cells, table && params && A_eff, "table / params / A_eff"); rc != GO) return rc;
   if (family != HOMMX_SAMPLER_AFFINE && family != HOMMX_SAMPLER_RECIPROCAL) return fail(HOMMX_EINVAL, "unknown sampler family %d", family);
   if (family == HOMMX_SAMPLER_RECIPROCAL && (n_q < 1 || !weights)) return fail(HOMMX_EINVAL, "reciprocal sampler needs n_q >= 1 and weights");
-  HIP_TRY(hipSetDevice(p->desc.device));
-  const int d = p->desc.dim, t = p->t;
+  const int d = p->desc.dim;
   const int64_t ntab = p->n_el * (family == HOMMX_SAMPLER_AFFINE ? 1 : n_q);
-  const bool has_w = weights && n_q > 0;
-  if (int rc = grow(p->st_table, sizeof(double) * ntab)) return rc;
-  if (int rc = grow(p->st_values, sizeof(double) * n_cells * 2 * p->n_comp)) return rc;
-  if (int rc = grow(p->st_out, sizeof(double) * n_cells * t * t)) return rc;
-  if (int rc = grow(p->st_info, sizeof(int32_t) * n_cells)) return rc;
-  if (has_w)
-    if (int rc = grow(p->st_w, sizeof(double) * n_q)) return rc;
-  if (M)
-    if (int rc = grow(p->st_M, sizeof(double) * n_cells * d * d)) return rc;
-  HIP_TRY(hipMemcpyAsync(p->st_table.p, table, sizeof(double) * ntab, hipMemcpyHostToDevice, nullptr));
-  HIP_TRY(hipMemcpyAsync(p->st_values.p, params, sizeof(double) * n_cells * 2 * p->n_comp, hipMemcpyHostToDevice, nullptr));
-  if (has_w) HIP_TRY(hipMemcpyAsync(p->st_w.p, weights, sizeof(double) * n_q, hipMemcpyHostToDevice, nullptr));
-  if (M) HIP_TRY(hipMemcpyAsync(p->st_M.p, M, sizeof(double) * n_cells * d * d, hipMemcpyHostToDevice, nullptr));
-  int rc = hommx_solve_batch_separable_device(p, n_cells, family, n_q, static_cast<const double*>(p->st_table.p),
-                                              has_w ? static_cast<const double*>(p->st_w.p) : nullptr, static_cast<const double*>(p->st_values.p),
-                                              M ? static_cast<const double*>(p->st_M.p) : nullptr, static_cast<double*>(p->st_out.p),
-                                              static_cast<int32_t*>(p->st_info.p), nullptr);
-  if (rc != HOMMX_OK) return rc;
-  HIP_TRY(hipMemcpy(A_eff, p->st_out.p, sizeof(double) * n_cells * t * t, hipMemcpyDeviceToHost));
-  if (info) HIP_TRY(hipMemcpy(info, p->st_info.p, sizeof(int32_t) * n_cells, hipMemcpyDeviceToHost));
-  return HOMMX_OK;
+  const HostIn in[] = {{table, sizeof(double) * ntab},
+                       {n_q > 0 ? weights : nullptr, sizeof(double) * (n_q > 0 ? n_q : 0)},
+                       {params, sizeof(double) * n_cells * 2 * p->ks.n_comp},
+                       {M, sizeof(double) * n_cells * d * d}};
+  return staged_call(p, n_cells, in, A_eff, info, [&](const void* const* d_in, double* d_A_eff, int32_t* d_info) {
+    return hommx_solve_batch_separable_device(p, n_cells, family, n_q, static_cast<const double*>(d_in[0]), static_cast<const double*>(d_in[1]),
+                                              static_cast<const double*>(d_in[2]), static_cast<const double*>(d_in[3]), d_A_eff, d_info, nullptr);
+  });
 }
 
 int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* coef, const double* M, double* A_eff,
                                  double* correctors, int32_t* info) {
-  if (!p) return fail(HOMMX_EINVAL, "null plan");
-  if (n_cells < 0) return fail(HOMMX_EINVAL, "negative n_cells");
-  if (n_cells == 0) return HOMMX_OK;
-  if (!coef || !A_eff || !correctors) return fail(HOMMX_EINVAL, "null coef / A_eff / correctors");
-  HIP_TRY(hipSetDevice(p->desc.device));
-  if (p->family != FAM_MESH && p->family != FAM_MESH_TREE && !p->ws) {
+  if (int rc = open_call(p, n_cells, coef && A_eff && correctors, "coef / A_eff / correctors"); rc != GO) return rc;
+  if (p->family == FAM_FUSED2D && !p->ws) {  // the fused 2D kernel returns no correctors: the blocked family does
     int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
     if (rc != 0) return fail(rc, "blocked path: %s", hommx::blocked_last_error());
   }
-  const int d = p->desc.dim, t = p->t;
-  const int bs = (p->desc.kind >= HOMMX_KIND_ELASTICITY_ISO) ? d : 1;
-  long long nn = 1;
-  if (p->family == FAM_MESH)
-    nn = hommx::mesh_num_nodes(p->mesh);
-  else if (p->family == FAM_MESH_TREE)
-    nn = hommx::mesh_tree_num_nodes(p->mtree);
-  else
-    for (int k = 0; k < d; ++k) nn *= p->desc.n_micro;
-  double *d_coef = nullptr, *d_M = nullptr, *d_out = nullptr, *d_corr = nullptr;
-  int32_t* d_info = nullptr;
-  auto cleanup = [&]() {
-    if (d_coef) hipFree(d_coef);
-    if (d_M) hipFree(d_M);
-    if (d_out) hipFree(d_out);
-    if (d_corr) hipFree(d_corr);
-    if (d_info) hipFree(d_info);
-  };
-#define HIP_TRY_C(expr)                                                                             \
-  do {                                                                                              \
-    hipError_t e__ = (expr);                                                                        \
-    if (e__ != hipSuccess) {                                                                        \
-      cleanup();                                                                                    \
-      return fail(e__ == hipErrorOutOfMemory ? HOMMX_ENOMEM : HOMMX_EHIP, "%s failed: %s", #expr,   \
-                  hipGetErrorString(e__));                                                          \
-    }                                                                                               \
-  } while (0)
-  const size_t ncoef = sizeof(double) * n_cells * p->n_el * p->n_comp, ncorr = sizeof(double) * n_cells * t * nn * bs;
-  HIP_TRY_C(hipMalloc(&d_coef, ncoef));
-  HIP_TRY_C(hipMalloc(&d_out, sizeof(double) * n_cells * t * t));
-  HIP_TRY_C(hipMalloc(&d_corr, ncorr));
-  HIP_TRY_C(hipMalloc(&d_info, sizeof(int32_t) * n_cells));
-  HIP_TRY_C(hipMemcpy(d_coef, coef, ncoef, hipMemcpyHostToDevice));
+  const int d = p->desc.dim, t = p->ks.t;
+  const long long nn = p->family == FAM_MESH ? hommx::mesh_num_nodes(p->mesh) : p->ws->G.nn;
+  // the call's own device buffers, freed when it returns: the correctors can run to gigabytes, the plan keeps none of them
+  struct CallBufs {
+    Buf coef, M, out, corr, info;
+    ~CallBufs() {
+      for (Buf* b : {&coef, &M, &out, &corr, &info}) b->release();
+    }
+  } b;
+  const size_t ncoef = sizeof(double) * n_cells * p->n_el * p->ks.n_comp, ncorr = sizeof(double) * n_cells * t * nn * p->ks.bs;
+  if (int rc = grow(b.coef, ncoef)) return rc;
+  if (int rc = grow(b.out, sizeof(double) * n_cells * t * t)) return rc;
+  if (int rc = grow(b.corr, ncorr)) return rc;
+  if (int rc = grow(b.info, sizeof(int32_t) * n_cells)) return rc;
+  HIP_TRY(hipMemcpy(b.coef.p, coef, ncoef, hipMemcpyHostToDevice));
   if (M) {
-    HIP_TRY_C(hipMalloc(&d_M, sizeof(double) * n_cells * d * d));
-    HIP_TRY_C(hipMemcpy(d_M, M, sizeof(double) * n_cells * d * d, hipMemcpyHostToDevice));
+    if (int rc = grow(b.M, sizeof(double) * n_cells * d * d)) return rc;
+    HIP_TRY(hipMemcpy(b.M.p, M, sizeof(double) * n_cells * d * d, hipMemcpyHostToDevice));
   }
-  const bool mesh = p->family == FAM_MESH || p->family == FAM_MESH_TREE;
-  int rc = p->family == FAM_MESH        ? hommx::mesh_solve(p->mesh, n_cells, d_coef, d_M, d_out, d_info, nullptr, d_corr)
-           : p->family == FAM_MESH_TREE ? hommx::mesh_tree_solve(p->mtree, n_cells, d_coef, d_M, d_out, d_info, nullptr, d_corr)
-                                        : hommx::blocked_solve(p->ws, n_cells, d_coef, d_M, d_out, d_info, nullptr, d_corr);
-  if (rc != 0) {
-    cleanup();
-    return fail(rc, "%s", mesh ? hommx::mesh_last_error() : hommx::blocked_last_error());
-  }
-  HIP_TRY_C(hipDeviceSynchronize());
-  HIP_TRY_C(hipMemcpy(A_eff, d_out, sizeof(double) * n_cells * t * t, hipMemcpyDeviceToHost));
-  HIP_TRY_C(hipMemcpy(correctors, d_corr, ncorr, hipMemcpyDeviceToHost));
-  if (info) HIP_TRY_C(hipMemcpy(info, d_info, sizeof(int32_t) * n_cells, hipMemcpyDeviceToHost));
-#undef HIP_TRY_C
-  cleanup();
+  int rc = route_solve(p, n_cells, static_cast<const double*>(b.coef.p), static_cast<const double*>(b.M.p), static_cast<double*>(b.out.p),
+                       static_cast<int32_t*>(b.info.p), nullptr, static_cast<double*>(b.corr.p));
+  if (rc != HOMMX_OK) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(A_eff, b.out.p, sizeof(double) * n_cells * t * t, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(correctors, b.corr.p, ncorr, hipMemcpyDeviceToHost));
+  if (info) HIP_TRY(hipMemcpy(info, b.info.p, sizeof(int32_t) * n_cells, hipMemcpyDeviceToHost));
   return HOMMX_OK;
 }
 

@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/hommx_hip.h"
@@ -936,20 +937,26 @@ static void ws_read_knobs(BlockedWorkspace* ws) {
   if (const char* e = getenv("HOMMX_TILE_SB")) ws->tile_sb = atoi(e);
 }
 
+// the nested-dissection route on the workspace's tree
+static int ws_take_tree(BlockedWorkspace* ws) {
+  if (int rc = mf_plan_from_tree(ws, false, &ws->mf)) return rc;
+  // the products of this route are tall and thin or lower-triangular: with the super-block tile order the 64 x 64 tiles (six workgroups
+  // per CU) are never slower than the 128 x 128 ones any more -- C4 +2 %, 3D elasticity 20^3 +2 %, scalar 24^3 -1.5 %
+  if (!getenv("HOMMX_GEMM128_MIN")) ws->gemm128_min = 1 << 30;
+  return 0;
+}
+
 int blocked_workspace_create(BlockedWorkspace** out, int dim, int n, int kind) {
   *out = nullptr;
   BlockedWorkspace* ws = new BlockedWorkspace();
   Geo& G = ws->G;
+  const KindSizes ks = kind_sizes(dim, kind);
   G.dim = dim;
   G.n = n;
   G.kind = kind;
-  const bool el = kind >= HOMMX_KIND_ELASTICITY_ISO;
-  G.bs = el ? dim : 1;
-  G.t = el ? dim * (dim + 1) / 2 : dim;
-  G.ncomp = kind == HOMMX_KIND_POISSON_SCALAR ? 1
-            : kind == HOMMX_KIND_POISSON_MATRIX ? dim * (dim + 1) / 2
-            : kind == HOMMX_KIND_ELASTICITY_ISO ? 2
-                                                : G.t * (G.t + 1) / 2;
+  G.bs = ks.bs;
+  G.t = ks.t;
+  G.ncomp = ks.n_comp;
   G.nn = dim == 2 ? n * n : n * n * n;
   G.npl = dim == 2 ? n : n * n;
   G.b = G.bs * G.npl;
@@ -974,31 +981,35 @@ int blocked_workspace_create(BlockedWorkspace** out, int dim, int n, int kind) {
   }
   // (a threshold from the environment below 65 takes effect only together with HOMMX_NO_SMALL_FUSED: A/B runs)
   if (ws->mf_min_b > 0 && G.b >= ws->mf_min_b && (G.b > 64 || !ws->small_fused || (!mf_env && G.b > 48))) {
-    if (int rc = mf_plan_create(&ws->mf, G)) {
-      delete ws;
+    mf_tree_structured(G, &ws->tree);
+    if (int rc = ws_take_tree(ws)) {
+      blocked_workspace_destroy(ws);
       return rc;
     }
-    // the products of this route are tall and thin or lower-triangular: with the super-block tile order the 64 x 64 tiles (six workgroups
-    // per CU) are never slower than the 128 x 128 ones any more -- C4 +2 %, 3D elasticity 20^3 +2 %, scalar 24^3 -1.5 %
-    if (!getenv("HOMMX_GEMM128_MIN")) ws->gemm128_min = 1 << 30;
   }
   *out = ws;
   return 0;
 }
 
-int blocked_workspace_create_mesh(BlockedWorkspace** out, const Geo& G, MfPlan* mf) {
+int blocked_workspace_create_mesh(BlockedWorkspace** out, const Geo& G, MfTree&& tree, const MeshAsm& a, void* tables) {
   *out = nullptr;
   BlockedWorkspace* ws = new BlockedWorkspace();
   ws->G = G;
+  ws->tree = std::move(tree);
+  ws->mesh = a;
+  ws->mesh_tables = tables;
   ws_read_knobs(ws);
-  ws->mf = mf;  // owned by the workspace from here on
-  if (!getenv("HOMMX_GEMM128_MIN")) ws->gemm128_min = 1 << 30;  // as for the structured multifrontal plans (blocked_workspace_create)
+  if (int rc = ws_take_tree(ws)) {
+    blocked_workspace_destroy(ws);
+    return rc;
+  }
   *out = ws;
   return 0;
 }
 
 const char* blocked_route_name(const BlockedWorkspace* ws) {
   if (!ws) return "blocked";
+  if (ws->mesh_tables) return "mesh_multifrontal";
   if (ws->mf) return "multifrontal";
   if (ws->G.b <= 64 && ws->small_fused) return (ws->G.b <= 48 && ws->small_waves != 2 && ws->small_waves != 4) ? "small_wave" : "small_fused";
   return "blocked";
@@ -1010,7 +1021,15 @@ const char* blocked_route_detail(BlockedWorkspace* ws) {
   if (ws->detail.empty()) {
     char buf[512];
     const Geo& G = ws->G;
-    if (ws->mf) ws->detail = mf_describe(ws, ws->mf);
+    if (ws->mesh_tables) {
+      const MfStats s = mf_stats(ws->mf);
+      snprintf(buf, sizeof(buf),
+               "mesh_multifrontal: coordinate bisection of %lld nodes, %d fronts in %d groups (largest s = %d, r = %d unknowns), arena %.1f MB per "
+               "cell, %d group(s) on k_mf_front, %d coupling codes; K1 k_mesh_assemble + k_mesh_c0; ",
+               (long long)G.nn, s.nfronts, s.ngroups, s.max_s, s.max_r, 8e-6 * s.arena_per_cell, s.front_groups, G.ncode);
+      ws->detail = std::string(buf) + mf_describe(ws, ws->mf);
+    } else if (ws->mf)
+      ws->detail = mf_describe(ws, ws->mf);
     else if (G.b <= 64 && ws->small_fused) {
       snprintf(buf, sizeof(buf), "%s: one launch after K1 (k_assemble_reg), plane block b = %d, f64 MFMA 16x16x4 tiles in %s", blocked_route_name(ws), G.b,
                (G.b <= 48 && ws->small_waves != 2 && ws->small_waves != 4) ? "registers (one wavefront per macro cell)" : "LDS (several waves per macro cell)");
@@ -1058,6 +1077,7 @@ void blocked_workspace_destroy(BlockedWorkspace* ws) {
   if (!ws) return;
   if (ws->mf) mf_plan_destroy(ws->mf);
   if (ws->mf_keep) mf_plan_destroy(ws->mf_keep);
+  if (ws->mesh_tables) (void)hipFree(ws->mesh_tables);
   for (auto& kv : ws->tilemaps) (void)hipFree(kv.second);
   ws_free(ws);
   delete ws;
@@ -1535,9 +1555,10 @@ int blocked_reserve(BlockedWorkspace* ws, long long n_cells) {
 int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, const double* d_M, double* d_out,
                   int32_t* d_info, hipStream_t st, double* d_corr) {
   if (ws->mf && !d_corr) return mf_solve(ws, ws->mf, ncells, d_coef, d_M, d_out, d_info, st);  // nested dissection (multifrontal.hip)
-  if (ws->mf && ws->mf_corr) {  // correctors on the same route: a second plan whose fronts keep their factors for the back substitution
+  // correctors on the same route: a second plan whose fronts keep their factors for the back substitution (a mesh has no planes to take)
+  if (ws->mf && (ws->mf_corr || ws->mesh_tables)) {
     if (!ws->mf_keep)
-      if (int rc = mf_plan_create(&ws->mf_keep, ws->G, true)) return rc;
+      if (int rc = mf_plan_from_tree(ws, true, &ws->mf_keep)) return rc;
     return mf_solve(ws, ws->mf_keep, ncells, d_coef, d_M, d_out, d_info, st, d_corr);
   }
   if (int rc = ws_reserve(ws, ncells, d_corr != nullptr)) return rc;

@@ -10,10 +10,19 @@
 #include <vector>
 
 #include "geo.h"
+#include "mesh_tree.h"
 
 namespace hommx {
 
 struct MfPlan;  // multifrontal.hip
+
+// Symbolic input of a nested-dissection plan, from either source (the box dissection of the n^d torus, or the coordinate bisection of an
+// unstructured mesh: mesh_tree.hip): the supernode tree and the coupling graph.  Nothing in it is geometric.
+struct MfTree {
+  std::vector<std::vector<int>> sn_nodes;     // nodes of every supernode; children come before their parent, the root is the last
+  std::vector<std::vector<int>> sn_children;  // at most two per supernode (MfChild has two slots)
+  std::vector<int> nb_ptr, nb_node, nb_code;  // CSR over nodes v: every node w coupled with v (v included) and the code of (row w, column v)
+};
 
 struct BlockedWorkspace {
   Geo G;
@@ -32,10 +41,14 @@ struct BlockedWorkspace {
   // corrector mode: per eliminated plane the inverse Schur block, the arrow block and the load rows are kept
   long long hchunk = 0;
   double *hS = nullptr, *hW = nullptr, *hR = nullptr, *Xa = nullptr, *Xb = nullptr, *Y = nullptr;
-  // nested-dissection route (3D, large plane blocks): symbolic analysis + arena, owned by multifrontal.hip
+  // nested-dissection route (large plane blocks, and every mesh plan of the tree route): the tree both plans are built from (mf_plan_from_tree)
+  MfTree tree;
   MfPlan* mf = nullptr;
   MfPlan* mf_keep = nullptr;   // corrector plan of the same route (fronts keep their factors), created by the first corrector call
-  bool mf_corr = true;         // HOMMX_MF_CORR=0: correctors of multifrontal plans take the plane elimination (A/B runs)
+  bool mf_corr = true;         // HOMMX_MF_CORR=0: correctors of structured multifrontal plans take the plane elimination (A/B runs)
+  // mesh plans of the tree route (blocked_workspace_create_mesh): K1 is the mesh assembly on these tables, one device block owned here
+  MeshAsm mesh{};
+  void* mesh_tables = nullptr;  // non-null marks a mesh workspace
   int mf_min_b = 192;          // smallest plane block b routed to the multifrontal elimination (set per dim / unknowns per node when the
                                // workspace is created; HOMMX_MF_MIN_B overrides, 0: never)
   bool mf_no_border_split = false;  // HOMMX_MF_NO_BORDER_SPLIT (A/B runs)
@@ -96,25 +109,17 @@ void invert(const Ctx& c, double* S, int off, int size, double* tmp);
 
 extern thread_local std::string g_berr;
 
-// Symbolic input of a nested-dissection plan, from either source (the box dissection of the n^d torus, or the coordinate bisection of an
-// unstructured mesh: mesh_tree.hip): the supernode tree and the coupling graph.  Nothing in it is geometric.
-struct MfTree {
-  std::vector<std::vector<int>> sn_nodes;     // nodes of every supernode; children come before their parent, the root is the last
-  std::vector<std::vector<int>> sn_children;  // at most two per supernode (MfChild has two slots)
-  std::vector<int> nb_ptr, nb_node, nb_code;  // CSR over nodes v: every node w coupled with v (v included) and the code of (row w, column v)
-};
 // supernode tree of the n^d torus (TreeBuilder: two planes per periodic direction, one per open one) with its stencil couplings
 void mf_tree_structured(const Geo& G, MfTree* T);
 // leaf size and ring-split depth of both tree builders (HOMMX_MF_LEAF, HOMMX_MF_SPLIT_DEPTH)
 int mf_leaf_max(int dim, int bs);
 int mf_split_depth();
 
-// multifrontal.hip
-int mf_plan_create(MfPlan** out, const Geo& G, bool keep = false);
-// host half of mf_plan_create on any tree: boundaries, heights, groups, arena, flop model and the index tables (no GPU); the gauge is the node of
-// highest elimination rank in the root.  G supplies nn, bs, ncode.  mf_plan_upload moves the tables to the current device.
+// multifrontal.hip: the plan of ws->tree on the current device (keep: the corrector plan, every front keeps its factors)
+int mf_plan_from_tree(BlockedWorkspace* ws, bool keep, MfPlan** out);
+// its host half on any tree: boundaries, heights, groups, arena, flop model and the index tables (no GPU); the gauge is the node of highest
+// elimination rank in the root.  G supplies nn, bs, ncode.
 int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep);
-int mf_plan_upload(MfPlan* P);
 // what the host analysis found: fronts, groups, the largest front (s + r, unknowns), the largest (s, r) pair, arena doubles per cell, groups on
 // k_mf_front
 struct MfStats {
@@ -123,8 +128,6 @@ struct MfStats {
   double flops;
 };
 MfStats mf_stats(const MfPlan* p);
-struct MeshAsm;
-void mf_set_mesh(MfPlan* p, const MeshAsm* a);  // K1 of the plan: the mesh assembly on these tables (mesh_tree.hip)
 void mf_plan_destroy(MfPlan* p);
 double mf_flops_per_cell(const MfPlan* p);
 std::string mf_describe(const BlockedWorkspace* ws, const MfPlan* p);  // one line: tree, stages, streams, tile sizes of the dense kernels
@@ -132,11 +135,12 @@ int mf_reserve(BlockedWorkspace* ws, MfPlan* P, long long ncells, bool ahead);
 // effective tensors, and with the corrector plan (keep = true) and d_corr != nullptr the correctors [cell][t][n^d bs] as well
 int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
              hipStream_t st, double* d_corr = nullptr);
-// mesh_tree.hip: K1 of a mesh plan -- Kst, Brhs and C0 of `nc` cells in the layout launch_assembly writes, from the element stream
-void launch_mesh_assembly(const MeshAsm& a, const double* coef, const double* Mm, long long nc, hipStream_t st, double* Kst, double* Brhs,
-                          double* C0);
 // remove the mean of every component of nc x t corrector fields (blocked.hip)
 void launch_center_corr(BlockedWorkspace* ws, double* corr, long long nc, hipStream_t st);
+// workspace of a mesh plan of the tree route (mesh_tree_workspace): G (nn = n_nodes, ncode = most coupling codes of a node, n unused), the
+// tree, and the assembly tables on the device, which the workspace owns from here on (also on failure); the same development knobs as
+// blocked_workspace_create
+int blocked_workspace_create_mesh(BlockedWorkspace** out, const Geo& G, MfTree&& tree, const MeshAsm& a, void* tables);
 // K1 of the blocked family (stencil rows, loads, C0 of `nc` cells into the given buffers), shared by both eliminations: each route owns
 // its buffers (a plan may serve effective tensors on one route and correctors on the other, with different chunk sizes)
 void launch_assembly(BlockedWorkspace* ws, const double* coef, const double* Mm, long long nc, hipStream_t st, double* Kst, double* Brhs,

@@ -3,7 +3,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/hommx_hip.h"
+
 namespace hommx {
+
+// unknowns per node, tensor size and coefficient components per element of a problem kind (include/hommx_hip.h)
+struct KindSizes {
+  int bs, t, n_comp;
+};
+constexpr KindSizes kind_sizes(int dim, int kind) {
+  const int te = dim * (dim + 1) / 2;  // elasticity (Voigt) tensor size
+  return kind == HOMMX_KIND_POISSON_SCALAR   ? KindSizes{1, dim, 1}
+         : kind == HOMMX_KIND_POISSON_MATRIX ? KindSizes{1, dim, te}
+         : kind == HOMMX_KIND_ELASTICITY_ISO ? KindSizes{dim, te, 2}
+                                             : KindSizes{dim, te, te * (te + 1) / 2};
+}
 
 // Where the per-element coefficient of a scalar Poisson cell comes from (device samplers).
 //   STREAM      coef[cell][n_el]: element means sampled by the caller
@@ -55,18 +69,14 @@ namespace hommx {
 // blocked.hip: generic block-cyclic path (any dim / kind / n); host-orchestrated batched kernels.
 struct BlockedWorkspace;
 int blocked_workspace_create(BlockedWorkspace** out, int dim, int n, int kind);
-// workspace of a mesh plan of the tree route (mesh_tree.hip): its Geo (nn = n_nodes, ncode = most coupling codes of a node, n unused) and its
-// multifrontal plan, which the workspace then owns; the same development knobs as blocked_workspace_create
-struct Geo;
-struct MfPlan;
-int blocked_workspace_create_mesh(BlockedWorkspace** out, const Geo& G, MfPlan* mf);
 void blocked_workspace_destroy(BlockedWorkspace* ws);
 int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, const double* d_M,
                   double* d_out, int32_t* d_info, hipStream_t stream, double* d_corr = nullptr);
 const char* blocked_last_error();
 // allocate the workspace of the route for batches of up to n_cells (what the first solve would otherwise do)
 int blocked_reserve(BlockedWorkspace* ws, long long n_cells);
-// "small_wave" (b <= 48), "small_fused" (48 < b <= 64) or "blocked": the route blocked_solve takes for effective tensors
+// "small_wave" (b <= 48), "small_fused" (48 < b <= 64), "blocked", "multifrontal" or, on a mesh, "mesh_multifrontal": the route
+// blocked_solve takes for effective tensors
 const char* blocked_route_name(const BlockedWorkspace* ws);
 const char* blocked_route_detail(BlockedWorkspace* ws);
 // dense flops one micro-cell solve executes on this route, by the route's own model (multifrontal: sum over the fronts of

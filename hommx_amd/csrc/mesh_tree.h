@@ -1,7 +1,8 @@
 // mesh_tree.h -- internal interface of the tree route of the mesh family (mesh_tree.hip): cell problems on an
 // unstructured periodic micro mesh whose frontal width exceeds HOMMX_MESH_MAX_FRONT (or any mesh with HOMMX_MESH_FLAG_TREE), solved by
-// the nested-dissection engine of multifrontal.hip.  Only three things are the mesh's own: the tree (recursive coordinate bisection with
-// vertex separators), the coupling codes (position of a neighbour in a node's sorted adjacency list) and K1 (k_mesh_assemble).
+// the nested-dissection engine of multifrontal.hip as a plan of the blocked family.  Only three things are the mesh's own: the tree
+// (recursive coordinate bisection with vertex separators), the coupling codes (position of a neighbour in a node's sorted adjacency list)
+// and K1 (k_mesh_assemble); the workspace (blocked_workspace_create_mesh) keeps the tree and the assembly tables.
 //
 // The symbolic phase is host code: hommx_mesh_analyze_tree and the argument checks of hommx_plan_create_mesh run it without a GPU.
 #pragma once
@@ -22,7 +23,12 @@ struct MeshAsm {
   const int* self_code;  // [nn] code of (i, i)
 };
 
-struct MeshTreePlan;
+// K1 of a mesh plan -- Kst, Brhs and C0 of `nc` cells in the layout launch_assembly (blocked.hip) writes, from the element stream
+void launch_mesh_assembly(const MeshAsm& a, const double* coef, const double* Mm, long long nc, hipStream_t st, double* Kst, double* Brhs,
+                          double* C0);
+
+struct MeshTreePlan;  // host-side analysis: geometry, tree, coupling codes, assembly tables
+struct BlockedWorkspace;
 
 // what hommx_mesh_analyze_tree reports
 struct MeshTreeInfo {
@@ -30,18 +36,13 @@ struct MeshTreeInfo {
   double flops;
 };
 
-// Validates the descriptor (mesh_check) and runs the symbolic phase: tree, codes, assembly tables, the host half of the multifrontal plan.
-// out == nullptr: analysis only.  supernode_of_node [n_nodes] / parent [n_fronts] may be null.  Errors: mesh_last_error().
+// Validates the descriptor (mesh_check) and runs the symbolic phase: tree, codes, assembly tables; with `info`, the host half of the
+// multifrontal plan as well.  out == nullptr: analysis only.  supernode_of_node [n_nodes] / parent [n_fronts] may be null.  Errors:
+// mesh_last_error().
 int mesh_tree_analyze(const hommx_mesh_desc* d, MeshTreePlan** out, MeshTreeInfo* info, int32_t* supernode_of_node, int32_t* parent);
-// device tables and the workspace (the caller has selected the plan's device)
-int mesh_tree_upload(MeshTreePlan* m);
+// the plan's workspace of the blocked family on the current device: the assembly tables uploaded, the tree moved in, its multifrontal plan
+// built; `m` keeps nothing the workspace needs
+int mesh_tree_workspace(MeshTreePlan* m, BlockedWorkspace** out);
 void mesh_tree_destroy(MeshTreePlan* m);
-double mesh_tree_flops_per_cell(const MeshTreePlan* m);
-int64_t mesh_tree_num_nodes(const MeshTreePlan* m);
-const char* mesh_tree_route_detail(MeshTreePlan* m);
-int mesh_tree_reserve(MeshTreePlan* m, long long n_cells);
-// as mesh_solve (mesh_front.h): coef[cell][el][n_comp], M or null -> out[cell][t][t], info; d_corr: correctors [cell][t][n_nodes bs]
-int mesh_tree_solve(MeshTreePlan* m, long long ncells, const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
-                    hipStream_t stream, double* d_corr = nullptr);
 
 }  // namespace hommx

@@ -18,9 +18,10 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
+#include <memory>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "blocked_internal.h"
@@ -32,17 +33,10 @@
 namespace hommx {
 
 struct MeshTreePlan {
-  int dim = 0, kind = 0, bs = 1, t = 0, n_comp = 0;
-  int64_t n_nodes = 0, n_el = 0;
   Geo G{};
   MfTree tree;
-  MfPlan* mf = nullptr;  // host analysis, then owned by ws
   std::vector<double> grads, vol;
   std::vector<int> cptr, centry, self_code;
-  MeshAsm dev{};
-  void* d_tables = nullptr;
-  BlockedWorkspace* ws = nullptr;
-  std::string detail;
 };
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -315,23 +309,10 @@ int mesh_tree_analyze(const hommx_mesh_desc* d, MeshTreePlan** out, MeshTreeInfo
   const int dim = d->dim, nv = dim + 1;
   const int n = (int)d->n_nodes, ne = (int)d->n_el;
   if (ne >= (1 << 27)) return mesh_error(HOMMX_EINVAL, "the tree route takes fewer than 2^27 elements, got " + std::to_string(ne));
-  MeshTreePlan* m = new (std::nothrow) MeshTreePlan();
+  std::unique_ptr<MeshTreePlan> m(new (std::nothrow) MeshTreePlan());
   if (!m) return mesh_error(HOMMX_ENOMEM, "host allocation failed");
-  struct Guard {
-    MeshTreePlan*& p;
-    ~Guard() {
-      if (p && p->mf) mf_plan_destroy(p->mf);
-      delete p;
-    }
-  } guard{m};
-  m->dim = dim;
-  m->kind = d->kind;
-  m->bs = d->kind >= HOMMX_KIND_ELASTICITY_ISO ? dim : 1;
-  m->t = d->kind >= HOMMX_KIND_ELASTICITY_ISO ? dim * (dim + 1) / 2 : dim;
-  m->n_comp = d->kind == 0 ? 1 : d->kind == 1 ? dim * (dim + 1) / 2 : d->kind == 2 ? 2 : m->t * (m->t + 1) / 2;
-  m->n_nodes = n;
-  m->n_el = ne;
-  const int bs = m->bs;
+  const KindSizes ks = kind_sizes(dim, d->kind);
+  const int bs = ks.bs;
 
   // coupling codes: position in the sorted list {i} u adj(i)
   std::vector<int> lptr(n + 1, 0), lst;
@@ -393,13 +374,12 @@ int mesh_tree_analyze(const hommx_mesh_desc* d, MeshTreePlan** out, MeshTreeInfo
   G.dim = dim;
   G.n = 0;
   G.bs = bs;
-  G.t = m->t;
+  G.t = ks.t;
   G.kind = d->kind;
-  G.ncomp = m->n_comp;
+  G.ncomp = ks.n_comp;
   G.nn = n;
   G.ncode = ncode;
   G.n_el = ne;
-  if (int rc = mf_plan_build(&m->mf, G, T, false)) return mesh_error(rc, g_berr);
 
   const int nsn = (int)T.sn_nodes.size();
   if (supernode_of_node)
@@ -410,8 +390,11 @@ int mesh_tree_analyze(const hommx_mesh_desc* d, MeshTreePlan** out, MeshTreeInfo
     for (int k = 0; k < nsn; ++k)
       for (int c : T.sn_children[k]) parent[c] = k;
   }
-  if (info) {
-    const MfStats s = mf_stats(m->mf);
+  if (info) {  // the host half of the plan mesh_tree_workspace builds
+    MfPlan* P = nullptr;
+    if (int rc = mf_plan_build(&P, G, T, false)) return mesh_error(rc, g_berr);
+    const MfStats s = mf_stats(P);
+    mf_plan_destroy(P);
     info->n_fronts = s.nfronts;
     info->n_groups = s.ngroups;
     info->max_front = s.max_front;
@@ -444,19 +427,19 @@ int mesh_tree_analyze(const hommx_mesh_desc* d, MeshTreePlan** out, MeshTreeInfo
   }
   m->grads.swap(geo.grads);
   m->vol.swap(geo.vol);
-  *out = m;
-  m = nullptr;  // released from the guard
+  *out = m.release();
   return HOMMX_OK;
 }
 
-int mesh_tree_upload(MeshTreePlan* m) {
+int mesh_tree_workspace(MeshTreePlan* m, BlockedWorkspace** out) {
+  *out = nullptr;
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
   struct Piece {
     const void* src;
     size_t bytes;
     const void** dst;
   };
-  MeshAsm& A = m->dev;
+  MeshAsm A{m->G.dim, m->G.kind, m->G.nn, m->G.n_el, m->G.ncode};
   Piece pcs[] = {
       {m->grads.data(), sizeof(double) * m->grads.size(), (const void**)&A.grads},
       {m->vol.data(), sizeof(double) * m->vol.size(), (const void**)&A.vol},
@@ -466,73 +449,25 @@ int mesh_tree_upload(MeshTreePlan* m) {
   };
   size_t total = 0;
   for (const Piece& p : pcs) total += up(p.bytes);
-  hipError_t e = hipMalloc(&m->d_tables, total);
+  void* tables = nullptr;
+  hipError_t e = hipMalloc(&tables, total);
   if (e != hipSuccess) return mesh_error(e == hipErrorOutOfMemory ? HOMMX_ENOMEM : HOMMX_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e));
   std::vector<char> host(total, 0);
   size_t off = 0;
   for (const Piece& p : pcs) {
     if (p.bytes) std::copy((const char*)p.src, (const char*)p.src + p.bytes, host.data() + off);
-    *p.dst = (const char*)m->d_tables + off;
+    *p.dst = (const char*)tables + off;
     off += up(p.bytes);
   }
-  e = hipMemcpy(m->d_tables, host.data(), total, hipMemcpyHostToDevice);
-  if (e != hipSuccess) return mesh_error(HOMMX_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-  A.dim = m->dim;
-  A.kind = m->kind;
-  A.nn = (int)m->n_nodes;
-  A.n_el = (int)m->n_el;
-  A.ncode = m->G.ncode;
-  if (int rc = mf_plan_upload(m->mf)) return mesh_error(rc, g_berr.empty() ? "multifrontal tables: upload failed" : g_berr);
-  mf_set_mesh(m->mf, &m->dev);
-  const MfStats s = mf_stats(m->mf);
-  if (int rc = blocked_workspace_create_mesh(&m->ws, m->G, m->mf)) return mesh_error(rc, g_berr);
-  m->mf = nullptr;  // the workspace owns it now
-  char buf[512];
-  snprintf(buf, sizeof(buf),
-           "mesh_multifrontal: coordinate bisection of %lld nodes, %d fronts in %d groups (largest s = %d, r = %d unknowns), arena %.1f MB per "
-           "cell, %d group(s) on k_mf_front, %d coupling codes; K1 k_mesh_assemble + k_mesh_c0; ",
-           (long long)m->n_nodes, s.nfronts, s.ngroups, s.max_s, s.max_r, 8e-6 * s.arena_per_cell, s.front_groups, m->G.ncode);
-  m->detail = std::string(buf) + mf_describe(m->ws, m->ws->mf);
-  return HOMMX_OK;
-}
-
-void mesh_tree_destroy(MeshTreePlan* m) {
-  if (!m) return;
-  if (m->ws) blocked_workspace_destroy(m->ws);
-  if (m->mf) mf_plan_destroy(m->mf);
-  if (m->d_tables) (void)hipFree(m->d_tables);
-  delete m;
-}
-
-double mesh_tree_flops_per_cell(const MeshTreePlan* m) { return m->ws ? mf_flops_per_cell(m->ws->mf) : mf_flops_per_cell(m->mf); }
-int64_t mesh_tree_num_nodes(const MeshTreePlan* m) { return m->n_nodes; }
-const char* mesh_tree_route_detail(MeshTreePlan* m) { return m->detail.c_str(); }
-
-int mesh_tree_reserve(MeshTreePlan* m, long long n_cells) {
-  if (int rc = mf_reserve(m->ws, m->ws->mf, n_cells, true)) return mesh_error(rc, g_berr);
-  return HOMMX_OK;
-}
-
-int mesh_tree_solve(MeshTreePlan* m, long long ncells, const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
-                    hipStream_t st, double* d_corr) {
-  if (ncells <= 0) return HOMMX_OK;
-  BlockedWorkspace* ws = m->ws;
-  if (!d_corr) {
-    if (int rc = mf_solve(ws, ws->mf, ncells, d_coef, d_M, d_out, d_info, st)) return mesh_error(rc, g_berr);
-    return HOMMX_OK;
+  e = hipMemcpy(tables, host.data(), total, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(tables);
+    return mesh_error(HOMMX_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
   }
-  if (!ws->mf_keep) {  // the corrector plan: the same tree, every front keeps its factors for the back substitution
-    MfPlan* k = nullptr;
-    if (int rc = mf_plan_build(&k, m->G, m->tree, true)) return mesh_error(rc, g_berr);
-    if (int rc = mf_plan_upload(k)) {
-      mf_plan_destroy(k);
-      return mesh_error(rc, g_berr);
-    }
-    mf_set_mesh(k, &m->dev);
-    ws->mf_keep = k;
-  }
-  if (int rc = mf_solve(ws, ws->mf_keep, ncells, d_coef, d_M, d_out, d_info, st, d_corr)) return mesh_error(rc, g_berr);
+  if (int rc = blocked_workspace_create_mesh(out, m->G, std::move(m->tree), A, tables)) return mesh_error(rc, g_berr);
   return HOMMX_OK;
 }
+
+void mesh_tree_destroy(MeshTreePlan* m) { delete m; }
 
 }  // namespace hommx

@@ -26,8 +26,8 @@
 //   * Every chunk of cells runs as two to four pieces side by side on as many streams (the caller's and plan-owned ones, mf_solve).
 // Gauge: the node of highest elimination rank is pinned in the root front -- node nn - 1 on the torus (cell_problem.py:349-361).
 // The numeric phase never looks at geometry: mf_plan_build takes the supernode tree and the coupling graph (MfTree) from either source, the
-// box dissection of the torus (mf_tree_structured) or the coordinate bisection of an unstructured mesh (mesh_tree.hip, whose plans carry
-// their own K1, launch_mesh_assembly).
+// box dissection of the torus (mf_tree_structured) or the coordinate bisection of an unstructured mesh (mesh_tree.hip, whose workspaces
+// carry their own K1, launch_mesh_assembly).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -75,7 +75,7 @@ struct MfGroup {
   int32_t* d_upos = nullptr;        // [nf][2][16 T]  unknown of the front -> unknown of the child's update matrix, -1: none
   uint16_t* d_tilemap = nullptr;    // [ntiles]       a << 8 | b
   bool has_children = false;
-  // the same tables on the host (mf_plan_build), until mf_plan_upload
+  // the same tables on the host (mf_plan_build), until mf_plan_from_tree uploads them
   std::vector<int32_t> h_nodes, h_cpos, h_dpos, h_upos;
   std::vector<int8_t> h_code;
   std::vector<MfChild> h_child;
@@ -101,8 +101,6 @@ struct MfPlan {
   int streams = 4;
   hipStream_t side[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
-  // plans of an unstructured mesh (mesh_tree.hip): K1 is the mesh assembly on these tables instead of the structured stencil kernel
-  const MeshAsm* mesh = nullptr;
 };
 
 constexpr int MF_BORDER = 8;  // load rows per front (t <= 6)
@@ -222,7 +220,6 @@ int upload(T** dst, const std::vector<T>& src) {
 }  // namespace
 
 double mf_flops_per_cell(const MfPlan* p) { return p ? p->flops_per_cell : 0.0; }
-void mf_set_mesh(MfPlan* p, const MeshAsm* a) { p->mesh = a; }
 
 std::string mf_describe(const BlockedWorkspace* ws, const MfPlan* p) {
   if (!p) return "";
@@ -521,7 +518,7 @@ int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep) {
     }
     P->arena_per_cell = peak;
   }
-  // index tables (host; mf_plan_upload moves them to the device)
+  // index tables (host; mf_plan_from_tree moves them to the device)
   std::vector<int> local(nn, -1);
   for (int t = 0; t < ng; ++t) {
     const int g = order[t];
@@ -612,24 +609,16 @@ int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep) {
   return 0;
 }
 
-int mf_plan_upload(MfPlan* P) {
+int mf_plan_from_tree(BlockedWorkspace* ws, bool keep, MfPlan** out) {
+  *out = nullptr;
+  MfPlan* P = nullptr;
+  if (int rc = mf_plan_build(&P, ws->G, ws->tree, keep)) return rc;
   for (MfGroup& mg : P->groups)
     if (upload(&mg.d_nodes, mg.h_nodes) || upload(&mg.d_code, mg.h_code) || upload(&mg.d_cpos, mg.h_cpos) || upload(&mg.d_dpos, mg.h_dpos) ||
-        upload(&mg.d_child, mg.h_child) || upload(&mg.d_upos, mg.h_upos) || upload(&mg.d_tilemap, mg.h_tilemap))
+        upload(&mg.d_child, mg.h_child) || upload(&mg.d_upos, mg.h_upos) || upload(&mg.d_tilemap, mg.h_tilemap)) {
+      mf_plan_destroy(P);
       return HOMMX_EHIP;
-  return 0;
-}
-
-int mf_plan_create(MfPlan** out, const Geo& G, bool keep) {
-  *out = nullptr;
-  MfTree T;
-  mf_tree_structured(G, &T);
-  MfPlan* P = nullptr;
-  if (int rc = mf_plan_build(&P, G, T, keep)) return rc;
-  if (int rc = mf_plan_upload(P)) {
-    mf_plan_destroy(P);
-    return rc;
-  }
+    }
   *out = P;
   return 0;
 }
@@ -1114,7 +1103,7 @@ int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_
       const double* coef = d_coef + h.c0 * G.n_el * G.ncomp;
       const double* Mm = d_M ? d_M + h.c0 * G.dim * G.dim : nullptr;
       double *Kst = P->Kst + h.base * G.ncode * bs * bs * G.nn, *Brhs = P->Brhs + h.base * G.t * bs * G.nn, *C0 = P->C0 + h.base * 36;
-      if (P->mesh) launch_mesh_assembly(*P->mesh, coef, Mm, h.nc, h.st, Kst, Brhs, C0);  // the only launch that knows the geometry
+      if (ws->mesh_tables) launch_mesh_assembly(ws->mesh, coef, Mm, h.nc, h.st, Kst, Brhs, C0);  // the only launch that knows the geometry
       else launch_assembly(ws, coef, Mm, h.nc, h.st, Kst, Brhs, C0);
     }
     int gi = 0;

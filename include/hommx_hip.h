@@ -51,7 +51,6 @@ extern "C" {
  *   HOMMX_SPARSE_V1        any value: generic instead of strip-form sparse E products
  *   HOMMX_LEAF32           any value: 32x32 leaves only in the recursive block inverse
  *   HOMMX_NO_SPLIT64       any value: the recursive block inverse halves 192 into 96 + 96 instead of 64 + 128
- *   HOMMX_NO_H2D_OVERLAP   any value: hommx_solve_batch copies the whole coefficient stream before the first kernel
  *   HOMMX_NO_SMALL_FUSED   any value: plane blocks b <= 64 take the HBM-resident kernels instead of the one-launch kernels
  *   HOMMX_MF_MIN_B         smallest plane block b routed to the nested-dissection (multifrontal) elimination instead of the plane
  *                          elimination (default: 65 in 3D, 49 in 2D, i.e. every plane block the one-launch kernels do not take or lose

@@ -1,5 +1,5 @@
 """Dev tool: the generic host entry hommx_solve_batch (pageable coefficient stream in, tensors out) on the C4 workload.
-    python tools/bench_host_stream.py [cells]     (HOMMX_NO_H2D_OVERLAP=1: one copy in front of the kernels)"""
+    python tools/bench_host_stream.py [cells]     (batches of two chunks or more pipeline the copy with the kernels)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
