@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = (
     "hommx_solve_batch",
     "hommx_solve_batch_device",
     "hommx_solve_batch_correctors",
+    "hommx_reconstruct_batch",
+    "hommx_reconstruct_batch_device",
     "hommx_solve_batch_two_phase",
     "hommx_solve_batch_two_phase_device",
     "hommx_solve_batch_separable",
@@ -170,6 +172,10 @@ def load():
     lib.hommx_solve_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp]
     lib.hommx_solve_batch_correctors.restype = C.c_int
     lib.hommx_solve_batch_correctors.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    lib.hommx_reconstruct_batch.restype = C.c_int
+    lib.hommx_reconstruct_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.hommx_reconstruct_batch_device.restype = C.c_int
+    lib.hommx_reconstruct_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hommx_solve_batch_two_phase.restype = C.c_int
     lib.hommx_solve_batch_two_phase.argtypes = [vp, i64, vp, vp, vp, vp, vp]
     lib.hommx_solve_batch_two_phase_device.restype = C.c_int

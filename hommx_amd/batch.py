@@ -8,6 +8,7 @@ macro cell of the batch.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -68,6 +69,34 @@ def mesh_analyze_tree(msh, kind: str = "poisson", constraint=None) -> dict:
     _lib.check(lib.hommx_mesh_analyze_tree(C.byref(desc), None, None, None, None, None, parent.ctypes.data), "hommx_mesh_analyze_tree")
     return {"n_fronts": int(nf.value), "n_groups": int(ng.value), "max_front": int(mx.value), "flops_per_solve": float(fl.value),
             "supernode_of_node": sn, "parent": parent}
+
+
+@dataclass
+class Reconstruction:
+    """Micro fields of macro cells reconstructed from their correctors (include/hommx_hip.h, hommx_reconstruct_batch).
+
+    ``xi[N, t]``: the macro gradient / engineering-Voigt strain of every cell.  ``mean_strain`` / ``mean_flux`` ``[N, t]``: sum |K| s_K and
+    sum |K| q_K over the micro elements; ``energy[N]``: sum |K| s_K . q_K; ``max_flux[N]``: the largest |q_K| (Frobenius norm of the stress
+    for elasticity) and ``argmax_element[N]`` the smallest element reaching it.  ``strain`` / ``flux`` ``[N, n_el, t]`` or None.  On the
+    discrete problem mean_strain = xi, mean_flux = A_eff xi and energy = xi . A_eff xi.  ``cells``: the macro cells (``BaseHMM.reconstruct``)."""
+
+    xi: np.ndarray
+    mean_strain: np.ndarray
+    mean_flux: np.ndarray
+    energy: np.ndarray
+    max_flux: np.ndarray
+    argmax_element: np.ndarray
+    A_eff: np.ndarray
+    info: np.ndarray
+    strain: np.ndarray | None = None
+    flux: np.ndarray | None = None
+    cells: np.ndarray | None = None
+
+    @classmethod
+    def from_stats(cls, xi, stats, A_eff, info, strain=None, flux=None, cells=None) -> "Reconstruction":
+        t = xi.shape[1]
+        return cls(xi, stats[:, :t].copy(), stats[:, t:2 * t].copy(), stats[:, 2 * t].copy(), stats[:, 2 * t + 1].copy(),
+                   stats[:, 2 * t + 2].astype(np.int64), A_eff, info, strain, flux, cells)
 
 
 class MicroCellPlan:
@@ -185,6 +214,47 @@ class MicroCellPlan:
                 "hommx_solve_batch",
             )
         return (out, info) if return_info else out
+
+    def reconstruct(self, coef: np.ndarray, xi: np.ndarray, M: np.ndarray | None = None, fields: bool = False) -> Reconstruction:
+        """HMM reconstruction (hommx_reconstruct_batch): coef[N_c, n_el(, n_comp)] and M as ``solve``, xi[N_c, t] the macro gradient /
+        engineering-Voigt strain of every cell -> ``Reconstruction``; ``fields``: the per-element strain and flux [N_c, n_el, t] as well.
+        The correctors never leave the device; the batch runs in chunks of HOMMX_RECON_MEM_MB of correctors."""
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        nc = coef.shape[0]
+        if coef.size != nc * self.n_el * self.n_comp:
+            raise ValueError(f"coef has shape {coef.shape}; expected ({nc}, {self.n_el}" + (f", {self.n_comp})" if self.n_comp > 1 else ")"))
+        xi = np.ascontiguousarray(xi, dtype=np.float64)
+        if xi.shape != (nc, self.t):
+            raise ValueError(f"xi has shape {xi.shape}; expected ({nc}, {self.t})")
+        Mp = None
+        if M is not None:
+            M = np.ascontiguousarray(M, dtype=np.float64)
+            if M.shape != (nc, self.dim, self.dim):
+                raise ValueError(f"M has shape {M.shape}; expected ({nc}, {self.dim}, {self.dim})")
+            Mp = M.ctypes.data
+        stats = np.empty((nc, 2 * self.t + 3), dtype=np.float64)
+        A = np.empty((nc, self.t, self.t), dtype=np.float64)
+        info = np.zeros(nc, dtype=np.int32)
+        strain = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
+        flux = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
+        if nc:
+            _lib.check(
+                self._lib.hommx_reconstruct_batch(self._h, nc, coef.ctypes.data, Mp, xi.ctypes.data, stats.ctypes.data,
+                                                  strain.ctypes.data if fields else None, flux.ctypes.data if fields else None,
+                                                  A.ctypes.data, info.ctypes.data),
+                "hommx_reconstruct_batch",
+            )
+        return Reconstruction.from_stats(xi, stats, A, info, strain, flux)
+
+    def reconstruct_device(self, n_cells: int, coef_ptr: int, M_ptr: int | None, xi_ptr: int, stats_ptr: int, strain_ptr: int | None = None,
+                           flux_ptr: int | None = None, A_ptr: int | None = None, info_ptr: int | None = None, stream: int | None = None):
+        """Device-pointer form of ``reconstruct`` (hommx_reconstruct_batch_device), asynchronous on ``stream``: stats[n_cells, 2t + 3] =
+        [mean_strain | mean_flux | energy | max_flux | argmax_element]."""
+        _lib.check(
+            self._lib.hommx_reconstruct_batch_device(self._h, int(n_cells), coef_ptr, M_ptr or None, xi_ptr, stats_ptr, strain_ptr or None,
+                                                     flux_ptr or None, A_ptr or None, info_ptr or None, stream or None),
+            "hommx_reconstruct_batch_device",
+        )
 
     def solve_two_phase(self, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None = None,
                         return_info: bool = False):

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "../../include/hommx_hip.h"
 #include "blocked_internal.h"
@@ -81,6 +82,13 @@ struct hommx_plan {
   // host-pointer entry point: coefficient chunks stream in on s_copy while s_comp solves the previous one
   hipStream_t s_copy = nullptr, s_comp = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
+  // reconstruction (hommx_reconstruct_batch): HOMMX_RECON_MEM_MB, read when the plan is created; the correctors of one chunk (and the chi^xi
+  // slots of cells too large for LDS), A_eff the caller did not ask for, the host entry's staging; mesh plans: a host copy of the element
+  // table, gradients and volumes, uploaded to rgeo by the first reconstruct call
+  int64_t recon_mem_mb = 1024;
+  Buf rcorr, rA, rin, rout, rgeo;
+  std::vector<int32_t> h_el_nodes;
+  std::vector<double> h_grads, h_vol;
 };
 
 namespace {
@@ -98,6 +106,13 @@ int open_call(const hommx_plan* p, int64_t n_cells, bool ptrs_ok = true, const c
   return GO;
 }
 
+// HOMMX_RECON_MEM_MB (include/hommx_hip.h): read once, when the plan is created
+int64_t recon_mem_mb_env() {
+  const char* v = getenv("HOMMX_RECON_MEM_MB");
+  const long long mb = v ? atoll(v) : 0;
+  return mb > 0 ? mb : 1024;
+}
+
 // a failed call into the plan's route, under the route's name
 int route_fail(const hommx_plan* p, int rc) {
   if (p->family == FAM_MESH) return fail(rc, "mesh route: %s", hommx::mesh_last_error());
@@ -111,6 +126,16 @@ int route_solve(hommx_plan* p, int64_t n_cells, const double* d_coef, const doub
                                        : hommx::blocked_solve(p->ws, n_cells, d_coef, d_M, d_A_eff, d_info, st, d_corr);
   return rc ? route_fail(p, rc) : HOMMX_OK;
 }
+
+// a fused 2D plan computes no correctors: the first call that needs them gives it a workspace of the blocked family, which does
+int corrector_workspace(hommx_plan* p) {
+  if (p->family != FAM_FUSED2D || p->ws) return HOMMX_OK;
+  int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
+  return rc ? fail(rc, "blocked path: %s", hommx::blocked_last_error()) : HOMMX_OK;
+}
+
+// periodic unknowns of a cell (nodes x bs): the length of one corrector
+long long plan_ndof(const hommx_plan* p) { return (p->family == FAM_MESH ? hommx::mesh_num_nodes(p->mesh) : p->ws->G.nn) * (long long)p->ks.bs; }
 
 // the sampler device entry points on the blocked and mesh families: expand(c0, nc, dst) launches the expansion of cells [c0, c0 + nc) into
 // the plan's element stream, which is solved chunk by chunk of at most 1 GiB
@@ -193,6 +218,7 @@ int hommx_plan_create(hommx_plan** out, const hommx_plan_desc* d) {
   hommx_plan* p = new (std::nothrow) hommx_plan();
   if (!p) return fail(HOMMX_ENOMEM, "host allocation failed");
   p->desc = *d;
+  p->recon_mem_mb = recon_mem_mb_env();
   const int dim = d->dim, n = d->n_micro;
   p->n_el = (dim == 2) ? 2ll * n * n : 6ll * n * n * n;
   p->ks = hommx::kind_sizes(dim, d->kind);
@@ -214,7 +240,9 @@ int hommx_plan_destroy(hommx_plan* p) {
   hipSetDevice(p->desc.device);
   if (p->ws) hommx::blocked_workspace_destroy(p->ws);
   if (p->mesh) hommx::mesh_destroy(p->mesh);
-  for (Buf* b : {&p->coef, &p->M, &p->out, &p->info, &p->expand, &p->dev_in, &p->dev_out, &p->pin_in, &p->pin_out}) b->release();
+  for (Buf* b : {&p->coef, &p->M, &p->out, &p->info, &p->expand, &p->dev_in, &p->dev_out, &p->pin_in, &p->pin_out, &p->rcorr, &p->rA, &p->rin,
+                 &p->rout, &p->rgeo})
+    b->release();
   if (p->s_copy) hipStreamDestroy(p->s_copy);
   if (p->s_comp) hipStreamDestroy(p->s_comp);
   for (hipEvent_t e : p->ev)
@@ -326,9 +354,17 @@ int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d) {
   p->mesh = m;
   p->n_el = d->n_el;
   p->ks = hommx::kind_sizes(d->dim, d->kind);
+  p->recon_mem_mb = recon_mem_mb_env();
   const bool dev_ok = hipSetDevice(d->device) == hipSuccess;
   if (dev_ok) rc = m ? hommx::mesh_upload(m) : hommx::mesh_tree_workspace(mt, &p->ws);
   hommx::mesh_tree_destroy(mt);  // host analysis only: the workspace holds what the tree route needs
+  if (dev_ok && !rc) {  // the reconstruction's geometry, host side only (no caller pointer is kept; the device copy is made on first use)
+    hommx::MeshGeom g;
+    rc = hommx::mesh_check(d, &g);
+    p->h_el_nodes.assign(d->el_nodes, d->el_nodes + (size_t)d->n_el * (d->dim + 1));
+    p->h_grads = std::move(g.grads);
+    p->h_vol = std::move(g.vol);
+  }
   if (!dev_ok || rc) {
     const std::string msg = rc ? hommx::mesh_last_error() : "hipSetDevice failed";
     hommx_plan_destroy(p);
@@ -475,10 +511,7 @@ int hommx_solve_batch_separable(hommx_plan* p, int64_t n_cells, int32_t family, 
 int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* coef, const double* M, double* A_eff,
                                  double* correctors, int32_t* info) {
   if (int rc = open_call(p, n_cells, coef && A_eff && correctors, "coef / A_eff / correctors"); rc != GO) return rc;
-  if (p->family == FAM_FUSED2D && !p->ws) {  // the fused 2D kernel returns no correctors: the blocked family does
-    int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
-    if (rc != 0) return fail(rc, "blocked path: %s", hommx::blocked_last_error());
-  }
+  if (int rc = corrector_workspace(p)) return rc;
   const int d = p->desc.dim, t = p->ks.t;
   const long long nn = p->family == FAM_MESH ? hommx::mesh_num_nodes(p->mesh) : p->ws->G.nn;
   // the call's own device buffers, freed when it returns: the correctors can run to gigabytes, the plan keeps none of them
@@ -505,6 +538,146 @@ int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* c
   HIP_TRY(hipMemcpy(A_eff, b.out.p, sizeof(double) * n_cells * t * t, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(correctors, b.corr.p, ncorr, hipMemcpyDeviceToHost));
   if (info) HIP_TRY(hipMemcpy(info, b.info.p, sizeof(int32_t) * n_cells, hipMemcpyDeviceToHost));
+  return HOMMX_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// what a reconstruction needs beyond the plan's effective-tensor route: a route that forms correctors, and on mesh plans the element table,
+// gradients and volumes on the device (one block, uploaded by the first call: plans that never reconstruct allocate nothing for it)
+int recon_prepare(hommx_plan* p) {
+  if (int rc = corrector_workspace(p)) return rc;
+  if (p->desc.n_micro != 0 || p->rgeo.p) return HOMMX_OK;
+  const size_t b_nodes = sizeof(int32_t) * p->h_el_nodes.size(), b_grads = sizeof(double) * p->h_grads.size();
+  const size_t o_grads = (b_nodes + 255) / 256 * 256, o_vol = o_grads + (b_grads + 255) / 256 * 256;
+  if (int rc = grow(p->rgeo, o_vol + sizeof(double) * p->h_vol.size())) return rc;
+  char* g = static_cast<char*>(p->rgeo.p);
+  HIP_TRY(hipMemcpy(g, p->h_el_nodes.data(), b_nodes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(g + o_grads, p->h_grads.data(), b_grads, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(g + o_vol, p->h_vol.data(), sizeof(double) * p->h_vol.size(), hipMemcpyHostToDevice));
+  return HOMMX_OK;
+}
+
+bool recon_in_lds(const hommx_plan* p) { return sizeof(double) * plan_ndof(p) <= hommx::recon_lds_limit(); }
+
+// cells per chunk: HOMMX_RECON_MEM_MB of correctors (with the chi^xi slots of cells too large for LDS) and of `extra` bytes per cell
+int64_t recon_chunk(const hommx_plan* p, int64_t n_cells, size_t extra) {
+  const long long nd = plan_ndof(p);
+  const size_t per = sizeof(double) * nd * (p->ks.t + (recon_in_lds(p) ? 0 : 1)) + extra;
+  return std::clamp<int64_t>((int64_t)((p->recon_mem_mb << 20) / per), 1, n_cells);
+}
+
+// one chunk of at most recon_chunk() cells on the device: the correctors into the plan's scratch, then k_recon
+int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_coef, const double* d_M, const double* d_xi, double* d_stats,
+              double* d_strain, double* d_flux, double* d_A_eff, int32_t* d_info, hipStream_t st) {
+  const int t = p->ks.t;
+  const long long nd = plan_ndof(p);
+  const bool lds = recon_in_lds(p);
+  if (int rc = grow(p->rcorr, sizeof(double) * chunk * nd * (t + (lds ? 0 : 1)))) return rc;
+  if (!d_A_eff) {
+    if (int rc = grow(p->rA, sizeof(double) * chunk * t * t)) return rc;
+    d_A_eff = static_cast<double*>(p->rA.p);
+  }
+  double* corr = static_cast<double*>(p->rcorr.p);
+  if (int rc = route_solve(p, nc, d_coef, d_M, d_A_eff, d_info, st, corr)) return rc;
+  hommx::ReconArgs a;
+  a.ndof = nd;
+  a.n_el = p->n_el;
+  if (p->desc.n_micro) {
+    const double n = p->desc.n_micro;
+    a.n = p->desc.n_micro;
+    a.vol_struct = 1.0 / (p->desc.dim == 2 ? 2.0 * n * n : 6.0 * n * n * n);
+  } else {
+    const size_t b_nodes = sizeof(int32_t) * p->h_el_nodes.size(), b_grads = sizeof(double) * p->h_grads.size();
+    const size_t o_grads = (b_nodes + 255) / 256 * 256, o_vol = o_grads + (b_grads + 255) / 256 * 256;
+    char* g = static_cast<char*>(p->rgeo.p);
+    a.el_nodes = reinterpret_cast<const int32_t*>(g);
+    a.grads = reinterpret_cast<const double*>(g + o_grads);
+    a.vol = reinterpret_cast<const double*>(g + o_vol);
+  }
+  a.corr = corr;
+  a.coef = d_coef;
+  a.M = d_M;
+  a.xi = d_xi;
+  a.stats = d_stats;
+  a.strain = d_strain;
+  a.flux = d_flux;
+  a.slot = lds ? nullptr : corr + chunk * t * nd;
+  HIP_TRY(hommx::launch_reconstruct(a, p->desc.dim, p->desc.kind, p->desc.n_micro == 0, nc, st));
+  return HOMMX_OK;
+}
+
+// the shared argument checks of both reconstruct entry points
+int recon_open(hommx_plan* p, int64_t n_cells, const void* coef, const void* xi, const void* stats, const void* strain, const void* flux,
+               bool device) {
+  if (int rc = open_call(p, n_cells, coef && xi && stats, "coef / xi / stats", device); rc != GO) return rc;
+  if (!strain != !flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
+  if (int rc = recon_prepare(p)) return rc;
+  return GO;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hommx_reconstruct_batch_device(hommx_plan* p, int64_t n_cells, const double* d_coef, const double* d_M, const double* d_xi, double* d_stats,
+                                   double* d_strain, double* d_flux, double* d_A_eff, int32_t* d_info, void* stream) {
+  if (int rc = recon_open(p, n_cells, d_coef, d_xi, d_stats, d_strain, d_flux, true); rc != GO) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int d = p->desc.dim, t = p->ks.t, ns = HOMMX_RECON_NSTATS(t);
+  const int64_t per = p->n_el * p->ks.n_comp, chunk = recon_chunk(p, n_cells, 0);
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    const int64_t nc = std::min(chunk, n_cells - c0);
+    const int64_t fo = c0 * p->n_el * t;
+    int rc = recon_run(p, nc, chunk, d_coef + c0 * per, d_M ? d_M + c0 * d * d : nullptr, d_xi + c0 * t, d_stats + c0 * ns,
+                       d_strain ? d_strain + fo : nullptr, d_flux ? d_flux + fo : nullptr, d_A_eff ? d_A_eff + c0 * t * t : nullptr,
+                       d_info ? d_info + c0 : nullptr, st);
+    if (rc != HOMMX_OK) return rc;
+  }
+  return HOMMX_OK;
+}
+
+int hommx_reconstruct_batch(hommx_plan* p, int64_t n_cells, const double* coef, const double* M, const double* xi, double* stats, double* strain,
+                            double* flux, double* A_eff, int32_t* info) {
+  if (int rc = recon_open(p, n_cells, coef, xi, stats, strain, flux, false); rc != GO) return rc;
+  const int d = p->desc.dim, t = p->ks.t, ns = HOMMX_RECON_NSTATS(t);
+  const int64_t per = p->n_el * p->ks.n_comp, nfield = strain ? 2 * p->n_el * t : 0;
+  // per cell, 256-byte aligned blocks: in = [coef | M | xi], out = [stats | A_eff | info | strain | flux]
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t in_cell = sizeof(double) * (per + (M ? d * d : 0) + t), out_cell = sizeof(double) * (ns + t * t + nfield) + sizeof(int32_t);
+  const int64_t chunk = recon_chunk(p, n_cells, in_cell + out_cell);
+  const size_t o_M = up(sizeof(double) * chunk * per), o_xi = o_M + (M ? up(sizeof(double) * chunk * d * d) : 0);
+  const size_t o_A = up(sizeof(double) * chunk * ns), o_info = o_A + up(sizeof(double) * chunk * t * t);
+  const size_t o_strain = o_info + up(sizeof(int32_t) * chunk), o_flux = o_strain + up(sizeof(double) * chunk * p->n_el * t * (strain ? 1 : 0));
+  if (int rc = grow(p->rin, o_xi + sizeof(double) * chunk * t)) return rc;
+  if (int rc = grow(p->rout, o_flux + sizeof(double) * chunk * p->n_el * t * (strain ? 1 : 0))) return rc;
+  char* din = static_cast<char*>(p->rin.p);
+  char* dout = static_cast<char*>(p->rout.p);
+  double* d_coef = reinterpret_cast<double*>(din);
+  double* d_M = M ? reinterpret_cast<double*>(din + o_M) : nullptr;
+  double* d_xi = reinterpret_cast<double*>(din + o_xi);
+  double* d_stats = reinterpret_cast<double*>(dout);
+  double* d_A = reinterpret_cast<double*>(dout + o_A);
+  int32_t* d_info = reinterpret_cast<int32_t*>(dout + o_info);
+  double* d_strain = strain ? reinterpret_cast<double*>(dout + o_strain) : nullptr;
+  double* d_flux = strain ? reinterpret_cast<double*>(dout + o_flux) : nullptr;
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    const int64_t nc = std::min(chunk, n_cells - c0);
+    HIP_TRY(hipMemcpy(d_coef, coef + c0 * per, sizeof(double) * nc * per, hipMemcpyHostToDevice));
+    if (M) HIP_TRY(hipMemcpy(d_M, M + c0 * d * d, sizeof(double) * nc * d * d, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_xi, xi + c0 * t, sizeof(double) * nc * t, hipMemcpyHostToDevice));
+    int rc = recon_run(p, nc, chunk, d_coef, d_M, d_xi, d_stats, d_strain, d_flux, d_A, d_info, nullptr);
+    if (rc != HOMMX_OK) return rc;
+    HIP_TRY(hipMemcpy(stats + c0 * ns, d_stats, sizeof(double) * nc * ns, hipMemcpyDeviceToHost));
+    if (A_eff) HIP_TRY(hipMemcpy(A_eff + c0 * t * t, d_A, sizeof(double) * nc * t * t, hipMemcpyDeviceToHost));
+    if (info) HIP_TRY(hipMemcpy(info + c0, d_info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
+    if (strain) {
+      HIP_TRY(hipMemcpy(strain + c0 * p->n_el * t, d_strain, sizeof(double) * nc * p->n_el * t, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(flux + c0 * p->n_el * t, d_flux, sizeof(double) * nc * p->n_el * t, hipMemcpyDeviceToHost));
+    }
+  }
   return HOMMX_OK;
 }
 

@@ -60,6 +60,28 @@ hipError_t launch_expand_separable(CoefSource src, const double* d_params, doubl
 hipError_t launch_expand_two_phase(const unsigned char* d_mask, const double* d_values, double* d_coef, long long n_el,
                                    int n_comp, long long ncells, hipStream_t stream);
 
+// reconstruct.hip: per-element gradient / strain and flux / stress of `nc` cells from their correctors, and the per-cell statistics
+// [mean_strain (t) | mean_flux (t) | energy | max_flux | argmax_element] (include/hommx_hip.h, hommx_reconstruct_batch)
+struct ReconArgs {
+  int n = 0;                         // structured plans: micro cells per side (geometry computed in the kernel)
+  double vol_struct = 0.0;           // structured plans: element volume
+  long long ndof = 0, n_el = 0;      // periodic unknowns (nodes x bs) and elements per cell
+  const int32_t* el_nodes = nullptr; // mesh plans: [n_el][dim+1] periodic nodes, [n_el][dim+1][dim] P1 gradients, [n_el] volumes
+  const double* grads = nullptr;
+  const double* vol = nullptr;
+  const double* corr = nullptr;      // [nc][t][ndof]
+  const double* coef = nullptr;      // [nc][n_el][n_comp]
+  const double* M = nullptr;         // [nc][d][d] or null
+  const double* xi = nullptr;        // [nc][t]
+  double* stats = nullptr;           // [nc][2t+3]
+  double* strain = nullptr;          // [nc][n_el][t] or null (then flux is null as well: no fields)
+  double* flux = nullptr;
+  double* slot = nullptr;            // [nc][ndof] scratch for chi^xi of cells too large for LDS (null: LDS)
+};
+// bytes of chi^xi above which a cell takes a scratch slot instead of LDS
+size_t recon_lds_limit();
+hipError_t launch_reconstruct(const ReconArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
+
 // calibrate.hip: best sustained v_mfma_f64_16x16x4_f64 and v_fma_f64 rates over 2 and 4 waves per SIMD.
 hipError_t run_fp64_calibration(double* mfma_flops_per_s, double* fma_flops_per_s, double* mfma_lds_fed_flops_per_s = nullptr);
 

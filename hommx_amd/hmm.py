@@ -28,7 +28,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import fem
-from .batch import MicroCellPlan
+from .batch import MicroCellPlan, Reconstruction
 from .mesh import Mesh, micro_cells_per_side
 
 _VOIGT = {2: [(0, 0), (1, 1), (0, 1)], 3: [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]}
@@ -283,6 +283,7 @@ class BaseHMM(ABC):
         self._plan: MicroCellPlan | None = None
         self.effective_tensors: np.ndarray | None = None  # A_H / C_H of every macro cell after assembly
         self.cell_info: np.ndarray | None = None
+        self._solved = False  # reconstruct() defaults to the last solve() result
         if self._reserve_at_construction:
             self.prepare()
 
@@ -716,7 +717,57 @@ class BaseHMM(ABC):
             self._logger.error("Something went wrong in the global problem solve. NaN in the assembled system")
         x = spla.spsolve(A.tocsc(), b)
         self._u.x.array[:] = x
+        self._solved = True
         return self._u
+
+    def _macro_strains(self, cells: np.ndarray, u: np.ndarray) -> np.ndarray:
+        """xi[c] of the macro field u on every cell: grad u_H|_T (Poisson), or the Voigt vector of eps(u_H)|_T with doubled shear -- W^T u_T
+        with the W of ``_local_stiffness_from_tensors``, so that u_T . S_loc u_T = vol(T) xi . A_H xi."""
+        d, bs = self._tdim, self._bs
+        X = self._msh.cell_vertices()[cells]
+        Minv = np.linalg.inv(np.concatenate([np.ones(X.shape[:2] + (1,)), X], axis=2))
+        G = np.transpose(Minv[:, 1:, :], (0, 2, 1))  # [nc, a, d]  grad phi_a
+        uT = u[_unroll_dofs(self._msh.cells[cells].astype(np.int64), bs)]  # [nc, nb]
+        if bs == 1:
+            return np.einsum("ca,cai->ci", uT, G)
+        I = np.eye(d)
+        eps = 0.5 * (np.einsum("pi,caj->capij", I, G) + np.einsum("pj,cai->capij", I, G))
+        eps = eps.reshape(len(cells), (d + 1) * bs, d, d)
+        Wv = np.stack([eps[:, :, k, l] * (1.0 if k == l else 2.0) for (k, l) in _VOIGT[d]], axis=-1)
+        return np.einsum("cb,cbm->cm", uT, Wv)
+
+    def reconstruct(self, u=None, cells=None, fields: bool = False, chunk_cells: int | None = None) -> Reconstruction:
+        """HMM reconstruction of the micro fields in the sampling boxes of ``cells`` (default: every macro cell) from the macro solution
+        ``u`` (a macro ``fem.Function`` or its dof array; default: the last ``solve()`` result): R = u_H + corrector of xi_T, with xi_T the
+        macro gradient / strain of u on the cell (hommx_reconstruct_batch).  Returns a ``Reconstruction`` with ``cells``:
+        per-cell mean strain / flux, energy (sum over the cells of vol(T) energy_T is the macro energy u . K_H u), the largest flux and
+        where it is reached, and with ``fields`` the per-element strain and flux [N, n_el, t].
+
+        The cells are sampled, uploaded and reconstructed in chunks of ``chunk_cells`` (default: about 256 MB of coefficient stream).
+        Under a process group this runs on the calling rank alone, for the cells it is given: there is no collective."""
+        if u is None:
+            if not self._solved:
+                raise RuntimeError("reconstruct() needs a macro solution: call solve() first or pass u")
+            u = self._u
+        x = np.asarray(u.x.array if hasattr(u, "x") else u, dtype=float)
+        if x.shape != (self._num_global_dofs,):
+            raise ValueError(f"u has {x.size} dofs; the macro space has {self._num_global_dofs}")
+        cells = np.arange(self._msh.num_cells) if cells is None else np.asarray(cells, dtype=np.int64).ravel()
+        if len(cells) == 0:
+            raise ValueError("reconstruct() needs at least one macro cell")
+        xi = self._macro_strains(cells, x)
+        if chunk_cells is None:
+            per = self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) * 8
+            chunk_cells = (256 << 20) // per
+        ch = max(1, int(chunk_cells))
+        parts = []
+        for b in range(0, len(cells), ch):
+            sub = cells[b:b + ch]
+            coef, kind = self._element_means(sub)
+            parts.append(self._ensure_plan(kind).reconstruct(coef, xi[b:b + ch], self._stratification(sub), fields=fields))
+        cat = lambda name: None if getattr(parts[0], name) is None else np.concatenate([getattr(r, name) for r in parts])
+        return Reconstruction(xi, cat("mean_strain"), cat("mean_flux"), cat("energy"), cat("max_flux"), cat("argmax_element"), cat("A_eff"),
+                              cat("info"), cat("strain"), cat("flux"), cells)
 
     def plot_solution(self, u=None):  # hmm.py:493-511 (visualisation: out of scope)
         raise NotImplementedError("plotting is out of scope of hommx_amd; use u.x.array with any plotting tool")

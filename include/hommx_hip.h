@@ -65,7 +65,9 @@ extern "C" {
  *   HOMMX_MF_LEAF, HOMMX_MF_SPLIT_DEPTH, HOMMX_MF_G128_MIN_K, HOMMX_MF_NO_BORDER_SPLIT, HOMMX_MF_VERBOSE   tuning / A-B knobs of that route
  *   HOMMX_SMALL_WAVES      2 / 4: plane blocks b <= 48 take the LDS-resident multi-wave kernel (that many waves per macro cell)
  *                          instead of the one-wave-per-cell register kernel; for 48 < b <= 64 it sets that kernel's wave count
- *                          (2 / 4 / 8, default 8)                                                                              */
+ *                          (2 / 4 / 8, default 8)
+ *   HOMMX_RECON_MEM_MB     correctors hommx_reconstruct_batch[_device] holds on the device at once, in MB (default 1024): the batch runs in
+ *                          chunks of that many cells' correctors                                                              */
 
 typedef struct hommx_plan hommx_plan;
 
@@ -194,6 +196,32 @@ int hommx_solve_batch_separable_device(hommx_plan* plan, int64_t n_cells, int32_
  * elimination of the blocked family here (the one-launch kernels and the fused 2D kernel never form the factors). */
 int hommx_solve_batch_correctors(hommx_plan* plan, int64_t n_cells, const double* coef, const double* M,
                                  double* A_eff, double* correctors, int32_t* info);
+
+/*
+ * HMM reconstruction: the micro fields inside the sampling box of every macro cell, from the macro solution.
+ * For macro cell c with macro gradient / strain xi[c] (t entries: grad u_H|_T for the Poisson kinds; for elasticity the Voigt vector of
+ * eps(u_H)|_T with doubled shear, (e00, e11[, e22], 2 e01[, 2 e02, 2 e12])) and the canonical correctors chi_m of the cell (the layout of
+ * hommx_solve_batch_correctors), chi^xi = sum_m xi_m chi_m and, for every micro element K (volume |K|, P1 gradients g_a, periodic nodes p_a):
+ *   s_K = xi + sum_a sum_alpha chi^xi[p_a bs + alpha] strain(g_a, M, alpha)   gradient / strain in the canonical-load basis (shear doubled)
+ *   q_K = material(coef_K) s_K                                                flux A grad R (no sign flip) / stress (s00, s11[, s22], s01[, s02, s12])
+ *   stats[c] = [ sum |K| s_K (t) | sum |K| q_K (t) | sum |K| s_K . q_K | max_K |q_K| | smallest K reaching the max (as a double) ]
+ * |q| is the Euclidean norm for Poisson, the Frobenius norm of the stress (shear entries counted twice) for elasticity.  Exactly, on the
+ * discrete problem: mean strain = xi, mean flux = A_eff xi, energy = xi . A_eff xi (Hill-Mandel).  A cell's stats do not depend on its batch
+ * position, the chunking or whether fields are written (fixed-order reduction).
+ *
+ *   coef, M          as hommx_solve_batch                      strain, flux  [n_cells][n_el][t] or both NULL: per-element fields
+ *   xi               [n_cells][t]                              A_eff, info   as hommx_solve_batch, or NULL
+ *   stats            [n_cells][HOMMX_RECON_NSTATS(t)], required
+ * Every plan: the structured routes (a fused 2D plan gets the corrector workspace of the blocked family on first use, as
+ * hommx_solve_batch_correctors) and both mesh routes.  The batch runs in chunks: the correctors of one chunk (HOMMX_RECON_MEM_MB) live in
+ * plan-owned scratch, never the whole batch's; the host entry also streams coef in and the outputs out chunk by chunk.
+ */
+#define HOMMX_RECON_NSTATS(t) (2 * (t) + 3) /* [mean_strain(t) | mean_flux(t) | energy | max_flux | argmax_element] */
+int hommx_reconstruct_batch(hommx_plan* plan, int64_t n_cells, const double* coef, const double* M, const double* xi, double* stats,
+                            double* strain, double* flux, double* A_eff, int32_t* info);
+/* Same with DEVICE pointers, asynchronous on `stream`; the plan's scratch is shared with its other entry points (not thread-safe). */
+int hommx_reconstruct_batch_device(hommx_plan* plan, int64_t n_cells, const double* d_coef, const double* d_M, const double* d_xi,
+                                   double* d_stats, double* d_strain, double* d_flux, double* d_A_eff, int32_t* d_info, void* stream);
 
 /*
  * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
