@@ -15,13 +15,16 @@
 
 #include "../../include/hommx_hip.h"
 #include "blocked_internal.h"
+#include "host_common.h"
 #include "kernels.h"
 #include "mesh_front.h"
 #include "mesh_tree.h"
 
-namespace {
+namespace hommx {
 
+namespace {
 thread_local std::string g_err;
+}
 
 int fail(int code, const char* fmt, ...) {
   char buf[512];
@@ -33,13 +36,33 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e__ = (expr);                                                                   \
-    if (e__ != hipSuccess)                                                                     \
-      return fail(e__ == hipErrorOutOfMemory ? HOMMX_ENOMEM : HOMMX_EHIP, "%s failed: %s", #expr, \
-                  hipGetErrorString(e__));                                                     \
-  } while (0)
+int prefix_error(int code, const char* prefix) {
+  g_err.insert(0, prefix);
+  return code;
+}
+
+int upload_packed(void** block, std::initializer_list<HostPiece> pieces) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  size_t total = 0;
+  for (const HostPiece& p : pieces) total += up(p.bytes);
+  std::vector<char> host(total, 0);
+  HIP_TRY(hipMalloc(block, total));
+  size_t off = 0;
+  for (const HostPiece& p : pieces) {
+    if (p.bytes) memcpy(host.data() + off, p.src, p.bytes);
+    *p.dst = static_cast<const char*>(*block) + off;
+    off += up(p.bytes);
+  }
+  HIP_TRY(hipMemcpy(*block, host.data(), total, hipMemcpyHostToDevice));
+  return HOMMX_OK;
+}
+
+}  // namespace hommx
+
+namespace {
+
+using hommx::fail;
+using hommx::prefix_error;
 
 // FAM_BLOCKED: structured plans beyond the fused 2D kernel, and the mesh plans of the tree route (their workspace carries the mesh)
 enum Family { FAM_FUSED2D = 0, FAM_BLOCKED = 1, FAM_MESH = 2 };
@@ -83,12 +106,12 @@ struct hommx_plan {
   hipStream_t s_copy = nullptr, s_comp = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
   // reconstruction (hommx_reconstruct_batch): HOMMX_RECON_MEM_MB, read when the plan is created; the correctors of one chunk (and the chi^xi
-  // slots of cells too large for LDS), A_eff the caller did not ask for, the host entry's staging; mesh plans: a host copy of the element
-  // table, gradients and volumes, uploaded to rgeo by the first reconstruct call
+  // slots of cells too large for LDS), A_eff the caller did not ask for, the host entry's staging
   int64_t recon_mem_mb = 1024;
-  Buf rcorr, rA, rin, rout, rgeo;
-  std::vector<int32_t> h_el_nodes;
-  std::vector<double> h_grads, h_vol;
+  Buf rcorr, rA, rin, rout;
+  // mesh plans: the element table, P1 gradients and volumes on the device, uploaded when the plan is created -- the one copy the route's
+  // kernels (MeshDev / MeshAsm) and the reconstruction read
+  hommx::MeshGeomDev geo{};
 };
 
 namespace {
@@ -114,10 +137,7 @@ int64_t recon_mem_mb_env() {
 }
 
 // a failed call into the plan's route, under the route's name
-int route_fail(const hommx_plan* p, int rc) {
-  if (p->family == FAM_MESH) return fail(rc, "mesh route: %s", hommx::mesh_last_error());
-  return fail(rc, "%s: %s", p->desc.n_micro ? "blocked path" : "mesh route", hommx::blocked_last_error());
-}
+int route_fail(const hommx_plan* p, int rc) { return prefix_error(rc, p->desc.n_micro ? "blocked path: " : "mesh route: "); }
 
 // an element stream on the device through the plan's mesh_front or blocked route; d_corr: the correctors as well
 int route_solve(hommx_plan* p, int64_t n_cells, const double* d_coef, const double* d_M, double* d_A_eff, int32_t* d_info, hipStream_t st,
@@ -131,7 +151,7 @@ int route_solve(hommx_plan* p, int64_t n_cells, const double* d_coef, const doub
 int corrector_workspace(hommx_plan* p) {
   if (p->family != FAM_FUSED2D || p->ws) return HOMMX_OK;
   int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
-  return rc ? fail(rc, "blocked path: %s", hommx::blocked_last_error()) : HOMMX_OK;
+  return rc ? prefix_error(rc, "blocked path: ") : HOMMX_OK;
 }
 
 // periodic unknowns of a cell (nodes x bs): the length of one corrector
@@ -203,7 +223,7 @@ int hommx_device_count(void) {
   return n;
 }
 
-const char* hommx_last_error(void) { return g_err.c_str(); }
+const char* hommx_last_error(void) { return hommx::g_err.c_str(); }
 
 int hommx_plan_create(hommx_plan** out, const hommx_plan_desc* d) {
   if (!out || !d) return fail(HOMMX_EINVAL, "null argument");
@@ -228,7 +248,7 @@ int hommx_plan_create(hommx_plan** out, const hommx_plan_desc* d) {
     int rc = hommx::blocked_workspace_create(&p->ws, dim, n, d->kind);
     if (rc != 0) {
       delete p;
-      return fail(rc, "blocked path: %s", hommx::blocked_last_error());
+      return prefix_error(rc, "blocked path: ");
     }
   }
   *out = p;
@@ -241,8 +261,9 @@ int hommx_plan_destroy(hommx_plan* p) {
   if (p->ws) hommx::blocked_workspace_destroy(p->ws);
   if (p->mesh) hommx::mesh_destroy(p->mesh);
   for (Buf* b : {&p->coef, &p->M, &p->out, &p->info, &p->expand, &p->dev_in, &p->dev_out, &p->pin_in, &p->pin_out, &p->rcorr, &p->rA, &p->rin,
-                 &p->rout, &p->rgeo})
+                 &p->rout})
     b->release();
+  if (p->geo.block) (void)hipFree(p->geo.block);
   if (p->s_copy) hipStreamDestroy(p->s_copy);
   if (p->s_comp) hipStreamDestroy(p->s_comp);
   for (hipEvent_t e : p->ev)
@@ -250,9 +271,6 @@ int hommx_plan_destroy(hommx_plan* p) {
   delete p;
   return HOMMX_OK;
 }
-
-// multi.hip reports its errors through the same thread-local message
-int hommx_set_error_(int code, const char* msg) { return fail(code, "%s", msg); }
 
 int32_t hommx_plan_dim(const hommx_plan* p) { return p ? p->desc.dim : 0; }
 int32_t hommx_plan_device(const hommx_plan* p) { return p ? p->desc.device : -1; }
@@ -301,15 +319,17 @@ const char* hommx_plan_route_detail(hommx_plan* p) {
 }
 
 int hommx_mesh_analyze(const hommx_mesh_desc* d, int32_t* front_width, double* flops_per_solve) {
-  int rc = hommx::mesh_analyze(d, nullptr, front_width, flops_per_solve);
-  return rc ? fail(rc, "%s", hommx::mesh_last_error()) : HOMMX_OK;
+  hommx::MeshGeom geo;
+  if (int rc = hommx::mesh_check(d, &geo)) return rc;
+  return hommx::mesh_analyze(d, geo, nullptr, front_width, flops_per_solve);
 }
 
 int hommx_mesh_analyze_tree(const hommx_mesh_desc* d, int32_t* n_fronts, int32_t* n_groups, int32_t* max_front, double* flops_per_solve,
                             int32_t* supernode_of_node, int32_t* parent) {
+  hommx::MeshGeom geo;
+  if (int rc = hommx::mesh_check(d, &geo)) return rc;
   hommx::MeshTreeInfo info{};
-  int rc = hommx::mesh_tree_analyze(d, nullptr, &info, supernode_of_node, parent);
-  if (rc) return fail(rc, "%s", hommx::mesh_last_error());
+  if (int rc = hommx::mesh_tree_analyze(d, geo, nullptr, &info, supernode_of_node, parent)) return rc;
   if (n_fronts) *n_fronts = info.n_fronts;
   if (n_groups) *n_groups = info.n_groups;
   if (max_front) *max_front = info.max_front;
@@ -320,17 +340,19 @@ int hommx_mesh_analyze_tree(const hommx_mesh_desc* d, int32_t* n_fronts, int32_t
 int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d) {
   if (!out || !d) return fail(HOMMX_EINVAL, "null argument");
   *out = nullptr;
-  // every argument check runs before the device is touched.  The frontal route takes what fits its LDS front; wider meshes, and any mesh
-  // with HOMMX_MESH_FLAG_TREE, take the tree route
+  // every argument check runs before the device is touched: the mesh is validated once (mesh_check), and both routes analyse that one
+  // MeshGeom.  The frontal route takes what fits its LDS front; wider meshes, and any mesh with HOMMX_MESH_FLAG_TREE, take the tree route
+  hommx::MeshGeom geo;
+  if (int rc = hommx::mesh_check(d, &geo)) return rc;
   hommx::MeshPlan* m = nullptr;
   hommx::MeshTreePlan* mt = nullptr;
   int rc = 0;
   if (!(d->flags & HOMMX_MESH_FLAG_TREE)) {
     int32_t width = 0;
-    rc = hommx::mesh_analyze(d, &m, &width, nullptr);
-    if (rc && !(rc == HOMMX_EINVAL && width > HOMMX_MESH_MAX_FRONT)) return fail(rc, "%s", hommx::mesh_last_error());
+    rc = hommx::mesh_analyze(d, geo, &m, &width, nullptr);
+    if (rc && !(rc == HOMMX_EINVAL && width > HOMMX_MESH_MAX_FRONT)) return rc;
   }
-  if (!m && (rc = hommx::mesh_tree_analyze(d, &mt, nullptr, nullptr, nullptr)) != 0) return fail(rc, "%s", hommx::mesh_last_error());
+  if (!m && (rc = hommx::mesh_tree_analyze(d, geo, &mt, nullptr, nullptr, nullptr)) != 0) return rc;
   auto drop = [&]() {
     hommx::mesh_destroy(m);
     hommx::mesh_tree_destroy(mt);
@@ -355,20 +377,13 @@ int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d) {
   p->n_el = d->n_el;
   p->ks = hommx::kind_sizes(d->dim, d->kind);
   p->recon_mem_mb = recon_mem_mb_env();
-  const bool dev_ok = hipSetDevice(d->device) == hipSuccess;
-  if (dev_ok) rc = m ? hommx::mesh_upload(m) : hommx::mesh_tree_workspace(mt, &p->ws);
+  rc = hipSetDevice(d->device) == hipSuccess ? HOMMX_OK : fail(HOMMX_EHIP, "hipSetDevice failed");
+  if (!rc) rc = hommx::mesh_geom_upload(d, geo, &p->geo);
+  if (!rc) rc = m ? hommx::mesh_upload(m, p->geo) : hommx::mesh_tree_workspace(mt, p->geo, &p->ws);
   hommx::mesh_tree_destroy(mt);  // host analysis only: the workspace holds what the tree route needs
-  if (dev_ok && !rc) {  // the reconstruction's geometry, host side only (no caller pointer is kept; the device copy is made on first use)
-    hommx::MeshGeom g;
-    rc = hommx::mesh_check(d, &g);
-    p->h_el_nodes.assign(d->el_nodes, d->el_nodes + (size_t)d->n_el * (d->dim + 1));
-    p->h_grads = std::move(g.grads);
-    p->h_vol = std::move(g.vol);
-  }
-  if (!dev_ok || rc) {
-    const std::string msg = rc ? hommx::mesh_last_error() : "hipSetDevice failed";
+  if (rc) {
     hommx_plan_destroy(p);
-    return fail(rc ? rc : HOMMX_EHIP, "mesh route: %s", msg.c_str());
+    return prefix_error(rc, "mesh route: ");
   }
   *out = p;
   return HOMMX_OK;
@@ -545,21 +560,6 @@ int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* c
 
 namespace {
 
-// what a reconstruction needs beyond the plan's effective-tensor route: a route that forms correctors, and on mesh plans the element table,
-// gradients and volumes on the device (one block, uploaded by the first call: plans that never reconstruct allocate nothing for it)
-int recon_prepare(hommx_plan* p) {
-  if (int rc = corrector_workspace(p)) return rc;
-  if (p->desc.n_micro != 0 || p->rgeo.p) return HOMMX_OK;
-  const size_t b_nodes = sizeof(int32_t) * p->h_el_nodes.size(), b_grads = sizeof(double) * p->h_grads.size();
-  const size_t o_grads = (b_nodes + 255) / 256 * 256, o_vol = o_grads + (b_grads + 255) / 256 * 256;
-  if (int rc = grow(p->rgeo, o_vol + sizeof(double) * p->h_vol.size())) return rc;
-  char* g = static_cast<char*>(p->rgeo.p);
-  HIP_TRY(hipMemcpy(g, p->h_el_nodes.data(), b_nodes, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(g + o_grads, p->h_grads.data(), b_grads, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(g + o_vol, p->h_vol.data(), sizeof(double) * p->h_vol.size(), hipMemcpyHostToDevice));
-  return HOMMX_OK;
-}
-
 bool recon_in_lds(const hommx_plan* p) { return sizeof(double) * plan_ndof(p) <= hommx::recon_lds_limit(); }
 
 // cells per chunk: HOMMX_RECON_MEM_MB of correctors (with the chi^xi slots of cells too large for LDS) and of `extra` bytes per cell
@@ -590,12 +590,9 @@ int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_coef, co
     a.n = p->desc.n_micro;
     a.vol_struct = 1.0 / (p->desc.dim == 2 ? 2.0 * n * n : 6.0 * n * n * n);
   } else {
-    const size_t b_nodes = sizeof(int32_t) * p->h_el_nodes.size(), b_grads = sizeof(double) * p->h_grads.size();
-    const size_t o_grads = (b_nodes + 255) / 256 * 256, o_vol = o_grads + (b_grads + 255) / 256 * 256;
-    char* g = static_cast<char*>(p->rgeo.p);
-    a.el_nodes = reinterpret_cast<const int32_t*>(g);
-    a.grads = reinterpret_cast<const double*>(g + o_grads);
-    a.vol = reinterpret_cast<const double*>(g + o_vol);
+    a.el_nodes = p->geo.el_nodes;
+    a.grads = p->geo.grads;
+    a.vol = p->geo.vol;
   }
   a.corr = corr;
   a.coef = d_coef;
@@ -614,7 +611,7 @@ int recon_open(hommx_plan* p, int64_t n_cells, const void* coef, const void* xi,
                bool device) {
   if (int rc = open_call(p, n_cells, coef && xi && stats, "coef / xi / stats", device); rc != GO) return rc;
   if (!strain != !flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
-  if (int rc = recon_prepare(p)) return rc;
+  if (int rc = corrector_workspace(p)) return rc;  // a reconstruction needs a route that forms correctors
   return GO;
 }
 

@@ -24,25 +24,14 @@
 #include <vector>
 
 #include "../../include/hommx_hip.h"
+#define HOMMX_HIP_TRY_FMT "%s: %s"
 #include "blocked_internal.h"
 #include "geo.h"
+#include "host_common.h"
 #include "kernels.h"
 #include "sweep.h"
 
 namespace hommx {
-
-
-thread_local std::string g_berr;
-const char* blocked_last_error() { return g_berr.c_str(); }
-
-#define BTRY(expr)                                                                       \
-  do {                                                                                   \
-    hipError_t e__ = (expr);                                                             \
-    if (e__ != hipSuccess) {                                                             \
-      g_berr = std::string(#expr) + ": " + hipGetErrorString(e__);                       \
-      return e__ == hipErrorOutOfMemory ? HOMMX_ENOMEM : HOMMX_EHIP;                     \
-    }                                                                                    \
-  } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------
 // K1: assembly
@@ -158,10 +147,7 @@ __global__ __launch_bounds__(128) void k_assemble_reg(Geo G, const double* __res
                                                       double* __restrict__ Kst, double* __restrict__ Brhs, long long ncells) {
   constexpr bool EL = KIND >= HOMMX_KIND_ELASTICITY_ISO;
   constexpr int BSV = EL ? D : 1, T = EL ? D * (D + 1) / 2 : D, NV = D + 1, NSUB = (D == 2) ? 2 : 6, NCODE = (D == 2) ? 9 : 27;
-  constexpr int NCOMP = KIND == HOMMX_KIND_POISSON_SCALAR ? 1
-                        : KIND == HOMMX_KIND_POISSON_MATRIX ? D * (D + 1) / 2
-                        : KIND == HOMMX_KIND_ELASTICITY_ISO ? 2
-                                                            : T * (T + 1) / 2;
+  constexpr int NCOMP = kind_sizes(D, KIND).n_comp;
   constexpr int NAL = ALSPLIT ? 1 : BSV;  // row components per thread
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long nodes = ALSPLIT ? idx / BSV : idx;
@@ -263,10 +249,7 @@ template <int D, int KIND, int WPC>
 __global__ __launch_bounds__(256) void k_c0(Geo G, const double* __restrict__ coef, double* __restrict__ C0, long long ncells) {
   constexpr bool EL = KIND >= HOMMX_KIND_ELASTICITY_ISO;
   constexpr int T = EL ? D * (D + 1) / 2 : D, TT = T * T;
-  constexpr int NCOMP = KIND == HOMMX_KIND_POISSON_SCALAR ? 1
-                        : KIND == HOMMX_KIND_POISSON_MATRIX ? D * (D + 1) / 2
-                        : KIND == HOMMX_KIND_ELASTICITY_ISO ? 2
-                                                            : T * (T + 1) / 2;
+  constexpr int NCOMP = kind_sizes(D, KIND).n_comp;
   constexpr int NTH = 64 * WPC;  // threads per cell
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long cell = WPC == 4 ? (long long)blockIdx.x : (long long)blockIdx.x * 4 + wave;
@@ -1107,12 +1090,12 @@ static int ws_reserve(BlockedWorkspace* ws, long long ncells, bool correctors) {
     if (hc > ws->hchunk) {
       ws_free_hist(ws);
       const long long mat = (long long)G.Bp * G.Bp;
-      BTRY(hipMalloc(&ws->hS, 8ll * hc * (G.n - 1) * mat));
-      BTRY(hipMalloc(&ws->hW, 8ll * hc * (G.n - 1) * mat));
-      BTRY(hipMalloc(&ws->hR, 8ll * hc * (G.n - 1) * 16 * G.Bp));
-      BTRY(hipMalloc(&ws->Xa, 8ll * hc * 16 * G.Bp));
-      BTRY(hipMalloc(&ws->Xb, 8ll * hc * 16 * G.Bp));
-      BTRY(hipMalloc(&ws->Y, 8ll * hc * 16 * G.Bp));
+      HIP_TRY(hipMalloc(&ws->hS, 8ll * hc * (G.n - 1) * mat));
+      HIP_TRY(hipMalloc(&ws->hW, 8ll * hc * (G.n - 1) * mat));
+      HIP_TRY(hipMalloc(&ws->hR, 8ll * hc * (G.n - 1) * 16 * G.Bp));
+      HIP_TRY(hipMalloc(&ws->Xa, 8ll * hc * 16 * G.Bp));
+      HIP_TRY(hipMalloc(&ws->Xb, 8ll * hc * 16 * G.Bp));
+      HIP_TRY(hipMalloc(&ws->Y, 8ll * hc * 16 * G.Bp));
       ws->hchunk = hc;
     }
   }
@@ -1123,19 +1106,19 @@ static int ws_reserve(BlockedWorkspace* ws, long long ncells, bool correctors) {
   if (chunk <= ws->chunk) return 0;
   ws_free_main(ws);
   const long long mat = (long long)G.Bp * G.Bp;
-  BTRY(hipMalloc(&ws->Kst, 8ll * chunk * G.ncode * G.bs * G.bs * G.nn));
-  BTRY(hipMalloc(&ws->Brhs, 8ll * chunk * G.t * G.bs * G.nn));
-  BTRY(hipMalloc(&ws->C0, 8ll * chunk * 36));
-  BTRY(hipMalloc(&ws->S, 8ll * chunk * mat));
-  BTRY(hipMalloc(&ws->W, 8ll * chunk * mat));
-  BTRY(hipMalloc(&ws->Sl, 8ll * chunk * mat));
-  BTRY(hipMalloc(&ws->V, 8ll * chunk * mat));
-  BTRY(hipMalloc(&ws->X, 8ll * chunk * mat));
-  BTRY(hipMalloc(&ws->T, 8ll * chunk * mat));
-  BTRY(hipMalloc(&ws->R, 8ll * chunk * 16 * G.Bp));
-  BTRY(hipMalloc(&ws->Rl, 8ll * chunk * 16 * G.Bp));
-  BTRY(hipMalloc(&ws->Vr, 8ll * chunk * 16 * G.Bp));
-  BTRY(hipMalloc(&ws->Gm, 8ll * chunk * 256));
+  HIP_TRY(hipMalloc(&ws->Kst, 8ll * chunk * G.ncode * G.bs * G.bs * G.nn));
+  HIP_TRY(hipMalloc(&ws->Brhs, 8ll * chunk * G.t * G.bs * G.nn));
+  HIP_TRY(hipMalloc(&ws->C0, 8ll * chunk * 36));
+  HIP_TRY(hipMalloc(&ws->S, 8ll * chunk * mat));
+  HIP_TRY(hipMalloc(&ws->W, 8ll * chunk * mat));
+  HIP_TRY(hipMalloc(&ws->Sl, 8ll * chunk * mat));
+  HIP_TRY(hipMalloc(&ws->V, 8ll * chunk * mat));
+  HIP_TRY(hipMalloc(&ws->X, 8ll * chunk * mat));
+  HIP_TRY(hipMalloc(&ws->T, 8ll * chunk * mat));
+  HIP_TRY(hipMalloc(&ws->R, 8ll * chunk * 16 * G.Bp));
+  HIP_TRY(hipMalloc(&ws->Rl, 8ll * chunk * 16 * G.Bp));
+  HIP_TRY(hipMalloc(&ws->Vr, 8ll * chunk * 16 * G.Bp));
+  HIP_TRY(hipMalloc(&ws->Gm, 8ll * chunk * 256));
   ws->chunk = chunk;
   return 0;
 }
@@ -1519,31 +1502,14 @@ void launch_center_corr(BlockedWorkspace* ws, double* corr, long long nc, hipStr
 void launch_assembly(BlockedWorkspace* ws, const double* coef, const double* Mm, long long nc, hipStream_t st, double* Kst, double* Brhs,
                      double* C0) {
   const Geo& G = ws->G;
-  // ---- K1: the stencil row of a node (3D elasticity: of one row component of a node) in registers, written once, no memset
-  {
-#define HOMMX_ASMR(D_, K_, SPLIT_)                                                                                          \
-  hipLaunchKernelGGL((k_assemble_reg<D_, K_, SPLIT_>), dim3(nblk(nc * G.nn * (SPLIT_ ? D_ : 1), 128)), dim3(128), 0, st, G, coef, Mm, \
-                     Kst, Brhs, nc)
-    if (G.dim == 2) {
-      if (G.kind == 0) HOMMX_ASMR(2, 0, 0); else if (G.kind == 1) HOMMX_ASMR(2, 1, 0); else if (G.kind == 2) HOMMX_ASMR(2, 2, 0); else HOMMX_ASMR(2, 3, 0);
-    } else {
-      if (G.kind == 0) HOMMX_ASMR(3, 0, 0); else if (G.kind == 1) HOMMX_ASMR(3, 1, 0); else if (G.kind == 2) HOMMX_ASMR(3, 2, 1); else HOMMX_ASMR(3, 3, 1);
-    }
-#undef HOMMX_ASMR
-  }
-  {
-#define HOMMX_C0(D_, K_)                                                                                                  \
-  do {                                                                                                                    \
-    if (G.n_el <= 4096) hipLaunchKernelGGL((k_c0<D_, K_, 1>), dim3(nblk(nc, 4)), dim3(256), 0, st, G, coef, C0, nc);   \
-    else hipLaunchKernelGGL((k_c0<D_, K_, 4>), dim3((unsigned)nc), dim3(256), 0, st, G, coef, C0, nc);                 \
-  } while (0)
-    if (G.dim == 2) {
-      if (G.kind == 0) HOMMX_C0(2, 0); else if (G.kind == 1) HOMMX_C0(2, 1); else if (G.kind == 2) HOMMX_C0(2, 2); else HOMMX_C0(2, 3);
-    } else {
-      if (G.kind == 0) HOMMX_C0(3, 0); else if (G.kind == 1) HOMMX_C0(3, 1); else if (G.kind == 2) HOMMX_C0(3, 2); else HOMMX_C0(3, 3);
-    }
-#undef HOMMX_C0
-  }
+  dispatch_dim_kind(G.dim, G.kind, [&](auto D, auto K) {
+    // ---- K1: the stencil row of a node (3D elasticity: of one row component of a node) in registers, written once, no memset
+    constexpr int SPLIT = D() == 3 && K() >= HOMMX_KIND_ELASTICITY_ISO;
+    hipLaunchKernelGGL((k_assemble_reg<D(), K(), SPLIT>), dim3(nblk(nc * G.nn * (SPLIT ? D() : 1), 128)), dim3(128), 0, st, G, coef, Mm, Kst,
+                       Brhs, nc);
+    if (G.n_el <= 4096) hipLaunchKernelGGL((k_c0<D(), K(), 1>), dim3(nblk(nc, 4)), dim3(256), 0, st, G, coef, C0, nc);
+    else hipLaunchKernelGGL((k_c0<D(), K(), 4>), dim3((unsigned)nc), dim3(256), 0, st, G, coef, C0, nc);
+  });
 }
 
 int blocked_reserve(BlockedWorkspace* ws, long long n_cells) {
@@ -1565,7 +1531,7 @@ int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, 
   const Geo& G = ws->G;
   const int n = G.n, Bp = G.Bp;
   const long long mat = (long long)Bp * Bp;
-  if (d_info) BTRY(hipMemsetAsync(d_info, 0, sizeof(int32_t) * ncells, st));
+  if (d_info) HIP_TRY(hipMemsetAsync(d_info, 0, sizeof(int32_t) * ncells, st));
   long long step_cells = d_corr ? std::min(ws->chunk, ws->hchunk) : ws->chunk;
   if (step_cells > 0) {  // equal chunks: a short tail chunk would run the small kernels of the inverse underfilled
     const long long nchunks = (ncells + step_cells - 1) / step_cells;
@@ -1582,15 +1548,15 @@ int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, 
       // (small_wave.h); 48 < b <= 64, or HOMMX_SMALL_WAVES = 2 | 4: that many waves per cell, matrices in LDS (small_fused.h)
       double* o = d_out + c0 * G.t * G.t;
       int32_t* inf = d_info ? d_info + c0 : nullptr;
-      BTRY(launch_small_fused(G, ws->Kst, ws->Brhs, ws->C0, o, inf, nc, ws->small_waves, st));
-      BTRY(hipGetLastError());
+      HIP_TRY(launch_small_fused(G, ws->Kst, ws->Brhs, ws->C0, o, inf, nc, ws->small_waves, st));
+      HIP_TRY(hipGetLastError());
       continue;
     }
     // ---- K2 init
-    BTRY(hipMemsetAsync(ws->S, 0, 8ll * nc * mat, st));
-    BTRY(hipMemsetAsync(ws->W, 0, 8ll * nc * mat, st));
-    BTRY(hipMemsetAsync(ws->Sl, 0, 8ll * nc * mat, st));
-    BTRY(hipMemsetAsync(ws->Gm, 0, 8ll * nc * 256, st));
+    HIP_TRY(hipMemsetAsync(ws->S, 0, 8ll * nc * mat, st));
+    HIP_TRY(hipMemsetAsync(ws->W, 0, 8ll * nc * mat, st));
+    HIP_TRY(hipMemsetAsync(ws->Sl, 0, 8ll * nc * mat, st));
+    HIP_TRY(hipMemsetAsync(ws->Gm, 0, 8ll * nc * 256, st));
     const long long scat = nc * (long long)Bp * (G.ncode / 3) * G.bs;
     hipLaunchKernelGGL(k_scatter_plane, dim3(nblk(scat)), dim3(256), 0, st, G, ws->Kst, ws->S, nc, 0, 0, 1);
     hipLaunchKernelGGL(k_scatter_plane, dim3(nblk(scat)), dim3(256), 0, st, G, ws->Kst, ws->W, nc, n - 1, +1, 0);
@@ -1605,9 +1571,9 @@ int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, 
         hipLaunchKernelGGL(k_scatter_plane, dim3(nblk(scat)), dim3(256), 0, st, G, ws->Kst, ws->W, nc, n - 1, -1, 0);
       invert(c, ws->S, 0, Bp, ws->T);                                                                   // S <- S^-1
       if (d_corr) {  // keep what the back substitution needs: S_j^-1, W_j (incl. E on the last step), R_j
-        BTRY(hipMemcpyAsync(ws->hS + (long long)j * nc * mat, ws->S, 8ll * nc * mat, hipMemcpyDeviceToDevice, st));
-        BTRY(hipMemcpyAsync(ws->hW + (long long)j * nc * mat, ws->W, 8ll * nc * mat, hipMemcpyDeviceToDevice, st));
-        BTRY(hipMemcpyAsync(ws->hR + (long long)j * nc * 16 * Bp, ws->R, 8ll * nc * 16 * Bp, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ws->hS + (long long)j * nc * mat, ws->S, 8ll * nc * mat, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ws->hW + (long long)j * nc * mat, ws->W, 8ll * nc * mat, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ws->hR + (long long)j * nc * 16 * Bp, ws->R, 8ll * nc * 16 * Bp, hipMemcpyDeviceToDevice, st));
       }
       gemm(c, false, false, Bp, Bp, Bp, 1.0, ws->W, Bp, mat, ws->S, Bp, mat, 0.0, ws->V, Bp, mat);      // V = W Sinv
       gemm(c, false, true, Bp, Bp, Bp, -1.0, ws->V, Bp, mat, ws->W, Bp, mat, 1.0, ws->Sl, Bp, mat, 1);  // S_last -= V W^T (lower tiles)
@@ -1638,7 +1604,7 @@ int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, 
       double* Xn = ws->Xa;  // chi_{j+1}
       double* Xc = ws->Xb;  // chi_j
       for (int j = n - 2; j >= 0; --j) {
-        BTRY(hipMemcpyAsync(ws->Y, ws->hR + (long long)j * nc * sx, 8ll * nc * sx, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ws->Y, ws->hR + (long long)j * nc * sx, 8ll * nc * sx, hipMemcpyDeviceToDevice, st));
         gemm(c, false, false, 16, Bp, Bp, -1.0, ws->Vr, Bp, sx, ws->hW + (long long)j * nc * mat, Bp, mat, 1.0, ws->Y, Bp, sx);
         if (j < n - 2) right_mult_Et(c, Xn, ws->Y, 16, j, -1.0, +1, 1);  // Y -= chi_{j+1} E_j  (E_j[r][c] = K[(c, j), (r, j+1)])
         gemm(c, false, false, 16, Bp, Bp, 1.0, ws->Y, Bp, sx, ws->hS + (long long)j * nc * mat, Bp, mat, 0.0, Xc, Bp, sx);
@@ -1649,7 +1615,7 @@ int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, 
     }
     // ---- K3
     hipLaunchKernelGGL(k_finalize, dim3(nblk(nc * G.t * G.t)), dim3(256), 0, st, G, ws->C0, ws->Gm, d_out + c0 * G.t * G.t, nc);
-    BTRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
   return 0;
 }

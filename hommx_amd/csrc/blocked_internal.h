@@ -107,8 +107,6 @@ const int* ensure_tilemap(BlockedWorkspace* ws, int ty);
 // size a multiple of 32); `tmp`: scratch of at least size^2 / 2 doubles per matrix, batch stride c.sT
 void invert(const Ctx& c, double* S, int off, int size, double* tmp);
 
-extern thread_local std::string g_berr;
-
 // supernode tree of the n^d torus (TreeBuilder: two planes per periodic direction, one per open one) with its stencil couplings
 void mf_tree_structured(const Geo& G, MfTree* T);
 // leaf size and ring-split depth of both tree builders (HOMMX_MF_LEAF, HOMMX_MF_SPLIT_DEPTH)

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/hommx_hip.h"
 
 namespace hommx {
@@ -17,6 +19,21 @@ constexpr KindSizes kind_sizes(int dim, int kind) {
          : kind == HOMMX_KIND_POISSON_MATRIX ? KindSizes{1, dim, te}
          : kind == HOMMX_KIND_ELASTICITY_ISO ? KindSizes{dim, te, 2}
                                              : KindSizes{dim, te, te * (te + 1) / 2};
+}
+
+// f(DIM, KIND) with the (validated) dim in {2, 3} and kind in 0..3 of a plan as std::integral_constants: the one list of the eight
+// (DIM, KIND) pairs the kernels are instantiated for
+template <typename F>
+auto dispatch_dim_kind(int dim, int kind, F&& f) {
+  auto with_dim = [&](auto D) {
+    switch (kind) {
+      case 0: return f(D, std::integral_constant<int, 0>{});
+      case 1: return f(D, std::integral_constant<int, 1>{});
+      case 2: return f(D, std::integral_constant<int, 2>{});
+      default: return f(D, std::integral_constant<int, 3>{});
+    }
+  };
+  return dim == 2 ? with_dim(std::integral_constant<int, 2>{}) : with_dim(std::integral_constant<int, 3>{});
 }
 
 // Where the per-element coefficient of a scalar Poisson cell comes from (device samplers).
@@ -94,7 +111,6 @@ int blocked_workspace_create(BlockedWorkspace** out, int dim, int n, int kind);
 void blocked_workspace_destroy(BlockedWorkspace* ws);
 int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, const double* d_M,
                   double* d_out, int32_t* d_info, hipStream_t stream, double* d_corr = nullptr);
-const char* blocked_last_error();
 // allocate the workspace of the route for batches of up to n_cells (what the first solve would otherwise do)
 int blocked_reserve(BlockedWorkspace* ws, long long n_cells);
 // "small_wave" (b <= 48), "small_fused" (48 < b <= 64), "blocked", "multifrontal" or, on a mesh, "mesh_multifrontal": the route

@@ -7,7 +7,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <string>
 #include <vector>
 
 #include "../../include/hommx_hip.h"
@@ -16,22 +15,31 @@ namespace hommx {
 
 struct MeshPlan;
 
-// what both mesh routes take from a validated descriptor
+// What the routes take from a validated descriptor, made once per plan or analysis call.
 struct MeshGeom {
   std::vector<double> grads, vol;  // [n_el][dim+1][dim] P1 gradients, [n_el] volumes (from the unfolded coordinates)
   std::vector<int> ptr, adj;       // node graph: CSR, neighbours sorted ascending, the node itself not included
+  std::vector<double> y;           // [n_nodes][dim] node coordinates folded into [0, 1): the max faces fold onto the min faces
 };
-// Every check of hommx_mesh_analyze but the front width, in the same order and with the same messages (mesh_last_error()).
+// The one place a descriptor is validated: every check of hommx_mesh_analyze but the front width.
 int mesh_check(const hommx_mesh_desc* d, MeshGeom* g);
 
-// Validates the descriptor and runs the symbolic phase.  out == nullptr: analysis only (hommx_mesh_analyze).  Returns 0 or HOMMX_EINVAL /
-// HOMMX_ENOMEM with the message in mesh_last_error().
-int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width, double* flops_per_solve);
-// device tables of the plan (after mesh_analyze with out != nullptr; the caller has selected the plan's device)
-int mesh_upload(MeshPlan* m);
+// The element geometry of a mesh plan on the device: one block, owned by the plan (api.hip).  The kernel arguments of both routes
+// (MeshDev, MeshAsm) and of the reconstruction (ReconArgs) point into it.
+struct MeshGeomDev {
+  void* block;
+  const int32_t* el_nodes;  // [n_el][dim+1] the descriptor's element table
+  const double* grads;      // [n_el][dim+1][dim]
+  const double* vol;        // [n_el]
+};
+int mesh_geom_upload(const hommx_mesh_desc* d, const MeshGeom& g, MeshGeomDev* out);
+
+// The symbolic phase of the frontal route on a checked mesh.  out == nullptr: analysis only (hommx_mesh_analyze).  Returns 0 or
+// HOMMX_EINVAL / HOMMX_ENOMEM.
+int mesh_analyze(const hommx_mesh_desc* d, const MeshGeom& g, MeshPlan** out, int32_t* front_width, double* flops_per_solve);
+// device tables of the plan (after mesh_analyze with out != nullptr; the caller has selected the plan's device and uploaded the geometry)
+int mesh_upload(MeshPlan* m, const MeshGeomDev& geo);
 void mesh_destroy(MeshPlan* m);
-const char* mesh_last_error();
-int mesh_error(int code, const std::string& msg);  // sets the message mesh_last_error() returns
 
 int32_t mesh_front_width(const MeshPlan* m);
 double mesh_flops_per_cell(const MeshPlan* m);

@@ -19,49 +19,27 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <new>
 #include <string>
 #include <vector>
 
+#include "host_common.h"
+#include "kernels.h"
 #include "mesh_elem.h"
 #include "mesh_front.h"
 
 namespace hommx {
 
 namespace {
-thread_local std::string g_merr;
-int mfail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_merr = buf;
-  return code;
-}
-#define MTRY(expr)                                                                                                      \
-  do {                                                                                                                  \
-    hipError_t e__ = (expr);                                                                                            \
-    if (e__ != hipSuccess)                                                                                              \
-      return mfail(e__ == hipErrorOutOfMemory ? HOMMX_ENOMEM : HOMMX_EHIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
-  } while (0)
-
 constexpr int kThreads = 256;
 constexpr int kRed = 21;  // t (t + 1) / 2 for t <= 6: the C0 partial sums
 }  // namespace
 
-const char* mesh_last_error() { return g_merr.c_str(); }
-int mesh_error(int code, const std::string& msg) {
-  g_merr = msg;
-  return code;
-}
-
 // device view of the symbolic phase (all arrays on the plan's device)
 struct MeshDev {
   int n_el, n_nodes, n_steps, S;  // S = t + front width: rows of the largest front
-  const double* grads;            // [n_el][dim+1][dim]  P1 gradients in the caller's element order
+  const double* grads;            // [n_el][dim+1][dim]  P1 gradients in the caller's element order (the plan's MeshGeomDev block)
   const double* vol;              // [n_el]
   const int* el_slot;             // [n_el][dim+1]  front slot of every vertex's node, -1 for the pinned node
   const int* el_seq;              // elements in assembly order
@@ -81,11 +59,10 @@ struct MeshPlan {
   double flops = 0.0;
   int n_steps = 0, nslots = 0, S = 0;
   std::vector<int> order, pos;
-  std::vector<double> grads, vol;
   std::vector<int> el_slot, el_seq, grp_ptr, step_grp, step_slot, step_S, step_node, owner;
   std::vector<long long> piv_off;
   MeshDev dev{};
-  void* d_tables = nullptr;  // one allocation holds every device table
+  void* d_tables = nullptr;  // one allocation holds every device table of the symbolic phase
   double* d_arena = nullptr;
   int32_t* d_binfo = nullptr;
   long long cap_arena_cells = 0;
@@ -102,10 +79,9 @@ template <int DIM, int KIND>
 __global__ void __launch_bounds__(kThreads) k_mesh_front(MeshDev G, const double* __restrict__ coef, const double* __restrict__ Mall,
                                                          double* __restrict__ out, int32_t* __restrict__ info, double* __restrict__ arena,
                                                          long long arena_per_cell) {
-  constexpr int T = KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM;
-  constexpr int BS = KIND >= 2 ? DIM : 1;
+  constexpr KindSizes ks = kind_sizes(DIM, KIND);
+  constexpr int T = ks.t, BS = ks.bs, NCOMP = ks.n_comp;
   constexpr int NV = DIM + 1, NL = NV * BS;
-  constexpr int NCOMP = KIND == 0 ? 1 : KIND == 1 ? DIM * (DIM + 1) / 2 : KIND == 2 ? 2 : T * (T + 1) / 2;
   constexpr int NKK = NL * (NL + 1) / 2, NE = NKK + NL * T;  // front entries one element adds (K lower triangle, B)
   extern __shared__ double smem[];
   const int S = G.S;
@@ -393,18 +369,7 @@ int width_of(const std::vector<int>& order, const hommx_mesh_desc* d) {
 
 // coordinate sweep: nodes sorted by their (folded) coordinate along `axis`, ties by the other axes -- two cross-sections wide on a
 // periodic mesh, where the level sets of a breadth-first search from one node grow to twice that
-std::vector<int> sweep_order(const hommx_mesh_desc* d, int axis) {
-  const int n = (int)d->n_nodes, ne = (int)d->n_el, dim = d->dim, nv = dim + 1;
-  std::vector<double> y((size_t)n * dim, 0.0);
-  for (int e = 0; e < ne; ++e)
-    for (int a = 0; a < nv; ++a) {
-      const int v = d->el_nodes[e * nv + a];
-      for (int c = 0; c < dim; ++c) {
-        double q = d->el_x[((size_t)e * nv + a) * dim + c];
-        q -= std::floor(q + 1e-9);  // the max faces fold onto the min faces
-        y[(size_t)v * dim + c] = q;
-      }
-    }
+std::vector<int> sweep_order(int n, int dim, const std::vector<double>& y, int axis) {
   std::vector<int> ord(n);
   for (int v = 0; v < n; ++v) ord[v] = v;
   std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
@@ -421,12 +386,12 @@ std::vector<int> sweep_order(const hommx_mesh_desc* d, int axis) {
 }  // namespace
 
 int mesh_check(const hommx_mesh_desc* d, MeshGeom* g) {
-  if (!d) return mfail(HOMMX_EINVAL, "null descriptor");
-  if (d->dim != 2 && d->dim != 3) return mfail(HOMMX_EINVAL, "dim must be 2 or 3, got %d", d->dim);
-  if (d->kind < 0 || d->kind > 3) return mfail(HOMMX_EINVAL, "unknown kind %d", d->kind);
-  if (d->n_nodes < 2 || d->n_nodes > 0x3fffffffll) return mfail(HOMMX_EINVAL, "n_nodes must be in [2, 2^30), got %lld", (long long)d->n_nodes);
-  if (d->n_el < 1 || d->n_el > 0x3fffffffll) return mfail(HOMMX_EINVAL, "n_el must be in [1, 2^30), got %lld", (long long)d->n_el);
-  if (!d->el_nodes || !d->el_x) return mfail(HOMMX_EINVAL, "null el_nodes / el_x");
+  if (!d) return fail(HOMMX_EINVAL, "null descriptor");
+  if (d->dim != 2 && d->dim != 3) return fail(HOMMX_EINVAL, "dim must be 2 or 3, got %d", d->dim);
+  if (d->kind < 0 || d->kind > 3) return fail(HOMMX_EINVAL, "unknown kind %d", d->kind);
+  if (d->n_nodes < 2 || d->n_nodes > 0x3fffffffll) return fail(HOMMX_EINVAL, "n_nodes must be in [2, 2^30), got %lld", (long long)d->n_nodes);
+  if (d->n_el < 1 || d->n_el > 0x3fffffffll) return fail(HOMMX_EINVAL, "n_el must be in [1, 2^30), got %lld", (long long)d->n_el);
+  if (!d->el_nodes || !d->el_x) return fail(HOMMX_EINVAL, "null el_nodes / el_x");
   const int dim = d->dim, nv = dim + 1;
   const int n = (int)d->n_nodes, ne = (int)d->n_el;
 
@@ -435,14 +400,14 @@ int mesh_check(const hommx_mesh_desc* d, MeshGeom* g) {
   for (int e = 0; e < ne; ++e)
     for (int a = 0; a < nv; ++a) {
       const int v = d->el_nodes[e * nv + a];
-      if (v < 0 || v >= n) return mfail(HOMMX_EINVAL, "element %d: node %d out of range [0, %d)", e, v, n);
+      if (v < 0 || v >= n) return fail(HOMMX_EINVAL, "element %d: node %d out of range [0, %d)", e, v, n);
       for (int b = 0; b < a; ++b)
         if (d->el_nodes[e * nv + b] == v)
-          return mfail(HOMMX_EINVAL, "element %d: periodic node %d appears twice (the mesh is too coarse for its periodic folding)", e, v);
+          return fail(HOMMX_EINVAL, "element %d: periodic node %d appears twice (the mesh is too coarse for its periodic folding)", e, v);
       used[v] = 1;
     }
   for (int v = 0; v < n; ++v)
-    if (!used[v]) return mfail(HOMMX_EINVAL, "node %d belongs to no element", v);
+    if (!used[v]) return fail(HOMMX_EINVAL, "node %d belongs to no element", v);
 
   // geometry: P1 gradients and volumes from the unfolded coordinates
   g->grads.assign((size_t)ne * nv * dim, 0.0);
@@ -470,7 +435,7 @@ int mesh_check(const hommx_mesh_desc* d, MeshGeom* g) {
         }
     }
     const double v = std::fabs(det) / (dim == 2 ? 2.0 : 6.0);
-    if (!(v > 1e-10 / ne) || !std::isfinite(v)) return mfail(HOMMX_EINVAL, "element %d is degenerate (volume %.3g)", e, v);
+    if (!(v > 1e-10 / ne) || !std::isfinite(v)) return fail(HOMMX_EINVAL, "element %d is degenerate (volume %.3g)", e, v);
     g->vol[e] = v;
     vsum += v;
     // grad phi_a = column a - 1 of J^-1 (a >= 1), grad phi_0 = -sum of the others
@@ -482,7 +447,7 @@ int mesh_check(const hommx_mesh_desc* d, MeshGeom* g) {
       }
   }
   if (!(std::fabs(vsum - 1.0) <= 1e-10))
-    return mfail(HOMMX_EINVAL, "element volumes sum to %.15g, expected 1 (the unit cell)", vsum);
+    return fail(HOMMX_EINVAL, "element volumes sum to %.15g, expected 1 (the unit cell)", vsum);
 
   // node graph (for the order and the connectivity check)
   std::vector<int>& ptr = g->ptr;
@@ -512,25 +477,40 @@ int mesh_check(const hommx_mesh_desc* d, MeshGeom* g) {
           seen[adj[e]] = 1;
           q.push_back(adj[e]);
         }
-    if ((int)q.size() != n) return mfail(HOMMX_EINVAL, "the mesh is not connected (%d of %d nodes reachable from node 0)", (int)q.size(), n);
+    if ((int)q.size() != n) return fail(HOMMX_EINVAL, "the mesh is not connected (%d of %d nodes reachable from node 0)", (int)q.size(), n);
   }
   if (d->order) {
     std::vector<char> seen(n, 0);
     for (int k = 0; k < n; ++k) {
       const int v = d->order[k];
-      if (v < 0 || v >= n || seen[v]) return mfail(HOMMX_EINVAL, "order is not a permutation of [0, %d): entry %d is %d", n, k, v);
+      if (v < 0 || v >= n || seen[v]) return fail(HOMMX_EINVAL, "order is not a permutation of [0, %d): entry %d is %d", n, k, v);
       seen[v] = 1;
     }
   }
+  // folded node coordinates (the coordinate sweeps of the frontal route, the bisection of the tree route)
+  g->y.assign((size_t)n * dim, 0.0);
+  for (int e = 0; e < ne; ++e)
+    for (int a = 0; a < nv; ++a) {
+      const int v = d->el_nodes[e * nv + a];
+      for (int c = 0; c < dim; ++c) {
+        double q = d->el_x[((size_t)e * nv + a) * dim + c];
+        q -= std::floor(q + 1e-9);  // the max faces fold onto the min faces
+        g->y[(size_t)v * dim + c] = q;
+      }
+    }
   return HOMMX_OK;
 }
 
-int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width, double* flops_per_solve) {
+int mesh_geom_upload(const hommx_mesh_desc* d, const MeshGeom& g, MeshGeomDev* out) {
+  return upload_packed(&out->block, {{d->el_nodes, sizeof(int32_t) * (size_t)d->n_el * (d->dim + 1), (const void**)&out->el_nodes},
+                                     {g.grads.data(), sizeof(double) * g.grads.size(), (const void**)&out->grads},
+                                     {g.vol.data(), sizeof(double) * g.vol.size(), (const void**)&out->vol}});
+}
+
+int mesh_analyze(const hommx_mesh_desc* d, const MeshGeom& geo, MeshPlan** out, int32_t* front_width, double* flops_per_solve) {
   if (out) *out = nullptr;
-  MeshGeom geo;
-  if (int rc = mesh_check(d, &geo)) return rc;
   MeshPlan* m = new (std::nothrow) MeshPlan();
-  if (!m) return mfail(HOMMX_ENOMEM, "host allocation failed");
+  if (!m) return fail(HOMMX_ENOMEM, "host allocation failed");
   struct Guard {
     MeshPlan*& p;
     ~Guard() { delete p; }
@@ -539,14 +519,13 @@ int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width,
   const int n = (int)d->n_nodes, ne = (int)d->n_el;
   m->dim = dim;
   m->kind = d->kind;
-  m->bs = d->kind >= HOMMX_KIND_ELASTICITY_ISO ? dim : 1;
-  m->t = d->kind >= HOMMX_KIND_ELASTICITY_ISO ? dim * (dim + 1) / 2 : dim;
-  m->n_comp = d->kind == 0 ? 1 : d->kind == 1 ? dim * (dim + 1) / 2 : d->kind == 2 ? 2 : m->t * (m->t + 1) / 2;
+  const KindSizes ks = kind_sizes(dim, d->kind);
+  m->bs = ks.bs;
+  m->t = ks.t;
+  m->n_comp = ks.n_comp;
   m->n_nodes = n;
   m->n_el = ne;
   const int bs = m->bs, t = m->t;
-  m->grads.swap(geo.grads);
-  m->vol.swap(geo.vol);
   const std::vector<int>& ptr = geo.ptr;
   const std::vector<int>& adj = geo.adj;
   if (d->order) {
@@ -556,7 +535,7 @@ int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width,
     m->order = rcm_order(n, ptr, adj);
     int best = width_of(m->order, d);
     for (int axis = 0; axis < dim; ++axis) {
-      std::vector<int> o = sweep_order(d, axis);
+      std::vector<int> o = sweep_order(n, dim, geo.y, axis);
       const int w = width_of(o, d);
       if (w < best) {
         best = w;
@@ -658,7 +637,7 @@ int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width,
   if (front_width) *front_width = m->front_width;
   if (flops_per_solve) *flops_per_solve = flops;
   if (m->front_width > HOMMX_MESH_MAX_FRONT)
-    return mfail(HOMMX_EINVAL, "front width %d of the elimination order exceeds HOMMX_MESH_MAX_FRONT = %d (unknowns)", m->front_width,
+    return fail(HOMMX_EINVAL, "front width %d of the elimination order exceeds HOMMX_MESH_MAX_FRONT = %d (unknowns)", m->front_width,
                  HOMMX_MESH_MAX_FRONT);
   if (!out) return HOMMX_OK;
 
@@ -694,39 +673,20 @@ int mesh_analyze(const hommx_mesh_desc* d, MeshPlan** out, int32_t* front_width,
   return HOMMX_OK;
 }
 
-int mesh_upload(MeshPlan* m) {
-  // one allocation, 256-byte aligned pieces
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  struct Piece {
-    const void* src;
-    size_t bytes;
-    const void** dst;
-  };
+int mesh_upload(MeshPlan* m, const MeshGeomDev& geo) {
   MeshDev& G = m->dev;
-  Piece pcs[] = {
-      {m->grads.data(), sizeof(double) * m->grads.size(), (const void**)&G.grads},
-      {m->vol.data(), sizeof(double) * m->vol.size(), (const void**)&G.vol},
-      {m->el_slot.data(), sizeof(int) * m->el_slot.size(), (const void**)&G.el_slot},
-      {m->el_seq.data(), sizeof(int) * m->el_seq.size(), (const void**)&G.el_seq},
-      {m->grp_ptr.data(), sizeof(int) * m->grp_ptr.size(), (const void**)&G.grp_ptr},
-      {m->step_grp.data(), sizeof(int) * m->step_grp.size(), (const void**)&G.step_grp},
-      {m->step_slot.data(), sizeof(int) * m->step_slot.size(), (const void**)&G.step_slot},
-      {m->step_S.data(), sizeof(int) * m->step_S.size(), (const void**)&G.step_S},
-      {m->piv_off.data(), sizeof(long long) * m->piv_off.size(), (const void**)&G.piv_off},
-      {m->step_node.data(), sizeof(int) * m->step_node.size(), (const void**)&G.step_node},
-      {m->owner.data(), sizeof(int) * m->owner.size(), (const void**)&G.owner},
-  };
-  size_t total = 0;
-  for (const Piece& p : pcs) total += up(p.bytes);
-  MTRY(hipMalloc(&m->d_tables, total));
-  std::vector<char> host(total, 0);
-  size_t off = 0;
-  for (const Piece& p : pcs) {
-    if (p.bytes) std::copy((const char*)p.src, (const char*)p.src + p.bytes, host.data() + off);
-    *p.dst = (const char*)m->d_tables + off;
-    off += up(p.bytes);
-  }
-  MTRY(hipMemcpy(m->d_tables, host.data(), total, hipMemcpyHostToDevice));
+  G.grads = geo.grads;
+  G.vol = geo.vol;
+  if (int rc = upload_packed(&m->d_tables, {{m->el_slot.data(), sizeof(int) * m->el_slot.size(), (const void**)&G.el_slot},
+                                            {m->el_seq.data(), sizeof(int) * m->el_seq.size(), (const void**)&G.el_seq},
+                                            {m->grp_ptr.data(), sizeof(int) * m->grp_ptr.size(), (const void**)&G.grp_ptr},
+                                            {m->step_grp.data(), sizeof(int) * m->step_grp.size(), (const void**)&G.step_grp},
+                                            {m->step_slot.data(), sizeof(int) * m->step_slot.size(), (const void**)&G.step_slot},
+                                            {m->step_S.data(), sizeof(int) * m->step_S.size(), (const void**)&G.step_S},
+                                            {m->piv_off.data(), sizeof(long long) * m->piv_off.size(), (const void**)&G.piv_off},
+                                            {m->step_node.data(), sizeof(int) * m->step_node.size(), (const void**)&G.step_node},
+                                            {m->owner.data(), sizeof(int) * m->owner.size(), (const void**)&G.owner}}))
+    return rc;
   G.n_el = (int)m->n_el;
   G.n_nodes = (int)m->n_nodes;
   G.n_steps = m->n_steps;
@@ -802,22 +762,13 @@ int mesh_solve(MeshPlan* m, long long ncells, const double* d_coef, const double
                double* d_corr) {
   if (ncells <= 0) return HOMMX_OK;
   auto front = [&](long long nc, const double* coef, const double* M, double* out, int32_t* info, double* arena) -> hipError_t {
-    switch (m->dim * 10 + m->kind) {
-      case 20: return launch_front<2, 0>(m, nc, coef, M, out, info, arena, st);
-      case 21: return launch_front<2, 1>(m, nc, coef, M, out, info, arena, st);
-      case 22: return launch_front<2, 2>(m, nc, coef, M, out, info, arena, st);
-      case 23: return launch_front<2, 3>(m, nc, coef, M, out, info, arena, st);
-      case 30: return launch_front<3, 0>(m, nc, coef, M, out, info, arena, st);
-      case 31: return launch_front<3, 1>(m, nc, coef, M, out, info, arena, st);
-      case 32: return launch_front<3, 2>(m, nc, coef, M, out, info, arena, st);
-      default: return launch_front<3, 3>(m, nc, coef, M, out, info, arena, st);
-    }
+    return dispatch_dim_kind(m->dim, m->kind, [&](auto D, auto K) { return launch_front<D(), K()>(m, nc, coef, M, out, info, arena, st); });
   };
   const int d = m->dim, t = m->t;
   if (!d_corr) {
     for (long long c0 = 0; c0 < ncells; c0 += 0x7fffffffll) {
       const long long nc = std::min(ncells - c0, 0x7fffffffll);
-      MTRY(front(nc, d_coef + c0 * m->n_el * m->n_comp, d_M ? d_M + c0 * d * d : nullptr, d_out + c0 * t * t, d_info ? d_info + c0 : nullptr,
+      HIP_TRY(front(nc, d_coef + c0 * m->n_el * m->n_comp, d_M ? d_M + c0 * d * d : nullptr, d_out + c0 * t * t, d_info ? d_info + c0 : nullptr,
                  nullptr));
     }
     return HOMMX_OK;
@@ -829,16 +780,16 @@ int mesh_solve(MeshPlan* m, long long ncells, const double* d_coef, const double
     m->d_arena = nullptr;
     m->d_binfo = nullptr;
     m->cap_arena_cells = 0;
-    MTRY(hipMalloc(&m->d_arena, sizeof(double) * chunk * arena_per_cell(m)));
-    MTRY(hipMalloc(&m->d_binfo, sizeof(int32_t) * chunk));
+    HIP_TRY(hipMalloc(&m->d_arena, sizeof(double) * chunk * arena_per_cell(m)));
+    HIP_TRY(hipMalloc(&m->d_binfo, sizeof(int32_t) * chunk));
     m->cap_arena_cells = chunk;
   }
   const long long nu = m->n_nodes * m->bs;
   for (long long c0 = 0; c0 < ncells; c0 += chunk) {
     const long long nc = std::min(ncells - c0, chunk);
-    MTRY(front(nc, d_coef + c0 * m->n_el * m->n_comp, d_M ? d_M + c0 * d * d : nullptr, d_out + c0 * t * t, m->d_binfo, m->d_arena));
-    MTRY(launch_backsub(m, nc, m->d_arena, m->d_binfo, d_corr + c0 * t * nu, st));
-    if (d_info) MTRY(hipMemcpyAsync(d_info + c0, m->d_binfo, sizeof(int32_t) * nc, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(front(nc, d_coef + c0 * m->n_el * m->n_comp, d_M ? d_M + c0 * d * d : nullptr, d_out + c0 * t * t, m->d_binfo, m->d_arena));
+    HIP_TRY(launch_backsub(m, nc, m->d_arena, m->d_binfo, d_corr + c0 * t * nu, st));
+    if (d_info) HIP_TRY(hipMemcpyAsync(d_info + c0, m->d_binfo, sizeof(int32_t) * nc, hipMemcpyDeviceToDevice, st));
   }
   return HOMMX_OK;
 }

@@ -16,7 +16,7 @@ namespace hommx {
 // device view of the assembly tables (K1 of a mesh plan, launch_mesh_assembly)
 struct MeshAsm {
   int dim, kind, nn, n_el, ncode;
-  const double* grads;   // [n_el][dim+1][dim]
+  const double* grads;   // [n_el][dim+1][dim]  in the plan's geometry block (MeshGeomDev)
   const double* vol;     // [n_el]
   const int* cptr;       // [ncode * nn + 1] contributions of (code c, node i) at cptr[c nn + i] .. cptr[c nn + i + 1]
   const int* centry;     // element << 4 | r << 2 | s: local vertex r is node i, s the node of code c; ascending element order
@@ -27,8 +27,10 @@ struct MeshAsm {
 void launch_mesh_assembly(const MeshAsm& a, const double* coef, const double* Mm, long long nc, hipStream_t st, double* Kst, double* Brhs,
                           double* C0);
 
-struct MeshTreePlan;  // host-side analysis: geometry, tree, coupling codes, assembly tables
+struct MeshTreePlan;  // host-side analysis: tree, coupling codes, assembly tables
 struct BlockedWorkspace;
+struct MeshGeom;     // mesh_front.h
+struct MeshGeomDev;
 
 // what hommx_mesh_analyze_tree reports
 struct MeshTreeInfo {
@@ -36,13 +38,13 @@ struct MeshTreeInfo {
   double flops;
 };
 
-// Validates the descriptor (mesh_check) and runs the symbolic phase: tree, codes, assembly tables; with `info`, the host half of the
-// multifrontal plan as well.  out == nullptr: analysis only.  supernode_of_node [n_nodes] / parent [n_fronts] may be null.  Errors:
-// mesh_last_error().
-int mesh_tree_analyze(const hommx_mesh_desc* d, MeshTreePlan** out, MeshTreeInfo* info, int32_t* supernode_of_node, int32_t* parent);
+// The symbolic phase on a checked mesh (mesh_front.h: mesh_check): tree, codes, assembly tables; with `info`, the host half of the
+// multifrontal plan as well.  out == nullptr: analysis only.  supernode_of_node [n_nodes] / parent [n_fronts] may be null.
+int mesh_tree_analyze(const hommx_mesh_desc* d, const MeshGeom& g, MeshTreePlan** out, MeshTreeInfo* info, int32_t* supernode_of_node,
+                      int32_t* parent);
 // the plan's workspace of the blocked family on the current device: the assembly tables uploaded, the tree moved in, its multifrontal plan
-// built; `m` keeps nothing the workspace needs
-int mesh_tree_workspace(MeshTreePlan* m, BlockedWorkspace** out);
+// built; `m` keeps nothing the workspace needs.  The element geometry stays in the plan's block `geo`
+int mesh_tree_workspace(MeshTreePlan* m, const MeshGeomDev& geo, BlockedWorkspace** out);
 void mesh_tree_destroy(MeshTreePlan* m);
 
 }  // namespace hommx

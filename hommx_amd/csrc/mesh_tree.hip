@@ -17,14 +17,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <memory>
 #include <new>
-#include <string>
 #include <utility>
 #include <vector>
 
 #include "blocked_internal.h"
+#include "host_common.h"
 #include "kernels.h"
 #include "mesh_elem.h"
 #include "mesh_front.h"
@@ -35,7 +34,6 @@ namespace hommx {
 struct MeshTreePlan {
   Geo G{};
   MfTree tree;
-  std::vector<double> grads, vol;
   std::vector<int> cptr, centry, self_code;
 };
 
@@ -48,10 +46,9 @@ struct MeshTreePlan {
 template <int DIM, int KIND>
 __global__ __launch_bounds__(256) void k_mesh_assemble(MeshAsm A, const double* __restrict__ coef, const double* __restrict__ Mall,
                                                        double* __restrict__ Kst, double* __restrict__ Brhs, long long nc) {
-  constexpr int T = KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM;
-  constexpr int BS = KIND >= 2 ? DIM : 1;
+  constexpr KindSizes ks = kind_sizes(DIM, KIND);
+  constexpr int T = ks.t, BS = ks.bs, NCOMP = ks.n_comp;
   constexpr int NV = DIM + 1;
-  constexpr int NCOMP = KIND == 0 ? 1 : KIND == 1 ? DIM * (DIM + 1) / 2 : KIND == 2 ? 2 : T * (T + 1) / 2;
   const int nn = A.nn;
   const long long per_cell = (long long)(A.ncode + 1) * nn;
   const long long total = nc * per_cell;
@@ -141,8 +138,8 @@ __global__ __launch_bounds__(256) void k_mesh_assemble(MeshAsm A, const double* 
 // butterfly per wave, the four wave totals added in order -- the same summation for every cell wherever it sits in the batch
 template <int DIM, int KIND>
 __global__ __launch_bounds__(256) void k_mesh_c0(MeshAsm A, const double* __restrict__ coef, double* __restrict__ C0, long long nc) {
-  constexpr int T = KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM;
-  constexpr int NCOMP = KIND == 0 ? 1 : KIND == 1 ? DIM * (DIM + 1) / 2 : KIND == 2 ? 2 : T * (T + 1) / 2;
+  constexpr KindSizes ks = kind_sizes(DIM, KIND);
+  constexpr int T = ks.t, NCOMP = ks.n_comp;
   constexpr int NTRI = T * (T + 1) / 2;
   __shared__ double red[4][NTRI];
   const int tid = threadIdx.x;
@@ -183,22 +180,10 @@ void launch_mesh_assembly(const MeshAsm& a, const double* coef, const double* Mm
   const long long work = nc * (long long)(a.ncode + 1) * a.nn;
   const unsigned blocks = (unsigned)std::max(1ll, std::min((work + 255) / 256, 1ll << 20));  // x 256 = 2^28 work-items per launch at most
   const unsigned cblocks = (unsigned)std::max(1ll, std::min(nc, 1ll << 20));
-#define HOMMX_MA(D_, K_)                                                                                               \
-  do {                                                                                                                 \
-    hipLaunchKernelGGL((k_mesh_assemble<D_, K_>), dim3(blocks), dim3(256), 0, st, a, coef, Mm, Kst, Brhs, nc);          \
-    hipLaunchKernelGGL((k_mesh_c0<D_, K_>), dim3(cblocks), dim3(256), 0, st, a, coef, C0, nc);                          \
-  } while (0)
-  switch (a.dim * 10 + a.kind) {
-    case 20: HOMMX_MA(2, 0); break;
-    case 21: HOMMX_MA(2, 1); break;
-    case 22: HOMMX_MA(2, 2); break;
-    case 23: HOMMX_MA(2, 3); break;
-    case 30: HOMMX_MA(3, 0); break;
-    case 31: HOMMX_MA(3, 1); break;
-    case 32: HOMMX_MA(3, 2); break;
-    default: HOMMX_MA(3, 3); break;
-  }
-#undef HOMMX_MA
+  dispatch_dim_kind(a.dim, a.kind, [&](auto D, auto K) {
+    hipLaunchKernelGGL((k_mesh_assemble<D(), K()>), dim3(blocks), dim3(256), 0, st, a, coef, Mm, Kst, Brhs, nc);
+    hipLaunchKernelGGL((k_mesh_c0<D(), K()>), dim3(cblocks), dim3(256), 0, st, a, coef, C0, nc);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -302,15 +287,14 @@ struct Bisector {
 
 }  // namespace
 
-int mesh_tree_analyze(const hommx_mesh_desc* d, MeshTreePlan** out, MeshTreeInfo* info, int32_t* supernode_of_node, int32_t* parent) {
+int mesh_tree_analyze(const hommx_mesh_desc* d, const MeshGeom& geo, MeshTreePlan** out, MeshTreeInfo* info, int32_t* supernode_of_node,
+                      int32_t* parent) {
   if (out) *out = nullptr;
-  MeshGeom geo;
-  if (int rc = mesh_check(d, &geo)) return rc;
   const int dim = d->dim, nv = dim + 1;
   const int n = (int)d->n_nodes, ne = (int)d->n_el;
-  if (ne >= (1 << 27)) return mesh_error(HOMMX_EINVAL, "the tree route takes fewer than 2^27 elements, got " + std::to_string(ne));
+  if (ne >= (1 << 27)) return fail(HOMMX_EINVAL, "the tree route takes fewer than 2^27 elements, got %d", ne);
   std::unique_ptr<MeshTreePlan> m(new (std::nothrow) MeshTreePlan());
-  if (!m) return mesh_error(HOMMX_ENOMEM, "host allocation failed");
+  if (!m) return fail(HOMMX_ENOMEM, "host allocation failed");
   const KindSizes ks = kind_sizes(dim, d->kind);
   const int bs = ks.bs;
 
@@ -329,28 +313,19 @@ int mesh_tree_analyze(const hommx_mesh_desc* d, MeshTreePlan** out, MeshTreeInfo
     int worst = 0;
     for (int v = 0; v < n; ++v)
       if (lptr[v + 1] - lptr[v] == ncode) worst = v;
-    return mesh_error(HOMMX_EINVAL, "node " + std::to_string(worst) + " couples with " + std::to_string(ncode - 1) +
-                                        " other nodes: the tree route's coupling codes are int8 (at most 127 per node, itself included)");
+    return fail(HOMMX_EINVAL,
+                "node %d couples with %d other nodes: the tree route's coupling codes are int8 (at most 127 per node, itself included)", worst,
+                ncode - 1);
   }
   auto code_of = [&](int i, int j) { return (int)(std::lower_bound(lst.begin() + lptr[i], lst.begin() + lptr[i + 1], j) - (lst.begin() + lptr[i])); };
 
   // the tree
   {
-    std::vector<double> y((size_t)n * dim, 0.0);
-    for (int e = 0; e < ne; ++e)
-      for (int a = 0; a < nv; ++a) {
-        const int v = d->el_nodes[e * nv + a];
-        for (int c = 0; c < dim; ++c) {
-          double q = d->el_x[((size_t)e * nv + a) * dim + c];
-          q -= std::floor(q + 1e-9);  // the max faces fold onto the min faces
-          y[(size_t)v * dim + c] = q;
-        }
-      }
     Bisector B;
     B.dim = dim;
     B.leaf_max = mf_leaf_max(dim, bs);
     B.split_depth = mf_split_depth();
-    B.y = &y;
+    B.y = &geo.y;
     B.ptr = &geo.ptr;
     B.adj = &geo.adj;
     B.side.assign(n, 0);
@@ -392,7 +367,7 @@ int mesh_tree_analyze(const hommx_mesh_desc* d, MeshTreePlan** out, MeshTreeInfo
   }
   if (info) {  // the host half of the plan mesh_tree_workspace builds
     MfPlan* P = nullptr;
-    if (int rc = mf_plan_build(&P, G, T, false)) return mesh_error(rc, g_berr);
+    if (int rc = mf_plan_build(&P, G, T, false)) return rc;
     const MfStats s = mf_stats(P);
     mf_plan_destroy(P);
     info->n_fronts = s.nfronts;
@@ -425,47 +400,21 @@ int mesh_tree_analyze(const hommx_mesh_desc* d, MeshTreePlan** out, MeshTreeInfo
     m->self_code.resize(n);
     for (int v = 0; v < n; ++v) m->self_code[v] = code_of(v, v);
   }
-  m->grads.swap(geo.grads);
-  m->vol.swap(geo.vol);
   *out = m.release();
   return HOMMX_OK;
 }
 
-int mesh_tree_workspace(MeshTreePlan* m, BlockedWorkspace** out) {
+int mesh_tree_workspace(MeshTreePlan* m, const MeshGeomDev& geo, BlockedWorkspace** out) {
   *out = nullptr;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  struct Piece {
-    const void* src;
-    size_t bytes;
-    const void** dst;
-  };
-  MeshAsm A{m->G.dim, m->G.kind, m->G.nn, m->G.n_el, m->G.ncode};
-  Piece pcs[] = {
-      {m->grads.data(), sizeof(double) * m->grads.size(), (const void**)&A.grads},
-      {m->vol.data(), sizeof(double) * m->vol.size(), (const void**)&A.vol},
-      {m->cptr.data(), sizeof(int) * m->cptr.size(), (const void**)&A.cptr},
-      {m->centry.data(), sizeof(int) * m->centry.size(), (const void**)&A.centry},
-      {m->self_code.data(), sizeof(int) * m->self_code.size(), (const void**)&A.self_code},
-  };
-  size_t total = 0;
-  for (const Piece& p : pcs) total += up(p.bytes);
+  MeshAsm A{m->G.dim, m->G.kind, m->G.nn, m->G.n_el, m->G.ncode, geo.grads, geo.vol};
   void* tables = nullptr;
-  hipError_t e = hipMalloc(&tables, total);
-  if (e != hipSuccess) return mesh_error(e == hipErrorOutOfMemory ? HOMMX_ENOMEM : HOMMX_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-  std::vector<char> host(total, 0);
-  size_t off = 0;
-  for (const Piece& p : pcs) {
-    if (p.bytes) std::copy((const char*)p.src, (const char*)p.src + p.bytes, host.data() + off);
-    *p.dst = (const char*)tables + off;
-    off += up(p.bytes);
-  }
-  e = hipMemcpy(tables, host.data(), total, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
+  if (int rc = upload_packed(&tables, {{m->cptr.data(), sizeof(int) * m->cptr.size(), (const void**)&A.cptr},
+                                       {m->centry.data(), sizeof(int) * m->centry.size(), (const void**)&A.centry},
+                                       {m->self_code.data(), sizeof(int) * m->self_code.size(), (const void**)&A.self_code}})) {
     (void)hipFree(tables);
-    return mesh_error(HOMMX_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    return rc;
   }
-  if (int rc = blocked_workspace_create_mesh(out, m->G, std::move(m->tree), A, tables)) return mesh_error(rc, g_berr);
-  return HOMMX_OK;
+  return blocked_workspace_create_mesh(out, m->G, std::move(m->tree), A, tables);
 }
 
 void mesh_tree_destroy(MeshTreePlan* m) { delete m; }

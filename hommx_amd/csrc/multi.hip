@@ -8,18 +8,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <new>
-#include <string>
 #include <vector>
 
 #include "../../include/hommx_hip.h"
-
-extern "C" int hommx_set_error_(int code, const char* msg);  // api.hip: thread-local message of hommx_last_error()
+#include "host_common.h"
 
 namespace {
+
+using hommx::fail;
 
 typedef void* ncclComm_t;
 typedef int ncclResult_t;
@@ -35,15 +33,6 @@ struct Rccl {
 constexpr int kNcclFloat64 = 8;  // ncclDouble (rccl.h: ncclFloat64 = 8)
 
 Rccl g_rccl;
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return hommx_set_error_(code, buf);
-}
 
 int load_rccl() {
   if (g_rccl.lib) return 0;
@@ -66,12 +55,6 @@ int load_rccl() {
   return 0;
 }
 
-#define HIP_TRY(expr)                                                                                            \
-  do {                                                                                                           \
-    hipError_t e__ = (expr);                                                                                     \
-    if (e__ != hipSuccess)                                                                                       \
-      return fail(e__ == hipErrorOutOfMemory ? HOMMX_ENOMEM : HOMMX_EHIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
-  } while (0)
 #define NCCL_TRY(expr)                                                                                     \
   do {                                                                                                     \
     ncclResult_t r__ = (expr);                                                                             \

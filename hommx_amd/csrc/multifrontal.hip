@@ -38,20 +38,13 @@
 #include <vector>
 
 #include "../../include/hommx_hip.h"
+#define HOMMX_HIP_TRY_FMT "%s: %s"
 #include "blocked_internal.h"
+#include "host_common.h"
 #include "kernels.h"
 #include "mf_front.h"
 
 namespace hommx {
-
-#define MTRY(expr)                                                                       \
-  do {                                                                                   \
-    hipError_t e__ = (expr);                                                             \
-    if (e__ != hipSuccess) {                                                             \
-      g_berr = std::string(#expr) + ": " + hipGetErrorString(e__);                       \
-      return e__ == hipErrorOutOfMemory ? HOMMX_ENOMEM : HOMMX_EHIP;                     \
-    }                                                                                    \
-  } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------
 // plan: symbolic analysis (host) + index tables (device)
@@ -212,8 +205,8 @@ template <typename T>
 int upload(T** dst, const std::vector<T>& src) {
   *dst = nullptr;
   if (src.empty()) return 0;
-  MTRY(hipMalloc(dst, sizeof(T) * src.size()));
-  MTRY(hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc(dst, sizeof(T) * src.size()));
+  HIP_TRY(hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -355,24 +348,21 @@ int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep) {
   if (keep) P->front_max_t = 0;  // the back substitution reads N_i and X_i of every front: the corrector plan keeps them in HBM
   const int nsn = (int)T.sn_nodes.size();
   if (nsn == 0 || T.sn_nodes.back().empty()) {
-    g_berr = "multifrontal plan: empty tree or empty root front";
     delete P;
-    return HOMMX_EINVAL;
+    return fail(HOMMX_EINVAL, "multifrontal plan: empty tree or empty root front");
   }
   std::vector<SN> sn(nsn);
   for (int k = 0; k < nsn; ++k) {
     sn[k].nodes = T.sn_nodes[k];
     sn[k].children = T.sn_children[k];
     if (sn[k].children.size() > 2) {
-      g_berr = "multifrontal plan: more than two children";
       delete P;
-      return HOMMX_EINVAL;
+      return fail(HOMMX_EINVAL, "multifrontal plan: more than two children");
     }
     for (int c : sn[k].children)
       if (c < 0 || c >= k) {
-        g_berr = "multifrontal plan: a child does not come before its parent";
         delete P;
-        return HOMMX_EINVAL;
+        return fail(HOMMX_EINVAL, "multifrontal plan: a child does not come before its parent");
       }
   }
   // elimination rank of every node: supernodes in list order (children before parents), ascending node id inside
@@ -383,18 +373,16 @@ int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep) {
       std::sort(sn[k].nodes.begin(), sn[k].nodes.end());
       for (int v : sn[k].nodes) {
         if (v < 0 || v >= nn || owner[v] >= 0) {
-          g_berr = "multifrontal plan: the supernodes do not partition the nodes";
           delete P;
-          return HOMMX_EINVAL;
+          return fail(HOMMX_EINVAL, "multifrontal plan: the supernodes do not partition the nodes");
         }
         rank[v] = r++;
         owner[v] = k;
       }
     }
     if (r != nn) {
-      g_berr = "multifrontal plan: the supernodes do not partition the nodes";
       delete P;
-      return HOMMX_EINVAL;
+      return fail(HOMMX_EINVAL, "multifrontal plan: the supernodes do not partition the nodes");
     }
   }
   // gauge: the node of highest elimination rank, in the root (structured trees: node nn - 1)
@@ -565,9 +553,8 @@ int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep) {
         for (int q = 0; q < (int)cs.bnd.size(); ++q) {
           const int i = local[cs.bnd[q]];
           if (i < 0) {
-            g_berr = "multifrontal plan: a child's boundary node is missing from its parent's front";
             mf_plan_destroy(P);
-            return HOMMX_EINVAL;
+            return fail(HOMMX_EINVAL, "multifrontal plan: a child's boundary node is missing from its parent's front");
           }
           cpos[((size_t)f * 2 + slot) * nloc + i] = q;
         }
@@ -895,12 +882,12 @@ int mf_reserve(BlockedWorkspace* ws, MfPlan* P, long long ncells, bool ahead) {
     *p = nullptr;
   }
   P->chunk = 0;
-  MTRY(hipMalloc(&P->arena, 8ll * chunk * P->arena_per_cell));
-  MTRY(hipMalloc(&P->scratch, 8ll * chunk * P->scratch_per_cell));
-  if (P->vbuf_per_cell) MTRY(hipMalloc(&P->vbuf, 8ll * chunk * P->vbuf_per_cell));
-  MTRY(hipMalloc(&P->Kst, 8ll * chunk * G.ncode * G.bs * G.bs * G.nn));
-  MTRY(hipMalloc(&P->Brhs, 8ll * chunk * G.t * G.bs * G.nn));
-  MTRY(hipMalloc(&P->C0, 8ll * chunk * 36));
+  HIP_TRY(hipMalloc(&P->arena, 8ll * chunk * P->arena_per_cell));
+  HIP_TRY(hipMalloc(&P->scratch, 8ll * chunk * P->scratch_per_cell));
+  if (P->vbuf_per_cell) HIP_TRY(hipMalloc(&P->vbuf, 8ll * chunk * P->vbuf_per_cell));
+  HIP_TRY(hipMalloc(&P->Kst, 8ll * chunk * G.ncode * G.bs * G.bs * G.nn));
+  HIP_TRY(hipMalloc(&P->Brhs, 8ll * chunk * G.t * G.bs * G.nn));
+  HIP_TRY(hipMalloc(&P->C0, 8ll * chunk * 36));
   P->chunk = chunk;
   return 0;
 }
@@ -1043,12 +1030,9 @@ void mf_backsub_step(BlockedWorkspace* ws, MfPlan* P, const MfHalf& h, const MfG
 int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
              hipStream_t st, double* d_corr) {
   const Geo& G = ws->G;
-  if (d_corr && !P->keep) {
-    g_berr = "mf_solve: correctors need the corrector plan";
-    return HOMMX_EINVAL;
-  }
+  if (d_corr && !P->keep) return fail(HOMMX_EINVAL, "mf_solve: correctors need the corrector plan");
   if (int rc = mf_reserve(ws, P, ncells, false)) return rc;
-  if (d_info) MTRY(hipMemsetAsync(d_info, 0, sizeof(int32_t) * ncells, st));
+  if (d_info) HIP_TRY(hipMemsetAsync(d_info, 0, sizeof(int32_t) * ncells, st));
   long long step_cells = P->chunk;
   {
     const long long nchunks = (ncells + step_cells - 1) / step_cells;
@@ -1063,22 +1047,16 @@ int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_
   const bool two = want >= 2 && step_cells >= 16;
   if (two) {  // every stream / event only if its own slot is still empty: a call that failed part-way leaks nothing on the next one
     for (int k = 0; k + 1 < want; ++k) {
-      if (!P->side[k]) MTRY(hipStreamCreateWithFlags(&P->side[k], hipStreamNonBlocking));
-      if (!P->ev_join[k]) MTRY(hipEventCreateWithFlags(&P->ev_join[k], hipEventDisableTiming));
+      if (!P->side[k]) HIP_TRY(hipStreamCreateWithFlags(&P->side[k], hipStreamNonBlocking));
+      if (!P->ev_join[k]) HIP_TRY(hipEventCreateWithFlags(&P->ev_join[k], hipEventDisableTiming));
     }
-    if (!P->ev_fork) MTRY(hipEventCreateWithFlags(&P->ev_fork, hipEventDisableTiming));
+    if (!P->ev_fork) HIP_TRY(hipEventCreateWithFlags(&P->ev_fork, hipEventDisableTiming));
   }
   // an error after the fork must not leave work on the plan-owned streams that the caller's stream never waits for
   int forked = 0;
-#define MTRY_J(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e__ = (expr);                                                              \
-    if (e__ != hipSuccess) {                                                              \
-      g_berr = std::string(#expr) + ": " + hipGetErrorString(e__);                        \
-      for (int k__ = 1; k__ < forked; ++k__) (void)hipStreamSynchronize(P->side[k__ - 1]); \
-      return e__ == hipErrorOutOfMemory ? HOMMX_ENOMEM : HOMMX_EHIP;                      \
-    }                                                                                     \
-  } while (0)
+  auto join = [&]() {
+    for (int k = 1; k < forked; ++k) (void)hipStreamSynchronize(P->side[k - 1]);
+  };
   const int bs = G.bs;
   for (long long c0 = 0; c0 < ncells; c0 += step_cells) {
     const long long nc = std::min(step_cells, ncells - c0);
@@ -1092,10 +1070,10 @@ int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_
         const long long a = std::min(nc, k * per), b = std::min(nc, (k + 1) * per);
         halves[k] = MfHalf{c0 + a, b - a, a, k == 0 ? st : P->side[k - 1]};
       }
-      MTRY(hipEventRecord(P->ev_fork, st));  // the side streams start behind everything queued on st (inputs, the previous chunk)
+      HIP_TRY(hipEventRecord(P->ev_fork, st));  // the side streams start behind everything queued on st (inputs, the previous chunk)
       for (int k = 1; k < nh; ++k) {
         forked = k + 1;
-        MTRY_J(hipStreamWaitEvent(P->side[k - 1], P->ev_fork, 0));
+        HIP_TRY_OR(join(), hipStreamWaitEvent(P->side[k - 1], P->ev_fork, 0));
       }
     }
     for (int k = 0; k < nh; ++k) {
@@ -1124,13 +1102,12 @@ int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_
         launch_center_corr(ws, d_corr + halves[k].c0 * G.t * (long long)G.nn * bs, halves[k].nc, halves[k].st);
     }
     for (int k = 1; k < nh; ++k) {  // st continues (next chunk, the caller's work) when every piece is done
-      MTRY_J(hipEventRecord(P->ev_join[k - 1], P->side[k - 1]));
-      MTRY_J(hipStreamWaitEvent(st, P->ev_join[k - 1], 0));
+      HIP_TRY_OR(join(), hipEventRecord(P->ev_join[k - 1], P->side[k - 1]));
+      HIP_TRY_OR(join(), hipStreamWaitEvent(st, P->ev_join[k - 1], 0));
     }
-    MTRY_J(hipGetLastError());
+    HIP_TRY_OR(join(), hipGetLastError());
     forked = 0;
   }
-#undef MTRY_J
   return 0;
 }
 

@@ -47,8 +47,8 @@ __device__ __forceinline__ void element(const double (&xi)[KIND >= 2 ? DIM * (DI
                                         const double (&g)[DIM + 1][DIM], double vol, const double* Mc, const double* __restrict__ ce,
                                         long long el, double* __restrict__ srow, double* __restrict__ qrow,
                                         Acc<KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM>& acc) {
-  constexpr int T = KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM;
-  constexpr int BS = KIND >= 2 ? DIM : 1;
+  constexpr KindSizes ks = kind_sizes(DIM, KIND);
+  constexpr int T = ks.t, BS = ks.bs;
   double s[T];
 #pragma unroll
   for (int m = 0; m < T; ++m) s[m] = xi[m];
@@ -97,8 +97,8 @@ __device__ __forceinline__ void element(const double (&xi)[KIND >= 2 ? DIM * (DI
 
 template <int DIM, int KIND, bool MESH, bool FIELDS>
 __global__ __launch_bounds__(kThreads) void k_recon(ReconArgs A) {
-  constexpr int T = KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM;
-  constexpr int NCOMP = KIND == 0 ? 1 : KIND == 1 ? DIM * (DIM + 1) / 2 : KIND == 2 ? 2 : T * (T + 1) / 2;
+  constexpr KindSizes ks = kind_sizes(DIM, KIND);
+  constexpr int T = ks.t, NCOMP = ks.n_comp;
   constexpr int NS = 2 * T + 3;
   extern __shared__ double lds_chi[];
   __shared__ double red[kWaves][kMaxStats];
@@ -247,33 +247,17 @@ hipError_t launch_one(const ReconArgs& a, long long nc, hipStream_t st) {
   return hipGetLastError();
 }
 
-template <int DIM, int KIND>
-hipError_t launch_kind(const ReconArgs& a, bool mesh, long long nc, hipStream_t st) {
-  const bool f = a.strain != nullptr;
-  if (mesh) return f ? launch_one<DIM, KIND, true, true>(a, nc, st) : launch_one<DIM, KIND, true, false>(a, nc, st);
-  return f ? launch_one<DIM, KIND, false, true>(a, nc, st) : launch_one<DIM, KIND, false, false>(a, nc, st);
-}
-
 }  // namespace
 
 size_t recon_lds_limit() { return 150 * 1024; }
 
 hipError_t launch_reconstruct(const ReconArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t st) {
   if (nc <= 0) return hipSuccess;
-  if (dim == 2) {
-    switch (kind) {
-      case 0: return launch_kind<2, 0>(a, mesh, nc, st);
-      case 1: return launch_kind<2, 1>(a, mesh, nc, st);
-      case 2: return launch_kind<2, 2>(a, mesh, nc, st);
-      default: return launch_kind<2, 3>(a, mesh, nc, st);
-    }
-  }
-  switch (kind) {
-    case 0: return launch_kind<3, 0>(a, mesh, nc, st);
-    case 1: return launch_kind<3, 1>(a, mesh, nc, st);
-    case 2: return launch_kind<3, 2>(a, mesh, nc, st);
-    default: return launch_kind<3, 3>(a, mesh, nc, st);
-  }
+  const bool f = a.strain != nullptr;
+  return dispatch_dim_kind(dim, kind, [&](auto D, auto K) {
+    if (mesh) return f ? launch_one<D(), K(), true, true>(a, nc, st) : launch_one<D(), K(), true, false>(a, nc, st);
+    return f ? launch_one<D(), K(), false, true>(a, nc, st) : launch_one<D(), K(), false, false>(a, nc, st);
+  });
 }
 
 }  // namespace hommx
