@@ -1,6 +1,7 @@
-// blocked_internal.h -- shared between blocked.hip (block-cyclic plane elimination) and multifrontal.hip (nested dissection):
-// the workspace object behind a plan of the blocked family and the batched fp64-MFMA building blocks (GEMM tiles, recursive
-// block inverse) both eliminations are made of.
+// blocked_internal.h -- everything the translation units of the blocked family share: the workspace object behind a plan and its route
+// (blocked.hip), K1 (assembly.hip), the batched fp64-MFMA building blocks both eliminations are made of (dense.hip: GEMM tiles, recursive
+// block inverse), the block-cyclic plane elimination (plane.hip), nested dissection (multifrontal.hip) and the one-launch kernels for small
+// plane blocks (small.hip, small_wave.hip).  What api.hip calls is declared in kernels.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,23 +25,31 @@ struct MfTree {
   std::vector<int> nb_ptr, nb_node, nb_code;  // CSR over nodes v: every node w coupled with v (v included) and the code of (row w, column v)
 };
 
-struct BlockedWorkspace {
-  Geo G;
-  // development knobs, read ONCE when the plan is created (include/hommx_hip.h lists them)
-  double budget_gb_env = 0.0;  // HOMMX_BLOCKED_MEM_GB (0: automatic)
-  int gemm128_min = 256;       // HOMMX_GEMM128_MIN
-  bool sparse_v1 = false;      // HOMMX_SPARSE_V1: generic instead of strip-form sparse E products
-  bool leaf32 = false;         // HOMMX_LEAF32: 32x32 leaves only in the recursive inverse
-  bool split64 = true;         // HOMMX_NO_SPLIT64: halve 192 into 96 + 96 (32- and 64-leaves) instead of 64 + 128
-  bool small_fused = true;     // HOMMX_NO_SMALL_FUSED switches the LDS-resident kernel for b <= 64 off (A/B runs)
-  int small_waves = 0;         // HOMMX_SMALL_WAVES: 2 / 4 = the LDS kernel with that many waves per macro cell; 0 = default routes
+// What a plan launches for effective tensors, decided once when its workspace is created (blocked.hip: ws_configure)
+enum class Route { SmallWave, SmallFused, Plane, Tree, MeshTree };
+
+// Buffers of the plane elimination (plane.hip), `chunk` / `hchunk` cells each: one device block per set.  The one-launch kernels take K1
+// from here as well.
+struct PlaneBufs {
   long long chunk = 0;
+  void* block = nullptr;
   double *Kst = nullptr, *Brhs = nullptr, *C0 = nullptr;
   double *S = nullptr, *W = nullptr, *Sl = nullptr, *V = nullptr, *X = nullptr, *T = nullptr;
   double *R = nullptr, *Rl = nullptr, *Vr = nullptr, *Gm = nullptr;
   // corrector mode: per eliminated plane the inverse Schur block, the arrow block and the load rows are kept
   long long hchunk = 0;
+  void* hblock = nullptr;
   double *hS = nullptr, *hW = nullptr, *hR = nullptr, *Xa = nullptr, *Xb = nullptr, *Y = nullptr;
+};
+
+struct BlockedWorkspace {
+  Geo G;
+  Route route = Route::Plane;
+  int small_nw = 0;            // Route::SmallFused: waves per macro cell (HOMMX_SMALL_WAVES, or the default of the padded block)
+  // development knobs, read ONCE when the plan is created (include/hommx_hip.h lists them)
+  double budget_gb_env = 0.0;  // HOMMX_BLOCKED_MEM_GB (0: automatic)
+  int gemm128_min = 256;       // HOMMX_GEMM128_MIN
+  PlaneBufs plane;
   // nested-dissection route (large plane blocks, and every mesh plan of the tree route): the tree both plans are built from (mf_plan_from_tree)
   MfTree tree;
   MfPlan* mf = nullptr;
@@ -49,16 +58,13 @@ struct BlockedWorkspace {
   // mesh plans of the tree route (blocked_workspace_create_mesh): K1 is the mesh assembly on these tables, one device block owned here
   MeshAsm mesh{};
   void* mesh_tables = nullptr;  // non-null marks a mesh workspace
-  int mf_min_b = 192;          // smallest plane block b routed to the multifrontal elimination (set per dim / unknowns per node when the
-                               // workspace is created; HOMMX_MF_MIN_B overrides, 0: never)
-  bool mf_no_border_split = false;  // HOMMX_MF_NO_BORDER_SPLIT (A/B runs)
-  int mf_gather128_min_k = 1024;  // HOMMX_MF_G128_MIN_K: gathering Schur updates of smaller rank take the 64 x 64 tiles
   // tile orders of big lower-triangle updates (gemm): device tables, one per tile count, made on first use
   int tile_sb = 4;                // HOMMX_TILE_SB: tiles walk the lower triangle in SB x SB super-blocks (0: row by row)
   std::map<int, int*> tilemaps;
   std::string detail;             // hommx_plan_route_detail: written once, on first request
 };
 
+inline unsigned nblk(long long work, int bs = 256) { return (unsigned)((work + bs - 1) / bs); }
 
 // One batched operation context: `nc` matrices (cells, or cells x fronts of one shape) on stream `st`.
 struct Ctx {
@@ -92,7 +98,7 @@ struct GatherC {
   int rowOff = 0;               // C row 0 is boundary unknown rowOff of the front (the border rows are updated by a launch of their own)
 };
 
-// C = alpha op(A) op(B) + beta C for every matrix of the batch (blocked.hip: k_gemm_tile, XCD-aware tiles); lowerOnly: tiles on and
+// C = alpha op(A) op(B) + beta C for every matrix of the batch (dense.hip: k_gemm_tile, XCD-aware tiles); lowerOnly: tiles on and
 // below the diagonal only; Ct: mirrored copy of the result (may be C itself with lowerOnly)
 void gemm(const Ctx& c, bool ta, bool tb, int M, int N, int K, double alpha, const double* A, int lda, long long sA, const double* B,
           int ldb, long long sB, double beta, double* C, int ldc, long long sC, int lowerOnly = 0, double* Ct = nullptr,
@@ -139,9 +145,24 @@ void launch_center_corr(BlockedWorkspace* ws, double* corr, long long nc, hipStr
 // tree, and the assembly tables on the device, which the workspace owns from here on (also on failure); the same development knobs as
 // blocked_workspace_create
 int blocked_workspace_create_mesh(BlockedWorkspace** out, const Geo& G, MfTree&& tree, const MeshAsm& a, void* tables);
+// assembly.hip: corner offsets and P1 gradients of the sub-elements of a structured cell (Geo::voff, Geo::grad)
+void fill_tables(Geo& G);
 // K1 of the blocked family (stencil rows, loads, C0 of `nc` cells into the given buffers), shared by both eliminations: each route owns
 // its buffers (a plan may serve effective tensors on one route and correctors on the other, with different chunk sizes)
 void launch_assembly(BlockedWorkspace* ws, const double* coef, const double* Mm, long long nc, hipStream_t st, double* Kst, double* Brhs,
                      double* C0);
+
+// plane.hip: buffers for batches of up to `ncells` (chunked by the memory budget), with the history set when correctors are asked for
+int plane_reserve(BlockedWorkspace* ws, long long ncells, bool correctors);
+void plane_free(BlockedWorkspace* ws);
+// K2 and K3 of the c.nc cells whose K1 is in ws->plane: tensors to `out`, and with corr != nullptr the correctors [cell][t][n^d bs]
+int plane_eliminate(Ctx c, double* out, double* corr);
+
+// small.hip: LDS-resident elimination of a Route::SmallFused plan (small_fused.h), nw = 2, 4 or 8 waves per macro cell
+hipError_t launch_small_fused(const Geo& G, const double* Kst, const double* Brhs, const double* C0, double* out, int32_t* info,
+                              long long ncells, int nw, hipStream_t stream);
+// small_wave.hip: register-resident elimination of a Route::SmallWave plan, one wavefront per macro cell (small_wave.h)
+hipError_t launch_small_wave(const Geo& G, const double* Kst, const double* Brhs, const double* C0, double* out, int32_t* info,
+                             long long ncells, hipStream_t stream);
 
 }  // namespace hommx

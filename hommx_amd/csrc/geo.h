@@ -1,4 +1,4 @@
-// geo.h -- geometry / stencil descriptor shared by the kernel files of the blocked family (blocked.hip, small.hip).
+// geo.h -- geometry / stencil descriptor shared by the kernel files of the blocked family.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,14 +24,5 @@ __device__ __forceinline__ int plane_neighbour(const Geo& G, int q, int ipc) {
   const int i = (q % n + ox + n) % n, j = (q / n + oy + n) % n;
   return i + n * j;
 }
-
-
-// small.hip: LDS-resident elimination for plane blocks b <= 64 (small_fused.h); nw = waves per macro cell (0: default)
-hipError_t launch_small_fused(const Geo& G, const double* Kst, const double* Brhs, const double* C0, double* out, int32_t* info,
-                              long long ncells, int nw, hipStream_t stream);
-
-// small_wave.hip: register-resident elimination for plane blocks b <= 48, one wavefront per macro cell (small_wave.h)
-hipError_t launch_small_wave(const Geo& G, const double* Kst, const double* Brhs, const double* C0, double* out, int32_t* info,
-                             long long ncells, hipStream_t stream);
 
 }  // namespace hommx

@@ -69,11 +69,11 @@ struct CoefSource {
 hipError_t launch_poisson2d_fused(const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
                                   int n, long long ncells, hipStream_t stream, CoefSource src = CoefSource());
 
-// blocked.hip: coef[cell][el][comp] of a separable coefficient (AFFINE / RECIPROCAL; params[cell][comp] = (a, b)) expanded into the element stream
+// assembly.hip: coef[cell][el][comp] of a separable coefficient (AFFINE / RECIPROCAL; params[cell][comp] = (a, b)) expanded into the element stream
 hipError_t launch_expand_separable(CoefSource src, const double* d_params, double* d_coef, long long n_el, int n_comp, long long ncells,
                                    hipStream_t stream);
 
-// blocked.hip: coef[cell][el][comp] = mask[el] ? values[cell][1][comp] : values[cell][0][comp]
+// assembly.hip: coef[cell][el][comp] = mask[el] ? values[cell][1][comp] : values[cell][0][comp]
 hipError_t launch_expand_two_phase(const unsigned char* d_mask, const double* d_values, double* d_coef, long long n_el,
                                    int n_comp, long long ncells, hipStream_t stream);
 
@@ -105,7 +105,7 @@ hipError_t run_fp64_calibration(double* mfma_flops_per_s, double* fma_flops_per_
 }  // namespace hommx
 
 namespace hommx {
-// blocked.hip: generic block-cyclic path (any dim / kind / n); host-orchestrated batched kernels.
+// blocked.hip: the blocked family (any dim / kind / n) as api.hip sees it; everything else of the family is in blocked_internal.h
 struct BlockedWorkspace;
 int blocked_workspace_create(BlockedWorkspace** out, int dim, int n, int kind);
 void blocked_workspace_destroy(BlockedWorkspace* ws);

@@ -23,7 +23,7 @@ struct MeshAsm {
   const int* self_code;  // [nn] code of (i, i)
 };
 
-// K1 of a mesh plan -- Kst, Brhs and C0 of `nc` cells in the layout launch_assembly (blocked.hip) writes, from the element stream
+// K1 of a mesh plan -- Kst, Brhs and C0 of `nc` cells in the layout launch_assembly (assembly.hip) writes, from the element stream
 void launch_mesh_assembly(const MeshAsm& a, const double* coef, const double* Mm, long long nc, hipStream_t st, double* Kst, double* Brhs,
                           double* C0);
 

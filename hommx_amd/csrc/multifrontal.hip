@@ -2,7 +2,7 @@
 // 6^3 micro cells -- BASELINE configurations C4 / C5: 16^3 micro cells x 3 components = 12,288 unknowns per macro cell -- and large 2D
 // meshes; the thresholds are set in blocked_workspace_create from measurements).
 //
-// Why: the block-cyclic plane elimination of blocked.hip carries a dense b x b arrow through n - 1 steps, (6 (n-1) + 2) b^3 model flops
+// Why: the block-cyclic plane elimination of plane.hip carries a dense b x b arrow through n - 1 steps, (6 (n-1) + 2) b^3 model flops
 // (41.7 GFLOP per C4 / C5 cell); a sparse Cholesky under nested dissection needs 11.3 GFLOP (profiles/fref.json).  Here the torus is
 // dissected geometrically -- two planes per periodic direction, one per open direction, down to 3 x 3 x 3-node leaves -- and every
 // supernode (separator or leaf) is eliminated as a dense FRONT
@@ -11,7 +11,7 @@
 //            [ F21  F22 ]
 //        N = F11^-1 ;  F12 <- N F21^T ;  F22 <- F22 - F21 F12 (lower tiles)
 //
-// with the SAME batched fp64-MFMA building blocks as the plane elimination (blocked.hip: k_gemm_tile, recursive block inverse).  All macro
+// with the SAME batched fp64-MFMA building blocks as the plane elimination (dense.hip: k_gemm_tile, recursive block inverse).  All macro
 // cells share the structure, and fronts of equal shape at equal height of the elimination tree are independent, so every step is ONE
 // batched launch over (cells x fronts of that shape).
 //   * The t canonical load vectors ride as a BORDER: 8 extra rows at the end of every front's boundary block (row m = load case m), so
@@ -892,7 +892,6 @@ int mf_reserve(BlockedWorkspace* ws, MfPlan* P, long long ncells, bool ahead) {
   return 0;
 }
 
-static inline unsigned nblk(long long work, int bs = 256) { return (unsigned)((work + bs - 1) / bs); }
 
 namespace {
 
@@ -979,8 +978,8 @@ void mf_group_step(BlockedWorkspace* ws, MfPlan* P, const MfHalf& h, const MfGro
   ga.nf = mg.nf;
   ga.rp = mg.rp;
   // F22 = children - F21 F12, lower tiles.  When the border rows would open a tile row of their own they get a (thin) launch instead.
-  const int TMg = (mg.rp >= ws->gemm128_min && mg.sp >= ws->mf_gather128_min_k) ? 128 : 64;
-  const bool split = mg.rb >= TMg && (mg.rp + TMg - 1) / TMg > (mg.rb + TMg - 1) / TMg && !ws->mf_no_border_split;
+  const int TMg = gemm_tile_size(ws, mg.rp, mg.rp, mg.sp, true);
+  const bool split = mg.rb >= TMg && (mg.rp + TMg - 1) / TMg > (mg.rb + TMg - 1) / TMg;
   const int main_n = split ? mg.rb : mg.rp;
   gemm(c, false, false, main_n, main_n, mg.sp, -1.0, F21, mg.L, sF, F12, mg.L, sF, 1.0, F22, mg.L, sF, 1, nullptr, &ga);
   if (split) {

@@ -1,20 +1,20 @@
 // small.hip -- translation unit of the LDS-resident small-block kernel (small_fused.h) and its dispatch over
-// (padded block size, components per node, in-plane stencil size, waves per macro cell); blocks b <= 48 go on to small_wave.hip.
+// (padded block size, components per node, in-plane stencil size, waves per macro cell).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "geo.h"
+#include <algorithm>
+
+#include "blocked_internal.h"
 #include "small_fused.h"
 
 namespace hommx {
 
 hipError_t launch_small_fused(const Geo& G, const double* Kst, const double* Brhs, const double* C0, double* out, int32_t* info,
-                              long long nc, int nw_req, hipStream_t st) {
+                              long long nc, int nw, hipStream_t st) {
   if (nc <= 0) return hipSuccess;
   const int nipc = G.ncode / 3;
-  if (G.b <= 48 && nw_req != 2 && nw_req != 4) return launch_small_wave(G, Kst, Brhs, C0, out, info, nc, st);  // small_wave.hip
-  const int bp = G.b <= 32 ? 32 : G.b <= 48 ? 48 : 64;
-  const int nw = (nw_req == 2 || nw_req == 4 || (nw_req == 8 && bp == 64)) ? nw_req : (bp == 64 ? 8 : 2);  // 64: 8 waves (two tiles each) +3..5 % over 4
+  const int bp = std::max(32, (G.b + 15) / 16 * 16);  // the block padded to whole 16-tiles: 32, 48 or 64
 #define HOMMX_SF(BP_, BS_, NI_, NW_) \
   hipLaunchKernelGGL((k_small_fused<BP_, BS_, NI_, NW_>), dim3((unsigned)nc), dim3(64 * NW_), 0, st, G, Kst, Brhs, C0, out, info, nc)
 #define HOMMX_SFK(BP_, NW_)                                \

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "geo.h"
+#include "blocked_internal.h"
 #include "small_wave.h"
 
 namespace hommx {

@@ -48,9 +48,6 @@ extern "C" {
  *   HOMMX_GEMM128_MIN      smallest M, N routed to the 128x128-tile GEMM (default 256 on the plane elimination; nested-dissection plans
  *                          use the 64x64 tiles throughout)
  *   HOMMX_TILE_SB          big lower-triangle updates walk their tiles in SB x SB super-blocks (default 4; 0: row by row)
- *   HOMMX_SPARSE_V1        any value: generic instead of strip-form sparse E products
- *   HOMMX_LEAF32           any value: 32x32 leaves only in the recursive block inverse
- *   HOMMX_NO_SPLIT64       any value: the recursive block inverse halves 192 into 96 + 96 instead of 64 + 128
  *   HOMMX_NO_SMALL_FUSED   any value: plane blocks b <= 64 take the HBM-resident kernels instead of the one-launch kernels
  *   HOMMX_MF_MIN_B         smallest plane block b routed to the nested-dissection (multifrontal) elimination instead of the plane
  *                          elimination (default: 65 in 3D, 49 in 2D, i.e. every plane block the one-launch kernels do not take or lose
@@ -62,7 +59,7 @@ extern "C" {
  *                          by side on the caller's stream and plan-owned ones; the caller's stream waits for all, results are bitwise equal)
  *   HOMMX_MF_CORR          0: hommx_solve_batch_correctors of a nested-dissection plan runs the plane elimination (default: back substitution
  *                          down the elimination tree on a second plan whose fronts all stay resident)
- *   HOMMX_MF_LEAF, HOMMX_MF_SPLIT_DEPTH, HOMMX_MF_G128_MIN_K, HOMMX_MF_NO_BORDER_SPLIT, HOMMX_MF_VERBOSE   tuning / A-B knobs of that route
+ *   HOMMX_MF_LEAF, HOMMX_MF_SPLIT_DEPTH, HOMMX_MF_VERBOSE   tuning / A-B knobs of that route
  *   HOMMX_SMALL_WAVES      2 / 4: plane blocks b <= 48 take the LDS-resident multi-wave kernel (that many waves per macro cell)
  *                          instead of the one-wave-per-cell register kernel; for 48 < b <= 64 it sets that kernel's wave count
  *                          (2 / 4 / 8, default 8)
