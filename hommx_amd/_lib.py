@@ -12,49 +12,6 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HOMMX_LIB") or os.path.join(_HERE, "libhommx_hip.so")  # HOMMX_LIB: A/B builds (dev)
 
-# every symbol include/hommx_hip.h declares (tests check the library exports all of them)
-EXPORTED_SYMBOLS = (
-    "hommx_device_count",
-    "hommx_plan_create",
-    "hommx_plan_destroy",
-    "hommx_plan_reserve",
-    "hommx_plan_dim",
-    "hommx_plan_device",
-    "hommx_plan_n_micro",
-    "hommx_plan_kind",
-    "hommx_plan_num_elements",
-    "hommx_plan_coef_components",
-    "hommx_plan_tensor_size",
-    "hommx_plan_kernel_name",
-    "hommx_plan_route_detail",
-    "hommx_plan_flops_per_solve",
-    "hommx_mesh_analyze",
-    "hommx_mesh_analyze_tree",
-    "hommx_plan_create_mesh",
-    "hommx_plan_front_width",
-    "hommx_solve_batch",
-    "hommx_solve_batch_device",
-    "hommx_solve_batch_correctors",
-    "hommx_reconstruct_batch",
-    "hommx_reconstruct_batch_device",
-    "hommx_solve_batch_two_phase",
-    "hommx_solve_batch_two_phase_device",
-    "hommx_solve_batch_separable",
-    "hommx_solve_batch_separable_device",
-    "hommx_comm_init_all",
-    "hommx_comm_destroy",
-    "hommx_comm_size",
-    "hommx_allgather_field",
-    "hommx_solve_batch_multi",
-    "hommx_solve_batch_multi_device",
-    "hommx_shard_range",
-    "hommx_unpack_field",
-    "hommx_calibrate_fp64",
-    "hommx_calibrate_fp64_mfma",
-    "hommx_calibrate_fp64_detail",
-    "hommx_last_error",
-)
-
 KIND_POISSON_SCALAR = 0
 KIND_POISSON_MATRIX = 1
 KIND_ELASTICITY_ISO = 2
@@ -89,6 +46,59 @@ class MeshDesc(C.Structure):
         ("order", C.c_void_p),
         ("reserved", C.c_int32 * 4),
     ]
+
+
+def _prototypes() -> dict:
+    """name -> (restype, argtypes) of every symbol include/hommx_hip.h declares: ``load()`` declares them from this table, and
+    the tests check that the header and the library export exactly these names."""
+    c_int, f64, char_p = C.c_int, C.c_double, C.c_char_p
+    vp, i32, i64, dp = C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_double)
+    vpp, i32p, i64p = C.POINTER(vp), C.POINTER(i32), C.POINTER(i64)
+    return {
+        "hommx_device_count": (c_int, []),
+        "hommx_plan_create": (c_int, [vpp, C.POINTER(PlanDesc)]),
+        "hommx_plan_destroy": (c_int, [vp]),
+        "hommx_plan_reserve": (c_int, [vp, i64]),
+        "hommx_plan_dim": (i32, [vp]),
+        "hommx_plan_device": (i32, [vp]),
+        "hommx_plan_n_micro": (i32, [vp]),
+        "hommx_plan_kind": (i32, [vp]),
+        "hommx_plan_num_elements": (i64, [vp]),
+        "hommx_plan_coef_components": (i32, [vp]),
+        "hommx_plan_tensor_size": (i32, [vp]),
+        "hommx_plan_kernel_name": (char_p, [vp]),
+        "hommx_plan_route_detail": (char_p, [vp]),
+        "hommx_plan_flops_per_solve": (f64, [vp]),
+        "hommx_mesh_analyze": (c_int, [C.POINTER(MeshDesc), i32p, dp]),
+        "hommx_mesh_analyze_tree": (c_int, [C.POINTER(MeshDesc), i32p, i32p, i32p, dp, vp, vp]),
+        "hommx_plan_create_mesh": (c_int, [vpp, C.POINTER(MeshDesc)]),
+        "hommx_plan_front_width": (i32, [vp]),
+        "hommx_solve_batch": (c_int, [vp, i64, vp, vp, vp, vp]),
+        "hommx_solve_batch_device": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
+        "hommx_solve_batch_correctors": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
+        "hommx_reconstruct_batch": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "hommx_reconstruct_batch_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "hommx_solve_batch_two_phase": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
+        "hommx_solve_batch_two_phase_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp]),
+        "hommx_solve_batch_separable": (c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "hommx_solve_batch_separable_device": (c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "hommx_comm_init_all": (c_int, [vpp, c_int, C.POINTER(c_int)]),
+        "hommx_comm_destroy": (c_int, [vp]),
+        "hommx_comm_size": (c_int, [vp]),
+        "hommx_allgather_field": (c_int, [vp, vpp, i64]),
+        "hommx_solve_batch_multi": (c_int, [vp, vpp, i64, vp, vp, vp, vp]),
+        "hommx_solve_batch_multi_device": (c_int, [vp, vpp, i64, vpp, vpp, vpp]),
+        "hommx_shard_range": (c_int, [i64, i32, i32, i64p, i64p, i64p]),
+        "hommx_unpack_field": (c_int, [i64, i32, i32, vp, vp, vp]),
+        "hommx_calibrate_fp64": (c_int, [c_int, dp, dp]),
+        "hommx_calibrate_fp64_mfma": (c_int, [c_int, dp]),
+        "hommx_calibrate_fp64_detail": (c_int, [c_int, dp, dp, dp]),
+        "hommx_last_error": (char_p, []),
+    }
+
+
+PROTOTYPES = _prototypes()
+EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 
 
 class HommxLibraryError(RuntimeError):
@@ -137,81 +147,9 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise HommxLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    vp, i32, i64, dp = C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_double)
-    lib.hommx_device_count.restype = C.c_int
-    lib.hommx_device_count.argtypes = []
-    lib.hommx_plan_create.restype = C.c_int
-    lib.hommx_plan_create.argtypes = [C.POINTER(vp), C.POINTER(PlanDesc)]
-    lib.hommx_mesh_analyze.restype = C.c_int
-    lib.hommx_mesh_analyze.argtypes = [C.POINTER(MeshDesc), C.POINTER(i32), dp]
-    lib.hommx_mesh_analyze_tree.restype = C.c_int
-    lib.hommx_mesh_analyze_tree.argtypes = [C.POINTER(MeshDesc), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), dp, vp, vp]
-    lib.hommx_plan_create_mesh.restype = C.c_int
-    lib.hommx_plan_create_mesh.argtypes = [C.POINTER(vp), C.POINTER(MeshDesc)]
-    lib.hommx_plan_front_width.restype = i32
-    lib.hommx_plan_front_width.argtypes = [vp]
-    lib.hommx_plan_reserve.restype = C.c_int
-    lib.hommx_plan_reserve.argtypes = [vp, i64]
-    lib.hommx_plan_destroy.restype = C.c_int
-    lib.hommx_plan_destroy.argtypes = [vp]
-    lib.hommx_plan_num_elements.restype = i64
-    lib.hommx_plan_num_elements.argtypes = [vp]
-    lib.hommx_plan_coef_components.restype = i32
-    lib.hommx_plan_coef_components.argtypes = [vp]
-    lib.hommx_plan_tensor_size.restype = i32
-    lib.hommx_plan_tensor_size.argtypes = [vp]
-    lib.hommx_plan_flops_per_solve.restype = C.c_double
-    lib.hommx_plan_flops_per_solve.argtypes = [vp]
-    lib.hommx_plan_kernel_name.restype = C.c_char_p
-    lib.hommx_plan_kernel_name.argtypes = [vp]
-    lib.hommx_plan_route_detail.restype = C.c_char_p
-    lib.hommx_plan_route_detail.argtypes = [vp]
-    lib.hommx_solve_batch.restype = C.c_int
-    lib.hommx_solve_batch.argtypes = [vp, i64, vp, vp, vp, vp]
-    lib.hommx_solve_batch_device.restype = C.c_int
-    lib.hommx_solve_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    lib.hommx_solve_batch_correctors.restype = C.c_int
-    lib.hommx_solve_batch_correctors.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    lib.hommx_reconstruct_batch.restype = C.c_int
-    lib.hommx_reconstruct_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.hommx_reconstruct_batch_device.restype = C.c_int
-    lib.hommx_reconstruct_batch_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.hommx_solve_batch_two_phase.restype = C.c_int
-    lib.hommx_solve_batch_two_phase.argtypes = [vp, i64, vp, vp, vp, vp, vp]
-    lib.hommx_solve_batch_two_phase_device.restype = C.c_int
-    lib.hommx_solve_batch_two_phase_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
-    lib.hommx_solve_batch_separable.restype = C.c_int
-    lib.hommx_solve_batch_separable.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
-    lib.hommx_solve_batch_separable_device.restype = C.c_int
-    lib.hommx_solve_batch_separable_device.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-    for q in ("hommx_plan_dim", "hommx_plan_device", "hommx_plan_n_micro", "hommx_plan_kind"):
-        getattr(lib, q).restype = i32
-        getattr(lib, q).argtypes = [vp]
-    lib.hommx_comm_init_all.restype = C.c_int
-    lib.hommx_comm_init_all.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.c_int)]
-    lib.hommx_comm_destroy.restype = C.c_int
-    lib.hommx_comm_destroy.argtypes = [vp]
-    lib.hommx_comm_size.restype = C.c_int
-    lib.hommx_comm_size.argtypes = [vp]
-    lib.hommx_allgather_field.restype = C.c_int
-    lib.hommx_allgather_field.argtypes = [vp, C.POINTER(vp), i64]
-    lib.hommx_solve_batch_multi.restype = C.c_int
-    lib.hommx_solve_batch_multi.argtypes = [vp, C.POINTER(vp), i64, vp, vp, vp, vp]
-    lib.hommx_solve_batch_multi_device.restype = C.c_int
-    lib.hommx_solve_batch_multi_device.argtypes = [vp, C.POINTER(vp), i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
-    i64p = C.POINTER(i64)
-    lib.hommx_shard_range.restype = C.c_int
-    lib.hommx_shard_range.argtypes = [i64, i32, i32, i64p, i64p, i64p]
-    lib.hommx_unpack_field.restype = C.c_int
-    lib.hommx_unpack_field.argtypes = [i64, i32, i32, vp, vp, vp]
-    lib.hommx_calibrate_fp64.restype = C.c_int
-    lib.hommx_calibrate_fp64.argtypes = [C.c_int, dp, dp]
-    lib.hommx_calibrate_fp64_detail.restype = C.c_int
-    lib.hommx_calibrate_fp64_detail.argtypes = [C.c_int, dp, dp, dp]
-    lib.hommx_calibrate_fp64_mfma.restype = C.c_int
-    lib.hommx_calibrate_fp64_mfma.argtypes = [C.c_int, dp]
-    lib.hommx_last_error.restype = C.c_char_p
-    lib.hommx_last_error.argtypes = []
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

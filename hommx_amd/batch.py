@@ -99,6 +99,50 @@ class Reconstruction:
                    stats[:, 2 * t + 2].astype(np.int64), A_eff, info, strain, flux, cells)
 
 
+@dataclass(frozen=True)
+class CoefStream:
+    """The coefficient of a block of macro cells in one of the three forms the library takes (include/hommx_hip.h): sampled element means,
+    phase mask + two values per cell, table of g + (a, b) per cell.  ``method`` names the plan's host method (``method + "_device"`` is its
+    device twin), ``shared`` holds the arguments every cell shares in the order that method takes them, ``per_cell`` is the one array whose
+    first axis is the macro cell: ``plan.<method>(*shared, per_cell, M, return_info=...)``."""
+
+    method: str
+    shared: tuple
+    per_cell: np.ndarray
+
+    @classmethod
+    def sampled(cls, coef) -> "CoefStream":
+        return cls("solve", (), np.ascontiguousarray(coef, dtype=np.float64))
+
+    @classmethod
+    def two_phase(cls, mask, values) -> "CoefStream":
+        return cls("solve_two_phase", (np.ascontiguousarray(np.asarray(mask).astype(np.uint8)),), np.ascontiguousarray(values, dtype=np.float64))
+
+    @classmethod
+    def separable(cls, family: str, table, weights, params) -> "CoefStream":
+        return cls("solve_separable", (family, np.ascontiguousarray(table, dtype=np.float64),
+                                       None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)),
+                   np.ascontiguousarray(params, dtype=np.float64))
+
+    def __len__(self) -> int:
+        return self.per_cell.shape[0]
+
+    def block(self, b: int, e: int) -> "CoefStream":
+        """Cells [b, e) of the stream (the shared arguments are shared, not copied)."""
+        return CoefStream(self.method, self.shared, self.per_cell[b:e])
+
+    def solve(self, plan, M, **kw):
+        """Through the host method of ``plan`` (a MicroCellPlan or a stand-in that offers ``method``)."""
+        return getattr(plan, self.method)(*self.shared, self.per_cell, M, **kw)
+
+    def solve_device(self, plan: "MicroCellPlan", upload, M_ptr, out_ptr, info_ptr, stream):
+        """Through the device twin of the method: ``upload(array) -> device pointer`` copies every array of the stream to the plan's device."""
+        args = [a if a is None or isinstance(a, str) else upload(a) for a in self.shared]
+        if self.method == "solve_separable":  # the device twin is told n_q; the host method reads it off the table
+            args.insert(1, 1 if self.shared[0] == "affine" else int(self.shared[1].shape[1]))
+        getattr(plan, self.method + "_device")(len(self), *args, upload(self.per_cell), M_ptr, out_ptr, info_ptr, stream)
+
+
 class MicroCellPlan:
     """Everything batch-independent for one (dim, n_micro, kind): kernel choice + device scratch.
 
@@ -109,20 +153,10 @@ class MicroCellPlan:
         if kind not in KINDS:
             raise ValueError(f"unknown kind {kind!r}; expected one of {sorted(KINDS)}")
         self._lib = _lib.load()
-        self.dim, self.n_micro, self.kind, self.device = int(dim), int(n_micro), kind, int(device)
-        desc = _lib.PlanDesc(self.dim, self.n_micro, KINDS[kind], self.device, int(flags))
+        desc = _lib.PlanDesc(int(dim), int(n_micro), KINDS[kind], int(device), int(flags))
         h = C.c_void_p()
         _lib.check(self._lib.hommx_plan_create(C.byref(h), C.byref(desc)), "hommx_plan_create")
-        self._h = h
-        self.n_el = int(self._lib.hommx_plan_num_elements(h))
-        self.n_comp = int(self._lib.hommx_plan_coef_components(h))
-        self.t = int(self._lib.hommx_plan_tensor_size(h))
-        self.kernel = self._lib.hommx_plan_kernel_name(h).decode()
-        self.route_detail = self._lib.hommx_plan_route_detail(h).decode()  # what that route launches for this plan (reports)
-        self.flops_per_solve = float(self._lib.hommx_plan_flops_per_solve(h))  # dense flops of the route, by its own model
-        self.n_nodes = self.n_micro**self.dim  # periodic nodes (correctors: dof = node * bs + component)
-        self.front_width = 0
-        self.to_periodic = None
+        self._adopt(h, int(dim), int(n_micro), kind, device, int(n_micro) ** int(dim), None)
 
     @classmethod
     def from_mesh(cls, msh, kind: str = "poisson", device: int = 0, order=None, constraint=None, route: str | None = None) -> "MicroCellPlan":
@@ -147,18 +181,22 @@ class MicroCellPlan:
             _lib.check(self._lib.hommx_mesh_analyze(C.byref(desc), None, None), "hommx_mesh_analyze")
         h = C.c_void_p()
         _lib.check(self._lib.hommx_plan_create_mesh(C.byref(h), C.byref(desc)), "hommx_plan_create_mesh")
+        self._adopt(h, int(desc.dim), None, kind, device, int(desc.n_nodes), keep["to_periodic"])
+        return self
+
+    def _adopt(self, h, dim: int, n_micro: int | None, kind: str, device: int, n_nodes: int, to_periodic):
+        """Take the handle of a created plan and read what the library decided for it."""
         self._h = h
-        self.dim, self.n_micro, self.kind, self.device = int(desc.dim), None, kind, int(device)
+        self.dim, self.n_micro, self.kind, self.device = dim, n_micro, kind, int(device)
         self.n_el = int(self._lib.hommx_plan_num_elements(h))
         self.n_comp = int(self._lib.hommx_plan_coef_components(h))
         self.t = int(self._lib.hommx_plan_tensor_size(h))
         self.kernel = self._lib.hommx_plan_kernel_name(h).decode()
-        self.route_detail = self._lib.hommx_plan_route_detail(h).decode()
-        self.flops_per_solve = float(self._lib.hommx_plan_flops_per_solve(h))
-        self.n_nodes = int(desc.n_nodes)
-        self.front_width = int(self._lib.hommx_plan_front_width(h))
-        self.to_periodic = keep["to_periodic"]
-        return self
+        self.route_detail = self._lib.hommx_plan_route_detail(h).decode()  # what that route launches for this plan (reports)
+        self.flops_per_solve = float(self._lib.hommx_plan_flops_per_solve(h))  # dense flops of the route, by its own model
+        self.n_nodes = n_nodes  # periodic nodes (correctors: dof = node * bs + component)
+        self.front_width = int(self._lib.hommx_plan_front_width(h))  # 0 unless the frontal mesh route
+        self.to_periodic = to_periodic
 
     def reserve(self, n_cells: int):
         """Allocate the device workspace for batches of up to ``n_cells`` now (otherwise the first solve does it)."""
@@ -176,85 +214,64 @@ class MicroCellPlan:
             pass
 
     # -- host arrays -----------------------------------------------------------------------------
+    def _check_coef(self, coef) -> tuple[np.ndarray, int]:
+        """coef[N_c, n_el(, n_comp)] as contiguous float64, and N_c."""
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        nc = coef.shape[0]
+        if coef.size != nc * self.n_el * self.n_comp:
+            raise ValueError(f"coef has shape {coef.shape}; expected ({nc}, {self.n_el}" + (f", {self.n_comp})" if self.n_comp > 1 else ")"))
+        return coef, nc
+
+    def _check_M(self, M, nc: int) -> tuple[np.ndarray | None, int | None]:
+        """M[N_c, d, d] as contiguous float64 and its address (the caller holds the array while the address is in use); None, None without M."""
+        if M is None:
+            return None, None
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        if M.shape != (nc, self.dim, self.dim):
+            raise ValueError(f"M has shape {M.shape}; expected ({nc}, {self.dim}, {self.dim})")
+        return M, M.ctypes.data
+
+    def _host_call(self, what: str, nc: int, M, call, return_info: bool = True):
+        """Check ``M``, allocate A_eff[N_c, t, t] and info[N_c], run ``call(M address, A_eff address, info address) -> status`` of the host
+        entry point ``what`` unless the batch is empty; returns (A_eff, info), or A_eff alone."""
+        M, Mp = self._check_M(M, nc)
+        out = np.empty((nc, self.t, self.t), dtype=np.float64)
+        info = np.zeros(nc, dtype=np.int32)
+        if nc:
+            _lib.check(call(Mp, out.ctypes.data, info.ctypes.data), what)
+        return (out, info) if return_info else out
+
     def solve(self, coef: np.ndarray, M: np.ndarray | None = None, return_info: bool = False,
               return_correctors: bool = False):
         """coef[N_c, n_el(, n_comp)] float64, M[N_c, d, d] or None -> A_eff[N_c, t, t] (and info[N_c]).
 
         With ``return_correctors`` the result is (A_eff, correctors[N_c, t, n^d * bs][, info]): the periodic cell solutions
         of the canonical loads (mean-free), dof = node * bs + component."""
-        coef = np.ascontiguousarray(coef, dtype=np.float64)
-        nc = coef.shape[0]
-        if coef.size != nc * self.n_el * self.n_comp:
-            raise ValueError(
-                f"coef has shape {coef.shape}; expected ({nc}, {self.n_el}"
-                + (f", {self.n_comp})" if self.n_comp > 1 else ")")
-            )
-        Mp = None
-        if M is not None:
-            M = np.ascontiguousarray(M, dtype=np.float64)
-            if M.shape != (nc, self.dim, self.dim):
-                raise ValueError(f"M has shape {M.shape}; expected ({nc}, {self.dim}, {self.dim})")
-            Mp = M.ctypes.data
-        out = np.empty((nc, self.t, self.t), dtype=np.float64)
-        info = np.zeros(nc, dtype=np.int32)
+        coef, nc = self._check_coef(coef)
         if return_correctors:
             bs = 1 if self.kind.startswith("poisson") else self.dim
             corr = np.empty((nc, self.t, self.n_nodes * bs), dtype=np.float64)
-            if nc:
-                _lib.check(
-                    self._lib.hommx_solve_batch_correctors(
-                        self._h, nc, coef.ctypes.data, Mp, out.ctypes.data, corr.ctypes.data, info.ctypes.data
-                    ),
-                    "hommx_solve_batch_correctors",
-                )
+            out, info = self._host_call("hommx_solve_batch_correctors", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch_correctors(
+                self._h, nc, coef.ctypes.data, Mp, o, corr.ctypes.data, i))
             return (out, corr, info) if return_info else (out, corr)
-        if nc:
-            _lib.check(
-                self._lib.hommx_solve_batch(self._h, nc, coef.ctypes.data, Mp, out.ctypes.data, info.ctypes.data),
-                "hommx_solve_batch",
-            )
-        return (out, info) if return_info else out
+        return self._host_call("hommx_solve_batch", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch(self._h, nc, coef.ctypes.data, Mp, o, i),
+                               return_info)
 
     def reconstruct(self, coef: np.ndarray, xi: np.ndarray, M: np.ndarray | None = None, fields: bool = False) -> Reconstruction:
         """HMM reconstruction (hommx_reconstruct_batch): coef[N_c, n_el(, n_comp)] and M as ``solve``, xi[N_c, t] the macro gradient /
         engineering-Voigt strain of every cell -> ``Reconstruction``; ``fields``: the per-element strain and flux [N_c, n_el, t] as well.
         The correctors never leave the device; the batch runs in chunks of HOMMX_RECON_MEM_MB of correctors."""
-        coef = np.ascontiguousarray(coef, dtype=np.float64)
-        nc = coef.shape[0]
-        if coef.size != nc * self.n_el * self.n_comp:
-            raise ValueError(f"coef has shape {coef.shape}; expected ({nc}, {self.n_el}" + (f", {self.n_comp})" if self.n_comp > 1 else ")"))
+        coef, nc = self._check_coef(coef)
         xi = np.ascontiguousarray(xi, dtype=np.float64)
         if xi.shape != (nc, self.t):
             raise ValueError(f"xi has shape {xi.shape}; expected ({nc}, {self.t})")
-        Mp = None
-        if M is not None:
-            M = np.ascontiguousarray(M, dtype=np.float64)
-            if M.shape != (nc, self.dim, self.dim):
-                raise ValueError(f"M has shape {M.shape}; expected ({nc}, {self.dim}, {self.dim})")
-            Mp = M.ctypes.data
         stats = np.empty((nc, 2 * self.t + 3), dtype=np.float64)
-        A = np.empty((nc, self.t, self.t), dtype=np.float64)
-        info = np.zeros(nc, dtype=np.int32)
         strain = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
         flux = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
-        if nc:
-            _lib.check(
-                self._lib.hommx_reconstruct_batch(self._h, nc, coef.ctypes.data, Mp, xi.ctypes.data, stats.ctypes.data,
-                                                  strain.ctypes.data if fields else None, flux.ctypes.data if fields else None,
-                                                  A.ctypes.data, info.ctypes.data),
-                "hommx_reconstruct_batch",
-            )
+        A, info = self._host_call("hommx_reconstruct_batch", nc, M, lambda Mp, o, i: self._lib.hommx_reconstruct_batch(
+            self._h, nc, coef.ctypes.data, Mp, xi.ctypes.data, stats.ctypes.data, strain.ctypes.data if fields else None,
+            flux.ctypes.data if fields else None, o, i))
         return Reconstruction.from_stats(xi, stats, A, info, strain, flux)
-
-    def reconstruct_device(self, n_cells: int, coef_ptr: int, M_ptr: int | None, xi_ptr: int, stats_ptr: int, strain_ptr: int | None = None,
-                           flux_ptr: int | None = None, A_ptr: int | None = None, info_ptr: int | None = None, stream: int | None = None):
-        """Device-pointer form of ``reconstruct`` (hommx_reconstruct_batch_device), asynchronous on ``stream``: stats[n_cells, 2t + 3] =
-        [mean_strain | mean_flux | energy | max_flux | argmax_element]."""
-        _lib.check(
-            self._lib.hommx_reconstruct_batch_device(self._h, int(n_cells), coef_ptr, M_ptr or None, xi_ptr, stats_ptr, strain_ptr or None,
-                                                     flux_ptr or None, A_ptr or None, info_ptr or None, stream or None),
-            "hommx_reconstruct_batch_device",
-        )
 
     def solve_two_phase(self, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None = None,
                         return_info: bool = False):
@@ -267,22 +284,8 @@ class MicroCellPlan:
         nc = values.shape[0]
         if values.size != nc * 2 * self.n_comp:
             raise ValueError(f"values has shape {values.shape}; expected ({nc}, 2" + (f", {self.n_comp})" if self.n_comp > 1 else ")"))
-        Mp = None
-        if M is not None:
-            M = np.ascontiguousarray(M, dtype=np.float64)
-            if M.shape != (nc, self.dim, self.dim):
-                raise ValueError(f"M has shape {M.shape}; expected ({nc}, {self.dim}, {self.dim})")
-            Mp = M.ctypes.data
-        out = np.empty((nc, self.t, self.t), dtype=np.float64)
-        info = np.zeros(nc, dtype=np.int32)
-        if nc:
-            _lib.check(
-                self._lib.hommx_solve_batch_two_phase(
-                    self._h, nc, mask.ctypes.data, values.ctypes.data, Mp, out.ctypes.data, info.ctypes.data
-                ),
-                "hommx_solve_batch_two_phase",
-            )
-        return (out, info) if return_info else out
+        return self._host_call("hommx_solve_batch_two_phase", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch_two_phase(
+            self._h, nc, mask.ctypes.data, values.ctypes.data, Mp, o, i), return_info)
 
     def solve_separable(self, family: str, table: np.ndarray, weights: np.ndarray | None, params: np.ndarray,
                         M: np.ndarray | None = None, return_info: bool = False):
@@ -301,21 +304,19 @@ class MicroCellPlan:
         want = (nc, 2) if self.n_comp == 1 else (nc, self.n_comp, 2)
         if params.shape != want:
             raise ValueError(f"params has shape {params.shape}; expected {want}")
-        Mp = None
-        if M is not None:
-            M = np.ascontiguousarray(M, dtype=np.float64)
-            if M.shape != (nc, self.dim, self.dim):
-                raise ValueError(f"M has shape {M.shape}; expected ({nc}, {self.dim}, {self.dim})")
-            Mp = M.ctypes.data
-        out = np.empty((nc, self.t, self.t), dtype=np.float64)
-        info = np.zeros(nc, dtype=np.int32)
-        if nc:
-            _lib.check(
-                self._lib.hommx_solve_batch_separable(self._h, nc, fam, nq, table.ctypes.data, None if w is None else w.ctypes.data,
-                                                      params.ctypes.data, Mp, out.ctypes.data, info.ctypes.data),
-                "hommx_solve_batch_separable",
-            )
-        return (out, info) if return_info else out
+        return self._host_call("hommx_solve_batch_separable", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch_separable(
+            self._h, nc, fam, nq, table.ctypes.data, None if w is None else w.ctypes.data, params.ctypes.data, Mp, o, i), return_info)
+
+    # -- device pointers (torch tensors or raw ints), asynchronous --------------------------------
+    def reconstruct_device(self, n_cells: int, coef_ptr: int, M_ptr: int | None, xi_ptr: int, stats_ptr: int, strain_ptr: int | None = None,
+                           flux_ptr: int | None = None, A_ptr: int | None = None, info_ptr: int | None = None, stream: int | None = None):
+        """Device-pointer form of ``reconstruct`` (hommx_reconstruct_batch_device), asynchronous on ``stream``: stats[n_cells, 2t + 3] =
+        [mean_strain | mean_flux | energy | max_flux | argmax_element]."""
+        _lib.check(
+            self._lib.hommx_reconstruct_batch_device(self._h, int(n_cells), coef_ptr, M_ptr or None, xi_ptr, stats_ptr, strain_ptr or None,
+                                                     flux_ptr or None, A_ptr or None, info_ptr or None, stream or None),
+            "hommx_reconstruct_batch_device",
+        )
 
     def solve_separable_device(self, n_cells: int, family: str, n_q: int, table_ptr: int, weights_ptr: int | None, params_ptr: int,
                                M_ptr: int | None, out_ptr: int, info_ptr: int | None, stream: int | None = None):
@@ -335,7 +336,6 @@ class MicroCellPlan:
             "hommx_solve_batch_two_phase_device",
         )
 
-    # -- device pointers (torch tensors or raw ints), asynchronous --------------------------------
     def solve_device(self, n_cells: int, coef_ptr: int, M_ptr: int | None, out_ptr: int, info_ptr: int | None,
                      stream: int | None = None):
         _lib.check(

@@ -15,6 +15,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .batch import CoefStream, MicroCellPlan
+
 
 def shard_range(n_cells: int, rank: int, world: int) -> tuple[int, int, int]:
     """Contiguous block partition padded to equal counts: returns (begin, end, per_rank).
@@ -165,107 +167,54 @@ def run_sharded(t: int, n_cells: int, local_solve, group=None, device=None):
     return full[:, : t * t].reshape(n_cells, t, t).copy(), np.rint(full[:, t * t]).astype(np.int32)
 
 
-def _has_device_entry(plan) -> bool:
-    return hasattr(plan, "solve_device") and hasattr(plan, "device")
-
-
 def _on_rccl(group=None) -> bool:
     import torch.distributed as dist
 
     return dist.is_available() and dist.is_initialized() and dist.get_backend(group) == "nccl"
 
 
-def solve_block(plan, coef: np.ndarray, M: np.ndarray | None, group=None):
-    """One rank's block through ``plan``: on a real plan under the RCCL backend the result stays on the device
-    (torch tensors, torch's current stream); otherwise ``plan.solve`` on host arrays."""
+def solve_block(plan, stream: CoefStream, M: np.ndarray | None, group=None):
+    """One rank's block of cells through ``plan`` -> (A_eff, info).  A ``MicroCellPlan`` under the RCCL backend: every array of the
+    stream and ``M`` are uploaded to the plan's device, the device twin of the stream's method runs on torch's current stream and the
+    result stays there (torch tensors) until the collective.  Otherwise the host method of ``plan``, with ``return_info=True``."""
+    if not (isinstance(plan, MicroCellPlan) and _on_rccl(group)):
+        return stream.solve(plan, M, return_info=True)
     import torch
 
-    if _has_device_entry(plan) and _on_rccl(group):
-        dev = torch.device("cuda", plan.device)
-        nc = coef.shape[0]
-        c = torch.from_numpy(np.ascontiguousarray(coef, dtype=np.float64)).to(dev)
-        m = None if M is None else torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(dev)
-        out = torch.empty((nc, plan.t, plan.t), dtype=torch.float64, device=dev)
-        info = torch.zeros(nc, dtype=torch.int32, device=dev)
-        plan.solve_device(nc, c.data_ptr(), None if m is None else m.data_ptr(), out.data_ptr(), info.data_ptr(),
-                          torch.cuda.current_stream(dev).cuda_stream)
-        return out, info
-    res = plan.solve(coef, M, return_info=True) if _accepts_return_info(plan.solve) else (plan.solve(coef, M), None)
-    A, info = res
-    return A, (np.zeros(len(coef), np.int32) if info is None else info)
+    dev = torch.device("cuda", plan.device)
+    held = []  # the uploads, until the launch below is queued (torch frees in stream order)
+
+    def upload(a):
+        held.append(torch.from_numpy(np.ascontiguousarray(a)).to(dev))
+        return held[-1].data_ptr()
+
+    out = torch.empty((len(stream), plan.t, plan.t), dtype=torch.float64, device=dev)
+    info = torch.zeros(len(stream), dtype=torch.int32, device=dev)
+    stream.solve_device(plan, upload, None if M is None else upload(np.asarray(M, dtype=np.float64)), out.data_ptr(), info.data_ptr(),
+                        torch.cuda.current_stream(dev).cuda_stream)
+    return out, info
 
 
-def solve_block_separable(plan, family: str, table: np.ndarray, weights: np.ndarray | None, params: np.ndarray,
-                          M: np.ndarray | None, group=None):
-    """Separable coefficient (table of g once + (a, b) per cell): under RCCL the shard's tensors stay on the device."""
-    import torch
-
-    if hasattr(plan, "solve_separable_device") and hasattr(plan, "device") and _on_rccl(group):
-        dev = torch.device("cuda", plan.device)
-        nc = params.shape[0]
-        tb = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(dev)
-        nq = 1 if family == "affine" else int(table.shape[1])
-        w = None if weights is None else torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64)).to(dev)
-        pr = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float64)).to(dev)
-        m = None if M is None else torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(dev)
-        out = torch.empty((nc, plan.t, plan.t), dtype=torch.float64, device=dev)
-        info = torch.zeros(nc, dtype=torch.int32, device=dev)
-        plan.solve_separable_device(nc, family, nq, tb.data_ptr(), None if w is None else w.data_ptr(), pr.data_ptr(),
-                                    None if m is None else m.data_ptr(), out.data_ptr(), info.data_ptr(),
-                                    torch.cuda.current_stream(dev).cuda_stream)
-        return out, info
-    return plan.solve_separable(family, table, weights, params, M, return_info=True)
-
-
-def solve_block_two_phase(plan, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None, group=None):
-    import torch
-
-    if hasattr(plan, "solve_two_phase_device") and hasattr(plan, "device") and _on_rccl(group):
-        dev = torch.device("cuda", plan.device)
-        nc = values.shape[0]
-        mk = torch.from_numpy(np.ascontiguousarray(np.asarray(mask).astype(np.uint8))).to(dev)
-        v = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64)).to(dev)
-        m = None if M is None else torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(dev)
-        out = torch.empty((nc, plan.t, plan.t), dtype=torch.float64, device=dev)
-        info = torch.zeros(nc, dtype=torch.int32, device=dev)
-        plan.solve_two_phase_device(nc, mk.data_ptr(), v.data_ptr(), None if m is None else m.data_ptr(), out.data_ptr(),
-                                    info.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        return out, info
-    if _accepts_return_info(plan.solve_two_phase):
-        return plan.solve_two_phase(mask, values, M, return_info=True)
-    return plan.solve_two_phase(mask, values, M), np.zeros(len(values), np.int32)
-
-
-def _accepts_return_info(fn) -> bool:
-    import inspect
-
-    try:
-        return "return_info" in inspect.signature(fn).parameters
-    except (TypeError, ValueError):
-        return False
-
-
-def solve_sharded(plan, coef: np.ndarray, M: np.ndarray | None, group=None, device=None, return_info: bool = False):
-    """Convenience form for callers that hold the whole batch: every rank solves its block of ``coef`` / ``M`` and the field
-    (and info) is all-gathered.  With no process group it degenerates to ``plan.solve``.  ``plan`` may be any object with
-    ``.solve`` and ``.t`` (the gloo tests use the CPU oracle)."""
+def _solve_sharded(plan, stream: CoefStream, M, group, device, return_info: bool):
+    """Every rank solves its block of ``stream`` / ``M`` and the field (and info) is all-gathered; with no process group, the host method
+    of ``plan``.  ``plan``: a MicroCellPlan, or any object with ``t`` and the stream's host method (the gloo tests use the CPU oracle)."""
     import torch.distributed as dist
 
     if not (dist.is_available() and dist.is_initialized()):
-        return plan.solve(coef, M, return_info=True) if return_info else plan.solve(coef, M)
-    A, info = run_sharded(plan.t, coef.shape[0], lambda b, e: solve_block(plan, coef[b:e], None if M is None else M[b:e], group),
-                          group, device if device is not None else getattr(plan, "device", None))
+        return stream.solve(plan, M, return_info=return_info)
+    if device is None and isinstance(plan, MicroCellPlan):
+        device = plan.device
+    A, info = run_sharded(plan.t, len(stream), lambda b, e: solve_block(plan, stream.block(b, e), None if M is None else M[b:e], group),
+                          group, device)
     return (A, info) if return_info else A
+
+
+def solve_sharded(plan, coef: np.ndarray, M: np.ndarray | None, group=None, device=None, return_info: bool = False):
+    """Convenience form for callers that hold the whole batch of sampled element means (``_solve_sharded``)."""
+    return _solve_sharded(plan, CoefStream.sampled(coef), M, group, device, return_info)
 
 
 def solve_sharded_two_phase(plan, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None, group=None, device=None,
                             return_info: bool = False):
     """Same for two-phase media: every rank holds the phase mask, the per-cell phase values shard."""
-    import torch.distributed as dist
-
-    if not (dist.is_available() and dist.is_initialized()):
-        return plan.solve_two_phase(mask, values, M, return_info=True) if return_info else plan.solve_two_phase(mask, values, M)
-    A, info = run_sharded(plan.t, values.shape[0],
-                          lambda b, e: solve_block_two_phase(plan, mask, values[b:e], None if M is None else M[b:e], group), group,
-                          device if device is not None else getattr(plan, "device", None))
-    return (A, info) if return_info else A
+    return _solve_sharded(plan, CoefStream.two_phase(mask, values), M, group, device, return_info)

@@ -47,20 +47,8 @@ class MultiGpuSolver:
             pass
 
     def solve(self, coef: np.ndarray, M: np.ndarray | None = None, return_info: bool = False):
-        coef = np.ascontiguousarray(coef, dtype=np.float64)
-        nc = coef.shape[0]
-        if coef.size != nc * self.n_el * self.n_comp:
-            raise ValueError(f"coef has shape {coef.shape}; expected ({nc}, {self.n_el}" + (f", {self.n_comp})" if self.n_comp > 1 else ")"))
-        Mp = None
-        if M is not None:
-            M = np.ascontiguousarray(M, dtype=np.float64)
-            if M.shape != (nc, self.dim, self.dim):
-                raise ValueError(f"M has shape {M.shape}; expected ({nc}, {self.dim}, {self.dim})")
-            Mp = M.ctypes.data
-        out = np.empty((nc, self.t, self.t), dtype=np.float64)
-        info = np.zeros(nc, dtype=np.int32)
+        """Checks and return value are those of ``MicroCellPlan.solve``; the cells are block-partitioned over the devices."""
+        coef, nc = self.plans[0]._check_coef(coef)
         plans = (C.c_void_p * len(self.plans))(*[p._h for p in self.plans])
-        if nc:
-            _lib.check(self._lib.hommx_solve_batch_multi(self._h, plans, nc, coef.ctypes.data, Mp, out.ctypes.data, info.ctypes.data),
-                       "hommx_solve_batch_multi")
-        return (out, info) if return_info else out
+        return self.plans[0]._host_call("hommx_solve_batch_multi", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch_multi(
+            self._h, plans, nc, coef.ctypes.data, Mp, o, i), return_info)

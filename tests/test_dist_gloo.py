@@ -17,14 +17,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 class _OraclePlan:
     t = 2
 
-    def solve(self, coef, M=None):
+    def solve(self, coef, M=None, return_info=False):
         from oracle import hommx_oracle as O
 
         n = int(round(np.sqrt(coef.shape[1] / 2)))
-        return O.effective_tensor_batch("poisson", 2, n, coef, M)
+        A = O.effective_tensor_batch("poisson", 2, n, coef, M)
+        return (A, np.zeros(len(coef), np.int32)) if return_info else A
 
-    def solve_two_phase(self, mask, values, M=None):
-        return self.solve(np.where(np.asarray(mask, bool)[None, :], values[:, 1:2], values[:, 0:1]), M)
+    def solve_two_phase(self, mask, values, M=None, return_info=False):
+        return self.solve(np.where(np.asarray(mask, bool)[None, :], values[:, 1:2], values[:, 0:1]), M, return_info)
 
 
 def _worker(rank, world, port, n_cells, q):
