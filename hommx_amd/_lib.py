@@ -20,6 +20,10 @@ SAMPLER_AFFINE = 0
 SAMPLER_RECIPROCAL = 1
 MESH_MAX_FRONT = 192  # HOMMX_MESH_MAX_FRONT
 MESH_FLAG_TREE = 1  # HOMMX_MESH_FLAG_TREE
+COEF_SAMPLED = 0  # HOMMX_COEF_*: the form of a hommx_coef_source
+COEF_TWO_PHASE = 1
+COEF_SEPARABLE = 2
+RECON_MAX_REGIONS = 8  # HOMMX_RECON_MAX_REGIONS
 
 
 class PlanDesc(C.Structure):
@@ -45,6 +49,23 @@ class MeshDesc(C.Structure):
         ("el_x", C.c_void_p),
         ("order", C.c_void_p),
         ("reserved", C.c_int32 * 4),
+    ]
+
+
+class CoefSource(C.Structure):
+    """hommx_coef_source: only the pointers of ``form`` are read."""
+
+    _fields_ = [
+        ("form", C.c_int32),
+        ("family", C.c_int32),
+        ("n_q", C.c_int32),
+        ("reserved", C.c_int32),
+        ("coef", C.c_void_p),
+        ("mask", C.c_void_p),
+        ("values", C.c_void_p),
+        ("table", C.c_void_p),
+        ("weights", C.c_void_p),
+        ("params", C.c_void_p),
     ]
 
 
@@ -78,6 +99,8 @@ def _prototypes() -> dict:
         "hommx_solve_batch_correctors": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
         "hommx_reconstruct_batch": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_reconstruct_batch_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "hommx_reconstruct_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "hommx_reconstruct_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_two_phase": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_two_phase_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_separable": (c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),

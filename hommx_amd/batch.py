@@ -78,7 +78,12 @@ class Reconstruction:
     ``xi[N, t]``: the macro gradient / engineering-Voigt strain of every cell.  ``mean_strain`` / ``mean_flux`` ``[N, t]``: sum |K| s_K and
     sum |K| q_K over the micro elements; ``energy[N]``: sum |K| s_K . q_K; ``max_flux[N]``: the largest |q_K| (Frobenius norm of the stress
     for elasticity) and ``argmax_element[N]`` the smallest element reaching it.  ``strain`` / ``flux`` ``[N, n_el, t]`` or None.  On the
-    discrete problem mean_strain = xi, mean_flux = A_eff xi and energy = xi . A_eff xi.  ``cells``: the macro cells (``BaseHMM.reconstruct``)."""
+    discrete problem mean_strain = xi, mean_flux = A_eff xi and energy = xi . A_eff xi.  ``cells``: the macro cells (``BaseHMM.reconstruct``).
+
+    With regions (hommx_reconstruct_source; R of them): ``region_volume[N, R]`` the volume of the elements labelled r, ``region_mean_strain`` /
+    ``region_mean_flux`` ``[N, R, t]`` their sums divided by that volume (NaN where it is 0), ``region_energy[N, R]`` the region's part of
+    ``energy`` (not divided: the regions of a cover sum to it), ``region_max_flux[N, R]`` the largest |q_K| in the region (-1 in an empty one)
+    and ``region_argmax_element[N, R]`` the smallest of its elements reaching it (-1)."""
 
     xi: np.ndarray
     mean_strain: np.ndarray
@@ -91,12 +96,56 @@ class Reconstruction:
     strain: np.ndarray | None = None
     flux: np.ndarray | None = None
     cells: np.ndarray | None = None
+    region_volume: np.ndarray | None = None
+    region_mean_strain: np.ndarray | None = None
+    region_mean_flux: np.ndarray | None = None
+    region_energy: np.ndarray | None = None
+    region_max_flux: np.ndarray | None = None
+    region_argmax_element: np.ndarray | None = None
 
     @classmethod
-    def from_stats(cls, xi, stats, A_eff, info, strain=None, flux=None, cells=None) -> "Reconstruction":
+    def from_stats(cls, xi, stats, A_eff, info, strain=None, flux=None, cells=None, region_stats=None) -> "Reconstruction":
+        """From the library's rows: stats[N, 2t + 3] and, with regions, region_stats[N, R, 2t + 4] = [volume | sums | max | argmax], whose
+        sums are not divided by the volume."""
         t = xi.shape[1]
-        return cls(xi, stats[:, :t].copy(), stats[:, t:2 * t].copy(), stats[:, 2 * t].copy(), stats[:, 2 * t + 1].copy(),
-                   stats[:, 2 * t + 2].astype(np.int64), A_eff, info, strain, flux, cells)
+        r = cls(xi, stats[:, :t].copy(), stats[:, t:2 * t].copy(), stats[:, 2 * t].copy(), stats[:, 2 * t + 1].copy(),
+                stats[:, 2 * t + 2].astype(np.int64), A_eff, info, strain, flux, cells)
+        if region_stats is not None:
+            vol = region_stats[:, :, 0].copy()
+            inv = np.full_like(vol, np.nan)
+            np.divide(1.0, vol, out=inv, where=vol > 0)
+            r.region_volume = vol
+            r.region_mean_strain = region_stats[:, :, 1:1 + t] * inv[:, :, None]
+            r.region_mean_flux = region_stats[:, :, 1 + t:1 + 2 * t] * inv[:, :, None]
+            r.region_energy = region_stats[:, :, 1 + 2 * t].copy()
+            r.region_max_flux = region_stats[:, :, 2 + 2 * t].copy()
+            r.region_argmax_element = region_stats[:, :, 3 + 2 * t].astype(np.int64)
+        return r
+
+
+REGION_FIELDS = ("region_volume", "region_mean_strain", "region_mean_flux", "region_energy", "region_max_flux", "region_argmax_element")
+
+
+def region_labels(labels, n_el: int, n_regions: int | None = None) -> tuple[np.ndarray, int]:
+    """labels[n_el] (integers or bool) as the uint8 array the library takes, and the number of regions.  A label below 0 or above 254
+    becomes 255; every label >= n_regions belongs to no region.  ``n_regions`` defaults to the largest label below
+    HOMMX_RECON_MAX_REGIONS plus one."""
+    lab = np.asarray(labels)
+    if lab.dtype == bool:
+        lab = lab.astype(np.uint8)
+    if not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"region labels must be integers; got {lab.dtype}")
+    if lab.shape != (n_el,):
+        raise ValueError(f"regions has shape {lab.shape}; expected ({n_el},)")
+    out = np.ascontiguousarray(np.where((lab >= 0) & (lab < 255), lab, 255).astype(np.uint8))
+    if n_regions is None:
+        used = out[out < _lib.RECON_MAX_REGIONS]
+        if used.size == 0:
+            raise ValueError(f"no region label below {_lib.RECON_MAX_REGIONS}")
+        n_regions = int(used.max()) + 1
+    if not 1 <= int(n_regions) <= _lib.RECON_MAX_REGIONS:
+        raise ValueError(f"n_regions must be 1 .. {_lib.RECON_MAX_REGIONS}; got {n_regions}")
+    return out, int(n_regions)
 
 
 @dataclass(frozen=True)
@@ -126,6 +175,22 @@ class CoefStream:
 
     def __len__(self) -> int:
         return self.per_cell.shape[0]
+
+    def coef_source(self, address=lambda a: a.ctypes.data) -> "_lib.CoefSource":
+        """The stream as the hommx_coef_source of the reconstruct entry points: the one place that spells the three forms for them.
+        ``address(array) -> pointer``: the array's own address (host entry; the stream keeps the arrays alive), or an upload."""
+        src = _lib.CoefSource()
+        if self.method == "solve":
+            src.form, src.coef = _lib.COEF_SAMPLED, address(self.per_cell)
+        elif self.method == "solve_two_phase":
+            src.form, src.mask, src.values = _lib.COEF_TWO_PHASE, address(self.shared[0]), address(self.per_cell)
+        else:
+            family, table, weights = self.shared
+            src.form, src.table, src.params = _lib.COEF_SEPARABLE, address(table), address(self.per_cell)
+            src.family = {"affine": _lib.SAMPLER_AFFINE, "reciprocal": _lib.SAMPLER_RECIPROCAL}[family]
+            src.n_q = 1 if family == "affine" else int(table.shape[1])
+            src.weights = None if weights is None or family == "affine" else address(weights)
+        return src
 
     def block(self, b: int, e: int) -> "CoefStream":
         """Cells [b, e) of the stream (the shared arguments are shared, not copied)."""
@@ -257,21 +322,68 @@ class MicroCellPlan:
         return self._host_call("hommx_solve_batch", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch(self._h, nc, coef.ctypes.data, Mp, o, i),
                                return_info)
 
-    def reconstruct(self, coef: np.ndarray, xi: np.ndarray, M: np.ndarray | None = None, fields: bool = False) -> Reconstruction:
-        """HMM reconstruction (hommx_reconstruct_batch): coef[N_c, n_el(, n_comp)] and M as ``solve``, xi[N_c, t] the macro gradient /
-        engineering-Voigt strain of every cell -> ``Reconstruction``; ``fields``: the per-element strain and flux [N_c, n_el, t] as well.
-        The correctors never leave the device; the batch runs in chunks of HOMMX_RECON_MEM_MB of correctors."""
-        coef, nc = self._check_coef(coef)
+    def _check_stream(self, stream: CoefStream) -> int:
+        """Shapes of a sampler stream against the plan (what ``solve_two_phase`` / ``solve_separable`` check); returns N_c."""
+        nc = len(stream)
+        if stream.method == "solve":
+            return self._check_coef(stream.per_cell)[1]
+        if stream.method == "solve_two_phase":
+            if stream.shared[0].shape != (self.n_el,):
+                raise ValueError(f"mask has shape {stream.shared[0].shape}; expected ({self.n_el},)")
+            if stream.per_cell.size != nc * 2 * self.n_comp:
+                raise ValueError(f"values has shape {stream.per_cell.shape}; expected ({nc}, 2" + (f", {self.n_comp})" if self.n_comp > 1 else ")"))
+            return nc
+        family, table, weights = stream.shared
+        nq = 1 if family == "affine" else int(table.shape[1])
+        if table.size != self.n_el * nq:
+            raise ValueError(f"table has shape {table.shape}; expected ({self.n_el}" + (f", {nq})" if nq > 1 else ",)"))
+        if family == "reciprocal" and (weights is None or weights.shape != (nq,)):
+            raise ValueError(f"weights must have shape ({nq},)")
+        want = (nc, 2) if self.n_comp == 1 else (nc, self.n_comp, 2)
+        if stream.per_cell.shape != want:
+            raise ValueError(f"params has shape {stream.per_cell.shape}; expected {want}")
+        return nc
+
+    def reconstruct(self, coef, xi: np.ndarray, M: np.ndarray | None = None, fields: bool = False, regions=None,
+                    n_regions: int | None = None) -> Reconstruction:
+        """HMM reconstruction: ``coef`` an array coef[N_c, n_el(, n_comp)] as ``solve`` takes it, or a ``CoefStream`` in any of its three
+        forms (a sampler form sends a few numbers per cell and is expanded on the device: hommx_reconstruct_source); M as ``solve``,
+        xi[N_c, t] the macro gradient / engineering-Voigt strain of every cell -> ``Reconstruction``; ``fields``: the per-element strain and
+        flux [N_c, n_el, t] as well.  The correctors never leave the device; the batch runs in chunks of HOMMX_RECON_MEM_MB of correctors.
+
+        ``regions``: integer labels [n_el] of the micro elements -> the ``region_*`` statistics over the elements of every label below
+        ``n_regions`` (default: the largest label below 8, plus one); elements with any other label are in no region.  ``True`` with a
+        two-phase stream: its mask is the labels (region 0: phase 0, region 1: phase 1)."""
+        stream = coef if isinstance(coef, CoefStream) else None
+        if stream is None and regions is None:  # the plain entry point, as before there were sources
+            coef, nc = self._check_coef(coef)
+        else:
+            stream = stream or CoefStream.sampled(coef)
+            nc = self._check_stream(stream)
         xi = np.ascontiguousarray(xi, dtype=np.float64)
         if xi.shape != (nc, self.t):
             raise ValueError(f"xi has shape {xi.shape}; expected ({nc}, {self.t})")
         stats = np.empty((nc, 2 * self.t + 3), dtype=np.float64)
         strain = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
         flux = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
-        A, info = self._host_call("hommx_reconstruct_batch", nc, M, lambda Mp, o, i: self._lib.hommx_reconstruct_batch(
-            self._h, nc, coef.ctypes.data, Mp, xi.ctypes.data, stats.ctypes.data, strain.ctypes.data if fields else None,
-            flux.ctypes.data if fields else None, o, i))
-        return Reconstruction.from_stats(xi, stats, A, info, strain, flux)
+        sp, fp = (strain.ctypes.data, flux.ctypes.data) if fields else (None, None)
+        if stream is None:
+            A, info = self._host_call("hommx_reconstruct_batch", nc, M, lambda Mp, o, i: self._lib.hommx_reconstruct_batch(
+                self._h, nc, coef.ctypes.data, Mp, xi.ctypes.data, stats.ctypes.data, sp, fp, o, i))
+            return Reconstruction.from_stats(xi, stats, A, info, strain, flux)
+        labels, nr = None, 0
+        if regions is True:
+            if stream.method != "solve_two_phase":
+                raise ValueError("regions=True takes the mask of a two-phase stream as the labels; pass labels for any other coefficient")
+            nr = 2
+        elif regions is not None:
+            labels, nr = region_labels(regions, self.n_el, n_regions)
+        rstats = np.empty((nc, nr, 2 * self.t + 4), dtype=np.float64) if nr else None
+        src = stream.coef_source()
+        A, info = self._host_call("hommx_reconstruct_source", nc, M, lambda Mp, o, i: self._lib.hommx_reconstruct_source(
+            self._h, nc, C.byref(src), Mp, xi.ctypes.data, nr, None if labels is None else labels.ctypes.data, stats.ctypes.data,
+            rstats.ctypes.data if nr else None, sp, fp, o, i))
+        return Reconstruction.from_stats(xi, stats, A, info, strain, flux, region_stats=rstats)
 
     def solve_two_phase(self, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None = None,
                         return_info: bool = False):
@@ -316,6 +428,20 @@ class MicroCellPlan:
             self._lib.hommx_reconstruct_batch_device(self._h, int(n_cells), coef_ptr, M_ptr or None, xi_ptr, stats_ptr, strain_ptr or None,
                                                      flux_ptr or None, A_ptr or None, info_ptr or None, stream or None),
             "hommx_reconstruct_batch_device",
+        )
+
+    def reconstruct_source_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, xi_ptr: int, stats_ptr: int,
+                                  n_regions: int = 0, region_ptr: int | None = None, region_stats_ptr: int | None = None,
+                                  strain_ptr: int | None = None, flux_ptr: int | None = None, A_ptr: int | None = None,
+                                  info_ptr: int | None = None, stream: int | None = None):
+        """Device-pointer form of ``reconstruct`` for any coefficient form (hommx_reconstruct_source_device), asynchronous on ``stream``:
+        ``source`` = ``CoefStream.coef_source(upload)`` with device addresses; region_stats[n_cells, n_regions, 2t + 4] =
+        [volume | sums (not divided) | max | argmax]; a two-phase source with ``n_regions`` 2 and no ``region_ptr`` takes its mask."""
+        _lib.check(
+            self._lib.hommx_reconstruct_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, xi_ptr, int(n_regions),
+                                                      region_ptr or None, stats_ptr, region_stats_ptr or None, strain_ptr or None,
+                                                      flux_ptr or None, A_ptr or None, info_ptr or None, stream or None),
+            "hommx_reconstruct_source_device",
         )
 
     def solve_separable_device(self, n_cells: int, family: str, n_q: int, table_ptr: int, weights_ptr: int | None, params_ptr: int,

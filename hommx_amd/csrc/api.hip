@@ -182,28 +182,36 @@ struct HostIn {
   const void* src;
   size_t bytes;
 };
-template <size_t N, typename Run>
-int staged_call(hommx_plan* p, int64_t n_cells, const HostIn (&in)[N], double* A_eff, int32_t* info, Run run) {
+// the inputs into the plan's pinned block and ONE asynchronous copy to its device twin; d_in[k]: the device copy of in[k] (null for a null input)
+template <size_t N>
+int stage_in(hommx_plan* p, const HostIn (&in)[N], const void* (&d_in)[N]) {
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
   size_t off[N], in_bytes = 0;
   for (size_t k = 0; k < N; ++k) {
     off[k] = in_bytes;
     if (in[k].src) in_bytes += up(in[k].bytes);
   }
-  const size_t a_bytes = sizeof(double) * n_cells * p->ks.t * p->ks.t, o_info = up(a_bytes), out_bytes = o_info + up(sizeof(int32_t) * n_cells);
   if (int rc = grow(p->pin_in, in_bytes)) return rc;
-  if (int rc = grow(p->pin_out, out_bytes)) return rc;
   if (int rc = grow(p->dev_in, in_bytes)) return rc;
-  if (int rc = grow(p->dev_out, out_bytes)) return rc;
   char* hin = static_cast<char*>(p->pin_in.p);
   char* din = static_cast<char*>(p->dev_in.p);
-  char* dout = static_cast<char*>(p->dev_out.p);
-  const void* d_in[N];
   for (size_t k = 0; k < N; ++k) {
     d_in[k] = in[k].src ? din + off[k] : nullptr;
     if (in[k].src) memcpy(hin + off[k], in[k].src, in[k].bytes);
   }
-  HIP_TRY(hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, nullptr));
+  if (in_bytes) HIP_TRY(hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, nullptr));
+  return HOMMX_OK;
+}
+
+template <size_t N, typename Run>
+int staged_call(hommx_plan* p, int64_t n_cells, const HostIn (&in)[N], double* A_eff, int32_t* info, Run run) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t a_bytes = sizeof(double) * n_cells * p->ks.t * p->ks.t, o_info = up(a_bytes), out_bytes = o_info + up(sizeof(int32_t) * n_cells);
+  if (int rc = grow(p->pin_out, out_bytes)) return rc;
+  if (int rc = grow(p->dev_out, out_bytes)) return rc;
+  char* dout = static_cast<char*>(p->dev_out.p);
+  const void* d_in[N];
+  if (int rc = stage_in(p, in, d_in)) return rc;
   if (int rc = run(d_in, reinterpret_cast<double*>(dout), reinterpret_cast<int32_t*>(dout + o_info))) return rc;
   HIP_TRY(hipMemcpyAsync(p->pin_out.p, dout, out_bytes, hipMemcpyDeviceToHost, nullptr));
   HIP_TRY(hipStreamSynchronize(nullptr));
@@ -211,6 +219,26 @@ int staged_call(hommx_plan* p, int64_t n_cells, const HostIn (&in)[N], double* A
   memcpy(A_eff, hout, a_bytes);
   if (info) memcpy(info, hout + o_info, sizeof(int32_t) * n_cells);
   return HOMMX_OK;
+}
+
+// kind and family of a separable sampler (hommx_solve_batch_separable, hommx_reconstruct_source): no device needed
+int sampler_check(const hommx_plan* p, int32_t family) {
+  if (p->desc.kind != HOMMX_KIND_POISSON_SCALAR && p->desc.kind != HOMMX_KIND_ELASTICITY_ISO)
+    return fail(HOMMX_EINVAL, "separable samplers are defined for the scalar Poisson and the isotropic elasticity kinds");
+  if (p->desc.kind == HOMMX_KIND_ELASTICITY_ISO && family != HOMMX_SAMPLER_AFFINE)
+    return fail(HOMMX_EINVAL, "the isotropic elasticity kind takes the affine sampler only ((lambda, mu) = a + b g)");
+  if (family != HOMMX_SAMPLER_AFFINE && family != HOMMX_SAMPLER_RECIPROCAL) return fail(HOMMX_EINVAL, "unknown sampler family %d", family);
+  return HOMMX_OK;
+}
+
+// the kernels.h form of a separable sampler
+hommx::CoefSource sampler_source(int32_t family, int32_t n_q, const double* d_table, const double* d_weights) {
+  hommx::CoefSource src;
+  src.mode = family == HOMMX_SAMPLER_AFFINE ? hommx::COEF_AFFINE : hommx::COEF_RECIPROCAL;
+  src.nq = family == HOMMX_SAMPLER_AFFINE ? 1 : n_q;
+  src.table = d_table;
+  src.weights = d_weights;
+  return src;
 }
 
 }  // namespace
@@ -482,20 +510,12 @@ int hommx_solve_batch_separable_device(hommx_plan* p, int64_t n_cells, int32_t f
                                        const double* d_weights, const double* d_params, const double* d_M, double* d_A_eff,
                                        int32_t* d_info, void* stream) {
   if (int rc = open_call(p, n_cells); rc != GO) return rc;
-  if (p->desc.kind != HOMMX_KIND_POISSON_SCALAR && p->desc.kind != HOMMX_KIND_ELASTICITY_ISO)
-    return fail(HOMMX_EINVAL, "separable samplers are defined for the scalar Poisson and the isotropic elasticity kinds");
-  if (p->desc.kind == HOMMX_KIND_ELASTICITY_ISO && family != HOMMX_SAMPLER_AFFINE)
-    return fail(HOMMX_EINVAL, "the isotropic elasticity kind takes the affine sampler only ((lambda, mu) = a + b g)");
-  if (family != HOMMX_SAMPLER_AFFINE && family != HOMMX_SAMPLER_RECIPROCAL) return fail(HOMMX_EINVAL, "unknown sampler family %d", family);
+  if (int rc = sampler_check(p, family)) return rc;
   if (!d_table || !d_params || !d_A_eff) return fail(HOMMX_EINVAL, "null table / params / A_eff");
   if (family == HOMMX_SAMPLER_RECIPROCAL && (n_q < 1 || !d_weights)) return fail(HOMMX_EINVAL, "reciprocal sampler needs n_q >= 1 and weights");
   if (n_cells > 0x7fffffffll) return fail(HOMMX_EINVAL, "n_cells too large for one launch");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hommx::CoefSource src;
-  src.mode = family == HOMMX_SAMPLER_AFFINE ? hommx::COEF_AFFINE : hommx::COEF_RECIPROCAL;
-  src.nq = family == HOMMX_SAMPLER_AFFINE ? 1 : n_q;
-  src.table = d_table;
-  src.weights = d_weights;
+  const hommx::CoefSource src = sampler_source(family, n_q, d_table, d_weights);
   if (p->family == FAM_FUSED2D) {
     HIP_TRY(hommx::launch_poisson2d_fused(d_params, d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st, src));
     return HOMMX_OK;
@@ -569,19 +589,31 @@ int64_t recon_chunk(const hommx_plan* p, int64_t n_cells, size_t extra) {
   return std::clamp<int64_t>((int64_t)((p->recon_mem_mb << 20) / per), 1, n_cells);
 }
 
+// device pointers of one chunk of a reconstruction
+struct ReconIO {
+  const double *coef, *M, *xi;
+  double *stats, *region_stats, *strain, *flux, *A_eff;
+  int32_t* info;
+};
+// the regions of a call: how many, and the label of every element on the device
+struct ReconRegions {
+  int32_t n = 0;
+  const uint8_t* label = nullptr;
+};
+
 // one chunk of at most recon_chunk() cells on the device: the correctors into the plan's scratch, then k_recon
-int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_coef, const double* d_M, const double* d_xi, double* d_stats,
-              double* d_strain, double* d_flux, double* d_A_eff, int32_t* d_info, hipStream_t st) {
+int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const ReconIO& io, ReconRegions rg, hipStream_t st) {
   const int t = p->ks.t;
   const long long nd = plan_ndof(p);
   const bool lds = recon_in_lds(p);
   if (int rc = grow(p->rcorr, sizeof(double) * chunk * nd * (t + (lds ? 0 : 1)))) return rc;
+  double* d_A_eff = io.A_eff;
   if (!d_A_eff) {
     if (int rc = grow(p->rA, sizeof(double) * chunk * t * t)) return rc;
     d_A_eff = static_cast<double*>(p->rA.p);
   }
   double* corr = static_cast<double*>(p->rcorr.p);
-  if (int rc = route_solve(p, nc, d_coef, d_M, d_A_eff, d_info, st, corr)) return rc;
+  if (int rc = route_solve(p, nc, io.coef, io.M, d_A_eff, io.info, st, corr)) return rc;
   hommx::ReconArgs a;
   a.ndof = nd;
   a.n_el = p->n_el;
@@ -595,24 +627,203 @@ int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_coef, co
     a.vol = p->geo.vol;
   }
   a.corr = corr;
-  a.coef = d_coef;
-  a.M = d_M;
-  a.xi = d_xi;
-  a.stats = d_stats;
-  a.strain = d_strain;
-  a.flux = d_flux;
+  a.coef = io.coef;
+  a.M = io.M;
+  a.xi = io.xi;
+  a.stats = io.stats;
+  a.strain = io.strain;
+  a.flux = io.flux;
   a.slot = lds ? nullptr : corr + chunk * t * nd;
+  a.n_regions = rg.n;
+  a.region = rg.label;
+  a.region_stats = io.region_stats;
   HIP_TRY(hommx::launch_reconstruct(a, p->desc.dim, p->desc.kind, p->desc.n_micro == 0, nc, st));
   return HOMMX_OK;
 }
 
-// the shared argument checks of both reconstruct entry points
+// the shared argument checks of the reconstruct entry points
 int recon_open(hommx_plan* p, int64_t n_cells, const void* coef, const void* xi, const void* stats, const void* strain, const void* flux,
                bool device) {
   if (int rc = open_call(p, n_cells, coef && xi && stats, "coef / xi / stats", device); rc != GO) return rc;
   if (!strain != !flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
   if (int rc = corrector_workspace(p)) return rc;  // a reconstruction needs a route that forms correctors
   return GO;
+}
+
+// what hommx_reconstruct_source[_device] checks of its source and regions: no device needed, nothing but p->desc read
+int source_check(const hommx_plan* p, const hommx_coef_source* s, int32_t n_regions, const void* region, const void* region_stats) {
+  if (!s) return fail(HOMMX_EINVAL, "null source");
+  switch (s->form) {
+    case HOMMX_COEF_SAMPLED:
+      if (!s->coef) return fail(HOMMX_EINVAL, "null coef");
+      break;
+    case HOMMX_COEF_TWO_PHASE:
+      if (!s->mask || !s->values) return fail(HOMMX_EINVAL, "null mask / values");
+      break;
+    case HOMMX_COEF_SEPARABLE:
+      if (int rc = sampler_check(p, s->family)) return rc;
+      if (!s->table || !s->params) return fail(HOMMX_EINVAL, "null table / params");
+      if (s->family == HOMMX_SAMPLER_RECIPROCAL && (s->n_q < 1 || !s->weights))
+        return fail(HOMMX_EINVAL, "reciprocal sampler needs n_q >= 1 and weights");
+      break;
+    default: return fail(HOMMX_EINVAL, "unknown coefficient form %d", s->form);
+  }
+  if (n_regions < 0 || n_regions > HOMMX_RECON_MAX_REGIONS)
+    return fail(HOMMX_EINVAL, "n_regions must be 0 .. %d, got %d", HOMMX_RECON_MAX_REGIONS, n_regions);
+  const bool mask_labels = s->form == HOMMX_COEF_TWO_PHASE && n_regions == 2 && !region;
+  if (n_regions == 0 ? (region || region_stats) : (!region_stats || (!region && !mask_labels)))
+    return fail(HOMMX_EINVAL, "region and region_stats: both with n_regions > 0 (n_regions == 2 of a two-phase source: the mask may be "
+                              "the labels), neither with n_regions == 0");
+  return HOMMX_OK;
+}
+
+// the source with the pointers of its form alone (the others are not the caller's to set)
+hommx_coef_source source_of_form(const hommx_coef_source& s) {
+  hommx_coef_source o{};
+  o.form = s.form;
+  if (s.form == HOMMX_COEF_SAMPLED) o.coef = s.coef;
+  if (s.form == HOMMX_COEF_TWO_PHASE) o.mask = s.mask, o.values = s.values;
+  if (s.form == HOMMX_COEF_SEPARABLE) {
+    o.family = s.family;
+    o.n_q = s.family == HOMMX_SAMPLER_AFFINE ? 1 : s.n_q;
+    o.table = s.table;
+    o.weights = s.family == HOMMX_SAMPLER_AFFINE ? nullptr : s.weights;
+    o.params = s.params;
+  }
+  return o;
+}
+hommx_coef_source sampled_source(const double* coef) {
+  hommx_coef_source s{};
+  s.form = HOMMX_COEF_SAMPLED;
+  s.coef = coef;
+  return s;
+}
+
+// cells per chunk of a source: recon_chunk() and, for a sampler form, the 1 GiB of expanded element stream (allocated here) of expand_and_solve
+int source_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t n_cells, size_t extra, int64_t* chunk) {
+  *chunk = recon_chunk(p, n_cells, extra);
+  if (s.form == HOMMX_COEF_SAMPLED) return HOMMX_OK;
+  const int64_t per = p->n_el * p->ks.n_comp;
+  *chunk = std::min(*chunk, std::max<int64_t>((1ll << 27) / std::max<int64_t>(per, 1), 1));
+  return grow(p->expand, sizeof(double) * *chunk * per);
+}
+
+// The chunk loop of the four reconstruct entry points.  `s` holds device pointers (a sampled stream may still be on the host).  Per chunk
+// of cells [c0, c0 + nc): in(c0, nc, io) fills io, bringing in what a host entry stages per chunk; a sampler form is expanded into the
+// plan's element stream by the kernels of expand_and_solve; recon_run; out(c0, nc, io) takes the outputs away (host entries).
+template <typename In, typename Out>
+int recon_chunks(hommx_plan* p, int64_t n_cells, int64_t chunk, const hommx_coef_source& s, ReconRegions rg, hipStream_t st, In in, Out out) {
+  const int n_comp = p->ks.n_comp;
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    const int64_t nc = std::min(chunk, n_cells - c0);
+    ReconIO io{};
+    if (int rc = in(c0, nc, io)) return rc;
+    if (s.form != HOMMX_COEF_SAMPLED) {
+      double* dst = static_cast<double*>(p->expand.p);
+      if (s.form == HOMMX_COEF_TWO_PHASE)
+        HIP_TRY(hommx::launch_expand_two_phase(s.mask, s.values + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st));
+      else
+        HIP_TRY(hommx::launch_expand_separable(sampler_source(s.family, s.n_q, s.table, s.weights), s.params + c0 * 2 * n_comp, dst, p->n_el,
+                                               n_comp, nc, st));
+      io.coef = dst;
+    }
+    if (int rc = recon_run(p, nc, chunk, io, rg, st)) return rc;
+    if (int rc = out(c0, nc, io)) return rc;
+  }
+  return HOMMX_OK;
+}
+
+// everything on the device already: the chunks are views of the caller's arrays
+int recon_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, const double* d_xi, ReconRegions rg,
+                 double* d_stats, double* d_region_stats, double* d_strain, double* d_flux, double* d_A_eff, int32_t* d_info, hipStream_t st) {
+  const int d = p->desc.dim, t = p->ks.t, ns = HOMMX_RECON_NSTATS(t), nr = rg.n * HOMMX_RECON_NREGION(t);
+  const int64_t per = p->n_el * p->ks.n_comp;
+  int64_t chunk = 0;
+  if (int rc = source_chunk(p, s, n_cells, 0, &chunk)) return rc;
+  return recon_chunks(
+      p, n_cells, chunk, s, rg, st,
+      [&](int64_t c0, int64_t, ReconIO& io) {
+        const int64_t fo = c0 * p->n_el * t;
+        io = ReconIO{s.coef ? s.coef + c0 * per : nullptr,
+                     d_M ? d_M + c0 * d * d : nullptr,
+                     d_xi + c0 * t,
+                     d_stats + c0 * ns,
+                     d_region_stats ? d_region_stats + c0 * nr : nullptr,
+                     d_strain ? d_strain + fo : nullptr,
+                     d_flux ? d_flux + fo : nullptr,
+                     d_A_eff ? d_A_eff + c0 * t * t : nullptr,
+                     d_info ? d_info + c0 : nullptr};
+        return HOMMX_OK;
+      },
+      [](int64_t, int64_t, const ReconIO&) { return HOMMX_OK; });
+}
+
+// host pointers.  What every cell shares (mask, table, weights, labels) and the per-cell values of a sampler form travel once, in the
+// plan's pinned block (as staged_call); a sampled stream, M and xi stream in and every output streams out chunk by chunk, so device
+// memory is bounded by the chunk
+int recon_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const double* xi, int32_t n_regions,
+               const uint8_t* region, double* stats, double* region_stats, double* strain, double* flux, double* A_eff, int32_t* info) {
+  const int d = p->desc.dim, t = p->ks.t, ns = HOMMX_RECON_NSTATS(t), nr = n_regions * HOMMX_RECON_NREGION(t);
+  const bool sampled = s.form == HOMMX_COEF_SAMPLED;
+  const int64_t per = p->n_el * p->ks.n_comp, nfield = strain ? 2 * p->n_el * t : 0;
+  const size_t nval = sizeof(double) * n_cells * 2 * p->ks.n_comp;
+  const HostIn shared[] = {{s.mask, (size_t)p->n_el},  {s.values, nval}, {s.table, sizeof(double) * p->n_el * s.n_q},
+                           {s.weights, sizeof(double) * s.n_q}, {s.params, nval}, {region, (size_t)p->n_el}};
+  const void* dv[6];
+  if (int rc = stage_in(p, shared, dv)) return rc;
+  hommx_coef_source ds = s;
+  ds.mask = static_cast<const uint8_t*>(dv[0]);
+  ds.values = static_cast<const double*>(dv[1]);
+  ds.table = static_cast<const double*>(dv[2]);
+  ds.weights = static_cast<const double*>(dv[3]);
+  ds.params = static_cast<const double*>(dv[4]);
+  const ReconRegions rg{n_regions, n_regions ? (region ? static_cast<const uint8_t*>(dv[5]) : ds.mask) : nullptr};
+  // per cell, 256-byte aligned blocks: in = [coef | M | xi], out = [stats | A_eff | info | strain | flux | region_stats]
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t in_cell = sizeof(double) * ((sampled ? per : 0) + (M ? d * d : 0) + t);
+  const size_t out_cell = sizeof(double) * (ns + nr + t * t + nfield) + sizeof(int32_t);
+  int64_t chunk = 0;
+  if (int rc = source_chunk(p, s, n_cells, in_cell + out_cell, &chunk)) return rc;
+  const size_t o_M = up(sizeof(double) * chunk * (sampled ? per : 0)), o_xi = o_M + (M ? up(sizeof(double) * chunk * d * d) : 0);
+  const size_t o_A = up(sizeof(double) * chunk * ns), o_info = o_A + up(sizeof(double) * chunk * t * t);
+  const size_t o_strain = o_info + up(sizeof(int32_t) * chunk), o_flux = o_strain + up(sizeof(double) * chunk * p->n_el * t * (strain ? 1 : 0));
+  const size_t o_reg = o_flux + up(sizeof(double) * chunk * p->n_el * t * (strain ? 1 : 0));
+  if (int rc = grow(p->rin, o_xi + sizeof(double) * chunk * t)) return rc;
+  if (int rc = grow(p->rout, o_reg + sizeof(double) * chunk * nr)) return rc;
+  char* din = static_cast<char*>(p->rin.p);
+  char* dout = static_cast<char*>(p->rout.p);
+  double* d_coef = sampled ? reinterpret_cast<double*>(din) : nullptr;
+  double* d_M = M ? reinterpret_cast<double*>(din + o_M) : nullptr;
+  double* d_xi = reinterpret_cast<double*>(din + o_xi);
+  const ReconIO dev{d_coef,
+                    d_M,
+                    d_xi,
+                    reinterpret_cast<double*>(dout),
+                    n_regions ? reinterpret_cast<double*>(dout + o_reg) : nullptr,
+                    strain ? reinterpret_cast<double*>(dout + o_strain) : nullptr,
+                    strain ? reinterpret_cast<double*>(dout + o_flux) : nullptr,
+                    reinterpret_cast<double*>(dout + o_A),
+                    reinterpret_cast<int32_t*>(dout + o_info)};
+  return recon_chunks(
+      p, n_cells, chunk, ds, rg, nullptr,
+      [&](int64_t c0, int64_t nc, ReconIO& io) {
+        if (sampled) HIP_TRY(hipMemcpy(d_coef, s.coef + c0 * per, sizeof(double) * nc * per, hipMemcpyHostToDevice));
+        if (M) HIP_TRY(hipMemcpy(d_M, M + c0 * d * d, sizeof(double) * nc * d * d, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_xi, xi + c0 * t, sizeof(double) * nc * t, hipMemcpyHostToDevice));
+        io = dev;
+        return HOMMX_OK;
+      },
+      [&](int64_t c0, int64_t nc, const ReconIO& io) {
+        HIP_TRY(hipMemcpy(stats + c0 * ns, io.stats, sizeof(double) * nc * ns, hipMemcpyDeviceToHost));
+        if (A_eff) HIP_TRY(hipMemcpy(A_eff + c0 * t * t, io.A_eff, sizeof(double) * nc * t * t, hipMemcpyDeviceToHost));
+        if (info) HIP_TRY(hipMemcpy(info + c0, io.info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
+        if (strain) {
+          HIP_TRY(hipMemcpy(strain + c0 * p->n_el * t, io.strain, sizeof(double) * nc * p->n_el * t, hipMemcpyDeviceToHost));
+          HIP_TRY(hipMemcpy(flux + c0 * p->n_el * t, io.flux, sizeof(double) * nc * p->n_el * t, hipMemcpyDeviceToHost));
+        }
+        if (n_regions) HIP_TRY(hipMemcpy(region_stats + c0 * nr, io.region_stats, sizeof(double) * nc * nr, hipMemcpyDeviceToHost));
+        return HOMMX_OK;
+      });
 }
 
 }  // namespace
@@ -622,60 +833,35 @@ extern "C" {
 int hommx_reconstruct_batch_device(hommx_plan* p, int64_t n_cells, const double* d_coef, const double* d_M, const double* d_xi, double* d_stats,
                                    double* d_strain, double* d_flux, double* d_A_eff, int32_t* d_info, void* stream) {
   if (int rc = recon_open(p, n_cells, d_coef, d_xi, d_stats, d_strain, d_flux, true); rc != GO) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int d = p->desc.dim, t = p->ks.t, ns = HOMMX_RECON_NSTATS(t);
-  const int64_t per = p->n_el * p->ks.n_comp, chunk = recon_chunk(p, n_cells, 0);
-  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
-    const int64_t nc = std::min(chunk, n_cells - c0);
-    const int64_t fo = c0 * p->n_el * t;
-    int rc = recon_run(p, nc, chunk, d_coef + c0 * per, d_M ? d_M + c0 * d * d : nullptr, d_xi + c0 * t, d_stats + c0 * ns,
-                       d_strain ? d_strain + fo : nullptr, d_flux ? d_flux + fo : nullptr, d_A_eff ? d_A_eff + c0 * t * t : nullptr,
-                       d_info ? d_info + c0 : nullptr, st);
-    if (rc != HOMMX_OK) return rc;
-  }
-  return HOMMX_OK;
+  return recon_device(p, n_cells, sampled_source(d_coef), d_M, d_xi, ReconRegions{}, d_stats, nullptr, d_strain, d_flux, d_A_eff, d_info,
+                      reinterpret_cast<hipStream_t>(stream));
 }
 
 int hommx_reconstruct_batch(hommx_plan* p, int64_t n_cells, const double* coef, const double* M, const double* xi, double* stats, double* strain,
                             double* flux, double* A_eff, int32_t* info) {
   if (int rc = recon_open(p, n_cells, coef, xi, stats, strain, flux, false); rc != GO) return rc;
-  const int d = p->desc.dim, t = p->ks.t, ns = HOMMX_RECON_NSTATS(t);
-  const int64_t per = p->n_el * p->ks.n_comp, nfield = strain ? 2 * p->n_el * t : 0;
-  // per cell, 256-byte aligned blocks: in = [coef | M | xi], out = [stats | A_eff | info | strain | flux]
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t in_cell = sizeof(double) * (per + (M ? d * d : 0) + t), out_cell = sizeof(double) * (ns + t * t + nfield) + sizeof(int32_t);
-  const int64_t chunk = recon_chunk(p, n_cells, in_cell + out_cell);
-  const size_t o_M = up(sizeof(double) * chunk * per), o_xi = o_M + (M ? up(sizeof(double) * chunk * d * d) : 0);
-  const size_t o_A = up(sizeof(double) * chunk * ns), o_info = o_A + up(sizeof(double) * chunk * t * t);
-  const size_t o_strain = o_info + up(sizeof(int32_t) * chunk), o_flux = o_strain + up(sizeof(double) * chunk * p->n_el * t * (strain ? 1 : 0));
-  if (int rc = grow(p->rin, o_xi + sizeof(double) * chunk * t)) return rc;
-  if (int rc = grow(p->rout, o_flux + sizeof(double) * chunk * p->n_el * t * (strain ? 1 : 0))) return rc;
-  char* din = static_cast<char*>(p->rin.p);
-  char* dout = static_cast<char*>(p->rout.p);
-  double* d_coef = reinterpret_cast<double*>(din);
-  double* d_M = M ? reinterpret_cast<double*>(din + o_M) : nullptr;
-  double* d_xi = reinterpret_cast<double*>(din + o_xi);
-  double* d_stats = reinterpret_cast<double*>(dout);
-  double* d_A = reinterpret_cast<double*>(dout + o_A);
-  int32_t* d_info = reinterpret_cast<int32_t*>(dout + o_info);
-  double* d_strain = strain ? reinterpret_cast<double*>(dout + o_strain) : nullptr;
-  double* d_flux = strain ? reinterpret_cast<double*>(dout + o_flux) : nullptr;
-  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
-    const int64_t nc = std::min(chunk, n_cells - c0);
-    HIP_TRY(hipMemcpy(d_coef, coef + c0 * per, sizeof(double) * nc * per, hipMemcpyHostToDevice));
-    if (M) HIP_TRY(hipMemcpy(d_M, M + c0 * d * d, sizeof(double) * nc * d * d, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_xi, xi + c0 * t, sizeof(double) * nc * t, hipMemcpyHostToDevice));
-    int rc = recon_run(p, nc, chunk, d_coef, d_M, d_xi, d_stats, d_strain, d_flux, d_A, d_info, nullptr);
-    if (rc != HOMMX_OK) return rc;
-    HIP_TRY(hipMemcpy(stats + c0 * ns, d_stats, sizeof(double) * nc * ns, hipMemcpyDeviceToHost));
-    if (A_eff) HIP_TRY(hipMemcpy(A_eff + c0 * t * t, d_A, sizeof(double) * nc * t * t, hipMemcpyDeviceToHost));
-    if (info) HIP_TRY(hipMemcpy(info + c0, d_info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
-    if (strain) {
-      HIP_TRY(hipMemcpy(strain + c0 * p->n_el * t, d_strain, sizeof(double) * nc * p->n_el * t, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(flux + c0 * p->n_el * t, d_flux, sizeof(double) * nc * p->n_el * t, hipMemcpyDeviceToHost));
-    }
-  }
-  return HOMMX_OK;
+  return recon_host(p, n_cells, sampled_source(coef), M, xi, 0, nullptr, stats, nullptr, strain, flux, A_eff, info);
+}
+
+int hommx_reconstruct_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const double* d_xi,
+                                    int32_t n_regions, const uint8_t* d_region, double* d_stats, double* d_region_stats, double* d_strain,
+                                    double* d_flux, double* d_A_eff, int32_t* d_info, void* stream) {
+  // the source and the regions are checked before the plan's device is made current (an empty batch and a null plan are recon_open's)
+  if (p && n_cells > 0)
+    if (int rc = source_check(p, src, n_regions, d_region, d_region_stats)) return rc;
+  if (int rc = recon_open(p, n_cells, src, d_xi, d_stats, d_strain, d_flux, true); rc != GO) return rc;
+  const hommx_coef_source s = source_of_form(*src);
+  return recon_device(p, n_cells, s, d_M, d_xi, ReconRegions{n_regions, n_regions ? (d_region ? d_region : s.mask) : nullptr}, d_stats,
+                      d_region_stats, d_strain, d_flux, d_A_eff, d_info, reinterpret_cast<hipStream_t>(stream));
+}
+
+int hommx_reconstruct_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const double* xi, int32_t n_regions,
+                             const uint8_t* region, double* stats, double* region_stats, double* strain, double* flux, double* A_eff,
+                             int32_t* info) {
+  if (p && n_cells > 0)
+    if (int rc = source_check(p, src, n_regions, region, region_stats)) return rc;
+  if (int rc = recon_open(p, n_cells, src, xi, stats, strain, flux, false); rc != GO) return rc;
+  return recon_host(p, n_cells, source_of_form(*src), M, xi, n_regions, region, stats, region_stats, strain, flux, A_eff, info);
 }
 
 int hommx_calibrate_fp64(int device, double* mfma_flops_per_s, double* fma_flops_per_s) {

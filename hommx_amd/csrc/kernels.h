@@ -94,6 +94,10 @@ struct ReconArgs {
   double* strain = nullptr;          // [nc][n_el][t] or null (then flux is null as well: no fields)
   double* flux = nullptr;
   double* slot = nullptr;            // [nc][ndof] scratch for chi^xi of cells too large for LDS (null: LDS)
+  // per-region statistics (hommx_reconstruct_source): n_regions > 0 selects the REGIONS instantiations
+  int n_regions = 0;
+  const uint8_t* region = nullptr;   // [n_el] label of every element; >= n_regions: in no region
+  double* region_stats = nullptr;    // [nc][n_regions][2t+4] = [volume | the 2t+3 statistics over the region]
 };
 // bytes of chi^xi above which a cell takes a scratch slot instead of LDS
 size_t recon_lds_limit();

@@ -28,7 +28,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import fem
-from .batch import CoefStream, MicroCellPlan, Reconstruction
+from .batch import REGION_FIELDS, CoefStream, MicroCellPlan, Reconstruction, region_labels
 from .mesh import Mesh, micro_cells_per_side
 
 _VOIGT = {2: [(0, 0), (1, 1), (0, 1)], 3: [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]}
@@ -562,7 +562,8 @@ class BaseHMM(ABC):
         What stands in ``self._plan`` is a ``MicroCellPlan`` or a stand-in for it (the CPU tests answer from a NumPy restatement).  A stand-in has
         ``t``, ``kind`` and ``solve(coef, M=None, return_info=False[, return_correctors])``; it may have ``reserve`` (needed by
         ``prepare()``), ``reconstruct``, ``device``, ``solve_two_phase`` and ``solve_separable``.  Without the last two it gets those
-        coefficients as element means: this is the one place that asks."""
+        coefficients as element means: this is the one place that asks.  ``reconstruct(coef, xi, M, fields=...)`` is given element means
+        as an array and a device-sampled coefficient as the ``CoefStream``, under the same rule."""
         form, kind = self._device_form(), self._micro_kind()
         if form is None or not hasattr(self._ensure_plan(kind), form):
             coef, kind = self._element_means(cells)
@@ -710,15 +711,35 @@ class BaseHMM(ABC):
             return np.einsum("ca,cai->ci", uT, G)
         return np.einsum("cb,cbm->cm", uT, Wv)
 
-    def reconstruct(self, u=None, cells=None, fields: bool = False, chunk_cells: int | None = None) -> Reconstruction:
+    def _region_labels(self, regions) -> tuple[np.ndarray, int] | None:
+        """``regions`` of ``reconstruct`` as (labels[n_el] uint8, number of regions): ``True`` is the indicator of a ``TwoPhase``
+        coefficient (region 0 outside, region 1 inside), a callable y[dim, n_el] -> int[n_el] is evaluated at the micro element midpoints
+        -- both exactly where ``_coef_stream`` evaluates the indicator --, anything else is the labels themselves."""
+        if regions is None:
+            return None
+        mid = self._cell_mesh.cell_midpoints()[:, : self._tdim].T
+        if regions is True:
+            if not isinstance(self._coeff, TwoPhase):
+                raise ValueError("regions=True uses the indicator of a TwoPhase coefficient; pass labels or a callable for any other coefficient")
+            return region_labels(np.asarray(self._coeff.indicator(mid), dtype=bool), mid.shape[1], 2)
+        return region_labels(regions(mid) if callable(regions) else regions, mid.shape[1])
+
+    def reconstruct(self, u=None, cells=None, fields: bool = False, chunk_cells: int | None = None, regions=None) -> Reconstruction:
         """HMM reconstruction of the micro fields in the sampling boxes of ``cells`` (default: every macro cell) from the macro solution
         ``u`` (a macro ``fem.Function`` or its dof array; default: the last ``solve()`` result): R = u_H + corrector of xi_T, with xi_T the
-        macro gradient / strain of u on the cell (hommx_reconstruct_batch).  Returns a ``Reconstruction`` with ``cells``:
+        macro gradient / strain of u on the cell (hommx_reconstruct_source).  Returns a ``Reconstruction`` with ``cells``:
         per-cell mean strain / flux, energy (sum over the cells of vol(T) energy_T is the macro energy u . K_H u), the largest flux and
         where it is reached, and with ``fields`` the per-element strain and flux [N, n_el, t].
 
-        The cells are sampled, uploaded and reconstructed in chunks of ``chunk_cells`` (default: about 256 MB of coefficient stream).
-        Under a process group this runs on the calling rank alone, for the cells it is given: there is no collective."""
+        The coefficient crosses the boundary as ``solve()`` sends it (``_coef_stream``): ``TwoPhase`` and ``Separable`` as a few numbers per
+        cell, sampled on the device; anything else as element means.  ``regions``: per-region statistics (the ``region_*`` fields: mean
+        strain and flux, energy, largest flux of, say, the fibre and the matrix) -- ``True`` (the two phases of a ``TwoPhase``
+        coefficient: region 0 outside, 1 inside), integer labels [n_el] of the micro elements, or a callable y -> label evaluated at the
+        micro element midpoints; labels from 8 up are in no region.
+
+        The cells are reconstructed in chunks of ``chunk_cells`` (default: about 256 MB of coefficient stream when it is sampled on the
+        host, of outputs when it is sampled on the device).  Under a process group this runs on the calling rank alone, for the cells it
+        is given: there is no collective."""
         if u is None:
             if not self._solved:
                 raise RuntimeError("reconstruct() needs a macro solution: call solve() first or pass u")
@@ -730,18 +751,26 @@ class BaseHMM(ABC):
         if len(cells) == 0:
             raise ValueError("reconstruct() needs at least one macro cell")
         xi = self._macro_strains(cells, x)
+        labels = self._region_labels(regions)
+        kw = {} if labels is None else {"regions": labels[0], "n_regions": labels[1]}
         if chunk_cells is None:
-            per = self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) * 8
+            n_el, t = self._cell_mesh.num_cells, self._tensor_size()
+            form = self._device_form()
+            if form is not None and hasattr(self._ensure_plan(self._micro_kind()), form):  # the rule of _coef_stream
+                per = 8 * (2 * t + 3 + t * t + (labels[1] * (2 * t + 4) if labels else 0) + (2 * n_el * t if fields else 0)) + 4
+            else:
+                per = n_el * (1 if self._kind == "poisson" else 2) * 8
             chunk_cells = (256 << 20) // per
         ch = max(1, int(chunk_cells))
         parts = []
         for b in range(0, len(cells), ch):
             sub = cells[b:b + ch]
-            coef, kind = self._element_means(sub)
-            parts.append(self._ensure_plan(kind).reconstruct(coef, xi[b:b + ch], self._stratification(sub), fields=fields))
+            stream, kind = self._coef_stream(sub)
+            coef = stream.per_cell if stream.method == "solve" else stream  # element means as the array every plan (and stand-in) takes
+            parts.append(self._ensure_plan(kind).reconstruct(coef, xi[b:b + ch], self._stratification(sub), fields=fields, **kw))
         cat = lambda name: None if getattr(parts[0], name) is None else np.concatenate([getattr(r, name) for r in parts])
         return Reconstruction(xi, cat("mean_strain"), cat("mean_flux"), cat("energy"), cat("max_flux"), cat("argmax_element"), cat("A_eff"),
-                              cat("info"), cat("strain"), cat("flux"), cells)
+                              cat("info"), cat("strain"), cat("flux"), cells, *(cat(name) for name in REGION_FIELDS))
 
     def plot_solution(self, u=None):  # hmm.py:493-511 (visualisation: out of scope)
         raise NotImplementedError("plotting is out of scope of hommx_amd; use u.x.array with any plotting tool")

@@ -221,6 +221,55 @@ int hommx_reconstruct_batch_device(hommx_plan* plan, int64_t n_cells, const doub
                                    double* d_stats, double* d_strain, double* d_flux, double* d_A_eff, int32_t* d_info, void* stream);
 
 /*
+ * Reconstruction from a coefficient in any of the three forms the solve entry points take, with optional per-region statistics.  The
+ * sampler forms send a few numbers per macro cell (hommx_solve_batch_two_phase / _separable) and are expanded into the plan's element
+ * stream on the device, chunk by chunk (the smaller of HOMMX_RECON_MEM_MB of correctors and 1 GiB of stream): the stream the host would
+ * form, bit for bit, so every output equals hommx_reconstruct_batch's on that stream.  Only the pointers of `form` are read:
+ *
+ *   HOMMX_COEF_SAMPLED     coef    [n_cells][n_el][n_comp]                     as hommx_solve_batch
+ *   HOMMX_COEF_TWO_PHASE   mask    [n_el] uint8, values [n_cells][2][n_comp]   as hommx_solve_batch_two_phase
+ *   HOMMX_COEF_SEPARABLE   family, n_q, table, weights, params [n_cells][n_comp][2]   as hommx_solve_batch_separable, with its
+ *                          restrictions on family and kind
+ *
+ * Regions: region[n_el] (uint8) labels every micro element; with n_regions = R > 0 the call also returns, per cell and region r < R,
+ *   region_stats[c][r] = [ volume | sum |K| s_K (t) | sum |K| q_K (t) | sum |K| s_K . q_K | max |q_K| | smallest K reaching it ]
+ * over the elements K with region[K] == r.  The sums are NOT divided by the volume.  An element whose label is >= R belongs to no region
+ * (this is how a caller leaves elements out; labels are not validated).  An empty region reports volume 0, sums 0, max = -1 and
+ * argmax = -1, the values the whole-cell reduction starts from.  Each region is reduced by the code and in the order of the whole-cell
+ * statistics, so the largest regional max equals stats' max bitwise when the regions cover the cell, and a region's statistics do not
+ * depend on batch position, chunking or fields either.  n_regions == 0: region and region_stats are NULL.  n_regions >
+ * HOMMX_RECON_MAX_REGIONS, or a non-zero n_regions without both pointers, is HOMMX_EINVAL -- but HOMMX_COEF_TWO_PHASE with n_regions == 2
+ * and region == NULL takes the mask as the labels (region 0: phase 0, region 1: phase 1).
+ * stats, strain, flux, A_eff, info, M, xi: as hommx_reconstruct_batch.  The host entry sends mask / table / weights / labels and the
+ * per-cell values in one pinned block owned by the plan; a sampled stream goes in, and every output comes back, chunk by chunk.
+ */
+#define HOMMX_COEF_SAMPLED 0
+#define HOMMX_COEF_TWO_PHASE 1
+#define HOMMX_COEF_SEPARABLE 2
+typedef struct hommx_coef_source {
+  int32_t form;     /* HOMMX_COEF_*                                    */
+  int32_t family;   /* HOMMX_SAMPLER_* (HOMMX_COEF_SEPARABLE)          */
+  int32_t n_q;      /* columns of table (HOMMX_SAMPLER_RECIPROCAL)     */
+  int32_t reserved;
+  const double* coef;
+  const uint8_t* mask;
+  const double* values;
+  const double* table;
+  const double* weights;
+  const double* params;
+} hommx_coef_source;
+
+#define HOMMX_RECON_MAX_REGIONS 8
+#define HOMMX_RECON_NREGION(t) (2 * (t) + 4) /* [volume | sum strain(t) | sum flux(t) | energy | max_flux | argmax_element] */
+int hommx_reconstruct_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const double* xi,
+                             int32_t n_regions, const uint8_t* region, double* stats, double* region_stats, double* strain, double* flux,
+                             double* A_eff, int32_t* info);
+/* Same with DEVICE pointers (in *src as well; the struct itself is host memory), asynchronous on `stream`. */
+int hommx_reconstruct_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const double* d_xi,
+                                    int32_t n_regions, const uint8_t* d_region, double* d_stats, double* d_region_stats, double* d_strain,
+                                    double* d_flux, double* d_A_eff, int32_t* d_info, void* stream);
+
+/*
  * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
  * periodic: the caller folds the mesh vertices into n_nodes independent (periodic) nodes -- cell_problem.py:38-300's slave -> master
  * map -- and passes, per element, the periodic node of every vertex and the UNFOLDED vertex coordinates (gradients and volumes).

@@ -5,11 +5,17 @@ elasticity, fibre element stream).
     python tools/bench_reconstruct.py [--reps 7] [--out profiles/recon_bench.json]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python tools/bench_reconstruct.py --reps 3 --no-json
     python tools/bench_reconstruct.py --merge-kernel-stats DIR/.../run_kernel_stats.csv [--out profiles/recon_bench.json]
+    python tools/bench_reconstruct.py --form two_phase [--regions] [--out profiles/recon_source_bench.json]
 
 Per case, the median wall time after one warm-up call of: hommx_solve_batch_correctors (host pointers: the only form it has; the
 correctors of the whole batch cross PCIe), hommx_reconstruct_batch_device with statistics only, and with fields.  The device entry takes
 torch tensors already resident.  --merge-kernel-stats adds the time of k_recon alone from a separate rocprofv3 run, and its algorithmic
-bytes/s: correctors and coef read once, xi / M read once, stats (and fields) written once."""
+bytes/s: correctors and coef read once, xi / M read once, stats (and fields) written once.
+
+--form two_phase: the C2 shape through hommx_reconstruct_source: PoissonHMM.reconstruct() end to end with the TwoPhase
+inclusion coefficient (the macro field is a fixed smooth function, no macro solve), the plan's host entry given the two-phase stream and
+given the sampled element stream (hommx_reconstruct_batch), every figure with its spread over the repetitions.  --regions adds the same
+legs with the two phases as regions; under rocprofv3 the k_recon<..., true> rows are the instantiations with regions."""
 
 from __future__ import annotations
 
@@ -94,6 +100,44 @@ def measure(reps):
     return out
 
 
+def spread(fn, reps):
+    """Median, minimum and maximum wall time of `reps` calls after one warm-up call."""
+    fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return {"median_s": float(np.median(ts)), "min_s": float(min(ts)), "max_s": float(max(ts))}
+
+
+def measure_source(reps, regions):
+    """C2, 8,192 cells: the host entries (they synchronise before they return) and the solver class."""
+    from hommx_amd import MicroCellPlan, hmm, mesh, workloads as W
+    from hommx_amd.batch import CoefStream
+
+    msh, mask, values = W.c2_inclusion_two_phase()
+    _, coef, _ = W.c2_inclusion()
+    p = MicroCellPlan(2, 32, "poisson")
+    xi = np.random.default_rng(0).standard_normal((coef.shape[0], 2))
+    stream = CoefStream.two_phase(mask, values)
+    tp = hmm.TwoPhase(lambda y: W.wrapped_disc(y[0], y[1]), lambda x: 0.001 * (1.0 + 9.0 * x[0]), lambda x: 0.1 + 0.0 * x[0])
+    h = hmm.PoissonHMM(msh, tp, lambda x: 1.0, mesh.create_unit_square(32, 32), 0.01)
+    x = h.function_space.tabulate_dof_coordinates()
+    u = np.sin(2.0 * x[:, 0]) * np.cos(x[:, 1])
+    legs = {"reconstruct_batch_sampled": lambda: p.reconstruct(coef, xi),
+            "reconstruct_source_two_phase": lambda: p.reconstruct(stream, xi),
+            "poisson_hmm_reconstruct": lambda: h.reconstruct(u)}
+    if regions:
+        legs["reconstruct_source_two_phase_regions"] = lambda: p.reconstruct(stream, xi, regions=True)
+        legs["poisson_hmm_reconstruct_regions"] = lambda: h.reconstruct(u, regions=True)
+    out = {"case": "C2: 8192 cells, 32^2 Poisson, TwoPhase inclusion", "cells": int(coef.shape[0]), "kernel_route": p.kernel}
+    for name, fn in legs.items():
+        out[name] = spread(fn, reps)
+        print(f"{name}: median {out[name]['median_s'] * 1e3:.1f} ms (min {out[name]['min_s'] * 1e3:.1f}, max {out[name]['max_s'] * 1e3:.1f})", flush=True)
+    return [out]
+
+
 def merge(res, stats_csv):
     rows = list(csv.DictReader(open(stats_csv)))
     for r in res:
@@ -116,8 +160,13 @@ def main():
     ap.add_argument("--out", default="profiles/recon_bench.json")
     ap.add_argument("--no-json", action="store_true")
     ap.add_argument("--merge-kernel-stats", default=None)
+    ap.add_argument("--form", choices=["sampled", "two_phase"], default="sampled")
+    ap.add_argument("--regions", action="store_true", help="with --form two_phase: the legs with the two phases as regions as well")
     a = ap.parse_args()
-    if a.merge_kernel_stats:
+    if a.form == "two_phase":
+        doc = {"tool": "tools/bench_reconstruct.py --form two_phase" + (" --regions" if a.regions else ""), "reps": a.reps,
+               "statistic": "median / min / max wall time after one warm-up call", "results": measure_source(a.reps, a.regions)}
+    elif a.merge_kernel_stats:
         doc = json.load(open(a.out))
         doc["results"] = merge(doc["results"], a.merge_kernel_stats)
         doc["kernel_stats_source"] = "rocprofv3 --kernel-trace --stats (separate run, AverageNs per instantiation)"
