@@ -42,16 +42,15 @@ int prefix_error(int code, const char* prefix) {
 }
 
 int upload_packed(void** block, std::initializer_list<HostPiece> pieces) {
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  size_t total = 0;
-  for (const HostPiece& p : pieces) total += up(p.bytes);
+  std::vector<size_t> bytes, off(pieces.size());
+  for (const HostPiece& p : pieces) bytes.push_back(p.bytes);
+  const size_t total = pack_offsets(bytes.size(), bytes.data(), off.data());
   std::vector<char> host(total, 0);
   HIP_TRY(hipMalloc(block, total));
-  size_t off = 0;
+  size_t k = 0;
   for (const HostPiece& p : pieces) {
-    if (p.bytes) memcpy(host.data() + off, p.src, p.bytes);
-    *p.dst = static_cast<const char*>(*block) + off;
-    off += up(p.bytes);
+    if (p.bytes) memcpy(host.data() + off[k], p.src, p.bytes);
+    *p.dst = static_cast<const char*>(*block) + off[k++];
   }
   HIP_TRY(hipMemcpy(*block, host.data(), total, hipMemcpyHostToDevice));
   return HOMMX_OK;
@@ -90,6 +89,24 @@ int grow(Buf& b, size_t bytes) {
   return HOMMX_OK;
 }
 
+// `b` grown to one block of pieces of bytes[k] bytes (host_common.h, pack_offsets); at[k]: where piece k starts, null for an empty piece;
+// *total: the size of the block
+template <size_t N>
+int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = nullptr) {
+  size_t off[N];
+  const size_t all = hommx::pack_offsets(N, bytes, off);
+  if (total) *total = all;
+  if (int rc = grow(b, all)) return rc;
+  for (size_t k = 0; k < N; ++k) at[k] = bytes[k] ? static_cast<char*>(b.p) + off[k] : nullptr;
+  return HOMMX_OK;
+}
+
+// The plan-owned buffers, grown on demand, never per call.  B_IN / B_OUT: the device block of the per-cell inputs / outputs of a host
+// entry point (hommx_solve_batch: the batch; recon_host: one chunk).  B_EXPAND: the expanded element stream of the sampler forms.
+// B_PIN_* / B_DEV_*: the small inputs of the sampler host entry points and their outputs, pinned host mirrors + device (plan_new pins).
+// B_RCORR, B_RA: the correctors of one reconstruction chunk (and the chi^xi slots of cells too large for LDS), A_eff the caller did not ask for
+enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, N_BUF };
+
 }  // namespace
 
 struct hommx_plan {
@@ -99,16 +116,12 @@ struct hommx_plan {
   hommx::KindSizes ks;
   hommx::BlockedWorkspace* ws = nullptr;  // FAM_BLOCKED, and a FAM_FUSED2D plan once it has served correctors
   hommx::MeshPlan* mesh = nullptr;        // FAM_MESH: symbolic phase + device tables of the unstructured micro mesh
-  // plan-owned staging, grown on demand, never per call: the plain host entry point's buffers, the expanded element stream of the sampler
-  // entry points, and the packed blocks of the sampler host entry points (pinned host mirrors + device)
-  Buf coef, M, out, info, expand, dev_in, dev_out, pin_in{nullptr, 0, true}, pin_out{nullptr, 0, true};
+  Buf buf[N_BUF];
   // host-pointer entry point: coefficient chunks stream in on s_copy while s_comp solves the previous one
   hipStream_t s_copy = nullptr, s_comp = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
-  // reconstruction (hommx_reconstruct_batch): HOMMX_RECON_MEM_MB, read when the plan is created; the correctors of one chunk (and the chi^xi
-  // slots of cells too large for LDS), A_eff the caller did not ask for, the host entry's staging
+  // reconstruction (hommx_reconstruct_batch): HOMMX_RECON_MEM_MB, read when the plan is created
   int64_t recon_mem_mb = 1024;
-  Buf rcorr, rA, rin, rout;
   // mesh plans: the element table, P1 gradients and volumes on the device, uploaded when the plan is created -- the one copy the route's
   // kernels (MeshDev / MeshAsm) and the reconstruction read
   hommx::MeshGeomDev geo{};
@@ -116,24 +129,47 @@ struct hommx_plan {
 
 namespace {
 
-// what opens a batch entry point, in this order: the plan, the batch size, the pointers (`names` lists them), the limit of one launch (device
-// entry points); then the plan's device is made current.  GO, or what the call returns: an error, HOMMX_OK for an empty batch
+// what opens a batch entry point, in this order: the plan, the batch size, the entry's own checks of a non-empty batch (`more`: a
+// coefficient source, regions), the pointers (`names` lists them), the limit of one launch (device entry points).  Nothing but p->desc
+// is read.  Only then is the plan's device made current.  GO, or what the call
+// returns: an error, HOMMX_OK for an empty batch
 constexpr int GO = 1;
-int open_call(const hommx_plan* p, int64_t n_cells, bool ptrs_ok = true, const char* names = "", bool one_launch = false) {
+int one_launch_check(int64_t n_cells) {
+  return n_cells > 0x7fffffffll ? fail(HOMMX_EINVAL, "n_cells too large for one launch") : HOMMX_OK;
+}
+template <typename More>
+int open_call(const hommx_plan* p, int64_t n_cells, bool ptrs_ok, const char* names, bool one_launch, More more) {
   if (!p) return fail(HOMMX_EINVAL, "null plan");
   if (n_cells < 0) return fail(HOMMX_EINVAL, "negative n_cells");
   if (n_cells == 0) return HOMMX_OK;
+  if (int rc = more()) return rc;
   if (!ptrs_ok) return fail(HOMMX_EINVAL, "null %s", names);
-  if (one_launch && n_cells > 0x7fffffffll) return fail(HOMMX_EINVAL, "n_cells too large for one launch");
+  if (one_launch)
+    if (int rc = one_launch_check(n_cells)) return rc;
   HIP_TRY(hipSetDevice(p->desc.device));
   return GO;
 }
+int open_call(const hommx_plan* p, int64_t n_cells, bool ptrs_ok = true, const char* names = "", bool one_launch = false) {
+  return open_call(p, n_cells, ptrs_ok, names, one_launch, [] { return HOMMX_OK; });
+}
 
-// HOMMX_RECON_MEM_MB (include/hommx_hip.h): read once, when the plan is created
-int64_t recon_mem_mb_env() {
+// What both plan constructors end with: the device range, then the plan with everything its descriptor determines.
+// HOMMX_RECON_MEM_MB (include/hommx_hip.h) is read here, once
+int plan_new(hommx_plan** out, const hommx_plan_desc& desc, int64_t n_el) {
+  const int ndev = hommx_device_count();
+  if (ndev <= 0) return fail(HOMMX_ENODEV, "no HIP device visible");
+  if (desc.device < 0 || desc.device >= ndev) return fail(HOMMX_EINVAL, "device %d out of range [0,%d)", desc.device, ndev);
+  hommx_plan* p = new (std::nothrow) hommx_plan();
+  if (!p) return fail(HOMMX_ENOMEM, "host allocation failed");
+  p->desc = desc;
+  p->n_el = n_el;
+  p->ks = hommx::kind_sizes(desc.dim, desc.kind);
+  p->buf[B_PIN_IN].pinned = p->buf[B_PIN_OUT].pinned = true;
   const char* v = getenv("HOMMX_RECON_MEM_MB");
   const long long mb = v ? atoll(v) : 0;
-  return mb > 0 ? mb : 1024;
+  p->recon_mem_mb = mb > 0 ? mb : 1024;
+  *out = p;
+  return HOMMX_OK;
 }
 
 // a failed call into the plan's route, under the route's name
@@ -157,88 +193,178 @@ int corrector_workspace(hommx_plan* p) {
 // periodic unknowns of a cell (nodes x bs): the length of one corrector
 long long plan_ndof(const hommx_plan* p) { return (p->family == FAM_MESH ? hommx::mesh_num_nodes(p->mesh) : p->ws->G.nn) * (long long)p->ks.bs; }
 
-// the sampler device entry points on the blocked and mesh families: expand(c0, nc, dst) launches the expansion of cells [c0, c0 + nc) into
-// the plan's element stream, which is solved chunk by chunk of at most 1 GiB
-template <typename Expand>
-int expand_and_solve(hommx_plan* p, int64_t n_cells, const double* d_M, double* d_A_eff, int32_t* d_info, hipStream_t st, Expand expand) {
+// -- coefficient sources: inside this file a coefficient is a normalised hommx_coef_source (the pointers of its form alone) ----------------
+hommx_coef_source sampled_source(const double* coef) {
+  hommx_coef_source s{};
+  s.form = HOMMX_COEF_SAMPLED;
+  s.coef = coef;
+  return s;
+}
+hommx_coef_source two_phase_source(const uint8_t* mask, const double* values) {
+  hommx_coef_source s{};
+  s.form = HOMMX_COEF_TWO_PHASE;
+  s.mask = mask;
+  s.values = values;
+  return s;
+}
+hommx_coef_source separable_source(int32_t family, int32_t n_q, const double* table, const double* weights, const double* params) {
+  hommx_coef_source s{};
+  s.form = HOMMX_COEF_SEPARABLE;
+  s.family = family;
+  s.n_q = family == HOMMX_SAMPLER_AFFINE ? 1 : n_q;
+  s.table = table;
+  s.weights = family == HOMMX_SAMPLER_AFFINE ? nullptr : weights;
+  s.params = params;
+  return s;
+}
+// a caller's source that coef_check has passed (the pointers of other forms are not the caller's to set)
+hommx_coef_source source_of_form(const hommx_coef_source& s) {
+  if (s.form == HOMMX_COEF_SAMPLED) return sampled_source(s.coef);
+  if (s.form == HOMMX_COEF_TWO_PHASE) return two_phase_source(s.mask, s.values);
+  return separable_source(s.family, s.n_q, s.table, s.weights, s.params);
+}
+
+// What every entry point checks of a coefficient source: the form, its pointers, the restrictions of a separable sampler.  `separable_ptrs`
+// names the pointers of the separable form as the entry point does, `more_ptrs`: the pointers it checks and names with them
+int coef_check(const hommx_plan* p, const hommx_coef_source* s, const char* separable_ptrs = "table / params", bool more_ptrs = true) {
+  if (!s) return fail(HOMMX_EINVAL, "null source");
+  switch (s->form) {
+    case HOMMX_COEF_SAMPLED: return s->coef ? HOMMX_OK : fail(HOMMX_EINVAL, "null coef");
+    case HOMMX_COEF_TWO_PHASE: return s->mask && s->values ? HOMMX_OK : fail(HOMMX_EINVAL, "null mask / values");
+    case HOMMX_COEF_SEPARABLE: break;
+    default: return fail(HOMMX_EINVAL, "unknown coefficient form %d", s->form);
+  }
+  if (p->desc.kind != HOMMX_KIND_POISSON_SCALAR && p->desc.kind != HOMMX_KIND_ELASTICITY_ISO)
+    return fail(HOMMX_EINVAL, "separable samplers are defined for the scalar Poisson and the isotropic elasticity kinds");
+  if (p->desc.kind == HOMMX_KIND_ELASTICITY_ISO && s->family != HOMMX_SAMPLER_AFFINE)
+    return fail(HOMMX_EINVAL, "the isotropic elasticity kind takes the affine sampler only ((lambda, mu) = a + b g)");
+  if (s->family != HOMMX_SAMPLER_AFFINE && s->family != HOMMX_SAMPLER_RECIPROCAL)
+    return fail(HOMMX_EINVAL, "unknown sampler family %d", s->family);
+  if (!s->table || !s->params || !more_ptrs) return fail(HOMMX_EINVAL, "null %s", separable_ptrs);
+  if (s->family == HOMMX_SAMPLER_RECIPROCAL && (s->n_q < 1 || !s->weights))
+    return fail(HOMMX_EINVAL, "reciprocal sampler needs n_q >= 1 and weights");
+  return HOMMX_OK;
+}
+
+// the kernels.h form of a source, and what its kernels read per cell: the stream, or the two values / (a, b) per component
+hommx::CoefSource sampler_source(const hommx_coef_source& s) {
+  hommx::CoefSource src;
+  if (s.form == HOMMX_COEF_TWO_PHASE) {
+    src.mode = hommx::COEF_TWO_PHASE;
+    src.table = s.mask;
+  } else if (s.form == HOMMX_COEF_SEPARABLE) {
+    src.mode = s.family == HOMMX_SAMPLER_AFFINE ? hommx::COEF_AFFINE : hommx::COEF_RECIPROCAL;
+    src.nq = s.n_q;
+    src.table = s.table;
+    src.weights = s.weights;
+  }
+  return src;
+}
+const double* per_cell(const hommx_coef_source& s) {
+  return s.form == HOMMX_COEF_SAMPLED ? s.coef : s.form == HOMMX_COEF_TWO_PHASE ? s.values : s.params;
+}
+
+// -- the element stream of a source ---------------------------------------------------------------------------------------------------
+// Cells per chunk of a source, given the `want` of the caller: a sampler form is expanded into the plan's element stream, at most 1 GiB of
+// it (at least one cell), which is grown here; a sampled stream has no such limit
+int stream_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t want, int64_t* chunk) {
+  *chunk = want;
+  if (s.form == HOMMX_COEF_SAMPLED) return HOMMX_OK;
   const int64_t per = p->n_el * p->ks.n_comp;
-  const int64_t chunk = std::clamp<int64_t>((1ll << 27) / std::max<int64_t>(per, 1), 1, n_cells);
-  if (int rc = grow(p->expand, sizeof(double) * chunk * per)) return rc;
-  double* dst = static_cast<double*>(p->expand.p);
+  *chunk = std::min(want, std::max<int64_t>((1ll << 27) / std::max<int64_t>(per, 1), 1));
+  return grow(p->buf[B_EXPAND], sizeof(double) * *chunk * per);
+}
+
+// *stream: the element stream of cells [c0, c0 + nc) of a source on the device.  A sampled stream is a view of the caller's; a sampler
+// form is expanded into the plan's element stream (nc <= the chunk of stream_chunk)
+int expand_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t c0, int64_t nc, hipStream_t st, const double** stream) {
+  const int n_comp = p->ks.n_comp;
+  if (s.form == HOMMX_COEF_SAMPLED) {
+    *stream = s.coef + c0 * p->n_el * n_comp;
+    return HOMMX_OK;
+  }
+  double* dst = static_cast<double*>(p->buf[B_EXPAND].p);
+  if (s.form == HOMMX_COEF_TWO_PHASE)
+    HIP_TRY(hommx::launch_expand_two_phase(s.mask, s.values + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st));
+  else
+    HIP_TRY(hommx::launch_expand_separable(sampler_source(s), s.params + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st));
+  *stream = dst;
+  return HOMMX_OK;
+}
+
+// A source on the device, solved: what the three *_device solve entry points do.  The fused 2D kernel samples every form itself.  The
+// other families read an element stream: a sampled one goes to the route in one call, a sampler form chunk by chunk of stream_chunk
+int solve_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, double* d_A_eff, int32_t* d_info,
+                        hipStream_t st) {
+  if (p->family == FAM_FUSED2D) {
+    HIP_TRY(hommx::launch_poisson2d_fused(per_cell(s), d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st, sampler_source(s)));
+    return HOMMX_OK;
+  }
+  int64_t chunk = 0;
+  if (int rc = stream_chunk(p, s, n_cells, &chunk)) return rc;
   const int d = p->desc.dim, t = p->ks.t;
   for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
     const int64_t nc = (n_cells - c0 < chunk) ? n_cells - c0 : chunk;
-    HIP_TRY(expand(c0, nc, dst));
-    int rc = route_solve(p, nc, dst, d_M ? d_M + c0 * d * d : nullptr, d_A_eff + c0 * t * t, d_info ? d_info + c0 : nullptr, st);
+    const double* stream = nullptr;
+    if (int rc = expand_chunk(p, s, c0, nc, st, &stream)) return rc;
+    int rc = route_solve(p, nc, stream, d_M ? d_M + c0 * d * d : nullptr, d_A_eff + c0 * t * t, d_info ? d_info + c0 : nullptr, st);
     if (rc != HOMMX_OK) return rc;
   }
   return HOMMX_OK;
 }
 
-// The sampler host entry points: their inputs are small, so they are packed into ONE pinned block owned by the plan and travel in one
-// asynchronous copy; the outputs come back the same way, and the call synchronises once.  No hipMalloc / hipFree per call.  in[k]: a host
-// input (a null one takes no room); run(d_in, d_A_eff, d_info) calls the device entry point with d_in[k] the device copy of in[k] (or null).
-struct HostIn {
-  const void* src;
-  size_t bytes;
-};
-// the inputs into the plan's pinned block and ONE asynchronous copy to its device twin; d_in[k]: the device copy of in[k] (null for a null input)
+// -- the sampler host entry points ------------------------------------------------------------------------------------------------------
+// Their inputs are small, so they are packed into ONE pinned block owned by the plan and travel in one asynchronous copy to its device
+// twin: no hipMalloc / hipFree per call.  A null input takes no room; *dst of a piece: its device copy (null for a null input)
 template <size_t N>
-int stage_in(hommx_plan* p, const HostIn (&in)[N], const void* (&d_in)[N]) {
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  size_t off[N], in_bytes = 0;
+int stage_in(hommx_plan* p, const hommx::HostPiece (&in)[N]) {
+  size_t bytes[N], total = 0;
+  char *pin[N], *dev[N];
+  for (size_t k = 0; k < N; ++k) bytes[k] = in[k].src ? in[k].bytes : 0;
+  if (int rc = carve(p->buf[B_PIN_IN], bytes, pin, &total)) return rc;
+  if (int rc = carve(p->buf[B_DEV_IN], bytes, dev)) return rc;
   for (size_t k = 0; k < N; ++k) {
-    off[k] = in_bytes;
-    if (in[k].src) in_bytes += up(in[k].bytes);
+    *in[k].dst = dev[k];
+    if (bytes[k]) memcpy(pin[k], in[k].src, bytes[k]);
   }
-  if (int rc = grow(p->pin_in, in_bytes)) return rc;
-  if (int rc = grow(p->dev_in, in_bytes)) return rc;
-  char* hin = static_cast<char*>(p->pin_in.p);
-  char* din = static_cast<char*>(p->dev_in.p);
-  for (size_t k = 0; k < N; ++k) {
-    d_in[k] = in[k].src ? din + off[k] : nullptr;
-    if (in[k].src) memcpy(hin + off[k], in[k].src, in[k].bytes);
-  }
-  if (in_bytes) HIP_TRY(hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, nullptr));
+  if (total) HIP_TRY(hipMemcpyAsync(p->buf[B_DEV_IN].p, p->buf[B_PIN_IN].p, total, hipMemcpyHostToDevice, nullptr));
   return HOMMX_OK;
 }
 
-template <size_t N, typename Run>
-int staged_call(hommx_plan* p, int64_t n_cells, const HostIn (&in)[N], double* A_eff, int32_t* info, Run run) {
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t a_bytes = sizeof(double) * n_cells * p->ks.t * p->ks.t, o_info = up(a_bytes), out_bytes = o_info + up(sizeof(int32_t) * n_cells);
-  if (int rc = grow(p->pin_out, out_bytes)) return rc;
-  if (int rc = grow(p->dev_out, out_bytes)) return rc;
-  char* dout = static_cast<char*>(p->dev_out.p);
-  const void* d_in[N];
-  if (int rc = stage_in(p, in, d_in)) return rc;
-  if (int rc = run(d_in, reinterpret_cast<double*>(dout), reinterpret_cast<int32_t*>(dout + o_info))) return rc;
-  HIP_TRY(hipMemcpyAsync(p->pin_out.p, dout, out_bytes, hipMemcpyDeviceToHost, nullptr));
+// The host arrays of a source staged so (what every cell shares and the per-cell values of a sampler form; a sampled stream stays where
+// it is, and ds->coef is null: the stream is no device pointer), with one more input of the entry point; *ds: the source with the
+// device copies
+int stage_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, hommx::HostPiece more, hommx_coef_source* ds) {
+  const size_t nval = sizeof(double) * n_cells * 2 * p->ks.n_comp;
+  *ds = s;
+  ds->coef = nullptr;
+  const hommx::HostPiece in[] = {{s.mask, (size_t)p->n_el, (const void**)&ds->mask},
+                                 {s.values, nval, (const void**)&ds->values},
+                                 {s.table, sizeof(double) * p->n_el * s.n_q, (const void**)&ds->table},
+                                 {s.weights, sizeof(double) * s.n_q, (const void**)&ds->weights},
+                                 {s.params, nval, (const void**)&ds->params},
+                                 more};
+  return stage_in(p, in);
+}
+
+// hommx_solve_batch_two_phase / _separable: the source and M go in staged, the outputs come back the same way, the call synchronises once
+int solve_source_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, double* A_eff, int32_t* info) {
+  const int d = p->desc.dim;
+  const size_t out_bytes[] = {sizeof(double) * n_cells * p->ks.t * p->ks.t, sizeof(int32_t) * n_cells};
+  size_t total = 0;
+  char *pin[2], *dev[2];
+  if (int rc = carve(p->buf[B_PIN_OUT], out_bytes, pin, &total)) return rc;
+  if (int rc = carve(p->buf[B_DEV_OUT], out_bytes, dev)) return rc;
+  hommx_coef_source ds;
+  const double* d_M = nullptr;
+  if (int rc = stage_source(p, n_cells, s, {M, sizeof(double) * n_cells * d * d, (const void**)&d_M}, &ds)) return rc;
+  if (int rc = one_launch_check(n_cells)) return rc;  // what the device entry point this call stands for would say here
+  if (int rc = solve_source_device(p, n_cells, ds, d_M, reinterpret_cast<double*>(dev[0]), reinterpret_cast<int32_t*>(dev[1]), nullptr)) return rc;
+  HIP_TRY(hipMemcpyAsync(pin[0], dev[0], total, hipMemcpyDeviceToHost, nullptr));
   HIP_TRY(hipStreamSynchronize(nullptr));
-  const char* hout = static_cast<const char*>(p->pin_out.p);
-  memcpy(A_eff, hout, a_bytes);
-  if (info) memcpy(info, hout + o_info, sizeof(int32_t) * n_cells);
+  memcpy(A_eff, pin[0], out_bytes[0]);
+  if (info) memcpy(info, pin[1], out_bytes[1]);
   return HOMMX_OK;
-}
-
-// kind and family of a separable sampler (hommx_solve_batch_separable, hommx_reconstruct_source): no device needed
-int sampler_check(const hommx_plan* p, int32_t family) {
-  if (p->desc.kind != HOMMX_KIND_POISSON_SCALAR && p->desc.kind != HOMMX_KIND_ELASTICITY_ISO)
-    return fail(HOMMX_EINVAL, "separable samplers are defined for the scalar Poisson and the isotropic elasticity kinds");
-  if (p->desc.kind == HOMMX_KIND_ELASTICITY_ISO && family != HOMMX_SAMPLER_AFFINE)
-    return fail(HOMMX_EINVAL, "the isotropic elasticity kind takes the affine sampler only ((lambda, mu) = a + b g)");
-  if (family != HOMMX_SAMPLER_AFFINE && family != HOMMX_SAMPLER_RECIPROCAL) return fail(HOMMX_EINVAL, "unknown sampler family %d", family);
-  return HOMMX_OK;
-}
-
-// the kernels.h form of a separable sampler
-hommx::CoefSource sampler_source(int32_t family, int32_t n_q, const double* d_table, const double* d_weights) {
-  hommx::CoefSource src;
-  src.mode = family == HOMMX_SAMPLER_AFFINE ? hommx::COEF_AFFINE : hommx::COEF_RECIPROCAL;
-  src.nq = family == HOMMX_SAMPLER_AFFINE ? 1 : n_q;
-  src.table = d_table;
-  src.weights = d_weights;
-  return src;
 }
 
 }  // namespace
@@ -259,17 +385,9 @@ int hommx_plan_create(hommx_plan** out, const hommx_plan_desc* d) {
   if (d->dim != 2 && d->dim != 3) return fail(HOMMX_EINVAL, "dim must be 2 or 3 (hmm.py:104-105), got %d", d->dim);
   if (d->kind < 0 || d->kind > 3) return fail(HOMMX_EINVAL, "unknown kind %d", d->kind);
   if (d->n_micro < 3) return fail(HOMMX_EINVAL, "n_micro must be >= 3 (got %d): with fewer cells per side periodic neighbours coincide", d->n_micro);
-  int ndev = hommx_device_count();
-  if (ndev <= 0) return fail(HOMMX_ENODEV, "no HIP device visible");
-  if (d->device < 0 || d->device >= ndev) return fail(HOMMX_EINVAL, "device %d out of range [0,%d)", d->device, ndev);
-
-  hommx_plan* p = new (std::nothrow) hommx_plan();
-  if (!p) return fail(HOMMX_ENOMEM, "host allocation failed");
-  p->desc = *d;
-  p->recon_mem_mb = recon_mem_mb_env();
   const int dim = d->dim, n = d->n_micro;
-  p->n_el = (dim == 2) ? 2ll * n * n : 6ll * n * n * n;
-  p->ks = hommx::kind_sizes(dim, d->kind);
+  hommx_plan* p = nullptr;
+  if (int rc = plan_new(&p, *d, (dim == 2) ? 2ll * n * n : 6ll * n * n * n)) return rc;
   const bool fused = dim == 2 && d->kind == HOMMX_KIND_POISSON_SCALAR && n <= 32 && !(d->flags & HOMMX_FLAG_FORCE_BLOCKED);
   p->family = fused ? FAM_FUSED2D : FAM_BLOCKED;
   if (p->family == FAM_BLOCKED) {
@@ -288,9 +406,7 @@ int hommx_plan_destroy(hommx_plan* p) {
   hipSetDevice(p->desc.device);
   if (p->ws) hommx::blocked_workspace_destroy(p->ws);
   if (p->mesh) hommx::mesh_destroy(p->mesh);
-  for (Buf* b : {&p->coef, &p->M, &p->out, &p->info, &p->expand, &p->dev_in, &p->dev_out, &p->pin_in, &p->pin_out, &p->rcorr, &p->rA, &p->rin,
-                 &p->rout})
-    b->release();
+  for (Buf& b : p->buf) b.release();
   if (p->geo.block) (void)hipFree(p->geo.block);
   if (p->s_copy) hipStreamDestroy(p->s_copy);
   if (p->s_comp) hipStreamDestroy(p->s_comp);
@@ -381,30 +497,19 @@ int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d) {
     if (rc && !(rc == HOMMX_EINVAL && width > HOMMX_MESH_MAX_FRONT)) return rc;
   }
   if (!m && (rc = hommx::mesh_tree_analyze(d, geo, &mt, nullptr, nullptr, nullptr)) != 0) return rc;
-  auto drop = [&]() {
+  hommx_plan_desc desc{};  // n_micro == 0: a mesh plan
+  desc.dim = d->dim;
+  desc.kind = d->kind;
+  desc.device = d->device;
+  desc.flags = d->flags;
+  hommx_plan* p = nullptr;
+  if ((rc = plan_new(&p, desc, d->n_el)) != 0) {
     hommx::mesh_destroy(m);
     hommx::mesh_tree_destroy(mt);
-  };
-  int ndev = hommx_device_count();
-  if (ndev <= 0 || d->device < 0 || d->device >= ndev) {
-    drop();
-    return ndev <= 0 ? fail(HOMMX_ENODEV, "no HIP device visible") : fail(HOMMX_EINVAL, "device %d out of range [0,%d)", d->device, ndev);
+    return rc;
   }
-  hommx_plan* p = new (std::nothrow) hommx_plan();
-  if (!p) {
-    drop();
-    return fail(HOMMX_ENOMEM, "host allocation failed");
-  }
-  p->desc.dim = d->dim;
-  p->desc.n_micro = 0;
-  p->desc.kind = d->kind;
-  p->desc.device = d->device;
-  p->desc.flags = d->flags;
   p->family = m ? FAM_MESH : FAM_BLOCKED;
   p->mesh = m;
-  p->n_el = d->n_el;
-  p->ks = hommx::kind_sizes(d->dim, d->kind);
-  p->recon_mem_mb = recon_mem_mb_env();
   rc = hipSetDevice(d->device) == hipSuccess ? HOMMX_OK : fail(HOMMX_EHIP, "hipSetDevice failed");
   if (!rc) rc = hommx::mesh_geom_upload(d, geo, &p->geo);
   if (!rc) rc = m ? hommx::mesh_upload(m, p->geo) : hommx::mesh_tree_workspace(mt, p->geo, &p->ws);
@@ -422,12 +527,7 @@ int32_t hommx_plan_front_width(const hommx_plan* p) { return p && p->family == F
 int hommx_solve_batch_device(hommx_plan* p, int64_t n_cells, const double* d_coef, const double* d_M,
                              double* d_A_eff, int32_t* d_info, void* stream) {
   if (int rc = open_call(p, n_cells, d_coef && d_A_eff, "coef / A_eff", true); rc != GO) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (p->family == FAM_FUSED2D) {
-    HIP_TRY(hommx::launch_poisson2d_fused(d_coef, d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st));
-    return HOMMX_OK;
-  }
-  return route_solve(p, n_cells, d_coef, d_M, d_A_eff, d_info, st);
+  return solve_source_device(p, n_cells, sampled_source(d_coef), d_M, d_A_eff, d_info, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hommx_solve_batch(hommx_plan* p, int64_t n_cells, const double* coef, const double* M, double* A_eff,
@@ -435,14 +535,15 @@ int hommx_solve_batch(hommx_plan* p, int64_t n_cells, const double* coef, const 
   if (int rc = open_call(p, n_cells, coef && A_eff, "coef / A_eff"); rc != GO) return rc;
   const int d = p->desc.dim, t = p->ks.t;
   const int64_t per = p->n_el * p->ks.n_comp;
-  if (int rc = grow(p->coef, sizeof(double) * n_cells * per)) return rc;
-  if (int rc = grow(p->M, sizeof(double) * n_cells * d * d)) return rc;
-  if (int rc = grow(p->out, sizeof(double) * n_cells * t * t)) return rc;
-  if (int rc = grow(p->info, sizeof(int32_t) * n_cells)) return rc;
-  double* d_coef = static_cast<double*>(p->coef.p);
-  double* d_M = M ? static_cast<double*>(p->M.p) : nullptr;
-  double* d_out = static_cast<double*>(p->out.p);
-  int32_t* d_info = static_cast<int32_t*>(p->info.p);
+  const size_t in_bytes[] = {sizeof(double) * n_cells * per, M ? sizeof(double) * n_cells * d * d : 0};
+  const size_t out_bytes[] = {sizeof(double) * n_cells * t * t, sizeof(int32_t) * n_cells};
+  char *in[2], *out[2];
+  if (int rc = carve(p->buf[B_IN], in_bytes, in)) return rc;
+  if (int rc = carve(p->buf[B_OUT], out_bytes, out)) return rc;
+  double* d_coef = reinterpret_cast<double*>(in[0]);
+  double* d_M = reinterpret_cast<double*>(in[1]);
+  double* d_out = reinterpret_cast<double*>(out[0]);
+  int32_t* d_info = reinterpret_cast<int32_t*>(out[1]);
   if (M) HIP_TRY(hipMemcpy(d_M, M, sizeof(double) * n_cells * d * d, hipMemcpyHostToDevice));
   // cells per chunk of the pipelined copy.  Fused 2D kernel: one wave per cell fills the 256 CUs x 8 wave slots exactly once; blocked
   // family: about 256 MB of coefficient stream, at least 256 cells (from there its throughput is flat: C4 / C5 393 KB per cell -> 682)
@@ -481,66 +582,30 @@ int hommx_solve_batch(hommx_plan* p, int64_t n_cells, const double* coef, const 
 int hommx_solve_batch_two_phase_device(hommx_plan* p, int64_t n_cells, const uint8_t* d_mask, const double* d_values,
                                        const double* d_M, double* d_A_eff, int32_t* d_info, void* stream) {
   if (int rc = open_call(p, n_cells, d_mask && d_values && d_A_eff, "mask / values / A_eff", true); rc != GO) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (p->family == FAM_FUSED2D) {
-    hommx::CoefSource src;
-    src.mode = hommx::COEF_TWO_PHASE;
-    src.table = d_mask;
-    HIP_TRY(hommx::launch_poisson2d_fused(d_values, d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st, src));
-    return HOMMX_OK;
-  }
-  const int n_comp = p->ks.n_comp;
-  return expand_and_solve(p, n_cells, d_M, d_A_eff, d_info, st, [&](int64_t c0, int64_t nc, double* dst) {
-    return hommx::launch_expand_two_phase(d_mask, d_values + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st);
-  });
+  return solve_source_device(p, n_cells, two_phase_source(d_mask, d_values), d_M, d_A_eff, d_info, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hommx_solve_batch_two_phase(hommx_plan* p, int64_t n_cells, const uint8_t* mask, const double* values,
                                 const double* M, double* A_eff, int32_t* info) {
   if (int rc = open_call(p, n_cells, mask && values && A_eff, "mask / values / A_eff"); rc != GO) return rc;
-  const int d = p->desc.dim;
-  const HostIn in[] = {{mask, (size_t)p->n_el}, {values, sizeof(double) * n_cells * 2 * p->ks.n_comp}, {M, sizeof(double) * n_cells * d * d}};
-  return staged_call(p, n_cells, in, A_eff, info, [&](const void* const* d_in, double* d_A_eff, int32_t* d_info) {
-    return hommx_solve_batch_two_phase_device(p, n_cells, static_cast<const uint8_t*>(d_in[0]), static_cast<const double*>(d_in[1]),
-                                              static_cast<const double*>(d_in[2]), d_A_eff, d_info, nullptr);
-  });
+  return solve_source_host(p, n_cells, two_phase_source(mask, values), M, A_eff, info);
 }
 
 int hommx_solve_batch_separable_device(hommx_plan* p, int64_t n_cells, int32_t family, int32_t n_q, const double* d_table,
                                        const double* d_weights, const double* d_params, const double* d_M, double* d_A_eff,
                                        int32_t* d_info, void* stream) {
-  if (int rc = open_call(p, n_cells); rc != GO) return rc;
-  if (int rc = sampler_check(p, family)) return rc;
-  if (!d_table || !d_params || !d_A_eff) return fail(HOMMX_EINVAL, "null table / params / A_eff");
-  if (family == HOMMX_SAMPLER_RECIPROCAL && (n_q < 1 || !d_weights)) return fail(HOMMX_EINVAL, "reciprocal sampler needs n_q >= 1 and weights");
-  if (n_cells > 0x7fffffffll) return fail(HOMMX_EINVAL, "n_cells too large for one launch");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const hommx::CoefSource src = sampler_source(family, n_q, d_table, d_weights);
-  if (p->family == FAM_FUSED2D) {
-    HIP_TRY(hommx::launch_poisson2d_fused(d_params, d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st, src));
-    return HOMMX_OK;
-  }
-  const int n_comp = p->ks.n_comp;
-  return expand_and_solve(p, n_cells, d_M, d_A_eff, d_info, st, [&](int64_t c0, int64_t nc, double* dst) {
-    return hommx::launch_expand_separable(src, d_params + 2 * n_comp * c0, dst, p->n_el, n_comp, nc, st);
-  });
+  const char* names = "table / params / A_eff";  // kind, family, pointers, n_q and weights: the order this entry always had
+  const hommx_coef_source s = separable_source(family, n_q, d_table, d_weights, d_params);
+  if (int rc = open_call(p, n_cells, true, "", true, [&] { return coef_check(p, &s, names, d_A_eff); }); rc != GO) return rc;
+  return solve_source_device(p, n_cells, s, d_M, d_A_eff, d_info, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hommx_solve_batch_separable(hommx_plan* p, int64_t n_cells, int32_t family, int32_t n_q, const double* table,
                                 const double* weights, const double* params, const double* M, double* A_eff, int32_t* info) {
-  if (int rc = open_call(p, n_cells, table && params && A_eff, "table / params / A_eff"); rc != GO) return rc;
-  if (family != HOMMX_SAMPLER_AFFINE && family != HOMMX_SAMPLER_RECIPROCAL) return fail(HOMMX_EINVAL, "unknown sampler family %d", family);
-  if (family == HOMMX_SAMPLER_RECIPROCAL && (n_q < 1 || !weights)) return fail(HOMMX_EINVAL, "reciprocal sampler needs n_q >= 1 and weights");
-  const int d = p->desc.dim;
-  const int64_t ntab = p->n_el * (family == HOMMX_SAMPLER_AFFINE ? 1 : n_q);
-  const HostIn in[] = {{table, sizeof(double) * ntab},
-                       {n_q > 0 ? weights : nullptr, sizeof(double) * (n_q > 0 ? n_q : 0)},
-                       {params, sizeof(double) * n_cells * 2 * p->ks.n_comp},
-                       {M, sizeof(double) * n_cells * d * d}};
-  return staged_call(p, n_cells, in, A_eff, info, [&](const void* const* d_in, double* d_A_eff, int32_t* d_info) {
-    return hommx_solve_batch_separable_device(p, n_cells, family, n_q, static_cast<const double*>(d_in[0]), static_cast<const double*>(d_in[1]),
-                                              static_cast<const double*>(d_in[2]), static_cast<const double*>(d_in[3]), d_A_eff, d_info, nullptr);
-  });
+  const char* names = "table / params / A_eff";
+  const hommx_coef_source s = separable_source(family, n_q, table, weights, params);
+  if (int rc = open_call(p, n_cells, true, "", false, [&] { return coef_check(p, &s, names, A_eff); }); rc != GO) return rc;
+  return solve_source_host(p, n_cells, s, M, A_eff, info);
 }
 
 int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* coef, const double* M, double* A_eff,
@@ -548,31 +613,23 @@ int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* c
   if (int rc = open_call(p, n_cells, coef && A_eff && correctors, "coef / A_eff / correctors"); rc != GO) return rc;
   if (int rc = corrector_workspace(p)) return rc;
   const int d = p->desc.dim, t = p->ks.t;
-  const long long nn = p->family == FAM_MESH ? hommx::mesh_num_nodes(p->mesh) : p->ws->G.nn;
-  // the call's own device buffers, freed when it returns: the correctors can run to gigabytes, the plan keeps none of them
-  struct CallBufs {
-    Buf coef, M, out, corr, info;
-    ~CallBufs() {
-      for (Buf* b : {&coef, &M, &out, &corr, &info}) b->release();
-    }
-  } b;
-  const size_t ncoef = sizeof(double) * n_cells * p->n_el * p->ks.n_comp, ncorr = sizeof(double) * n_cells * t * nn * p->ks.bs;
-  if (int rc = grow(b.coef, ncoef)) return rc;
-  if (int rc = grow(b.out, sizeof(double) * n_cells * t * t)) return rc;
-  if (int rc = grow(b.corr, ncorr)) return rc;
-  if (int rc = grow(b.info, sizeof(int32_t) * n_cells)) return rc;
-  HIP_TRY(hipMemcpy(b.coef.p, coef, ncoef, hipMemcpyHostToDevice));
-  if (M) {
-    if (int rc = grow(b.M, sizeof(double) * n_cells * d * d)) return rc;
-    HIP_TRY(hipMemcpy(b.M.p, M, sizeof(double) * n_cells * d * d, hipMemcpyHostToDevice));
-  }
-  int rc = route_solve(p, n_cells, static_cast<const double*>(b.coef.p), static_cast<const double*>(b.M.p), static_cast<double*>(b.out.p),
-                       static_cast<int32_t*>(b.info.p), nullptr, static_cast<double*>(b.corr.p));
+  // the call's own device block, freed when it returns: the correctors can run to gigabytes, the plan keeps none of them
+  struct CallBuf : Buf {
+    ~CallBuf() { release(); }
+  } block;
+  const size_t bytes[] = {sizeof(double) * n_cells * p->n_el * p->ks.n_comp, M ? sizeof(double) * n_cells * d * d : 0,
+                          sizeof(double) * n_cells * t * t, sizeof(double) * n_cells * t * plan_ndof(p), sizeof(int32_t) * n_cells};
+  char* at[5];
+  if (int rc = carve(block, bytes, at)) return rc;
+  HIP_TRY(hipMemcpy(at[0], coef, bytes[0], hipMemcpyHostToDevice));
+  if (M) HIP_TRY(hipMemcpy(at[1], M, bytes[1], hipMemcpyHostToDevice));
+  int rc = route_solve(p, n_cells, reinterpret_cast<const double*>(at[0]), reinterpret_cast<const double*>(at[1]),
+                       reinterpret_cast<double*>(at[2]), reinterpret_cast<int32_t*>(at[4]), nullptr, reinterpret_cast<double*>(at[3]));
   if (rc != HOMMX_OK) return rc;
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(A_eff, b.out.p, sizeof(double) * n_cells * t * t, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(correctors, b.corr.p, ncorr, hipMemcpyDeviceToHost));
-  if (info) HIP_TRY(hipMemcpy(info, b.info.p, sizeof(int32_t) * n_cells, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(A_eff, at[2], bytes[2], hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(correctors, at[3], bytes[3], hipMemcpyDeviceToHost));
+  if (info) HIP_TRY(hipMemcpy(info, at[4], bytes[4], hipMemcpyDeviceToHost));
   return HOMMX_OK;
 }
 
@@ -606,13 +663,13 @@ int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const ReconIO& io, Recon
   const int t = p->ks.t;
   const long long nd = plan_ndof(p);
   const bool lds = recon_in_lds(p);
-  if (int rc = grow(p->rcorr, sizeof(double) * chunk * nd * (t + (lds ? 0 : 1)))) return rc;
+  if (int rc = grow(p->buf[B_RCORR], sizeof(double) * chunk * nd * (t + (lds ? 0 : 1)))) return rc;
   double* d_A_eff = io.A_eff;
   if (!d_A_eff) {
-    if (int rc = grow(p->rA, sizeof(double) * chunk * t * t)) return rc;
-    d_A_eff = static_cast<double*>(p->rA.p);
+    if (int rc = grow(p->buf[B_RA], sizeof(double) * chunk * t * t)) return rc;
+    d_A_eff = static_cast<double*>(p->buf[B_RA].p);
   }
-  double* corr = static_cast<double*>(p->rcorr.p);
+  double* corr = static_cast<double*>(p->buf[B_RCORR].p);
   if (int rc = route_solve(p, nc, io.coef, io.M, d_A_eff, io.info, st, corr)) return rc;
   hommx::ReconArgs a;
   a.ndof = nd;
@@ -641,33 +698,8 @@ int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const ReconIO& io, Recon
   return HOMMX_OK;
 }
 
-// the shared argument checks of the reconstruct entry points
-int recon_open(hommx_plan* p, int64_t n_cells, const void* coef, const void* xi, const void* stats, const void* strain, const void* flux,
-               bool device) {
-  if (int rc = open_call(p, n_cells, coef && xi && stats, "coef / xi / stats", device); rc != GO) return rc;
-  if (!strain != !flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
-  if (int rc = corrector_workspace(p)) return rc;  // a reconstruction needs a route that forms correctors
-  return GO;
-}
-
-// what hommx_reconstruct_source[_device] checks of its source and regions: no device needed, nothing but p->desc read
-int source_check(const hommx_plan* p, const hommx_coef_source* s, int32_t n_regions, const void* region, const void* region_stats) {
-  if (!s) return fail(HOMMX_EINVAL, "null source");
-  switch (s->form) {
-    case HOMMX_COEF_SAMPLED:
-      if (!s->coef) return fail(HOMMX_EINVAL, "null coef");
-      break;
-    case HOMMX_COEF_TWO_PHASE:
-      if (!s->mask || !s->values) return fail(HOMMX_EINVAL, "null mask / values");
-      break;
-    case HOMMX_COEF_SEPARABLE:
-      if (int rc = sampler_check(p, s->family)) return rc;
-      if (!s->table || !s->params) return fail(HOMMX_EINVAL, "null table / params");
-      if (s->family == HOMMX_SAMPLER_RECIPROCAL && (s->n_q < 1 || !s->weights))
-        return fail(HOMMX_EINVAL, "reciprocal sampler needs n_q >= 1 and weights");
-      break;
-    default: return fail(HOMMX_EINVAL, "unknown coefficient form %d", s->form);
-  }
+// the regions of hommx_reconstruct_source[_device]; `s` has passed coef_check
+int regions_check(const hommx_coef_source* s, int32_t n_regions, const void* region, const void* region_stats) {
   if (n_regions < 0 || n_regions > HOMMX_RECON_MAX_REGIONS)
     return fail(HOMMX_EINVAL, "n_regions must be 0 .. %d, got %d", HOMMX_RECON_MAX_REGIONS, n_regions);
   const bool mask_labels = s->form == HOMMX_COEF_TWO_PHASE && n_regions == 2 && !region;
@@ -677,56 +709,31 @@ int source_check(const hommx_plan* p, const hommx_coef_source* s, int32_t n_regi
   return HOMMX_OK;
 }
 
-// the source with the pointers of its form alone (the others are not the caller's to set)
-hommx_coef_source source_of_form(const hommx_coef_source& s) {
-  hommx_coef_source o{};
-  o.form = s.form;
-  if (s.form == HOMMX_COEF_SAMPLED) o.coef = s.coef;
-  if (s.form == HOMMX_COEF_TWO_PHASE) o.mask = s.mask, o.values = s.values;
-  if (s.form == HOMMX_COEF_SEPARABLE) {
-    o.family = s.family;
-    o.n_q = s.family == HOMMX_SAMPLER_AFFINE ? 1 : s.n_q;
-    o.table = s.table;
-    o.weights = s.family == HOMMX_SAMPLER_AFFINE ? nullptr : s.weights;
-    o.params = s.params;
-  }
-  return o;
+// the shared argument checks of the reconstruct entry points; `more`: the source and the regions of the entry points that take them
+template <typename More>
+int recon_open(hommx_plan* p, int64_t n_cells, const void* coef, const void* xi, const void* stats, const void* strain, const void* flux,
+               bool device, More more) {
+  if (int rc = open_call(p, n_cells, coef && xi && stats, "coef / xi / stats", device, more); rc != GO) return rc;
+  if (!strain != !flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
+  if (int rc = corrector_workspace(p)) return rc;  // a reconstruction needs a route that forms correctors
+  return GO;
 }
-hommx_coef_source sampled_source(const double* coef) {
-  hommx_coef_source s{};
-  s.form = HOMMX_COEF_SAMPLED;
-  s.coef = coef;
-  return s;
+int recon_open(hommx_plan* p, int64_t n_cells, const void* coef, const void* xi, const void* stats, const void* strain, const void* flux,
+               bool device) {
+  return recon_open(p, n_cells, coef, xi, stats, strain, flux, device, [] { return HOMMX_OK; });
 }
 
-// cells per chunk of a source: recon_chunk() and, for a sampler form, the 1 GiB of expanded element stream (allocated here) of expand_and_solve
-int source_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t n_cells, size_t extra, int64_t* chunk) {
-  *chunk = recon_chunk(p, n_cells, extra);
-  if (s.form == HOMMX_COEF_SAMPLED) return HOMMX_OK;
-  const int64_t per = p->n_el * p->ks.n_comp;
-  *chunk = std::min(*chunk, std::max<int64_t>((1ll << 27) / std::max<int64_t>(per, 1), 1));
-  return grow(p->expand, sizeof(double) * *chunk * per);
-}
-
-// The chunk loop of the four reconstruct entry points.  `s` holds device pointers (a sampled stream may still be on the host).  Per chunk
-// of cells [c0, c0 + nc): in(c0, nc, io) fills io, bringing in what a host entry stages per chunk; a sampler form is expanded into the
-// plan's element stream by the kernels of expand_and_solve; recon_run; out(c0, nc, io) takes the outputs away (host entries).
+// The chunk loop of the four reconstruct entry points.  `s` holds device pointers (a host entry stages its sampled stream per chunk: s.coef is null then).  Per chunk
+// of cells [c0, c0 + nc): in(c0, nc, io) fills io, bringing in what a host entry stages per chunk (its sampled stream among it);
+// expand_chunk gives the element stream of every other source; recon_run; out(c0, nc, io) takes the outputs away (host entries).
 template <typename In, typename Out>
 int recon_chunks(hommx_plan* p, int64_t n_cells, int64_t chunk, const hommx_coef_source& s, ReconRegions rg, hipStream_t st, In in, Out out) {
-  const int n_comp = p->ks.n_comp;
   for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
     const int64_t nc = std::min(chunk, n_cells - c0);
     ReconIO io{};
     if (int rc = in(c0, nc, io)) return rc;
-    if (s.form != HOMMX_COEF_SAMPLED) {
-      double* dst = static_cast<double*>(p->expand.p);
-      if (s.form == HOMMX_COEF_TWO_PHASE)
-        HIP_TRY(hommx::launch_expand_two_phase(s.mask, s.values + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st));
-      else
-        HIP_TRY(hommx::launch_expand_separable(sampler_source(s.family, s.n_q, s.table, s.weights), s.params + c0 * 2 * n_comp, dst, p->n_el,
-                                               n_comp, nc, st));
-      io.coef = dst;
-    }
+    if (!io.coef)
+      if (int rc = expand_chunk(p, s, c0, nc, st, &io.coef)) return rc;
     if (int rc = recon_run(p, nc, chunk, io, rg, st)) return rc;
     if (int rc = out(c0, nc, io)) return rc;
   }
@@ -737,14 +744,13 @@ int recon_chunks(hommx_plan* p, int64_t n_cells, int64_t chunk, const hommx_coef
 int recon_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, const double* d_xi, ReconRegions rg,
                  double* d_stats, double* d_region_stats, double* d_strain, double* d_flux, double* d_A_eff, int32_t* d_info, hipStream_t st) {
   const int d = p->desc.dim, t = p->ks.t, ns = HOMMX_RECON_NSTATS(t), nr = rg.n * HOMMX_RECON_NREGION(t);
-  const int64_t per = p->n_el * p->ks.n_comp;
   int64_t chunk = 0;
-  if (int rc = source_chunk(p, s, n_cells, 0, &chunk)) return rc;
+  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, 0), &chunk)) return rc;
   return recon_chunks(
       p, n_cells, chunk, s, rg, st,
       [&](int64_t c0, int64_t, ReconIO& io) {
         const int64_t fo = c0 * p->n_el * t;
-        io = ReconIO{s.coef ? s.coef + c0 * per : nullptr,
+        io = ReconIO{nullptr,
                      d_M ? d_M + c0 * d * d : nullptr,
                      d_xi + c0 * t,
                      d_stats + c0 * ns,
@@ -759,57 +765,37 @@ int recon_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, con
 }
 
 // host pointers.  What every cell shares (mask, table, weights, labels) and the per-cell values of a sampler form travel once, in the
-// plan's pinned block (as staged_call); a sampled stream, M and xi stream in and every output streams out chunk by chunk, so device
+// plan's pinned block (stage_source); a sampled stream, M and xi stream in and every output streams out chunk by chunk, so device
 // memory is bounded by the chunk
 int recon_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const double* xi, int32_t n_regions,
                const uint8_t* region, double* stats, double* region_stats, double* strain, double* flux, double* A_eff, int32_t* info) {
   const int d = p->desc.dim, t = p->ks.t, ns = HOMMX_RECON_NSTATS(t), nr = n_regions * HOMMX_RECON_NREGION(t);
-  const bool sampled = s.form == HOMMX_COEF_SAMPLED;
-  const int64_t per = p->n_el * p->ks.n_comp, nfield = strain ? 2 * p->n_el * t : 0;
-  const size_t nval = sizeof(double) * n_cells * 2 * p->ks.n_comp;
-  const HostIn shared[] = {{s.mask, (size_t)p->n_el},  {s.values, nval}, {s.table, sizeof(double) * p->n_el * s.n_q},
-                           {s.weights, sizeof(double) * s.n_q}, {s.params, nval}, {region, (size_t)p->n_el}};
-  const void* dv[6];
-  if (int rc = stage_in(p, shared, dv)) return rc;
-  hommx_coef_source ds = s;
-  ds.mask = static_cast<const uint8_t*>(dv[0]);
-  ds.values = static_cast<const double*>(dv[1]);
-  ds.table = static_cast<const double*>(dv[2]);
-  ds.weights = static_cast<const double*>(dv[3]);
-  ds.params = static_cast<const double*>(dv[4]);
-  const ReconRegions rg{n_regions, n_regions ? (region ? static_cast<const uint8_t*>(dv[5]) : ds.mask) : nullptr};
-  // per cell, 256-byte aligned blocks: in = [coef | M | xi], out = [stats | A_eff | info | strain | flux | region_stats]
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t in_cell = sizeof(double) * ((sampled ? per : 0) + (M ? d * d : 0) + t);
-  const size_t out_cell = sizeof(double) * (ns + nr + t * t + nfield) + sizeof(int32_t);
+  const int64_t per = s.form == HOMMX_COEF_SAMPLED ? p->n_el * p->ks.n_comp : 0, field = strain ? p->n_el * t : 0;
+  hommx_coef_source ds;
+  const uint8_t* d_region = nullptr;
+  if (int rc = stage_source(p, n_cells, s, {region, (size_t)p->n_el, (const void**)&d_region}, &ds)) return rc;
+  const ReconRegions rg{n_regions, n_regions ? (region ? d_region : ds.mask) : nullptr};
+  // doubles per cell of the plan's blocks: in = [coef | M | xi], out = [stats | A_eff | strain | flux | region_stats], and info
+  const int64_t n_in[] = {per, M ? d * d : 0, t}, n_out[] = {ns, t * t, field, field, nr};
   int64_t chunk = 0;
-  if (int rc = source_chunk(p, s, n_cells, in_cell + out_cell, &chunk)) return rc;
-  const size_t o_M = up(sizeof(double) * chunk * (sampled ? per : 0)), o_xi = o_M + (M ? up(sizeof(double) * chunk * d * d) : 0);
-  const size_t o_A = up(sizeof(double) * chunk * ns), o_info = o_A + up(sizeof(double) * chunk * t * t);
-  const size_t o_strain = o_info + up(sizeof(int32_t) * chunk), o_flux = o_strain + up(sizeof(double) * chunk * p->n_el * t * (strain ? 1 : 0));
-  const size_t o_reg = o_flux + up(sizeof(double) * chunk * p->n_el * t * (strain ? 1 : 0));
-  if (int rc = grow(p->rin, o_xi + sizeof(double) * chunk * t)) return rc;
-  if (int rc = grow(p->rout, o_reg + sizeof(double) * chunk * nr)) return rc;
-  char* din = static_cast<char*>(p->rin.p);
-  char* dout = static_cast<char*>(p->rout.p);
-  double* d_coef = sampled ? reinterpret_cast<double*>(din) : nullptr;
-  double* d_M = M ? reinterpret_cast<double*>(din + o_M) : nullptr;
-  double* d_xi = reinterpret_cast<double*>(din + o_xi);
-  const ReconIO dev{d_coef,
-                    d_M,
-                    d_xi,
-                    reinterpret_cast<double*>(dout),
-                    n_regions ? reinterpret_cast<double*>(dout + o_reg) : nullptr,
-                    strain ? reinterpret_cast<double*>(dout + o_strain) : nullptr,
-                    strain ? reinterpret_cast<double*>(dout + o_flux) : nullptr,
-                    reinterpret_cast<double*>(dout + o_A),
-                    reinterpret_cast<int32_t*>(dout + o_info)};
+  const size_t cell = sizeof(double) * (per + n_in[1] + t + ns + t * t + 2 * field + nr) + sizeof(int32_t);
+  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, cell), &chunk)) return rc;
+  size_t in_bytes[3], out_bytes[6];
+  for (int k = 0; k < 3; ++k) in_bytes[k] = sizeof(double) * chunk * n_in[k];
+  for (int k = 0; k < 5; ++k) out_bytes[k] = sizeof(double) * chunk * n_out[k];
+  out_bytes[5] = sizeof(int32_t) * chunk;
+  char *in[3], *out[6];
+  if (int rc = carve(p->buf[B_IN], in_bytes, in)) return rc;
+  if (int rc = carve(p->buf[B_OUT], out_bytes, out)) return rc;
+  auto f64 = [](char* at) { return reinterpret_cast<double*>(at); };
+  const ReconIO dev{f64(in[0]), f64(in[1]), f64(in[2]), f64(out[0]), f64(out[4]), f64(out[2]), f64(out[3]), f64(out[1]),
+                    reinterpret_cast<int32_t*>(out[5])};
   return recon_chunks(
       p, n_cells, chunk, ds, rg, nullptr,
       [&](int64_t c0, int64_t nc, ReconIO& io) {
-        if (sampled) HIP_TRY(hipMemcpy(d_coef, s.coef + c0 * per, sizeof(double) * nc * per, hipMemcpyHostToDevice));
-        if (M) HIP_TRY(hipMemcpy(d_M, M + c0 * d * d, sizeof(double) * nc * d * d, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_xi, xi + c0 * t, sizeof(double) * nc * t, hipMemcpyHostToDevice));
+        if (per) HIP_TRY(hipMemcpy(in[0], s.coef + c0 * per, sizeof(double) * nc * per, hipMemcpyHostToDevice));
+        if (M) HIP_TRY(hipMemcpy(in[1], M + c0 * d * d, sizeof(double) * nc * d * d, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(in[2], xi + c0 * t, sizeof(double) * nc * t, hipMemcpyHostToDevice));
         io = dev;
         return HOMMX_OK;
       },
@@ -818,8 +804,8 @@ int recon_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const
         if (A_eff) HIP_TRY(hipMemcpy(A_eff + c0 * t * t, io.A_eff, sizeof(double) * nc * t * t, hipMemcpyDeviceToHost));
         if (info) HIP_TRY(hipMemcpy(info + c0, io.info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
         if (strain) {
-          HIP_TRY(hipMemcpy(strain + c0 * p->n_el * t, io.strain, sizeof(double) * nc * p->n_el * t, hipMemcpyDeviceToHost));
-          HIP_TRY(hipMemcpy(flux + c0 * p->n_el * t, io.flux, sizeof(double) * nc * p->n_el * t, hipMemcpyDeviceToHost));
+          HIP_TRY(hipMemcpy(strain + c0 * field, io.strain, sizeof(double) * nc * field, hipMemcpyDeviceToHost));
+          HIP_TRY(hipMemcpy(flux + c0 * field, io.flux, sizeof(double) * nc * field, hipMemcpyDeviceToHost));
         }
         if (n_regions) HIP_TRY(hipMemcpy(region_stats + c0 * nr, io.region_stats, sizeof(double) * nc * nr, hipMemcpyDeviceToHost));
         return HOMMX_OK;
@@ -846,10 +832,11 @@ int hommx_reconstruct_batch(hommx_plan* p, int64_t n_cells, const double* coef, 
 int hommx_reconstruct_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const double* d_xi,
                                     int32_t n_regions, const uint8_t* d_region, double* d_stats, double* d_region_stats, double* d_strain,
                                     double* d_flux, double* d_A_eff, int32_t* d_info, void* stream) {
-  // the source and the regions are checked before the plan's device is made current (an empty batch and a null plan are recon_open's)
-  if (p && n_cells > 0)
-    if (int rc = source_check(p, src, n_regions, d_region, d_region_stats)) return rc;
-  if (int rc = recon_open(p, n_cells, src, d_xi, d_stats, d_strain, d_flux, true); rc != GO) return rc;
+  auto more = [&] {
+    if (int rc = coef_check(p, src)) return rc;
+    return regions_check(src, n_regions, d_region, d_region_stats);
+  };
+  if (int rc = recon_open(p, n_cells, src, d_xi, d_stats, d_strain, d_flux, true, more); rc != GO) return rc;
   const hommx_coef_source s = source_of_form(*src);
   return recon_device(p, n_cells, s, d_M, d_xi, ReconRegions{n_regions, n_regions ? (d_region ? d_region : s.mask) : nullptr}, d_stats,
                       d_region_stats, d_strain, d_flux, d_A_eff, d_info, reinterpret_cast<hipStream_t>(stream));
@@ -858,9 +845,11 @@ int hommx_reconstruct_source_device(hommx_plan* p, int64_t n_cells, const hommx_
 int hommx_reconstruct_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const double* xi, int32_t n_regions,
                              const uint8_t* region, double* stats, double* region_stats, double* strain, double* flux, double* A_eff,
                              int32_t* info) {
-  if (p && n_cells > 0)
-    if (int rc = source_check(p, src, n_regions, region, region_stats)) return rc;
-  if (int rc = recon_open(p, n_cells, src, xi, stats, strain, flux, false); rc != GO) return rc;
+  auto more = [&] {
+    if (int rc = coef_check(p, src)) return rc;
+    return regions_check(src, n_regions, region, region_stats);
+  };
+  if (int rc = recon_open(p, n_cells, src, xi, stats, strain, flux, false, more); rc != GO) return rc;
   return recon_host(p, n_cells, source_of_form(*src), M, xi, n_regions, region, stats, region_stats, strain, flux, A_eff, info);
 }
 

@@ -31,7 +31,18 @@ int prefix_error(int code, const char* prefix);
     }                                                                                                                             \
   } while (0)
 
-// One device allocation (*block, the caller's to hipFree) that holds a copy of every host array, each piece 256-byte aligned; *dst of a
+// The layout of every packed block: pieces of bytes[k] bytes end to end, each 256-byte aligned (so a piece of 0 bytes takes no room).
+// off[k]: where piece k starts; returns the size of the block.
+inline size_t pack_offsets(size_t n, const size_t* bytes, size_t* off) {
+  size_t total = 0;
+  for (size_t k = 0; k < n; ++k) {
+    off[k] = total;
+    total += (bytes[k] + 255) / 256 * 256;
+  }
+  return total;
+}
+
+// One device allocation (*block, the caller's to hipFree) that holds a copy of every host array, laid out by pack_offsets; *dst of a
 // piece is where it starts on the device.
 struct HostPiece {
   const void* src;
