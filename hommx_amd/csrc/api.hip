@@ -105,7 +105,8 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 // entry point (hommx_solve_batch: the batch; recon_host: one chunk).  B_EXPAND: the expanded element stream of the sampler forms.
 // B_PIN_* / B_DEV_*: the small inputs of the sampler host entry points and their outputs, pinned host mirrors + device (plan_new pins).
 // B_RCORR, B_RA: the correctors of one reconstruction chunk (and the chi^xi slots of cells too large for LDS), A_eff the caller did not ask for
-enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, N_BUF };
+// B_FACT: the factor records of one chunk of a fused 2D plan's corrector route (kernels.h)
+enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, N_BUF };
 
 }  // namespace
 
@@ -114,7 +115,8 @@ struct hommx_plan {
   Family family;
   int64_t n_el;
   hommx::KindSizes ks;
-  hommx::BlockedWorkspace* ws = nullptr;  // FAM_BLOCKED, and a FAM_FUSED2D plan once it has served correctors
+  hommx::BlockedWorkspace* ws = nullptr;  // FAM_BLOCKED, and a FAM_FUSED2D plan with HOMMX_FUSED_CORR=0 once it has served correctors
+  bool fused_corr = true;                 // FAM_FUSED2D: correctors by substitution on the fused kernel's own factors (HOMMX_FUSED_CORR)
   hommx::MeshPlan* mesh = nullptr;        // FAM_MESH: symbolic phase + device tables of the unstructured micro mesh
   Buf buf[N_BUF];
   // host-pointer entry point: coefficient chunks stream in on s_copy while s_comp solves the previous one
@@ -154,7 +156,7 @@ int open_call(const hommx_plan* p, int64_t n_cells, bool ptrs_ok = true, const c
 }
 
 // What both plan constructors end with: the device range, then the plan with everything its descriptor determines.
-// HOMMX_RECON_MEM_MB (include/hommx_hip.h) is read here, once
+// HOMMX_RECON_MEM_MB and HOMMX_FUSED_CORR (include/hommx_hip.h) are read here, once
 int plan_new(hommx_plan** out, const hommx_plan_desc& desc, int64_t n_el) {
   const int ndev = hommx_device_count();
   if (ndev <= 0) return fail(HOMMX_ENODEV, "no HIP device visible");
@@ -168,9 +170,15 @@ int plan_new(hommx_plan** out, const hommx_plan_desc& desc, int64_t n_el) {
   const char* v = getenv("HOMMX_RECON_MEM_MB");
   const long long mb = v ? atoll(v) : 0;
   p->recon_mem_mb = mb > 0 ? mb : 1024;
+  if (const char* e = getenv("HOMMX_FUSED_CORR")) p->fused_corr = atoi(e) != 0;
   *out = p;
   return HOMMX_OK;
 }
+
+// a fused 2D plan whose correctors come from its own factors
+bool fused_subst(const hommx_plan* p) { return p->family == FAM_FUSED2D && p->fused_corr; }
+// bytes of factor record per cell of that route (0 on every other)
+size_t fact_bytes(const hommx_plan* p) { return fused_subst(p) ? sizeof(double) * hommx::fused_fact_doubles(p->desc.n_micro) : 0; }
 
 // a failed call into the plan's route, under the route's name
 int route_fail(const hommx_plan* p, int rc) { return prefix_error(rc, p->desc.n_micro ? "blocked path: " : "mesh route: "); }
@@ -178,20 +186,35 @@ int route_fail(const hommx_plan* p, int rc) { return prefix_error(rc, p->desc.n_
 // an element stream on the device through the plan's mesh_front or blocked route; d_corr: the correctors as well
 int route_solve(hommx_plan* p, int64_t n_cells, const double* d_coef, const double* d_M, double* d_A_eff, int32_t* d_info, hipStream_t st,
                 double* d_corr = nullptr) {
+  if (d_corr && fused_subst(p)) {
+    // the fused elimination once more, keeping its block inverses, then the substitution on them: A_eff and info from the forward kernel
+    if (int rc = grow(p->buf[B_FACT], fact_bytes(p) * n_cells)) return rc;
+    double* fact = static_cast<double*>(p->buf[B_FACT].p);
+    HIP_TRY(hommx::launch_poisson2d_fused_fact(d_coef, d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st, fact));
+    HIP_TRY(hommx::launch_fused2d_subst(fact, d_corr, p->desc.n_micro, n_cells, st));
+    return HOMMX_OK;
+  }
   const int rc = p->family == FAM_MESH ? hommx::mesh_solve(p->mesh, n_cells, d_coef, d_M, d_A_eff, d_info, st, d_corr)
                                        : hommx::blocked_solve(p->ws, n_cells, d_coef, d_M, d_A_eff, d_info, st, d_corr);
   return rc ? route_fail(p, rc) : HOMMX_OK;
 }
 
-// a fused 2D plan computes no correctors: the first call that needs them gives it a workspace of the blocked family, which does
+// a fused 2D plan forms its correctors from its own factors (route_solve); with HOMMX_FUSED_CORR=0 the first call that needs them gives it
+// a workspace of the blocked family instead
 int corrector_workspace(hommx_plan* p) {
-  if (p->family != FAM_FUSED2D || p->ws) return HOMMX_OK;
+  if (p->family != FAM_FUSED2D || p->ws || p->fused_corr) return HOMMX_OK;
   int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
   return rc ? prefix_error(rc, "blocked path: ") : HOMMX_OK;
 }
 
 // periodic unknowns of a cell (nodes x bs): the length of one corrector
-long long plan_ndof(const hommx_plan* p) { return (p->family == FAM_MESH ? hommx::mesh_num_nodes(p->mesh) : p->ws->G.nn) * (long long)p->ks.bs; }
+long long plan_ndof(const hommx_plan* p) {
+  const long long n = p->desc.n_micro;
+  const long long nodes = p->family == FAM_MESH ? hommx::mesh_num_nodes(p->mesh) : n ? (p->desc.dim == 2 ? n * n : n * n * n) : p->ws->G.nn;
+  return nodes * p->ks.bs;
+}
+
+int64_t recon_chunk(const hommx_plan* p, int64_t n_cells, size_t extra);  // below, with the reconstruction
 
 // -- coefficient sources: inside this file a coefficient is a normalised hommx_coef_source (the pointers of its form alone) ----------------
 hommx_coef_source sampled_source(const double* coef) {
@@ -451,12 +474,21 @@ const char* hommx_plan_kernel_name(const hommx_plan* p) {
   }
 }
 
+const char* hommx_plan_corrector_kernel_name(const hommx_plan* p) {
+  if (!p) return "";
+  switch (p->family) {
+    case FAM_FUSED2D: return p->fused_corr ? "fused2d_subst" : "blocked";
+    case FAM_MESH: return "mesh_front";
+    default: return hommx::blocked_corrector_route_name(p->ws);
+  }
+}
+
 const char* hommx_plan_route_detail(hommx_plan* p) {
   if (!p) return "";
   switch (p->family) {
     case FAM_FUSED2D:
-      return p->desc.n_micro > 16 ? "fused2d: k_poisson2d_fused<32>, one wavefront per macro cell, every matrix in the f64 MFMA accumulator layout"
-                                  : "fused2d: k_poisson2d_fused<16>, one wavefront per macro cell, every matrix in the f64 MFMA accumulator layout";
+      return p->desc.n_micro > 16 ? "fused2d: k_poisson2d_fused<32, false>, one wavefront per macro cell, every matrix in the f64 MFMA accumulator layout"
+                                  : "fused2d: k_poisson2d_fused<16, false>, one wavefront per macro cell, every matrix in the f64 MFMA accumulator layout";
     case FAM_MESH: return hommx::mesh_route_detail(p->mesh);
     default: return hommx::blocked_route_detail(p->ws);
   }
@@ -623,9 +655,16 @@ int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* c
   if (int rc = carve(block, bytes, at)) return rc;
   HIP_TRY(hipMemcpy(at[0], coef, bytes[0], hipMemcpyHostToDevice));
   if (M) HIP_TRY(hipMemcpy(at[1], M, bytes[1], hipMemcpyHostToDevice));
-  int rc = route_solve(p, n_cells, reinterpret_cast<const double*>(at[0]), reinterpret_cast<const double*>(at[1]),
-                       reinterpret_cast<double*>(at[2]), reinterpret_cast<int32_t*>(at[4]), nullptr, reinterpret_cast<double*>(at[3]));
-  if (rc != HOMMX_OK) return rc;
+  // one call into the route; a fused 2D plan on its own route: chunks whose factor records and correctors fit HOMMX_RECON_MEM_MB
+  const int64_t chunk = fused_subst(p) ? recon_chunk(p, n_cells, 0) : n_cells;
+  const double *d_coef = reinterpret_cast<const double*>(at[0]), *d_M = reinterpret_cast<const double*>(at[1]);
+  double *d_A = reinterpret_cast<double*>(at[2]), *d_corr = reinterpret_cast<double*>(at[3]);
+  int32_t* d_info = reinterpret_cast<int32_t*>(at[4]);
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    int rc = route_solve(p, std::min(chunk, n_cells - c0), d_coef + c0 * p->n_el * p->ks.n_comp, d_M ? d_M + c0 * d * d : nullptr,
+                         d_A + c0 * t * t, d_info + c0, nullptr, d_corr + c0 * t * plan_ndof(p));
+    if (rc != HOMMX_OK) return rc;
+  }
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(A_eff, at[2], bytes[2], hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(correctors, at[3], bytes[3], hipMemcpyDeviceToHost));
@@ -639,10 +678,11 @@ namespace {
 
 bool recon_in_lds(const hommx_plan* p) { return sizeof(double) * plan_ndof(p) <= hommx::recon_lds_limit(); }
 
-// cells per chunk: HOMMX_RECON_MEM_MB of correctors (with the chi^xi slots of cells too large for LDS) and of `extra` bytes per cell
+// cells per chunk: HOMMX_RECON_MEM_MB of correctors (with the chi^xi slots of cells too large for LDS), of the factor records of a fused
+// 2D plan's own corrector route and of `extra` bytes per cell
 int64_t recon_chunk(const hommx_plan* p, int64_t n_cells, size_t extra) {
   const long long nd = plan_ndof(p);
-  const size_t per = sizeof(double) * nd * (p->ks.t + (recon_in_lds(p) ? 0 : 1)) + extra;
+  const size_t per = sizeof(double) * nd * (p->ks.t + (recon_in_lds(p) ? 0 : 1)) + fact_bytes(p) + extra;
   return std::clamp<int64_t>((int64_t)((p->recon_mem_mb << 20) / per), 1, n_cells);
 }
 

@@ -132,6 +132,8 @@ const char* blocked_route_name(const BlockedWorkspace* ws) {
   return ws ? names[(int)ws->route] : "blocked";
 }
 
+const char* blocked_corrector_route_name(const BlockedWorkspace* ws) { return ws && ws_corr_on_tree(ws) ? blocked_route_name(ws) : "blocked"; }
+
 // one line for reports (bench.py's roofline.kernel): what the route launches, derived from the plan itself
 const char* blocked_route_detail(BlockedWorkspace* ws) {
   if (!ws) return "";

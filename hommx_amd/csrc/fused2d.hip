@@ -30,6 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "kernels.h"
 #include "sweep_acc.h"
 
@@ -74,10 +76,13 @@ struct alignas(16) Lds {
   double cenat[NB + 2]; // [1 + i] = D_{j+1}[i][i+1]; [0] = 0
 };
 
-template <int NB>
+// FACT: the kernel also writes the factor record of its cell (kernels.h) for k_fused2d_subst; the last kernel argument is then the
+// records, and an empty struct otherwise
+struct NoFact {};
+template <int NB, bool FACT>
 __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fused(
     const double* __restrict__ coef, const double* __restrict__ Mmat, double* __restrict__ out,
-    int32_t* __restrict__ info, int n, long long ncells, const CoefSource src
+    int32_t* __restrict__ info, int n, long long ncells, const CoefSource src, std::conditional_t<FACT, double*, NoFact> fact
 #ifdef HOMMX_FUSED_DEBUG
     , double* __restrict__ dbg
 #endif
@@ -196,6 +201,11 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
     }
   };
 
+  [[maybe_unused]] double* rec = nullptr;  // FACT: the record of this cell, and of the current step
+  if constexpr (FACT) rec = fact + cell * fused_fact_doubles(n);
+  [[maybe_unused]] double* srec = nullptr;
+  if constexpr (FACT) srec = rec + fused_fact_header(NB);
+
   // ---- prologue: rows n-2, n-1, 0 ---------------------------------------------------------------
   double wf[NT][KK];          // W, operand layout
   double a[NT][NT][4];        // T = -S / N, acc layout
@@ -210,6 +220,15 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
     const CoefRow rowB = load_row(n - 1);
     cur = load_row(0);
     asum = (rowB.a0 + rowB.a1) + (cur.a0 + cur.a1);
+    if constexpr (FACT) {  // header of the record: the wrap coupling C = E_{n-1} as its two sparse vectors, and M
+      const double neB = st_NE(rowB);
+      const double c1 = __shfl(neB, lb + cm, 64);
+      if (g == 0) {
+        rec[c] = st_N(rowB);
+        rec[NB + c] = c1;
+      }
+      if (l < 4) rec[4 * NB + l] = l == 0 ? m00 : l == 1 ? m01 : l == 2 ? m10 : m11;
+    }
     // S_last = D_{n-1}
     {
       const double dv = st_diag(rowB, rowA), ov = st_E(rowB, rowA);
@@ -323,6 +342,18 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 #endif
       if (badj && !bad) { bad = 1; badstep = jr + 1; }
     }
+    if constexpr (FACT) {  // N'_j as the registers hold it: every store one contiguous 512 B run; the coupling vectors of the step
+#pragma unroll
+      for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < NT; ++tj)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) srec[((ti * NT + tj) * 4 + r) * 64 + l] = a[ti][tj][r];
+      if (g == 0) {
+        srec[NB * NB + 2 * NB + c] = e0c;
+        srec[NB * NB + 3 * NB + c] = e1c;
+      }
+    }
 #ifdef HOMMX_FUSED_DEBUG
     if (dbg && cell == 0) {
       double* q = dbg + (size_t)jr * 4 * NB * NB;
@@ -414,6 +445,10 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
     gb_ = fma(z, rr[1], gb_);
     L.vnat[k >> 1][c] = z;
     L.vrow[k >> 1][prow] = z;
+    if constexpr (FACT) {  // N'_j r~_j, both load cases (NB = 16: lane rows 2 m and 2 m + 1 hold the same values)
+      if (NB == 32 || !(k & 1)) srec[NB * NB + (k >> 1) * NB + c] = z;
+      srec += fused_fact_step(NB);
+    }
 
     // (6) R_last += Vr' W^T
     {
@@ -631,6 +666,9 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
     }
     ga_ = fma(z, L.vnat[0][c], ga_);
     gb_ = fma(z, L.vnat[1][c], gb_);
+    if constexpr (FACT) {  // y_last: the solution of the last node row (its pinned last entry is 0)
+      if (NB == 32 || !(k & 1)) rec[2 * NB + (k >> 1) * NB + c] = z;
+    }
   }
 
   // ---- K3: wave reduction and output ----------------------------------------------------------------
@@ -662,6 +700,10 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 }
 
 // ---- launch ---------------------------------------------------------------------------------------
+// The two instantiations of FACT are compiled in translation units of their own (fused2d_fact.hip includes this file with
+// HOMMX_FUSED_FACT_TU): with <NB, true> in the same module the compiler schedules <32, false> differently (234 instead of 236 VGPRs, another
+// instruction order), and the tensor path is to stay bit for bit and cycle for cycle what it was.
+#ifndef HOMMX_FUSED_FACT_TU
 hipError_t launch_poisson2d_fused(const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
                                   int n, long long ncells, hipStream_t stream, CoefSource src) {
   if (ncells <= 0) return hipSuccess;
@@ -672,16 +714,38 @@ hipError_t launch_poisson2d_fused(const double* d_coef, const double* d_M, doubl
 #ifdef HOMMX_FUSED_DEBUG
   extern double* g_fused_dbg;
   if (n <= 16)
-    hipLaunchKernelGGL(k_poisson2d_fused<16>, grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, g_fused_dbg);
+    hipLaunchKernelGGL((k_poisson2d_fused<16, false>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, NoFact{}, g_fused_dbg);
   else
-    hipLaunchKernelGGL(k_poisson2d_fused<32>, grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, g_fused_dbg);
+    hipLaunchKernelGGL((k_poisson2d_fused<32, false>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, NoFact{}, g_fused_dbg);
 #else
   if (n <= 16)
-    hipLaunchKernelGGL(k_poisson2d_fused<16>, grid, block, HOMMX_DEV_LDS_PAD, stream, d_coef, d_M, d_out, d_info, n, ncells, src);
+    hipLaunchKernelGGL((k_poisson2d_fused<16, false>), grid, block, HOMMX_DEV_LDS_PAD, stream, d_coef, d_M, d_out, d_info, n, ncells, src, NoFact{});
   else
-    hipLaunchKernelGGL(k_poisson2d_fused<32>, grid, block, HOMMX_DEV_LDS_PAD, stream, d_coef, d_M, d_out, d_info, n, ncells, src);
+    hipLaunchKernelGGL((k_poisson2d_fused<32, false>), grid, block, HOMMX_DEV_LDS_PAD, stream, d_coef, d_M, d_out, d_info, n, ncells, src, NoFact{});
 #endif
   return hipGetLastError();
 }
+
+#else
+hipError_t launch_poisson2d_fused_fact(const double* d_coef, const double* d_M, double* d_out, int32_t* d_info, int n, long long ncells,
+                                       hipStream_t stream, double* d_fact) {
+  if (ncells <= 0) return hipSuccess;
+  dim3 grid((unsigned)ncells), block(64);
+  const CoefSource src;
+#ifdef HOMMX_FUSED_DEBUG
+  extern double* g_fused_dbg;
+  if (n <= 16)
+    hipLaunchKernelGGL((k_poisson2d_fused<16, true>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, d_fact, g_fused_dbg);
+  else
+    hipLaunchKernelGGL((k_poisson2d_fused<32, true>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, d_fact, g_fused_dbg);
+#else
+  if (n <= 16)
+    hipLaunchKernelGGL((k_poisson2d_fused<16, true>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, d_fact);
+  else
+    hipLaunchKernelGGL((k_poisson2d_fused<32, true>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, d_fact);
+#endif
+  return hipGetLastError();
+}
+#endif  // HOMMX_FUSED_FACT_TU
 
 }  // namespace hommx

@@ -69,6 +69,21 @@ struct CoefSource {
 hipError_t launch_poisson2d_fused(const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
                                   int n, long long ncells, hipStream_t stream, CoefSource src = CoefSource());
 
+// The factor record of one cell, written by k_poisson2d_fused<NB, true> and read by k_fused2d_subst<NB> (NB = 16 for n <= 16, else 32);
+// private to the two kernels.  In doubles, with N' = -S^-1 as the elimination carries it:
+//   header  [C e0 (NB) | C e1 (NB) | y_last (2 NB) | M (4) | pad (4)]           C = the wrap coupling E_{n-1}, y_last = z of the final sweep
+//   step j  [N'_j (NB NB, register-major [ti][tj][r][lane]) | N'_j r~_j (2 NB) | E_j e0 (NB) | E_j e1 (NB)],  j = 0 .. n-2
+// e0[i] = E[i][i], e1[i] = E[i][i-1] (cyclic on the real indices, padding first).  n = NB = 32: 136 + 31 * 1152 = 35,848 doubles =
+// 286,784 bytes per cell; n = NB = 16: 72 + 15 * 320 = 4,872 doubles = 38,976 bytes.
+constexpr long long fused_fact_header(int NB) { return 4 * NB + 8; }
+constexpr long long fused_fact_step(int NB) { return (long long)NB * NB + 4 * NB; }
+constexpr long long fused_fact_doubles(int n) { return fused_fact_header(n <= 16 ? 16 : 32) + (n - 1) * fused_fact_step(n <= 16 ? 16 : 32); }
+// fused2d.hip: the same elimination of an element stream, and the factor record of every cell into d_fact[ncells][fused_fact_doubles(n)]
+hipError_t launch_poisson2d_fused_fact(const double* d_coef, const double* d_M, double* d_out, int32_t* d_info, int n, long long ncells,
+                                       hipStream_t stream, double* d_fact);
+// fused2d_subst.hip: correctors d_corr[ncells][2][n n] (dof = i + n j, mean-free) by substitution on the factor records, one wave per cell
+hipError_t launch_fused2d_subst(const double* d_fact, double* d_corr, int n, long long ncells, hipStream_t stream);
+
 // assembly.hip: coef[cell][el][comp] of a separable coefficient (AFFINE / RECIPROCAL; params[cell][comp] = (a, b)) expanded into the element stream
 hipError_t launch_expand_separable(CoefSource src, const double* d_params, double* d_coef, long long n_el, int n_comp, long long ncells,
                                    hipStream_t stream);
@@ -121,6 +136,8 @@ int blocked_reserve(BlockedWorkspace* ws, long long n_cells);
 // blocked_solve takes for effective tensors
 const char* blocked_route_name(const BlockedWorkspace* ws);
 const char* blocked_route_detail(BlockedWorkspace* ws);
+// the route blocked_solve takes when correctors are asked for: the tree route's name where they stay on it, else "blocked"
+const char* blocked_corrector_route_name(const BlockedWorkspace* ws);
 // dense flops one micro-cell solve executes on this route, by the route's own model (multifrontal: sum over the fronts of
 // s^3 + 2 s^2 r + s r^2 on the padded sizes; plane elimination: (6 (n - 1) + 2) b^3)
 double blocked_flops_per_cell(const BlockedWorkspace* ws);

@@ -64,7 +64,10 @@ extern "C" {
  *                          instead of the one-wave-per-cell register kernel; for 48 < b <= 64 it sets that kernel's wave count
  *                          (2 / 4 / 8, default 8)
  *   HOMMX_RECON_MEM_MB     correctors hommx_reconstruct_batch[_device] holds on the device at once, in MB (default 1024): the batch runs in
- *                          chunks of that many cells' correctors                                                              */
+ *                          chunks of that many cells' correctors; a fused 2D plan's factor records (HOMMX_FUSED_CORR) count with them
+ *   HOMMX_FUSED_CORR       0: the correctors of a fused 2D plan come from the plane elimination of the blocked family (a blocked workspace
+ *                          on first use).  Default: substitution on the block inverses of the fused kernel itself (k_poisson2d_fused<NB, true>
+ *                          keeps them, k_fused2d_subst substitutes): two launches per chunk                                    */
 
 typedef struct hommx_plan hommx_plan;
 
@@ -96,7 +99,7 @@ int hommx_plan_reserve(hommx_plan* plan, int64_t n_cells);
  * t = size of the effective tensor (d for Poisson, d(d+1)/2 for elasticity), the descriptor fields, and the name of the
  * kernel route the plan's effective-tensor solves take: "fused2d" (2D scalar Poisson, n <= 32), "small_wave" (plane block
  * b <= 48: one wavefront per cell), "small_fused" (3D meshes with 48 < b <= 64: LDS), "multifrontal" (plane blocks b > 64 and 2D meshes with b > 48, e.g. 3D elasticity
- * from 5^3 micro cells: nested dissection, batched fronts) or "blocked" (everything else: plane elimination; also the corrector entry point of plans whose tensors take a one-launch route);
+ * from 5^3 micro cells: nested dissection, batched fronts) or "blocked" (everything else: plane elimination; also the corrector entry point of the small-block plans, see hommx_plan_corrector_kernel_name);
  * mesh plans: "mesh_front" or "mesh_multifrontal". */
 int32_t hommx_plan_dim(const hommx_plan* plan);
 int32_t hommx_plan_device(const hommx_plan* plan);
@@ -106,6 +109,10 @@ int64_t hommx_plan_num_elements(const hommx_plan* plan);
 int32_t hommx_plan_coef_components(const hommx_plan* plan);
 int32_t hommx_plan_tensor_size(const hommx_plan* plan);
 const char* hommx_plan_kernel_name(const hommx_plan* plan);
+/* The route the plan's corrector and reconstruction calls take: "fused2d_subst" (fused 2D plans; "blocked" with HOMMX_FUSED_CORR=0),
+ * "multifrontal" / "mesh_multifrontal" (nested-dissection plans; "blocked" with HOMMX_MF_CORR=0 on a structured one), "mesh_front"
+ * (frontal mesh plans), "blocked" (every other plan: plane elimination). */
+const char* hommx_plan_corrector_kernel_name(const hommx_plan* plan);
 /* One line describing what that route launches for THIS plan (kernel names with their tile sizes, tree shape of the nested dissection,
  * stage size, streams): for reports -- bench.py's roofline.kernel label is this string, so it cannot drift from the code. */
 const char* hommx_plan_route_detail(hommx_plan* plan);
@@ -189,8 +196,10 @@ int hommx_solve_batch_separable_device(hommx_plan* plan, int64_t n_cells, int32_
  * (hmm.py:1211-1213, 1239-1240), for the canonical loads instead of the nb macro basis functions: the corrector of a
  * macro basis function is the linear combination  eps * sum_m (grad phi_i)_m chi_m  (SURVEY A.2, row A5).
  * Route: plans whose tensors take the nested-dissection route get the correctors by back substitution down the same elimination tree
- * (a second plan of that tree whose fronts all stay resident; HOMMX_MF_CORR=0: plane elimination); every other plan runs the plane
- * elimination of the blocked family here (the one-launch kernels and the fused 2D kernel never form the factors). */
+ * (a second plan of that tree whose fronts all stay resident; HOMMX_MF_CORR=0: plane elimination); a fused 2D plan runs its elimination
+ * once more with the block inverses kept and substitutes on them (k_fused2d_subst; HOMMX_FUSED_CORR=0: plane elimination), in chunks of
+ * HOMMX_RECON_MEM_MB of factor records and correctors; every other plan runs the plane elimination of the blocked family here (the
+ * one-launch kernels never form the factors).  hommx_plan_corrector_kernel_name names the route. */
 int hommx_solve_batch_correctors(hommx_plan* plan, int64_t n_cells, const double* coef, const double* M,
                                  double* A_eff, double* correctors, int32_t* info);
 
@@ -209,9 +218,9 @@ int hommx_solve_batch_correctors(hommx_plan* plan, int64_t n_cells, const double
  *   coef, M          as hommx_solve_batch                      strain, flux  [n_cells][n_el][t] or both NULL: per-element fields
  *   xi               [n_cells][t]                              A_eff, info   as hommx_solve_batch, or NULL
  *   stats            [n_cells][HOMMX_RECON_NSTATS(t)], required
- * Every plan: the structured routes (a fused 2D plan gets the corrector workspace of the blocked family on first use, as
- * hommx_solve_batch_correctors) and both mesh routes.  The batch runs in chunks: the correctors of one chunk (HOMMX_RECON_MEM_MB) live in
- * plan-owned scratch, never the whole batch's; the host entry also streams coef in and the outputs out chunk by chunk.
+ * Every plan: the structured routes (a fused 2D plan forms the correctors from its own factors, as
+ * hommx_solve_batch_correctors) and both mesh routes.  The batch runs in chunks: the correctors of one chunk, with the factor records of a
+ * fused 2D plan (HOMMX_RECON_MEM_MB), live in plan-owned scratch, never the whole batch's; the host entry also streams coef in and the outputs out chunk by chunk.
  */
 #define HOMMX_RECON_NSTATS(t) (2 * (t) + 3) /* [mean_strain(t) | mean_flux(t) | energy | max_flux | argmax_element] */
 int hommx_reconstruct_batch(hommx_plan* plan, int64_t n_cells, const double* coef, const double* M, const double* xi, double* stats,

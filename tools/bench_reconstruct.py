@@ -1,6 +1,7 @@
 """Cost split of the HMM reconstruction (hommx_reconstruct_batch_device): the corrector solve against the reconstruction
 kernel k_recon, on the C2 shape (8,192 cells, 32^2 scalar Poisson, inclusion element stream) and the C4 shape (256 cells, 16^3 isotropic
-elasticity, fibre element stream).
+elasticity, fibre element stream); the C2 shape at 8^2 as well (the NB = 16 kernels of the fused family).  `corrector_kernel` in the JSON
+is the route the corrector solve took (hommx_plan_corrector_kernel_name; HOMMX_FUSED_CORR=0 / HOMMX_MF_CORR=0 for the A/B runs).
 
     python tools/bench_reconstruct.py [--reps 7] [--out profiles/recon_bench.json]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python tools/bench_reconstruct.py --reps 3 --no-json
@@ -37,9 +38,11 @@ def cases():
     from hommx_amd import workloads as W
 
     _, coef2, _ = W.c2_inclusion(nx=64, n=32)
+    _, coef2s, _ = W.c2_inclusion(nx=64, n=8)
     _, mask, values, _ = W.c4_two_phase(cells=np.arange(256))
     coef4 = values[:, mask.astype(int), :]
     return [("C2: 8192 cells, 32^2 Poisson", 2, 32, "poisson", coef2, "k_recon<2, 0, false"),
+            ("C2 at 8^2: 8192 cells, 8^2 Poisson", 2, 8, "poisson", coef2s, "k_recon<2, 0, false"),  # the NB = 16 kernels of the fused family
             ("C4: 256 cells, 16^3 elasticity", 3, 16, "elasticity", coef4, "k_recon<3, 2, false")]
 
 
@@ -64,13 +67,15 @@ def median_time(fn, reps):
     return float(np.median(ts))
 
 
-def measure(reps):
+def measure(reps, only=None):
     import torch
 
     from hommx_amd import MicroCellPlan
 
     out = []
     for name, dim, n, kind, coef, kname in cases():
+        if only and only not in name:
+            continue
         p = MicroCellPlan(dim, n, kind)
         nc = coef.shape[0]
         t = p.t
@@ -90,7 +95,7 @@ def measure(reps):
         t_fields = median_time(lambda: p.reconstruct_device(nc, dc.data_ptr(), None, dx.data_ptr(), st.data_ptr(), fs.data_ptr(),
                                                             fq.data_ptr(), A.data_ptr(), info.data_ptr(), s), reps)
         assert int((info != 0).sum()) == 0
-        out.append({"case": name, "cells": nc, "kernel_route": p.kernel, "correctors_host_s": t_corr,
+        out.append({"case": name, "cells": nc, "kernel_route": p.kernel, "corrector_kernel": p.corrector_kernel, "correctors_host_s": t_corr,
                     "reconstruct_stats_s": t_stats, "reconstruct_fields_s": t_fields,
                     "alg_bytes_per_cell_stats": bytes_per_cell(p, False), "alg_bytes_per_cell_fields": bytes_per_cell(p, True),
                     "kernel_name_prefix": kname})
@@ -131,7 +136,8 @@ def measure_source(reps, regions):
     if regions:
         legs["reconstruct_source_two_phase_regions"] = lambda: p.reconstruct(stream, xi, regions=True)
         legs["poisson_hmm_reconstruct_regions"] = lambda: h.reconstruct(u, regions=True)
-    out = {"case": "C2: 8192 cells, 32^2 Poisson, TwoPhase inclusion", "cells": int(coef.shape[0]), "kernel_route": p.kernel}
+    out = {"case": "C2: 8192 cells, 32^2 Poisson, TwoPhase inclusion", "cells": int(coef.shape[0]), "kernel_route": p.kernel,
+           "corrector_kernel": p.corrector_kernel}
     for name, fn in legs.items():
         out[name] = spread(fn, reps)
         print(f"{name}: median {out[name]['median_s'] * 1e3:.1f} ms (min {out[name]['min_s'] * 1e3:.1f}, max {out[name]['max_s'] * 1e3:.1f})", flush=True)
@@ -160,6 +166,8 @@ def main():
     ap.add_argument("--out", default="profiles/recon_bench.json")
     ap.add_argument("--no-json", action="store_true")
     ap.add_argument("--merge-kernel-stats", default=None)
+    ap.add_argument("--case", default=None, help="only the cases whose name contains this (the two C2 shapes share one k_recon instantiation: "
+                    "profile them in runs of their own before --merge-kernel-stats)")
     ap.add_argument("--form", choices=["sampled", "two_phase"], default="sampled")
     ap.add_argument("--regions", action="store_true", help="with --form two_phase: the legs with the two phases as regions as well")
     a = ap.parse_args()
@@ -172,7 +180,7 @@ def main():
         doc["kernel_stats_source"] = "rocprofv3 --kernel-trace --stats (separate run, AverageNs per instantiation)"
     else:
         doc = {"tool": "tools/bench_reconstruct.py", "reps": a.reps, "statistic": "median wall time after one warm-up call",
-               "hbm_spec_Bps": HBM_SPEC, "hbm_copy_Bps": HBM_COPY, "results": measure(a.reps)}
+               "hbm_spec_Bps": HBM_SPEC, "hbm_copy_Bps": HBM_COPY, "results": measure(a.reps, a.case)}
     if not a.no_json:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         json.dump(doc, open(a.out, "w"), indent=1)
