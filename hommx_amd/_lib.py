@@ -24,6 +24,7 @@ COEF_SAMPLED = 0  # HOMMX_COEF_*: the form of a hommx_coef_source
 COEF_TWO_PHASE = 1
 COEF_SEPARABLE = 2
 RECON_MAX_REGIONS = 8  # HOMMX_RECON_MAX_REGIONS
+SENS_MAX_DIRS = 8  # HOMMX_SENS_MAX_DIRS
 
 
 class PlanDesc(C.Structure):
@@ -69,6 +70,21 @@ class CoefSource(C.Structure):
     ]
 
 
+class SensArgs(C.Structure):
+    """hommx_sens_args: what hommx_sensitivity_source[_device] is asked for and where it goes."""
+
+    _fields_ = [
+        ("n_dirs", C.c_int32),
+        ("per_cell", C.c_int32),
+        ("dirs", C.c_void_p),
+        ("dA", C.c_void_p),
+        ("weights", C.c_void_p),
+        ("grad", C.c_void_p),
+        ("A_eff", C.c_void_p),
+        ("info", C.c_void_p),
+    ]
+
+
 def _prototypes() -> dict:
     """name -> (restype, argtypes) of every symbol include/hommx_hip.h declares: ``load()`` declares them from this table, and
     the tests check that the header and the library export exactly these names."""
@@ -102,6 +118,8 @@ def _prototypes() -> dict:
         "hommx_reconstruct_batch_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_reconstruct_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_reconstruct_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "hommx_sensitivity_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SensArgs)]),
+        "hommx_sensitivity_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SensArgs), vp]),
         "hommx_solve_batch_two_phase": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_two_phase_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_separable": (c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),

@@ -123,6 +123,23 @@ class Reconstruction:
         return r
 
 
+@dataclass
+class Sensitivities:
+    """Derivatives of A_H of macro cells with respect to the micro coefficient (include/hommx_hip.h, hommx_sensitivity_source).
+
+    ``dA[N, n_dirs, t, t]``: the derivative of A_H along every direction (a perturbation of the element stream), symmetric in its last two
+    axes; ``grad[N, n_el(, n_comp)]`` or None: the per-element gradient of ``weights : A_H``, shaped like the coefficient, with
+    sum grad * dir = weights : dA[dir]; ``A_eff[N, t, t]`` and ``info[N]`` as ``solve`` returns them.  ``names`` / ``cells``: what the
+    directions are called and the macro cells (``BaseHMM.tensor_derivatives``)."""
+
+    dA: np.ndarray
+    grad: np.ndarray | None
+    A_eff: np.ndarray
+    info: np.ndarray
+    names: tuple | None = None
+    cells: np.ndarray | None = None
+
+
 REGION_FIELDS = ("region_volume", "region_mean_strain", "region_mean_flux", "region_energy", "region_max_flux", "region_argmax_element")
 
 
@@ -386,6 +403,45 @@ class MicroCellPlan:
             rstats.ctypes.data if nr else None, sp, fp, o, i))
         return Reconstruction.from_stats(xi, stats, A, info, strain, flux, region_stats=rstats)
 
+    def sensitivities(self, coef, M: np.ndarray | None = None, directions=None, per_cell: bool = False, weights=None) -> Sensitivities:
+        """Derivatives of A_H with respect to the micro coefficient (hommx_sensitivity_source): ``coef`` an array or a ``CoefStream`` and M
+        as ``reconstruct`` takes them.  ``directions[n_dirs, n_el(, n_comp)]`` (shared by all cells) or, with ``per_cell``,
+        ``directions[N_c, n_dirs, n_el(, n_comp)]``: up to 8 perturbations of one cell's element stream -> ``dA[N_c, n_dirs, t, t]`` =
+        sum_K |K| s^m_K . material(dir_K) s^n_K, the derivative of A_H along each (the direction ``coef`` itself gives A_eff).
+        ``weights[N_c, t, t]`` -> ``grad[N_c, n_el(, n_comp)]``, the gradient of weights : A_H with respect to every coefficient entry.
+        At least one of the two.  The correctors never leave the device; the batch runs in the chunks of ``reconstruct``."""
+        stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
+        nc = self._check_stream(stream)
+        el = (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
+        nd, dirs = 0, None
+        if directions is not None:
+            dirs = np.ascontiguousarray(directions, dtype=np.float64)
+            lead = ((nc,) if per_cell else ())
+            nd = dirs.shape[len(lead)] if dirs.ndim == len(lead) + 1 + len(el) else -1
+            if nd < 0 or dirs.shape != lead + (nd,) + el:
+                raise ValueError(f"directions has shape {dirs.shape}; expected {lead + ('n_dirs',) + el}")
+            if not 1 <= nd <= _lib.SENS_MAX_DIRS:
+                raise ValueError(f"n_dirs must be 1 .. {_lib.SENS_MAX_DIRS}; got {nd}")
+        grad = None
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64)
+            if weights.shape != (nc, self.t, self.t):
+                raise ValueError(f"weights has shape {weights.shape}; expected ({nc}, {self.t}, {self.t})")
+            grad = np.empty((nc,) + el, dtype=np.float64)
+        elif nd == 0:
+            raise ValueError("nothing requested: pass directions, weights or both")
+        dA = np.empty((nc, nd, self.t, self.t), dtype=np.float64)
+        src = stream.coef_source()
+        args = _lib.SensArgs(nd, int(bool(per_cell)), dirs.ctypes.data if nd else None, dA.ctypes.data if nd else None,
+                             None if grad is None else weights.ctypes.data, None if grad is None else grad.ctypes.data)
+
+        def call(Mp, o, i):
+            args.A_eff, args.info = o, i
+            return self._lib.hommx_sensitivity_source(self._h, nc, C.byref(src), Mp, C.byref(args))
+
+        A, info = self._host_call("hommx_sensitivity_source", nc, M, call)
+        return Sensitivities(dA, grad, A, info)
+
     def solve_two_phase(self, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None = None,
                         return_info: bool = False):
         """Two-phase media sampled on the device: mask[n_el] (bool / uint8, phase of every micro element) and
@@ -444,6 +500,17 @@ class MicroCellPlan:
                                                       flux_ptr or None, A_ptr or None, info_ptr or None, stream or None),
             "hommx_reconstruct_source_device",
         )
+
+    def sensitivities_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, n_dirs: int = 0, dirs_ptr: int | None = None,
+                             per_cell: bool = False, dA_ptr: int | None = None, weights_ptr: int | None = None, grad_ptr: int | None = None,
+                             A_ptr: int | None = None, info_ptr: int | None = None, stream: int | None = None):
+        """Device-pointer form of ``sensitivities`` (hommx_sensitivity_source_device), asynchronous on ``stream``: ``source`` =
+        ``CoefStream.coef_source(upload)`` with device addresses; dirs[n_dirs, n_el, n_comp] or, ``per_cell``, [n_cells, n_dirs, n_el, n_comp]
+        -> dA[n_cells, n_dirs, t, t]; weights[n_cells, t, t] -> grad[n_cells, n_el, n_comp]."""
+        args = _lib.SensArgs(int(n_dirs), int(bool(per_cell)), dirs_ptr or None, dA_ptr or None, weights_ptr or None, grad_ptr or None,
+                             A_ptr or None, info_ptr or None)
+        _lib.check(self._lib.hommx_sensitivity_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
+                   "hommx_sensitivity_source_device")
 
     def solve_separable_device(self, n_cells: int, family: str, n_q: int, table_ptr: int, weights_ptr: int | None, params_ptr: int,
                                M_ptr: int | None, out_ptr: int, info_ptr: int | None, stream: int | None = None):

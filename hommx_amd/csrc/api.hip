@@ -698,21 +698,25 @@ struct ReconRegions {
   const uint8_t* label = nullptr;
 };
 
-// one chunk of at most recon_chunk() cells on the device: the correctors into the plan's scratch, then k_recon
-int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const ReconIO& io, ReconRegions rg, hipStream_t st) {
+// The correctors of one chunk (nc of at most `chunk` cells) through the plan's route into its scratch, with room for `slots` more vectors
+// of ndof per cell behind them; A_eff into *d_A_eff or, if that is null, into the plan's own array (*d_A_eff then names it)
+int chunk_correctors(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_coef, const double* d_M, double** d_A_eff, int32_t* d_info,
+                     int slots, hipStream_t st, double** corr) {
   const int t = p->ks.t;
-  const long long nd = plan_ndof(p);
-  const bool lds = recon_in_lds(p);
-  if (int rc = grow(p->buf[B_RCORR], sizeof(double) * chunk * nd * (t + (lds ? 0 : 1)))) return rc;
-  double* d_A_eff = io.A_eff;
-  if (!d_A_eff) {
+  if (int rc = grow(p->buf[B_RCORR], sizeof(double) * chunk * plan_ndof(p) * (t + slots))) return rc;
+  if (!*d_A_eff) {
     if (int rc = grow(p->buf[B_RA], sizeof(double) * chunk * t * t)) return rc;
-    d_A_eff = static_cast<double*>(p->buf[B_RA].p);
+    *d_A_eff = static_cast<double*>(p->buf[B_RA].p);
   }
-  double* corr = static_cast<double*>(p->buf[B_RCORR].p);
-  if (int rc = route_solve(p, nc, io.coef, io.M, d_A_eff, io.info, st, corr)) return rc;
-  hommx::ReconArgs a;
-  a.ndof = nd;
+  *corr = static_cast<double*>(p->buf[B_RCORR].p);
+  return route_solve(p, nc, d_coef, d_M, *d_A_eff, d_info, st, *corr);
+}
+
+// the element geometry of the plan in the arguments of a kernel that walks the elements (ReconArgs, SensArgs): structured plans
+// compute it, mesh plans read the plan's geometry block
+template <typename Args>
+void set_geometry(const hommx_plan* p, Args& a) {
+  a.ndof = plan_ndof(p);
   a.n_el = p->n_el;
   if (p->desc.n_micro) {
     const double n = p->desc.n_micro;
@@ -723,6 +727,15 @@ int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const ReconIO& io, Recon
     a.grads = p->geo.grads;
     a.vol = p->geo.vol;
   }
+}
+
+// one chunk of at most recon_chunk() cells on the device: the correctors into the plan's scratch, then k_recon
+int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const ReconIO& io, ReconRegions rg, hipStream_t st) {
+  const bool lds = recon_in_lds(p);
+  double *d_A_eff = io.A_eff, *corr = nullptr;
+  if (int rc = chunk_correctors(p, nc, chunk, io.coef, io.M, &d_A_eff, io.info, lds ? 0 : 1, st, &corr)) return rc;
+  hommx::ReconArgs a;
+  set_geometry(p, a);
   a.corr = corr;
   a.coef = io.coef;
   a.M = io.M;
@@ -730,7 +743,7 @@ int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const ReconIO& io, Recon
   a.stats = io.stats;
   a.strain = io.strain;
   a.flux = io.flux;
-  a.slot = lds ? nullptr : corr + chunk * t * nd;
+  a.slot = lds ? nullptr : corr + chunk * p->ks.t * a.ndof;
   a.n_regions = rg.n;
   a.region = rg.label;
   a.region_stats = io.region_stats;
@@ -763,18 +776,19 @@ int recon_open(hommx_plan* p, int64_t n_cells, const void* coef, const void* xi,
   return recon_open(p, n_cells, coef, xi, stats, strain, flux, device, [] { return HOMMX_OK; });
 }
 
-// The chunk loop of the four reconstruct entry points.  `s` holds device pointers (a host entry stages its sampled stream per chunk: s.coef is null then).  Per chunk
-// of cells [c0, c0 + nc): in(c0, nc, io) fills io, bringing in what a host entry stages per chunk (its sampled stream among it);
-// expand_chunk gives the element stream of every other source; recon_run; out(c0, nc, io) takes the outputs away (host entries).
-template <typename In, typename Out>
-int recon_chunks(hommx_plan* p, int64_t n_cells, int64_t chunk, const hommx_coef_source& s, ReconRegions rg, hipStream_t st, In in, Out out) {
+// The chunk loop of the reconstruct and sensitivity entry points.  `s` holds device pointers (a host entry stages its sampled stream per
+// chunk: s.coef is null then).  Per chunk of cells [c0, c0 + nc): in(c0, nc, io) fills io (a ReconIO or a SensIO), bringing in what a host
+// entry stages per chunk (its sampled stream among it); expand_chunk gives the element stream of every other source; run(nc, io):
+// the correctors and the kernel; out(c0, nc, io) takes the outputs away (host entries).
+template <typename IO, typename In, typename Run, typename Out>
+int source_chunks(hommx_plan* p, int64_t n_cells, int64_t chunk, const hommx_coef_source& s, hipStream_t st, In in, Run run, Out out) {
   for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
     const int64_t nc = std::min(chunk, n_cells - c0);
-    ReconIO io{};
+    IO io{};
     if (int rc = in(c0, nc, io)) return rc;
     if (!io.coef)
       if (int rc = expand_chunk(p, s, c0, nc, st, &io.coef)) return rc;
-    if (int rc = recon_run(p, nc, chunk, io, rg, st)) return rc;
+    if (int rc = run(nc, io)) return rc;
     if (int rc = out(c0, nc, io)) return rc;
   }
   return HOMMX_OK;
@@ -786,8 +800,8 @@ int recon_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, con
   const int d = p->desc.dim, t = p->ks.t, ns = HOMMX_RECON_NSTATS(t), nr = rg.n * HOMMX_RECON_NREGION(t);
   int64_t chunk = 0;
   if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, 0), &chunk)) return rc;
-  return recon_chunks(
-      p, n_cells, chunk, s, rg, st,
+  return source_chunks<ReconIO>(
+      p, n_cells, chunk, s, st,
       [&](int64_t c0, int64_t, ReconIO& io) {
         const int64_t fo = c0 * p->n_el * t;
         io = ReconIO{nullptr,
@@ -801,6 +815,7 @@ int recon_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, con
                      d_info ? d_info + c0 : nullptr};
         return HOMMX_OK;
       },
+      [&](int64_t nc, const ReconIO& io) { return recon_run(p, nc, chunk, io, rg, st); },
       [](int64_t, int64_t, const ReconIO&) { return HOMMX_OK; });
 }
 
@@ -830,8 +845,8 @@ int recon_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const
   auto f64 = [](char* at) { return reinterpret_cast<double*>(at); };
   const ReconIO dev{f64(in[0]), f64(in[1]), f64(in[2]), f64(out[0]), f64(out[4]), f64(out[2]), f64(out[3]), f64(out[1]),
                     reinterpret_cast<int32_t*>(out[5])};
-  return recon_chunks(
-      p, n_cells, chunk, ds, rg, nullptr,
+  return source_chunks<ReconIO>(
+      p, n_cells, chunk, ds, nullptr,
       [&](int64_t c0, int64_t nc, ReconIO& io) {
         if (per) HIP_TRY(hipMemcpy(in[0], s.coef + c0 * per, sizeof(double) * nc * per, hipMemcpyHostToDevice));
         if (M) HIP_TRY(hipMemcpy(in[1], M + c0 * d * d, sizeof(double) * nc * d * d, hipMemcpyHostToDevice));
@@ -839,6 +854,7 @@ int recon_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const
         io = dev;
         return HOMMX_OK;
       },
+      [&](int64_t nc, const ReconIO& io) { return recon_run(p, nc, chunk, io, rg, nullptr); },
       [&](int64_t c0, int64_t nc, const ReconIO& io) {
         HIP_TRY(hipMemcpy(stats + c0 * ns, io.stats, sizeof(double) * nc * ns, hipMemcpyDeviceToHost));
         if (A_eff) HIP_TRY(hipMemcpy(A_eff + c0 * t * t, io.A_eff, sizeof(double) * nc * t * t, hipMemcpyDeviceToHost));
@@ -848,6 +864,120 @@ int recon_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const
           HIP_TRY(hipMemcpy(flux + c0 * field, io.flux, sizeof(double) * nc * field, hipMemcpyDeviceToHost));
         }
         if (n_regions) HIP_TRY(hipMemcpy(region_stats + c0 * nr, io.region_stats, sizeof(double) * nc * nr, hipMemcpyDeviceToHost));
+        return HOMMX_OK;
+      });
+}
+
+// -- sensitivities (hommx_sensitivity_source[_device]) -----------------------------------------------------------------------------------
+// device pointers of one chunk
+struct SensIO {
+  const double *coef, *M, *dirs, *weights;
+  double *dA, *grad, *A_eff;
+  int32_t* info;
+};
+
+// the argument checks of both entry points, then a route that forms correctors
+int sens_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_sens_args* a, bool device) {
+  auto more = [&] {
+    if (int rc = coef_check(p, src)) return rc;
+    if (!a) return fail(HOMMX_EINVAL, "null arguments");
+    if (a->n_dirs < 0 || a->n_dirs > HOMMX_SENS_MAX_DIRS)
+      return fail(HOMMX_EINVAL, "n_dirs must be 0 .. %d, got %d", HOMMX_SENS_MAX_DIRS, a->n_dirs);
+    if (a->n_dirs > 0 && !(a->dirs && a->dA)) return fail(HOMMX_EINVAL, "n_dirs > 0 needs both dirs and dA");
+    if (!a->weights != !a->grad) return fail(HOMMX_EINVAL, "weights and grad: both or neither");
+    if (a->n_dirs == 0 && !a->grad) return fail(HOMMX_EINVAL, "nothing requested: neither directions nor a gradient");
+    return HOMMX_OK;
+  };
+  if (int rc = open_call(p, n_cells, true, "", device, more); rc != GO) return rc;
+  if (int rc = corrector_workspace(p)) return rc;
+  return GO;
+}
+
+// one chunk of at most recon_chunk() cells on the device: the correctors into the plan's scratch, then k_sens
+int sens_run(hommx_plan* p, int64_t nc, int64_t chunk, const SensIO& io, const hommx_sens_args& a, hipStream_t st) {
+  double *d_A_eff = io.A_eff, *corr = nullptr;
+  if (int rc = chunk_correctors(p, nc, chunk, io.coef, io.M, &d_A_eff, io.info, 0, st, &corr)) return rc;
+  hommx::SensArgs k;
+  set_geometry(p, k);
+  k.corr = corr;
+  k.M = io.M;
+  k.n_dirs = a.n_dirs;
+  k.per_cell = a.per_cell != 0;
+  k.dirs = io.dirs;
+  k.dA = io.dA;
+  k.weights = io.weights;
+  k.grad = io.grad;
+  HIP_TRY(hommx::launch_sensitivity(k, p->desc.dim, p->desc.kind, p->desc.n_micro == 0, nc, st));
+  return HOMMX_OK;
+}
+
+// everything on the device already: the chunks are views of the caller's arrays
+int sens_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, const hommx_sens_args& a, hipStream_t st) {
+  const int d = p->desc.dim, tt = p->ks.t * p->ks.t;
+  const int64_t per = p->n_el * p->ks.n_comp;
+  int64_t chunk = 0;
+  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, 0), &chunk)) return rc;
+  return source_chunks<SensIO>(
+      p, n_cells, chunk, s, st,
+      [&](int64_t c0, int64_t, SensIO& io) {
+        io = SensIO{nullptr,
+                    d_M ? d_M + c0 * d * d : nullptr,
+                    a.n_dirs && a.per_cell ? a.dirs + c0 * a.n_dirs * per : a.dirs,
+                    a.weights ? a.weights + c0 * tt : nullptr,
+                    a.n_dirs ? a.dA + c0 * a.n_dirs * tt : nullptr,
+                    a.grad ? a.grad + c0 * per : nullptr,
+                    a.A_eff ? a.A_eff + c0 * tt : nullptr,
+                    a.info ? a.info + c0 : nullptr};
+        return HOMMX_OK;
+      },
+      [&](int64_t nc, const SensIO& io) { return sens_run(p, nc, chunk, io, a, st); },
+      [](int64_t, int64_t, const SensIO&) { return HOMMX_OK; });
+}
+
+// host pointers.  What every cell shares (mask, table, weights of the sampler, shared directions) and the per-cell values of a sampler
+// form travel once, in the plan's pinned block (stage_source); a sampled stream, M, per-cell directions and the weights stream in and
+// every output streams out chunk by chunk, so device memory is bounded by the chunk
+int sens_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_sens_args& a) {
+  const int d = p->desc.dim, tt = p->ks.t * p->ks.t;
+  const int64_t el = p->n_el * p->ks.n_comp, per = s.form == HOMMX_COEF_SAMPLED ? el : 0;
+  const bool per_cell = a.n_dirs && a.per_cell;
+  hommx_coef_source ds;
+  const double* d_shared = nullptr;
+  const hommx::HostPiece shared{per_cell ? nullptr : a.dirs, sizeof(double) * a.n_dirs * el, (const void**)&d_shared};
+  if (int rc = stage_source(p, n_cells, s, shared, &ds)) return rc;
+  // doubles per cell of the plan's blocks: in = [coef | M | dirs | weights], out = [dA | A_eff | grad], and info
+  const int64_t n_in[] = {per, M ? d * d : 0, per_cell ? a.n_dirs * el : 0, a.grad ? tt : 0}, n_out[] = {a.n_dirs * tt, tt, a.grad ? el : 0};
+  size_t cell = sizeof(int32_t);
+  for (int64_t k : n_in) cell += sizeof(double) * k;
+  for (int64_t k : n_out) cell += sizeof(double) * k;
+  int64_t chunk = 0;
+  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, cell), &chunk)) return rc;
+  size_t in_bytes[4], out_bytes[4];
+  for (int k = 0; k < 4; ++k) in_bytes[k] = sizeof(double) * chunk * n_in[k];
+  for (int k = 0; k < 3; ++k) out_bytes[k] = sizeof(double) * chunk * n_out[k];
+  out_bytes[3] = sizeof(int32_t) * chunk;
+  char *in[4], *out[4];
+  if (int rc = carve(p->buf[B_IN], in_bytes, in)) return rc;
+  if (int rc = carve(p->buf[B_OUT], out_bytes, out)) return rc;
+  auto f64 = [](char* at) { return reinterpret_cast<double*>(at); };
+  const SensIO dev{f64(in[0]), f64(in[1]), per_cell ? f64(in[2]) : d_shared, f64(in[3]), f64(out[0]), f64(out[2]), f64(out[1]),
+                   reinterpret_cast<int32_t*>(out[3])};
+  const double* src_in[] = {s.coef, M, a.dirs, a.weights};
+  return source_chunks<SensIO>(
+      p, n_cells, chunk, ds, nullptr,
+      [&](int64_t c0, int64_t nc, SensIO& io) {
+        for (int k = 0; k < 4; ++k)
+          if (n_in[k]) HIP_TRY(hipMemcpy(in[k], src_in[k] + c0 * n_in[k], sizeof(double) * nc * n_in[k], hipMemcpyHostToDevice));
+        io = dev;
+        return HOMMX_OK;
+      },
+      [&](int64_t nc, const SensIO& io) { return sens_run(p, nc, chunk, io, a, nullptr); },
+      [&](int64_t c0, int64_t nc, const SensIO& io) {
+        double* dst_out[] = {a.dA, a.A_eff, a.grad};
+        for (int k = 0; k < 3; ++k)
+          if (n_out[k] && dst_out[k])
+            HIP_TRY(hipMemcpy(dst_out[k] + c0 * n_out[k], out[k], sizeof(double) * nc * n_out[k], hipMemcpyDeviceToHost));
+        if (a.info) HIP_TRY(hipMemcpy(a.info + c0, io.info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
         return HOMMX_OK;
       });
 }
@@ -891,6 +1021,17 @@ int hommx_reconstruct_source(hommx_plan* p, int64_t n_cells, const hommx_coef_so
   };
   if (int rc = recon_open(p, n_cells, src, xi, stats, strain, flux, false, more); rc != GO) return rc;
   return recon_host(p, n_cells, source_of_form(*src), M, xi, n_regions, region, stats, region_stats, strain, flux, A_eff, info);
+}
+
+int hommx_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const hommx_sens_args* args,
+                                    void* stream) {
+  if (int rc = sens_open(p, n_cells, src, args, true); rc != GO) return rc;
+  return sens_device(p, n_cells, source_of_form(*src), d_M, *args, reinterpret_cast<hipStream_t>(stream));
+}
+
+int hommx_sensitivity_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_sens_args* args) {
+  if (int rc = sens_open(p, n_cells, src, args, false); rc != GO) return rc;
+  return sens_host(p, n_cells, source_of_form(*src), M, *args);
 }
 
 int hommx_calibrate_fp64(int device, double* mfma_flops_per_s, double* fma_flops_per_s) {

@@ -118,6 +118,26 @@ struct ReconArgs {
 size_t recon_lds_limit();
 hipError_t launch_reconstruct(const ReconArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
 
+// sensitivity.hip: derivatives of A_H along coefficient directions and its per-element gradient, from the correctors of `nc` cells
+// (include/hommx_hip.h, hommx_sensitivity_source).  The geometry fields are those of ReconArgs
+struct SensArgs {
+  int n = 0;
+  double vol_struct = 0.0;
+  long long ndof = 0, n_el = 0;
+  const int32_t* el_nodes = nullptr;
+  const double* grads = nullptr;
+  const double* vol = nullptr;
+  const double* corr = nullptr;      // [nc][t][ndof]
+  const double* M = nullptr;         // [nc][d][d] or null
+  int n_dirs = 0;                    // 0 .. HOMMX_SENS_MAX_DIRS
+  bool per_cell = false;             // dirs[nc][n_dirs][n_el][n_comp] instead of dirs[n_dirs][n_el][n_comp]
+  const double* dirs = nullptr;
+  double* dA = nullptr;              // [nc][n_dirs][t][t]
+  const double* weights = nullptr;   // [nc][t][t], with grad[nc][n_el][n_comp]; or both null
+  double* grad = nullptr;
+};
+hipError_t launch_sensitivity(const SensArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
+
 // calibrate.hip: best sustained v_mfma_f64_16x16x4_f64 and v_fma_f64 rates over 2 and 4 waves per SIMD.
 hipError_t run_fp64_calibration(double* mfma_flops_per_s, double* fma_flops_per_s, double* mfma_lds_fed_flops_per_s = nullptr);
 

@@ -14,6 +14,7 @@
 
 #include "kernels.h"
 #include "mesh_elem.h"
+#include "struct_elem.h"
 
 namespace hommx {
 
@@ -22,17 +23,6 @@ namespace {
 constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxStats = 2 * 6 + 3;
-
-// Sub-simplices of a structured grid cell (hommx_amd/mesh.py: DiagonalType.right triangles, six tetrahedra around the v0-v7 diagonal):
-// corner offset of local vertex a and its P1 gradient on the unit-size cell (h = 1: multiply by n)
-__device__ constexpr int kOff2[2][3][2] = {{{0, 0}, {1, 0}, {1, 1}}, {{0, 0}, {0, 1}, {1, 1}}};
-__device__ constexpr int kGrad2[2][3][2] = {{{-1, 0}, {1, -1}, {0, 1}}, {{0, -1}, {-1, 1}, {1, 0}}};
-__device__ constexpr int kOff3[6][4][3] = {{{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {1, 1, 1}}, {{0, 0, 0}, {1, 0, 0}, {1, 1, 1}, {1, 0, 1}},
-                                           {{0, 0, 0}, {1, 0, 1}, {1, 1, 1}, {0, 0, 1}}, {{0, 0, 0}, {1, 1, 0}, {0, 1, 0}, {1, 1, 1}},
-                                           {{0, 0, 0}, {0, 1, 1}, {0, 0, 1}, {1, 1, 1}}, {{0, 0, 0}, {0, 1, 0}, {0, 1, 1}, {1, 1, 1}}};
-__device__ constexpr int kGrad3[6][4][3] = {{{-1, 0, 0}, {1, -1, 0}, {0, 1, -1}, {0, 0, 1}}, {{-1, 0, 0}, {1, 0, -1}, {0, 1, 0}, {0, -1, 1}},
-                                            {{0, 0, -1}, {1, -1, 0}, {0, 1, 0}, {-1, 0, 1}}, {{0, -1, 0}, {1, 0, -1}, {-1, 1, 0}, {0, 0, 1}},
-                                            {{0, 0, -1}, {-1, 1, 0}, {0, -1, 1}, {1, 0, 0}}, {{0, -1, 0}, {0, 1, -1}, {-1, 0, 1}, {1, 0, 0}}};
 
 // per-thread running statistics of the elements it visits (ascending element index)
 template <int T>

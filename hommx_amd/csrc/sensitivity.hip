@@ -1,0 +1,220 @@
+// sensitivity.hip -- derivatives of the effective tensor with respect to the micro coefficient.
+//
+// For macro cell c with canonical correctors chi_m, the strain of micro element K under the canonical load e_m is
+//   s^m_K = e_m + sum_a sum_alpha chi_m[p_a bs + alpha] strain(g_a, M, alpha)        (k_recon's s_K for xi = e_m)
+// and, the element operator being linear in the coefficient, for a perturbation dir of the element stream
+//   dA[c][d][m][n] = sum_K |K| s^m_K . material(dir_d[K]) s^n_K                      (no derivative of a corrector: the cell equation)
+//   grad[c][K][q]  = |K| sum_{m,n} w[c][m][n] s^m_K . material(e_q) s^n_K            (so that sum grad . dir = w : dA[dir])
+// The element formulas are those of the mesh routes (mesh_elem.h), the structured geometry that of the reconstruction (struct_elem.h).
+//
+// One workgroup per macro cell, elements on lanes.  The t correctors of a cell are gathered from global memory, every size the same
+// way: a node is shared by six (2D) to twenty-four (3D) elements of neighbouring lanes and steps, so the gathers are served by the
+// caches, and a 16^3 elasticity cell (590 KB of correctors) would not fit LDS anyway.  One pass over the elements per direction -- the
+// t (t + 1) / 2 running sums of eight directions do not fit the registers beside the t x t strains -- and one more for the gradient,
+// which has no reduction.  dA: element-strided partial sums per thread, a butterfly in each wave, the wave totals in order, the upper
+// triangle computed and mirrored: a cell's outputs do not depend on its batch position, the chunking or which outputs are asked for.
+// No atomics, no inline assembly.
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+#include "mesh_elem.h"
+#include "struct_elem.h"
+
+namespace hommx {
+
+namespace {
+
+constexpr int kThreads = 512;
+constexpr int kWaves = kThreads / 64;
+
+constexpr int tensor_size(int dim, int kind) { return kind_sizes(dim, kind).t; }
+
+// f(el, vol, vertex) for the elements of this thread, ascending: the element loops of k_recon.  vertex(a, node, g): the periodic node
+// and the P1 gradient of local vertex a, read (mesh plans) or computed (structured plans) when asked for
+template <int DIM, bool MESH, typename F>
+__device__ __forceinline__ void for_elements(const SensArgs& A, int tid, F&& f) {
+  if constexpr (MESH) {
+    for (long long el = tid; el < A.n_el; el += kThreads)
+      f(el, A.vol[el], [&](int a, int& node, double(&g)[DIM]) {
+        node = A.el_nodes[el * (DIM + 1) + a];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) g[k] = A.grads[(el * (DIM + 1) + a) * DIM + k];
+      });
+  } else {
+    // one grid cell (all its sub-simplices, element order n_sub (i + n j [+ n^2 k]) + s) per thread and step; the 3D loop stays rolled
+    constexpr int NSUB = DIM == 2 ? 2 : 6;
+    constexpr int UNROLL = DIM == 2 ? 2 : 1;
+    const int n = A.n;
+    const double hn = (double)n;
+    const long long ncube = A.n_el / NSUB;
+    for (long long cube = tid; cube < ncube; cube += kThreads) {
+      const int i = (int)(cube % n), j = (int)((cube / n) % n), k = DIM == 3 ? (int)(cube / ((long long)n * n)) : 0;
+#pragma unroll UNROLL
+      for (int s = 0; s < NSUB; ++s)
+        f(cube * NSUB + s, A.vol_struct, [&](int a, int& node, double(&g)[DIM]) { struct_vertex<DIM>(i, j, k, s, a, n, hn, node, g); });
+    }
+  }
+}
+
+// s[m] = s^m_K for the t canonical loads: the arithmetic of k_recon's element<>() on chi^xi = chi_m.  3D elasticity takes one vertex at
+// a time (a rolled loop): its 72 gathers in flight at once would not leave registers for the 36 strains and the running sums
+template <int DIM, int KIND, typename V>
+__device__ __forceinline__ void load_strains(const double* __restrict__ corr, long long ndof, V&& vertex, const double* Mc,
+                                             double (&s)[tensor_size(DIM, KIND)][tensor_size(DIM, KIND)]) {
+  constexpr KindSizes ks = kind_sizes(DIM, KIND);
+  constexpr int T = ks.t, BS = ks.bs, VERTS = T == 6 ? 1 : DIM + 1;
+#pragma unroll
+  for (int m = 0; m < T; ++m)
+#pragma unroll
+    for (int k = 0; k < T; ++k) s[m][k] = m == k ? 1.0 : 0.0;
+#pragma unroll VERTS
+  for (int a = 0; a < DIM + 1; ++a) {
+    int node;
+    double g[DIM];
+    vertex(a, node, g);
+#pragma unroll
+    for (int al = 0; al < BS; ++al) {
+      double sa[T];
+      strain<DIM, KIND>(g, Mc, al, sa);
+      const double* __restrict__ at = corr + (long long)node * BS + al;
+#pragma unroll
+      for (int m = 0; m < T; ++m) {
+        const double c = at[m * ndof];
+#pragma unroll
+        for (int k = 0; k < T; ++k) s[m][k] += c * sa[k];
+      }
+    }
+  }
+}
+
+template <int DIM, int KIND, bool MESH>
+__global__ __launch_bounds__(kThreads) void k_sens(SensArgs A) {
+  constexpr KindSizes ks = kind_sizes(DIM, KIND);
+  constexpr int T = ks.t, NCOMP = ks.n_comp;
+  constexpr int NSUM = T * (T + 1) / 2;  // dA[m][n], m <= n, at n (n + 1) / 2 + m
+  __shared__ double red[kWaves][NSUM];
+  const int tid = threadIdx.x;
+  const long long cell = blockIdx.x;
+  const double* corr = A.corr + cell * T * A.ndof;
+
+  // M, or the identity (exact: the same gradients as without M), as k_recon holds it
+  double Mp[DIM * DIM];
+#pragma unroll
+  for (int k = 0; k < DIM * DIM; ++k) Mp[k] = A.M ? A.M[cell * DIM * DIM + k] : (k % (DIM + 1) == 0 ? 1.0 : 0.0);
+
+  for (int d = 0; d < A.n_dirs; ++d) {
+    const double* dir = A.dirs + ((A.per_cell ? cell * A.n_dirs : 0) + d) * A.n_el * NCOMP;
+    double acc[NSUM];
+#pragma unroll
+    for (int q = 0; q < NSUM; ++q) acc[q] = 0.0;
+    for_elements<DIM, MESH>(A, tid, [&](long long el, double vol, auto vertex) {
+      double s[T][T], C[T][T];
+      load_strains<DIM, KIND>(corr, A.ndof, vertex, Mp, s);
+      material<DIM, KIND>(dir + el * NCOMP, C);
+#pragma unroll
+      for (int n = 0; n < T; ++n) {
+        double cs[T];  // material(dir_K) s^n
+#pragma unroll
+        for (int k = 0; k < T; ++k) {
+          double v = 0.0;
+#pragma unroll
+          for (int l = 0; l < T; ++l) v += C[k][l] * s[n][l];
+          cs[k] = v;
+        }
+#pragma unroll
+        for (int m = 0; m <= n; ++m) {
+          double v = 0.0;
+#pragma unroll
+          for (int k = 0; k < T; ++k) v += s[m][k] * cs[k];
+          acc[n * (n + 1) / 2 + m] += vol * v;
+        }
+      }
+    });
+
+    // fixed-order reduction: wave butterfly, then the wave totals in order
+#pragma unroll
+    for (int q = 0; q < NSUM; ++q)
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
+    if ((tid & 63) == 0) {
+#pragma unroll
+      for (int q = 0; q < NSUM; ++q) red[tid >> 6][q] = acc[q];
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double* out = A.dA + (cell * A.n_dirs + d) * T * T;
+#pragma unroll
+      for (int n = 0; n < T; ++n)
+#pragma unroll
+        for (int m = 0; m <= n; ++m) {
+          double v = red[0][n * (n + 1) / 2 + m];
+          for (int w = 1; w < kWaves; ++w) v += red[w][n * (n + 1) / 2 + m];
+          out[m * T + n] = out[n * T + m] = v;
+        }
+    }
+    __syncthreads();  // the next pass writes `red` again
+  }
+
+  if (A.grad) {
+    double w[T][T];  // uniform over the cell
+#pragma unroll
+    for (int m = 0; m < T; ++m)
+#pragma unroll
+      for (int n = 0; n < T; ++n) w[m][n] = A.weights[cell * T * T + m * T + n];
+    double* grad = A.grad + cell * A.n_el * NCOMP;
+    for_elements<DIM, MESH>(A, tid, [&](long long el, double vol, auto vertex) {
+      double s[T][T];
+      load_strains<DIM, KIND>(corr, A.ndof, vertex, Mp, s);
+      // P[k][l] + P[l][k] (k < l) and P[k][k] of P = sum_{m,n} w[m][n] s^m (x) s^n: all a symmetric material(e_q) reads of it
+      double P[NSUM];
+#pragma unroll
+      for (int q = 0; q < NSUM; ++q) P[q] = 0.0;
+#pragma unroll
+      for (int m = 0; m < T; ++m) {
+        double u[T];  // sum_n w[m][n] s^n
+#pragma unroll
+        for (int l = 0; l < T; ++l) {
+          double v = 0.0;
+#pragma unroll
+          for (int n = 0; n < T; ++n) v += w[m][n] * s[n][l];
+          u[l] = v;
+        }
+#pragma unroll
+        for (int l = 0; l < T; ++l)
+#pragma unroll
+          for (int k = 0; k <= l; ++k) P[l * (l + 1) / 2 + k] += k == l ? s[m][k] * u[k] : s[m][k] * u[l] + s[m][l] * u[k];
+      }
+#pragma unroll
+      for (int q = 0; q < NCOMP; ++q) {
+        double eq[NCOMP], C[T][T];
+#pragma unroll
+        for (int r = 0; r < NCOMP; ++r) eq[r] = r == q ? 1.0 : 0.0;
+        material<DIM, KIND>(eq, C);  // constants once unrolled: only its non-zero entries cost anything
+        double v = 0.0;
+#pragma unroll
+        for (int l = 0; l < T; ++l)
+#pragma unroll
+          for (int k = 0; k <= l; ++k)
+            if (C[k][l] != 0.0) v += C[k][l] * P[l * (l + 1) / 2 + k];
+        grad[el * NCOMP + q] = vol * v;
+      }
+    });
+  }
+}
+
+template <int DIM, int KIND, bool MESH>
+hipError_t launch_one(const SensArgs& a, long long nc, hipStream_t st) {
+  hipLaunchKernelGGL((k_sens<DIM, KIND, MESH>), dim3((unsigned)nc), dim3(kThreads), 0, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_sensitivity(const SensArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t st) {
+  if (nc <= 0) return hipSuccess;
+  return dispatch_dim_kind(dim, kind, [&](auto D, auto K) {
+    return mesh ? launch_one<D(), K(), true>(a, nc, st) : launch_one<D(), K(), false>(a, nc, st);
+  });
+}
+
+}  // namespace hommx

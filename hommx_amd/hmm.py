@@ -28,7 +28,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import fem
-from .batch import REGION_FIELDS, CoefStream, MicroCellPlan, Reconstruction, region_labels
+from .batch import REGION_FIELDS, CoefStream, MicroCellPlan, Reconstruction, Sensitivities, region_labels
 from .mesh import Mesh, micro_cells_per_side
 
 _VOIGT = {2: [(0, 0), (1, 1), (0, 1)], 3: [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]}
@@ -307,9 +307,10 @@ class BaseHMM(ABC):
     def _setup_macro_function_space(self) -> fem.FunctionSpace: ...
 
     # -- coefficient sampling (hmm.py:190-198, 349-352) ---------------------------------------------
-    def _sample_one(self, c_T: np.ndarray, yq: np.ndarray):
-        """A(c_T, y) at the quadrature points yq[dim, npts] -> array [npts, ...] (or Lame)."""
-        v = self._coeff(c_T, yq)
+    def _sample_one(self, c_T: np.ndarray, yq: np.ndarray, coeff=None):
+        """A(c_T, y) at the quadrature points yq[dim, npts] -> array [npts, ...] (or Lame).  ``coeff``: another callable of the
+        coefficient's shape (a direction of ``tensor_derivatives``) instead of A."""
+        v = (coeff or self._coeff)(c_T, yq)
         if isinstance(v, Lame):
             lam = np.broadcast_to(np.asarray(v.lam, float), (yq.shape[1],))
             mu = np.broadcast_to(np.asarray(v.mu, float), (yq.shape[1],))
@@ -363,34 +364,34 @@ class BaseHMM(ABC):
                              degrees[0], "; ".join(f"cell {k}: {f[1]}" for k, f in zip(probe, found)))
         return degrees[0]
 
-    def _element_means(self, cells: np.ndarray) -> tuple[np.ndarray, str]:
+    def _element_means(self, cells: np.ndarray, coeff=None) -> tuple[np.ndarray, str]:
         yq, w = self._quadrature_points()
         n_el, nq = yq.shape[:2]
         yflat = yq.reshape(-1, self._tdim).T
         c = self._msh.cell_midpoints()[cells]
-        out = self._sample_batched(c, yflat, n_el, nq, w)
+        out = self._sample_batched(c, yflat, n_el, nq, w, coeff)
         if out is None:  # the callable is not broadcastable over cells: one call per macro cell (as the reference)
-            first = self._sample_one(c[0], yflat)
+            first = self._sample_one(c[0], yflat, coeff)
             out = np.empty((len(cells),) + (n_el,) + first.shape[1:])
             for k in range(len(cells)):
-                v = first if k == 0 else self._sample_one(c[k], yflat)
+                v = first if k == 0 else self._sample_one(c[k], yflat, coeff)
                 out[k] = np.tensordot(w, v.reshape((n_el, nq) + v.shape[1:]), axes=([0], [1]))
         return self._pack_coefficient(out)
 
-    def _sample_batched(self, c: np.ndarray, yflat: np.ndarray, n_el: int, nq: int, w: np.ndarray):
+    def _sample_batched(self, c: np.ndarray, yflat: np.ndarray, n_el: int, nq: int, w: np.ndarray, coeff=None):
         """Try ONE broadcast call A(x[3, N_c, 1], y[d, 1, npts]) -> [N_c, npts(, ...)] per chunk of cells; accept it only
         if it reproduces the per-cell call on the first and last cell.  Returns None when the callable cannot broadcast."""
         nc, npts = c.shape[0], yflat.shape[1]
         if nc < 4:
             return None
         try:
-            ref0 = self._sample_one(c[0], yflat)
-            ref1 = self._sample_one(c[-1], yflat)
+            ref0 = self._sample_one(c[0], yflat, coeff)
+            ref1 = self._sample_one(c[-1], yflat, coeff)
             chunk = max(1, int(2.0e7 // max(1, npts)))
             parts = []
             for a in range(0, nc, chunk):
                 xb = c[a : a + chunk].T[:, :, None]
-                v = self._coeff(xb, yflat[:, None, :])
+                v = (coeff or self._coeff)(xb, yflat[:, None, :])
                 if isinstance(v, Lame):
                     lam = np.broadcast_to(np.asarray(v.lam, float), (xb.shape[1], npts))
                     mu = np.broadcast_to(np.asarray(v.mu, float), (xb.shape[1], npts))
@@ -512,8 +513,8 @@ class BaseHMM(ABC):
             self._reserved_cells = int(n_cells)
         return self._plan
 
-    def _local_cell_count(self) -> int:
-        """Macro cells this rank solves: all of them, or its block under a process group (hmm.py:307-310)."""
+    def _local_cells(self) -> np.ndarray:
+        """The macro cells this rank solves (``_local_cell_count``): all of them, or its block under a process group."""
         n = self._msh.num_cells
         if self._sharded():
             import torch.distributed as dist
@@ -521,8 +522,12 @@ class BaseHMM(ABC):
             from .dist import shard_range
 
             b, e, _ = shard_range(n, dist.get_rank(), dist.get_world_size())
-            return e - b
-        return n
+            return np.arange(b, e)
+        return np.arange(n)
+
+    def _local_cell_count(self) -> int:
+        """Macro cells this rank solves (hmm.py:307-310)."""
+        return len(self._local_cells())
 
     def prepare(self) -> "BaseHMM":
         """Create the plan and allocate its device workspace for this rank's share of the macro cells now, so that the first
@@ -570,13 +575,17 @@ class BaseHMM(ABC):
             return CoefStream.sampled(coef), kind
         co, c = self._coeff, self._msh.cell_midpoints()[cells]
         if form == "solve_two_phase":
-            mask = np.asarray(co.indicator(self._cell_mesh.cell_midpoints()[:, : self._tdim].T), dtype=bool)
+            mask = self._phase_mask()
             values = co.phase_values(c)
             if (values.ndim == 2) != (kind == "poisson"):
                 raise ValueError("TwoPhase values must be scalars for PoissonHMM and Lame(lam, mu) for LinearElasticityHMM")
             return CoefStream.two_phase(mask, values), kind
         yq, w = self._quadrature_points()
         return CoefStream.separable(co.family, co.table(yq, w), w, co.params(c)), kind
+
+    def _phase_mask(self) -> np.ndarray:
+        """The indicator of a ``TwoPhase`` coefficient at the micro element barycentres."""
+        return np.asarray(self._coeff.indicator(self._cell_mesh.cell_midpoints()[:, : self._tdim].T), dtype=bool)
 
     def _effective_tensors(self, cells: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
         """A_H / C_H and the per-cell info flags of ``cells``.  Under a process group every rank samples, uploads and solves
@@ -771,6 +780,93 @@ class BaseHMM(ABC):
         cat = lambda name: None if getattr(parts[0], name) is None else np.concatenate([getattr(r, name) for r in parts])
         return Reconstruction(xi, cat("mean_strain"), cat("mean_flux"), cat("energy"), cat("max_flux"), cat("argmax_element"), cat("A_eff"),
                               cat("info"), cat("strain"), cat("flux"), cells, *(cat(name) for name in REGION_FIELDS))
+
+    def _parameter_directions(self) -> tuple[tuple, np.ndarray]:
+        """(names, directions[n_dirs, n_el(, n_comp)]) of the parameters of a ``TwoPhase`` or affine ``Separable`` coefficient: the element
+        stream is linear in them, so its derivative with respect to each is one direction every macro cell shares.  ``TwoPhase``: the
+        outside and the inside value of every component -- the indicator of each phase; affine: a and b of every component -- 1 and the
+        table of g.  Elasticity: the components are (lambda, mu)."""
+        co = self._coeff
+        if isinstance(co, TwoPhase):
+            inside = self._phase_mask().astype(float)
+            basis, labels = [1.0 - inside, inside], ["outside", "inside"]
+        elif isinstance(co, Separable) and co.family == "affine":
+            yq, w = self._quadrature_points()
+            table = np.asarray(co.table(yq, w), dtype=float)
+            basis, labels = [np.ones_like(table), table], ["a", "b"]
+        else:
+            raise ValueError("the coefficient has no parameters the element stream is linear in (a TwoPhase or an affine Separable has): "
+                             "pass directions=[dA_0, ...], callables (x, y) of the coefficient's shape")
+        if self._kind == "poisson":
+            return tuple(labels), np.stack(basis)
+        comps = ("lambda", "mu")
+        unit = np.eye(2)
+        if isinstance(co, TwoPhase):  # the order of the values [2][n_comp]
+            pairs = [(b, q) for b in range(2) for q in range(2)]
+        else:  # the order of the params [n_comp][2]
+            pairs = [(b, q) for q in range(2) for b in range(2)]
+        return (tuple(f"{labels[b]}.{comps[q]}" for b, q in pairs), np.stack([basis[b][:, None] * unit[q][None, :] for b, q in pairs]))
+
+    def tensor_derivatives(self, cells=None, directions=None, chunk_cells: int | None = None) -> Sensitivities:
+        """Derivatives of A_H / C_H of ``cells`` (default: this rank's macro cells) with respect to the micro coefficient
+        (hommx_sensitivity_source) -> ``Sensitivities`` with ``names``, ``dA[N, n_dirs, t, t]``, ``A_eff``, ``info`` and ``cells``.
+
+        Without ``directions`` the derivatives are those with respect to the parameters of the coefficient: the outside and the inside
+        value of a ``TwoPhase`` coefficient, a and b of an affine ``Separable`` one, of every component (lambda and mu for the elasticity
+        classes).  Any other coefficient raises ``ValueError``: its element stream is not linear in a few parameters.
+        ``directions=[dA_0, ...]``: callables (x, y) of the coefficient's shape, up to 8; each is sampled exactly as the coefficient is
+        (the same quadrature degree and packing) and dA[:, k] is the derivative of A_H along it.
+
+        The coefficient crosses the boundary as ``solve()`` sends it (``_coef_stream``).  The cells run in chunks of ``chunk_cells``
+        (default: about 256 MB of coefficient and direction streams).  Under a process group this runs on the calling rank alone:
+        there is no collective."""
+        cells = self._local_cells() if cells is None else np.asarray(cells, dtype=np.int64).ravel()
+        if len(cells) == 0:
+            raise ValueError("tensor_derivatives() needs at least one macro cell")
+        if directions is None:
+            names, shared = self._parameter_directions()
+        else:
+            directions = list(directions)
+            names, shared = tuple(getattr(f, "__name__", f"direction{k}") for k, f in enumerate(directions)), None
+        if chunk_cells is None:
+            streams = 1 + (len(directions) if shared is None else 0)
+            chunk_cells = (256 << 20) // (8 * self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) * streams)
+        ch = max(1, int(chunk_cells))
+        parts = []
+        for b in range(0, len(cells), ch):
+            sub = cells[b:b + ch]
+            stream, kind = self._coef_stream(sub)
+            coef = stream.per_cell if stream.method == "solve" else stream
+            dirs = shared
+            if dirs is None:
+                sampled = [self._element_means(sub, f) for f in directions]
+                if any(k != kind for _, k in sampled):
+                    raise ValueError(f"every direction must have the coefficient's shape (plan kind {kind!r}); got {[k for _, k in sampled]}")
+                dirs = np.stack([d for d, _ in sampled], axis=1)
+            parts.append(self._ensure_plan(kind).sensitivities(coef, self._stratification(sub), directions=dirs, per_cell=shared is None))
+        cat = lambda name: np.concatenate([getattr(r, name) for r in parts])
+        return Sensitivities(cat("dA"), None, cat("A_eff"), cat("info"), names, cells)
+
+    def energy_derivatives(self, u=None, v=None, **kw) -> np.ndarray:
+        """[N, n_dirs]: vol(T)/vol(Y) xi_v(T) . dA_H[d](T) xi_u(T) for the cells and directions of ``tensor_derivatives(**kw)``, with xi the
+        macro gradient / Voigt strain ``reconstruct()`` forms -- the contribution of macro cell T to d(v . K_H u)/d theta_d at frozen u, v:
+        the compliance gradient for v = u (the default; ``u`` defaults to the last ``solve()`` result), the adjoint product otherwise."""
+        if u is None:
+            if not self._solved:
+                raise RuntimeError("energy_derivatives() needs a macro solution: call solve() first or pass u")
+            u = self._u
+        td = self.tensor_derivatives(**kw)
+
+        def xi(f):
+            x = np.asarray(f.x.array if hasattr(f, "x") else f, dtype=float)
+            if x.shape != (self._num_global_dofs,):
+                raise ValueError(f"the macro field has {x.size} dofs; the macro space has {self._num_global_dofs}")
+            return self._macro_strains(td.cells, x)
+
+        xu = xi(u)
+        xv = xu if v is None else xi(v)
+        vol = self._msh.cell_volumes()[td.cells] / self._cell_mesh_area
+        return vol[:, None] * np.einsum("cm,cdmn,cn->cd", xv, td.dA, xu)
 
     def plot_solution(self, u=None):  # hmm.py:493-511 (visualisation: out of scope)
         raise NotImplementedError("plotting is out of scope of hommx_amd; use u.x.array with any plotting tool")

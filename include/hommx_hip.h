@@ -279,6 +279,47 @@ int hommx_reconstruct_source_device(hommx_plan* plan, int64_t n_cells, const hom
                                     double* d_flux, double* d_A_eff, int32_t* d_info, void* stream);
 
 /*
+ * Derivatives of A_H along coefficient directions.  Let s^m_K be the gradient / strain of micro element K under
+ * the canonical load xi = e_m (the s_K of hommx_reconstruct_batch: shear doubled, M applied) and material(c) the element operator of the
+ * plan's kind, which is linear in the coefficient components for all four kinds.  For any perturbation dir[K][q] of the element stream,
+ * exactly on the discrete problem,
+ *   dA[c][d][m][n] = sum_K |K| s^m_K . material(dir_d[K]) s^n_K
+ * -- no derivative of a corrector appears (the cell equation makes those terms vanish), the gauge does not matter, and A_H being
+ * 1-homogeneous in the coefficient, the direction dir = coef gives dA = A_eff (Euler).  With weights w[c][t][t] the call also returns the
+ * per-element gradient of the functional w : A_H,
+ *   grad[c][K][q] = |K| sum_{m,n} w[c][m][n] s^m_K . material(e_q) s^n_K        (e_q: the unit coefficient vector of component q)
+ * so that sum_{K,q} grad[c][K][q] dir[K][q] = sum_{m,n} w[c][m][n] dA[dir][c][m][n].
+ *
+ *   n_dirs      0 .. HOMMX_SENS_MAX_DIRS direction streams, each shaped like one cell's coefficient [n_el][n_comp]
+ *   per_cell    0: dirs[n_dirs][n_el][n_comp], shared by all cells; 1: dirs[n_cells][n_dirs][n_el][n_comp]
+ *   dA          [n_cells][n_dirs][t][t] (symmetric, bitwise); required with n_dirs > 0, as dirs
+ *   weights     [n_cells][t][t] and grad [n_cells][n_el][n_comp] (the shape of coef): both or neither
+ *   A_eff, info as hommx_solve_batch, or NULL
+ * src, M: as hommx_reconstruct_source.  HOMMX_EINVAL, before the plan's device is made current: a null plan, source or argument struct,
+ * n_dirs out of range, n_dirs > 0 without both dirs and dA, one of weights / grad without the other, nothing requested (n_dirs == 0 and
+ * no grad).  Every plan is accepted; the correctors of one chunk (HOMMX_RECON_MEM_MB, the chunk rule of the reconstruction) live in
+ * plan-owned scratch.  A cell's outputs do not depend on its batch position, the chunking or which outputs are requested (fixed-order
+ * reduction).  A cell whose elimination flags a pivot keeps its info; its outputs may hold anything, no other cell's change.  The host
+ * entry sends shared directions with the source's shared arrays once; per-cell directions, weights and a sampled stream go in, and
+ * every output comes back, chunk by chunk.
+ */
+#define HOMMX_SENS_MAX_DIRS 8
+typedef struct hommx_sens_args {
+  int32_t n_dirs;
+  int32_t per_cell;
+  const double* dirs;
+  double* dA;
+  const double* weights;
+  double* grad;
+  double* A_eff;
+  int32_t* info;
+} hommx_sens_args;
+int hommx_sensitivity_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_sens_args* args);
+/* Same with DEVICE pointers (in *src and *args as well; the structs themselves are host memory), asynchronous on `stream`. */
+int hommx_sensitivity_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                    const hommx_sens_args* args, void* stream);
+
+/*
  * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
  * periodic: the caller folds the mesh vertices into n_nodes independent (periodic) nodes -- cell_problem.py:38-300's slave -> master
  * map -- and passes, per element, the periodic node of every vertex and the UNFOLDED vertex coordinates (gradients and volumes).
