@@ -85,6 +85,24 @@ class SensArgs(C.Structure):
     ]
 
 
+class LoadArgs(C.Structure):
+    """hommx_load_args: the loads of hommx_loads_source[_device], what is asked for and where it goes."""
+
+    _fields_ = [
+        ("n_loads", C.c_int32),
+        ("per_cell", C.c_int32),
+        ("P", C.c_void_p),
+        ("P_eff", C.c_void_p),
+        ("A_eff", C.c_void_p),
+        ("energy", C.c_void_p),
+        ("stats", C.c_void_p),
+        ("strain", C.c_void_p),
+        ("flux", C.c_void_p),
+        ("correctors", C.c_void_p),
+        ("info", C.c_void_p),
+    ]
+
+
 def _prototypes() -> dict:
     """name -> (restype, argtypes) of every symbol include/hommx_hip.h declares: ``load()`` declares them from this table, and
     the tests check that the header and the library export exactly these names."""
@@ -120,6 +138,8 @@ def _prototypes() -> dict:
         "hommx_reconstruct_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_sensitivity_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SensArgs)]),
         "hommx_sensitivity_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SensArgs), vp]),
+        "hommx_loads_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(LoadArgs)]),
+        "hommx_loads_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(LoadArgs), vp]),
         "hommx_solve_batch_two_phase": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_two_phase_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_separable": (c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),

@@ -140,6 +140,30 @@ class Sensitivities:
     cells: np.ndarray | None = None
 
 
+@dataclass
+class LoadResponse:
+    """Effective polarisation and response of macro cells to user-supplied loads P (include/hommx_hip.h, hommx_loads_source).
+
+    ``P_eff[N, n_loads, t]``: the mean total flux / stress of every load, by Levin's identity from the canonical correctors (every plan);
+    ``A_eff[N, t, t]`` and ``info[N]`` of that canonical pass.  With ``response`` (a solve for the loads themselves): ``energy[N, n_loads,
+    n_loads]`` = sum |K| eps(chi_l) . material eps(chi_l'), ``mean_flux[N, n_loads, t]`` (the mean of q = P + material eps(chi_l), equal
+    to ``P_eff`` up to rounding), ``max_flux[N, n_loads]`` and ``argmax_element[N, n_loads]`` as ``Reconstruction`` defines them; with
+    ``fields`` ``strain`` and ``flux`` ``[N, n_loads, n_el, t]``; with ``return_correctors`` ``correctors[N, n_loads, n_nodes * bs]``,
+    mean-free.  ``cells``: the macro cells (``BaseHMM.load_response``).  What was not asked for is None."""
+
+    P_eff: np.ndarray
+    A_eff: np.ndarray
+    info: np.ndarray
+    energy: np.ndarray | None = None
+    mean_flux: np.ndarray | None = None
+    max_flux: np.ndarray | None = None
+    argmax_element: np.ndarray | None = None
+    strain: np.ndarray | None = None
+    flux: np.ndarray | None = None
+    correctors: np.ndarray | None = None
+    cells: np.ndarray | None = None
+
+
 REGION_FIELDS = ("region_volume", "region_mean_strain", "region_mean_flux", "region_energy", "region_max_flux", "region_argmax_element")
 
 
@@ -442,6 +466,50 @@ class MicroCellPlan:
         A, info = self._host_call("hommx_sensitivity_source", nc, M, call)
         return Sensitivities(dA, grad, A, info)
 
+    def loads(self, coef, P, M: np.ndarray | None = None, per_cell: bool | None = None, response: bool = False, fields: bool = False,
+              return_correctors: bool = False) -> LoadResponse:
+        """User-supplied polarisation loads (hommx_loads_source): ``coef`` an array or a ``CoefStream`` and M as ``reconstruct`` takes them.
+        ``P[n_loads, n_el, t]`` (shared by all cells) or ``P[N_c, n_loads, n_el, t]`` (``per_cell``, inferred from ``P.ndim`` when None):
+        up to t prescribed flux / stress fields, constant per micro element, components in the order of ``Reconstruction.flux`` (shear not
+        doubled) -> ``LoadResponse``.  ``P_eff`` comes from the canonical correctors alone on every plan; ``response`` adds a solve for the
+        loads themselves (energy, mean / max total flux), ``fields`` the per-element strain and total flux of every load,
+        ``return_correctors`` the load correctors (each implies ``response``; not on the frontal mesh route).  The batch runs in the chunks
+        of ``reconstruct``."""
+        stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
+        nc = self._check_stream(stream)
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        if per_cell is None:
+            per_cell = P.ndim == 4
+        lead = (nc,) if per_cell else ()
+        nl = P.shape[len(lead)] if P.ndim == len(lead) + 3 else -1
+        if nl < 0 or P.shape != lead + (nl, self.n_el, self.t):
+            raise ValueError(f"P has shape {P.shape}; expected {lead + ('n_loads', self.n_el, self.t)}")
+        if not 1 <= nl <= self.t:
+            raise ValueError(f"n_loads must be 1 .. {self.t}; got {nl}")
+        response = bool(response or fields or return_correctors)
+        bs = 1 if self.kind.startswith("poisson") else self.dim
+        P_eff = np.empty((nc, nl, self.t), dtype=np.float64)
+        energy = np.empty((nc, nl, nl), dtype=np.float64) if response else None
+        stats = np.empty((nc, nl, self.t + 2), dtype=np.float64) if response else None
+        strain = np.empty((nc, nl, self.n_el, self.t), dtype=np.float64) if fields else None
+        flux = np.empty((nc, nl, self.n_el, self.t), dtype=np.float64) if fields else None
+        corr = np.empty((nc, nl, self.n_nodes * bs), dtype=np.float64) if return_correctors else None
+        addr = lambda a: None if a is None else a.ctypes.data
+        src = stream.coef_source()
+        args = _lib.LoadArgs(nl, int(bool(per_cell)), P.ctypes.data, P_eff.ctypes.data, None, addr(energy), addr(stats), addr(strain), addr(flux),
+                             addr(corr), None)
+
+        def call(Mp, o, i):
+            args.A_eff, args.info = o, i
+            return self._lib.hommx_loads_source(self._h, nc, C.byref(src), Mp, C.byref(args))
+
+        A, info = self._host_call("hommx_loads_source", nc, M, call)
+        r = LoadResponse(P_eff, A, info, energy, strain=strain, flux=flux, correctors=corr)
+        if response:
+            r.mean_flux, r.max_flux = stats[:, :, :self.t].copy(), stats[:, :, self.t].copy()
+            r.argmax_element = stats[:, :, self.t + 1].astype(np.int64)
+        return r
+
     def solve_two_phase(self, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None = None,
                         return_info: bool = False):
         """Two-phase media sampled on the device: mask[n_el] (bool / uint8, phase of every micro element) and
@@ -511,6 +579,19 @@ class MicroCellPlan:
                              A_ptr or None, info_ptr or None)
         _lib.check(self._lib.hommx_sensitivity_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
                    "hommx_sensitivity_source_device")
+
+    def loads_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, n_loads: int, P_ptr: int, P_eff_ptr: int,
+                     per_cell: bool = False, A_ptr: int | None = None, info_ptr: int | None = None, energy_ptr: int | None = None,
+                     stats_ptr: int | None = None, strain_ptr: int | None = None, flux_ptr: int | None = None,
+                     correctors_ptr: int | None = None, stream: int | None = None):
+        """Device-pointer form of ``loads`` (hommx_loads_source_device), asynchronous on ``stream``: ``source`` =
+        ``CoefStream.coef_source(upload)`` with device addresses; P[n_loads, n_el, t] or, ``per_cell``, [n_cells, n_loads, n_el, t] ->
+        P_eff[n_cells, n_loads, t]; energy[n_cells, n_loads, n_loads], stats[n_cells, n_loads, t + 2] = [mean total flux | max | argmax],
+        strain / flux[n_cells, n_loads, n_el, t] and correctors[n_cells, n_loads, n_nodes * bs]: any of them triggers the load solve."""
+        args = _lib.LoadArgs(int(n_loads), int(bool(per_cell)), P_ptr, P_eff_ptr, A_ptr or None, energy_ptr or None, stats_ptr or None,
+                             strain_ptr or None, flux_ptr or None, correctors_ptr or None, info_ptr or None)
+        _lib.check(self._lib.hommx_loads_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
+                   "hommx_loads_source_device")
 
     def solve_separable_device(self, n_cells: int, family: str, n_q: int, table_ptr: int, weights_ptr: int | None, params_ptr: int,
                                M_ptr: int | None, out_ptr: int, info_ptr: int | None, stream: int | None = None):

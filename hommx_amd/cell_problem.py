@@ -108,14 +108,20 @@ class PeriodicLinearProblem:
         kind   'poisson' | 'poisson_matrix' | 'elasticity' | 'elasticity_voigt'      (hmm.py:644-650 / 891-903)
         coef   element means of the coefficient on the micro mesh, in mesh element order
         M      optional Dtheta^T (stratified forms, hmm.py:759-772 / 1032-1048)
+        loads  optional P[n_loads, n_el, t]: further linear forms l(z) = sum_K |K| P_K . eps(z)_K, a prescribed flux / stress per micro
+               element (components in the order of ``Reconstruction.flux``, shear not doubled) -- the general ``L`` of the
+               reference restricted to P1, where only element means of such a field matter.  An unstructured mesh then takes the
+               tree route of the mesh family (the frontal route solves for the canonical loads only)
 
     ``solve()`` returns one ``fem.Function`` per canonical load on the micro mesh (slave nodes filled by back substitution,
     constants projected out as the reference's null-space handling does, cell_problem.py:349-361, 382) and stores the
-    effective tensor in ``effective_tensor``.  ``petsc_options`` is accepted and ignored (direct factorisation).
+    effective tensor in ``effective_tensor``.  With ``loads`` it also leaves their correctors ``a(chi_l, z) = -l_l(z)`` in
+    ``load_correctors`` (one ``fem.Function`` per load) and the mean total flux of every load in ``effective_polarisation[n_loads, t]``.
+    ``petsc_options`` is accepted and ignored (direct factorisation).
     """
 
     def __init__(self, kind: str, coef: np.ndarray, mpc: PeriodicConstraint, M: np.ndarray | None = None,
-                 petsc_options: dict | None = None, device: int = 0):
+                 petsc_options: dict | None = None, device: int = 0, loads: np.ndarray | None = None):
         self._mpc = mpc
         self._kind = kind
         msh = mpc.function_space.mesh
@@ -126,18 +132,34 @@ class PeriodicLinearProblem:
             self._n = micro_cells_per_side(msh)
         except ValueError:  # unstructured (or nx != ny) micro mesh: the mesh route, on the constraint's periodic numbering
             self._n = None
-            self._plan = MicroCellPlan.from_mesh(msh, kind, device=device, constraint=mpc)
+            self._plan = MicroCellPlan.from_mesh(msh, kind, device=device, constraint=mpc, route=None if loads is None else "tree")
         else:
             self._plan = MicroCellPlan(self._dim, self._n, kind, device=device)
         self.effective_tensor: np.ndarray | None = None
         self.info: int | None = None
+        self._loads = None
+        if loads is not None:
+            self._loads = np.ascontiguousarray(loads, dtype=float)
+            if self._loads.ndim != 3 or self._loads.shape[1:] != (self._plan.n_el, self._plan.t):
+                raise ValueError(f"loads has shape {self._loads.shape}; expected (n_loads, {self._plan.n_el}, {self._plan.t})")
+        self.load_correctors: list[fem.Function] | None = None
+        self.effective_polarisation: np.ndarray | None = None
+
+    def _functions(self, chi: np.ndarray) -> list[fem.Function]:
+        """chi[k, n_periodic * bs] as functions on the micro mesh, slave nodes filled by back substitution."""
+        out = []
+        for m in range(chi.shape[0]):
+            f = fem.Function(self._mpc.function_space)
+            f.x.array[:] = self._mpc.backsubstitution(chi[m])
+            out.append(f)
+        return out
 
     def solve(self) -> list[fem.Function]:
         AH, chi, info = self._plan.solve(self._coef, self._M, return_info=True, return_correctors=True)
         self.effective_tensor, self.info = AH[0], int(info[0])
-        out = []
-        for m in range(chi.shape[1]):
-            f = fem.Function(self._mpc.function_space)
-            f.x.array[:] = self._mpc.backsubstitution(chi[0, m])
-            out.append(f)
-        return out
+        if self._loads is not None:  # t loads per call
+            t = self._plan.t
+            parts = [self._plan.loads(self._coef, self._loads[b:b + t], self._M, return_correctors=True) for b in range(0, len(self._loads), t)]
+            self.load_correctors = self._functions(np.concatenate([r.correctors[0] for r in parts]))
+            self.effective_polarisation = np.concatenate([r.P_eff[0] for r in parts])
+        return self._functions(chi[0])

@@ -106,7 +106,8 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 // B_PIN_* / B_DEV_*: the small inputs of the sampler host entry points and their outputs, pinned host mirrors + device (plan_new pins).
 // B_RCORR, B_RA: the correctors of one reconstruction chunk (and the chi^xi slots of cells too large for LDS), A_eff the caller did not ask for
 // B_FACT: the factor records of one chunk of a fused 2D plan's corrector route (kernels.h)
-enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, N_BUF };
+// B_LOADS: what a load pass leaves where a corrector pass leaves A_eff (hommx_loads_source: C0 - f^T K^+ f, unused)
+enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, N_BUF };
 
 }  // namespace
 
@@ -982,6 +983,156 @@ int sens_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const 
       });
 }
 
+// -- polarisation loads (hommx_loads_source[_device]) ------------------------------------------------------------------------------------
+// device pointers of one chunk
+struct LoadIO {
+  const double *coef, *M, *P;
+  double *P_eff, *A_eff, *energy, *stats, *strain, *flux, *correctors;
+  int32_t* info;
+};
+
+bool load_response(const hommx_load_args& a) { return a.energy || a.stats || a.strain || a.flux || a.correctors; }
+
+// the argument checks of both entry points, then the routes the call needs: one that forms correctors, and for a response the blocked
+// workspace a fused 2D plan does not have yet (its own substitution takes the canonical loads only)
+int loads_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_load_args* a, bool device) {
+  auto more = [&] {
+    if (int rc = coef_check(p, src)) return rc;
+    if (!a) return fail(HOMMX_EINVAL, "null arguments");
+    const int t = hommx::kind_sizes(p->desc.dim, p->desc.kind).t;
+    if (a->n_loads < 1 || a->n_loads > t) return fail(HOMMX_EINVAL, "n_loads must be 1 .. %d (the tensor size of the plan), got %d", t, a->n_loads);
+    if (!a->P || !a->P_eff) return fail(HOMMX_EINVAL, "null P / P_eff");
+    if (!a->strain != !a->flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
+    return HOMMX_OK;
+  };
+  if (int rc = open_call(p, n_cells, true, "", device, more); rc != GO) return rc;
+  // the one check that reads more of the plan than its descriptor (its family), so it cannot run on the plan-shaped memory the checks
+  // above accept: it comes after open_call, with the device current already, and before any work
+  if (load_response(*a) && p->family == FAM_MESH)
+    return fail(HOMMX_EINVAL, "the frontal mesh route (mesh_front) solves for the canonical loads only: energy, stats, strain / flux and "
+                              "correctors of user loads need a plan of the tree route (HOMMX_MESH_FLAG_TREE, route=\"tree\"); P_eff alone works here");
+  if (int rc = corrector_workspace(p)) return rc;
+  if (load_response(*a) && !p->ws) {
+    int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
+    if (rc) return prefix_error(rc, "blocked path: ");
+  }
+  return GO;
+}
+
+// one chunk of at most recon_chunk() cells on the device: the canonical correctors into the plan's scratch and k_polar; for a response
+// the correctors of the loads behind them (a corrector pass of the blocked family on the overridden load rows) and k_load_stats
+int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const LoadIO& io, const hommx_load_args& a, hipStream_t st) {
+  const bool response = load_response(a), mesh = p->desc.n_micro == 0;
+  const int t = p->ks.t;
+  double *d_A_eff = io.A_eff, *corr = nullptr;
+  if (int rc = chunk_correctors(p, nc, chunk, io.coef, io.M, &d_A_eff, io.info, response ? t : 0, st, &corr)) return rc;
+  hommx::LoadArgs k;
+  set_geometry(p, k);
+  k.corr = corr;
+  k.coef = io.coef;
+  k.M = io.M;
+  k.n_loads = a.n_loads;
+  k.per_cell = a.per_cell != 0;
+  k.P = io.P;
+  k.P_eff = io.P_eff;
+  HIP_TRY(hommx::launch_polar(k, p->desc.dim, p->desc.kind, mesh, nc, st));
+  if (!response) return HOMMX_OK;
+  if (int rc = grow(p->buf[B_LOADS], sizeof(double) * chunk * t * t)) return rc;
+  double* corr_l = corr + chunk * t * k.ndof;
+  const hommx::LoadOverride lo{io.P, a.n_loads, a.per_cell != 0};
+  if (int rc = hommx::blocked_solve(p->ws, nc, io.coef, io.M, static_cast<double*>(p->buf[B_LOADS].p), nullptr, st, corr_l, &lo))
+    return route_fail(p, rc);
+  k.corr = corr_l;
+  k.energy = io.energy;
+  k.stats = io.stats;
+  k.strain = io.strain;
+  k.flux = io.flux;
+  if (io.energy || io.stats || io.strain) HIP_TRY(hommx::launch_load_stats(k, p->desc.dim, p->desc.kind, mesh, nc, st));
+  if (io.correctors)  // rows l < n_loads of every cell
+    HIP_TRY(hipMemcpy2DAsync(io.correctors, sizeof(double) * a.n_loads * k.ndof, corr_l, sizeof(double) * t * k.ndof,
+                             sizeof(double) * a.n_loads * k.ndof, nc, hipMemcpyDeviceToDevice, st));
+  return HOMMX_OK;
+}
+
+// doubles per cell of the outputs of a call, in the order of LoadIO: P_eff, A_eff, energy, stats, strain, flux, correctors
+void load_out_sizes(const hommx_plan* p, const hommx_load_args& a, int64_t (&n)[7]) {
+  const int64_t t = p->ks.t, nl = a.n_loads, field = a.strain ? nl * p->n_el * t : 0;
+  const int64_t sizes[7] = {nl * t, t * t, a.energy ? nl * nl : 0, a.stats ? nl * (t + 2) : 0, field, field, a.correctors ? nl * plan_ndof(p) : 0};
+  for (int k = 0; k < 7; ++k) n[k] = sizes[k];
+}
+
+// everything on the device already: the chunks are views of the caller's arrays.  A response holds a second corrector block per cell
+int loads_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, const hommx_load_args& a, hipStream_t st) {
+  const int d = p->desc.dim;
+  const int64_t el = p->n_el * p->ks.t;
+  int64_t n_out[7], chunk = 0;
+  load_out_sizes(p, a, n_out);
+  const size_t second = load_response(a) ? sizeof(double) * plan_ndof(p) * p->ks.t : 0;
+  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, second), &chunk)) return rc;
+  return source_chunks<LoadIO>(
+      p, n_cells, chunk, s, st,
+      [&](int64_t c0, int64_t, LoadIO& io) {
+        double* const out[7] = {a.P_eff, a.A_eff, a.energy, a.stats, a.strain, a.flux, a.correctors};
+        double* at[7];
+        for (int k = 0; k < 7; ++k) at[k] = out[k] ? out[k] + c0 * n_out[k] : nullptr;
+        io = LoadIO{nullptr, d_M ? d_M + c0 * d * d : nullptr, a.per_cell ? a.P + c0 * a.n_loads * el : a.P,
+                    at[0], at[1], at[2], at[3], at[4], at[5], at[6], a.info ? a.info + c0 : nullptr};
+        return HOMMX_OK;
+      },
+      [&](int64_t nc, const LoadIO& io) { return loads_run(p, nc, chunk, io, a, st); },
+      [](int64_t, int64_t, const LoadIO&) { return HOMMX_OK; });
+}
+
+// host pointers.  What every cell shares (mask, table, weights of the sampler, a shared P) and the per-cell values of a sampler form travel
+// once, in the plan's pinned block (stage_source); a sampled stream, M and a per-cell P stream in and every output streams out chunk by
+// chunk, so device memory is bounded by the chunk
+int loads_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_load_args& a) {
+  const int d = p->desc.dim;
+  const int64_t per = s.form == HOMMX_COEF_SAMPLED ? p->n_el * p->ks.n_comp : 0, load = a.n_loads * p->n_el * p->ks.t;
+  const bool per_cell = a.per_cell != 0;
+  hommx_coef_source ds;
+  const double* d_shared = nullptr;
+  const hommx::HostPiece shared{per_cell ? nullptr : a.P, sizeof(double) * load, (const void**)&d_shared};
+  if (int rc = stage_source(p, n_cells, s, shared, &ds)) return rc;
+  // doubles per cell of the plan's blocks: in = [coef | M | P], out = the seven of load_out_sizes (A_eff always: the caller may not want it), and info
+  const int64_t n_in[] = {per, M ? d * d : 0, per_cell ? load : 0};
+  int64_t n_out[7];
+  load_out_sizes(p, a, n_out);
+  size_t cell = sizeof(int32_t) + (load_response(a) ? sizeof(double) * plan_ndof(p) * p->ks.t : 0);
+  for (int64_t k : n_in) cell += sizeof(double) * k;
+  for (int64_t k : n_out) cell += sizeof(double) * k;
+  int64_t chunk = 0;
+  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, cell), &chunk)) return rc;
+  size_t in_bytes[3], out_bytes[8];
+  for (int k = 0; k < 3; ++k) in_bytes[k] = sizeof(double) * chunk * n_in[k];
+  for (int k = 0; k < 7; ++k) out_bytes[k] = sizeof(double) * chunk * n_out[k];
+  out_bytes[7] = sizeof(int32_t) * chunk;
+  char *in[3], *out[8];
+  if (int rc = carve(p->buf[B_IN], in_bytes, in)) return rc;
+  if (int rc = carve(p->buf[B_OUT], out_bytes, out)) return rc;
+  auto f64 = [](char* at) { return reinterpret_cast<double*>(at); };
+  const LoadIO dev{f64(in[0]), f64(in[1]), per_cell ? f64(in[2]) : d_shared, f64(out[0]), f64(out[1]), f64(out[2]), f64(out[3]),
+                   f64(out[4]), f64(out[5]), f64(out[6]), reinterpret_cast<int32_t*>(out[7])};
+  const double* src_in[] = {s.coef, M, a.P};
+  return source_chunks<LoadIO>(
+      p, n_cells, chunk, ds, nullptr,
+      [&](int64_t c0, int64_t nc, LoadIO& io) {
+        for (int k = 0; k < 3; ++k)
+          if (n_in[k]) HIP_TRY(hipMemcpy(in[k], src_in[k] + c0 * n_in[k], sizeof(double) * nc * n_in[k], hipMemcpyHostToDevice));
+        io = dev;
+        return HOMMX_OK;
+      },
+      [&](int64_t nc, const LoadIO& io) { return loads_run(p, nc, chunk, io, a, nullptr); },
+      [&](int64_t c0, int64_t nc, const LoadIO& io) {
+        double* dst_out[] = {a.P_eff, a.A_eff, a.energy, a.stats, a.strain, a.flux, a.correctors};
+        for (int k = 0; k < 7; ++k)
+          if (n_out[k] && dst_out[k])
+            HIP_TRY(hipMemcpy(dst_out[k] + c0 * n_out[k], out[k], sizeof(double) * nc * n_out[k], hipMemcpyDeviceToHost));
+        if (a.info) HIP_TRY(hipMemcpy(a.info + c0, io.info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
+        return HOMMX_OK;
+      });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1032,6 +1183,17 @@ int hommx_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_
 int hommx_sensitivity_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_sens_args* args) {
   if (int rc = sens_open(p, n_cells, src, args, false); rc != GO) return rc;
   return sens_host(p, n_cells, source_of_form(*src), M, *args);
+}
+
+int hommx_loads_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const hommx_load_args* args,
+                               void* stream) {
+  if (int rc = loads_open(p, n_cells, src, args, true); rc != GO) return rc;
+  return loads_device(p, n_cells, source_of_form(*src), d_M, *args, reinterpret_cast<hipStream_t>(stream));
+}
+
+int hommx_loads_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_load_args* args) {
+  if (int rc = loads_open(p, n_cells, src, args, false); rc != GO) return rc;
+  return loads_host(p, n_cells, source_of_form(*src), M, *args);
 }
 
 int hommx_calibrate_fp64(int device, double* mfma_flops_per_s, double* fma_flops_per_s) {

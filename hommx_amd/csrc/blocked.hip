@@ -186,13 +186,14 @@ int blocked_reserve(BlockedWorkspace* ws, long long n_cells) {
 }
 
 int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, const double* d_M, double* d_out,
-                  int32_t* d_info, hipStream_t st, double* d_corr) {
+                  int32_t* d_info, hipStream_t st, double* d_corr, const LoadOverride* loads) {
+  if (loads && !d_corr) return fail(HOMMX_EINVAL, "blocked_solve: a load override needs the correctors");
   if (ws_on_tree(ws) && !d_corr) return mf_solve(ws, ws->mf, ncells, d_coef, d_M, d_out, d_info, st);  // nested dissection (multifrontal.hip)
   // correctors on the same route: a second plan whose fronts keep their factors for the back substitution
   if (ws_corr_on_tree(ws)) {
     if (!ws->mf_keep)
       if (int rc = mf_plan_from_tree(ws, true, &ws->mf_keep)) return rc;
-    return mf_solve(ws, ws->mf_keep, ncells, d_coef, d_M, d_out, d_info, st, d_corr);
+    return mf_solve(ws, ws->mf_keep, ncells, d_coef, d_M, d_out, d_info, st, d_corr, loads);
   }
   if (int rc = plane_reserve(ws, ncells, d_corr != nullptr)) return rc;
   const Geo& G = ws->G;
@@ -210,6 +211,7 @@ int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, 
     const double* Mm = d_M ? d_M + c0 * G.dim * G.dim : nullptr;
     double* out = d_out + c0 * G.t * G.t;
     launch_assembly(ws, coef, Mm, nc, st, pb.Kst, pb.Brhs, pb.C0);
+    if (loads) HIP_TRY(launch_assemble_loads(ws, *loads, c0, Mm, nc, st, pb.Brhs));
     if (d_corr || ws->route == Route::Plane) {
       if (int rc = plane_eliminate(c, out, d_corr ? d_corr + c0 * (long long)G.t * G.nn * G.bs : nullptr)) return rc;
       continue;

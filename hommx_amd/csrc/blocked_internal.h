@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "geo.h"
+#include "kernels.h"
 #include "mesh_tree.h"
 
 namespace hommx {
@@ -138,7 +139,10 @@ std::string mf_describe(const BlockedWorkspace* ws, const MfPlan* p);  // one li
 int mf_reserve(BlockedWorkspace* ws, MfPlan* P, long long ncells, bool ahead);
 // effective tensors, and with the corrector plan (keep = true) and d_corr != nullptr the correctors [cell][t][n^d bs] as well
 int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
-             hipStream_t st, double* d_corr = nullptr);
+             hipStream_t st, double* d_corr = nullptr, const LoadOverride* loads = nullptr);
+// loads.hip: Brhs of `nc` cells (the layout K1 writes) from the loads of cells [cell0, cell0 + nc) of `lo`, on the geometry of the workspace
+hipError_t launch_assemble_loads(const BlockedWorkspace* ws, const LoadOverride& lo, long long cell0, const double* Mm, long long nc,
+                                 hipStream_t st, double* Brhs);
 // remove the mean of every component of nc x t corrector fields (blocked.hip)
 void launch_center_corr(BlockedWorkspace* ws, double* corr, long long nc, hipStream_t st);
 // workspace of a mesh plan of the tree route (mesh_tree_workspace): G (nn = n_nodes, ncode = most coupling codes of a node, n unused), the

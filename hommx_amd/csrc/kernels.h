@@ -138,6 +138,39 @@ struct SensArgs {
 };
 hipError_t launch_sensitivity(const SensArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
 
+// loads.hip: user-supplied polarisation loads P[load][el][t] (include/hommx_hip.h, hommx_loads_source).  The
+// geometry fields are those of ReconArgs.  launch_polar: P_eff from the canonical correctors (Levin); launch_load_stats: the response
+// outputs from the correctors of the loads themselves, every one of them optional
+struct LoadArgs {
+  int n = 0;
+  double vol_struct = 0.0;
+  long long ndof = 0, n_el = 0;
+  const int32_t* el_nodes = nullptr;
+  const double* grads = nullptr;
+  const double* vol = nullptr;
+  const double* corr = nullptr;      // [nc][t][ndof]: the canonical correctors (k_polar), the correctors of the loads, rows >= n_loads unused (k_load_stats)
+  const double* coef = nullptr;      // [nc][n_el][n_comp] (k_load_stats)
+  const double* M = nullptr;         // [nc][d][d] or null
+  int n_loads = 0;                   // 1 .. t
+  bool per_cell = false;             // P[nc][n_loads][n_el][t] instead of P[n_loads][n_el][t]
+  const double* P = nullptr;
+  double* P_eff = nullptr;           // [nc][n_loads][t] (k_polar)
+  double* energy = nullptr;          // [nc][n_loads][n_loads] or null
+  double* stats = nullptr;           // [nc][n_loads][t+2] or null
+  double* strain = nullptr;          // [nc][n_loads][n_el][t] or null (then flux is null as well)
+  double* flux = nullptr;
+};
+hipError_t launch_polar(const LoadArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
+hipError_t launch_load_stats(const LoadArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
+
+// the loads a corrector pass of the blocked family solves for instead of the canonical ones: rows l < n_loads of Brhs from P (device), the
+// rest zero.  P starts at the first cell of the call
+struct LoadOverride {
+  const double* P = nullptr;         // [n_loads][n_el][t] or, per_cell, [ncells][n_loads][n_el][t]
+  int n_loads = 0;
+  bool per_cell = false;
+};
+
 // calibrate.hip: best sustained v_mfma_f64_16x16x4_f64 and v_fma_f64 rates over 2 and 4 waves per SIMD.
 hipError_t run_fp64_calibration(double* mfma_flops_per_s, double* fma_flops_per_s, double* mfma_lds_fed_flops_per_s = nullptr);
 
@@ -148,8 +181,10 @@ namespace hommx {
 struct BlockedWorkspace;
 int blocked_workspace_create(BlockedWorkspace** out, int dim, int n, int kind);
 void blocked_workspace_destroy(BlockedWorkspace* ws);
+// `loads` (with d_corr): the correctors of these loads instead of the canonical ones, on the route that forms correctors; d_out then
+// holds C0 - f^T K^+ f, which is no effective tensor
 int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, const double* d_M,
-                  double* d_out, int32_t* d_info, hipStream_t stream, double* d_corr = nullptr);
+                  double* d_out, int32_t* d_info, hipStream_t stream, double* d_corr = nullptr, const LoadOverride* loads = nullptr);
 // allocate the workspace of the route for batches of up to n_cells (what the first solve would otherwise do)
 int blocked_reserve(BlockedWorkspace* ws, long long n_cells);
 // "small_wave" (b <= 48), "small_fused" (48 < b <= 64), "blocked", "multifrontal" or, on a mesh, "mesh_multifrontal": the route

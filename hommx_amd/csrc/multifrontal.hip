@@ -1027,7 +1027,7 @@ void mf_backsub_step(BlockedWorkspace* ws, MfPlan* P, const MfHalf& h, const MfG
 }  // namespace
 
 int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
-             hipStream_t st, double* d_corr) {
+             hipStream_t st, double* d_corr, const LoadOverride* loads) {
   const Geo& G = ws->G;
   if (d_corr && !P->keep) return fail(HOMMX_EINVAL, "mf_solve: correctors need the corrector plan");
   if (int rc = mf_reserve(ws, P, ncells, false)) return rc;
@@ -1082,6 +1082,7 @@ int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_
       double *Kst = P->Kst + h.base * G.ncode * bs * bs * G.nn, *Brhs = P->Brhs + h.base * G.t * bs * G.nn, *C0 = P->C0 + h.base * 36;
       if (ws->mesh_tables) launch_mesh_assembly(ws->mesh, coef, Mm, h.nc, h.st, Kst, Brhs, C0);  // the only launch that knows the geometry
       else launch_assembly(ws, coef, Mm, h.nc, h.st, Kst, Brhs, C0);
+      if (loads) HIP_TRY_OR(join(), launch_assemble_loads(ws, *loads, h.c0, Mm, h.nc, h.st, Brhs));
     }
     int gi = 0;
     for (const MfGroup& mg : P->groups) {  // launches of the pieces interleaved: all queues fill at the same pace

@@ -16,76 +16,17 @@
 // No atomics, no inline assembly.
 #include <hip/hip_runtime.h>
 
+#include "elem_walk.h"
 #include "kernels.h"
-#include "mesh_elem.h"
-#include "struct_elem.h"
 
 namespace hommx {
 
 namespace {
 
-constexpr int kThreads = 512;
-constexpr int kWaves = kThreads / 64;
+constexpr int kThreads = kWalkThreads;
+constexpr int kWaves = kWalkWaves;
 
 constexpr int tensor_size(int dim, int kind) { return kind_sizes(dim, kind).t; }
-
-// f(el, vol, vertex) for the elements of this thread, ascending: the element loops of k_recon.  vertex(a, node, g): the periodic node
-// and the P1 gradient of local vertex a, read (mesh plans) or computed (structured plans) when asked for
-template <int DIM, bool MESH, typename F>
-__device__ __forceinline__ void for_elements(const SensArgs& A, int tid, F&& f) {
-  if constexpr (MESH) {
-    for (long long el = tid; el < A.n_el; el += kThreads)
-      f(el, A.vol[el], [&](int a, int& node, double(&g)[DIM]) {
-        node = A.el_nodes[el * (DIM + 1) + a];
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) g[k] = A.grads[(el * (DIM + 1) + a) * DIM + k];
-      });
-  } else {
-    // one grid cell (all its sub-simplices, element order n_sub (i + n j [+ n^2 k]) + s) per thread and step; the 3D loop stays rolled
-    constexpr int NSUB = DIM == 2 ? 2 : 6;
-    constexpr int UNROLL = DIM == 2 ? 2 : 1;
-    const int n = A.n;
-    const double hn = (double)n;
-    const long long ncube = A.n_el / NSUB;
-    for (long long cube = tid; cube < ncube; cube += kThreads) {
-      const int i = (int)(cube % n), j = (int)((cube / n) % n), k = DIM == 3 ? (int)(cube / ((long long)n * n)) : 0;
-#pragma unroll UNROLL
-      for (int s = 0; s < NSUB; ++s)
-        f(cube * NSUB + s, A.vol_struct, [&](int a, int& node, double(&g)[DIM]) { struct_vertex<DIM>(i, j, k, s, a, n, hn, node, g); });
-    }
-  }
-}
-
-// s[m] = s^m_K for the t canonical loads: the arithmetic of k_recon's element<>() on chi^xi = chi_m.  3D elasticity takes one vertex at
-// a time (a rolled loop): its 72 gathers in flight at once would not leave registers for the 36 strains and the running sums
-template <int DIM, int KIND, typename V>
-__device__ __forceinline__ void load_strains(const double* __restrict__ corr, long long ndof, V&& vertex, const double* Mc,
-                                             double (&s)[tensor_size(DIM, KIND)][tensor_size(DIM, KIND)]) {
-  constexpr KindSizes ks = kind_sizes(DIM, KIND);
-  constexpr int T = ks.t, BS = ks.bs, VERTS = T == 6 ? 1 : DIM + 1;
-#pragma unroll
-  for (int m = 0; m < T; ++m)
-#pragma unroll
-    for (int k = 0; k < T; ++k) s[m][k] = m == k ? 1.0 : 0.0;
-#pragma unroll VERTS
-  for (int a = 0; a < DIM + 1; ++a) {
-    int node;
-    double g[DIM];
-    vertex(a, node, g);
-#pragma unroll
-    for (int al = 0; al < BS; ++al) {
-      double sa[T];
-      strain<DIM, KIND>(g, Mc, al, sa);
-      const double* __restrict__ at = corr + (long long)node * BS + al;
-#pragma unroll
-      for (int m = 0; m < T; ++m) {
-        const double c = at[m * ndof];
-#pragma unroll
-        for (int k = 0; k < T; ++k) s[m][k] += c * sa[k];
-      }
-    }
-  }
-}
 
 template <int DIM, int KIND, bool MESH>
 __global__ __launch_bounds__(kThreads) void k_sens(SensArgs A) {

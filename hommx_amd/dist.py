@@ -119,8 +119,9 @@ def _unpad_index(n_cells: int, per: int, world: int) -> np.ndarray:
                            for r in range(world)])
 
 
-def run_sharded(t: int, n_cells: int, local_solve, group=None, device=None):
-    """Solve this rank's block with ``local_solve(b, e) -> (A[e-b, t, t], info[e-b])`` and all-gather both.
+def run_sharded(t: int, n_cells: int, local_solve, group=None, device=None, shape: tuple | None = None):
+    """Solve this rank's block with ``local_solve(b, e) -> (A[e-b, t, t], info[e-b])`` and all-gather both.  ``shape``: the shape of
+    one cell's row of the field when it is not (t, t) (the effective polarisation: (t,)).
 
     ``local_solve`` may return NumPy arrays or torch tensors (on the rank's GPU: the shard then never leaves the device before
     the collective).  The tensors and the info flags travel in ONE packed buffer [per_rank, t*t + 1] (info as a double: small
@@ -132,6 +133,8 @@ def run_sharded(t: int, n_cells: int, local_solve, group=None, device=None):
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     b, e, per = shard_range(n_cells, rank, world)
     nloc = e - b
+    shape = (t, t) if shape is None else tuple(shape)
+    tt = int(np.prod(shape))
     A = info = None
     failure = None
     if nloc > 0:
@@ -149,22 +152,22 @@ def run_sharded(t: int, n_cells: int, local_solve, group=None, device=None):
     elif not isinstance(device, torch.device):
         device = torch.device("cuda", int(device)) if dist.get_backend(group) == "nccl" else None
     # one extra row per rank carries the failure flag, so that ranks agree on an exception instead of waiting for ever
-    buf = torch.zeros((per + 1, t * t + 1), dtype=torch.float64, device=device if device is not None else "cpu")
+    buf = torch.zeros((per + 1, tt + 1), dtype=torch.float64, device=device if device is not None else "cpu")
     if failure is not None:
-        buf[per, t * t] = FAILED
+        buf[per, tt] = FAILED
     elif nloc > 0:
         At = A if torch.is_tensor(A) else torch.from_numpy(np.ascontiguousarray(A, dtype=np.float64))
         it = info if torch.is_tensor(info) else torch.from_numpy(np.ascontiguousarray(info))
-        buf[:nloc, : t * t] = At.reshape(nloc, t * t).to(buf.device)
-        buf[:nloc, t * t] = it.to(buf.device, dtype=torch.float64)
-    full = all_gather_field(buf, world * (per + 1), group).cpu().numpy().reshape(world, per + 1, t * t + 1)
-    failed = [r for r in range(world) if full[r, per, t * t] == FAILED]
+        buf[:nloc, : tt] = At.reshape(nloc, tt).to(buf.device)
+        buf[:nloc, tt] = it.to(buf.device, dtype=torch.float64)
+    full = all_gather_field(buf, world * (per + 1), group).cpu().numpy().reshape(world, per + 1, tt + 1)
+    failed = [r for r in range(world) if full[r, per, tt] == FAILED]
     if failed:
         if failure is not None:
             raise failure
         raise ShardFailure(f"micro-cell solve failed on rank(s) {failed} (see their exceptions); no field was assembled")
-    full = full[:, :per].reshape(world * per, t * t + 1)[_unpad_index(n_cells, per, world)]
-    return full[:, : t * t].reshape(n_cells, t, t).copy(), np.rint(full[:, t * t]).astype(np.int32)
+    full = full[:, :per].reshape(world * per, tt + 1)[_unpad_index(n_cells, per, world)]
+    return full[:, : tt].reshape((n_cells,) + shape).copy(), np.rint(full[:, tt]).astype(np.int32)
 
 
 def _on_rccl(group=None) -> bool:

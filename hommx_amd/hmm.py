@@ -28,7 +28,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import fem
-from .batch import REGION_FIELDS, CoefStream, MicroCellPlan, Reconstruction, Sensitivities, region_labels
+from .batch import REGION_FIELDS, CoefStream, LoadResponse, MicroCellPlan, Reconstruction, Sensitivities, region_labels
 from .mesh import Mesh, micro_cells_per_side
 
 _VOIGT = {2: [(0, 0), (1, 1), (0, 1)], 3: [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]}
@@ -285,6 +285,8 @@ class BaseHMM(ABC):
         self.effective_tensors: np.ndarray | None = None  # A_H / C_H of every macro cell after assembly
         self.cell_info: np.ndarray | None = None
         self._solved = False  # reconstruct() defaults to the last solve() result
+        self._polarisation = None  # set_polarisation
+        self.effective_polarisation: np.ndarray | None = None  # P_eff[N, t] of every macro cell after a solve() with a polarisation
         if self._reserve_at_construction:
             self.prepare()
 
@@ -302,6 +304,23 @@ class BaseHMM(ABC):
     def set_right_hand_side(self, f: Callable):
         """hmm.py:289-296."""
         self._f = f
+
+    def set_polarisation(self, P):
+        """A prescribed micro flux / stress field P(x, y): a thermal eigenstress -A : alpha dT, a prestress, the gravity
+        term of Darcy flow.  The micro total flux becomes A (grad / eps of the reconstruction) + P, and ``solve()`` adds the load
+        b_T = -vol(T)/vol(Y) (macro strains of the basis functions) . P_eff[T] of the effective polarisation of every macro cell.
+
+        ``P``: a NumPy-vectorised callable ``P(x, y) -> [t, ...]`` (components in the order of ``Reconstruction.flux``: the flux vector, or
+        s00, s11[, s22], s01[, s02, s12], shear not doubled), sampled with the micro rule that samples the coefficient; an array
+        ``[n_el, t]`` of element means shared by all macro cells; an array ``[N, n_el, t]``; ``None`` removes it (``solve()`` is then bit
+        for bit what it is without this call)."""
+        if P is not None and not callable(P):
+            P = np.ascontiguousarray(P, dtype=float)
+            n_el, t = self._cell_mesh.num_cells, self._tensor_size()
+            if P.shape not in ((n_el, t), (self._msh.num_cells, n_el, t)):
+                raise ValueError(f"P has shape {P.shape}; expected ({n_el}, {t}) or ({self._msh.num_cells}, {n_el}, {t})")
+        self._polarisation = P
+        self.effective_polarisation = None
 
     @abstractmethod
     def _setup_macro_function_space(self) -> fem.FunctionSpace: ...
@@ -365,6 +384,10 @@ class BaseHMM(ABC):
         return degrees[0]
 
     def _element_means(self, cells: np.ndarray, coeff=None) -> tuple[np.ndarray, str]:
+        return self._pack_coefficient(self._sampled_means(cells, coeff))
+
+    def _sampled_means(self, cells: np.ndarray, coeff=None) -> np.ndarray:
+        """Element means [N, n_el, ...] of ``coeff`` (default: the coefficient) on the sampling boxes of ``cells``, as sampled."""
         yq, w = self._quadrature_points()
         n_el, nq = yq.shape[:2]
         yflat = yq.reshape(-1, self._tdim).T
@@ -376,7 +399,7 @@ class BaseHMM(ABC):
             for k in range(len(cells)):
                 v = first if k == 0 else self._sample_one(c[k], yflat, coeff)
                 out[k] = np.tensordot(w, v.reshape((n_el, nq) + v.shape[1:]), axes=([0], [1]))
-        return self._pack_coefficient(out)
+        return out
 
     def _sample_batched(self, c: np.ndarray, yflat: np.ndarray, n_el: int, nq: int, w: np.ndarray, coeff=None):
         """Try ONE broadcast call A(x[3, N_c, 1], y[d, 1, npts]) -> [N_c, npts(, ...)] per chunk of cells; accept it only
@@ -603,6 +626,44 @@ class BaseHMM(ABC):
         plan, stream, M = block(0, len(cells))
         return stream.solve(plan, M, return_info=True)
 
+    def _polarisation_loads(self, cells: np.ndarray) -> tuple[np.ndarray, bool]:
+        """The polarisation of ``cells`` as ``plan.loads`` takes it, one load: (P[1, n_el, t], False) when every cell shares it, else
+        (P[N, 1, n_el, t], True).  A callable is sampled where the coefficient is sampled (``_sampled_means``)."""
+        P = self._polarisation
+        if not callable(P):
+            return (P[None], False) if P.ndim == 2 else (P[cells][:, None], True)
+        t = self._tensor_size()
+
+        def components_last(x, y):  # [t, ...] -> [..., t] over the broadcast of x and y: the layout the sampling takes a coefficient in
+            v = P(x, y)
+            if len(v) != t:
+                raise ValueError(f"the polarisation P(x, y) must return {t} components; got {len(v)}")
+            shape = np.broadcast(x[0], y[0]).shape
+            return np.stack([np.broadcast_to(np.asarray(c, dtype=float), shape) for c in v], axis=-1)
+
+        return np.ascontiguousarray(self._sampled_means(cells, components_last)[:, None]), True
+
+    def _load_block(self, cells: np.ndarray, **kw) -> LoadResponse:
+        """``plan.loads`` of the polarisation on ``cells``: the coefficient crosses the boundary as ``solve()`` sends it."""
+        stream, kind = self._coef_stream(cells)
+        coef = stream.per_cell if stream.method == "solve" else stream  # element means as the array every plan (and stand-in) takes
+        P, per_cell = self._polarisation_loads(cells)
+        return self._ensure_plan(kind).loads(coef, P, self._stratification(cells), per_cell=per_cell, **kw)
+
+    def _effective_polarisation(self, cells: np.ndarray) -> np.ndarray:
+        """P_eff[N, t] of ``cells`` (Levin: from the canonical correctors, on every route).  Under a process group every rank solves its
+        block and one more all-gather of t numbers per cell returns the field to every rank; a failing rank makes all ranks raise."""
+
+        def block(b, e):
+            r = self._load_block(cells[b:e])
+            return r.P_eff[:, 0], r.info
+
+        if self._sharded():
+            from .dist import run_sharded
+
+            return run_sharded(self._tensor_size(), len(cells), block, device=self._shard_device(), shape=(self._tensor_size(),))[0]
+        return block(0, len(cells))[0]
+
     def _strain_basis(self, cells: np.ndarray) -> tuple[np.ndarray, np.ndarray | None]:
         """G[c, a, i] = d phi_a / d x_i of the macro basis functions on ``cells`` and, for vector-valued spaces, W[c, b, m]: the Voigt
         strain (doubled shear) of the b-th basis function, b = a * bs + component.  For a scalar space the basis of xi is G itself (W None)."""
@@ -694,6 +755,13 @@ class BaseHMM(ABC):
         self._assemble_stiffness()
         A = self._A.copy()
         b = fem.assemble_load_vector(self._V_macro, self._f, self._rhs_degree)
+        if self._polarisation is not None:  # b_T = -vol(T)/vol(Y) W P_eff[T], before the Dirichlet lifting
+            cells = np.arange(self._msh.num_cells)
+            self.effective_polarisation = self._effective_polarisation(cells)
+            G, Wv = self._strain_basis(cells)
+            vol = self._msh.cell_volumes() / self._cell_mesh_area
+            bT = -vol[:, None] * np.einsum("cbm,cm->cb", G if Wv is None else Wv, self.effective_polarisation)
+            np.add.at(b, _unroll_dofs(self._msh.cells.astype(np.int64), self._bs).ravel(), bT.ravel())
         for bc in self._bcs:  # hmm.py:453-480, bc by bc
             idx, val = bc.unrolled()
             u_bc = np.zeros(self._num_global_dofs)
@@ -780,6 +848,32 @@ class BaseHMM(ABC):
         cat = lambda name: None if getattr(parts[0], name) is None else np.concatenate([getattr(r, name) for r in parts])
         return Reconstruction(xi, cat("mean_strain"), cat("mean_flux"), cat("energy"), cat("max_flux"), cat("argmax_element"), cat("A_eff"),
                               cat("info"), cat("strain"), cat("flux"), cells, *(cat(name) for name in REGION_FIELDS))
+
+    def load_response(self, cells=None, fields: bool = False, correctors: bool = False, chunk_cells: int | None = None) -> LoadResponse:
+        """The response of the sampling boxes of ``cells`` (default: every macro cell) to the polarisation alone (hommx_loads_source with
+        a load solve) -> ``LoadResponse`` with ``cells`` and one load: the effective polarisation, the energy of the
+        polarisation corrector, the mean and the largest total flux q = P + A eps(chi_P) and where it is reached; with ``fields`` the
+        per-element strain and total flux [N, 1, n_el, t], with ``correctors`` the corrector [N, 1, n_nodes * bs].
+
+        By linearity the micro stress under the macro strain of a solution plus the prestress is
+        ``reconstruct(...).flux + load_response(...).flux[:, 0]``.  Not on a micro mesh of the frontal mesh route (the load solve needs
+        the tree route).  The cells run in chunks of ``chunk_cells`` (default: 256 MB of sampled loads and outputs).  Under a process group
+        this runs on the calling rank alone, for the cells it is given: there is no collective."""
+        if self._polarisation is None:
+            raise RuntimeError("load_response() needs a polarisation: call set_polarisation() first")
+        cells = np.arange(self._msh.num_cells) if cells is None else np.asarray(cells, dtype=np.int64).ravel()
+        if len(cells) == 0:
+            raise ValueError("load_response() needs at least one macro cell")
+        if chunk_cells is None:
+            n_el, t = self._cell_mesh.num_cells, self._tensor_size()
+            n_dof = (int(self._periodic_to_micro_nodes().max()) + 1) * self._bs if correctors else 0
+            # doubles per cell: P[n_el, t] | P_eff, energy, stats, A_eff | strain and flux | corrector (info: 4 bytes more)
+            chunk_cells = (256 << 20) // (8 * (n_el * t + (t + 1 + t + 2 + t * t) + (2 * n_el * t if fields else 0) + n_dof) + 4)
+        ch = max(1, int(chunk_cells))
+        parts = [self._load_block(cells[b:b + ch], response=True, fields=fields, return_correctors=correctors) for b in range(0, len(cells), ch)]
+        cat = lambda name: None if getattr(parts[0], name) is None else np.concatenate([getattr(r, name) for r in parts])
+        return LoadResponse(cat("P_eff"), cat("A_eff"), cat("info"), cat("energy"), cat("mean_flux"), cat("max_flux"), cat("argmax_element"),
+                            cat("strain"), cat("flux"), cat("correctors"), cells)
 
     def _parameter_directions(self) -> tuple[tuple, np.ndarray]:
         """(names, directions[n_dirs, n_el(, n_comp)]) of the parameters of a ``TwoPhase`` or affine ``Separable`` coefficient: the element

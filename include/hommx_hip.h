@@ -320,6 +320,59 @@ int hommx_sensitivity_source_device(hommx_plan* plan, int64_t n_cells, const hom
                                     const hommx_sens_args* args, void* stream);
 
 /*
+ * User-supplied polarisation loads of the cell problem: a prescribed micro flux / stress field P(y), such as a
+ * thermal eigenstress -A : alpha dT, a prestress, the gravity term of Darcy flow or the residual of a Newton step.  Per macro cell the
+ * caller gives n_loads fields P^l[n_el][t], constant per micro element, components in the order of hommx_reconstruct_batch's flux
+ * (Poisson: the flux vector; elasticity: s00, s11[, s22], s01[, s02, s12], shear NOT doubled).  With eps(z)_K the strain of a periodic
+ * field z on element K (shear doubled, M applied, as s_K of hommx_reconstruct_batch) and chi^m the canonical correctors, exactly on the
+ * discrete problem:
+ *   corrector      a(chi_l, z) = -sum_K |K| P^l_K . eps(z)_K  for all z                 (P^l = material(coef) e_m gives chi_l = chi^m)
+ *   total flux     q^l_K       = P^l_K + material(coef_K) eps(chi_l)_K
+ *   P_eff[c][l]    = sum_K |K| q^l_K = sum_K |K| (e_m + eps(chi^m)_K) . P^l_K, m < t       (Levin: from the canonical correctors alone)
+ *   energy[c][l][l'] = sum_K |K| eps(chi_l)_K . material(coef_K) eps(chi_l')_K              (symmetric, bitwise)
+ * P_eff is all a macro solve needs (its load gains -vol(T) eps_macro(v) . P_eff); it is computed by the Levin form, which needs no
+ * second elimination, on EVERY plan.  The response outputs come from a solve for the loads themselves: one more corrector pass of the
+ * blocked family with the load rows replaced (a fused 2D plan gets a blocked workspace on the first such call; a mesh plan needs the tree
+ * route).
+ *
+ *   n_loads     1 .. t of the plan (callers loop for more)
+ *   per_cell    0: P[n_loads][n_el][t], shared by all cells; 1: P[n_cells][n_loads][n_el][t]
+ *   P_eff       [n_cells][n_loads][t], required
+ *   A_eff, info of the canonical pass, as hommx_solve_batch, or NULL
+ *   response, every one optional, any of them triggers the load solve:
+ *   energy      [n_cells][n_loads][n_loads]
+ *   stats       [n_cells][n_loads][t+2] = [sum |K| q^l_K (t) | max_K |q^l_K| | smallest K reaching it]; norms and rule of
+ *               hommx_reconstruct_batch (Frobenius for elasticity); the first t equal P_eff up to rounding (two independent paths)
+ *   strain, flux [n_cells][n_loads][n_el][t]: eps(chi_l)_K and q^l_K; both or neither
+ *   correctors  [n_cells][n_loads][ndof], mean-free per component, dof order of hommx_solve_batch_correctors
+ * src, M: as hommx_reconstruct_source.  HOMMX_EINVAL, before the plan's device is made current: a null plan, source or argument struct,
+ * n_loads out of range, a null P or P_eff, one of strain / flux without the other.  HOMMX_EINVAL as well, before any work: a response output on a
+ * plan of the frontal mesh route ("mesh_front": it builds its loads in the basis of the canonical ones; create the plan with
+ * HOMMX_MESH_FLAG_TREE, the tree route, for these).  The correctors of
+ * one chunk (HOMMX_RECON_MEM_MB, the chunk rule of the reconstruction; a response holds two blocks of t correctors per cell) live in
+ * plan-owned scratch.  A cell's outputs do not depend on its batch position, the chunking or which outputs are requested (fixed-order
+ * reductions).  A cell whose elimination flags a pivot keeps its info; no other cell's outputs change.  The host entry sends a shared P
+ * with the source's shared arrays once; a per-cell P and a sampled stream go in, and every output comes back, chunk by chunk.
+ */
+typedef struct hommx_load_args {
+  int32_t n_loads;
+  int32_t per_cell;
+  const double* P;
+  double* P_eff;
+  double* A_eff;
+  double* energy;
+  double* stats;
+  double* strain;
+  double* flux;
+  double* correctors;
+  int32_t* info;
+} hommx_load_args;
+int hommx_loads_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_load_args* args);
+/* Same with DEVICE pointers (in *src and *args as well; the structs themselves are host memory), asynchronous on `stream`. */
+int hommx_loads_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                              const hommx_load_args* args, void* stream);
+
+/*
  * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
  * periodic: the caller folds the mesh vertices into n_nodes independent (periodic) nodes -- cell_problem.py:38-300's slave -> master
  * map -- and passes, per element, the periodic node of every vertex and the UNFOLDED vertex coordinates (gradients and volumes).
