@@ -321,6 +321,55 @@ void fill_tables(Geo& G) {
   }
 }
 
+// ---- magnitude normalisation (blocked_internal.h) -------------------------------------------------------------------------------------
+// one 256-thread workgroup per cell (grid-stride): largest exponent field of the cell's coefficient stream (wave butterflies, four wave
+// maxima through LDS), then the scaled copy.  8 max|coef| |M|_F^2 < 2^esh <= 32 max|coef| |M|_F^2 (exponents of the two factors + 5): the largest stiffness diagonal, sum over the elements of a node
+// of vol g~ . C g~, comes out of order one or below in 2D and below in 3D.
+__global__ __launch_bounds__(256) void k_coef_normalise(const double* __restrict__ coef, const double* __restrict__ Mall, double* __restrict__ scaled,
+                                                        int32_t* __restrict__ esh, long long per_cell, int dim, long long nc) {
+  __shared__ int red[4];
+  const int tid = threadIdx.x;
+  for (long long cell = blockIdx.x; cell < nc; cell += gridDim.x) {
+    const double* cc = coef + cell * per_cell;
+    int ef = 0;
+    for (long long i = tid; i < per_cell; i += 256) ef = max(ef, (__double2hiint(cc[i]) >> 20) & 0x7ff);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) ef = max(ef, __shfl_xor(ef, o, 64));
+    if ((tid & 63) == 0) red[tid >> 6] = ef;
+    __syncthreads();
+    ef = max(max(red[0], red[1]), max(red[2], red[3]));
+    double m2 = (double)dim;
+    if (Mall) {
+      m2 = 0.0;
+      for (int i = 0; i < dim * dim; ++i) m2 += Mall[cell * dim * dim + i] * Mall[cell * dim * dim + i];
+    }
+    const int fm = (__double2hiint(m2) >> 20) & 0x7ff;
+    const int sh = (ef == 0 || ef == 0x7ff) ? 0 : (ef - 1023) + (fm == 0 || fm == 0x7ff ? 0 : fm - 1023) + 5;
+    double* sc = scaled + cell * per_cell;
+    for (long long i = tid; i < per_cell; i += 256) sc[i] = ldexp(cc[i], -sh);
+    if (tid == 0) esh[cell] = sh;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void k_scale_cells(double* __restrict__ buf, long long per_cell, const int32_t* __restrict__ esh, int sign,
+                                                     long long nc) {
+  const long long total = nc * per_cell;
+  for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += (long long)gridDim.x * blockDim.x)
+    buf[w] = ldexp(buf[w], sign * esh[w / per_cell]);
+}
+
+void launch_coef_normalise(const Geo& G, const double* coef, const double* Mm, long long nc, hipStream_t st, double* scaled, int32_t* esh) {
+  if (nc <= 0) return;
+  hipLaunchKernelGGL(k_coef_normalise, dim3((unsigned)std::min(nc, 1ll << 20)), dim3(256), 0, st, coef, Mm, scaled, esh,
+                     (long long)G.n_el * G.ncomp, G.dim, nc);
+}
+
+void launch_scale_cells(double* buf, long long per_cell, const int32_t* esh, int sign, long long nc, hipStream_t st) {
+  if (nc <= 0) return;
+  hipLaunchKernelGGL(k_scale_cells, dim3((unsigned)std::min((nc * per_cell + 255) / 256, 1ll << 20)), dim3(256), 0, st, buf, per_cell, esh, sign, nc);
+}
+
 void launch_assembly(BlockedWorkspace* ws, const double* coef, const double* Mm, long long nc, hipStream_t st, double* Kst, double* Brhs,
                      double* C0) {
   const Geo& G = ws->G;

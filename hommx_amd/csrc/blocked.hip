@@ -210,14 +210,19 @@ int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, 
     const double* coef = d_coef + c0 * G.n_el * G.ncomp;
     const double* Mm = d_M ? d_M + c0 * G.dim * G.dim : nullptr;
     double* out = d_out + c0 * G.t * G.t;
-    launch_assembly(ws, coef, Mm, nc, st, pb.Kst, pb.Brhs, pb.C0);
-    if (loads) HIP_TRY(launch_assemble_loads(ws, *loads, c0, Mm, nc, st, pb.Brhs));
+    // K1 reads the cell at magnitude one (blocked_internal.h, launch_coef_normalise); the tensors go back to the caller's magnitude below
+    int32_t* esh = pb.esh();
+    launch_coef_normalise(G, coef, Mm, nc, st, pb.Cn, esh);
+    launch_assembly(ws, pb.Cn, Mm, nc, st, pb.Kst, pb.Brhs, pb.C0);
+    if (loads) {
+      HIP_TRY(launch_assemble_loads(ws, *loads, c0, Mm, nc, st, pb.Brhs));
+      launch_scale_cells(pb.Brhs, (long long)G.t * G.bs * G.nn, esh, -1, nc, st);
+    }
     if (d_corr || ws->route == Route::Plane) {
       if (int rc = plane_eliminate(c, out, d_corr ? d_corr + c0 * (long long)G.t * G.nn * G.bs : nullptr)) return rc;
-      continue;
-    }
-    if (ws->route == Route::SmallWave) HIP_TRY(launch_small_wave(G, pb.Kst, pb.Brhs, pb.C0, out, c.info, nc, st));
+    } else if (ws->route == Route::SmallWave) HIP_TRY(launch_small_wave(G, pb.Kst, pb.Brhs, pb.C0, out, c.info, nc, st));
     else HIP_TRY(launch_small_fused(G, pb.Kst, pb.Brhs, pb.C0, out, c.info, nc, ws->small_nw, st));
+    launch_scale_cells(out, (long long)G.t * G.t, esh, +1, nc, st);
     HIP_TRY(hipGetLastError());
   }
   return 0;

@@ -35,6 +35,9 @@ struct PlaneBufs {
   long long chunk = 0;
   void* block = nullptr;
   double *Kst = nullptr, *Brhs = nullptr, *C0 = nullptr;
+  double* Cn = nullptr;        // magnitude normalisation: the scaled coefficient stream of the chunk
+  double* EshSlot = nullptr;   // its exponents: carved from the block like the others (one 8-byte slot per cell), read through esh()
+  int32_t* esh() const { return reinterpret_cast<int32_t*>(EshSlot); }
   double *S = nullptr, *W = nullptr, *Sl = nullptr, *V = nullptr, *X = nullptr, *T = nullptr;
   double *R = nullptr, *Rl = nullptr, *Vr = nullptr, *Gm = nullptr;
   // corrector mode: per eliminated plane the inverse Schur block, the arrow block and the load rows are kept
@@ -155,6 +158,14 @@ void fill_tables(Geo& G);
 // its buffers (a plan may serve effective tensors on one route and correctors on the other, with different chunk sizes)
 void launch_assembly(BlockedWorkspace* ws, const double* coef, const double* Mm, long long nc, hipStream_t st, double* Kst, double* Brhs,
                      double* C0);
+
+// assembly.hip: magnitude normalisation of the blocked family.  The exchange sweeps of the one-launch kernels and of the tree's
+// leaves (sweep_acc.h) lose eps |d| on a pivot |d| >> 1, so every route eliminates a cell whose coefficient is scaled by a power of two
+// 2^-esh[cell] that brings the stiffness diagonal to order one: `scaled` = coef * 2^-esh is what K1 reads, and the tensors are scaled back
+// by launch_scale_cells(out, t t, esh, +1).  Exact, and the correctors do not see it; user-supplied loads (launch_assemble_loads) are scaled
+// with launch_scale_cells(Brhs, ., esh, -1) so that their correctors do not either.  NaN / Inf / all-zero cells take esh = 0.
+void launch_coef_normalise(const Geo& G, const double* coef, const double* Mm, long long nc, hipStream_t st, double* scaled, int32_t* esh);
+void launch_scale_cells(double* buf, long long per_cell, const int32_t* esh, int sign, long long nc, hipStream_t st);
 
 // plane.hip: buffers for batches of up to `ncells` (chunked by the memory budget), with the history set when correctors are asked for
 int plane_reserve(BlockedWorkspace* ws, long long ncells, bool correctors);

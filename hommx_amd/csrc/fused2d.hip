@@ -119,6 +119,23 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
   const unsigned matOff = accl::lds_offset(&L.mat[0]);
   const unsigned haloA = matOff + 8u * (unsigned)(p0 * P + j);  // halo row = row index p0 - 1: copy of row NB - 1
 
+  // Coefficient source (kernels.h): the element stream coef[cell][2 n^2], or a device sampler fed by two numbers per cell
+  const int mode = src.mode;
+  const unsigned char* mask = static_cast<const unsigned char*>(src.table);
+  const double* table = static_cast<const double*>(src.table);
+  const double* cc = mode == COEF_STREAM ? coef + cell * (2ll * n * n) : coef + cell * 2;
+  // element stream: the loads of the normalisation pass (below) go out first, NB NB / 64 double2 per lane all in flight at once, so that their
+  // latency passes under the zeroing of the staging matrix and the loads of M
+  constexpr int NL = NB * NB / 64;
+  double2 pv[NL];
+  if (mode == COEF_STREAM) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      const int el = 2 * l + 128 * i;
+      pv[i] = el < 2 * n * n ? *reinterpret_cast<const double2*>(cc + el) : double2{0.0, 0.0};
+    }
+  }
+
   // zero the staging matrix once
   for (int i = l; i < (NB + 1) * P; i += 64) L.mat[i] = 0.0;
   if (l == 0) L.cenat[0] = 0.0;
@@ -134,11 +151,6 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
   const double ga = uniform_f64(0.5 * (m00 * m01 + m10 * m11));
   const double ab = uniform_f64(al - 2.0 * ga + be);
 
-  // Coefficient source (kernels.h): the element stream coef[cell][2 n^2], or a device sampler fed by two numbers per cell
-  const int mode = src.mode;
-  const unsigned char* mask = static_cast<const unsigned char*>(src.table);
-  const double* table = static_cast<const double*>(src.table);
-  const double* cc = mode == COEF_STREAM ? coef + cell * (2ll * n * n) : coef + cell * 2;
   double ph0 = 0.0, ph1 = 0.0;  // phase values / (a, b)
   if (mode != COEF_STREAM) {
     ph0 = cc[0];
@@ -151,26 +163,64 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
       acc = add_rn(acc, mul_rn(src.weights[q], div_rn(1.0, add_rn(ph0, mul_rn(ph1, table[el * nq + q])))));
     return acc;
   };
+  // the two coefficients of square `el / 2` as the source gives them
+  auto load_pair = [&](long long el, double& a0, double& a1) {
+    if (mode == COEF_TWO_PHASE) {
+      const uchar2 mk = *reinterpret_cast<const uchar2*>(mask + el);
+      a0 = mk.x ? ph1 : ph0;
+      a1 = mk.y ? ph1 : ph0;
+    } else if (mode == COEF_AFFINE) {
+      const double2 g2 = *reinterpret_cast<const double2*>(table + el);
+      a0 = add_rn(ph0, mul_rn(ph1, g2.x));
+      a1 = add_rn(ph0, mul_rn(ph1, g2.y));
+    } else if (mode == COEF_RECIPROCAL) {
+      a0 = sample(el);
+      a1 = sample(el + 1);
+    } else {
+      const double2 v = *reinterpret_cast<const double2*>(cc + el);
+      a0 = v.x; a1 = v.y;
+    }
+  };
+  // ---- magnitude normalisation ---------------------------------------------------
+  // The exchange sweep (sweep_acc.h) carries the column rule as 1/d - 1, which rounds 1/d on an absolute grid of eps: a pivot |d| >> 1
+  // costs eps |d| of relative accuracy.  The Schur complements of an SPD matrix have diagonals no larger than the matrix's own, and the
+  // stencil diagonal is at most 6 (al + be) max|a|, so the coefficient is scaled HERE, where the kernel first touches it, by the power of two
+  // 2^-esh that brings this bound below 1; A_H is scaled back at the output.  Powers of two: exact, the correctors and the factor record's
+  // products are of degree 0 in the scale.  A NaN / Inf / all-zero cell takes no scale and is flagged by its pivots as before.
+  // The largest exponent takes one more pass over the cell's coefficients.  Element stream (what bench.py runs): 16 KB at n = 32, loaded at
+  // the top of the kernel (pv); the rows stream from L2 afterwards.
+  // Sampler modes: through the sampler itself, so that a sampled cell and the same cell as a stream take the same exponent and stay
+  // bit-identical -- one byte per element (TWO_PHASE), one multiply-add (AFFINE), the whole quadrature a second time (RECIPROCAL; DESIGN.md
+  // 4.11 has the cost).
+  int esh;
+  {
+    int ef = 0;
+    if (mode == COEF_STREAM) {
+      int hm = 0;  // only the high words are looked at
+#pragma unroll
+      for (int i = 0; i < NL; ++i) hm = max(hm, max(__double2hiint(pv[i].x) & 0x7fffffff, __double2hiint(pv[i].y) & 0x7fffffff));
+      ef = hm >> 20;
+    } else {
+      for (long long el = 2 * l; el < 2ll * n * n; el += 128) {
+        double a0, a1;
+        load_pair(el, a0, a1);
+        const int f0 = (__double2hiint(a0) >> 20) & 0x7ff, f1 = (__double2hiint(a1) >> 20) & 0x7ff;
+        ef = max(ef, max(f0, f1));
+      }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) ef = max(ef, __shfl_xor(ef, off, 64));
+    const int fm = (__double2hiint(6.0 * (al + be)) >> 20) & 0x7ff;
+    const int sh = (ef == 0 || ef == 0x7ff ? 0 : ef - 1023) + (fm == 0 || fm == 0x7ff ? 0 : fm - 1023) + 2;
+    esh = __builtin_amdgcn_readfirstlane(ef == 0 || ef == 0x7ff ? 0 : sh);
+  }
   auto load_row = [&](int jc) {
     CoefRow r;
     r.a0 = 0.0; r.a1 = 0.0;
     if (valid) {
-      const long long el = 2 * (jc * n + cn);
-      if (mode == COEF_TWO_PHASE) {
-        const uchar2 mk = *reinterpret_cast<const uchar2*>(mask + el);
-        r.a0 = mk.x ? ph1 : ph0;
-        r.a1 = mk.y ? ph1 : ph0;
-      } else if (mode == COEF_AFFINE) {
-        const double2 g2 = *reinterpret_cast<const double2*>(table + el);
-        r.a0 = add_rn(ph0, mul_rn(ph1, g2.x));
-        r.a1 = add_rn(ph0, mul_rn(ph1, g2.y));
-      } else if (mode == COEF_RECIPROCAL) {
-        r.a0 = sample(el);
-        r.a1 = sample(el + 1);
-      } else {
-        const double2 v = *reinterpret_cast<const double2*>(cc + el);
-        r.a0 = v.x; r.a1 = v.y;
-      }
+      load_pair(2 * (jc * n + cn), r.a0, r.a1);
+      r.a0 = ldexp(r.a0, -esh);
+      r.a1 = ldexp(r.a1, -esh);
     }
     r.a0m = __shfl(r.a0, lb + cm, 64);
     r.a1m = __shfl(r.a1, lb + cm, 64);
@@ -689,10 +739,10 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
     const double t00 = m00 * g00 + m01 * g01, t01 = m00 * g01 + m01 * g11;
     const double t10 = m10 * g00 + m11 * g01, t11 = m10 * g01 + m11 * g11;
     double* o = out + cell * 4;
-    o[0] = c0 + sc * (t00 * m00 + t01 * m01);
-    o[1] = sc * (t00 * m10 + t01 * m11);
-    o[2] = sc * (t10 * m00 + t11 * m01);
-    o[3] = c0 + sc * (t10 * m10 + t11 * m11);
+    o[0] = ldexp(c0 + sc * (t00 * m00 + t01 * m01), esh);  // back to the caller's magnitude
+    o[1] = ldexp(sc * (t00 * m10 + t01 * m11), esh);
+    o[2] = ldexp(sc * (t10 * m00 + t11 * m01), esh);
+    o[3] = ldexp(c0 + sc * (t10 * m10 + t11 * m11), esh);
     if (info) info[cell] = bad ? badstep : 0;
   }
 #undef OWN

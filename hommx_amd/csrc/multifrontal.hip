@@ -90,6 +90,8 @@ struct MfPlan {
   long long chunk = 0;
   double *arena = nullptr, *scratch = nullptr, *vbuf = nullptr;
   double *Kst = nullptr, *Brhs = nullptr, *C0 = nullptr;  // K1 output of this route's chunks (the plane elimination keeps its own)
+  double* Cn = nullptr;    // magnitude normalisation (blocked_internal.h): the scaled coefficient stream of the chunk
+  int32_t* Esh = nullptr;  // and the exponent of every cell
   // side streams of mf_solve: a chunk runs as up to four pieces side by side (HOMMX_MF_STREAMS = 1: off, 2 .. 4)
   int streams = 4;
   hipStream_t side[3] = {nullptr, nullptr, nullptr};
@@ -253,8 +255,9 @@ void mf_plan_destroy(MfPlan* p) {
     if (g.d_upos) (void)hipFree(g.d_upos);
     if (g.d_tilemap) (void)hipFree(g.d_tilemap);
   }
-  for (double* q : {p->arena, p->scratch, p->vbuf, p->Kst, p->Brhs, p->C0})
+  for (double* q : {p->arena, p->scratch, p->vbuf, p->Kst, p->Brhs, p->C0, p->Cn})
     if (q) (void)hipFree(q);
+  if (p->Esh) (void)hipFree(p->Esh);
   for (int k = 0; k < 3; ++k) {
     if (p->side[k]) (void)hipStreamDestroy(p->side[k]);
     if (p->ev_join[k]) (void)hipEventDestroy(p->ev_join[k]);
@@ -850,7 +853,7 @@ __global__ __launch_bounds__(256) void k_mf_bs_store(MfGroupDev g, const double*
 // ---------------------------------------------------------------------------------------------------------------
 int mf_reserve(BlockedWorkspace* ws, MfPlan* P, long long ncells, bool ahead) {
   const Geo& G = ws->G;
-  const long long stencil = (long long)G.ncode * G.bs * G.bs * G.nn + (long long)G.t * G.bs * G.nn + 36;
+  const long long stencil = (long long)G.ncode * G.bs * G.bs * G.nn + (long long)G.t * G.bs * G.nn + 36 + (long long)G.n_el * G.ncomp + 1;
   const long long per_cell = 8ll * (P->arena_per_cell + P->scratch_per_cell + P->vbuf_per_cell + stencil);
   // Fronts are big (C4 / C5: 0.2 GB per cell) and the card has 288 GB, but a call pays for what it allocates (2.5 - 3 s per 64 GB
   // measured) and the throughput is nearly flat from 256 cells per chunk (C4: 2,390 / 2,510 / 2,580 / 2,655 / 2,654 solves/s at 64 / 128 /
@@ -877,10 +880,12 @@ int mf_reserve(BlockedWorkspace* ws, MfPlan* P, long long ncells, bool ahead) {
         if (mn > 0 && ty >= 2 * ws->tile_sb) (void)ensure_tilemap(ws, ty);
       }
   if (chunk <= P->chunk) return 0;
-  for (double** p : {&P->arena, &P->scratch, &P->vbuf, &P->Kst, &P->Brhs, &P->C0}) {
+  for (double** p : {&P->arena, &P->scratch, &P->vbuf, &P->Kst, &P->Brhs, &P->C0, &P->Cn}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
+  if (P->Esh) (void)hipFree(P->Esh);
+  P->Esh = nullptr;
   P->chunk = 0;
   HIP_TRY(hipMalloc(&P->arena, 8ll * chunk * P->arena_per_cell));
   HIP_TRY(hipMalloc(&P->scratch, 8ll * chunk * P->scratch_per_cell));
@@ -888,6 +893,8 @@ int mf_reserve(BlockedWorkspace* ws, MfPlan* P, long long ncells, bool ahead) {
   HIP_TRY(hipMalloc(&P->Kst, 8ll * chunk * G.ncode * G.bs * G.bs * G.nn));
   HIP_TRY(hipMalloc(&P->Brhs, 8ll * chunk * G.t * G.bs * G.nn));
   HIP_TRY(hipMalloc(&P->C0, 8ll * chunk * 36));
+  HIP_TRY(hipMalloc(&P->Cn, 8ll * chunk * G.n_el * G.ncomp));
+  HIP_TRY(hipMalloc(&P->Esh, sizeof(int32_t) * chunk));
   P->chunk = chunk;
   return 0;
 }
@@ -1080,9 +1087,16 @@ int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_
       const double* coef = d_coef + h.c0 * G.n_el * G.ncomp;
       const double* Mm = d_M ? d_M + h.c0 * G.dim * G.dim : nullptr;
       double *Kst = P->Kst + h.base * G.ncode * bs * bs * G.nn, *Brhs = P->Brhs + h.base * G.t * bs * G.nn, *C0 = P->C0 + h.base * 36;
-      if (ws->mesh_tables) launch_mesh_assembly(ws->mesh, coef, Mm, h.nc, h.st, Kst, Brhs, C0);  // the only launch that knows the geometry
-      else launch_assembly(ws, coef, Mm, h.nc, h.st, Kst, Brhs, C0);
-      if (loads) HIP_TRY_OR(join(), launch_assemble_loads(ws, *loads, h.c0, Mm, h.nc, h.st, Brhs));
+      // K1 reads the cell at magnitude one (blocked_internal.h, launch_coef_normalise); k_mf_finalize's tensors are scaled back below
+      double* Cn = P->Cn + h.base * G.n_el * G.ncomp;
+      int32_t* esh = P->Esh + h.base;
+      launch_coef_normalise(G, coef, Mm, h.nc, h.st, Cn, esh);
+      if (ws->mesh_tables) launch_mesh_assembly(ws->mesh, Cn, Mm, h.nc, h.st, Kst, Brhs, C0);  // the only launch that knows the geometry
+      else launch_assembly(ws, Cn, Mm, h.nc, h.st, Kst, Brhs, C0);
+      if (loads) {
+        HIP_TRY_OR(join(), launch_assemble_loads(ws, *loads, h.c0, Mm, h.nc, h.st, Brhs));
+        launch_scale_cells(Brhs, (long long)G.t * bs * G.nn, esh, -1, h.nc, h.st);
+      }
     }
     int gi = 0;
     for (const MfGroup& mg : P->groups) {  // launches of the pieces interleaved: all queues fill at the same pace
@@ -1094,6 +1108,7 @@ int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_
       const MfHalf& h = halves[k];
       hipLaunchKernelGGL(k_mf_finalize, dim3(nblk(h.nc * G.t * G.t)), dim3(256), 0, h.st, P->C0 + h.base * 36,
                          P->arena + h.base * P->arena_per_cell, root.offF, root.L, root.sp, root.rb, G.t, d_out + h.c0 * G.t * G.t, h.nc);
+      launch_scale_cells(d_out + h.c0 * G.t * G.t, (long long)G.t * G.t, P->Esh + h.base, +1, h.nc, h.st);
     }
     if (d_corr) {  // back substitution: root first; then the mean of every component goes (cell_problem.py:349-361, 382)
       for (auto it = P->groups.rbegin(); it != P->groups.rend(); ++it)

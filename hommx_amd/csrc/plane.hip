@@ -519,7 +519,8 @@ struct PlaneBuf {
 
 static std::vector<PlaneBuf> main_set(PlaneBufs& pb, const Geo& G) {
   const long long mat = (long long)G.Bp * G.Bp, rows = 16ll * G.Bp;
-  return {{&pb.Kst, (long long)G.ncode * G.bs * G.bs * G.nn}, {&pb.Brhs, (long long)G.t * G.bs * G.nn}, {&pb.C0, 36}, {&pb.S, mat}, {&pb.W, mat},
+  return {{&pb.Kst, (long long)G.ncode * G.bs * G.bs * G.nn}, {&pb.Brhs, (long long)G.t * G.bs * G.nn}, {&pb.C0, 36}, {&pb.Cn, (long long)G.n_el * G.ncomp},
+          {&pb.EshSlot, 1}, {&pb.S, mat}, {&pb.W, mat},
           {&pb.Sl, mat}, {&pb.V, mat}, {&pb.X, mat}, {&pb.T, mat}, {&pb.R, rows}, {&pb.Rl, rows}, {&pb.Vr, rows}, {&pb.Gm, 256}};
 }
 

@@ -21,7 +21,7 @@ struct Cfg {
 // d comes out of v_readlane, i.e. out of SGPRs, and this keeps the test on the scalar unit (a v_cmp_f64 per pivot is a
 // VALU issue slot, and those are what the sweep is short of).
 __device__ __forceinline__ int bad_pivot_hi(int hi) {
-  return (unsigned)(hi - 1) >= 0x7fefffffu;  // hi in [0x00000001, 0x7fefffff] <=> positive normal finite
+  return (unsigned)(hi - 0x00100000) >= 0x7fe00000u;  // hi in [0x00100000, 0x7fefffff] <=> positive, normal, finite (as readlane_neg_pivot, sweep_acc.h)
 }
 __device__ __forceinline__ int bad_pivot(double d) { return bad_pivot_hi(__double2hiint(d)); }
 // v_readlane of a double that also flags an unusable pivot, tested on the SGPR the high word arrives in

@@ -1,0 +1,237 @@
+"""GPU side of the accuracy and pivot-contract tests: runs the case groups of tests/accuracy_ref.py through the plans and returns raw
+results.  Nothing here computes a bound.  Environment knobs are read when a plan is created, so the forced groups run this module as a
+child process:  python accuracy_gpu.py <accuracy|pivot> <group> <out.npz>."""
+
+from __future__ import annotations
+
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+import accuracy_ref as R
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def skey(kind, dim, n, flags):
+    return f"{kind}_{dim}_{n}_{flags}"
+
+
+def mkey(kind, builder, args, route):
+    return f"{kind}_{builder}_{'x'.join(map(str, args))}_{route}"
+
+
+def _plan(kernel, kind, dim, n, flags):
+    from hommx_amd import MicroCellPlan
+
+    p = MicroCellPlan(dim, n, kind, flags=flags)
+    assert p.kernel == kernel, (p.kernel, kernel, kind, dim, n, flags)
+    return p
+
+
+def _mesh_plan(kernel, kind, msh, route):
+    from hommx_amd import MicroCellPlan
+
+    p = MicroCellPlan.from_mesh(msh, kind, route=route)
+    assert p.kernel == kernel, (p.kernel, kernel)
+    return p
+
+
+def _families(kind):
+    return [(f, m) for f in R.FAMILIES[kind] for m in (False, True)]
+
+
+def run_accuracy_group(group: str) -> dict:
+    """Every structured case of the group (and, in the default group, the mesh and corrector cases), every family with and without M, and
+    the magnitude sweep of the group's kernel families."""
+    out = {}
+    for kernel, kind, dim, n, flags in R.STRUCTURED_CASES[group]:
+        p = _plan(kernel, kind, dim, n, flags)
+        for family, with_M in _families(kind):
+            coef, M = R.structured_inputs(kind, dim, n, family, with_M)
+            A, info = p.solve(coef, M, return_info=True)
+            out[f"A|{skey(kind, dim, n, flags)}|{family}|{int(with_M)}"] = A
+            out[f"info|{skey(kind, dim, n, flags)}|{family}|{int(with_M)}"] = info
+    for g, kernel, kind, dim, n, flags in R.SWEEP_CASES:
+        if g != group:
+            continue
+        p = _plan(kernel, kind, dim, n, flags)
+        coef, M = R.structured_inputs(kind, dim, n, "log2", True)
+        for k in R.SWEEP_K:
+            A, info = p.solve(coef * 2.0**k, M, return_info=True)
+            out[f"sweepA|{skey(kind, dim, n, flags)}|{k}"] = A
+            out[f"sweepinfo|{skey(kind, dim, n, flags)}|{k}"] = info
+    if group != "default":
+        return out
+    for kernel, kind, builder, args, route in R.MESH_CASES:
+        for family, with_M in _families(kind):
+            msh, coef, M = R.mesh_inputs(kind, builder, args, family, with_M)
+            p = _mesh_plan(kernel, kind, msh, route)
+            A, info = p.solve(coef, M, return_info=True)
+            out[f"A|{mkey(kind, builder, args, route)}|{family}|{int(with_M)}"] = A
+            out[f"info|{mkey(kind, builder, args, route)}|{family}|{int(with_M)}"] = info
+    kernel, kind, builder, args, route = R.SWEEP_MESH
+    msh, coef, M = R.mesh_inputs(kind, builder, args, "log2", True)
+    p = _mesh_plan(kernel, kind, msh, route)
+    for k in R.SWEEP_K:
+        A, info = p.solve(coef * 2.0**k, M, return_info=True)
+        out[f"sweepA|{mkey(kind, builder, args, route)}|{k}"] = A
+        out[f"sweepinfo|{mkey(kind, builder, args, route)}|{k}"] = info
+    for ckernel, kind, dim, n, _ in R.CORRECTOR_CASES:
+        from hommx_amd import MicroCellPlan
+
+        p = MicroCellPlan(dim, n, kind)
+        assert p.corrector_kernel == ckernel, (p.corrector_kernel, ckernel)
+        for family, with_M in _families(kind):
+            coef, M = R.structured_inputs(kind, dim, n, family, with_M)
+            A, chi, info = p.solve(coef, M, return_info=True, return_correctors=True)
+            out[f"corrA|{skey(kind, dim, n, 0)}|{family}|{int(with_M)}"] = A
+            out[f"corr|{skey(kind, dim, n, 0)}|{family}|{int(with_M)}"] = chi
+            out[f"corrinfo|{skey(kind, dim, n, 0)}|{family}|{int(with_M)}"] = info
+    # correctors and user-supplied loads with coefficient AND loads scaled by 2^k
+    for kind, dim, n in R.SWEEP_LOAD_CASES:
+        from hommx_amd import MicroCellPlan
+
+        p = MicroCellPlan(dim, n, kind)
+        coef, M = R.structured_inputs(kind, dim, n, "log2", True)
+        P = R.load_inputs(kind, dim, n)
+        for k in R.SWEEP_LOAD_K:
+            A, chi, info = p.solve(coef * 2.0**k, M, return_info=True, return_correctors=True)
+            r = p.loads(coef * 2.0**k, P * 2.0**k, M, response=True, return_correctors=True)
+            tail = f"{skey(kind, dim, n, 0)}|{k}"
+            out["lsw_chi|" + tail], out["lsw_info|" + tail] = chi, np.maximum(info, r.info)
+            out["lsw_Peff|" + tail], out["lsw_energy|" + tail], out["lsw_mean|" + tail] = r.P_eff, r.energy, r.mean_flux
+            out["lsw_lchi|" + tail] = r.correctors
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# pivot contract: localized failures
+# ------------------------------------------------------------------------------------------------------------------------------
+
+# (group, kernel, kind, dim, n, flags) and the mesh cases
+PIVOT_CASES = [("default", "fused2d", "poisson", 2, 5, 0), ("default", "fused2d", "poisson", 2, 17, 0),
+               ("default", "small_wave", "elasticity", 2, 10, 0), ("default", "small_wave", "poisson", 3, 6, 0),
+               ("default", "small_fused", "poisson", 3, 7, 0), ("default", "multifrontal", "elasticity", 3, 5, 0),
+               ("plane", "blocked", "poisson", 3, 6, 0)]
+PIVOT_MESH = [R.MESH_CASES[0], R.MESH_CASES[2]]
+# doctored copies of good cell 0: (name, factor on the changed element).  -100 x: indefinite; -0.25 x and 0 x: still SPD (classified by the
+# test from the eigenvalues of the pinned float64 matrix, both classes must occur)
+FACTORS = (("neg100", -100.0), ("negq", -0.25), ("zero", 0.0))
+
+
+def pivot_elements(cells_p: np.ndarray, n_nodes: int, seed: int) -> list:
+    """The six changed elements of a case: the first element, one at the last (gauge) periodic node, one at node 0, three seeded random."""
+    at = lambda node: int(np.nonzero((cells_p == node).any(axis=1))[0][-1])  # noqa: E731
+    rng = np.random.default_rng(seed)
+    return [0, at(n_nodes - 1), at(0)] + [int(e) for e in rng.choice(cells_p.shape[0], 3, replace=False)]
+
+
+def pivot_batches(kind: str, cells_p: np.ndarray, n_nodes: int, good: np.ndarray, M, n_iso: int = 1) -> dict:
+    """Batches of 12 cells: the 6 good cells at even positions, 6 doctored copies of good cell 0 at odd positions.
+
+    name -> (coef[12, ...], M[12, d, d] or None, changed elements).  'neg100' / 'negq' / 'zero': the six elements times a factor;
+    'isolated': all elements of one node zero (an exactly zero pivot; never node 0 or the last node, the gauge of the structured routes;
+    ``n_iso`` = 2 nodes on mesh plans, whose gauge node is the library's choice: one of the two is not it); 'nan' / 'inf': one element NaN / +Inf;
+    'nanM': one NaN entry in the M of the doctored cells."""
+    seed = R.case_seed(kind, cells_p.shape, n_nodes)
+    els = pivot_elements(cells_p, n_nodes, seed)
+    rng = np.random.default_rng(seed + 1)
+
+    def batch():
+        c = np.empty((12,) + good.shape[1:])
+        c[0::2] = good
+        c[1::2] = good[0]
+        return c
+
+    MM = None
+    if M is not None:
+        MM = np.empty((12,) + M.shape[1:])
+        MM[0::2] = M
+        MM[1::2] = M[0]
+    out = {}
+    for name, f in FACTORS:
+        c = batch()
+        for i, e in enumerate(els):
+            c[1 + 2 * i, e] *= f
+        out[name] = (c, MM, els)
+    c = batch()
+    nodes = rng.choice(np.arange(1, n_nodes - 1), (6, n_iso), replace=False)
+    for i, v in enumerate(nodes):
+        c[1 + 2 * i, np.isin(cells_p, v).any(axis=1)] = 0.0
+    out["isolated"] = (c, MM, nodes)
+    for name, val in (("nan", np.nan), ("inf", np.inf)):
+        c = batch()
+        for i, e in enumerate(els):
+            c[(1 + 2 * i, e) + ((0,) if c.ndim == 3 else ())] = val
+        out[name] = (c, MM, els)
+    if M is not None:
+        Mb = MM.copy()
+        for i in range(6):
+            Mb[1 + 2 * i].flat[i % Mb[0].size] = np.nan
+        out["nanM"] = (batch(), Mb, els)
+    return out
+
+
+def pivot_inputs_structured(kind, dim, n):
+    from oracle import hommx_oracle as O
+
+    ne = (2 if dim == 2 else 6) * n**dim
+    seed = R.case_seed("pivot", kind, dim, n)
+    good = R.coefficients(kind, dim, ne, "log2", 6, seed)
+    M = R.stratification(dim, 6, seed)
+    cells_p = O.periodic_master_map(dim, n)[O.unit_cell_mesh(dim, n)[1]]
+    return good, M, cells_p, n**dim
+
+
+def pivot_inputs_mesh(kind, builder, args):
+    msh = R.mesh_of(builder, args)
+    seed = R.case_seed("pivot", kind, builder, args)
+    dim = msh.topology.dim
+    good = R.coefficients(kind, dim, msh.num_cells, "log2", 6, seed)
+    M = R.stratification(dim, 6, seed)
+    x, cells, tp = R.mesh_arrays(msh)
+    return msh, good, M, tp[cells], int(tp.max()) + 1
+
+
+def _run_pivot(p, kind, cells_p, n_nodes, good, M, key, out, n_iso=1):
+    A0, i0 = p.solve(good, M, return_info=True)
+    out[f"goodA|{key}"], out[f"goodinfo|{key}"] = A0, i0
+    for name, (c, MM, _) in pivot_batches(kind, cells_p, n_nodes, good, M, n_iso).items():
+        A, info = p.solve(c, MM, return_info=True)
+        out[f"A|{key}|{name}"], out[f"info|{key}|{name}"] = A, info
+
+
+def run_pivot_group(group: str) -> dict:
+    out = {}
+    for g, kernel, kind, dim, n, flags in PIVOT_CASES:
+        if g != group:
+            continue
+        good, M, cells_p, nn = pivot_inputs_structured(kind, dim, n)
+        _run_pivot(_plan(kernel, kind, dim, n, flags), kind, cells_p, nn, good, M, skey(kind, dim, n, flags), out)
+    if group == "default":
+        for kernel, kind, builder, args, route in PIVOT_MESH:
+            msh, good, M, cells_p, nn = pivot_inputs_mesh(kind, builder, args)
+            _run_pivot(_mesh_plan(kernel, kind, msh, route), kind, cells_p, nn, good, M, mkey(kind, builder, args, route), out, n_iso=2)
+    return out
+
+
+RUNNERS = {"accuracy": run_accuracy_group, "pivot": run_pivot_group}
+
+
+def run_in_child(what: str, group: str, tmp_path) -> dict:
+    """One fresh child process with the group's environment (one child at a time)."""
+    f = os.path.join(str(tmp_path), f"{what}_{group}.npz")
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), what, group, f], env=dict(os.environ, **R.CHILD_ENV[group]),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    with np.load(f) as z:
+        return {k: z[k] for k in z.files}
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, os.path.dirname(HERE))
+    np.savez(sys.argv[3], **RUNNERS[sys.argv[1]](sys.argv[2]))
+    print("ok")

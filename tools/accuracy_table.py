@@ -1,0 +1,123 @@
+"""Ratio e / yardstick of every case of tests/test_gpu_accuracy.py on this GPU -> profiles/accuracy.json and a Markdown table.
+
+e = max|A_gpu - T| / max|T| against the long-double truth of tests/accuracy_ref.py; yardstick = max(e_oracle_schur, e_cholesky_schur, 16 eps),
+what float64 delivers on the same inputs.  The tests assert ratio <= 32.  Per case the largest ratio over its cells, families and M / no M.
+
+    python tools/accuracy_table.py [--dumps DIR] [--out profiles/accuracy.json]
+
+--dumps DIR: take the raw GPU results from DIR/accuracy_<group>.npz -- the name tests/accuracy_gpu.py's run_in_child gives them; written by
+`python tests/accuracy_gpu.py accuracy <group> DIR/accuracy_<group>.npz` with the group's environment -- instead of running the plans here.
+"""
+
+import argparse
+import json
+import os
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import numpy as np  # noqa: E402
+
+import accuracy_gpu as G  # noqa: E402
+import accuracy_ref as R  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dumps")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "accuracy.json"))
+    args = ap.parse_args()
+
+    def results(group, tmp):
+        if args.dumps:
+            with np.load(os.path.join(args.dumps, f"accuracy_{group}.npz")) as z:
+                return {k: z[k] for k in z.files}
+        return G.run_accuracy_group(group) if group == "default" else G.run_in_child("accuracy", group, tmp)
+
+    with tempfile.TemporaryDirectory() as tmp:
+        res = {g: results(g, tmp) for g in R.STRUCTURED_CASES}
+    cache, rows = {}, []
+
+    def ref(key, kind, x, cells, tp, coef, M, **kw):
+        if key not in cache:
+            T = R.truth(kind, x, cells, tp, coef, M)
+            cache[key] = (T, R.float64_errors(kind, x, cells, tp, coef, M, T=T, **kw))
+        return cache[key]
+
+    def yard(e):
+        return e["bound"] / R.FACTOR
+
+    for group, cases in R.STRUCTURED_CASES.items():
+        for kernel, kind, dim, n, flags in cases:
+            x, cells, tp = R.structured(dim, n)
+            worst = (0.0, 0.0, "")
+            for family in R.FAMILIES[kind]:
+                for wm in (False, True):
+                    coef, M = R.structured_inputs(kind, dim, n, family, wm)
+                    A = res[group][f"A|{G.skey(kind, dim, n, flags)}|{family}|{int(wm)}"]
+                    for c in range(R.NC):
+                        T, e = ref((kind, dim, n, family, wm, c), kind, x, cells, tp, coef[c], None if M is None else M[c], n=n)
+                        err = R.rel(A[c], T[0])
+                        worst = max(worst, (err / yard(e), err, f"{family}{' M' if wm else ''}"))
+            rows.append({"group": group, "kernel": kernel, "case": f"{kind} {dim}D n={n}" + (" forced" if flags else ""), "ratio": worst[0],
+                         "e": worst[1], "worst": worst[2]})
+    for kernel, kind, builder, args_, route in R.MESH_CASES:
+        worst = (0.0, 0.0, "")
+        for family in R.FAMILIES[kind]:
+            for wm in (False, True):
+                msh, coef, M = R.mesh_inputs(kind, builder, args_, family, wm)
+                x, cells, tp = R.mesh_arrays(msh)
+                A = res["default"][f"A|{G.mkey(kind, builder, args_, route)}|{family}|{int(wm)}"]
+                for c in range(R.NC):
+                    T, e = ref((kind, builder, args_, family, wm, c), kind, x, cells, tp, coef[c], None if M is None else M[c], msh=msh)
+                    err = R.rel(A[c], T[0])
+                    worst = max(worst, (err / yard(e), err, f"{family}{' M' if wm else ''}"))
+        rows.append({"group": "default", "kernel": kernel, "case": f"{kind} {builder}{args_}", "ratio": worst[0], "e": worst[1], "worst": worst[2]})
+    for ckernel, kind, dim, n, group in R.CORRECTOR_CASES:
+        x, cells, tp = R.structured(dim, n)
+        worst = (0.0, 0.0, "")
+        for family in R.FAMILIES[kind]:
+            for wm in (False, True):
+                coef, M = R.structured_inputs(kind, dim, n, family, wm)
+                chi = res[group][f"corr|{G.skey(kind, dim, n, 0)}|{family}|{int(wm)}"]
+                for c in range(R.NC):
+                    T, e = ref((kind, dim, n, family, wm, c), kind, x, cells, tp, coef[c], None if M is None else M[c], n=n)
+                    err = R.rel(chi[c].T, T[1])
+                    worst = max(worst, (err / (e["bound_corr"] / R.FACTOR), err, f"{family}{' M' if wm else ''}"))
+        rows.append({"group": group, "kernel": "correctors: " + ckernel, "case": f"{kind} {dim}D n={n}", "ratio": worst[0], "e": worst[1],
+                     "worst": worst[2]})
+    sweep = []
+    for case in list(R.SWEEP_CASES) + [("default",) + R.SWEEP_MESH]:
+        group = case[0]
+        if isinstance(case[3], str):
+            _, kernel, kind, builder, args_, route = case
+            msh, coef, M = R.mesh_inputs(kind, builder, args_, "log2", True)
+            x, cells, tp = R.mesh_arrays(msh)
+            key, kw, ck, name = G.mkey(kind, builder, args_, route), {"msh": msh}, (kind, builder, args_, "log2", True), f"{kind} {builder}{args_}"
+        else:
+            _, kernel, kind, dim, n, flags = case
+            coef, M = R.structured_inputs(kind, dim, n, "log2", True)
+            x, cells, tp = R.structured(dim, n)
+            key, kw, ck, name = G.skey(kind, dim, n, flags), {"n": n}, (kind, dim, n, "log2", True), f"{kind} {dim}D n={n}"
+        per_k = {}
+        for k in R.SWEEP_K:
+            r = 0.0
+            for c in range(R.NC):
+                T, e = ref(ck + (c,), kind, x, cells, tp, coef[c], M[c], **kw)
+                r = max(r, R.rel(res[group][f"sweepA|{key}|{k}"][c] * 2.0**-k, T[0]) / yard(e))
+            per_k[str(k)] = r
+        sweep.append({"group": group, "kernel": kernel, "case": name, "ratio_by_k": per_k})
+    with open(args.out, "w") as f:
+        json.dump({"bound_factor": R.FACTOR, "floor_eps": R.FLOOR_EPS, "cases": rows, "magnitude_sweep": sweep}, f, indent=1)
+    print("| Route | Case | worst ratio | e | at |\n|---|---|---|---|---|")
+    for r in rows:
+        print(f"| `{r['kernel']}`{'' if r['group'] == 'default' else ' (' + r['group'] + ')'} | {r['case']} | {r['ratio']:.2f} | {r['e']:.1e} | {r['worst']} |")
+    print("\n| Route | Case | " + " | ".join(f"2^{k}" for k in R.SWEEP_K) + " |\n|---|---|" + "---|" * len(R.SWEEP_K))
+    for s in sweep:
+        print(f"| `{s['kernel']}` | {s['case']} | " + " | ".join(f"{s['ratio_by_k'][str(k)]:.2f}" for k in R.SWEEP_K) + " |")
+
+
+if __name__ == "__main__":
+    main()
