@@ -123,6 +123,7 @@ def _prototypes() -> dict:
         "hommx_plan_tensor_size": (i32, [vp]),
         "hommx_plan_kernel_name": (char_p, [vp]),
         "hommx_plan_corrector_kernel_name": (char_p, [vp]),
+        "hommx_plan_load_kernel_name": (char_p, [vp]),
         "hommx_plan_route_detail": (char_p, [vp]),
         "hommx_plan_flops_per_solve": (f64, [vp]),
         "hommx_mesh_analyze": (c_int, [C.POINTER(MeshDesc), i32p, dp]),

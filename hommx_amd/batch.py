@@ -299,6 +299,7 @@ class MicroCellPlan:
         self.t = int(self._lib.hommx_plan_tensor_size(h))
         self.kernel = self._lib.hommx_plan_kernel_name(h).decode()
         self.corrector_kernel = self._lib.hommx_plan_corrector_kernel_name(h).decode()  # the route of its corrector / reconstruct calls
+        self.load_kernel = self._lib.hommx_plan_load_kernel_name(h).decode()  # the route of the load solve of loads(..., response=True)
         self.route_detail = self._lib.hommx_plan_route_detail(h).decode()  # what that route launches for this plan (reports)
         self.flops_per_solve = float(self._lib.hommx_plan_flops_per_solve(h))  # dense flops of the route, by its own model
         self.n_nodes = n_nodes  # periodic nodes (correctors: dof = node * bs + component)

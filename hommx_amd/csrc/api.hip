@@ -118,6 +118,7 @@ struct hommx_plan {
   hommx::KindSizes ks;
   hommx::BlockedWorkspace* ws = nullptr;  // FAM_BLOCKED, and a FAM_FUSED2D plan with HOMMX_FUSED_CORR=0 once it has served correctors
   bool fused_corr = true;                 // FAM_FUSED2D: correctors by substitution on the fused kernel's own factors (HOMMX_FUSED_CORR)
+  bool fused_loads = true;                // ... and the correctors of user loads on the same records (HOMMX_FUSED_LOADS; needs fused_corr)
   hommx::MeshPlan* mesh = nullptr;        // FAM_MESH: symbolic phase + device tables of the unstructured micro mesh
   Buf buf[N_BUF];
   // host-pointer entry point: coefficient chunks stream in on s_copy while s_comp solves the previous one
@@ -157,7 +158,7 @@ int open_call(const hommx_plan* p, int64_t n_cells, bool ptrs_ok = true, const c
 }
 
 // What both plan constructors end with: the device range, then the plan with everything its descriptor determines.
-// HOMMX_RECON_MEM_MB and HOMMX_FUSED_CORR (include/hommx_hip.h) are read here, once
+// HOMMX_RECON_MEM_MB, HOMMX_FUSED_CORR and HOMMX_FUSED_LOADS (include/hommx_hip.h) are read here, once
 int plan_new(hommx_plan** out, const hommx_plan_desc& desc, int64_t n_el) {
   const int ndev = hommx_device_count();
   if (ndev <= 0) return fail(HOMMX_ENODEV, "no HIP device visible");
@@ -172,12 +173,15 @@ int plan_new(hommx_plan** out, const hommx_plan_desc& desc, int64_t n_el) {
   const long long mb = v ? atoll(v) : 0;
   p->recon_mem_mb = mb > 0 ? mb : 1024;
   if (const char* e = getenv("HOMMX_FUSED_CORR")) p->fused_corr = atoi(e) != 0;
+  if (const char* e = getenv("HOMMX_FUSED_LOADS")) p->fused_loads = atoi(e) != 0;
   *out = p;
   return HOMMX_OK;
 }
 
 // a fused 2D plan whose correctors come from its own factors
 bool fused_subst(const hommx_plan* p) { return p->family == FAM_FUSED2D && p->fused_corr; }
+// ... and whose load solve substitutes on the same records (k_fused2d_subst_rhs) instead of eliminating once more on the blocked route
+bool fused_loads(const hommx_plan* p) { return fused_subst(p) && p->fused_loads; }
 // bytes of factor record per cell of that route (0 on every other)
 size_t fact_bytes(const hommx_plan* p) { return fused_subst(p) ? sizeof(double) * hommx::fused_fact_doubles(p->desc.n_micro) : 0; }
 
@@ -480,6 +484,15 @@ const char* hommx_plan_corrector_kernel_name(const hommx_plan* p) {
   switch (p->family) {
     case FAM_FUSED2D: return p->fused_corr ? "fused2d_subst" : "blocked";
     case FAM_MESH: return "mesh_front";
+    default: return hommx::blocked_corrector_route_name(p->ws);
+  }
+}
+
+const char* hommx_plan_load_kernel_name(const hommx_plan* p) {
+  if (!p) return "";
+  switch (p->family) {
+    case FAM_FUSED2D: return fused_loads(p) ? "fused2d_subst" : "blocked";
+    case FAM_MESH: return "none";
     default: return hommx::blocked_corrector_route_name(p->ws);
   }
 }
@@ -994,7 +1007,7 @@ struct LoadIO {
 bool load_response(const hommx_load_args& a) { return a.energy || a.stats || a.strain || a.flux || a.correctors; }
 
 // the argument checks of both entry points, then the routes the call needs: one that forms correctors, and for a response the blocked
-// workspace a fused 2D plan does not have yet (its own substitution takes the canonical loads only)
+// workspace of a fused 2D plan whose load solve does not run on its own records (HOMMX_FUSED_LOADS=0 / HOMMX_FUSED_CORR=0)
 int loads_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_load_args* a, bool device) {
   auto more = [&] {
     if (int rc = coef_check(p, src)) return rc;
@@ -1012,7 +1025,7 @@ int loads_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, con
     return fail(HOMMX_EINVAL, "the frontal mesh route (mesh_front) solves for the canonical loads only: energy, stats, strain / flux and "
                               "correctors of user loads need a plan of the tree route (HOMMX_MESH_FLAG_TREE, route=\"tree\"); P_eff alone works here");
   if (int rc = corrector_workspace(p)) return rc;
-  if (load_response(*a) && !p->ws) {
+  if (load_response(*a) && !p->ws && !fused_loads(p)) {
     int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
     if (rc) return prefix_error(rc, "blocked path: ");
   }
@@ -1020,7 +1033,8 @@ int loads_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, con
 }
 
 // one chunk of at most recon_chunk() cells on the device: the canonical correctors into the plan's scratch and k_polar; for a response
-// the correctors of the loads behind them (a corrector pass of the blocked family on the overridden load rows) and k_load_stats
+// the correctors of the loads behind them (fused 2D plans: k_fused2d_subst_rhs on the records the canonical pass of this chunk has just left
+// in B_FACT; else a corrector pass of the blocked family on the overridden load rows) and k_load_stats
 int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const LoadIO& io, const hommx_load_args& a, hipStream_t st) {
   const bool response = load_response(a), mesh = p->desc.n_micro == 0;
   const int t = p->ks.t;
@@ -1037,11 +1051,16 @@ int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const LoadIO& io, const 
   k.P_eff = io.P_eff;
   HIP_TRY(hommx::launch_polar(k, p->desc.dim, p->desc.kind, mesh, nc, st));
   if (!response) return HOMMX_OK;
-  if (int rc = grow(p->buf[B_LOADS], sizeof(double) * chunk * t * t)) return rc;
   double* corr_l = corr + chunk * t * k.ndof;
-  const hommx::LoadOverride lo{io.P, a.n_loads, a.per_cell != 0};
-  if (int rc = hommx::blocked_solve(p->ws, nc, io.coef, io.M, static_cast<double*>(p->buf[B_LOADS].p), nullptr, st, corr_l, &lo))
-    return route_fail(p, rc);
+  if (fused_loads(p)) {
+    HIP_TRY(hommx::launch_fused2d_subst_rhs(static_cast<const double*>(p->buf[B_FACT].p), io.P, a.n_loads, a.per_cell != 0, io.M, corr_l,
+                                            p->desc.n_micro, nc, st));
+  } else {
+    if (int rc = grow(p->buf[B_LOADS], sizeof(double) * chunk * t * t)) return rc;
+    const hommx::LoadOverride lo{io.P, a.n_loads, a.per_cell != 0};
+    if (int rc = hommx::blocked_solve(p->ws, nc, io.coef, io.M, static_cast<double*>(p->buf[B_LOADS].p), nullptr, st, corr_l, &lo))
+      return route_fail(p, rc);
+  }
   k.corr = corr_l;
   k.energy = io.energy;
   k.stats = io.stats;

@@ -278,6 +278,7 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
         rec[NB + c] = c1;
       }
       if (l < 4) rec[4 * NB + l] = l == 0 ? m00 : l == 1 ? m01 : l == 2 ? m10 : m11;
+      if (l == 4) rec[4 * NB + 4] = (double)esh;  // the magnitude exponent: a general load is of degree 1 in the scale (k_fused2d_subst_rhs)
     }
     // S_last = D_{n-1}
     {
@@ -683,6 +684,14 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
     int badj = 0;
     accl::Sweep<NB>::run(a, L.ubuf, j, k, badj);
     if (badj && !bad) { bad = 1; badstep = n; }
+    if constexpr (FACT) {  // N'_last, the inverse of the gauged last Schur block, behind step n-2 (srec stands there) in the layout of the steps
+#pragma unroll
+      for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < NT; ++tj)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) srec[((ti * NT + tj) * 4 + r) * 64 + l] = a[ti][tj][r];
+    }
     double part[2][NT];
 #pragma unroll
     for (int m = 0; m < 2; ++m)

@@ -69,20 +69,29 @@ struct CoefSource {
 hipError_t launch_poisson2d_fused(const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
                                   int n, long long ncells, hipStream_t stream, CoefSource src = CoefSource());
 
-// The factor record of one cell, written by k_poisson2d_fused<NB, true> and read by k_fused2d_subst<NB> (NB = 16 for n <= 16, else 32);
-// private to the two kernels.  In doubles, with N' = -S^-1 as the elimination carries it:
-//   header  [C e0 (NB) | C e1 (NB) | y_last (2 NB) | M (4) | pad (4)]           C = the wrap coupling E_{n-1}, y_last = z of the final sweep
+// The factor record of one cell, written by k_poisson2d_fused<NB, true> and read by k_fused2d_subst<NB> and k_fused2d_subst_rhs<NB> (NB = 16 for
+// n <= 16, else 32); private to the three kernels.  In doubles, with N' = -S^-1 as the elimination carries it:
+//   header  [C e0 (NB) | C e1 (NB) | y_last (2 NB) | M (4) | esh (1) | pad (3)]   C = the wrap coupling E_{n-1}, y_last = z of the final sweep,
+//                                                                                esh = the magnitude exponent of the cell
 //   step j  [N'_j (NB NB, register-major [ti][tj][r][lane]) | N'_j r~_j (2 NB) | E_j e0 (NB) | E_j e1 (NB)],  j = 0 .. n-2
-// e0[i] = E[i][i], e1[i] = E[i][i-1] (cyclic on the real indices, padding first).  n = NB = 32: 136 + 31 * 1152 = 35,848 doubles =
-// 286,784 bytes per cell; n = NB = 16: 72 + 15 * 320 = 4,872 doubles = 38,976 bytes.
+//   last    [N'_last (NB NB, register-major)]                                     the inverse of the gauged last Schur block, behind step n-2
+// e0[i] = E[i][i], e1[i] = E[i][i-1] (cyclic on the real indices, padding first).  n = NB = 32: 136 + 31 * 1152 + 1024 = 36,872 doubles =
+// 294,976 bytes per cell; n = NB = 16: 72 + 15 * 320 + 256 = 5,128 doubles = 41,024 bytes.  k_fused2d_subst reads neither esh nor the last block.
 constexpr long long fused_fact_header(int NB) { return 4 * NB + 8; }
 constexpr long long fused_fact_step(int NB) { return (long long)NB * NB + 4 * NB; }
-constexpr long long fused_fact_doubles(int n) { return fused_fact_header(n <= 16 ? 16 : 32) + (n - 1) * fused_fact_step(n <= 16 ? 16 : 32); }
+constexpr long long fused_fact_doubles(int n) {
+  return fused_fact_header(n <= 16 ? 16 : 32) + (n - 1) * fused_fact_step(n <= 16 ? 16 : 32) + (n <= 16 ? 16 * 16 : 32 * 32);
+}
 // fused2d.hip: the same elimination of an element stream, and the factor record of every cell into d_fact[ncells][fused_fact_doubles(n)]
 hipError_t launch_poisson2d_fused_fact(const double* d_coef, const double* d_M, double* d_out, int32_t* d_info, int n, long long ncells,
                                        hipStream_t stream, double* d_fact);
 // fused2d_subst.hip: correctors d_corr[ncells][2][n n] (dof = i + n j, mean-free) by substitution on the factor records, one wave per cell
 hipError_t launch_fused2d_subst(const double* d_fact, double* d_corr, int n, long long ncells, hipStream_t stream);
+// fused2d_rhs.hip: the correctors of user loads by substitution on the same records: rows l < n_loads of d_corr[ncells][2][n n] (mean-free; the
+// other rows are not written) solve K chi_l = -f^l with f^l of P[n_loads][2 n n][2] (per_cell: P[ncells][n_loads][2 n n][2]) as loads.hip
+// forms it; d_M [ncells][2][2] or null
+hipError_t launch_fused2d_subst_rhs(const double* d_fact, const double* d_P, int n_loads, bool per_cell, const double* d_M, double* d_corr, int n,
+                                    long long ncells, hipStream_t stream);
 
 // assembly.hip: coef[cell][el][comp] of a separable coefficient (AFFINE / RECIPROCAL; params[cell][comp] = (a, b)) expanded into the element stream
 hipError_t launch_expand_separable(CoefSource src, const double* d_params, double* d_coef, long long n_el, int n_comp, long long ncells,

@@ -67,7 +67,10 @@ extern "C" {
  *                          chunks of that many cells' correctors; a fused 2D plan's factor records (HOMMX_FUSED_CORR) count with them
  *   HOMMX_FUSED_CORR       0: the correctors of a fused 2D plan come from the plane elimination of the blocked family (a blocked workspace
  *                          on first use).  Default: substitution on the block inverses of the fused kernel itself (k_poisson2d_fused<NB, true>
- *                          keeps them, k_fused2d_subst substitutes): two launches per chunk                                    */
+ *                          keeps them, k_fused2d_subst substitutes): two launches per chunk
+ *   HOMMX_FUSED_LOADS      0: the load solve of hommx_loads_source[_device] on a fused 2D plan runs the plane elimination of the blocked family
+ *                          (a blocked workspace on first use); implied by HOMMX_FUSED_CORR=0.  Default: substitution on the factor records of
+ *                          the chunk's canonical pass (k_fused2d_subst_rhs): no second elimination.  Kept for A/B runs        */
 
 typedef struct hommx_plan hommx_plan;
 
@@ -113,6 +116,10 @@ const char* hommx_plan_kernel_name(const hommx_plan* plan);
  * "multifrontal" / "mesh_multifrontal" (nested-dissection plans; "blocked" with HOMMX_MF_CORR=0 on a structured one), "mesh_front"
  * (frontal mesh plans), "blocked" (every other plan: plane elimination). */
 const char* hommx_plan_corrector_kernel_name(const hommx_plan* plan);
+/* The route the load solve of hommx_loads_source[_device] takes (the response outputs; P_eff alone needs none): "fused2d_subst" (fused 2D
+ * plans; "blocked" with HOMMX_FUSED_LOADS=0 or HOMMX_FUSED_CORR=0), "none" (frontal mesh plans: the response is refused), else the name
+ * hommx_plan_corrector_kernel_name returns. */
+const char* hommx_plan_load_kernel_name(const hommx_plan* plan);
 /* One line describing what that route launches for THIS plan (kernel names with their tile sizes, tree shape of the nested dissection,
  * stage size, streams): for reports -- bench.py's roofline.kernel label is this string, so it cannot drift from the code. */
 const char* hommx_plan_route_detail(hommx_plan* plan);
@@ -331,9 +338,10 @@ int hommx_sensitivity_source_device(hommx_plan* plan, int64_t n_cells, const hom
  *   P_eff[c][l]    = sum_K |K| q^l_K = sum_K |K| (e_m + eps(chi^m)_K) . P^l_K, m < t       (Levin: from the canonical correctors alone)
  *   energy[c][l][l'] = sum_K |K| eps(chi_l)_K . material(coef_K) eps(chi_l')_K              (symmetric, bitwise)
  * P_eff is all a macro solve needs (its load gains -vol(T) eps_macro(v) . P_eff); it is computed by the Levin form, which needs no
- * second elimination, on EVERY plan.  The response outputs come from a solve for the loads themselves: one more corrector pass of the
- * blocked family with the load rows replaced (a fused 2D plan gets a blocked workspace on the first such call; a mesh plan needs the tree
- * route).
+ * second elimination, on EVERY plan.  The response outputs come from a solve for the loads themselves (hommx_plan_load_kernel_name names
+ * its route): a fused 2D plan substitutes on the factor records its canonical pass has just left (k_fused2d_subst_rhs; with
+ * HOMMX_FUSED_LOADS=0 it gets a blocked workspace on the first such call instead), every other plan runs one more corrector pass of the
+ * blocked family with the load rows replaced (a mesh plan needs the tree route).
  *
  *   n_loads     1 .. t of the plan (callers loop for more)
  *   per_cell    0: P[n_loads][n_el][t], shared by all cells; 1: P[n_cells][n_loads][n_el][t]

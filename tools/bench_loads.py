@@ -2,7 +2,7 @@
 Poisson, the TwoPhase inclusion) and on 256 cells of the C4 shape (16^3 isotropic elasticity, the TwoPhase fibre), one load shared by all
 cells (a thermal eigenstress: material(phase) applied to one unit strain).
 
-    python tools/bench_loads.py [--reps 7] [--out profiles/loads_bench.json]
+    python tools/bench_loads.py [--reps 7] [--fused-loads 0|1] [--out profiles/loads_bench.json]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python tools/bench_loads.py --case C2 --profile-leg --reps 3
     python tools/bench_loads.py --case C2 --merge-kernel-stats DIR/.../run_kernel_stats.csv [--out profiles/loads_bench.json]
 
@@ -11,8 +11,11 @@ Per case, the median wall time after one warm-up call of
         direction (hommx_sensitivity_source), the same correctors and one contraction;
     the response (device entry, statistics and energy, no fields): one more corrector pass on the overridden load rows and k_load_stats --
         next to the reconstruction (statistics only) and the corrector call (hommx_solve_batch_correctors, host entry) of the same batch.
---profile-leg runs the response's device entry of one case alone, so that a rocprofv3 trace of that run holds the kernels of both corrector
-passes, k_polar, k_assemble_loads and k_load_stats; --merge-kernel-stats adds their times per API call and their algorithmic bytes."""
+--fused-loads sets HOMMX_FUSED_LOADS before the plans are created: 0 is the plane elimination for the load solve of the fused 2D plan (the
+yardstick of DESIGN.md 4.10), 1 / default the substitution on the factor records (k_fused2d_subst_rhs); `load_kernel` in the JSON is the route
+taken.  --profile-leg runs the response's device entry of one case alone, so that a rocprofv3 trace of that run holds the kernels of both
+corrector passes, k_polar, k_assemble_loads (blocked load pass) or k_fused2d_subst_rhs, and k_load_stats; --merge-kernel-stats adds their
+times per API call and their algorithmic bytes."""
 
 from __future__ import annotations
 
@@ -92,7 +95,8 @@ def measure(reps, only, profile_leg):
         P_eff, energy, lstats, dA, st, A = new(nc, 1, t), new(nc, 1, 1), new(nc, 1, t + 2), new(nc, 1, t, t), new(nc, 2 * t + 3), new(nc, t, t)
         info = torch.empty(nc, dtype=torch.int32, device=dev)
         s = torch.cuda.current_stream(dev).cuda_stream
-        r = {"case": name, "cells": nc, "n_loads": 1, "kernel_route": p.kernel, "corrector_kernel": p.corrector_kernel}
+        r = {"case": name, "cells": nc, "n_loads": 1, "kernel_route": p.kernel, "corrector_kernel": p.corrector_kernel,
+             "load_kernel": p.load_kernel}
         response = lambda: p.loads_device(nc, src, None, 1, d_P, P_eff.data_ptr(), False, A.data_ptr(), info.data_ptr(), energy.data_ptr(),
                                           lstats.data_ptr(), stream=s)
         if not profile_leg:
@@ -121,7 +125,7 @@ def merge(res, stats_csv, only, api_calls):
     """The three load kernels against the corrector kernels of the same call, per API call, with their algorithmic bytes."""
     rows = list(csv.DictReader(open(stats_csv)))
     total = lambda pick: sum(float(r["TotalDurationNs"]) for r in rows if pick(r["Name"]))
-    mine = ("k_polar", "k_assemble_loads", "k_load_stats")
+    mine = ("k_polar", "k_assemble_loads", "k_load_stats", "k_fused2d_subst_rhs")
     ours = lambda k: "hommx::" in k and not any(m in k for m in mine) and "expand" not in k
     for r in res:
         if only in r["case"]:
@@ -131,7 +135,9 @@ def merge(res, stats_csv, only, api_calls):
             # k_load_stats reads the coefficient and P per load and, in the pass of load l, the correctors 0 .. l: one corrector at the one
             # load of this benchmark (n_loads (n_loads + 1) / 2 corrector reads per cell in general)
             bytes_ = {"k_polar": 8.0 * nc * (t * ndof + t) + 8.0 * n_el * t, "k_assemble_loads": 8.0 * nc * t * ndof + 8.0 * n_el * t,
-                      "k_load_stats": 8.0 * nc * (ndof + n_el * n_comp + t + 3) + 8.0 * n_el * t}
+                      "k_load_stats": 8.0 * nc * (ndof + n_el * n_comp + t + 3) + 8.0 * n_el * t,
+                      # the record's block inverses four times (the last one once), the load and one corrector row
+                      "k_fused2d_subst_rhs": 8.0 * nc * ((4 * (n - 1) - 2) * n * n + ndof) + 8.0 * n_el * t if dim == 2 else 0.0}
             for m in mine:
                 r[m + "_s"] = total(lambda k: m in k) * 1e-9 / api_calls
                 r[m + "_bytes"] = bytes_[m]
@@ -144,10 +150,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default="profiles/loads_bench.json")
+    ap.add_argument("--fused-loads", choices=("0", "1"), default=None, help="HOMMX_FUSED_LOADS for the plans of this run (default: unset)")
     ap.add_argument("--case", default=None, help="only the cases whose name contains this")
     ap.add_argument("--profile-leg", action="store_true", help="the device entry of the response alone, no JSON: the run to trace")
     ap.add_argument("--merge-kernel-stats", default=None, help="kernel stats CSV of a traced --profile-leg run of --case (with its --reps)")
     a = ap.parse_args()
+    if a.fused_loads is not None:
+        os.environ["HOMMX_FUSED_LOADS"] = a.fused_loads
     if a.merge_kernel_stats:
         doc = json.load(open(a.out))
         doc["results"] = merge(doc["results"], a.merge_kernel_stats, a.case, a.reps + 1)
