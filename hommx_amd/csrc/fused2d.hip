@@ -78,8 +78,12 @@ struct alignas(16) Lds {
 
 // FACT: the kernel also writes the factor record of its cell (kernels.h) for k_fused2d_subst; the last kernel argument is then the
 // records, and an empty struct otherwise
+// ISO: the unstratified cell (Mmat == nullptr, Q = I: al = be = 1/2, ga = 0).  The P1 stencil is then the 5-point stencil and the coupling E
+// between consecutive node rows is diagonal (E[i][i-1] = -ga (a0 + a1) = 0), so every term of the step that carries e1 is an exact zero.  The
+// ISO path is the general one with those terms deleted -- the surviving operations and their order are the same, results agree bit for bit up
+// to the sign of an exact zero -- and with them go the LDS round trips that only fetched the neighbours they multiply.
 struct NoFact {};
-template <int NB, bool FACT>
+template <int NB, bool FACT, bool ISO>
 __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fused(
     const double* __restrict__ coef, const double* __restrict__ Mmat, double* __restrict__ out,
     int32_t* __restrict__ info, int n, long long ncells, const CoefSource src, std::conditional_t<FACT, double*, NoFact> fact
@@ -89,6 +93,7 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 ) {
   constexpr int NT = NB / 16, KK = NB / 4, CG = 64 / NB;
   constexpr int P = MATP;
+  static_assert(!(FACT && ISO), "the factor record keeps the general path");
   __shared__ Lds<NB> L;
 
   const long long cell = blockIdx.x;
@@ -108,7 +113,7 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 
   // LDS addressing of the staging matrix (in doubles)
   const int ownB = (k + 1) * P + j;  // entry (k, j); element (ti, tj, r): + (16 ti + 4 r) * P + 16 tj
-  int leftB[NT];                     // entry (k, cyclic-left of column 16 tj + j)
+  [[maybe_unused]] int leftB[NT];    // entry (k, cyclic-left of column 16 tj + j)
 #pragma unroll
   for (int tj = 0; tj < NT; ++tj) {
     const int col = 16 * tj + j;
@@ -117,7 +122,7 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 #define OWN(ti, tj, r) (ownB + (16 * (ti) + 4 * (r)) * P + 16 * (tj))
 #define LEFT(ti, tj, r) (leftB[tj] + (16 * (ti) + 4 * (r)) * P)
   const unsigned matOff = accl::lds_offset(&L.mat[0]);
-  const unsigned haloA = matOff + 8u * (unsigned)(p0 * P + j);  // halo row = row index p0 - 1: copy of row NB - 1
+  [[maybe_unused]] const unsigned haloA = matOff + 8u * (unsigned)(p0 * P + j);  // halo row = row index p0 - 1: copy of row NB - 1
 
   // Coefficient source (kernels.h): the element stream coef[cell][2 n^2], or a device sampler fed by two numbers per cell
   const int mode = src.mode;
@@ -142,14 +147,14 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 
   // ---- stratification matrix M = Dtheta^T(c_T) -> Q = M^T M (hmm.py:759-766) -------------------
   double m00 = 1.0, m01 = 0.0, m10 = 0.0, m11 = 1.0;
-  if (Mmat) {
+  if (!ISO && Mmat) {
     const double* mp = Mmat + cell * 4;
     m00 = mp[0]; m01 = mp[1]; m10 = mp[2]; m11 = mp[3];
   }
-  const double al = uniform_f64(0.5 * (m00 * m00 + m10 * m10));
-  const double be = uniform_f64(0.5 * (m01 * m01 + m11 * m11));
-  const double ga = uniform_f64(0.5 * (m00 * m01 + m10 * m11));
-  const double ab = uniform_f64(al - 2.0 * ga + be);
+  const double al = ISO ? 0.5 : uniform_f64(0.5 * (m00 * m00 + m10 * m10));
+  const double be = ISO ? 0.5 : uniform_f64(0.5 * (m01 * m01 + m11 * m11));
+  const double ga = ISO ? 0.0 : uniform_f64(0.5 * (m00 * m01 + m10 * m11));
+  const double ab = ISO ? 1.0 : uniform_f64(al - 2.0 * ga + be);
 
   double ph0 = 0.0, ph1 = 0.0;  // phase values / (a, b)
   if (mode != COEF_STREAM) {
@@ -346,17 +351,22 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
       nxt = load_row(jr + 1);
       asum += nxt.a0 + nxt.a1;
     }
-    // coupling E = K[(., jr+1), (., jr)] from cell row jr:  E[i][i] = cN[i], E[i][i-1] = cNE[i-1]
+    // coupling E = K[(., jr+1), (., jr)] from cell row jr:  E[i][i] = cN[i], E[i][i-1] = cNE[i-1] (ISO: E is diagonal)
     const double e0c = st_N(cur);
-    const double neC = st_NE(cur);
-    const double e1c = __shfl(neC, lb + cm, 64);
+    [[maybe_unused]] double neC = 0.0, e1c = 0.0;
+    if constexpr (!ISO) {
+      neC = st_NE(cur);
+      e1c = __shfl(neC, lb + cm, 64);
+    }
     if (lastStep) {
       // the last node row couples to row n-2 through E as well as through the arrow: W += E, i.e. W^T += E^T
       for (int i = l; i < (NB + 1) * P; i += 64) L.mat[i] = 0.0;
       __syncthreads();
       if (g == 0) {
         L.mat[(c + 1) * P + c] = e0c;
-        if (valid) L.mat[(c + 1) * P + cp] = neC;  // E^T[c][cp] = E[cp][c]
+        if constexpr (!ISO) {
+          if (valid) L.mat[(c + 1) * P + cp] = neC;  // E^T[c][cp] = E[cp][c]
+        }
       }
       __syncthreads();
 #pragma unroll
@@ -371,9 +381,9 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
       L.rrow[0][prow] = rr[0];
       L.rrow[1][prow] = rr[1];
       L.e0row[prow] = e0c;
-      L.e1row[prow] = e1c;
+      if constexpr (!ISO) L.e1row[prow] = e1c;
       L.e0nat[c] = e0c;
-      L.e1nat[c] = e1c;
+      if constexpr (!ISO) L.e1nat[c] = e1c;
       L.dgnat[c] = dgc;
       L.cenat[1 + c] = cec;
     }
@@ -421,8 +431,8 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
     }
 #endif
 
-    if (!lastStep) {
-      // (2) N -> staging matrix (for T_next), with the halo copy of row NB-1 in front of the first real row
+    if (!ISO && !lastStep) {
+      // (2) N -> staging matrix (for T_next), with the halo copy of row NB-1 in front of the first real row (ISO: T_next reads no neighbour)
 #pragma unroll
       for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
@@ -541,22 +551,30 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 
     if (!lastStep) {
       // row-layout coupling coefficients: e0r[kk] = E[i][i], e1r[kk] = E[i][i-1] at i = 4 kk + k = 16 ti + 4 r + k
-      double e0r[KK], e1r[KK];
+      double e0r[KK];
+      [[maybe_unused]] double e1r[KK];
 #pragma unroll
       for (int q4 = 0; q4 < KK; q4 += 4) {
-        const d4 x = *reinterpret_cast<const d4*>(&L.e0row[k * KK + q4]);
-        const d4 y = *reinterpret_cast<const d4*>(&L.e1row[k * KK + q4]);
-        e0r[q4] = x[0]; e0r[q4 + 1] = x[1]; e0r[q4 + 2] = x[2]; e0r[q4 + 3] = x[3];
-        e1r[q4] = y[0]; e1r[q4 + 1] = y[1]; e1r[q4 + 2] = y[2]; e1r[q4 + 3] = y[3];
+        if constexpr (ISO) {  // (a branch of its own: the general one keeps its statement order, and with it the code it compiled to)
+          const d4 x = *reinterpret_cast<const d4*>(&L.e0row[k * KK + q4]);
+          e0r[q4] = x[0]; e0r[q4 + 1] = x[1]; e0r[q4 + 2] = x[2]; e0r[q4 + 3] = x[3];
+        } else {
+          const d4 x = *reinterpret_cast<const d4*>(&L.e0row[k * KK + q4]);
+          const d4 y = *reinterpret_cast<const d4*>(&L.e1row[k * KK + q4]);
+          e0r[q4] = x[0]; e0r[q4 + 1] = x[1]; e0r[q4 + 2] = x[2]; e0r[q4 + 3] = x[3];
+          e1r[q4] = y[0]; e1r[q4 + 1] = y[1]; e1r[q4 + 2] = y[2]; e1r[q4 + 3] = y[3];
+        }
       }
       // (8) T_next = -D_{j+1} - E N E^T in place.  X(r, q) = e0[q] N[r][q] + e1[q] N[r][q-1];
       //     (E N E^T)[r][q] = e0[r] X(r, q) + e1[r] X(r-1, q); neighbours from the staging matrix (halo row = wrap-around).
+      //     ISO: e1 = 0, (E N E^T)[r][q] = e0[r] (e0[q] N[r][q]) from the registers alone.
       {
-        double e0q[NT], e1q[NT], dgq[NT], ceq[NT], cemq[NT];
+        double e0q[NT], dgq[NT], ceq[NT], cemq[NT];
+        [[maybe_unused]] double e1q[NT];
 #pragma unroll
         for (int tj = 0; tj < NT; ++tj) {
           e0q[tj] = L.e0nat[16 * tj + j];
-          e1q[tj] = L.e1nat[16 * tj + j];
+          if constexpr (!ISO) e1q[tj] = L.e1nat[16 * tj + j];
           dgq[tj] = L.dgnat[16 * tj + j];
           ceq[tj] = L.cenat[1 + 16 * tj + j];   // D[i][i+1], i = my column
           cemq[tj] = L.cenat[16 * tj + j];      // D[i-1][i] (no wrap: the slot in front of index 0 is 0)
@@ -567,12 +585,16 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
           for (int r = 0; r < 4; ++r)
 #pragma unroll
             for (int tj = 0; tj < NT; ++tj) {
-              const double nl = L.mat[LEFT(ti, tj, r)];
-              const double nu = L.mat[OWN(ti, tj, r) - P];
-              const double nul = L.mat[LEFT(ti, tj, r) - P];
-              const double x = fma(e1q[tj], nl, e0q[tj] * a[ti][tj][r]);
-              const double xu = fma(e1q[tj], nul, e0q[tj] * nu);
-              a[ti][tj][r] = -fma(e0r[4 * ti + r], x, e1r[4 * ti + r] * xu);
+              if constexpr (ISO) {
+                a[ti][tj][r] = -(e0r[4 * ti + r] * (e0q[tj] * a[ti][tj][r]));
+              } else {
+                const double nl = L.mat[LEFT(ti, tj, r)];
+                const double nu = L.mat[OWN(ti, tj, r) - P];
+                const double nul = L.mat[LEFT(ti, tj, r) - P];
+                const double x = fma(e1q[tj], nl, e0q[tj] * a[ti][tj][r]);
+                const double xu = fma(e1q[tj], nul, e0q[tj] * nu);
+                a[ti][tj][r] = -fma(e0r[4 * ti + r], x, e1r[4 * ti + r] * xu);
+              }
             }
         // band of -D_{j+1}: diagonal j = 4 r + k, sub-diagonal (row = col + 1) j = 4 r + k - 1, super-diagonal j = 4 r + k + 1
 #pragma unroll
@@ -618,30 +640,43 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
         }
       }
 
-      // (7) W_next = V' E^T: W_next^T[i][.] = e0[i] V'^T[i][.] + e1[i] V'^T[i-1][.]  (row shift through the staging matrix)
+      // (7) W_next = V' E^T: W_next^T[i][.] = e0[i] V'^T[i][.] + e1[i] V'^T[i-1][.]  (row shift through the staging matrix; ISO: a row scaling
+      //     in the registers)
+      if constexpr (ISO) {
 #pragma unroll
-      for (int x = 0; x < NT; ++x)
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+          for (int kk = 0; kk < KK; ++kk) wf[t][kk] = e0r[kk] * vt[kk >> 2][t][kk & 3];
+      } else {
+#pragma unroll
+        for (int x = 0; x < NT; ++x)
+#pragma unroll
+          for (int y = 0; y < NT; ++y)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) L.mat[OWN(x, y, r)] = vt[x][y][r];
 #pragma unroll
         for (int y = 0; y < NT; ++y)
+          accl::masked_lds_store<accl::RowMask<3>::lo, accl::RowMask<3>::hi>(haloA + 128u * y, vt[NT - 1][y][3]);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) L.mat[OWN(x, y, r)] = vt[x][y][r];
+        for (int t = 0; t < NT; ++t)
 #pragma unroll
-      for (int y = 0; y < NT; ++y)
-        accl::masked_lds_store<accl::RowMask<3>::lo, accl::RowMask<3>::hi>(haloA + 128u * y, vt[NT - 1][y][3]);
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) {
-          const double up = L.mat[OWN(kk >> 2, t, kk & 3) - P];
-          wf[t][kk] = fma(e1r[kk], up, e0r[kk] * vt[kk >> 2][t][kk & 3]);
-        }
+          for (int kk = 0; kk < KK; ++kk) {
+            const double up = L.mat[OWN(kk >> 2, t, kk & 3) - P];
+            wf[t][kk] = fma(e1r[kk], up, e0r[kk] * vt[kk >> 2][t][kk & 3]);
+          }
+      }
 
       // (9) R_next = P_{j+1} + Vr' E^T
       {
         const double v0 = L.vnat[0][c], v1 = L.vnat[1][c];
-        const double vm0 = L.vnat[0][cm], vm1 = L.vnat[1][cm];
-        rr[0] = fma(vm0, e1c, fma(v0, e0c, st_p0(nxt, cur)));
-        rr[1] = fma(vm1, e1c, fma(v1, e0c, st_p1(nxt, cur)));
+        if constexpr (ISO) {
+          rr[0] = fma(v0, e0c, st_p0(nxt, cur));
+          rr[1] = fma(v1, e0c, st_p1(nxt, cur));
+        } else {
+          const double vm0 = L.vnat[0][cm], vm1 = L.vnat[1][cm];
+          rr[0] = fma(vm0, e1c, fma(v0, e0c, st_p0(nxt, cur)));
+          rr[1] = fma(vm1, e1c, fma(v1, e0c, st_p1(nxt, cur)));
+        }
       }
       cur = nxt;
       __syncthreads();
@@ -759,29 +794,49 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 }
 
 // ---- launch ---------------------------------------------------------------------------------------
-// The two instantiations of FACT are compiled in translation units of their own (fused2d_fact.hip includes this file with
-// HOMMX_FUSED_FACT_TU): with <NB, true> in the same module the compiler schedules <32, false> differently (234 instead of 236 VGPRs, another
-// instruction order), and the tensor path is to stay bit for bit and cycle for cycle what it was.
-#ifndef HOMMX_FUSED_FACT_TU
-hipError_t launch_poisson2d_fused(const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
-                                  int n, long long ncells, hipStream_t stream, CoefSource src) {
-  if (ncells <= 0) return hipSuccess;
-  dim3 grid((unsigned)ncells), block(64);
+// The instantiations of FACT and of ISO are compiled in translation units of their own (fused2d_fact.hip and fused2d_iso.hip include this file
+// with HOMMX_FUSED_FACT_TU / HOMMX_FUSED_ISO_TU): with <NB, true, false> in the same module the compiler schedules <32, false, false> differently
+// (234 instead of 236 VGPRs, another instruction order), and the general tensor path is to stay bit for bit and cycle for cycle what it was.
 #ifndef HOMMX_DEV_LDS_PAD
 #define HOMMX_DEV_LDS_PAD 0  // dev builds: dynamic LDS bytes per workgroup, to pin the occupancy for latency experiments
 #endif
 #ifdef HOMMX_FUSED_DEBUG
-  extern double* g_fused_dbg;
-  if (n <= 16)
-    hipLaunchKernelGGL((k_poisson2d_fused<16, false>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, NoFact{}, g_fused_dbg);
-  else
-    hipLaunchKernelGGL((k_poisson2d_fused<32, false>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, NoFact{}, g_fused_dbg);
+extern double* g_fused_dbg;
+#define HOMMX_FUSED_LDS 0
+#define HOMMX_FUSED_DBG_ARG , g_fused_dbg
 #else
-  if (n <= 16)
-    hipLaunchKernelGGL((k_poisson2d_fused<16, false>), grid, block, HOMMX_DEV_LDS_PAD, stream, d_coef, d_M, d_out, d_info, n, ncells, src, NoFact{});
-  else
-    hipLaunchKernelGGL((k_poisson2d_fused<32, false>), grid, block, HOMMX_DEV_LDS_PAD, stream, d_coef, d_M, d_out, d_info, n, ncells, src, NoFact{});
+#define HOMMX_FUSED_LDS HOMMX_DEV_LDS_PAD
+#define HOMMX_FUSED_DBG_ARG
 #endif
+
+#if defined(HOMMX_FUSED_ISO_TU)
+// the unstratified cells (no M), every coefficient source
+hipError_t launch_poisson2d_fused_iso(const double* d_coef, double* d_out, int32_t* d_info, int n, long long ncells, hipStream_t stream,
+                                      CoefSource src) {
+  if (ncells <= 0) return hipSuccess;
+  dim3 grid((unsigned)ncells), block(64);
+  const double* d_M = nullptr;
+  if (n <= 16)
+    hipLaunchKernelGGL((k_poisson2d_fused<16, false, true>), grid, block, HOMMX_FUSED_LDS, stream, d_coef, d_M, d_out, d_info, n, ncells, src,
+                       NoFact{} HOMMX_FUSED_DBG_ARG);
+  else
+    hipLaunchKernelGGL((k_poisson2d_fused<32, false, true>), grid, block, HOMMX_FUSED_LDS, stream, d_coef, d_M, d_out, d_info, n, ncells, src,
+                       NoFact{} HOMMX_FUSED_DBG_ARG);
+  return hipGetLastError();
+}
+
+#elif !defined(HOMMX_FUSED_FACT_TU)
+hipError_t launch_poisson2d_fused(const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
+                                  int n, long long ncells, hipStream_t stream, CoefSource src) {
+  if (ncells <= 0) return hipSuccess;
+  if (!d_M) return launch_poisson2d_fused_iso(d_coef, d_out, d_info, n, ncells, stream, src);
+  dim3 grid((unsigned)ncells), block(64);
+  if (n <= 16)
+    hipLaunchKernelGGL((k_poisson2d_fused<16, false, false>), grid, block, HOMMX_FUSED_LDS, stream, d_coef, d_M, d_out, d_info, n, ncells, src,
+                       NoFact{} HOMMX_FUSED_DBG_ARG);
+  else
+    hipLaunchKernelGGL((k_poisson2d_fused<32, false, false>), grid, block, HOMMX_FUSED_LDS, stream, d_coef, d_M, d_out, d_info, n, ncells, src,
+                       NoFact{} HOMMX_FUSED_DBG_ARG);
   return hipGetLastError();
 }
 
@@ -791,20 +846,14 @@ hipError_t launch_poisson2d_fused_fact(const double* d_coef, const double* d_M, 
   if (ncells <= 0) return hipSuccess;
   dim3 grid((unsigned)ncells), block(64);
   const CoefSource src;
-#ifdef HOMMX_FUSED_DEBUG
-  extern double* g_fused_dbg;
   if (n <= 16)
-    hipLaunchKernelGGL((k_poisson2d_fused<16, true>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, d_fact, g_fused_dbg);
+    hipLaunchKernelGGL((k_poisson2d_fused<16, true, false>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src,
+                       d_fact HOMMX_FUSED_DBG_ARG);
   else
-    hipLaunchKernelGGL((k_poisson2d_fused<32, true>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, d_fact, g_fused_dbg);
-#else
-  if (n <= 16)
-    hipLaunchKernelGGL((k_poisson2d_fused<16, true>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, d_fact);
-  else
-    hipLaunchKernelGGL((k_poisson2d_fused<32, true>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src, d_fact);
-#endif
+    hipLaunchKernelGGL((k_poisson2d_fused<32, true, false>), grid, block, 0, stream, d_coef, d_M, d_out, d_info, n, ncells, src,
+                       d_fact HOMMX_FUSED_DBG_ARG);
   return hipGetLastError();
 }
-#endif  // HOMMX_FUSED_FACT_TU
+#endif
 
 }  // namespace hommx

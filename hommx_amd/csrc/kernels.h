@@ -68,6 +68,9 @@ struct CoefSource {
 // fused2d.hip: 2D scalar Poisson (optionally stratified), 3 <= n <= 32, one wave per macro cell.
 hipError_t launch_poisson2d_fused(const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
                                   int n, long long ncells, hipStream_t stream, CoefSource src = CoefSource());
+// fused2d_iso.hip: the same for unstratified cells (no M): launch_poisson2d_fused hands every call with d_M == nullptr to it
+hipError_t launch_poisson2d_fused_iso(const double* d_coef, double* d_out, int32_t* d_info, int n, long long ncells, hipStream_t stream,
+                                      CoefSource src);
 
 // The factor record of one cell, written by k_poisson2d_fused<NB, true> and read by k_fused2d_subst<NB> and k_fused2d_subst_rhs<NB> (NB = 16 for
 // n <= 16, else 32); private to the three kernels.  In doubles, with N' = -S^-1 as the elimination carries it:

@@ -23,11 +23,12 @@ st = glob.glob(out + "/stats/**/*kernel_stats.csv", recursive=True)[0]
 rows = list(csv.reader(open(st)))
 open(f"profiles/{tag}_bench_kernel_stats.csv", "w").write("\n".join(",".join('"%s"' % c for c in r) for r in rows[:6]) + "\n")
 k = json.load(open(out + "/pmc_all.json"))["kernels"]
-name = [n for n in k if "k_poisson2d_fused<32, false>" in n][0]
+# the bench line runs without M: the unstratified instantiation <32, false, true>
+name = [n for n in k if "k_poisson2d_fused<32, false" in n][0]
 e = k[name]
 per = lambda c: e[c]["per_dispatch"]
 fetch, write = per("FETCH_SIZE") * 1024, per("WRITE_SIZE") * 1024
-avg_ns = [float(r[3]) for r in rows[1:] if "k_poisson2d_fused<32, false>" in r[0]][0]
+avg_ns = [float(r[3]) for r in rows[1:] if "k_poisson2d_fused<32, false" in r[0]][0]
 s = {
     "command": "tools/profile_c2.sh: rocprofv3 --pmc <counters> -- python3 bench.py --no-c5 --no-cpu-baseline --no-host-boundary --steps 20 --warmup 3 (separate passes: FETCH_SIZE; WRITE_SIZE; two SQ sets), summarised by tools/pmc_summary.py",
     "kernel": "k_poisson2d_fused<32>",
