@@ -85,6 +85,18 @@ class SensArgs(C.Structure):
     ]
 
 
+class StratSensArgs(C.Structure):
+    """hommx_strat_sens_args: what hommx_stratification_sensitivity_source[_device] is asked for and where it goes."""
+
+    _fields_ = [
+        ("dA_dM", C.c_void_p),
+        ("weights", C.c_void_p),
+        ("grad_M", C.c_void_p),
+        ("A_eff", C.c_void_p),
+        ("info", C.c_void_p),
+    ]
+
+
 class LoadArgs(C.Structure):
     """hommx_load_args: the loads of hommx_loads_source[_device], what is asked for and where it goes."""
 
@@ -139,6 +151,8 @@ def _prototypes() -> dict:
         "hommx_reconstruct_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_sensitivity_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SensArgs)]),
         "hommx_sensitivity_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SensArgs), vp]),
+        "hommx_stratification_sensitivity_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(StratSensArgs)]),
+        "hommx_stratification_sensitivity_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(StratSensArgs), vp]),
         "hommx_loads_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(LoadArgs)]),
         "hommx_loads_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(LoadArgs), vp]),
         "hommx_solve_batch_two_phase": (c_int, [vp, i64, vp, vp, vp, vp, vp]),

@@ -141,6 +141,25 @@ class Sensitivities:
 
 
 @dataclass
+class StratSensitivities:
+    """Derivatives of A_H of macro cells with respect to the stratification M = Dtheta^T (include/hommx_hip.h,
+    hommx_stratification_sensitivity_source).
+
+    ``dA_dM[N, d, d, t, t]`` or None: the derivative of A_H[m, n] with respect to M[a, b], symmetric in its last two axes;
+    ``grad_M[N, d, d]`` or None: sum_mn weights[m, n] dA_dM[a, b, m, n], the gradient of ``weights : A_H`` with respect to M;
+    ``A_eff[N, t, t]`` and ``info[N]`` as ``solve`` returns them.  ``cells``: the macro cells; with design parameters
+    (``BaseHMM.stratification_derivatives``) ``names`` and ``dA[N, n_params, t, t]``, the derivative of A_H along each."""
+
+    dA_dM: np.ndarray | None
+    grad_M: np.ndarray | None
+    A_eff: np.ndarray
+    info: np.ndarray
+    cells: np.ndarray | None = None
+    names: tuple | None = None
+    dA: np.ndarray | None = None
+
+
+@dataclass
 class LoadResponse:
     """Effective polarisation and response of macro cells to user-supplied loads P (include/hommx_hip.h, hommx_loads_source).
 
@@ -467,6 +486,34 @@ class MicroCellPlan:
         A, info = self._host_call("hommx_sensitivity_source", nc, M, call)
         return Sensitivities(dA, grad, A, info)
 
+    def stratification_sensitivities(self, coef, M: np.ndarray | None = None, weights=None, full: bool = True) -> StratSensitivities:
+        """Derivatives of A_H with respect to the stratification M (hommx_stratification_sensitivity_source): ``coef`` an array or a
+        ``CoefStream`` and M as ``reconstruct`` takes them (without M: the derivative at M = I).  ``full`` -> ``dA_dM[N_c, d, d, t, t]``
+        = dA_H[m, n] / dM[a, b]; ``weights[N_c, t, t]`` -> ``grad_M[N_c, d, d]`` = sum_mn weights[m, n] dA_dM[a, b, m, n], formed in one
+        pass without the t x t intermediate.  At least one of the two.  The correctors never leave the device; the batch runs in the
+        chunks of ``reconstruct``."""
+        stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
+        nc = self._check_stream(stream)
+        grad = None
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64)
+            if weights.shape != (nc, self.t, self.t):
+                raise ValueError(f"weights has shape {weights.shape}; expected ({nc}, {self.t}, {self.t})")
+            grad = np.empty((nc, self.dim, self.dim), dtype=np.float64)
+        elif not full:
+            raise ValueError("nothing requested: pass weights, full=True or both")
+        dA_dM = np.empty((nc, self.dim, self.dim, self.t, self.t), dtype=np.float64) if full else None
+        src = stream.coef_source()
+        args = _lib.StratSensArgs(dA_dM.ctypes.data if full else None, None if grad is None else weights.ctypes.data,
+                                  None if grad is None else grad.ctypes.data)
+
+        def call(Mp, o, i):
+            args.A_eff, args.info = o, i
+            return self._lib.hommx_stratification_sensitivity_source(self._h, nc, C.byref(src), Mp, C.byref(args))
+
+        A, info = self._host_call("hommx_stratification_sensitivity_source", nc, M, call)
+        return StratSensitivities(dA_dM, grad, A, info)
+
     def loads(self, coef, P, M: np.ndarray | None = None, per_cell: bool | None = None, response: bool = False, fields: bool = False,
               return_correctors: bool = False) -> LoadResponse:
         """User-supplied polarisation loads (hommx_loads_source): ``coef`` an array or a ``CoefStream`` and M as ``reconstruct`` takes them.
@@ -580,6 +627,17 @@ class MicroCellPlan:
                              A_ptr or None, info_ptr or None)
         _lib.check(self._lib.hommx_sensitivity_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
                    "hommx_sensitivity_source_device")
+
+    def stratification_sensitivities_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, dA_dM_ptr: int | None = None,
+                                            weights_ptr: int | None = None, grad_M_ptr: int | None = None, A_ptr: int | None = None,
+                                            info_ptr: int | None = None, stream: int | None = None):
+        """Device-pointer form of ``stratification_sensitivities`` (hommx_stratification_sensitivity_source_device), asynchronous on
+        ``stream``: ``source`` = ``CoefStream.coef_source(upload)`` with device addresses; dA_dM[n_cells, d, d, t, t];
+        weights[n_cells, t, t] -> grad_M[n_cells, d, d]."""
+        args = _lib.StratSensArgs(dA_dM_ptr or None, weights_ptr or None, grad_M_ptr or None, A_ptr or None, info_ptr or None)
+        _lib.check(self._lib.hommx_stratification_sensitivity_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
+                                                                            stream or None),
+                   "hommx_stratification_sensitivity_source_device")
 
     def loads_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, n_loads: int, P_ptr: int, P_eff_ptr: int,
                      per_cell: bool = False, A_ptr: int | None = None, info_ptr: int | None = None, energy_ptr: int | None = None,

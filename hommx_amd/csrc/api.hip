@@ -996,6 +996,110 @@ int sens_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const 
       });
 }
 
+// -- stratification sensitivities (hommx_stratification_sensitivity_source[_device]) --------------------------------------------------------
+// device pointers of one chunk
+struct StratIO {
+  const double *coef, *M, *weights;
+  double *dA_dM, *grad_M, *A_eff;
+  int32_t* info;
+};
+
+// the argument checks of both entry points, then a route that forms correctors
+int strat_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_strat_sens_args* a, bool device) {
+  auto more = [&] {
+    if (int rc = coef_check(p, src)) return rc;
+    if (!a) return fail(HOMMX_EINVAL, "null arguments");
+    if (!a->weights != !a->grad_M) return fail(HOMMX_EINVAL, "weights and grad_M: both or neither");
+    if (!a->dA_dM && !a->grad_M) return fail(HOMMX_EINVAL, "nothing requested: neither dA_dM nor grad_M");
+    return HOMMX_OK;
+  };
+  if (int rc = open_call(p, n_cells, true, "", device, more); rc != GO) return rc;
+  if (int rc = corrector_workspace(p)) return rc;
+  return GO;
+}
+
+// one chunk of at most recon_chunk() cells on the device: the correctors into the plan's scratch, then k_sens_strat
+int strat_run(hommx_plan* p, int64_t nc, int64_t chunk, const StratIO& io, hipStream_t st) {
+  double *d_A_eff = io.A_eff, *corr = nullptr;
+  if (int rc = chunk_correctors(p, nc, chunk, io.coef, io.M, &d_A_eff, io.info, 0, st, &corr)) return rc;
+  hommx::StratSensArgs k;
+  set_geometry(p, k);
+  k.corr = corr;
+  k.coef = io.coef;
+  k.M = io.M;
+  k.dA_dM = io.dA_dM;
+  k.weights = io.weights;
+  k.grad_M = io.grad_M;
+  HIP_TRY(hommx::launch_sens_strat(k, p->desc.dim, p->desc.kind, p->desc.n_micro == 0, nc, st));
+  return HOMMX_OK;
+}
+
+// everything on the device already: the chunks are views of the caller's arrays
+int strat_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, const hommx_strat_sens_args& a, hipStream_t st) {
+  const int dd = p->desc.dim * p->desc.dim, tt = p->ks.t * p->ks.t;
+  int64_t chunk = 0;
+  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, 0), &chunk)) return rc;
+  return source_chunks<StratIO>(
+      p, n_cells, chunk, s, st,
+      [&](int64_t c0, int64_t, StratIO& io) {
+        io = StratIO{nullptr,
+                     d_M ? d_M + c0 * dd : nullptr,
+                     a.weights ? a.weights + c0 * tt : nullptr,
+                     a.dA_dM ? a.dA_dM + c0 * dd * tt : nullptr,
+                     a.grad_M ? a.grad_M + c0 * dd : nullptr,
+                     a.A_eff ? a.A_eff + c0 * tt : nullptr,
+                     a.info ? a.info + c0 : nullptr};
+        return HOMMX_OK;
+      },
+      [&](int64_t nc, const StratIO& io) { return strat_run(p, nc, chunk, io, st); },
+      [](int64_t, int64_t, const StratIO&) { return HOMMX_OK; });
+}
+
+// host pointers.  What every cell shares (mask, table, weights of the sampler) and the per-cell values of a sampler form travel once, in
+// the plan's pinned block (stage_source); a sampled stream, M and the weights stream in and every output streams out chunk by chunk, so
+// device memory is bounded by the chunk
+int strat_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_strat_sens_args& a) {
+  const int dd = p->desc.dim * p->desc.dim, tt = p->ks.t * p->ks.t;
+  const int64_t per = s.form == HOMMX_COEF_SAMPLED ? p->n_el * p->ks.n_comp : 0;
+  hommx_coef_source ds;
+  const void* none = nullptr;
+  if (int rc = stage_source(p, n_cells, s, {nullptr, 0, &none}, &ds)) return rc;
+  // doubles per cell of the plan's blocks: in = [coef | M | weights], out = [dA_dM | A_eff | grad_M], and info
+  const int64_t n_in[] = {per, M ? dd : 0, a.grad_M ? tt : 0}, n_out[] = {a.dA_dM ? (int64_t)dd * tt : 0, tt, a.grad_M ? dd : 0};
+  size_t cell = sizeof(int32_t);
+  for (int64_t k : n_in) cell += sizeof(double) * k;
+  for (int64_t k : n_out) cell += sizeof(double) * k;
+  int64_t chunk = 0;
+  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, cell), &chunk)) return rc;
+  size_t in_bytes[3], out_bytes[4];
+  for (int k = 0; k < 3; ++k) in_bytes[k] = sizeof(double) * chunk * n_in[k];
+  for (int k = 0; k < 3; ++k) out_bytes[k] = sizeof(double) * chunk * n_out[k];
+  out_bytes[3] = sizeof(int32_t) * chunk;
+  char *in[3], *out[4];
+  if (int rc = carve(p->buf[B_IN], in_bytes, in)) return rc;
+  if (int rc = carve(p->buf[B_OUT], out_bytes, out)) return rc;
+  auto f64 = [](char* at) { return reinterpret_cast<double*>(at); };
+  const StratIO dev{f64(in[0]), f64(in[1]), f64(in[2]), f64(out[0]), f64(out[2]), f64(out[1]), reinterpret_cast<int32_t*>(out[3])};
+  const double* src_in[] = {s.coef, M, a.weights};
+  return source_chunks<StratIO>(
+      p, n_cells, chunk, ds, nullptr,
+      [&](int64_t c0, int64_t nc, StratIO& io) {
+        for (int k = 0; k < 3; ++k)
+          if (n_in[k]) HIP_TRY(hipMemcpy(in[k], src_in[k] + c0 * n_in[k], sizeof(double) * nc * n_in[k], hipMemcpyHostToDevice));
+        io = dev;
+        return HOMMX_OK;
+      },
+      [&](int64_t nc, const StratIO& io) { return strat_run(p, nc, chunk, io, nullptr); },
+      [&](int64_t c0, int64_t nc, const StratIO& io) {
+        double* dst_out[] = {a.dA_dM, a.A_eff, a.grad_M};
+        for (int k = 0; k < 3; ++k)
+          if (n_out[k] && dst_out[k])
+            HIP_TRY(hipMemcpy(dst_out[k] + c0 * n_out[k], out[k], sizeof(double) * nc * n_out[k], hipMemcpyDeviceToHost));
+        if (a.info) HIP_TRY(hipMemcpy(a.info + c0, io.info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
+        return HOMMX_OK;
+      });
+}
+
 // -- polarisation loads (hommx_loads_source[_device]) ------------------------------------------------------------------------------------
 // device pointers of one chunk
 struct LoadIO {
@@ -1202,6 +1306,18 @@ int hommx_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_
 int hommx_sensitivity_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_sens_args* args) {
   if (int rc = sens_open(p, n_cells, src, args, false); rc != GO) return rc;
   return sens_host(p, n_cells, source_of_form(*src), M, *args);
+}
+
+int hommx_stratification_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                                   const hommx_strat_sens_args* args, void* stream) {
+  if (int rc = strat_open(p, n_cells, src, args, true); rc != GO) return rc;
+  return strat_device(p, n_cells, source_of_form(*src), d_M, *args, reinterpret_cast<hipStream_t>(stream));
+}
+
+int hommx_stratification_sensitivity_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M,
+                                            const hommx_strat_sens_args* args) {
+  if (int rc = strat_open(p, n_cells, src, args, false); rc != GO) return rc;
+  return strat_host(p, n_cells, source_of_form(*src), M, *args);
 }
 
 int hommx_loads_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const hommx_load_args* args,

@@ -1,5 +1,5 @@
 // elem_walk.h -- the element loop and the canonical strains of the kernels that read a cell's correctors with one workgroup per macro
-// cell and elements on lanes (sensitivity.hip, loads.hip).  `Args` carries the geometry fields of ReconArgs (kernels.h).
+// cell and elements on lanes (sensitivity.hip, loads.hip, sens_strat.hip).  `Args` carries the geometry fields of ReconArgs (kernels.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -69,6 +69,36 @@ __device__ __forceinline__ void load_strains(const double* __restrict__ corr, lo
 #pragma unroll
           for (int k = 0; k < T; ++k) s[m][k] += c * sa[k];
         }
+    }
+  }
+}
+
+// H[n][alpha][b] = sum_a chi_n[p_a bs + alpha] g_a[b]: the raw gradient of the first COUNT fields of `corr` on the element, M not applied
+// (sens_strat.hip).  Six fields of 3D elasticity take one vertex at a time, as in load_strains
+template <int DIM, int KIND, int COUNT, typename V>
+__device__ __forceinline__ void load_gradients(const double* __restrict__ corr, long long ndof, V&& vertex,
+                                               double (&H)[COUNT][kind_sizes(DIM, KIND).bs][DIM]) {
+  constexpr int BS = kind_sizes(DIM, KIND).bs, VERTS = COUNT == 6 ? 1 : DIM + 1;
+#pragma unroll
+  for (int n = 0; n < COUNT; ++n)
+#pragma unroll
+    for (int al = 0; al < BS; ++al)
+#pragma unroll
+      for (int b = 0; b < DIM; ++b) H[n][al][b] = 0.0;
+#pragma unroll VERTS
+  for (int a = 0; a < DIM + 1; ++a) {
+    int node;
+    double g[DIM];
+    vertex(a, node, g);
+#pragma unroll
+    for (int al = 0; al < BS; ++al) {
+      const double* __restrict__ at = corr + (long long)node * BS + al;
+#pragma unroll
+      for (int n = 0; n < COUNT; ++n) {
+        const double c = at[n * ndof];
+#pragma unroll
+        for (int b = 0; b < DIM; ++b) H[n][al][b] += c * g[b];
+      }
     }
   }
 }

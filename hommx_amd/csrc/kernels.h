@@ -150,6 +150,24 @@ struct SensArgs {
 };
 hipError_t launch_sensitivity(const SensArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
 
+// sens_strat.hip: derivatives of A_H with respect to the stratification M and their product with caller weights, from the correctors
+// of `nc` cells (include/hommx_hip.h, hommx_stratification_sensitivity_source).  The geometry fields are those of ReconArgs
+struct StratSensArgs {
+  int n = 0;
+  double vol_struct = 0.0;
+  long long ndof = 0, n_el = 0;
+  const int32_t* el_nodes = nullptr;
+  const double* grads = nullptr;
+  const double* vol = nullptr;
+  const double* corr = nullptr;      // [nc][t][ndof]
+  const double* coef = nullptr;      // [nc][n_el][n_comp]
+  const double* M = nullptr;         // [nc][d][d] or null
+  double* dA_dM = nullptr;           // [nc][d][d][t][t] or null
+  const double* weights = nullptr;   // [nc][t][t], with grad_M[nc][d][d]; or both null
+  double* grad_M = nullptr;
+};
+hipError_t launch_sens_strat(const StratSensArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
+
 // loads.hip: user-supplied polarisation loads P[load][el][t] (include/hommx_hip.h, hommx_loads_source).  The
 // geometry fields are those of ReconArgs.  launch_polar: P_eff from the canonical correctors (Levin); launch_load_stats: the response
 // outputs from the correctors of the loads themselves, every one of them optional

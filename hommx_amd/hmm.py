@@ -28,7 +28,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import fem
-from .batch import REGION_FIELDS, CoefStream, LoadResponse, MicroCellPlan, Reconstruction, Sensitivities, region_labels
+from .batch import REGION_FIELDS, CoefStream, LoadResponse, MicroCellPlan, Reconstruction, Sensitivities, StratSensitivities, region_labels
 from .mesh import Mesh, micro_cells_per_side
 
 _VOIGT = {2: [(0, 0), (1, 1), (0, 1)], 3: [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]}
@@ -469,14 +469,19 @@ class BaseHMM(ABC):
         call on the first and the last cell), else one call per cell as the reference does."""
         if self._Dtheta_t is None:
             return None
+        return self._matrix_at_midpoints(self._Dtheta_t, cells, "Dtheta_transpose")
+
+    def _matrix_at_midpoints(self, fn, cells: np.ndarray, name: str) -> np.ndarray:
+        """[N_c, d, d]: the matrix-valued callable ``fn`` (``Dtheta_transpose`` or its derivative with respect to a design parameter) at
+        the midpoints of the given macro cells, by the rule of ``_stratification``."""
         c = self._msh.cell_midpoints()[cells]
         d = self._tdim
         nc = len(cells)
 
         def one(x):
-            m = np.asarray(self._Dtheta_t(x), dtype=float)
+            m = np.asarray(fn(x), dtype=float)
             if m.shape != (d, d):
-                raise ValueError(f"Dtheta_transpose must return a {d}x{d} matrix (hmm.py:741, :762); got {m.shape}")
+                raise ValueError(f"{name} must return a {d}x{d} matrix (hmm.py:741, :762); got {m.shape}")
             return m
 
         if nc == 0:
@@ -489,7 +494,7 @@ class BaseHMM(ABC):
             # argument, or indexes into it, agrees at the ends at best
             probe = sorted({nc // 2, nc // 3, (2 * nc) // 3, (7 * nc) // 11, 1, nc - 2} - {0, nc - 1})
             try:
-                rows = self._Dtheta_t(c.T)
+                rows = fn(c.T)
                 mb = np.empty((d, d, nc))
                 for i in range(d):
                     for j in range(d):
@@ -499,9 +504,9 @@ class BaseHMM(ABC):
                     known[k] = one(c[k])
                 if all(np.array_equal(mb[k], v) for k, v in known.items()):
                     return mb
-                self._logger.debug("Dtheta_transpose: the broadcast call disagrees with the per-cell calls; evaluating cell by cell")
+                self._logger.debug(f"{name}: the broadcast call disagrees with the per-cell calls; evaluating cell by cell")
             except Exception as exc:
-                self._logger.debug(f"Dtheta_transpose: no broadcast evaluation ({type(exc).__name__}: {exc}); evaluating cell by cell")
+                self._logger.debug(f"{name}: no broadcast evaluation ({type(exc).__name__}: {exc}); evaluating cell by cell")
         M = np.empty((nc, d, d))
         for k in range(nc):
             M[k] = known[k] if k in known else one(c[k])
@@ -961,6 +966,82 @@ class BaseHMM(ABC):
         xv = xu if v is None else xi(v)
         vol = self._msh.cell_volumes()[td.cells] / self._cell_mesh_area
         return vol[:, None] * np.einsum("cm,cdmn,cn->cd", xv, td.dA, xu)
+
+    def _stratification_parameters(self, cells: np.ndarray, parameters) -> tuple[tuple, np.ndarray]:
+        """(names, dM[N, n_params, d, d]) of the design parameters of the stratification: every entry of ``parameters`` is a callable
+        x -> [d, d], the derivative of ``Dtheta_transpose`` with respect to one parameter, evaluated as ``_stratification`` evaluates M."""
+        parameters = list(parameters)
+        if not parameters:
+            raise ValueError("parameters must hold at least one callable x -> [d, d]")
+        names = tuple(getattr(f, "__name__", f"parameter{k}") for k, f in enumerate(parameters))
+        return names, np.stack([self._matrix_at_midpoints(f, cells, f"parameters[{k}]") for k, f in enumerate(parameters)], axis=1)
+
+    def _stratification_blocks(self, cells: np.ndarray, chunk_cells: int | None, weights=None, full: bool = True) -> list:
+        """``plan.stratification_sensitivities`` of ``cells`` in chunks of ``chunk_cells`` (default: about 256 MB of coefficient stream
+        and outputs); the coefficient crosses the boundary as ``solve()`` sends it."""
+        if chunk_cells is None:
+            d, t = self._tdim, self._tensor_size()
+            per = 8 * (self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) + d * d * (t * t if full else 1) + 2 * t * t) + 4
+            chunk_cells = (256 << 20) // per
+        ch = max(1, int(chunk_cells))
+        parts = []
+        for b in range(0, len(cells), ch):
+            sub = cells[b:b + ch]
+            stream, kind = self._coef_stream(sub)
+            coef = stream.per_cell if stream.method == "solve" else stream
+            parts.append(self._ensure_plan(kind).stratification_sensitivities(coef, self._stratification(sub),
+                                                                              weights=None if weights is None else weights[b:b + ch], full=full))
+        return parts
+
+    def stratification_derivatives(self, cells=None, parameters=None, chunk_cells: int | None = None) -> StratSensitivities:
+        """Derivatives of A_H / C_H of ``cells`` (default: this rank's macro cells) with respect to the stratification M = Dtheta^T(c_T)
+        (hommx_stratification_sensitivity_source) -> ``StratSensitivities`` with ``dA_dM[N, d, d, t, t]``, ``A_eff``, ``info``
+        and ``cells``.  A class without stratification differentiates at M = I.
+
+        ``parameters=[dM_0, ...]``: callables x -> [d, d], the derivative of ``Dtheta_transpose`` with respect to a design parameter (a
+        fibre angle, a curvature), evaluated as ``Dtheta_transpose`` itself is; the result then also carries ``names`` and
+        ``dA[N, n_params, t, t]`` = sum_ab dM_p[a, b] dA_dM[:, a, b], the derivative of A_H along each parameter (formed on the host).
+
+        The cells run in chunks of ``chunk_cells``.  Under a process group this runs on the calling rank alone: there is no collective."""
+        cells = self._local_cells() if cells is None else np.asarray(cells, dtype=np.int64).ravel()
+        if len(cells) == 0:
+            raise ValueError("stratification_derivatives() needs at least one macro cell")
+        parts = self._stratification_blocks(cells, chunk_cells)
+        cat = lambda name: np.concatenate([getattr(r, name) for r in parts])
+        out = StratSensitivities(cat("dA_dM"), None, cat("A_eff"), cat("info"), cells)
+        if parameters is not None:
+            out.names, dM = self._stratification_parameters(cells, parameters)
+            out.dA = np.einsum("cpab,cabmn->cpmn", dM, out.dA_dM)
+        return out
+
+    def stratification_energy_derivatives(self, u=None, v=None, cells=None, parameters=None) -> np.ndarray:
+        """[N, d, d]: vol(T)/vol(Y) sum_mn xi_v(T)[m] dA_H[m, n]/dM(T) xi_u(T)[n] for ``cells`` (default: this rank's macro cells), with xi
+        the macro gradient / Voigt strain ``reconstruct()`` forms -- the derivative of the contribution of macro cell T to v . K_H u with
+        respect to its M at frozen u, v: the compliance gradient for v = u (the default; ``u`` defaults to the last ``solve()`` result),
+        the adjoint product otherwise.  The weights xi_v (x) xi_u go to the device, only d d numbers per cell come back.  With
+        ``parameters`` (as ``stratification_derivatives`` takes them) the result is contracted with them: [N, n_params]."""
+        if u is None:
+            if not self._solved:
+                raise RuntimeError("stratification_energy_derivatives() needs a macro solution: call solve() first or pass u")
+            u = self._u
+        cells = self._local_cells() if cells is None else np.asarray(cells, dtype=np.int64).ravel()
+        if len(cells) == 0:
+            raise ValueError("stratification_energy_derivatives() needs at least one macro cell")
+
+        def xi(f):
+            x = np.asarray(f.x.array if hasattr(f, "x") else f, dtype=float)
+            if x.shape != (self._num_global_dofs,):
+                raise ValueError(f"the macro field has {x.size} dofs; the macro space has {self._num_global_dofs}")
+            return self._macro_strains(cells, x)
+
+        xu = xi(u)
+        xv = xu if v is None else xi(v)
+        parts = self._stratification_blocks(cells, None, weights=np.einsum("cm,cn->cmn", xv, xu), full=False)
+        vol = self._msh.cell_volumes()[cells] / self._cell_mesh_area
+        grad = vol[:, None, None] * np.concatenate([r.grad_M for r in parts])
+        if parameters is None:
+            return grad
+        return np.einsum("cpab,cab->cp", self._stratification_parameters(cells, parameters)[1], grad)
 
     def plot_solution(self, u=None):  # hmm.py:493-511 (visualisation: out of scope)
         raise NotImplementedError("plotting is out of scope of hommx_amd; use u.x.array with any plotting tool")

@@ -327,6 +327,43 @@ int hommx_sensitivity_source_device(hommx_plan* plan, int64_t n_cells, const hom
                                     const hommx_sens_args* args, void* stream);
 
 /*
+ * Derivatives of A_H with respect to the stratification M.  M = Dtheta^T(c_T) enters a cell problem only through
+ * the strain of a local dof, which is linear in it: with H^n_K[alpha][b] = sum_a chi_n[p_a bs + alpha] g_a[b] the raw gradient of the
+ * canonical corrector n on micro element K (no M), s^n_K = e_n + voigt(H^n_K M^T) is the s^n_K of hommx_sensitivity_source (shear doubled)
+ * and sigma^n_K = material(coef_K) s^n_K its flux / stress (Poisson: the vector q^n[a]; elasticity: the symmetric d x d tensor of the Voigt
+ * vector, shear NOT doubled).  C0 does not depend on M, and exactly on the discrete problem
+ *   dA_dM[c][a][b][m][n] = sum_K |K| [ (sigma^m_K H^n_K)[a][b] + (sigma^n_K H^m_K)[a][b] ]         (Poisson: q^m[a] h^n[b] + q^n[a] h^m[b])
+ * -- no derivative of a corrector appears (the cell equation makes those terms vanish) and the gauge does not matter.  A_H being
+ * 0-homogeneous in M (scaling M rescales the correctors), sum_{a,b} M[a][b] dA_dM[c][a][b] = 0 (Euler).  With weights w[c][t][t] the call
+ * also returns the adjoint product
+ *   grad_M[c][a][b] = sum_{m,n} w[c][m][n] dA_dM[c][a][b][m][n]
+ * in one pass and without the t x t intermediate: d d numbers per cell instead of d d t t (w = xi_v (x) xi_u: the derivative of the
+ * energy density xi_v . A_H xi_u).
+ *
+ *   dA_dM       [n_cells][d][d][t][t] (symmetric in (m, n), bitwise), or NULL
+ *   weights     [n_cells][t][t] and grad_M [n_cells][d][d]: both or neither
+ *   A_eff, info as hommx_solve_batch, or NULL
+ * src, M: as hommx_reconstruct_source; M == NULL differentiates at M = I.  HOMMX_EINVAL, before the plan's device is made current: a null
+ * plan, source or argument struct, one of weights / grad_M without the other, nothing requested (neither dA_dM nor grad_M).  Every plan
+ * is accepted; the correctors of one chunk (HOMMX_RECON_MEM_MB, the chunk rule of the reconstruction) live in plan-owned scratch.  A
+ * cell's outputs do not depend on its batch position, the chunking or which outputs are requested (fixed-order reduction).  A cell whose
+ * elimination flags a pivot keeps its info; its outputs may hold anything, no other cell's change.  The host entry sends a sampled stream,
+ * M and the weights in, and every output back, chunk by chunk.
+ */
+typedef struct hommx_strat_sens_args {
+  double* dA_dM;
+  const double* weights;
+  double* grad_M;
+  double* A_eff;
+  int32_t* info;
+} hommx_strat_sens_args;
+int hommx_stratification_sensitivity_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M,
+                                            const hommx_strat_sens_args* args);
+/* Same with DEVICE pointers (in *src and *args as well; the structs themselves are host memory), asynchronous on `stream`. */
+int hommx_stratification_sensitivity_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                                   const hommx_strat_sens_args* args, void* stream);
+
+/*
  * User-supplied polarisation loads of the cell problem: a prescribed micro flux / stress field P(y), such as a
  * thermal eigenstress -A : alpha dT, a prestress, the gravity term of Darcy flow or the residual of a Newton step.  Per macro cell the
  * caller gives n_loads fields P^l[n_el][t], constant per micro element, components in the order of hommx_reconstruct_batch's flux
