@@ -142,11 +142,21 @@ double hommx_plan_flops_per_solve(const hommx_plan* plan);
 int hommx_solve_batch(hommx_plan* plan, int64_t n_cells, const double* coef, const double* M,
                       double* A_eff, int32_t* info);
 
-/* Same with DEVICE pointers, asynchronous on `stream` (a hipStream_t, NULL = default stream).
- * No caller pointer is retained after return; the caller synchronises the stream before reading A_eff.  The blocked and
- * small-block kernel families work out of scratch the PLAN owns (workspace, expanded coefficient stream): a plan is not
- * thread-safe, and two calls on the same plan must not be in flight on different streams at once (distinct plans are
- * independent; the fused 2D family keeps no scratch). */
+/* Same with DEVICE pointers, asynchronous on `stream` (a hipStream_t, NULL = default stream).  What that means, here and for every
+ * other *_device entry point below (the stream-order contract; tests/test_gpu_stream_order.py pins it):
+ *   - the call only queues work.  The inputs are read, and the outputs and the plan's scratch written, in the order of `stream`: behind
+ *     everything queued on `stream` before the call (an input may still be in flight there when the call is made), and before anything
+ *     queued on it afterwards (a later command on `stream` may read the outputs, overwrite the inputs or free them in stream order);
+ *   - work the plan puts on streams of its own (the pieces of a nested-dissection chunk, HOMMX_MF_STREAMS) starts behind everything
+ *     queued on `stream` before the call, and `stream` continues only behind all of that work;
+ *   - a call may block the host while it grows the plan's scratch (a first call, a larger batch: hipFree / hipMalloc); it never
+ *     waits for its own work, so the caller synchronises `stream`, or orders against it, before reading an output on the host or on
+ *     another stream.
+ * The library keeps no caller pointer beyond the work this call has queued: the arrays must stay valid until that work has run (free
+ * them in stream order or after a synchronise, not on return).  The blocked and small-block kernel families work out of scratch the
+ * PLAN owns (workspace, expanded coefficient stream): a plan is not thread-safe, and two calls on the same plan must not be in flight on
+ * different streams at once (distinct plans are independent; the fused 2D family keeps no scratch beyond the factor records of its
+ * corrector route). */
 int hommx_solve_batch_device(hommx_plan* plan, int64_t n_cells, const double* d_coef, const double* d_M,
                              double* d_A_eff, int32_t* d_info, void* stream);
 
@@ -165,7 +175,7 @@ int hommx_solve_batch_device(hommx_plan* plan, int64_t n_cells, const double* d_
 int hommx_solve_batch_two_phase(hommx_plan* plan, int64_t n_cells, const uint8_t* mask, const double* values,
                                 const double* M, double* A_eff, int32_t* info);
 
-/* Same with DEVICE pointers, asynchronous on `stream`. */
+/* Same with DEVICE pointers, asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
 int hommx_solve_batch_two_phase_device(hommx_plan* plan, int64_t n_cells, const uint8_t* d_mask, const double* d_values,
                                        const double* d_M, double* d_A_eff, int32_t* d_info, void* stream);
 
@@ -190,7 +200,7 @@ int hommx_solve_batch_two_phase_device(hommx_plan* plan, int64_t n_cells, const 
 int hommx_solve_batch_separable(hommx_plan* plan, int64_t n_cells, int32_t family, int32_t n_q, const double* table,
                                 const double* weights, const double* params, const double* M, double* A_eff, int32_t* info);
 
-/* Same with DEVICE pointers, asynchronous on `stream`. */
+/* Same with DEVICE pointers, asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
 int hommx_solve_batch_separable_device(hommx_plan* plan, int64_t n_cells, int32_t family, int32_t n_q, const double* d_table,
                                        const double* d_weights, const double* d_params, const double* d_M, double* d_A_eff,
                                        int32_t* d_info, void* stream);
@@ -232,7 +242,7 @@ int hommx_solve_batch_correctors(hommx_plan* plan, int64_t n_cells, const double
 #define HOMMX_RECON_NSTATS(t) (2 * (t) + 3) /* [mean_strain(t) | mean_flux(t) | energy | max_flux | argmax_element] */
 int hommx_reconstruct_batch(hommx_plan* plan, int64_t n_cells, const double* coef, const double* M, const double* xi, double* stats,
                             double* strain, double* flux, double* A_eff, int32_t* info);
-/* Same with DEVICE pointers, asynchronous on `stream`; the plan's scratch is shared with its other entry points (not thread-safe). */
+/* Same with DEVICE pointers, asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract); the plan's scratch is shared with its other entry points (not thread-safe). */
 int hommx_reconstruct_batch_device(hommx_plan* plan, int64_t n_cells, const double* d_coef, const double* d_M, const double* d_xi,
                                    double* d_stats, double* d_strain, double* d_flux, double* d_A_eff, int32_t* d_info, void* stream);
 
@@ -280,7 +290,7 @@ typedef struct hommx_coef_source {
 int hommx_reconstruct_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const double* xi,
                              int32_t n_regions, const uint8_t* region, double* stats, double* region_stats, double* strain, double* flux,
                              double* A_eff, int32_t* info);
-/* Same with DEVICE pointers (in *src as well; the struct itself is host memory), asynchronous on `stream`. */
+/* Same with DEVICE pointers (in *src as well; the struct itself is host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
 int hommx_reconstruct_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const double* d_xi,
                                     int32_t n_regions, const uint8_t* d_region, double* d_stats, double* d_region_stats, double* d_strain,
                                     double* d_flux, double* d_A_eff, int32_t* d_info, void* stream);
@@ -322,7 +332,7 @@ typedef struct hommx_sens_args {
   int32_t* info;
 } hommx_sens_args;
 int hommx_sensitivity_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_sens_args* args);
-/* Same with DEVICE pointers (in *src and *args as well; the structs themselves are host memory), asynchronous on `stream`. */
+/* Same with DEVICE pointers (in *src and *args as well; the structs themselves are host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
 int hommx_sensitivity_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                                     const hommx_sens_args* args, void* stream);
 
@@ -359,7 +369,7 @@ typedef struct hommx_strat_sens_args {
 } hommx_strat_sens_args;
 int hommx_stratification_sensitivity_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M,
                                             const hommx_strat_sens_args* args);
-/* Same with DEVICE pointers (in *src and *args as well; the structs themselves are host memory), asynchronous on `stream`. */
+/* Same with DEVICE pointers (in *src and *args as well; the structs themselves are host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
 int hommx_stratification_sensitivity_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                                                    const hommx_strat_sens_args* args, void* stream);
 
@@ -413,7 +423,7 @@ typedef struct hommx_load_args {
   int32_t* info;
 } hommx_load_args;
 int hommx_loads_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_load_args* args);
-/* Same with DEVICE pointers (in *src and *args as well; the structs themselves are host memory), asynchronous on `stream`. */
+/* Same with DEVICE pointers (in *src and *args as well; the structs themselves are host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
 int hommx_loads_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                               const hommx_load_args* args, void* stream);
 
