@@ -107,7 +107,8 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 // B_RCORR, B_RA: the correctors of one reconstruction chunk (and the chi^xi slots of cells too large for LDS), A_eff the caller did not ask for
 // B_FACT: the factor records of one chunk of a fused 2D plan's corrector route (kernels.h)
 // B_LOADS: what a load pass leaves where a corrector pass leaves A_eff (hommx_loads_source: C0 - f^T K^+ f, unused)
-enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, N_BUF };
+// B_REFINE: canonical flux field and correction of the refinement step of a fused 2D plan's correctors (10 n^2 doubles per cell)
+enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, N_BUF };
 
 }  // namespace
 
@@ -184,6 +185,8 @@ bool fused_subst(const hommx_plan* p) { return p->family == FAM_FUSED2D && p->fu
 bool fused_loads(const hommx_plan* p) { return fused_subst(p) && p->fused_loads; }
 // bytes of factor record per cell of that route (0 on every other)
 size_t fact_bytes(const hommx_plan* p) { return fused_subst(p) ? sizeof(double) * hommx::fused_fact_doubles(p->desc.n_micro) : 0; }
+// ... and of the scratch of its refinement step: the canonical flux field (8 n^2 doubles) and the correction (2 n^2)
+size_t refine_bytes(const hommx_plan* p) { return fused_subst(p) ? sizeof(double) * 10 * p->desc.n_micro * p->desc.n_micro : 0; }
 
 // a failed call into the plan's route, under the route's name
 int route_fail(const hommx_plan* p, int rc) { return prefix_error(rc, p->desc.n_micro ? "blocked path: " : "mesh route: "); }
@@ -197,6 +200,11 @@ int route_solve(hommx_plan* p, int64_t n_cells, const double* d_coef, const doub
     double* fact = static_cast<double*>(p->buf[B_FACT].p);
     HIP_TRY(hommx::launch_poisson2d_fused_fact(d_coef, d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st, fact));
     HIP_TRY(hommx::launch_fused2d_subst(fact, d_corr, p->desc.n_micro, n_cells, st));
+    // one refinement step: the substitution on explicit block inverses loses a larger multiple of cond(K) eps than a sparse LU
+    const size_t nn = (size_t)p->desc.n_micro * p->desc.n_micro;
+    if (int rc = grow(p->buf[B_REFINE], refine_bytes(p) * n_cells)) return rc;
+    double* q = static_cast<double*>(p->buf[B_REFINE].p);
+    HIP_TRY(hommx::launch_fused2d_refine(fact, d_coef, d_M, d_corr, q, q + 8 * nn * n_cells, p->desc.n_micro, n_cells, st));
     return HOMMX_OK;
   }
   const int rc = p->family == FAM_MESH ? hommx::mesh_solve(p->mesh, n_cells, d_coef, d_M, d_A_eff, d_info, st, d_corr)
@@ -693,10 +701,10 @@ namespace {
 bool recon_in_lds(const hommx_plan* p) { return sizeof(double) * plan_ndof(p) <= hommx::recon_lds_limit(); }
 
 // cells per chunk: HOMMX_RECON_MEM_MB of correctors (with the chi^xi slots of cells too large for LDS), of the factor records of a fused
-// 2D plan's own corrector route and of `extra` bytes per cell
+// 2D plan's own corrector route with its refinement scratch, and of `extra` bytes per cell
 int64_t recon_chunk(const hommx_plan* p, int64_t n_cells, size_t extra) {
   const long long nd = plan_ndof(p);
-  const size_t per = sizeof(double) * nd * (p->ks.t + (recon_in_lds(p) ? 0 : 1)) + fact_bytes(p) + extra;
+  const size_t per = sizeof(double) * nd * (p->ks.t + (recon_in_lds(p) ? 0 : 1)) + fact_bytes(p) + refine_bytes(p) + extra;
   return std::clamp<int64_t>((int64_t)((p->recon_mem_mb << 20) / per), 1, n_cells);
 }
 

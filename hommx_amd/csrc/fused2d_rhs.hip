@@ -215,4 +215,60 @@ hipError_t launch_fused2d_subst_rhs(const double* d_fact, const double* d_P, int
   return hipGetLastError();
 }
 
+// ---- one step of iterative refinement of the canonical correctors ---------------------------------------------------------------
+// The residual of K chi_m = b_m is the load vector of the polarisation field q^m_K = a_K (e_m + M grad chi_m): r = -f(q^m).  So the correction
+// is the load corrector of P = q^m on the same record: k_fused2d_subst_rhs with per-cell loads, then chi_m += delta_m (both mean-free).
+// One thread per element; q[cell][m][element][2], the layout of P.
+__global__ __launch_bounds__(256) void k_fused2d_canonical_flux(const double* __restrict__ coef, const double* __restrict__ Mmat,
+                                                                const double* __restrict__ corr, double* __restrict__ q, int n, long long ncells) {
+  const long long n_el = 2ll * n * n, nn = (long long)n * n;
+  const long long w = blockIdx.x * 256ll + threadIdx.x;
+  if (w >= ncells * n_el) return;
+  const long long cell = w / n_el;
+  const int e = (int)(w - cell * n_el), s = e & 1, ci = (e >> 1) % n, cj = (e >> 1) / n;
+  double Mp[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) Mp[k] = Mmat ? Mmat[cell * 4 + k] : (k % 3 == 0 ? 1.0 : 0.0);
+  const double hn = (double)n, a = coef[w];
+  const double* chi = corr + cell * 2 * nn;
+  double sm[2][2] = {{1.0, 0.0}, {0.0, 1.0}};
+#pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    const int ii = ci + kOff2[s][v][0], jj = cj + kOff2[s][v][1];
+    const long long node = (ii == n ? 0 : ii) + (long long)n * (jj == n ? 0 : jj);
+    const double g[2] = {kGrad2[s][v][0] * hn, kGrad2[s][v][1] * hn};
+    double sb[2];
+    strain<2, HOMMX_KIND_POISSON_SCALAR>(g, Mp, 0, sb);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const double c = chi[m * nn + node];
+      sm[m][0] = fma(c, sb[0], sm[m][0]);
+      sm[m][1] = fma(c, sb[1], sm[m][1]);
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    double* out = q + ((cell * 2 + m) * n_el + e) * 2;
+    out[0] = a * sm[m][0];
+    out[1] = a * sm[m][1];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_fused2d_add(double* __restrict__ corr, const double* __restrict__ delta, long long total) {
+  const long long w = blockIdx.x * 256ll + threadIdx.x;
+  if (w < total) corr[w] += delta[w];
+}
+
+// d_q: 8 n^2 doubles per cell, d_delta: 2 n^2 doubles per cell (scratch)
+hipError_t launch_fused2d_refine(const double* d_fact, const double* d_coef, const double* d_M, double* d_corr, double* d_q, double* d_delta, int n,
+                                 long long ncells, hipStream_t stream) {
+  if (ncells <= 0) return hipSuccess;
+  const long long els = ncells * 2ll * n * n;
+  hipLaunchKernelGGL(k_fused2d_canonical_flux, dim3((unsigned)((els + 255) / 256)), dim3(256), 0, stream, d_coef, d_M, d_corr, d_q, n, ncells);
+  if (hipError_t e = hipGetLastError()) return e;
+  if (hipError_t e = launch_fused2d_subst_rhs(d_fact, d_q, 2, true, d_M, d_delta, n, ncells, stream)) return e;
+  hipLaunchKernelGGL(k_fused2d_add, dim3((unsigned)((els + 255) / 256)), dim3(256), 0, stream, d_corr, d_delta, els);
+  return hipGetLastError();
+}
+
 }  // namespace hommx

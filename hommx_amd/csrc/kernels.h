@@ -95,6 +95,10 @@ hipError_t launch_fused2d_subst(const double* d_fact, double* d_corr, int n, lon
 // forms it; d_M [ncells][2][2] or null
 hipError_t launch_fused2d_subst_rhs(const double* d_fact, const double* d_P, int n_loads, bool per_cell, const double* d_M, double* d_corr, int n,
                                     long long ncells, hipStream_t stream);
+// one step of iterative refinement of the canonical correctors of a fused 2D plan on its own record: the residual is the load vector of the
+// canonical flux field, the correction its load corrector (fused2d_rhs.hip).  Scratch: d_q 8 n^2 doubles, d_delta 2 n^2 doubles per cell
+hipError_t launch_fused2d_refine(const double* d_fact, const double* d_coef, const double* d_M, double* d_corr, double* d_q, double* d_delta, int n,
+                                 long long ncells, hipStream_t stream);
 
 // assembly.hip: coef[cell][el][comp] of a separable coefficient (AFFINE / RECIPROCAL; params[cell][comp] = (a, b)) expanded into the element stream
 hipError_t launch_expand_separable(CoefSource src, const double* d_params, double* d_coef, long long n_el, int n_comp, long long ncells,

@@ -1,6 +1,6 @@
 """GPU side of the accuracy and pivot-contract tests: runs the case groups of tests/accuracy_ref.py through the plans and returns raw
 results.  Nothing here computes a bound.  Environment knobs are read when a plan is created, so the forced groups run this module as a
-child process:  python accuracy_gpu.py <accuracy|pivot> <group> <out.npz>."""
+child process:  python accuracy_gpu.py <accuracy|pivot|derived> <group> <out.npz>  (the derived outputs have the default group only)."""
 
 from __future__ import annotations
 
@@ -63,6 +63,7 @@ def run_accuracy_group(group: str) -> dict:
             A, info = p.solve(coef * 2.0**k, M, return_info=True)
             out[f"sweepA|{skey(kind, dim, n, flags)}|{k}"] = A
             out[f"sweepinfo|{skey(kind, dim, n, flags)}|{k}"] = info
+    _run_stratification(group, out)
     if group != "default":
         return out
     for kernel, kind, builder, args, route in R.MESH_CASES:
@@ -104,6 +105,80 @@ def run_accuracy_group(group: str) -> dict:
             out["lsw_chi|" + tail], out["lsw_info|" + tail] = chi, np.maximum(info, r.info)
             out["lsw_Peff|" + tail], out["lsw_energy|" + tail], out["lsw_mean|" + tail] = r.P_eff, r.energy, r.mean_flux
             out["lsw_lchi|" + tail] = r.correctors
+    return out
+
+
+def _case_plan(case, geometry):
+    """The plan of a case without its group, structured or mesh, with its route asserted."""
+    if R.is_mesh_case(case):
+        return _mesh_plan(case[0], case[1], geometry["kw"]["msh"], case[4])
+    return _plan(*case[:4], case[4] if len(case) > 4 else 0)
+
+
+def _run_stratification(group: str, out: dict):
+    """The M_CASES of the group: badly conditioned M on log2 and the top-contrast family, and log2 with coef * 2^k, M * 2^j."""
+    for case in R.M_CASES:
+        if case[0] != group:
+            continue
+        case, cid = case[1:], R.case_id(case[1:])
+        p = None
+        for family in ("log2", R.top_family(case[1])):
+            for mf in R.M_CONDITIONING:
+                coef, M, g = R.case_inputs(case, family, mf)
+                p = p or _case_plan(case, g)
+                out[f"MA|{cid}|{family}|{mf}"], out[f"Minfo|{cid}|{family}|{mf}"] = p.solve(coef, M, return_info=True)
+        coef, M, _ = R.case_inputs(case, "log2", "mild")
+        for k, j in R.M_SCALES:
+            out[f"MsA|{cid}|{k}|{j}"], out[f"Msinfo|{cid}|{k}|{j}"] = p.solve(coef * 2.0**k, M * 2.0**j, return_info=True)
+
+
+def _derived_calls(p, coef, M, inp, with_response: bool) -> dict:
+    """One call each of reconstruct, sensitivities, stratification_sensitivities and loads on NC cells; the arrays under the names of
+    accuracy_ref.derived_truth, ``info`` the largest of the four."""
+    nc = coef.shape[0]
+    tile = lambda v: np.ascontiguousarray(np.broadcast_to(v, (nc,) + v.shape))  # noqa: E731
+    r = p.reconstruct(coef, tile(inp["xi"]), M, fields=True, regions=inp["labels"])
+    s = p.sensitivities(coef, M, directions=inp["directions"], weights=tile(inp["weights"]))
+    m = p.stratification_sensitivities(coef, M, weights=tile(inp["weights"]), full=True)
+    out = {"A": r.A_eff, "strain": r.strain, "flux": r.flux, "mean_strain": r.mean_strain, "mean_flux": r.mean_flux, "energy": r.energy,
+           "max_flux": r.max_flux, "argmax": r.argmax_element, "region_volume": r.region_volume, "region_mean_strain": r.region_mean_strain,
+           "region_mean_flux": r.region_mean_flux, "region_energy": r.region_energy, "region_max_flux": r.region_max_flux,
+           "region_argmax": r.region_argmax_element, "dA": s.dA, "grad": s.grad, "dA_dM": m.dA_dM, "grad_M": m.grad_M}
+    info = np.maximum(np.maximum(r.info, s.info), m.info)
+    if with_response:
+        l = p.loads(coef, inp["loads"], M, response=True, fields=True, return_correctors=True)
+        out.update(load_chi=l.correctors, P_eff=l.P_eff, load_mean_flux=l.mean_flux, load_energy=l.energy, load_strain=l.strain,
+                   load_flux=l.flux, load_max_flux=l.max_flux, load_argmax=l.argmax_element)
+    else:  # the frontal mesh route solves no load problem: P_eff by Levin's identity alone
+        l = p.loads(coef, inp["loads"], M)
+        out["P_eff"] = l.P_eff
+    out["info"] = np.maximum(info, l.info)
+    return out
+
+
+def run_derived_group(group: str = "default") -> dict:
+    """Every derived output of every DERIVED_CASES case and family (keys d|case|family index|name), and of the DERIVED_SWEEP_CASES with
+    coef * 2^k, M * 2^j, loads * 2^k (keys dsw|case|k|j|name)."""
+    out = {}
+    for case in R.DERIVED_CASES:
+        kernel, ckernel, cs = R.derived_case(case)
+        cid = R.case_id(cs)
+        coef0, _, g = R.case_inputs(cs, "log2", None)
+        inp = R.derived_inputs(cs, coef0[0])
+        p = _case_plan(cs, g)
+        assert p.corrector_kernel == ckernel, (p.corrector_kernel, ckernel)
+        response = p.load_kernel != "none"
+        assert response == (kernel != "mesh_front")
+        for fi, (family, mf) in enumerate(R.DERIVED_FAMILIES):
+            coef, M, _ = R.case_inputs(cs, family or R.top_family(cs[1]), mf)
+            for name, v in _derived_calls(p, coef, M, inp, response).items():
+                out[f"d|{cid}|{fi}|{name}"] = v
+        if case in R.DERIVED_SWEEP_CASES:
+            coef, M, _ = R.case_inputs(cs, "log2", "mild")
+            for k, j in R.DERIVED_SWEEP_KJ:
+                scaled = dict(inp, loads=inp["loads"] * 2.0**k)
+                for name, v in _derived_calls(p, coef * 2.0**k, M * 2.0**j, scaled, response).items():
+                    out[f"dsw|{cid}|{k}|{j}|{name}"] = v
     return out
 
 
@@ -218,7 +293,7 @@ def run_pivot_group(group: str) -> dict:
     return out
 
 
-RUNNERS = {"accuracy": run_accuracy_group, "pivot": run_pivot_group}
+RUNNERS = {"accuracy": run_accuracy_group, "pivot": run_pivot_group, "derived": run_derived_group}
 
 
 def run_in_child(what: str, group: str, tmp_path) -> dict:

@@ -1,6 +1,8 @@
 """The extended-precision reference of tests/accuracy_ref.py checks itself (CPU only): its two solvers against each other, against a
 40-digit mpmath solve, the structured against the mesh path, and the float64 yardsticks of the GPU accuracy tests on every case family
-(below 1e-12: an ill-posed input cannot loosen a GPU bound unnoticed)."""
+(below 1e-12: an ill-posed input cannot loosen a GPU bound unnoticed).  The derived truth (reconstruction, derivatives, loads): its exact
+identities to 1e-16, dA_dM against a central difference of ``truth``, the exact scaling laws under coef 2^k, M 2^j, loads 2^k, and caps on
+every yardstick the GPU tests of the derived outputs and of the stratification families use (1e-11; correctors 1e-10)."""
 
 import numpy as np
 import pytest
@@ -150,3 +152,123 @@ def test_truth_scales_exactly_with_a_power_of_two():
     for k in (-40, 40):
         A, c = R.truth("poisson", x, cells, tp, coef[0] * 2.0**k, M[0])
         assert R.rel(A * LD(2.0) ** -k, A0) < 1e-18 and R.rel(c, c0) < 1e-17
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the derived truth (reconstruction, coefficient and stratification derivatives, loads) and the stratification families
+# ------------------------------------------------------------------------------------------------------------------------------
+
+SMALL = [("poisson", 2, 16), ("poisson_matrix", 2, 12), ("elasticity", 2, 10), ("elasticity_voigt", 2, 7),
+         ("poisson", 3, 6), ("elasticity", 3, 4), ("poisson_matrix", 3, 3), ("elasticity_voigt", 3, 3)]
+
+
+def _small_cell(kind, dim, n, m_family="mild"):
+    case = ("host", kind, dim, n)
+    coef, M, g = R.case_inputs(case, "log2", m_family)
+    return case, coef[0], M[0], g, R.derived_inputs(case, coef[0])
+
+
+def _small(v, ref) -> float:
+    return float(np.abs(np.asarray(v, dtype=LD)).max() / np.abs(np.asarray(ref, dtype=LD)).max())
+
+
+@pytest.mark.parametrize("kind,dim,n", SMALL)
+def test_identities_of_the_derived_truth(kind, dim, n):
+    """In long double, to 1e-16 of the quantity's largest entry."""
+    case, coef, M, g, inp = _small_cell(kind, dim, n)
+    ne = len(coef)
+    canon = np.transpose(R.voigt_material(kind, coef, dim), (2, 0, 1))  # P^m = V e_m, in long double: lambda + 2 mu is no float64
+    T = R.derived_truth(kind, g["x"], g["cells"], g["tp"], coef, M, inp["xi"], np.concatenate([coef[None], inp["directions"][1:]]),
+                        inp["weights"], canon, inp["labels"])
+    A, xi, W = T["A"], inp["xi"].astype(LD), inp["weights"].astype(LD)
+    tol = 1e-16
+    assert all(v.dtype == LD for v in T.values() if isinstance(v, np.ndarray))
+    assert R.rel(T["mean_strain"], xi) <= tol and R.rel(T["mean_flux"], A @ xi) <= tol and R.rel(T["energy"], xi @ A @ xi) <= tol
+    assert R.rel(T["dA"][0], A) <= tol  # Euler: A_H is homogeneous of degree one in the coefficient
+    for d in range(3):
+        terms = T["grad"] * (coef if d == 0 else inp["directions"][d]).astype(LD)
+        assert abs(terms.sum() - (W * T["dA"][d]).sum()) <= tol * np.abs(terms).max(), d
+    assert _small(np.einsum("abmn,ab->mn", T["dA_dM"], M.astype(LD)), T["dA_dM"]) <= tol  # the derivative of the invariance under M -> c M
+    assert R.rel(T["grad_M"], np.einsum("mn,abmn->ab", W, T["dA_dM"])) <= tol
+    assert R.rel(T["P_eff"].T, A) <= tol and R.rel(T["load_energy"], T["C0"] - A) <= tol  # the canonical loads reproduce A_H
+    # regions cover the cell
+    assert R.rel(T["region_volume"].sum(), 1.0) <= tol and R.rel(T["region_energy"].sum(), T["energy"]) <= tol
+    assert R.rel(T["region_volume"] @ T["region_mean_flux"], T["mean_flux"]) <= tol and T["region_max_flux"].max() == T["max_flux"]
+
+
+@pytest.mark.parametrize("kind,dim,n", [("poisson", 2, 5), ("elasticity_voigt", 2, 4), ("elasticity", 3, 3)])
+def test_dA_dM_against_a_central_difference_of_truth(kind, dim, n):
+    """Step 2^-20 in long double: truncation h^2 ~ 1e-12, rounding 1e-19 / h ~ 1e-13; agreement to 1e-10."""
+    case, coef, M, g, inp = _small_cell(kind, dim, n)
+    T = R.derived_truth(kind, g["x"], g["cells"], g["tp"], coef, M)
+    h = 2.0**-20
+    for a in range(dim):
+        for b in range(dim):
+            E = np.zeros((dim, dim))
+            E[a, b] = h
+            Ap = R.truth(kind, g["x"], g["cells"], g["tp"], coef, M + E)[0]
+            Am = R.truth(kind, g["x"], g["cells"], g["tp"], coef, M - E)[0]
+            assert float(np.abs((Ap - Am) / LD(2 * h) - T["dA_dM"][a, b]).max() / np.abs(T["dA_dM"]).max()) <= 1e-10, (a, b)
+
+
+@pytest.mark.parametrize("kind,dim,n", [("poisson", 2, 5), ("elasticity", 3, 3)])
+def test_scaling_laws_are_exact(kind, dim, n):
+    """coef * 2^k, M * 2^j, loads * 2^k with xi, directions and weights fixed: every derived output scales by the power of two of
+    accuracy_ref.SCALING_LAWS, to 4 eps_ld of its largest entry, and the argmax stays.  This test decides the laws the GPU sweeps use."""
+    case, coef, M, g, inp = _small_cell(kind, dim, n)
+    args = (inp["xi"], inp["directions"], inp["weights"])
+    T0 = R.derived_truth(kind, g["x"], g["cells"], g["tp"], coef, M, *args, inp["loads"], inp["labels"])
+    tol = 4 * float(np.finfo(LD).eps)
+    for k, j in ((40, 0), (-40, 0), (0, 20), (0, -20), (0, 10), (40, -20), (-40, 20), (40, 20)):
+        T = R.derived_truth(kind, g["x"], g["cells"], g["tp"], coef * 2.0**k, M * 2.0**j, *args, inp["loads"] * 2.0**k, inp["labels"])
+        for name, (pk, pj) in R.SCALING_LAWS.items():
+            assert R.rel(T[name] * LD(2.0) ** -(k * pk + j * pj), T0[name]) <= tol, (name, k, j)
+        assert set(R.SCALING_LAWS) >= set(T) - {"C0", "vol", "s_canon", "norm", "region_norm", "load_norm"}
+        assert T["norm"].argmax() == T0["norm"].argmax() and np.array_equal(T["load_norm"].argmax(axis=1), T0["load_norm"].argmax(axis=1))
+        assert np.array_equal(T["region_norm"].argmax(axis=1), T0["region_norm"].argmax(axis=1))
+
+
+def test_stratification_families():
+    for dim in (2, 3):
+        Q = R.stratification_family("rot", dim, 1, 0)[0]
+        assert np.allclose(Q @ Q.T, np.eye(dim), atol=1e-15) and np.isclose(np.linalg.det(Q), 1.0) and not np.allclose(Q, np.eye(dim), atol=0.1)
+        S = R.stratification_family("squeeze16", dim, 2, 0)
+        assert np.allclose(np.linalg.svd(S[0], compute_uv=False), [1.0] * (dim - 1) + [1 / 16]) and np.array_equal(S[0], S[1])
+        H = R.stratification_family("shear30", dim, 1, 0)[0]
+        assert np.array_equal(H, np.eye(dim) + 30.0 * np.outer(np.eye(dim)[0], np.eye(dim)[dim - 1]))
+        assert np.array_equal(R.stratification_family("mild", dim, 2, 5), R.stratification(dim, 2, 5))
+
+
+CAP = 1e-11  # tensors, fields, derivatives: a condition that keeps a bound from becoming vacuous, not a measurement
+CAP_CORRECTORS = 1e-10
+
+
+@pytest.mark.parametrize("case", R.M_CASES, ids=lambda c: R.case_id(c[1:]))
+def test_truth_converges_and_tensor_yardstick_is_capped_on_every_M_family(case):
+    """The cases of test_gpu_accuracy.py's stratification tests: ``truth`` converges (a stall above STALL_LIMIT raises) and the float64
+    yardsticks of A_H stay below the cap, on log2 and the top-contrast family with shear30, squeeze16 and rot."""
+    kind = case[2]
+    for family in ("log2", R.top_family(kind)):
+        for mf in R.M_CONDITIONING:
+            coef, M, g = R.case_inputs(case[1:], family, mf)
+            for c in range(R.NC):
+                e = R.float64_errors(kind, g["x"], g["cells"], g["tp"], coef[c], M[c], **g["kw"])
+                print(f"{R.case_id(case[1:])} {family} {mf} cell {c}: oracle {e['e_oracle']:.1e} cholesky {e['e_cholesky']:.1e} corr {e['e_corr']:.1e}")
+                assert e["e_oracle"] <= CAP and e["e_cholesky"] <= CAP and e["e_corr"] <= CAP_CORRECTORS, (family, mf, c, e)
+
+
+@pytest.mark.parametrize("case", R.DERIVED_CASES, ids=lambda c: R.case_id(R.derived_case(c)[2]))
+def test_derived_yardsticks_are_capped(case):
+    """Every case, family and cell of test_gpu_accuracy_derived.py: the truth converges and no float64 yardstick passes its cap."""
+    _, _, cs = R.derived_case(case)
+    kind = cs[1]
+    inp = R.derived_inputs(cs, R.case_inputs(cs, "log2", None)[0][0])
+    worst = {}
+    for family, mf in R.DERIVED_FAMILIES:
+        coef, M, g = R.case_inputs(cs, family or R.top_family(kind), mf)
+        for c in range(R.NC):
+            e = R.derived_float64_errors(kind, g["x"], g["cells"], g["tp"], coef[c], None if M is None else M[c], **inp, **g["kw"])["e"]
+            for name, v in e.items():
+                worst[name] = max(worst.get(name, 0.0), v)
+                assert v <= (CAP_CORRECTORS if name in R.CORRECTOR_QUANTITIES else CAP), (family, mf, c, name, v)
+    print(R.case_id(cs), {k: f"{v:.1e}" for k, v in worst.items()})

@@ -11,6 +11,10 @@ knobs are read when a plan is created, so the forced routes (staged tree, plane 
 
 Magnitude sweep: one mild case per kernel family with the coefficient scaled by 2^k, k in {-40, -20, 0, 20, 30, 40} (k = 30 .. 37 is an
 elastic modulus in pascals).  The truth scales exactly; the same bound holds at every k and info stays 0.
+
+Stratification: one case per kernel family, the padded fused blocks and both mesh routes (accuracy_ref.M_CASES) with M far from the
+identity (shear 30, a squeeze by 16 under a rotation, a pure rotation) under the same rule, and with M 2^j, coef 2^k, where A_H 2^-k must
+return the numbers of (k, j) = (0, 0) to 16 eps: both normalisations take an exponent from M.
 """
 
 import numpy as np
@@ -165,3 +169,45 @@ def test_magnitude_sweep_correctors_and_loads(results, kind, dim, n):
             d = float(np.abs(got - ref).max() / np.abs(ref).max())
             print(f"sweep loads {key} {name} 2^{k}: {d:.2e}")
             assert d <= tol, (name, k, d)
+
+
+def _m_reference(case, family, mf, c):
+    coef, M, g = R.case_inputs(case, family, mf)
+    return _reference(("M", R.case_id(case), family, mf, c), case[1], g["x"], g["cells"], g["tp"], coef[c], M[c], **g["kw"])
+
+
+@pytest.mark.parametrize("case", R.M_CASES, ids=lambda c: R.case_id(c[1:]))
+def test_stratification_conditioning(results, case):
+    """M far from the identity -- shear 30, a squeeze by 16 under a rotation, a pure rotation -- on log2 and the kind's top-contrast family,
+    one case per kernel family and the padded fused blocks: the rule of every other test here, with the truth and the yardsticks of that
+    very (coef, M).  tests/test_accuracy_ref_host.py holds those yardsticks below 1e-11; accuracy_ref.SOFTENED lists the softened cases."""
+    res, case = results(case[0]), case[1:]
+    cid = R.case_id(case)
+    for family in ("log2", R.top_family(case[1])):
+        for mf in R.M_CONDITIONING:
+            A, info = res[f"MA|{cid}|{family}|{mf}"], res[f"Minfo|{cid}|{family}|{mf}"]
+            for c in range(R.NC):
+                T, e = _m_reference(case, family, mf, c)
+                _check(A[c], info[c], T, e, f"{cid} {family} {mf} cell {c}")
+
+
+@pytest.mark.parametrize("case", R.M_CASES, ids=lambda c: R.case_id(c[1:]))
+def test_stratification_scale(results, case):
+    """log2 with M = (I + 0.3 N) 2^j and coef 2^k: A_H 2^-k is invariant under the scale of M (exactly so in long double:
+    tests/test_accuracy_ref_host.py), so every (k, j) meets the bound of the (0, 0) truth with info 0, and -- a power of two commutes with
+    every rounding -- returns the (0, 0) numbers of the device again, to 16 eps of the largest entry.  This is what pins the exponent that
+    both normalisations take from M (k_poisson2d_fused, k_coef_normalise)."""
+    res, case = results(case[0]), case[1:]
+    cid = R.case_id(case)
+    base = res[f"MsA|{cid}|0|0"]
+    failures = []
+    for c in range(R.NC):
+        T, e = _m_reference(case, "log2", "mild", c)
+        for k, j in R.M_SCALES:
+            A, info = res[f"MsA|{cid}|{k}|{j}"][c] * 2.0**-k, res[f"Msinfo|{cid}|{k}|{j}"][c]
+            err, d = R.rel(A, T[0]), float(np.abs(A - base[c]).max() / np.abs(base[c]).max())
+            print(f"M scale {cid} cell {c} coef 2^{k} M 2^{j}: e = {err:.2e} bound {e['bound']:.1e} ratio {err / (e['bound'] / R.FACTOR):.2f}"
+                  f"  against (0, 0): {d:.2e}  info {info}")
+            if info != 0 or not err <= e["bound"] or not d <= 16 * R.EPS:
+                failures.append((k, j, c, err, d, int(info)))
+    assert not failures, (cid, failures)

@@ -2,11 +2,14 @@
 
 e = max|A_gpu - T| / max|T| against the long-double truth of tests/accuracy_ref.py; yardstick = max(e_oracle_schur, e_cholesky_schur, 16 eps),
 what float64 delivers on the same inputs.  The tests assert ratio <= 32.  Per case the largest ratio over its cells, families and M / no M.
+Likewise the stratification tests (conditioning of M per family; coef 2^k, M 2^j) and, per group of quantities, the derived outputs of
+tests/test_gpu_accuracy_derived.py against their own float64 yardsticks (accuracy_ref.derived_float64_errors).
 
     python tools/accuracy_table.py [--dumps DIR] [--out profiles/accuracy.json]
 
 --dumps DIR: take the raw GPU results from DIR/accuracy_<group>.npz -- the name tests/accuracy_gpu.py's run_in_child gives them; written by
 `python tests/accuracy_gpu.py accuracy <group> DIR/accuracy_<group>.npz` with the group's environment -- instead of running the plans here.
+The derived outputs come from DIR/derived_default.npz (`python tests/accuracy_gpu.py derived default DIR/derived_default.npz`).
 """
 
 import argparse
@@ -22,6 +25,10 @@ import numpy as np  # noqa: E402
 
 import accuracy_gpu as G  # noqa: E402
 import accuracy_ref as R  # noqa: E402
+
+DERIVED_GROUPS = {"tensor": ("A",), "fields": ("strain", "flux"), "statistics": ("mean_strain", "mean_flux", "energy", "max_flux"),
+                  "regions": R.REGION_QUANTITIES, "dA, grad": ("dA", "grad"), "dA_dM, grad_M": ("dA_dM", "grad_M"),
+                  "loads": tuple(q for q in R.LOAD_QUANTITIES if q != "load_chi"), "load correctors": ("load_chi",)}
 
 
 def main():
@@ -109,14 +116,78 @@ def main():
                 r = max(r, R.rel(res[group][f"sweepA|{key}|{k}"][c] * 2.0**-k, T[0]) / yard(e))
             per_k[str(k)] = r
         sweep.append({"group": group, "kernel": kernel, "case": name, "ratio_by_k": per_k})
+    # the stratification on the tensor routes: conditioning (worst ratio per M family over two cells x log2 / top contrast) and scale
+    m_cond, m_scale = [], []
+    for case in R.M_CASES:
+        group, case = case[0], case[1:]
+        cid = R.case_id(case)
+        per_family = {}
+        for mf in R.M_CONDITIONING:
+            worst = (0.0, 0.0, "")
+            for family in ("log2", R.top_family(case[1])):
+                coef, M, g = R.case_inputs(case, family, mf)
+                for c in range(R.NC):
+                    T, e = ref(("M", cid, family, mf, c), case[1], g["x"], g["cells"], g["tp"], coef[c], M[c], **g["kw"])
+                    err = R.rel(res[group][f"MA|{cid}|{family}|{mf}"][c], T[0])
+                    worst = max(worst, (err / yard(e), err, family))
+            per_family[mf] = {"ratio": worst[0], "e": worst[1], "worst": worst[2]}
+        m_cond.append({"group": group, "case": cid, "by_family": per_family})
+        coef, M, g = R.case_inputs(case, "log2", "mild")
+        per_kj = {}
+        for k, j in R.M_SCALES:
+            r = 0.0
+            for c in range(R.NC):
+                T, e = ref(("M", cid, "log2", "mild", c), case[1], g["x"], g["cells"], g["tp"], coef[c], M[c], **g["kw"])
+                r = max(r, R.rel(res[group][f"MsA|{cid}|{k}|{j}"][c] * 2.0**-k, T[0]) / yard(e))
+            per_kj[f"{k},{j}"] = r
+        m_scale.append({"group": group, "case": cid, "ratio_by_kj": per_kj})
+    # derived outputs: worst ratio e / float64 yardstick per case and group of quantities, over two cells x five families
+    if args.dumps:
+        with np.load(os.path.join(args.dumps, "derived_default.npz")) as z:
+            dres = {k: z[k] for k in z.files}
+    else:
+        dres = G.run_derived_group()
+    derived = []
+    for case in R.DERIVED_CASES:
+        _, ckernel, cs = R.derived_case(case)
+        cid = R.case_id(cs)
+        inp = R.derived_inputs(cs, R.case_inputs(cs, "log2", None)[0][0])
+        worst = {name: (0.0, 0.0, "") for name in DERIVED_GROUPS}
+        for fi, (family, mf) in enumerate(R.DERIVED_FAMILIES):
+            coef, M, g = R.case_inputs(cs, family or R.top_family(cs[1]), mf)
+            for c in range(R.NC):
+                a = (cs[1], g["x"], g["cells"], g["tp"], coef[c], None if M is None else M[c])
+                T = R.derived_truth(*a, **inp)
+                y = R.derived_float64_errors(*a, **inp, T=T, **g["kw"])
+                for gname, names in DERIVED_GROUPS.items():
+                    for name in names:
+                        key = f"d|{cid}|{fi}|{name}"
+                        if key in dres:
+                            v = dres[key][c]
+                            err = R.rel(v.T if name == "load_chi" else v, T[name])
+                            worst[gname] = max(worst[gname], (err / (y["bound"][name] / R.FACTOR), err, f"{name} {family or R.top_family(cs[1])} {mf or 'no M'}"))
+        derived.append({"case": cid, "correctors": ckernel, "by_group": {k: {"ratio": v[0], "e": v[1], "worst": v[2]} for k, v in worst.items()}})
     with open(args.out, "w") as f:
-        json.dump({"bound_factor": R.FACTOR, "floor_eps": R.FLOOR_EPS, "cases": rows, "magnitude_sweep": sweep}, f, indent=1)
+        json.dump({"bound_factor": R.FACTOR, "floor_eps": R.FLOOR_EPS, "cases": rows, "magnitude_sweep": sweep, "stratification_conditioning": m_cond,
+                   "stratification_scale": m_scale, "derived": derived}, f, indent=1)
     print("| Route | Case | worst ratio | e | at |\n|---|---|---|---|---|")
     for r in rows:
         print(f"| `{r['kernel']}`{'' if r['group'] == 'default' else ' (' + r['group'] + ')'} | {r['case']} | {r['ratio']:.2f} | {r['e']:.1e} | {r['worst']} |")
     print("\n| Route | Case | " + " | ".join(f"2^{k}" for k in R.SWEEP_K) + " |\n|---|---|" + "---|" * len(R.SWEEP_K))
     for s in sweep:
         print(f"| `{s['kernel']}` | {s['case']} | " + " | ".join(f"{s['ratio_by_k'][str(k)]:.2f}" for k in R.SWEEP_K) + " |")
+
+    print("\nDerived outputs\n| Case | correctors | " + " | ".join(DERIVED_GROUPS) + " | worst at |\n|---|---|" + "---|" * (len(DERIVED_GROUPS) + 1))
+    for d in derived:
+        top = max(d["by_group"].values(), key=lambda v: v["ratio"])
+        print(f"| {d['case']} | `{d['correctors']}` | " + " | ".join(f"{d['by_group'][k]['ratio']:.2f}" for k in DERIVED_GROUPS) + f" | {top['worst']} |")
+    print("\nConditioning of M\n| Case | " + " | ".join(R.M_CONDITIONING) + " |\n|---|" + "---|" * len(R.M_CONDITIONING))
+    for m in m_cond:
+        print(f"| {m['case']}{'' if m['group'] == 'default' else ' (' + m['group'] + ')'} | "
+              + " | ".join(f"{m['by_family'][f]['ratio']:.2f} ({m['by_family'][f]['worst']})" for f in R.M_CONDITIONING) + " |")
+    print("\nScale of M: coef 2^k, M 2^j\n| Case | " + " | ".join(f"({k}, {j})" for k, j in R.M_SCALES) + " |\n|---|" + "---|" * len(R.M_SCALES))
+    for m in m_scale:
+        print(f"| {m['case']} | " + " | ".join(f"{m['ratio_by_kj'][f'{k},{j}']:.2f}" for k, j in R.M_SCALES) + " |")
 
 
 if __name__ == "__main__":
