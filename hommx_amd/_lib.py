@@ -85,6 +85,20 @@ class SensArgs(C.Structure):
     ]
 
 
+class Sens2Args(C.Structure):
+    """hommx_sens2_args: what hommx_second_sensitivity_source[_device] is asked for and where it goes."""
+
+    _fields_ = [
+        ("n_dirs", C.c_int32),
+        ("per_cell", C.c_int32),
+        ("dirs", C.c_void_p),
+        ("d2A", C.c_void_p),
+        ("dA", C.c_void_p),
+        ("A_eff", C.c_void_p),
+        ("info", C.c_void_p),
+    ]
+
+
 class StratSensArgs(C.Structure):
     """hommx_strat_sens_args: what hommx_stratification_sensitivity_source[_device] is asked for and where it goes."""
 
@@ -151,6 +165,8 @@ def _prototypes() -> dict:
         "hommx_reconstruct_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_sensitivity_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SensArgs)]),
         "hommx_sensitivity_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SensArgs), vp]),
+        "hommx_second_sensitivity_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(Sens2Args)]),
+        "hommx_second_sensitivity_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(Sens2Args), vp]),
         "hommx_stratification_sensitivity_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(StratSensArgs)]),
         "hommx_stratification_sensitivity_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(StratSensArgs), vp]),
         "hommx_loads_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(LoadArgs)]),

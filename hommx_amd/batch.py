@@ -141,6 +141,25 @@ class Sensitivities:
 
 
 @dataclass
+class SecondSensitivities:
+    """Second derivatives of A_H of macro cells along coefficient directions (include/hommx_hip.h, hommx_second_sensitivity_source;
+    DESIGN 4.13).
+
+    ``d2A[N, n_dirs, n_dirs, t, t]``: d^2 A_H / d theta_a d theta_b for the perturbation coef + theta_a dir_a + theta_b dir_b of the element
+    stream, exact on the discrete problem, symmetric bitwise in its last two axes and in (a, b); every ``d2A[:, a, a]`` is negative
+    semidefinite.  ``dA[N, n_dirs, t, t]`` or None: the first derivatives along the same directions, the bits ``sensitivities`` returns;
+    ``A_eff[N, t, t]`` and ``info[N]`` as ``solve`` returns them.  ``names`` / ``cells``: what the directions are called and the macro
+    cells (``BaseHMM.tensor_second_derivatives``)."""
+
+    d2A: np.ndarray
+    dA: np.ndarray | None
+    A_eff: np.ndarray
+    info: np.ndarray
+    names: tuple | None = None
+    cells: np.ndarray | None = None
+
+
+@dataclass
 class StratSensitivities:
     """Derivatives of A_H of macro cells with respect to the stratification M = Dtheta^T (include/hommx_hip.h,
     hommx_stratification_sensitivity_source).
@@ -486,6 +505,38 @@ class MicroCellPlan:
         A, info = self._host_call("hommx_sensitivity_source", nc, M, call)
         return Sensitivities(dA, grad, A, info)
 
+    def second_sensitivities(self, coef, M: np.ndarray | None = None, directions=None, per_cell: bool = False,
+                             first: bool = False) -> SecondSensitivities:
+        """Second derivatives of A_H along coefficient directions (hommx_second_sensitivity_source): ``coef`` an array or a ``CoefStream``,
+        M and ``directions`` (shared, or ``per_cell``) as ``sensitivities`` takes them -> ``d2A[N_c, n_dirs, n_dirs, t, t]``, exact on the
+        discrete problem: the derivative of every canonical corrector along a direction is the corrector of a polarisation load, which the
+        plan solves on the route ``load_kernel`` names (not on the frontal mesh route).  ``first``: ``dA[N_c, n_dirs, t, t]`` of the same
+        call as well.  One canonical pass and one load solve per direction; correctors and loads never leave the device; the batch runs in
+        the chunks of ``reconstruct``."""
+        stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
+        nc = self._check_stream(stream)
+        el = (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
+        if directions is None:
+            raise ValueError("directions is required")
+        dirs = np.ascontiguousarray(directions, dtype=np.float64)
+        lead = ((nc,) if per_cell else ())
+        nd = dirs.shape[len(lead)] if dirs.ndim == len(lead) + 1 + len(el) else -1
+        if nd < 0 or dirs.shape != lead + (nd,) + el:
+            raise ValueError(f"directions has shape {dirs.shape}; expected {lead + ('n_dirs',) + el}")
+        if not 1 <= nd <= _lib.SENS_MAX_DIRS:
+            raise ValueError(f"n_dirs must be 1 .. {_lib.SENS_MAX_DIRS}; got {nd}")
+        d2A = np.empty((nc, nd, nd, self.t, self.t), dtype=np.float64)
+        dA = np.empty((nc, nd, self.t, self.t), dtype=np.float64) if first else None
+        src = stream.coef_source()
+        args = _lib.Sens2Args(nd, int(bool(per_cell)), dirs.ctypes.data, d2A.ctypes.data, dA.ctypes.data if first else None)
+
+        def call(Mp, o, i):
+            args.A_eff, args.info = o, i
+            return self._lib.hommx_second_sensitivity_source(self._h, nc, C.byref(src), Mp, C.byref(args))
+
+        A, info = self._host_call("hommx_second_sensitivity_source", nc, M, call)
+        return SecondSensitivities(d2A, dA, A, info)
+
     def stratification_sensitivities(self, coef, M: np.ndarray | None = None, weights=None, full: bool = True) -> StratSensitivities:
         """Derivatives of A_H with respect to the stratification M (hommx_stratification_sensitivity_source): ``coef`` an array or a
         ``CoefStream`` and M as ``reconstruct`` takes them (without M: the derivative at M = I).  ``full`` -> ``dA_dM[N_c, d, d, t, t]``
@@ -627,6 +678,17 @@ class MicroCellPlan:
                              A_ptr or None, info_ptr or None)
         _lib.check(self._lib.hommx_sensitivity_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
                    "hommx_sensitivity_source_device")
+
+    def second_sensitivities_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, n_dirs: int, dirs_ptr: int, d2A_ptr: int,
+                                    per_cell: bool = False, dA_ptr: int | None = None, A_ptr: int | None = None, info_ptr: int | None = None,
+                                    stream: int | None = None):
+        """Device-pointer form of ``second_sensitivities`` (hommx_second_sensitivity_source_device), asynchronous on ``stream``: ``source`` =
+        ``CoefStream.coef_source(upload)`` with device addresses; dirs[n_dirs, n_el, n_comp] or, ``per_cell``, [n_cells, n_dirs, n_el, n_comp]
+        -> d2A[n_cells, n_dirs, n_dirs, t, t]; dA[n_cells, n_dirs, t, t] on request."""
+        args = _lib.Sens2Args(int(n_dirs), int(bool(per_cell)), dirs_ptr or None, d2A_ptr or None, dA_ptr or None, A_ptr or None, info_ptr or None)
+        _lib.check(self._lib.hommx_second_sensitivity_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
+                                                                    stream or None),
+                   "hommx_second_sensitivity_source_device")
 
     def stratification_sensitivities_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, dA_dM_ptr: int | None = None,
                                             weights_ptr: int | None = None, grad_M_ptr: int | None = None, A_ptr: int | None = None,

@@ -108,7 +108,8 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 // B_FACT: the factor records of one chunk of a fused 2D plan's corrector route (kernels.h)
 // B_LOADS: what a load pass leaves where a corrector pass leaves A_eff (hommx_loads_source: C0 - f^T K^+ f, unused)
 // B_REFINE: canonical flux field and correction of the refinement step of a fused 2D plan's correctors (10 n^2 doubles per cell)
-enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, N_BUF };
+// B_SENS2: the polarisation loads of one direction of a second-derivative chunk (t n_el t doubles per cell)
+enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, B_SENS2, N_BUF };
 
 }  // namespace
 
@@ -555,7 +556,7 @@ int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d) {
   desc.dim = d->dim;
   desc.kind = d->kind;
   desc.device = d->device;
-  desc.flags = d->flags;
+  desc.flags = m ? d->flags : d->flags | HOMMX_MESH_FLAG_TREE;  // the descriptor names the route the plan took
   hommx_plan* p = nullptr;
   if ((rc = plan_new(&p, desc, d->n_el)) != 0) {
     hommx::mesh_destroy(m);
@@ -1144,9 +1145,24 @@ int loads_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, con
   return GO;
 }
 
+// The correctors of the loads `lo` of nc cells of a chunk into corr_l[nc][t][ndof] (rows l < n_loads), on the route
+// hommx_plan_load_kernel_name names: fused 2D plans substitute on the records the canonical pass of this chunk has just left in B_FACT
+// (k_fused2d_subst_rhs); every other plan runs a corrector pass of the blocked family on the overridden load rows
+int load_correctors(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_coef, const double* d_M, const hommx::LoadOverride& lo, hipStream_t st,
+                    double* corr_l) {
+  if (fused_loads(p)) {
+    HIP_TRY(hommx::launch_fused2d_subst_rhs(static_cast<const double*>(p->buf[B_FACT].p), lo.P, lo.n_loads, lo.per_cell, d_M, corr_l,
+                                            p->desc.n_micro, nc, st));
+    return HOMMX_OK;
+  }
+  const int t = p->ks.t;
+  if (int rc = grow(p->buf[B_LOADS], sizeof(double) * chunk * t * t)) return rc;
+  if (int rc = hommx::blocked_solve(p->ws, nc, d_coef, d_M, static_cast<double*>(p->buf[B_LOADS].p), nullptr, st, corr_l, &lo)) return route_fail(p, rc);
+  return HOMMX_OK;
+}
+
 // one chunk of at most recon_chunk() cells on the device: the canonical correctors into the plan's scratch and k_polar; for a response
-// the correctors of the loads behind them (fused 2D plans: k_fused2d_subst_rhs on the records the canonical pass of this chunk has just left
-// in B_FACT; else a corrector pass of the blocked family on the overridden load rows) and k_load_stats
+// the correctors of the loads behind them (load_correctors) and k_load_stats
 int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const LoadIO& io, const hommx_load_args& a, hipStream_t st) {
   const bool response = load_response(a), mesh = p->desc.n_micro == 0;
   const int t = p->ks.t;
@@ -1164,15 +1180,7 @@ int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const LoadIO& io, const 
   HIP_TRY(hommx::launch_polar(k, p->desc.dim, p->desc.kind, mesh, nc, st));
   if (!response) return HOMMX_OK;
   double* corr_l = corr + chunk * t * k.ndof;
-  if (fused_loads(p)) {
-    HIP_TRY(hommx::launch_fused2d_subst_rhs(static_cast<const double*>(p->buf[B_FACT].p), io.P, a.n_loads, a.per_cell != 0, io.M, corr_l,
-                                            p->desc.n_micro, nc, st));
-  } else {
-    if (int rc = grow(p->buf[B_LOADS], sizeof(double) * chunk * t * t)) return rc;
-    const hommx::LoadOverride lo{io.P, a.n_loads, a.per_cell != 0};
-    if (int rc = hommx::blocked_solve(p->ws, nc, io.coef, io.M, static_cast<double*>(p->buf[B_LOADS].p), nullptr, st, corr_l, &lo))
-      return route_fail(p, rc);
-  }
+  if (int rc = load_correctors(p, nc, chunk, io.coef, io.M, hommx::LoadOverride{io.P, a.n_loads, a.per_cell != 0}, st, corr_l)) return rc;
   k.corr = corr_l;
   k.energy = io.energy;
   k.stats = io.stats;
@@ -1264,6 +1272,149 @@ int loads_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const
       });
 }
 
+// -- second derivatives (hommx_second_sensitivity_source[_device]) ------------------------------------------------------------------------
+// device pointers of one chunk
+struct Sens2IO {
+  const double *coef, *M, *dirs;
+  double *d2A, *dA, *A_eff;
+  int32_t* info;
+};
+
+// the argument checks of both entry points -- the frontal mesh route among them: the descriptor of a mesh plan names its route --, then
+// the routes the call needs: one that forms correctors, and the blocked workspace of a fused 2D plan whose load solve does not run on
+// its own records (HOMMX_FUSED_LOADS=0 / HOMMX_FUSED_CORR=0), as loads_open
+int sens2_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_sens2_args* a, bool device) {
+  auto more = [&] {
+    if (int rc = coef_check(p, src)) return rc;
+    if (!a) return fail(HOMMX_EINVAL, "null arguments");
+    if (a->n_dirs < 1 || a->n_dirs > HOMMX_SENS_MAX_DIRS)
+      return fail(HOMMX_EINVAL, "n_dirs must be 1 .. %d, got %d", HOMMX_SENS_MAX_DIRS, a->n_dirs);
+    if (!a->dirs || !a->d2A) return fail(HOMMX_EINVAL, "null dirs / d2A");
+    if (p->desc.n_micro == 0 && !(p->desc.flags & HOMMX_MESH_FLAG_TREE))
+      return fail(HOMMX_EINVAL, "the frontal mesh route (mesh_front) solves for the canonical loads only: second derivatives need the load "
+                                "solve of a plan of the tree route (HOMMX_MESH_FLAG_TREE, route=\"tree\")");
+    return HOMMX_OK;
+  };
+  if (int rc = open_call(p, n_cells, true, "", device, more); rc != GO) return rc;
+  if (int rc = corrector_workspace(p)) return rc;
+  if (!p->ws && !fused_loads(p)) {
+    int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
+    if (rc) return prefix_error(rc, "blocked path: ");
+  }
+  return GO;
+}
+
+// bytes per cell of a chunk beside the canonical correctors: the second corrector block and the loads of one direction
+size_t sens2_extra(const hommx_plan* p) { return sizeof(double) * p->ks.t * (plan_ndof(p) + p->n_el * p->ks.t); }
+
+// one chunk of at most recon_chunk() cells on the device: the canonical correctors into the plan's scratch, k_sens for the first
+// derivatives; then per direction b its loads (k_sens2_loads), their correctors behind the canonical ones (load_correctors), and k_sens2 for the blocks (a, b) and (b, a), a <= b
+int sens2_run(hommx_plan* p, int64_t nc, int64_t chunk, const Sens2IO& io, const hommx_sens2_args& a, hipStream_t st) {
+  const bool mesh = p->desc.n_micro == 0;
+  const int t = p->ks.t;
+  double *d_A_eff = io.A_eff, *corr = nullptr;
+  if (int rc = chunk_correctors(p, nc, chunk, io.coef, io.M, &d_A_eff, io.info, t, st, &corr)) return rc;
+  if (io.dA) {
+    hommx::SensArgs s;
+    set_geometry(p, s);
+    s.corr = corr;
+    s.M = io.M;
+    s.n_dirs = a.n_dirs;
+    s.per_cell = a.per_cell != 0;
+    s.dirs = io.dirs;
+    s.dA = io.dA;
+    HIP_TRY(hommx::launch_sensitivity(s, p->desc.dim, p->desc.kind, mesh, nc, st));
+  }
+  if (int rc = grow(p->buf[B_SENS2], sizeof(double) * chunk * t * p->n_el * t)) return rc;
+  hommx::Sens2Args k;
+  set_geometry(p, k);
+  double* corr_b = corr + chunk * t * k.ndof;
+  k.corr = corr;
+  k.corr_b = corr_b;
+  k.M = io.M;
+  k.n_dirs = a.n_dirs;
+  k.per_cell = a.per_cell != 0;
+  k.dirs = io.dirs;
+  k.P = static_cast<double*>(p->buf[B_SENS2].p);
+  k.d2A = io.d2A;
+  for (int b = 0; b < a.n_dirs; ++b) {
+    k.b = b;
+    HIP_TRY(hommx::launch_sens2_loads(k, p->desc.dim, p->desc.kind, mesh, nc, st));
+    if (int rc = load_correctors(p, nc, chunk, io.coef, io.M, hommx::LoadOverride{k.P, t, true}, st, corr_b)) return rc;  // t per-cell loads
+    HIP_TRY(hommx::launch_sens2(k, p->desc.dim, p->desc.kind, mesh, nc, st));
+  }
+  return HOMMX_OK;
+}
+
+// everything on the device already: the chunks are views of the caller's arrays
+int sens2_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, const hommx_sens2_args& a, hipStream_t st) {
+  const int d = p->desc.dim, tt = p->ks.t * p->ks.t;
+  const int64_t per = p->n_el * p->ks.n_comp;
+  int64_t chunk = 0;
+  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, sens2_extra(p)), &chunk)) return rc;
+  return source_chunks<Sens2IO>(
+      p, n_cells, chunk, s, st,
+      [&](int64_t c0, int64_t, Sens2IO& io) {
+        io = Sens2IO{nullptr,
+                     d_M ? d_M + c0 * d * d : nullptr,
+                     a.per_cell ? a.dirs + c0 * a.n_dirs * per : a.dirs,
+                     a.d2A + c0 * a.n_dirs * a.n_dirs * tt,
+                     a.dA ? a.dA + c0 * a.n_dirs * tt : nullptr,
+                     a.A_eff ? a.A_eff + c0 * tt : nullptr,
+                     a.info ? a.info + c0 : nullptr};
+        return HOMMX_OK;
+      },
+      [&](int64_t nc, const Sens2IO& io) { return sens2_run(p, nc, chunk, io, a, st); },
+      [](int64_t, int64_t, const Sens2IO&) { return HOMMX_OK; });
+}
+
+// host pointers.  What every cell shares (mask, table, weights of the sampler, shared directions) and the per-cell values of a sampler
+// form travel once, in the plan's pinned block (stage_source); a sampled stream, M and per-cell directions stream in and every output
+// streams out chunk by chunk, so device memory is bounded by the chunk
+int sens2_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_sens2_args& a) {
+  const int d = p->desc.dim, tt = p->ks.t * p->ks.t;
+  const int64_t el = p->n_el * p->ks.n_comp, per = s.form == HOMMX_COEF_SAMPLED ? el : 0;
+  const bool per_cell = a.per_cell != 0;
+  hommx_coef_source ds;
+  const double* d_shared = nullptr;
+  const hommx::HostPiece shared{per_cell ? nullptr : a.dirs, sizeof(double) * a.n_dirs * el, (const void**)&d_shared};
+  if (int rc = stage_source(p, n_cells, s, shared, &ds)) return rc;
+  // doubles per cell of the plan's blocks: in = [coef | M | dirs], out = [d2A | A_eff | dA], and info
+  const int64_t n_in[] = {per, M ? d * d : 0, per_cell ? a.n_dirs * el : 0}, n_out[] = {(int64_t)a.n_dirs * a.n_dirs * tt, tt, a.dA ? a.n_dirs * tt : 0};
+  size_t cell = sizeof(int32_t) + sens2_extra(p);
+  for (int64_t k : n_in) cell += sizeof(double) * k;
+  for (int64_t k : n_out) cell += sizeof(double) * k;
+  int64_t chunk = 0;
+  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, cell), &chunk)) return rc;
+  size_t in_bytes[3], out_bytes[4];
+  for (int k = 0; k < 3; ++k) in_bytes[k] = sizeof(double) * chunk * n_in[k];
+  for (int k = 0; k < 3; ++k) out_bytes[k] = sizeof(double) * chunk * n_out[k];
+  out_bytes[3] = sizeof(int32_t) * chunk;
+  char *in[3], *out[4];
+  if (int rc = carve(p->buf[B_IN], in_bytes, in)) return rc;
+  if (int rc = carve(p->buf[B_OUT], out_bytes, out)) return rc;
+  auto f64 = [](char* at) { return reinterpret_cast<double*>(at); };
+  const Sens2IO dev{f64(in[0]), f64(in[1]), per_cell ? f64(in[2]) : d_shared, f64(out[0]), f64(out[2]), f64(out[1]), reinterpret_cast<int32_t*>(out[3])};
+  const double* src_in[] = {s.coef, M, a.dirs};
+  return source_chunks<Sens2IO>(
+      p, n_cells, chunk, ds, nullptr,
+      [&](int64_t c0, int64_t nc, Sens2IO& io) {
+        for (int k = 0; k < 3; ++k)
+          if (n_in[k]) HIP_TRY(hipMemcpy(in[k], src_in[k] + c0 * n_in[k], sizeof(double) * nc * n_in[k], hipMemcpyHostToDevice));
+        io = dev;
+        return HOMMX_OK;
+      },
+      [&](int64_t nc, const Sens2IO& io) { return sens2_run(p, nc, chunk, io, a, nullptr); },
+      [&](int64_t c0, int64_t nc, const Sens2IO& io) {
+        double* dst_out[] = {a.d2A, a.A_eff, a.dA};
+        for (int k = 0; k < 3; ++k)
+          if (n_out[k] && dst_out[k])
+            HIP_TRY(hipMemcpy(dst_out[k] + c0 * n_out[k], out[k], sizeof(double) * nc * n_out[k], hipMemcpyDeviceToHost));
+        if (a.info) HIP_TRY(hipMemcpy(a.info + c0, io.info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
+        return HOMMX_OK;
+      });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1337,6 +1488,17 @@ int hommx_loads_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_s
 int hommx_loads_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_load_args* args) {
   if (int rc = loads_open(p, n_cells, src, args, false); rc != GO) return rc;
   return loads_host(p, n_cells, source_of_form(*src), M, *args);
+}
+
+int hommx_second_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                           const hommx_sens2_args* args, void* stream) {
+  if (int rc = sens2_open(p, n_cells, src, args, true); rc != GO) return rc;
+  return sens2_device(p, n_cells, source_of_form(*src), d_M, *args, reinterpret_cast<hipStream_t>(stream));
+}
+
+int hommx_second_sensitivity_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_sens2_args* args) {
+  if (int rc = sens2_open(p, n_cells, src, args, false); rc != GO) return rc;
+  return sens2_host(p, n_cells, source_of_form(*src), M, *args);
 }
 
 int hommx_calibrate_fp64(int device, double* mfma_flops_per_s, double* fma_flops_per_s) {

@@ -154,6 +154,30 @@ struct SensArgs {
 };
 hipError_t launch_sensitivity(const SensArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
 
+// sens2.hip: second derivatives of A_H along coefficient directions (include/hommx_hip.h, hommx_second_sensitivity_source; DESIGN.md
+// section 4.13), one direction b per launch.  The geometry fields are those of ReconArgs.  launch_sens2_loads: the polarisation loads
+// P^{b,m} = material(dir_b) s^m from the canonical correctors; launch_sens2: d2A[a][b] and d2A[b][a], a <= b, from the canonical
+// correctors and the correctors of those loads
+struct Sens2Args {
+  int n = 0;
+  double vol_struct = 0.0;
+  long long ndof = 0, n_el = 0;
+  const int32_t* el_nodes = nullptr;
+  const double* grads = nullptr;
+  const double* vol = nullptr;
+  const double* corr = nullptr;      // [nc][t][ndof]: the canonical correctors
+  const double* corr_b = nullptr;    // [nc][t][ndof]: the correctors of the loads of direction b (k_sens2)
+  const double* M = nullptr;         // [nc][d][d] or null
+  int n_dirs = 0;                    // 1 .. HOMMX_SENS_MAX_DIRS
+  int b = 0;                         // the direction of this launch
+  bool per_cell = false;             // dirs[nc][n_dirs][n_el][n_comp] instead of dirs[n_dirs][n_el][n_comp]
+  const double* dirs = nullptr;
+  double* P = nullptr;               // [nc][t][n_el][t]: written by k_sens2_loads, a per-cell load block of loads.hip
+  double* d2A = nullptr;             // [nc][n_dirs][n_dirs][t][t] (k_sens2)
+};
+hipError_t launch_sens2_loads(const Sens2Args& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
+hipError_t launch_sens2(const Sens2Args& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
+
 // sens_strat.hip: derivatives of A_H with respect to the stratification M and their product with caller weights, from the correctors
 // of `nc` cells (include/hommx_hip.h, hommx_stratification_sensitivity_source).  The geometry fields are those of ReconArgs
 struct StratSensArgs {

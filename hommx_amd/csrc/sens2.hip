@@ -1,0 +1,175 @@
+// sens2.hip -- second derivatives of the effective tensor along coefficient directions.
+//
+// With s^m_K = e_m + eps(chi^m)_K the canonical strains (sensitivity.hip) and the element operator linear in the coefficient, the
+// derivative of the canonical corrector m along a perturbation dir_b of the element stream is the corrector of a polarisation load:
+//   load        P^{b,m}_K = material(dir_b[K]) s^m_K                         k_sens2_loads: into plan scratch, as a per-cell load block
+//   corrector   K chi^m_b = -f(P^{b,m})                                      the load solve of loads.hip / fused2d_rhs.hip, between the two
+//   g_ab[m][n]  = sum_K |K| eps(chi^m_b)_K . material(dir_a[K]) s^n_K        k_sens2: for every a <= b
+//   d2A[a][b]   = g_ab + g_ab^T = d2A[b][a]                                  formed once and mirrored: symmetric bitwise in (m, n) and (a, b)
+// There is no second derivative of the operator.  P is in flux / stress components (shear not doubled), the strains have the shear
+// doubled: the conventions of loads.hip.
+//
+// Both kernels: one workgroup per macro cell, elements on lanes, correctors gathered from global memory (elem_walk.h).  k_sens2_loads has
+// no reduction; every element writes its t loads.  k_sens2 takes one pass over the elements per a <= b: the t x t canonical strains stay
+// in registers, the strain of one load corrector at a time is gathered in a rolled loop and its row of the t x t sums picked by selects
+// (k_polar's device), so that 3D elasticity (t = 6) fits the registers.  Sums: element-strided partial sums per
+// thread, a butterfly in each wave, the wave totals in order -- a cell's outputs do not depend on its batch position or the chunking.
+// No atomics, no inline assembly.
+#include <hip/hip_runtime.h>
+
+#include "elem_walk.h"
+#include "kernels.h"
+
+namespace hommx {
+
+namespace {
+
+constexpr int kThreads = kWalkThreads;
+constexpr int kWaves = kWalkWaves;
+
+// M of the cell, or the identity (exact: the same gradients as without M), as k_recon holds it
+template <int DIM>
+__device__ __forceinline__ void cell_M(const double* M, long long cell, double (&Mp)[DIM * DIM]) {
+#pragma unroll
+  for (int k = 0; k < DIM * DIM; ++k) Mp[k] = M ? M[cell * DIM * DIM + k] : (k % (DIM + 1) == 0 ? 1.0 : 0.0);
+}
+
+// P[cell][m][K] = material(dir_b[K]) s^m_K for the t canonical loads: a per-cell load block of hommx_loads_source.  Lane K writes the t
+// components of its element next to those of lane K + 1
+template <int DIM, int KIND, bool MESH>
+__global__ __launch_bounds__(kThreads) void k_sens2_loads(Sens2Args A) {
+  constexpr KindSizes ks = kind_sizes(DIM, KIND);
+  constexpr int T = ks.t, NCOMP = ks.n_comp;
+  const int tid = threadIdx.x;
+  const long long cell = blockIdx.x;
+  const double* corr = A.corr + cell * T * A.ndof;
+  const double* dir = A.dirs + ((A.per_cell ? cell * A.n_dirs : 0) + A.b) * A.n_el * NCOMP;
+  double* P = A.P + cell * T * A.n_el * T;
+  double Mp[DIM * DIM];
+  cell_M<DIM>(A.M, cell, Mp);
+  for_elements<DIM, MESH>(A, tid, [&](long long el, double, auto vertex) {
+    double s[T][T], C[T][T];
+    load_strains<DIM, KIND>(corr, A.ndof, vertex, Mp, s);
+    material<DIM, KIND>(dir + el * NCOMP, C);
+#pragma unroll
+    for (int m = 0; m < T; ++m) {
+      double* __restrict__ pk = P + ((long long)m * A.n_el + el) * T;
+#pragma unroll
+      for (int k = 0; k < T; ++k) {
+        double v = 0.0;
+#pragma unroll
+        for (int l = 0; l < T; ++l) v += C[k][l] * s[m][l];
+        pk[k] = v;
+      }
+    }
+  });
+}
+
+// d2A[cell][a][b] and its mirror d2A[cell][b][a] for every a <= b = A.b, from the canonical correctors and the load correctors of dir_b
+template <int DIM, int KIND, bool MESH>
+__global__ __launch_bounds__(kThreads) void k_sens2(Sens2Args A) {
+  constexpr KindSizes ks = kind_sizes(DIM, KIND);
+  constexpr int T = ks.t, NCOMP = ks.n_comp, NSUM = T * T;
+  __shared__ double red[kWaves][NSUM];
+  __shared__ double g[T * T];  // g_ab[m][n], the totals
+  const int tid = threadIdx.x;
+  const long long cell = blockIdx.x;
+  const double* corr = A.corr + cell * T * A.ndof;
+  const double* corr_b = A.corr_b + cell * T * A.ndof;
+  const int b = A.b, nd = A.n_dirs;
+  double Mp[DIM * DIM];
+  cell_M<DIM>(A.M, cell, Mp);
+
+  for (int a = 0; a <= b; ++a) {
+    const double* dir = A.dirs + ((A.per_cell ? cell * nd : 0) + a) * A.n_el * NCOMP;
+    double acc[NSUM];  // g_ab[m][n], this thread's elements
+#pragma unroll
+    for (int q = 0; q < NSUM; ++q) acc[q] = 0.0;
+    for_elements<DIM, MESH>(A, tid, [&](long long el, double vol, auto vertex) {
+      double s[T][T], C[T][T];
+      load_strains<DIM, KIND>(corr, A.ndof, vertex, Mp, s);
+      material<DIM, KIND>(dir + el * NCOMP, C);
+      // one load corrector at a time (a rolled loop: the 36 strains of six of them beside the 36 canonical strains, the operator and
+      // the 36 sums of 3D elasticity do not fit the registers); row m of the sums is picked by selects over the unrolled rows
+#pragma unroll 1
+      for (int m = 0; m < T; ++m) {
+        double eb[T][T], ce[T];  // row 0: eps(chi^m_b)_K; material(dir_a[K]) eps(chi^m_b)_K (the operator is symmetric)
+        load_strains<DIM, KIND, false>(corr_b + (long long)m * A.ndof, A.ndof, vertex, Mp, eb, 1);
+#pragma unroll
+        for (int k = 0; k < T; ++k) {
+          double v = 0.0;
+#pragma unroll
+          for (int l = 0; l < T; ++l) v += C[k][l] * eb[0][l];
+          ce[k] = v;
+        }
+#pragma unroll
+        for (int n = 0; n < T; ++n) {
+          double v = 0.0;
+#pragma unroll
+          for (int k = 0; k < T; ++k) v += ce[k] * s[n][k];
+          v *= vol;
+#pragma unroll
+          for (int q = 0; q < T; ++q) acc[q * T + n] = q == m ? acc[q * T + n] + v : acc[q * T + n];
+        }
+      }
+    });
+    // fixed-order reduction: wave butterfly, then thread q adds the wave totals of sum q in order
+#pragma unroll
+    for (int q = 0; q < NSUM; ++q)
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
+    if ((tid & 63) == 0) {
+#pragma unroll
+      for (int q = 0; q < NSUM; ++q) red[tid >> 6][q] = acc[q];
+    }
+    __syncthreads();
+    if (tid < NSUM) {
+      double v = red[0][tid];
+      for (int w = 1; w < kWaves; ++w) v += red[w][tid];
+      g[tid] = v;
+    }
+    __syncthreads();
+    // g + g^T once per pair m <= n, stored at its four places
+    if (tid < T * T) {
+      const int m = tid / T, n = tid % T;
+      if (m <= n) {
+        const double v = g[m * T + n] + g[n * T + m];
+        double* ab = A.d2A + ((cell * nd + a) * nd + b) * T * T;
+        double* ba = A.d2A + ((cell * nd + b) * nd + a) * T * T;
+        ab[m * T + n] = ab[n * T + m] = v;
+        ba[m * T + n] = ba[n * T + m] = v;
+      }
+    }
+    __syncthreads();  // the next direction writes red and g again
+  }
+}
+
+template <int DIM, int KIND, bool MESH>
+hipError_t launch_loads_one(const Sens2Args& a, long long nc, hipStream_t st) {
+  hipLaunchKernelGGL((k_sens2_loads<DIM, KIND, MESH>), dim3((unsigned)nc), dim3(kThreads), 0, st, a);
+  return hipGetLastError();
+}
+
+template <int DIM, int KIND, bool MESH>
+hipError_t launch_one(const Sens2Args& a, long long nc, hipStream_t st) {
+  hipLaunchKernelGGL((k_sens2<DIM, KIND, MESH>), dim3((unsigned)nc), dim3(kThreads), 0, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_sens2_loads(const Sens2Args& a, int dim, int kind, bool mesh, long long nc, hipStream_t st) {
+  if (nc <= 0) return hipSuccess;
+  return dispatch_dim_kind(dim, kind, [&](auto D, auto K) {
+    return mesh ? launch_loads_one<D(), K(), true>(a, nc, st) : launch_loads_one<D(), K(), false>(a, nc, st);
+  });
+}
+
+hipError_t launch_sens2(const Sens2Args& a, int dim, int kind, bool mesh, long long nc, hipStream_t st) {
+  if (nc <= 0) return hipSuccess;
+  return dispatch_dim_kind(dim, kind, [&](auto D, auto K) {
+    return mesh ? launch_one<D(), K(), true>(a, nc, st) : launch_one<D(), K(), false>(a, nc, st);
+  });
+}
+
+}  // namespace hommx

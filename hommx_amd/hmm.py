@@ -28,7 +28,8 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import fem
-from .batch import REGION_FIELDS, CoefStream, LoadResponse, MicroCellPlan, Reconstruction, Sensitivities, StratSensitivities, region_labels
+from .batch import (REGION_FIELDS, CoefStream, LoadResponse, MicroCellPlan, Reconstruction, SecondSensitivities, Sensitivities,
+                    StratSensitivities, region_labels)
 from .mesh import Mesh, micro_cells_per_side
 
 _VOIGT = {2: [(0, 0), (1, 1), (0, 1)], 3: [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]}
@@ -919,9 +920,17 @@ class BaseHMM(ABC):
         The coefficient crosses the boundary as ``solve()`` sends it (``_coef_stream``).  The cells run in chunks of ``chunk_cells``
         (default: about 256 MB of coefficient and direction streams).  Under a process group this runs on the calling rank alone:
         there is no collective."""
+        names, cells, parts = self._direction_blocks("tensor_derivatives", cells, directions, chunk_cells,
+                                                     lambda plan, coef, M, **kw: plan.sensitivities(coef, M, **kw))
+        cat = lambda name: np.concatenate([getattr(r, name) for r in parts])
+        return Sensitivities(cat("dA"), None, cat("A_eff"), cat("info"), names, cells)
+
+    def _direction_blocks(self, what: str, cells, directions, chunk_cells: int | None, call) -> tuple[tuple, np.ndarray, list]:
+        """(names, cells, results) of ``call(plan, coef, M, directions=..., per_cell=...)`` over ``cells`` (default: this rank's macro
+        cells) in chunks of ``chunk_cells``: the cells, names and directions of ``tensor_derivatives`` and ``tensor_second_derivatives``."""
         cells = self._local_cells() if cells is None else np.asarray(cells, dtype=np.int64).ravel()
         if len(cells) == 0:
-            raise ValueError("tensor_derivatives() needs at least one macro cell")
+            raise ValueError(f"{what}() needs at least one macro cell")
         if directions is None:
             names, shared = self._parameter_directions()
         else:
@@ -942,9 +951,8 @@ class BaseHMM(ABC):
                 if any(k != kind for _, k in sampled):
                     raise ValueError(f"every direction must have the coefficient's shape (plan kind {kind!r}); got {[k for _, k in sampled]}")
                 dirs = np.stack([d for d, _ in sampled], axis=1)
-            parts.append(self._ensure_plan(kind).sensitivities(coef, self._stratification(sub), directions=dirs, per_cell=shared is None))
-        cat = lambda name: np.concatenate([getattr(r, name) for r in parts])
-        return Sensitivities(cat("dA"), None, cat("A_eff"), cat("info"), names, cells)
+            parts.append(call(self._ensure_plan(kind), coef, self._stratification(sub), directions=dirs, per_cell=shared is None))
+        return names, cells, parts
 
     def energy_derivatives(self, u=None, v=None, **kw) -> np.ndarray:
         """[N, n_dirs]: vol(T)/vol(Y) xi_v(T) . dA_H[d](T) xi_u(T) for the cells and directions of ``tensor_derivatives(**kw)``, with xi the
@@ -955,17 +963,49 @@ class BaseHMM(ABC):
                 raise RuntimeError("energy_derivatives() needs a macro solution: call solve() first or pass u")
             u = self._u
         td = self.tensor_derivatives(**kw)
+        xv, xu, vol = self._energy_weights(td.cells, u, v)
+        return vol[:, None] * np.einsum("cm,cdmn,cn->cd", xv, td.dA, xu)
+
+    def _energy_weights(self, cells: np.ndarray, u, v) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(xi_v[N, t], xi_u[N, t], vol(T)/vol(Y)[N]) of ``cells``: the macro gradient / Voigt strain of the macro fields (``v`` None: u)."""
 
         def xi(f):
             x = np.asarray(f.x.array if hasattr(f, "x") else f, dtype=float)
             if x.shape != (self._num_global_dofs,):
                 raise ValueError(f"the macro field has {x.size} dofs; the macro space has {self._num_global_dofs}")
-            return self._macro_strains(td.cells, x)
+            return self._macro_strains(cells, x)
 
         xu = xi(u)
-        xv = xu if v is None else xi(v)
-        vol = self._msh.cell_volumes()[td.cells] / self._cell_mesh_area
-        return vol[:, None] * np.einsum("cm,cdmn,cn->cd", xv, td.dA, xu)
+        return (xu if v is None else xi(v)), xu, self._msh.cell_volumes()[cells] / self._cell_mesh_area
+
+    def tensor_second_derivatives(self, cells=None, directions=None, chunk_cells: int | None = None) -> SecondSensitivities:
+        """Second derivatives of A_H / C_H of ``cells`` (default: this rank's macro cells) with respect to the micro coefficient
+        (hommx_second_sensitivity_source) -> ``SecondSensitivities`` with ``names``, ``d2A[N, n_dirs, n_dirs, t, t]``, the
+        first derivatives ``dA[N, n_dirs, t, t]`` of the same call, ``A_eff``, ``info`` and ``cells``.
+
+        Names and directions are those of ``tensor_derivatives``: without ``directions`` the parameters of a ``TwoPhase`` or an affine
+        ``Separable`` coefficient (any other coefficient raises ``ValueError``), else up to 8 callables (x, y) of the coefficient's shape.
+        d2A[:, a, b] is exact on the discrete problem -- the Hessian of A_H a Newton or Gauss-Newton step needs, with no step size to
+        tune -- and costs one load solve per direction.  Not on a micro mesh of the frontal mesh route (the load solve needs the tree
+        route).  The cells run in chunks of ``chunk_cells``.  Under a process group this runs on the calling rank alone: there is no
+        collective."""
+        names, cells, parts = self._direction_blocks("tensor_second_derivatives", cells, directions, chunk_cells,
+                                                     lambda plan, coef, M, **kw: plan.second_sensitivities(coef, M, first=True, **kw))
+        cat = lambda name: np.concatenate([getattr(r, name) for r in parts])
+        return SecondSensitivities(cat("d2A"), cat("dA"), cat("A_eff"), cat("info"), names, cells)
+
+    def energy_second_derivatives(self, u=None, v=None, **kw) -> np.ndarray:
+        """[N, n_dirs, n_dirs]: vol(T)/vol(Y) xi_v(T) . d2A_H[a][b](T) xi_u(T) for the cells and directions of
+        ``tensor_second_derivatives(**kw)`` -- the contribution of macro cell T to the second derivative of v . K_H u at FROZEN u, v
+        (``u`` defaults to the last ``solve()`` result, ``v`` to u).  The response of u itself to the parameters (the du/dtheta terms of a
+        compliance or misfit Hessian) is the caller's macro solve: it needs ``energy_derivatives`` and K_H, not the cell problems."""
+        if u is None:
+            if not self._solved:
+                raise RuntimeError("energy_second_derivatives() needs a macro solution: call solve() first or pass u")
+            u = self._u
+        td = self.tensor_second_derivatives(**kw)
+        xv, xu, vol = self._energy_weights(td.cells, u, v)
+        return vol[:, None, None] * np.einsum("cm,cabmn,cn->cab", xv, td.d2A, xu)
 
     def _stratification_parameters(self, cells: np.ndarray, parameters) -> tuple[tuple, np.ndarray]:
         """(names, dM[N, n_params, d, d]) of the design parameters of the stratification: every entry of ``parameters`` is a callable

@@ -428,6 +428,48 @@ int hommx_loads_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coe
                               const hommx_load_args* args, void* stream);
 
 /*
+ * Second derivatives of A_H along coefficient directions, exact on the discrete problem.  With s^m_K,
+ * material() and the directions of hommx_sensitivity_source, and eps(z)_K the strain of a periodic field z as in hommx_loads_source: the
+ * derivative of the canonical corrector m along dir_b is the corrector of a polarisation load,
+ *   K chi^m_b = -f(P^{b,m}),  P^{b,m}_K = material(dir_b[K]) s^m_K                        (the load convention of hommx_loads_source)
+ *   g_ab[m][n] = sum_K |K| eps(chi^m_b)_K . material(dir_a[K]) s^n_K
+ *   d2A[c][a][b][m][n] = g_ab[m][n] + g_ab[n][m] = d^2 A_H[m][n] / d theta_a d theta_b     (coef + theta_a dir_a + theta_b dir_b)
+ * -- the element operator is linear in the stream, so no second derivative of it appears.  d2A is symmetric in (m, n) and in (a, b),
+ * both bitwise (every block is formed once and mirrored); d2A[a][a] is negative semidefinite (A_H is concave in the coefficient); A_H
+ * being 1-homogeneous, every block with the cell's own coefficient as one of its directions vanishes up to rounding (Euler).  The call
+ * costs one canonical corrector pass and one load solve per direction (hommx_plan_load_kernel_name names its route: a fused 2D plan
+ * substitutes on the factor records the canonical pass has just left, every other plan runs one more corrector pass of the blocked
+ * family) against the 2 n_dirs + 1 eliminations of central differences of hommx_sensitivity_source.
+ *
+ *   n_dirs      1 .. HOMMX_SENS_MAX_DIRS
+ *   per_cell    0: dirs[n_dirs][n_el][n_comp], shared by all cells; 1: dirs[n_cells][n_dirs][n_el][n_comp]
+ *   d2A         [n_cells][n_dirs][n_dirs][t][t], required
+ *   dA          [n_cells][n_dirs][t][t] or NULL: the first derivatives along the same directions, the bits hommx_sensitivity_source returns
+ *   A_eff, info as hommx_solve_batch, or NULL
+ * src, M: as hommx_reconstruct_source.  HOMMX_EINVAL, before the plan's device is made current: a null plan, source or argument struct,
+ * n_dirs out of range, a null dirs or d2A, and a plan of the frontal mesh route ("mesh_front" has no load solve: create the plan with
+ * HOMMX_MESH_FLAG_TREE, the tree route).  Every other plan is accepted.  Per cell of a chunk (HOMMX_RECON_MEM_MB, the chunk rule of the
+ * reconstruction) plan-owned scratch holds two blocks of t correctors and the t loads of one direction (t n_el t doubles).  A cell's
+ * outputs do not depend on its batch position, the chunking or which optional outputs are requested (fixed-order reductions).  A cell
+ * whose elimination flags a pivot keeps its info; its outputs may hold anything, no other cell's change.  The host entry sends shared
+ * directions with the source's shared arrays once; per-cell directions, a sampled stream and M go in, and every output comes back,
+ * chunk by chunk.
+ */
+typedef struct hommx_sens2_args {
+  int32_t n_dirs;
+  int32_t per_cell;
+  const double* dirs;
+  double* d2A;
+  double* dA;
+  double* A_eff;
+  int32_t* info;
+} hommx_sens2_args;
+int hommx_second_sensitivity_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_sens2_args* args);
+/* Same with DEVICE pointers (in *src and *args as well; the structs themselves are host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
+int hommx_second_sensitivity_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                           const hommx_sens2_args* args, void* stream);
+
+/*
  * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
  * periodic: the caller folds the mesh vertices into n_nodes independent (periodic) nodes -- cell_problem.py:38-300's slave -> master
  * map -- and passes, per element, the periodic node of every vertex and the UNFOLDED vertex coordinates (gradients and volumes).
