@@ -1,6 +1,6 @@
 """GPU side of the accuracy and pivot-contract tests: runs the case groups of tests/accuracy_ref.py through the plans and returns raw
 results.  Nothing here computes a bound.  Environment knobs are read when a plan is created, so the forced groups run this module as a
-child process:  python accuracy_gpu.py <accuracy|pivot|derived> <group> <out.npz>  (the derived outputs have the default group only)."""
+child process:  python accuracy_gpu.py <accuracy|pivot|derived> <group> <out.npz>  (the derived outputs: the default group, and blocked_loads for the second load route of the fused plans)."""
 
 from __future__ import annotations
 
@@ -146,22 +146,35 @@ def _derived_calls(p, coef, M, inp, with_response: bool) -> dict:
            "region_argmax": r.region_argmax_element, "dA": s.dA, "grad": s.grad, "dA_dM": m.dA_dM, "grad_M": m.grad_M}
     info = np.maximum(np.maximum(r.info, s.info), m.info)
     if with_response:
-        l = p.loads(coef, inp["loads"], M, response=True, fields=True, return_correctors=True)
-        out.update(load_chi=l.correctors, P_eff=l.P_eff, load_mean_flux=l.mean_flux, load_energy=l.energy, load_strain=l.strain,
-                   load_flux=l.flux, load_max_flux=l.max_flux, load_argmax=l.argmax_element)
-    else:  # the frontal mesh route solves no load problem: P_eff by Levin's identity alone
+        out.update(_load_calls(p, coef, M, inp, s.dA))
+    else:  # the frontal mesh route solves no load problem: P_eff by Levin's identity alone, and no second derivatives
         l = p.loads(coef, inp["loads"], M)
-        out["P_eff"] = l.P_eff
-    out["info"] = np.maximum(info, l.info)
+        out.update(P_eff=l.P_eff, info=l.info)
+    out["info"] = np.maximum(info, out["info"])
     return out
+
+
+def _load_calls(p, coef, M, inp, dA=None) -> dict:
+    """The two calls that solve load problems, loads and second_sensitivities, on a plan with a load solve; ``info`` the larger of the two.
+    The first derivatives of second_sensitivities are the bits of ``dA`` (those of sensitivities() on the same inputs)."""
+    l = p.loads(coef, inp["loads"], M, response=True, fields=True, return_correctors=True)
+    s2 = p.second_sensitivities(coef, M, directions=inp["directions"], first=True)
+    assert np.array_equal(s2.dA, p.sensitivities(coef, M, directions=inp["directions"]).dA if dA is None else dA)
+    return dict(load_chi=l.correctors, P_eff=l.P_eff, load_mean_flux=l.mean_flux, load_energy=l.energy, load_strain=l.strain, load_flux=l.flux,
+                load_max_flux=l.max_flux, load_argmax=l.argmax_element, d2A=s2.d2A, info=np.maximum(l.info, s2.info))
 
 
 def run_derived_group(group: str = "default") -> dict:
     """Every derived output of every DERIVED_CASES case and family (keys d|case|family index|name), and of the DERIVED_SWEEP_CASES with
-    coef * 2^k, M * 2^j, loads * 2^k (keys dsw|case|k|j|name)."""
+    coef * 2^k, M * 2^j, loads * 2^k (keys dsw|case|k|j|name) and with directions * 2^i alone (keys ddir|case|i|name: dA, d2A, info).
+
+    group 'blocked_loads' (a child process with HOMMX_FUSED_LOADS=0): the fused cases alone, and of them the calls that solve load problems
+    (loads, second_sensitivities), with the load route asserted; the same keys d|case|family index|name."""
     out = {}
     for case in R.DERIVED_CASES:
         kernel, ckernel, cs = R.derived_case(case)
+        if group == "blocked_loads" and kernel != "fused2d":
+            continue
         cid = R.case_id(cs)
         coef0, _, g = R.case_inputs(cs, "log2", None)
         inp = R.derived_inputs(cs, coef0[0])
@@ -169,16 +182,26 @@ def run_derived_group(group: str = "default") -> dict:
         assert p.corrector_kernel == ckernel, (p.corrector_kernel, ckernel)
         response = p.load_kernel != "none"
         assert response == (kernel != "mesh_front")
+        if kernel == "fused2d":  # both load routes of the fused plans: substitution in process, the blocked family in the child
+            assert p.load_kernel == ("blocked" if group == "blocked_loads" else "fused2d_subst"), p.load_kernel
         for fi, (family, mf) in enumerate(R.DERIVED_FAMILIES):
             coef, M, _ = R.case_inputs(cs, family or R.top_family(cs[1]), mf)
-            for name, v in _derived_calls(p, coef, M, inp, response).items():
+            calls = _load_calls(p, coef, M, inp) if group == "blocked_loads" else _derived_calls(p, coef, M, inp, response)
+            for name, v in calls.items():
                 out[f"d|{cid}|{fi}|{name}"] = v
-        if case in R.DERIVED_SWEEP_CASES:
+        if case in R.DERIVED_SWEEP_CASES and group == "default":
             coef, M, _ = R.case_inputs(cs, "log2", "mild")
             for k, j in R.DERIVED_SWEEP_KJ:
                 scaled = dict(inp, loads=inp["loads"] * 2.0**k)
                 for name, v in _derived_calls(p, coef * 2.0**k, M * 2.0**j, scaled, response).items():
                     out[f"dsw|{cid}|{k}|{j}|{name}"] = v
+            for i in R.DERIVED_SWEEP_DIR:
+                s = p.sensitivities(coef, M, directions=inp["directions"] * 2.0**i)
+                out[f"ddir|{cid}|{i}|dA"], out[f"ddir|{cid}|{i}|info"] = s.dA, s.info
+                if response:
+                    s2 = p.second_sensitivities(coef, M, directions=inp["directions"] * 2.0**i, first=True)
+                    assert np.array_equal(s2.dA, s.dA)
+                    out[f"ddir|{cid}|{i}|d2A"], out[f"ddir|{cid}|{i}|info"] = s2.d2A, np.maximum(s.info, s2.info)
     return out
 
 
@@ -293,7 +316,47 @@ def run_pivot_group(group: str) -> dict:
     return out
 
 
-RUNNERS = {"accuracy": run_accuracy_group, "pivot": run_pivot_group, "derived": run_derived_group}
+# second derivatives on the doctored batches: one case per load route (substitution on the fused records with the padded NB = 32, the plane
+# elimination behind a small-block plan, the tree's back substitution)
+PIVOT_SENS2_CASES = [PIVOT_CASES[1], PIVOT_CASES[2], PIVOT_CASES[5]]
+
+
+def pivot_sens2_batches(dim: int) -> tuple:
+    """The doctored batches of a case: both classes occur in ('neg100', 'negq') on all three; the zero element on the 2D cases only (a long-
+    double truth of 3D elasticity n = 5 with its float64 yardstick takes a second, and 'negq' asks for six already)."""
+    return ("neg100", "negq", "zero") if dim == 2 else ("neg100", "negq")
+
+
+def pivot_directions(kind, dim, n, good: np.ndarray) -> np.ndarray:
+    """Three seeded directions shared by the cells of a pivot case: a random stream, the indicator of every other element, a second random
+    stream.  None is a cell's coefficient: no block vanishes, and every block has a scale of its own."""
+    rng = np.random.default_rng(R.case_seed("pivot directions", kind, dim, n))
+    every_other = np.zeros(good.shape[1:])
+    every_other[::2] = 1.0
+    return np.stack([rng.standard_normal(good.shape[1:]), every_other, rng.standard_normal(good.shape[1:])])
+
+
+def run_pivot_sens2_group(group: str = "default") -> dict:
+    """second_sensitivities on the all-good batch (keys good<name>|case) and on the doctored batches (keys <name>|case|batch) of the
+    PIVOT_SENS2_CASES: d2A, dA, A, info."""
+    out = {}
+    for g, kernel, kind, dim, n, flags in PIVOT_SENS2_CASES:
+        assert g == group
+        good, M, cells_p, nn = pivot_inputs_structured(kind, dim, n)
+        p = _plan(kernel, kind, dim, n, flags)
+        dirs = pivot_directions(kind, dim, n, good)
+        key = skey(kind, dim, n, flags)
+        r = p.second_sensitivities(good, M, directions=dirs, first=True)
+        out[f"goodd2A|{key}"], out[f"gooddA|{key}"], out[f"goodA|{key}"], out[f"goodinfo|{key}"] = r.d2A, r.dA, r.A_eff, r.info
+        batches = pivot_batches(kind, cells_p, nn, good, M)
+        for name in pivot_sens2_batches(dim):
+            c, MM, _ = batches[name]
+            r = p.second_sensitivities(c, MM, directions=dirs, first=True)
+            out[f"d2A|{key}|{name}"], out[f"dA|{key}|{name}"], out[f"A|{key}|{name}"], out[f"info|{key}|{name}"] = r.d2A, r.dA, r.A_eff, r.info
+    return out
+
+
+RUNNERS = {"accuracy": run_accuracy_group, "pivot": run_pivot_group, "derived": run_derived_group, "pivot_sens2": run_pivot_sens2_group}
 
 
 def run_in_child(what: str, group: str, tmp_path) -> dict:

@@ -17,7 +17,7 @@ The case tables and coefficient families of the GPU accuracy tests live here too
 below 1e-12 on every family (an ill-posed input cannot loosen a bound unnoticed) and tools/accuracy_table.py can reuse them.
 
 ``derived_truth`` extends the truth to everything the package computes FROM the correctors (reconstruction, coefficient and stratification
-derivatives, load responses); ``derived_float64_errors`` measures the float64 NumPy references of the coarse tests against it, per
+derivatives, load responses, second coefficient derivatives); ``derived_float64_errors`` measures the float64 NumPy references of the coarse tests against it, per
 quantity: the yardsticks of tests/test_gpu_accuracy_derived.py.  ``stratification_family`` holds the M families (mild, shear30,
 squeeze16, rot) of the stratification tests.
 """
@@ -386,7 +386,11 @@ def derived_truth(kind, x, cells, to_periodic, coef, M=None, xi=None, directions
     always    A[t, t], chi[n_dof, t] (mean-free), C0[t, t], vol[e], s_canon[t, e, t] (the strain of every canonical load)
     xi[t]     strain / flux [e, t], mean_strain / mean_flux [t], energy, norm[e] (the flux norm), max_flux; with labels[e] the region_* rows
               (mean strain and flux divided by the region's volume, energy not) and region_norm[r, e] (-1 outside the region)
-    directions[n, e(, n_comp)]   dA[n, t, t] = sum_K |K| s^m_K . material(dir_K) s^n_K
+    directions[n, e(, n_comp)]   dA[n, t, t] = sum_K |K| s^m_K . material(dir_K) s^n_K;  d2A[n, n, t, t], the second derivatives along
+                                 the directions in the energy form of tests/sens2_ref.py (eps_b[m] the strain of the corrector of the load
+                                 material(dir_b) s^m):  -sum_K |K| (eps_b[m] . V(coef) eps_a[n] + eps_a[m] . V(coef) eps_b[n]);  d2A_direct, the
+                                 form the library sums (g_ab + g_ab^T, g_ab[m][n] = sum_K |K| eps_b[m] . material(dir_a) s^n): the same number
+                                 in exact arithmetic, no sum shared; for the identity check of the host test only
     weights[t, t]                grad[e(, n_comp)] of weights : A_H;  dA_dM[d, d, t, t] (always) and grad_M[d, d] by the moment form
     loads[l, e, t]               load_chi[n_dof, l] (mean-free), P_eff / load_mean_flux [l, t], load_energy[l, l], load_strain / load_flux
                                  [l, e, t], load_norm[l, e], load_max_flux[l]"""
@@ -417,6 +421,18 @@ def derived_truth(kind, x, cells, to_periodic, coef, M=None, xi=None, directions
             out.update(region_rows(vol, s, q, nrm, labels, int(np.max(labels)) + 1))
     if directions is not None:
         out["dA"] = np.stack([np.einsum("e,met,etu,neu->mn", vol, s_canon, voigt_material(kind, d, dim), s_canon) for d in directions])
+        Vd = np.stack([voigt_material(kind, d, dim) for d in directions])
+        # the derivative of chi^m along dir_b is the corrector of the load V(dir_b) s^m (tests/sens2_ref.py); a second solve: its
+        # right-hand sides are formed from the canonical correctors
+        nd = len(Vd)
+        Pd = np.einsum("betu,meu->bmet", Vd, s_canon).reshape(nd * t, ne, t)
+        Fd = np.zeros((a.nd, nd * t), dtype=LD)
+        np.add.at(Fd, a.rows.ravel(), -np.einsum("e,eta,let->eal", vol, B, Pd).reshape(-1, nd * t))
+        eps_d = np.einsum("eta,eal->let", B, solve_ld(a, Fd, solver)[a.rows]).reshape(nd, t, ne, t)
+        en = np.einsum("e,bmet,etu,aneu->abmn", vol, eps_d, V, eps_d)
+        out["d2A"] = -(en + np.transpose(en, (1, 0, 2, 3)))
+        gd = np.einsum("e,bmet,aetu,neu->abmn", vol, eps_d, Vd, s_canon)
+        out["d2A_direct"] = gd + np.transpose(gd, (0, 1, 3, 2))
     # the stratification: H^n_K[alpha][b] = sum_a chi_n[p_a bs + alpha] g_a[b] (no M), sigma^m_K as a d x bs matrix
     g = element_geometry(x, cells, dim, LD)[0]
     H = np.einsum("eaxn,eab->nexb", chi[a.rows].reshape(ne, dim + 1, a.bs, t), g)
@@ -462,6 +478,7 @@ def derived_float64(kind, x, cells, to_periodic, coef, M=None, xi=None, directio
     strat_sens_ref and loads_ref (their own sparse LU, dof order of ``to_periodic``), sens_ref.Cell on the canonical strains of loads_ref."""
     import loads_ref as LR
     import recon_ref as RR
+    import sens2_ref as S2
     import sens_ref as SR
     import strat_sens_ref as TR
 
@@ -485,6 +502,7 @@ def derived_float64(kind, x, cells, to_periodic, coef, M=None, xi=None, directio
     sc = SR.Cell(kind, dim, st.cell.vol, list(st.cell.s_canon), st.cell.A)
     if directions is not None:
         out["dA"] = np.stack([sc.dA(d) for d in directions])
+        out["d2A"] = S2.second_derivatives(st.cell, directions)  # the energy form, on the cell of loads_ref built above
     if weights is not None:
         gr = sc.grad(np.asarray(weights, float), n_components(kind, dim))
         out["grad"] = gr if gr.shape[1] > 1 else gr[:, 0]
@@ -499,15 +517,40 @@ def derived_float64(kind, x, cells, to_periodic, coef, M=None, xi=None, directio
     return out
 
 
+def euler_directions(coef, directions) -> list:
+    """The directions that ARE the cell's coefficient.  A_H is homogeneous of degree one in the coefficient, so every block of d2A with such
+    a direction vanishes (Euler): the truth holds rounding there (1e-20 of the largest block), and an error relative to the block itself
+    means nothing.  Decided from the inputs, never from the size of a result."""
+    coef = np.asarray(coef)
+    return [k for k, d in enumerate(directions) if np.array_equal(np.asarray(d), coef)]
+
+
+def block_rel(A, T, euler=()) -> np.ndarray:
+    """e[a, b] = max|A[a, b] - T[a, b]| / max|T[a, b]| of d2A[a, b, t, t] per block; the blocks with a or b in ``euler``
+    (``euler_directions``) over max|T| of the whole array."""
+    T = np.asarray(T, dtype=LD)
+    d = np.abs(np.asarray(A, dtype=LD) - T).max(axis=(2, 3))
+    scale = np.abs(T).max(axis=(2, 3))
+    for k in euler:
+        scale[k, :] = scale[:, k] = np.abs(T).max()
+    return (d / scale).astype(np.float64)
+
+
 def derived_float64_errors(kind, x, cells, to_periodic, coef, M=None, xi=None, directions=None, weights=None, loads=None, labels=None,
                            T: dict | None = None, n: int | None = None, msh=None) -> dict:
     """Per quantity  e = max|ref64 - T| / max|T|  over the cell's whole array (T = ``derived_truth``, computed here when None; ref64 =
-    ``derived_float64``) and  bound = 32 * max(e, 16 eps):  {"e": {name: e}, "bound": {name: bound}}.  Never from a GPU result."""
+    ``derived_float64``) and  bound = 32 * max(e, 16 eps):  {"e": {name: e}, "bound": {name: bound}}.  Never from a GPU result.
+    d2A PER BLOCK: e["d2A"] and bound["d2A"] are [n_dirs, n_dirs] arrays (``block_rel`` with the ``euler_directions`` of the inputs): the
+    blocks differ by three orders of magnitude, so the whole-array error would hide a loss in the small ones."""
     if T is None:
         T = derived_truth(kind, x, cells, to_periodic, coef, M, xi, directions, weights, loads, labels)
     ref = derived_float64(kind, x, cells, to_periodic, coef, M, xi, directions, weights, loads, labels, n=n, msh=msh)
-    e = {k: rel(v, T[k]) for k, v in ref.items() if k in T and k != "region_norm"}
-    return {"e": e, "bound": {k: bound(v, 0.0) for k, v in e.items()}}
+    e = {k: rel(v, T[k]) for k, v in ref.items() if k in T and k not in ("region_norm", "d2A")}
+    b = {k: bound(v, 0.0) for k, v in e.items()}
+    if "d2A" in ref:
+        e["d2A"] = block_rel(ref["d2A"], T["d2A"], euler_directions(coef, directions))
+        b["d2A"] = FACTOR * np.maximum(e["d2A"], FLOOR_EPS * EPS)
+    return {"e": e, "bound": b}
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -607,7 +650,9 @@ STRUCTURED_CASES = {
     "plane": [("blocked", "poisson", 3, 6, 0), ("blocked", "elasticity", 3, 4, 0), ("blocked", "elasticity", 3, 5, 0),
               ("blocked", "poisson", 3, 9, 0), ("blocked", "poisson", 2, 16, 1)],
 }
-CHILD_ENV = {"default": {}, "staged": {"HOMMX_MF_STAGE": "64"}, "plane": {"HOMMX_NO_SMALL_FUSED": "1", "HOMMX_MF_MIN_B": "0"}}
+CHILD_ENV = {"default": {}, "staged": {"HOMMX_MF_STAGE": "64"}, "plane": {"HOMMX_NO_SMALL_FUSED": "1", "HOMMX_MF_MIN_B": "0"},
+             # derived outputs only: the load solves of the fused 2D plans by one more elimination of the blocked family
+             "blocked_loads": {"HOMMX_FUSED_LOADS": "0"}}
 # (kernel, kind, mesh builder name, builder arguments, route)
 MESH_CASES = [
     ("mesh_front", "elasticity", "jittered_unit_square", (9, 7), None), ("mesh_front", "poisson", "jittered_unit_cube", (3, 4, 3), None),
@@ -736,7 +781,12 @@ SCALING_LAWS = {
     "max_flux": (1, 0), "region_volume": (0, 0), "region_mean_strain": (0, 0), "region_mean_flux": (1, 0), "region_energy": (1, 0),
     "region_max_flux": (1, 0), "dA": (0, 0), "grad": (0, 0), "dA_dM": (1, -1), "grad_M": (1, -1), "load_chi": (0, -1), "P_eff": (1, 0),
     "load_mean_flux": (1, 0), "load_energy": (1, 0), "load_strain": (0, 0), "load_flux": (1, 0), "load_max_flux": (1, 0),
+    "d2A": (-1, 0), "d2A_direct": (-1, 0),
 }
+# the third sweep: directions * 2^i with everything else fixed, at (k, j) = (0, 0).  The power of 2^i by which dA and d2A scale (linear and
+# bilinear in the directions); decided by the same host test
+DERIVED_SWEEP_DIR = (-20, 20)
+DIRECTION_LAWS = {"dA": 1, "d2A": 2, "d2A_direct": 2}
 
 
 def derived_case(case):

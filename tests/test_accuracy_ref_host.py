@@ -2,7 +2,9 @@
 40-digit mpmath solve, the structured against the mesh path, and the float64 yardsticks of the GPU accuracy tests on every case family
 (below 1e-12: an ill-posed input cannot loosen a GPU bound unnoticed).  The derived truth (reconstruction, derivatives, loads): its exact
 identities to 1e-16, dA_dM against a central difference of ``truth``, the exact scaling laws under coef 2^k, M 2^j, loads 2^k, and caps on
-every yardstick the GPU tests of the derived outputs and of the stratification families use (1e-11; correctors 1e-10)."""
+every yardstick the GPU tests of the derived outputs and of the stratification families use (1e-11; correctors 1e-10).  The truth's second
+derivatives d2A: energy form against direct form, symmetry, Euler blocks and concavity on every input the GPU test uses, central second
+differences of ``truth``, the scaling laws (also under directions 2^i), and the per-block yardstick under the same cap."""
 
 import numpy as np
 import pytest
@@ -194,6 +196,65 @@ def test_identities_of_the_derived_truth(kind, dim, n):
     # regions cover the cell
     assert R.rel(T["region_volume"].sum(), 1.0) <= tol and R.rel(T["region_energy"].sum(), T["energy"]) <= tol
     assert R.rel(T["region_volume"] @ T["region_mean_flux"], T["mean_flux"]) <= tol and T["region_max_flux"].max() == T["max_flux"]
+    _check_d2A_identities(T, [0], f"{kind} {dim}D n={n}")  # direction 0 is the cell's own coefficient here
+
+
+TOL_D2A = 1e-15  # the identities of the truth's d2A, of the block's (Euler blocks: the array's) largest entry; measured 2.4e-16 at most
+
+
+def _check_d2A_identities(T, euler, what):
+    """The truth's d2A: the energy form against the direct form per block, symmetry in (a, b) and (m, n), the Euler blocks, and concavity
+    (no diagonal block has a positive eigenvalue; the eigenvalues in float64: 1e-16 of the block)."""
+    D = T["d2A"]
+    scale, eps_ld = np.abs(D).max(), float(np.finfo(LD).eps)
+    ident = R.block_rel(T["d2A_direct"], D, euler)
+    print(f"{what}: d2A energy form against direct form, per block {ident.max():.1e}")
+    assert D.dtype == LD and ident.max() <= TOL_D2A, (what, ident)
+    # (the direct form is symmetric in (a, b) only as far as it agrees with the energy form)
+    assert float(np.abs(D - np.swapaxes(D, 0, 1)).max() / scale) <= 4 * eps_ld and float(np.abs(D - np.swapaxes(D, 2, 3)).max() / scale) <= 4 * eps_ld
+    for k in euler:
+        assert float(max(np.abs(D[k]).max(), np.abs(D[:, k]).max()) / scale) <= TOL_D2A, (what, k)
+    for a in range(D.shape[0]):
+        assert np.linalg.eigvalsh(D[a, a].astype(np.float64)).max() <= TOL_D2A * float(scale), (what, a)
+
+
+def _central_second_differences(A, coef, dirs, h):
+    """d2A[a, b] of the long-double tensor A(coef) by central second differences (the stencils of sens2_ref.central_second_differences).
+    ``truth`` reads its coefficient as float64, so every perturbed stream must be one exactly: asserted."""
+    nd, A0 = len(dirs), A(coef)
+
+    def at(sa, a, sb=0.0, b=0):
+        c = coef.astype(LD) + LD(sa * h) * dirs[a].astype(LD) + LD(sb * h) * dirs[b].astype(LD)
+        assert np.array_equal(c.astype(np.float64).astype(LD), c)
+        return A(c.astype(np.float64))
+
+    out = np.empty((nd, nd) + A0.shape, dtype=LD)
+    for a in range(nd):
+        out[a, a] = (at(1, a) - 2 * A0 + at(-1, a)) / LD(h) ** 2
+        for b in range(a):
+            out[a, b] = out[b, a] = (at(1, a, 1, b) - at(1, a, -1, b) - at(-1, a, 1, b) + at(-1, a, -1, b)) / (4 * LD(h) ** 2)
+    return out
+
+
+FD_STEP = 2.0**-16  # eps_ld^(1/4) = 1.8e-5: truncation h^2 d4A / 12 and rounding 4 eps_ld |A| / h^2 balance (both 2e-10 |A| at d4A ~ |A|)
+FD_GRID = 2.0**-20  # coefficient and directions are rounded to this grid, so that coef +- h dir_a +- h dir_b is a float64 exactly
+
+
+@pytest.mark.parametrize("kind,dim,n,tol", [("poisson", 2, 5, 1e-8), ("elasticity", 3, 3, 1e-6)])
+def test_d2A_against_central_second_differences_of_truth(kind, dim, n, tol):
+    """The independent check of the truth's d2A: central second differences of ``truth``'s A_H in long double (dense Cholesky: no stopping
+    criterion), step 2^-16, with coefficient and directions on a grid of 2^-20 so that no perturbed stream is rounded.  The difference
+    quotient's own error is h^2 d4A / 12 + 4 eps_ld |A| / h^2; the directions reach 30 times the smallest coefficient, so d4A is far above |A|.
+    Achieved, of the largest entry: 9.2e-10 (Poisson 2D n = 5) and 9.5e-8 (3D elasticity n = 3); ``tol`` is 10 x that."""
+    case, coef, M, g, inp = _small_cell(kind, dim, n)
+    q = lambda v: np.round(v / FD_GRID) * FD_GRID  # noqa: E731
+    coef = q(coef)
+    dirs = np.stack([coef, q(inp["directions"][1]), q(inp["directions"][2])])
+    T = R.derived_truth(kind, g["x"], g["cells"], g["tp"], coef, M, directions=dirs, solver="dense")
+    fd = _central_second_differences(lambda c: R.truth(kind, g["x"], g["cells"], g["tp"], c, M, solver="dense")[0], coef, dirs, FD_STEP)
+    err = float(np.abs(fd - T["d2A"]).max() / np.abs(T["d2A"]).max())
+    print(f"{kind} {dim}D n={n}: d2A against central second differences of truth {err:.2e}")
+    assert err <= tol
 
 
 @pytest.mark.parametrize("kind,dim,n", [("poisson", 2, 5), ("elasticity_voigt", 2, 4), ("elasticity", 3, 3)])
@@ -226,6 +287,12 @@ def test_scaling_laws_are_exact(kind, dim, n):
         assert set(R.SCALING_LAWS) >= set(T) - {"C0", "vol", "s_canon", "norm", "region_norm", "load_norm"}
         assert T["norm"].argmax() == T0["norm"].argmax() and np.array_equal(T["load_norm"].argmax(axis=1), T0["load_norm"].argmax(axis=1))
         assert np.array_equal(T["region_norm"].argmax(axis=1), T0["region_norm"].argmax(axis=1))
+    # the third sweep: the directions alone times 2^i.  dA is linear and d2A bilinear in them; nothing else moves
+    for i in (20, -20, 7):
+        T = R.derived_truth(kind, g["x"], g["cells"], g["tp"], coef, M, inp["xi"], inp["directions"] * 2.0**i, inp["weights"], inp["loads"],
+                            inp["labels"])
+        for name in set(T) - {"region_norm"}:
+            assert R.rel(T[name] * LD(2.0) ** -(i * R.DIRECTION_LAWS.get(name, 0)), T0[name]) <= tol, (name, i)
 
 
 def test_stratification_families():
@@ -259,7 +326,11 @@ def test_truth_converges_and_tensor_yardstick_is_capped_on_every_M_family(case):
 
 @pytest.mark.parametrize("case", R.DERIVED_CASES, ids=lambda c: R.case_id(R.derived_case(c)[2]))
 def test_derived_yardsticks_are_capped(case):
-    """Every case, family and cell of test_gpu_accuracy_derived.py: the truth converges and no float64 yardstick passes its cap."""
+    """Every case, family and cell of test_gpu_accuracy_derived.py: the truth converges and no float64 yardstick passes its cap; d2A per
+    block (the largest block of the cell decides), and its truth meets its identities on these very inputs.  The Euler blocks are those
+    of cell 0 of the four log2 families, whose coefficient is direction 0: read off the inputs.
+
+    Measured, d2A per block: 4.2e-12 at most (small_wave-elasticity-2-10, log2 shear30, cell 1); below 1e-14 without a hard M."""
     _, _, cs = R.derived_case(case)
     kind = cs[1]
     inp = R.derived_inputs(cs, R.case_inputs(cs, "log2", None)[0][0])
@@ -267,8 +338,16 @@ def test_derived_yardsticks_are_capped(case):
     for family, mf in R.DERIVED_FAMILIES:
         coef, M, g = R.case_inputs(cs, family or R.top_family(kind), mf)
         for c in range(R.NC):
-            e = R.derived_float64_errors(kind, g["x"], g["cells"], g["tp"], coef[c], None if M is None else M[c], **inp, **g["kw"])["e"]
+            a = (kind, g["x"], g["cells"], g["tp"], coef[c], None if M is None else M[c])
+            T = R.derived_truth(*a, **inp)
+            euler = R.euler_directions(coef[c], inp["directions"])
+            assert euler == ([0] if family == "log2" and c == 0 else []), (family, mf, c, euler)
+            _check_d2A_identities(T, euler, f"{R.case_id(cs)} {family} {mf} cell {c}")
+            e = R.derived_float64_errors(*a, **inp, T=T, **g["kw"])["e"]
+            assert e["d2A"].shape == (3, 3)
+            print(f"{R.case_id(cs)} {family} {mf} cell {c}: d2A yardstick per block, largest {e['d2A'].max():.1e}")
             for name, v in e.items():
+                v = float(np.max(v))
                 worst[name] = max(worst.get(name, 0.0), v)
                 assert v <= (CAP_CORRECTORS if name in R.CORRECTOR_QUANTITIES else CAP), (family, mf, c, name, v)
     print(R.case_id(cs), {k: f"{v:.1e}" for k, v in worst.items()})

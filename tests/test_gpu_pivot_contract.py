@@ -12,6 +12,9 @@ every cell must be decisive, |lambda_min / lambda_max| > 1e-6:
     one NaN / +Inf element, one NaN entry of M        -> info > 0
 
 The good cells keep the bits they have in a batch of good cells only.
+
+The same batches through second_sensitivities on one case per load route: the flag, the accuracy of d2A on the cells that stay SPD
+(per block, the bound of tests/test_gpu_accuracy_derived.py), the bits of the neighbours.
 """
 
 import numpy as np
@@ -82,6 +85,53 @@ def test_localized_failures_structured(results, group, kernel, kind, dim, n, fla
     good, M, cells_p, nn = G.pivot_inputs_structured(kind, dim, n)
     x, cells, tp = R.structured(dim, n)
     _check_case(results(group), G.skey(kind, dim, n, flags), kind, x, cells, tp, good, M, 1, {"n": n})
+
+
+@pytest.fixture(scope="module")
+def sens2_results():
+    return G.run_pivot_sens2_group()
+
+
+@pytest.mark.parametrize("group,kernel,kind,dim,n,flags", G.PIVOT_SENS2_CASES, ids=lambda v: str(v))
+def test_second_derivatives_of_localized_failures(sens2_results, group, kernel, kind, dim, n, flags):
+    """second_sensitivities on the same doctored batches, one case per load route: a cell that stays SPD keeps info == 0 and its d2A meets the
+    per-block bound of tests/test_gpu_accuracy_derived.py against its OWN long-double truth; an indefinite cell is flagged; every good
+    neighbour keeps the bits it has in a batch of good cells only (d2A, dA, A_eff).  Three shared directions, none of them a coefficient."""
+    res, key = sens2_results, G.skey(kind, dim, n, flags)
+    good, M, cells_p, nn = G.pivot_inputs_structured(kind, dim, n)
+    x, cells, tp = R.structured(dim, n)
+    dirs = G.pivot_directions(kind, dim, n, good)
+    assert np.all(res[f"goodinfo|{key}"] == 0)
+    batches = G.pivot_batches(kind, cells_p, nn, good, M)
+    classes, failures = set(), []
+    for name in G.pivot_sens2_batches(dim):
+        coef, MM, where = batches[name]
+        d2A, info = res[f"d2A|{key}|{name}"], res[f"info|{key}|{name}"]
+        assert np.all(info[0::2] == 0), (key, name, info)
+        for q in ("d2A", "dA", "A"):
+            assert np.array_equal(res[f"{q}|{key}|{name}"][0::2], res[f"good{q}|{key}"]), (key, name, q)
+        for i in range(6):
+            c = 1 + 2 * i
+            ratio = _spectrum_ratio(kind, x, cells, tp, coef[c], MM[c])
+            assert abs(ratio) > 1e-6, (key, name, i, ratio)
+            if ratio < 0:
+                classes.add("indefinite")
+                assert info[c] != 0, (key, name, i, where[i], ratio, info)
+                continue
+            classes.add("spd")
+            assert info[c] == 0, (key, name, i, where[i], ratio, info)
+            a = (kind, x, cells, tp, coef[c], MM[c])
+            assert R.euler_directions(coef[c], dirs) == []
+            T = R.derived_truth(*a, directions=dirs)
+            y = R.derived_float64_errors(*a, directions=dirs, T=T, n=n)
+            err = R.block_rel(d2A[c], T["d2A"])
+            print(f"{key} {name} element {where[i]}: ratio {ratio:.1e} d2A e = {err.max():.2e} float64 {y['e']['d2A'].max():.1e} "
+                  f"ratio to the yardstick {(err / (y['bound']['d2A'] / R.FACTOR)).max():.2f}")
+            if not np.all(err <= y["bound"]["d2A"]):
+                failures.append((key, name, i, err, y["bound"]["d2A"]))
+            assert np.array_equal(d2A[c], np.swapaxes(d2A[c], 0, 1)) and np.array_equal(d2A[c], np.swapaxes(d2A[c], 2, 3))
+    assert classes == {"indefinite", "spd"}, (key, classes)
+    assert not failures, failures
 
 
 @pytest.mark.parametrize("case", G.PIVOT_MESH, ids=lambda c: c[0])

@@ -1,11 +1,13 @@
 """hommx_second_sensitivity_source[_device] on an MI355X (-m gpu): every (dim, kind, mesh) instantiation of k_sens2_loads / k_sens2 on the
 smallest shape of each route against the NumPy / SciPy reference (tests/sens2_ref.py, the energy form; the library sums the direct form),
 the exact identities (bitwise symmetry, Euler, concavity, bilinearity), both load routes of the fused 2D plans, the sampler forms against
-the host-formed stream (bitwise), invariance (batch position, outputs asked for, device against host entry, chunking), a failing cell,
+the host-formed stream (bitwise), invariance (batch position, outputs asked for, device against host entry, chunking), the two ends of
+n_dirs (1 and HOMMX_SENS_MAX_DIRS = 8; 0 and 9 refused by the Python layer), a failing cell,
 the frontal mesh refusal, the stream-order contract of the device entry, and the solver classes end to end against central differences.
 
 Tolerance: 1e-9 of the cell's max |d2A|, the project's tolerance for correctors and fields (header of tests/test_gpu_loads.py): d2A is
-linear in a load corrector whose load is itself formed from the canonical correctors.
+linear in a load corrector whose load is itself formed from the canonical correctors.  This file is the coarse parity check; the accuracy
+of d2A is pinned per block against extended precision, at 32 x the float64 yardstick, by tests/test_gpu_accuracy_derived.py.
 
 Both kernels gather the correctors from global memory at every size: there is no size-dependent path to straddle."""
 
@@ -257,9 +259,71 @@ def test_device_entry_equals_host_entry(name, per_cell):
     assert np.array_equal(A.cpu().numpy(), want.A_eff) and np.array_equal(info.cpu().numpy(), want.info)
 
 
+# -- 5b. the two ends of n_dirs ----------------------------------------------------------------------------------------------------------------
+MAX_DIRS = 8  # HOMMX_SENS_MAX_DIRS
+
+
+@functools.lru_cache(maxsize=None)
+def _eight(name):
+    """Eight shared directions whose first three are the case's, eight per-cell directions whose first two are the case's, and the
+    reference d2A of both; computed once (read only)."""
+    coef, M, shared, per_cell, _, _ = _case(name)
+    rng = np.random.default_rng(77 + sorted(SHAPES).index(name))
+    shared8 = np.concatenate([shared, rng.standard_normal((MAX_DIRS - 3,) + shared.shape[1:])])
+    per_cell8 = np.concatenate([per_cell, rng.standard_normal((NC, MAX_DIRS - 2) + per_cell.shape[2:])], axis=1)
+    cells = [_ref_cell(name, coef[k], M[k]) for k in range(NC)]
+    want_shared = np.stack([S2.second_derivatives(c, shared8) for c in cells])
+    want_per_cell = np.stack([S2.second_derivatives(c, per_cell8[k]) for k, c in enumerate(cells)])
+    for a in (shared8, per_cell8, want_shared, want_per_cell):
+        a.setflags(write=False)
+    return shared8, per_cell8, want_shared, want_per_cell
+
+
+@pytest.mark.parametrize("name", INVARIANT)
+@pytest.mark.parametrize("per_cell", [False, True])
+def test_one_and_eight_directions(name, per_cell):
+    """n_dirs = HOMMX_SENS_MAX_DIRS: all 36 blocks a <= b (and their mirror images) against the reference; the blocks of the first three
+    directions and of the first one are the bits of the calls with three directions and with one.  Per cell, the directions of a chunk
+    start at c0 * n_dirs * (elements * components)."""
+    p = _plan(name)
+    coef, M = _case(name)[:2]
+    shared8, per_cell8, want_shared, want_per_cell = _eight(name)
+    dirs, want = (per_cell8, want_per_cell) if per_cell else (shared8, want_shared)
+    first = lambda n: dirs[:, :n] if per_cell else dirs[:n]  # noqa: E731
+    r8 = p.second_sensitivities(coef, M, directions=dirs, per_cell=per_cell, first=True)
+    assert r8.d2A.shape == (NC, MAX_DIRS, MAX_DIRS, p.t, p.t) and r8.dA.shape == (NC, MAX_DIRS, p.t, p.t) and not r8.info.any()
+    assert _bitwise_symmetric(r8.d2A)
+    _close_per_cell(r8.d2A, want, TOL, f"{name} eight {'per-cell' if per_cell else 'shared'} directions")
+    assert np.array_equal(r8.dA, p.sensitivities(coef, M, directions=dirs, per_cell=per_cell).dA)
+    for n in (3, 1):
+        r = p.second_sensitivities(coef, M, directions=first(n), per_cell=per_cell, first=True)
+        assert r.d2A.shape == (NC, n, n, p.t, p.t) and not r.info.any()
+        assert np.array_equal(r.d2A, r8.d2A[:, :n, :n]) and np.array_equal(r.dA, r8.dA[:, :n]) and np.array_equal(r.A_eff, r8.A_eff), n
+
+
+@pytest.mark.parametrize("per_cell", [False, True])
+def test_python_layer_refuses_zero_and_nine_directions(per_cell, monkeypatch):
+    """Before any device call: the plan's host-call path is never entered.  (The C side: test_abi.py's argument test.)"""
+    p = _plan("fused2d_16")
+    coef, M = _case("fused2d_16")[:2]
+
+    def never(*a, **k):
+        raise AssertionError("the device was reached")
+
+    monkeypatch.setattr(p, "_host_call", never)
+    for n in (0, MAX_DIRS + 1):
+        dirs = np.ones(((NC,) if per_cell else ()) + (n, p.n_el))
+        with pytest.raises(ValueError, match="n_dirs must be 1 .. 8"):
+            p.second_sensitivities(coef, M, directions=dirs, per_cell=per_cell)
+    monkeypatch.undo()
+    assert not p.second_sensitivities(coef, M, directions=np.ones((1, p.n_el))).info.any()  # the refusals left the plan usable
+
+
 # Cells per chunk of 1 MB (recon_chunk of api.hip; per cell: two blocks of t correctors, t n_el t doubles of loads, on the fused plan the
 # factor record and the refinement scratch, and the host entry's staging blocks):
 #   fused2d_32            n = 17: 207,600 B (157 KB of it the factor record) and up to 19 KB of staging -> 4 cells: 12 cells run as 4 + 4 + 4
+#                         (the device blocks do not depend on n_dirs: one direction's loads at a time; with eight per-cell directions
+#                         the staging of the host entry grows to 46 KB -- 37 KB of directions --: 254 KB a cell, still 4 cells)
 #   multifrontal          3D elasticity n = 5: 2 x 18 KB + 216 KB of loads and up to 36 KB of staging -> 3 or 4 cells: 10 cells run in 3 or 4 chunks
 #   mesh_tree_elasticity  216 elements, 36 nodes: 2 x 5 KB + 62 KB and up to 10 KB of staging -> 12 to 14 cells: 30 cells run in 3 chunks
 #   elasticity_8          3D elasticity n = 8 (not in SHAPES): 2 x 74 KB + 885 KB = 1,032,192 B before any staging -> ONE cell per chunk: 3 cells, 3 chunks
@@ -281,6 +345,10 @@ def _chunk_case():
         a = p.second_sensitivities(CoefStream.two_phase(mask, values), M, directions=shared, first=True)  # a sampler form, shared directions
         b = p.second_sensitivities(values[:, mask.astype(int)], M, directions=per_cell, per_cell=True)  # everything per cell
         out.update({f"{name}.d2A_a": a.d2A, f"{name}.dA_a": a.dA, f"{name}.A_a": a.A_eff, f"{name}.d2A_b": b.d2A, f"{name}.info_b": b.info})
+        if name == "fused2d_32":  # HOMMX_SENS_MAX_DIRS per-cell directions: the directions of a chunk start at c0 * 8 * n_el
+            eight = rng.standard_normal((nc, 8) + el)
+            c = p.second_sensitivities(values[:, mask.astype(int)], M, directions=eight, per_cell=True, first=True)
+            out.update({f"{name}.d2A_c": c.d2A, f"{name}.dA_c": c.dA, f"{name}.info_c": c.info})
         p.close()
     return out
 
@@ -288,7 +356,7 @@ def _chunk_case():
 def test_outputs_do_not_depend_on_chunking(tmp_path):
     """HOMMX_RECON_MEM_MB is read when a plan is created: a fresh child process runs the batches in chunks of 1 MB (CHUNKED)."""
     here = _chunk_case()
-    assert not any(v.any() for k, v in here.items() if k.endswith("info_b"))
+    assert not any(v.any() for k, v in here.items() if k.endswith(("info_b", "info_c")))
     out = str(tmp_path / "chunked.npz")
     subprocess.run([sys.executable, os.path.abspath(__file__), out], check=True, env=dict(os.environ, HOMMX_RECON_MEM_MB="1"), timeout=300)
     child = np.load(out)

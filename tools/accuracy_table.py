@@ -9,7 +9,11 @@ tests/test_gpu_accuracy_derived.py against their own float64 yardsticks (accurac
 
 --dumps DIR: take the raw GPU results from DIR/accuracy_<group>.npz -- the name tests/accuracy_gpu.py's run_in_child gives them; written by
 `python tests/accuracy_gpu.py accuracy <group> DIR/accuracy_<group>.npz` with the group's environment -- instead of running the plans here.
-The derived outputs come from DIR/derived_default.npz (`python tests/accuracy_gpu.py derived default DIR/derived_default.npz`).
+The derived outputs come from DIR/derived_default.npz (`python tests/accuracy_gpu.py derived default DIR/derived_default.npz`) and, for the
+second load route of the fused plans, DIR/derived_blocked_loads.npz (the same with `blocked_loads` and HOMMX_FUSED_LOADS=0).
+
+"second_derivatives": the ratio of d2A per (case, family, cell, load route) -- the largest over the cell's blocks, each block against its own
+yardstick (accuracy_ref.block_rel).
 """
 
 import argparse
@@ -147,9 +151,16 @@ def main():
             dres = {k: z[k] for k in z.files}
     else:
         dres = G.run_derived_group()
-    derived = []
+    # the second load route of the fused plans (HOMMX_FUSED_LOADS=0: a child process)
+    if args.dumps:
+        with np.load(os.path.join(args.dumps, "derived_blocked_loads.npz")) as z:
+            bres = {k: z[k] for k in z.files}
+    else:
+        with tempfile.TemporaryDirectory() as tmp:
+            bres = G.run_in_child("derived", "blocked_loads", tmp)
+    derived, second = [], []
     for case in R.DERIVED_CASES:
-        _, ckernel, cs = R.derived_case(case)
+        kernel, ckernel, cs = R.derived_case(case)
         cid = R.case_id(cs)
         inp = R.derived_inputs(cs, R.case_inputs(cs, "log2", None)[0][0])
         worst = {name: (0.0, 0.0, "") for name in DERIVED_GROUPS}
@@ -166,10 +177,20 @@ def main():
                             v = dres[key][c]
                             err = R.rel(v.T if name == "load_chi" else v, T[name])
                             worst[gname] = max(worst[gname], (err / (y["bound"][name] / R.FACTOR), err, f"{name} {family or R.top_family(cs[1])} {mf or 'no M'}"))
+                # d2A per block (accuracy_ref.block_rel), on every load route: the plan's own, and the blocked family's on the fused plans
+                euler = R.euler_directions(coef[c], inp["directions"])
+                for route, rr in ((("fused2d_subst" if kernel == "fused2d" else ckernel), dres), ("blocked", bres)):
+                    key = f"d|{cid}|{fi}|d2A"
+                    if key in rr:
+                        err = R.block_rel(rr[key][c], T["d2A"], euler)
+                        ratio = err / (y["bound"]["d2A"] / R.FACTOR)
+                        at = np.unravel_index(ratio.argmax(), ratio.shape)
+                        second.append({"case": cid, "family": family or R.top_family(cs[1]), "M": mf or "no M", "cell": c, "load_route": route,
+                                       "ratio": float(ratio[at]), "e": float(err[at]), "e_float64": float(y["e"]["d2A"][at]), "block": [int(v) for v in at]})
         derived.append({"case": cid, "correctors": ckernel, "by_group": {k: {"ratio": v[0], "e": v[1], "worst": v[2]} for k, v in worst.items()}})
     with open(args.out, "w") as f:
         json.dump({"bound_factor": R.FACTOR, "floor_eps": R.FLOOR_EPS, "cases": rows, "magnitude_sweep": sweep, "stratification_conditioning": m_cond,
-                   "stratification_scale": m_scale, "derived": derived}, f, indent=1)
+                   "stratification_scale": m_scale, "derived": derived, "second_derivatives": second}, f, indent=1)
     print("| Route | Case | worst ratio | e | at |\n|---|---|---|---|---|")
     for r in rows:
         print(f"| `{r['kernel']}`{'' if r['group'] == 'default' else ' (' + r['group'] + ')'} | {r['case']} | {r['ratio']:.2f} | {r['e']:.1e} | {r['worst']} |")
@@ -181,6 +202,10 @@ def main():
     for d in derived:
         top = max(d["by_group"].values(), key=lambda v: v["ratio"])
         print(f"| {d['case']} | `{d['correctors']}` | " + " | ".join(f"{d['by_group'][k]['ratio']:.2f}" for k in DERIVED_GROUPS) + f" | {top['worst']} |")
+    print("\nSecond derivatives: worst per-block ratio per case and load route\n| Case | load route | ratio | e | e_float64 | at |\n|---|---|---|---|---|---|")
+    for cid, route in dict.fromkeys((s["case"], s["load_route"]) for s in second):
+        w = max((s for s in second if (s["case"], s["load_route"]) == (cid, route)), key=lambda s: s["ratio"])
+        print(f"| {cid} | `{route}` | {w['ratio']:.2f} | {w['e']:.1e} | {w['e_float64']:.1e} | {w['family']} {w['M']} cell {w['cell']} block {tuple(w['block'])} |")
     print("\nConditioning of M\n| Case | " + " | ".join(R.M_CONDITIONING) + " |\n|---|" + "---|" * len(R.M_CONDITIONING))
     for m in m_cond:
         print(f"| {m['case']}{'' if m['group'] == 'default' else ' (' + m['group'] + ')'} | "
