@@ -20,6 +20,7 @@ SAMPLER_AFFINE = 0
 SAMPLER_RECIPROCAL = 1
 MESH_MAX_FRONT = 192  # HOMMX_MESH_MAX_FRONT
 MESH_FLAG_TREE = 1  # HOMMX_MESH_FLAG_TREE
+MESH_FLAG_LOADS = 2  # HOMMX_MESH_FLAG_LOADS
 COEF_SAMPLED = 0  # HOMMX_COEF_*: the form of a hommx_coef_source
 COEF_TWO_PHASE = 1
 COEF_SEPARABLE = 2

@@ -303,7 +303,8 @@ class MicroCellPlan:
         self._adopt(h, int(dim), int(n_micro), kind, device, int(n_micro) ** int(dim), None)
 
     @classmethod
-    def from_mesh(cls, msh, kind: str = "poisson", device: int = 0, order=None, constraint=None, route: str | None = None) -> "MicroCellPlan":
+    def from_mesh(cls, msh, kind: str = "poisson", device: int = 0, order=None, constraint=None, route: str | None = None,
+                  load_solve: bool = False) -> "MicroCellPlan":
         """Plan of the mesh route for ANY periodic simplicial mesh of the unit cell (include/hommx_hip.h, hommx_plan_create_mesh).
 
         The periodic nodes are those of ``create_periodic_boundary_conditions`` (or of ``constraint``, when given); ``to_periodic``
@@ -313,12 +314,18 @@ class MicroCellPlan:
 
         ``route``: None lets the library choose (the frontal route "mesh_front" up to a front of 192 unknowns, the nested-dissection route
         "mesh_multifrontal" beyond); "front" insists on the frontal route (HOMMX_EINVAL for a mesh too wide for it); "tree" takes the
-        nested-dissection route for any mesh (``order`` is then ignored)."""
+        nested-dissection route for any mesh (``order`` is then ignored).
+
+        ``load_solve``: a plan of the frontal route gets a load solve (HOMMX_MESH_FLAG_LOADS; ``load_kernel`` is then
+        "mesh_front_subst": substitution on the pivot columns of its corrector arena) and with it the response outputs of ``loads`` and
+        ``second_sensitivities``; without it such a plan refuses them.  Meaningless on the tree route, which has a load solve of its own:
+        the flag is ignored there.  ``solve`` and the correctors do not depend on it."""
         if kind not in KINDS:
             raise ValueError(f"unknown kind {kind!r}; expected one of {sorted(KINDS)}")
         if route not in (None, "front", "tree"):
             raise ValueError(f"unknown route {route!r}; expected None, 'front' or 'tree'")
-        desc, keep = mesh_desc(msh, kind, device, order, constraint, flags=_lib.MESH_FLAG_TREE if route == "tree" else 0)
+        flags = (_lib.MESH_FLAG_TREE if route == "tree" else 0) | (_lib.MESH_FLAG_LOADS if load_solve else 0)
+        desc, keep = mesh_desc(msh, kind, device, order, constraint, flags=flags)
         self = cls.__new__(cls)
         self._lib = _lib.load()
         if route == "front":  # the frontal route's own analysis: its error (front too wide) instead of the tree route
@@ -510,7 +517,7 @@ class MicroCellPlan:
         """Second derivatives of A_H along coefficient directions (hommx_second_sensitivity_source): ``coef`` an array or a ``CoefStream``,
         M and ``directions`` (shared, or ``per_cell``) as ``sensitivities`` takes them -> ``d2A[N_c, n_dirs, n_dirs, t, t]``, exact on the
         discrete problem: the derivative of every canonical corrector along a direction is the corrector of a polarisation load, which the
-        plan solves on the route ``load_kernel`` names (not on the frontal mesh route).  ``first``: ``dA[N_c, n_dirs, t, t]`` of the same
+        plan solves on the route ``load_kernel`` names (needs ``load_solve=True`` on the frontal mesh route).  ``first``: ``dA[N_c, n_dirs, t, t]`` of the same
         call as well.  One canonical pass and one load solve per direction; correctors and loads never leave the device; the batch runs in
         the chunks of ``reconstruct``."""
         stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
@@ -572,7 +579,7 @@ class MicroCellPlan:
         up to t prescribed flux / stress fields, constant per micro element, components in the order of ``Reconstruction.flux`` (shear not
         doubled) -> ``LoadResponse``.  ``P_eff`` comes from the canonical correctors alone on every plan; ``response`` adds a solve for the
         loads themselves (energy, mean / max total flux), ``fields`` the per-element strain and total flux of every load,
-        ``return_correctors`` the load correctors (each implies ``response``; not on the frontal mesh route).  The batch runs in the chunks
+        ``return_correctors`` the load correctors (each implies ``response``; needs ``load_solve=True`` on the frontal mesh route).  The batch runs in the chunks
         of ``reconstruct``."""
         stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
         nc = self._check_stream(stream)

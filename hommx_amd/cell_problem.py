@@ -111,7 +111,7 @@ class PeriodicLinearProblem:
         loads  optional P[n_loads, n_el, t]: further linear forms l(z) = sum_K |K| P_K . eps(z)_K, a prescribed flux / stress per micro
                element (components in the order of ``Reconstruction.flux``, shear not doubled) -- the general ``L`` of the
                reference restricted to P1, where only element means of such a field matter.  An unstructured mesh then takes the
-               tree route of the mesh family (the frontal route solves for the canonical loads only)
+               tree route of the mesh family (a frontal plan has a load solve only with ``load_solve=True``; this class keeps the tree)
 
     ``solve()`` returns one ``fem.Function`` per canonical load on the micro mesh (slave nodes filled by back substitution,
     constants projected out as the reference's null-space handling does, cell_problem.py:349-361, 382) and stores the

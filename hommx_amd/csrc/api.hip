@@ -184,6 +184,9 @@ int plan_new(hommx_plan** out, const hommx_plan_desc& desc, int64_t n_el) {
 bool fused_subst(const hommx_plan* p) { return p->family == FAM_FUSED2D && p->fused_corr; }
 // ... and whose load solve substitutes on the same records (k_fused2d_subst_rhs) instead of eliminating once more on the blocked route
 bool fused_loads(const hommx_plan* p) { return fused_subst(p) && p->fused_loads; }
+// a frontal mesh plan created with HOMMX_MESH_FLAG_LOADS: its load solve substitutes on the pivot columns of the corrector arena
+// (k_mesh_front_rhs)
+bool mesh_loads(const hommx_plan* p) { return p->family == FAM_MESH && (p->desc.flags & HOMMX_MESH_FLAG_LOADS) != 0; }
 // bytes of factor record per cell of that route (0 on every other)
 size_t fact_bytes(const hommx_plan* p) { return fused_subst(p) ? sizeof(double) * hommx::fused_fact_doubles(p->desc.n_micro) : 0; }
 // ... and of the scratch of its refinement step: the canonical flux field (8 n^2 doubles) and the correction (2 n^2)
@@ -501,7 +504,7 @@ const char* hommx_plan_load_kernel_name(const hommx_plan* p) {
   if (!p) return "";
   switch (p->family) {
     case FAM_FUSED2D: return fused_loads(p) ? "fused2d_subst" : "blocked";
-    case FAM_MESH: return "none";
+    case FAM_MESH: return mesh_loads(p) ? "mesh_front_subst" : "none";
     default: return hommx::blocked_corrector_route_name(p->ws);
   }
 }
@@ -707,6 +710,14 @@ int64_t recon_chunk(const hommx_plan* p, int64_t n_cells, size_t extra) {
   const long long nd = plan_ndof(p);
   const size_t per = sizeof(double) * nd * (p->ks.t + (recon_in_lds(p) ? 0 : 1)) + fact_bytes(p) + refine_bytes(p) + extra;
   return std::clamp<int64_t>((int64_t)((p->recon_mem_mb << 20) / per), 1, n_cells);
+}
+
+// cells per chunk of an entry point whose chunks end in a load solve (load_correctors): the chunk rule of the reconstruction, and on a
+// flagged frontal mesh plan the pivot columns of the arena as well, at most one arena chunk of them -- mesh_solve then runs the chunk as
+// one arena chunk and its columns are still there when the load pass reads them
+int64_t load_chunk(const hommx_plan* p, int64_t n_cells, size_t extra) {
+  if (!mesh_loads(p)) return recon_chunk(p, n_cells, extra);
+  return std::min<int64_t>(recon_chunk(p, n_cells, extra + hommx::mesh_arena_bytes_per_cell(p->mesh)), hommx::mesh_arena_chunk(p->mesh, n_cells));
 }
 
 // device pointers of one chunk of a reconstruction
@@ -1134,11 +1145,11 @@ int loads_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, con
   if (int rc = open_call(p, n_cells, true, "", device, more); rc != GO) return rc;
   // the one check that reads more of the plan than its descriptor (its family), so it cannot run on the plan-shaped memory the checks
   // above accept: it comes after open_call, with the device current already, and before any work
-  if (load_response(*a) && p->family == FAM_MESH)
+  if (load_response(*a) && p->family == FAM_MESH && !mesh_loads(p))
     return fail(HOMMX_EINVAL, "the frontal mesh route (mesh_front) solves for the canonical loads only: energy, stats, strain / flux and "
                               "correctors of user loads need a plan of the tree route (HOMMX_MESH_FLAG_TREE, route=\"tree\"); P_eff alone works here");
   if (int rc = corrector_workspace(p)) return rc;
-  if (load_response(*a) && !p->ws && !fused_loads(p)) {
+  if (load_response(*a) && !p->ws && !fused_loads(p) && !mesh_loads(p)) {
     int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
     if (rc) return prefix_error(rc, "blocked path: ");
   }
@@ -1147,13 +1158,18 @@ int loads_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, con
 
 // The correctors of the loads `lo` of nc cells of a chunk into corr_l[nc][t][ndof] (rows l < n_loads), on the route
 // hommx_plan_load_kernel_name names: fused 2D plans substitute on the records the canonical pass of this chunk has just left in B_FACT
-// (k_fused2d_subst_rhs); every other plan runs a corrector pass of the blocked family on the overridden load rows
+// (k_fused2d_subst_rhs), flagged frontal mesh plans on the pivot columns it has left in the arena (k_mesh_front_rhs; load_chunk keeps
+// them resident); every other plan runs a corrector pass of the blocked family on the overridden load rows
 int load_correctors(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_coef, const double* d_M, const hommx::LoadOverride& lo, hipStream_t st,
                     double* corr_l) {
   if (fused_loads(p)) {
     HIP_TRY(hommx::launch_fused2d_subst_rhs(static_cast<const double*>(p->buf[B_FACT].p), lo.P, lo.n_loads, lo.per_cell, d_M, corr_l,
                                             p->desc.n_micro, nc, st));
     return HOMMX_OK;
+  }
+  if (mesh_loads(p)) {
+    const int rc = hommx::mesh_load_correctors(p->mesh, nc, lo, d_M, corr_l, st);
+    return rc ? route_fail(p, rc) : HOMMX_OK;
   }
   const int t = p->ks.t;
   if (int rc = grow(p->buf[B_LOADS], sizeof(double) * chunk * t * t)) return rc;
@@ -1207,7 +1223,7 @@ int loads_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, con
   int64_t n_out[7], chunk = 0;
   load_out_sizes(p, a, n_out);
   const size_t second = load_response(a) ? sizeof(double) * plan_ndof(p) * p->ks.t : 0;
-  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, second), &chunk)) return rc;
+  if (int rc = stream_chunk(p, s, second ? load_chunk(p, n_cells, second) : recon_chunk(p, n_cells, 0), &chunk)) return rc;
   return source_chunks<LoadIO>(
       p, n_cells, chunk, s, st,
       [&](int64_t c0, int64_t, LoadIO& io) {
@@ -1241,7 +1257,7 @@ int loads_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const
   for (int64_t k : n_in) cell += sizeof(double) * k;
   for (int64_t k : n_out) cell += sizeof(double) * k;
   int64_t chunk = 0;
-  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, cell), &chunk)) return rc;
+  if (int rc = stream_chunk(p, s, load_response(a) ? load_chunk(p, n_cells, cell) : recon_chunk(p, n_cells, cell), &chunk)) return rc;
   size_t in_bytes[3], out_bytes[8];
   for (int k = 0; k < 3; ++k) in_bytes[k] = sizeof(double) * chunk * n_in[k];
   for (int k = 0; k < 7; ++k) out_bytes[k] = sizeof(double) * chunk * n_out[k];
@@ -1290,14 +1306,14 @@ int sens2_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, con
     if (a->n_dirs < 1 || a->n_dirs > HOMMX_SENS_MAX_DIRS)
       return fail(HOMMX_EINVAL, "n_dirs must be 1 .. %d, got %d", HOMMX_SENS_MAX_DIRS, a->n_dirs);
     if (!a->dirs || !a->d2A) return fail(HOMMX_EINVAL, "null dirs / d2A");
-    if (p->desc.n_micro == 0 && !(p->desc.flags & HOMMX_MESH_FLAG_TREE))
+    if (p->desc.n_micro == 0 && !(p->desc.flags & (HOMMX_MESH_FLAG_TREE | HOMMX_MESH_FLAG_LOADS)))
       return fail(HOMMX_EINVAL, "the frontal mesh route (mesh_front) solves for the canonical loads only: second derivatives need the load "
                                 "solve of a plan of the tree route (HOMMX_MESH_FLAG_TREE, route=\"tree\")");
     return HOMMX_OK;
   };
   if (int rc = open_call(p, n_cells, true, "", device, more); rc != GO) return rc;
   if (int rc = corrector_workspace(p)) return rc;
-  if (!p->ws && !fused_loads(p)) {
+  if (!p->ws && !fused_loads(p) && !mesh_loads(p)) {
     int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
     if (rc) return prefix_error(rc, "blocked path: ");
   }
@@ -1351,7 +1367,7 @@ int sens2_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, con
   const int d = p->desc.dim, tt = p->ks.t * p->ks.t;
   const int64_t per = p->n_el * p->ks.n_comp;
   int64_t chunk = 0;
-  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, sens2_extra(p)), &chunk)) return rc;
+  if (int rc = stream_chunk(p, s, load_chunk(p, n_cells, sens2_extra(p)), &chunk)) return rc;
   return source_chunks<Sens2IO>(
       p, n_cells, chunk, s, st,
       [&](int64_t c0, int64_t, Sens2IO& io) {
@@ -1385,7 +1401,7 @@ int sens2_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const
   for (int64_t k : n_in) cell += sizeof(double) * k;
   for (int64_t k : n_out) cell += sizeof(double) * k;
   int64_t chunk = 0;
-  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, cell), &chunk)) return rc;
+  if (int rc = stream_chunk(p, s, load_chunk(p, n_cells, cell), &chunk)) return rc;
   size_t in_bytes[3], out_bytes[4];
   for (int k = 0; k < 3; ++k) in_bytes[k] = sizeof(double) * chunk * n_in[k];
   for (int k = 0; k < 3; ++k) out_bytes[k] = sizeof(double) * chunk * n_out[k];

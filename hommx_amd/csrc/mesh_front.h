@@ -53,4 +53,15 @@ int mesh_reserve(MeshPlan* m, long long n_cells);
 int mesh_solve(MeshPlan* m, long long ncells, const double* d_coef, const double* d_M, double* d_out, int32_t* d_info, hipStream_t stream,
                double* d_corr = nullptr);
 
+// Load solves on the factor arena (k_mesh_front_rhs).  A mesh_solve with d_corr leaves the pivot columns of its cells in the plan's arena
+// only when it ran them as one arena chunk: callers that follow it with a load solve size their chunks by mesh_arena_bytes_per_cell and
+// cap them at mesh_arena_chunk (api.hip, load_chunk).
+struct LoadOverride;  // kernels.h
+size_t mesh_arena_bytes_per_cell(const MeshPlan* m);
+long long mesh_arena_chunk(const MeshPlan* m, long long n_cells);
+// The correctors of the loads `lo` of the first ncells cells of the last mesh_solve(..., d_corr) into rows l < n_loads of
+// d_corr_l[cell][t][n_nodes * bs] (mean-free; NaN for a cell whose elimination failed; rows l >= n_loads untouched), on `stream`.
+// HOMMX_EINVAL when the arena does not hold the columns of that many cells: stale columns are never read.
+int mesh_load_correctors(MeshPlan* m, long long ncells, const LoadOverride& lo, const double* d_M, double* d_corr_l, hipStream_t stream);
+
 }  // namespace hommx

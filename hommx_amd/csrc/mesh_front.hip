@@ -15,6 +15,10 @@
 //
 // Correctors: every pivot's column (before the update) goes to a per-chunk HBM arena; a second kernel substitutes backwards through
 // it and removes the mean per component.
+//
+// Load solves: the arena is a complete L D L^T record of K, so a right-hand side that is not one of the canonical loads needs no
+// second elimination.  k_mesh_front_rhs assembles the loads of a LoadOverride per node, carries them forwards through the stored
+// columns and substitutes backwards as k_mesh_backsub does (mesh_load_correctors; the arena must still hold the cells' columns).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +38,8 @@ namespace hommx {
 namespace {
 constexpr int kThreads = 256;
 constexpr int kRed = 21;  // t (t + 1) / 2 for t <= 6: the C0 partial sums
+// k_mesh_front_rhs: a work item is one load on one segment of kSeg front rows, taken by half a wavefront
+constexpr int kSeg = 32, kHalves = kThreads / kSeg, kMaxSeg = HOMMX_MESH_MAX_FRONT / kSeg;
 }  // namespace
 
 // device view of the symbolic phase (all arrays on the plan's device)
@@ -52,6 +58,14 @@ struct MeshDev {
   const int* owner;               // [n_steps][W / bs] node in every slot at the step (-1: free)
 };
 
+// node -> (element, vertex) incidence on the device: what k_mesh_front_rhs assembles a node's load entries through.  Kept out of
+// MeshDev, whose layout is part of the kernel arguments of k_mesh_front and k_mesh_backsub
+struct MeshInc {
+  const int* ptr;  // [n_nodes + 1]
+  const int* ent;  // [n_el (dim + 1)] element * 4 + vertex; the entries of a node ascend by element
+  int pinned;      // the node whose unknowns never enter the front
+};
+
 struct MeshPlan {
   int dim = 0, kind = 0, bs = 1, t = 0, n_comp = 0;
   int64_t n_nodes = 0, n_el = 0;
@@ -61,11 +75,16 @@ struct MeshPlan {
   std::vector<int> order, pos;
   std::vector<int> el_slot, el_seq, grp_ptr, step_grp, step_slot, step_S, step_node, owner;
   std::vector<long long> piv_off;
+  std::vector<int> inc_ptr, inc_ent;
   MeshDev dev{};
+  MeshInc inc{};
   void* d_tables = nullptr;  // one allocation holds every device table of the symbolic phase
   double* d_arena = nullptr;
   int32_t* d_binfo = nullptr;
   long long cap_arena_cells = 0;
+  // cells whose columns the arena holds, counted from the first cell of the last corrector call: all of them when that call ran as one
+  // arena chunk, none when it walked several (the arena then holds the last chunk's alone)
+  long long arena_valid = 0;
   std::string detail;
 };
 
@@ -289,6 +308,152 @@ __global__ void __launch_bounds__(kThreads) k_mesh_backsub(MeshDev G, const doub
       for (long long nd = tid; nd < G.n_nodes; nd += kThreads) x[m * nu + nd * BS + c] -= mean;
       __syncthreads();
     }
+  }
+}
+
+// Correctors of user loads by substitution on the arena k_mesh_front has just filled: K chi_l = -f^l for the loads l < n_loads of `lo`,
+// in place on rows l < n_loads of corr[cell][t][n_nodes * bs] (the rows behind them are not written).  One workgroup per macro cell.
+//   assemble   r[l][i bs + al] = -sum_{K ni i} |K| P^l_K . strain(g_{a(i,K)}, M, al), one thread per node over its incidence list in
+//              order (the arithmetic of k_assemble_loads_mesh); the pinned node's entries are zero and stay so
+//   forward    pivots in elimination order: y = r at the pivot, r[owner(i)] -= col[i] (y / d) for the other front rows i of the stored
+//              column (distinct rows are distinct entries: no atomics; rows the elimination cleared hold 0 and are skipped)
+//   backward   k_mesh_backsub's recurrence with y in place of the border entry: x_p = (y_p - sum_{i != p} col[i] x_owner(i)) / d
+// and the mean removed per component.  The lanes are spread over (front row x load): an item is one load on one segment of kSeg front
+// rows, the kHalves half-waves take the items in turn.  A load's sum over the rows of a pivot is formed per segment by a butterfly and
+// over the segments in order, so a load's corrector does not depend on how many loads the call has.  The vectors stay in global memory
+// (n_nodes is not bounded by the front width); within the workgroup they are ordered by fences and barriers, as in k_mesh_backsub.
+template <int DIM, int KIND>
+__global__ void __launch_bounds__(kThreads) k_mesh_front_rhs(MeshDev G, MeshInc I, const double* __restrict__ arena, long long arena_per_cell,
+                                                             const int32_t* __restrict__ info, LoadOverride lo, const double* __restrict__ Mall,
+                                                             double* corr) {
+  constexpr KindSizes ks = kind_sizes(DIM, KIND);
+  constexpr int T = ks.t, BS = ks.bs, NV = DIM + 1;
+  __shared__ double part[kMaxSeg][T];
+  __shared__ double wsum[kThreads / 64];
+  const int tid = threadIdx.x, lane = tid % kSeg, half = tid / kSeg;
+  const long long cell = blockIdx.x;
+  const double* ar = arena + cell * arena_per_cell;
+  const long long nu = (long long)G.n_nodes * BS;
+  double* x = corr + cell * T * nu;
+  const int nl = lo.n_loads;
+  const int W = (G.S - T) / BS;  // slots
+  if (info[cell] != 0) {         // uniform across the workgroup
+    for (long long q = tid; q < nl * nu; q += kThreads) x[q] = NAN;
+    return;
+  }
+
+  // assemble
+  {
+    const double* M = Mall ? Mall + cell * DIM * DIM : nullptr;
+    const double* P = lo.P + (lo.per_cell ? cell * nl : 0) * (long long)G.n_el * T;
+    for (int i = tid; i < G.n_nodes; i += kThreads) {
+      double acc[T][BS];
+#pragma unroll
+      for (int m = 0; m < T; ++m)
+#pragma unroll
+        for (int b = 0; b < BS; ++b) acc[m][b] = 0.0;
+      const int q1 = i == I.pinned ? 0 : I.ptr[i + 1];
+      for (int q = I.ptr[i]; q < q1; ++q) {
+        const unsigned ent = (unsigned)I.ent[q];
+        const long long el = ent >> 2;
+        const double vol = G.vol[el];
+        const double* gr = G.grads + (el * NV + (ent & 3)) * DIM;
+#pragma unroll
+        for (int b = 0; b < BS; ++b) {
+          double sb[T];
+          strain<DIM, KIND>(gr, M, b, sb);
+#pragma unroll
+          for (int m = 0; m < T; ++m)
+            if (m < nl) {
+              const double* __restrict__ pk = P + ((long long)m * G.n_el + el) * T;
+              double v = 0.0;
+#pragma unroll
+              for (int k = 0; k < T; ++k) v += pk[k] * sb[k];
+              acc[m][b] -= vol * v;
+            }
+        }
+      }
+#pragma unroll
+      for (int m = 0; m < T; ++m)
+        if (m < nl) {
+#pragma unroll
+          for (int b = 0; b < BS; ++b) x[m * nu + (long long)i * BS + b] = acc[m][b];
+        }
+    }
+  }
+  __threadfence_block();
+  __syncthreads();
+
+  // forward
+  for (int k = 0; k < G.n_steps; ++k) {
+    const int Sk = G.step_S[k], nseg = (Sk - T + kSeg - 1) / kSeg, nitem = nseg * nl;
+    const long long un = (long long)G.step_node[k] * BS;
+    const int* own = G.owner + (long long)k * W;
+    for (int c = 0; c < BS; ++c) {
+      const double* col = ar + G.piv_off[k * BS + c];
+      const int p = T + G.step_slot[k] * BS + c;
+      const double d = col[p];
+      for (int q = half; q < nitem; q += kHalves) {
+        const int l = q / nseg, i = T + (q - l * nseg) * kSeg + lane;
+        if (i >= Sk || i == p) continue;
+        const int nd = own[(i - T) / BS];
+        const double v = col[i];
+        if (nd < 0 || v == 0.0) continue;
+        double* xl = x + l * nu;
+        xl[(long long)nd * BS + (i - T) % BS] -= v * (xl[un + c] / d);
+      }
+      __threadfence_block();
+      __syncthreads();
+    }
+  }
+
+  // backward
+  for (int k = G.n_steps - 1; k >= 0; --k) {
+    const int Sk = G.step_S[k], nseg = (Sk - T + kSeg - 1) / kSeg, nitem = nseg * nl;
+    const long long un = (long long)G.step_node[k] * BS;
+    const int* own = G.owner + (long long)k * W;
+    for (int c = BS - 1; c >= 0; --c) {
+      const double* col = ar + G.piv_off[k * BS + c];
+      const int p = T + G.step_slot[k] * BS + c;
+      for (int q0 = 0; q0 < nitem; q0 += kHalves) {  // the same trips for every half-wave: the butterfly runs in uniform control flow
+        const int q = q0 + half;
+        const bool active = q < nitem;
+        const int l = active ? q / nseg : 0, seg = q - l * nseg, i = T + seg * kSeg + lane;
+        double a = 0.0;
+        if (active && i < Sk && i != p) {
+          const int nd = own[(i - T) / BS];
+          const double v = col[i];
+          if (nd >= 0 && v != 0.0) a = v * x[l * nu + (long long)nd * BS + (i - T) % BS];
+        }
+#pragma unroll
+        for (int o = kSeg / 2; o >= 1; o >>= 1) a += __shfl_xor(a, o, kSeg);
+        if (active && lane == 0) part[seg][l] = a;
+      }
+      __syncthreads();
+      if (tid < nl) {
+        double s = 0.0;
+        for (int seg = 0; seg < nseg; ++seg) s += part[seg][tid];
+        x[tid * nu + un + c] = (x[tid * nu + un + c] - s) / col[p];
+      }
+      __threadfence_block();
+      __syncthreads();
+    }
+  }
+
+  // mean-free per component
+  for (int lc = 0; lc < nl * BS; ++lc) {
+    const int l = lc / BS, c = lc % BS;
+    double s = 0.0;
+    for (long long nd = tid; nd < G.n_nodes; nd += kThreads) s += x[l * nu + nd * BS + c];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_down(s, o, 64);
+    if ((tid & 63) == 0) wsum[tid >> 6] = s;
+    __syncthreads();
+    double tot = 0.0;
+    for (int w = 0; w < kThreads / 64; ++w) tot += wsum[w];
+    const double mean = tot / (double)G.n_nodes;
+    for (long long nd = tid; nd < G.n_nodes; nd += kThreads) x[l * nu + nd * BS + c] -= mean;
+    __syncthreads();
   }
 }
 
@@ -668,6 +833,16 @@ int mesh_analyze(const hommx_mesh_desc* d, const MeshGeom& geo, MeshPlan** out, 
   m->piv_off.assign((size_t)m->n_steps * bs + 1, 0);
   for (int k = 0; k < m->n_steps; ++k)
     for (int c = 0; c < bs; ++c) m->piv_off[(size_t)k * bs + c + 1] = m->piv_off[(size_t)k * bs + c] + m->step_S[k];
+  // node -> (element, vertex) incidence, CSR; filled element by element, so the entries of a node ascend by element
+  m->inc_ptr.assign(n + 1, 0);
+  for (size_t q = 0; q < (size_t)ne * nv; ++q) ++m->inc_ptr[d->el_nodes[q] + 1];
+  for (int v = 0; v < n; ++v) m->inc_ptr[v + 1] += m->inc_ptr[v];
+  m->inc_ent.assign((size_t)ne * nv, 0);
+  {
+    std::vector<int> fill(m->inc_ptr.begin(), m->inc_ptr.end() - 1);
+    for (int e = 0; e < ne; ++e)
+      for (int a = 0; a < nv; ++a) m->inc_ent[fill[d->el_nodes[e * nv + a]]++] = (int)((unsigned)e << 2 | (unsigned)a);
+  }
   *out = m;
   m = nullptr;  // released from the guard
   return HOMMX_OK;
@@ -685,8 +860,11 @@ int mesh_upload(MeshPlan* m, const MeshGeomDev& geo) {
                                             {m->step_S.data(), sizeof(int) * m->step_S.size(), (const void**)&G.step_S},
                                             {m->piv_off.data(), sizeof(long long) * m->piv_off.size(), (const void**)&G.piv_off},
                                             {m->step_node.data(), sizeof(int) * m->step_node.size(), (const void**)&G.step_node},
-                                            {m->owner.data(), sizeof(int) * m->owner.size(), (const void**)&G.owner}}))
+                                            {m->owner.data(), sizeof(int) * m->owner.size(), (const void**)&G.owner},
+                                            {m->inc_ptr.data(), sizeof(int) * m->inc_ptr.size(), (const void**)&m->inc.ptr},
+                                            {m->inc_ent.data(), sizeof(int) * m->inc_ent.size(), (const void**)&m->inc.ent}}))
     return rc;
+  m->inc.pinned = m->order.back();
   G.n_el = (int)m->n_el;
   G.n_nodes = (int)m->n_nodes;
   G.n_steps = m->n_steps;
@@ -722,6 +900,12 @@ long long arena_chunk(const MeshPlan* m, long long ncells) {
   c = std::max(1ll, std::min(c, 65536ll));
   return std::min(c, ncells);
 }
+}  // namespace
+
+size_t mesh_arena_bytes_per_cell(const MeshPlan* m) { return sizeof(double) * (size_t)arena_per_cell(m); }
+long long mesh_arena_chunk(const MeshPlan* m, long long n_cells) { return arena_chunk(m, n_cells); }
+
+namespace {
 
 template <int DIM, int KIND>
 hipError_t launch_front(const MeshPlan* m, long long nc, const double* coef, const double* M, double* out, int32_t* info, double* arena,
@@ -784,6 +968,7 @@ int mesh_solve(MeshPlan* m, long long ncells, const double* d_coef, const double
     HIP_TRY(hipMalloc(&m->d_binfo, sizeof(int32_t) * chunk));
     m->cap_arena_cells = chunk;
   }
+  m->arena_valid = chunk == ncells ? ncells : 0;
   const long long nu = m->n_nodes * m->bs;
   for (long long c0 = 0; c0 < ncells; c0 += chunk) {
     const long long nc = std::min(ncells - c0, chunk);
@@ -791,6 +976,21 @@ int mesh_solve(MeshPlan* m, long long ncells, const double* d_coef, const double
     HIP_TRY(launch_backsub(m, nc, m->d_arena, m->d_binfo, d_corr + c0 * t * nu, st));
     if (d_info) HIP_TRY(hipMemcpyAsync(d_info + c0, m->d_binfo, sizeof(int32_t) * nc, hipMemcpyDeviceToDevice, st));
   }
+  return HOMMX_OK;
+}
+
+int mesh_load_correctors(MeshPlan* m, long long ncells, const LoadOverride& lo, const double* d_M, double* d_corr_l, hipStream_t st) {
+  if (ncells <= 0) return HOMMX_OK;
+  if (lo.n_loads < 1 || lo.n_loads > m->t || !lo.P) return fail(HOMMX_EINVAL, "load solve: n_loads must be 1 .. %d with loads given", m->t);
+  if (ncells > m->arena_valid)
+    return fail(HOMMX_EINVAL, "load solve of %lld cells, but the factor arena holds the columns of %lld: the corrector call before it must "
+                              "run them as one arena chunk",
+                ncells, m->arena_valid);
+  HIP_TRY(dispatch_dim_kind(m->dim, m->kind, [&](auto D, auto K) {
+    hipLaunchKernelGGL((k_mesh_front_rhs<D(), K()>), dim3((unsigned)ncells), dim3(kThreads), 0, st, m->dev, m->inc, m->d_arena, arena_per_cell(m),
+                       m->d_binfo, lo, d_M, d_corr_l);
+    return hipGetLastError();
+  }));
   return HOMMX_OK;
 }
 

@@ -533,7 +533,8 @@ class BaseHMM(ABC):
 
                 self._device = default_device()
             if self._n_micro is None:
-                self._plan = MicroCellPlan.from_mesh(self._cell_mesh, kind, device=self._device)
+                # load_solve: the frontal route serves load_response() and the second derivatives as every other route does
+                self._plan = MicroCellPlan.from_mesh(self._cell_mesh, kind, device=self._device, load_solve=True)
             else:
                 self._plan = MicroCellPlan(self._tdim, self._n_micro, kind, device=self._device)
             self._reserved_cells = 0
@@ -862,8 +863,8 @@ class BaseHMM(ABC):
         per-element strain and total flux [N, 1, n_el, t], with ``correctors`` the corrector [N, 1, n_nodes * bs].
 
         By linearity the micro stress under the macro strain of a solution plus the prestress is
-        ``reconstruct(...).flux + load_response(...).flux[:, 0]``.  Not on a micro mesh of the frontal mesh route (the load solve needs
-        the tree route).  The cells run in chunks of ``chunk_cells`` (default: 256 MB of sampled loads and outputs).  Under a process group
+        ``reconstruct(...).flux + load_response(...).flux[:, 0]``.  Every micro mesh has the load solve (an unstructured one on the frontal
+        route substitutes on its pivot columns).  The cells run in chunks of ``chunk_cells`` (default: 256 MB of sampled loads and outputs).  Under a process group
         this runs on the calling rank alone, for the cells it is given: there is no collective."""
         if self._polarisation is None:
             raise RuntimeError("load_response() needs a polarisation: call set_polarisation() first")
@@ -986,9 +987,8 @@ class BaseHMM(ABC):
         Names and directions are those of ``tensor_derivatives``: without ``directions`` the parameters of a ``TwoPhase`` or an affine
         ``Separable`` coefficient (any other coefficient raises ``ValueError``), else up to 8 callables (x, y) of the coefficient's shape.
         d2A[:, a, b] is exact on the discrete problem -- the Hessian of A_H a Newton or Gauss-Newton step needs, with no step size to
-        tune -- and costs one load solve per direction.  Not on a micro mesh of the frontal mesh route (the load solve needs the tree
-        route).  The cells run in chunks of ``chunk_cells``.  Under a process group this runs on the calling rank alone: there is no
-        collective."""
+        tune -- and costs one load solve per direction, on every micro mesh.  The cells run in chunks of ``chunk_cells``.  Under a process
+        group this runs on the calling rank alone: there is no collective."""
         names, cells, parts = self._direction_blocks("tensor_second_derivatives", cells, directions, chunk_cells,
                                                      lambda plan, coef, M, **kw: plan.second_sensitivities(coef, M, first=True, **kw))
         cat = lambda name: np.concatenate([getattr(r, name) for r in parts])

@@ -117,8 +117,9 @@ const char* hommx_plan_kernel_name(const hommx_plan* plan);
  * (frontal mesh plans), "blocked" (every other plan: plane elimination). */
 const char* hommx_plan_corrector_kernel_name(const hommx_plan* plan);
 /* The route the load solve of hommx_loads_source[_device] takes (the response outputs; P_eff alone needs none): "fused2d_subst" (fused 2D
- * plans; "blocked" with HOMMX_FUSED_LOADS=0 or HOMMX_FUSED_CORR=0), "none" (frontal mesh plans: the response is refused), else the name
- * hommx_plan_corrector_kernel_name returns. */
+ * plans; "blocked" with HOMMX_FUSED_LOADS=0 or HOMMX_FUSED_CORR=0), "mesh_front_subst" (frontal mesh plans created with HOMMX_MESH_FLAG_LOADS:
+ * substitution on the pivot columns of the corrector arena), "none" (frontal mesh plans without the flag: the response is refused), else
+ * the name hommx_plan_corrector_kernel_name returns. */
 const char* hommx_plan_load_kernel_name(const hommx_plan* plan);
 /* One line describing what that route launches for THIS plan (kernel names with their tile sizes, tree shape of the nested dissection,
  * stage size, streams): for reports -- bench.py's roofline.kernel label is this string, so it cannot drift from the code. */
@@ -388,7 +389,8 @@ int hommx_stratification_sensitivity_source_device(hommx_plan* plan, int64_t n_c
  * second elimination, on EVERY plan.  The response outputs come from a solve for the loads themselves (hommx_plan_load_kernel_name names
  * its route): a fused 2D plan substitutes on the factor records its canonical pass has just left (k_fused2d_subst_rhs; with
  * HOMMX_FUSED_LOADS=0 it gets a blocked workspace on the first such call instead), every other plan runs one more corrector pass of the
- * blocked family with the load rows replaced (a mesh plan needs the tree route).
+ * blocked family with the load rows replaced (a mesh plan of the tree route among them); a frontal mesh plan substitutes on the pivot
+ * columns its canonical pass has just left in the corrector arena (k_mesh_front_rhs) when it was created with HOMMX_MESH_FLAG_LOADS.
  *
  *   n_loads     1 .. t of the plan (callers loop for more)
  *   per_cell    0: P[n_loads][n_el][t], shared by all cells; 1: P[n_cells][n_loads][n_el][t]
@@ -402,8 +404,9 @@ int hommx_stratification_sensitivity_source_device(hommx_plan* plan, int64_t n_c
  *   correctors  [n_cells][n_loads][ndof], mean-free per component, dof order of hommx_solve_batch_correctors
  * src, M: as hommx_reconstruct_source.  HOMMX_EINVAL, before the plan's device is made current: a null plan, source or argument struct,
  * n_loads out of range, a null P or P_eff, one of strain / flux without the other.  HOMMX_EINVAL as well, before any work: a response output on a
- * plan of the frontal mesh route ("mesh_front": it builds its loads in the basis of the canonical ones; create the plan with
- * HOMMX_MESH_FLAG_TREE, the tree route, for these).  The correctors of
+ * plan of the frontal mesh route created without HOMMX_MESH_FLAG_LOADS ("mesh_front" builds its loads in the basis of the canonical ones;
+ * with the flag the load solve substitutes on its pivot columns, and a chunk then also holds them: HOMMX_RECON_MEM_MB counts the arena,
+ * and a chunk is at most one arena chunk; HOMMX_MESH_FLAG_TREE, the tree route, serves these too).  The correctors of
  * one chunk (HOMMX_RECON_MEM_MB, the chunk rule of the reconstruction; a response holds two blocks of t correctors per cell) live in
  * plan-owned scratch.  A cell's outputs do not depend on its batch position, the chunking or which outputs are requested (fixed-order
  * reductions).  A cell whose elimination flags a pivot keeps its info; no other cell's outputs change.  The host entry sends a shared P
@@ -438,8 +441,8 @@ int hommx_loads_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coe
  * both bitwise (every block is formed once and mirrored); d2A[a][a] is negative semidefinite (A_H is concave in the coefficient); A_H
  * being 1-homogeneous, every block with the cell's own coefficient as one of its directions vanishes up to rounding (Euler).  The call
  * costs one canonical corrector pass and one load solve per direction (hommx_plan_load_kernel_name names its route: a fused 2D plan
- * substitutes on the factor records the canonical pass has just left, every other plan runs one more corrector pass of the blocked
- * family) against the 2 n_dirs + 1 eliminations of central differences of hommx_sensitivity_source.
+ * substitutes on the factor records the canonical pass has just left, a frontal mesh plan with HOMMX_MESH_FLAG_LOADS on the pivot
+ * columns of its corrector arena, every other plan runs one more corrector pass of the blocked family) against the 2 n_dirs + 1 eliminations of central differences of hommx_sensitivity_source.
  *
  *   n_dirs      1 .. HOMMX_SENS_MAX_DIRS
  *   per_cell    0: dirs[n_dirs][n_el][n_comp], shared by all cells; 1: dirs[n_cells][n_dirs][n_el][n_comp]
@@ -447,8 +450,8 @@ int hommx_loads_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coe
  *   dA          [n_cells][n_dirs][t][t] or NULL: the first derivatives along the same directions, the bits hommx_sensitivity_source returns
  *   A_eff, info as hommx_solve_batch, or NULL
  * src, M: as hommx_reconstruct_source.  HOMMX_EINVAL, before the plan's device is made current: a null plan, source or argument struct,
- * n_dirs out of range, a null dirs or d2A, and a plan of the frontal mesh route ("mesh_front" has no load solve: create the plan with
- * HOMMX_MESH_FLAG_TREE, the tree route).  Every other plan is accepted.  Per cell of a chunk (HOMMX_RECON_MEM_MB, the chunk rule of the
+ * n_dirs out of range, a null dirs or d2A, and a plan of the frontal mesh route created without HOMMX_MESH_FLAG_LOADS ("mesh_front" has no load
+ * solve then: create the plan with that flag, or with HOMMX_MESH_FLAG_TREE, the tree route).  Every other plan is accepted.  Per cell of a chunk (HOMMX_RECON_MEM_MB, the chunk rule of the
  * reconstruction) plan-owned scratch holds two blocks of t correctors and the t loads of one direction (t n_el t doubles).  A cell's
  * outputs do not depend on its batch position, the chunking or which optional outputs are requested (fixed-order reductions).  A cell
  * whose elimination flags a pivot keeps its info; its outputs may hold anything, no other cell's change.  The host entry sends shared
@@ -491,9 +494,12 @@ int hommx_second_sensitivity_source_device(hommx_plan* plan, int64_t n_cells, co
  */
 #define HOMMX_MESH_MAX_FRONT 192  /* largest front, in unknowns: the packed front of t + 192 rows fills the 160 KiB LDS of a CU */
 #define HOMMX_MESH_FLAG_TREE 1    /* hommx_mesh_desc.flags: take the tree route whatever the frontal width                   */
+#define HOMMX_MESH_FLAG_LOADS 2   /* hommx_mesh_desc.flags: a plan of the frontal route gets a load solve ("mesh_front_subst": the
+                                   * response outputs of hommx_loads_source, hommx_second_sensitivity_source); without it such a plan
+                                   * refuses them.  Ignored on the tree route, which has its own; the plan's descriptor keeps the bit */
 
 typedef struct hommx_mesh_desc {
-  int32_t dim, kind, device, flags;   /* as hommx_plan_desc; flags: 0 or HOMMX_MESH_FLAG_TREE                     */
+  int32_t dim, kind, device, flags;   /* as hommx_plan_desc; flags: 0 or HOMMX_MESH_FLAG_* or'ed                  */
   int64_t n_nodes;                    /* independent (periodic) nodes                                             */
   int64_t n_el;                       /* micro elements; coef[cell][el] follows THIS order                        */
   const int32_t* el_nodes;            /* [n_el][dim+1]  periodic node of each vertex                              */
