@@ -75,6 +75,22 @@ struct alignas(16) Lds {
   double dgnat[NB];     // diag of D_{j+1}
   double cenat[NB + 2]; // [1 + i] = D_{j+1}[i][i+1]; [0] = 0
 };
+// The unstratified kernel (ISO) reads no neighbour and builds its band matrices in the registers: no staging matrix, no e1.  NB = 32: the
+// twelve S_last accumulator registers park here between two steps, [register][lane]: every access one contiguous 512 B run.
+template <int NB>
+struct alignas(16) LdsIso {
+  static constexpr int PARK = NB == 32 ? 12 * 64 : 0;
+  double ubuf[4 * NB];
+  double tsc[16 * 17];
+  double rrow[2][NB];
+  double vrow[2][NB];
+  double vnat[2][NB];
+  double e0row[NB];
+  double e0nat[NB];
+  double dgnat[NB];
+  double cenat[NB + 2];
+  double park[PARK ? PARK : 1];
+};
 
 // FACT: the kernel also writes the factor record of its cell (kernels.h) for k_fused2d_subst; the last kernel argument is then the
 // records, and an empty struct otherwise
@@ -82,9 +98,12 @@ struct alignas(16) Lds {
 // between consecutive node rows is diagonal (E[i][i-1] = -ga (a0 + a1) = 0), so every term of the step that carries e1 is an exact zero.  The
 // ISO path is the general one with those terms deleted -- the surviving operations and their order are the same, results agree bit for bit up
 // to the sign of an exact zero -- and with them go the LDS round trips that only fetched the neighbours they multiply.
+// <32, false, true> runs at three waves per SIMD: at most 168 VGPRs and 13,312 B of LDS (LdsIso, S_last parked in LDS between two steps, the
+// launch bound below; tests/test_fused2d_iso_resources.py holds the budget).  That is data movement only: no arithmetic operation differs
+// from the two-wave form.
 struct NoFact {};
 template <int NB, bool FACT, bool ISO>
-__global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fused(
+__global__ __launch_bounds__(64, (NB == 32 && ISO) ? 3 : HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fused(
     const double* __restrict__ coef, const double* __restrict__ Mmat, double* __restrict__ out,
     int32_t* __restrict__ info, int n, long long ncells, const CoefSource src, std::conditional_t<FACT, double*, NoFact> fact
 #ifdef HOMMX_FUSED_DEBUG
@@ -93,8 +112,9 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 ) {
   constexpr int NT = NB / 16, KK = NB / 4, CG = 64 / NB;
   constexpr int P = MATP;
+  constexpr bool PARK = ISO && NB == 32;  // S_last lives in LDS between its uses (three waves per SIMD: 168 VGPRs)
   static_assert(!(FACT && ISO), "the factor record keeps the general path");
-  __shared__ Lds<NB> L;
+  __shared__ std::conditional_t<ISO, LdsIso<NB>, Lds<NB>> L;
 
   const long long cell = blockIdx.x;
   if (cell >= ncells) return;
@@ -121,7 +141,8 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
   }
 #define OWN(ti, tj, r) (ownB + (16 * (ti) + 4 * (r)) * P + 16 * (tj))
 #define LEFT(ti, tj, r) (leftB[tj] + (16 * (ti) + 4 * (r)) * P)
-  const unsigned matOff = accl::lds_offset(&L.mat[0]);
+  [[maybe_unused]] unsigned matOff = 0;
+  if constexpr (!ISO) matOff = accl::lds_offset(&L.mat[0]);
   [[maybe_unused]] const unsigned haloA = matOff + 8u * (unsigned)(p0 * P + j);  // halo row = row index p0 - 1: copy of row NB - 1
 
   // Coefficient source (kernels.h): the element stream coef[cell][2 n^2], or a device sampler fed by two numbers per cell
@@ -142,7 +163,8 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
   }
 
   // zero the staging matrix once
-  for (int i = l; i < (NB + 1) * P; i += 64) L.mat[i] = 0.0;
+  if constexpr (!ISO)
+    for (int i = l; i < (NB + 1) * P; i += 64) L.mat[i] = 0.0;
   if (l == 0) L.cenat[0] = 0.0;
 
   // ---- stratification matrix M = Dtheta^T(c_T) -> Q = M^T M (hmm.py:759-766) -------------------
@@ -245,15 +267,80 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
   // band matrices through the staging matrix: write the few non-zeros, read in acc layout, clear them again
   //   sym == true :  X[c][c] = dv, X[cp][c] = X[c][cp] = ov          (D blocks)
   //   sym == false:  X[c][c] = dv, X[cp][c] = ov                     (E: row cp couples to column c)
-  auto band_write = [&](double dv, double ov, bool sym, bool clear) {
-    if (g == 0) {
-      const double d_ = clear ? 0.0 : dv, o_ = clear ? 0.0 : ov;
-      L.mat[(c + 1) * P + c] = d_;
-      if (valid) {
-        L.mat[(cp + 1) * P + c] = o_;
-        if (sym) L.mat[(c + 1) * P + cp] = o_;
+  [[maybe_unused]] auto band_write = [&](double dv, double ov, bool sym, bool clear) {
+    if constexpr (!ISO) {
+      if (g == 0) {
+        const double d_ = clear ? 0.0 : dv, o_ = clear ? 0.0 : ov;
+        L.mat[(c + 1) * P + c] = d_;
+        if (valid) {
+          L.mat[(cp + 1) * P + c] = o_;
+          if (sym) L.mat[(c + 1) * P + cp] = o_;
+        }
       }
     }
+  };
+  // x -= band matrix of the acc layout, under literal exec masks: diagonal j = 4 r + k, sub-diagonal (row = col + 1) j = 4 r + k - 1,
+  // super-diagonal j = 4 r + k + 1.  dgq / ceq: diagonal and X[i+1][i] of the lane's column i = 16 tj + j; cemq: X[i-1][i]
+  auto sub_band = [&](double (&x)[NT][NT][4], const double (&dgq)[NT], const double (&ceq)[NT], const double (&cemq)[NT]) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      using namespace accl;
+#define DIAG_LO(r) (OneLane<0, 4 * (r)>::lo | OneLane<1, 4 * (r) + 1>::lo | OneLane<2, 4 * (r) + 2>::lo | OneLane<3, 4 * (r) + 3>::lo)
+#define DIAG_HI(r) (OneLane<0, 4 * (r)>::hi | OneLane<1, 4 * (r) + 1>::hi | OneLane<2, 4 * (r) + 2>::hi | OneLane<3, 4 * (r) + 3>::hi)
+      masked_sub4<DIAG_LO(0), DIAG_HI(0), DIAG_LO(1), DIAG_HI(1), DIAG_LO(2), DIAG_HI(2), DIAG_LO(3), DIAG_HI(3)>(
+          x[t][t][0], x[t][t][1], x[t][t][2], x[t][t][3], dgq[t]);
+      // sub-diagonal: lanes (j = 4 r + k - 1, k); for r = 0 lane row 0 has no such lane in this tile
+#define SUB_LO(r) (((r) ? OneLane<0, (4 * (r) - 1) & 15>::lo : 0u) | OneLane<1, 4 * (r)>::lo | OneLane<2, 4 * (r) + 1>::lo | OneLane<3, 4 * (r) + 2>::lo)
+#define SUB_HI(r) (((r) ? OneLane<0, (4 * (r) - 1) & 15>::hi : 0u) | OneLane<1, 4 * (r)>::hi | OneLane<2, 4 * (r) + 1>::hi | OneLane<3, 4 * (r) + 2>::hi)
+      masked_sub4<SUB_LO(0), SUB_HI(0), SUB_LO(1), SUB_HI(1), SUB_LO(2), SUB_HI(2), SUB_LO(3), SUB_HI(3)>(
+          x[t][t][0], x[t][t][1], x[t][t][2], x[t][t][3], ceq[t]);
+      // super-diagonal: lanes (j = 4 r + k + 1, k); for r = 3 lane row 3 has no such lane in this tile
+#define SUP_LO(r) (OneLane<0, 4 * (r) + 1>::lo | OneLane<1, 4 * (r) + 2>::lo | OneLane<2, 4 * (r) + 3>::lo | ((r) < 3 ? OneLane<3, (4 * (r) + 4) & 15>::lo : 0u))
+#define SUP_HI(r) (OneLane<0, 4 * (r) + 1>::hi | OneLane<1, 4 * (r) + 2>::hi | OneLane<2, 4 * (r) + 3>::hi | ((r) < 3 ? OneLane<3, (4 * (r) + 4) & 15>::hi : 0u))
+      masked_sub4<SUP_LO(0), SUP_HI(0), SUP_LO(1), SUP_HI(1), SUP_LO(2), SUP_HI(2), SUP_LO(3), SUP_HI(3)>(
+          x[t][t][0], x[t][t][1], x[t][t][2], x[t][t][3], cemq[t]);
+#undef DIAG_LO
+#undef DIAG_HI
+#undef SUB_LO
+#undef SUB_HI
+#undef SUP_LO
+#undef SUP_HI
+    }
+    if (NT == 2) {
+      using namespace accl;
+      // tile crossings: T[16][15] in (1, 0, r = 0) lane (j = 15, k = 0); T[15][16] in (0, 1, r = 3) lane (j = 0, k = 3)
+      masked_sub<OneLane<0, 15>::lo, OneLane<0, 15>::hi>(x[NT - 1][0][0], ceq[0]);
+      masked_sub<OneLane<3, 0>::lo, OneLane<3, 0>::hi>(x[0][NT - 1][3], cemq[NT - 1]);
+    }
+  };
+  // ISO: the same band matrices straight into zeroed registers.  x -= X with X[i][i] = dq, X[i+1][i] = X[i][i+1] = oq of column i and the
+  // wrap-around pair X[NB-1][p0] = X[p0][NB-1] = cw; dq / oq / omq are the values of the lane's column 16 tj + j and omq those of the column
+  // in front of it.  0 - (+-v) is exact, so the registers hold the bits the staging matrix delivered.  The wrap-around entries are lane
+  // selects, not products with a 0/1 selector: a NaN or Inf coefficient reaches the entries it reached through LDS and no others.
+  [[maybe_unused]] auto band_regs = [&](double (&x)[NT][NT][4], double dv, double ov) {
+    double dq[NT], oq[NT], omq[NT];
+#pragma unroll
+    for (int tj = 0; tj < NT; ++tj) {
+      const int col = 16 * tj + j;
+      dq[tj] = __shfl(dv, col, 64);  // (lane i < NB holds column i)
+      oq[tj] = __shfl(ov, col, 64);
+      const double om = __shfl(ov, (col + 63) & 63, 64);
+      omq[tj] = col == 0 ? 0.0 : om;
+    }
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+      for (int tj = 0; tj < NT; ++tj)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) x[ti][tj][r] = 0.0;
+    sub_band(x, dq, oq, omq);
+    const double cw = readlane_f64(ov, NB - 1);
+#pragma unroll
+    for (int tj = 0; tj < NT; ++tj) x[NT - 1][tj][3] = (k == 3 && 16 * tj + j == p0) ? x[NT - 1][tj][3] - cw : x[NT - 1][tj][3];
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) x[ti][NT - 1][r] = (j == 15 && 16 * ti + 4 * r + k == p0) ? x[ti][NT - 1][r] - cw : x[ti][NT - 1][r];
   };
 
   [[maybe_unused]] double* rec = nullptr;  // FACT: the record of this cell, and of the current step
@@ -285,6 +372,38 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
       if (l < 4) rec[4 * NB + l] = l == 0 ? m00 : l == 1 ? m01 : l == 2 ? m10 : m11;
       if (l == 4) rec[4 * NB + 4] = (double)esh;  // the magnitude exponent: a general load is of degree 1 in the scale (k_fused2d_subst_rhs)
     }
+    if constexpr (ISO) {
+      // S_last = D_{n-1} (lower tiles), T_0 = -D_0, and W_0 = E_{n-1}^T, which is diagonal here: in the operand layout its entries sit on the
+      // diagonal lanes of wf[t][kk] with kk >> 2 == t
+      band_regs(a, -st_diag(rowB, rowA), -st_E(rowB, rowA));
+#pragma unroll
+      for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int tj = 0; tj <= ti; ++tj)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) slr[ti][tj][r] = a[ti][tj][r];
+      if constexpr (PARK) {
+#pragma unroll
+        for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+          for (int tj = 0; tj <= ti; ++tj)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) L.park[(4 * (ti * (ti + 1) / 2 + tj) + r) * 64 + l] = slr[ti][tj][r];
+      }
+      band_regs(a, st_diag(cur, rowB), st_E(cur, rowB));
+      const double dv = st_N(rowB);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        using namespace accl;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) wf[t][kk] = 0.0;
+        const double dq = __shfl(dv, 16 * t + j, 64);
+        amov<DiagMask<0>::lo, DiagMask<0>::hi>(wf[t][4 * t], dq);
+        amov<DiagMask<1>::lo, DiagMask<1>::hi>(wf[t][4 * t + 1], dq);
+        amov<DiagMask<2>::lo, DiagMask<2>::hi>(wf[t][4 * t + 2], dq);
+        amov<DiagMask<3>::lo, DiagMask<3>::hi>(wf[t][4 * t + 3], dq);
+      }
+    } else {
     // S_last = D_{n-1}
     {
       const double dv = st_diag(rowB, rowA), ov = st_E(rowB, rowA);
@@ -328,16 +447,19 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
       band_write(dv, ov, true, true);
       __syncthreads();
     }
+    }  // !ISO
     rr[0] = st_p0(cur, rowB); rr[1] = st_p1(cur, rowB);                       // R_0
     rlm = (k >> 1) ? st_p1(rowB, rowA) : st_p0(rowB, rowA);                   // R_last
   }
   double ga_ = 0.0, gb_ = 0.0;  // -G partial sums: lane rows 0,1: (G00, G01); lane rows 2,3: (G10, G11)
   int bad = 0, badstep = 0;
   // wrap-around entries of D (first real index <-> last index): per-lane selectors
-  double wselR[NT];  // 1 on the lane holding T[NB-1][p0] in register (NT-1, tj, 3)
+  [[maybe_unused]] double wselR[NT];  // 1 on the lane holding T[NB-1][p0] in register (NT-1, tj, 3)
 #pragma unroll
   for (int tj = 0; tj < NT; ++tj) wselR[tj] = (k == 3 && 16 * tj + j == p0) ? 1.0 : 0.0;
-  const double wselC = (j == 15 && k == (p0 & 3)) ? 1.0 : 0.0;  // lane holding T[p0][NB-1] in register (p0/16, NT-1, (p0%16)/4)
+  [[maybe_unused]] const double wselC = (j == 15 && k == (p0 & 3)) ? 1.0 : 0.0;  // lane holding T[p0][NB-1] in register (p0/16, NT-1, (p0%16)/4)
+  // ISO: lane predicates instead (a select between the product with 1 and the product with 0: the same bits, no selector registers)
+  [[maybe_unused]] const int laneR = 48 + (p0 & 15), tileR = p0 >> 4, laneC = 16 * (p0 & 3) + 15;
   double indw[KK];  // wave-uniform 0/1: which (tile row, register) of column tile NT-1 holds row p0
 #pragma unroll
   for (int q = 0; q < KK; ++q) indw[q] = uniform_f64((q == (p0 >> 2)) ? 1.0 : 0.0);
@@ -360,22 +482,35 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
     }
     if (lastStep) {
       // the last node row couples to row n-2 through E as well as through the arrow: W += E, i.e. W^T += E^T
-      for (int i = l; i < (NB + 1) * P; i += 64) L.mat[i] = 0.0;
-      __syncthreads();
-      if (g == 0) {
-        L.mat[(c + 1) * P + c] = e0c;
-        if constexpr (!ISO) {
+      if constexpr (ISO) {  // E is diagonal: an add on the diagonal lanes (x - (-e) == x + e)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          using namespace accl;
+          const double me = -__shfl(e0c, 16 * t + j, 64);
+          masked_sub4<DiagMask<0>::lo, DiagMask<0>::hi, DiagMask<1>::lo, DiagMask<1>::hi, DiagMask<2>::lo, DiagMask<2>::hi, DiagMask<3>::lo,
+                      DiagMask<3>::hi>(wf[t][4 * t], wf[t][4 * t + 1], wf[t][4 * t + 2], wf[t][4 * t + 3], me);
+        }
+      } else {
+        for (int i = l; i < (NB + 1) * P; i += 64) L.mat[i] = 0.0;
+        __syncthreads();
+        if (g == 0) {
+          L.mat[(c + 1) * P + c] = e0c;
           if (valid) L.mat[(c + 1) * P + cp] = neC;  // E^T[c][cp] = E[cp][c]
         }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+          for (int kk = 0; kk < KK; ++kk) wf[t][kk] += L.mat[OWN(kk >> 2, t, kk & 3)];
+        __syncthreads();
       }
-      __syncthreads();
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) wf[t][kk] += L.mat[OWN(kk >> 2, t, kk & 3)];
-      __syncthreads();
     }
     // next block's diagonal data
+    [[maybe_unused]] double pn0 = 0.0, pn1 = 0.0;  // ISO: P_{j+1} here, where cur is last read: one coefficient line less in registers over the step
+    if constexpr (ISO) {
+      pn0 = st_p0(nxt, cur);
+      pn1 = st_p1(nxt, cur);
+    }
     const double dgc = st_diag(nxt, cur), cec = st_E(nxt, cur);
     if (g == 0) {
       L.rrow[0][prow] = rr[0];
@@ -431,7 +566,7 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
     }
 #endif
 
-    if (!ISO && !lastStep) {
+    if constexpr (!ISO) if (!lastStep) {
       // (2) N -> staging matrix (for T_next), with the halo copy of row NB-1 in front of the first real row (ISO: T_next reads no neighbour)
 #pragma unroll
       for (int ti = 0; ti < NT; ++ti)
@@ -459,6 +594,21 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
           vt[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk >> 2][x][kk & 3], wf[y][kk], vt[x][y], 0, 0, 0);
 
     // (4) S_last += V' W^T: symmetric, tiles on and below the diagonal only
+    if constexpr (PARK) {  // tile after tile out of LDS and back: four accumulator registers live instead of twelve, per tile the same chain
+#pragma unroll
+      for (int x = 0; x < NT; ++x)
+#pragma unroll
+        for (int y = 0; y <= x; ++y) {
+          double* pk = &L.park[4 * (x * (x + 1) / 2 + y) * 64 + l];
+          d4 s;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s[r] = pk[64 * r];
+#pragma unroll
+          for (int kk = 0; kk < KK; ++kk) s = __builtin_amdgcn_mfma_f64_16x16x4f64(vt[kk >> 2][x][kk & 3], wf[y][kk], s, 0, 0, 0);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) pk[64 * r] = s[r];
+        }
+    } else {
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk)
 #pragma unroll
@@ -466,6 +616,7 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 #pragma unroll
         for (int y = 0; y <= x; ++y)
           slr[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(vt[kk >> 2][x][kk & 3], wf[y][kk], slr[x][y], 0, 0, 0);
+    }
 
     // (5) Vr' = R N: partial sums over the lane's rows, transposing butterfly over the four lane rows
     //     -> lane row k holds Vr'[k >> 1][column c]
@@ -502,8 +653,13 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
         z = add_xor16(x + y);
       }
     }
-    ga_ = fma(z, rr[0], ga_);
-    gb_ = fma(z, rr[1], gb_);
+    if constexpr (ISO) {  // R of this block from its row-layout copy: rr holds no registers across the sweep and the products
+      ga_ = fma(z, L.rrow[0][prow], ga_);
+      gb_ = fma(z, L.rrow[1][prow], gb_);
+    } else {
+      ga_ = fma(z, rr[0], ga_);
+      gb_ = fma(z, rr[1], gb_);
+    }
     L.vnat[k >> 1][c] = z;
     L.vrow[k >> 1][prow] = z;
     if constexpr (FACT) {  // N'_j r~_j, both load cases (NB = 16: lane rows 2 m and 2 m + 1 hold the same values)
@@ -551,14 +707,11 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 
     if (!lastStep) {
       // row-layout coupling coefficients: e0r[kk] = E[i][i], e1r[kk] = E[i][i-1] at i = 4 kk + k = 16 ti + 4 r + k
-      double e0r[KK];
+      [[maybe_unused]] double e0r[KK];
       [[maybe_unused]] double e1r[KK];
 #pragma unroll
       for (int q4 = 0; q4 < KK; q4 += 4) {
-        if constexpr (ISO) {  // (a branch of its own: the general one keeps its statement order, and with it the code it compiled to)
-          const d4 x = *reinterpret_cast<const d4*>(&L.e0row[k * KK + q4]);
-          e0r[q4] = x[0]; e0r[q4 + 1] = x[1]; e0r[q4 + 2] = x[2]; e0r[q4 + 3] = x[3];
-        } else {
+        if constexpr (!ISO) {  // (ISO reads e0row where it uses it: no sixteen registers held across (8) and (7))
           const d4 x = *reinterpret_cast<const d4*>(&L.e0row[k * KK + q4]);
           const d4 y = *reinterpret_cast<const d4*>(&L.e1row[k * KK + q4]);
           e0r[q4] = x[0]; e0r[q4 + 1] = x[1]; e0r[q4 + 2] = x[2]; e0r[q4 + 3] = x[3];
@@ -586,7 +739,7 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 #pragma unroll
             for (int tj = 0; tj < NT; ++tj) {
               if constexpr (ISO) {
-                a[ti][tj][r] = -(e0r[4 * ti + r] * (e0q[tj] * a[ti][tj][r]));
+                a[ti][tj][r] = -(L.e0row[k * KK + 4 * ti + r] * (e0q[tj] * a[ti][tj][r]));
               } else {
                 const double nl = L.mat[LEFT(ti, tj, r)];
                 const double nu = L.mat[OWN(ti, tj, r) - P];
@@ -596,43 +749,19 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
                 a[ti][tj][r] = -fma(e0r[4 * ti + r], x, e1r[4 * ti + r] * xu);
               }
             }
-        // band of -D_{j+1}: diagonal j = 4 r + k, sub-diagonal (row = col + 1) j = 4 r + k - 1, super-diagonal j = 4 r + k + 1
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          using namespace accl;
-#define DIAG_LO(r) (OneLane<0, 4 * (r)>::lo | OneLane<1, 4 * (r) + 1>::lo | OneLane<2, 4 * (r) + 2>::lo | OneLane<3, 4 * (r) + 3>::lo)
-#define DIAG_HI(r) (OneLane<0, 4 * (r)>::hi | OneLane<1, 4 * (r) + 1>::hi | OneLane<2, 4 * (r) + 2>::hi | OneLane<3, 4 * (r) + 3>::hi)
-          masked_sub4<DIAG_LO(0), DIAG_HI(0), DIAG_LO(1), DIAG_HI(1), DIAG_LO(2), DIAG_HI(2), DIAG_LO(3), DIAG_HI(3)>(
-              a[t][t][0], a[t][t][1], a[t][t][2], a[t][t][3], dgq[t]);
-          // sub-diagonal: lanes (j = 4 r + k - 1, k); for r = 0 lane row 0 has no such lane in this tile
-#define SUB_LO(r) (((r) ? OneLane<0, (4 * (r) - 1) & 15>::lo : 0u) | OneLane<1, 4 * (r)>::lo | OneLane<2, 4 * (r) + 1>::lo | OneLane<3, 4 * (r) + 2>::lo)
-#define SUB_HI(r) (((r) ? OneLane<0, (4 * (r) - 1) & 15>::hi : 0u) | OneLane<1, 4 * (r)>::hi | OneLane<2, 4 * (r) + 1>::hi | OneLane<3, 4 * (r) + 2>::hi)
-          masked_sub4<SUB_LO(0), SUB_HI(0), SUB_LO(1), SUB_HI(1), SUB_LO(2), SUB_HI(2), SUB_LO(3), SUB_HI(3)>(
-              a[t][t][0], a[t][t][1], a[t][t][2], a[t][t][3], ceq[t]);
-          // super-diagonal: lanes (j = 4 r + k + 1, k); for r = 3 lane row 3 has no such lane in this tile
-#define SUP_LO(r) (OneLane<0, 4 * (r) + 1>::lo | OneLane<1, 4 * (r) + 2>::lo | OneLane<2, 4 * (r) + 3>::lo | ((r) < 3 ? OneLane<3, (4 * (r) + 4) & 15>::lo : 0u))
-#define SUP_HI(r) (OneLane<0, 4 * (r) + 1>::hi | OneLane<1, 4 * (r) + 2>::hi | OneLane<2, 4 * (r) + 3>::hi | ((r) < 3 ? OneLane<3, (4 * (r) + 4) & 15>::hi : 0u))
-          masked_sub4<SUP_LO(0), SUP_HI(0), SUP_LO(1), SUP_HI(1), SUP_LO(2), SUP_HI(2), SUP_LO(3), SUP_HI(3)>(
-              a[t][t][0], a[t][t][1], a[t][t][2], a[t][t][3], cemq[t]);
-#undef DIAG_LO
-#undef DIAG_HI
-#undef SUB_LO
-#undef SUB_HI
-#undef SUP_LO
-#undef SUP_HI
-        }
-        if (NT == 2) {
-          using namespace accl;
-          // tile crossings: T[16][15] in (1, 0, r = 0) lane (j = 15, k = 0); T[15][16] in (0, 1, r = 3) lane (j = 0, k = 3)
-          masked_sub<OneLane<0, 15>::lo, OneLane<0, 15>::hi>(a[NT - 1][0][0], ceq[0]);
-          masked_sub<OneLane<3, 0>::lo, OneLane<3, 0>::hi>(a[0][NT - 1][3], cemq[NT - 1]);
-        }
+        // band of -D_{j+1}
+        sub_band(a, dgq, ceq, cemq);
         // wrap-around entries D[p0][NB-1] = D[NB-1][p0] = coupling of the last real column to the first
         {
           const double cw = readlane_f64(cec, NB - 1);
 #pragma unroll
-          for (int tj = 0; tj < NT; ++tj) a[NT - 1][tj][3] = fma(-cw, wselR[tj], a[NT - 1][tj][3]);
-          const double vcol = -cw * wselC;
+          for (int tj = 0; tj < NT; ++tj) {
+            if constexpr (ISO) a[NT - 1][tj][3] = (l == laneR && tj == tileR) ? fma(-cw, 1.0, a[NT - 1][tj][3]) : fma(-cw, 0.0, a[NT - 1][tj][3]);
+            else a[NT - 1][tj][3] = fma(-cw, wselR[tj], a[NT - 1][tj][3]);
+          }
+          double vcol;
+          if constexpr (ISO) vcol = l == laneC ? -cw : -cw * 0.0;
+          else vcol = -cw * wselC;
 #pragma unroll
           for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
@@ -644,9 +773,9 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
       //     in the registers)
       if constexpr (ISO) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t)
+        for (int kk = 0; kk < KK; ++kk)
 #pragma unroll
-          for (int kk = 0; kk < KK; ++kk) wf[t][kk] = e0r[kk] * vt[kk >> 2][t][kk & 3];
+          for (int t = 0; t < NT; ++t) wf[t][kk] = L.e0row[k * KK + kk] * vt[kk >> 2][t][kk & 3];
       } else {
 #pragma unroll
         for (int x = 0; x < NT; ++x)
@@ -670,8 +799,9 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
       {
         const double v0 = L.vnat[0][c], v1 = L.vnat[1][c];
         if constexpr (ISO) {
-          rr[0] = fma(v0, e0c, st_p0(nxt, cur));
-          rr[1] = fma(v1, e0c, st_p1(nxt, cur));
+          const double e0 = L.e0nat[c];  // == e0c
+          rr[0] = fma(v0, e0, pn0);
+          rr[1] = fma(v1, e0, pn1);
         } else {
           const double vm0 = L.vnat[0][cm], vm1 = L.vnat[1][cm];
           rr[0] = fma(vm0, e1c, fma(v0, e0c, st_p0(nxt, cur)));
@@ -683,13 +813,43 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
     }
   }
 
+  // ISO: the tail takes its lane indices from a fresh copy of the lane id, so that neither they nor the shuffle addresses of its reductions
+  // (the same as those of the magnitude pass at the top) are held in vector registers across the elimination loop
+  int lt = l, jt = j, kt = k, ct = c, prowt = prow;
+  if constexpr (ISO) {
+    lt = (int)__lane_id();  // (one wave per workgroup: the lane id is threadIdx.x)
+    asm volatile("" : "+v"(lt));
+    jt = lt & 15;
+    kt = lt >> 4;
+    ct = lt % NB;
+    prowt = (ct & 3) * KK + (ct >> 2);
+  }
+  {
+  const int l = lt, j = jt, k = kt, c = ct, prow = prowt;
+  [[maybe_unused]] auto bfly = [&](double v, int off) {  // ISO's __shfl_xor(v, off, 64), its address made from the fresh lane id
+    const int ad = (l ^ off) << 2;
+    return __hiloint2double(__builtin_amdgcn_ds_bpermute(ad, __double2hiint(v)), __builtin_amdgcn_ds_bpermute(ad, __double2loint(v)));
+  };
   // ---- last node row: T_last = -S_last, pin node (n-1, n-1), sweep ------------------------------------
   {
     // upper tile = transpose of the lower one, through the staging matrix
-    if (NT == 2) {
+    if constexpr (PARK) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) L.mat[OWN(1, 0, r)] = slr[NT - 1][0][r];
-      __syncthreads();
+      for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int tj = 0; tj <= ti; ++tj)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) slr[ti][tj][r] = L.park[(4 * (ti * (ti + 1) / 2 + tj) + r) * 64 + l];
+    }
+    [[maybe_unused]] d4 sup = d4{0.0, 0.0, 0.0, 0.0};  // ISO: the upper tile, by the tile transpose of the block inverse
+    if (NT == 2) {
+      if constexpr (ISO) {
+        sup = accl::transpose_tile(slr[NT - 1][0], L.tsc, j, k);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) L.mat[OWN(1, 0, r)] = slr[NT - 1][0][r];
+        __syncthreads();
+      }
     }
 #pragma unroll
     for (int ti = 0; ti < NT; ++ti)
@@ -698,6 +858,7 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           if (tj <= ti) a[ti][tj][r] = -slr[ti][tj][r];
+          else if constexpr (ISO) a[ti][tj][r] = -sup[r];
           else a[ti][tj][r] = -L.mat[(16 + j + 1) * P + 4 * r + k];  // S[4r+k][16+j] = S[16+j][4r+k]
         }
     // gauge: drop the last unknown (cell_problem.py:349-361): row / column NB-1 <- 0, diagonal <- -1
@@ -769,10 +930,17 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
   double g00 = (k < 2) ? ga_ : 0.0, g01 = (k < 2) ? gb_ : 0.0, g11 = (k < 2) ? 0.0 : gb_;
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {
-    g00 += __shfl_xor(g00, off, 64);
-    g01 += __shfl_xor(g01, off, 64);
-    g11 += __shfl_xor(g11, off, 64);
-    asum += __shfl_xor(asum, off, 64);
+    if constexpr (ISO) {
+      g00 += bfly(g00, off);
+      g01 += bfly(g01, off);
+      g11 += bfly(g11, off);
+      asum += bfly(asum, off);
+    } else {
+      g00 += __shfl_xor(g00, off, 64);
+      g01 += __shfl_xor(g01, off, 64);
+      g11 += __shfl_xor(g11, off, 64);
+      asum += __shfl_xor(asum, off, 64);
+    }
   }
   if (l == 0) {
     const double h = 1.0 / n;
@@ -789,6 +957,7 @@ __global__ __launch_bounds__(64, HOMMX_FUSED_WAVES_PER_SIMD) void k_poisson2d_fu
     o[3] = ldexp(c0 + sc * (t10 * m10 + t11 * m11), esh);
     if (info) info[cell] = bad ? badstep : 0;
   }
+  }  // tail
 #undef OWN
 #undef LEFT
 }
