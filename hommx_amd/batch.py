@@ -394,6 +394,35 @@ class MicroCellPlan:
             _lib.check(call(Mp, out.ctypes.data, info.ctypes.data), what)
         return (out, info) if return_info else out
 
+    def _source_call(self, what: str, nc: int, M, stream: "CoefStream", args):
+        """``_host_call`` of a host entry point that takes (plan, N_c, source, M, argument struct): A_eff and info go into ``args``."""
+        src = stream.coef_source()
+
+        def call(Mp, o, i):
+            args.A_eff, args.info = o, i
+            return getattr(self._lib, what)(self._h, nc, C.byref(src), Mp, C.byref(args))
+
+        return self._host_call(what, nc, M, call)
+
+    def _check_directions(self, directions, nc: int, per_cell: bool) -> tuple[np.ndarray, int]:
+        """directions[(N_c,) n_dirs, n_el(, n_comp)] as float64 -> (directions, n_dirs)."""
+        el = (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
+        dirs = np.ascontiguousarray(directions, dtype=np.float64)
+        lead = ((nc,) if per_cell else ())
+        nd = dirs.shape[len(lead)] if dirs.ndim == len(lead) + 1 + len(el) else -1
+        if nd < 0 or dirs.shape != lead + (nd,) + el:
+            raise ValueError(f"directions has shape {dirs.shape}; expected {lead + ('n_dirs',) + el}")
+        if not 1 <= nd <= _lib.SENS_MAX_DIRS:
+            raise ValueError(f"n_dirs must be 1 .. {_lib.SENS_MAX_DIRS}; got {nd}")
+        return dirs, nd
+
+    def _check_weights(self, weights, nc: int) -> np.ndarray:
+        """weights[N_c, t, t] as float64."""
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if weights.shape != (nc, self.t, self.t):
+            raise ValueError(f"weights has shape {weights.shape}; expected ({nc}, {self.t}, {self.t})")
+        return weights
+
     def solve(self, coef: np.ndarray, M: np.ndarray | None = None, return_info: bool = False,
               return_correctors: bool = False):
         """coef[N_c, n_el(, n_comp)] float64, M[N_c, d, d] or None -> A_eff[N_c, t, t] (and info[N_c]).
@@ -485,31 +514,17 @@ class MicroCellPlan:
         el = (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
         nd, dirs = 0, None
         if directions is not None:
-            dirs = np.ascontiguousarray(directions, dtype=np.float64)
-            lead = ((nc,) if per_cell else ())
-            nd = dirs.shape[len(lead)] if dirs.ndim == len(lead) + 1 + len(el) else -1
-            if nd < 0 or dirs.shape != lead + (nd,) + el:
-                raise ValueError(f"directions has shape {dirs.shape}; expected {lead + ('n_dirs',) + el}")
-            if not 1 <= nd <= _lib.SENS_MAX_DIRS:
-                raise ValueError(f"n_dirs must be 1 .. {_lib.SENS_MAX_DIRS}; got {nd}")
+            dirs, nd = self._check_directions(directions, nc, per_cell)
         grad = None
         if weights is not None:
-            weights = np.ascontiguousarray(weights, dtype=np.float64)
-            if weights.shape != (nc, self.t, self.t):
-                raise ValueError(f"weights has shape {weights.shape}; expected ({nc}, {self.t}, {self.t})")
+            weights = self._check_weights(weights, nc)
             grad = np.empty((nc,) + el, dtype=np.float64)
         elif nd == 0:
             raise ValueError("nothing requested: pass directions, weights or both")
         dA = np.empty((nc, nd, self.t, self.t), dtype=np.float64)
-        src = stream.coef_source()
         args = _lib.SensArgs(nd, int(bool(per_cell)), dirs.ctypes.data if nd else None, dA.ctypes.data if nd else None,
                              None if grad is None else weights.ctypes.data, None if grad is None else grad.ctypes.data)
-
-        def call(Mp, o, i):
-            args.A_eff, args.info = o, i
-            return self._lib.hommx_sensitivity_source(self._h, nc, C.byref(src), Mp, C.byref(args))
-
-        A, info = self._host_call("hommx_sensitivity_source", nc, M, call)
+        A, info = self._source_call("hommx_sensitivity_source", nc, M, stream, args)
         return Sensitivities(dA, grad, A, info)
 
     def second_sensitivities(self, coef, M: np.ndarray | None = None, directions=None, per_cell: bool = False,
@@ -522,26 +537,13 @@ class MicroCellPlan:
         the chunks of ``reconstruct``."""
         stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
         nc = self._check_stream(stream)
-        el = (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
         if directions is None:
             raise ValueError("directions is required")
-        dirs = np.ascontiguousarray(directions, dtype=np.float64)
-        lead = ((nc,) if per_cell else ())
-        nd = dirs.shape[len(lead)] if dirs.ndim == len(lead) + 1 + len(el) else -1
-        if nd < 0 or dirs.shape != lead + (nd,) + el:
-            raise ValueError(f"directions has shape {dirs.shape}; expected {lead + ('n_dirs',) + el}")
-        if not 1 <= nd <= _lib.SENS_MAX_DIRS:
-            raise ValueError(f"n_dirs must be 1 .. {_lib.SENS_MAX_DIRS}; got {nd}")
+        dirs, nd = self._check_directions(directions, nc, per_cell)
         d2A = np.empty((nc, nd, nd, self.t, self.t), dtype=np.float64)
         dA = np.empty((nc, nd, self.t, self.t), dtype=np.float64) if first else None
-        src = stream.coef_source()
         args = _lib.Sens2Args(nd, int(bool(per_cell)), dirs.ctypes.data, d2A.ctypes.data, dA.ctypes.data if first else None)
-
-        def call(Mp, o, i):
-            args.A_eff, args.info = o, i
-            return self._lib.hommx_second_sensitivity_source(self._h, nc, C.byref(src), Mp, C.byref(args))
-
-        A, info = self._host_call("hommx_second_sensitivity_source", nc, M, call)
+        A, info = self._source_call("hommx_second_sensitivity_source", nc, M, stream, args)
         return SecondSensitivities(d2A, dA, A, info)
 
     def stratification_sensitivities(self, coef, M: np.ndarray | None = None, weights=None, full: bool = True) -> StratSensitivities:
@@ -554,22 +556,14 @@ class MicroCellPlan:
         nc = self._check_stream(stream)
         grad = None
         if weights is not None:
-            weights = np.ascontiguousarray(weights, dtype=np.float64)
-            if weights.shape != (nc, self.t, self.t):
-                raise ValueError(f"weights has shape {weights.shape}; expected ({nc}, {self.t}, {self.t})")
+            weights = self._check_weights(weights, nc)
             grad = np.empty((nc, self.dim, self.dim), dtype=np.float64)
         elif not full:
             raise ValueError("nothing requested: pass weights, full=True or both")
         dA_dM = np.empty((nc, self.dim, self.dim, self.t, self.t), dtype=np.float64) if full else None
-        src = stream.coef_source()
         args = _lib.StratSensArgs(dA_dM.ctypes.data if full else None, None if grad is None else weights.ctypes.data,
                                   None if grad is None else grad.ctypes.data)
-
-        def call(Mp, o, i):
-            args.A_eff, args.info = o, i
-            return self._lib.hommx_stratification_sensitivity_source(self._h, nc, C.byref(src), Mp, C.byref(args))
-
-        A, info = self._host_call("hommx_stratification_sensitivity_source", nc, M, call)
+        A, info = self._source_call("hommx_stratification_sensitivity_source", nc, M, stream, args)
         return StratSensitivities(dA_dM, grad, A, info)
 
     def loads(self, coef, P, M: np.ndarray | None = None, per_cell: bool | None = None, response: bool = False, fields: bool = False,
@@ -601,15 +595,9 @@ class MicroCellPlan:
         flux = np.empty((nc, nl, self.n_el, self.t), dtype=np.float64) if fields else None
         corr = np.empty((nc, nl, self.n_nodes * bs), dtype=np.float64) if return_correctors else None
         addr = lambda a: None if a is None else a.ctypes.data
-        src = stream.coef_source()
         args = _lib.LoadArgs(nl, int(bool(per_cell)), P.ctypes.data, P_eff.ctypes.data, None, addr(energy), addr(stats), addr(strain), addr(flux),
                              addr(corr), None)
-
-        def call(Mp, o, i):
-            args.A_eff, args.info = o, i
-            return self._lib.hommx_loads_source(self._h, nc, C.byref(src), Mp, C.byref(args))
-
-        A, info = self._host_call("hommx_loads_source", nc, M, call)
+        A, info = self._source_call("hommx_loads_source", nc, M, stream, args)
         r = LoadResponse(P_eff, A, info, energy, strain=strain, flux=flux, correctors=corr)
         if response:
             r.mean_flux, r.max_flux = stats[:, :, :self.t].copy(), stats[:, :, self.t].copy()

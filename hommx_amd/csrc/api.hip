@@ -102,7 +102,7 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 }
 
 // The plan-owned buffers, grown on demand, never per call.  B_IN / B_OUT: the device block of the per-cell inputs / outputs of a host
-// entry point (hommx_solve_batch: the batch; recon_host: one chunk).  B_EXPAND: the expanded element stream of the sampler forms.
+// entry point (hommx_solve_batch: the batch; derived_call: one chunk).  B_EXPAND: the expanded element stream of the sampler forms.
 // B_PIN_* / B_DEV_*: the small inputs of the sampler host entry points and their outputs, pinned host mirrors + device (plan_new pins).
 // B_RCORR, B_RA: the correctors of one reconstruction chunk (and the chi^xi slots of cells too large for LDS), A_eff the caller did not ask for
 // B_FACT: the factor records of one chunk of a fused 2D plan's corrector route (kernels.h)
@@ -720,18 +720,6 @@ int64_t load_chunk(const hommx_plan* p, int64_t n_cells, size_t extra) {
   return std::min<int64_t>(recon_chunk(p, n_cells, extra + hommx::mesh_arena_bytes_per_cell(p->mesh)), hommx::mesh_arena_chunk(p->mesh, n_cells));
 }
 
-// device pointers of one chunk of a reconstruction
-struct ReconIO {
-  const double *coef, *M, *xi;
-  double *stats, *region_stats, *strain, *flux, *A_eff;
-  int32_t* info;
-};
-// the regions of a call: how many, and the label of every element on the device
-struct ReconRegions {
-  int32_t n = 0;
-  const uint8_t* label = nullptr;
-};
-
 // The correctors of one chunk (nc of at most `chunk` cells) through the plan's route into its scratch, with room for `slots` more vectors
 // of ndof per cell behind them; A_eff into *d_A_eff or, if that is null, into the plan's own array (*d_A_eff then names it)
 int chunk_correctors(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_coef, const double* d_M, double** d_A_eff, int32_t* d_info,
@@ -763,24 +751,154 @@ void set_geometry(const hommx_plan* p, Args& a) {
   }
 }
 
+// -- the derived outputs: one chunk driver under reconstruction, first derivatives, stratification, loads, second derivatives -------------
+// One per-cell array of a call.  `slot` is a pointer member of the chunk's view (Chunk::a, a copy of the caller's argument struct): it
+// holds the caller's pointer when the call starts (null: absent, as is an array of n == 0) and receives the chunk's device pointer.
+// n: elements of `elem` bytes per cell.  SHARED (an input, at most one per call): one array of n elements serves every cell.  KEPT (an
+// output): it has room in a host call's B_OUT even if the caller does not ask for it (A_eff, info).
+enum ArrayKind { PER_CELL, SHARED, KEPT };
+struct CellArray {
+  void* slot;
+  int64_t n;
+  ArrayKind kind = PER_CELL;
+  size_t elem = sizeof(double);
+  char* get() const {
+    char* q;
+    memcpy(&q, slot, sizeof(q));
+    return q;
+  }
+  void set(const void* q) const { memcpy(slot, &q, sizeof(q)); }
+};
+
+// what a family's run sees of one chunk: the element stream and M of its cells, the source on the device (for what every cell shares),
+// and the caller's arguments with every pointer re-based to the chunk
+template <typename Args>
+struct Chunk {
+  const double *coef, *M;
+  const hommx_coef_source* src;
+  Args a;
+};
+
+using ChunkRule = int64_t (*)(const hommx_plan*, int64_t, size_t);  // recon_chunk or load_chunk
+
+// The chunk loop of every derived output.  v.a holds the caller's arguments; `ins` / `outs` list its per-cell arrays in the order of the
+// blocks of B_IN = [coef | M | ins] and B_OUT = [outs | info]; `scratch`: bytes per cell a chunk holds beside the canonical correctors.
+// Per chunk of cells [c0, c0 + nc): every slot is re-based, expand_chunk gives the element stream of a sampler form, run(nc, chunk, v) forms
+// the correctors and launches the family's kernels.
+// device: the slots become views of the caller's arrays (pointer + c0 * n; a shared input as it is), everything on `st`, no copy and no
+// synchronisation.
+// host: what every cell shares (mask, table, weights of the source, the shared input) and the per-cell values of a sampler form travel
+// once, in the plan's pinned block (stage_source); the other inputs stream into B_IN and the outputs the caller asked for stream out of
+// B_OUT chunk by chunk, so device memory is bounded by the chunk, whose bytes per cell count both blocks
+template <typename Args, size_t NI, size_t NO, typename Run>
+int derived_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, Chunk<Args>& v, const CellArray (&ins)[NI],
+                 const CellArray (&outs)[NO], int32_t** info, size_t scratch, ChunkRule rule, bool device, hipStream_t st, Run run) {
+  constexpr size_t N[2] = {NI + 2, NO + 1};
+  constexpr size_t NMAX = std::max(N[0], N[1]);
+  v.coef = s.coef;
+  v.M = M;
+  CellArray tab[2][NMAX] = {{{&v.coef, s.form == HOMMX_COEF_SAMPLED ? p->n_el * p->ks.n_comp : 0}, {&v.M, p->desc.dim * p->desc.dim}}, {}};
+  std::copy(ins, ins + NI, tab[0] + 2);
+  std::copy(outs, outs + NO, tab[1]);
+  tab[1][NO] = CellArray{info, 1, KEPT, sizeof(int32_t)};
+  // the caller's pointers, and the bytes per cell of those that take room in a chunk
+  char* user[2][NMAX];
+  size_t cell[2][NMAX], per_cell = scratch;
+  const CellArray* shared = nullptr;
+  for (int io = 0; io < 2; ++io)
+    for (size_t k = 0; k < N[io]; ++k) {
+      const CellArray& c = tab[io][k];
+      user[io][k] = c.get();
+      if (c.kind == SHARED) shared = &c;
+      cell[io][k] = c.kind != SHARED && (user[io][k] || c.kind == KEPT) ? c.elem * c.n : 0;
+      per_cell += cell[io][k];
+    }
+  hommx_coef_source ds = s;
+  char* dev[2][NMAX] = {};
+  int64_t chunk = 0;
+  if (device) {
+    if (int rc = stream_chunk(p, s, rule(p, n_cells, scratch), &chunk)) return rc;
+  } else {
+    const void* d_shared = nullptr;
+    const hommx::HostPiece more{shared ? shared->get() : nullptr, shared ? shared->elem * shared->n : 0, &d_shared};
+    if (int rc = stage_source(p, n_cells, s, more, &ds)) return rc;
+    if (shared) shared->set(d_shared);
+    if (int rc = stream_chunk(p, s, rule(p, n_cells, per_cell), &chunk)) return rc;
+    for (int io = 0; io < 2; ++io) {
+      size_t bytes[NMAX] = {};
+      for (size_t k = 0; k < N[io]; ++k) bytes[k] = cell[io][k] * chunk;
+      if (int rc = carve(p->buf[io ? B_OUT : B_IN], bytes, dev[io])) return rc;
+    }
+  }
+  v.src = &ds;
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    const int64_t nc = std::min(chunk, n_cells - c0);
+    for (int io = 0; io < 2; ++io)
+      for (size_t k = 0; k < N[io]; ++k) {
+        if (tab[io][k].kind == SHARED) continue;
+        char* at = !cell[io][k] ? nullptr : device ? (user[io][k] ? user[io][k] + c0 * cell[io][k] : nullptr) : dev[io][k];
+        tab[io][k].set(at);
+        if (!device && !io && at) HIP_TRY(hipMemcpy(at, user[io][k] + c0 * cell[io][k], nc * cell[io][k], hipMemcpyHostToDevice));
+      }
+    if (!v.coef)
+      if (int rc = expand_chunk(p, ds, c0, nc, st, &v.coef)) return rc;
+    if (int rc = run(nc, chunk, v)) return rc;
+    if (device) continue;
+    for (size_t k = 0; k < N[1]; ++k)
+      if (cell[1][k] && user[1][k]) HIP_TRY(hipMemcpy(user[1][k] + c0 * cell[1][k], dev[1][k], nc * cell[1][k], hipMemcpyDeviceToHost));
+  }
+  return HOMMX_OK;
+}
+
+// what opens both entry points of a family that takes a source and an argument struct: the source, the struct, `checks` of the struct
+// against the plan's descriptor (open_call), then a route that forms correctors
+template <typename Args, typename Checks>
+int source_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const Args* a, bool device, Checks checks) {
+  auto more = [&] {
+    if (int rc = coef_check(p, src)) return rc;
+    if (!a) return fail(HOMMX_EINVAL, "null arguments");
+    return checks();
+  };
+  if (int rc = open_call(p, n_cells, true, "", device, more); rc != GO) return rc;
+  if (int rc = corrector_workspace(p)) return rc;
+  return GO;
+}
+
+// the blocked workspace of a fused 2D plan whose load solve does not run on its own records (HOMMX_FUSED_LOADS=0 / HOMMX_FUSED_CORR=0)
+int load_workspace(hommx_plan* p) {
+  if (p->ws || fused_loads(p) || mesh_loads(p)) return HOMMX_OK;
+  int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
+  return rc ? prefix_error(rc, "blocked path: ") : HOMMX_OK;
+}
+
+// -- reconstruction (hommx_reconstruct_batch[_device], hommx_reconstruct_source[_device]) ------------------------------------------------
+// the arguments of a reconstruction beside the source and M (these entry points have no public struct); region: the label of every element
+struct ReconCall {
+  const double* xi;
+  int32_t n_regions;
+  const uint8_t* region;
+  double *stats, *region_stats, *strain, *flux, *A_eff;
+  int32_t* info;
+};
+
 // one chunk of at most recon_chunk() cells on the device: the correctors into the plan's scratch, then k_recon
-int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const ReconIO& io, ReconRegions rg, hipStream_t st) {
+int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<ReconCall>& v, hipStream_t st) {
   const bool lds = recon_in_lds(p);
-  double *d_A_eff = io.A_eff, *corr = nullptr;
-  if (int rc = chunk_correctors(p, nc, chunk, io.coef, io.M, &d_A_eff, io.info, lds ? 0 : 1, st, &corr)) return rc;
+  double *d_A_eff = v.a.A_eff, *corr = nullptr;
+  if (int rc = chunk_correctors(p, nc, chunk, v.coef, v.M, &d_A_eff, v.a.info, lds ? 0 : 1, st, &corr)) return rc;
   hommx::ReconArgs a;
   set_geometry(p, a);
   a.corr = corr;
-  a.coef = io.coef;
-  a.M = io.M;
-  a.xi = io.xi;
-  a.stats = io.stats;
-  a.strain = io.strain;
-  a.flux = io.flux;
+  a.coef = v.coef;
+  a.M = v.M;
+  a.xi = v.a.xi;
+  a.stats = v.a.stats;
+  a.strain = v.a.strain;
+  a.flux = v.a.flux;
   a.slot = lds ? nullptr : corr + chunk * p->ks.t * a.ndof;
-  a.n_regions = rg.n;
-  a.region = rg.label;
-  a.region_stats = io.region_stats;
+  a.n_regions = v.a.n_regions;
+  a.region = !v.a.n_regions ? nullptr : v.a.region ? v.a.region : v.src->mask;  // n_regions == 2 of a two-phase source: the mask may be the labels
+  a.region_stats = v.a.region_stats;
   HIP_TRY(hommx::launch_reconstruct(a, p->desc.dim, p->desc.kind, p->desc.n_micro == 0, nc, st));
   return HOMMX_OK;
 }
@@ -798,363 +916,110 @@ int regions_check(const hommx_coef_source* s, int32_t n_regions, const void* reg
 
 // the shared argument checks of the reconstruct entry points; `more`: the source and the regions of the entry points that take them
 template <typename More>
-int recon_open(hommx_plan* p, int64_t n_cells, const void* coef, const void* xi, const void* stats, const void* strain, const void* flux,
-               bool device, More more) {
-  if (int rc = open_call(p, n_cells, coef && xi && stats, "coef / xi / stats", device, more); rc != GO) return rc;
-  if (!strain != !flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
+int recon_open(hommx_plan* p, int64_t n_cells, const void* coef, const ReconCall& a, bool device, More more) {
+  if (int rc = open_call(p, n_cells, coef && a.xi && a.stats, "coef / xi / stats", device, more); rc != GO) return rc;
+  if (!a.strain != !a.flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
   if (int rc = corrector_workspace(p)) return rc;  // a reconstruction needs a route that forms correctors
   return GO;
 }
-int recon_open(hommx_plan* p, int64_t n_cells, const void* coef, const void* xi, const void* stats, const void* strain, const void* flux,
-               bool device) {
-  return recon_open(p, n_cells, coef, xi, stats, strain, flux, device, [] { return HOMMX_OK; });
-}
 
-// The chunk loop of the reconstruct and sensitivity entry points.  `s` holds device pointers (a host entry stages its sampled stream per
-// chunk: s.coef is null then).  Per chunk of cells [c0, c0 + nc): in(c0, nc, io) fills io (a ReconIO or a SensIO), bringing in what a host
-// entry stages per chunk (its sampled stream among it); expand_chunk gives the element stream of every other source; run(nc, io):
-// the correctors and the kernel; out(c0, nc, io) takes the outputs away (host entries).
-template <typename IO, typename In, typename Run, typename Out>
-int source_chunks(hommx_plan* p, int64_t n_cells, int64_t chunk, const hommx_coef_source& s, hipStream_t st, In in, Run run, Out out) {
-  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
-    const int64_t nc = std::min(chunk, n_cells - c0);
-    IO io{};
-    if (int rc = in(c0, nc, io)) return rc;
-    if (!io.coef)
-      if (int rc = expand_chunk(p, s, c0, nc, st, &io.coef)) return rc;
-    if (int rc = run(nc, io)) return rc;
-    if (int rc = out(c0, nc, io)) return rc;
-  }
-  return HOMMX_OK;
-}
-
-// everything on the device already: the chunks are views of the caller's arrays
-int recon_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, const double* d_xi, ReconRegions rg,
-                 double* d_stats, double* d_region_stats, double* d_strain, double* d_flux, double* d_A_eff, int32_t* d_info, hipStream_t st) {
-  const int d = p->desc.dim, t = p->ks.t, ns = HOMMX_RECON_NSTATS(t), nr = rg.n * HOMMX_RECON_NREGION(t);
-  int64_t chunk = 0;
-  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, 0), &chunk)) return rc;
-  return source_chunks<ReconIO>(
-      p, n_cells, chunk, s, st,
-      [&](int64_t c0, int64_t, ReconIO& io) {
-        const int64_t fo = c0 * p->n_el * t;
-        io = ReconIO{nullptr,
-                     d_M ? d_M + c0 * d * d : nullptr,
-                     d_xi + c0 * t,
-                     d_stats + c0 * ns,
-                     d_region_stats ? d_region_stats + c0 * nr : nullptr,
-                     d_strain ? d_strain + fo : nullptr,
-                     d_flux ? d_flux + fo : nullptr,
-                     d_A_eff ? d_A_eff + c0 * t * t : nullptr,
-                     d_info ? d_info + c0 : nullptr};
-        return HOMMX_OK;
-      },
-      [&](int64_t nc, const ReconIO& io) { return recon_run(p, nc, chunk, io, rg, st); },
-      [](int64_t, int64_t, const ReconIO&) { return HOMMX_OK; });
-}
-
-// host pointers.  What every cell shares (mask, table, weights, labels) and the per-cell values of a sampler form travel once, in the
-// plan's pinned block (stage_source); a sampled stream, M and xi stream in and every output streams out chunk by chunk, so device
-// memory is bounded by the chunk
-int recon_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const double* xi, int32_t n_regions,
-               const uint8_t* region, double* stats, double* region_stats, double* strain, double* flux, double* A_eff, int32_t* info) {
-  const int d = p->desc.dim, t = p->ks.t, ns = HOMMX_RECON_NSTATS(t), nr = n_regions * HOMMX_RECON_NREGION(t);
-  const int64_t per = s.form == HOMMX_COEF_SAMPLED ? p->n_el * p->ks.n_comp : 0, field = strain ? p->n_el * t : 0;
-  hommx_coef_source ds;
-  const uint8_t* d_region = nullptr;
-  if (int rc = stage_source(p, n_cells, s, {region, (size_t)p->n_el, (const void**)&d_region}, &ds)) return rc;
-  const ReconRegions rg{n_regions, n_regions ? (region ? d_region : ds.mask) : nullptr};
-  // doubles per cell of the plan's blocks: in = [coef | M | xi], out = [stats | A_eff | strain | flux | region_stats], and info
-  const int64_t n_in[] = {per, M ? d * d : 0, t}, n_out[] = {ns, t * t, field, field, nr};
-  int64_t chunk = 0;
-  const size_t cell = sizeof(double) * (per + n_in[1] + t + ns + t * t + 2 * field + nr) + sizeof(int32_t);
-  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, cell), &chunk)) return rc;
-  size_t in_bytes[3], out_bytes[6];
-  for (int k = 0; k < 3; ++k) in_bytes[k] = sizeof(double) * chunk * n_in[k];
-  for (int k = 0; k < 5; ++k) out_bytes[k] = sizeof(double) * chunk * n_out[k];
-  out_bytes[5] = sizeof(int32_t) * chunk;
-  char *in[3], *out[6];
-  if (int rc = carve(p->buf[B_IN], in_bytes, in)) return rc;
-  if (int rc = carve(p->buf[B_OUT], out_bytes, out)) return rc;
-  auto f64 = [](char* at) { return reinterpret_cast<double*>(at); };
-  const ReconIO dev{f64(in[0]), f64(in[1]), f64(in[2]), f64(out[0]), f64(out[4]), f64(out[2]), f64(out[3]), f64(out[1]),
-                    reinterpret_cast<int32_t*>(out[5])};
-  return source_chunks<ReconIO>(
-      p, n_cells, chunk, ds, nullptr,
-      [&](int64_t c0, int64_t nc, ReconIO& io) {
-        if (per) HIP_TRY(hipMemcpy(in[0], s.coef + c0 * per, sizeof(double) * nc * per, hipMemcpyHostToDevice));
-        if (M) HIP_TRY(hipMemcpy(in[1], M + c0 * d * d, sizeof(double) * nc * d * d, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(in[2], xi + c0 * t, sizeof(double) * nc * t, hipMemcpyHostToDevice));
-        io = dev;
-        return HOMMX_OK;
-      },
-      [&](int64_t nc, const ReconIO& io) { return recon_run(p, nc, chunk, io, rg, nullptr); },
-      [&](int64_t c0, int64_t nc, const ReconIO& io) {
-        HIP_TRY(hipMemcpy(stats + c0 * ns, io.stats, sizeof(double) * nc * ns, hipMemcpyDeviceToHost));
-        if (A_eff) HIP_TRY(hipMemcpy(A_eff + c0 * t * t, io.A_eff, sizeof(double) * nc * t * t, hipMemcpyDeviceToHost));
-        if (info) HIP_TRY(hipMemcpy(info + c0, io.info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
-        if (strain) {
-          HIP_TRY(hipMemcpy(strain + c0 * field, io.strain, sizeof(double) * nc * field, hipMemcpyDeviceToHost));
-          HIP_TRY(hipMemcpy(flux + c0 * field, io.flux, sizeof(double) * nc * field, hipMemcpyDeviceToHost));
-        }
-        if (n_regions) HIP_TRY(hipMemcpy(region_stats + c0 * nr, io.region_stats, sizeof(double) * nc * nr, hipMemcpyDeviceToHost));
-        return HOMMX_OK;
-      });
+int recon_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const ReconCall& args, bool device, hipStream_t st) {
+  const int64_t t = p->ks.t, field = p->n_el * t;
+  Chunk<ReconCall> v{};
+  ReconCall& a = v.a = args;
+  const CellArray in[] = {{&a.xi, t}, {&a.region, p->n_el, SHARED, sizeof(uint8_t)}};
+  const CellArray out[] = {{&a.stats, HOMMX_RECON_NSTATS(t)},
+                           {&a.A_eff, t * t, KEPT},
+                           {&a.strain, field},
+                           {&a.flux, field},
+                           {&a.region_stats, a.n_regions * HOMMX_RECON_NREGION(t)}};
+  return derived_call(p, n_cells, s, M, v, in, out, &a.info, 0, recon_chunk, device, st,
+                      [&](int64_t nc, int64_t chunk, const Chunk<ReconCall>& c) { return recon_run(p, nc, chunk, c, st); });
 }
 
 // -- sensitivities (hommx_sensitivity_source[_device]) -----------------------------------------------------------------------------------
-// device pointers of one chunk
-struct SensIO {
-  const double *coef, *M, *dirs, *weights;
-  double *dA, *grad, *A_eff;
-  int32_t* info;
-};
-
-// the argument checks of both entry points, then a route that forms correctors
-int sens_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_sens_args* a, bool device) {
-  auto more = [&] {
-    if (int rc = coef_check(p, src)) return rc;
-    if (!a) return fail(HOMMX_EINVAL, "null arguments");
-    if (a->n_dirs < 0 || a->n_dirs > HOMMX_SENS_MAX_DIRS)
-      return fail(HOMMX_EINVAL, "n_dirs must be 0 .. %d, got %d", HOMMX_SENS_MAX_DIRS, a->n_dirs);
-    if (a->n_dirs > 0 && !(a->dirs && a->dA)) return fail(HOMMX_EINVAL, "n_dirs > 0 needs both dirs and dA");
-    if (!a->weights != !a->grad) return fail(HOMMX_EINVAL, "weights and grad: both or neither");
-    if (a->n_dirs == 0 && !a->grad) return fail(HOMMX_EINVAL, "nothing requested: neither directions nor a gradient");
-    return HOMMX_OK;
-  };
-  if (int rc = open_call(p, n_cells, true, "", device, more); rc != GO) return rc;
-  if (int rc = corrector_workspace(p)) return rc;
-  return GO;
-}
-
-// one chunk of at most recon_chunk() cells on the device: the correctors into the plan's scratch, then k_sens
-int sens_run(hommx_plan* p, int64_t nc, int64_t chunk, const SensIO& io, const hommx_sens_args& a, hipStream_t st) {
-  double *d_A_eff = io.A_eff, *corr = nullptr;
-  if (int rc = chunk_correctors(p, nc, chunk, io.coef, io.M, &d_A_eff, io.info, 0, st, &corr)) return rc;
+// the arguments of k_sens for the first derivatives along the directions of a chunk
+hommx::SensArgs sens_dirs_args(const hommx_plan* p, const double* corr, const double* M, int32_t n_dirs, int32_t per_cell, const double* dirs,
+                               double* dA) {
   hommx::SensArgs k;
   set_geometry(p, k);
   k.corr = corr;
-  k.M = io.M;
-  k.n_dirs = a.n_dirs;
-  k.per_cell = a.per_cell != 0;
-  k.dirs = io.dirs;
-  k.dA = io.dA;
-  k.weights = io.weights;
-  k.grad = io.grad;
+  k.M = M;
+  k.n_dirs = n_dirs;
+  k.per_cell = per_cell != 0;
+  k.dirs = dirs;
+  k.dA = dA;
+  return k;
+}
+
+// one chunk of at most recon_chunk() cells on the device: the correctors into the plan's scratch, then k_sens
+int sens_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_sens_args>& v, hipStream_t st) {
+  const hommx_sens_args& a = v.a;
+  double *d_A_eff = a.A_eff, *corr = nullptr;
+  if (int rc = chunk_correctors(p, nc, chunk, v.coef, v.M, &d_A_eff, a.info, 0, st, &corr)) return rc;
+  hommx::SensArgs k = sens_dirs_args(p, corr, v.M, a.n_dirs, a.per_cell, a.dirs, a.dA);
+  k.weights = a.weights;
+  k.grad = a.grad;
   HIP_TRY(hommx::launch_sensitivity(k, p->desc.dim, p->desc.kind, p->desc.n_micro == 0, nc, st));
   return HOMMX_OK;
 }
 
-// everything on the device already: the chunks are views of the caller's arrays
-int sens_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, const hommx_sens_args& a, hipStream_t st) {
-  const int d = p->desc.dim, tt = p->ks.t * p->ks.t;
-  const int64_t per = p->n_el * p->ks.n_comp;
-  int64_t chunk = 0;
-  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, 0), &chunk)) return rc;
-  return source_chunks<SensIO>(
-      p, n_cells, chunk, s, st,
-      [&](int64_t c0, int64_t, SensIO& io) {
-        io = SensIO{nullptr,
-                    d_M ? d_M + c0 * d * d : nullptr,
-                    a.n_dirs && a.per_cell ? a.dirs + c0 * a.n_dirs * per : a.dirs,
-                    a.weights ? a.weights + c0 * tt : nullptr,
-                    a.n_dirs ? a.dA + c0 * a.n_dirs * tt : nullptr,
-                    a.grad ? a.grad + c0 * per : nullptr,
-                    a.A_eff ? a.A_eff + c0 * tt : nullptr,
-                    a.info ? a.info + c0 : nullptr};
-        return HOMMX_OK;
-      },
-      [&](int64_t nc, const SensIO& io) { return sens_run(p, nc, chunk, io, a, st); },
-      [](int64_t, int64_t, const SensIO&) { return HOMMX_OK; });
+int sens_checks(const hommx_sens_args* a) {
+  if (a->n_dirs < 0 || a->n_dirs > HOMMX_SENS_MAX_DIRS)
+    return fail(HOMMX_EINVAL, "n_dirs must be 0 .. %d, got %d", HOMMX_SENS_MAX_DIRS, a->n_dirs);
+  if (a->n_dirs > 0 && !(a->dirs && a->dA)) return fail(HOMMX_EINVAL, "n_dirs > 0 needs both dirs and dA");
+  if (!a->weights != !a->grad) return fail(HOMMX_EINVAL, "weights and grad: both or neither");
+  if (a->n_dirs == 0 && !a->grad) return fail(HOMMX_EINVAL, "nothing requested: neither directions nor a gradient");
+  return HOMMX_OK;
 }
 
-// host pointers.  What every cell shares (mask, table, weights of the sampler, shared directions) and the per-cell values of a sampler
-// form travel once, in the plan's pinned block (stage_source); a sampled stream, M, per-cell directions and the weights stream in and
-// every output streams out chunk by chunk, so device memory is bounded by the chunk
-int sens_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_sens_args& a) {
-  const int d = p->desc.dim, tt = p->ks.t * p->ks.t;
-  const int64_t el = p->n_el * p->ks.n_comp, per = s.form == HOMMX_COEF_SAMPLED ? el : 0;
-  const bool per_cell = a.n_dirs && a.per_cell;
-  hommx_coef_source ds;
-  const double* d_shared = nullptr;
-  const hommx::HostPiece shared{per_cell ? nullptr : a.dirs, sizeof(double) * a.n_dirs * el, (const void**)&d_shared};
-  if (int rc = stage_source(p, n_cells, s, shared, &ds)) return rc;
-  // doubles per cell of the plan's blocks: in = [coef | M | dirs | weights], out = [dA | A_eff | grad], and info
-  const int64_t n_in[] = {per, M ? d * d : 0, per_cell ? a.n_dirs * el : 0, a.grad ? tt : 0}, n_out[] = {a.n_dirs * tt, tt, a.grad ? el : 0};
-  size_t cell = sizeof(int32_t);
-  for (int64_t k : n_in) cell += sizeof(double) * k;
-  for (int64_t k : n_out) cell += sizeof(double) * k;
-  int64_t chunk = 0;
-  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, cell), &chunk)) return rc;
-  size_t in_bytes[4], out_bytes[4];
-  for (int k = 0; k < 4; ++k) in_bytes[k] = sizeof(double) * chunk * n_in[k];
-  for (int k = 0; k < 3; ++k) out_bytes[k] = sizeof(double) * chunk * n_out[k];
-  out_bytes[3] = sizeof(int32_t) * chunk;
-  char *in[4], *out[4];
-  if (int rc = carve(p->buf[B_IN], in_bytes, in)) return rc;
-  if (int rc = carve(p->buf[B_OUT], out_bytes, out)) return rc;
-  auto f64 = [](char* at) { return reinterpret_cast<double*>(at); };
-  const SensIO dev{f64(in[0]), f64(in[1]), per_cell ? f64(in[2]) : d_shared, f64(in[3]), f64(out[0]), f64(out[2]), f64(out[1]),
-                   reinterpret_cast<int32_t*>(out[3])};
-  const double* src_in[] = {s.coef, M, a.dirs, a.weights};
-  return source_chunks<SensIO>(
-      p, n_cells, chunk, ds, nullptr,
-      [&](int64_t c0, int64_t nc, SensIO& io) {
-        for (int k = 0; k < 4; ++k)
-          if (n_in[k]) HIP_TRY(hipMemcpy(in[k], src_in[k] + c0 * n_in[k], sizeof(double) * nc * n_in[k], hipMemcpyHostToDevice));
-        io = dev;
-        return HOMMX_OK;
-      },
-      [&](int64_t nc, const SensIO& io) { return sens_run(p, nc, chunk, io, a, nullptr); },
-      [&](int64_t c0, int64_t nc, const SensIO& io) {
-        double* dst_out[] = {a.dA, a.A_eff, a.grad};
-        for (int k = 0; k < 3; ++k)
-          if (n_out[k] && dst_out[k])
-            HIP_TRY(hipMemcpy(dst_out[k] + c0 * n_out[k], out[k], sizeof(double) * nc * n_out[k], hipMemcpyDeviceToHost));
-        if (a.info) HIP_TRY(hipMemcpy(a.info + c0, io.info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
-        return HOMMX_OK;
-      });
+int sens_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_sens_args& args, bool device,
+              hipStream_t st) {
+  const int64_t tt = p->ks.t * p->ks.t, el = p->n_el * p->ks.n_comp;
+  Chunk<hommx_sens_args> v{};
+  hommx_sens_args& a = v.a = args;
+  const CellArray in[] = {{&a.dirs, a.n_dirs * el, a.n_dirs && a.per_cell ? PER_CELL : SHARED}, {&a.weights, tt}};
+  const CellArray out[] = {{&a.dA, a.n_dirs * tt}, {&a.A_eff, tt, KEPT}, {&a.grad, el}};
+  return derived_call(p, n_cells, s, M, v, in, out, &a.info, 0, recon_chunk, device, st,
+                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_sens_args>& c) { return sens_run(p, nc, chunk, c, st); });
 }
 
 // -- stratification sensitivities (hommx_stratification_sensitivity_source[_device]) --------------------------------------------------------
-// device pointers of one chunk
-struct StratIO {
-  const double *coef, *M, *weights;
-  double *dA_dM, *grad_M, *A_eff;
-  int32_t* info;
-};
-
-// the argument checks of both entry points, then a route that forms correctors
-int strat_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_strat_sens_args* a, bool device) {
-  auto more = [&] {
-    if (int rc = coef_check(p, src)) return rc;
-    if (!a) return fail(HOMMX_EINVAL, "null arguments");
-    if (!a->weights != !a->grad_M) return fail(HOMMX_EINVAL, "weights and grad_M: both or neither");
-    if (!a->dA_dM && !a->grad_M) return fail(HOMMX_EINVAL, "nothing requested: neither dA_dM nor grad_M");
-    return HOMMX_OK;
-  };
-  if (int rc = open_call(p, n_cells, true, "", device, more); rc != GO) return rc;
-  if (int rc = corrector_workspace(p)) return rc;
-  return GO;
-}
-
 // one chunk of at most recon_chunk() cells on the device: the correctors into the plan's scratch, then k_sens_strat
-int strat_run(hommx_plan* p, int64_t nc, int64_t chunk, const StratIO& io, hipStream_t st) {
-  double *d_A_eff = io.A_eff, *corr = nullptr;
-  if (int rc = chunk_correctors(p, nc, chunk, io.coef, io.M, &d_A_eff, io.info, 0, st, &corr)) return rc;
+int strat_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_strat_sens_args>& v, hipStream_t st) {
+  double *d_A_eff = v.a.A_eff, *corr = nullptr;
+  if (int rc = chunk_correctors(p, nc, chunk, v.coef, v.M, &d_A_eff, v.a.info, 0, st, &corr)) return rc;
   hommx::StratSensArgs k;
   set_geometry(p, k);
   k.corr = corr;
-  k.coef = io.coef;
-  k.M = io.M;
-  k.dA_dM = io.dA_dM;
-  k.weights = io.weights;
-  k.grad_M = io.grad_M;
+  k.coef = v.coef;
+  k.M = v.M;
+  k.dA_dM = v.a.dA_dM;
+  k.weights = v.a.weights;
+  k.grad_M = v.a.grad_M;
   HIP_TRY(hommx::launch_sens_strat(k, p->desc.dim, p->desc.kind, p->desc.n_micro == 0, nc, st));
   return HOMMX_OK;
 }
 
-// everything on the device already: the chunks are views of the caller's arrays
-int strat_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, const hommx_strat_sens_args& a, hipStream_t st) {
-  const int dd = p->desc.dim * p->desc.dim, tt = p->ks.t * p->ks.t;
-  int64_t chunk = 0;
-  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, 0), &chunk)) return rc;
-  return source_chunks<StratIO>(
-      p, n_cells, chunk, s, st,
-      [&](int64_t c0, int64_t, StratIO& io) {
-        io = StratIO{nullptr,
-                     d_M ? d_M + c0 * dd : nullptr,
-                     a.weights ? a.weights + c0 * tt : nullptr,
-                     a.dA_dM ? a.dA_dM + c0 * dd * tt : nullptr,
-                     a.grad_M ? a.grad_M + c0 * dd : nullptr,
-                     a.A_eff ? a.A_eff + c0 * tt : nullptr,
-                     a.info ? a.info + c0 : nullptr};
-        return HOMMX_OK;
-      },
-      [&](int64_t nc, const StratIO& io) { return strat_run(p, nc, chunk, io, st); },
-      [](int64_t, int64_t, const StratIO&) { return HOMMX_OK; });
+int strat_checks(const hommx_strat_sens_args* a) {
+  if (!a->weights != !a->grad_M) return fail(HOMMX_EINVAL, "weights and grad_M: both or neither");
+  if (!a->dA_dM && !a->grad_M) return fail(HOMMX_EINVAL, "nothing requested: neither dA_dM nor grad_M");
+  return HOMMX_OK;
 }
 
-// host pointers.  What every cell shares (mask, table, weights of the sampler) and the per-cell values of a sampler form travel once, in
-// the plan's pinned block (stage_source); a sampled stream, M and the weights stream in and every output streams out chunk by chunk, so
-// device memory is bounded by the chunk
-int strat_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_strat_sens_args& a) {
-  const int dd = p->desc.dim * p->desc.dim, tt = p->ks.t * p->ks.t;
-  const int64_t per = s.form == HOMMX_COEF_SAMPLED ? p->n_el * p->ks.n_comp : 0;
-  hommx_coef_source ds;
-  const void* none = nullptr;
-  if (int rc = stage_source(p, n_cells, s, {nullptr, 0, &none}, &ds)) return rc;
-  // doubles per cell of the plan's blocks: in = [coef | M | weights], out = [dA_dM | A_eff | grad_M], and info
-  const int64_t n_in[] = {per, M ? dd : 0, a.grad_M ? tt : 0}, n_out[] = {a.dA_dM ? (int64_t)dd * tt : 0, tt, a.grad_M ? dd : 0};
-  size_t cell = sizeof(int32_t);
-  for (int64_t k : n_in) cell += sizeof(double) * k;
-  for (int64_t k : n_out) cell += sizeof(double) * k;
-  int64_t chunk = 0;
-  if (int rc = stream_chunk(p, s, recon_chunk(p, n_cells, cell), &chunk)) return rc;
-  size_t in_bytes[3], out_bytes[4];
-  for (int k = 0; k < 3; ++k) in_bytes[k] = sizeof(double) * chunk * n_in[k];
-  for (int k = 0; k < 3; ++k) out_bytes[k] = sizeof(double) * chunk * n_out[k];
-  out_bytes[3] = sizeof(int32_t) * chunk;
-  char *in[3], *out[4];
-  if (int rc = carve(p->buf[B_IN], in_bytes, in)) return rc;
-  if (int rc = carve(p->buf[B_OUT], out_bytes, out)) return rc;
-  auto f64 = [](char* at) { return reinterpret_cast<double*>(at); };
-  const StratIO dev{f64(in[0]), f64(in[1]), f64(in[2]), f64(out[0]), f64(out[2]), f64(out[1]), reinterpret_cast<int32_t*>(out[3])};
-  const double* src_in[] = {s.coef, M, a.weights};
-  return source_chunks<StratIO>(
-      p, n_cells, chunk, ds, nullptr,
-      [&](int64_t c0, int64_t nc, StratIO& io) {
-        for (int k = 0; k < 3; ++k)
-          if (n_in[k]) HIP_TRY(hipMemcpy(in[k], src_in[k] + c0 * n_in[k], sizeof(double) * nc * n_in[k], hipMemcpyHostToDevice));
-        io = dev;
-        return HOMMX_OK;
-      },
-      [&](int64_t nc, const StratIO& io) { return strat_run(p, nc, chunk, io, nullptr); },
-      [&](int64_t c0, int64_t nc, const StratIO& io) {
-        double* dst_out[] = {a.dA_dM, a.A_eff, a.grad_M};
-        for (int k = 0; k < 3; ++k)
-          if (n_out[k] && dst_out[k])
-            HIP_TRY(hipMemcpy(dst_out[k] + c0 * n_out[k], out[k], sizeof(double) * nc * n_out[k], hipMemcpyDeviceToHost));
-        if (a.info) HIP_TRY(hipMemcpy(a.info + c0, io.info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
-        return HOMMX_OK;
-      });
+int strat_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_strat_sens_args& args, bool device,
+               hipStream_t st) {
+  const int64_t dd = p->desc.dim * p->desc.dim, tt = p->ks.t * p->ks.t;
+  Chunk<hommx_strat_sens_args> v{};
+  hommx_strat_sens_args& a = v.a = args;
+  const CellArray in[] = {{&a.weights, tt}};
+  const CellArray out[] = {{&a.dA_dM, dd * tt}, {&a.A_eff, tt, KEPT}, {&a.grad_M, dd}};
+  return derived_call(p, n_cells, s, M, v, in, out, &a.info, 0, recon_chunk, device, st,
+                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_strat_sens_args>& c) { return strat_run(p, nc, chunk, c, st); });
 }
 
 // -- polarisation loads (hommx_loads_source[_device]) ------------------------------------------------------------------------------------
-// device pointers of one chunk
-struct LoadIO {
-  const double *coef, *M, *P;
-  double *P_eff, *A_eff, *energy, *stats, *strain, *flux, *correctors;
-  int32_t* info;
-};
-
 bool load_response(const hommx_load_args& a) { return a.energy || a.stats || a.strain || a.flux || a.correctors; }
-
-// the argument checks of both entry points, then the routes the call needs: one that forms correctors, and for a response the blocked
-// workspace of a fused 2D plan whose load solve does not run on its own records (HOMMX_FUSED_LOADS=0 / HOMMX_FUSED_CORR=0)
-int loads_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_load_args* a, bool device) {
-  auto more = [&] {
-    if (int rc = coef_check(p, src)) return rc;
-    if (!a) return fail(HOMMX_EINVAL, "null arguments");
-    const int t = hommx::kind_sizes(p->desc.dim, p->desc.kind).t;
-    if (a->n_loads < 1 || a->n_loads > t) return fail(HOMMX_EINVAL, "n_loads must be 1 .. %d (the tensor size of the plan), got %d", t, a->n_loads);
-    if (!a->P || !a->P_eff) return fail(HOMMX_EINVAL, "null P / P_eff");
-    if (!a->strain != !a->flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
-    return HOMMX_OK;
-  };
-  if (int rc = open_call(p, n_cells, true, "", device, more); rc != GO) return rc;
-  // the one check that reads more of the plan than its descriptor (its family), so it cannot run on the plan-shaped memory the checks
-  // above accept: it comes after open_call, with the device current already, and before any work
-  if (load_response(*a) && p->family == FAM_MESH && !mesh_loads(p))
-    return fail(HOMMX_EINVAL, "the frontal mesh route (mesh_front) solves for the canonical loads only: energy, stats, strain / flux and "
-                              "correctors of user loads need a plan of the tree route (HOMMX_MESH_FLAG_TREE, route=\"tree\"); P_eff alone works here");
-  if (int rc = corrector_workspace(p)) return rc;
-  if (load_response(*a) && !p->ws && !fused_loads(p) && !mesh_loads(p)) {
-    int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
-    if (rc) return prefix_error(rc, "blocked path: ");
-  }
-  return GO;
-}
 
 // The correctors of the loads `lo` of nc cells of a chunk into corr_l[nc][t][ndof] (rows l < n_loads), on the route
 // hommx_plan_load_kernel_name names: fused 2D plans substitute on the records the canonical pass of this chunk has just left in B_FACT
@@ -1179,130 +1044,110 @@ int load_correctors(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_co
 
 // one chunk of at most recon_chunk() cells on the device: the canonical correctors into the plan's scratch and k_polar; for a response
 // the correctors of the loads behind them (load_correctors) and k_load_stats
-int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const LoadIO& io, const hommx_load_args& a, hipStream_t st) {
+int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_load_args>& v, hipStream_t st) {
+  const hommx_load_args& a = v.a;
   const bool response = load_response(a), mesh = p->desc.n_micro == 0;
   const int t = p->ks.t;
-  double *d_A_eff = io.A_eff, *corr = nullptr;
-  if (int rc = chunk_correctors(p, nc, chunk, io.coef, io.M, &d_A_eff, io.info, response ? t : 0, st, &corr)) return rc;
+  double *d_A_eff = a.A_eff, *corr = nullptr;
+  if (int rc = chunk_correctors(p, nc, chunk, v.coef, v.M, &d_A_eff, a.info, response ? t : 0, st, &corr)) return rc;
   hommx::LoadArgs k;
   set_geometry(p, k);
   k.corr = corr;
-  k.coef = io.coef;
-  k.M = io.M;
+  k.coef = v.coef;
+  k.M = v.M;
   k.n_loads = a.n_loads;
   k.per_cell = a.per_cell != 0;
-  k.P = io.P;
-  k.P_eff = io.P_eff;
+  k.P = a.P;
+  k.P_eff = a.P_eff;
   HIP_TRY(hommx::launch_polar(k, p->desc.dim, p->desc.kind, mesh, nc, st));
   if (!response) return HOMMX_OK;
   double* corr_l = corr + chunk * t * k.ndof;
-  if (int rc = load_correctors(p, nc, chunk, io.coef, io.M, hommx::LoadOverride{io.P, a.n_loads, a.per_cell != 0}, st, corr_l)) return rc;
+  if (int rc = load_correctors(p, nc, chunk, v.coef, v.M, hommx::LoadOverride{a.P, a.n_loads, a.per_cell != 0}, st, corr_l)) return rc;
   k.corr = corr_l;
-  k.energy = io.energy;
-  k.stats = io.stats;
-  k.strain = io.strain;
-  k.flux = io.flux;
-  if (io.energy || io.stats || io.strain) HIP_TRY(hommx::launch_load_stats(k, p->desc.dim, p->desc.kind, mesh, nc, st));
-  if (io.correctors)  // rows l < n_loads of every cell
-    HIP_TRY(hipMemcpy2DAsync(io.correctors, sizeof(double) * a.n_loads * k.ndof, corr_l, sizeof(double) * t * k.ndof,
+  k.energy = a.energy;
+  k.stats = a.stats;
+  k.strain = a.strain;
+  k.flux = a.flux;
+  if (a.energy || a.stats || a.strain) HIP_TRY(hommx::launch_load_stats(k, p->desc.dim, p->desc.kind, mesh, nc, st));
+  if (a.correctors)  // rows l < n_loads of every cell
+    HIP_TRY(hipMemcpy2DAsync(a.correctors, sizeof(double) * a.n_loads * k.ndof, corr_l, sizeof(double) * t * k.ndof,
                              sizeof(double) * a.n_loads * k.ndof, nc, hipMemcpyDeviceToDevice, st));
   return HOMMX_OK;
 }
 
-// doubles per cell of the outputs of a call, in the order of LoadIO: P_eff, A_eff, energy, stats, strain, flux, correctors
-void load_out_sizes(const hommx_plan* p, const hommx_load_args& a, int64_t (&n)[7]) {
-  const int64_t t = p->ks.t, nl = a.n_loads, field = a.strain ? nl * p->n_el * t : 0;
-  const int64_t sizes[7] = {nl * t, t * t, a.energy ? nl * nl : 0, a.stats ? nl * (t + 2) : 0, field, field, a.correctors ? nl * plan_ndof(p) : 0};
-  for (int k = 0; k < 7; ++k) n[k] = sizes[k];
+// the argument checks of both entry points, then the routes the call needs: one that forms correctors, and for a response a load solve
+int loads_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_load_args* a, bool device) {
+  auto checks = [&] {
+    const int t = hommx::kind_sizes(p->desc.dim, p->desc.kind).t;
+    if (a->n_loads < 1 || a->n_loads > t) return fail(HOMMX_EINVAL, "n_loads must be 1 .. %d (the tensor size of the plan), got %d", t, a->n_loads);
+    if (!a->P || !a->P_eff) return fail(HOMMX_EINVAL, "null P / P_eff");
+    if (!a->strain != !a->flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
+    return HOMMX_OK;
+  };
+  if (int rc = source_open(p, n_cells, src, a, device, checks); rc != GO) return rc;
+  if (!load_response(*a)) return GO;
+  // the one check that reads more of the plan than its descriptor (its family), so it cannot run on the plan-shaped memory the checks
+  // above accept: it comes after open_call, with the device current already, and before any work (a mesh plan gets no workspace above)
+  if (p->family == FAM_MESH && !mesh_loads(p))
+    return fail(HOMMX_EINVAL, "the frontal mesh route (mesh_front) solves for the canonical loads only: energy, stats, strain / flux and "
+                              "correctors of user loads need a plan of the tree route (HOMMX_MESH_FLAG_TREE, route=\"tree\"); P_eff alone works here");
+  if (int rc = load_workspace(p)) return rc;
+  return GO;
 }
 
-// everything on the device already: the chunks are views of the caller's arrays.  A response holds a second corrector block per cell
-int loads_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, const hommx_load_args& a, hipStream_t st) {
-  const int d = p->desc.dim;
-  const int64_t el = p->n_el * p->ks.t;
-  int64_t n_out[7], chunk = 0;
-  load_out_sizes(p, a, n_out);
-  const size_t second = load_response(a) ? sizeof(double) * plan_ndof(p) * p->ks.t : 0;
-  if (int rc = stream_chunk(p, s, second ? load_chunk(p, n_cells, second) : recon_chunk(p, n_cells, 0), &chunk)) return rc;
-  return source_chunks<LoadIO>(
-      p, n_cells, chunk, s, st,
-      [&](int64_t c0, int64_t, LoadIO& io) {
-        double* const out[7] = {a.P_eff, a.A_eff, a.energy, a.stats, a.strain, a.flux, a.correctors};
-        double* at[7];
-        for (int k = 0; k < 7; ++k) at[k] = out[k] ? out[k] + c0 * n_out[k] : nullptr;
-        io = LoadIO{nullptr, d_M ? d_M + c0 * d * d : nullptr, a.per_cell ? a.P + c0 * a.n_loads * el : a.P,
-                    at[0], at[1], at[2], at[3], at[4], at[5], at[6], a.info ? a.info + c0 : nullptr};
-        return HOMMX_OK;
-      },
-      [&](int64_t nc, const LoadIO& io) { return loads_run(p, nc, chunk, io, a, st); },
-      [](int64_t, int64_t, const LoadIO&) { return HOMMX_OK; });
-}
-
-// host pointers.  What every cell shares (mask, table, weights of the sampler, a shared P) and the per-cell values of a sampler form travel
-// once, in the plan's pinned block (stage_source); a sampled stream, M and a per-cell P stream in and every output streams out chunk by
-// chunk, so device memory is bounded by the chunk
-int loads_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_load_args& a) {
-  const int d = p->desc.dim;
-  const int64_t per = s.form == HOMMX_COEF_SAMPLED ? p->n_el * p->ks.n_comp : 0, load = a.n_loads * p->n_el * p->ks.t;
-  const bool per_cell = a.per_cell != 0;
-  hommx_coef_source ds;
-  const double* d_shared = nullptr;
-  const hommx::HostPiece shared{per_cell ? nullptr : a.P, sizeof(double) * load, (const void**)&d_shared};
-  if (int rc = stage_source(p, n_cells, s, shared, &ds)) return rc;
-  // doubles per cell of the plan's blocks: in = [coef | M | P], out = the seven of load_out_sizes (A_eff always: the caller may not want it), and info
-  const int64_t n_in[] = {per, M ? d * d : 0, per_cell ? load : 0};
-  int64_t n_out[7];
-  load_out_sizes(p, a, n_out);
-  size_t cell = sizeof(int32_t) + (load_response(a) ? sizeof(double) * plan_ndof(p) * p->ks.t : 0);
-  for (int64_t k : n_in) cell += sizeof(double) * k;
-  for (int64_t k : n_out) cell += sizeof(double) * k;
-  int64_t chunk = 0;
-  if (int rc = stream_chunk(p, s, load_response(a) ? load_chunk(p, n_cells, cell) : recon_chunk(p, n_cells, cell), &chunk)) return rc;
-  size_t in_bytes[3], out_bytes[8];
-  for (int k = 0; k < 3; ++k) in_bytes[k] = sizeof(double) * chunk * n_in[k];
-  for (int k = 0; k < 7; ++k) out_bytes[k] = sizeof(double) * chunk * n_out[k];
-  out_bytes[7] = sizeof(int32_t) * chunk;
-  char *in[3], *out[8];
-  if (int rc = carve(p->buf[B_IN], in_bytes, in)) return rc;
-  if (int rc = carve(p->buf[B_OUT], out_bytes, out)) return rc;
-  auto f64 = [](char* at) { return reinterpret_cast<double*>(at); };
-  const LoadIO dev{f64(in[0]), f64(in[1]), per_cell ? f64(in[2]) : d_shared, f64(out[0]), f64(out[1]), f64(out[2]), f64(out[3]),
-                   f64(out[4]), f64(out[5]), f64(out[6]), reinterpret_cast<int32_t*>(out[7])};
-  const double* src_in[] = {s.coef, M, a.P};
-  return source_chunks<LoadIO>(
-      p, n_cells, chunk, ds, nullptr,
-      [&](int64_t c0, int64_t nc, LoadIO& io) {
-        for (int k = 0; k < 3; ++k)
-          if (n_in[k]) HIP_TRY(hipMemcpy(in[k], src_in[k] + c0 * n_in[k], sizeof(double) * nc * n_in[k], hipMemcpyHostToDevice));
-        io = dev;
-        return HOMMX_OK;
-      },
-      [&](int64_t nc, const LoadIO& io) { return loads_run(p, nc, chunk, io, a, nullptr); },
-      [&](int64_t c0, int64_t nc, const LoadIO& io) {
-        double* dst_out[] = {a.P_eff, a.A_eff, a.energy, a.stats, a.strain, a.flux, a.correctors};
-        for (int k = 0; k < 7; ++k)
-          if (n_out[k] && dst_out[k])
-            HIP_TRY(hipMemcpy(dst_out[k] + c0 * n_out[k], out[k], sizeof(double) * nc * n_out[k], hipMemcpyDeviceToHost));
-        if (a.info) HIP_TRY(hipMemcpy(a.info + c0, io.info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
-        return HOMMX_OK;
-      });
+// A response holds a second corrector block per cell, and its chunks end in a load solve
+int loads_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_load_args& args, bool device,
+               hipStream_t st) {
+  const int64_t t = p->ks.t, nl = args.n_loads, field = nl * p->n_el * t;
+  const bool response = load_response(args);
+  Chunk<hommx_load_args> v{};
+  hommx_load_args& a = v.a = args;
+  const CellArray in[] = {{&a.P, field, a.per_cell ? PER_CELL : SHARED}};
+  const CellArray out[] = {{&a.P_eff, nl * t}, {&a.A_eff, t * t, KEPT},   {&a.energy, nl * nl},          {&a.stats, nl * (t + 2)},
+                           {&a.strain, field}, {&a.flux, field},          {&a.correctors, nl * plan_ndof(p)}};
+  return derived_call(p, n_cells, s, M, v, in, out, &a.info, response ? sizeof(double) * plan_ndof(p) * t : 0, response ? load_chunk : recon_chunk,
+                      device, st, [&](int64_t nc, int64_t chunk, const Chunk<hommx_load_args>& c) { return loads_run(p, nc, chunk, c, st); });
 }
 
 // -- second derivatives (hommx_second_sensitivity_source[_device]) ------------------------------------------------------------------------
-// device pointers of one chunk
-struct Sens2IO {
-  const double *coef, *M, *dirs;
-  double *d2A, *dA, *A_eff;
-  int32_t* info;
-};
+// bytes per cell of a chunk beside the canonical correctors: the second corrector block and the loads of one direction
+size_t sens2_extra(const hommx_plan* p) { return sizeof(double) * p->ks.t * (plan_ndof(p) + p->n_el * p->ks.t); }
+
+// one chunk of at most recon_chunk() cells on the device: the canonical correctors into the plan's scratch, k_sens for the first
+// derivatives; then per direction b its loads (k_sens2_loads), their correctors behind the canonical ones (load_correctors), and k_sens2 for the blocks (a, b) and (b, a), a <= b
+int sens2_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_sens2_args>& v, hipStream_t st) {
+  const hommx_sens2_args& a = v.a;
+  const bool mesh = p->desc.n_micro == 0;
+  const int t = p->ks.t;
+  double *d_A_eff = a.A_eff, *corr = nullptr;
+  if (int rc = chunk_correctors(p, nc, chunk, v.coef, v.M, &d_A_eff, a.info, t, st, &corr)) return rc;
+  if (a.dA)
+    HIP_TRY(hommx::launch_sensitivity(sens_dirs_args(p, corr, v.M, a.n_dirs, a.per_cell, a.dirs, a.dA), p->desc.dim, p->desc.kind, mesh, nc, st));
+  if (int rc = grow(p->buf[B_SENS2], sizeof(double) * chunk * t * p->n_el * t)) return rc;
+  hommx::Sens2Args k;
+  set_geometry(p, k);
+  double* corr_b = corr + chunk * t * k.ndof;
+  k.corr = corr;
+  k.corr_b = corr_b;
+  k.M = v.M;
+  k.n_dirs = a.n_dirs;
+  k.per_cell = a.per_cell != 0;
+  k.dirs = a.dirs;
+  k.P = static_cast<double*>(p->buf[B_SENS2].p);
+  k.d2A = a.d2A;
+  for (int b = 0; b < a.n_dirs; ++b) {
+    k.b = b;
+    HIP_TRY(hommx::launch_sens2_loads(k, p->desc.dim, p->desc.kind, mesh, nc, st));
+    if (int rc = load_correctors(p, nc, chunk, v.coef, v.M, hommx::LoadOverride{k.P, t, true}, st, corr_b)) return rc;  // t per-cell loads
+    HIP_TRY(hommx::launch_sens2(k, p->desc.dim, p->desc.kind, mesh, nc, st));
+  }
+  return HOMMX_OK;
+}
 
 // the argument checks of both entry points -- the frontal mesh route among them: the descriptor of a mesh plan names its route --, then
-// the routes the call needs: one that forms correctors, and the blocked workspace of a fused 2D plan whose load solve does not run on
-// its own records (HOMMX_FUSED_LOADS=0 / HOMMX_FUSED_CORR=0), as loads_open
+// the routes the call needs: one that forms correctors and a load solve
 int sens2_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_sens2_args* a, bool device) {
-  auto more = [&] {
-    if (int rc = coef_check(p, src)) return rc;
-    if (!a) return fail(HOMMX_EINVAL, "null arguments");
+  auto checks = [&] {
     if (a->n_dirs < 1 || a->n_dirs > HOMMX_SENS_MAX_DIRS)
       return fail(HOMMX_EINVAL, "n_dirs must be 1 .. %d, got %d", HOMMX_SENS_MAX_DIRS, a->n_dirs);
     if (!a->dirs || !a->d2A) return fail(HOMMX_EINVAL, "null dirs / d2A");
@@ -1311,124 +1156,20 @@ int sens2_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, con
                                 "solve of a plan of the tree route (HOMMX_MESH_FLAG_TREE, route=\"tree\")");
     return HOMMX_OK;
   };
-  if (int rc = open_call(p, n_cells, true, "", device, more); rc != GO) return rc;
-  if (int rc = corrector_workspace(p)) return rc;
-  if (!p->ws && !fused_loads(p) && !mesh_loads(p)) {
-    int rc = hommx::blocked_workspace_create(&p->ws, p->desc.dim, p->desc.n_micro, p->desc.kind);
-    if (rc) return prefix_error(rc, "blocked path: ");
-  }
+  if (int rc = source_open(p, n_cells, src, a, device, checks); rc != GO) return rc;
+  if (int rc = load_workspace(p)) return rc;
   return GO;
 }
 
-// bytes per cell of a chunk beside the canonical correctors: the second corrector block and the loads of one direction
-size_t sens2_extra(const hommx_plan* p) { return sizeof(double) * p->ks.t * (plan_ndof(p) + p->n_el * p->ks.t); }
-
-// one chunk of at most recon_chunk() cells on the device: the canonical correctors into the plan's scratch, k_sens for the first
-// derivatives; then per direction b its loads (k_sens2_loads), their correctors behind the canonical ones (load_correctors), and k_sens2 for the blocks (a, b) and (b, a), a <= b
-int sens2_run(hommx_plan* p, int64_t nc, int64_t chunk, const Sens2IO& io, const hommx_sens2_args& a, hipStream_t st) {
-  const bool mesh = p->desc.n_micro == 0;
-  const int t = p->ks.t;
-  double *d_A_eff = io.A_eff, *corr = nullptr;
-  if (int rc = chunk_correctors(p, nc, chunk, io.coef, io.M, &d_A_eff, io.info, t, st, &corr)) return rc;
-  if (io.dA) {
-    hommx::SensArgs s;
-    set_geometry(p, s);
-    s.corr = corr;
-    s.M = io.M;
-    s.n_dirs = a.n_dirs;
-    s.per_cell = a.per_cell != 0;
-    s.dirs = io.dirs;
-    s.dA = io.dA;
-    HIP_TRY(hommx::launch_sensitivity(s, p->desc.dim, p->desc.kind, mesh, nc, st));
-  }
-  if (int rc = grow(p->buf[B_SENS2], sizeof(double) * chunk * t * p->n_el * t)) return rc;
-  hommx::Sens2Args k;
-  set_geometry(p, k);
-  double* corr_b = corr + chunk * t * k.ndof;
-  k.corr = corr;
-  k.corr_b = corr_b;
-  k.M = io.M;
-  k.n_dirs = a.n_dirs;
-  k.per_cell = a.per_cell != 0;
-  k.dirs = io.dirs;
-  k.P = static_cast<double*>(p->buf[B_SENS2].p);
-  k.d2A = io.d2A;
-  for (int b = 0; b < a.n_dirs; ++b) {
-    k.b = b;
-    HIP_TRY(hommx::launch_sens2_loads(k, p->desc.dim, p->desc.kind, mesh, nc, st));
-    if (int rc = load_correctors(p, nc, chunk, io.coef, io.M, hommx::LoadOverride{k.P, t, true}, st, corr_b)) return rc;  // t per-cell loads
-    HIP_TRY(hommx::launch_sens2(k, p->desc.dim, p->desc.kind, mesh, nc, st));
-  }
-  return HOMMX_OK;
-}
-
-// everything on the device already: the chunks are views of the caller's arrays
-int sens2_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, const hommx_sens2_args& a, hipStream_t st) {
-  const int d = p->desc.dim, tt = p->ks.t * p->ks.t;
-  const int64_t per = p->n_el * p->ks.n_comp;
-  int64_t chunk = 0;
-  if (int rc = stream_chunk(p, s, load_chunk(p, n_cells, sens2_extra(p)), &chunk)) return rc;
-  return source_chunks<Sens2IO>(
-      p, n_cells, chunk, s, st,
-      [&](int64_t c0, int64_t, Sens2IO& io) {
-        io = Sens2IO{nullptr,
-                     d_M ? d_M + c0 * d * d : nullptr,
-                     a.per_cell ? a.dirs + c0 * a.n_dirs * per : a.dirs,
-                     a.d2A + c0 * a.n_dirs * a.n_dirs * tt,
-                     a.dA ? a.dA + c0 * a.n_dirs * tt : nullptr,
-                     a.A_eff ? a.A_eff + c0 * tt : nullptr,
-                     a.info ? a.info + c0 : nullptr};
-        return HOMMX_OK;
-      },
-      [&](int64_t nc, const Sens2IO& io) { return sens2_run(p, nc, chunk, io, a, st); },
-      [](int64_t, int64_t, const Sens2IO&) { return HOMMX_OK; });
-}
-
-// host pointers.  What every cell shares (mask, table, weights of the sampler, shared directions) and the per-cell values of a sampler
-// form travel once, in the plan's pinned block (stage_source); a sampled stream, M and per-cell directions stream in and every output
-// streams out chunk by chunk, so device memory is bounded by the chunk
-int sens2_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_sens2_args& a) {
-  const int d = p->desc.dim, tt = p->ks.t * p->ks.t;
-  const int64_t el = p->n_el * p->ks.n_comp, per = s.form == HOMMX_COEF_SAMPLED ? el : 0;
-  const bool per_cell = a.per_cell != 0;
-  hommx_coef_source ds;
-  const double* d_shared = nullptr;
-  const hommx::HostPiece shared{per_cell ? nullptr : a.dirs, sizeof(double) * a.n_dirs * el, (const void**)&d_shared};
-  if (int rc = stage_source(p, n_cells, s, shared, &ds)) return rc;
-  // doubles per cell of the plan's blocks: in = [coef | M | dirs], out = [d2A | A_eff | dA], and info
-  const int64_t n_in[] = {per, M ? d * d : 0, per_cell ? a.n_dirs * el : 0}, n_out[] = {(int64_t)a.n_dirs * a.n_dirs * tt, tt, a.dA ? a.n_dirs * tt : 0};
-  size_t cell = sizeof(int32_t) + sens2_extra(p);
-  for (int64_t k : n_in) cell += sizeof(double) * k;
-  for (int64_t k : n_out) cell += sizeof(double) * k;
-  int64_t chunk = 0;
-  if (int rc = stream_chunk(p, s, load_chunk(p, n_cells, cell), &chunk)) return rc;
-  size_t in_bytes[3], out_bytes[4];
-  for (int k = 0; k < 3; ++k) in_bytes[k] = sizeof(double) * chunk * n_in[k];
-  for (int k = 0; k < 3; ++k) out_bytes[k] = sizeof(double) * chunk * n_out[k];
-  out_bytes[3] = sizeof(int32_t) * chunk;
-  char *in[3], *out[4];
-  if (int rc = carve(p->buf[B_IN], in_bytes, in)) return rc;
-  if (int rc = carve(p->buf[B_OUT], out_bytes, out)) return rc;
-  auto f64 = [](char* at) { return reinterpret_cast<double*>(at); };
-  const Sens2IO dev{f64(in[0]), f64(in[1]), per_cell ? f64(in[2]) : d_shared, f64(out[0]), f64(out[2]), f64(out[1]), reinterpret_cast<int32_t*>(out[3])};
-  const double* src_in[] = {s.coef, M, a.dirs};
-  return source_chunks<Sens2IO>(
-      p, n_cells, chunk, ds, nullptr,
-      [&](int64_t c0, int64_t nc, Sens2IO& io) {
-        for (int k = 0; k < 3; ++k)
-          if (n_in[k]) HIP_TRY(hipMemcpy(in[k], src_in[k] + c0 * n_in[k], sizeof(double) * nc * n_in[k], hipMemcpyHostToDevice));
-        io = dev;
-        return HOMMX_OK;
-      },
-      [&](int64_t nc, const Sens2IO& io) { return sens2_run(p, nc, chunk, io, a, nullptr); },
-      [&](int64_t c0, int64_t nc, const Sens2IO& io) {
-        double* dst_out[] = {a.d2A, a.A_eff, a.dA};
-        for (int k = 0; k < 3; ++k)
-          if (n_out[k] && dst_out[k])
-            HIP_TRY(hipMemcpy(dst_out[k] + c0 * n_out[k], out[k], sizeof(double) * nc * n_out[k], hipMemcpyDeviceToHost));
-        if (a.info) HIP_TRY(hipMemcpy(a.info + c0, io.info, sizeof(int32_t) * nc, hipMemcpyDeviceToHost));
-        return HOMMX_OK;
-      });
+int sens2_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_sens2_args& args, bool device,
+               hipStream_t st) {
+  const int64_t tt = p->ks.t * p->ks.t, el = p->n_el * p->ks.n_comp;
+  Chunk<hommx_sens2_args> v{};
+  hommx_sens2_args& a = v.a = args;
+  const CellArray in[] = {{&a.dirs, a.n_dirs * el, a.per_cell ? PER_CELL : SHARED}};
+  const CellArray out[] = {{&a.d2A, a.n_dirs * a.n_dirs * tt}, {&a.A_eff, tt, KEPT}, {&a.dA, a.n_dirs * tt}};
+  return derived_call(p, n_cells, s, M, v, in, out, &a.info, sens2_extra(p), load_chunk, device, st,
+                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_sens2_args>& c) { return sens2_run(p, nc, chunk, c, st); });
 }
 
 }  // namespace
@@ -1437,84 +1178,85 @@ extern "C" {
 
 int hommx_reconstruct_batch_device(hommx_plan* p, int64_t n_cells, const double* d_coef, const double* d_M, const double* d_xi, double* d_stats,
                                    double* d_strain, double* d_flux, double* d_A_eff, int32_t* d_info, void* stream) {
-  if (int rc = recon_open(p, n_cells, d_coef, d_xi, d_stats, d_strain, d_flux, true); rc != GO) return rc;
-  return recon_device(p, n_cells, sampled_source(d_coef), d_M, d_xi, ReconRegions{}, d_stats, nullptr, d_strain, d_flux, d_A_eff, d_info,
-                      reinterpret_cast<hipStream_t>(stream));
+  const ReconCall a{d_xi, 0, nullptr, d_stats, nullptr, d_strain, d_flux, d_A_eff, d_info};
+  if (int rc = recon_open(p, n_cells, d_coef, a, true, [] { return HOMMX_OK; }); rc != GO) return rc;
+  return recon_call(p, n_cells, sampled_source(d_coef), d_M, a, true, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hommx_reconstruct_batch(hommx_plan* p, int64_t n_cells, const double* coef, const double* M, const double* xi, double* stats, double* strain,
                             double* flux, double* A_eff, int32_t* info) {
-  if (int rc = recon_open(p, n_cells, coef, xi, stats, strain, flux, false); rc != GO) return rc;
-  return recon_host(p, n_cells, sampled_source(coef), M, xi, 0, nullptr, stats, nullptr, strain, flux, A_eff, info);
+  const ReconCall a{xi, 0, nullptr, stats, nullptr, strain, flux, A_eff, info};
+  if (int rc = recon_open(p, n_cells, coef, a, false, [] { return HOMMX_OK; }); rc != GO) return rc;
+  return recon_call(p, n_cells, sampled_source(coef), M, a, false, nullptr);
 }
 
 int hommx_reconstruct_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const double* d_xi,
                                     int32_t n_regions, const uint8_t* d_region, double* d_stats, double* d_region_stats, double* d_strain,
                                     double* d_flux, double* d_A_eff, int32_t* d_info, void* stream) {
+  const ReconCall a{d_xi, n_regions, d_region, d_stats, d_region_stats, d_strain, d_flux, d_A_eff, d_info};
   auto more = [&] {
     if (int rc = coef_check(p, src)) return rc;
     return regions_check(src, n_regions, d_region, d_region_stats);
   };
-  if (int rc = recon_open(p, n_cells, src, d_xi, d_stats, d_strain, d_flux, true, more); rc != GO) return rc;
-  const hommx_coef_source s = source_of_form(*src);
-  return recon_device(p, n_cells, s, d_M, d_xi, ReconRegions{n_regions, n_regions ? (d_region ? d_region : s.mask) : nullptr}, d_stats,
-                      d_region_stats, d_strain, d_flux, d_A_eff, d_info, reinterpret_cast<hipStream_t>(stream));
+  if (int rc = recon_open(p, n_cells, src, a, true, more); rc != GO) return rc;
+  return recon_call(p, n_cells, source_of_form(*src), d_M, a, true, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hommx_reconstruct_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const double* xi, int32_t n_regions,
                              const uint8_t* region, double* stats, double* region_stats, double* strain, double* flux, double* A_eff,
                              int32_t* info) {
+  const ReconCall a{xi, n_regions, region, stats, region_stats, strain, flux, A_eff, info};
   auto more = [&] {
     if (int rc = coef_check(p, src)) return rc;
     return regions_check(src, n_regions, region, region_stats);
   };
-  if (int rc = recon_open(p, n_cells, src, xi, stats, strain, flux, false, more); rc != GO) return rc;
-  return recon_host(p, n_cells, source_of_form(*src), M, xi, n_regions, region, stats, region_stats, strain, flux, A_eff, info);
+  if (int rc = recon_open(p, n_cells, src, a, false, more); rc != GO) return rc;
+  return recon_call(p, n_cells, source_of_form(*src), M, a, false, nullptr);
 }
 
 int hommx_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const hommx_sens_args* args,
                                     void* stream) {
-  if (int rc = sens_open(p, n_cells, src, args, true); rc != GO) return rc;
-  return sens_device(p, n_cells, source_of_form(*src), d_M, *args, reinterpret_cast<hipStream_t>(stream));
+  if (int rc = source_open(p, n_cells, src, args, true, [&] { return sens_checks(args); }); rc != GO) return rc;
+  return sens_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hommx_sensitivity_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_sens_args* args) {
-  if (int rc = sens_open(p, n_cells, src, args, false); rc != GO) return rc;
-  return sens_host(p, n_cells, source_of_form(*src), M, *args);
+  if (int rc = source_open(p, n_cells, src, args, false, [&] { return sens_checks(args); }); rc != GO) return rc;
+  return sens_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
 }
 
 int hommx_stratification_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                                                    const hommx_strat_sens_args* args, void* stream) {
-  if (int rc = strat_open(p, n_cells, src, args, true); rc != GO) return rc;
-  return strat_device(p, n_cells, source_of_form(*src), d_M, *args, reinterpret_cast<hipStream_t>(stream));
+  if (int rc = source_open(p, n_cells, src, args, true, [&] { return strat_checks(args); }); rc != GO) return rc;
+  return strat_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hommx_stratification_sensitivity_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M,
                                             const hommx_strat_sens_args* args) {
-  if (int rc = strat_open(p, n_cells, src, args, false); rc != GO) return rc;
-  return strat_host(p, n_cells, source_of_form(*src), M, *args);
+  if (int rc = source_open(p, n_cells, src, args, false, [&] { return strat_checks(args); }); rc != GO) return rc;
+  return strat_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
 }
 
 int hommx_loads_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const hommx_load_args* args,
                                void* stream) {
   if (int rc = loads_open(p, n_cells, src, args, true); rc != GO) return rc;
-  return loads_device(p, n_cells, source_of_form(*src), d_M, *args, reinterpret_cast<hipStream_t>(stream));
+  return loads_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hommx_loads_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_load_args* args) {
   if (int rc = loads_open(p, n_cells, src, args, false); rc != GO) return rc;
-  return loads_host(p, n_cells, source_of_form(*src), M, *args);
+  return loads_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
 }
 
 int hommx_second_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                                            const hommx_sens2_args* args, void* stream) {
   if (int rc = sens2_open(p, n_cells, src, args, true); rc != GO) return rc;
-  return sens2_device(p, n_cells, source_of_form(*src), d_M, *args, reinterpret_cast<hipStream_t>(stream));
+  return sens2_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hommx_second_sensitivity_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_sens2_args* args) {
   if (int rc = sens2_open(p, n_cells, src, args, false); rc != GO) return rc;
-  return sens2_host(p, n_cells, source_of_form(*src), M, *args);
+  return sens2_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
 }
 
 int hommx_calibrate_fp64(int device, double* mfma_flops_per_s, double* fma_flops_per_s) {
