@@ -24,6 +24,8 @@ MESH_FLAG_LOADS = 2  # HOMMX_MESH_FLAG_LOADS
 COEF_SAMPLED = 0  # HOMMX_COEF_*: the form of a hommx_coef_source
 COEF_TWO_PHASE = 1
 COEF_SEPARABLE = 2
+COEF_PROGRAM = 3
+PROGRAM_MAX_OPS, PROGRAM_MAX_CONSTS, PROGRAM_MAX_STACK = 128, 32, 16  # the limits of a hommx_coef_program
 RECON_MAX_REGIONS = 8  # HOMMX_RECON_MAX_REGIONS
 SENS_MAX_DIRS = 8  # HOMMX_SENS_MAX_DIRS
 
@@ -54,6 +56,19 @@ class MeshDesc(C.Structure):
     ]
 
 
+class CoefProgram(C.Structure):
+    """hommx_coef_program: the postfix program of an expression coefficient (host memory, also in the device entries)."""
+
+    _fields_ = [
+        ("n_ops", C.c_int32),
+        ("n_consts", C.c_int32),
+        ("n_comp", C.c_int32),
+        ("reserved", C.c_int32),
+        ("ops", C.c_void_p),
+        ("consts", C.c_void_p),
+    ]
+
+
 class CoefSource(C.Structure):
     """hommx_coef_source: only the pointers of ``form`` are read."""
 
@@ -68,6 +83,7 @@ class CoefSource(C.Structure):
         ("table", C.c_void_p),
         ("weights", C.c_void_p),
         ("params", C.c_void_p),
+        ("program", C.POINTER(CoefProgram)),
     ]
 
 
@@ -160,6 +176,10 @@ def _prototypes() -> dict:
         "hommx_solve_batch": (c_int, [vp, i64, vp, vp, vp, vp]),
         "hommx_solve_batch_device": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_correctors": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
+        "hommx_solve_batch_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, vp]),
+        "hommx_solve_batch_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, vp, vp]),
+        "hommx_expand_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp]),
+        "hommx_expand_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp]),
         "hommx_reconstruct_batch": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_reconstruct_batch_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_reconstruct_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),

@@ -228,9 +228,24 @@ def region_labels(labels, n_el: int, n_regions: int | None = None) -> tuple[np.n
 
 
 @dataclass(frozen=True)
+class Program:
+    """The postfix program of an expression coefficient (include/hommx_hip.h, hommx_coef_program; ``hommx_amd.expr.Expression.program``):
+    ops[n_ops, 2] uint8 = (opcode, operand), consts[n_consts] float64, and the number of components it stores."""
+
+    ops: np.ndarray
+    consts: np.ndarray
+    n_comp: int
+
+    def struct(self) -> "_lib.CoefProgram":
+        """The hommx_coef_program that points into this program's arrays (host memory; keep ``self`` alive while it is in use)."""
+        return _lib.CoefProgram(int(self.ops.shape[0]), int(self.consts.size), int(self.n_comp), 0, self.ops.ctypes.data,
+                                self.consts.ctypes.data if self.consts.size else None)
+
+
+@dataclass(frozen=True)
 class CoefStream:
-    """The coefficient of a block of macro cells in one of the three forms the library takes (include/hommx_hip.h): sampled element means,
-    phase mask + two values per cell, table of g + (a, b) per cell.  ``method`` names the plan's host method (``method + "_device"`` is its
+    """The coefficient of a block of macro cells in one of the four forms the library takes (include/hommx_hip.h): sampled element means,
+    phase mask + two values per cell, table of g + (a, b) per cell, program of an expression + quadrature points + midpoint per cell.  ``method`` names the plan's host method (``method + "_device"`` is its
     device twin), ``shared`` holds the arguments every cell shares in the order that method takes them, ``per_cell`` is the one array whose
     first axis is the macro cell: ``plan.<method>(*shared, per_cell, M, return_info=...)``."""
 
@@ -252,17 +267,32 @@ class CoefStream:
                                        None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)),
                    np.ascontiguousarray(params, dtype=np.float64))
 
+    @classmethod
+    def program(cls, points, weights, ops, consts, n_comp: int, midpoints) -> "CoefStream":
+        """An expression coefficient: points[n_el, n_q, dim] and weights[n_q] of the micro quadrature rule, the program of
+        ``Expression.program()`` with its number of components, midpoints[N_c, 3] of the macro cells."""
+        prog = Program(np.ascontiguousarray(ops, dtype=np.uint8).reshape(-1, 2), np.ascontiguousarray(consts, dtype=np.float64).ravel(), int(n_comp))
+        return cls("solve_program", (np.ascontiguousarray(points, dtype=np.float64), np.ascontiguousarray(weights, dtype=np.float64), prog),
+                   np.ascontiguousarray(midpoints, dtype=np.float64))
+
     def __len__(self) -> int:
         return self.per_cell.shape[0]
 
     def coef_source(self, address=lambda a: a.ctypes.data) -> "_lib.CoefSource":
-        """The stream as the hommx_coef_source of the reconstruct entry points: the one place that spells the three forms for them.
-        ``address(array) -> pointer``: the array's own address (host entry; the stream keeps the arrays alive), or an upload."""
+        """The stream as the hommx_coef_source of the entry points that take one: the one place that spells the four forms for them.
+        ``address(array) -> pointer``: the array's own address (host entry; the stream keeps the arrays alive), or an upload.  The
+        program of an expression is host memory either way; the source keeps its struct alive."""
         src = _lib.CoefSource()
         if self.method == "solve":
             src.form, src.coef = _lib.COEF_SAMPLED, address(self.per_cell)
         elif self.method == "solve_two_phase":
             src.form, src.mask, src.values = _lib.COEF_TWO_PHASE, address(self.shared[0]), address(self.per_cell)
+        elif self.method == "solve_program":
+            points, weights, prog = self.shared
+            src.form, src.n_q = _lib.COEF_PROGRAM, int(points.shape[1])
+            src.table, src.weights, src.params = address(points), address(weights), address(self.per_cell)
+            src._program = (prog, prog.struct())  # ctypes keeps no reference to what a pointer member points at
+            src.program = C.pointer(src._program[1])
         else:
             family, table, weights = self.shared
             src.form, src.table, src.params = _lib.COEF_SEPARABLE, address(table), address(self.per_cell)
@@ -281,7 +311,9 @@ class CoefStream:
 
     def solve_device(self, plan: "MicroCellPlan", upload, M_ptr, out_ptr, info_ptr, stream):
         """Through the device twin of the method: ``upload(array) -> device pointer`` copies every array of the stream to the plan's device."""
-        args = [a if a is None or isinstance(a, str) else upload(a) for a in self.shared]
+        args = [a if a is None or isinstance(a, (str, Program)) else upload(a) for a in self.shared]
+        if self.method == "solve_program":  # the device twin is told n_q as well
+            args.insert(2, int(self.shared[0].shape[1]))
         if self.method == "solve_separable":  # the device twin is told n_q; the host method reads it off the table
             args.insert(1, 1 if self.shared[0] == "affine" else int(self.shared[1].shape[1]))
         getattr(plan, self.method + "_device")(len(self), *args, upload(self.per_cell), M_ptr, out_ptr, info_ptr, stream)
@@ -449,6 +481,17 @@ class MicroCellPlan:
                 raise ValueError(f"mask has shape {stream.shared[0].shape}; expected ({self.n_el},)")
             if stream.per_cell.size != nc * 2 * self.n_comp:
                 raise ValueError(f"values has shape {stream.per_cell.shape}; expected ({nc}, 2" + (f", {self.n_comp})" if self.n_comp > 1 else ")"))
+            return nc
+        if stream.method == "solve_program":
+            points, weights, prog = stream.shared
+            if points.ndim != 3 or points.shape[0] != self.n_el or points.shape[2] != self.dim or points.shape[1] < 1:
+                raise ValueError(f"points has shape {points.shape}; expected ({self.n_el}, n_q, {self.dim})")
+            if weights.shape != (points.shape[1],):
+                raise ValueError(f"weights must have shape ({points.shape[1]},)")
+            if stream.per_cell.shape != (nc, 3):
+                raise ValueError(f"midpoints has shape {stream.per_cell.shape}; expected ({nc}, 3)")
+            if prog.n_comp != self.n_comp:
+                raise ValueError(f"the expression has {prog.n_comp} components; the plan's coefficient has {self.n_comp}")
             return nc
         family, table, weights = stream.shared
         nq = 1 if family == "affine" else int(table.shape[1])
@@ -638,7 +681,48 @@ class MicroCellPlan:
         return self._host_call("hommx_solve_batch_separable", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch_separable(
             self._h, nc, fam, nq, table.ctypes.data, None if w is None else w.ctypes.data, params.ctypes.data, Mp, o, i), return_info)
 
+    def solve_program(self, points: np.ndarray, weights: np.ndarray, program: Program, midpoints: np.ndarray, M: np.ndarray | None = None,
+                      return_info: bool = False):
+        """Expression coefficient sampled on the device (include/hommx_hip.h, HOMMX_COEF_PROGRAM): points[n_el, n_q, dim] and
+        weights[n_q] of the micro quadrature rule, the program, midpoints[N_c, 3] of the macro cells -> A_eff[N_c, t, t]."""
+        stream = CoefStream("solve_program", (np.ascontiguousarray(points, dtype=np.float64), np.ascontiguousarray(weights, dtype=np.float64), program),
+                            np.ascontiguousarray(midpoints, dtype=np.float64))
+        nc = self._check_stream(stream)
+        src = stream.coef_source()
+        return self._host_call("hommx_solve_batch_source", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch_source(
+            self._h, nc, C.byref(src), Mp, o, i), return_info)
+
+    def expand(self, stream: CoefStream) -> np.ndarray:
+        """The element stream coef[N_c, n_el(, n_comp)] the library expands ``stream`` to on the device (hommx_expand_source): what
+        ``solve`` would be given.  A program's stream equals ``Expression.host_stream`` bit for bit for exactly rounded operations."""
+        nc = self._check_stream(stream)
+        out = np.empty((nc, self.n_el) + ((self.n_comp,) if self.n_comp > 1 else ()), dtype=np.float64)
+        if nc:
+            src = stream.coef_source()
+            _lib.check(self._lib.hommx_expand_source(self._h, nc, C.byref(src), out.ctypes.data), "hommx_expand_source")
+        return out
+
     # -- device pointers (torch tensors or raw ints), asynchronous --------------------------------
+    def solve_source_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, out_ptr: int, info_ptr: int | None,
+                            stream: int | None = None):
+        """Device-pointer solve of a coefficient in any form (hommx_solve_batch_source_device), asynchronous on ``stream``: ``source`` =
+        ``CoefStream.coef_source(upload)`` with device addresses."""
+        _lib.check(self._lib.hommx_solve_batch_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, out_ptr, info_ptr or None,
+                                                             stream or None), "hommx_solve_batch_source_device")
+
+    def expand_device(self, n_cells: int, source: "_lib.CoefSource", out_ptr: int, stream: int | None = None):
+        """Device-pointer form of ``expand`` (hommx_expand_source_device), asynchronous on ``stream``."""
+        _lib.check(self._lib.hommx_expand_source_device(self._h, int(n_cells), C.byref(source), out_ptr, stream or None),
+                   "hommx_expand_source_device")
+
+    def solve_program_device(self, n_cells: int, points_ptr: int, weights_ptr: int, n_q: int, program: Program, midpoints_ptr: int,
+                             M_ptr: int | None, out_ptr: int, info_ptr: int | None, stream: int | None = None):
+        """Device twin of ``solve_program``: the points, weights and midpoints are device pointers, the program stays host memory."""
+        prog = program.struct()
+        src = _lib.CoefSource(form=_lib.COEF_PROGRAM, n_q=int(n_q), table=points_ptr, weights=weights_ptr, params=midpoints_ptr,
+                              program=C.pointer(prog))
+        self.solve_source_device(n_cells, src, M_ptr, out_ptr, info_ptr, stream)
+
     def reconstruct_device(self, n_cells: int, coef_ptr: int, M_ptr: int | None, xi_ptr: int, stats_ptr: int, strain_ptr: int | None = None,
                            flux_ptr: int | None = None, A_ptr: int | None = None, info_ptr: int | None = None, stream: int | None = None):
         """Device-pointer form of ``reconstruct`` (hommx_reconstruct_batch_device), asynchronous on ``stream``: stats[n_cells, 2t + 3] =

@@ -15,6 +15,7 @@
 
 #include "../../include/hommx_hip.h"
 #include "blocked_internal.h"
+#include "coef_program.h"
 #include "host_common.h"
 #include "kernels.h"
 #include "mesh_front.h"
@@ -257,11 +258,65 @@ hommx_coef_source separable_source(int32_t family, int32_t n_q, const double* ta
   s.params = params;
   return s;
 }
-// a caller's source that coef_check has passed (the pointers of other forms are not the caller's to set)
+hommx_coef_source program_source(const hommx_coef_program* program, int32_t n_q, const double* points, const double* weights,
+                                 const double* midpoints) {
+  hommx_coef_source s{};
+  s.form = HOMMX_COEF_PROGRAM;
+  s.n_q = n_q;
+  s.table = points;
+  s.weights = weights;
+  s.params = midpoints;
+  s.program = program;
+  return s;
+}
+// a caller's source that coef_check has passed (the pointers of other forms are not the caller's to set; `program`, the member a
+// caller built against the shorter struct does not have, is read for its own form only)
 hommx_coef_source source_of_form(const hommx_coef_source& s) {
   if (s.form == HOMMX_COEF_SAMPLED) return sampled_source(s.coef);
   if (s.form == HOMMX_COEF_TWO_PHASE) return two_phase_source(s.mask, s.values);
+  if (s.form == HOMMX_COEF_PROGRAM) return program_source(s.program, s.n_q, s.table, s.weights, s.params);
   return separable_source(s.family, s.n_q, s.table, s.weights, s.params);
+}
+
+// The whole program of a HOMMX_COEF_PROGRAM source against the plan's descriptor, on the host: the kernel then interprets it unchecked
+int program_check(const hommx_plan* p, const hommx_coef_source* s) {
+  if (p->desc.kind == HOMMX_KIND_ELASTICITY_VOIGT)
+    return fail(HOMMX_EINVAL, "expression coefficients are not supported for the 21-component Voigt kind");
+  const hommx_coef_program* g = s->program;
+  if (!g) return fail(HOMMX_EINVAL, "null program");
+  if (g->n_ops < 1 || g->n_ops > hommx::PROGRAM_MAX_OPS)
+    return fail(HOMMX_EINVAL, "program: n_ops must be 1 .. %d, got %d", hommx::PROGRAM_MAX_OPS, g->n_ops);
+  if (g->n_consts < 0 || g->n_consts > hommx::PROGRAM_MAX_CONSTS)
+    return fail(HOMMX_EINVAL, "program: n_consts must be 0 .. %d, got %d", hommx::PROGRAM_MAX_CONSTS, g->n_consts);
+  const int n_comp = hommx::kind_sizes(p->desc.dim, p->desc.kind).n_comp;
+  if (g->n_comp != n_comp) return fail(HOMMX_EINVAL, "program: n_comp is %d, the plan's coefficient has %d components", g->n_comp, n_comp);
+  if (!g->ops || (g->n_consts > 0 && !g->consts)) return fail(HOMMX_EINVAL, "null program ops / consts");
+  if (s->n_q < 1) return fail(HOMMX_EINVAL, "program source needs n_q >= 1");
+  if (!s->table || !s->weights || !s->params) return fail(HOMMX_EINVAL, "null table / weights / params");
+  int depth = 0;
+  bool stored[hommx::PROGRAM_MAX_COMP] = {};
+  for (int pc = 0; pc < g->n_ops; ++pc) {
+    const int op = g->ops[2 * pc], k = g->ops[2 * pc + 1];
+    if (op >= hommx::OP_COUNT) return fail(HOMMX_EINVAL, "program: unknown opcode %d at instruction %d", op, pc);
+    if (op == hommx::OP_CONST && k >= g->n_consts)
+      return fail(HOMMX_EINVAL, "program: constant index %d out of range [0,%d) at instruction %d", k, g->n_consts, pc);
+    if (op == hommx::OP_X && k >= 3) return fail(HOMMX_EINVAL, "program: x index %d out of range [0,3) at instruction %d", k, pc);
+    if (op == hommx::OP_Y && k >= p->desc.dim)
+      return fail(HOMMX_EINVAL, "program: y index %d out of range [0,%d) at instruction %d", k, p->desc.dim, pc);
+    if (depth < hommx::op_pops(op)) return fail(HOMMX_EINVAL, "program: stack underflow at instruction %d", pc);
+    depth += hommx::op_pushes(op) - hommx::op_pops(op);
+    if (depth > hommx::PROGRAM_MAX_STACK)
+      return fail(HOMMX_EINVAL, "program: stack depth above %d at instruction %d", hommx::PROGRAM_MAX_STACK, pc);
+    if (op == hommx::OP_STORE) {
+      if (k >= n_comp) return fail(HOMMX_EINVAL, "program: component index %d out of range [0,%d) at instruction %d", k, n_comp, pc);
+      if (stored[k]) return fail(HOMMX_EINVAL, "program: component %d stored twice (instruction %d)", k, pc);
+      stored[k] = true;
+    }
+  }
+  if (depth != 0) return fail(HOMMX_EINVAL, "program: %d values left on the stack at the end", depth);
+  for (int c = 0; c < n_comp; ++c)
+    if (!stored[c]) return fail(HOMMX_EINVAL, "program: component %d never stored", c);
+  return HOMMX_OK;
 }
 
 // What every entry point checks of a coefficient source: the form, its pointers, the restrictions of a separable sampler.  `separable_ptrs`
@@ -272,6 +327,7 @@ int coef_check(const hommx_plan* p, const hommx_coef_source* s, const char* sepa
     case HOMMX_COEF_SAMPLED: return s->coef ? HOMMX_OK : fail(HOMMX_EINVAL, "null coef");
     case HOMMX_COEF_TWO_PHASE: return s->mask && s->values ? HOMMX_OK : fail(HOMMX_EINVAL, "null mask / values");
     case HOMMX_COEF_SEPARABLE: break;
+    case HOMMX_COEF_PROGRAM: return program_check(p, s);
     default: return fail(HOMMX_EINVAL, "unknown coefficient form %d", s->form);
   }
   if (p->desc.kind != HOMMX_KIND_POISSON_SCALAR && p->desc.kind != HOMMX_KIND_ELASTICITY_ISO)
@@ -304,39 +360,63 @@ const double* per_cell(const hommx_coef_source& s) {
   return s.form == HOMMX_COEF_SAMPLED ? s.coef : s.form == HOMMX_COEF_TWO_PHASE ? s.values : s.params;
 }
 
+// the program of a checked HOMMX_COEF_PROGRAM source as the kernel takes it
+hommx::ProgramArgs program_args(const hommx_coef_program& g) {
+  hommx::ProgramArgs a{};
+  memcpy(a.code, g.ops, 2 * (size_t)g.n_ops);
+  if (g.n_consts) memcpy(a.consts, g.consts, sizeof(double) * g.n_consts);
+  a.n_ops = g.n_ops;
+  a.n_comp = g.n_comp;
+  return a;
+}
+
+// doubles per cell of the per-cell array of a sampler form (per_cell), and entries of its table
+int64_t per_cell_doubles(const hommx_plan* p, const hommx_coef_source& s) { return s.form == HOMMX_COEF_PROGRAM ? 3 : 2 * p->ks.n_comp; }
+int64_t table_doubles(const hommx_plan* p, const hommx_coef_source& s) {
+  return p->n_el * s.n_q * (s.form == HOMMX_COEF_PROGRAM ? p->desc.dim : 1);
+}
+
 // -- the element stream of a source ---------------------------------------------------------------------------------------------------
 // Cells per chunk of a source, given the `want` of the caller: a sampler form is expanded into the plan's element stream, at most 1 GiB of
 // it (at least one cell), which is grown here; a sampled stream has no such limit
+int64_t stream_cells(const hommx_plan* p, int64_t want) {
+  return std::min(want, std::max<int64_t>((1ll << 27) / std::max<int64_t>(p->n_el * p->ks.n_comp, 1), 1));
+}
 int stream_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t want, int64_t* chunk) {
   *chunk = want;
   if (s.form == HOMMX_COEF_SAMPLED) return HOMMX_OK;
-  const int64_t per = p->n_el * p->ks.n_comp;
-  *chunk = std::min(want, std::max<int64_t>((1ll << 27) / std::max<int64_t>(per, 1), 1));
-  return grow(p->buf[B_EXPAND], sizeof(double) * *chunk * per);
+  *chunk = stream_cells(p, want);
+  return grow(p->buf[B_EXPAND], sizeof(double) * *chunk * p->n_el * p->ks.n_comp);
 }
 
 // *stream: the element stream of cells [c0, c0 + nc) of a source on the device.  A sampled stream is a view of the caller's; a sampler
-// form is expanded into the plan's element stream (nc <= the chunk of stream_chunk)
-int expand_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t c0, int64_t nc, hipStream_t st, const double** stream) {
+// form is expanded into the plan's element stream (nc <= the chunk of stream_chunk) or, if given, into `into`
+int expand_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t c0, int64_t nc, hipStream_t st, const double** stream,
+                 double* into = nullptr) {
   const int n_comp = p->ks.n_comp;
   if (s.form == HOMMX_COEF_SAMPLED) {
     *stream = s.coef + c0 * p->n_el * n_comp;
     return HOMMX_OK;
   }
-  double* dst = static_cast<double*>(p->buf[B_EXPAND].p);
+  double* dst = into ? into : static_cast<double*>(p->buf[B_EXPAND].p);
   if (s.form == HOMMX_COEF_TWO_PHASE)
     HIP_TRY(hommx::launch_expand_two_phase(s.mask, s.values + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st));
+  else if (s.form == HOMMX_COEF_PROGRAM)
+    HIP_TRY(hommx::launch_expand_program(program_args(*s.program), s.table, s.weights, s.n_q, p->desc.dim, s.params + c0 * 3, dst, p->n_el,
+                                         nc, st));
   else
     HIP_TRY(hommx::launch_expand_separable(sampler_source(s), s.params + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st));
   *stream = dst;
   return HOMMX_OK;
 }
 
-// A source on the device, solved: what the three *_device solve entry points do.  The fused 2D kernel samples every form itself.  The
-// other families read an element stream: a sampled one goes to the route in one call, a sampler form chunk by chunk of stream_chunk
+// A source on the device, solved: what the *_device solve entry points do.  The fused 2D kernel samples the two-phase and separable
+// forms itself; a program is expanded chunk by chunk and solved in the kernel's STREAM mode.  The other families read an element
+// stream: a sampled one goes to the route in one call, a sampler form chunk by chunk of stream_chunk
 int solve_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* d_M, double* d_A_eff, int32_t* d_info,
                         hipStream_t st) {
-  if (p->family == FAM_FUSED2D) {
+  const bool fused = p->family == FAM_FUSED2D;
+  if (fused && s.form != HOMMX_COEF_PROGRAM) {
     HIP_TRY(hommx::launch_poisson2d_fused(per_cell(s), d_M, d_A_eff, d_info, p->desc.n_micro, n_cells, st, sampler_source(s)));
     return HOMMX_OK;
   }
@@ -347,8 +427,13 @@ int solve_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source&
     const int64_t nc = (n_cells - c0 < chunk) ? n_cells - c0 : chunk;
     const double* stream = nullptr;
     if (int rc = expand_chunk(p, s, c0, nc, st, &stream)) return rc;
-    int rc = route_solve(p, nc, stream, d_M ? d_M + c0 * d * d : nullptr, d_A_eff + c0 * t * t, d_info ? d_info + c0 : nullptr, st);
-    if (rc != HOMMX_OK) return rc;
+    const double* M = d_M ? d_M + c0 * d * d : nullptr;
+    int32_t* info = d_info ? d_info + c0 : nullptr;
+    if (fused) {
+      HIP_TRY(hommx::launch_poisson2d_fused(stream, M, d_A_eff + c0 * t * t, info, p->desc.n_micro, nc, st));
+      continue;
+    }
+    if (int rc = route_solve(p, nc, stream, M, d_A_eff + c0 * t * t, info, st)) return rc;
   }
   return HOMMX_OK;
 }
@@ -375,19 +460,19 @@ int stage_in(hommx_plan* p, const hommx::HostPiece (&in)[N]) {
 // it is, and ds->coef is null: the stream is no device pointer), with one more input of the entry point; *ds: the source with the
 // device copies
 int stage_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, hommx::HostPiece more, hommx_coef_source* ds) {
-  const size_t nval = sizeof(double) * n_cells * 2 * p->ks.n_comp;
+  const size_t nval = sizeof(double) * n_cells * per_cell_doubles(p, s);
   *ds = s;
   ds->coef = nullptr;
   const hommx::HostPiece in[] = {{s.mask, (size_t)p->n_el, (const void**)&ds->mask},
                                  {s.values, nval, (const void**)&ds->values},
-                                 {s.table, sizeof(double) * p->n_el * s.n_q, (const void**)&ds->table},
+                                 {s.table, sizeof(double) * table_doubles(p, s), (const void**)&ds->table},
                                  {s.weights, sizeof(double) * s.n_q, (const void**)&ds->weights},
                                  {s.params, nval, (const void**)&ds->params},
                                  more};
   return stage_in(p, in);
 }
 
-// hommx_solve_batch_two_phase / _separable: the source and M go in staged, the outputs come back the same way, the call synchronises once
+// hommx_solve_batch_two_phase / _separable / _source: the source and M go in staged, the outputs come back the same way, the call synchronises once
 int solve_source_host(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, double* A_eff, int32_t* info) {
   const int d = p->desc.dim;
   const size_t out_bytes[] = {sizeof(double) * n_cells * p->ks.t * p->ks.t, sizeof(int32_t) * n_cells};
@@ -664,6 +749,58 @@ int hommx_solve_batch_separable(hommx_plan* p, int64_t n_cells, int32_t family, 
   const hommx_coef_source s = separable_source(family, n_q, table, weights, params);
   if (int rc = open_call(p, n_cells, true, "", false, [&] { return coef_check(p, &s, names, A_eff); }); rc != GO) return rc;
   return solve_source_host(p, n_cells, s, M, A_eff, info);
+}
+
+int hommx_solve_batch_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M, double* d_A_eff,
+                                    int32_t* d_info, void* stream) {
+  if (int rc = open_call(p, n_cells, d_A_eff, "A_eff", true, [&] { return coef_check(p, src); }); rc != GO) return rc;
+  return solve_source_device(p, n_cells, source_of_form(*src), d_M, d_A_eff, d_info, reinterpret_cast<hipStream_t>(stream));
+}
+
+int hommx_solve_batch_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, double* A_eff, int32_t* info) {
+  if (int rc = open_call(p, n_cells, A_eff, "A_eff", false, [&] { return coef_check(p, src); }); rc != GO) return rc;
+  if (src->form == HOMMX_COEF_SAMPLED) return hommx_solve_batch(p, n_cells, src->coef, M, A_eff, info);  // the pipelined copy of the stream
+  return solve_source_host(p, n_cells, source_of_form(*src), M, A_eff, info);
+}
+
+int hommx_expand_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, double* d_coef_out, void* stream) {
+  if (int rc = open_call(p, n_cells, d_coef_out, "coef_out", true, [&] { return coef_check(p, src); }); rc != GO) return rc;
+  const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const hommx_coef_source s = source_of_form(*src);
+  const int64_t per = p->n_el * p->ks.n_comp;
+  if (s.form == HOMMX_COEF_SAMPLED) {
+    HIP_TRY(hipMemcpyAsync(d_coef_out, s.coef, sizeof(double) * n_cells * per, hipMemcpyDeviceToDevice, st));
+    return HOMMX_OK;
+  }
+  const int64_t chunk = stream_cells(p, n_cells);  // straight into the caller's array, in launches of at most 1 GiB of stream
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    const double* at = nullptr;
+    if (int rc = expand_chunk(p, s, c0, std::min(chunk, n_cells - c0), st, &at, d_coef_out + c0 * per)) return rc;
+  }
+  return HOMMX_OK;
+}
+
+int hommx_expand_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, double* coef_out) {
+  if (int rc = open_call(p, n_cells, coef_out, "coef_out", false, [&] { return coef_check(p, src); }); rc != GO) return rc;
+  const hommx_coef_source s = source_of_form(*src);
+  const int64_t per = p->n_el * p->ks.n_comp;
+  if (s.form == HOMMX_COEF_SAMPLED) {
+    memcpy(coef_out, s.coef, sizeof(double) * n_cells * per);
+    return HOMMX_OK;
+  }
+  hommx_coef_source ds;
+  const void* none = nullptr;
+  if (int rc = stage_source(p, n_cells, s, {nullptr, 0, &none}, &ds)) return rc;
+  int64_t chunk = 0;
+  if (int rc = stream_chunk(p, s, n_cells, &chunk)) return rc;
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    const int64_t nc = std::min(chunk, n_cells - c0);
+    const double* at = nullptr;
+    if (int rc = expand_chunk(p, ds, c0, nc, nullptr, &at)) return rc;
+    HIP_TRY(hipMemcpyAsync(coef_out + c0 * per, at, sizeof(double) * nc * per, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+  }
+  return HOMMX_OK;
 }
 
 int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* coef, const double* M, double* A_eff,

@@ -1,0 +1,38 @@
+// coef_program.h -- the bytecode of an expression coefficient (include/hommx_hip.h, HOMMX_COEF_PROGRAM): what api.hip validates on the
+// host and coef_program.hip interprets on the device.  hommx_amd/expr.py writes the same numbers.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace hommx {
+
+// A postfix program over a stack of doubles.  Every instruction is (opcode, operand); the operand is the index of CONST / X / Y / STORE
+// and unused otherwise.  A comparison leaves 1.0 or 0.0; AND / OR / NOT / SELECT read "non-zero" as true; SELECT takes (c, a, b), b on
+// top, and leaves c ? a : b, both evaluated; MIN / MAX leave (b < a ? b : a) / (b > a ? b : a) for (a, b), b on top; STORE c pops the
+// value of component c at this quadrature point
+enum CoefOp : uint8_t {
+  OP_CONST = 0, OP_X, OP_Y, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_NEG, OP_ABS, OP_MIN, OP_MAX, OP_LT, OP_LE, OP_GT, OP_GE, OP_AND, OP_OR,
+  OP_NOT, OP_SELECT, OP_SQRT, OP_SIN, OP_COS, OP_TAN, OP_EXP, OP_LOG, OP_TANH, OP_DUP, OP_STORE, OP_COUNT
+};
+constexpr int PROGRAM_MAX_OPS = 128, PROGRAM_MAX_CONSTS = 32, PROGRAM_MAX_STACK = 16, PROGRAM_MAX_COMP = 6;
+
+// values an instruction takes from the stack / leaves on it
+constexpr int op_pops(int op) {
+  return op <= OP_Y ? 0 : op == OP_SELECT ? 3 : (op == OP_NEG || op == OP_ABS || op == OP_NOT || (op >= OP_SQRT && op <= OP_STORE)) ? 1 : 2;
+}
+constexpr int op_pushes(int op) { return op == OP_STORE ? 0 : op == OP_DUP ? 2 : 1; }
+
+// the program as the kernel takes it, by value in its arguments (wave-uniform: scalar loads).  code: the bytes of ops[n_ops][2], two
+// instructions per 32-bit word, so that the fetch is an aligned s_load_dword (a byte pair compiles to a vector global_load_ushort)
+struct ProgramArgs {
+  uint32_t code[PROGRAM_MAX_OPS / 2];
+  double consts[PROGRAM_MAX_CONSTS];
+  int n_ops = 0, n_comp = 0;
+};
+
+// coef_program.hip: coef[cell][el][comp] = sum_q w[q] * program(x = mid[cell], y = points[el][q]) as separately rounded operations,
+// q ascending from 0.  points [n_el][n_q][dim], weights [n_q], mid [ncells][3], all on the device; `prog` has passed the host validation
+hipError_t launch_expand_program(const ProgramArgs& prog, const double* d_points, const double* d_weights, int n_q, int dim,
+                                 const double* d_mid, double* d_coef, long long n_el, long long ncells, hipStream_t stream);
+
+}  // namespace hommx

@@ -30,6 +30,7 @@ import scipy.sparse.linalg as spla
 from . import fem
 from .batch import (REGION_FIELDS, CoefStream, LoadResponse, MicroCellPlan, Reconstruction, SecondSensitivities, Sensitivities,
                     StratSensitivities, region_labels)
+from .expr import Expression
 from .mesh import Mesh, micro_cells_per_side
 
 _VOIGT = {2: [(0, 0), (1, 1), (0, 1)], 3: [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]}
@@ -224,7 +225,8 @@ class BaseHMM(ABC):
         degree): it looks at the samples of the first, the middle and the last macro cell -- piecewise constant on every micro
         element, or only a handful of distinct values over the cell -> centroid rule (degree 0), anything else -> degree 3 --
         logs the choice with its evidence at WARNING level and raises when the three cells disagree.  Pass an integer to choose
-        the rule yourself; ``TwoPhase`` / ``Separable`` coefficients carry their own degree and never guess.
+        the rule yourself; ``TwoPhase`` / ``Separable`` coefficients carry their own degree and never guess, and an ``Expression`` has
+        a tree: its degree is estimated from it by UFL's rules (``Expression.degree``), nothing is sampled and nothing is logged.
         ``device``: HIP device ordinal; resolved at the first solve (``dist.default_device``: the ordinal given to
         ``dist.select_device``, the process group's bound device, the torch device the caller selected, else LOCAL_RANK modulo the
         visible devices, else 0).
@@ -260,7 +262,7 @@ class BaseHMM(ABC):
                              f"quadrature_degree={quadrature_degree} would be ignored by the device sampler")
         self._quadrature_degree = quadrature_degree  # None: decided from the samples on first use (quadrature_degree_used)
         self.quadrature_degree_used: int | None = 0 if isinstance(A, TwoPhase) else quadrature_degree
-        if isinstance(A, Separable) and quadrature_degree is None:
+        if isinstance(A, (Separable, Expression)) and quadrature_degree is None:
             self.quadrature_degree_used = A.degree
         self._rhs_degree = rhs_quadrature_degree
         self._device = device  # None: resolved lazily in _ensure_plan (the solver may be built before init_process_group)
@@ -577,8 +579,10 @@ class BaseHMM(ABC):
         return d if self._kind == "poisson" else d * (d + 1) // 2
 
     def _micro_kind(self) -> str:
-        """Plan kind of the coefficient forms that are sampled on the device (scalar / Lame values)."""
-        return "poisson" if self._kind == "poisson" else "elasticity"
+        """Plan kind of the coefficient forms that are sampled on the device (scalar / Lame values; the matrix of an ``Expression``)."""
+        if self._kind == "poisson":
+            return "poisson_matrix" if isinstance(self._coeff, Expression) and self._coeff.shape == "matrix" else "poisson"
+        return "elasticity"
 
     def _device_form(self) -> str | None:
         """Plan method that samples this coefficient on the device, or None for sampled element means."""
@@ -587,16 +591,26 @@ class BaseHMM(ABC):
             return "solve_two_phase"
         if isinstance(co, Separable) and (self._kind == "poisson" or co.family == "affine"):  # Lame-valued: affine only
             return "solve_separable"
+        if isinstance(co, Expression):
+            fits = ("scalar", "matrix") if self._kind == "poisson" else ("lame",)
+            if co.shape not in fits or (co.shape == "matrix" and co.dim != self._tdim):
+                raise ValueError(f"an Expression for {type(self).__name__} must be " + (
+                    f"a scalar or a symmetric {self._tdim} x {self._tdim} matrix" if self._kind == "poisson" else "Expression(lam=..., mu=...)")
+                    + f"; got a {co.shape}" + (f" of size {co.dim}" if co.shape == "matrix" else ""))
+            if co.n_y > self._tdim:
+                raise ValueError(f"the Expression reads y[{co.n_y - 1}]; the micro mesh has {self._tdim} dimensions")
+            return "solve_program"
         return None
 
     def _coef_stream(self, cells: np.ndarray) -> tuple[CoefStream, str]:
         """The coefficient of ``cells`` as the plan takes it, and the plan kind: ``TwoPhase`` as one mask (evaluated at the element
         barycentres) + two values per cell, ``Separable`` as one table of g + (a, b) per cell (per Lame parameter for the elasticity
-        classes: test_integration_linear_elasticity.py:78-93), anything else as sampled element means.
+        classes: test_integration_linear_elasticity.py:78-93), an ``Expression`` as its program + the points of the micro quadrature rule
+        + the midpoint of every cell, anything else as sampled element means.
 
         What stands in ``self._plan`` is a ``MicroCellPlan`` or a stand-in for it (the CPU tests answer from a NumPy restatement).  A stand-in has
         ``t``, ``kind`` and ``solve(coef, M=None, return_info=False[, return_correctors])``; it may have ``reserve`` (needed by
-        ``prepare()``), ``reconstruct``, ``device``, ``solve_two_phase`` and ``solve_separable``.  Without the last two it gets those
+        ``prepare()``), ``reconstruct``, ``device``, ``solve_two_phase``, ``solve_separable`` and ``solve_program``.  Without the last three it gets those
         coefficients as element means: this is the one place that asks.  ``reconstruct(coef, xi, M, fields=...)`` is given element means
         as an array and a device-sampled coefficient as the ``CoefStream``, under the same rule."""
         form, kind = self._device_form(), self._micro_kind()
@@ -611,6 +625,8 @@ class BaseHMM(ABC):
                 raise ValueError("TwoPhase values must be scalars for PoissonHMM and Lame(lam, mu) for LinearElasticityHMM")
             return CoefStream.two_phase(mask, values), kind
         yq, w = self._quadrature_points()
+        if form == "solve_program":
+            return CoefStream.program(yq, w, *co.program(), co.n_comp, c), kind
         return CoefStream.separable(co.family, co.table(yq, w), w, co.params(c)), kind
 
     def _phase_mask(self) -> np.ndarray:

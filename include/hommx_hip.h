@@ -248,7 +248,7 @@ int hommx_reconstruct_batch_device(hommx_plan* plan, int64_t n_cells, const doub
                                    double* d_stats, double* d_strain, double* d_flux, double* d_A_eff, int32_t* d_info, void* stream);
 
 /*
- * Reconstruction from a coefficient in any of the three forms the solve entry points take, with optional per-region statistics.  The
+ * Reconstruction from a coefficient in any of the four forms the solve entry points take, with optional per-region statistics.  The
  * sampler forms send a few numbers per macro cell (hommx_solve_batch_two_phase / _separable) and are expanded into the plan's element
  * stream on the device, chunk by chunk (the smaller of HOMMX_RECON_MEM_MB of correctors and 1 GiB of stream): the stream the host would
  * form, bit for bit, so every output equals hommx_reconstruct_batch's on that stream.  Only the pointers of `form` are read:
@@ -257,6 +257,7 @@ int hommx_reconstruct_batch_device(hommx_plan* plan, int64_t n_cells, const doub
  *   HOMMX_COEF_TWO_PHASE   mask    [n_el] uint8, values [n_cells][2][n_comp]   as hommx_solve_batch_two_phase
  *   HOMMX_COEF_SEPARABLE   family, n_q, table, weights, params [n_cells][n_comp][2]   as hommx_solve_batch_separable, with its
  *                          restrictions on family and kind
+ *   HOMMX_COEF_PROGRAM     program, n_q, table [n_el][n_q][dim], weights [n_q], params [n_cells][3]   an expression, see hommx_coef_program
  *
  * Regions: region[n_el] (uint8) labels every micro element; with n_regions = R > 0 the call also returns, per cell and region r < R,
  *   region_stats[c][r] = [ volume | sum |K| s_K (t) | sum |K| q_K (t) | sum |K| s_K . q_K | max |q_K| | smallest K reaching it ]
@@ -273,6 +274,39 @@ int hommx_reconstruct_batch_device(hommx_plan* plan, int64_t n_cells, const doub
 #define HOMMX_COEF_SAMPLED 0
 #define HOMMX_COEF_TWO_PHASE 1
 #define HOMMX_COEF_SEPARABLE 2
+#define HOMMX_COEF_PROGRAM 3
+
+/*
+ * Expression coefficients sampled on the device: A(x, y) as a postfix program over a stack of doubles, interpreted by a hand-written
+ * kernel (csrc/coef_program.hip) -- the program is data, nothing is compiled at run time.  With the source's
+ *   table    [n_el][n_q][dim]   the points y_{K,q} of the micro quadrature rule on every micro element
+ *   weights  [n_q]              its weights,  n_q >= 1 their number
+ *   params   [n_cells][3]       the midpoint c_T of every macro cell (x of the expression)
+ * the element mean of component c is  A_K[c] = sum_q weights[q] * v_c(c_T, y_{K,q}),  accumulated as acc = acc + weights[q] * v from 0
+ * with q ascending, every operation of the program and of the sum one separately rounded IEEE-754 operation in the written order: a
+ * host that interprets the same program (hommx_amd.expr.Expression.host_stream) reproduces the element stream bit for bit when the
+ * program holds exactly rounded operations only (everything but SQRT .. TANH below), and to the accuracy of the device's math
+ * functions otherwise.  The stream is expanded into the plan's scratch chunk by chunk (at most 1 GiB) on EVERY
+ * plan -- a fused 2D plan then runs the mode that reads a sampled stream -- so every output equals the one of that stream, bit for bit.
+ *
+ * ops[n_ops][2] = (opcode, operand); the operand is the index of CONST / X / Y / STORE and ignored otherwise:
+ *    0 CONST k  push consts[k]      1 X i  push x[i], i < 3      2 Y i  push y[i], i < dim
+ *    3 ADD  4 SUB  5 MUL  6 DIV     (a, b) -> a op b, b on top
+ *    7 NEG  8 ABS                   9 MIN  10 MAX  (a, b) -> b < a ? b : a  /  b > a ? b : a
+ *   11 LT  12 LE  13 GT  14 GE      (a, b) -> 1.0 or 0.0         15 AND  16 OR  17 NOT  on "non-zero is true", -> 1.0 or 0.0
+ *   18 SELECT   (c, a, b) -> c != 0 ? a : b  (both evaluated)
+ *   19 SQRT  20 SIN  21 COS  22 TAN  23 EXP  24 LOG  25 TANH      26 DUP      27 STORE c  pop the value of component c
+ * Validation (HOMMX_EINVAL with a text naming the fault, on the host, before the plan's device is made current): a null program, ops
+ * or consts, n_q < 1, null table / weights / params; n_ops outside 1 .. 128, n_consts outside 0 .. 32; n_comp other than the plan's;
+ * a plan of the HOMMX_KIND_ELASTICITY_VOIGT kind (21 components: not supported); an unknown opcode; a CONST, X or Y index out of range;
+ * stack underflow; stack depth above 16; a component stored twice or never; values left on the stack at the end.
+ */
+typedef struct hommx_coef_program {
+  int32_t n_ops, n_consts, n_comp, reserved;
+  const uint8_t* ops;    /* [n_ops][2]: opcode, operand */
+  const double* consts;  /* [n_consts]                  */
+} hommx_coef_program;
+
 typedef struct hommx_coef_source {
   int32_t form;     /* HOMMX_COEF_*                                    */
   int32_t family;   /* HOMMX_SAMPLER_* (HOMMX_COEF_SEPARABLE)          */
@@ -284,7 +318,22 @@ typedef struct hommx_coef_source {
   const double* table;
   const double* weights;
   const double* params;
+  const hommx_coef_program* program; /* HOMMX_COEF_PROGRAM: host memory in the device entries too; read for that form ONLY, so a caller
+                                        built against the struct that ended with params is never read past its end */
 } hommx_coef_source;
+
+/* The generic twin of hommx_solve_batch / _two_phase / _separable: a coefficient source in any form (hommx_reconstruct_source lists
+ * them; only the pointers of `form` are read), M, A_eff and info as hommx_solve_batch.  The host entry sends the small arrays of a
+ * sampler form in one pinned block owned by the plan (a sampled stream goes the way of hommx_solve_batch). */
+int hommx_solve_batch_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, double* A_eff, int32_t* info);
+/* Same with DEVICE pointers (in *src as well; the structs themselves are host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
+int hommx_solve_batch_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M, double* d_A_eff,
+                                    int32_t* d_info, void* stream);
+/* The element stream a source expands to: coef_out[n_cells][n_el][n_comp], what hommx_solve_batch would be given (a sampled source is
+ * copied).  For checking a sampler against its host equivalent, and for callers that want the stream itself. */
+int hommx_expand_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, double* coef_out);
+/* Same with DEVICE pointers (in *src as well), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
+int hommx_expand_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, double* d_coef_out, void* stream);
 
 #define HOMMX_RECON_MAX_REGIONS 8
 #define HOMMX_RECON_NREGION(t) (2 * (t) + 4) /* [volume | sum strain(t) | sum flux(t) | energy | max_flux | argmax_element] */
