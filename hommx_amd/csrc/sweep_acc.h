@@ -17,9 +17,10 @@
 // pivot must be negative, normal and finite.
 //
 // Hazard rule (gfx9): a VGPR written by a VALU instruction must not be read through DPP within the next 2 wait states --
-// the hardware does NOT interlock (tools/probe_dpp64.hip shows the stale read).  All DPP reads therefore live in asm blocks
-// that start with `s_nop 1`, and every write to a matrix register between two blocks is itself inside such a block or
-// precedes its `s_nop`.
+// the hardware does NOT interlock (tools/probe_dpp64.hip shows the stale read; tools/probe_dpp64_rowmask.hip: the same under a
+// row_mask).  All DPP reads therefore live in asm blocks, and a block starts with `s_nop 1` unless the instruction order INSIDE the
+// asm statements already puts two vector instructions between every write of a matrix register and its next DPP read: that is the
+// case for pivots K >= 1 of the 16-sweep, whose row rule is tied in front of the bulk block (see Sweep<16>::step).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -88,10 +89,6 @@ __device__ __forceinline__ void row_rule2(double& a0, double& a1, double w0, dou
   asm(HOMMX_EXEC_SET("rlo", "rhi") "v_mov_b64 %[a0], %[w0]\n\tv_mov_b64 %[a1], %[w1]\n\t" HOMMX_EXEC_ALL
       : [a0] "+v"(a0), [a1] "+v"(a1) : [w0] "v"(w0), [w1] "v"(w1), [rlo] "i"(RLO), [rhi] "i"(RHI));
 }
-template <unsigned RLO, unsigned RHI>
-__device__ __forceinline__ void row_rule1(double& a0, double w0) {
-  asm(HOMMX_EXEC_SET("rlo", "rhi") "v_mov_b64 %[a0], %[w0]\n\t" HOMMX_EXEC_ALL : [a0] "+v"(a0) : [w0] "v"(w0), [rlo] "i"(RLO), [rhi] "i"(RHI));
-}
 // diagonal of a diagonal tile: register r holds it on the lanes (j = 4 r + k, k)
 template <int R> struct DiagMask {
   static constexpr unsigned lo = OneLane<0, 4 * R>::lo | OneLane<1, 4 * R + 1>::lo | OneLane<2, 4 * R + 2>::lo | OneLane<3, 4 * R + 3>::lo;
@@ -114,8 +111,10 @@ __device__ __forceinline__ unsigned lds_offset(T* p) {
 
 // "not a usable pivot" of T = -S: d must be negative, normal and finite, i.e. its high word in [0x80100000, 0xffefffff], i.e.
 // hi + 0x00100000 >= 0x80200000 without wrapping.  d comes from v_readlane; the sweep keeps the running minimum of hi + 0x00100000.
-// (The compiler folds the 32 minima into a v_min3_u32 chain AFTER the sweep; forcing them onto the scalar unit with inline asm puts
-// 2 SALU per pivot into the dependent chain behind v_readlane and costs 1 % of the kernel: measured, rejected.)
+// Left to the compiler the minima become a v_mov + v_min3_u32 chain on the vector unit (38 VALU per 32 pivots).  The 16-sweep keeps
+// them on the scalar unit instead, s_add_u32 + s_min_u32 per pivot INSIDE the bulk update block, between its vector instructions
+// (HOMMX_PIVMIN): right behind v_readlane, in the dependent chain of the pivot, the same two instructions cost 1 % of the kernel
+// (measured, rejected); behind the bulk block, in front of the next pivot's `w`, they give back a third of what they save.
 __device__ __forceinline__ double readlane_neg_pivot(double v, int lane, unsigned& mn) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
@@ -124,6 +123,12 @@ __device__ __forceinline__ double readlane_neg_pivot(double v, int lane, unsigne
   return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ int bad_pivot_min(unsigned mn) { return mn < 0x80200000u; }
+// the pivot and its high word, no minimum: the caller's asm block takes it
+__device__ __forceinline__ double readlane_pivot(double v, int lane, int& hi) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+  hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+  return __hiloint2double(hi, lo);
+}
 
 #define HOMMX_BC " row_newbcast:%[jk] row_mask:0xf bank_mask:0xf\n\t"
 // y += bcast(x) * wo ; x += bcast(x) * wk   (x = register of the pivot's column tile, y = the other column tile)
@@ -135,6 +140,9 @@ __device__ __forceinline__ int bad_pivot_min(unsigned mn) { return mn < 0x802000
 #define HOMMX_RCPE "v_fma_f64 %[e], -%[d], %[r], 1.0\n\t"
 #define HOMMX_RCPT "v_fma_f64 %[e], %[e], %[e], %[e]\n\t"
 #define HOMMX_RCPR "v_fma_f64 %[r], %[r], %[e], %[r]\n\t"
+// running minimum of the pivots' high words + 0x00100000 on the scalar unit (clobbers scc), in two pieces to go between vector instructions
+#define HOMMX_PIVADD "s_add_u32 %[t], %[h], 0x100000\n\t"
+#define HOMMX_PIVMIN "s_min_u32 %[m], %[m], %[t]\n\t"
 
 template <int NB> struct Sweep;
 
@@ -231,6 +239,17 @@ struct Sweep<16> {
   static constexpr int NB = 16, NT = 1;
   typedef double Mat[1][1][4];
 
+  // Order of a pivot (all of it on the dependent chain pivot -> pivot, so nothing that can wait stands in it):
+  //   w = u * -pinv | FMA of the register of row K + 1 | publish it, v_readlane the next pivot, slot K + 1 <- d - 1, fetch row K + 1 |
+  //   [row rule] | bulk block: v_rcp, the three other FMAs with the reciprocal's refinement and the pivot check between them.
+  // Row rule (row K <- w) of a[rK], two v_cndmask_b32 on a loop-invariant lane-row mask (cheaper than a move under an exec mask, literal or
+  // from a scalar register pair: 2 or 3 SALU + 1 move, measured).  For K % 4 != 3 that register is also the register of row K + 1: it has had
+  // its FMA in the first block and is no FMA operand of the bulk block, but it is handed to the bulk block as the untouched operand [z], so
+  // the selects stand between the two asm statements -- where the compiler puts them into the wait states v_readlane needs anyway, the
+  // cheapest place found (inside the bulk block behind v_rcp: 0.5 % slower; behind the bulk block: 0.7 % slower).  For K % 4 == 3 a[rK] is an
+  // FMA operand of the bulk block and the select follows it.  With that every write of the register the NEXT first block reads through DPP
+  // lies in front of the bulk block, and the bulk block's own last FMA is followed by its v_fma and the next `w`: two vector instructions
+  // either way, so the first block needs its `s_nop 1` only at K = 0, where the caller's code precedes it.
   template <int K>
   static __device__ __forceinline__ void step(Mat& a, double* ubuf, int lk, int j, unsigned& bad, double u0, double pinv, int npiv) {
     constexpr int jK = K, rK = K / 4, kK = K % 4;
@@ -241,27 +260,37 @@ struct Sweep<16> {
     const double w = u0 * -pinv;  // entry K arrives as d - 1: w[K] = 1/d - 1 (column rule)
     double nu0 = 0.0, pn = 1.0;
     if constexpr (more) {
-      asm volatile("s_nop 1\n\t" HOMMX_ONE("x") : [x] "+v"(a[0][0][rK1]) : [wk] "v"(w), [jk] "n"(jK));
+      if constexpr (K == 0) asm volatile("s_nop 1\n\t" HOMMX_ONE("x") : [x] "+v"(a[0][0][rK1]) : [wk] "v"(w), [jk] "n"(jK));
+      else asm volatile(HOMMX_ONE("x") : [x] "+v"(a[0][0][rK1]) : [wk] "v"(w), [jk] "n"(jK));
       ubuf[lk + j] = a[0][0][rK1];
-      const double dn = readlane_neg_pivot(a[0][0][rK1], 16 * kK1 + jK1, bad);
+      int dhi;
+      const double dn = readlane_pivot(a[0][0][rK1], 16 * kK1 + jK1, dhi);
       ubuf[NB * kK1 + K1] = dn - 1.0;
       nu0 = ubuf[NB * kK1 + j];
       asm volatile("" ::: "memory");
       double e;
-      asm volatile(HOMMX_RCP0 HOMMX_ONE("x0") HOMMX_RCPE HOMMX_ONE("x1") HOMMX_RCPT HOMMX_ONE("x2") HOMMX_RCPR
-                   : [x0] "+v"(a[0][0][PI(0)]), [x1] "+v"(a[0][0][PI(1)]), [x2] "+v"(a[0][0][PI(2)]), [r] "=&v"(pn), [e] "=&v"(e)
-                   : [wk] "v"(w), [d] "s"(dn), [jk] "n"(jK));
+      unsigned t;
+      if constexpr (rK == rK1) {
+        a[0][0][rK] = (lk == NB * kK) ? w : a[0][0][rK];  // row rule, see above: [z] ties it in front of the bulk block
+        asm volatile(HOMMX_RCP0 HOMMX_PIVADD HOMMX_ONE("x0") HOMMX_PIVMIN HOMMX_RCPE HOMMX_ONE("x1") HOMMX_RCPT HOMMX_ONE("x2") HOMMX_RCPR
+                     : [x0] "+v"(a[0][0][PI(0)]), [x1] "+v"(a[0][0][PI(1)]), [x2] "+v"(a[0][0][PI(2)]), [r] "=&v"(pn), [e] "=&v"(e),
+                       [t] "=&s"(t), [m] "+s"(bad), [z] "+v"(a[0][0][rK])
+                     : [wk] "v"(w), [d] "s"(dn), [jk] "n"(jK), [h] "s"(dhi)
+                     : "scc");
+      } else {
+        asm volatile(HOMMX_RCP0 HOMMX_PIVADD HOMMX_ONE("x0") HOMMX_PIVMIN HOMMX_RCPE HOMMX_ONE("x1") HOMMX_RCPT HOMMX_ONE("x2") HOMMX_RCPR
+                     : [x0] "+v"(a[0][0][PI(0)]), [x1] "+v"(a[0][0][PI(1)]), [x2] "+v"(a[0][0][PI(2)]), [r] "=&v"(pn), [e] "=&v"(e),
+                       [t] "=&s"(t), [m] "+s"(bad)
+                     : [wk] "v"(w), [d] "s"(dn), [jk] "n"(jK), [h] "s"(dhi)
+                     : "scc");
+      }
     } else {
       asm volatile("s_nop 1\n\t" HOMMX_ONE("x0") HOMMX_ONE("x1") HOMMX_ONE("x2") HOMMX_ONE("x3")
                    : [x0] "+v"(a[0][0][0]), [x1] "+v"(a[0][0][1]), [x2] "+v"(a[0][0][2]), [x3] "+v"(a[0][0][3])
                    : [wk] "v"(w), [jk] "n"(jK));
     }
 #undef PI
-#ifdef HOMMX_ROW_RULE_EXEC
-    row_rule1<RowMask<kK>::lo, RowMask<kK>::hi>(a[0][0][rK], w);
-#else
-    a[0][0][rK] = (lk == NB * kK) ? w : a[0][0][rK];  // two v_cndmask_b32 on a loop-invariant lane-row mask: cheaper than 3 SALU + 1 move
-#endif
+    if constexpr (!more || rK != rK1) a[0][0][rK] = (lk == NB * kK) ? w : a[0][0][rK];
     if constexpr (more) {
       if (K + 1 < npiv) step<K + 1>(a, ubuf, lk, j, bad, nu0, pn, npiv);
     }
@@ -310,6 +339,7 @@ __device__ __forceinline__ void block_inverse32(double (&a)[2][2][4], double* ub
   double t00[1][1][4], sc[1][1][4], nu[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) { t00[0][0][r] = a[0][0][r]; nu[r] = -a[0][1][r]; }
+  asm volatile("" : "+v"(nu[0]), "+v"(nu[1]), "+v"(nu[2]), "+v"(nu[3]));  // -U formed here, not between two pivots of the sweep
   Sweep<16>::run(t00, ubuf, j, k, bad);
   v4d nxt = v4d{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
