@@ -871,10 +871,12 @@ int chunk_correctors(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_c
   return route_solve(p, nc, d_coef, d_M, *d_A_eff, d_info, st, *corr);
 }
 
-// the element geometry of the plan in the arguments of a kernel that walks the elements (ReconArgs, SensArgs): structured plans
-// compute it, mesh plans read the plan's geometry block
-template <typename Args>
-void set_geometry(const hommx_plan* p, Args& a) {
+// what a kernel that walks the elements reads of the plan (hommx::ElemWalk, the base of its arguments): dim, kind and the element
+// geometry, which structured plans compute and mesh plans read from the plan's geometry block
+void set_geometry(const hommx_plan* p, hommx::ElemWalk& a) {
+  a.dim = p->desc.dim;
+  a.kind = p->desc.kind;
+  a.mesh = p->desc.n_micro == 0;
   a.ndof = plan_ndof(p);
   a.n_el = p->n_el;
   if (p->desc.n_micro) {
@@ -1036,7 +1038,7 @@ int recon_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<ReconCall>& 
   a.n_regions = v.a.n_regions;
   a.region = !v.a.n_regions ? nullptr : v.a.region ? v.a.region : v.src->mask;  // n_regions == 2 of a two-phase source: the mask may be the labels
   a.region_stats = v.a.region_stats;
-  HIP_TRY(hommx::launch_reconstruct(a, p->desc.dim, p->desc.kind, p->desc.n_micro == 0, nc, st));
+  HIP_TRY(hommx::launch_reconstruct(a, nc, st));
   return HOMMX_OK;
 }
 
@@ -1097,7 +1099,7 @@ int sens_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_sens_ar
   hommx::SensArgs k = sens_dirs_args(p, corr, v.M, a.n_dirs, a.per_cell, a.dirs, a.dA);
   k.weights = a.weights;
   k.grad = a.grad;
-  HIP_TRY(hommx::launch_sensitivity(k, p->desc.dim, p->desc.kind, p->desc.n_micro == 0, nc, st));
+  HIP_TRY(hommx::launch_sensitivity(k, nc, st));
   return HOMMX_OK;
 }
 
@@ -1134,7 +1136,7 @@ int strat_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_strat_
   k.dA_dM = v.a.dA_dM;
   k.weights = v.a.weights;
   k.grad_M = v.a.grad_M;
-  HIP_TRY(hommx::launch_sens_strat(k, p->desc.dim, p->desc.kind, p->desc.n_micro == 0, nc, st));
+  HIP_TRY(hommx::launch_sens_strat(k, nc, st));
   return HOMMX_OK;
 }
 
@@ -1183,7 +1185,7 @@ int load_correctors(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_co
 // the correctors of the loads behind them (load_correctors) and k_load_stats
 int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_load_args>& v, hipStream_t st) {
   const hommx_load_args& a = v.a;
-  const bool response = load_response(a), mesh = p->desc.n_micro == 0;
+  const bool response = load_response(a);
   const int t = p->ks.t;
   double *d_A_eff = a.A_eff, *corr = nullptr;
   if (int rc = chunk_correctors(p, nc, chunk, v.coef, v.M, &d_A_eff, a.info, response ? t : 0, st, &corr)) return rc;
@@ -1196,7 +1198,7 @@ int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_load_a
   k.per_cell = a.per_cell != 0;
   k.P = a.P;
   k.P_eff = a.P_eff;
-  HIP_TRY(hommx::launch_polar(k, p->desc.dim, p->desc.kind, mesh, nc, st));
+  HIP_TRY(hommx::launch_polar(k, nc, st));
   if (!response) return HOMMX_OK;
   double* corr_l = corr + chunk * t * k.ndof;
   if (int rc = load_correctors(p, nc, chunk, v.coef, v.M, hommx::LoadOverride{a.P, a.n_loads, a.per_cell != 0}, st, corr_l)) return rc;
@@ -1205,7 +1207,7 @@ int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_load_a
   k.stats = a.stats;
   k.strain = a.strain;
   k.flux = a.flux;
-  if (a.energy || a.stats || a.strain) HIP_TRY(hommx::launch_load_stats(k, p->desc.dim, p->desc.kind, mesh, nc, st));
+  if (a.energy || a.stats || a.strain) HIP_TRY(hommx::launch_load_stats(k, nc, st));
   if (a.correctors)  // rows l < n_loads of every cell
     HIP_TRY(hipMemcpy2DAsync(a.correctors, sizeof(double) * a.n_loads * k.ndof, corr_l, sizeof(double) * t * k.ndof,
                              sizeof(double) * a.n_loads * k.ndof, nc, hipMemcpyDeviceToDevice, st));
@@ -1254,12 +1256,11 @@ size_t sens2_extra(const hommx_plan* p) { return sizeof(double) * p->ks.t * (pla
 // derivatives; then per direction b its loads (k_sens2_loads), their correctors behind the canonical ones (load_correctors), and k_sens2 for the blocks (a, b) and (b, a), a <= b
 int sens2_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_sens2_args>& v, hipStream_t st) {
   const hommx_sens2_args& a = v.a;
-  const bool mesh = p->desc.n_micro == 0;
   const int t = p->ks.t;
   double *d_A_eff = a.A_eff, *corr = nullptr;
   if (int rc = chunk_correctors(p, nc, chunk, v.coef, v.M, &d_A_eff, a.info, t, st, &corr)) return rc;
   if (a.dA)
-    HIP_TRY(hommx::launch_sensitivity(sens_dirs_args(p, corr, v.M, a.n_dirs, a.per_cell, a.dirs, a.dA), p->desc.dim, p->desc.kind, mesh, nc, st));
+    HIP_TRY(hommx::launch_sensitivity(sens_dirs_args(p, corr, v.M, a.n_dirs, a.per_cell, a.dirs, a.dA), nc, st));
   if (int rc = grow(p->buf[B_SENS2], sizeof(double) * chunk * t * p->n_el * t)) return rc;
   hommx::Sens2Args k;
   set_geometry(p, k);
@@ -1274,9 +1275,9 @@ int sens2_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_sens2_
   k.d2A = a.d2A;
   for (int b = 0; b < a.n_dirs; ++b) {
     k.b = b;
-    HIP_TRY(hommx::launch_sens2_loads(k, p->desc.dim, p->desc.kind, mesh, nc, st));
+    HIP_TRY(hommx::launch_sens2_loads(k, nc, st));
     if (int rc = load_correctors(p, nc, chunk, v.coef, v.M, hommx::LoadOverride{k.P, t, true}, st, corr_b)) return rc;  // t per-cell loads
-    HIP_TRY(hommx::launch_sens2(k, p->desc.dim, p->desc.kind, mesh, nc, st));
+    HIP_TRY(hommx::launch_sens2(k, nc, st));
   }
   return HOMMX_OK;
 }

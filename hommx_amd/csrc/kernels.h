@@ -108,18 +108,26 @@ hipError_t launch_expand_separable(CoefSource src, const double* d_params, doubl
 hipError_t launch_expand_two_phase(const unsigned char* d_mask, const double* d_values, double* d_coef, long long n_el,
                                    int n_comp, long long ncells, hipStream_t stream);
 
-// reconstruct.hip: per-element gradient / strain and flux / stress of `nc` cells from their correctors, and the per-cell statistics
-// [mean_strain (t) | mean_flux (t) | energy | max_flux | argmax_element] (include/hommx_hip.h, hommx_reconstruct_batch)
-struct ReconArgs {
-  int n = 0;                         // structured plans: micro cells per side (geometry computed in the kernel)
+// What every kernel that walks the elements of a cell with one workgroup per macro cell reads (elem_walk.h): the element geometry, the
+// correctors, M and the (dim, kind, mesh) its launcher dispatches on.  The base of the argument structs below; api.hip::set_geometry
+// fills everything but corr and M from the plan
+struct ElemWalk {
+  int dim = 0, kind = 0;             // of the plan
+  bool mesh = false;                 // a mesh plan: the geometry is read; else computed in the kernel
+  int n = 0;                         // structured plans: micro cells per side
   double vol_struct = 0.0;           // structured plans: element volume
   long long ndof = 0, n_el = 0;      // periodic unknowns (nodes x bs) and elements per cell
   const int32_t* el_nodes = nullptr; // mesh plans: [n_el][dim+1] periodic nodes, [n_el][dim+1][dim] P1 gradients, [n_el] volumes
   const double* grads = nullptr;
   const double* vol = nullptr;
   const double* corr = nullptr;      // [nc][t][ndof]
-  const double* coef = nullptr;      // [nc][n_el][n_comp]
   const double* M = nullptr;         // [nc][d][d] or null
+};
+
+// reconstruct.hip: per-element gradient / strain and flux / stress of `nc` cells from their correctors, and the per-cell statistics
+// [mean_strain (t) | mean_flux (t) | energy | max_flux | argmax_element] (include/hommx_hip.h, hommx_reconstruct_batch)
+struct ReconArgs : ElemWalk {
+  const double* coef = nullptr;      // [nc][n_el][n_comp]
   const double* xi = nullptr;        // [nc][t]
   double* stats = nullptr;           // [nc][2t+3]
   double* strain = nullptr;          // [nc][n_el][t] or null (then flux is null as well: no fields)
@@ -132,19 +140,11 @@ struct ReconArgs {
 };
 // bytes of chi^xi above which a cell takes a scratch slot instead of LDS
 size_t recon_lds_limit();
-hipError_t launch_reconstruct(const ReconArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
+hipError_t launch_reconstruct(const ReconArgs& a, long long nc, hipStream_t stream);
 
 // sensitivity.hip: derivatives of A_H along coefficient directions and its per-element gradient, from the correctors of `nc` cells
-// (include/hommx_hip.h, hommx_sensitivity_source).  The geometry fields are those of ReconArgs
-struct SensArgs {
-  int n = 0;
-  double vol_struct = 0.0;
-  long long ndof = 0, n_el = 0;
-  const int32_t* el_nodes = nullptr;
-  const double* grads = nullptr;
-  const double* vol = nullptr;
-  const double* corr = nullptr;      // [nc][t][ndof]
-  const double* M = nullptr;         // [nc][d][d] or null
+// (include/hommx_hip.h, hommx_sensitivity_source)
+struct SensArgs : ElemWalk {
   int n_dirs = 0;                    // 0 .. HOMMX_SENS_MAX_DIRS
   bool per_cell = false;             // dirs[nc][n_dirs][n_el][n_comp] instead of dirs[n_dirs][n_el][n_comp]
   const double* dirs = nullptr;
@@ -152,22 +152,13 @@ struct SensArgs {
   const double* weights = nullptr;   // [nc][t][t], with grad[nc][n_el][n_comp]; or both null
   double* grad = nullptr;
 };
-hipError_t launch_sensitivity(const SensArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
+hipError_t launch_sensitivity(const SensArgs& a, long long nc, hipStream_t stream);
 
 // sens2.hip: second derivatives of A_H along coefficient directions (include/hommx_hip.h, hommx_second_sensitivity_source; DESIGN.md
-// section 4.13), one direction b per launch.  The geometry fields are those of ReconArgs.  launch_sens2_loads: the polarisation loads
-// P^{b,m} = material(dir_b) s^m from the canonical correctors; launch_sens2: d2A[a][b] and d2A[b][a], a <= b, from the canonical
-// correctors and the correctors of those loads
-struct Sens2Args {
-  int n = 0;
-  double vol_struct = 0.0;
-  long long ndof = 0, n_el = 0;
-  const int32_t* el_nodes = nullptr;
-  const double* grads = nullptr;
-  const double* vol = nullptr;
-  const double* corr = nullptr;      // [nc][t][ndof]: the canonical correctors
+// section 4.13), one direction b per launch.  launch_sens2_loads: the polarisation loads P^{b,m} = material(dir_b) s^m from the canonical
+// correctors (corr); launch_sens2: d2A[a][b] and d2A[b][a], a <= b, from the canonical correctors and the correctors of those loads
+struct Sens2Args : ElemWalk {
   const double* corr_b = nullptr;    // [nc][t][ndof]: the correctors of the loads of direction b (k_sens2)
-  const double* M = nullptr;         // [nc][d][d] or null
   int n_dirs = 0;                    // 1 .. HOMMX_SENS_MAX_DIRS
   int b = 0;                         // the direction of this launch
   bool per_cell = false;             // dirs[nc][n_dirs][n_el][n_comp] instead of dirs[n_dirs][n_el][n_comp]
@@ -175,40 +166,24 @@ struct Sens2Args {
   double* P = nullptr;               // [nc][t][n_el][t]: written by k_sens2_loads, a per-cell load block of loads.hip
   double* d2A = nullptr;             // [nc][n_dirs][n_dirs][t][t] (k_sens2)
 };
-hipError_t launch_sens2_loads(const Sens2Args& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
-hipError_t launch_sens2(const Sens2Args& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
+hipError_t launch_sens2_loads(const Sens2Args& a, long long nc, hipStream_t stream);
+hipError_t launch_sens2(const Sens2Args& a, long long nc, hipStream_t stream);
 
 // sens_strat.hip: derivatives of A_H with respect to the stratification M and their product with caller weights, from the correctors
-// of `nc` cells (include/hommx_hip.h, hommx_stratification_sensitivity_source).  The geometry fields are those of ReconArgs
-struct StratSensArgs {
-  int n = 0;
-  double vol_struct = 0.0;
-  long long ndof = 0, n_el = 0;
-  const int32_t* el_nodes = nullptr;
-  const double* grads = nullptr;
-  const double* vol = nullptr;
-  const double* corr = nullptr;      // [nc][t][ndof]
+// of `nc` cells (include/hommx_hip.h, hommx_stratification_sensitivity_source)
+struct StratSensArgs : ElemWalk {
   const double* coef = nullptr;      // [nc][n_el][n_comp]
-  const double* M = nullptr;         // [nc][d][d] or null
   double* dA_dM = nullptr;           // [nc][d][d][t][t] or null
   const double* weights = nullptr;   // [nc][t][t], with grad_M[nc][d][d]; or both null
   double* grad_M = nullptr;
 };
-hipError_t launch_sens_strat(const StratSensArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
+hipError_t launch_sens_strat(const StratSensArgs& a, long long nc, hipStream_t stream);
 
-// loads.hip: user-supplied polarisation loads P[load][el][t] (include/hommx_hip.h, hommx_loads_source).  The
-// geometry fields are those of ReconArgs.  launch_polar: P_eff from the canonical correctors (Levin); launch_load_stats: the response
-// outputs from the correctors of the loads themselves, every one of them optional
-struct LoadArgs {
-  int n = 0;
-  double vol_struct = 0.0;
-  long long ndof = 0, n_el = 0;
-  const int32_t* el_nodes = nullptr;
-  const double* grads = nullptr;
-  const double* vol = nullptr;
-  const double* corr = nullptr;      // [nc][t][ndof]: the canonical correctors (k_polar), the correctors of the loads, rows >= n_loads unused (k_load_stats)
+// loads.hip: user-supplied polarisation loads P[load][el][t] (include/hommx_hip.h, hommx_loads_source).
+// launch_polar: P_eff from the canonical correctors in corr (Levin); launch_load_stats: the response outputs from the correctors of the
+// loads themselves in corr (rows >= n_loads unused), every one of them optional
+struct LoadArgs : ElemWalk {
   const double* coef = nullptr;      // [nc][n_el][n_comp] (k_load_stats)
-  const double* M = nullptr;         // [nc][d][d] or null
   int n_loads = 0;                   // 1 .. t
   bool per_cell = false;             // P[nc][n_loads][n_el][t] instead of P[n_loads][n_el][t]
   const double* P = nullptr;
@@ -218,8 +193,8 @@ struct LoadArgs {
   double* strain = nullptr;          // [nc][n_loads][n_el][t] or null (then flux is null as well)
   double* flux = nullptr;
 };
-hipError_t launch_polar(const LoadArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
-hipError_t launch_load_stats(const LoadArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t stream);
+hipError_t launch_polar(const LoadArgs& a, long long nc, hipStream_t stream);
+hipError_t launch_load_stats(const LoadArgs& a, long long nc, hipStream_t stream);
 
 // the loads a corrector pass of the blocked family solves for instead of the canonical ones: rows l < n_loads of Brhs from P (device), the
 // rest zero.  P starts at the first cell of the call

@@ -10,9 +10,9 @@
 //   energy      energy[l][l'] = sum_K |K| eps(chi_l)_K . material(coef_K) eps(chi_l')_K
 //
 // k_polar and k_load_stats: one workgroup per macro cell, elements on lanes, the correctors gathered from global memory as k_sens
-// gathers them (elem_walk.h); sums as element-strided partial sums per thread, a butterfly in each wave, the wave totals in order, so a
-// cell's outputs do not depend on its batch position, the chunking or which outputs are asked for.  k_assemble_loads: one thread per
-// node gathers the load entries of its incident elements and writes each entry of Brhs once.  No atomics, no inline assembly.
+// gathers them and the fixed-order reductions of elem_walk.h (block_sums, block_argmax), so a cell's outputs do not depend on its batch
+// position, the chunking or which outputs are asked for.  k_assemble_loads: one thread per node gathers the load entries of its
+// incident elements and writes each entry of Brhs once.  No atomics, no inline assembly.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,43 +25,11 @@ namespace hommx {
 
 namespace {
 
-constexpr int kThreads = kWalkThreads;
-constexpr int kWaves = kWalkWaves;
-
-// M of the cell, or the identity (exact: the same gradients as without M), as k_recon holds it
-template <int DIM>
-__device__ __forceinline__ void cell_M(const double* M, long long cell, double (&Mp)[DIM * DIM]) {
-#pragma unroll
-  for (int k = 0; k < DIM * DIM; ++k) Mp[k] = M ? M[cell * DIM * DIM + k] : (k % (DIM + 1) == 0 ? 1.0 : 0.0);
-}
-
-// v[q] over the workgroup in the fixed order of k_recon; thread 0 returns with the totals in v
-template <int N>
-__device__ __forceinline__ void block_sum(double (&v)[N], double (*red)[N], int tid) {
-#pragma unroll
-  for (int q = 0; q < N; ++q)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v[q] += __shfl_xor(v[q], o, 64);
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) red[tid >> 6][q] = v[q];
-  }
-  __syncthreads();
-  if (tid == 0) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-      double t = red[0][q];
-      for (int w = 1; w < kWaves; ++w) t += red[w][q];
-      v[q] = t;
-    }
-  }
-}
-
 // P_eff[cell][l][m] = sum_K |K| s^m_K . P^l_K: the t canonical strains of an element once, contracted with every load; P is read once
 template <int DIM, int KIND, bool MESH>
-__global__ __launch_bounds__(kThreads) void k_polar(LoadArgs A) {
+__global__ __launch_bounds__(kWalkThreads) void k_polar(LoadArgs A) {
   constexpr int T = kind_sizes(DIM, KIND).t;
-  __shared__ double red[kWaves][T * T];
+  __shared__ double red[kWalkWaves][T * T];
   const int tid = threadIdx.x;
   const long long cell = blockIdx.x;
   const double* corr = A.corr + cell * T * A.ndof;
@@ -95,22 +63,9 @@ __global__ __launch_bounds__(kThreads) void k_polar(LoadArgs A) {
       }
     }
   });
-  // fixed-order reduction: wave butterfly, then thread q adds the wave totals of sum q in order (one thread holding all t^2 totals
-  // beside the sums spills at t = 6)
-#pragma unroll
-  for (int q = 0; q < T * T; ++q)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < T * T; ++q) red[tid >> 6][q] = acc[q];
-  }
-  __syncthreads();
-  if (tid < nl * T) {
-    double v = red[0][tid];
-    for (int w = 1; w < kWaves; ++w) v += red[w][tid];
-    A.P_eff[cell * nl * T + tid] = v;
-  }
+  // thread q takes total q: one thread holding all t^2 totals beside its sums spills at t = 6
+  const double total = block_sums<T * T>(acc, red, tid, nl * T);
+  if (tid < nl * T) A.P_eff[cell * nl * T + tid] = total;
 }
 
 // The response of a cell to its loads, from their correctors chi_l (rows l < n_loads of corr).  One pass over the elements per load,
@@ -119,12 +74,11 @@ __global__ __launch_bounds__(kThreads) void k_polar(LoadArgs A) {
 // |q_K| (Frobenius norm for elasticity) with the smallest element reaching it, row l of the energy matrix up to the diagonal (mirrored,
 // so the matrix is symmetric bitwise) and, on request, the fields of load l
 template <int DIM, int KIND, bool MESH, bool FIELDS>
-__global__ __launch_bounds__(kThreads) void k_load_stats(LoadArgs A) {
+__global__ __launch_bounds__(kWalkThreads) void k_load_stats(LoadArgs A) {
   constexpr KindSizes ks = kind_sizes(DIM, KIND);
   constexpr int T = ks.t, NCOMP = ks.n_comp;
   constexpr int NSUM = 2 * T;  // mean flux (t) | energy[l][0 .. l] (at most t)
-  __shared__ double red[kWaves][NSUM];
-  __shared__ double red_mx[kWaves], red_arg[kWaves];
+  __shared__ double red[kWalkWaves][NSUM], red_max[kWalkWaves][2];
   const int tid = threadIdx.x;
   const long long cell = blockIdx.x;
   const double* corr = A.corr + cell * T * A.ndof;
@@ -193,45 +147,23 @@ __global__ __launch_bounds__(kThreads) void k_load_stats(LoadArgs A) {
       }
     });
 
-    // the largest norm and the smallest element reaching it: butterfly, then the waves in order (the rule of k_recon)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const double omx = __shfl_xor(mx, o, 64);
-      const long long oarg = __shfl_xor(arg, o, 64);
-      if (omx > mx || (omx == mx && oarg < arg && oarg >= 0)) {
-        mx = omx;
-        arg = oarg;
+    double barg = (double)arg;
+    block_argmax(mx, barg, red_max, tid);
+    double* st = A.stats ? A.stats + (cell * nl + l) * (T + 2) : nullptr;
+    double* en = A.energy ? A.energy + cell * nl * nl : nullptr;
+    block_sums<NSUM>(acc, red, tid, [&](int q, double total) {
+      const int m = q - T;
+      if (q < T) {
+        if (st) st[q] = total;
+      } else if (en && m <= l) {
+        en[l * nl + m] = en[m * nl + l] = total;
       }
+    });
+    if (tid == 0 && st) {
+      st[T] = mx;
+      st[T + 1] = barg;
     }
-    if ((tid & 63) == 0) {
-      red_mx[tid >> 6] = mx;
-      red_arg[tid >> 6] = (double)arg;
-    }
-    block_sum<NSUM>(acc, red, tid);  // its barrier covers red_mx / red_arg
-    if (tid == 0) {
-      double bmx = red_mx[0], barg = red_arg[0];
-      for (int w = 1; w < kWaves; ++w) {
-        const double omx = red_mx[w], oarg = red_arg[w];
-        if (omx > bmx || (omx == bmx && oarg < barg && oarg >= 0)) {
-          bmx = omx;
-          barg = oarg;
-        }
-      }
-      if (A.stats) {
-        double* st = A.stats + (cell * nl + l) * (T + 2);
-#pragma unroll
-        for (int k = 0; k < T; ++k) st[k] = acc[k];
-        st[T] = bmx;
-        st[T + 1] = barg;
-      }
-      if (A.energy) {
-        double* en = A.energy + cell * nl * nl;
-#pragma unroll
-        for (int m = 0; m < T; ++m)
-          if (m <= l) en[l * nl + m] = en[m * nl + l] = acc[T + m];
-      }
-    }
-    __syncthreads();  // the next pass writes the reduction arrays again
+    __syncthreads();  // the next pass writes the reduction rows again
   }
 }
 
@@ -342,33 +274,15 @@ __global__ __launch_bounds__(256) void k_assemble_loads_mesh(MeshAsm A, LoadOver
   }
 }
 
-template <int DIM, int KIND, bool MESH>
-hipError_t launch_polar_one(const LoadArgs& a, long long nc, hipStream_t st) {
-  hipLaunchKernelGGL((k_polar<DIM, KIND, MESH>), dim3((unsigned)nc), dim3(kThreads), 0, st, a);
-  return hipGetLastError();
-}
-
-template <int DIM, int KIND, bool MESH>
-hipError_t launch_stats_one(const LoadArgs& a, long long nc, hipStream_t st) {
-  if (a.strain) hipLaunchKernelGGL((k_load_stats<DIM, KIND, MESH, true>), dim3((unsigned)nc), dim3(kThreads), 0, st, a);
-  else hipLaunchKernelGGL((k_load_stats<DIM, KIND, MESH, false>), dim3((unsigned)nc), dim3(kThreads), 0, st, a);
-  return hipGetLastError();
-}
-
 }  // namespace
 
-hipError_t launch_polar(const LoadArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t st) {
-  if (nc <= 0) return hipSuccess;
-  return dispatch_dim_kind(dim, kind, [&](auto D, auto K) {
-    return mesh ? launch_polar_one<D(), K(), true>(a, nc, st) : launch_polar_one<D(), K(), false>(a, nc, st);
-  });
+hipError_t launch_polar(const LoadArgs& a, long long nc, hipStream_t st) {
+  return launch_walk(a, nc, st, walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_polar<D(), K(), MESH()>; }));
 }
 
-hipError_t launch_load_stats(const LoadArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t st) {
-  if (nc <= 0) return hipSuccess;
-  return dispatch_dim_kind(dim, kind, [&](auto D, auto K) {
-    return mesh ? launch_stats_one<D(), K(), true>(a, nc, st) : launch_stats_one<D(), K(), false>(a, nc, st);
-  });
+hipError_t launch_load_stats(const LoadArgs& a, long long nc, hipStream_t st) {
+  if (a.strain) return launch_walk(a, nc, st, walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_load_stats<D(), K(), MESH(), true>; }));
+  return launch_walk(a, nc, st, walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_load_stats<D(), K(), MESH(), false>; }));
 }
 
 hipError_t launch_assemble_loads(const BlockedWorkspace* ws, const LoadOverride& lo, long long cell0, const double* Mm, long long nc,

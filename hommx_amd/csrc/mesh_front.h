@@ -25,7 +25,7 @@ struct MeshGeom {
 int mesh_check(const hommx_mesh_desc* d, MeshGeom* g);
 
 // The element geometry of a mesh plan on the device: one block, owned by the plan (api.hip).  The kernel arguments of both routes
-// (MeshDev, MeshAsm) and of the reconstruction (ReconArgs) point into it.
+// (MeshDev, MeshAsm) and of the derived-output kernels (ElemWalk, kernels.h) point into it.
 struct MeshGeomDev {
   void* block;
   const int32_t* el_nodes;  // [n_el][dim+1] the descriptor's element table

@@ -8,20 +8,17 @@
 // formulas are those of the mesh routes (mesh_elem.h).
 //
 // One workgroup per macro cell.  chi^xi lives in LDS (or, for cells too large for it, in a per-cell slot of the caller's scratch).
-// Statistics: element-strided partial sums per thread, a butterfly in each wave, the wave totals in order -- a fixed order, so a cell's
-// statistics do not depend on its batch position, the chunking or whether fields are written.  No atomics, no inline assembly.
+// Statistics: the fixed-order reduction of elem_walk.h (written out in the kernel, see there), so a cell's statistics do not depend on
+// its batch position, the chunking or whether fields are written.  No atomics, no inline assembly.
 #include <hip/hip_runtime.h>
 
+#include "elem_walk.h"
 #include "kernels.h"
-#include "mesh_elem.h"
-#include "struct_elem.h"
 
 namespace hommx {
 
 namespace {
 
-constexpr int kThreads = 512;
-constexpr int kWaves = kThreads / 64;
 constexpr int kMaxStats = 2 * 6 + 3;
 
 // per-thread running statistics of the elements it visits (ascending element index)
@@ -92,12 +89,12 @@ __device__ __forceinline__ void element(const double (&xi)[KIND >= 2 ? DIM * (DI
 // the statistics are bitwise the same with and without FIELDS).  Passes, not per-region running sums: eight regions x (2t + 2) sums per
 // thread fit neither the registers nor LDS beside chi^xi.
 template <int DIM, int KIND, bool MESH, bool FIELDS, bool REGIONS>
-__global__ __launch_bounds__(kThreads) void k_recon(ReconArgs A) {
+__global__ __launch_bounds__(kWalkThreads) void k_recon(ReconArgs A) {
   constexpr KindSizes ks = kind_sizes(DIM, KIND);
   constexpr int T = ks.t, NCOMP = ks.n_comp;
   constexpr int NSUM = 2 * T + 1 + (REGIONS ? 1 : 0);  // sums of a pass: strain, flux, energy (and the volume of a region)
   extern __shared__ double lds_chi[];
-  __shared__ double red[kWaves][kMaxStats + (REGIONS ? 1 : 0)];
+  __shared__ double red[kWalkWaves][kMaxStats + (REGIONS ? 1 : 0)];
   const int tid = threadIdx.x;
   const long long cell = blockIdx.x;
   const long long ndof = A.ndof;
@@ -105,15 +102,13 @@ __global__ __launch_bounds__(kThreads) void k_recon(ReconArgs A) {
   double xi[T];
 #pragma unroll
   for (int m = 0; m < T; ++m) xi[m] = A.xi[cell * T + m];
-  // M, or the identity (exact: the same gradients as without M); one private array that never escapes, so it stays in registers
   double Mp[DIM * DIM];
-#pragma unroll
-  for (int k = 0; k < DIM * DIM; ++k) Mp[k] = A.M ? A.M[cell * DIM * DIM + k] : (k % (DIM + 1) == 0 ? 1.0 : 0.0);
+  cell_M<DIM>(A.M, cell, Mp);
 
   // chi^xi = sum_m xi_m chi_m: every corrector of the cell read once, lanes along the dof index
   double* X = A.slot ? A.slot + cell * ndof : lds_chi;
   const double* corr = A.corr + cell * T * ndof;
-  for (long long j = tid; j < ndof; j += kThreads) {
+  for (long long j = tid; j < ndof; j += kWalkThreads) {
     double v = 0.0;
 #pragma unroll
     for (int m = 0; m < T; ++m) v += xi[m] * corr[m * ndof + j];
@@ -135,63 +130,21 @@ __global__ __launch_bounds__(kThreads) void k_recon(ReconArgs A) {
     acc.mx = -1.0;
     acc.arg = -1;
     double rvol = 0.0;
+    for_elements<DIM, MESH>(A, tid, [&](long long el, double vol, auto vertex) {
+      if constexpr (REGIONS)
+        if (r >= 0 && A.region[el] != r) return;
+      int node[DIM + 1];
+      double g[DIM + 1][DIM];
+#pragma unroll
+      for (int a = 0; a < DIM + 1; ++a) vertex(a, node[a], g[a]);
+      element<DIM, KIND, WRITE>(xi, X, node, g, vol, Mp, cc + el * NCOMP, el, WRITE ? srow0 + el * T : nullptr,
+                                WRITE ? qrow0 + el * T : nullptr, acc);
+      if constexpr (REGIONS) rvol += vol;
+    });
 
-    if constexpr (MESH) {
-      for (long long el = tid; el < A.n_el; el += kThreads) {
-        if constexpr (REGIONS)
-          if (r >= 0 && A.region[el] != r) continue;
-        int node[DIM + 1];
-        double g[DIM + 1][DIM];
-#pragma unroll
-        for (int a = 0; a < DIM + 1; ++a) {
-          node[a] = A.el_nodes[el * (DIM + 1) + a];
-#pragma unroll
-          for (int k = 0; k < DIM; ++k) g[a][k] = A.grads[(el * (DIM + 1) + a) * DIM + k];
-        }
-        const double vol = A.vol[el];
-        element<DIM, KIND, WRITE>(xi, X, node, g, vol, Mp, cc + el * NCOMP, el, WRITE ? srow0 + el * T : nullptr,
-                                  WRITE ? qrow0 + el * T : nullptr, acc);
-        if constexpr (REGIONS) rvol += vol;
-      }
-    } else {
-      // structured: one grid cell (all its sub-simplices, element order n_sub (i + n j [+ n^2 k]) + s) per thread and step
-      // (six tetrahedra unrolled hold too many registers: the 3D loop stays rolled, its tables read from constant memory)
-      constexpr int NSUB = DIM == 2 ? 2 : 6;
-      constexpr int UNROLL = DIM == 2 ? 2 : 1;
-      const int n = A.n;
-      const double hn = (double)n;
-      const long long ncube = A.n_el / NSUB;
-      for (long long cube = tid; cube < ncube; cube += kThreads) {
-        const int i = (int)(cube % n), j = (int)((cube / n) % n), k = DIM == 3 ? (int)(cube / ((long long)n * n)) : 0;
-#pragma unroll UNROLL
-        for (int s = 0; s < NSUB; ++s) {
-          const long long el = cube * NSUB + s;
-          if constexpr (REGIONS)
-            if (r >= 0 && A.region[el] != r) continue;
-          int node[DIM + 1];
-          double g[DIM + 1][DIM];
-#pragma unroll
-          for (int a = 0; a < DIM + 1; ++a) {
-            if constexpr (DIM == 2) {
-              const int ii = i + kOff2[s][a][0], jj = j + kOff2[s][a][1];
-              node[a] = (ii == n ? 0 : ii) + n * (jj == n ? 0 : jj);
-#pragma unroll
-              for (int c = 0; c < 2; ++c) g[a][c] = kGrad2[s][a][c] * hn;
-            } else {
-              const int ii = i + kOff3[s][a][0], jj = j + kOff3[s][a][1], kk = k + kOff3[s][a][2];
-              node[a] = (ii == n ? 0 : ii) + n * ((jj == n ? 0 : jj) + n * (kk == n ? 0 : kk));
-#pragma unroll
-              for (int c = 0; c < 3; ++c) g[a][c] = kGrad3[s][a][c] * hn;
-            }
-          }
-          element<DIM, KIND, WRITE>(xi, X, node, g, A.vol_struct, Mp, cc + el * NCOMP, el, WRITE ? srow0 + el * T : nullptr,
-                                    WRITE ? qrow0 + el * T : nullptr, acc);
-          if constexpr (REGIONS) rvol += A.vol_struct;
-        }
-      }
-    }
-
-    // fixed-order reduction: wave butterfly, then the wave totals in order
+    // The fixed-order reduction of elem_walk.h, written out here: sums and maximum under one barrier, thread 0 adding wave after wave with
+    // every total in registers.  On block_sums / block_argmax the kernel computes the same bits in fewer registers, and 3D elasticity
+    // runs 2.5 - 6 % slower for it (the compiler then schedules for an occupancy that the LDS of chi^xi does not allow): DESIGN.md section 3
     double v[NSUM];
 #pragma unroll
     for (int m = 0; m < T; ++m) {
@@ -228,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void k_recon(ReconArgs A) {
 #pragma unroll
       for (int q = 0; q < NSUM; ++q) t[q] = red[0][q];
       double bmx = red[0][NSUM], barg = red[0][NSUM + 1];
-      for (int ww = 1; ww < kWaves; ++ww) {
+      for (int ww = 1; ww < kWalkWaves; ++ww) {
 #pragma unroll
         for (int q = 0; q < NSUM; ++q) t[q] += red[ww][q];
         const double omx = red[ww][NSUM], oarg = red[ww][NSUM + 1];
@@ -249,38 +202,31 @@ __global__ __launch_bounds__(kThreads) void k_recon(ReconArgs A) {
       st[2 * T + 1] = bmx;
       st[2 * T + 2] = barg;
     }
-    if constexpr (REGIONS) __syncthreads();  // the next pass writes `red` again
+    if constexpr (REGIONS) __syncthreads();  // the next pass writes the reduction rows again
   };
   pass(std::true_type{}, -1);
   if constexpr (REGIONS)
     for (int r = 0; r < A.n_regions; ++r) pass(std::false_type{}, r);
 }
 
-template <int DIM, int KIND, bool MESH, bool FIELDS, bool REGIONS>
-hipError_t launch_one(const ReconArgs& a, long long nc, hipStream_t st) {
-  const size_t lds = a.slot ? 0 : sizeof(double) * (size_t)a.ndof;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_recon<DIM, KIND, MESH, FIELDS, REGIONS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((k_recon<DIM, KIND, MESH, FIELDS, REGIONS>), dim3((unsigned)nc), dim3(kThreads), lds, st, a);
-  return hipGetLastError();
-}
-
 }  // namespace
 
 size_t recon_lds_limit() { return 150 * 1024; }
 
-hipError_t launch_reconstruct(const ReconArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t st) {
+hipError_t launch_reconstruct(const ReconArgs& a, long long nc, hipStream_t st) {
   if (nc <= 0) return hipSuccess;
+  auto with = [&](auto F, auto R) {
+    return walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_recon<D(), K(), MESH(), decltype(F)::value, decltype(R)::value>; });
+  };
   const bool f = a.strain != nullptr;
-  return dispatch_dim_kind(dim, kind, [&](auto D, auto K) {
-    auto with = [&](auto MESH, auto REG) {
-      return f ? launch_one<D(), K(), MESH(), true, REG()>(a, nc, st) : launch_one<D(), K(), MESH(), false, REG()>(a, nc, st);
-    };
-    if (a.n_regions > 0) return mesh ? with(std::true_type{}, std::true_type{}) : with(std::false_type{}, std::true_type{});
-    return mesh ? with(std::true_type{}, std::false_type{}) : with(std::false_type{}, std::false_type{});
-  });
+  const auto kernel = a.n_regions > 0 ? (f ? with(std::true_type{}, std::true_type{}) : with(std::false_type{}, std::true_type{}))
+                                      : (f ? with(std::true_type{}, std::false_type{}) : with(std::false_type{}, std::false_type{}));
+  const size_t lds = a.slot ? 0 : sizeof(double) * (size_t)a.ndof;
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  return launch_walk(a, nc, st, kernel, lds);
 }
 
 }  // namespace hommx

@@ -12,9 +12,8 @@
 // Both kernels: one workgroup per macro cell, elements on lanes, correctors gathered from global memory (elem_walk.h).  k_sens2_loads has
 // no reduction; every element writes its t loads.  k_sens2 takes one pass over the elements per a <= b: the t x t canonical strains stay
 // in registers, the strain of one load corrector at a time is gathered in a rolled loop and its row of the t x t sums picked by selects
-// (k_polar's device), so that 3D elasticity (t = 6) fits the registers.  Sums: element-strided partial sums per
-// thread, a butterfly in each wave, the wave totals in order -- a cell's outputs do not depend on its batch position or the chunking.
-// No atomics, no inline assembly.
+// (k_polar's device), so that 3D elasticity (t = 6) fits the registers.  Sums: the fixed-order sums of elem_walk.h (block_sums) -- a
+// cell's outputs do not depend on its batch position or the chunking.  No atomics, no inline assembly.
 #include <hip/hip_runtime.h>
 
 #include "elem_walk.h"
@@ -24,20 +23,10 @@ namespace hommx {
 
 namespace {
 
-constexpr int kThreads = kWalkThreads;
-constexpr int kWaves = kWalkWaves;
-
-// M of the cell, or the identity (exact: the same gradients as without M), as k_recon holds it
-template <int DIM>
-__device__ __forceinline__ void cell_M(const double* M, long long cell, double (&Mp)[DIM * DIM]) {
-#pragma unroll
-  for (int k = 0; k < DIM * DIM; ++k) Mp[k] = M ? M[cell * DIM * DIM + k] : (k % (DIM + 1) == 0 ? 1.0 : 0.0);
-}
-
 // P[cell][m][K] = material(dir_b[K]) s^m_K for the t canonical loads: a per-cell load block of hommx_loads_source.  Lane K writes the t
 // components of its element next to those of lane K + 1
 template <int DIM, int KIND, bool MESH>
-__global__ __launch_bounds__(kThreads) void k_sens2_loads(Sens2Args A) {
+__global__ __launch_bounds__(kWalkThreads) void k_sens2_loads(Sens2Args A) {
   constexpr KindSizes ks = kind_sizes(DIM, KIND);
   constexpr int T = ks.t, NCOMP = ks.n_comp;
   const int tid = threadIdx.x;
@@ -67,10 +56,10 @@ __global__ __launch_bounds__(kThreads) void k_sens2_loads(Sens2Args A) {
 
 // d2A[cell][a][b] and its mirror d2A[cell][b][a] for every a <= b = A.b, from the canonical correctors and the load correctors of dir_b
 template <int DIM, int KIND, bool MESH>
-__global__ __launch_bounds__(kThreads) void k_sens2(Sens2Args A) {
+__global__ __launch_bounds__(kWalkThreads) void k_sens2(Sens2Args A) {
   constexpr KindSizes ks = kind_sizes(DIM, KIND);
   constexpr int T = ks.t, NCOMP = ks.n_comp, NSUM = T * T;
-  __shared__ double red[kWaves][NSUM];
+  __shared__ double red[kWalkWaves][NSUM];
   __shared__ double g[T * T];  // g_ab[m][n], the totals
   const int tid = threadIdx.x;
   const long long cell = blockIdx.x;
@@ -113,21 +102,9 @@ __global__ __launch_bounds__(kThreads) void k_sens2(Sens2Args A) {
         }
       }
     });
-    // fixed-order reduction: wave butterfly, then thread q adds the wave totals of sum q in order
-#pragma unroll
-    for (int q = 0; q < NSUM; ++q)
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
-    if ((tid & 63) == 0) {
-#pragma unroll
-      for (int q = 0; q < NSUM; ++q) red[tid >> 6][q] = acc[q];
-    }
-    __syncthreads();
-    if (tid < NSUM) {
-      double v = red[0][tid];
-      for (int w = 1; w < kWaves; ++w) v += red[w][tid];
-      g[tid] = v;
-    }
+    // thread q takes total q: one thread holding all t^2 totals beside its sums spills at t = 6
+    const double total = block_sums<NSUM>(acc, red, tid, NSUM);
+    if (tid < NSUM) g[tid] = total;
     __syncthreads();
     // g + g^T once per pair m <= n, stored at its four places
     if (tid < T * T) {
@@ -144,32 +121,14 @@ __global__ __launch_bounds__(kThreads) void k_sens2(Sens2Args A) {
   }
 }
 
-template <int DIM, int KIND, bool MESH>
-hipError_t launch_loads_one(const Sens2Args& a, long long nc, hipStream_t st) {
-  hipLaunchKernelGGL((k_sens2_loads<DIM, KIND, MESH>), dim3((unsigned)nc), dim3(kThreads), 0, st, a);
-  return hipGetLastError();
-}
-
-template <int DIM, int KIND, bool MESH>
-hipError_t launch_one(const Sens2Args& a, long long nc, hipStream_t st) {
-  hipLaunchKernelGGL((k_sens2<DIM, KIND, MESH>), dim3((unsigned)nc), dim3(kThreads), 0, st, a);
-  return hipGetLastError();
-}
-
 }  // namespace
 
-hipError_t launch_sens2_loads(const Sens2Args& a, int dim, int kind, bool mesh, long long nc, hipStream_t st) {
-  if (nc <= 0) return hipSuccess;
-  return dispatch_dim_kind(dim, kind, [&](auto D, auto K) {
-    return mesh ? launch_loads_one<D(), K(), true>(a, nc, st) : launch_loads_one<D(), K(), false>(a, nc, st);
-  });
+hipError_t launch_sens2_loads(const Sens2Args& a, long long nc, hipStream_t st) {
+  return launch_walk(a, nc, st, walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_sens2_loads<D(), K(), MESH()>; }));
 }
 
-hipError_t launch_sens2(const Sens2Args& a, int dim, int kind, bool mesh, long long nc, hipStream_t st) {
-  if (nc <= 0) return hipSuccess;
-  return dispatch_dim_kind(dim, kind, [&](auto D, auto K) {
-    return mesh ? launch_one<D(), K(), true>(a, nc, st) : launch_one<D(), K(), false>(a, nc, st);
-  });
+hipError_t launch_sens2(const Sens2Args& a, long long nc, hipStream_t st) {
+  return launch_walk(a, nc, st, walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_sens2<D(), K(), MESH()>; }));
 }
 
 }  // namespace hommx

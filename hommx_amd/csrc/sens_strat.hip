@@ -10,9 +10,9 @@
 //
 // One workgroup per macro cell, elements on lanes, the correctors gathered from global memory as k_sens gathers them.  The t (t + 1) / 2
 // running sums of all d d entries (a, b) fit the registers of every kind but 3D elasticity (t = 6: 9 x 21 sums), which takes one pass over
-// the elements per (a, b); the gradient is one more pass with d d sums and no t x t intermediate.  Element-strided partial sums per
-// thread, a butterfly in each wave, the wave totals in order, m <= n computed and mirrored: a cell's outputs do not depend on its batch
-// position, the chunking or which outputs are asked for.  No atomics, no inline assembly.
+// the elements per (a, b); the gradient is one more pass with d d sums and no t x t intermediate.  The fixed-order sums of elem_walk.h
+// (block_sums), m <= n computed and mirrored: a cell's outputs do not depend on its batch position, the chunking or which outputs are
+// asked for.  No atomics, no inline assembly.
 #include <hip/hip_runtime.h>
 
 #include "elem_walk.h"
@@ -21,9 +21,6 @@
 namespace hommx {
 
 namespace {
-
-constexpr int kThreads = kWalkThreads;
-constexpr int kWaves = kWalkWaves;
 
 // entries (a, b) of dA_dM per pass over the elements
 constexpr int pass_group(int dim, int kind) { return kind_sizes(dim, kind).t == 6 ? 1 : dim * dim; }
@@ -96,44 +93,19 @@ __device__ __forceinline__ double stress_entry(const double (&sv)[kind_sizes(DIM
 }
 
 template <int DIM, int KIND, bool MESH>
-__global__ __launch_bounds__(kThreads) void k_sens_strat(StratSensArgs A) {
+__global__ __launch_bounds__(kWalkThreads) void k_sens_strat(StratSensArgs A) {
   constexpr KindSizes ks = kind_sizes(DIM, KIND);
   constexpr int T = ks.t, BS = ks.bs, NCOMP = ks.n_comp;
   constexpr int NSUM = T * (T + 1) / 2;  // dA_dM[a][b][m][n], m <= n, at n (n + 1) / 2 + m
   constexpr int GROUP = pass_group(DIM, KIND), NACC = GROUP * NSUM > DIM * DIM ? GROUP * NSUM : DIM * DIM;
-  __shared__ double red[kWaves][NACC];
+  __shared__ double red[kWalkWaves * NACC];  // the rows of block_sums, of either pass
   const int tid = threadIdx.x;
   const long long cell = blockIdx.x;
   const double* corr = A.corr + cell * T * A.ndof;
   const double* coef = A.coef + cell * A.n_el * NCOMP;
 
-  // M, or the identity (exact: the same gradients as without M), as k_sens holds it
   double Mp[DIM * DIM];
-#pragma unroll
-  for (int k = 0; k < DIM * DIM; ++k) Mp[k] = A.M ? A.M[cell * DIM * DIM + k] : (k % (DIM + 1) == 0 ? 1.0 : 0.0);
-
-  // fixed-order reduction of `count` running sums: wave butterfly, then the wave totals in order; thread 0 hands total q to out(q, v)
-  auto reduce = [&](auto count, double* acc, auto out) {
-    constexpr int N = decltype(count)::value;
-#pragma unroll
-    for (int q = 0; q < N; ++q)
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
-    if ((tid & 63) == 0) {
-#pragma unroll
-      for (int q = 0; q < N; ++q) red[tid >> 6][q] = acc[q];
-    }
-    __syncthreads();
-    if (tid == 0) {
-#pragma unroll
-      for (int q = 0; q < N; ++q) {
-        double v = red[0][q];
-        for (int w = 1; w < kWaves; ++w) v += red[w][q];
-        out(q, v);
-      }
-    }
-    __syncthreads();  // the next pass writes `red` again
-  };
+  cell_M<DIM>(A.M, cell, Mp);
 
   if (A.dA_dM) {
     for (int ab0 = 0; ab0 < DIM * DIM; ab0 += GROUP) {
@@ -175,13 +147,11 @@ __global__ __launch_bounds__(kThreads) void k_sens_strat(StratSensArgs A) {
             }
       });
       double* out = A.dA_dM + (cell * DIM * DIM + ab0) * T * T;
-      reduce(std::integral_constant<int, GROUP * NSUM>{}, acc, [&](int q, double v) {
-        const int g = q / NSUM, r = q % NSUM;
-        int n = 0;
-        while ((n + 1) * (n + 2) / 2 <= r) ++n;
-        const int m = r - n * (n + 1) / 2;
-        out[(g * T + m) * T + n] = out[(g * T + n) * T + m] = v;
+      block_sums<GROUP * NSUM>(acc, reinterpret_cast<double(*)[GROUP * NSUM]>(red), tid, [&](int q, double total) {
+        const int g = q / NSUM, n = tri_row(q % NSUM), m = q % NSUM - n * (n + 1) / 2;
+        out[(g * T + m) * T + n] = out[(g * T + n) * T + m] = total;
       });
+      __syncthreads();  // the next pass writes `red` again
     }
   }
 
@@ -226,23 +196,14 @@ __global__ __launch_bounds__(kThreads) void k_sens_strat(StratSensArgs A) {
       }
     });
     double* out = A.grad_M + cell * DIM * DIM;
-    reduce(std::integral_constant<int, DIM * DIM>{}, acc, [&](int q, double v) { out[q] = v; });
+    block_sums<DIM * DIM>(acc, reinterpret_cast<double(*)[DIM * DIM]>(red), tid, [&](int q, double total) { out[q] = total; });
   }
-}
-
-template <int DIM, int KIND, bool MESH>
-hipError_t launch_one(const StratSensArgs& a, long long nc, hipStream_t st) {
-  hipLaunchKernelGGL((k_sens_strat<DIM, KIND, MESH>), dim3((unsigned)nc), dim3(kThreads), 0, st, a);
-  return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_sens_strat(const StratSensArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t st) {
-  if (nc <= 0) return hipSuccess;
-  return dispatch_dim_kind(dim, kind, [&](auto D, auto K) {
-    return mesh ? launch_one<D(), K(), true>(a, nc, st) : launch_one<D(), K(), false>(a, nc, st);
-  });
+hipError_t launch_sens_strat(const StratSensArgs& a, long long nc, hipStream_t st) {
+  return launch_walk(a, nc, st, walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_sens_strat<D(), K(), MESH()>; }));
 }
 
 }  // namespace hommx

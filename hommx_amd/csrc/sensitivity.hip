@@ -11,9 +11,8 @@
 // way: a node is shared by six (2D) to twenty-four (3D) elements of neighbouring lanes and steps, so the gathers are served by the
 // caches, and a 16^3 elasticity cell (590 KB of correctors) would not fit LDS anyway.  One pass over the elements per direction -- the
 // t (t + 1) / 2 running sums of eight directions do not fit the registers beside the t x t strains -- and one more for the gradient,
-// which has no reduction.  dA: element-strided partial sums per thread, a butterfly in each wave, the wave totals in order, the upper
-// triangle computed and mirrored: a cell's outputs do not depend on its batch position, the chunking or which outputs are asked for.
-// No atomics, no inline assembly.
+// which has no reduction.  dA: the fixed-order sums of elem_walk.h (block_sums), the upper triangle computed and mirrored: a cell's
+// outputs do not depend on its batch position, the chunking or which outputs are asked for.  No atomics, no inline assembly.
 #include <hip/hip_runtime.h>
 
 #include "elem_walk.h"
@@ -23,25 +22,18 @@ namespace hommx {
 
 namespace {
 
-constexpr int kThreads = kWalkThreads;
-constexpr int kWaves = kWalkWaves;
-
-constexpr int tensor_size(int dim, int kind) { return kind_sizes(dim, kind).t; }
-
 template <int DIM, int KIND, bool MESH>
-__global__ __launch_bounds__(kThreads) void k_sens(SensArgs A) {
+__global__ __launch_bounds__(kWalkThreads) void k_sens(SensArgs A) {
   constexpr KindSizes ks = kind_sizes(DIM, KIND);
   constexpr int T = ks.t, NCOMP = ks.n_comp;
   constexpr int NSUM = T * (T + 1) / 2;  // dA[m][n], m <= n, at n (n + 1) / 2 + m
-  __shared__ double red[kWaves][NSUM];
+  __shared__ double red[kWalkWaves][NSUM];
   const int tid = threadIdx.x;
   const long long cell = blockIdx.x;
   const double* corr = A.corr + cell * T * A.ndof;
 
-  // M, or the identity (exact: the same gradients as without M), as k_recon holds it
   double Mp[DIM * DIM];
-#pragma unroll
-  for (int k = 0; k < DIM * DIM; ++k) Mp[k] = A.M ? A.M[cell * DIM * DIM + k] : (k % (DIM + 1) == 0 ? 1.0 : 0.0);
+  cell_M<DIM>(A.M, cell, Mp);
 
   for (int d = 0; d < A.n_dirs; ++d) {
     const double* dir = A.dirs + ((A.per_cell ? cell * A.n_dirs : 0) + d) * A.n_el * NCOMP;
@@ -72,27 +64,11 @@ __global__ __launch_bounds__(kThreads) void k_sens(SensArgs A) {
       }
     });
 
-    // fixed-order reduction: wave butterfly, then the wave totals in order
-#pragma unroll
-    for (int q = 0; q < NSUM; ++q)
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
-    if ((tid & 63) == 0) {
-#pragma unroll
-      for (int q = 0; q < NSUM; ++q) red[tid >> 6][q] = acc[q];
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double* out = A.dA + (cell * A.n_dirs + d) * T * T;
-#pragma unroll
-      for (int n = 0; n < T; ++n)
-#pragma unroll
-        for (int m = 0; m <= n; ++m) {
-          double v = red[0][n * (n + 1) / 2 + m];
-          for (int w = 1; w < kWaves; ++w) v += red[w][n * (n + 1) / 2 + m];
-          out[m * T + n] = out[n * T + m] = v;
-        }
-    }
+    double* out = A.dA + (cell * A.n_dirs + d) * T * T;
+    block_sums<NSUM>(acc, red, tid, [&](int q, double total) {
+      const int n = tri_row(q), m = q - n * (n + 1) / 2;
+      out[m * T + n] = out[n * T + m] = total;
+    });
     __syncthreads();  // the next pass writes `red` again
   }
 
@@ -143,19 +119,10 @@ __global__ __launch_bounds__(kThreads) void k_sens(SensArgs A) {
   }
 }
 
-template <int DIM, int KIND, bool MESH>
-hipError_t launch_one(const SensArgs& a, long long nc, hipStream_t st) {
-  hipLaunchKernelGGL((k_sens<DIM, KIND, MESH>), dim3((unsigned)nc), dim3(kThreads), 0, st, a);
-  return hipGetLastError();
-}
-
 }  // namespace
 
-hipError_t launch_sensitivity(const SensArgs& a, int dim, int kind, bool mesh, long long nc, hipStream_t st) {
-  if (nc <= 0) return hipSuccess;
-  return dispatch_dim_kind(dim, kind, [&](auto D, auto K) {
-    return mesh ? launch_one<D(), K(), true>(a, nc, st) : launch_one<D(), K(), false>(a, nc, st);
-  });
+hipError_t launch_sensitivity(const SensArgs& a, long long nc, hipStream_t st) {
+  return launch_walk(a, nc, st, walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_sens<D(), K(), MESH()>; }));
 }
 
 }  // namespace hommx

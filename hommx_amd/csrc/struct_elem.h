@@ -1,4 +1,4 @@
-// struct_elem.h -- the micro elements of a structured plan, computed in the kernel (reconstruct.hip, sensitivity.hip).
+// struct_elem.h -- the micro elements of a structured plan, computed in the kernel (for_elements of elem_walk.h, k_assemble_loads of loads.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
