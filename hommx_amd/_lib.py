@@ -28,6 +28,8 @@ COEF_PROGRAM = 3
 PROGRAM_MAX_OPS, PROGRAM_MAX_CONSTS, PROGRAM_MAX_STACK = 128, 32, 16  # the limits of a hommx_coef_program
 RECON_MAX_REGIONS = 8  # HOMMX_RECON_MAX_REGIONS
 SENS_MAX_DIRS = 8  # HOMMX_SENS_MAX_DIRS
+PROGRAM_MAX_PARAMS = 4  # HOMMX_PROGRAM_MAX_PARAMS
+DIRS_PARAMETERS = 2  # HOMMX_DIRS_PARAMETERS: per_cell of SensArgs / Sens2Args, the directions are the program's parameter tangents
 
 
 class PlanDesc(C.Structure):
@@ -63,7 +65,7 @@ class CoefProgram(C.Structure):
         ("n_ops", C.c_int32),
         ("n_consts", C.c_int32),
         ("n_comp", C.c_int32),
-        ("reserved", C.c_int32),
+        ("n_params", C.c_int32),  # the first n_params constants are the parameters (0 .. PROGRAM_MAX_PARAMS)
         ("ops", C.c_void_p),
         ("consts", C.c_void_p),
     ]
@@ -180,6 +182,8 @@ def _prototypes() -> dict:
         "hommx_solve_batch_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, vp, vp]),
         "hommx_expand_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp]),
         "hommx_expand_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp]),
+        "hommx_expand_tangents": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp]),
+        "hommx_expand_tangents_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, vp]),
         "hommx_reconstruct_batch": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_reconstruct_batch_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_reconstruct_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),

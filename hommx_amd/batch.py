@@ -227,18 +227,25 @@ def region_labels(labels, n_el: int, n_regions: int | None = None) -> tuple[np.n
     return out, int(n_regions)
 
 
+def _per_cell_code(per_cell) -> int:
+    """per_cell of hommx_sens_args / hommx_sens2_args: 0 shared, 1 per cell, ``"parameters"`` HOMMX_DIRS_PARAMETERS."""
+    return _lib.DIRS_PARAMETERS if isinstance(per_cell, str) and per_cell == "parameters" else int(bool(per_cell))
+
+
 @dataclass(frozen=True)
 class Program:
     """The postfix program of an expression coefficient (include/hommx_hip.h, hommx_coef_program; ``hommx_amd.expr.Expression.program``):
-    ops[n_ops, 2] uint8 = (opcode, operand), consts[n_consts] float64, and the number of components it stores."""
+    ops[n_ops, 2] uint8 = (opcode, operand), consts[n_consts] float64, the number of components it stores, and how many of its first
+    constants are parameters (``Expression(..., p=[...])``)."""
 
     ops: np.ndarray
     consts: np.ndarray
     n_comp: int
+    n_params: int = 0
 
     def struct(self) -> "_lib.CoefProgram":
         """The hommx_coef_program that points into this program's arrays (host memory; keep ``self`` alive while it is in use)."""
-        return _lib.CoefProgram(int(self.ops.shape[0]), int(self.consts.size), int(self.n_comp), 0, self.ops.ctypes.data,
+        return _lib.CoefProgram(int(self.ops.shape[0]), int(self.consts.size), int(self.n_comp), int(self.n_params), self.ops.ctypes.data,
                                 self.consts.ctypes.data if self.consts.size else None)
 
 
@@ -268,10 +275,12 @@ class CoefStream:
                    np.ascontiguousarray(params, dtype=np.float64))
 
     @classmethod
-    def program(cls, points, weights, ops, consts, n_comp: int, midpoints) -> "CoefStream":
+    def program(cls, points, weights, ops, consts, n_comp: int, midpoints, *, n_params: int = 0) -> "CoefStream":
         """An expression coefficient: points[n_el, n_q, dim] and weights[n_q] of the micro quadrature rule, the program of
-        ``Expression.program()`` with its number of components, midpoints[N_c, 3] of the macro cells."""
-        prog = Program(np.ascontiguousarray(ops, dtype=np.uint8).reshape(-1, 2), np.ascontiguousarray(consts, dtype=np.float64).ravel(), int(n_comp))
+        ``Expression.program()`` with its number of components, midpoints[N_c, 3] of the macro cells; ``n_params``: how many of the
+        first constants are the expression's parameters."""
+        prog = Program(np.ascontiguousarray(ops, dtype=np.uint8).reshape(-1, 2), np.ascontiguousarray(consts, dtype=np.float64).ravel(), int(n_comp),
+                       int(n_params))
         return cls("solve_program", (np.ascontiguousarray(points, dtype=np.float64), np.ascontiguousarray(weights, dtype=np.float64), prog),
                    np.ascontiguousarray(midpoints, dtype=np.float64))
 
@@ -448,6 +457,14 @@ class MicroCellPlan:
             raise ValueError(f"n_dirs must be 1 .. {_lib.SENS_MAX_DIRS}; got {nd}")
         return dirs, nd
 
+    @staticmethod
+    def _parameter_count(coef) -> int:
+        """n_params of ``directions="parameters"``: the coefficient must be a program ``CoefStream`` with parameters."""
+        prog = coef.shared[2] if isinstance(coef, CoefStream) and coef.method == "solve_program" else None
+        if prog is None or prog.n_params < 1:
+            raise ValueError('directions="parameters" needs the CoefStream of an expression with parameters (CoefStream.program(..., n_params=...))')
+        return int(prog.n_params)
+
     def _check_weights(self, weights, nc: int) -> np.ndarray:
         """weights[N_c, t, t] as float64."""
         weights = np.ascontiguousarray(weights, dtype=np.float64)
@@ -551,12 +568,17 @@ class MicroCellPlan:
         ``directions[N_c, n_dirs, n_el(, n_comp)]``: up to 8 perturbations of one cell's element stream -> ``dA[N_c, n_dirs, t, t]`` =
         sum_K |K| s^m_K . material(dir_K) s^n_K, the derivative of A_H along each (the direction ``coef`` itself gives A_eff).
         ``weights[N_c, t, t]`` -> ``grad[N_c, n_el(, n_comp)]``, the gradient of weights : A_H with respect to every coefficient entry.
-        At least one of the two.  The correctors never leave the device; the batch runs in the chunks of ``reconstruct``."""
+        At least one of the two.  The correctors never leave the device; the batch runs in the chunks of ``reconstruct``.
+        ``directions="parameters"`` (``coef`` the program stream of an expression with parameters): the directions are the derivatives of
+        the stream with respect to the parameters, formed on the device with the stream itself; ``dA[N_c, n_params, t, t]``."""
         stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
+        parameters = isinstance(directions, str) and directions == "parameters"
+        nd, dirs = (self._parameter_count(coef), None) if parameters else (0, None)
         nc = self._check_stream(stream)
         el = (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
-        nd, dirs = 0, None
-        if directions is not None:
+        if parameters:
+            per_cell = _lib.DIRS_PARAMETERS
+        elif directions is not None:
             dirs, nd = self._check_directions(directions, nc, per_cell)
         grad = None
         if weights is not None:
@@ -565,7 +587,7 @@ class MicroCellPlan:
         elif nd == 0:
             raise ValueError("nothing requested: pass directions, weights or both")
         dA = np.empty((nc, nd, self.t, self.t), dtype=np.float64)
-        args = _lib.SensArgs(nd, int(bool(per_cell)), dirs.ctypes.data if nd else None, dA.ctypes.data if nd else None,
+        args = _lib.SensArgs(nd, int(per_cell), None if dirs is None else dirs.ctypes.data, dA.ctypes.data if nd else None,
                              None if grad is None else weights.ctypes.data, None if grad is None else grad.ctypes.data)
         A, info = self._source_call("hommx_sensitivity_source", nc, M, stream, args)
         return Sensitivities(dA, grad, A, info)
@@ -577,15 +599,21 @@ class MicroCellPlan:
         discrete problem: the derivative of every canonical corrector along a direction is the corrector of a polarisation load, which the
         plan solves on the route ``load_kernel`` names (needs ``load_solve=True`` on the frontal mesh route).  ``first``: ``dA[N_c, n_dirs, t, t]`` of the same
         call as well.  One canonical pass and one load solve per direction; correctors and loads never leave the device; the batch runs in
-        the chunks of ``reconstruct``."""
+        the chunks of ``reconstruct``.  ``directions="parameters"``: as in ``sensitivities``; d2A holds the second derivatives along the
+        parameter tangents, which is the Hessian in the parameters when the expression is affine in them (``affine_in_parameters``)."""
         stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
+        parameters = isinstance(directions, str) and directions == "parameters"
+        nd, dirs = (self._parameter_count(coef), None) if parameters else (0, None)
         nc = self._check_stream(stream)
         if directions is None:
             raise ValueError("directions is required")
-        dirs, nd = self._check_directions(directions, nc, per_cell)
+        if parameters:
+            per_cell = _lib.DIRS_PARAMETERS
+        else:
+            dirs, nd = self._check_directions(directions, nc, per_cell)
         d2A = np.empty((nc, nd, nd, self.t, self.t), dtype=np.float64)
         dA = np.empty((nc, nd, self.t, self.t), dtype=np.float64) if first else None
-        args = _lib.Sens2Args(nd, int(bool(per_cell)), dirs.ctypes.data, d2A.ctypes.data, dA.ctypes.data if first else None)
+        args = _lib.Sens2Args(nd, int(per_cell), None if dirs is None else dirs.ctypes.data, d2A.ctypes.data, dA.ctypes.data if first else None)
         A, info = self._source_call("hommx_second_sensitivity_source", nc, M, stream, args)
         return SecondSensitivities(d2A, dA, A, info)
 
@@ -702,7 +730,26 @@ class MicroCellPlan:
             _lib.check(self._lib.hommx_expand_source(self._h, nc, C.byref(src), out.ctypes.data), "hommx_expand_source")
         return out
 
+    def expand_tangents(self, stream: CoefStream) -> tuple[np.ndarray, np.ndarray]:
+        """(coef[N_c, n_el(, n_comp)], dirs[N_c, n_params, n_el(, n_comp)]) of the program stream of an expression with parameters
+        (hommx_expand_tangents): the stream of ``expand``, bit for bit, and its derivatives with respect to the parameters, formed in one
+        forward-mode pass on the device.  dirs equals ``Expression.host_tangents`` bit for bit for exactly rounded operations."""
+        n_params = self._parameter_count(stream)
+        nc = self._check_stream(stream)
+        el = (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
+        coef, dirs = np.empty((nc,) + el, dtype=np.float64), np.empty((nc, n_params) + el, dtype=np.float64)
+        if nc:
+            src = stream.coef_source()
+            _lib.check(self._lib.hommx_expand_tangents(self._h, nc, C.byref(src), coef.ctypes.data, dirs.ctypes.data), "hommx_expand_tangents")
+        return coef, dirs
+
     # -- device pointers (torch tensors or raw ints), asynchronous --------------------------------
+    def expand_tangents_device(self, n_cells: int, source: "_lib.CoefSource", coef_ptr: int | None, dirs_ptr: int, stream: int | None = None):
+        """Device-pointer form of ``expand_tangents`` (hommx_expand_tangents_device), asynchronous on ``stream``; ``coef_ptr`` None: the
+        tangents alone."""
+        _lib.check(self._lib.hommx_expand_tangents_device(self._h, int(n_cells), C.byref(source), coef_ptr or None, dirs_ptr, stream or None),
+                   "hommx_expand_tangents_device")
+
     def solve_source_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, out_ptr: int, info_ptr: int | None,
                             stream: int | None = None):
         """Device-pointer solve of a coefficient in any form (hommx_solve_batch_source_device), asynchronous on ``stream``: ``source`` =
@@ -752,8 +799,9 @@ class MicroCellPlan:
                              A_ptr: int | None = None, info_ptr: int | None = None, stream: int | None = None):
         """Device-pointer form of ``sensitivities`` (hommx_sensitivity_source_device), asynchronous on ``stream``: ``source`` =
         ``CoefStream.coef_source(upload)`` with device addresses; dirs[n_dirs, n_el, n_comp] or, ``per_cell``, [n_cells, n_dirs, n_el, n_comp]
-        -> dA[n_cells, n_dirs, t, t]; weights[n_cells, t, t] -> grad[n_cells, n_el, n_comp]."""
-        args = _lib.SensArgs(int(n_dirs), int(bool(per_cell)), dirs_ptr or None, dA_ptr or None, weights_ptr or None, grad_ptr or None,
+        -> dA[n_cells, n_dirs, t, t]; weights[n_cells, t, t] -> grad[n_cells, n_el, n_comp].  ``per_cell="parameters"``: the directions
+        are the parameter tangents of the source's program (no ``dirs_ptr``, ``n_dirs`` its n_params)."""
+        args = _lib.SensArgs(int(n_dirs), _per_cell_code(per_cell), dirs_ptr or None, dA_ptr or None, weights_ptr or None, grad_ptr or None,
                              A_ptr or None, info_ptr or None)
         _lib.check(self._lib.hommx_sensitivity_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
                    "hommx_sensitivity_source_device")
@@ -763,8 +811,9 @@ class MicroCellPlan:
                                     stream: int | None = None):
         """Device-pointer form of ``second_sensitivities`` (hommx_second_sensitivity_source_device), asynchronous on ``stream``: ``source`` =
         ``CoefStream.coef_source(upload)`` with device addresses; dirs[n_dirs, n_el, n_comp] or, ``per_cell``, [n_cells, n_dirs, n_el, n_comp]
-        -> d2A[n_cells, n_dirs, n_dirs, t, t]; dA[n_cells, n_dirs, t, t] on request."""
-        args = _lib.Sens2Args(int(n_dirs), int(bool(per_cell)), dirs_ptr or None, d2A_ptr or None, dA_ptr or None, A_ptr or None, info_ptr or None)
+        -> d2A[n_cells, n_dirs, n_dirs, t, t]; dA[n_cells, n_dirs, t, t] on request.  ``per_cell="parameters"``: as in
+        ``sensitivities_device``."""
+        args = _lib.Sens2Args(int(n_dirs), _per_cell_code(per_cell), dirs_ptr or None, d2A_ptr or None, dA_ptr or None, A_ptr or None, info_ptr or None)
         _lib.check(self._lib.hommx_second_sensitivity_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
                                                                     stream or None),
                    "hommx_second_sensitivity_source_device")

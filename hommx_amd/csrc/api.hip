@@ -110,7 +110,8 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 // B_LOADS: what a load pass leaves where a corrector pass leaves A_eff (hommx_loads_source: C0 - f^T K^+ f, unused)
 // B_REFINE: canonical flux field and correction of the refinement step of a fused 2D plan's correctors (10 n^2 doubles per cell)
 // B_SENS2: the polarisation loads of one direction of a second-derivative chunk (t n_el t doubles per cell)
-enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, B_SENS2, N_BUF };
+// B_TANGENT: the parameter tangents of one chunk of a program source, [nc][n_params][n_el][n_comp] (grown with B_EXPAND, by stream_chunk)
+enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, B_SENS2, B_TANGENT, N_BUF };
 
 }  // namespace
 
@@ -288,6 +289,10 @@ int program_check(const hommx_plan* p, const hommx_coef_source* s) {
     return fail(HOMMX_EINVAL, "program: n_ops must be 1 .. %d, got %d", hommx::PROGRAM_MAX_OPS, g->n_ops);
   if (g->n_consts < 0 || g->n_consts > hommx::PROGRAM_MAX_CONSTS)
     return fail(HOMMX_EINVAL, "program: n_consts must be 0 .. %d, got %d", hommx::PROGRAM_MAX_CONSTS, g->n_consts);
+  if (g->n_params < 0 || g->n_params > hommx::PROGRAM_MAX_PARAMS)
+    return fail(HOMMX_EINVAL, "program: n_params must be 0 .. %d, got %d", hommx::PROGRAM_MAX_PARAMS, g->n_params);
+  if (g->n_params > g->n_consts)
+    return fail(HOMMX_EINVAL, "program: n_params is %d, above n_consts (%d): the parameters are the first constants", g->n_params, g->n_consts);
   const int n_comp = hommx::kind_sizes(p->desc.dim, p->desc.kind).n_comp;
   if (g->n_comp != n_comp) return fail(HOMMX_EINVAL, "program: n_comp is %d, the plan's coefficient has %d components", g->n_comp, n_comp);
   if (!g->ops || (g->n_consts > 0 && !g->consts)) return fail(HOMMX_EINVAL, "null program ops / consts");
@@ -378,28 +383,41 @@ int64_t table_doubles(const hommx_plan* p, const hommx_coef_source& s) {
 
 // -- the element stream of a source ---------------------------------------------------------------------------------------------------
 // Cells per chunk of a source, given the `want` of the caller: a sampler form is expanded into the plan's element stream, at most 1 GiB of
-// it (at least one cell), which is grown here; a sampled stream has no such limit
-int64_t stream_cells(const hommx_plan* p, int64_t want) {
-  return std::min(want, std::max<int64_t>((1ll << 27) / std::max<int64_t>(p->n_el * p->ks.n_comp, 1), 1));
+// it (at least one cell), which is grown here; a sampled stream has no such limit.  n_tan: the parameter tangents of a program are
+// expanded beside it (B_TANGENT), and the 1 GiB counts the 1 + n_tan streams
+int64_t stream_cells(const hommx_plan* p, int64_t want, int n_tan = 0) {
+  return std::min(want, std::max<int64_t>((1ll << 27) / std::max<int64_t>(p->n_el * p->ks.n_comp * (1 + n_tan), 1), 1));
 }
-int stream_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t want, int64_t* chunk) {
+int stream_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t want, int64_t* chunk, int n_tan = 0) {
   *chunk = want;
   if (s.form == HOMMX_COEF_SAMPLED) return HOMMX_OK;
-  *chunk = stream_cells(p, want);
-  return grow(p->buf[B_EXPAND], sizeof(double) * *chunk * p->n_el * p->ks.n_comp);
+  *chunk = stream_cells(p, want, n_tan);
+  const size_t stream = sizeof(double) * *chunk * p->n_el * p->ks.n_comp;
+  if (int rc = grow(p->buf[B_TANGENT], stream * n_tan)) return rc;
+  return grow(p->buf[B_EXPAND], stream);
+}
+
+// the stream of cells [c0, c0 + nc) of a program source (into `coef`; null: not wanted) and its parameter tangents, in one launch
+int expand_tangents_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t c0, int64_t nc, hipStream_t st, double* coef, double* tangents) {
+  HIP_TRY(hommx::launch_expand_program_tangent(program_args(*s.program), s.program->n_params, s.table, s.weights, s.n_q, p->desc.dim,
+                                               s.params + c0 * 3, coef, tangents, p->n_el, nc, st));
+  return HOMMX_OK;
 }
 
 // *stream: the element stream of cells [c0, c0 + nc) of a source on the device.  A sampled stream is a view of the caller's; a sampler
-// form is expanded into the plan's element stream (nc <= the chunk of stream_chunk) or, if given, into `into`
+// form is expanded into the plan's element stream (nc <= the chunk of stream_chunk) or, if given, into `into`; `tangents`: a program's
+// parameter tangents as well, in the same launch
 int expand_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t c0, int64_t nc, hipStream_t st, const double** stream,
-                 double* into = nullptr) {
+                 double* into = nullptr, double* tangents = nullptr) {
   const int n_comp = p->ks.n_comp;
   if (s.form == HOMMX_COEF_SAMPLED) {
     *stream = s.coef + c0 * p->n_el * n_comp;
     return HOMMX_OK;
   }
   double* dst = into ? into : static_cast<double*>(p->buf[B_EXPAND].p);
-  if (s.form == HOMMX_COEF_TWO_PHASE)
+  if (tangents) {
+    if (int rc = expand_tangents_chunk(p, s, c0, nc, st, dst, tangents)) return rc;
+  } else if (s.form == HOMMX_COEF_TWO_PHASE)
     HIP_TRY(hommx::launch_expand_two_phase(s.mask, s.values + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st));
   else if (s.form == HOMMX_COEF_PROGRAM)
     HIP_TRY(hommx::launch_expand_program(program_args(*s.program), s.table, s.weights, s.n_q, p->desc.dim, s.params + c0 * 3, dst, p->n_el,
@@ -803,6 +821,55 @@ int hommx_expand_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source*
   return HOMMX_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// what hommx_expand_tangents[_device] check of the source beyond coef_check
+int tangents_check(const hommx_plan* p, const hommx_coef_source* src) {
+  if (int rc = coef_check(p, src)) return rc;
+  if (src->form != HOMMX_COEF_PROGRAM) return fail(HOMMX_EINVAL, "parameter tangents need a HOMMX_COEF_PROGRAM source, got form %d", src->form);
+  if (src->program->n_params < 1) return fail(HOMMX_EINVAL, "parameter tangents: the program has no parameters (n_params == 0)");
+  return HOMMX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int hommx_expand_tangents_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, double* d_coef_out, double* d_dirs_out,
+                                 void* stream) {
+  if (int rc = open_call(p, n_cells, d_dirs_out, "dirs_out", true, [&] { return tangents_check(p, src); }); rc != GO) return rc;
+  const hommx_coef_source s = source_of_form(*src);
+  const int n_tan = s.program->n_params;
+  const int64_t per = p->n_el * p->ks.n_comp;
+  const int64_t chunk = stream_cells(p, n_cells, n_tan);  // straight into the caller's arrays, in launches of at most 1 GiB of streams
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk)
+    if (int rc = expand_tangents_chunk(p, s, c0, std::min(chunk, n_cells - c0), reinterpret_cast<hipStream_t>(stream),
+                                       d_coef_out ? d_coef_out + c0 * per : nullptr, d_dirs_out + c0 * n_tan * per))
+      return rc;
+  return HOMMX_OK;
+}
+
+int hommx_expand_tangents(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, double* coef_out, double* dirs_out) {
+  if (int rc = open_call(p, n_cells, dirs_out, "dirs_out", false, [&] { return tangents_check(p, src); }); rc != GO) return rc;
+  const hommx_coef_source s = source_of_form(*src);
+  const int n_tan = s.program->n_params;
+  const int64_t per = p->n_el * p->ks.n_comp;
+  hommx_coef_source ds;
+  const void* none = nullptr;
+  if (int rc = stage_source(p, n_cells, s, {nullptr, 0, &none}, &ds)) return rc;
+  int64_t chunk = 0;
+  if (int rc = stream_chunk(p, s, n_cells, &chunk, n_tan)) return rc;
+  double *d_coef = static_cast<double*>(p->buf[B_EXPAND].p), *d_dirs = static_cast<double*>(p->buf[B_TANGENT].p);
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    const int64_t nc = std::min(chunk, n_cells - c0);
+    if (int rc = expand_tangents_chunk(p, ds, c0, nc, nullptr, coef_out ? d_coef : nullptr, d_dirs)) return rc;
+    if (coef_out) HIP_TRY(hipMemcpyAsync(coef_out + c0 * per, d_coef, sizeof(double) * nc * per, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpyAsync(dirs_out + c0 * n_tan * per, d_dirs, sizeof(double) * nc * n_tan * per, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+  }
+  return HOMMX_OK;
+}
+
 int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* coef, const double* M, double* A_eff,
                                  double* correctors, int32_t* info) {
   if (int rc = open_call(p, n_cells, coef && A_eff && correctors, "coef / A_eff / correctors"); rc != GO) return rc;
@@ -928,10 +995,15 @@ using ChunkRule = int64_t (*)(const hommx_plan*, int64_t, size_t);  // recon_chu
 // synchronisation.
 // host: what every cell shares (mask, table, weights of the source, the shared input) and the per-cell values of a sampler form travel
 // once, in the plan's pinned block (stage_source); the other inputs stream into B_IN and the outputs the caller asked for stream out of
-// B_OUT chunk by chunk, so device memory is bounded by the chunk, whose bytes per cell count both blocks
+// B_OUT chunk by chunk, so device memory is bounded by the chunk, whose bytes per cell count both blocks.
+// tangents (HOMMX_DIRS_PARAMETERS): a pointer member of v.a that receives, per chunk, the parameter tangents of the program source --
+// [nc][n_params][n_el][n_comp] in B_TANGENT, formed by the launch that expands the stream; their bytes count as scratch of the chunk
 template <typename Args, size_t NI, size_t NO, typename Run>
 int derived_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, Chunk<Args>& v, const CellArray (&ins)[NI],
-                 const CellArray (&outs)[NO], int32_t** info, size_t scratch, ChunkRule rule, bool device, hipStream_t st, Run run) {
+                 const CellArray (&outs)[NO], int32_t** info, size_t scratch, ChunkRule rule, bool device, hipStream_t st, Run run,
+                 const double** tangents = nullptr) {
+  const int n_tan = tangents ? s.program->n_params : 0;
+  scratch += sizeof(double) * n_tan * p->n_el * p->ks.n_comp;
   constexpr size_t N[2] = {NI + 2, NO + 1};
   constexpr size_t NMAX = std::max(N[0], N[1]);
   v.coef = s.coef;
@@ -956,13 +1028,13 @@ int derived_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, con
   char* dev[2][NMAX] = {};
   int64_t chunk = 0;
   if (device) {
-    if (int rc = stream_chunk(p, s, rule(p, n_cells, scratch), &chunk)) return rc;
+    if (int rc = stream_chunk(p, s, rule(p, n_cells, scratch), &chunk, n_tan)) return rc;
   } else {
     const void* d_shared = nullptr;
     const hommx::HostPiece more{shared ? shared->get() : nullptr, shared ? shared->elem * shared->n : 0, &d_shared};
     if (int rc = stage_source(p, n_cells, s, more, &ds)) return rc;
     if (shared) shared->set(d_shared);
-    if (int rc = stream_chunk(p, s, rule(p, n_cells, per_cell), &chunk)) return rc;
+    if (int rc = stream_chunk(p, s, rule(p, n_cells, per_cell), &chunk, n_tan)) return rc;
     for (int io = 0; io < 2; ++io) {
       size_t bytes[NMAX] = {};
       for (size_t k = 0; k < N[io]; ++k) bytes[k] = cell[io][k] * chunk;
@@ -979,8 +1051,10 @@ int derived_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, con
         tab[io][k].set(at);
         if (!device && !io && at) HIP_TRY(hipMemcpy(at, user[io][k] + c0 * cell[io][k], nc * cell[io][k], hipMemcpyHostToDevice));
       }
+    double* tan = n_tan ? static_cast<double*>(p->buf[B_TANGENT].p) : nullptr;
     if (!v.coef)
-      if (int rc = expand_chunk(p, ds, c0, nc, st, &v.coef)) return rc;
+      if (int rc = expand_chunk(p, ds, c0, nc, st, &v.coef, nullptr, tan)) return rc;
+    if (tan) *tangents = tan;
     if (int rc = run(nc, chunk, v)) return rc;
     if (device) continue;
     for (size_t k = 0; k < N[1]; ++k)
@@ -1103,10 +1177,23 @@ int sens_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_sens_ar
   return HOMMX_OK;
 }
 
-int sens_checks(const hommx_sens_args* a) {
+// HOMMX_DIRS_PARAMETERS: the directions are the parameter tangents of the source's program; `s` has passed coef_check
+bool parameter_dirs(int32_t per_cell) { return per_cell == HOMMX_DIRS_PARAMETERS; }
+int parameter_dirs_check(const hommx_coef_source* s, int32_t n_dirs, const void* dirs) {
+  if (s->form != HOMMX_COEF_PROGRAM) return fail(HOMMX_EINVAL, "HOMMX_DIRS_PARAMETERS needs a HOMMX_COEF_PROGRAM source, got form %d", s->form);
+  if (s->program->n_params == 0) return fail(HOMMX_EINVAL, "HOMMX_DIRS_PARAMETERS: the program has no parameters (n_params == 0)");
+  if (n_dirs != s->program->n_params)
+    return fail(HOMMX_EINVAL, "HOMMX_DIRS_PARAMETERS: n_dirs must be the program's n_params (%d), got %d", s->program->n_params, n_dirs);
+  if (dirs) return fail(HOMMX_EINVAL, "HOMMX_DIRS_PARAMETERS: dirs must be NULL (the library forms the directions)");
+  return HOMMX_OK;
+}
+
+int sens_checks(const hommx_coef_source* s, const hommx_sens_args* a) {
   if (a->n_dirs < 0 || a->n_dirs > HOMMX_SENS_MAX_DIRS)
     return fail(HOMMX_EINVAL, "n_dirs must be 0 .. %d, got %d", HOMMX_SENS_MAX_DIRS, a->n_dirs);
-  if (a->n_dirs > 0 && !(a->dirs && a->dA)) return fail(HOMMX_EINVAL, "n_dirs > 0 needs both dirs and dA");
+  if (parameter_dirs(a->per_cell))
+    if (int rc = parameter_dirs_check(s, a->n_dirs, a->dirs)) return rc;
+  if (a->n_dirs > 0 && !((a->dirs || parameter_dirs(a->per_cell)) && a->dA)) return fail(HOMMX_EINVAL, "n_dirs > 0 needs both dirs and dA");
   if (!a->weights != !a->grad) return fail(HOMMX_EINVAL, "weights and grad: both or neither");
   if (a->n_dirs == 0 && !a->grad) return fail(HOMMX_EINVAL, "nothing requested: neither directions nor a gradient");
   return HOMMX_OK;
@@ -1120,7 +1207,8 @@ int sens_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const 
   const CellArray in[] = {{&a.dirs, a.n_dirs * el, a.n_dirs && a.per_cell ? PER_CELL : SHARED}, {&a.weights, tt}};
   const CellArray out[] = {{&a.dA, a.n_dirs * tt}, {&a.A_eff, tt, KEPT}, {&a.grad, el}};
   return derived_call(p, n_cells, s, M, v, in, out, &a.info, 0, recon_chunk, device, st,
-                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_sens_args>& c) { return sens_run(p, nc, chunk, c, st); });
+                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_sens_args>& c) { return sens_run(p, nc, chunk, c, st); },
+                      parameter_dirs(a.per_cell) ? &a.dirs : nullptr);
 }
 
 // -- stratification sensitivities (hommx_stratification_sensitivity_source[_device]) --------------------------------------------------------
@@ -1288,7 +1376,9 @@ int sens2_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, con
   auto checks = [&] {
     if (a->n_dirs < 1 || a->n_dirs > HOMMX_SENS_MAX_DIRS)
       return fail(HOMMX_EINVAL, "n_dirs must be 1 .. %d, got %d", HOMMX_SENS_MAX_DIRS, a->n_dirs);
-    if (!a->dirs || !a->d2A) return fail(HOMMX_EINVAL, "null dirs / d2A");
+    if (parameter_dirs(a->per_cell))
+      if (int rc = parameter_dirs_check(src, a->n_dirs, a->dirs)) return rc;
+    if ((!a->dirs && !parameter_dirs(a->per_cell)) || !a->d2A) return fail(HOMMX_EINVAL, "null dirs / d2A");
     if (p->desc.n_micro == 0 && !(p->desc.flags & (HOMMX_MESH_FLAG_TREE | HOMMX_MESH_FLAG_LOADS)))
       return fail(HOMMX_EINVAL, "the frontal mesh route (mesh_front) solves for the canonical loads only: second derivatives need the load "
                                 "solve of a plan of the tree route (HOMMX_MESH_FLAG_TREE, route=\"tree\")");
@@ -1307,7 +1397,8 @@ int sens2_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const
   const CellArray in[] = {{&a.dirs, a.n_dirs * el, a.per_cell ? PER_CELL : SHARED}};
   const CellArray out[] = {{&a.d2A, a.n_dirs * a.n_dirs * tt}, {&a.A_eff, tt, KEPT}, {&a.dA, a.n_dirs * tt}};
   return derived_call(p, n_cells, s, M, v, in, out, &a.info, sens2_extra(p), load_chunk, device, st,
-                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_sens2_args>& c) { return sens2_run(p, nc, chunk, c, st); });
+                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_sens2_args>& c) { return sens2_run(p, nc, chunk, c, st); },
+                      parameter_dirs(a.per_cell) ? &a.dirs : nullptr);
 }
 
 }  // namespace
@@ -1354,12 +1445,12 @@ int hommx_reconstruct_source(hommx_plan* p, int64_t n_cells, const hommx_coef_so
 
 int hommx_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const hommx_sens_args* args,
                                     void* stream) {
-  if (int rc = source_open(p, n_cells, src, args, true, [&] { return sens_checks(args); }); rc != GO) return rc;
+  if (int rc = source_open(p, n_cells, src, args, true, [&] { return sens_checks(src, args); }); rc != GO) return rc;
   return sens_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hommx_sensitivity_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_sens_args* args) {
-  if (int rc = source_open(p, n_cells, src, args, false, [&] { return sens_checks(args); }); rc != GO) return rc;
+  if (int rc = source_open(p, n_cells, src, args, false, [&] { return sens_checks(src, args); }); rc != GO) return rc;
   return sens_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
 }
 

@@ -35,4 +35,14 @@ struct ProgramArgs {
 hipError_t launch_expand_program(const ProgramArgs& prog, const double* d_points, const double* d_weights, int n_q, int dim,
                                  const double* d_mid, double* d_coef, long long n_el, long long ncells, hipStream_t stream);
 
+// The parameters of a program are its first n_params constants (include/hommx_hip.h, HOMMX_PROGRAM_MAX_PARAMS)
+constexpr int PROGRAM_MAX_PARAMS = 4;
+
+// coef_program.hip, forward mode: in one pass the stream of launch_expand_program, bit for bit (d_coef; null: not written), and its
+// derivatives with respect to the parameters, dirs[cell][j][el][comp], j < n_params (1 .. PROGRAM_MAX_PARAMS), by the rules of
+// include/hommx_hip.h (hommx_expand_tangents)
+hipError_t launch_expand_program_tangent(const ProgramArgs& prog, int n_params, const double* d_points, const double* d_weights, int n_q,
+                                         int dim, const double* d_mid, double* d_coef, double* d_dirs, long long n_el, long long ncells,
+                                         hipStream_t stream);
+
 }  // namespace hommx

@@ -3,16 +3,24 @@
 order on both sides.
 
 The text is parsed with ``ast`` and never evaluated by Python.  Grammar: the names ``x[0..2]`` (macro cell midpoint), ``y[0..d-1]`` (fast
-variable) and ``pi``, numeric literals, ``+ - * /``, unary ``-``, ``**`` with a literal integer exponent 0 .. 8, the comparisons
-``< <= > >=`` with ``and`` / ``or`` / ``not`` on them, and the calls ``abs min max where(c, a, b) sqrt sin cos tan exp log tanh``.
+variable), ``p[0..3]`` (a parameter, its value given with ``Expression(..., p=[...])``) and ``pi``, numeric literals, ``+ - * /``, unary
+``-``, ``**`` with a literal integer exponent 0 .. 8, the comparisons ``< <= > >=`` with ``and`` / ``or`` / ``not`` on them, and the
+calls ``abs min max where(c, a, b) sqrt sin cos tan exp log tanh``.
 
 Because the library can read the expression, its quadrature degree is estimated from the tree by the rules of UFL's degree estimation
 (recalled here, UFL is not a dependency): see ``Expression.degree``.
+
+Parameters are the first constants of the program (``p[k]`` is ``CONST k``), so every path that takes a program takes one with
+parameters.  The library also differentiates the program with respect to them in forward mode (csrc/coef_program.hip,
+``k_expand_program_tangent``); ``Expression.host_tangents`` is the NumPy twin of that pass: the rules of ``_run_tangent``, the same
+operations in the same order.
 """
 
 from __future__ import annotations
 
 import ast
+import copy
+import logging
 import math
 
 import numpy as np
@@ -22,6 +30,7 @@ import numpy as np
  OP_SELECT, OP_SQRT, OP_SIN, OP_COS, OP_TAN, OP_EXP, OP_LOG, OP_TANH, OP_DUP, OP_STORE) = range(28)
 MAX_OPS, MAX_CONSTS, MAX_STACK, MAX_COMP = 128, 32, 16, 6
 MAX_POWER = 8
+MAX_PARAMS = 4  # HOMMX_PROGRAM_MAX_PARAMS
 
 _BINARY = {ast.Add: OP_ADD, ast.Sub: OP_SUB, ast.Mult: OP_MUL, ast.Div: OP_DIV}
 _COMPARE = {ast.Lt: OP_LT, ast.LtE: OP_LE, ast.Gt: OP_GT, ast.GtE: OP_GE}
@@ -31,6 +40,7 @@ _MATH_NUMPY = {OP_SQRT: np.sqrt, OP_SIN: np.sin, OP_COS: np.cos, OP_TAN: np.tan,
 _POPS = {OP_CONST: 0, OP_X: 0, OP_Y: 0, OP_DUP: 1, OP_NEG: 1, OP_ABS: 1, OP_NOT: 1, OP_SELECT: 3, OP_STORE: 1}
 _POPS.update({op: 1 for op in _MATH.values()})
 _PUSHES = {OP_DUP: 2, OP_STORE: 0}
+_INF = float("inf")
 
 
 def _bad(node, why: str):
@@ -43,14 +53,16 @@ def _bad(node, why: str):
 
 
 class _Node:
-    """One node of the checked tree: ``op`` with ``args`` (nodes) or a leaf (``value``: the constant, or the index of x / y);
+    """One node of the checked tree: ``op`` with ``args`` (nodes) or a leaf (``value``: the constant, or the index of x / y / p);
     ``boolean``: a comparison or a combination of comparisons; ``degree``: the estimate of the module docstring; ``varying``: depends on
-    x or y (a subtree that does not is folded into one constant)."""
+    x, y or a parameter (a subtree that does not is folded into one constant); ``p_degree``: the degree in the parameters
+    (``Expression.p_degree``)."""
 
-    __slots__ = ("op", "args", "value", "boolean", "degree", "varying", "power")
+    __slots__ = ("op", "args", "value", "boolean", "degree", "varying", "power", "p_degree")
 
-    def __init__(self, op, args=(), value=None, boolean=False, degree=0, varying=False, power=0):
+    def __init__(self, op, args=(), value=None, boolean=False, degree=0, varying=False, power=0, p_degree=0):
         self.op, self.args, self.value, self.boolean, self.degree, self.varying, self.power = op, tuple(args), value, boolean, degree, varying, power
+        self.p_degree = p_degree
 
     def key(self):
         """Structural identity (the off-diagonal texts of a matrix must parse to equal trees)."""
@@ -59,6 +71,15 @@ class _Node:
 
 
 _POW = -1  # a node of the tree only: the program spells it DUP / MUL
+_PARAM = -2  # p[k], a node of the tree only: the program spells it CONST k (the parameters are the first constants)
+
+
+class _Context:
+    """What the components of one Expression share while they are checked: the number of parameters (None: no ``p=``) and the texts of
+    the comparisons that read one."""
+
+    def __init__(self, n_params=None):
+        self.n_params, self.compared = n_params, []
 
 
 def _number(node, value) -> _Node:
@@ -67,7 +88,11 @@ def _number(node, value) -> _Node:
     return _Node(OP_CONST, value=float(value))
 
 
-def _check(node) -> _Node:
+def _literal_int(node, lo: int, hi: int) -> bool:
+    return isinstance(node, ast.Constant) and isinstance(node.value, int) and not isinstance(node.value, bool) and lo <= node.value <= hi
+
+
+def _check(node, ctx: _Context) -> _Node:
     """ast node -> checked tree; anything outside the grammar raises ValueError naming the node."""
     if isinstance(node, ast.Constant):
         return _number(node, node.value)
@@ -76,17 +101,22 @@ def _check(node) -> _Node:
             return _Node(OP_CONST, value=math.pi)
         raise _bad(node, "unknown name (x[i], y[i] and pi are the names)")
     if isinstance(node, ast.Subscript):
+        if isinstance(node.value, ast.Name) and node.value.id == "p" and ctx.n_params is not None:
+            if not _literal_int(node.slice, 0, ctx.n_params - 1):
+                raise _bad(node, f"the index of p is a literal integer below the number of parameters ({ctx.n_params})")
+            return _Node(_PARAM, value=int(node.slice.value), varying=True, p_degree=1)
+        if isinstance(node.value, ast.Name) and node.value.id == "p":
+            raise _bad(node, "p[k] needs the values of the parameters (p=[...])")
         if not (isinstance(node.value, ast.Name) and node.value.id in ("x", "y")):
             raise _bad(node, "only x and y are indexed")
-        idx = node.slice
-        if not (isinstance(idx, ast.Constant) and isinstance(idx.value, int) and not isinstance(idx.value, bool) and 0 <= idx.value <= 2):
+        if not _literal_int(node.slice, 0, 2):
             raise _bad(node, "the index of x and y is a literal 0, 1 or 2")
         fast = node.value.id == "y"
-        return _Node(OP_Y if fast else OP_X, value=int(idx.value), degree=1 if fast else 0, varying=True)
+        return _Node(OP_Y if fast else OP_X, value=int(node.slice.value), degree=1 if fast else 0, varying=True)
     if isinstance(node, ast.UnaryOp):
-        a = _check(node.operand)
+        a = _check(node.operand, ctx)
         if isinstance(node.op, ast.USub):
-            return _Node(OP_NEG, [_numeric(a, node)], degree=a.degree, varying=a.varying)
+            return _Node(OP_NEG, [_numeric(a, node)], degree=a.degree, varying=a.varying, p_degree=a.p_degree)
         if isinstance(node.op, ast.UAdd):
             return _numeric(a, node)
         if isinstance(node.op, ast.Not):
@@ -94,25 +124,34 @@ def _check(node) -> _Node:
         raise _bad(node, "unknown unary operator")
     if isinstance(node, ast.BinOp):
         if isinstance(node.op, ast.Pow):
-            a = _numeric(_check(node.left), node)
+            a = _numeric(_check(node.left, ctx), node)
             k = node.right
-            if not (isinstance(k, ast.Constant) and isinstance(k.value, int) and not isinstance(k.value, bool) and 0 <= k.value <= MAX_POWER):
+            if not _literal_int(k, 0, MAX_POWER):
                 raise _bad(node, f"the exponent of ** is a literal integer 0 .. {MAX_POWER}")
-            return _Node(_POW, [a], power=int(k.value), degree=k.value * a.degree, varying=a.varying and k.value > 0)
+            return _Node(_POW, [a], power=int(k.value), degree=k.value * a.degree, varying=a.varying and k.value > 0,
+                         p_degree=k.value * a.p_degree if k.value else 0)
         if type(node.op) not in _BINARY:
             raise _bad(node, "unknown binary operator")
-        a, b = _numeric(_check(node.left), node), _numeric(_check(node.right), node)
+        a, b = _numeric(_check(node.left, ctx), node), _numeric(_check(node.right, ctx), node)
         op = _BINARY[type(node.op)]
         degree = max(a.degree, b.degree) if op in (OP_ADD, OP_SUB) else a.degree + b.degree
-        return _Node(op, [a, b], degree=degree, varying=a.varying or b.varying)
+        if op in (OP_ADD, OP_SUB):
+            p_degree = max(a.p_degree, b.p_degree)
+        elif op == OP_MUL:
+            p_degree = a.p_degree + b.p_degree
+        else:  # a quotient is a polynomial in the parameters only over a denominator without them
+            p_degree = a.p_degree if b.p_degree == 0 else _INF
+        return _Node(op, [a, b], degree=degree, varying=a.varying or b.varying, p_degree=p_degree)
     if isinstance(node, ast.Compare):
         if len(node.ops) != 1 or type(node.ops[0]) not in _COMPARE:
             raise _bad(node, "a comparison is one of < <= > >= between two values")
-        a, b = _numeric(_check(node.left), node), _numeric(_check(node.comparators[0]), node)
+        a, b = _numeric(_check(node.left, ctx), node), _numeric(_check(node.comparators[0], ctx), node)
+        if a.p_degree or b.p_degree:
+            ctx.compared.append(ast.unparse(node))
         return _Node(_COMPARE[type(node.ops[0])], [a, b], boolean=True, varying=a.varying or b.varying)
     if isinstance(node, ast.BoolOp):
         op = OP_AND if isinstance(node.op, ast.And) else OP_OR
-        parts = [_logical(_check(v), node) for v in node.values]
+        parts = [_logical(_check(v, ctx), node) for v in node.values]
         out = parts[0]
         for p in parts[1:]:  # left to right, as Python evaluates them
             out = _Node(op, [out, p], boolean=True, varying=out.varying or p.varying)
@@ -120,19 +159,21 @@ def _check(node) -> _Node:
     if isinstance(node, ast.Call):
         if not isinstance(node.func, ast.Name) or node.keywords:
             raise _bad(node, "unknown call")
-        name, args = node.func.id, [_check(a) for a in node.args]
+        name, args = node.func.id, [_check(a, ctx) for a in node.args]
         varying = any(a.varying for a in args)
+        kinked = _INF if any(a.p_degree for a in args) else 0  # abs, min, max and the math functions are no polynomials
         if name == "abs" and len(args) == 1:
-            return _Node(OP_ABS, [_numeric(args[0], node)], degree=args[0].degree, varying=varying)
+            return _Node(OP_ABS, [_numeric(args[0], node)], degree=args[0].degree, varying=varying, p_degree=kinked)
         if name in ("min", "max") and len(args) == 2:
             a, b = _numeric(args[0], node), _numeric(args[1], node)
-            return _Node(OP_MIN if name == "min" else OP_MAX, [a, b], degree=max(a.degree, b.degree), varying=varying)
+            return _Node(OP_MIN if name == "min" else OP_MAX, [a, b], degree=max(a.degree, b.degree), varying=varying, p_degree=kinked)
         if name == "where" and len(args) == 3:
             c, a, b = _logical(args[0], node), _numeric(args[1], node), _numeric(args[2], node)
-            return _Node(OP_SELECT, [c, a, b], degree=max(a.degree, b.degree), varying=varying)  # the condition does not count
+            return _Node(OP_SELECT, [c, a, b], degree=max(a.degree, b.degree), varying=varying,
+                         p_degree=max(a.p_degree, b.p_degree))  # the condition does not count
         if name in _MATH and len(args) == 1:
             a = _numeric(args[0], node)
-            return _Node(_MATH[name], [a], degree=0 if a.degree == 0 else a.degree + 2, varying=varying)
+            return _Node(_MATH[name], [a], degree=0 if a.degree == 0 else a.degree + 2, varying=varying, p_degree=kinked)
         raise _bad(node, "unknown call (abs min max where sqrt sin cos tan exp log tanh are the calls)")
     raise _bad(node, "not part of the expression grammar")
 
@@ -149,7 +190,7 @@ def _logical(n: _Node, at) -> _Node:
     return n
 
 
-def _parse(text) -> _Node:
+def _parse(text, ctx: _Context | None = None) -> _Node:
     if isinstance(text, (int, float)) and not isinstance(text, bool):
         text = repr(float(text))
     if not isinstance(text, str):
@@ -158,49 +199,52 @@ def _parse(text) -> _Node:
         tree = ast.parse(text.strip(), mode="eval")
     except SyntaxError as e:
         raise ValueError(f"expression: cannot parse {text!r}: {e.msg}") from None
-    return _numeric(_check(tree.body), tree.body)
+    return _numeric(_check(tree.body, ctx or _Context()), tree.body)
 
 
-def _emit(n: _Node, ops: list, consts: list):
-    """Postfix code of a tree.  A subtree without x and y is one constant: the value this module's own interpreter gives it, so literals
-    fold exactly where Python's evaluation order brings two of them together (``2*pi*y[0]`` holds the constant 2 pi; ``y[0]*2*pi`` none)."""
+def _emit(n: _Node, ops: list, consts: list, n_params: int = 0):
+    """Postfix code of a tree.  A subtree without x, y and p is one constant: the value this module's own interpreter gives it, so
+    literals fold exactly where Python's evaluation order brings two of them together (``2*pi*y[0]`` holds the constant 2 pi;
+    ``y[0]*2*pi`` none).  Equal constants share a slot, but never one of the first ``n_params``: those are the parameters."""
     if not n.varying and not n.boolean:
         if n.op == OP_CONST:
             value = n.value
         else:
             sub_ops, sub_consts = [], []
-            _emit_plain(n, sub_ops, sub_consts)
+            _emit_plain(n, sub_ops, sub_consts, 0)
             sub_ops.append((OP_STORE, 0))
             with np.errstate(all="ignore"):
                 value = float(np.asarray(_run(sub_ops, sub_consts, 1, np.zeros((3, 1)), np.zeros((3, 1)))[0]).reshape(-1)[0])
         bits = np.float64(value).tobytes()
-        for k, c in enumerate(consts):
-            if np.float64(c).tobytes() == bits:
+        for k in range(n_params, len(consts)):
+            if np.float64(consts[k]).tobytes() == bits:
                 break
         else:
             k = len(consts)
             consts.append(value)
         ops.append((OP_CONST, k))
         return
-    _emit_plain(n, ops, consts)
+    _emit_plain(n, ops, consts, n_params)
 
 
-def _emit_plain(n: _Node, ops: list, consts: list):
+def _emit_plain(n: _Node, ops: list, consts: list, n_params: int):
     if n.op == OP_CONST:
         consts.append(n.value)
         ops.append((OP_CONST, len(consts) - 1))
+    elif n.op == _PARAM:
+        ops.append((OP_CONST, n.value))
     elif n.op in (OP_X, OP_Y):
         ops.append((n.op, n.value))
     elif n.op == _POW:
         if n.power == 0:  # a**0 is 1 whatever a is
-            _emit(_Node(OP_CONST, value=1.0), ops, consts)
+            _emit(_Node(OP_CONST, value=1.0), ops, consts, n_params)
             return
-        _emit(n.args[0], ops, consts)
+        _emit(n.args[0], ops, consts, n_params)
         ops.extend([(OP_DUP, 0)] * (n.power - 1))  # a a ... a, then the products: ((a a) a) a up to the order of commuting factors
         ops.extend([(OP_MUL, 0)] * (n.power - 1))
     else:
         for a in n.args:
-            _emit(a, ops, consts)
+            _emit(a, ops, consts, n_params)
         ops.append((n.op, 0))
 
 
@@ -241,34 +285,122 @@ def _run(ops, consts, n_comp: int, x, y) -> list:
             stack.append(-a if op == OP_NEG else np.abs(a) if op == OP_ABS else flag(a == 0.0) if op == OP_NOT else _MATH_NUMPY[op](a))
         else:
             b, a = stack.pop(), stack.pop()
-            if op == OP_ADD:
-                v = a + b
-            elif op == OP_SUB:
-                v = a - b
-            elif op == OP_MUL:
-                v = a * b
-            elif op == OP_DIV:
-                v = a / b
-            elif op == OP_MIN:
-                v = np.where(b < a, b, a)
-            elif op == OP_MAX:
-                v = np.where(b > a, b, a)
-            elif op == OP_LT:
-                v = flag(a < b)
-            elif op == OP_LE:
-                v = flag(a <= b)
-            elif op == OP_GT:
-                v = flag(a > b)
-            elif op == OP_GE:
-                v = flag(a >= b)
-            elif op == OP_AND:
-                v = flag((a != 0.0) & (b != 0.0))
-            elif op == OP_OR:
-                v = flag((a != 0.0) | (b != 0.0))
-            else:
-                raise ValueError(f"program: unknown opcode {op}")
-            stack.append(v)
+            stack.append(_binary(op, a, b, flag))
     return out
+
+
+def _binary(op, a, b, flag):
+    """The value of a two-operand instruction for (a, b), b on top."""
+    if op == OP_ADD:
+        return a + b
+    if op == OP_SUB:
+        return a - b
+    if op == OP_MUL:
+        return a * b
+    if op == OP_DIV:
+        return a / b
+    if op == OP_MIN:
+        return np.where(b < a, b, a)
+    if op == OP_MAX:
+        return np.where(b > a, b, a)
+    if op == OP_LT:
+        return flag(a < b)
+    if op == OP_LE:
+        return flag(a <= b)
+    if op == OP_GT:
+        return flag(a > b)
+    if op == OP_GE:
+        return flag(a >= b)
+    if op == OP_AND:
+        return flag((a != 0.0) & (b != 0.0))
+    if op == OP_OR:
+        return flag((a != 0.0) | (b != 0.0))
+    raise ValueError(f"program: unknown opcode {op}")
+
+
+def _run_tangent(ops, consts, n_comp: int, n_params: int, x, y) -> tuple[list, list]:
+    """``_run`` in forward mode: (values[n_comp], tangents[n_comp][n_params]), the rules of include/hommx_hip.h (hommx_expand_tangents)
+    as k_expand_program_tangent applies them.  A stack entry is (v, d_0 .. d_{P-1}); the value part is ``_run``'s.  A tangent that is
+    None is +0.0 everywhere: where every operand's d_j is 0.0 the result's d_j is +0.0 and the formula is not evaluated -- structurally
+    (None) or, point by point, through ``np.where`` -- so a sqrt(0) or a division by zero in a part of the expression that does not read
+    p[j] cannot make its tangent NaN."""
+    P = n_params
+    stack, out_v, out_d = [], [None] * n_comp, [None] * n_comp
+    one, zero, two = np.float64(1.0), np.float64(0.0), np.float64(2.0)
+    flag = lambda m: np.where(m, one, zero)
+    none = [None] * P
+
+    def rule(operands, formula):
+        """d_j of a result from the d_j of its operands: +0.0 where all of them are 0.0, else formula(*operands)."""
+        if all(d is None for d in operands):
+            return None
+        full = [zero if d is None else d for d in operands]
+        dead = full[0] == 0.0
+        for d in full[1:]:
+            dead = dead & (d == 0.0)
+        return np.where(dead, zero, formula(*full))
+
+    for op, k in ops:
+        if op == OP_CONST:
+            stack.append((np.float64(consts[k]), [one if (k == j and k < P) else None for j in range(P)]))
+        elif op == OP_X:
+            stack.append((np.asarray(x[k], dtype=np.float64), list(none)))
+        elif op == OP_Y:
+            stack.append((np.asarray(y[k], dtype=np.float64), list(none)))
+        elif op == OP_DUP:
+            stack.append((stack[-1][0], list(stack[-1][1])))
+        elif op == OP_STORE:
+            out_v[k], out_d[k] = stack.pop()
+        elif op == OP_SELECT:
+            (b, db), (a, da), (c, _) = stack.pop(), stack.pop(), stack.pop()
+            pick = c != 0.0
+            stack.append((np.where(pick, a, b), [rule((da[j], db[j]), lambda p, q: np.where(pick, p, q)) for j in range(P)]))
+        elif op == OP_NOT:
+            a, _ = stack.pop()
+            stack.append((flag(a == 0.0), list(none)))
+        elif op == OP_NEG:
+            a, da = stack.pop()
+            stack.append((-a, [rule((da[j],), lambda p: -p) for j in range(P)]))
+        elif op == OP_ABS:
+            a, da = stack.pop()
+            stack.append((np.abs(a), [rule((da[j],), lambda p: np.where(a < 0.0, -p, p)) for j in range(P)]))
+        elif op in _MATH_NUMPY:
+            a, da = stack.pop()
+            v = _MATH_NUMPY[op](a)
+            if op == OP_SQRT:
+                f = lambda p: p / (two * v)
+            elif op == OP_SIN:
+                f = lambda p: np.cos(a) * p
+            elif op == OP_COS:
+                f = lambda p: -(np.sin(a) * p)
+            elif op == OP_TAN:
+                f = lambda p: p * (one + v * v)
+            elif op == OP_EXP:
+                f = lambda p: v * p
+            elif op == OP_LOG:
+                f = lambda p: p / a
+            else:  # OP_TANH
+                f = lambda p: p * (one + -(v * v))
+            stack.append((v, [rule((da[j],), f) for j in range(P)]))
+        else:
+            (b, db), (a, da) = stack.pop(), stack.pop()
+            v = _binary(op, a, b, flag)
+            if op == OP_ADD:
+                f = lambda p, q: p + q
+            elif op == OP_SUB:
+                f = lambda p, q: p + (-q)
+            elif op == OP_MUL:
+                f = lambda p, q: a * q + p * b
+            elif op == OP_DIV:
+                f = lambda p, q: (p + -(v * q)) / b
+            elif op == OP_MIN:
+                f = lambda p, q: np.where(b < a, q, p)
+            elif op == OP_MAX:
+                f = lambda p, q: np.where(b > a, q, p)
+            else:  # comparisons, AND, OR: piecewise constant
+                f = None
+            stack.append((v, list(none) if f is None else [rule((da[j], db[j]), f) for j in range(P)]))
+    return out_v, out_d
 
 
 class Expression:
@@ -279,19 +411,38 @@ class Expression:
     parse to equal trees).  Passing one as ``A`` lets the solver classes sample on the DEVICE: the points of the micro quadrature rule go
     once, three numbers per macro cell (its midpoint) after them, and a bytecode kernel forms the element means.
 
-    ``degree``: the quadrature degree of the expression, estimated from its tree by UFL's rules -- a literal, ``x[i]`` and ``pi`` 0;
-    ``y[i]`` 1; a sum or difference the larger; a product or quotient the sum; ``a**k`` k times; ``abs`` keeps; ``where`` / ``min`` /
-    ``max`` the larger of the values (not the condition); a math function 0 of an argument of degree 0, else the argument's + 2.  (UFL is
-    not installed where this is developed: the rules are recalled, not run.)  Several components: the largest.
+    ``degree``: the quadrature degree of the expression, estimated from its tree by UFL's rules -- a literal, ``x[i]``, ``p[k]`` and
+    ``pi`` 0; ``y[i]`` 1; a sum or difference the larger; a product or quotient the sum; ``a**k`` k times; ``abs`` keeps; ``where`` /
+    ``min`` / ``max`` the larger of the values (not the condition); a math function 0 of an argument of degree 0, else the argument's
+    + 2.  (UFL is not installed where this is developed: the rules are recalled, not run.)  Several components: the largest.
+
+    ``p=[...]``: the values of up to 4 parameters ``p[k]`` of the text, shared by all macro cells (a graded parameter is written
+    ``p[0] + p[1]*x[0]``), ``parameter_names`` their names (default ``"p0"``, ``"p1"``, ...).  They are the first ``n_params``
+    constants of the program, each in a slot of its own even when the text does not read it, and a subtree that reads one is never
+    folded.  ``with_parameters(p)`` changes the values without parsing again.  ``p_degree``: the degree of the tree in the parameters,
+    computed like ``degree`` -- ``p[k]`` 1; a literal, ``x``, ``y`` 0; ``+ - where min max`` the larger; ``*`` the sum; ``**k`` k times;
+    ``/`` by something without parameters keeps; a quotient by, a math function of, or ``abs`` / ``min`` / ``max`` of something that
+    reads a parameter: infinity.  ``affine_in_parameters``: ``p_degree <= 1``; the second derivatives along the parameter tangents
+    are then the whole Hessian.  A parameter inside a comparison logs one WARNING: the derivative ignores the motion of the interface
+    (it is zero almost everywhere); a smooth transition such as ``tanh`` is the way to differentiate a radius.
 
     The object is also a plain callable ``A(x, y)`` -- it interprets ``program()`` with NumPy --, so every generic path accepts it.
-    ``host_stream`` is the documented host equivalent of the device sampler: the same IEEE operations in the same order.
+    ``host_stream`` is the documented host equivalent of the device sampler, ``host_tangents`` of its forward-mode pass: the same IEEE
+    operations in the same order.
     """
 
-    def __init__(self, text=None, *, lam=None, mu=None):
+    def __init__(self, text=None, *, lam=None, mu=None, p=None, parameter_names=None):
         if (lam is None) != (mu is None) or (text is None) == (lam is None):
             raise ValueError("Expression(text), Expression([[a, b], [b, c]]) or Expression(lam=..., mu=...)")
         self.dim = None  # the d of a matrix
+        values = _parameter_values(p, None) if p is not None else np.zeros(0)
+        self.n_params = int(values.size)
+        if parameter_names is None:
+            parameter_names = tuple(f"p{k}" for k in range(self.n_params))
+        self.parameter_names = tuple(str(s) for s in parameter_names)
+        if len(self.parameter_names) != self.n_params:
+            raise ValueError(f"expression: {len(self.parameter_names)} parameter_names for {self.n_params} parameters")
+        ctx = _Context(self.n_params if p is not None else None)
         if lam is not None:
             self.shape, texts = "lame", [lam, mu]
         elif isinstance(text, (list, tuple)):
@@ -301,33 +452,53 @@ class Expression:
             self.shape, self.dim = "matrix", d
             pairs = [(0, 0), (1, 1), (0, 1)] if d == 2 else [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]  # the component order of the ABI
             for i, j in pairs:
-                if i != j and _parse(text[i][j]).key() != _parse(text[j][i]).key():
+                if i != j and _parse(text[i][j], _Context(ctx.n_params)).key() != _parse(text[j][i], _Context(ctx.n_params)).key():
                     raise ValueError(f"expression: the matrix must be symmetric; entries [{i}][{j}] and [{j}][{i}] differ")
             texts, self._pairs = [text[i][j] for i, j in pairs], pairs
         else:
             self.shape, texts = "scalar", [text]
         self.texts = tuple(str(t) for t in texts)
-        trees = [_parse(t) for t in texts]
+        trees = [_parse(t, ctx) for t in texts]
         self.n_comp = len(trees)
         self.degree = max(t.degree for t in trees)
-        ops, consts = [], []
+        self.p_degree = max(t.p_degree for t in trees)
+        self.affine_in_parameters = self.p_degree <= 1
+        ops, consts = [], [float(v) for v in values]
         for c, t in enumerate(trees):
-            _emit(t, ops, consts)
+            _emit(t, ops, consts, self.n_params)
             ops.append((OP_STORE, c))
         if len(ops) > MAX_OPS:
             raise ValueError(f"expression: too long: {len(ops)} instructions, at most {MAX_OPS}")
         if len(consts) > MAX_CONSTS:
-            raise ValueError(f"expression: too many constants: {len(consts)}, at most {MAX_CONSTS}")
+            raise ValueError(f"expression: too many constants: {len(consts)} (the parameters among them), at most {MAX_CONSTS}")
         deepest = max(stack_depths(ops))
         if deepest > MAX_STACK:
             raise ValueError(f"expression: too deep: stack depth {deepest}, at most {MAX_STACK}")
         self._ops = np.array(ops, dtype=np.uint8).reshape(-1, 2)
         self._consts = np.array(consts, dtype=np.float64)
         self.n_y = 1 + max([int(k) for op, k in ops if op == OP_Y], default=-1)  # fast-variable components the expression reads
+        if ctx.compared:
+            logging.getLogger(__name__).warning(
+                "expression: a parameter occurs inside a comparison (%s): the derivative with respect to it ignores the motion of the "
+                "interface (it is zero almost everywhere); use a smooth transition such as tanh to differentiate a radius",
+                "; ".join(dict.fromkeys(ctx.compared)))
+
+    @property
+    def p(self) -> np.ndarray:
+        """The values of the parameters (a copy)."""
+        return self._consts[:self.n_params].copy()
+
+    def with_parameters(self, p) -> "Expression":
+        """The same expression at other parameter values: the same ``ops``, only ``consts[:n_params]`` replaced -- nothing is parsed."""
+        values = _parameter_values(p, self.n_params)
+        other = copy.copy(self)
+        other._consts = self._consts.copy()
+        other._consts[:self.n_params] = values
+        return other
 
     def program(self) -> tuple[np.ndarray, np.ndarray]:
         """(ops[n_ops, 2] uint8 = (opcode, operand), consts[n_consts] float64): the postfix program of hommx_coef_program -- every
-        component's code followed by its ``STORE c``."""
+        component's code followed by its ``STORE c``.  The first ``n_params`` constants are the parameters."""
         return self._ops.copy(), self._consts.copy()
 
     def components(self, x, y) -> list:
@@ -364,3 +535,43 @@ class Expression:
             for c in range(self.n_comp):
                 acc[c] = acc[c] + w[q] * v[c]
         return acc[0] if self.n_comp == 1 else np.stack(acc, axis=-1)
+
+    def host_tangents(self, x: np.ndarray, yq: np.ndarray, w: np.ndarray) -> np.ndarray:
+        """The derivatives of ``host_stream`` with respect to the parameters, dirs[N, n_params, n_el(, n_comp)], exactly as the device's
+        forward-mode pass forms them (``_run_tangent``: the rules), ``acc_j = acc_j + w[q] * d_j`` with q ascending, from 0."""
+        if self.n_params == 0:
+            raise ValueError("the expression has no parameters (p=[...])")
+        x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+        n_el, nq, d = yq.shape
+        if self.n_y > d:
+            raise ValueError(f"the expression reads y[{self.n_y - 1}]; the fast variable has {d} components")
+        P, shape = self.n_params, (x.shape[0], n_el)
+        acc = [[np.zeros(shape) for _ in range(self.n_comp)] for _ in range(P)]
+        ops = self._ops.tolist()
+        for q in range(nq):
+            with np.errstate(all="ignore"):
+                _, dv = _run_tangent(ops, self._consts, self.n_comp, P, x.T[:, :, None], np.moveaxis(yq[:, q, :], -1, 0)[:, None, :])
+            for j in range(P):
+                for c in range(self.n_comp):
+                    dj = np.float64(0.0) if dv[c][j] is None else dv[c][j]
+                    acc[j][c] = acc[j][c] + w[q] * np.broadcast_to(dj, shape)
+        out = np.stack([np.stack(a, axis=-1) for a in acc], axis=1)  # [N, P, n_el, n_comp]
+        return out[..., 0] if self.n_comp == 1 else out
+
+
+def _parameter_values(p, n_params: int | None) -> np.ndarray:
+    """p as float64[n_params] (``n_params`` None: whatever its length, up to MAX_PARAMS), every value finite."""
+    try:
+        values = np.array(p, dtype=np.float64).reshape(-1) if np.ndim(p) <= 1 else None
+    except (TypeError, ValueError):
+        values = None
+    if values is None:
+        raise ValueError(f"expression: p must be a sequence of numbers; got {p!r}")
+    if values.size > MAX_PARAMS:
+        raise ValueError(f"expression: at most {MAX_PARAMS} parameters; got {values.size}")
+    if n_params is not None and values.size != n_params:
+        raise ValueError(f"expression: the expression has {n_params} parameters; got {values.size} values")
+    for k, v in enumerate(values):
+        if not np.isfinite(v):
+            raise ValueError(f"expression: parameter p[{k}] is not finite: {v}")
+    return values

@@ -308,6 +308,15 @@ class BaseHMM(ABC):
         """hmm.py:289-296."""
         self._f = f
 
+    def set_parameters(self, p):
+        """New values of the parameters ``p[k]`` of an ``Expression`` coefficient (``Expression.with_parameters``: nothing is parsed
+        again).  The macro matrix is reassembled by the next ``solve()``; the plan and its workspace are kept -- the step of a
+        calibration loop.  ``ValueError`` when the coefficient is no ``Expression`` with parameters, or ``p`` has another length."""
+        if not isinstance(self._coeff, Expression) or self._coeff.n_params == 0:
+            raise ValueError("set_parameters() needs an Expression coefficient with parameters (Expression(..., p=[...]))")
+        self._coeff = self._coeff.with_parameters(p)
+        self._needs_reassembly = True
+
     def set_polarisation(self, P):
         """A prescribed micro flux / stress field P(x, y): a thermal eigenstress -A : alpha dT, a prestress, the gravity
         term of Darcy flow.  The micro total flux becomes A (grad / eps of the reconstruction) + P, and ``solve()`` adds the load
@@ -626,7 +635,7 @@ class BaseHMM(ABC):
             return CoefStream.two_phase(mask, values), kind
         yq, w = self._quadrature_points()
         if form == "solve_program":
-            return CoefStream.program(yq, w, *co.program(), co.n_comp, c), kind
+            return CoefStream.program(yq, w, *co.program(), co.n_comp, c, n_params=co.n_params), kind
         return CoefStream.separable(co.family, co.table(yq, w), w, co.params(c)), kind
 
     def _phase_mask(self) -> np.ndarray:
@@ -930,7 +939,10 @@ class BaseHMM(ABC):
 
         Without ``directions`` the derivatives are those with respect to the parameters of the coefficient: the outside and the inside
         value of a ``TwoPhase`` coefficient, a and b of an affine ``Separable`` one, of every component (lambda and mu for the elasticity
-        classes).  Any other coefficient raises ``ValueError``: its element stream is not linear in a few parameters.
+        classes), and the named parameters ``p[k]`` of an ``Expression`` (``Expression(..., p=[...], parameter_names=...)``): the
+        program is differentiated on the device in forward mode, in the pass that samples it, so nothing is sampled on the host and no
+        direction stream crosses the boundary.  Any other coefficient raises ``ValueError``: its element stream is not linear in a few
+        parameters.
         ``directions=[dA_0, ...]``: callables (x, y) of the coefficient's shape, up to 8; each is sampled exactly as the coefficient is
         (the same quadrature degree and packing) and dA[:, k] is the derivative of A_H along it.
 
@@ -948,13 +960,24 @@ class BaseHMM(ABC):
         cells = self._local_cells() if cells is None else np.asarray(cells, dtype=np.int64).ravel()
         if len(cells) == 0:
             raise ValueError(f"{what}() needs at least one macro cell")
-        if directions is None:
+        co = self._coeff
+        if directions is None and isinstance(co, Expression) and co.n_params and self._device_form() == "solve_program" \
+                and hasattr(self._ensure_plan(self._micro_kind()), "solve_program"):
+            # the parameter tangents of the program, formed on the device with the stream: nothing is sampled, no direction stream is sent
+            if what == "tensor_second_derivatives" and not co.affine_in_parameters:
+                raise ValueError(
+                    f"the expression is not affine in its parameters (p_degree {co.p_degree}): the Hessian of A_H also needs dA_H along "
+                    "d2A/dp_a dp_b, which second-order tangents would give and this library does not form.  directions=[...] with your own "
+                    "streams remains available: the second derivatives along them, and tensor_derivatives(directions=[d2A/dp_a dp_b, ...]) "
+                    "for the curvature term")
+            names, shared = co.parameter_names, "parameters"
+        elif directions is None:
             names, shared = self._parameter_directions()
         else:
             directions = list(directions)
             names, shared = tuple(getattr(f, "__name__", f"direction{k}") for k, f in enumerate(directions)), None
         if chunk_cells is None:
-            streams = 1 + (len(directions) if shared is None else 0)
+            streams = 1 + (len(directions) if shared is None else 0)  # the parameter tangents never cross the boundary
             chunk_cells = (256 << 20) // (8 * self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) * streams)
         ch = max(1, int(chunk_cells))
         parts = []
@@ -1001,7 +1024,9 @@ class BaseHMM(ABC):
         first derivatives ``dA[N, n_dirs, t, t]`` of the same call, ``A_eff``, ``info`` and ``cells``.
 
         Names and directions are those of ``tensor_derivatives``: without ``directions`` the parameters of a ``TwoPhase`` or an affine
-        ``Separable`` coefficient (any other coefficient raises ``ValueError``), else up to 8 callables (x, y) of the coefficient's shape.
+        ``Separable`` coefficient or of an ``Expression`` that is affine in its parameters (``affine_in_parameters``: the curvature term
+        vanishes and d2A is the exact Hessian; one that is not raises ``ValueError``, as any other coefficient does), else up to 8
+        callables (x, y) of the coefficient's shape.
         d2A[:, a, b] is exact on the discrete problem -- the Hessian of A_H a Newton or Gauss-Newton step needs, with no step size to
         tune -- and costs one load solve per direction, on every micro mesh.  The cells run in chunks of ``chunk_cells``.  Under a process
         group this runs on the calling rank alone: there is no collective."""

@@ -299,10 +299,18 @@ int hommx_reconstruct_batch_device(hommx_plan* plan, int64_t n_cells, const doub
  * Validation (HOMMX_EINVAL with a text naming the fault, on the host, before the plan's device is made current): a null program, ops
  * or consts, n_q < 1, null table / weights / params; n_ops outside 1 .. 128, n_consts outside 0 .. 32; n_comp other than the plan's;
  * a plan of the HOMMX_KIND_ELASTICITY_VOIGT kind (21 components: not supported); an unknown opcode; a CONST, X or Y index out of range;
- * stack underflow; stack depth above 16; a component stored twice or never; values left on the stack at the end.
+ * stack underflow; stack depth above 16; a component stored twice or never; values left on the stack at the end; n_params outside
+ * 0 .. HOMMX_PROGRAM_MAX_PARAMS or above n_consts.
+ *
+ * Parameters: the first n_params constants are the parameters p[0 .. n_params-1] of the expression, shared by all macro cells.  For
+ * the solve, expand, reconstruct and loads entries they are constants like the others, and n_params == 0 is a program without
+ * parameters on every path.  hommx_expand_tangents differentiates the program with respect to them, and HOMMX_DIRS_PARAMETERS makes
+ * those derivatives the directions of the derivative entries.
  */
+#define HOMMX_PROGRAM_MAX_PARAMS 4
 typedef struct hommx_coef_program {
-  int32_t n_ops, n_consts, n_comp, reserved;
+  int32_t n_ops, n_consts, n_comp;
+  int32_t n_params;      /* 0 .. HOMMX_PROGRAM_MAX_PARAMS, <= n_consts (this member was `reserved`, 0) */
   const uint8_t* ops;    /* [n_ops][2]: opcode, operand */
   const double* consts;  /* [n_consts]                  */
 } hommx_coef_program;
@@ -335,6 +343,31 @@ int hommx_expand_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_sour
 /* Same with DEVICE pointers (in *src as well), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
 int hommx_expand_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, double* d_coef_out, void* stream);
 
+/*
+ * The derivatives of the element stream of a HOMMX_COEF_PROGRAM source with respect to its parameters, in forward mode: ONE pass of
+ * the interpreter (csrc/coef_program.hip, k_expand_program_tangent) carries (v, d_0 .. d_{P-1}) per stack entry and yields
+ *   coef_out [n_cells][n_el][n_comp]             the stream of hommx_expand_source, bit for bit (or NULL: not wanted)
+ *   dirs_out [n_cells][n_params][n_el][n_comp]   d coef / d p[j], the layout of per-cell directions (hommx_sens_args, per_cell == 1)
+ * Every arithmetic step is one separately rounded IEEE-754 operation in the written order, no contraction; hommx_amd.expr.Expression
+ * .host_tangents applies the same rules in the same order with NumPy.  For parameter j, if every operand's d_j is 0.0 the result's d_j
+ * is +0.0 and the formula is not evaluated: a sqrt(0) or a division by zero in a part of the expression that does not depend on p[j]
+ * cannot make its tangent NaN.  Otherwise, for operands (a, da), (b, db), b on top, and the instruction's own value v:
+ *   CONST k   d_j = (k == j && k < n_params) ? 1 : 0           X, Y   d_j = 0           DUP   copies
+ *   ADD  da + db         SUB  da + (-db)         NEG  -da
+ *   MUL  add(mul(a, db), mul(da, b))             DIV  div(add(da, -mul(v, db)), b),  v = a / b
+ *   ABS  a < 0 ? -da : da          MIN / MAX / SELECT  the tangent of the operand the value rule picks
+ *   LT .. GE, AND, OR, NOT  0      (a parameter inside a comparison moves an interface: its derivative is zero almost everywhere)
+ *   SQRT div(da, mul(2, v))        SIN  mul(cos(a), da)        COS  -mul(sin(a), da)        TAN  mul(da, add(1, mul(v, v)))
+ *   EXP  mul(v, da)                LOG  div(da, a)             TANH mul(da, add(1, -mul(v, v)))
+ *   STORE c   acc[c] = add(acc[c], mul(w, v));  accd[c][j] = add(accd[c][j], mul(w, d_j)),  q ascending, from 0
+ * Validation: that of hommx_expand_source, and HOMMX_EINVAL with a text for a source of another form, n_params == 0, a null dirs_out.
+ * The host entry stages the source as hommx_expand_source does and returns chunk by chunk (at most 1 GiB of the 1 + n_params streams).
+ */
+int hommx_expand_tangents(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, double* coef_out, double* dirs_out);
+/* Same with DEVICE pointers (in *src as well), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
+int hommx_expand_tangents_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, double* d_coef_out, double* d_dirs_out,
+                                 void* stream);
+
 #define HOMMX_RECON_MAX_REGIONS 8
 #define HOMMX_RECON_NREGION(t) (2 * (t) + 4) /* [volume | sum strain(t) | sum flux(t) | energy | max_flux | argmax_element] */
 int hommx_reconstruct_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const double* xi,
@@ -358,7 +391,11 @@ int hommx_reconstruct_source_device(hommx_plan* plan, int64_t n_cells, const hom
  * so that sum_{K,q} grad[c][K][q] dir[K][q] = sum_{m,n} w[c][m][n] dA[dir][c][m][n].
  *
  *   n_dirs      0 .. HOMMX_SENS_MAX_DIRS direction streams, each shaped like one cell's coefficient [n_el][n_comp]
- *   per_cell    0: dirs[n_dirs][n_el][n_comp], shared by all cells; 1: dirs[n_cells][n_dirs][n_el][n_comp]
+ *   per_cell    0: dirs[n_dirs][n_el][n_comp], shared by all cells; 1: dirs[n_cells][n_dirs][n_el][n_comp];
+ *               HOMMX_DIRS_PARAMETERS: the directions are the derivatives of the source's program with respect to its parameters
+ *               (hommx_expand_tangents), formed on the device chunk by chunk in the launch that expands the stream, into plan-owned
+ *               scratch whose bytes the chunk rule counts: dirs == NULL, n_dirs == the program's n_params, dA as with per_cell == 1.
+ *               HOMMX_EINVAL with a text for a source that is no HOMMX_COEF_PROGRAM, n_params == 0, another n_dirs, a non-null dirs
  *   dA          [n_cells][n_dirs][t][t] (symmetric, bitwise); required with n_dirs > 0, as dirs
  *   weights     [n_cells][t][t] and grad [n_cells][n_el][n_comp] (the shape of coef): both or neither
  *   A_eff, info as hommx_solve_batch, or NULL
@@ -371,6 +408,7 @@ int hommx_reconstruct_source_device(hommx_plan* plan, int64_t n_cells, const hom
  * every output comes back, chunk by chunk.
  */
 #define HOMMX_SENS_MAX_DIRS 8
+#define HOMMX_DIRS_PARAMETERS 2 /* a value of per_cell in hommx_sens_args and hommx_sens2_args */
 typedef struct hommx_sens_args {
   int32_t n_dirs;
   int32_t per_cell;
@@ -494,7 +532,11 @@ int hommx_loads_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coe
  * columns of its corrector arena, every other plan runs one more corrector pass of the blocked family) against the 2 n_dirs + 1 eliminations of central differences of hommx_sensitivity_source.
  *
  *   n_dirs      1 .. HOMMX_SENS_MAX_DIRS
- *   per_cell    0: dirs[n_dirs][n_el][n_comp], shared by all cells; 1: dirs[n_cells][n_dirs][n_el][n_comp]
+ *   per_cell    0: dirs[n_dirs][n_el][n_comp], shared by all cells; 1: dirs[n_cells][n_dirs][n_el][n_comp];
+ *               HOMMX_DIRS_PARAMETERS: the parameter tangents of the source's program, as in hommx_sens_args (dirs == NULL, n_dirs ==
+ *               n_params).  d2A then holds the second derivatives ALONG THE TANGENT DIRECTIONS.  For a program that is affine in its
+ *               parameters that is the Hessian of A_H with respect to them; for any other the Hessian also needs dA_H along
+ *               d2 coef / dp_a dp_b, a first derivative along directions the library does not form: that term is the caller's
  *   d2A         [n_cells][n_dirs][n_dirs][t][t], required
  *   dA          [n_cells][n_dirs][t][t] or NULL: the first derivatives along the same directions, the bits hommx_sensitivity_source returns
  *   A_eff, info as hommx_solve_batch, or NULL
