@@ -29,6 +29,7 @@ PROGRAM_MAX_OPS, PROGRAM_MAX_CONSTS, PROGRAM_MAX_STACK = 128, 32, 16  # the limi
 RECON_MAX_REGIONS = 8  # HOMMX_RECON_MAX_REGIONS
 SENS_MAX_DIRS = 8  # HOMMX_SENS_MAX_DIRS
 PROGRAM_MAX_PARAMS = 4  # HOMMX_PROGRAM_MAX_PARAMS
+PROGRAM_MAX_FIELDS = 4  # HOMMX_PROGRAM_MAX_FIELDS
 DIRS_PARAMETERS = 2  # HOMMX_DIRS_PARAMETERS: per_cell of SensArgs / Sens2Args, the directions are the program's parameter tangents
 
 
@@ -71,14 +72,22 @@ class CoefProgram(C.Structure):
     ]
 
 
-class CoefSource(C.Structure):
-    """hommx_coef_source: only the pointers of ``form`` are read."""
+class _SourceFields(C.Union):
+    """The member of hommx_coef_source that was ``reserved`` (0) and is ``n_fields`` now: both names, one word."""
 
+    _fields_ = [("n_fields", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CoefSource(C.Structure):
+    """hommx_coef_source: only the pointers of ``form`` are read; ``n_fields`` (HOMMX_COEF_PROGRAM: fields per macro cell after the
+    midpoint in ``params``, 0 .. PROGRAM_MAX_FIELDS) for that form only."""
+
+    _anonymous_ = ("_fields_word",)
     _fields_ = [
         ("form", C.c_int32),
         ("family", C.c_int32),
         ("n_q", C.c_int32),
-        ("reserved", C.c_int32),
+        ("_fields_word", _SourceFields),
         ("coef", C.c_void_p),
         ("mask", C.c_void_p),
         ("values", C.c_void_p),

@@ -236,12 +236,15 @@ def _per_cell_code(per_cell) -> int:
 class Program:
     """The postfix program of an expression coefficient (include/hommx_hip.h, hommx_coef_program; ``hommx_amd.expr.Expression.program``):
     ops[n_ops, 2] uint8 = (opcode, operand), consts[n_consts] float64, the number of components it stores, and how many of its first
-    constants are parameters (``Expression(..., p=[...])``)."""
+    constants are parameters (``Expression(..., p=[...])``).  ``n_fields``: how many per-cell fields it reads
+    (``Expression(..., fields=...)``; ``X k``, k >= 3) -- no member of hommx_coef_program: it travels in the source
+    (hommx_coef_source.n_fields), with the rows [N_c, 3 + n_fields] it describes."""
 
     ops: np.ndarray
     consts: np.ndarray
     n_comp: int
     n_params: int = 0
+    n_fields: int = 0
 
     def struct(self) -> "_lib.CoefProgram":
         """The hommx_coef_program that points into this program's arrays (host memory; keep ``self`` alive while it is in use)."""
@@ -275,12 +278,12 @@ class CoefStream:
                    np.ascontiguousarray(params, dtype=np.float64))
 
     @classmethod
-    def program(cls, points, weights, ops, consts, n_comp: int, midpoints, *, n_params: int = 0) -> "CoefStream":
+    def program(cls, points, weights, ops, consts, n_comp: int, midpoints, *, n_params: int = 0, n_fields: int = 0) -> "CoefStream":
         """An expression coefficient: points[n_el, n_q, dim] and weights[n_q] of the micro quadrature rule, the program of
-        ``Expression.program()`` with its number of components, midpoints[N_c, 3] of the macro cells; ``n_params``: how many of the
-        first constants are the expression's parameters."""
+        ``Expression.program()`` with its number of components, midpoints[N_c, 3 + n_fields] of the macro cells -- the midpoint, then
+        the ``n_fields`` fields of the cell; ``n_params``: how many of the first constants are the expression's parameters."""
         prog = Program(np.ascontiguousarray(ops, dtype=np.uint8).reshape(-1, 2), np.ascontiguousarray(consts, dtype=np.float64).ravel(), int(n_comp),
-                       int(n_params))
+                       int(n_params), int(n_fields))
         return cls("solve_program", (np.ascontiguousarray(points, dtype=np.float64), np.ascontiguousarray(weights, dtype=np.float64), prog),
                    np.ascontiguousarray(midpoints, dtype=np.float64))
 
@@ -298,7 +301,7 @@ class CoefStream:
             src.form, src.mask, src.values = _lib.COEF_TWO_PHASE, address(self.shared[0]), address(self.per_cell)
         elif self.method == "solve_program":
             points, weights, prog = self.shared
-            src.form, src.n_q = _lib.COEF_PROGRAM, int(points.shape[1])
+            src.form, src.n_q, src.n_fields = _lib.COEF_PROGRAM, int(points.shape[1]), int(prog.n_fields)
             src.table, src.weights, src.params = address(points), address(weights), address(self.per_cell)
             src._program = (prog, prog.struct())  # ctypes keeps no reference to what a pointer member points at
             src.program = C.pointer(src._program[1])
@@ -459,11 +462,12 @@ class MicroCellPlan:
 
     @staticmethod
     def _parameter_count(coef) -> int:
-        """n_params of ``directions="parameters"``: the coefficient must be a program ``CoefStream`` with parameters."""
+        """The differentiable slots of ``directions="parameters"``, n_params + n_fields: the coefficient must be a program ``CoefStream``
+        with parameters or fields."""
         prog = coef.shared[2] if isinstance(coef, CoefStream) and coef.method == "solve_program" else None
-        if prog is None or prog.n_params < 1:
+        if prog is None or prog.n_params + prog.n_fields < 1:
             raise ValueError('directions="parameters" needs the CoefStream of an expression with parameters (CoefStream.program(..., n_params=...))')
-        return int(prog.n_params)
+        return int(prog.n_params + prog.n_fields)
 
     def _check_weights(self, weights, nc: int) -> np.ndarray:
         """weights[N_c, t, t] as float64."""
@@ -505,8 +509,9 @@ class MicroCellPlan:
                 raise ValueError(f"points has shape {points.shape}; expected ({self.n_el}, n_q, {self.dim})")
             if weights.shape != (points.shape[1],):
                 raise ValueError(f"weights must have shape ({points.shape[1]},)")
-            if stream.per_cell.shape != (nc, 3):
-                raise ValueError(f"midpoints has shape {stream.per_cell.shape}; expected ({nc}, 3)")
+            if stream.per_cell.shape != (nc, 3 + prog.n_fields):
+                raise ValueError(f"midpoints has shape {stream.per_cell.shape}; expected ({nc}, 3" + (
+                    f" + {prog.n_fields}): the midpoint, then the fields" if prog.n_fields else ")"))
             if prog.n_comp != self.n_comp:
                 raise ValueError(f"the expression has {prog.n_comp} components; the plan's coefficient has {self.n_comp}")
             return nc
@@ -712,7 +717,7 @@ class MicroCellPlan:
     def solve_program(self, points: np.ndarray, weights: np.ndarray, program: Program, midpoints: np.ndarray, M: np.ndarray | None = None,
                       return_info: bool = False):
         """Expression coefficient sampled on the device (include/hommx_hip.h, HOMMX_COEF_PROGRAM): points[n_el, n_q, dim] and
-        weights[n_q] of the micro quadrature rule, the program, midpoints[N_c, 3] of the macro cells -> A_eff[N_c, t, t]."""
+        weights[n_q] of the micro quadrature rule, the program, midpoints[N_c, 3 + program.n_fields] of the macro cells -> A_eff[N_c, t, t]."""
         stream = CoefStream("solve_program", (np.ascontiguousarray(points, dtype=np.float64), np.ascontiguousarray(weights, dtype=np.float64), program),
                             np.ascontiguousarray(midpoints, dtype=np.float64))
         nc = self._check_stream(stream)
@@ -731,8 +736,9 @@ class MicroCellPlan:
         return out
 
     def expand_tangents(self, stream: CoefStream) -> tuple[np.ndarray, np.ndarray]:
-        """(coef[N_c, n_el(, n_comp)], dirs[N_c, n_params, n_el(, n_comp)]) of the program stream of an expression with parameters
-        (hommx_expand_tangents): the stream of ``expand``, bit for bit, and its derivatives with respect to the parameters, formed in one
+        """(coef[N_c, n_el(, n_comp)], dirs[N_c, n_params + n_fields, n_el(, n_comp)]) of the program stream of an expression with
+        parameters or fields (hommx_expand_tangents): the stream of ``expand``, bit for bit, and its derivatives with respect to the
+        parameters, then the fields (of a cell: its own value), formed in one
         forward-mode pass on the device.  dirs equals ``Expression.host_tangents`` bit for bit for exactly rounded operations."""
         n_params = self._parameter_count(stream)
         nc = self._check_stream(stream)
@@ -766,8 +772,8 @@ class MicroCellPlan:
                              M_ptr: int | None, out_ptr: int, info_ptr: int | None, stream: int | None = None):
         """Device twin of ``solve_program``: the points, weights and midpoints are device pointers, the program stays host memory."""
         prog = program.struct()
-        src = _lib.CoefSource(form=_lib.COEF_PROGRAM, n_q=int(n_q), table=points_ptr, weights=weights_ptr, params=midpoints_ptr,
-                              program=C.pointer(prog))
+        src = _lib.CoefSource(form=_lib.COEF_PROGRAM, n_q=int(n_q), n_fields=int(program.n_fields), table=points_ptr, weights=weights_ptr,
+                              params=midpoints_ptr, program=C.pointer(prog))
         self.solve_source_device(n_cells, src, M_ptr, out_ptr, info_ptr, stream)
 
     def reconstruct_device(self, n_cells: int, coef_ptr: int, M_ptr: int | None, xi_ptr: int, stats_ptr: int, strain_ptr: int | None = None,

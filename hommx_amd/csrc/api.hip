@@ -110,7 +110,8 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 // B_LOADS: what a load pass leaves where a corrector pass leaves A_eff (hommx_loads_source: C0 - f^T K^+ f, unused)
 // B_REFINE: canonical flux field and correction of the refinement step of a fused 2D plan's correctors (10 n^2 doubles per cell)
 // B_SENS2: the polarisation loads of one direction of a second-derivative chunk (t n_el t doubles per cell)
-// B_TANGENT: the parameter tangents of one chunk of a program source, [nc][n_params][n_el][n_comp] (grown with B_EXPAND, by stream_chunk)
+// B_TANGENT: the tangents of one chunk of a program source, one stream per differentiable slot (its parameters, then its fields):
+//            [nc][n_params + n_fields][n_el][n_comp] (grown with B_EXPAND, by stream_chunk)
 enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, B_SENS2, B_TANGENT, N_BUF };
 
 }  // namespace
@@ -260,22 +261,23 @@ hommx_coef_source separable_source(int32_t family, int32_t n_q, const double* ta
   return s;
 }
 hommx_coef_source program_source(const hommx_coef_program* program, int32_t n_q, const double* points, const double* weights,
-                                 const double* midpoints) {
+                                 const double* rows, int32_t n_fields) {
   hommx_coef_source s{};
   s.form = HOMMX_COEF_PROGRAM;
   s.n_q = n_q;
+  s.n_fields = n_fields;
   s.table = points;
   s.weights = weights;
-  s.params = midpoints;
+  s.params = rows;
   s.program = program;
   return s;
 }
 // a caller's source that coef_check has passed (the pointers of other forms are not the caller's to set; `program`, the member a
-// caller built against the shorter struct does not have, is read for its own form only)
+// caller built against the shorter struct does not have, and `n_fields`, which was `reserved`, are read for their own form only)
 hommx_coef_source source_of_form(const hommx_coef_source& s) {
   if (s.form == HOMMX_COEF_SAMPLED) return sampled_source(s.coef);
   if (s.form == HOMMX_COEF_TWO_PHASE) return two_phase_source(s.mask, s.values);
-  if (s.form == HOMMX_COEF_PROGRAM) return program_source(s.program, s.n_q, s.table, s.weights, s.params);
+  if (s.form == HOMMX_COEF_PROGRAM) return program_source(s.program, s.n_q, s.table, s.weights, s.params, s.n_fields);
   return separable_source(s.family, s.n_q, s.table, s.weights, s.params);
 }
 
@@ -293,6 +295,9 @@ int program_check(const hommx_plan* p, const hommx_coef_source* s) {
     return fail(HOMMX_EINVAL, "program: n_params must be 0 .. %d, got %d", hommx::PROGRAM_MAX_PARAMS, g->n_params);
   if (g->n_params > g->n_consts)
     return fail(HOMMX_EINVAL, "program: n_params is %d, above n_consts (%d): the parameters are the first constants", g->n_params, g->n_consts);
+  if (s->n_fields < 0 || s->n_fields > hommx::PROGRAM_MAX_FIELDS)
+    return fail(HOMMX_EINVAL, "program source: n_fields must be 0 .. %d, got %d", hommx::PROGRAM_MAX_FIELDS, s->n_fields);
+  const int n_row = hommx::program_row_doubles(s->n_fields);
   const int n_comp = hommx::kind_sizes(p->desc.dim, p->desc.kind).n_comp;
   if (g->n_comp != n_comp) return fail(HOMMX_EINVAL, "program: n_comp is %d, the plan's coefficient has %d components", g->n_comp, n_comp);
   if (!g->ops || (g->n_consts > 0 && !g->consts)) return fail(HOMMX_EINVAL, "null program ops / consts");
@@ -305,7 +310,10 @@ int program_check(const hommx_plan* p, const hommx_coef_source* s) {
     if (op >= hommx::OP_COUNT) return fail(HOMMX_EINVAL, "program: unknown opcode %d at instruction %d", op, pc);
     if (op == hommx::OP_CONST && k >= g->n_consts)
       return fail(HOMMX_EINVAL, "program: constant index %d out of range [0,%d) at instruction %d", k, g->n_consts, pc);
-    if (op == hommx::OP_X && k >= 3) return fail(HOMMX_EINVAL, "program: x index %d out of range [0,3) at instruction %d", k, pc);
+    if (op == hommx::OP_X && k >= n_row) {
+      if (s->n_fields == 0) return fail(HOMMX_EINVAL, "program: x index %d out of range [0,3) at instruction %d", k, pc);
+      return fail(HOMMX_EINVAL, "program: x index %d out of range [0,%d) (the midpoint and %d fields) at instruction %d", k, n_row, s->n_fields, pc);
+    }
     if (op == hommx::OP_Y && k >= p->desc.dim)
       return fail(HOMMX_EINVAL, "program: y index %d out of range [0,%d) at instruction %d", k, p->desc.dim, pc);
     if (depth < hommx::op_pops(op)) return fail(HOMMX_EINVAL, "program: stack underflow at instruction %d", pc);
@@ -375,8 +383,14 @@ hommx::ProgramArgs program_args(const hommx_coef_program& g) {
   return a;
 }
 
-// doubles per cell of the per-cell array of a sampler form (per_cell), and entries of its table
-int64_t per_cell_doubles(const hommx_plan* p, const hommx_coef_source& s) { return s.form == HOMMX_COEF_PROGRAM ? 3 : 2 * p->ks.n_comp; }
+// doubles per cell of the per-cell array of a sampler form (per_cell), and entries of its table.  A program's row is the midpoint and
+// the fields of the cell (coef_program.h, program_row_doubles: nothing else knows its width); program_rows: the rows from cell c0 on
+int64_t per_cell_doubles(const hommx_plan* p, const hommx_coef_source& s) {
+  return s.form == HOMMX_COEF_PROGRAM ? hommx::program_row_doubles(s.n_fields) : 2 * p->ks.n_comp;
+}
+const double* program_rows(const hommx_coef_source& s, int64_t c0) { return s.params + c0 * hommx::program_row_doubles(s.n_fields); }
+// the differentiable slots of a checked program source: its parameters, then its fields
+int source_tangents(const hommx_coef_source& s) { return s.program->n_params + s.n_fields; }
 int64_t table_doubles(const hommx_plan* p, const hommx_coef_source& s) {
   return p->n_el * s.n_q * (s.form == HOMMX_COEF_PROGRAM ? p->desc.dim : 1);
 }
@@ -399,8 +413,8 @@ int stream_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t want, int64_
 
 // the stream of cells [c0, c0 + nc) of a program source (into `coef`; null: not wanted) and its parameter tangents, in one launch
 int expand_tangents_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t c0, int64_t nc, hipStream_t st, double* coef, double* tangents) {
-  HIP_TRY(hommx::launch_expand_program_tangent(program_args(*s.program), s.program->n_params, s.table, s.weights, s.n_q, p->desc.dim,
-                                               s.params + c0 * 3, coef, tangents, p->n_el, nc, st));
+  HIP_TRY(hommx::launch_expand_program_tangent(program_args(*s.program), s.program->n_params, s.n_fields, s.table, s.weights, s.n_q,
+                                               p->desc.dim, program_rows(s, c0), coef, tangents, p->n_el, nc, st));
   return HOMMX_OK;
 }
 
@@ -420,8 +434,8 @@ int expand_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t c0, int64_t 
   } else if (s.form == HOMMX_COEF_TWO_PHASE)
     HIP_TRY(hommx::launch_expand_two_phase(s.mask, s.values + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st));
   else if (s.form == HOMMX_COEF_PROGRAM)
-    HIP_TRY(hommx::launch_expand_program(program_args(*s.program), s.table, s.weights, s.n_q, p->desc.dim, s.params + c0 * 3, dst, p->n_el,
-                                         nc, st));
+    HIP_TRY(hommx::launch_expand_program(program_args(*s.program), s.table, s.weights, s.n_q, p->desc.dim, program_rows(s, c0), s.n_fields,
+                                         dst, p->n_el, nc, st));
   else
     HIP_TRY(hommx::launch_expand_separable(sampler_source(s), s.params + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st));
   *stream = dst;
@@ -824,12 +838,20 @@ int hommx_expand_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source*
 }  // extern "C"
 
 namespace {
+// the differentiable slots of a checked program source, 1 .. HOMMX_PROGRAM_MAX_PARAMS of them: its parameters, then its fields
+int tangent_slots_check(const hommx_coef_source* s, const char* who) {
+  const int n_params = s->program->n_params, n_fields = s->n_fields;
+  if (n_params + n_fields == 0) return fail(HOMMX_EINVAL, "%s: the program has no parameters (n_params == 0)", who);
+  if (n_params + n_fields > HOMMX_PROGRAM_MAX_PARAMS)
+    return fail(HOMMX_EINVAL, "%s: at most %d differentiable slots, got n_params (%d) + n_fields (%d) = %d", who, HOMMX_PROGRAM_MAX_PARAMS,
+                n_params, n_fields, n_params + n_fields);
+  return HOMMX_OK;
+}
 // what hommx_expand_tangents[_device] check of the source beyond coef_check
 int tangents_check(const hommx_plan* p, const hommx_coef_source* src) {
   if (int rc = coef_check(p, src)) return rc;
   if (src->form != HOMMX_COEF_PROGRAM) return fail(HOMMX_EINVAL, "parameter tangents need a HOMMX_COEF_PROGRAM source, got form %d", src->form);
-  if (src->program->n_params < 1) return fail(HOMMX_EINVAL, "parameter tangents: the program has no parameters (n_params == 0)");
-  return HOMMX_OK;
+  return tangent_slots_check(src, "parameter tangents");
 }
 }  // namespace
 
@@ -839,7 +861,7 @@ int hommx_expand_tangents_device(hommx_plan* p, int64_t n_cells, const hommx_coe
                                  void* stream) {
   if (int rc = open_call(p, n_cells, d_dirs_out, "dirs_out", true, [&] { return tangents_check(p, src); }); rc != GO) return rc;
   const hommx_coef_source s = source_of_form(*src);
-  const int n_tan = s.program->n_params;
+  const int n_tan = source_tangents(s);
   const int64_t per = p->n_el * p->ks.n_comp;
   const int64_t chunk = stream_cells(p, n_cells, n_tan);  // straight into the caller's arrays, in launches of at most 1 GiB of streams
   for (int64_t c0 = 0; c0 < n_cells; c0 += chunk)
@@ -852,7 +874,7 @@ int hommx_expand_tangents_device(hommx_plan* p, int64_t n_cells, const hommx_coe
 int hommx_expand_tangents(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, double* coef_out, double* dirs_out) {
   if (int rc = open_call(p, n_cells, dirs_out, "dirs_out", false, [&] { return tangents_check(p, src); }); rc != GO) return rc;
   const hommx_coef_source s = source_of_form(*src);
-  const int n_tan = s.program->n_params;
+  const int n_tan = source_tangents(s);
   const int64_t per = p->n_el * p->ks.n_comp;
   hommx_coef_source ds;
   const void* none = nullptr;
@@ -997,12 +1019,12 @@ using ChunkRule = int64_t (*)(const hommx_plan*, int64_t, size_t);  // recon_chu
 // once, in the plan's pinned block (stage_source); the other inputs stream into B_IN and the outputs the caller asked for stream out of
 // B_OUT chunk by chunk, so device memory is bounded by the chunk, whose bytes per cell count both blocks.
 // tangents (HOMMX_DIRS_PARAMETERS): a pointer member of v.a that receives, per chunk, the parameter tangents of the program source --
-// [nc][n_params][n_el][n_comp] in B_TANGENT, formed by the launch that expands the stream; their bytes count as scratch of the chunk
+// [nc][n_params + n_fields][n_el][n_comp] in B_TANGENT, formed by the launch that expands the stream; their bytes count as scratch of the chunk
 template <typename Args, size_t NI, size_t NO, typename Run>
 int derived_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, Chunk<Args>& v, const CellArray (&ins)[NI],
                  const CellArray (&outs)[NO], int32_t** info, size_t scratch, ChunkRule rule, bool device, hipStream_t st, Run run,
                  const double** tangents = nullptr) {
-  const int n_tan = tangents ? s.program->n_params : 0;
+  const int n_tan = tangents ? source_tangents(s) : 0;
   scratch += sizeof(double) * n_tan * p->n_el * p->ks.n_comp;
   constexpr size_t N[2] = {NI + 2, NO + 1};
   constexpr size_t NMAX = std::max(N[0], N[1]);
@@ -1181,9 +1203,12 @@ int sens_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_sens_ar
 bool parameter_dirs(int32_t per_cell) { return per_cell == HOMMX_DIRS_PARAMETERS; }
 int parameter_dirs_check(const hommx_coef_source* s, int32_t n_dirs, const void* dirs) {
   if (s->form != HOMMX_COEF_PROGRAM) return fail(HOMMX_EINVAL, "HOMMX_DIRS_PARAMETERS needs a HOMMX_COEF_PROGRAM source, got form %d", s->form);
-  if (s->program->n_params == 0) return fail(HOMMX_EINVAL, "HOMMX_DIRS_PARAMETERS: the program has no parameters (n_params == 0)");
-  if (n_dirs != s->program->n_params)
+  if (int rc = tangent_slots_check(s, "HOMMX_DIRS_PARAMETERS")) return rc;
+  if (s->n_fields == 0 && n_dirs != s->program->n_params)
     return fail(HOMMX_EINVAL, "HOMMX_DIRS_PARAMETERS: n_dirs must be the program's n_params (%d), got %d", s->program->n_params, n_dirs);
+  if (n_dirs != s->program->n_params + s->n_fields)
+    return fail(HOMMX_EINVAL, "HOMMX_DIRS_PARAMETERS: n_dirs must be the source's n_params (%d) + n_fields (%d), got %d", s->program->n_params,
+                s->n_fields, n_dirs);
   if (dirs) return fail(HOMMX_EINVAL, "HOMMX_DIRS_PARAMETERS: dirs must be NULL (the library forms the directions)");
   return HOMMX_OK;
 }

@@ -4,11 +4,16 @@
 // One thread per (cell, element), 256 per block.  The program travels by value in the kernel arguments and is the same for every
 // thread, so the dispatch is a scalar branch on readfirstlane of the opcode: no divergence, whatever the program.  The top of the value
 // stack lives in a register, the rest in LDS as stack[depth][thread] -- consecutive lanes on consecutive 8-byte words, so no access has
-// a bank conflict, and a thread only ever touches its own column, so there is no barrier.  32 KiB per block; 140 VGPRs: 3 waves/SIMD.  No
+// a bank conflict, and a thread only ever touches its own column, so there is no barrier.  32 KiB per block; 142 VGPRs: 3 waves/SIMD.  No
 // register array is indexed dynamically (x, y and the component accumulators are selected by switches on the uniform operand), hence no
 // scratch.  Every arithmetic operation is one separately rounded IEEE operation (no contraction), in the order of the program, so a host
 // that interprets the same program (hommx_amd.expr.Expression.host_stream) reproduces the stream bit for bit wherever the program
 // contains exactly rounded operations only.
+//
+// The per-cell row is the midpoint and then the n_fields fields of the cell (coef_program.h, program_row_doubles).  The midpoint lives in
+// registers; a field does not -- `X k`, k >= 3, loads row[k] where it is read.  The row is 32 .. 56 bytes and stays in cache, the lanes
+// of a wave may belong to different cells (a vector load, not a scalar one), and the forward-mode kernel of four slots has no
+// registers to spare for four more live doubles.  A program without fields never takes that branch and computes what it always did.
 #include "coef_program.h"
 
 #include "kernels.h"
@@ -25,15 +30,16 @@ __device__ __forceinline__ double pick3(int k, double a0, double a1, double a2) 
 
 __global__ __launch_bounds__(BLOCK) void k_expand_program(const ProgramArgs prog, const double* __restrict__ points,
                                                          const double* __restrict__ weights, int n_q, int dim,
-                                                         const double* __restrict__ mid, double* __restrict__ coef, long long n_el,
-                                                         long long total) {
+                                                         const double* __restrict__ mid, int n_fields, double* __restrict__ coef,
+                                                         long long n_el, long long total) {
 #pragma clang fp contract(off)
   __shared__ double stack[PROGRAM_MAX_STACK][BLOCK];
   const int tid = threadIdx.x;
   const long long idx = (long long)blockIdx.x * BLOCK + tid;
   if (idx >= total) return;  // the tail of the grid; nothing below synchronises
   const long long cell = idx / n_el, el = idx - cell * n_el;
-  const double x0 = mid[cell * 3], x1 = mid[cell * 3 + 1], x2 = mid[cell * 3 + 2];
+  const double* row = mid + cell * program_row_doubles(n_fields);  // the midpoint, then the fields of the cell
+  const double x0 = row[0], x1 = row[1], x2 = row[2];
   const double* yp = points + el * n_q * dim;
   double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0, acc4 = 0.0, acc5 = 0.0;
   const int n_ops = prog.n_ops;
@@ -53,7 +59,7 @@ __global__ __launch_bounds__(BLOCK) void k_expand_program(const ProgramArgs prog
           break;
         case OP_X:
           stack[sp++][tid] = t;
-          t = pick3(k, x0, x1, x2);
+          t = k < 3 ? pick3(k, x0, x1, x2) : row[k];  // a field: loaded where it is read (uniform k: a scalar branch, a vector load)
           break;
         case OP_Y:
           stack[sp++][tid] = t;
@@ -128,7 +134,9 @@ __global__ __launch_bounds__(BLOCK) void k_expand_program(const ProgramArgs prog
   if (prog.n_comp > 5) out[5] = acc5;
 }
 
-// -- forward mode: the stream and its derivatives with respect to the parameters, the first n_params constants ---------------------------
+// -- forward mode: the stream and its derivatives with respect to the parameters (the first n_params constants) and the fields ----------
+// The differentiable slots are the parameters, then the fields (n_tan = n_params + n_fields <= P): `X k`, k >= 3, seeds slot
+// n_params + k - 3 as `CONST k`, k < n_params, seeds slot k.
 // The rules of include/hommx_hip.h (hommx_expand_tangents), which hommx_amd.expr._run_tangent restates with NumPy.  A stack entry is
 // (v, d_0 .. d_{P-1}); the value part is computed by exactly the operations of k_expand_program, so the value stream is that kernel's bit
 // for bit.  Where every operand's d_j is 0.0 the result's d_j is +0.0 and the formula does not count (live1 / live2 below): a sqrt(0) or
@@ -144,7 +152,7 @@ __global__ __launch_bounds__(BLOCK) void k_expand_program(const ProgramArgs prog
 constexpr int tangent_block(int P) { return P == 4 ? 64 : 128; }
 
 template <int P>
-__global__ __launch_bounds__(tangent_block(P)) void k_expand_program_tangent(const ProgramArgs prog, int n_params,
+__global__ __launch_bounds__(tangent_block(P)) void k_expand_program_tangent(const ProgramArgs prog, int n_params, int n_fields,
                                                                              const double* __restrict__ points,
                                                                              const double* __restrict__ weights, int n_q, int dim,
                                                                              const double* __restrict__ mid, double* __restrict__ coef,
@@ -156,7 +164,9 @@ __global__ __launch_bounds__(tangent_block(P)) void k_expand_program_tangent(con
   const long long idx = (long long)blockIdx.x * BLK + tid;
   if (idx >= total) return;  // the tail of the grid; nothing below synchronises
   const long long cell = idx / n_el, el = idx - cell * n_el;
-  const double x0 = mid[cell * 3], x1 = mid[cell * 3 + 1], x2 = mid[cell * 3 + 2];
+  const double* row = mid + cell * program_row_doubles(n_fields);  // the midpoint, then the fields of the cell
+  const double x0 = row[0], x1 = row[1], x2 = row[2];
+  const int n_tan = n_params + n_fields;  // the differentiable slots: the parameters, then the fields
   const double* yp = points + el * n_q * dim;
   double acc[PROGRAM_MAX_COMP], accd[PROGRAM_MAX_COMP][P];
 #pragma unroll
@@ -204,8 +214,14 @@ __global__ __launch_bounds__(tangent_block(P)) void k_expand_program_tangent(con
           break;
         case OP_X:
           push();
-          t = pick3(k, x0, x1, x2);
-          flat();
+          if (k < 3) {
+            t = pick3(k, x0, x1, x2);
+            flat();
+          } else {  // field k - 3, loaded where it is read (uniform k: a scalar branch, a vector load); it seeds its own slot
+            t = row[k];
+#pragma unroll
+            for (int j = 0; j < P; ++j) d[j] = (j == n_params + k - 3) ? 1.0 : 0.0;
+          }
           break;
         case OP_Y:
           push();
@@ -380,36 +396,38 @@ __global__ __launch_bounds__(tangent_block(P)) void k_expand_program_tangent(con
       if (coef) coef[idx * n_comp + c] = acc[c];
 #pragma unroll
       for (int j = 0; j < P; ++j)
-        if (j < n_params) dirs[((cell * n_params + j) * n_el + el) * n_comp + c] = accd[c][j];
+        if (j < n_tan) dirs[((cell * n_tan + j) * n_el + el) * n_comp + c] = accd[c][j];
     }
 }
 
 }  // namespace
 
-hipError_t launch_expand_program_tangent(const ProgramArgs& prog, int n_params, const double* d_points, const double* d_weights, int n_q,
-                                         int dim, const double* d_mid, double* d_coef, double* d_dirs, long long n_el, long long ncells,
-                                         hipStream_t stream) {
+hipError_t launch_expand_program_tangent(const ProgramArgs& prog, int n_params, int n_fields, const double* d_points,
+                                         const double* d_weights, int n_q, int dim, const double* d_mid, double* d_coef, double* d_dirs,
+                                         long long n_el, long long ncells, hipStream_t stream) {
   const long long total = ncells * n_el;
   if (total <= 0) return hipSuccess;
   auto launch = [&](auto kernel, int block) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((total + block - 1) / block)), dim3(block), 0, stream, prog, n_params, d_points, d_weights,
-                       n_q, dim, d_mid, d_coef, d_dirs, n_el, total);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((total + block - 1) / block)), dim3(block), 0, stream, prog, n_params, n_fields, d_points,
+                       d_weights, n_q, dim, d_mid, d_coef, d_dirs, n_el, total);
   };
-  if (n_params == 1)
+  const int n_tan = n_params + n_fields;
+  if (n_tan == 1)
     launch(k_expand_program_tangent<1>, tangent_block(1));
-  else if (n_params == 2)
+  else if (n_tan == 2)
     launch(k_expand_program_tangent<2>, tangent_block(2));
-  else  // 3 parameters run the kernel of 4 with a tangent nothing seeds and nothing stores
+  else  // 3 slots run the kernel of 4 with a tangent nothing seeds and nothing stores
     launch(k_expand_program_tangent<4>, tangent_block(4));
   return hipGetLastError();
 }
 
 hipError_t launch_expand_program(const ProgramArgs& prog, const double* d_points, const double* d_weights, int n_q, int dim,
-                                 const double* d_mid, double* d_coef, long long n_el, long long ncells, hipStream_t stream) {
+                                 const double* d_mid, int n_fields, double* d_coef, long long n_el, long long ncells,
+                                 hipStream_t stream) {
   const long long total = ncells * n_el;
   if (total <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_expand_program, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, prog, d_points, d_weights,
-                     n_q, dim, d_mid, d_coef, n_el, total);
+                     n_q, dim, d_mid, n_fields, d_coef, n_el, total);
   return hipGetLastError();
 }
 

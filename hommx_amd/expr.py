@@ -3,7 +3,8 @@
 order on both sides.
 
 The text is parsed with ``ast`` and never evaluated by Python.  Grammar: the names ``x[0..2]`` (macro cell midpoint), ``y[0..d-1]`` (fast
-variable), ``p[0..3]`` (a parameter, its value given with ``Expression(..., p=[...])``) and ``pi``, numeric literals, ``+ - * /``, unary
+variable), ``p[0..3]`` (a parameter, its value given with ``Expression(..., p=[...])``), ``f[0..3]`` (a field: one value per macro
+cell, admitted with ``Expression(..., fields=...)``) and ``pi``, numeric literals, ``+ - * /``, unary
 ``-``, ``**`` with a literal integer exponent 0 .. 8, the comparisons ``< <= > >=`` with ``and`` / ``or`` / ``not`` on them, and the
 calls ``abs min max where(c, a, b) sqrt sin cos tan exp log tanh``.
 
@@ -14,6 +15,10 @@ Parameters are the first constants of the program (``p[k]`` is ``CONST k``), so 
 parameters.  The library also differentiates the program with respect to them in forward mode (csrc/coef_program.hip,
 ``k_expand_program_tangent``); ``Expression.host_tangents`` is the NumPy twin of that pass: the rules of ``_run_tangent``, the same
 operations in the same order.
+
+Fields are read like the midpoint: ``f[k]`` is ``X 3 + k``, entry ``3 + k`` of the cell's row, so everywhere in this module they ride
+as extra rows of ``x`` (``x[3 + n_fields, ...]``), and every path that takes a program takes one with fields.  They are differentiated
+like parameters; the differentiable slots are the parameters, then the fields.
 """
 
 from __future__ import annotations
@@ -31,6 +36,7 @@ import numpy as np
 MAX_OPS, MAX_CONSTS, MAX_STACK, MAX_COMP = 128, 32, 16, 6
 MAX_POWER = 8
 MAX_PARAMS = 4  # HOMMX_PROGRAM_MAX_PARAMS
+MAX_FIELDS = 4  # HOMMX_PROGRAM_MAX_FIELDS
 
 _BINARY = {ast.Add: OP_ADD, ast.Sub: OP_SUB, ast.Mult: OP_MUL, ast.Div: OP_DIV}
 _COMPARE = {ast.Lt: OP_LT, ast.LtE: OP_LE, ast.Gt: OP_GT, ast.GtE: OP_GE}
@@ -55,8 +61,8 @@ def _bad(node, why: str):
 class _Node:
     """One node of the checked tree: ``op`` with ``args`` (nodes) or a leaf (``value``: the constant, or the index of x / y / p);
     ``boolean``: a comparison or a combination of comparisons; ``degree``: the estimate of the module docstring; ``varying``: depends on
-    x, y or a parameter (a subtree that does not is folded into one constant); ``p_degree``: the degree in the parameters
-    (``Expression.p_degree``)."""
+    x, y, a parameter or a field (a subtree that does not is folded into one constant); ``p_degree``: the degree in the parameters
+    and fields (``Expression.p_degree``)."""
 
     __slots__ = ("op", "args", "value", "boolean", "degree", "varying", "power", "p_degree")
 
@@ -72,14 +78,15 @@ class _Node:
 
 _POW = -1  # a node of the tree only: the program spells it DUP / MUL
 _PARAM = -2  # p[k], a node of the tree only: the program spells it CONST k (the parameters are the first constants)
+_FIELD = -3  # f[k], a node of the tree only: the program spells it X 3 + k (the fields stand after the midpoint in the cell's row)
 
 
 class _Context:
-    """What the components of one Expression share while they are checked: the number of parameters (None: no ``p=``) and the texts of
-    the comparisons that read one."""
+    """What the components of one Expression share while they are checked: the number of parameters (None: no ``p=``), of fields
+    (None: no ``fields=``) and the texts of the comparisons that read one."""
 
-    def __init__(self, n_params=None):
-        self.n_params, self.compared = n_params, []
+    def __init__(self, n_params=None, n_fields=None):
+        self.n_params, self.n_fields, self.compared = n_params, n_fields, []
 
 
 def _number(node, value) -> _Node:
@@ -107,6 +114,10 @@ def _check(node, ctx: _Context) -> _Node:
             return _Node(_PARAM, value=int(node.slice.value), varying=True, p_degree=1)
         if isinstance(node.value, ast.Name) and node.value.id == "p":
             raise _bad(node, "p[k] needs the values of the parameters (p=[...])")
+        if isinstance(node.value, ast.Name) and node.value.id == "f" and ctx.n_fields is not None:
+            if not _literal_int(node.slice, 0, ctx.n_fields - 1):
+                raise _bad(node, f"the index of f is a literal integer below the number of fields ({ctx.n_fields})")
+            return _Node(_FIELD, value=int(node.slice.value), varying=True, p_degree=1)
         if not (isinstance(node.value, ast.Name) and node.value.id in ("x", "y")):
             raise _bad(node, "only x and y are indexed")
         if not _literal_int(node.slice, 0, 2):
@@ -233,6 +244,8 @@ def _emit_plain(n: _Node, ops: list, consts: list, n_params: int):
         ops.append((OP_CONST, len(consts) - 1))
     elif n.op == _PARAM:
         ops.append((OP_CONST, n.value))
+    elif n.op == _FIELD:
+        ops.append((OP_X, 3 + n.value))
     elif n.op in (OP_X, OP_Y):
         ops.append((n.op, n.value))
     elif n.op == _POW:
@@ -261,8 +274,8 @@ def stack_depths(ops) -> list[int]:
 
 
 def _run(ops, consts, n_comp: int, x, y) -> list:
-    """Interpret a program with NumPy on x[3, ...] and y[d, ...] (broadcast against each other): one array per component, each operation
-    the separately rounded IEEE operation the kernel performs."""
+    """Interpret a program with NumPy on x[3 + n_fields, ...] (the midpoint, then the fields: ``X k`` reads row k) and y[d, ...]
+    (broadcast against each other): one array per component, each operation the separately rounded IEEE operation the kernel performs."""
     stack, out = [], [None] * n_comp
     one, zero = np.float64(1.0), np.float64(0.0)
     flag = lambda m: np.where(m, one, zero)
@@ -318,13 +331,14 @@ def _binary(op, a, b, flag):
     raise ValueError(f"program: unknown opcode {op}")
 
 
-def _run_tangent(ops, consts, n_comp: int, n_params: int, x, y) -> tuple[list, list]:
-    """``_run`` in forward mode: (values[n_comp], tangents[n_comp][n_params]), the rules of include/hommx_hip.h (hommx_expand_tangents)
-    as k_expand_program_tangent applies them.  A stack entry is (v, d_0 .. d_{P-1}); the value part is ``_run``'s.  A tangent that is
+def _run_tangent(ops, consts, n_comp: int, n_params: int, x, y, n_fields: int = 0) -> tuple[list, list]:
+    """``_run`` in forward mode: (values[n_comp], tangents[n_comp][n_params + n_fields]), the rules of include/hommx_hip.h
+    (hommx_expand_tangents) as k_expand_program_tangent applies them; the slots are the parameters, then the fields (``X k``, k >= 3,
+    seeds slot ``n_params + k - 3``).  A stack entry is (v, d_0 .. d_{P-1}); the value part is ``_run``'s.  A tangent that is
     None is +0.0 everywhere: where every operand's d_j is 0.0 the result's d_j is +0.0 and the formula is not evaluated -- structurally
     (None) or, point by point, through ``np.where`` -- so a sqrt(0) or a division by zero in a part of the expression that does not read
     p[j] cannot make its tangent NaN."""
-    P = n_params
+    P = n_params + n_fields
     stack, out_v, out_d = [], [None] * n_comp, [None] * n_comp
     one, zero, two = np.float64(1.0), np.float64(0.0), np.float64(2.0)
     flag = lambda m: np.where(m, one, zero)
@@ -342,9 +356,9 @@ def _run_tangent(ops, consts, n_comp: int, n_params: int, x, y) -> tuple[list, l
 
     for op, k in ops:
         if op == OP_CONST:
-            stack.append((np.float64(consts[k]), [one if (k == j and k < P) else None for j in range(P)]))
+            stack.append((np.float64(consts[k]), [one if (k == j and k < n_params) else None for j in range(P)]))
         elif op == OP_X:
-            stack.append((np.asarray(x[k], dtype=np.float64), list(none)))
+            stack.append((np.asarray(x[k], dtype=np.float64), [one if (k >= 3 and j == n_params + k - 3) else None for j in range(P)]))
         elif op == OP_Y:
             stack.append((np.asarray(y[k], dtype=np.float64), list(none)))
         elif op == OP_DUP:
@@ -426,12 +440,20 @@ class Expression:
     are then the whole Hessian.  A parameter inside a comparison logs one WARNING: the derivative ignores the motion of the interface
     (it is zero almost everywhere); a smooth transition such as ``tanh`` is the way to differentiate a radius.
 
+    ``fields=2`` or ``fields=("radius", "phase")``: up to 4 fields ``f[k]`` (literal index), each ONE VALUE PER MACRO CELL -- a design
+    variable, the macro solution at the midpoint, a random draw --, ``field_names`` their names (default ``"f0"``, ``"f1"``, ...).  The
+    solver classes take the values with ``set_fields``; the device reads them from the cell's row, after the midpoint.  ``f[k]`` has
+    quadrature degree 0 and ``p_degree`` 1, so ``p_degree`` and ``affine_in_parameters`` speak of parameters and fields together, and a
+    field inside a comparison logs the same WARNING.  In this module the fields ride as extra rows of ``x``: ``components``,
+    ``__call__``, ``host_stream`` and ``host_tangents`` take ``x`` with ``3 + n_fields`` entries, and ``host_tangents`` returns the
+    ``n_params + n_fields`` differentiable slots, the parameters first.
+
     The object is also a plain callable ``A(x, y)`` -- it interprets ``program()`` with NumPy --, so every generic path accepts it.
     ``host_stream`` is the documented host equivalent of the device sampler, ``host_tangents`` of its forward-mode pass: the same IEEE
     operations in the same order.
     """
 
-    def __init__(self, text=None, *, lam=None, mu=None, p=None, parameter_names=None):
+    def __init__(self, text=None, *, lam=None, mu=None, p=None, parameter_names=None, fields=None):
         if (lam is None) != (mu is None) or (text is None) == (lam is None):
             raise ValueError("Expression(text), Expression([[a, b], [b, c]]) or Expression(lam=..., mu=...)")
         self.dim = None  # the d of a matrix
@@ -442,7 +464,8 @@ class Expression:
         self.parameter_names = tuple(str(s) for s in parameter_names)
         if len(self.parameter_names) != self.n_params:
             raise ValueError(f"expression: {len(self.parameter_names)} parameter_names for {self.n_params} parameters")
-        ctx = _Context(self.n_params if p is not None else None)
+        self.n_fields, self.field_names = _field_names(fields)
+        ctx = _Context(self.n_params if p is not None else None, self.n_fields if fields is not None else None)
         if lam is not None:
             self.shape, texts = "lame", [lam, mu]
         elif isinstance(text, (list, tuple)):
@@ -452,7 +475,8 @@ class Expression:
             self.shape, self.dim = "matrix", d
             pairs = [(0, 0), (1, 1), (0, 1)] if d == 2 else [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]  # the component order of the ABI
             for i, j in pairs:
-                if i != j and _parse(text[i][j], _Context(ctx.n_params)).key() != _parse(text[j][i], _Context(ctx.n_params)).key():
+                if i != j and _parse(text[i][j], _Context(ctx.n_params, ctx.n_fields)).key() != \
+                        _parse(text[j][i], _Context(ctx.n_params, ctx.n_fields)).key():
                     raise ValueError(f"expression: the matrix must be symmetric; entries [{i}][{j}] and [{j}][{i}] differ")
             texts, self._pairs = [text[i][j] for i, j in pairs], pairs
         else:
@@ -502,14 +526,28 @@ class Expression:
         return self._ops.copy(), self._consts.copy()
 
     def components(self, x, y) -> list:
-        """The components at x[3, ...], y[d, ...], each broadcast to the common shape of x[0] and y[0]."""
+        """The components at x[3 + n_fields, ...] (the midpoint, then the fields), y[d, ...], each broadcast to the common shape of x[0]
+        and y[0]."""
         x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+        self._check_rows(x.shape[0])
         if self.n_y > y.shape[0]:
             raise ValueError(f"the expression reads y[{self.n_y - 1}]; the fast variable has {y.shape[0]} components")
         shape = np.broadcast(x[0], y[0]).shape
         with np.errstate(all="ignore"):
             out = _run(self._ops.tolist(), self._consts, self.n_comp, x, y)
         return [np.broadcast_to(v, shape) for v in out]
+
+    def _check_rows(self, rows: int):
+        if self.n_fields and rows < 3 + self.n_fields:
+            raise ValueError(f"the expression reads the fields {', '.join(self.field_names)}: x must have 3 + {self.n_fields} entries "
+                             f"(the midpoint, then the fields of the cell); got {rows}")
+
+    def _rows(self, x) -> np.ndarray:
+        """x as float64[N, 3 + n_fields]: the rows of the cells."""
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim >= 1:
+            self._check_rows(x.shape[-1])
+        return x.reshape(-1, 3 + self.n_fields)
 
     def __call__(self, x, y):
         v = self.components(x, y)
@@ -525,9 +563,9 @@ class Expression:
         return out
 
     def host_stream(self, x: np.ndarray, yq: np.ndarray, w: np.ndarray) -> np.ndarray:
-        """Element means coef[N, n_el(, n_comp)] at the midpoints x[N, 3] from the points yq[n_el, n_q, d] and weights w[n_q], exactly as
-        the device forms them: ``acc = acc + w[q] * v_q`` with q ascending, from 0."""
-        x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+        """Element means coef[N, n_el(, n_comp)] at the rows x[N, 3 + n_fields] (midpoint, then fields) from the points yq[n_el, n_q, d] and
+        weights w[n_q], exactly as the device forms them: ``acc = acc + w[q] * v_q`` with q ascending, from 0."""
+        x = self._rows(x)
         n_el, nq, d = yq.shape
         acc = [np.zeros((x.shape[0], n_el)) for _ in range(self.n_comp)]
         for q in range(nq):
@@ -537,26 +575,45 @@ class Expression:
         return acc[0] if self.n_comp == 1 else np.stack(acc, axis=-1)
 
     def host_tangents(self, x: np.ndarray, yq: np.ndarray, w: np.ndarray) -> np.ndarray:
-        """The derivatives of ``host_stream`` with respect to the parameters, dirs[N, n_params, n_el(, n_comp)], exactly as the device's
-        forward-mode pass forms them (``_run_tangent``: the rules), ``acc_j = acc_j + w[q] * d_j`` with q ascending, from 0."""
-        if self.n_params == 0:
+        """The derivatives of ``host_stream`` with respect to the parameters, then the fields (of a cell: its own value),
+        dirs[N, n_params + n_fields, n_el(, n_comp)], exactly as the device's forward-mode pass forms them (``_run_tangent``: the rules),
+        ``acc_j = acc_j + w[q] * d_j`` with q ascending, from 0."""
+        if self.n_params + self.n_fields == 0:
             raise ValueError("the expression has no parameters (p=[...])")
-        x = np.asarray(x, dtype=np.float64).reshape(-1, 3)
+        x = self._rows(x)
         n_el, nq, d = yq.shape
         if self.n_y > d:
             raise ValueError(f"the expression reads y[{self.n_y - 1}]; the fast variable has {d} components")
-        P, shape = self.n_params, (x.shape[0], n_el)
+        P, shape = self.n_params + self.n_fields, (x.shape[0], n_el)
         acc = [[np.zeros(shape) for _ in range(self.n_comp)] for _ in range(P)]
         ops = self._ops.tolist()
         for q in range(nq):
             with np.errstate(all="ignore"):
-                _, dv = _run_tangent(ops, self._consts, self.n_comp, P, x.T[:, :, None], np.moveaxis(yq[:, q, :], -1, 0)[:, None, :])
+                _, dv = _run_tangent(ops, self._consts, self.n_comp, self.n_params, x.T[:, :, None],
+                                     np.moveaxis(yq[:, q, :], -1, 0)[:, None, :], self.n_fields)
             for j in range(P):
                 for c in range(self.n_comp):
                     dj = np.float64(0.0) if dv[c][j] is None else dv[c][j]
                     acc[j][c] = acc[j][c] + w[q] * np.broadcast_to(dj, shape)
         out = np.stack([np.stack(a, axis=-1) for a in acc], axis=1)  # [N, P, n_el, n_comp]
         return out[..., 0] if self.n_comp == 1 else out
+
+
+def _field_names(fields) -> tuple[int, tuple]:
+    """(n_fields, field_names) of ``fields=``: a count, or the names."""
+    if fields is None:
+        return 0, ()
+    if isinstance(fields, (int, np.integer)) and not isinstance(fields, bool):
+        names = tuple(f"f{k}" for k in range(int(fields)))
+        if fields < 0:
+            raise ValueError(f"expression: fields must be a count 0 .. {MAX_FIELDS} or a sequence of names; got {fields!r}")
+    elif isinstance(fields, (list, tuple)) and all(isinstance(s, str) for s in fields):
+        names = tuple(fields)
+    else:
+        raise ValueError(f"expression: fields must be a count 0 .. {MAX_FIELDS} or a sequence of names; got {fields!r}")
+    if len(names) > MAX_FIELDS:
+        raise ValueError(f"expression: at most {MAX_FIELDS} fields; got {len(names)}")
+    return len(names), names
 
 
 def _parameter_values(p, n_params: int | None) -> np.ndarray:

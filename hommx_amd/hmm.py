@@ -289,6 +289,7 @@ class BaseHMM(ABC):
         self.cell_info: np.ndarray | None = None
         self._solved = False  # reconstruct() defaults to the last solve() result
         self._polarisation = None  # set_polarisation
+        self._fields: np.ndarray | None = None  # set_fields: [num_cells, n_fields] of an Expression with fields
         self.effective_polarisation: np.ndarray | None = None  # P_eff[N, t] of every macro cell after a solve() with a polarisation
         if self._reserve_at_construction:
             self.prepare()
@@ -316,6 +317,59 @@ class BaseHMM(ABC):
             raise ValueError("set_parameters() needs an Expression coefficient with parameters (Expression(..., p=[...]))")
         self._coeff = self._coeff.with_parameters(p)
         self._needs_reassembly = True
+
+    def set_fields(self, values):
+        """The values of the fields ``f[k]`` of an ``Expression`` coefficient (``Expression(..., fields=...)``), one per macro cell: a
+        design variable, the macro solution at the midpoint (``cell_means``), a random draw.  ``values``: an array
+        ``[num_cells, n_fields]`` (``[num_cells]`` is accepted for one field), or a callable ``x[3, num_cells] -> [n_fields, num_cells]``
+        evaluated at the cell midpoints.  Every value must be finite.  The macro matrix is reassembled by the next ``solve()``; the
+        plan and its workspace are kept -- the step of a Picard loop or of a design iteration.  Under a process group every rank is
+        given the whole array and reads the rows of its own cells.  ``ValueError`` when the coefficient is no ``Expression`` with
+        fields, or ``values`` has another shape."""
+        co = self._coeff
+        if not isinstance(co, Expression) or co.n_fields == 0:
+            raise ValueError("set_fields() needs an Expression coefficient with fields (Expression(..., fields=...))")
+        n, k = self._msh.num_cells, co.n_fields
+        if callable(values):
+            v = np.asarray(values(self._msh.cell_midpoints().T), dtype=np.float64)
+            v = (v[None] if v.ndim == 1 and k == 1 else v).T
+        else:
+            v = np.asarray(values, dtype=np.float64)
+            if v.ndim == 1 and k == 1:
+                v = v[:, None]
+        if v.shape != (n, k):
+            raise ValueError(f"the fields {', '.join(co.field_names)} need values of shape ({n}, {k}); got {np.shape(values) if not callable(values) else v.T.shape}")
+        if not np.isfinite(v).all():
+            c, j = np.argwhere(~np.isfinite(v))[0]
+            raise ValueError(f"field {co.field_names[j]} is not finite on macro cell {c}: {v[c, j]}")
+        self._fields = np.array(v, dtype=np.float64, order="C")
+        self._needs_reassembly = True
+
+    def cell_means(self, u=None) -> np.ndarray:
+        """[num_cells] (a scalar macro space) or [num_cells, d]: the mean of the vertex values of the macro field ``u`` (a macro
+        ``fem.Function`` or its dof array; default: the last ``solve()`` result) on every macro cell -- u_H at the cell midpoint, what a
+        solution-dependent coefficient ``A(x, u_H(x), y)`` is fed: ``h.set_fields(h.cell_means(u))``."""
+        if u is None:
+            if not self._solved:
+                raise RuntimeError("cell_means() needs a macro solution: call solve() first or pass u")
+            u = self._u
+        x = np.asarray(u.x.array if hasattr(u, "x") else u, dtype=float)
+        if x.shape != (self._num_global_dofs,):
+            raise ValueError(f"u has {x.size} dofs; the macro space has {self._num_global_dofs}")
+        uT = x[_unroll_dofs(self._msh.cells.astype(np.int64), self._bs)]  # [nc, (d + 1) * bs], dof = vertex * bs + component
+        mean = uT.reshape(uT.shape[0], -1, self._bs).mean(axis=1)
+        return mean[:, 0] if self._bs == 1 else mean
+
+    def _cell_rows(self, cells: np.ndarray, coeff=None) -> np.ndarray:
+        """x of ``coeff`` (default: the coefficient) on ``cells``: the midpoints [N, 3] and, for an ``Expression`` with fields, the fields
+        of the cells after them, [N, 3 + n_fields] -- the rows the device reads and the x every host path evaluates the expression at."""
+        c = self._msh.cell_midpoints()[cells]
+        co = self._coeff if coeff is None else coeff
+        if not isinstance(co, Expression) or co.n_fields == 0:
+            return c
+        if self._fields is None or self._fields.shape[1] != co.n_fields:
+            raise RuntimeError(f"the Expression reads the fields {', '.join(co.field_names)}: call set_fields() with their values per macro cell first")
+        return np.concatenate([c, self._fields[cells]], axis=1)
 
     def set_polarisation(self, P):
         """A prescribed micro flux / stress field P(x, y): a thermal eigenstress -A : alpha dT, a prestress, the gravity
@@ -403,7 +457,7 @@ class BaseHMM(ABC):
         yq, w = self._quadrature_points()
         n_el, nq = yq.shape[:2]
         yflat = yq.reshape(-1, self._tdim).T
-        c = self._msh.cell_midpoints()[cells]
+        c = self._cell_rows(cells, coeff)
         out = self._sample_batched(c, yflat, n_el, nq, w, coeff)
         if out is None:  # the callable is not broadcastable over cells: one call per macro cell (as the reference)
             first = self._sample_one(c[0], yflat, coeff)
@@ -615,7 +669,7 @@ class BaseHMM(ABC):
         """The coefficient of ``cells`` as the plan takes it, and the plan kind: ``TwoPhase`` as one mask (evaluated at the element
         barycentres) + two values per cell, ``Separable`` as one table of g + (a, b) per cell (per Lame parameter for the elasticity
         classes: test_integration_linear_elasticity.py:78-93), an ``Expression`` as its program + the points of the micro quadrature rule
-        + the midpoint of every cell, anything else as sampled element means.
+        + the midpoint (and the fields, ``set_fields``) of every cell, anything else as sampled element means.
 
         What stands in ``self._plan`` is a ``MicroCellPlan`` or a stand-in for it (the CPU tests answer from a NumPy restatement).  A stand-in has
         ``t``, ``kind`` and ``solve(coef, M=None, return_info=False[, return_correctors])``; it may have ``reserve`` (needed by
@@ -626,7 +680,7 @@ class BaseHMM(ABC):
         if form is None or not hasattr(self._ensure_plan(kind), form):
             coef, kind = self._element_means(cells)
             return CoefStream.sampled(coef), kind
-        co, c = self._coeff, self._msh.cell_midpoints()[cells]
+        co, c = self._coeff, self._cell_rows(cells)
         if form == "solve_two_phase":
             mask = self._phase_mask()
             values = co.phase_values(c)
@@ -635,7 +689,7 @@ class BaseHMM(ABC):
             return CoefStream.two_phase(mask, values), kind
         yq, w = self._quadrature_points()
         if form == "solve_program":
-            return CoefStream.program(yq, w, *co.program(), co.n_comp, c, n_params=co.n_params), kind
+            return CoefStream.program(yq, w, *co.program(), co.n_comp, c, n_params=co.n_params, n_fields=co.n_fields), kind
         return CoefStream.separable(co.family, co.table(yq, w), w, co.params(c)), kind
 
     def _phase_mask(self) -> np.ndarray:
@@ -941,7 +995,9 @@ class BaseHMM(ABC):
         value of a ``TwoPhase`` coefficient, a and b of an affine ``Separable`` one, of every component (lambda and mu for the elasticity
         classes), and the named parameters ``p[k]`` of an ``Expression`` (``Expression(..., p=[...], parameter_names=...)``): the
         program is differentiated on the device in forward mode, in the pass that samples it, so nothing is sampled on the host and no
-        direction stream crosses the boundary.  Any other coefficient raises ``ValueError``: its element stream is not linear in a few
+        direction stream crosses the boundary.  The fields ``f[k]`` of an ``Expression`` (``fields=...``, ``set_fields``) follow the
+        parameters: ``names == parameter_names + field_names`` and ``dA[N, n_params + n_fields, t, t]``, where the field entry of cell
+        T is the derivative with respect to T's OWN value (the tensor of a cell does not depend on another cell's).  Any other coefficient raises ``ValueError``: its element stream is not linear in a few
         parameters.
         ``directions=[dA_0, ...]``: callables (x, y) of the coefficient's shape, up to 8; each is sampled exactly as the coefficient is
         (the same quadrature degree and packing) and dA[:, k] is the derivative of A_H along it.
@@ -961,7 +1017,8 @@ class BaseHMM(ABC):
         if len(cells) == 0:
             raise ValueError(f"{what}() needs at least one macro cell")
         co = self._coeff
-        if directions is None and isinstance(co, Expression) and co.n_params and self._device_form() == "solve_program" \
+        self._cell_rows(cells[:1])  # an Expression whose fields are not set: the RuntimeError that names set_fields, before anything else
+        if directions is None and isinstance(co, Expression) and (co.n_params or co.n_fields) and self._device_form() == "solve_program" \
                 and hasattr(self._ensure_plan(self._micro_kind()), "solve_program"):
             # the parameter tangents of the program, formed on the device with the stream: nothing is sampled, no direction stream is sent
             if what == "tensor_second_derivatives" and not co.affine_in_parameters:
@@ -970,7 +1027,7 @@ class BaseHMM(ABC):
                     "d2A/dp_a dp_b, which second-order tangents would give and this library does not form.  directions=[...] with your own "
                     "streams remains available: the second derivatives along them, and tensor_derivatives(directions=[d2A/dp_a dp_b, ...]) "
                     "for the curvature term")
-            names, shared = co.parameter_names, "parameters"
+            names, shared = co.parameter_names + co.field_names, "parameters"
         elif directions is None:
             names, shared = self._parameter_directions()
         else:
@@ -997,7 +1054,9 @@ class BaseHMM(ABC):
     def energy_derivatives(self, u=None, v=None, **kw) -> np.ndarray:
         """[N, n_dirs]: vol(T)/vol(Y) xi_v(T) . dA_H[d](T) xi_u(T) for the cells and directions of ``tensor_derivatives(**kw)``, with xi the
         macro gradient / Voigt strain ``reconstruct()`` forms -- the contribution of macro cell T to d(v . K_H u)/d theta_d at frozen u, v:
-        the compliance gradient for v = u (the default; ``u`` defaults to the last ``solve()`` result), the adjoint product otherwise."""
+        the compliance gradient for v = u (the default; ``u`` defaults to the last ``solve()`` result), the adjoint product otherwise.
+        For a field ``f[k]`` of an ``Expression`` only cell T depends on the value of T, so entry ``[T, n_params + k]`` is the WHOLE
+        derivative of u . K_H u at frozen u with respect to the design variable (T, k), not one contribution among many."""
         if u is None:
             if not self._solved:
                 raise RuntimeError("energy_derivatives() needs a macro solution: call solve() first or pass u")

@@ -281,7 +281,7 @@ int hommx_reconstruct_batch_device(hommx_plan* plan, int64_t n_cells, const doub
  * kernel (csrc/coef_program.hip) -- the program is data, nothing is compiled at run time.  With the source's
  *   table    [n_el][n_q][dim]   the points y_{K,q} of the micro quadrature rule on every micro element
  *   weights  [n_q]              its weights,  n_q >= 1 their number
- *   params   [n_cells][3]       the midpoint c_T of every macro cell (x of the expression)
+ *   params   [n_cells][3 + n_fields]   the midpoint c_T of every macro cell (x of the expression), then the cell's fields
  * the element mean of component c is  A_K[c] = sum_q weights[q] * v_c(c_T, y_{K,q}),  accumulated as acc = acc + weights[q] * v from 0
  * with q ascending, every operation of the program and of the sum one separately rounded IEEE-754 operation in the written order: a
  * host that interprets the same program (hommx_amd.expr.Expression.host_stream) reproduces the element stream bit for bit when the
@@ -290,7 +290,7 @@ int hommx_reconstruct_batch_device(hommx_plan* plan, int64_t n_cells, const doub
  * plan -- a fused 2D plan then runs the mode that reads a sampled stream -- so every output equals the one of that stream, bit for bit.
  *
  * ops[n_ops][2] = (opcode, operand); the operand is the index of CONST / X / Y / STORE and ignored otherwise:
- *    0 CONST k  push consts[k]      1 X i  push x[i], i < 3      2 Y i  push y[i], i < dim
+ *    0 CONST k  push consts[k]      1 X i  push x[i], i < 3; field i - 3, 3 <= i < 3 + n_fields      2 Y i  push y[i], i < dim
  *    3 ADD  4 SUB  5 MUL  6 DIV     (a, b) -> a op b, b on top
  *    7 NEG  8 ABS                   9 MIN  10 MAX  (a, b) -> b < a ? b : a  /  b > a ? b : a
  *   11 LT  12 LE  13 GT  14 GE      (a, b) -> 1.0 or 0.0         15 AND  16 OR  17 NOT  on "non-zero is true", -> 1.0 or 0.0
@@ -300,14 +300,24 @@ int hommx_reconstruct_batch_device(hommx_plan* plan, int64_t n_cells, const doub
  * or consts, n_q < 1, null table / weights / params; n_ops outside 1 .. 128, n_consts outside 0 .. 32; n_comp other than the plan's;
  * a plan of the HOMMX_KIND_ELASTICITY_VOIGT kind (21 components: not supported); an unknown opcode; a CONST, X or Y index out of range;
  * stack underflow; stack depth above 16; a component stored twice or never; values left on the stack at the end; n_params outside
- * 0 .. HOMMX_PROGRAM_MAX_PARAMS or above n_consts.
+ * 0 .. HOMMX_PROGRAM_MAX_PARAMS or above n_consts; the source's n_fields outside 0 .. HOMMX_PROGRAM_MAX_FIELDS; an X index at or above
+ * 3 + n_fields.
  *
  * Parameters: the first n_params constants are the parameters p[0 .. n_params-1] of the expression, shared by all macro cells.  For
  * the solve, expand, reconstruct and loads entries they are constants like the others, and n_params == 0 is a program without
  * parameters on every path.  hommx_expand_tangents differentiates the program with respect to them, and HOMMX_DIRS_PARAMETERS makes
  * those derivatives the directions of the derivative entries.
+ *
+ * Fields: hommx_coef_source.n_fields (0 .. HOMMX_PROGRAM_MAX_FIELDS) values PER MACRO CELL -- a design variable, the macro solution at
+ * the midpoint, a random draw -- which stand after the midpoint in the cell's row of `params` and are read by `X k`, k >= 3, like a
+ * coordinate of the midpoint.  No entry point, opcode or struct is added for them: the member was `reserved` (0), so a caller that
+ * never heard of fields passes a program without them, and everything about such a source is what it was.  The kernels load a field
+ * where it is read (the row stays in cache) instead of holding it in a register.  The differentiable slots of hommx_expand_tangents and
+ * HOMMX_DIRS_PARAMETERS are the parameters, then the fields: n_tan = n_params + n_fields, at most HOMMX_PROGRAM_MAX_PARAMS together;
+ * the derivative with respect to a field is the derivative of the cell's stream with respect to the cell's OWN value.
  */
 #define HOMMX_PROGRAM_MAX_PARAMS 4
+#define HOMMX_PROGRAM_MAX_FIELDS 4
 typedef struct hommx_coef_program {
   int32_t n_ops, n_consts, n_comp;
   int32_t n_params;      /* 0 .. HOMMX_PROGRAM_MAX_PARAMS, <= n_consts (this member was `reserved`, 0) */
@@ -319,7 +329,8 @@ typedef struct hommx_coef_source {
   int32_t form;     /* HOMMX_COEF_*                                    */
   int32_t family;   /* HOMMX_SAMPLER_* (HOMMX_COEF_SEPARABLE)          */
   int32_t n_q;      /* columns of table (HOMMX_SAMPLER_RECIPROCAL)     */
-  int32_t reserved;
+  int32_t n_fields; /* HOMMX_COEF_PROGRAM: fields per macro cell, 0 .. HOMMX_PROGRAM_MAX_FIELDS; read for that form ONLY (this member was
+                       `reserved`, 0) */
   const double* coef;
   const uint8_t* mask;
   const double* values;
@@ -344,15 +355,18 @@ int hommx_expand_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_sour
 int hommx_expand_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, double* d_coef_out, void* stream);
 
 /*
- * The derivatives of the element stream of a HOMMX_COEF_PROGRAM source with respect to its parameters, in forward mode: ONE pass of
+ * The derivatives of the element stream of a HOMMX_COEF_PROGRAM source with respect to its parameters and its fields (the n_tan =
+ * n_params + n_fields differentiable slots, the parameters first; 1 <= n_tan <= HOMMX_PROGRAM_MAX_PARAMS), in forward mode: ONE pass of
  * the interpreter (csrc/coef_program.hip, k_expand_program_tangent) carries (v, d_0 .. d_{P-1}) per stack entry and yields
  *   coef_out [n_cells][n_el][n_comp]             the stream of hommx_expand_source, bit for bit (or NULL: not wanted)
- *   dirs_out [n_cells][n_params][n_el][n_comp]   d coef / d p[j], the layout of per-cell directions (hommx_sens_args, per_cell == 1)
+ *   dirs_out [n_cells][n_tan][n_el][n_comp]      d coef / d slot j (p[j], or field j - n_params of the cell itself), the layout of
+ *                                                per-cell directions (hommx_sens_args, per_cell == 1)
  * Every arithmetic step is one separately rounded IEEE-754 operation in the written order, no contraction; hommx_amd.expr.Expression
  * .host_tangents applies the same rules in the same order with NumPy.  For parameter j, if every operand's d_j is 0.0 the result's d_j
  * is +0.0 and the formula is not evaluated: a sqrt(0) or a division by zero in a part of the expression that does not depend on p[j]
  * cannot make its tangent NaN.  Otherwise, for operands (a, da), (b, db), b on top, and the instruction's own value v:
- *   CONST k   d_j = (k == j && k < n_params) ? 1 : 0           X, Y   d_j = 0           DUP   copies
+ *   CONST k   d_j = (k == j && k < n_params) ? 1 : 0           X k, k < 3, Y   d_j = 0           DUP   copies
+ *   X k, k >= 3:   d_j = (j == n_params + k - 3) ? 1 : 0
  *   ADD  da + db         SUB  da + (-db)         NEG  -da
  *   MUL  add(mul(a, db), mul(da, b))             DIV  div(add(da, -mul(v, db)), b),  v = a / b
  *   ABS  a < 0 ? -da : da          MIN / MAX / SELECT  the tangent of the operand the value rule picks
@@ -360,8 +374,9 @@ int hommx_expand_source_device(hommx_plan* plan, int64_t n_cells, const hommx_co
  *   SQRT div(da, mul(2, v))        SIN  mul(cos(a), da)        COS  -mul(sin(a), da)        TAN  mul(da, add(1, mul(v, v)))
  *   EXP  mul(v, da)                LOG  div(da, a)             TANH mul(da, add(1, -mul(v, v)))
  *   STORE c   acc[c] = add(acc[c], mul(w, v));  accd[c][j] = add(accd[c][j], mul(w, d_j)),  q ascending, from 0
- * Validation: that of hommx_expand_source, and HOMMX_EINVAL with a text for a source of another form, n_params == 0, a null dirs_out.
- * The host entry stages the source as hommx_expand_source does and returns chunk by chunk (at most 1 GiB of the 1 + n_params streams).
+ * Validation: that of hommx_expand_source, and HOMMX_EINVAL with a text for a source of another form, n_tan == 0, n_tan above
+ * HOMMX_PROGRAM_MAX_PARAMS (the text names both counts), a null dirs_out.
+ * The host entry stages the source as hommx_expand_source does and returns chunk by chunk (at most 1 GiB of the 1 + n_tan streams).
  */
 int hommx_expand_tangents(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, double* coef_out, double* dirs_out);
 /* Same with DEVICE pointers (in *src as well), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
@@ -392,10 +407,11 @@ int hommx_reconstruct_source_device(hommx_plan* plan, int64_t n_cells, const hom
  *
  *   n_dirs      0 .. HOMMX_SENS_MAX_DIRS direction streams, each shaped like one cell's coefficient [n_el][n_comp]
  *   per_cell    0: dirs[n_dirs][n_el][n_comp], shared by all cells; 1: dirs[n_cells][n_dirs][n_el][n_comp];
- *               HOMMX_DIRS_PARAMETERS: the directions are the derivatives of the source's program with respect to its parameters
+ *               HOMMX_DIRS_PARAMETERS: the directions are the derivatives of the source's program with respect to its parameters and fields
  *               (hommx_expand_tangents), formed on the device chunk by chunk in the launch that expands the stream, into plan-owned
- *               scratch whose bytes the chunk rule counts: dirs == NULL, n_dirs == the program's n_params, dA as with per_cell == 1.
- *               HOMMX_EINVAL with a text for a source that is no HOMMX_COEF_PROGRAM, n_params == 0, another n_dirs, a non-null dirs
+ *               scratch whose bytes the chunk rule counts: dirs == NULL, n_dirs == n_tan = the program's n_params + the source's
+ *               n_fields (1 .. HOMMX_PROGRAM_MAX_PARAMS), dA as with per_cell == 1.
+ *               HOMMX_EINVAL with a text for a source that is no HOMMX_COEF_PROGRAM, n_tan == 0 or above 4, another n_dirs, a non-null dirs
  *   dA          [n_cells][n_dirs][t][t] (symmetric, bitwise); required with n_dirs > 0, as dirs
  *   weights     [n_cells][t][t] and grad [n_cells][n_el][n_comp] (the shape of coef): both or neither
  *   A_eff, info as hommx_solve_batch, or NULL
