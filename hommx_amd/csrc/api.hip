@@ -411,16 +411,9 @@ int stream_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t want, int64_
   return grow(p->buf[B_EXPAND], stream);
 }
 
-// the stream of cells [c0, c0 + nc) of a program source (into `coef`; null: not wanted) and its parameter tangents, in one launch
-int expand_tangents_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t c0, int64_t nc, hipStream_t st, double* coef, double* tangents) {
-  HIP_TRY(hommx::launch_expand_program_tangent(program_args(*s.program), s.program->n_params, s.n_fields, s.table, s.weights, s.n_q,
-                                               p->desc.dim, program_rows(s, c0), coef, tangents, p->n_el, nc, st));
-  return HOMMX_OK;
-}
-
 // *stream: the element stream of cells [c0, c0 + nc) of a source on the device.  A sampled stream is a view of the caller's; a sampler
 // form is expanded into the plan's element stream (nc <= the chunk of stream_chunk) or, if given, into `into`; `tangents`: a program's
-// parameter tangents as well, in the same launch
+// parameter tangents as well, in the same launch -- and then a null `stream`: the tangents alone, no element stream is written
 int expand_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t c0, int64_t nc, hipStream_t st, const double** stream,
                  double* into = nullptr, double* tangents = nullptr) {
   const int n_comp = p->ks.n_comp;
@@ -428,17 +421,15 @@ int expand_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t c0, int64_t 
     *stream = s.coef + c0 * p->n_el * n_comp;
     return HOMMX_OK;
   }
-  double* dst = into ? into : static_cast<double*>(p->buf[B_EXPAND].p);
-  if (tangents) {
-    if (int rc = expand_tangents_chunk(p, s, c0, nc, st, dst, tangents)) return rc;
-  } else if (s.form == HOMMX_COEF_TWO_PHASE)
+  double* dst = !stream ? nullptr : into ? into : static_cast<double*>(p->buf[B_EXPAND].p);
+  if (s.form == HOMMX_COEF_TWO_PHASE)
     HIP_TRY(hommx::launch_expand_two_phase(s.mask, s.values + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st));
   else if (s.form == HOMMX_COEF_PROGRAM)
-    HIP_TRY(hommx::launch_expand_program(program_args(*s.program), s.table, s.weights, s.n_q, p->desc.dim, program_rows(s, c0), s.n_fields,
-                                         dst, p->n_el, nc, st));
+    HIP_TRY(hommx::launch_expand_program(program_args(*s.program), s.program->n_params, s.n_fields, s.table, s.weights, s.n_q, p->desc.dim,
+                                         program_rows(s, c0), dst, tangents, p->n_el, nc, st));
   else
     HIP_TRY(hommx::launch_expand_separable(sampler_source(s), s.params + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st));
-  *stream = dst;
+  if (stream) *stream = dst;
   return HOMMX_OK;
 }
 
@@ -864,10 +855,12 @@ int hommx_expand_tangents_device(hommx_plan* p, int64_t n_cells, const hommx_coe
   const int n_tan = source_tangents(s);
   const int64_t per = p->n_el * p->ks.n_comp;
   const int64_t chunk = stream_cells(p, n_cells, n_tan);  // straight into the caller's arrays, in launches of at most 1 GiB of streams
-  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk)
-    if (int rc = expand_tangents_chunk(p, s, c0, std::min(chunk, n_cells - c0), reinterpret_cast<hipStream_t>(stream),
-                                       d_coef_out ? d_coef_out + c0 * per : nullptr, d_dirs_out + c0 * n_tan * per))
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    const double* at = nullptr;
+    if (int rc = expand_chunk(p, s, c0, std::min(chunk, n_cells - c0), reinterpret_cast<hipStream_t>(stream), d_coef_out ? &at : nullptr,
+                              d_coef_out ? d_coef_out + c0 * per : nullptr, d_dirs_out + c0 * n_tan * per))
       return rc;
+  }
   return HOMMX_OK;
 }
 
@@ -881,10 +874,11 @@ int hommx_expand_tangents(hommx_plan* p, int64_t n_cells, const hommx_coef_sourc
   if (int rc = stage_source(p, n_cells, s, {nullptr, 0, &none}, &ds)) return rc;
   int64_t chunk = 0;
   if (int rc = stream_chunk(p, s, n_cells, &chunk, n_tan)) return rc;
-  double *d_coef = static_cast<double*>(p->buf[B_EXPAND].p), *d_dirs = static_cast<double*>(p->buf[B_TANGENT].p);
+  double* d_dirs = static_cast<double*>(p->buf[B_TANGENT].p);
   for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
     const int64_t nc = std::min(chunk, n_cells - c0);
-    if (int rc = expand_tangents_chunk(p, ds, c0, nc, nullptr, coef_out ? d_coef : nullptr, d_dirs)) return rc;
+    const double* d_coef = nullptr;
+    if (int rc = expand_chunk(p, ds, c0, nc, nullptr, coef_out ? &d_coef : nullptr, nullptr, d_dirs)) return rc;
     if (coef_out) HIP_TRY(hipMemcpyAsync(coef_out + c0 * per, d_coef, sizeof(double) * nc * per, hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipMemcpyAsync(dirs_out + c0 * n_tan * per, d_dirs, sizeof(double) * nc * n_tan * per, hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));

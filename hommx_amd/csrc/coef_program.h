@@ -32,25 +32,22 @@ struct ProgramArgs {
 
 // The per-cell row of a program source (hommx_coef_source.params): the midpoint of the macro cell, then its n_fields fields
 // (include/hommx_hip.h, HOMMX_PROGRAM_MAX_FIELDS); `X k` reads entry k of the row.  THE place that knows the width of the row: the
-// host (api.hip: staging, chunk offsets) and the kernels stride by it
+// host (api.hip: staging, chunk offsets) and the kernel stride by it
 constexpr int PROGRAM_MAX_FIELDS = 4;
 __host__ __device__ constexpr int program_row_doubles(int n_fields) { return 3 + n_fields; }
-
-// coef_program.hip: coef[cell][el][comp] = sum_q w[q] * program(x = mid[cell], y = points[el][q]) as separately rounded operations,
-// q ascending from 0.  points [n_el][n_q][dim], weights [n_q], mid [ncells][program_row_doubles(n_fields)], all on the device; `prog`
-// has passed the host validation
-hipError_t launch_expand_program(const ProgramArgs& prog, const double* d_points, const double* d_weights, int n_q, int dim,
-                                 const double* d_mid, int n_fields, double* d_coef, long long n_el, long long ncells, hipStream_t stream);
 
 // The parameters of a program are its first n_params constants (include/hommx_hip.h, HOMMX_PROGRAM_MAX_PARAMS); the differentiable
 // slots of the forward mode are the parameters, then the fields, at most PROGRAM_MAX_PARAMS together
 constexpr int PROGRAM_MAX_PARAMS = 4;
 
-// coef_program.hip, forward mode: in one pass the stream of launch_expand_program, bit for bit (d_coef; null: not written), and its
-// derivatives with respect to the parameters and the fields, dirs[cell][j][el][comp], j < n_params + n_fields
-// (1 .. PROGRAM_MAX_PARAMS), by the rules of include/hommx_hip.h (hommx_expand_tangents)
-hipError_t launch_expand_program_tangent(const ProgramArgs& prog, int n_params, int n_fields, const double* d_points,
-                                         const double* d_weights, int n_q, int dim, const double* d_mid, double* d_coef, double* d_dirs,
-                                         long long n_el, long long ncells, hipStream_t stream);
+// coef_program.hip: coef[cell][el][comp] = sum_q w[q] * program(x = rows[cell], y = points[el][q]) as separately rounded operations,
+// q ascending from 0 (d_coef; null: not written), and with d_dirs, in the same pass, its derivatives with respect to the parameters and
+// the fields, dirs[cell][j][el][comp], j < n_params + n_fields (1 .. PROGRAM_MAX_PARAMS), by the rules of include/hommx_hip.h
+// (hommx_expand_tangents).  d_dirs null: the value pass, whatever slots the program has; both passes are instantiations of one kernel
+// and give the same coef bit for bit.  points [n_el][n_q][dim], weights [n_q], rows [ncells][program_row_doubles(n_fields)], all on the
+// device; `prog` has passed the host validation
+hipError_t launch_expand_program(const ProgramArgs& prog, int n_params, int n_fields, const double* d_points, const double* d_weights,
+                                 int n_q, int dim, const double* d_rows, double* d_coef, double* d_dirs, long long n_el, long long ncells,
+                                 hipStream_t stream);
 
 }  // namespace hommx

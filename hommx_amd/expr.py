@@ -12,8 +12,9 @@ Because the library can read the expression, its quadrature degree is estimated 
 (recalled here, UFL is not a dependency): see ``Expression.degree``.
 
 Parameters are the first constants of the program (``p[k]`` is ``CONST k``), so every path that takes a program takes one with
-parameters.  The library also differentiates the program with respect to them in forward mode (csrc/coef_program.hip,
-``k_expand_program_tangent``); ``Expression.host_tangents`` is the NumPy twin of that pass: the rules of ``_run_tangent``, the same
+parameters.  The library also differentiates the program with respect to them in forward mode -- the value pass is the instantiation
+of its one interpreter kernel without differentiable slots (csrc/coef_program.hip, ``k_expand_program<P>``), and ``_run`` here is
+built the same way; ``Expression.host_tangents`` is the NumPy twin of the forward-mode pass: the rules of ``_TANGENT``, the same
 operations in the same order.
 
 Fields are read like the midpoint: ``f[k]`` is ``X 3 + k``, entry ``3 + k`` of the cell's row, so everywhere in this module they ride
@@ -225,7 +226,7 @@ def _emit(n: _Node, ops: list, consts: list, n_params: int = 0):
             _emit_plain(n, sub_ops, sub_consts, 0)
             sub_ops.append((OP_STORE, 0))
             with np.errstate(all="ignore"):
-                value = float(np.asarray(_run(sub_ops, sub_consts, 1, np.zeros((3, 1)), np.zeros((3, 1)))[0]).reshape(-1)[0])
+                value = float(np.asarray(_run(sub_ops, sub_consts, 1, np.zeros((3, 1)), np.zeros((3, 1)))[0][0]).reshape(-1)[0])
         bits = np.float64(value).tobytes()
         for k in range(n_params, len(consts)):
             if np.float64(consts[k]).tobytes() == bits:
@@ -273,36 +274,25 @@ def stack_depths(ops) -> list[int]:
     return out
 
 
-def _run(ops, consts, n_comp: int, x, y) -> list:
-    """Interpret a program with NumPy on x[3 + n_fields, ...] (the midpoint, then the fields: ``X k`` reads row k) and y[d, ...]
-    (broadcast against each other): one array per component, each operation the separately rounded IEEE operation the kernel performs."""
-    stack, out = [], [None] * n_comp
-    one, zero = np.float64(1.0), np.float64(0.0)
-    flag = lambda m: np.where(m, one, zero)
-    for op, k in ops:
-        if op == OP_CONST:
-            stack.append(np.float64(consts[k]))
-        elif op == OP_X:
-            stack.append(np.asarray(x[k], dtype=np.float64))
-        elif op == OP_Y:
-            stack.append(np.asarray(y[k], dtype=np.float64))
-        elif op == OP_DUP:
-            stack.append(stack[-1])
-        elif op == OP_STORE:
-            out[k] = stack.pop()
-        elif op == OP_SELECT:
-            b, a, c = stack.pop(), stack.pop(), stack.pop()
-            stack.append(np.where(c != 0.0, a, b))
-        elif op in (OP_NEG, OP_ABS, OP_NOT) or op in _MATH_NUMPY:
-            a = stack.pop()
-            stack.append(-a if op == OP_NEG else np.abs(a) if op == OP_ABS else flag(a == 0.0) if op == OP_NOT else _MATH_NUMPY[op](a))
-        else:
-            b, a = stack.pop(), stack.pop()
-            stack.append(_binary(op, a, b, flag))
-    return out
+_ONE, _ZERO, _TWO = np.float64(1.0), np.float64(0.0), np.float64(2.0)
 
 
-def _binary(op, a, b, flag):
+def _flag(m):
+    return np.where(m, _ONE, _ZERO)
+
+
+def _unary(op, a):
+    """The value of a one-operand instruction."""
+    if op == OP_NEG:
+        return -a
+    if op == OP_ABS:
+        return np.abs(a)
+    if op == OP_NOT:
+        return _flag(a == 0.0)
+    return _MATH_NUMPY[op](a)
+
+
+def _binary(op, a, b):
     """The value of a two-operand instruction for (a, b), b on top."""
     if op == OP_ADD:
         return a + b
@@ -317,103 +307,88 @@ def _binary(op, a, b, flag):
     if op == OP_MAX:
         return np.where(b > a, b, a)
     if op == OP_LT:
-        return flag(a < b)
+        return _flag(a < b)
     if op == OP_LE:
-        return flag(a <= b)
+        return _flag(a <= b)
     if op == OP_GT:
-        return flag(a > b)
+        return _flag(a > b)
     if op == OP_GE:
-        return flag(a >= b)
+        return _flag(a >= b)
     if op == OP_AND:
-        return flag((a != 0.0) & (b != 0.0))
+        return _flag((a != 0.0) & (b != 0.0))
     if op == OP_OR:
-        return flag((a != 0.0) | (b != 0.0))
+        return _flag((a != 0.0) | (b != 0.0))
     raise ValueError(f"program: unknown opcode {op}")
 
 
-def _run_tangent(ops, consts, n_comp: int, n_params: int, x, y, n_fields: int = 0) -> tuple[list, list]:
-    """``_run`` in forward mode: (values[n_comp], tangents[n_comp][n_params + n_fields]), the rules of include/hommx_hip.h
-    (hommx_expand_tangents) as k_expand_program_tangent applies them; the slots are the parameters, then the fields (``X k``, k >= 3,
-    seeds slot ``n_params + k - 3``).  A stack entry is (v, d_0 .. d_{P-1}); the value part is ``_run``'s.  A tangent that is
-    None is +0.0 everywhere: where every operand's d_j is 0.0 the result's d_j is +0.0 and the formula is not evaluated -- structurally
-    (None) or, point by point, through ``np.where`` -- so a sqrt(0) or a division by zero in a part of the expression that does not read
-    p[j] cannot make its tangent NaN."""
+# The tangent rules of include/hommx_hip.h (hommx_expand_tangents), as the kernel applies them: d_j of an instruction's result from the
+# d_j of its operands -- p for the operand a of a one-operand instruction, (p, q) for (a, b), b on top; v: the instruction's value.  An
+# instruction that is not here (a comparison, AND, OR, NOT) is piecewise constant
+_TANGENT = {
+    OP_NEG: lambda a, v, p: -p,
+    OP_ABS: lambda a, v, p: np.where(a < 0.0, -p, p),
+    OP_SQRT: lambda a, v, p: p / (_TWO * v),
+    OP_SIN: lambda a, v, p: np.cos(a) * p,
+    OP_COS: lambda a, v, p: -(np.sin(a) * p),
+    OP_TAN: lambda a, v, p: p * (_ONE + v * v),
+    OP_EXP: lambda a, v, p: v * p,
+    OP_LOG: lambda a, v, p: p / a,
+    OP_TANH: lambda a, v, p: p * (_ONE + -(v * v)),
+    OP_ADD: lambda a, b, v, p, q: p + q,
+    OP_SUB: lambda a, b, v, p, q: p + (-q),
+    OP_MUL: lambda a, b, v, p, q: a * q + p * b,
+    OP_DIV: lambda a, b, v, p, q: (p + -(v * q)) / b,
+    OP_MIN: lambda a, b, v, p, q: np.where(b < a, q, p),
+    OP_MAX: lambda a, b, v, p, q: np.where(b > a, q, p),
+}
+
+
+def _run(ops, consts, n_comp: int, x, y, n_params: int = 0, n_fields: int = 0) -> tuple[list, list]:
+    """Interpret a program with NumPy on x[3 + n_fields, ...] (the midpoint, then the fields: ``X k`` reads row k) and y[d, ...]
+    (broadcast against each other), in forward mode over its P = n_params + n_fields differentiable slots, the parameters, then the
+    fields (``CONST k``, k < n_params, seeds slot k; ``X k``, k >= 3, slot ``n_params + k - 3``): (values[n_comp],
+    tangents[n_comp][P]), each operation the separately rounded IEEE operation k_expand_program<P> performs.  Like the kernel's, the
+    value pass is the pass without slots: a stack entry is (v, [d_0 .. d_{P-1}]) and v is computed in one place whatever P is.
+
+    A tangent that is None is +0.0 everywhere: where every operand's d_j is 0.0 the result's d_j is +0.0 and the formula is not
+    evaluated -- structurally (None) or, point by point, through ``np.where`` -- so a sqrt(0) or a division by zero in a part of the
+    expression that does not read slot j cannot make its tangent NaN."""
     P = n_params + n_fields
     stack, out_v, out_d = [], [None] * n_comp, [None] * n_comp
-    one, zero, two = np.float64(1.0), np.float64(0.0), np.float64(2.0)
-    flag = lambda m: np.where(m, one, zero)
-    none = [None] * P
 
-    def rule(operands, formula):
+    def rule(formula, *operands):
         """d_j of a result from the d_j of its operands: +0.0 where all of them are 0.0, else formula(*operands)."""
-        if all(d is None for d in operands):
+        if formula is None or all(d is None for d in operands):
             return None
-        full = [zero if d is None else d for d in operands]
+        full = [_ZERO if d is None else d for d in operands]
         dead = full[0] == 0.0
         for d in full[1:]:
             dead = dead & (d == 0.0)
-        return np.where(dead, zero, formula(*full))
+        return np.where(dead, _ZERO, formula(*full))
 
     for op, k in ops:
         if op == OP_CONST:
-            stack.append((np.float64(consts[k]), [one if (k == j and k < n_params) else None for j in range(P)]))
+            stack.append((np.float64(consts[k]), [_ONE if (k == j and k < n_params) else None for j in range(P)]))
         elif op == OP_X:
-            stack.append((np.asarray(x[k], dtype=np.float64), [one if (k >= 3 and j == n_params + k - 3) else None for j in range(P)]))
+            stack.append((np.asarray(x[k], dtype=np.float64), [_ONE if (k >= 3 and j == n_params + k - 3) else None for j in range(P)]))
         elif op == OP_Y:
-            stack.append((np.asarray(y[k], dtype=np.float64), list(none)))
+            stack.append((np.asarray(y[k], dtype=np.float64), [None] * P))
         elif op == OP_DUP:
             stack.append((stack[-1][0], list(stack[-1][1])))
         elif op == OP_STORE:
             out_v[k], out_d[k] = stack.pop()
         elif op == OP_SELECT:
-            (b, db), (a, da), (c, _) = stack.pop(), stack.pop(), stack.pop()
+            (b, db), (a, da), (c, _) = stack.pop(), stack.pop(), stack.pop()  # a condition carries no tangent
             pick = c != 0.0
-            stack.append((np.where(pick, a, b), [rule((da[j], db[j]), lambda p, q: np.where(pick, p, q)) for j in range(P)]))
-        elif op == OP_NOT:
-            a, _ = stack.pop()
-            stack.append((flag(a == 0.0), list(none)))
-        elif op == OP_NEG:
+            stack.append((np.where(pick, a, b), [rule(lambda p, q: np.where(pick, p, q), da[j], db[j]) for j in range(P)]))
+        elif _POPS.get(op, 2) == 1:
             a, da = stack.pop()
-            stack.append((-a, [rule((da[j],), lambda p: -p) for j in range(P)]))
-        elif op == OP_ABS:
-            a, da = stack.pop()
-            stack.append((np.abs(a), [rule((da[j],), lambda p: np.where(a < 0.0, -p, p)) for j in range(P)]))
-        elif op in _MATH_NUMPY:
-            a, da = stack.pop()
-            v = _MATH_NUMPY[op](a)
-            if op == OP_SQRT:
-                f = lambda p: p / (two * v)
-            elif op == OP_SIN:
-                f = lambda p: np.cos(a) * p
-            elif op == OP_COS:
-                f = lambda p: -(np.sin(a) * p)
-            elif op == OP_TAN:
-                f = lambda p: p * (one + v * v)
-            elif op == OP_EXP:
-                f = lambda p: v * p
-            elif op == OP_LOG:
-                f = lambda p: p / a
-            else:  # OP_TANH
-                f = lambda p: p * (one + -(v * v))
-            stack.append((v, [rule((da[j],), f) for j in range(P)]))
+            v, f = _unary(op, a), _TANGENT.get(op)
+            stack.append((v, [rule(f and (lambda p: f(a, v, p)), da[j]) for j in range(P)]))
         else:
             (b, db), (a, da) = stack.pop(), stack.pop()
-            v = _binary(op, a, b, flag)
-            if op == OP_ADD:
-                f = lambda p, q: p + q
-            elif op == OP_SUB:
-                f = lambda p, q: p + (-q)
-            elif op == OP_MUL:
-                f = lambda p, q: a * q + p * b
-            elif op == OP_DIV:
-                f = lambda p, q: (p + -(v * q)) / b
-            elif op == OP_MIN:
-                f = lambda p, q: np.where(b < a, q, p)
-            elif op == OP_MAX:
-                f = lambda p, q: np.where(b > a, q, p)
-            else:  # comparisons, AND, OR: piecewise constant
-                f = None
-            stack.append((v, list(none) if f is None else [rule((da[j], db[j]), f) for j in range(P)]))
+            v, f = _binary(op, a, b), _TANGENT.get(op)
+            stack.append((v, [rule(f and (lambda p, q: f(a, b, v, p, q)), da[j], db[j]) for j in range(P)]))
     return out_v, out_d
 
 
@@ -534,7 +509,7 @@ class Expression:
             raise ValueError(f"the expression reads y[{self.n_y - 1}]; the fast variable has {y.shape[0]} components")
         shape = np.broadcast(x[0], y[0]).shape
         with np.errstate(all="ignore"):
-            out = _run(self._ops.tolist(), self._consts, self.n_comp, x, y)
+            out, _ = _run(self._ops.tolist(), self._consts, self.n_comp, x, y)
         return [np.broadcast_to(v, shape) for v in out]
 
     def _check_rows(self, rows: int):
@@ -576,7 +551,7 @@ class Expression:
 
     def host_tangents(self, x: np.ndarray, yq: np.ndarray, w: np.ndarray) -> np.ndarray:
         """The derivatives of ``host_stream`` with respect to the parameters, then the fields (of a cell: its own value),
-        dirs[N, n_params + n_fields, n_el(, n_comp)], exactly as the device's forward-mode pass forms them (``_run_tangent``: the rules),
+        dirs[N, n_params + n_fields, n_el(, n_comp)], exactly as the device's forward-mode pass forms them (``_TANGENT``: the rules),
         ``acc_j = acc_j + w[q] * d_j`` with q ascending, from 0."""
         if self.n_params + self.n_fields == 0:
             raise ValueError("the expression has no parameters (p=[...])")
@@ -589,8 +564,8 @@ class Expression:
         ops = self._ops.tolist()
         for q in range(nq):
             with np.errstate(all="ignore"):
-                _, dv = _run_tangent(ops, self._consts, self.n_comp, self.n_params, x.T[:, :, None],
-                                     np.moveaxis(yq[:, q, :], -1, 0)[:, None, :], self.n_fields)
+                _, dv = _run(ops, self._consts, self.n_comp, x.T[:, :, None], np.moveaxis(yq[:, q, :], -1, 0)[:, None, :], self.n_params,
+                             self.n_fields)
             for j in range(P):
                 for c in range(self.n_comp):
                     dj = np.float64(0.0) if dv[c][j] is None else dv[c][j]

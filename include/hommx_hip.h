@@ -357,7 +357,8 @@ int hommx_expand_source_device(hommx_plan* plan, int64_t n_cells, const hommx_co
 /*
  * The derivatives of the element stream of a HOMMX_COEF_PROGRAM source with respect to its parameters and its fields (the n_tan =
  * n_params + n_fields differentiable slots, the parameters first; 1 <= n_tan <= HOMMX_PROGRAM_MAX_PARAMS), in forward mode: ONE pass of
- * the interpreter (csrc/coef_program.hip, k_expand_program_tangent) carries (v, d_0 .. d_{P-1}) per stack entry and yields
+ * the interpreter (csrc/coef_program.hip, k_expand_program<P>; the value pass is its P = 0) carries (v, d_0 .. d_{P-1}) per stack
+ * entry and yields
  *   coef_out [n_cells][n_el][n_comp]             the stream of hommx_expand_source, bit for bit (or NULL: not wanted)
  *   dirs_out [n_cells][n_tan][n_el][n_comp]      d coef / d slot j (p[j], or field j - n_params of the cell itself), the layout of
  *                                                per-cell directions (hommx_sens_args, per_cell == 1)

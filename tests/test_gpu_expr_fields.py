@@ -164,7 +164,7 @@ def test_tangents_of_a_math_function_are_within_its_ulps(name, f):
     print(f"{name} {f}: max |device - host| of the tangent = {err:.3e}, tolerance {tol:.3e} (U = {U}, K = {K(U)}, n_q = {len(w)}, D = {D:.4f})")
     assert np.all(np.isfinite(host)) and np.abs(host).max() > 0.05
     assert err <= tol
-    assert np.array_equal(coef, G._plan(name).expand(stream))  # the value part is k_expand_program's, whatever the functions
+    assert np.array_equal(coef, G._plan(name).expand(stream))  # the value part is the value pass's (k_expand_program<0>), whatever the functions
 
 
 # -- 3. a field with one value in every cell is a parameter ------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""Parameters of expression coefficients on an MI355X (-m gpu): the forward-mode interpreter k_expand_program_tangent against
+"""Parameters of expression coefficients on an MI355X (-m gpu): the forward-mode passes of the interpreter k_expand_program<P> against
 ``Expression.host_tangents`` (bitwise for exactly rounded operations, to the accuracy of the device's math functions otherwise), the
 derivative families with ``directions="parameters"`` against the same calls on the sampled stream and sampled tangents (bitwise, host
 and device entries, any chunking), against ``TwoPhase``, a failing cell, and the solver classes end to end against central differences
@@ -149,7 +149,7 @@ def test_tangents_of_a_math_function_are_within_its_ulps(name, f):
     print(f"{name} {f}: max |device - host| of the tangent = {err:.3e}, tolerance {tol:.3e} (U = {U}, K = {K(U)}, n_q = {len(w)}, D = {D:.4f})")
     assert np.all(np.isfinite(host)) and np.abs(host).max() > 0.05
     assert err <= tol
-    assert np.array_equal(coef, G._plan(name).expand(stream))  # the value part is k_expand_program's, whatever the functions
+    assert np.array_equal(coef, G._plan(name).expand(stream))  # the value part is the value pass's (k_expand_program<0>), whatever the functions
 
 
 # -- 3. the derivative families ----------------------------------------------------------------------------------------------------------
