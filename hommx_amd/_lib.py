@@ -31,6 +31,7 @@ SENS_MAX_DIRS = 8  # HOMMX_SENS_MAX_DIRS
 PROGRAM_MAX_PARAMS = 4  # HOMMX_PROGRAM_MAX_PARAMS
 PROGRAM_MAX_FIELDS = 4  # HOMMX_PROGRAM_MAX_FIELDS
 DIRS_PARAMETERS = 2  # HOMMX_DIRS_PARAMETERS: per_cell of SensArgs / Sens2Args, the directions are the program's parameter tangents
+DIRS_PARAMETERS_CURVATURE = 3  # HOMMX_DIRS_PARAMETERS_CURVATURE: per_cell of Sens2Args, d2A takes the curvature term as well (the Hessian)
 
 
 class PlanDesc(C.Structure):
@@ -193,6 +194,8 @@ def _prototypes() -> dict:
         "hommx_expand_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp]),
         "hommx_expand_tangents": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp]),
         "hommx_expand_tangents_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, vp]),
+        "hommx_expand_second_tangents": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, vp]),
+        "hommx_expand_second_tangents_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, vp, vp]),
         "hommx_reconstruct_batch": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_reconstruct_batch_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hommx_reconstruct_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),

@@ -598,22 +598,27 @@ class MicroCellPlan:
         return Sensitivities(dA, grad, A, info)
 
     def second_sensitivities(self, coef, M: np.ndarray | None = None, directions=None, per_cell: bool = False,
-                             first: bool = False) -> SecondSensitivities:
+                             first: bool = False, curvature: bool = False) -> SecondSensitivities:
         """Second derivatives of A_H along coefficient directions (hommx_second_sensitivity_source): ``coef`` an array or a ``CoefStream``,
         M and ``directions`` (shared, or ``per_cell``) as ``sensitivities`` takes them -> ``d2A[N_c, n_dirs, n_dirs, t, t]``, exact on the
         discrete problem: the derivative of every canonical corrector along a direction is the corrector of a polarisation load, which the
         plan solves on the route ``load_kernel`` names (needs ``load_solve=True`` on the frontal mesh route).  ``first``: ``dA[N_c, n_dirs, t, t]`` of the same
         call as well.  One canonical pass and one load solve per direction; correctors and loads never leave the device; the batch runs in
         the chunks of ``reconstruct``.  ``directions="parameters"``: as in ``sensitivities``; d2A holds the second derivatives along the
-        parameter tangents, which is the Hessian in the parameters when the expression is affine in them (``affine_in_parameters``)."""
+        parameter tangents, which is the Hessian in the parameters when the expression is affine in them (``affine_in_parameters``).
+        ``curvature=True`` (with ``directions="parameters"`` only): d2A also takes dA_H along the second derivatives of the stream
+        (``expand_second_tangents``), formed on the device in the same pass -- the Hessian of A_H in the parameters and fields for any
+        expression (HOMMX_DIRS_PARAMETERS_CURVATURE)"""
         stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
         parameters = isinstance(directions, str) and directions == "parameters"
+        if curvature and not parameters:
+            raise ValueError('curvature=True needs directions="parameters": the curvature term is that of the program\'s own parameters')
         nd, dirs = (self._parameter_count(coef), None) if parameters else (0, None)
         nc = self._check_stream(stream)
         if directions is None:
             raise ValueError("directions is required")
         if parameters:
-            per_cell = _lib.DIRS_PARAMETERS
+            per_cell = _lib.DIRS_PARAMETERS_CURVATURE if curvature else _lib.DIRS_PARAMETERS
         else:
             dirs, nd = self._check_directions(directions, nc, per_cell)
         d2A = np.empty((nc, nd, nd, self.t, self.t), dtype=np.float64)
@@ -749,7 +754,31 @@ class MicroCellPlan:
             _lib.check(self._lib.hommx_expand_tangents(self._h, nc, C.byref(src), coef.ctypes.data, dirs.ctypes.data), "hommx_expand_tangents")
         return coef, dirs
 
+    def expand_second_tangents(self, stream: CoefStream) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(coef, dirs, curv[N_c, n_pairs, n_el(, n_comp)]) of the program stream of an expression with parameters or fields
+        (hommx_expand_second_tangents): coef and dirs are those of ``expand_tangents``, bit for bit, and curv the second derivatives of
+        the stream with respect to the pairs (a, b), a <= b, of the differentiable slots in the order of ``Expression.pairs``, formed
+        in one second-order forward-mode pass on the device (one per pair of slots for 3 or 4 slots).  curv equals
+        ``Expression.host_second_tangents`` bit for bit for exactly rounded operations."""
+        n_tan = self._parameter_count(stream)
+        nc = self._check_stream(stream)
+        el = (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
+        coef, dirs = np.empty((nc,) + el, dtype=np.float64), np.empty((nc, n_tan) + el, dtype=np.float64)
+        curv = np.empty((nc, n_tan * (n_tan + 1) // 2) + el, dtype=np.float64)
+        if nc:
+            src = stream.coef_source()
+            _lib.check(self._lib.hommx_expand_second_tangents(self._h, nc, C.byref(src), coef.ctypes.data, dirs.ctypes.data, curv.ctypes.data),
+                       "hommx_expand_second_tangents")
+        return coef, dirs, curv
+
     # -- device pointers (torch tensors or raw ints), asynchronous --------------------------------
+    def expand_second_tangents_device(self, n_cells: int, source: "_lib.CoefSource", coef_ptr: int | None, dirs_ptr: int | None, curv_ptr: int,
+                                      stream: int | None = None):
+        """Device-pointer form of ``expand_second_tangents`` (hommx_expand_second_tangents_device), asynchronous on ``stream``;
+        ``coef_ptr`` / ``dirs_ptr`` None: not written."""
+        _lib.check(self._lib.hommx_expand_second_tangents_device(self._h, int(n_cells), C.byref(source), coef_ptr or None, dirs_ptr or None,
+                                                                 curv_ptr, stream or None), "hommx_expand_second_tangents_device")
+
     def expand_tangents_device(self, n_cells: int, source: "_lib.CoefSource", coef_ptr: int | None, dirs_ptr: int, stream: int | None = None):
         """Device-pointer form of ``expand_tangents`` (hommx_expand_tangents_device), asynchronous on ``stream``; ``coef_ptr`` None: the
         tangents alone."""
@@ -814,12 +843,17 @@ class MicroCellPlan:
 
     def second_sensitivities_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, n_dirs: int, dirs_ptr: int, d2A_ptr: int,
                                     per_cell: bool = False, dA_ptr: int | None = None, A_ptr: int | None = None, info_ptr: int | None = None,
-                                    stream: int | None = None):
+                                    stream: int | None = None, curvature: bool = False):
         """Device-pointer form of ``second_sensitivities`` (hommx_second_sensitivity_source_device), asynchronous on ``stream``: ``source`` =
         ``CoefStream.coef_source(upload)`` with device addresses; dirs[n_dirs, n_el, n_comp] or, ``per_cell``, [n_cells, n_dirs, n_el, n_comp]
         -> d2A[n_cells, n_dirs, n_dirs, t, t]; dA[n_cells, n_dirs, t, t] on request.  ``per_cell="parameters"``: as in
-        ``sensitivities_device``."""
-        args = _lib.Sens2Args(int(n_dirs), _per_cell_code(per_cell), dirs_ptr or None, d2A_ptr or None, dA_ptr or None, A_ptr or None, info_ptr or None)
+        ``sensitivities_device``; with ``curvature=True`` d2A takes the curvature term as well (HOMMX_DIRS_PARAMETERS_CURVATURE)."""
+        code = _per_cell_code(per_cell)
+        if curvature:
+            if code != _lib.DIRS_PARAMETERS:
+                raise ValueError('curvature=True needs per_cell="parameters": the curvature term is that of the program\'s own parameters')
+            code = _lib.DIRS_PARAMETERS_CURVATURE
+        args = _lib.Sens2Args(int(n_dirs), code, dirs_ptr or None, d2A_ptr or None, dA_ptr or None, A_ptr or None, info_ptr or None)
         _lib.check(self._lib.hommx_second_sensitivity_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
                                                                     stream or None),
                    "hommx_second_sensitivity_source_device")

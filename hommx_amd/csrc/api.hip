@@ -112,7 +112,12 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 // B_SENS2: the polarisation loads of one direction of a second-derivative chunk (t n_el t doubles per cell)
 // B_TANGENT: the tangents of one chunk of a program source, one stream per differentiable slot (its parameters, then its fields):
 //            [nc][n_params + n_fields][n_el][n_comp] (grown with B_EXPAND, by stream_chunk)
-enum { B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, B_SENS2, B_TANGENT, N_BUF };
+// B_CURVATURE: the second-order streams of such a chunk, one per pair a <= b of the slots, [nc][n_pairs][n_el][n_comp], and behind
+//            them, at [chunk][n_pairs][n_el][n_comp], the first derivatives of A_H along them, [nc][n_pairs][t][t] (stream_chunk too)
+enum {
+  B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, B_SENS2, B_TANGENT, B_CURVATURE,
+  N_BUF
+};
 
 }  // namespace
 
@@ -391,6 +396,17 @@ int64_t per_cell_doubles(const hommx_plan* p, const hommx_coef_source& s) {
 const double* program_rows(const hommx_coef_source& s, int64_t c0) { return s.params + c0 * hommx::program_row_doubles(s.n_fields); }
 // the differentiable slots of a checked program source: its parameters, then its fields
 int source_tangents(const hommx_coef_source& s) { return s.program->n_params + s.n_fields; }
+// ... and the pairs a <= b of n_tan of them: the second-order streams
+int tangent_pairs(int n_tan) { return n_tan * (n_tan + 1) / 2; }
+// the maximal stack depth of a checked program (program_check has simulated it): the rows of the second-order kernel's stack
+int program_depth(const hommx_coef_program& g) {
+  int depth = 0, deepest = 0;
+  for (int pc = 0; pc < g.n_ops; ++pc) {
+    depth += hommx::op_pushes(g.ops[2 * pc]) - hommx::op_pops(g.ops[2 * pc]);
+    deepest = std::max(deepest, depth);
+  }
+  return deepest;
+}
 int64_t table_doubles(const hommx_plan* p, const hommx_coef_source& s) {
   return p->n_el * s.n_q * (s.form == HOMMX_COEF_PROGRAM ? p->desc.dim : 1);
 }
@@ -398,24 +414,27 @@ int64_t table_doubles(const hommx_plan* p, const hommx_coef_source& s) {
 // -- the element stream of a source ---------------------------------------------------------------------------------------------------
 // Cells per chunk of a source, given the `want` of the caller: a sampler form is expanded into the plan's element stream, at most 1 GiB of
 // it (at least one cell), which is grown here; a sampled stream has no such limit.  n_tan: the parameter tangents of a program are
-// expanded beside it (B_TANGENT), and the 1 GiB counts the 1 + n_tan streams
-int64_t stream_cells(const hommx_plan* p, int64_t want, int n_tan = 0) {
-  return std::min(want, std::max<int64_t>((1ll << 27) / std::max<int64_t>(p->n_el * p->ks.n_comp * (1 + n_tan), 1), 1));
+// expanded beside it (B_TANGENT), and the 1 GiB counts the 1 + n_tan streams; n_curv: its second-order streams as well (B_CURVATURE,
+// with the t x t first derivatives along them behind), and the 1 GiB counts the 1 + n_tan + n_curv streams
+int64_t stream_cells(const hommx_plan* p, int64_t want, int n_tan = 0, int n_curv = 0) {
+  return std::min(want, std::max<int64_t>((1ll << 27) / std::max<int64_t>(p->n_el * p->ks.n_comp * (1 + n_tan + n_curv), 1), 1));
 }
-int stream_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t want, int64_t* chunk, int n_tan = 0) {
+int stream_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t want, int64_t* chunk, int n_tan = 0, int n_curv = 0) {
   *chunk = want;
   if (s.form == HOMMX_COEF_SAMPLED) return HOMMX_OK;
-  *chunk = stream_cells(p, want, n_tan);
+  *chunk = stream_cells(p, want, n_tan, n_curv);
   const size_t stream = sizeof(double) * *chunk * p->n_el * p->ks.n_comp;
   if (int rc = grow(p->buf[B_TANGENT], stream * n_tan)) return rc;
+  if (int rc = grow(p->buf[B_CURVATURE], (stream + sizeof(double) * *chunk * p->ks.t * p->ks.t) * n_curv)) return rc;
   return grow(p->buf[B_EXPAND], stream);
 }
 
 // *stream: the element stream of cells [c0, c0 + nc) of a source on the device.  A sampled stream is a view of the caller's; a sampler
 // form is expanded into the plan's element stream (nc <= the chunk of stream_chunk) or, if given, into `into`; `tangents`: a program's
-// parameter tangents as well, in the same launch -- and then a null `stream`: the tangents alone, no element stream is written
+// parameter tangents as well, in the same launch -- and then a null `stream`: the tangents alone, no element stream is written;
+// `curvature`: the second-order pass instead, which writes the second-order streams and, where given, the stream and the tangents
 int expand_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t c0, int64_t nc, hipStream_t st, const double** stream,
-                 double* into = nullptr, double* tangents = nullptr) {
+                 double* into = nullptr, double* tangents = nullptr, double* curvature = nullptr) {
   const int n_comp = p->ks.n_comp;
   if (s.form == HOMMX_COEF_SAMPLED) {
     *stream = s.coef + c0 * p->n_el * n_comp;
@@ -424,6 +443,9 @@ int expand_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t c0, int64_t 
   double* dst = !stream ? nullptr : into ? into : static_cast<double*>(p->buf[B_EXPAND].p);
   if (s.form == HOMMX_COEF_TWO_PHASE)
     HIP_TRY(hommx::launch_expand_two_phase(s.mask, s.values + c0 * 2 * n_comp, dst, p->n_el, n_comp, nc, st));
+  else if (s.form == HOMMX_COEF_PROGRAM && curvature)
+    HIP_TRY(hommx::launch_expand_program2(program_args(*s.program), s.program->n_params, s.n_fields, program_depth(*s.program), s.table,
+                                          s.weights, s.n_q, p->desc.dim, program_rows(s, c0), dst, tangents, curvature, p->n_el, nc, st));
   else if (s.form == HOMMX_COEF_PROGRAM)
     HIP_TRY(hommx::launch_expand_program(program_args(*s.program), s.program->n_params, s.n_fields, s.table, s.weights, s.n_q, p->desc.dim,
                                          program_rows(s, c0), dst, tangents, p->n_el, nc, st));
@@ -886,6 +908,47 @@ int hommx_expand_tangents(hommx_plan* p, int64_t n_cells, const hommx_coef_sourc
   return HOMMX_OK;
 }
 
+int hommx_expand_second_tangents_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, double* d_coef_out, double* d_dirs_out,
+                                        double* d_curv_out, void* stream) {
+  if (int rc = open_call(p, n_cells, d_curv_out, "curv_out", true, [&] { return tangents_check(p, src); }); rc != GO) return rc;
+  const hommx_coef_source s = source_of_form(*src);
+  const int n_tan = source_tangents(s), n_pairs = tangent_pairs(n_tan);
+  const int64_t per = p->n_el * p->ks.n_comp;
+  const int64_t chunk = stream_cells(p, n_cells, n_tan, n_pairs);  // straight into the caller's arrays, in launches of at most 1 GiB of streams
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    const double* at = nullptr;
+    if (int rc = expand_chunk(p, s, c0, std::min(chunk, n_cells - c0), reinterpret_cast<hipStream_t>(stream), d_coef_out ? &at : nullptr,
+                              d_coef_out ? d_coef_out + c0 * per : nullptr, d_dirs_out ? d_dirs_out + c0 * n_tan * per : nullptr,
+                              d_curv_out + c0 * n_pairs * per))
+      return rc;
+  }
+  return HOMMX_OK;
+}
+
+int hommx_expand_second_tangents(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, double* coef_out, double* dirs_out,
+                                 double* curv_out) {
+  if (int rc = open_call(p, n_cells, curv_out, "curv_out", false, [&] { return tangents_check(p, src); }); rc != GO) return rc;
+  const hommx_coef_source s = source_of_form(*src);
+  const int n_tan = source_tangents(s), n_pairs = tangent_pairs(n_tan);
+  const int64_t per = p->n_el * p->ks.n_comp;
+  hommx_coef_source ds;
+  const void* none = nullptr;
+  if (int rc = stage_source(p, n_cells, s, {nullptr, 0, &none}, &ds)) return rc;
+  int64_t chunk = 0;
+  if (int rc = stream_chunk(p, s, n_cells, &chunk, n_tan, n_pairs)) return rc;
+  double *d_dirs = static_cast<double*>(p->buf[B_TANGENT].p), *d_curv = static_cast<double*>(p->buf[B_CURVATURE].p);
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    const int64_t nc = std::min(chunk, n_cells - c0);
+    const double* d_coef = nullptr;
+    if (int rc = expand_chunk(p, ds, c0, nc, nullptr, coef_out ? &d_coef : nullptr, nullptr, dirs_out ? d_dirs : nullptr, d_curv)) return rc;
+    if (coef_out) HIP_TRY(hipMemcpyAsync(coef_out + c0 * per, d_coef, sizeof(double) * nc * per, hipMemcpyDeviceToHost, nullptr));
+    if (dirs_out) HIP_TRY(hipMemcpyAsync(dirs_out + c0 * n_tan * per, d_dirs, sizeof(double) * nc * n_tan * per, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpyAsync(curv_out + c0 * n_pairs * per, d_curv, sizeof(double) * nc * n_pairs * per, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+  }
+  return HOMMX_OK;
+}
+
 int hommx_solve_batch_correctors(hommx_plan* p, int64_t n_cells, const double* coef, const double* M, double* A_eff,
                                  double* correctors, int32_t* info) {
   if (int rc = open_call(p, n_cells, coef && A_eff && correctors, "coef / A_eff / correctors"); rc != GO) return rc;
@@ -999,6 +1062,7 @@ struct Chunk {
   const double *coef, *M;
   const hommx_coef_source* src;
   Args a;
+  double* curv = nullptr;  // HOMMX_DIRS_PARAMETERS_CURVATURE: the second-order streams of the chunk (B_CURVATURE), else null
 };
 
 using ChunkRule = int64_t (*)(const hommx_plan*, int64_t, size_t);  // recon_chunk or load_chunk
@@ -1014,12 +1078,14 @@ using ChunkRule = int64_t (*)(const hommx_plan*, int64_t, size_t);  // recon_chu
 // B_OUT chunk by chunk, so device memory is bounded by the chunk, whose bytes per cell count both blocks.
 // tangents (HOMMX_DIRS_PARAMETERS): a pointer member of v.a that receives, per chunk, the parameter tangents of the program source --
 // [nc][n_params + n_fields][n_el][n_comp] in B_TANGENT, formed by the launch that expands the stream; their bytes count as scratch of the chunk
+// curvature (HOMMX_DIRS_PARAMETERS_CURVATURE, with tangents): that launch is the second-order pass and also forms the second-order
+// streams of the chunk, [nc][n_pairs][n_el][n_comp] in B_CURVATURE (v.curv), whose bytes count as scratch too
 template <typename Args, size_t NI, size_t NO, typename Run>
 int derived_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, Chunk<Args>& v, const CellArray (&ins)[NI],
                  const CellArray (&outs)[NO], int32_t** info, size_t scratch, ChunkRule rule, bool device, hipStream_t st, Run run,
-                 const double** tangents = nullptr) {
-  const int n_tan = tangents ? source_tangents(s) : 0;
-  scratch += sizeof(double) * n_tan * p->n_el * p->ks.n_comp;
+                 const double** tangents = nullptr, bool curvature = false) {
+  const int n_tan = tangents ? source_tangents(s) : 0, n_curv = curvature ? tangent_pairs(n_tan) : 0;
+  scratch += sizeof(double) * (n_tan * p->n_el * p->ks.n_comp + n_curv * (p->n_el * p->ks.n_comp + p->ks.t * p->ks.t));
   constexpr size_t N[2] = {NI + 2, NO + 1};
   constexpr size_t NMAX = std::max(N[0], N[1]);
   v.coef = s.coef;
@@ -1044,13 +1110,13 @@ int derived_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, con
   char* dev[2][NMAX] = {};
   int64_t chunk = 0;
   if (device) {
-    if (int rc = stream_chunk(p, s, rule(p, n_cells, scratch), &chunk, n_tan)) return rc;
+    if (int rc = stream_chunk(p, s, rule(p, n_cells, scratch), &chunk, n_tan, n_curv)) return rc;
   } else {
     const void* d_shared = nullptr;
     const hommx::HostPiece more{shared ? shared->get() : nullptr, shared ? shared->elem * shared->n : 0, &d_shared};
     if (int rc = stage_source(p, n_cells, s, more, &ds)) return rc;
     if (shared) shared->set(d_shared);
-    if (int rc = stream_chunk(p, s, rule(p, n_cells, per_cell), &chunk, n_tan)) return rc;
+    if (int rc = stream_chunk(p, s, rule(p, n_cells, per_cell), &chunk, n_tan, n_curv)) return rc;
     for (int io = 0; io < 2; ++io) {
       size_t bytes[NMAX] = {};
       for (size_t k = 0; k < N[io]; ++k) bytes[k] = cell[io][k] * chunk;
@@ -1068,8 +1134,9 @@ int derived_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, con
         if (!device && !io && at) HIP_TRY(hipMemcpy(at, user[io][k] + c0 * cell[io][k], nc * cell[io][k], hipMemcpyHostToDevice));
       }
     double* tan = n_tan ? static_cast<double*>(p->buf[B_TANGENT].p) : nullptr;
+    v.curv = n_curv ? static_cast<double*>(p->buf[B_CURVATURE].p) : nullptr;
     if (!v.coef)
-      if (int rc = expand_chunk(p, ds, c0, nc, st, &v.coef, nullptr, tan)) return rc;
+      if (int rc = expand_chunk(p, ds, c0, nc, st, &v.coef, nullptr, tan, v.curv)) return rc;
     if (tan) *tangents = tan;
     if (int rc = run(nc, chunk, v)) return rc;
     if (device) continue;
@@ -1193,8 +1260,10 @@ int sens_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_sens_ar
   return HOMMX_OK;
 }
 
-// HOMMX_DIRS_PARAMETERS: the directions are the parameter tangents of the source's program; `s` has passed coef_check
-bool parameter_dirs(int32_t per_cell) { return per_cell == HOMMX_DIRS_PARAMETERS; }
+// HOMMX_DIRS_PARAMETERS: the directions are the parameter tangents of the source's program; `s` has passed coef_check.
+// HOMMX_DIRS_PARAMETERS_CURVATURE (hommx_sens2_args only): the same, and d2A also takes dA_H along the second-order streams
+bool curvature_dirs(int32_t per_cell) { return per_cell == HOMMX_DIRS_PARAMETERS_CURVATURE; }
+bool parameter_dirs(int32_t per_cell) { return per_cell == HOMMX_DIRS_PARAMETERS || curvature_dirs(per_cell); }
 int parameter_dirs_check(const hommx_coef_source* s, int32_t n_dirs, const void* dirs) {
   if (s->form != HOMMX_COEF_PROGRAM) return fail(HOMMX_EINVAL, "HOMMX_DIRS_PARAMETERS needs a HOMMX_COEF_PROGRAM source, got form %d", s->form);
   if (int rc = tangent_slots_check(s, "HOMMX_DIRS_PARAMETERS")) return rc;
@@ -1210,6 +1279,9 @@ int parameter_dirs_check(const hommx_coef_source* s, int32_t n_dirs, const void*
 int sens_checks(const hommx_coef_source* s, const hommx_sens_args* a) {
   if (a->n_dirs < 0 || a->n_dirs > HOMMX_SENS_MAX_DIRS)
     return fail(HOMMX_EINVAL, "n_dirs must be 0 .. %d, got %d", HOMMX_SENS_MAX_DIRS, a->n_dirs);
+  if (curvature_dirs(a->per_cell))
+    return fail(HOMMX_EINVAL, "HOMMX_DIRS_PARAMETERS_CURVATURE is a value of per_cell in hommx_sens2_args only: first derivatives have no "
+                              "curvature term (use HOMMX_DIRS_PARAMETERS)");
   if (parameter_dirs(a->per_cell))
     if (int rc = parameter_dirs_check(s, a->n_dirs, a->dirs)) return rc;
   if (a->n_dirs > 0 && !((a->dirs || parameter_dirs(a->per_cell)) && a->dA)) return fail(HOMMX_EINVAL, "n_dirs > 0 needs both dirs and dA");
@@ -1386,6 +1458,14 @@ int sens2_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_sens2_
     if (int rc = load_correctors(p, nc, chunk, v.coef, v.M, hommx::LoadOverride{k.P, t, true}, st, corr_b)) return rc;  // t per-cell loads
     HIP_TRY(hommx::launch_sens2(k, nc, st));
   }
+  if (v.curv) {
+    // the curvature term: dA_H along the second-order streams of the chunk, every pair a <= b in one launch of k_sens (it loops over its
+    // directions at run time; HOMMX_SENS_MAX_DIRS bounds the ABI, not the kernel), behind the streams; then d2A[a][b] += dA_H[pair(a, b)]
+    const int n_pairs = tangent_pairs(a.n_dirs);
+    double* dAk = v.curv + chunk * n_pairs * p->n_el * p->ks.n_comp;
+    HIP_TRY(hommx::launch_sensitivity(sens_dirs_args(p, corr, v.M, n_pairs, 1, v.curv, dAk), nc, st));
+    HIP_TRY(hommx::launch_sens2_add_curvature(a.d2A, dAk, a.n_dirs, t, nc, st));
+  }
   return HOMMX_OK;
 }
 
@@ -1417,7 +1497,7 @@ int sens2_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const
   const CellArray out[] = {{&a.d2A, a.n_dirs * a.n_dirs * tt}, {&a.A_eff, tt, KEPT}, {&a.dA, a.n_dirs * tt}};
   return derived_call(p, n_cells, s, M, v, in, out, &a.info, sens2_extra(p), load_chunk, device, st,
                       [&](int64_t nc, int64_t chunk, const Chunk<hommx_sens2_args>& c) { return sens2_run(p, nc, chunk, c, st); },
-                      parameter_dirs(a.per_cell) ? &a.dirs : nullptr);
+                      parameter_dirs(a.per_cell) ? &a.dirs : nullptr, curvature_dirs(a.per_cell));
 }
 
 }  // namespace

@@ -50,4 +50,13 @@ hipError_t launch_expand_program(const ProgramArgs& prog, int n_params, int n_fi
                                  int n_q, int dim, const double* d_rows, double* d_coef, double* d_dirs, long long n_el, long long ncells,
                                  hipStream_t stream);
 
+// The second-order forward mode, in the same pass: curv[cell][pair][el][comp] = d2 coef / d slot_a d slot_b for the pairs (a, b),
+// a <= b, of the n_tan = n_params + n_fields slots in row-major order -- (0,0), (0,1), .., (0,n-1), (1,1), .. --, n_pairs =
+// n_tan (n_tan + 1) / 2, by the rules of include/hommx_hip.h (hommx_expand_second_tangents).  d_coef and d_dirs as above, both optional
+// here, and where given the bits launch_expand_program writes.  depth: the maximal stack depth of the program (1 .. PROGRAM_MAX_STACK),
+// which with prog.n_comp sizes the kernel's dynamic LDS.  One launch for n_tan <= 2, one per pair of slots a < b for n_tan = 3, 4
+hipError_t launch_expand_program2(const ProgramArgs& prog, int n_params, int n_fields, int depth, const double* d_points,
+                                  const double* d_weights, int n_q, int dim, const double* d_rows, double* d_coef, double* d_dirs,
+                                  double* d_curv, long long n_el, long long ncells, hipStream_t stream);
+
 }  // namespace hommx

@@ -168,6 +168,9 @@ struct Sens2Args : ElemWalk {
 };
 hipError_t launch_sens2_loads(const Sens2Args& a, long long nc, hipStream_t stream);
 hipError_t launch_sens2(const Sens2Args& a, long long nc, hipStream_t stream);
+// the curvature term of HOMMX_DIRS_PARAMETERS_CURVATURE: d2A[nc][n_dirs][n_dirs][t][t] += dAk[nc][n_pairs][t][t], the first derivatives
+// along the second-order streams of the pairs a <= b in row-major order, one separately rounded addition per entry
+hipError_t launch_sens2_add_curvature(double* d2A, const double* dAk, int n_dirs, int t, long long nc, hipStream_t stream);
 
 // sens_strat.hip: derivatives of A_H with respect to the stratification M and their product with caller weights, from the correctors
 // of `nc` cells (include/hommx_hip.h, hommx_stratification_sensitivity_source)

@@ -121,7 +121,30 @@ __global__ __launch_bounds__(kWalkThreads) void k_sens2(Sens2Args A) {
   }
 }
 
+// d2A[cell][a][b][q] = add(d2A[cell][a][b][q], dAk[cell][pair(a, b)][q]), q < t t, for every (a, b): the curvature term of
+// HOMMX_DIRS_PARAMETERS_CURVATURE.  One thread per entry of d2A; (a, b) and (b, a) take the same addend and dAk is symmetric in (m, n)
+// bitwise (k_sens mirrors it), so the bitwise symmetries of d2A survive
+__global__ __launch_bounds__(256) void k_sens2_add_curvature(double* __restrict__ d2A, const double* __restrict__ dAk, int nd, int tt,
+                                                             long long total) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int q = (int)(idx % tt);
+  const long long r = idx / tt;
+  const int b = (int)(r % nd), a = (int)((r / nd) % nd);
+  const long long cell = r / ((long long)nd * nd);
+  const int lo = a < b ? a : b, hi = a < b ? b : a;
+  const int pair = lo * nd - lo * (lo - 1) / 2 + (hi - lo), n_pairs = nd * (nd + 1) / 2;  // row-major over lo <= hi
+  d2A[idx] = add_rn(d2A[idx], dAk[(cell * n_pairs + pair) * tt + q]);
+}
+
 }  // namespace
+
+hipError_t launch_sens2_add_curvature(double* d2A, const double* dAk, int n_dirs, int t, long long nc, hipStream_t st) {
+  const long long total = nc * n_dirs * n_dirs * t * t;
+  if (total <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sens2_add_curvature, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d2A, dAk, n_dirs, t * t, total);
+  return hipGetLastError();
+}
 
 hipError_t launch_sens2_loads(const Sens2Args& a, long long nc, hipStream_t st) {
   return launch_walk(a, nc, st, walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_sens2_loads<D(), K(), MESH()>; }));

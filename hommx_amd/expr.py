@@ -15,7 +15,8 @@ Parameters are the first constants of the program (``p[k]`` is ``CONST k``), so 
 parameters.  The library also differentiates the program with respect to them in forward mode -- the value pass is the instantiation
 of its one interpreter kernel without differentiable slots (csrc/coef_program.hip, ``k_expand_program<P>``), and ``_run`` here is
 built the same way; ``Expression.host_tangents`` is the NumPy twin of the forward-mode pass: the rules of ``_TANGENT``, the same
-operations in the same order.
+operations in the same order.  The second-order pass (``k_expand_program2<P>``, the same interpreter body) has its twin in
+``Expression.host_second_tangents`` and the rules of ``_TANGENT2``.
 
 Fields are read like the midpoint: ``f[k]`` is ``X 3 + k``, entry ``3 + k`` of the cell's row, so everywhere in this module they ride
 as extra rows of ``x`` (``x[3 + n_fields, ...]``), and every path that takes a program takes one with fields.  They are differentiated
@@ -343,7 +344,35 @@ _TANGENT = {
 }
 
 
-def _run(ops, consts, n_comp: int, x, y, n_params: int = 0, n_fields: int = 0) -> tuple[list, list]:
+# The second-order rules of include/hommx_hip.h (hommx_expand_second_tangents), as the kernel applies them: h_ij of an instruction's
+# result for the pair (i, j) of slots.  One operand (a, its tangents pi, pj, its ha): f(a, v, di, dj, pi, pj, ha); two, (a, pi, pj, ha)
+# and (b, qi, qj, hb), b on top: f(a, b, v, di, dj, pi, pj, qi, qj, ha, hb).  v: the instruction's value, di, dj: its own tangents
+# (``_TANGENT``).  An instruction that is not here is piecewise constant
+_TANGENT2 = {
+    OP_NEG: lambda a, v, di, dj, pi, pj, ha: -ha,
+    OP_ABS: lambda a, v, di, dj, pi, pj, ha: np.where(a < 0.0, -ha, ha),
+    OP_SQRT: lambda a, v, di, dj, pi, pj, ha: (ha + -((_TWO * di) * dj)) / (_TWO * v),
+    OP_SIN: lambda a, v, di, dj, pi, pj, ha: np.cos(a) * ha + -((v * pi) * pj),
+    OP_COS: lambda a, v, di, dj, pi, pj, ha: -(np.sin(a) * ha) + -((v * pi) * pj),
+    OP_TAN: lambda a, v, di, dj, pi, pj, ha: (_ONE + v * v) * ha + ((_TWO * v) * dj) * pi,
+    OP_EXP: lambda a, v, di, dj, pi, pj, ha: v * ha + dj * pi,
+    OP_LOG: lambda a, v, di, dj, pi, pj, ha: (ha + -(pi * dj)) / a,
+    OP_TANH: lambda a, v, di, dj, pi, pj, ha: (_ONE + -(v * v)) * ha + -(((_TWO * v) * dj) * pi),
+    OP_ADD: lambda a, b, v, di, dj, pi, pj, qi, qj, ha, hb: ha + hb,
+    OP_SUB: lambda a, b, v, di, dj, pi, pj, qi, qj, ha, hb: ha + (-hb),
+    OP_MUL: lambda a, b, v, di, dj, pi, pj, qi, qj, ha, hb: ((a * hb + ha * b) + pi * qj) + pj * qi,
+    OP_DIV: lambda a, b, v, di, dj, pi, pj, qi, qj, ha, hb: (((ha + -(di * qj)) + -(dj * qi)) + -(v * hb)) / b,
+    OP_MIN: lambda a, b, v, di, dj, pi, pj, qi, qj, ha, hb: np.where(b < a, hb, ha),
+    OP_MAX: lambda a, b, v, di, dj, pi, pj, qi, qj, ha, hb: np.where(b > a, hb, ha),
+}
+
+
+def _pairs(n: int) -> tuple:
+    """The pairs (a, b), a <= b, of n slots in the row-major order of the ABI: (0,0), (0,1), .., (0,n-1), (1,1), ..."""
+    return tuple((a, b) for a in range(n) for b in range(a, n))
+
+
+def _run(ops, consts, n_comp: int, x, y, n_params: int = 0, n_fields: int = 0, second: bool = False) -> tuple:
     """Interpret a program with NumPy on x[3 + n_fields, ...] (the midpoint, then the fields: ``X k`` reads row k) and y[d, ...]
     (broadcast against each other), in forward mode over its P = n_params + n_fields differentiable slots, the parameters, then the
     fields (``CONST k``, k < n_params, seeds slot k; ``X k``, k >= 3, slot ``n_params + k - 3``): (values[n_comp],
@@ -352,9 +381,32 @@ def _run(ops, consts, n_comp: int, x, y, n_params: int = 0, n_fields: int = 0) -
 
     A tangent that is None is +0.0 everywhere: where every operand's d_j is 0.0 the result's d_j is +0.0 and the formula is not
     evaluated -- structurally (None) or, point by point, through ``np.where`` -- so a sqrt(0) or a division by zero in a part of the
-    expression that does not read slot j cannot make its tangent NaN."""
+    expression that does not read slot j cannot make its tangent NaN.
+
+    ``second``: the second-order pass, k_expand_program2 -- a stack entry is (v, [d_j], [h_ij for (i, j) in _pairs(P)]), v and d are
+    computed by the same statements, and the result is (values, tangents, second[n_comp][n_pairs]).  Its dead rule: h_ij is +0.0
+    (None) where every operand's h_ij is 0.0 and every operand's d_i, or every operand's d_j, is 0.0."""
     P = n_params + n_fields
-    stack, out_v, out_d = [], [None] * n_comp, [None] * n_comp
+    pairs = _pairs(P) if second else ()
+    stack, out_v, out_d, out_h = [], [None] * n_comp, [None] * n_comp, [None] * n_comp
+    no_h = [None] * len(pairs)
+
+    def zeros(ds):
+        """Where every entry of ``ds`` (None: +0.0 everywhere) is 0.0."""
+        full = [_ZERO if d is None else d for d in ds]
+        dead = full[0] == 0.0
+        for d in full[1:]:
+            dead = dead & (d == 0.0)
+        return dead
+
+    def rule_h(formula, hs, dis, djs):
+        """h_ij of a result from its operands' h_ij (hs) and tangents d_i (dis), d_j (djs): +0.0 where it is dead, else formula()."""
+        if formula is None or (all(h is None for h in hs) and (all(d is None for d in dis) or all(d is None for d in djs))):
+            return None
+        return np.where(zeros(hs) & (zeros(dis) | zeros(djs)), _ZERO, formula())
+
+    def fill(d):
+        return _ZERO if d is None else d
 
     def rule(formula, *operands):
         """d_j of a result from the d_j of its operands: +0.0 where all of them are 0.0, else formula(*operands)."""
@@ -368,28 +420,36 @@ def _run(ops, consts, n_comp: int, x, y, n_params: int = 0, n_fields: int = 0) -
 
     for op, k in ops:
         if op == OP_CONST:
-            stack.append((np.float64(consts[k]), [_ONE if (k == j and k < n_params) else None for j in range(P)]))
+            stack.append((np.float64(consts[k]), [_ONE if (k == j and k < n_params) else None for j in range(P)], list(no_h)))
         elif op == OP_X:
-            stack.append((np.asarray(x[k], dtype=np.float64), [_ONE if (k >= 3 and j == n_params + k - 3) else None for j in range(P)]))
+            stack.append((np.asarray(x[k], dtype=np.float64), [_ONE if (k >= 3 and j == n_params + k - 3) else None for j in range(P)],
+                          list(no_h)))
         elif op == OP_Y:
-            stack.append((np.asarray(y[k], dtype=np.float64), [None] * P))
+            stack.append((np.asarray(y[k], dtype=np.float64), [None] * P, list(no_h)))
         elif op == OP_DUP:
-            stack.append((stack[-1][0], list(stack[-1][1])))
+            stack.append((stack[-1][0], list(stack[-1][1]), list(stack[-1][2])))
         elif op == OP_STORE:
-            out_v[k], out_d[k] = stack.pop()
+            out_v[k], out_d[k], out_h[k] = stack.pop()
         elif op == OP_SELECT:
-            (b, db), (a, da), (c, _) = stack.pop(), stack.pop(), stack.pop()  # a condition carries no tangent
+            (b, db, hb), (a, da, ha), (c, _, _) = stack.pop(), stack.pop(), stack.pop()  # a condition carries no tangent
             pick = c != 0.0
-            stack.append((np.where(pick, a, b), [rule(lambda p, q: np.where(pick, p, q), da[j], db[j]) for j in range(P)]))
+            stack.append((np.where(pick, a, b), [rule(lambda p, q: np.where(pick, p, q), da[j], db[j]) for j in range(P)],
+                          [rule_h(lambda s=s: np.where(pick, fill(ha[s]), fill(hb[s])), [ha[s], hb[s]], [da[i], db[i]], [da[j], db[j]])
+                           for s, (i, j) in enumerate(pairs)]))
         elif _POPS.get(op, 2) == 1:
-            a, da = stack.pop()
-            v, f = _unary(op, a), _TANGENT.get(op)
-            stack.append((v, [rule(f and (lambda p: f(a, v, p)), da[j]) for j in range(P)]))
+            a, da, ha = stack.pop()
+            v, f, g = _unary(op, a), _TANGENT.get(op), _TANGENT2.get(op)
+            d = [rule(f and (lambda p: f(a, v, p)), da[j]) for j in range(P)]
+            stack.append((v, d, [rule_h(g and (lambda s=s, i=i, j=j: g(a, v, fill(d[i]), fill(d[j]), fill(da[i]), fill(da[j]), fill(ha[s]))),
+                                        [ha[s]], [da[i]], [da[j]]) for s, (i, j) in enumerate(pairs)]))
         else:
-            (b, db), (a, da) = stack.pop(), stack.pop()
-            v, f = _binary(op, a, b), _TANGENT.get(op)
-            stack.append((v, [rule(f and (lambda p, q: f(a, b, v, p, q)), da[j], db[j]) for j in range(P)]))
-    return out_v, out_d
+            (b, db, hb), (a, da, ha) = stack.pop(), stack.pop()
+            v, f, g = _binary(op, a, b), _TANGENT.get(op), _TANGENT2.get(op)
+            d = [rule(f and (lambda p, q: f(a, b, v, p, q)), da[j], db[j]) for j in range(P)]
+            stack.append((v, d, [rule_h(g and (lambda s=s, i=i, j=j: g(a, b, v, fill(d[i]), fill(d[j]), fill(da[i]), fill(da[j]), fill(db[i]),
+                                                                        fill(db[j]), fill(ha[s]), fill(hb[s]))),
+                                        [ha[s], hb[s]], [da[i], db[i]], [da[j], db[j]]) for s, (i, j) in enumerate(pairs)]))
+    return (out_v, out_d, out_h) if second else (out_v, out_d)
 
 
 class Expression:
@@ -415,6 +475,9 @@ class Expression:
     are then the whole Hessian.  A parameter inside a comparison logs one WARNING: the derivative ignores the motion of the interface
     (it is zero almost everywhere); a smooth transition such as ``tanh`` is the way to differentiate a radius.
 
+    ``pairs``: the pairs (a, b), a <= b, of the differentiable slots in the order of the second-order streams
+    (``host_second_tangents``, hommx_expand_second_tangents): (0, 0), (0, 1), .., (1, 1), ...
+
     ``fields=2`` or ``fields=("radius", "phase")``: up to 4 fields ``f[k]`` (literal index), each ONE VALUE PER MACRO CELL -- a design
     variable, the macro solution at the midpoint, a random draw --, ``field_names`` their names (default ``"f0"``, ``"f1"``, ...).  The
     solver classes take the values with ``set_fields``; the device reads them from the cell's row, after the midpoint.  ``f[k]`` has
@@ -424,8 +487,8 @@ class Expression:
     ``n_params + n_fields`` differentiable slots, the parameters first.
 
     The object is also a plain callable ``A(x, y)`` -- it interprets ``program()`` with NumPy --, so every generic path accepts it.
-    ``host_stream`` is the documented host equivalent of the device sampler, ``host_tangents`` of its forward-mode pass: the same IEEE
-    operations in the same order.
+    ``host_stream`` is the documented host equivalent of the device sampler, ``host_tangents`` of its forward-mode pass and
+    ``host_second_tangents`` of its second-order pass: the same IEEE operations in the same order.
     """
 
     def __init__(self, text=None, *, lam=None, mu=None, p=None, parameter_names=None, fields=None):
@@ -486,6 +549,11 @@ class Expression:
     def p(self) -> np.ndarray:
         """The values of the parameters (a copy)."""
         return self._consts[:self.n_params].copy()
+
+    @property
+    def pairs(self) -> tuple:
+        """The pairs (a, b), a <= b, of the n_params + n_fields differentiable slots, in the order of the second-order streams."""
+        return _pairs(self.n_params + self.n_fields)
 
     def with_parameters(self, p) -> "Expression":
         """The same expression at other parameter values: the same ``ops``, only ``consts[:n_params]`` replaced -- nothing is parsed."""
@@ -571,6 +639,31 @@ class Expression:
                     dj = np.float64(0.0) if dv[c][j] is None else dv[c][j]
                     acc[j][c] = acc[j][c] + w[q] * np.broadcast_to(dj, shape)
         out = np.stack([np.stack(a, axis=-1) for a in acc], axis=1)  # [N, P, n_el, n_comp]
+        return out[..., 0] if self.n_comp == 1 else out
+
+
+    def host_second_tangents(self, x: np.ndarray, yq: np.ndarray, w: np.ndarray) -> np.ndarray:
+        """The second derivatives of ``host_stream`` with respect to the pairs ``self.pairs`` of the parameters, then the fields,
+        curv[N, n_pairs, n_el(, n_comp)], exactly as the device's second-order forward-mode pass forms them (``_TANGENT2``: the rules),
+        ``acc_ab = acc_ab + w[q] * h_ab`` with q ascending, from 0."""
+        if self.n_params + self.n_fields == 0:
+            raise ValueError("the expression has no parameters (p=[...])")
+        x = self._rows(x)
+        n_el, nq, d = yq.shape
+        if self.n_y > d:
+            raise ValueError(f"the expression reads y[{self.n_y - 1}]; the fast variable has {d} components")
+        pairs, shape = self.pairs, (x.shape[0], n_el)
+        acc = [[np.zeros(shape) for _ in range(self.n_comp)] for _ in pairs]
+        ops = self._ops.tolist()
+        for q in range(nq):
+            with np.errstate(all="ignore"):
+                _, _, hv = _run(ops, self._consts, self.n_comp, x.T[:, :, None], np.moveaxis(yq[:, q, :], -1, 0)[:, None, :], self.n_params,
+                                self.n_fields, second=True)
+            for s in range(len(pairs)):
+                for c in range(self.n_comp):
+                    hs = np.float64(0.0) if hv[c][s] is None else hv[c][s]
+                    acc[s][c] = acc[s][c] + w[q] * np.broadcast_to(hs, shape)
+        out = np.stack([np.stack(a, axis=-1) for a in acc], axis=1)  # [N, n_pairs, n_el, n_comp]
         return out[..., 0] if self.n_comp == 1 else out
 
 

@@ -1010,9 +1010,11 @@ class BaseHMM(ABC):
         cat = lambda name: np.concatenate([getattr(r, name) for r in parts])
         return Sensitivities(cat("dA"), None, cat("A_eff"), cat("info"), names, cells)
 
-    def _direction_blocks(self, what: str, cells, directions, chunk_cells: int | None, call) -> tuple[tuple, np.ndarray, list]:
+    def _direction_blocks(self, what: str, cells, directions, chunk_cells: int | None, call, curvature: bool = False) -> tuple[tuple, np.ndarray, list]:
         """(names, cells, results) of ``call(plan, coef, M, directions=..., per_cell=...)`` over ``cells`` (default: this rank's macro
-        cells) in chunks of ``chunk_cells``: the cells, names and directions of ``tensor_derivatives`` and ``tensor_second_derivatives``."""
+        cells) in chunks of ``chunk_cells``: the cells, names and directions of ``tensor_derivatives`` and ``tensor_second_derivatives``.
+        ``curvature``: the parameter directions of a device-sampled ``Expression`` with the curvature term, for any ``p_degree``
+        (``call`` then also takes ``curvature=True``); every other coefficient raises ``ValueError``."""
         cells = self._local_cells() if cells is None else np.asarray(cells, dtype=np.int64).ravel()
         if len(cells) == 0:
             raise ValueError(f"{what}() needs at least one macro cell")
@@ -1021,13 +1023,23 @@ class BaseHMM(ABC):
         if directions is None and isinstance(co, Expression) and (co.n_params or co.n_fields) and self._device_form() == "solve_program" \
                 and hasattr(self._ensure_plan(self._micro_kind()), "solve_program"):
             # the parameter tangents of the program, formed on the device with the stream: nothing is sampled, no direction stream is sent
-            if what == "tensor_second_derivatives" and not co.affine_in_parameters:
+            if what == "tensor_second_derivatives" and not co.affine_in_parameters and not curvature:
                 raise ValueError(
                     f"the expression is not affine in its parameters (p_degree {co.p_degree}): the Hessian of A_H also needs dA_H along "
-                    "d2A/dp_a dp_b, which second-order tangents would give and this library does not form.  directions=[...] with your own "
-                    "streams remains available: the second derivatives along them, and tensor_derivatives(directions=[d2A/dp_a dp_b, ...]) "
-                    "for the curvature term")
+                    "d2A/dp_a dp_b, the curvature term.  Pass curvature=True: the library then forms those streams on the device in "
+                    "second-order forward mode and d2A is the whole Hessian.  directions=[...] with your own streams remains available: "
+                    "the second derivatives along them")
             names, shared = co.parameter_names + co.field_names, "parameters"
+        elif curvature:
+            if directions is not None:
+                why = "directions=[...] are the caller's own streams, whose second derivatives the library cannot know"
+            elif not isinstance(co, Expression):
+                why = f"the coefficient is a {type(co).__name__}, not an Expression (TwoPhase and Separable are affine: their curvature term is zero)"
+            elif not (co.n_params or co.n_fields):
+                why = "the Expression has neither parameters (p=[...]) nor fields (fields=...)"
+            else:
+                why = "the Expression is sampled on the host here, and the second-order tangents are formed by the device sampler only"
+            raise ValueError(f"curvature=True needs a device-sampled Expression with parameters or fields: {why}")
         elif directions is None:
             names, shared = self._parameter_directions()
         else:
@@ -1048,7 +1060,8 @@ class BaseHMM(ABC):
                 if any(k != kind for _, k in sampled):
                     raise ValueError(f"every direction must have the coefficient's shape (plan kind {kind!r}); got {[k for _, k in sampled]}")
                 dirs = np.stack([d for d, _ in sampled], axis=1)
-            parts.append(call(self._ensure_plan(kind), coef, self._stratification(sub), directions=dirs, per_cell=shared is None))
+            more = {"curvature": True} if curvature else {}
+            parts.append(call(self._ensure_plan(kind), coef, self._stratification(sub), directions=dirs, per_cell=shared is None, **more))
         return names, cells, parts
 
     def energy_derivatives(self, u=None, v=None, **kw) -> np.ndarray:
@@ -1077,7 +1090,8 @@ class BaseHMM(ABC):
         xu = xi(u)
         return (xu if v is None else xi(v)), xu, self._msh.cell_volumes()[cells] / self._cell_mesh_area
 
-    def tensor_second_derivatives(self, cells=None, directions=None, chunk_cells: int | None = None) -> SecondSensitivities:
+    def tensor_second_derivatives(self, cells=None, directions=None, chunk_cells: int | None = None,
+                                  curvature: bool = False) -> SecondSensitivities:
         """Second derivatives of A_H / C_H of ``cells`` (default: this rank's macro cells) with respect to the micro coefficient
         (hommx_second_sensitivity_source) -> ``SecondSensitivities`` with ``names``, ``d2A[N, n_dirs, n_dirs, t, t]``, the
         first derivatives ``dA[N, n_dirs, t, t]`` of the same call, ``A_eff``, ``info`` and ``cells``.
@@ -1088,9 +1102,16 @@ class BaseHMM(ABC):
         callables (x, y) of the coefficient's shape.
         d2A[:, a, b] is exact on the discrete problem -- the Hessian of A_H a Newton or Gauss-Newton step needs, with no step size to
         tune -- and costs one load solve per direction, on every micro mesh.  The cells run in chunks of ``chunk_cells``.  Under a process
-        group this runs on the calling rank alone: there is no collective."""
+        group this runs on the calling rank alone: there is no collective.
+
+        ``curvature=True`` (a device-sampled ``Expression`` with parameters or fields, without ``directions``): the whole Hessian of A_H
+        in the parameters and fields for ANY expression -- a radius inside ``tanh``, ``p[0]*p[1]``, a parameter in a denominator.  The
+        device pass that samples the program carries second-order tangents, and d2A[:, a, b] also takes dA_H along d2 coef / dp_a dp_b
+        (hommx_expand_second_tangents, HOMMX_DIRS_PARAMETERS_CURVATURE).  For an affine expression that term is +0.0 and the result is
+        the default call's; any other coefficient, ``directions=[...]`` or a host-sampled expression raises ``ValueError``."""
         names, cells, parts = self._direction_blocks("tensor_second_derivatives", cells, directions, chunk_cells,
-                                                     lambda plan, coef, M, **kw: plan.second_sensitivities(coef, M, first=True, **kw))
+                                                     lambda plan, coef, M, **kw: plan.second_sensitivities(coef, M, first=True, **kw),
+                                                     curvature=curvature)
         cat = lambda name: np.concatenate([getattr(r, name) for r in parts])
         return SecondSensitivities(cat("d2A"), cat("dA"), cat("A_eff"), cat("info"), names, cells)
 

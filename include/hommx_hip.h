@@ -384,6 +384,39 @@ int hommx_expand_tangents(hommx_plan* plan, int64_t n_cells, const hommx_coef_so
 int hommx_expand_tangents_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, double* d_coef_out, double* d_dirs_out,
                                  void* stream);
 
+/*
+ * The second derivatives of that element stream with respect to the same n_tan slots, in SECOND-ORDER forward mode: the interpreter
+ * (csrc/coef_program.hip, k_expand_program2<P>, the same body as k_expand_program<P>) carries (v, d_a, d_b, h_aa, h_ab, h_bb) per stack
+ * entry -- (v, d, h) for one slot -- and yields, beside the two streams of hommx_expand_tangents,
+ *   curv_out [n_cells][n_pairs][n_el][n_comp]    d2 coef / d slot a d slot b for the pairs (a, b), a <= b, in row-major order:
+ *                                                (0,0), (0,1), .., (0,n_tan-1), (1,1), ..;  n_pairs = n_tan (n_tan + 1) / 2.  Required
+ *   coef_out, dirs_out                           as in hommx_expand_tangents, the same bits; either may be NULL: not wanted
+ * n_tan <= 2 is one pass; n_tan = 3, 4 runs the two-slot pass once per pair of slots a < b (3 or 6 launches), each launch storing
+ * the streams no earlier one has stored.  Every arithmetic step is one separately rounded operation in the written order, no
+ * contraction; hommx_amd.expr.Expression.host_second_tangents applies the same rules in the same order with NumPy.  For operands
+ * (a, da, ha), (b, db, hb), b on top, the instruction's own value v and its own tangents d (the rules above), h = h_ij of the result:
+ * if every operand's h_ij is 0.0 and every operand's d_i, or every operand's d_j, is 0.0, the result's h_ij is +0.0 and the formula
+ * is not evaluated (a sqrt(0) or a division by zero in a part that does not read both slots cannot make it NaN).  Otherwise
+ *   CONST, X, Y   0          DUP  copies          LT .. GE, AND, OR, NOT   0
+ *   ADD  add(ha, hb)         SUB  add(ha, -hb)    NEG  -ha          ABS  a < 0 ? -ha : ha
+ *   MUL  add(add(add(mul(a, hb), mul(ha, b)), mul(da_i, db_j)), mul(da_j, db_i))
+ *   DIV  div(add(add(add(ha, -mul(d_i, db_j)), -mul(d_j, db_i)), -mul(v, hb)), b)
+ *   MIN / MAX / SELECT  the h of the operand the value rule picks
+ *   SQRT div(add(ha, -mul(mul(2, d_i), d_j)), mul(2, v))
+ *   SIN  add(mul(cos(a), ha), -mul(mul(v, da_i), da_j))        COS  add(-mul(sin(a), ha), -mul(mul(v, da_i), da_j))
+ *   TAN  add(mul(g, ha), mul(mul(mul(2, v), d_j), da_i)),  g = add(1, mul(v, v))
+ *   TANH add(mul(g, ha), -mul(mul(mul(2, v), d_j), da_i)), g = add(1, -mul(v, v))
+ *   EXP  add(mul(v, ha), mul(d_j, da_i))                       LOG  div(add(ha, -mul(da_i, d_j)), a)
+ *   STORE c   acch[c][ij] = add(acch[c][ij], mul(w, h_ij)),  q ascending, from 0
+ * Validation: that of hommx_expand_tangents, with a null curv_out in the place of a null dirs_out.  The host entry stages and
+ * chunks as hommx_expand_tangents does (at most 1 GiB of the 1 + n_tan + n_pairs streams).
+ */
+int hommx_expand_second_tangents(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, double* coef_out, double* dirs_out,
+                                 double* curv_out);
+/* Same with DEVICE pointers (in *src as well), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
+int hommx_expand_second_tangents_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, double* d_coef_out, double* d_dirs_out,
+                                        double* d_curv_out, void* stream);
+
 #define HOMMX_RECON_MAX_REGIONS 8
 #define HOMMX_RECON_NREGION(t) (2 * (t) + 4) /* [volume | sum strain(t) | sum flux(t) | energy | max_flux | argmax_element] */
 int hommx_reconstruct_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const double* xi,
@@ -412,7 +445,8 @@ int hommx_reconstruct_source_device(hommx_plan* plan, int64_t n_cells, const hom
  *               (hommx_expand_tangents), formed on the device chunk by chunk in the launch that expands the stream, into plan-owned
  *               scratch whose bytes the chunk rule counts: dirs == NULL, n_dirs == n_tan = the program's n_params + the source's
  *               n_fields (1 .. HOMMX_PROGRAM_MAX_PARAMS), dA as with per_cell == 1.
- *               HOMMX_EINVAL with a text for a source that is no HOMMX_COEF_PROGRAM, n_tan == 0 or above 4, another n_dirs, a non-null dirs
+ *               HOMMX_EINVAL with a text for a source that is no HOMMX_COEF_PROGRAM, n_tan == 0 or above 4, another n_dirs, a non-null dirs;
+ *               and for HOMMX_DIRS_PARAMETERS_CURVATURE, which hommx_sens2_args alone takes (a first derivative has no curvature term)
  *   dA          [n_cells][n_dirs][t][t] (symmetric, bitwise); required with n_dirs > 0, as dirs
  *   weights     [n_cells][t][t] and grad [n_cells][n_el][n_comp] (the shape of coef): both or neither
  *   A_eff, info as hommx_solve_batch, or NULL
@@ -426,6 +460,7 @@ int hommx_reconstruct_source_device(hommx_plan* plan, int64_t n_cells, const hom
  */
 #define HOMMX_SENS_MAX_DIRS 8
 #define HOMMX_DIRS_PARAMETERS 2 /* a value of per_cell in hommx_sens_args and hommx_sens2_args */
+#define HOMMX_DIRS_PARAMETERS_CURVATURE 3 /* a value of per_cell in hommx_sens2_args only: d2A takes the curvature term as well */
 typedef struct hommx_sens_args {
   int32_t n_dirs;
   int32_t per_cell;
@@ -553,7 +588,13 @@ int hommx_loads_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coe
  *               HOMMX_DIRS_PARAMETERS: the parameter tangents of the source's program, as in hommx_sens_args (dirs == NULL, n_dirs ==
  *               n_params).  d2A then holds the second derivatives ALONG THE TANGENT DIRECTIONS.  For a program that is affine in its
  *               parameters that is the Hessian of A_H with respect to them; for any other the Hessian also needs dA_H along
- *               d2 coef / dp_a dp_b, a first derivative along directions the library does not form: that term is the caller's
+ *               d2 coef / dp_a dp_b, the curvature term, which this value leaves out;
+ *               HOMMX_DIRS_PARAMETERS_CURVATURE: the arguments and checks of HOMMX_DIRS_PARAMETERS, and the launch that expands the
+ *               chunk is the second-order pass (hommx_expand_second_tangents): it also forms the n_pairs second-order streams, in
+ *               plan-owned scratch whose bytes the chunk rule counts; k_sens contracts them into dA_H[kappa_ab] ([n_pairs][t][t]
+ *               per cell, scratch too) and d2A[a][b] = add(d2A[a][b], dA_H[kappa_ab]) for every (a, b), (b, a) with the addend of
+ *               (a, b): d2A is then the HESSIAN of A_H in the parameters and fields for any program, still symmetric bitwise in
+ *               (a, b) and (m, n).  dA, A_eff and info are exactly those of HOMMX_DIRS_PARAMETERS
  *   d2A         [n_cells][n_dirs][n_dirs][t][t], required
  *   dA          [n_cells][n_dirs][t][t] or NULL: the first derivatives along the same directions, the bits hommx_sensitivity_source returns
  *   A_eff, info as hommx_solve_batch, or NULL
