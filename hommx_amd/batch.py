@@ -227,9 +227,15 @@ def region_labels(labels, n_el: int, n_regions: int | None = None) -> tuple[np.n
     return out, int(n_regions)
 
 
-def _per_cell_code(per_cell) -> int:
-    """per_cell of hommx_sens_args / hommx_sens2_args: 0 shared, 1 per cell, ``"parameters"`` HOMMX_DIRS_PARAMETERS."""
-    return _lib.DIRS_PARAMETERS if isinstance(per_cell, str) and per_cell == "parameters" else int(bool(per_cell))
+def _per_cell_code(per_cell, curvature: bool = False, argument: str = "per_cell") -> int:
+    """per_cell of hommx_sens_args / hommx_sens2_args: 0 shared, 1 per cell, ``"parameters"`` HOMMX_DIRS_PARAMETERS or, with ``curvature``,
+    HOMMX_DIRS_PARAMETERS_CURVATURE.  ``argument``: what the caller's method calls the argument that says ``"parameters"``."""
+    code = _lib.DIRS_PARAMETERS if isinstance(per_cell, str) and per_cell == "parameters" else int(bool(per_cell))
+    if curvature:
+        if code != _lib.DIRS_PARAMETERS:
+            raise ValueError(f'curvature=True needs {argument}="parameters": the curvature term is that of the program\'s own parameters')
+        code = _lib.DIRS_PARAMETERS_CURVATURE
+    return code
 
 
 @dataclass(frozen=True)
@@ -322,13 +328,9 @@ class CoefStream:
         return getattr(plan, self.method)(*self.shared, self.per_cell, M, **kw)
 
     def solve_device(self, plan: "MicroCellPlan", upload, M_ptr, out_ptr, info_ptr, stream):
-        """Through the device twin of the method: ``upload(array) -> device pointer`` copies every array of the stream to the plan's device."""
-        args = [a if a is None or isinstance(a, (str, Program)) else upload(a) for a in self.shared]
-        if self.method == "solve_program":  # the device twin is told n_q as well
-            args.insert(2, int(self.shared[0].shape[1]))
-        if self.method == "solve_separable":  # the device twin is told n_q; the host method reads it off the table
-            args.insert(1, 1 if self.shared[0] == "affine" else int(self.shared[1].shape[1]))
-        getattr(plan, self.method + "_device")(len(self), *args, upload(self.per_cell), M_ptr, out_ptr, info_ptr, stream)
+        """Through ``plan.solve_source_device``: ``upload(array) -> device pointer`` copies every array of the stream that the library reads
+        to the plan's device (``coef_source``)."""
+        plan.solve_source_device(len(self), self.coef_source(upload), M_ptr, out_ptr, info_ptr, stream)
 
 
 class MicroCellPlan:
@@ -411,6 +413,21 @@ class MicroCellPlan:
             pass
 
     # -- host arrays -----------------------------------------------------------------------------
+    @property
+    def _el(self) -> tuple:
+        """Shape of one cell's element stream: (n_el,) or (n_el, n_comp)."""
+        return (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
+
+    @property
+    def _bs(self) -> int:
+        """Unknowns per periodic node."""
+        return 1 if self.kind.startswith("poisson") else self.dim
+
+    @staticmethod
+    def _as_stream(coef) -> CoefStream:
+        """``coef`` as every method below takes it -- an array of element means or a ``CoefStream`` -- as a stream."""
+        return coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
+
     def _check_coef(self, coef) -> tuple[np.ndarray, int]:
         """coef[N_c, n_el(, n_comp)] as contiguous float64, and N_c."""
         coef = np.ascontiguousarray(coef, dtype=np.float64)
@@ -450,7 +467,7 @@ class MicroCellPlan:
 
     def _check_directions(self, directions, nc: int, per_cell: bool) -> tuple[np.ndarray, int]:
         """directions[(N_c,) n_dirs, n_el(, n_comp)] as float64 -> (directions, n_dirs)."""
-        el = (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
+        el = self._el
         dirs = np.ascontiguousarray(directions, dtype=np.float64)
         lead = ((nc,) if per_cell else ())
         nd = dirs.shape[len(lead)] if dirs.ndim == len(lead) + 1 + len(el) else -1
@@ -484,16 +501,23 @@ class MicroCellPlan:
         of the canonical loads (mean-free), dof = node * bs + component."""
         coef, nc = self._check_coef(coef)
         if return_correctors:
-            bs = 1 if self.kind.startswith("poisson") else self.dim
-            corr = np.empty((nc, self.t, self.n_nodes * bs), dtype=np.float64)
+            corr = np.empty((nc, self.t, self.n_nodes * self._bs), dtype=np.float64)
             out, info = self._host_call("hommx_solve_batch_correctors", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch_correctors(
                 self._h, nc, coef.ctypes.data, Mp, o, corr.ctypes.data, i))
             return (out, corr, info) if return_info else (out, corr)
         return self._host_call("hommx_solve_batch", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch(self._h, nc, coef.ctypes.data, Mp, o, i),
                                return_info)
 
+    def _solve_stream(self, stream: CoefStream, M, return_info: bool):
+        """The host solve of a coefficient in any form (hommx_solve_batch_source): what the three sampler methods below come to."""
+        nc = self._check_stream(stream)
+        src = stream.coef_source()
+        return self._host_call("hommx_solve_batch_source", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch_source(
+            self._h, nc, C.byref(src), Mp, o, i), return_info)
+
     def _check_stream(self, stream: CoefStream) -> int:
-        """Shapes of a sampler stream against the plan (what ``solve_two_phase`` / ``solve_separable`` check); returns N_c."""
+        """Shapes of a stream against the plan: the checks of ``solve``, ``solve_two_phase``, ``solve_separable`` and ``solve_program``;
+        returns N_c."""
         nc = len(stream)
         if stream.method == "solve":
             return self._check_coef(stream.per_cell)[1]
@@ -516,6 +540,8 @@ class MicroCellPlan:
                 raise ValueError(f"the expression has {prog.n_comp} components; the plan's coefficient has {self.n_comp}")
             return nc
         family, table, weights = stream.shared
+        if family not in ("affine", "reciprocal"):
+            raise KeyError(family)
         nq = 1 if family == "affine" else int(table.shape[1])
         if table.size != self.n_el * nq:
             raise ValueError(f"table has shape {table.shape}; expected ({self.n_el}" + (f", {nq})" if nq > 1 else ",)"))
@@ -536,12 +562,8 @@ class MicroCellPlan:
         ``regions``: integer labels [n_el] of the micro elements -> the ``region_*`` statistics over the elements of every label below
         ``n_regions`` (default: the largest label below 8, plus one); elements with any other label are in no region.  ``True`` with a
         two-phase stream: its mask is the labels (region 0: phase 0, region 1: phase 1)."""
-        stream = coef if isinstance(coef, CoefStream) else None
-        if stream is None and regions is None:  # the plain entry point, as before there were sources
-            coef, nc = self._check_coef(coef)
-        else:
-            stream = stream or CoefStream.sampled(coef)
-            nc = self._check_stream(stream)
+        stream = self._as_stream(coef)
+        nc = self._check_stream(stream)
         xi = np.ascontiguousarray(xi, dtype=np.float64)
         if xi.shape != (nc, self.t):
             raise ValueError(f"xi has shape {xi.shape}; expected ({nc}, {self.t})")
@@ -549,10 +571,6 @@ class MicroCellPlan:
         strain = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
         flux = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
         sp, fp = (strain.ctypes.data, flux.ctypes.data) if fields else (None, None)
-        if stream is None:
-            A, info = self._host_call("hommx_reconstruct_batch", nc, M, lambda Mp, o, i: self._lib.hommx_reconstruct_batch(
-                self._h, nc, coef.ctypes.data, Mp, xi.ctypes.data, stats.ctypes.data, sp, fp, o, i))
-            return Reconstruction.from_stats(xi, stats, A, info, strain, flux)
         labels, nr = None, 0
         if regions is True:
             if stream.method != "solve_two_phase":
@@ -576,23 +594,20 @@ class MicroCellPlan:
         At least one of the two.  The correctors never leave the device; the batch runs in the chunks of ``reconstruct``.
         ``directions="parameters"`` (``coef`` the program stream of an expression with parameters): the directions are the derivatives of
         the stream with respect to the parameters, formed on the device with the stream itself; ``dA[N_c, n_params, t, t]``."""
-        stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
+        stream = self._as_stream(coef)
         parameters = isinstance(directions, str) and directions == "parameters"
         nd, dirs = (self._parameter_count(coef), None) if parameters else (0, None)
         nc = self._check_stream(stream)
-        el = (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
-        if parameters:
-            per_cell = _lib.DIRS_PARAMETERS
-        elif directions is not None:
+        if not parameters and directions is not None:
             dirs, nd = self._check_directions(directions, nc, per_cell)
         grad = None
         if weights is not None:
             weights = self._check_weights(weights, nc)
-            grad = np.empty((nc,) + el, dtype=np.float64)
+            grad = np.empty((nc,) + self._el, dtype=np.float64)
         elif nd == 0:
             raise ValueError("nothing requested: pass directions, weights or both")
         dA = np.empty((nc, nd, self.t, self.t), dtype=np.float64)
-        args = _lib.SensArgs(nd, int(per_cell), None if dirs is None else dirs.ctypes.data, dA.ctypes.data if nd else None,
+        args = _lib.SensArgs(nd, _per_cell_code(directions if parameters else per_cell), None if dirs is None else dirs.ctypes.data, dA.ctypes.data if nd else None,
                              None if grad is None else weights.ctypes.data, None if grad is None else grad.ctypes.data)
         A, info = self._source_call("hommx_sensitivity_source", nc, M, stream, args)
         return Sensitivities(dA, grad, A, info)
@@ -609,21 +624,18 @@ class MicroCellPlan:
         ``curvature=True`` (with ``directions="parameters"`` only): d2A also takes dA_H along the second derivatives of the stream
         (``expand_second_tangents``), formed on the device in the same pass -- the Hessian of A_H in the parameters and fields for any
         expression (HOMMX_DIRS_PARAMETERS_CURVATURE)"""
-        stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
+        stream = self._as_stream(coef)
         parameters = isinstance(directions, str) and directions == "parameters"
-        if curvature and not parameters:
-            raise ValueError('curvature=True needs directions="parameters": the curvature term is that of the program\'s own parameters')
+        code = _per_cell_code(directions if parameters else per_cell, curvature, "directions")
         nd, dirs = (self._parameter_count(coef), None) if parameters else (0, None)
         nc = self._check_stream(stream)
         if directions is None:
             raise ValueError("directions is required")
-        if parameters:
-            per_cell = _lib.DIRS_PARAMETERS_CURVATURE if curvature else _lib.DIRS_PARAMETERS
-        else:
+        if not parameters:
             dirs, nd = self._check_directions(directions, nc, per_cell)
         d2A = np.empty((nc, nd, nd, self.t, self.t), dtype=np.float64)
         dA = np.empty((nc, nd, self.t, self.t), dtype=np.float64) if first else None
-        args = _lib.Sens2Args(nd, int(per_cell), None if dirs is None else dirs.ctypes.data, d2A.ctypes.data, dA.ctypes.data if first else None)
+        args = _lib.Sens2Args(nd, code, None if dirs is None else dirs.ctypes.data, d2A.ctypes.data, dA.ctypes.data if first else None)
         A, info = self._source_call("hommx_second_sensitivity_source", nc, M, stream, args)
         return SecondSensitivities(d2A, dA, A, info)
 
@@ -633,7 +645,7 @@ class MicroCellPlan:
         = dA_H[m, n] / dM[a, b]; ``weights[N_c, t, t]`` -> ``grad_M[N_c, d, d]`` = sum_mn weights[m, n] dA_dM[a, b, m, n], formed in one
         pass without the t x t intermediate.  At least one of the two.  The correctors never leave the device; the batch runs in the
         chunks of ``reconstruct``."""
-        stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
+        stream = self._as_stream(coef)
         nc = self._check_stream(stream)
         grad = None
         if weights is not None:
@@ -656,7 +668,7 @@ class MicroCellPlan:
         loads themselves (energy, mean / max total flux), ``fields`` the per-element strain and total flux of every load,
         ``return_correctors`` the load correctors (each implies ``response``; needs ``load_solve=True`` on the frontal mesh route).  The batch runs in the chunks
         of ``reconstruct``."""
-        stream = coef if isinstance(coef, CoefStream) else CoefStream.sampled(coef)
+        stream = self._as_stream(coef)
         nc = self._check_stream(stream)
         P = np.ascontiguousarray(P, dtype=np.float64)
         if per_cell is None:
@@ -668,13 +680,12 @@ class MicroCellPlan:
         if not 1 <= nl <= self.t:
             raise ValueError(f"n_loads must be 1 .. {self.t}; got {nl}")
         response = bool(response or fields or return_correctors)
-        bs = 1 if self.kind.startswith("poisson") else self.dim
         P_eff = np.empty((nc, nl, self.t), dtype=np.float64)
         energy = np.empty((nc, nl, nl), dtype=np.float64) if response else None
         stats = np.empty((nc, nl, self.t + 2), dtype=np.float64) if response else None
         strain = np.empty((nc, nl, self.n_el, self.t), dtype=np.float64) if fields else None
         flux = np.empty((nc, nl, self.n_el, self.t), dtype=np.float64) if fields else None
-        corr = np.empty((nc, nl, self.n_nodes * bs), dtype=np.float64) if return_correctors else None
+        corr = np.empty((nc, nl, self.n_nodes * self._bs), dtype=np.float64) if return_correctors else None
         addr = lambda a: None if a is None else a.ctypes.data
         args = _lib.LoadArgs(nl, int(bool(per_cell)), P.ctypes.data, P_eff.ctypes.data, None, addr(energy), addr(stats), addr(strain), addr(flux),
                              addr(corr), None)
@@ -689,35 +700,13 @@ class MicroCellPlan:
                         return_info: bool = False):
         """Two-phase media sampled on the device: mask[n_el] (bool / uint8, phase of every micro element) and
         values[N_c, 2(, n_comp)] = coefficient of phase 0 / phase 1 at every macro cell -> A_eff[N_c, t, t]."""
-        mask = np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
-        if mask.shape != (self.n_el,):
-            raise ValueError(f"mask has shape {mask.shape}; expected ({self.n_el},)")
-        values = np.ascontiguousarray(values, dtype=np.float64)
-        nc = values.shape[0]
-        if values.size != nc * 2 * self.n_comp:
-            raise ValueError(f"values has shape {values.shape}; expected ({nc}, 2" + (f", {self.n_comp})" if self.n_comp > 1 else ")"))
-        return self._host_call("hommx_solve_batch_two_phase", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch_two_phase(
-            self._h, nc, mask.ctypes.data, values.ctypes.data, Mp, o, i), return_info)
+        return self._solve_stream(CoefStream.two_phase(mask, values), M, return_info)
 
     def solve_separable(self, family: str, table: np.ndarray, weights: np.ndarray | None, params: np.ndarray,
                         M: np.ndarray | None = None, return_info: bool = False):
         """Separable coefficient sampled on the device (include/hommx_hip.h): ``family`` "affine" (table[n_el] = element means of
         g) or "reciprocal" (table[n_el, n_q] = g at the quadrature points, weights[n_q]); params[N_c, 2] = (a, b) per macro cell."""
-        fam = {"affine": _lib.SAMPLER_AFFINE, "reciprocal": _lib.SAMPLER_RECIPROCAL}[family]
-        table = np.ascontiguousarray(table, dtype=np.float64)
-        nq = 1 if fam == _lib.SAMPLER_AFFINE else int(table.shape[1])
-        if table.size != self.n_el * nq:
-            raise ValueError(f"table has shape {table.shape}; expected ({self.n_el}" + (f", {nq})" if nq > 1 else ",)"))
-        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
-        if fam == _lib.SAMPLER_RECIPROCAL and (w is None or w.shape != (nq,)):
-            raise ValueError(f"weights must have shape ({nq},)")
-        params = np.ascontiguousarray(params, dtype=np.float64)
-        nc = params.shape[0]
-        want = (nc, 2) if self.n_comp == 1 else (nc, self.n_comp, 2)
-        if params.shape != want:
-            raise ValueError(f"params has shape {params.shape}; expected {want}")
-        return self._host_call("hommx_solve_batch_separable", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch_separable(
-            self._h, nc, fam, nq, table.ctypes.data, None if w is None else w.ctypes.data, params.ctypes.data, Mp, o, i), return_info)
+        return self._solve_stream(CoefStream.separable(family, table, weights, params), M, return_info)
 
     def solve_program(self, points: np.ndarray, weights: np.ndarray, program: Program, midpoints: np.ndarray, M: np.ndarray | None = None,
                       return_info: bool = False):
@@ -725,34 +714,29 @@ class MicroCellPlan:
         weights[n_q] of the micro quadrature rule, the program, midpoints[N_c, 3 + program.n_fields] of the macro cells -> A_eff[N_c, t, t]."""
         stream = CoefStream("solve_program", (np.ascontiguousarray(points, dtype=np.float64), np.ascontiguousarray(weights, dtype=np.float64), program),
                             np.ascontiguousarray(midpoints, dtype=np.float64))
-        nc = self._check_stream(stream)
-        src = stream.coef_source()
-        return self._host_call("hommx_solve_batch_source", nc, M, lambda Mp, o, i: self._lib.hommx_solve_batch_source(
-            self._h, nc, C.byref(src), Mp, o, i), return_info)
+        return self._solve_stream(stream, M, return_info)
 
     def expand(self, stream: CoefStream) -> np.ndarray:
         """The element stream coef[N_c, n_el(, n_comp)] the library expands ``stream`` to on the device (hommx_expand_source): what
         ``solve`` would be given.  A program's stream equals ``Expression.host_stream`` bit for bit for exactly rounded operations."""
+        return self._expand("hommx_expand_source", stream)[0]
+
+    def _expand(self, what: str, stream: CoefStream, *slots: int) -> tuple:
+        """Check ``stream``, allocate coef[N_c, n_el(, n_comp)] and one array [N_c, k, n_el(, n_comp)] for every k of ``slots``, and run the
+        host entry point ``what``(plan, N_c, source, outputs...) unless the batch is empty."""
         nc = self._check_stream(stream)
-        out = np.empty((nc, self.n_el) + ((self.n_comp,) if self.n_comp > 1 else ()), dtype=np.float64)
+        outs = tuple(np.empty((nc,) + lead + self._el, dtype=np.float64) for lead in [()] + [(k,) for k in slots])
         if nc:
             src = stream.coef_source()
-            _lib.check(self._lib.hommx_expand_source(self._h, nc, C.byref(src), out.ctypes.data), "hommx_expand_source")
-        return out
+            _lib.check(getattr(self._lib, what)(self._h, nc, C.byref(src), *(o.ctypes.data for o in outs)), what)
+        return outs
 
     def expand_tangents(self, stream: CoefStream) -> tuple[np.ndarray, np.ndarray]:
         """(coef[N_c, n_el(, n_comp)], dirs[N_c, n_params + n_fields, n_el(, n_comp)]) of the program stream of an expression with
         parameters or fields (hommx_expand_tangents): the stream of ``expand``, bit for bit, and its derivatives with respect to the
         parameters, then the fields (of a cell: its own value), formed in one
         forward-mode pass on the device.  dirs equals ``Expression.host_tangents`` bit for bit for exactly rounded operations."""
-        n_params = self._parameter_count(stream)
-        nc = self._check_stream(stream)
-        el = (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
-        coef, dirs = np.empty((nc,) + el, dtype=np.float64), np.empty((nc, n_params) + el, dtype=np.float64)
-        if nc:
-            src = stream.coef_source()
-            _lib.check(self._lib.hommx_expand_tangents(self._h, nc, C.byref(src), coef.ctypes.data, dirs.ctypes.data), "hommx_expand_tangents")
-        return coef, dirs
+        return self._expand("hommx_expand_tangents", stream, self._parameter_count(stream))
 
     def expand_second_tangents(self, stream: CoefStream) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(coef, dirs, curv[N_c, n_pairs, n_el(, n_comp)]) of the program stream of an expression with parameters or fields
@@ -761,15 +745,7 @@ class MicroCellPlan:
         in one second-order forward-mode pass on the device (one per pair of slots for 3 or 4 slots).  curv equals
         ``Expression.host_second_tangents`` bit for bit for exactly rounded operations."""
         n_tan = self._parameter_count(stream)
-        nc = self._check_stream(stream)
-        el = (self.n_el,) + ((self.n_comp,) if self.n_comp > 1 else ())
-        coef, dirs = np.empty((nc,) + el, dtype=np.float64), np.empty((nc, n_tan) + el, dtype=np.float64)
-        curv = np.empty((nc, n_tan * (n_tan + 1) // 2) + el, dtype=np.float64)
-        if nc:
-            src = stream.coef_source()
-            _lib.check(self._lib.hommx_expand_second_tangents(self._h, nc, C.byref(src), coef.ctypes.data, dirs.ctypes.data, curv.ctypes.data),
-                       "hommx_expand_second_tangents")
-        return coef, dirs, curv
+        return self._expand("hommx_expand_second_tangents", stream, n_tan, n_tan * (n_tan + 1) // 2)
 
     # -- device pointers (torch tensors or raw ints), asynchronous --------------------------------
     def expand_second_tangents_device(self, n_cells: int, source: "_lib.CoefSource", coef_ptr: int | None, dirs_ptr: int | None, curv_ptr: int,
@@ -848,12 +824,7 @@ class MicroCellPlan:
         ``CoefStream.coef_source(upload)`` with device addresses; dirs[n_dirs, n_el, n_comp] or, ``per_cell``, [n_cells, n_dirs, n_el, n_comp]
         -> d2A[n_cells, n_dirs, n_dirs, t, t]; dA[n_cells, n_dirs, t, t] on request.  ``per_cell="parameters"``: as in
         ``sensitivities_device``; with ``curvature=True`` d2A takes the curvature term as well (HOMMX_DIRS_PARAMETERS_CURVATURE)."""
-        code = _per_cell_code(per_cell)
-        if curvature:
-            if code != _lib.DIRS_PARAMETERS:
-                raise ValueError('curvature=True needs per_cell="parameters": the curvature term is that of the program\'s own parameters')
-            code = _lib.DIRS_PARAMETERS_CURVATURE
-        args = _lib.Sens2Args(int(n_dirs), code, dirs_ptr or None, d2A_ptr or None, dA_ptr or None, A_ptr or None, info_ptr or None)
+        args = _lib.Sens2Args(int(n_dirs), _per_cell_code(per_cell, curvature), dirs_ptr or None, d2A_ptr or None, dA_ptr or None, A_ptr or None, info_ptr or None)
         _lib.check(self._lib.hommx_second_sensitivity_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
                                                                     stream or None),
                    "hommx_second_sensitivity_source_device")

@@ -177,9 +177,9 @@ def _on_rccl(group=None) -> bool:
 
 
 def solve_block(plan, stream: CoefStream, M: np.ndarray | None, group=None):
-    """One rank's block of cells through ``plan`` -> (A_eff, info).  A ``MicroCellPlan`` under the RCCL backend: every array of the
-    stream and ``M`` are uploaded to the plan's device, the device twin of the stream's method runs on torch's current stream and the
-    result stays there (torch tensors) until the collective.  Otherwise the host method of ``plan``, with ``return_info=True``."""
+    """One rank's block of cells through ``plan`` -> (A_eff, info).  A ``MicroCellPlan`` under the RCCL backend: the arrays of the
+    stream and ``M`` are uploaded to the plan's device, ``solve_source_device`` runs on torch's current stream and the result stays
+    there (torch tensors) until the collective.  Otherwise the host method of ``plan``, with ``return_info=True``."""
     if not (isinstance(plan, MicroCellPlan) and _on_rccl(group)):
         return stream.solve(plan, M, return_info=True)
     import torch

@@ -19,6 +19,7 @@ The micro solves have NO CPU path in this package: without the HIP library / a G
 
 from __future__ import annotations
 
+import dataclasses
 import logging
 from abc import ABC, abstractmethod
 from collections.abc import Callable
@@ -28,12 +29,18 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import fem
-from .batch import (REGION_FIELDS, CoefStream, LoadResponse, MicroCellPlan, Reconstruction, SecondSensitivities, Sensitivities,
-                    StratSensitivities, region_labels)
+from .batch import CoefStream, LoadResponse, MicroCellPlan, Reconstruction, SecondSensitivities, Sensitivities, StratSensitivities, region_labels
 from .expr import Expression
 from .mesh import Mesh, micro_cells_per_side
 
 _VOIGT = {2: [(0, 0), (1, 1), (0, 1)], 3: [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]}
+
+
+def _join(parts: list, **override):
+    """The results of the chunks of a batch (one of the result dataclasses of ``batch``) as one: every field concatenated along the
+    cells, a field that is None staying None, the fields of ``override`` as given (what the chunks do not know: ``cells``, ``names``)."""
+    cat = lambda name: None if getattr(parts[0], name) is None else np.concatenate([getattr(r, name) for r in parts])
+    return type(parts[0])(**{f.name: override[f.name] if f.name in override else cat(f.name) for f in dataclasses.fields(parts[0])})
 
 
 def _unroll_dofs(dofs: np.ndarray, bs: int) -> np.ndarray:
@@ -86,6 +93,11 @@ class Lame:
 
     def __init__(self, lam, mu):
         self.lam, self.mu = lam, mu
+
+
+def _lame_stacked(v: Lame, shape: tuple) -> np.ndarray:
+    """[shape..., 2] = (lambda, mu), each broadcast to ``shape``: the layout the sampling takes an isotropic coefficient in."""
+    return np.stack([np.broadcast_to(np.asarray(v.lam, float), shape), np.broadcast_to(np.asarray(v.mu, float), shape)], axis=-1)
 
 
 class TwoPhase:
@@ -349,16 +361,43 @@ class BaseHMM(ABC):
         """[num_cells] (a scalar macro space) or [num_cells, d]: the mean of the vertex values of the macro field ``u`` (a macro
         ``fem.Function`` or its dof array; default: the last ``solve()`` result) on every macro cell -- u_H at the cell midpoint, what a
         solution-dependent coefficient ``A(x, u_H(x), y)`` is fed: ``h.set_fields(h.cell_means(u))``."""
-        if u is None:
-            if not self._solved:
-                raise RuntimeError("cell_means() needs a macro solution: call solve() first or pass u")
-            u = self._u
-        x = np.asarray(u.x.array if hasattr(u, "x") else u, dtype=float)
-        if x.shape != (self._num_global_dofs,):
-            raise ValueError(f"u has {x.size} dofs; the macro space has {self._num_global_dofs}")
-        uT = x[_unroll_dofs(self._msh.cells.astype(np.int64), self._bs)]  # [nc, (d + 1) * bs], dof = vertex * bs + component
+        uT = self._macro_dofs(self._or_last_solve(u, "cell_means"))[self._cell_dofs()]  # [nc, (d + 1) * bs], dof = vertex * bs + component
         mean = uT.reshape(uT.shape[0], -1, self._bs).mean(axis=1)
         return mean[:, 0] if self._bs == 1 else mean
+
+    # -- the arguments every method takes --------------------------------------------------------------
+    def _or_last_solve(self, u, method: str):
+        """``u`` of the public method ``method``: None means the last ``solve()`` result."""
+        if u is None:
+            if not self._solved:
+                raise RuntimeError(f"{method}() needs a macro solution: call solve() first or pass u")
+            u = self._u
+        return u
+
+    def _macro_dofs(self, u, subject: str = "u") -> np.ndarray:
+        """The dof vector of a macro field (a macro ``fem.Function`` or its dof array), checked against the macro space."""
+        x = np.asarray(u.x.array if hasattr(u, "x") else u, dtype=float)
+        if x.shape != (self._num_global_dofs,):
+            raise ValueError(f"{subject} has {x.size} dofs; the macro space has {self._num_global_dofs}")
+        return x
+
+    def _cells_argument(self, cells, method: str, local: bool) -> np.ndarray:
+        """``cells`` of the public method ``method`` as int64[N], N >= 1: None means every macro cell, or (``local``) this rank's."""
+        if cells is None:
+            cells = self._local_cells() if local else np.arange(self._msh.num_cells)
+        else:
+            cells = np.asarray(cells, dtype=np.int64).ravel()
+        if len(cells) == 0:
+            raise ValueError(f"{method}() needs at least one macro cell")
+        return cells
+
+    def _cell_dofs(self, cells=slice(None)) -> np.ndarray:
+        """[N, nb]: the macro dofs of ``cells`` (default: every macro cell), dof = vertex * bs + component."""
+        return _unroll_dofs(self._msh.cells[cells].astype(np.int64), self._bs)
+
+    def _volume_ratio(self, cells=slice(None)) -> np.ndarray:
+        """vol(T) / vol(Y) of ``cells`` (default: every macro cell)."""
+        return self._msh.cell_volumes()[cells] / self._cell_mesh_area
 
     def _cell_rows(self, cells: np.ndarray, coeff=None) -> np.ndarray:
         """x of ``coeff`` (default: the coefficient) on ``cells``: the midpoints [N, 3] and, for an ``Expression`` with fields, the fields
@@ -397,9 +436,7 @@ class BaseHMM(ABC):
         coefficient's shape (a direction of ``tensor_derivatives``) instead of A."""
         v = (coeff or self._coeff)(c_T, yq)
         if isinstance(v, Lame):
-            lam = np.broadcast_to(np.asarray(v.lam, float), (yq.shape[1],))
-            mu = np.broadcast_to(np.asarray(v.mu, float), (yq.shape[1],))
-            return np.stack([lam, mu], axis=-1)
+            return _lame_stacked(v, (yq.shape[1],))
         v = np.asarray(v, dtype=float)
         if v.ndim == 0 or v.shape[0] != yq.shape[1]:
             v = np.broadcast_to(v, (yq.shape[1],) + v.shape).copy()
@@ -482,9 +519,7 @@ class BaseHMM(ABC):
                 xb = c[a : a + chunk].T[:, :, None]
                 v = (coeff or self._coeff)(xb, yflat[:, None, :])
                 if isinstance(v, Lame):
-                    lam = np.broadcast_to(np.asarray(v.lam, float), (xb.shape[1], npts))
-                    mu = np.broadcast_to(np.asarray(v.mu, float), (xb.shape[1], npts))
-                    v = np.stack([lam, mu], axis=-1)
+                    v = _lame_stacked(v, (xb.shape[1], npts))
                 else:
                     v = np.asarray(v, dtype=float)
                     if v.ndim < 2 or v.shape[:2] != (xb.shape[1], npts):
@@ -665,6 +700,13 @@ class BaseHMM(ABC):
             return "solve_program"
         return None
 
+    def _sampled_on_device(self) -> str | None:
+        """The plan method that samples this coefficient on the device WITH THE PLAN THAT STANDS HERE, or None for sampled element
+        means: the coefficient has a device form (``_device_form``) and the plan offers that method -- a ``MicroCellPlan`` offers all
+        of them, a stand-in may not (``_coef_stream``).  This is the one place that asks."""
+        form = self._device_form()
+        return form if form is not None and hasattr(self._ensure_plan(self._micro_kind()), form) else None
+
     def _coef_stream(self, cells: np.ndarray) -> tuple[CoefStream, str]:
         """The coefficient of ``cells`` as the plan takes it, and the plan kind: ``TwoPhase`` as one mask (evaluated at the element
         barycentres) + two values per cell, ``Separable`` as one table of g + (a, b) per cell (per Lame parameter for the elasticity
@@ -674,13 +716,13 @@ class BaseHMM(ABC):
         What stands in ``self._plan`` is a ``MicroCellPlan`` or a stand-in for it (the CPU tests answer from a NumPy restatement).  A stand-in has
         ``t``, ``kind`` and ``solve(coef, M=None, return_info=False[, return_correctors])``; it may have ``reserve`` (needed by
         ``prepare()``), ``reconstruct``, ``device``, ``solve_two_phase``, ``solve_separable`` and ``solve_program``.  Without the last three it gets those
-        coefficients as element means: this is the one place that asks.  ``reconstruct(coef, xi, M, fields=...)`` is given element means
+        coefficients as element means (``_sampled_on_device``: the one place that asks).  ``reconstruct(coef, xi, M, fields=...)`` is given element means
         as an array and a device-sampled coefficient as the ``CoefStream``, under the same rule."""
-        form, kind = self._device_form(), self._micro_kind()
-        if form is None or not hasattr(self._ensure_plan(kind), form):
+        form = self._sampled_on_device()
+        if form is None:
             coef, kind = self._element_means(cells)
             return CoefStream.sampled(coef), kind
-        co, c = self._coeff, self._cell_rows(cells)
+        kind, co, c = self._micro_kind(), self._coeff, self._cell_rows(cells)
         if form == "solve_two_phase":
             mask = self._phase_mask()
             values = co.phase_values(c)
@@ -729,19 +771,34 @@ class BaseHMM(ABC):
 
         return np.ascontiguousarray(self._sampled_means(cells, components_last)[:, None]), True
 
-    def _load_block(self, cells: np.ndarray, **kw) -> LoadResponse:
-        """``plan.loads`` of the polarisation on ``cells``: the coefficient crosses the boundary as ``solve()`` sends it."""
+    def _plan_inputs(self, cells: np.ndarray, sample=None) -> tuple:
+        """(plan, coef, M, sampled) of ``cells`` for the derived outputs of a plan (``reconstruct``, ``loads``, the sensitivities): the
+        coefficient crosses the boundary as ``solve()`` sends it (``_coef_stream``).  ``sample(cells, kind)``: what else the caller
+        samples on these cells (a polarisation, directions) -- after the coefficient and before the plan is asked for, so that what it
+        raises comes first."""
         stream, kind = self._coef_stream(cells)
         coef = stream.per_cell if stream.method == "solve" else stream  # element means as the array every plan (and stand-in) takes
-        P, per_cell = self._polarisation_loads(cells)
-        return self._ensure_plan(kind).loads(coef, P, self._stratification(cells), per_cell=per_cell, **kw)
+        sampled = None if sample is None else sample(cells, kind)
+        return self._ensure_plan(kind), coef, self._stratification(cells), sampled
+
+    def _chunks(self, cells: np.ndarray, chunk_cells: int | None, bytes_per_cell, call, sample=None) -> list:
+        """The results of ``call(plan, coef, M, sampled, sub, b)`` on ``cells`` in chunks ``sub = cells[b:b + chunk_cells]`` with the
+        ``_plan_inputs`` of each.  ``chunk_cells`` None: 256 MB of what ``bytes_per_cell()`` counts for one cell -- every method has its
+        own figure, for what it streams."""
+        ch = max(1, int((256 << 20) // bytes_per_cell() if chunk_cells is None else chunk_cells))
+        return [call(*self._plan_inputs(cells[b:b + ch], sample), cells[b:b + ch], b) for b in range(0, len(cells), ch)]
+
+    def _load_blocks(self, cells: np.ndarray, chunk_cells: int | None, bytes_per_cell=None, **kw) -> list:
+        """``plan.loads`` of the polarisation on ``cells``, chunk by chunk."""
+        return self._chunks(cells, chunk_cells, bytes_per_cell, lambda plan, coef, M, P, sub, b: plan.loads(coef, P[0], M, per_cell=P[1], **kw),
+                            lambda sub, kind: self._polarisation_loads(sub))
 
     def _effective_polarisation(self, cells: np.ndarray) -> np.ndarray:
         """P_eff[N, t] of ``cells`` (Levin: from the canonical correctors, on every route).  Under a process group every rank solves its
         block and one more all-gather of t numbers per cell returns the field to every rank; a failing rank makes all ranks raise."""
 
         def block(b, e):
-            r = self._load_block(cells[b:e])
+            (r,) = self._load_blocks(cells[b:e], e - b)
             return r.P_eff[:, 0], r.info
 
         if self._sharded():
@@ -767,7 +824,7 @@ class BaseHMM(ABC):
     def _local_stiffness_from_tensors(self, cells: np.ndarray, AH: np.ndarray) -> np.ndarray:
         """S_loc = vol(T)/vol(Y) * (macro gradients) A_H (macro gradients)^T  == hmm.py:361-369."""
         G, Wv = self._strain_basis(cells)
-        vol = self._msh.cell_volumes()[cells] / self._cell_mesh_area
+        vol = self._volume_ratio(cells)
         if Wv is None:
             return vol[:, None, None] * np.einsum("cai,cij,cbj->cab", G, AH, G)
         return vol[:, None, None] * np.einsum("cam,cmn,cbn->cab", Wv, AH, Wv)
@@ -803,13 +860,16 @@ class BaseHMM(ABC):
         _, chi = self._ensure_plan(kind).solve(coef, M, return_correctors=True)  # [1, t, n^d * bs]
         G, W = self._strain_basis(cells)
         Wv = (G if W is None else W)[0]  # [nb, t]
-        per = self._eps * (Wv @ chi[0])  # [nb, n^d * bs]
+        return self._on_micro_mesh(self._eps * (Wv @ chi[0]))  # [nb, n^d * bs]
+
+    def _on_micro_mesh(self, rows: np.ndarray) -> list[fem.Function]:
+        """rows[k, n_nodes * bs] on the periodic unknowns -> one function on the micro mesh per row."""
         idx = self._periodic_to_micro_nodes()
         V_micro = fem.FunctionSpace(self._cell_mesh, self._bs)
         out = []
-        for i in range(per.shape[0]):
+        for row in rows:
             f = fem.Function(V_micro)
-            f.x.array[:] = per[i].reshape(-1, self._bs)[idx].ravel()
+            f.x.array[:] = row.reshape(-1, self._bs)[idx].ravel()
             out.append(f)
         return out
 
@@ -828,7 +888,7 @@ class BaseHMM(ABC):
 
     def _set_macro_matrix(self, S: np.ndarray):
         """Local stiffness matrices S[nc, nb, nb] of all macro cells -> the CSR macro matrix (MatSetValues(ADD), hmm.py:325-330)."""
-        dofs = _unroll_dofs(self._msh.cells.astype(np.int64), self._bs)  # [nc, nb]
+        dofs = self._cell_dofs()  # [nc, nb]
         nb = dofs.shape[1]
         rows = np.repeat(dofs, nb, axis=1).ravel()
         cols = np.tile(dofs, (1, nb)).ravel()
@@ -845,9 +905,8 @@ class BaseHMM(ABC):
             cells = np.arange(self._msh.num_cells)
             self.effective_polarisation = self._effective_polarisation(cells)
             G, Wv = self._strain_basis(cells)
-            vol = self._msh.cell_volumes() / self._cell_mesh_area
-            bT = -vol[:, None] * np.einsum("cbm,cm->cb", G if Wv is None else Wv, self.effective_polarisation)
-            np.add.at(b, _unroll_dofs(self._msh.cells.astype(np.int64), self._bs).ravel(), bT.ravel())
+            bT = -self._volume_ratio()[:, None] * np.einsum("cbm,cm->cb", G if Wv is None else Wv, self.effective_polarisation)
+            np.add.at(b, self._cell_dofs().ravel(), bT.ravel())
         for bc in self._bcs:  # hmm.py:453-480, bc by bc
             idx, val = bc.unrolled()
             u_bc = np.zeros(self._num_global_dofs)
@@ -869,7 +928,7 @@ class BaseHMM(ABC):
         """xi[c] of the macro field u on every cell: grad u_H|_T (Poisson), or the Voigt vector of eps(u_H)|_T with doubled shear -- W^T u_T
         with the W of ``_local_stiffness_from_tensors``, so that u_T . S_loc u_T = vol(T) xi . A_H xi."""
         G, Wv = self._strain_basis(cells)
-        uT = u[_unroll_dofs(self._msh.cells[cells].astype(np.int64), self._bs)]  # [nc, nb]
+        uT = u[self._cell_dofs(cells)]  # [nc, nb]
         if Wv is None:
             return np.einsum("ca,cai->ci", uT, G)
         return np.einsum("cb,cbm->cm", uT, Wv)
@@ -903,37 +962,21 @@ class BaseHMM(ABC):
         The cells are reconstructed in chunks of ``chunk_cells`` (default: about 256 MB of coefficient stream when it is sampled on the
         host, of outputs when it is sampled on the device).  Under a process group this runs on the calling rank alone, for the cells it
         is given: there is no collective."""
-        if u is None:
-            if not self._solved:
-                raise RuntimeError("reconstruct() needs a macro solution: call solve() first or pass u")
-            u = self._u
-        x = np.asarray(u.x.array if hasattr(u, "x") else u, dtype=float)
-        if x.shape != (self._num_global_dofs,):
-            raise ValueError(f"u has {x.size} dofs; the macro space has {self._num_global_dofs}")
-        cells = np.arange(self._msh.num_cells) if cells is None else np.asarray(cells, dtype=np.int64).ravel()
-        if len(cells) == 0:
-            raise ValueError("reconstruct() needs at least one macro cell")
+        x = self._macro_dofs(self._or_last_solve(u, "reconstruct"))
+        cells = self._cells_argument(cells, "reconstruct", local=False)
         xi = self._macro_strains(cells, x)
         labels = self._region_labels(regions)
         kw = {} if labels is None else {"regions": labels[0], "n_regions": labels[1]}
-        if chunk_cells is None:
+
+        def bytes_per_cell():
             n_el, t = self._cell_mesh.num_cells, self._tensor_size()
-            form = self._device_form()
-            if form is not None and hasattr(self._ensure_plan(self._micro_kind()), form):  # the rule of _coef_stream
-                per = 8 * (2 * t + 3 + t * t + (labels[1] * (2 * t + 4) if labels else 0) + (2 * n_el * t if fields else 0)) + 4
-            else:
-                per = n_el * (1 if self._kind == "poisson" else 2) * 8
-            chunk_cells = (256 << 20) // per
-        ch = max(1, int(chunk_cells))
-        parts = []
-        for b in range(0, len(cells), ch):
-            sub = cells[b:b + ch]
-            stream, kind = self._coef_stream(sub)
-            coef = stream.per_cell if stream.method == "solve" else stream  # element means as the array every plan (and stand-in) takes
-            parts.append(self._ensure_plan(kind).reconstruct(coef, xi[b:b + ch], self._stratification(sub), fields=fields, **kw))
-        cat = lambda name: None if getattr(parts[0], name) is None else np.concatenate([getattr(r, name) for r in parts])
-        return Reconstruction(xi, cat("mean_strain"), cat("mean_flux"), cat("energy"), cat("max_flux"), cat("argmax_element"), cat("A_eff"),
-                              cat("info"), cat("strain"), cat("flux"), cells, *(cat(name) for name in REGION_FIELDS))
+            if self._sampled_on_device():  # the outputs
+                return 8 * (2 * t + 3 + t * t + (labels[1] * (2 * t + 4) if labels else 0) + (2 * n_el * t if fields else 0)) + 4
+            return n_el * (1 if self._kind == "poisson" else 2) * 8  # the coefficient stream
+
+        parts = self._chunks(cells, chunk_cells, bytes_per_cell,
+                             lambda plan, coef, M, _, sub, b: plan.reconstruct(coef, xi[b:b + len(sub)], M, fields=fields, **kw))
+        return _join(parts, xi=xi, cells=cells)
 
     def load_response(self, cells=None, fields: bool = False, correctors: bool = False, chunk_cells: int | None = None) -> LoadResponse:
         """The response of the sampling boxes of ``cells`` (default: every macro cell) to the polarisation alone (hommx_loads_source with
@@ -947,19 +990,15 @@ class BaseHMM(ABC):
         this runs on the calling rank alone, for the cells it is given: there is no collective."""
         if self._polarisation is None:
             raise RuntimeError("load_response() needs a polarisation: call set_polarisation() first")
-        cells = np.arange(self._msh.num_cells) if cells is None else np.asarray(cells, dtype=np.int64).ravel()
-        if len(cells) == 0:
-            raise ValueError("load_response() needs at least one macro cell")
-        if chunk_cells is None:
+        cells = self._cells_argument(cells, "load_response", local=False)
+
+        def bytes_per_cell():
             n_el, t = self._cell_mesh.num_cells, self._tensor_size()
             n_dof = (int(self._periodic_to_micro_nodes().max()) + 1) * self._bs if correctors else 0
             # doubles per cell: P[n_el, t] | P_eff, energy, stats, A_eff | strain and flux | corrector (info: 4 bytes more)
-            chunk_cells = (256 << 20) // (8 * (n_el * t + (t + 1 + t + 2 + t * t) + (2 * n_el * t if fields else 0) + n_dof) + 4)
-        ch = max(1, int(chunk_cells))
-        parts = [self._load_block(cells[b:b + ch], response=True, fields=fields, return_correctors=correctors) for b in range(0, len(cells), ch)]
-        cat = lambda name: None if getattr(parts[0], name) is None else np.concatenate([getattr(r, name) for r in parts])
-        return LoadResponse(cat("P_eff"), cat("A_eff"), cat("info"), cat("energy"), cat("mean_flux"), cat("max_flux"), cat("argmax_element"),
-                            cat("strain"), cat("flux"), cat("correctors"), cells)
+            return 8 * (n_el * t + (t + 1 + t + 2 + t * t) + (2 * n_el * t if fields else 0) + n_dof) + 4
+
+        return _join(self._load_blocks(cells, chunk_cells, bytes_per_cell, response=True, fields=fields, return_correctors=correctors), cells=cells)
 
     def _parameter_directions(self) -> tuple[tuple, np.ndarray]:
         """(names, directions[n_dirs, n_el(, n_comp)]) of the parameters of a ``TwoPhase`` or affine ``Separable`` coefficient: the element
@@ -1007,21 +1046,37 @@ class BaseHMM(ABC):
         there is no collective."""
         names, cells, parts = self._direction_blocks("tensor_derivatives", cells, directions, chunk_cells,
                                                      lambda plan, coef, M, **kw: plan.sensitivities(coef, M, **kw))
-        cat = lambda name: np.concatenate([getattr(r, name) for r in parts])
-        return Sensitivities(cat("dA"), None, cat("A_eff"), cat("info"), names, cells)
+        return _join(parts, grad=None, names=names, cells=cells)
 
     def _direction_blocks(self, what: str, cells, directions, chunk_cells: int | None, call, curvature: bool = False) -> tuple[tuple, np.ndarray, list]:
         """(names, cells, results) of ``call(plan, coef, M, directions=..., per_cell=...)`` over ``cells`` (default: this rank's macro
         cells) in chunks of ``chunk_cells``: the cells, names and directions of ``tensor_derivatives`` and ``tensor_second_derivatives``.
         ``curvature``: the parameter directions of a device-sampled ``Expression`` with the curvature term, for any ``p_degree``
         (``call`` then also takes ``curvature=True``); every other coefficient raises ``ValueError``."""
-        cells = self._local_cells() if cells is None else np.asarray(cells, dtype=np.int64).ravel()
-        if len(cells) == 0:
-            raise ValueError(f"{what}() needs at least one macro cell")
-        co = self._coeff
+        cells = self._cells_argument(cells, what, local=True)
         self._cell_rows(cells[:1])  # an Expression whose fields are not set: the RuntimeError that names set_fields, before anything else
-        if directions is None and isinstance(co, Expression) and (co.n_params or co.n_fields) and self._device_form() == "solve_program" \
-                and hasattr(self._ensure_plan(self._micro_kind()), "solve_program"):
+        names, shared, directions = self._directions(what, directions, curvature)
+        more = {"curvature": True} if curvature else {}
+
+        def sample(sub, kind):  # the caller's directions on a chunk, each sampled as the coefficient is
+            if shared is not None:
+                return shared
+            sampled = [self._element_means(sub, f) for f in directions]
+            if any(k != kind for _, k in sampled):
+                raise ValueError(f"every direction must have the coefficient's shape (plan kind {kind!r}); got {[k for _, k in sampled]}")
+            return np.stack([d for d, _ in sampled], axis=1)
+
+        streams = 1 + (len(directions) if shared is None else 0)  # the parameter tangents never cross the boundary
+        parts = self._chunks(cells, chunk_cells, lambda: 8 * self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) * streams,
+                             lambda plan, coef, M, dirs, sub, b: call(plan, coef, M, directions=dirs, per_cell=shared is None, **more), sample)
+        return names, cells, parts
+
+    def _directions(self, what: str, directions, curvature: bool) -> tuple[tuple, object, list | None]:
+        """(names, shared, callables) of the directions of ``_direction_blocks``.  ``shared``: the directions every cell shares
+        [n_dirs, n_el(, n_comp)] (``_parameter_directions``), ``"parameters"`` (the parameter tangents of a device-sampled
+        ``Expression``), or None: ``callables``, the caller's ``directions``, are sampled cell by cell."""
+        co = self._coeff
+        if directions is None and isinstance(co, Expression) and (co.n_params or co.n_fields) and self._sampled_on_device() == "solve_program":
             # the parameter tangents of the program, formed on the device with the stream: nothing is sampled, no direction stream is sent
             if what == "tensor_second_derivatives" and not co.affine_in_parameters and not curvature:
                 raise ValueError(
@@ -1045,24 +1100,7 @@ class BaseHMM(ABC):
         else:
             directions = list(directions)
             names, shared = tuple(getattr(f, "__name__", f"direction{k}") for k, f in enumerate(directions)), None
-        if chunk_cells is None:
-            streams = 1 + (len(directions) if shared is None else 0)  # the parameter tangents never cross the boundary
-            chunk_cells = (256 << 20) // (8 * self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) * streams)
-        ch = max(1, int(chunk_cells))
-        parts = []
-        for b in range(0, len(cells), ch):
-            sub = cells[b:b + ch]
-            stream, kind = self._coef_stream(sub)
-            coef = stream.per_cell if stream.method == "solve" else stream
-            dirs = shared
-            if dirs is None:
-                sampled = [self._element_means(sub, f) for f in directions]
-                if any(k != kind for _, k in sampled):
-                    raise ValueError(f"every direction must have the coefficient's shape (plan kind {kind!r}); got {[k for _, k in sampled]}")
-                dirs = np.stack([d for d, _ in sampled], axis=1)
-            more = {"curvature": True} if curvature else {}
-            parts.append(call(self._ensure_plan(kind), coef, self._stratification(sub), directions=dirs, per_cell=shared is None, **more))
-        return names, cells, parts
+        return names, shared, directions
 
     def energy_derivatives(self, u=None, v=None, **kw) -> np.ndarray:
         """[N, n_dirs]: vol(T)/vol(Y) xi_v(T) . dA_H[d](T) xi_u(T) for the cells and directions of ``tensor_derivatives(**kw)``, with xi the
@@ -1070,25 +1108,16 @@ class BaseHMM(ABC):
         the compliance gradient for v = u (the default; ``u`` defaults to the last ``solve()`` result), the adjoint product otherwise.
         For a field ``f[k]`` of an ``Expression`` only cell T depends on the value of T, so entry ``[T, n_params + k]`` is the WHOLE
         derivative of u . K_H u at frozen u with respect to the design variable (T, k), not one contribution among many."""
-        if u is None:
-            if not self._solved:
-                raise RuntimeError("energy_derivatives() needs a macro solution: call solve() first or pass u")
-            u = self._u
+        u = self._or_last_solve(u, "energy_derivatives")
         td = self.tensor_derivatives(**kw)
         xv, xu, vol = self._energy_weights(td.cells, u, v)
         return vol[:, None] * np.einsum("cm,cdmn,cn->cd", xv, td.dA, xu)
 
     def _energy_weights(self, cells: np.ndarray, u, v) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(xi_v[N, t], xi_u[N, t], vol(T)/vol(Y)[N]) of ``cells``: the macro gradient / Voigt strain of the macro fields (``v`` None: u)."""
-
-        def xi(f):
-            x = np.asarray(f.x.array if hasattr(f, "x") else f, dtype=float)
-            if x.shape != (self._num_global_dofs,):
-                raise ValueError(f"the macro field has {x.size} dofs; the macro space has {self._num_global_dofs}")
-            return self._macro_strains(cells, x)
-
+        xi = lambda f: self._macro_strains(cells, self._macro_dofs(f, "the macro field"))
         xu = xi(u)
-        return (xu if v is None else xi(v)), xu, self._msh.cell_volumes()[cells] / self._cell_mesh_area
+        return (xu if v is None else xi(v)), xu, self._volume_ratio(cells)
 
     def tensor_second_derivatives(self, cells=None, directions=None, chunk_cells: int | None = None,
                                   curvature: bool = False) -> SecondSensitivities:
@@ -1112,18 +1141,14 @@ class BaseHMM(ABC):
         names, cells, parts = self._direction_blocks("tensor_second_derivatives", cells, directions, chunk_cells,
                                                      lambda plan, coef, M, **kw: plan.second_sensitivities(coef, M, first=True, **kw),
                                                      curvature=curvature)
-        cat = lambda name: np.concatenate([getattr(r, name) for r in parts])
-        return SecondSensitivities(cat("d2A"), cat("dA"), cat("A_eff"), cat("info"), names, cells)
+        return _join(parts, names=names, cells=cells)
 
     def energy_second_derivatives(self, u=None, v=None, **kw) -> np.ndarray:
         """[N, n_dirs, n_dirs]: vol(T)/vol(Y) xi_v(T) . d2A_H[a][b](T) xi_u(T) for the cells and directions of
         ``tensor_second_derivatives(**kw)`` -- the contribution of macro cell T to the second derivative of v . K_H u at FROZEN u, v
         (``u`` defaults to the last ``solve()`` result, ``v`` to u).  The response of u itself to the parameters (the du/dtheta terms of a
         compliance or misfit Hessian) is the caller's macro solve: it needs ``energy_derivatives`` and K_H, not the cell problems."""
-        if u is None:
-            if not self._solved:
-                raise RuntimeError("energy_second_derivatives() needs a macro solution: call solve() first or pass u")
-            u = self._u
+        u = self._or_last_solve(u, "energy_second_derivatives")
         td = self.tensor_second_derivatives(**kw)
         xv, xu, vol = self._energy_weights(td.cells, u, v)
         return vol[:, None, None] * np.einsum("cm,cabmn,cn->cab", xv, td.d2A, xu)
@@ -1140,19 +1165,11 @@ class BaseHMM(ABC):
     def _stratification_blocks(self, cells: np.ndarray, chunk_cells: int | None, weights=None, full: bool = True) -> list:
         """``plan.stratification_sensitivities`` of ``cells`` in chunks of ``chunk_cells`` (default: about 256 MB of coefficient stream
         and outputs); the coefficient crosses the boundary as ``solve()`` sends it."""
-        if chunk_cells is None:
-            d, t = self._tdim, self._tensor_size()
-            per = 8 * (self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) + d * d * (t * t if full else 1) + 2 * t * t) + 4
-            chunk_cells = (256 << 20) // per
-        ch = max(1, int(chunk_cells))
-        parts = []
-        for b in range(0, len(cells), ch):
-            sub = cells[b:b + ch]
-            stream, kind = self._coef_stream(sub)
-            coef = stream.per_cell if stream.method == "solve" else stream
-            parts.append(self._ensure_plan(kind).stratification_sensitivities(coef, self._stratification(sub),
-                                                                              weights=None if weights is None else weights[b:b + ch], full=full))
-        return parts
+        d, t = self._tdim, self._tensor_size()
+        return self._chunks(cells, chunk_cells,
+                            lambda: 8 * (self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) + d * d * (t * t if full else 1) + 2 * t * t) + 4,
+                            lambda plan, coef, M, _, sub, b: plan.stratification_sensitivities(
+                                coef, M, weights=None if weights is None else weights[b:b + len(sub)], full=full))
 
     def stratification_derivatives(self, cells=None, parameters=None, chunk_cells: int | None = None) -> StratSensitivities:
         """Derivatives of A_H / C_H of ``cells`` (default: this rank's macro cells) with respect to the stratification M = Dtheta^T(c_T)
@@ -1164,12 +1181,8 @@ class BaseHMM(ABC):
         ``dA[N, n_params, t, t]`` = sum_ab dM_p[a, b] dA_dM[:, a, b], the derivative of A_H along each parameter (formed on the host).
 
         The cells run in chunks of ``chunk_cells``.  Under a process group this runs on the calling rank alone: there is no collective."""
-        cells = self._local_cells() if cells is None else np.asarray(cells, dtype=np.int64).ravel()
-        if len(cells) == 0:
-            raise ValueError("stratification_derivatives() needs at least one macro cell")
-        parts = self._stratification_blocks(cells, chunk_cells)
-        cat = lambda name: np.concatenate([getattr(r, name) for r in parts])
-        out = StratSensitivities(cat("dA_dM"), None, cat("A_eff"), cat("info"), cells)
+        cells = self._cells_argument(cells, "stratification_derivatives", local=True)
+        out = _join(self._stratification_blocks(cells, chunk_cells), grad_M=None, cells=cells)
         if parameters is not None:
             out.names, dM = self._stratification_parameters(cells, parameters)
             out.dA = np.einsum("cpab,cabmn->cpmn", dM, out.dA_dM)
@@ -1181,24 +1194,10 @@ class BaseHMM(ABC):
         respect to its M at frozen u, v: the compliance gradient for v = u (the default; ``u`` defaults to the last ``solve()`` result),
         the adjoint product otherwise.  The weights xi_v (x) xi_u go to the device, only d d numbers per cell come back.  With
         ``parameters`` (as ``stratification_derivatives`` takes them) the result is contracted with them: [N, n_params]."""
-        if u is None:
-            if not self._solved:
-                raise RuntimeError("stratification_energy_derivatives() needs a macro solution: call solve() first or pass u")
-            u = self._u
-        cells = self._local_cells() if cells is None else np.asarray(cells, dtype=np.int64).ravel()
-        if len(cells) == 0:
-            raise ValueError("stratification_energy_derivatives() needs at least one macro cell")
-
-        def xi(f):
-            x = np.asarray(f.x.array if hasattr(f, "x") else f, dtype=float)
-            if x.shape != (self._num_global_dofs,):
-                raise ValueError(f"the macro field has {x.size} dofs; the macro space has {self._num_global_dofs}")
-            return self._macro_strains(cells, x)
-
-        xu = xi(u)
-        xv = xu if v is None else xi(v)
+        u = self._or_last_solve(u, "stratification_energy_derivatives")
+        cells = self._cells_argument(cells, "stratification_energy_derivatives", local=True)
+        xv, xu, vol = self._energy_weights(cells, u, v)
         parts = self._stratification_blocks(cells, None, weights=np.einsum("cm,cn->cmn", xv, xu), full=False)
-        vol = self._msh.cell_volumes()[cells] / self._cell_mesh_area
         grad = vol[:, None, None] * np.concatenate([r.grad_M for r in parts])
         if parameters is None:
             return grad
@@ -1316,13 +1315,7 @@ class PoissonPeriodicHMM:
         if info[0]:
             h._logger.error("Something went wrong in the cell problem solving for the periodic cell")
         self._A_hom = AH[0]
-        idx = h._periodic_to_micro_nodes()
-        V_micro = fem.FunctionSpace(h._cell_mesh, 1)
-        self._correctors = []
-        for q in range(chi.shape[1]):
-            f = fem.Function(V_micro)
-            f.x.array[:] = chi[0, q][idx]
-            self._correctors.append(f)
+        self._correctors = h._on_micro_mesh(chi[0])
         return self._A_hom
 
     def solve(self) -> fem.Function:
