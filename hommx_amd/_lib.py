@@ -32,6 +32,8 @@ PROGRAM_MAX_PARAMS = 4  # HOMMX_PROGRAM_MAX_PARAMS
 PROGRAM_MAX_FIELDS = 4  # HOMMX_PROGRAM_MAX_FIELDS
 DIRS_PARAMETERS = 2  # HOMMX_DIRS_PARAMETERS: per_cell of SensArgs / Sens2Args, the directions are the program's parameter tangents
 DIRS_PARAMETERS_CURVATURE = 3  # HOMMX_DIRS_PARAMETERS_CURVATURE: per_cell of Sens2Args, d2A takes the curvature term as well (the Hessian)
+LOADS_SHARED, LOADS_PER_CELL, LOADS_PROGRAM = 0, 1, 2  # HOMMX_LOADS_*: per_cell of LoadArgs, where the load comes from
+LOADS_EIGENSTRAIN = 4  # HOMMX_LOADS_EIGENSTRAIN: a flag or-ed to them, what arrives is an eigenstrain
 
 
 class PlanDesc(C.Structure):
@@ -141,7 +143,8 @@ class StratSensArgs(C.Structure):
 
 
 class LoadArgs(C.Structure):
-    """hommx_load_args: the loads of hommx_loads_source[_device], what is asked for and where it goes."""
+    """hommx_load_args: the loads of hommx_loads_source[_device], what is asked for and where it goes.  ``P_source`` is read for
+    ``LOADS_PROGRAM`` only."""
 
     _fields_ = [
         ("n_loads", C.c_int32),
@@ -155,6 +158,7 @@ class LoadArgs(C.Structure):
         ("flux", C.c_void_p),
         ("correctors", C.c_void_p),
         ("info", C.c_void_p),
+        ("P_source", C.POINTER(CoefSource)),
     ]
 
 

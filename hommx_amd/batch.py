@@ -339,6 +339,8 @@ class MicroCellPlan:
     Replaces the per-right-hand-side ``dolfinx_mpc.LinearProblem`` construction of hmm.py:420-425.
     """
 
+    load_sources = True  # loads() takes a program CoefStream as P and eigenstrain=True (what the solver classes ask a plan before they send either)
+
     def __init__(self, dim: int, n_micro: int, kind: str = "poisson", device: int = 0, flags: int = 0):
         if kind not in KINDS:
             raise ValueError(f"unknown kind {kind!r}; expected one of {sorted(KINDS)}")
@@ -659,26 +661,55 @@ class MicroCellPlan:
         A, info = self._source_call("hommx_stratification_sensitivity_source", nc, M, stream, args)
         return StratSensitivities(dA_dM, grad, A, info)
 
+    def _check_load_stream(self, P: CoefStream, nc: int):
+        """Shapes of the program stream of a load (``CoefStream.program`` of a vector ``Expression``) against the plan."""
+        if P.method != "solve_program":
+            raise ValueError(f"a load given as a CoefStream must be CoefStream.program(...) of a vector Expression; got a {P.method!r} stream")
+        points, weights, prog = P.shared
+        if prog.n_comp != self.t:
+            raise ValueError(f"the load expression has {prog.n_comp} components; a load of this plan has n_comp == t == {self.t}")
+        if points.ndim != 3 or points.shape[0] != self.n_el or points.shape[2] != self.dim or points.shape[1] < 1:
+            raise ValueError(f"points of the load has shape {points.shape}; expected ({self.n_el}, n_q, {self.dim})")
+        if weights.shape != (points.shape[1],):
+            raise ValueError(f"weights of the load must have shape ({points.shape[1]},)")
+        if P.per_cell.shape != (nc, 3 + prog.n_fields):
+            raise ValueError(f"the rows of the load have shape {P.per_cell.shape}; expected ({nc}, 3" + (
+                f" + {prog.n_fields}): the midpoint, then the fields of the load expression" if prog.n_fields else ")"))
+
     def loads(self, coef, P, M: np.ndarray | None = None, per_cell: bool | None = None, response: bool = False, fields: bool = False,
-              return_correctors: bool = False) -> LoadResponse:
+              return_correctors: bool = False, eigenstrain: bool = False) -> LoadResponse:
         """User-supplied polarisation loads (hommx_loads_source): ``coef`` an array or a ``CoefStream`` and M as ``reconstruct`` takes them.
         ``P[n_loads, n_el, t]`` (shared by all cells) or ``P[N_c, n_loads, n_el, t]`` (``per_cell``, inferred from ``P.ndim`` when None):
         up to t prescribed flux / stress fields, constant per micro element, components in the order of ``Reconstruction.flux`` (shear not
         doubled) -> ``LoadResponse``.  ``P_eff`` comes from the canonical correctors alone on every plan; ``response`` adds a solve for the
         loads themselves (energy, mean / max total flux), ``fields`` the per-element strain and total flux of every load,
         ``return_correctors`` the load correctors (each implies ``response``; needs ``load_solve=True`` on the frontal mesh route).  The batch runs in the chunks
-        of ``reconstruct``."""
+        of ``reconstruct``.
+
+        ``P`` may also be a ``CoefStream.program(points, weights, ops, consts, t, rows, ...)`` built from a vector ``Expression`` with
+        t components, the points and weights of a quadrature rule and the rows [N_c, 3 + n_fields] of the cells (HOMMX_LOADS_PROGRAM):
+        ONE load, sampled on the device; only the rows cross per cell.  ``eigenstrain``: what ``P`` delivers -- array or program -- is
+        an eigenstrain E in the components of ``Reconstruction.strain`` (shear DOUBLED), and the device forms the load
+        ``-material(coef) E`` from the coefficient of the call (HOMMX_LOADS_EIGENSTRAIN)."""
         stream = self._as_stream(coef)
         nc = self._check_stream(stream)
-        P = np.ascontiguousarray(P, dtype=np.float64)
-        if per_cell is None:
-            per_cell = P.ndim == 4
-        lead = (nc,) if per_cell else ()
-        nl = P.shape[len(lead)] if P.ndim == len(lead) + 3 else -1
-        if nl < 0 or P.shape != lead + (nl, self.n_el, self.t):
-            raise ValueError(f"P has shape {P.shape}; expected {lead + ('n_loads', self.n_el, self.t)}")
-        if not 1 <= nl <= self.t:
-            raise ValueError(f"n_loads must be 1 .. {self.t}; got {nl}")
+        P_src = None
+        if isinstance(P, CoefStream):
+            self._check_load_stream(P, nc)
+            P_src, nl, code, P_ptr = P.coef_source(), 1, _lib.LOADS_PROGRAM, None
+        else:
+            P = np.ascontiguousarray(P, dtype=np.float64)
+            if per_cell is None:
+                per_cell = P.ndim == 4
+            lead = (nc,) if per_cell else ()
+            nl = P.shape[len(lead)] if P.ndim == len(lead) + 3 else -1
+            if nl < 0 or P.shape != lead + (nl, self.n_el, self.t):
+                raise ValueError(f"P has shape {P.shape}; expected {lead + ('n_loads', self.n_el, self.t)}")
+            if not 1 <= nl <= self.t:
+                raise ValueError(f"n_loads must be 1 .. {self.t}; got {nl}")
+            code, P_ptr = int(bool(per_cell)), P.ctypes.data
+        if eigenstrain:
+            code |= _lib.LOADS_EIGENSTRAIN
         response = bool(response or fields or return_correctors)
         P_eff = np.empty((nc, nl, self.t), dtype=np.float64)
         energy = np.empty((nc, nl, nl), dtype=np.float64) if response else None
@@ -687,8 +718,8 @@ class MicroCellPlan:
         flux = np.empty((nc, nl, self.n_el, self.t), dtype=np.float64) if fields else None
         corr = np.empty((nc, nl, self.n_nodes * self._bs), dtype=np.float64) if return_correctors else None
         addr = lambda a: None if a is None else a.ctypes.data
-        args = _lib.LoadArgs(nl, int(bool(per_cell)), P.ctypes.data, P_eff.ctypes.data, None, addr(energy), addr(stats), addr(strain), addr(flux),
-                             addr(corr), None)
+        args = _lib.LoadArgs(nl, code, P_ptr, P_eff.ctypes.data, None, addr(energy), addr(stats), addr(strain), addr(flux),
+                             addr(corr), None, C.pointer(P_src) if P_src is not None else None)
         A, info = self._source_call("hommx_loads_source", nc, M, stream, args)
         r = LoadResponse(P_eff, A, info, energy, strain=strain, flux=flux, correctors=corr)
         if response:
@@ -843,13 +874,21 @@ class MicroCellPlan:
     def loads_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, n_loads: int, P_ptr: int, P_eff_ptr: int,
                      per_cell: bool = False, A_ptr: int | None = None, info_ptr: int | None = None, energy_ptr: int | None = None,
                      stats_ptr: int | None = None, strain_ptr: int | None = None, flux_ptr: int | None = None,
-                     correctors_ptr: int | None = None, stream: int | None = None):
+                     correctors_ptr: int | None = None, stream: int | None = None, eigenstrain: bool = False,
+                     P_source: "_lib.CoefSource | None" = None):
         """Device-pointer form of ``loads`` (hommx_loads_source_device), asynchronous on ``stream``: ``source`` =
         ``CoefStream.coef_source(upload)`` with device addresses; P[n_loads, n_el, t] or, ``per_cell``, [n_cells, n_loads, n_el, t] ->
         P_eff[n_cells, n_loads, t]; energy[n_cells, n_loads, n_loads], stats[n_cells, n_loads, t + 2] = [mean total flux | max | argmax],
-        strain / flux[n_cells, n_loads, n_el, t] and correctors[n_cells, n_loads, n_nodes * bs]: any of them triggers the load solve."""
-        args = _lib.LoadArgs(int(n_loads), int(bool(per_cell)), P_ptr, P_eff_ptr, A_ptr or None, energy_ptr or None, stats_ptr or None,
-                             strain_ptr or None, flux_ptr or None, correctors_ptr or None, info_ptr or None)
+        strain / flux[n_cells, n_loads, n_el, t] and correctors[n_cells, n_loads, n_nodes * bs]: any of them triggers the load solve.
+        ``P_source``: the load comes from a program instead (HOMMX_LOADS_PROGRAM) -- ``CoefStream.program(...).coef_source(upload)`` of a
+        vector ``Expression`` with t components; ``P_ptr`` and ``per_cell`` are then not read and ``n_loads`` must be 1.
+        ``eigenstrain``: the array or the program delivers an eigenstrain (HOMMX_LOADS_EIGENSTRAIN), as ``loads`` describes."""
+        code = _lib.LOADS_PROGRAM if P_source is not None else int(bool(per_cell))
+        if eigenstrain:
+            code |= _lib.LOADS_EIGENSTRAIN
+        args = _lib.LoadArgs(int(n_loads), code, None if P_source is not None else P_ptr, P_eff_ptr, A_ptr or None, energy_ptr or None,
+                             stats_ptr or None, strain_ptr or None, flux_ptr or None, correctors_ptr or None, info_ptr or None,
+                             C.pointer(P_source) if P_source is not None else None)
         _lib.check(self._lib.hommx_loads_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
                    "hommx_loads_source_device")
 

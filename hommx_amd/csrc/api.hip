@@ -114,9 +114,12 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 //            [nc][n_params + n_fields][n_el][n_comp] (grown with B_EXPAND, by stream_chunk)
 // B_CURVATURE: the second-order streams of such a chunk, one per pair a <= b of the slots, [nc][n_pairs][n_el][n_comp], and behind
 //            them, at [chunk][n_pairs][n_el][n_comp], the first derivatives of A_H along them, [nc][n_pairs][t][t] (stream_chunk too)
+// B_POLAR: the loads of one chunk of hommx_loads_source that the device forms: the expansion of a program load, [nc][n_el][t]
+//            (derived_call; an eigenstrain becomes the eigenstress in place), or the eigenstresses of an eigenstrain array that is not
+//            the plan's to overwrite, [nc][n_loads][n_el][t] (loads_run)
 enum {
   B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, B_SENS2, B_TANGENT, B_CURVATURE,
-  N_BUF
+  B_POLAR, N_BUF
 };
 
 }  // namespace
@@ -286,9 +289,11 @@ hommx_coef_source source_of_form(const hommx_coef_source& s) {
   return separable_source(s.family, s.n_q, s.table, s.weights, s.params);
 }
 
-// The whole program of a HOMMX_COEF_PROGRAM source against the plan's descriptor, on the host: the kernel then interprets it unchecked
-int program_check(const hommx_plan* p, const hommx_coef_source* s) {
-  if (p->desc.kind == HOMMX_KIND_ELASTICITY_VOIGT)
+// The whole program of a HOMMX_COEF_PROGRAM source against the plan's descriptor, on the host: the kernel then interprets it unchecked.
+// load_comp: 0 for the coefficient; the tensor size t of the plan for the program of a load (HOMMX_LOADS_PROGRAM), which has t
+// components on every kind
+int program_check(const hommx_plan* p, const hommx_coef_source* s, int load_comp = 0) {
+  if (!load_comp && p->desc.kind == HOMMX_KIND_ELASTICITY_VOIGT)
     return fail(HOMMX_EINVAL, "expression coefficients are not supported for the 21-component Voigt kind");
   const hommx_coef_program* g = s->program;
   if (!g) return fail(HOMMX_EINVAL, "null program");
@@ -303,7 +308,9 @@ int program_check(const hommx_plan* p, const hommx_coef_source* s) {
   if (s->n_fields < 0 || s->n_fields > hommx::PROGRAM_MAX_FIELDS)
     return fail(HOMMX_EINVAL, "program source: n_fields must be 0 .. %d, got %d", hommx::PROGRAM_MAX_FIELDS, s->n_fields);
   const int n_row = hommx::program_row_doubles(s->n_fields);
-  const int n_comp = hommx::kind_sizes(p->desc.dim, p->desc.kind).n_comp;
+  const int n_comp = load_comp ? load_comp : hommx::kind_sizes(p->desc.dim, p->desc.kind).n_comp;
+  if (g->n_comp != n_comp && load_comp)
+    return fail(HOMMX_EINVAL, "program: n_comp is %d, a load of this plan has t = %d components", g->n_comp, n_comp);
   if (g->n_comp != n_comp) return fail(HOMMX_EINVAL, "program: n_comp is %d, the plan's coefficient has %d components", g->n_comp, n_comp);
   if (!g->ops || (g->n_consts > 0 && !g->consts)) return fail(HOMMX_EINVAL, "null program ops / consts");
   if (s->n_q < 1) return fail(HOMMX_EINVAL, "program source needs n_q >= 1");
@@ -415,14 +422,15 @@ int64_t table_doubles(const hommx_plan* p, const hommx_coef_source& s) {
 // Cells per chunk of a source, given the `want` of the caller: a sampler form is expanded into the plan's element stream, at most 1 GiB of
 // it (at least one cell), which is grown here; a sampled stream has no such limit.  n_tan: the parameter tangents of a program are
 // expanded beside it (B_TANGENT), and the 1 GiB counts the 1 + n_tan streams; n_curv: its second-order streams as well (B_CURVATURE,
-// with the t x t first derivatives along them behind), and the 1 GiB counts the 1 + n_tan + n_curv streams
-int64_t stream_cells(const hommx_plan* p, int64_t want, int n_tan = 0, int n_curv = 0) {
-  return std::min(want, std::max<int64_t>((1ll << 27) / std::max<int64_t>(p->n_el * p->ks.n_comp * (1 + n_tan + n_curv), 1), 1));
+// with the t x t first derivatives along them behind), and the 1 GiB counts the 1 + n_tan + n_curv streams; more: doubles per cell of
+// what else the device expands for the chunk (the load of HOMMX_LOADS_PROGRAM), counted with them
+int64_t stream_cells(const hommx_plan* p, int64_t want, int n_tan = 0, int n_curv = 0, int64_t more = 0) {
+  return std::min(want, std::max<int64_t>((1ll << 27) / std::max<int64_t>(p->n_el * p->ks.n_comp * (1 + n_tan + n_curv) + more, 1), 1));
 }
-int stream_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t want, int64_t* chunk, int n_tan = 0, int n_curv = 0) {
+int stream_chunk(hommx_plan* p, const hommx_coef_source& s, int64_t want, int64_t* chunk, int n_tan = 0, int n_curv = 0, int64_t more = 0) {
   *chunk = want;
   if (s.form == HOMMX_COEF_SAMPLED) return HOMMX_OK;
-  *chunk = stream_cells(p, want, n_tan, n_curv);
+  *chunk = stream_cells(p, want, n_tan, n_curv, more);
   const size_t stream = sizeof(double) * *chunk * p->n_el * p->ks.n_comp;
   if (int rc = grow(p->buf[B_TANGENT], stream * n_tan)) return rc;
   if (int rc = grow(p->buf[B_CURVATURE], (stream + sizeof(double) * *chunk * p->ks.t * p->ks.t) * n_curv)) return rc;
@@ -503,17 +511,25 @@ int stage_in(hommx_plan* p, const hommx::HostPiece (&in)[N]) {
 
 // The host arrays of a source staged so (what every cell shares and the per-cell values of a sampler form; a sampled stream stays where
 // it is, and ds->coef is null: the stream is no device pointer), with one more input of the entry point; *ds: the source with the
-// device copies
-int stage_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, hommx::HostPiece more, hommx_coef_source* ds) {
+// device copies; load: the program source of a load (HOMMX_LOADS_PROGRAM) or null -- its points, weights and rows travel in the same
+// copy and their device copies replace its pointers
+int stage_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, hommx::HostPiece more, hommx_coef_source* ds,
+                 hommx_coef_source* load = nullptr) {
   const size_t nval = sizeof(double) * n_cells * per_cell_doubles(p, s);
   *ds = s;
   ds->coef = nullptr;
+  hommx_coef_source none{};
+  const hommx_coef_source host = load ? *load : none;
+  hommx_coef_source& dl = load ? *load : none;  // without a load its three pieces are empty
   const hommx::HostPiece in[] = {{s.mask, (size_t)p->n_el, (const void**)&ds->mask},
                                  {s.values, nval, (const void**)&ds->values},
                                  {s.table, sizeof(double) * table_doubles(p, s), (const void**)&ds->table},
                                  {s.weights, sizeof(double) * s.n_q, (const void**)&ds->weights},
                                  {s.params, nval, (const void**)&ds->params},
-                                 more};
+                                 more,
+                                 {host.table, load ? sizeof(double) * table_doubles(p, host) : 0, (const void**)&dl.table},
+                                 {host.weights, sizeof(double) * host.n_q, (const void**)&dl.weights},
+                                 {host.params, load ? sizeof(double) * n_cells * per_cell_doubles(p, host) : 0, (const void**)&dl.params}};
   return stage_in(p, in);
 }
 
@@ -1080,11 +1096,20 @@ using ChunkRule = int64_t (*)(const hommx_plan*, int64_t, size_t);  // recon_chu
 // [nc][n_params + n_fields][n_el][n_comp] in B_TANGENT, formed by the launch that expands the stream; their bytes count as scratch of the chunk
 // curvature (HOMMX_DIRS_PARAMETERS_CURVATURE, with tangents): that launch is the second-order pass and also forms the second-order
 // streams of the chunk, [nc][n_pairs][n_el][n_comp] in B_CURVATURE (v.curv), whose bytes count as scratch too
+// load (HOMMX_LOADS_PROGRAM): a program source of the call's own beside the coefficient's, and the pointer member of v.a that receives,
+// per chunk, its expansion on the rows of the chunk's cells -- [nc][n_el][n_comp of its program] in B_POLAR, the value pass of the
+// interpreter; a host call stages its points, weights and rows with the coefficient source's shared arrays.  The caller counts its
+// bytes in `scratch`; the 1 GiB bound of stream_chunk counts them with the streams
+struct ProgramLoad {
+  hommx_coef_source src;
+  const double** slot;
+};
 template <typename Args, size_t NI, size_t NO, typename Run>
 int derived_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, Chunk<Args>& v, const CellArray (&ins)[NI],
                  const CellArray (&outs)[NO], int32_t** info, size_t scratch, ChunkRule rule, bool device, hipStream_t st, Run run,
-                 const double** tangents = nullptr, bool curvature = false) {
+                 const double** tangents = nullptr, bool curvature = false, ProgramLoad* load = nullptr) {
   const int n_tan = tangents ? source_tangents(s) : 0, n_curv = curvature ? tangent_pairs(n_tan) : 0;
+  const int64_t load_doubles = load ? p->n_el * load->src.program->n_comp : 0;
   scratch += sizeof(double) * (n_tan * p->n_el * p->ks.n_comp + n_curv * (p->n_el * p->ks.n_comp + p->ks.t * p->ks.t));
   constexpr size_t N[2] = {NI + 2, NO + 1};
   constexpr size_t NMAX = std::max(N[0], N[1]);
@@ -1110,13 +1135,13 @@ int derived_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, con
   char* dev[2][NMAX] = {};
   int64_t chunk = 0;
   if (device) {
-    if (int rc = stream_chunk(p, s, rule(p, n_cells, scratch), &chunk, n_tan, n_curv)) return rc;
+    if (int rc = stream_chunk(p, s, rule(p, n_cells, scratch), &chunk, n_tan, n_curv, load_doubles)) return rc;
   } else {
     const void* d_shared = nullptr;
     const hommx::HostPiece more{shared ? shared->get() : nullptr, shared ? shared->elem * shared->n : 0, &d_shared};
-    if (int rc = stage_source(p, n_cells, s, more, &ds)) return rc;
+    if (int rc = stage_source(p, n_cells, s, more, &ds, load ? &load->src : nullptr)) return rc;
     if (shared) shared->set(d_shared);
-    if (int rc = stream_chunk(p, s, rule(p, n_cells, per_cell), &chunk, n_tan, n_curv)) return rc;
+    if (int rc = stream_chunk(p, s, rule(p, n_cells, per_cell), &chunk, n_tan, n_curv, load_doubles)) return rc;
     for (int io = 0; io < 2; ++io) {
       size_t bytes[NMAX] = {};
       for (size_t k = 0; k < N[io]; ++k) bytes[k] = cell[io][k] * chunk;
@@ -1124,6 +1149,8 @@ int derived_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, con
     }
   }
   v.src = &ds;
+  if (load)
+    if (int rc = grow(p->buf[B_POLAR], sizeof(double) * chunk * load_doubles)) return rc;
   for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
     const int64_t nc = std::min(chunk, n_cells - c0);
     for (int io = 0; io < 2; ++io)
@@ -1138,6 +1165,13 @@ int derived_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, con
     if (!v.coef)
       if (int rc = expand_chunk(p, ds, c0, nc, st, &v.coef, nullptr, tan, v.curv)) return rc;
     if (tan) *tangents = tan;
+    if (load) {
+      const hommx_coef_source& l = load->src;
+      double* field = static_cast<double*>(p->buf[B_POLAR].p);
+      HIP_TRY(hommx::launch_expand_program(program_args(*l.program), l.program->n_params, l.n_fields, l.table, l.weights, l.n_q, p->desc.dim,
+                                           program_rows(l, c0), field, nullptr, p->n_el, nc, st));
+      *load->slot = field;
+    }
     if (int rc = run(nc, chunk, v)) return rc;
     if (device) continue;
     for (size_t k = 0; k < N[1]; ++k)
@@ -1338,6 +1372,32 @@ int strat_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const
 
 // -- polarisation loads (hommx_loads_source[_device]) ------------------------------------------------------------------------------------
 bool load_response(const hommx_load_args& a) { return a.energy || a.stats || a.strain || a.flux || a.correctors; }
+// the code in hommx_load_args.per_cell: where the load comes from (HOMMX_LOADS_SHARED / _PER_CELL / _PROGRAM), and whether it is an eigenstrain
+int load_form(int32_t code) { return code & 3; }
+bool load_eigenstrain(int32_t code) { return (code & HOMMX_LOADS_EIGENSTRAIN) != 0; }
+// a caller's arguments that loads_open has passed: P_source, the member a caller built against the shorter struct does not have, is
+// read for its own code only
+hommx_load_args load_args_of(const hommx_load_args& a) {
+  hommx_load_args c{};
+  c.n_loads = a.n_loads;
+  c.per_cell = a.per_cell;
+  c.P = load_form(a.per_cell) == HOMMX_LOADS_PROGRAM ? nullptr : a.P;
+  c.P_eff = a.P_eff;
+  c.A_eff = a.A_eff;
+  c.energy = a.energy;
+  c.stats = a.stats;
+  c.strain = a.strain;
+  c.flux = a.flux;
+  c.correctors = a.correctors;
+  c.info = a.info;
+  c.P_source = load_form(a.per_cell) == HOMMX_LOADS_PROGRAM ? a.P_source : nullptr;
+  return c;
+}
+// an eigenstrain array the plan must not overwrite: one that every cell shares, and in a device call the caller's own per-cell array
+// (a host call's per-cell array lies in B_IN, the expansion of a program in B_POLAR: those become the eigenstress in place)
+bool eigenstress_scratch(int32_t code, bool device) {
+  return load_eigenstrain(code) && (load_form(code) == HOMMX_LOADS_SHARED || (load_form(code) == HOMMX_LOADS_PER_CELL && device));
+}
 
 // The correctors of the loads `lo` of nc cells of a chunk into corr_l[nc][t][ndof] (rows l < n_loads), on the route
 // hommx_plan_load_kernel_name names: fused 2D plans substitute on the records the canonical pass of this chunk has just left in B_FACT
@@ -1362,10 +1422,24 @@ int load_correctors(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_co
 
 // one chunk of at most recon_chunk() cells on the device: the canonical correctors into the plan's scratch and k_polar; for a response
 // the correctors of the loads behind them (load_correctors) and k_load_stats
-int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_load_args>& v, hipStream_t st) {
+// an eigenstrain first becomes the eigenstress of every cell (k_eigenstress: in place, or into B_POLAR where the array is not the plan's
+// to overwrite), which every consumer then reads as a per-cell load
+int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_load_args>& v, bool device, hipStream_t st) {
   const hommx_load_args& a = v.a;
   const bool response = load_response(a);
   const int t = p->ks.t;
+  const double* P = a.P;
+  bool per_cell = load_form(a.per_cell) != HOMMX_LOADS_SHARED;
+  if (load_eigenstrain(a.per_cell)) {
+    double* stress = const_cast<double*>(a.P);
+    if (eigenstress_scratch(a.per_cell, device)) {
+      if (int rc = grow(p->buf[B_POLAR], sizeof(double) * chunk * a.n_loads * p->n_el * t)) return rc;
+      stress = static_cast<double*>(p->buf[B_POLAR].p);
+    }
+    HIP_TRY(hommx::launch_eigenstress(p->desc.dim, p->desc.kind, v.coef, a.P, per_cell, stress, a.n_loads, p->n_el, nc, st));
+    P = stress;
+    per_cell = true;
+  }
   double *d_A_eff = a.A_eff, *corr = nullptr;
   if (int rc = chunk_correctors(p, nc, chunk, v.coef, v.M, &d_A_eff, a.info, response ? t : 0, st, &corr)) return rc;
   hommx::LoadArgs k;
@@ -1374,13 +1448,13 @@ int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_load_a
   k.coef = v.coef;
   k.M = v.M;
   k.n_loads = a.n_loads;
-  k.per_cell = a.per_cell != 0;
-  k.P = a.P;
+  k.per_cell = per_cell;
+  k.P = P;
   k.P_eff = a.P_eff;
   HIP_TRY(hommx::launch_polar(k, nc, st));
   if (!response) return HOMMX_OK;
   double* corr_l = corr + chunk * t * k.ndof;
-  if (int rc = load_correctors(p, nc, chunk, v.coef, v.M, hommx::LoadOverride{a.P, a.n_loads, a.per_cell != 0}, st, corr_l)) return rc;
+  if (int rc = load_correctors(p, nc, chunk, v.coef, v.M, hommx::LoadOverride{P, a.n_loads, per_cell}, st, corr_l)) return rc;
   k.corr = corr_l;
   k.energy = a.energy;
   k.stats = a.stats;
@@ -1398,7 +1472,19 @@ int loads_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, con
   auto checks = [&] {
     const int t = hommx::kind_sizes(p->desc.dim, p->desc.kind).t;
     if (a->n_loads < 1 || a->n_loads > t) return fail(HOMMX_EINVAL, "n_loads must be 1 .. %d (the tensor size of the plan), got %d", t, a->n_loads);
-    if (!a->P || !a->P_eff) return fail(HOMMX_EINVAL, "null P / P_eff");
+    if ((a->per_cell & ~7) || load_form(a->per_cell) == 3)
+      return fail(HOMMX_EINVAL, "unknown load code %d in per_cell: HOMMX_LOADS_SHARED, HOMMX_LOADS_PER_CELL or HOMMX_LOADS_PROGRAM, alone or "
+                                "or-ed with HOMMX_LOADS_EIGENSTRAIN", a->per_cell);
+    if (load_form(a->per_cell) == HOMMX_LOADS_PROGRAM) {
+      const hommx_coef_source* l = a->P_source;
+      if (!l) return fail(HOMMX_EINVAL, "HOMMX_LOADS_PROGRAM needs P_source, the program source of the load");
+      if (l->form != HOMMX_COEF_PROGRAM) return fail(HOMMX_EINVAL, "P_source must be a HOMMX_COEF_PROGRAM source, got form %d", l->form);
+      if (a->n_loads != 1) return fail(HOMMX_EINVAL, "HOMMX_LOADS_PROGRAM takes n_loads == 1 (callers loop for more), got %d", a->n_loads);
+      if (int rc = program_check(p, l, t)) return prefix_error(rc, "P_source: ");
+      if (!a->P_eff) return fail(HOMMX_EINVAL, "null P_eff");
+    } else if (!a->P || !a->P_eff) {
+      return fail(HOMMX_EINVAL, "null P / P_eff");
+    }
     if (!a->strain != !a->flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
     return HOMMX_OK;
   };
@@ -1419,12 +1505,22 @@ int loads_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const
   const int64_t t = p->ks.t, nl = args.n_loads, field = nl * p->n_el * t;
   const bool response = load_response(args);
   Chunk<hommx_load_args> v{};
-  hommx_load_args& a = v.a = args;
-  const CellArray in[] = {{&a.P, field, a.per_cell ? PER_CELL : SHARED}};
+  hommx_load_args& a = v.a = load_args_of(args);
+  const bool program = load_form(a.per_cell) == HOMMX_LOADS_PROGRAM;
+  ProgramLoad load{};
+  if (program) {
+    const hommx_coef_source& l = *a.P_source;
+    load = {program_source(l.program, l.n_q, l.table, l.weights, l.params, l.n_fields), &a.P};
+  }
+  // what a chunk holds of the load beside the caller's array: the expansion of a program, the eigenstresses of an array that stays as it is
+  const size_t formed = program || eigenstress_scratch(a.per_cell, device) ? sizeof(double) * field : 0;
+  const CellArray in[] = {{&a.P, field, load_form(a.per_cell) == HOMMX_LOADS_SHARED ? SHARED : PER_CELL}};
   const CellArray out[] = {{&a.P_eff, nl * t}, {&a.A_eff, t * t, KEPT},   {&a.energy, nl * nl},          {&a.stats, nl * (t + 2)},
                            {&a.strain, field}, {&a.flux, field},          {&a.correctors, nl * plan_ndof(p)}};
-  return derived_call(p, n_cells, s, M, v, in, out, &a.info, response ? sizeof(double) * plan_ndof(p) * t : 0, response ? load_chunk : recon_chunk,
-                      device, st, [&](int64_t nc, int64_t chunk, const Chunk<hommx_load_args>& c) { return loads_run(p, nc, chunk, c, st); });
+  return derived_call(p, n_cells, s, M, v, in, out, &a.info, formed + (response ? sizeof(double) * plan_ndof(p) * t : 0),
+                      response ? load_chunk : recon_chunk, device, st,
+                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_load_args>& c) { return loads_run(p, nc, chunk, c, device, st); },
+                      nullptr, false, program ? &load : nullptr);
 }
 
 // -- second derivatives (hommx_second_sensitivity_source[_device]) ------------------------------------------------------------------------

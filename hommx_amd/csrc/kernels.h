@@ -198,6 +198,10 @@ struct LoadArgs : ElemWalk {
 };
 hipError_t launch_polar(const LoadArgs& a, long long nc, hipStream_t stream);
 hipError_t launch_load_stats(const LoadArgs& a, long long nc, hipStream_t stream);
+// k_eigenstress: P[nc][n_loads][n_el][t] = -(material(coef[nc][n_el][n_comp]) E), E[nc][n_loads][n_el][t] (per_cell) or [n_loads][n_el][t]
+// in the components of the reconstruction's strain (shear doubled); P may be E itself when per_cell
+hipError_t launch_eigenstress(int dim, int kind, const double* coef, const double* E, bool per_cell, double* P, int n_loads, long long n_el,
+                              long long nc, hipStream_t stream);
 
 // the loads a corrector pass of the blocked family solves for instead of the canonical ones: rows l < n_loads of Brhs from P (device), the
 // rest zero.  P starts at the first cell of the call

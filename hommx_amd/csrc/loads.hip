@@ -12,7 +12,9 @@
 // k_polar and k_load_stats: one workgroup per macro cell, elements on lanes, the correctors gathered from global memory as k_sens
 // gathers them and the fixed-order reductions of elem_walk.h (block_sums, block_argmax), so a cell's outputs do not depend on its batch
 // position, the chunking or which outputs are asked for.  k_assemble_loads: one thread per node gathers the load entries of its
-// incident elements and writes each entry of Brhs once.  No atomics, no inline assembly.
+// incident elements and writes each entry of Brhs once.  k_eigenstress: an eigenstrain E^l_K (the components and convention of the
+// reconstruction's strain: shear doubled) becomes the load P^l_K = -material(coef_K) E^l_K before any of them runs, one thread per
+// (cell, load, element), every entry written once.  No atomics, no inline assembly.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,10 +22,37 @@
 #include "blocked_internal.h"
 #include "elem_walk.h"
 #include "kernels.h"
+#include "mesh_elem.h"
 
 namespace hommx {
 
 namespace {
+
+// P[cell][l][K][:] = -(material(coef[cell][K]) E^l_K), E[cell][l][K][:] (per_cell) or E[l][K][:].  Thread i is entry (cell, l, K) with K
+// fastest, so a wave reads and writes consecutive elements.  E_K is in registers before P_K is written: P may be E (per_cell only).
+// Every index is a constant of an unrolled loop (the 6 x 6 matrix of 3D elasticity stays in registers)
+template <int DIM, int KIND>
+__global__ __launch_bounds__(256) void k_eigenstress(const double* __restrict__ coef, const double* E, bool per_cell, double* P, int n_loads,
+                                                     long long n_el, long long total) {
+  constexpr KindSizes ks = kind_sizes(DIM, KIND);
+  constexpr int T = ks.t, NCOMP = ks.n_comp;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const long long el = i % n_el, cl = i / n_el, cell = cl / n_loads, l = cl % n_loads;
+  double C[T][T], e[T];
+  material<DIM, KIND>(coef + (cell * n_el + el) * NCOMP, C);
+  const double* ek = E + (((per_cell ? cell * n_loads : 0) + l) * n_el + el) * T;
+#pragma unroll
+  for (int k = 0; k < T; ++k) e[k] = ek[k];
+  double* pk = P + i * T;
+#pragma unroll
+  for (int m = 0; m < T; ++m) {
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < T; ++k) v += C[m][k] * e[k];
+    pk[m] = -v;
+  }
+}
 
 // P_eff[cell][l][m] = sum_K |K| s^m_K . P^l_K: the t canonical strains of an element once, contracted with every load; P is read once
 template <int DIM, int KIND, bool MESH>
@@ -283,6 +312,16 @@ hipError_t launch_polar(const LoadArgs& a, long long nc, hipStream_t st) {
 hipError_t launch_load_stats(const LoadArgs& a, long long nc, hipStream_t st) {
   if (a.strain) return launch_walk(a, nc, st, walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_load_stats<D(), K(), MESH(), true>; }));
   return launch_walk(a, nc, st, walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_load_stats<D(), K(), MESH(), false>; }));
+}
+
+hipError_t launch_eigenstress(int dim, int kind, const double* coef, const double* E, bool per_cell, double* P, int n_loads, long long n_el,
+                              long long nc, hipStream_t st) {
+  const long long total = nc * n_loads * n_el;
+  if (total <= 0) return hipSuccess;
+  return dispatch_dim_kind(dim, kind, [&](auto D, auto K) {
+    hipLaunchKernelGGL((k_eigenstress<D(), K()>), dim3(nblk(total)), dim3(256), 0, st, coef, E, per_cell, P, n_loads, n_el, total);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_assemble_loads(const BlockedWorkspace* ws, const LoadOverride& lo, long long cell0, const double* Mm, long long nc,

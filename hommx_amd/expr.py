@@ -457,7 +457,10 @@ class Expression:
 
     ``Expression(text)`` is a scalar coefficient (the Poisson classes), ``Expression(lam=..., mu=...)`` a ``Lame`` pair (the elasticity
     classes), ``Expression([[a, b], [b, c]])`` a symmetric d x d matrix (the Poisson classes; the two texts of an off-diagonal entry must
-    parse to equal trees).  Passing one as ``A`` lets the solver classes sample on the DEVICE: the points of the micro quadrature rule go
+    parse to equal trees).  ``Expression(["c0", "c1", ...])``, a FLAT list of 1 to 6 texts, is a vector (``shape == "vector"``): no
+    coefficient but a load -- a polarisation or an eigenstrain of the solver classes (``set_polarisation`` / ``set_eigenstrain``), whose
+    components stand in the order of the reconstruction's flux / strain; as a callable it returns ``[n_comp, ...]``, and its streams keep
+    the component axis whatever its length.  Passing a coefficient as ``A`` lets the solver classes sample on the DEVICE: the points of the micro quadrature rule go
     once, three numbers per macro cell (its midpoint) after them, and a bytecode kernel forms the element means.
 
     ``degree``: the quadrature degree of the expression, estimated from its tree by UFL's rules -- a literal, ``x[i]``, ``p[k]`` and
@@ -493,7 +496,7 @@ class Expression:
 
     def __init__(self, text=None, *, lam=None, mu=None, p=None, parameter_names=None, fields=None):
         if (lam is None) != (mu is None) or (text is None) == (lam is None):
-            raise ValueError("Expression(text), Expression([[a, b], [b, c]]) or Expression(lam=..., mu=...)")
+            raise ValueError("Expression(text), Expression([[a, b], [b, c]]), Expression([c0, c1, ...]) or Expression(lam=..., mu=...)")
         self.dim = None  # the d of a matrix
         values = _parameter_values(p, None) if p is not None else np.zeros(0)
         self.n_params = int(values.size)
@@ -506,10 +509,14 @@ class Expression:
         ctx = _Context(self.n_params if p is not None else None, self.n_fields if fields is not None else None)
         if lam is not None:
             self.shape, texts = "lame", [lam, mu]
+        elif isinstance(text, (list, tuple)) and not any(isinstance(r, (list, tuple)) for r in text):
+            if not 1 <= len(text) <= MAX_COMP:
+                raise ValueError(f"expression: a vector has 1 .. {MAX_COMP} components; got {len(text)}")
+            self.shape, texts = "vector", list(text)
         elif isinstance(text, (list, tuple)):
             d = len(text)
             if d not in (2, 3) or any(not isinstance(r, (list, tuple)) or len(r) != d for r in text):
-                raise ValueError("expression: a matrix is 2 x 2 or 3 x 3")
+                raise ValueError("expression: a matrix is 2 x 2 or 3 x 3 (nested lists; a flat list of texts is a vector)")
             self.shape, self.dim = "matrix", d
             pairs = [(0, 0), (1, 1), (0, 1)] if d == 2 else [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]  # the component order of the ABI
             for i, j in pairs:
@@ -554,6 +561,11 @@ class Expression:
     def pairs(self) -> tuple:
         """The pairs (a, b), a <= b, of the n_params + n_fields differentiable slots, in the order of the second-order streams."""
         return _pairs(self.n_params + self.n_fields)
+
+    @property
+    def _flat(self) -> bool:
+        """Whether the streams drop the component axis: one component, except of a vector, which keeps its axis whatever its length."""
+        return self.n_comp == 1 and self.shape != "vector"
 
     def with_parameters(self, p) -> "Expression":
         """The same expression at other parameter values: the same ``ops``, only ``consts[:n_params]`` replaced -- nothing is parsed."""
@@ -600,6 +612,8 @@ class Expression:
             from .hmm import Lame
 
             return Lame(np.array(v[0]), np.array(v[1]))
+        if self.shape == "vector":
+            return np.stack(v)
         out = np.empty(v[0].shape + (self.dim, self.dim))
         for c, (i, j) in enumerate(self._pairs):
             out[..., i, j] = out[..., j, i] = v[c]
@@ -615,7 +629,7 @@ class Expression:
             v = self.components(x.T[:, :, None], np.moveaxis(yq[:, q, :], -1, 0)[:, None, :])
             for c in range(self.n_comp):
                 acc[c] = acc[c] + w[q] * v[c]
-        return acc[0] if self.n_comp == 1 else np.stack(acc, axis=-1)
+        return acc[0] if self._flat else np.stack(acc, axis=-1)
 
     def host_tangents(self, x: np.ndarray, yq: np.ndarray, w: np.ndarray) -> np.ndarray:
         """The derivatives of ``host_stream`` with respect to the parameters, then the fields (of a cell: its own value),
@@ -639,7 +653,7 @@ class Expression:
                     dj = np.float64(0.0) if dv[c][j] is None else dv[c][j]
                     acc[j][c] = acc[j][c] + w[q] * np.broadcast_to(dj, shape)
         out = np.stack([np.stack(a, axis=-1) for a in acc], axis=1)  # [N, P, n_el, n_comp]
-        return out[..., 0] if self.n_comp == 1 else out
+        return out[..., 0] if self._flat else out
 
 
     def host_second_tangents(self, x: np.ndarray, yq: np.ndarray, w: np.ndarray) -> np.ndarray:
@@ -664,7 +678,7 @@ class Expression:
                     hs = np.float64(0.0) if hv[c][s] is None else hv[c][s]
                     acc[s][c] = acc[s][c] + w[q] * np.broadcast_to(hs, shape)
         out = np.stack([np.stack(a, axis=-1) for a in acc], axis=1)  # [N, n_pairs, n_el, n_comp]
-        return out[..., 0] if self.n_comp == 1 else out
+        return out[..., 0] if self._flat else out
 
 
 def _field_names(fields) -> tuple[int, tuple]:

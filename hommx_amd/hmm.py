@@ -86,6 +86,36 @@ def hooke_to_voigt(C: np.ndarray, dim: int) -> np.ndarray:
     return out
 
 
+def material_matrix(coef: np.ndarray, kind: str, dim: int) -> np.ndarray:
+    """[..., t, t]: the material matrix of element means ``coef[...(, n_comp)]`` in the layout of the plan kind ``kind``, in the basis
+    of the canonical loads (Poisson: A; elasticity: ``hooke_to_voigt`` of the Hooke tensor) -- the host statement of ``material()`` in
+    csrc/mesh_elem.h."""
+    coef = np.asarray(coef, dtype=float)
+    t = dim if kind.startswith("poisson") else dim * (dim + 1) // 2
+    if kind == "poisson":
+        return coef[..., None, None] * np.eye(t)
+    C = np.zeros(coef.shape[:-1] + (t, t))
+    if kind == "poisson_matrix":
+        for c, (i, j) in enumerate(_VOIGT[dim]):
+            C[..., i, j] = C[..., j, i] = coef[..., c]
+    elif kind == "elasticity":
+        lam, mu = coef[..., 0], coef[..., 1]
+        C[..., :dim, :dim] = lam[..., None, None]
+        for m in range(t):
+            C[..., m, m] += 2.0 * mu if m < dim else mu
+    else:  # the upper triangle of the t x t matrix, row-major
+        iu = np.triu_indices(t)
+        C[..., iu[0], iu[1]] = coef
+        C[..., iu[1], iu[0]] = coef
+    return C
+
+
+def eigenstress(coef: np.ndarray, kind: str, dim: int, E: np.ndarray) -> np.ndarray:
+    """P = -material(coef) E: the polarisation of an eigenstrain ``E[..., t]`` (the components of ``Reconstruction.strain``, shear
+    doubled) on elements of the coefficient ``coef`` (``material_matrix``); the leading axes broadcast."""
+    return -np.einsum("...mn,...n->...m", material_matrix(coef, kind, dim), np.asarray(E, dtype=float))
+
+
 class Lame:
     """Isotropic Hooke tensor given by its Lame parameters: ``A = lambda d_ij d_kl + mu (d_ik d_jl + d_il d_jk)``
     (test_integration_linear_elasticity.py:84-93; rotated_fibers.py:66-76).  Returning ``Lame(lam, mu)`` from the
@@ -300,7 +330,9 @@ class BaseHMM(ABC):
         self.effective_tensors: np.ndarray | None = None  # A_H / C_H of every macro cell after assembly
         self.cell_info: np.ndarray | None = None
         self._solved = False  # reconstruct() defaults to the last solve() result
-        self._polarisation = None  # set_polarisation
+        self._polarisation = None  # set_polarisation / set_eigenstrain
+        self._eigenstrain = False  # what _polarisation holds is an eigenstrain E: the load is -A : E
+        self._polarisation_fields: np.ndarray | None = None  # set_polarisation_fields: [num_cells, n_fields] of a load Expression with fields
         self._fields: np.ndarray | None = None  # set_fields: [num_cells, n_fields] of an Expression with fields
         self.effective_polarisation: np.ndarray | None = None  # P_eff[N, t] of every macro cell after a solve() with a polarisation
         if self._reserve_at_construction:
@@ -341,6 +373,12 @@ class BaseHMM(ABC):
         co = self._coeff
         if not isinstance(co, Expression) or co.n_fields == 0:
             raise ValueError("set_fields() needs an Expression coefficient with fields (Expression(..., fields=...))")
+        self._fields = self._field_values(co, values)
+        self._needs_reassembly = True
+
+    def _field_values(self, co: Expression, values) -> np.ndarray:
+        """``values`` of the fields of the expression ``co`` as float64[num_cells, n_fields], every value finite (``set_fields``: the
+        shapes it takes)."""
         n, k = self._msh.num_cells, co.n_fields
         if callable(values):
             v = np.asarray(values(self._msh.cell_midpoints().T), dtype=np.float64)
@@ -354,8 +392,7 @@ class BaseHMM(ABC):
         if not np.isfinite(v).all():
             c, j = np.argwhere(~np.isfinite(v))[0]
             raise ValueError(f"field {co.field_names[j]} is not finite on macro cell {c}: {v[c, j]}")
-        self._fields = np.array(v, dtype=np.float64, order="C")
-        self._needs_reassembly = True
+        return np.array(v, dtype=np.float64, order="C")
 
     def cell_means(self, u=None) -> np.ndarray:
         """[num_cells] (a scalar macro space) or [num_cells, d]: the mean of the vertex values of the macro field ``u`` (a macro
@@ -418,14 +455,65 @@ class BaseHMM(ABC):
         ``P``: a NumPy-vectorised callable ``P(x, y) -> [t, ...]`` (components in the order of ``Reconstruction.flux``: the flux vector, or
         s00, s11[, s22], s01[, s02, s12], shear not doubled), sampled with the micro rule that samples the coefficient; an array
         ``[n_el, t]`` of element means shared by all macro cells; an array ``[N, n_el, t]``; ``None`` removes it (``solve()`` is then bit
-        for bit what it is without this call)."""
-        if P is not None and not callable(P):
+        for bit what it is without this call).
+
+        ``P`` may also be a vector ``Expression`` with t components (``Expression(["...", ...])``): it is sampled ON THE DEVICE, at the
+        points that sample the coefficient -- only its program and one row per macro cell cross the boundary (hommx_loads_source,
+        HOMMX_LOADS_PROGRAM).  Its parameters change through ``P.with_parameters(p)`` and this call again (the plan is kept), its
+        fields ``f[k]`` are its own: ``set_polarisation_fields``.  A plan stand-in without the capability is given the element means
+        of the expression, as of a callable.  Replaces an eigenstrain (``set_eigenstrain``)."""
+        self._set_load(P, False)
+
+    def set_eigenstrain(self, E):
+        """A prescribed micro eigenstrain E(x, y): a thermal strain alpha dT, a swelling, a misfit.  The polarisation is the eigenstress
+        ``P = -A : E``, formed ON THE DEVICE from the coefficient as it is sampled there (hommx_loads_source,
+        HOMMX_LOADS_EIGENSTRAIN), whatever the form of the coefficient: nobody multiplies by the stiffness by hand.
+
+        ``E`` takes what ``set_polarisation`` takes -- a callable ``E(x, y) -> [t, ...]``, ``[n_el, t]``, ``[N, n_el, t]``, a vector
+        ``Expression`` with t components, ``None`` --, with the components in the order and convention of ``Reconstruction.strain``:
+        Poisson a gradient; elasticity e00, e11[, e22], then the DOUBLED shears 2 e01[, 2 e02, 2 e12].  Replaces a polarisation.  A
+        plan stand-in without the capability is given ``-material(element means of A) E`` formed on the host (``eigenstress``)."""
+        self._set_load(E, True)
+
+    def _set_load(self, P, eigenstrain: bool):
+        what = "E" if eigenstrain else "P"
+        t = self._tensor_size()
+        if isinstance(P, Expression):
+            if P.shape != "vector" or P.n_comp != t:
+                raise ValueError(f"an Expression for {what} must be a vector of {t} components (Expression([c0, c1, ...])); got a {P.shape} "
+                                 f"of {P.n_comp}")
+            if P.n_y > self._tdim:
+                raise ValueError(f"the Expression reads y[{P.n_y - 1}]; the micro mesh has {self._tdim} dimensions")
+        elif P is not None and not callable(P):
             P = np.ascontiguousarray(P, dtype=float)
-            n_el, t = self._cell_mesh.num_cells, self._tensor_size()
+            n_el = self._cell_mesh.num_cells
             if P.shape not in ((n_el, t), (self._msh.num_cells, n_el, t)):
-                raise ValueError(f"P has shape {P.shape}; expected ({n_el}, {t}) or ({self._msh.num_cells}, {n_el}, {t})")
+                raise ValueError(f"{what} has shape {P.shape}; expected ({n_el}, {t}) or ({self._msh.num_cells}, {n_el}, {t})")
         self._polarisation = P
+        self._eigenstrain = bool(eigenstrain) and P is not None
         self.effective_polarisation = None
+
+    def set_polarisation_fields(self, values):
+        """The values of the fields ``f[k]`` of the LOAD expression (``set_polarisation`` / ``set_eigenstrain`` of an
+        ``Expression(..., fields=...)``), one per macro cell -- the temperature change of a thermal strain, say: the shapes, the
+        finiteness check and the process-group rule of ``set_fields``.  They are the load's own: the coefficient's fields are
+        ``set_fields``.  The plan is kept.  ``ValueError`` when the load is no ``Expression`` with fields."""
+        P = self._polarisation
+        if not isinstance(P, Expression) or P.n_fields == 0:
+            raise ValueError("set_polarisation_fields() needs a polarisation or an eigenstrain given as an Expression with fields "
+                             "(Expression([...], fields=...))")
+        self._polarisation_fields = self._field_values(P, values)
+        self.effective_polarisation = None
+
+    def _load_rows(self, cells: np.ndarray) -> np.ndarray:
+        """The rows of the load expression on ``cells``: the midpoints [N, 3] and, for one with fields, its own fields after them."""
+        c, P = self._msh.cell_midpoints()[cells], self._polarisation
+        if P.n_fields == 0:
+            return c
+        if self._polarisation_fields is None or self._polarisation_fields.shape[1] != P.n_fields:
+            raise RuntimeError(f"the load Expression reads the fields {', '.join(P.field_names)}: call set_polarisation_fields() with their "
+                               "values per macro cell first")
+        return np.concatenate([c, self._polarisation_fields[cells]], axis=1)
 
     @abstractmethod
     def _setup_macro_function_space(self) -> fem.FunctionSpace: ...
@@ -489,12 +577,13 @@ class BaseHMM(ABC):
     def _element_means(self, cells: np.ndarray, coeff=None) -> tuple[np.ndarray, str]:
         return self._pack_coefficient(self._sampled_means(cells, coeff))
 
-    def _sampled_means(self, cells: np.ndarray, coeff=None) -> np.ndarray:
-        """Element means [N, n_el, ...] of ``coeff`` (default: the coefficient) on the sampling boxes of ``cells``, as sampled."""
+    def _sampled_means(self, cells: np.ndarray, coeff=None, rows: np.ndarray | None = None) -> np.ndarray:
+        """Element means [N, n_el, ...] of ``coeff`` (default: the coefficient) on the sampling boxes of ``cells``, as sampled.
+        ``rows``: the x of ``coeff`` on ``cells`` when it is not that of the coefficient (``_load_rows``)."""
         yq, w = self._quadrature_points()
         n_el, nq = yq.shape[:2]
         yflat = yq.reshape(-1, self._tdim).T
-        c = self._cell_rows(cells, coeff)
+        c = self._cell_rows(cells, coeff) if rows is None else rows
         out = self._sample_batched(c, yflat, n_el, nq, w, coeff)
         if out is None:  # the callable is not broadcastable over cells: one call per macro cell (as the reference)
             first = self._sample_one(c[0], yflat, coeff)
@@ -717,7 +806,10 @@ class BaseHMM(ABC):
         ``t``, ``kind`` and ``solve(coef, M=None, return_info=False[, return_correctors])``; it may have ``reserve`` (needed by
         ``prepare()``), ``reconstruct``, ``device``, ``solve_two_phase``, ``solve_separable`` and ``solve_program``.  Without the last three it gets those
         coefficients as element means (``_sampled_on_device``: the one place that asks).  ``reconstruct(coef, xi, M, fields=...)`` is given element means
-        as an array and a device-sampled coefficient as the ``CoefStream``, under the same rule."""
+        as an array and a device-sampled coefficient as the ``CoefStream``, under the same rule.  ``loads(coef, P, M, per_cell=...,
+        response=..., fields=..., return_correctors=...)`` is given the load as per-cell element means unless the stand-in says
+        ``load_sources = True``: then an ``Expression`` load comes as its program ``CoefStream`` and an eigenstrain with
+        ``eigenstrain=True`` (``_loads_on_device``: the one place that asks that)."""
         form = self._sampled_on_device()
         if form is None:
             coef, kind = self._element_means(cells)
@@ -754,13 +846,35 @@ class BaseHMM(ABC):
         plan, stream, M = block(0, len(cells))
         return stream.solve(plan, M, return_info=True)
 
-    def _polarisation_loads(self, cells: np.ndarray) -> tuple[np.ndarray, bool]:
-        """The polarisation of ``cells`` as ``plan.loads`` takes it, one load: (P[1, n_el, t], False) when every cell shares it, else
-        (P[N, 1, n_el, t], True).  A callable is sampled where the coefficient is sampled (``_sampled_means``)."""
+    def _loads_on_device(self, kind: str) -> bool:
+        """Whether THE PLAN THAT STANDS HERE takes a load as a program ``CoefStream`` and forms the eigenstress itself
+        (``loads(..., eigenstrain=True)``): a ``MicroCellPlan`` says so with ``load_sources``; a stand-in without it gets per-cell
+        element means of the polarisation, as ever (``_coef_stream``).  The one place that asks."""
+        return bool(getattr(self._ensure_plan(kind), "load_sources", False))
+
+    def _polarisation_loads(self, cells: np.ndarray, kind: str | None = None) -> tuple:
+        """The load of ``cells`` as ``plan.loads`` takes it, one load: (P, per_cell, eigenstrain) with P[1, n_el, t] and per_cell False
+        when every cell shares it, else P[N, 1, n_el, t] and True.  A callable is sampled where the coefficient is sampled
+        (``_sampled_means``).  On a plan of kind ``kind`` that takes load sources (``_loads_on_device``) an ``Expression`` is its program
+        ``CoefStream`` on the same points (per_cell None) and an eigenstrain crosses as it is, ``eigenstrain`` True; on every other plan
+        the ``Expression`` is sampled like a callable and the eigenstress is formed here, from the element means of the coefficient."""
+        device = kind is not None and self._loads_on_device(kind)
+        P = self._load_input(cells, device)
+        if not self._eigenstrain or device:
+            return P + (self._eigenstrain,)
+        coef, packed = self._element_means(cells)
+        return np.ascontiguousarray(eigenstress(coef[:, None], packed, self._tdim, P[0])), True, False
+
+    def _load_input(self, cells: np.ndarray, device: bool) -> tuple:
+        """(P, per_cell) of ``_polarisation_loads``: what was set -- a polarisation or an eigenstrain -- on ``cells``."""
         P = self._polarisation
+        if isinstance(P, Expression) and device:
+            yq, w = self._quadrature_points()
+            return CoefStream.program(yq, w, *P.program(), P.n_comp, self._load_rows(cells), n_params=P.n_params, n_fields=P.n_fields), None
         if not callable(P):
             return (P[None], False) if P.ndim == 2 else (P[cells][:, None], True)
         t = self._tensor_size()
+        rows = self._load_rows(cells) if isinstance(P, Expression) else None
 
         def components_last(x, y):  # [t, ...] -> [..., t] over the broadcast of x and y: the layout the sampling takes a coefficient in
             v = P(x, y)
@@ -769,7 +883,7 @@ class BaseHMM(ABC):
             shape = np.broadcast(x[0], y[0]).shape
             return np.stack([np.broadcast_to(np.asarray(c, dtype=float), shape) for c in v], axis=-1)
 
-        return np.ascontiguousarray(self._sampled_means(cells, components_last)[:, None]), True
+        return np.ascontiguousarray(self._sampled_means(cells, components_last, rows)[:, None]), True
 
     def _plan_inputs(self, cells: np.ndarray, sample=None) -> tuple:
         """(plan, coef, M, sampled) of ``cells`` for the derived outputs of a plan (``reconstruct``, ``loads``, the sensitivities): the
@@ -790,8 +904,10 @@ class BaseHMM(ABC):
 
     def _load_blocks(self, cells: np.ndarray, chunk_cells: int | None, bytes_per_cell=None, **kw) -> list:
         """``plan.loads`` of the polarisation on ``cells``, chunk by chunk."""
-        return self._chunks(cells, chunk_cells, bytes_per_cell, lambda plan, coef, M, P, sub, b: plan.loads(coef, P[0], M, per_cell=P[1], **kw),
-                            lambda sub, kind: self._polarisation_loads(sub))
+        def call(plan, coef, M, P, sub, b):
+            return plan.loads(coef, P[0], M, per_cell=P[1], **(dict(eigenstrain=True) if P[2] else {}), **kw)
+
+        return self._chunks(cells, chunk_cells, bytes_per_cell, call, lambda sub, kind: self._polarisation_loads(sub, kind))
 
     def _effective_polarisation(self, cells: np.ndarray) -> np.ndarray:
         """P_eff[N, t] of ``cells`` (Levin: from the canonical correctors, on every route).  Under a process group every rank solves its

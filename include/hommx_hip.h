@@ -532,7 +532,26 @@ int hommx_stratification_sensitivity_source_device(hommx_plan* plan, int64_t n_c
  * columns its canonical pass has just left in the corrector arena (k_mesh_front_rhs) when it was created with HOMMX_MESH_FLAG_LOADS.
  *
  *   n_loads     1 .. t of the plan (callers loop for more)
- *   per_cell    0: P[n_loads][n_el][t], shared by all cells; 1: P[n_cells][n_loads][n_el][t]
+ *   per_cell    a code: where the load comes from, alone or or-ed with the flag HOMMX_LOADS_EIGENSTRAIN
+ *               HOMMX_LOADS_SHARED (0): P[n_loads][n_el][t], shared by all cells; HOMMX_LOADS_PER_CELL (1): P[n_cells][n_loads][n_el][t]
+ *               HOMMX_LOADS_PROGRAM (2): P is not read (NULL); the load is sampled on the device from P_source, a HOMMX_COEF_PROGRAM
+ *               source of the load's OWN beside the coefficient's: its own program with n_comp == t (the components of P in their
+ *               order), its own table (points), weights and n_q, its own params rows [n_cells][3 + n_fields] and n_fields.  n_loads
+ *               must be 1 (callers loop for more).  Per chunk the rows of its cells are expanded by the value pass of the interpreter
+ *               into plan-owned scratch, [cell][el][comp] = P[cell][0][el][:], and every consumer reads that as a per-cell load.  The
+ *               rounding contract of a program holds word for word: separately rounded operations in the written order, acc = acc +
+ *               w[q] v with q ascending from 0, so the load is bit for bit the per-cell array a host interpreter of the same program
+ *               forms.  Everything a HOMMX_COEF_PROGRAM coefficient source is checked for is checked of P_source, against t
+ *               components (and on every kind, HOMMX_KIND_ELASTICITY_VOIGT included)
+ *               HOMMX_LOADS_EIGENSTRAIN (4, a flag): what the array or the program delivers is an eigenstrain E^l_K[t] -- a thermal
+ *               strain alpha dT, a swelling, a misfit -- in the components and convention of hommx_reconstruct_batch's strain
+ *               (Poisson: a gradient; elasticity: e00, e11[, e22], then DOUBLED shears), and the load is the eigenstress
+ *               P^l_K = -material(coef_K) E^l_K, formed on the device (k_eigenstress) from the element stream of the call's
+ *               coefficient source, whatever its form, before anything reads P.  A shared E becomes a per-cell P (the coefficient
+ *               differs per cell) in plan-owned scratch, as does the caller's per-cell E of the device entry, which is left as it
+ *               is; the expansion of a program and the chunk of a per-cell E a host call has sent are overwritten in place
+ *   P_source    read ONLY when (per_cell & 3) == HOMMX_LOADS_PROGRAM: a caller built against the struct that ended with `info` and
+ *               passes codes 0 and 1 is never read past its end
  *   P_eff       [n_cells][n_loads][t], required
  *   A_eff, info of the canonical pass, as hommx_solve_batch, or NULL
  *   response, every one optional, any of them triggers the load solve:
@@ -542,7 +561,9 @@ int hommx_stratification_sensitivity_source_device(hommx_plan* plan, int64_t n_c
  *   strain, flux [n_cells][n_loads][n_el][t]: eps(chi_l)_K and q^l_K; both or neither
  *   correctors  [n_cells][n_loads][ndof], mean-free per component, dof order of hommx_solve_batch_correctors
  * src, M: as hommx_reconstruct_source.  HOMMX_EINVAL, before the plan's device is made current: a null plan, source or argument struct,
- * n_loads out of range, a null P or P_eff, one of strain / flux without the other.  HOMMX_EINVAL as well, before any work: a response output on a
+ * n_loads out of range, an unknown code in per_cell (a bit beyond 7, or (per_cell & 3) == 3), a null P (codes without HOMMX_LOADS_PROGRAM)
+ * or P_eff, for HOMMX_LOADS_PROGRAM a null P_source, one of another form, n_loads != 1, a program whose n_comp is not t and everything
+ * else a program source is refused for, one of strain / flux without the other.  HOMMX_EINVAL as well, before any work: a response output on a
  * plan of the frontal mesh route created without HOMMX_MESH_FLAG_LOADS ("mesh_front" builds its loads in the basis of the canonical ones;
  * with the flag the load solve substitutes on its pivot columns, and a chunk then also holds them: HOMMX_RECON_MEM_MB counts the arena,
  * and a chunk is at most one arena chunk; HOMMX_MESH_FLAG_TREE, the tree route, serves these too).  The correctors of
@@ -550,7 +571,15 @@ int hommx_stratification_sensitivity_source_device(hommx_plan* plan, int64_t n_c
  * plan-owned scratch.  A cell's outputs do not depend on its batch position, the chunking or which outputs are requested (fixed-order
  * reductions).  A cell whose elimination flags a pivot keeps its info; no other cell's outputs change.  The host entry sends a shared P
  * with the source's shared arrays once; a per-cell P and a sampled stream go in, and every output comes back, chunk by chunk.
+ * The points, weights and rows of P_source travel with the source's shared arrays too (the device entry takes device pointers in
+ * *P_source as in *src; both structs and the program are host memory and are read before it returns).  What the device forms of the load
+ * for a chunk (n_el t doubles per cell for a program, n_loads n_el t for an eigenstrain array it may not overwrite) counts in the chunk
+ * rule, and the expansion of a program in the 1 GiB bound of the expanded streams.
  */
+#define HOMMX_LOADS_SHARED 0
+#define HOMMX_LOADS_PER_CELL 1
+#define HOMMX_LOADS_PROGRAM 2     /* P is NULL; the load comes from P_source */
+#define HOMMX_LOADS_EIGENSTRAIN 4 /* flag, or-ed to any of the three: what arrives is an eigenstrain E, P = -material(coef) E */
 typedef struct hommx_load_args {
   int32_t n_loads;
   int32_t per_cell;
@@ -563,6 +592,7 @@ typedef struct hommx_load_args {
   double* flux;
   double* correctors;
   int32_t* info;
+  const hommx_coef_source* P_source; /* read only when (per_cell & 3) == HOMMX_LOADS_PROGRAM */
 } hommx_load_args;
 int hommx_loads_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_load_args* args);
 /* Same with DEVICE pointers (in *src and *args as well; the structs themselves are host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
