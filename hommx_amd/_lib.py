@@ -34,6 +34,7 @@ DIRS_PARAMETERS = 2  # HOMMX_DIRS_PARAMETERS: per_cell of SensArgs / Sens2Args, 
 DIRS_PARAMETERS_CURVATURE = 3  # HOMMX_DIRS_PARAMETERS_CURVATURE: per_cell of Sens2Args, d2A takes the curvature term as well (the Hessian)
 LOADS_SHARED, LOADS_PER_CELL, LOADS_PROGRAM = 0, 1, 2  # HOMMX_LOADS_*: per_cell of LoadArgs, where the load comes from
 LOADS_EIGENSTRAIN = 4  # HOMMX_LOADS_EIGENSTRAIN: a flag or-ed to them, what arrives is an eigenstrain
+CRIT_NSTATS = 4  # HOMMX_CRIT_NSTATS: max, argmax element, sum |K| v, sum |K| [v >= threshold]
 
 
 class PlanDesc(C.Structure):
@@ -162,6 +163,30 @@ class LoadArgs(C.Structure):
     ]
 
 
+class CriterionArgs(C.Structure):
+    """hommx_criterion_args: the criterion of hommx_criterion_source[_device], its one optional load, what is asked for and where it
+    goes.  The load members are read with ``has_load`` only, ``P_source`` for ``LOADS_PROGRAM`` only."""
+
+    _fields_ = [
+        ("program", C.POINTER(CoefProgram)),
+        ("n_fields", C.c_int32),
+        ("rows", C.c_void_p),
+        ("points", C.c_void_p),
+        ("xi", C.c_void_p),
+        ("threshold", C.c_double),
+        ("has_load", C.c_int32),
+        ("per_cell", C.c_int32),
+        ("P", C.c_void_p),
+        ("P_source", C.POINTER(CoefSource)),
+        ("crit", C.c_void_p),
+        ("values", C.c_void_p),
+        ("strain", C.c_void_p),
+        ("flux", C.c_void_p),
+        ("A_eff", C.c_void_p),
+        ("info", C.c_void_p),
+    ]
+
+
 def _prototypes() -> dict:
     """name -> (restype, argtypes) of every symbol include/hommx_hip.h declares: ``load()`` declares them from this table, and
     the tests check that the header and the library export exactly these names."""
@@ -212,6 +237,8 @@ def _prototypes() -> dict:
         "hommx_stratification_sensitivity_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(StratSensArgs), vp]),
         "hommx_loads_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(LoadArgs)]),
         "hommx_loads_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(LoadArgs), vp]),
+        "hommx_criterion_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(CriterionArgs)]),
+        "hommx_criterion_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(CriterionArgs), vp]),
         "hommx_solve_batch_two_phase": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_two_phase_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_separable": (c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),

@@ -202,6 +202,28 @@ class LoadResponse:
     cells: np.ndarray | None = None
 
 
+@dataclass
+class CriterionResult:
+    """A failure criterion on the reconstructed micro state of macro cells (include/hommx_hip.h, hommx_criterion_source).
+
+    ``max[N]``: the largest value v_K of the criterion over the micro elements and ``argmax_element[N]`` the smallest element reaching
+    it (a NaN value never wins; -inf and -1 when every value is NaN); ``mean[N]``: sum |K| v_K over the unit cell (NaN when a value
+    is); ``exceed_volume[N]``: the volume fraction of the elements with v_K >= threshold.  With ``values`` ``values[N, n_el]``, with
+    ``fields`` ``strain`` and ``flux`` ``[N, n_el, t]``, the total state the criterion saw (a load included).  ``A_eff[N, t, t]`` and
+    ``info[N]`` of the canonical pass.  ``cells``: the macro cells (``BaseHMM.criterion``).  What was not asked for is None."""
+
+    max: np.ndarray
+    argmax_element: np.ndarray
+    mean: np.ndarray
+    exceed_volume: np.ndarray
+    A_eff: np.ndarray
+    info: np.ndarray
+    values: np.ndarray | None = None
+    strain: np.ndarray | None = None
+    flux: np.ndarray | None = None
+    cells: np.ndarray | None = None
+
+
 REGION_FIELDS = ("region_volume", "region_mean_strain", "region_mean_flux", "region_energy", "region_max_flux", "region_argmax_element")
 
 
@@ -727,6 +749,75 @@ class MicroCellPlan:
             r.argmax_element = stats[:, :, self.t + 1].astype(np.int64)
         return r
 
+    def _criterion_program(self, crit) -> Program:
+        """The program of a ``hommx_amd.expr.Criterion`` on this plan (its index checks against t and n_comp run here)."""
+        ops, consts = crit.program(self.t, self.n_comp)
+        if crit.n_y > self.dim:
+            raise ValueError(f"the criterion reads y[{crit.n_y - 1}]; the micro mesh has {self.dim} dimensions")
+        return Program(np.ascontiguousarray(ops), np.ascontiguousarray(consts), 1, int(crit.n_params), int(crit.n_fields))
+
+    def criterion(self, coef, xi: np.ndarray, crit, M: np.ndarray | None = None, rows=None, points=None, values: bool = False,
+                  fields: bool = False, P=None, per_cell: bool | None = None, eigenstrain: bool = False) -> CriterionResult:
+        """A failure criterion on the reconstructed micro state (hommx_criterion_source): ``coef`` an array or a ``CoefStream``, xi and M
+        as ``reconstruct`` takes them, ``crit`` a ``hommx_amd.expr.Criterion`` -> ``CriterionResult``: per cell the largest value, the
+        element reaching it, the mean and the volume fraction at or above ``crit.threshold``.  The stress never leaves the device:
+        four numbers per macro cell come back, unless ``values`` (v_K of every element) or ``fields`` (the strain and flux the
+        criterion saw) ask for more.  ``rows[N_c, 3 + crit.n_fields]``: the macro midpoint and the criterion's own fields of every cell
+        (required when the criterion reads ``f``; without them ``x`` is 0); ``points[n_el, dim]``: the element centroids, required when
+        it reads ``y``.
+
+        ``P``: ONE load as ``loads`` takes it -- ``P[n_el, t]`` / ``P[1, n_el, t]`` shared by all cells, ``P[N_c, (1,) n_el, t]`` per
+        cell, or a program ``CoefStream`` of a vector ``Expression``; ``eigenstrain`` as in ``loads``.  The criterion then sees the
+        total state, strain xi + eps(chi^xi + chi_P) and flux material . strain + P, after a load solve on the route ``load_kernel``
+        names (needs ``load_solve=True`` on the frontal mesh route).  The batch runs in the chunks of ``reconstruct`` / ``loads``."""
+        stream = self._as_stream(coef)
+        nc = self._check_stream(stream)
+        xi = np.ascontiguousarray(xi, dtype=np.float64)
+        if xi.shape != (nc, self.t):
+            raise ValueError(f"xi has shape {xi.shape}; expected ({nc}, {self.t})")
+        prog = self._criterion_program(crit)
+        pstruct = prog.struct()
+        if rows is None:
+            if crit.n_fields:
+                raise ValueError(f"the criterion reads the fields {', '.join(crit.field_names)}: pass rows[N_c, 3 + {crit.n_fields}]")
+            rows = np.zeros((nc, 3))
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        if rows.shape != (nc, 3 + crit.n_fields):
+            raise ValueError(f"rows has shape {rows.shape}; expected ({nc}, 3 + {crit.n_fields}): the midpoint, then the criterion's fields")
+        if points is not None:
+            points = np.ascontiguousarray(points, dtype=np.float64)
+            if points.shape != (self.n_el, self.dim):
+                raise ValueError(f"points has shape {points.shape}; expected ({self.n_el}, {self.dim}): the element centroids")
+        elif crit.n_y:
+            raise ValueError(f"the criterion reads y[{crit.n_y - 1}]: pass points[n_el, dim], the element centroids")
+        P_src, P_ptr, code = None, None, 0
+        if isinstance(P, CoefStream):
+            self._check_load_stream(P, nc)
+            P_src, code = P.coef_source(), _lib.LOADS_PROGRAM
+        elif P is not None:
+            P = np.asarray(P, dtype=np.float64)
+            if P.ndim == 4 and P.shape[1] == 1:  # per cell, with the axis of the one load
+                P = P[:, 0]
+            elif P.ndim == 3 and P.shape[0] == 1 and not per_cell:  # shared, with that axis
+                P = P[0]
+            if P.shape not in ((self.n_el, self.t), (nc, self.n_el, self.t)):
+                raise ValueError(f"P has shape {P.shape}; expected ({self.n_el}, {self.t}) or ({nc}, {self.n_el}, {self.t}), one load "
+                                 "(an axis of length 1 for it is accepted)")
+            P = np.ascontiguousarray(np.broadcast_to(P, (nc, self.n_el, self.t)))  # a shared load is repeated: points is the call's shared array
+            P_ptr, code = P.ctypes.data, _lib.LOADS_PER_CELL
+        if eigenstrain and P is not None:
+            code |= _lib.LOADS_EIGENSTRAIN
+        out = np.empty((nc, _lib.CRIT_NSTATS), dtype=np.float64)
+        vals = np.empty((nc, self.n_el), dtype=np.float64) if values else None
+        strain = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
+        flux = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
+        addr = lambda a: None if a is None else a.ctypes.data
+        args = _lib.CriterionArgs(C.pointer(pstruct), int(crit.n_fields), rows.ctypes.data, addr(points), xi.ctypes.data, float(crit.threshold),
+                                  int(P is not None), code, P_ptr, C.pointer(P_src) if P_src is not None else None, out.ctypes.data,
+                                  addr(vals), addr(strain), addr(flux), None, None)
+        A, info = self._source_call("hommx_criterion_source", nc, M, stream, args)
+        return CriterionResult(out[:, 0].copy(), out[:, 1].astype(np.int64), out[:, 2].copy(), out[:, 3].copy(), A, info, vals, strain, flux)
+
     def solve_two_phase(self, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None = None,
                         return_info: bool = False):
         """Two-phase media sampled on the device: mask[n_el] (bool / uint8, phase of every micro element) and
@@ -891,6 +982,26 @@ class MicroCellPlan:
                              C.pointer(P_source) if P_source is not None else None)
         _lib.check(self._lib.hommx_loads_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
                    "hommx_loads_source_device")
+
+    def criterion_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, xi_ptr: int, crit, rows_ptr: int, crit_ptr: int,
+                         points_ptr: int | None = None, values_ptr: int | None = None, strain_ptr: int | None = None,
+                         flux_ptr: int | None = None, P_ptr: int | None = None, P_source: "_lib.CoefSource | None" = None,
+                         eigenstrain: bool = False, A_ptr: int | None = None, info_ptr: int | None = None, stream: int | None = None):
+        """Device-pointer form of ``criterion`` (hommx_criterion_source_device), asynchronous on ``stream``: ``source`` =
+        ``CoefStream.coef_source(upload)`` with device addresses; ``crit`` the ``Criterion`` (its program is host memory);
+        rows[n_cells, 3 + crit.n_fields], points[n_el, dim] (None: the criterion reads no ``y``) -> crit[n_cells, 4] = [max | argmax
+        element | sum |K| v | sum |K| [v >= threshold]], values[n_cells, n_el], strain / flux[n_cells, n_el, t].  A load:
+        ``P_ptr`` (P[n_cells, n_el, t], per cell) or ``P_source`` (a program, as in ``loads_device``), ``eigenstrain`` as there."""
+        prog = self._criterion_program(crit)
+        pstruct = prog.struct()
+        has_load = P_ptr is not None or P_source is not None
+        code = (_lib.LOADS_PROGRAM if P_source is not None else _lib.LOADS_PER_CELL) | (_lib.LOADS_EIGENSTRAIN if eigenstrain else 0)
+        args = _lib.CriterionArgs(C.pointer(pstruct), int(crit.n_fields), rows_ptr, points_ptr or None, xi_ptr, float(crit.threshold),
+                                  int(has_load), code if has_load else 0, None if P_source is not None else P_ptr or None,
+                                  C.pointer(P_source) if P_source is not None else None, crit_ptr, values_ptr or None, strain_ptr or None,
+                                  flux_ptr or None, A_ptr or None, info_ptr or None)
+        _lib.check(self._lib.hommx_criterion_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
+                   "hommx_criterion_source_device")
 
     def solve_separable_device(self, n_cells: int, family: str, n_q: int, table_ptr: int, weights_ptr: int | None, params_ptr: int,
                                M_ptr: int | None, out_ptr: int, info_ptr: int | None, stream: int | None = None):

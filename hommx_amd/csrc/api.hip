@@ -116,7 +116,7 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 //            them, at [chunk][n_pairs][n_el][n_comp], the first derivatives of A_H along them, [nc][n_pairs][t][t] (stream_chunk too)
 // B_POLAR: the loads of one chunk of hommx_loads_source that the device forms: the expansion of a program load, [nc][n_el][t]
 //            (derived_call; an eigenstrain becomes the eigenstress in place), or the eigenstresses of an eigenstrain array that is not
-//            the plan's to overwrite, [nc][n_loads][n_el][t] (loads_run)
+//            the plan's to overwrite, [nc][n_loads][n_el][t] (loads_run; crit_run: the one load of a criterion)
 enum {
   B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, B_SENS2, B_TANGENT, B_CURVATURE,
   B_POLAR, N_BUF
@@ -291,9 +291,10 @@ hommx_coef_source source_of_form(const hommx_coef_source& s) {
 
 // The whole program of a HOMMX_COEF_PROGRAM source against the plan's descriptor, on the host: the kernel then interprets it unchecked.
 // load_comp: 0 for the coefficient; the tensor size t of the plan for the program of a load (HOMMX_LOADS_PROGRAM), which has t
-// components on every kind
-int program_check(const hommx_plan* p, const hommx_coef_source* s, int load_comp = 0) {
-  if (!load_comp && p->desc.kind == HOMMX_KIND_ELASTICITY_VOIGT)
+// components on every kind.  state: 0, or the 2 t + n_comp state entries behind the fields in the row of a criterion
+// (hommx_criterion_args.program): one component on every kind, and of `s` only program and n_fields are read
+int program_check(const hommx_plan* p, const hommx_coef_source* s, int load_comp = 0, int state = 0) {
+  if (!load_comp && !state && p->desc.kind == HOMMX_KIND_ELASTICITY_VOIGT)
     return fail(HOMMX_EINVAL, "expression coefficients are not supported for the 21-component Voigt kind");
   const hommx_coef_program* g = s->program;
   if (!g) return fail(HOMMX_EINVAL, "null program");
@@ -307,14 +308,17 @@ int program_check(const hommx_plan* p, const hommx_coef_source* s, int load_comp
     return fail(HOMMX_EINVAL, "program: n_params is %d, above n_consts (%d): the parameters are the first constants", g->n_params, g->n_consts);
   if (s->n_fields < 0 || s->n_fields > hommx::PROGRAM_MAX_FIELDS)
     return fail(HOMMX_EINVAL, "program source: n_fields must be 0 .. %d, got %d", hommx::PROGRAM_MAX_FIELDS, s->n_fields);
-  const int n_row = hommx::program_row_doubles(s->n_fields);
-  const int n_comp = load_comp ? load_comp : hommx::kind_sizes(p->desc.dim, p->desc.kind).n_comp;
+  const int n_row = hommx::program_row_doubles(s->n_fields) + state;
+  const int n_comp = state ? 1 : load_comp ? load_comp : hommx::kind_sizes(p->desc.dim, p->desc.kind).n_comp;
+  if (g->n_comp != n_comp && state) return fail(HOMMX_EINVAL, "program: n_comp is %d, a criterion has one component", g->n_comp);
   if (g->n_comp != n_comp && load_comp)
     return fail(HOMMX_EINVAL, "program: n_comp is %d, a load of this plan has t = %d components", g->n_comp, n_comp);
   if (g->n_comp != n_comp) return fail(HOMMX_EINVAL, "program: n_comp is %d, the plan's coefficient has %d components", g->n_comp, n_comp);
   if (!g->ops || (g->n_consts > 0 && !g->consts)) return fail(HOMMX_EINVAL, "null program ops / consts");
-  if (s->n_q < 1) return fail(HOMMX_EINVAL, "program source needs n_q >= 1");
-  if (!s->table || !s->weights || !s->params) return fail(HOMMX_EINVAL, "null table / weights / params");
+  if (!state) {  // a criterion is interpreted on the element's state: no quadrature rule, and its rows are the call's own argument
+    if (s->n_q < 1) return fail(HOMMX_EINVAL, "program source needs n_q >= 1");
+    if (!s->table || !s->weights || !s->params) return fail(HOMMX_EINVAL, "null table / weights / params");
+  }
   int depth = 0;
   bool stored[hommx::PROGRAM_MAX_COMP] = {};
   for (int pc = 0; pc < g->n_ops; ++pc) {
@@ -323,6 +327,9 @@ int program_check(const hommx_plan* p, const hommx_coef_source* s, int load_comp
     if (op == hommx::OP_CONST && k >= g->n_consts)
       return fail(HOMMX_EINVAL, "program: constant index %d out of range [0,%d) at instruction %d", k, g->n_consts, pc);
     if (op == hommx::OP_X && k >= n_row) {
+      if (state)
+        return fail(HOMMX_EINVAL, "program: x index %d out of range [0,%d) (the midpoint, %d fields and the 2 t + n_comp = %d state entries) "
+                                  "at instruction %d", k, n_row, s->n_fields, state, pc);
       if (s->n_fields == 0) return fail(HOMMX_EINVAL, "program: x index %d out of range [0,3) at instruction %d", k, pc);
       return fail(HOMMX_EINVAL, "program: x index %d out of range [0,%d) (the midpoint and %d fields) at instruction %d", k, n_row, s->n_fields, pc);
     }
@@ -1467,20 +1474,35 @@ int loads_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_load_a
   return HOMMX_OK;
 }
 
+// the code of a load (hommx_load_args.per_cell; hommx_criterion_args.per_cell) and, for HOMMX_LOADS_PROGRAM, its source `l`
+int load_code_check(const hommx_plan* p, int32_t n_loads, int32_t code, const hommx_coef_source* l) {
+  if ((code & ~7) || load_form(code) == 3)
+    return fail(HOMMX_EINVAL, "unknown load code %d in per_cell: HOMMX_LOADS_SHARED, HOMMX_LOADS_PER_CELL or HOMMX_LOADS_PROGRAM, alone or "
+                              "or-ed with HOMMX_LOADS_EIGENSTRAIN", code);
+  if (load_form(code) != HOMMX_LOADS_PROGRAM) return HOMMX_OK;
+  if (!l) return fail(HOMMX_EINVAL, "HOMMX_LOADS_PROGRAM needs P_source, the program source of the load");
+  if (l->form != HOMMX_COEF_PROGRAM) return fail(HOMMX_EINVAL, "P_source must be a HOMMX_COEF_PROGRAM source, got form %d", l->form);
+  if (n_loads != 1) return fail(HOMMX_EINVAL, "HOMMX_LOADS_PROGRAM takes n_loads == 1 (callers loop for more), got %d", n_loads);
+  if (int rc = program_check(p, l, hommx::kind_sizes(p->desc.dim, p->desc.kind).t)) return prefix_error(rc, "P_source: ");
+  return HOMMX_OK;
+}
+
+// what refuses a load solve before any work: the one check that reads more of the plan than its descriptor (its family), so it cannot
+// run on the plan-shaped memory the argument checks accept: it comes after open_call, with the device current already
+int load_solve_check(const hommx_plan* p) {
+  if (p->family == FAM_MESH && !mesh_loads(p))
+    return fail(HOMMX_EINVAL, "the frontal mesh route (mesh_front) solves for the canonical loads only: energy, stats, strain / flux and "
+                              "correctors of user loads need a plan of the tree route (HOMMX_MESH_FLAG_TREE, route=\"tree\"); P_eff alone works here");
+  return HOMMX_OK;
+}
+
 // the argument checks of both entry points, then the routes the call needs: one that forms correctors, and for a response a load solve
 int loads_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_load_args* a, bool device) {
   auto checks = [&] {
     const int t = hommx::kind_sizes(p->desc.dim, p->desc.kind).t;
     if (a->n_loads < 1 || a->n_loads > t) return fail(HOMMX_EINVAL, "n_loads must be 1 .. %d (the tensor size of the plan), got %d", t, a->n_loads);
-    if ((a->per_cell & ~7) || load_form(a->per_cell) == 3)
-      return fail(HOMMX_EINVAL, "unknown load code %d in per_cell: HOMMX_LOADS_SHARED, HOMMX_LOADS_PER_CELL or HOMMX_LOADS_PROGRAM, alone or "
-                                "or-ed with HOMMX_LOADS_EIGENSTRAIN", a->per_cell);
+    if (int rc = load_code_check(p, a->n_loads, a->per_cell, a->P_source)) return rc;
     if (load_form(a->per_cell) == HOMMX_LOADS_PROGRAM) {
-      const hommx_coef_source* l = a->P_source;
-      if (!l) return fail(HOMMX_EINVAL, "HOMMX_LOADS_PROGRAM needs P_source, the program source of the load");
-      if (l->form != HOMMX_COEF_PROGRAM) return fail(HOMMX_EINVAL, "P_source must be a HOMMX_COEF_PROGRAM source, got form %d", l->form);
-      if (a->n_loads != 1) return fail(HOMMX_EINVAL, "HOMMX_LOADS_PROGRAM takes n_loads == 1 (callers loop for more), got %d", a->n_loads);
-      if (int rc = program_check(p, l, t)) return prefix_error(rc, "P_source: ");
       if (!a->P_eff) return fail(HOMMX_EINVAL, "null P_eff");
     } else if (!a->P || !a->P_eff) {
       return fail(HOMMX_EINVAL, "null P / P_eff");
@@ -1490,11 +1512,7 @@ int loads_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, con
   };
   if (int rc = source_open(p, n_cells, src, a, device, checks); rc != GO) return rc;
   if (!load_response(*a)) return GO;
-  // the one check that reads more of the plan than its descriptor (its family), so it cannot run on the plan-shaped memory the checks
-  // above accept: it comes after open_call, with the device current already, and before any work (a mesh plan gets no workspace above)
-  if (p->family == FAM_MESH && !mesh_loads(p))
-    return fail(HOMMX_EINVAL, "the frontal mesh route (mesh_front) solves for the canonical loads only: energy, stats, strain / flux and "
-                              "correctors of user loads need a plan of the tree route (HOMMX_MESH_FLAG_TREE, route=\"tree\"); P_eff alone works here");
+  if (int rc = load_solve_check(p)) return rc;  // before any work (a mesh plan gets no workspace above)
   if (int rc = load_workspace(p)) return rc;
   return GO;
 }
@@ -1520,6 +1538,124 @@ int loads_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const
   return derived_call(p, n_cells, s, M, v, in, out, &a.info, formed + (response ? sizeof(double) * plan_ndof(p) * t : 0),
                       response ? load_chunk : recon_chunk, device, st,
                       [&](int64_t nc, int64_t chunk, const Chunk<hommx_load_args>& c) { return loads_run(p, nc, chunk, c, device, st); },
+                      nullptr, false, program ? &load : nullptr);
+}
+
+// -- failure criteria (hommx_criterion_source[_device]) ------------------------------------------------------------------------------------
+// a caller's arguments that crit_open has passed: the load members are read with has_load only, P_source for its own code only
+hommx_criterion_args crit_args_of(const hommx_criterion_args& a) {
+  hommx_criterion_args c = a;
+  const bool program = a.has_load && load_form(a.per_cell) == HOMMX_LOADS_PROGRAM;
+  c.has_load = a.has_load != 0;
+  c.per_cell = a.has_load ? a.per_cell : 0;
+  c.P = a.has_load && !program ? a.P : nullptr;
+  c.P_source = program ? a.P_source : nullptr;
+  return c;
+}
+// the field of a cell lies in LDS beside the stack rows of the program, or in a slot of the chunk's scratch
+bool crit_in_lds(const hommx_plan* p, int depth) { return hommx::criterion_lds_bytes(plan_ndof(p), depth) <= hommx::recon_lds_limit(); }
+
+// one chunk on the device.  Without a load: the canonical correctors into the plan's scratch, then k_criterion.  With one, the chunk of
+// a response of loads_run: the eigenstress where the flag is set, the canonical correctors, the corrector of the load into the second
+// block (load_correctors), then k_criterion with chi_P and P
+int crit_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_criterion_args>& v, bool device, hipStream_t st) {
+  const hommx_criterion_args& a = v.a;
+  const int t = p->ks.t, depth = program_depth(*a.program);
+  const bool slot = !crit_in_lds(p, depth);
+  const double* P = a.P;
+  if (a.has_load && load_eigenstrain(a.per_cell)) {
+    double* stress = const_cast<double*>(a.P);
+    if (eigenstress_scratch(a.per_cell, device)) {
+      if (int rc = grow(p->buf[B_POLAR], sizeof(double) * chunk * p->n_el * t)) return rc;
+      stress = static_cast<double*>(p->buf[B_POLAR].p);
+    }
+    HIP_TRY(hommx::launch_eigenstress(p->desc.dim, p->desc.kind, v.coef, a.P, true, stress, 1, p->n_el, nc, st));
+    P = stress;
+  }
+  double *d_A_eff = a.A_eff, *corr = nullptr;
+  if (int rc = chunk_correctors(p, nc, chunk, v.coef, v.M, &d_A_eff, a.info, (a.has_load ? t : 0) + (slot ? 1 : 0), st, &corr)) return rc;
+  hommx::CritArgs k;
+  set_geometry(p, k);
+  k.corr = corr;
+  k.coef = v.coef;
+  k.M = v.M;
+  k.xi = a.xi;
+  k.prog = program_args(*a.program);
+  k.n_fields = a.n_fields;
+  k.rows = a.rows;
+  k.points = a.points;
+  k.threshold = a.threshold;
+  k.crit = a.crit;
+  k.values = a.values;
+  k.strain = a.strain;
+  k.flux = a.flux;
+  double* behind = corr + chunk * t * k.ndof;
+  if (a.has_load) {
+    if (int rc = load_correctors(p, nc, chunk, v.coef, v.M, hommx::LoadOverride{P, 1, true}, st, behind)) return rc;
+    k.corr_load = behind;
+    k.P = P;
+    k.per_cell = true;
+    behind += chunk * t * k.ndof;
+  }
+  k.slot = slot ? behind : nullptr;
+  HIP_TRY(hommx::launch_criterion(k, depth, nc, st));
+  return HOMMX_OK;
+}
+
+// the argument checks of both entry points, then the routes the call needs: one that forms correctors, and with a load a load solve
+int crit_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_criterion_args* a, bool device) {
+  auto checks = [&] {
+    const hommx::KindSizes ks = hommx::kind_sizes(p->desc.dim, p->desc.kind);
+    if (!a->program) return fail(HOMMX_EINVAL, "null program");
+    if (!a->rows || !a->xi || !a->crit) return fail(HOMMX_EINVAL, "null rows / xi / crit");
+    if (!a->strain != !a->flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
+    hommx_coef_source own{};  // what program_check reads of a source
+    own.n_fields = a->n_fields;
+    own.program = a->program;
+    if (int rc = program_check(p, &own, 0, 2 * ks.t + ks.n_comp)) return rc;
+    if (!a->points)
+      for (int pc = 0; pc < a->program->n_ops; ++pc)
+        if (a->program->ops[2 * pc] == hommx::OP_Y)
+          return fail(HOMMX_EINVAL, "null points: the program reads y (instruction %d), the centroid of the element", pc);
+    if (a->threshold != a->threshold) return fail(HOMMX_EINVAL, "the threshold is NaN");
+    if (!a->has_load) return HOMMX_OK;
+    if (int rc = load_code_check(p, 1, a->per_cell, a->P_source)) return rc;
+    if (load_form(a->per_cell) == HOMMX_LOADS_SHARED)
+      return fail(HOMMX_EINVAL, "a criterion takes its load per cell (HOMMX_LOADS_PER_CELL) or as a program (HOMMX_LOADS_PROGRAM): points is "
+                                "the one array every cell shares");
+    if (load_form(a->per_cell) == HOMMX_LOADS_PER_CELL && !a->P) return fail(HOMMX_EINVAL, "null P");
+    return HOMMX_OK;
+  };
+  if (int rc = source_open(p, n_cells, src, a, device, checks); rc != GO) return rc;
+  if (!a->has_load) return GO;
+  if (int rc = load_solve_check(p)) return rc;
+  if (int rc = load_workspace(p)) return rc;
+  return GO;
+}
+
+// With a load a chunk holds a second corrector block per cell and ends in a load solve; the slot of a field that does not fit LDS
+// beside the stack counts where the chunk rule of the reconstruction does not count one already
+int crit_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_criterion_args& args, bool device,
+              hipStream_t st) {
+  const int64_t t = p->ks.t, field = p->n_el * t;
+  Chunk<hommx_criterion_args> v{};
+  hommx_criterion_args& a = v.a = crit_args_of(args);
+  const bool program = a.P_source != nullptr;
+  ProgramLoad load{};
+  if (program) {
+    const hommx_coef_source& l = *a.P_source;
+    load = {program_source(l.program, l.n_q, l.table, l.weights, l.params, l.n_fields), &a.P};
+  }
+  const size_t formed = program || (a.has_load && eigenstress_scratch(a.per_cell, device)) ? sizeof(double) * field : 0;
+  const bool own_slot = !crit_in_lds(p, program_depth(*a.program)) && recon_in_lds(p);
+  const size_t blocks = sizeof(double) * plan_ndof(p) * ((a.has_load ? t : 0) + (own_slot ? 1 : 0));
+  const CellArray in[] = {{&a.rows, hommx::program_row_doubles(a.n_fields)},
+                          {&a.xi, t},
+                          {&a.P, a.has_load ? field : 0},
+                          {&a.points, p->n_el * p->desc.dim, SHARED}};
+  const CellArray out[] = {{&a.crit, HOMMX_CRIT_NSTATS}, {&a.A_eff, t * t, KEPT}, {&a.values, p->n_el}, {&a.strain, field}, {&a.flux, field}};
+  return derived_call(p, n_cells, s, M, v, in, out, &a.info, formed + blocks, a.has_load ? load_chunk : recon_chunk, device, st,
+                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_criterion_args>& c) { return crit_run(p, nc, chunk, c, device, st); },
                       nullptr, false, program ? &load : nullptr);
 }
 
@@ -1670,6 +1806,17 @@ int hommx_loads_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_s
 int hommx_loads_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_load_args* args) {
   if (int rc = loads_open(p, n_cells, src, args, false); rc != GO) return rc;
   return loads_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
+}
+
+int hommx_criterion_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                  const hommx_criterion_args* args, void* stream) {
+  if (int rc = crit_open(p, n_cells, src, args, true); rc != GO) return rc;
+  return crit_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream));
+}
+
+int hommx_criterion_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_criterion_args* args) {
+  if (int rc = crit_open(p, n_cells, src, args, false); rc != GO) return rc;
+  return crit_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
 }
 
 int hommx_second_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "../../include/hommx_hip.h"
+#include "coef_program.h"
 
 namespace hommx {
 
@@ -202,6 +203,30 @@ hipError_t launch_load_stats(const LoadArgs& a, long long nc, hipStream_t stream
 // in the components of the reconstruction's strain (shear doubled); P may be E itself when per_cell
 hipError_t launch_eigenstress(int dim, int kind, const double* coef, const double* E, bool per_cell, double* P, int n_loads, long long n_el,
                               long long nc, hipStream_t stream);
+
+// criterion.hip: a failure criterion -- one scalar program of the element's strain, flux and coefficient -- on the reconstructed micro
+// state of `nc` cells, and its per-cell statistics (include/hommx_hip.h, hommx_criterion_source)
+struct CritArgs : ElemWalk {
+  const double* coef = nullptr;      // [nc][n_el][n_comp]
+  const double* xi = nullptr;        // [nc][t]
+  ProgramArgs prog;                  // n_comp == 1; `X k` reads the row [midpoint (3) | fields | strain (t) | flux (t) | coefficient (n_comp)]
+  int n_fields = 0;
+  const double* rows = nullptr;      // [nc][3 + n_fields]
+  const double* points = nullptr;    // [n_el][dim] element centroids, or null (no Y in the program)
+  double threshold = 1.0;
+  const double* corr_load = nullptr; // [nc][t][ndof]: row 0 is the corrector of the load, or null (no load: P is null as well)
+  const double* P = nullptr;         // [n_el][t] or, per_cell, [nc][n_el][t]
+  bool per_cell = false;
+  double* crit = nullptr;            // [nc][4] = [max | argmax element | sum |K| v | sum |K| [v >= threshold]]
+  double* values = nullptr;          // [nc][n_el] or null
+  double* strain = nullptr;          // [nc][n_el][t] or null (then flux is null as well)
+  double* flux = nullptr;
+  double* slot = nullptr;            // [nc][ndof] scratch for the field of cells that do not fit LDS beside the stack (null: LDS)
+};
+// dynamic LDS of k_criterion with the field in it: the field and the stack rows below the top, one of kWalkThreads doubles per level
+size_t criterion_lds_bytes(long long ndof, int depth);
+// depth: the maximal stack depth of the (validated) program
+hipError_t launch_criterion(const CritArgs& a, int depth, long long nc, hipStream_t stream);
 
 // the loads a corrector pass of the blocked family solves for instead of the canonical ones: rows l < n_loads of Brhs from P (device), the
 // rest zero.  P starts at the first cell of the call

@@ -81,14 +81,17 @@ class _Node:
 _POW = -1  # a node of the tree only: the program spells it DUP / MUL
 _PARAM = -2  # p[k], a node of the tree only: the program spells it CONST k (the parameters are the first constants)
 _FIELD = -3  # f[k], a node of the tree only: the program spells it X 3 + k (the fields stand after the midpoint in the cell's row)
+_STATE = -4  # e[k], s[k] or c[k] of a Criterion, a node of the tree only (value: the name and k): ``X`` on the wider row, once t is known
+MAX_STATE_INDEX = 20  # the largest index a state name can have on any plan (c[20]: the 21 Voigt entries)
 
 
 class _Context:
     """What the components of one Expression share while they are checked: the number of parameters (None: no ``p=``), of fields
-    (None: no ``fields=``) and the texts of the comparisons that read one."""
+    (None: no ``fields=``) and the texts of the comparisons that read one.  ``state``: the text is a ``Criterion``'s, which also
+    reads the element's strain ``e[k]``, flux ``s[k]`` and coefficient ``c[k]``."""
 
-    def __init__(self, n_params=None, n_fields=None):
-        self.n_params, self.n_fields, self.compared = n_params, n_fields, []
+    def __init__(self, n_params=None, n_fields=None, state=False):
+        self.n_params, self.n_fields, self.compared, self.state = n_params, n_fields, [], state
 
 
 def _number(node, value) -> _Node:
@@ -120,6 +123,10 @@ def _check(node, ctx: _Context) -> _Node:
             if not _literal_int(node.slice, 0, ctx.n_fields - 1):
                 raise _bad(node, f"the index of f is a literal integer below the number of fields ({ctx.n_fields})")
             return _Node(_FIELD, value=int(node.slice.value), varying=True, p_degree=1)
+        if ctx.state and isinstance(node.value, ast.Name) and node.value.id in ("e", "s", "c"):
+            if not _literal_int(node.slice, 0, MAX_STATE_INDEX):
+                raise _bad(node, f"the index of {node.value.id} is a literal integer 0 .. {MAX_STATE_INDEX}")
+            return _Node(_STATE, value=(node.value.id, int(node.slice.value)), degree=1, varying=True)
         if not (isinstance(node.value, ast.Name) and node.value.id in ("x", "y")):
             raise _bad(node, "only x and y are indexed")
         if not _literal_int(node.slice, 0, 2):
@@ -248,6 +255,8 @@ def _emit_plain(n: _Node, ops: list, consts: list, n_params: int):
         ops.append((OP_CONST, n.value))
     elif n.op == _FIELD:
         ops.append((OP_X, 3 + n.value))
+    elif n.op == _STATE:
+        ops.append((OP_X, n.value))  # (name, k): Criterion.program(t, n_comp) writes the index
     elif n.op in (OP_X, OP_Y):
         ops.append((n.op, n.value))
     elif n.op == _POW:
@@ -679,6 +688,135 @@ class Expression:
                     acc[s][c] = acc[s][c] + w[q] * np.broadcast_to(hs, shape)
         out = np.stack([np.stack(a, axis=-1) for a in acc], axis=1)  # [N, n_pairs, n_el, n_comp]
         return out[..., 0] if self._flat else out
+
+
+class Criterion:
+    """A failure criterion: ONE scalar expression of the reconstructed micro state of an element, evaluated on the device where the
+    stress is formed (include/hommx_hip.h, hommx_criterion_source; csrc/criterion.hip) and, by ``host_values``, with
+    NumPy -- the same operations in the same order.
+
+    The grammar is ``Expression``'s with three more indexed names: ``s[k]``, k < t, the flux / stress of the element in the
+    component order of ``Reconstruction.flux`` (shear not doubled); ``e[k]``, k < t, its gradient / strain in the order of
+    ``Reconstruction.strain`` (shear doubled); ``c[k]``, k < n_comp, its coefficient entry (``c[0]`` of scalar Poisson, ``c[0],
+    c[1]`` = lambda, mu, ...), so ``where(c[1] > 20, 900, 60)`` tells fibre from matrix whatever the form of the coefficient.
+    ``x[i]`` is the macro midpoint, ``y[i]`` the fast variable AT THE ELEMENT CENTROID, ``p[k]`` the parameters (``p=[...]``,
+    ``with_parameters``), ``f[k]`` per-cell fields of the criterion's own (``fields=``), a strength per macro cell, say.
+
+    No opcode is added: the state is read like a field, through ``X k`` on a wider row -- ``e[k]`` is ``X 3 + n_fields + k``,
+    ``s[k]`` ``X 3 + n_fields + t + k`` and ``c[k]`` ``X 3 + n_fields + 2 t + k``.  t and n_comp are the plan's, so the program is
+    written, and the indices are checked, when the criterion meets one: ``program(t, n_comp)``.  The limits of a program hold (128
+    instructions, 32 constants with the parameters first, depth 16), and it has one component.
+
+    ``threshold``: the value from which an element counts into ``CriterionResult.exceed_volume`` (default 1: an index)."""
+
+    def __init__(self, text, p=None, parameter_names=None, fields=None, threshold=1.0):
+        values = _parameter_values(p, None) if p is not None else np.zeros(0)
+        self.n_params = int(values.size)
+        if parameter_names is None:
+            parameter_names = tuple(f"p{k}" for k in range(self.n_params))
+        self.parameter_names = tuple(str(s) for s in parameter_names)
+        if len(self.parameter_names) != self.n_params:
+            raise ValueError(f"criterion: {len(self.parameter_names)} parameter_names for {self.n_params} parameters")
+        self.n_fields, self.field_names = _field_names(fields)
+        self.threshold = float(threshold)
+        if math.isnan(self.threshold):
+            raise ValueError("criterion: the threshold is NaN")
+        self.text = str(text)
+        tree = _parse(text, _Context(self.n_params if p is not None else None, self.n_fields if fields is not None else None, state=True))
+        ops, consts = [], [float(v) for v in values]
+        _emit(tree, ops, consts, self.n_params)
+        ops.append((OP_STORE, 0))
+        if len(ops) > MAX_OPS:
+            raise ValueError(f"criterion: too long: {len(ops)} instructions, at most {MAX_OPS}")
+        if len(consts) > MAX_CONSTS:
+            raise ValueError(f"criterion: too many constants: {len(consts)} (the parameters among them), at most {MAX_CONSTS}")
+        self.depth = max(stack_depths(ops))
+        if self.depth > MAX_STACK:
+            raise ValueError(f"criterion: too deep: stack depth {self.depth}, at most {MAX_STACK}")
+        self._ops = ops  # the operand of a state read is still (name, k)
+        self._consts = np.array(consts, dtype=np.float64)
+        self.n_y = 1 + max([int(k) for op, k in ops if op == OP_Y], default=-1)  # fast-variable components the criterion reads
+        self.state_indices = {name: 1 + max([k[1] for op, k in ops if op == OP_X and isinstance(k, tuple) and k[0] == name], default=-1)
+                              for name in "esc"}  # entries of e, s and c it reads
+
+    @property
+    def p(self) -> np.ndarray:
+        """The values of the parameters (a copy)."""
+        return self._consts[:self.n_params].copy()
+
+    def with_parameters(self, p) -> "Criterion":
+        """The same criterion at other parameter values: only ``consts[:n_params]`` replaced -- nothing is parsed."""
+        values = _parameter_values(p, self.n_params)
+        other = copy.copy(self)
+        other._consts = self._consts.copy()
+        other._consts[:self.n_params] = values
+        return other
+
+    def program(self, t: int, n_comp: int) -> tuple[np.ndarray, np.ndarray]:
+        """(ops[n_ops, 2] uint8, consts[n_consts] float64) on a plan of tensor size ``t`` whose coefficient has ``n_comp`` entries per
+        element: the one component's code and ``STORE 0``.  ``ValueError`` for an index of ``s`` / ``e`` at or above t, of ``c`` at or
+        above n_comp."""
+        base = {"e": 3 + self.n_fields, "s": 3 + self.n_fields + t, "c": 3 + self.n_fields + 2 * t}
+        for name, bound, what in (("e", t, "t"), ("s", t, "t"), ("c", n_comp, "n_comp")):
+            if self.state_indices[name] > bound:
+                raise ValueError(f"criterion: {name}[{self.state_indices[name] - 1}] is out of range: the plan has {what} = {bound} "
+                                 f"(t = {t}, n_comp = {n_comp})")
+        ops = [(op, base[k[0]] + k[1] if isinstance(k, tuple) else k) for op, k in self._ops]
+        return np.array(ops, dtype=np.uint8).reshape(-1, 2), self._consts.copy()
+
+    def host_values(self, e, s, c, x, y=None, fields=None) -> np.ndarray:
+        """values[N, n_el]: the criterion of every element from e[N, n_el, t] and s[N, n_el, t] (``CriterionResult.strain`` / ``flux``),
+        c[N, n_el(, n_comp)] (the coefficient stream), x[N, 3] (the macro midpoints), y[n_el, d] (the element centroids; may be None
+        when the criterion reads no ``y``) and fields[N, n_fields] -- ``_run``, value pass, on the rows the device reads: the
+        midpoint, the fields, then e, s and c of the element.  Bit for bit the device's values wherever the program holds exactly
+        rounded operations only."""
+        e, s = np.asarray(e, dtype=np.float64), np.asarray(s, dtype=np.float64)
+        N, n_el, t = e.shape
+        c = np.asarray(c, dtype=np.float64).reshape(N, n_el, -1)
+        ops, consts = self.program(t, c.shape[2])
+        x = np.asarray(x, dtype=np.float64).reshape(N, -1)
+        x = np.concatenate([x, np.zeros((N, 3 - x.shape[1]))], axis=1) if x.shape[1] < 3 else x[:, :3]
+        if self.n_fields:
+            if fields is None:
+                raise ValueError(f"the criterion reads the fields {', '.join(self.field_names)}: pass fields[N, {self.n_fields}]")
+            fields = np.asarray(fields, dtype=np.float64).reshape(N, self.n_fields)
+        if self.n_y and (y is None or np.shape(y)[-1] < self.n_y):
+            raise ValueError(f"the criterion reads y[{self.n_y - 1}]: pass the element centroids y[n_el, d]")
+        rows = [x[:, k, None] for k in range(3)] + [fields[:, k, None] for k in range(self.n_fields)]
+        rows += [a[:, :, k] for a in (e, s, c) for k in range(a.shape[2])]
+        yr = [] if y is None else [np.asarray(y, dtype=np.float64)[None, :, k] for k in range(np.shape(y)[-1])]
+        with np.errstate(all="ignore"):
+            out, _ = _run(ops.tolist(), consts, 1, rows, yr)
+        return np.array(np.broadcast_to(out[0], (N, n_el)))
+
+    # -- ready-made texts ------------------------------------------------------------------------------------------------------------
+    @classmethod
+    def flux_norm(cls, kind: str, dim: int, **kw) -> "Criterion":
+        """The norm ``reconstruct`` reports as ``max_flux``: |q| for the Poisson kinds, the Frobenius norm of the stress tensor (shear
+        entries counted twice) for the elasticity kinds -- ``sqrt(sum_k w_k s[k]**2)``."""
+        elastic = kind.startswith("elasticity")
+        t = dim * (dim + 1) // 2 if elastic else dim
+        terms = [("2*" if elastic and k >= dim else "") + f"s[{k}]**2" for k in range(t)]
+        return cls("sqrt(" + " + ".join(terms) + ")", **kw)
+
+    @classmethod
+    def von_mises(cls, dim: int, strength="1", plane: str = "strain", **kw) -> "Criterion":
+        """The von Mises stress over ``strength`` (any text of the grammar: it may read ``c``, ``y``, ``x``, ``p`` and ``f``) for the
+        ``Lame`` kinds.  2D, ``plane="strain"``: the out-of-plane stress is ``c[0]*(e[0] + e[1])``; ``plane="stress"``: it is 0."""
+        if plane not in ("strain", "stress"):
+            raise ValueError(f"plane must be 'strain' or 'stress'; got {plane!r}")
+        if dim == 3:
+            a, b, c3, shear = "s[0]", "s[1]", "s[2]", "s[3]**2 + s[4]**2 + s[5]**2"
+        elif dim == 2:
+            a, b, c3, shear = "s[0]", "s[1]", "(c[0]*(e[0] + e[1]))" if plane == "strain" else "0.0", "s[2]**2"
+        else:
+            raise ValueError(f"dim must be 2 or 3; got {dim}")
+        return cls(f"sqrt(0.5*(({a} - {b})**2 + ({b} - {c3})**2 + ({c3} - {a})**2) + 3*({shear})) / ({strength})", **kw)
+
+    @classmethod
+    def max_principal(cls, strength="1", **kw) -> "Criterion":
+        """The largest principal stress of 2D elasticity over ``strength``."""
+        return cls(f"(0.5*(s[0] + s[1]) + sqrt((0.5*(s[0] - s[1]))**2 + s[2]**2)) / ({strength})", **kw)
 
 
 def _field_names(fields) -> tuple[int, tuple]:

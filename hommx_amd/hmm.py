@@ -29,8 +29,9 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import fem
-from .batch import CoefStream, LoadResponse, MicroCellPlan, Reconstruction, SecondSensitivities, Sensitivities, StratSensitivities, region_labels
-from .expr import Expression
+from .batch import (CoefStream, CriterionResult, LoadResponse, MicroCellPlan, Reconstruction, SecondSensitivities, Sensitivities,
+                    StratSensitivities, region_labels)
+from .expr import Criterion, Expression
 from .mesh import Mesh, micro_cells_per_side
 
 _VOIGT = {2: [(0, 0), (1, 1), (0, 1)], 3: [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]}
@@ -1115,6 +1116,49 @@ class BaseHMM(ABC):
             return 8 * (n_el * t + (t + 1 + t + 2 + t * t) + (2 * n_el * t if fields else 0) + n_dof) + 4
 
         return _join(self._load_blocks(cells, chunk_cells, bytes_per_cell, response=True, fields=fields, return_correctors=correctors), cells=cells)
+
+    def criterion(self, crit: Criterion, u=None, cells=None, field_values=None, values: bool = False, fields: bool = False, load=None,
+                  chunk_cells: int | None = None) -> CriterionResult:
+        """A failure criterion ``crit`` (a ``Criterion``: von Mises against a phase-dependent yield stress, a largest principal stress, a
+        critical flux, ...) on the micro state ``reconstruct`` forms in the sampling boxes of ``cells`` (default: every macro cell) from
+        the macro solution ``u`` (default: the last ``solve()`` result), evaluated ON THE DEVICE where the stress is formed
+        (hommx_criterion_source) -> ``CriterionResult`` with ``cells``: per cell the largest value, the element reaching it,
+        the mean and the volume fraction at or above ``crit.threshold`` -- four numbers per macro cell cross the boundary.  ``values``:
+        the criterion of every element [N, n_el] as well; ``fields``: the strain and flux it saw [N, n_el, t].
+
+        ``load``: None includes the polarisation or eigenstrain when one is set (the physical stress contains it: the criterion sees
+        ``reconstruct(...).flux + load_response(...).flux[:, 0]``, sampled as ``load_response`` samples it, on the device where the plan
+        takes load sources); False is the mechanical part alone; True insists on the load and raises ``RuntimeError`` without one.
+        ``field_values``: the values of the criterion's own fields ``f[k]`` per macro cell, in the shapes ``set_fields`` takes;
+        ``RuntimeError`` when the criterion reads fields and they are missing.  In the criterion ``x`` is the macro cell midpoint and
+        ``y`` the centroid of the micro element.  The cells run in chunks of ``chunk_cells`` (default: about 256 MB of what crosses the
+        boundary).  Under a process group this runs on the calling rank alone, for the cells it is given: there is no collective."""
+        if load is True and self._polarisation is None:
+            raise RuntimeError("criterion(load=True) needs a polarisation: call set_polarisation() or set_eigenstrain() first")
+        if crit.n_fields and field_values is None:
+            raise RuntimeError(f"the criterion reads the fields {', '.join(crit.field_names)}: pass field_values, their values per macro cell")
+        x = self._macro_dofs(self._or_last_solve(u, "criterion"))
+        cells = self._cells_argument(cells, "criterion", local=False)
+        xi = self._macro_strains(cells, x)
+        rows = self._msh.cell_midpoints()[cells]
+        if crit.n_fields:
+            rows = np.concatenate([rows, self._field_values(crit, field_values)[cells]], axis=1)
+        points = np.ascontiguousarray(self._cell_mesh.cell_midpoints()[:, : self._tdim])  # where _region_labels evaluates a callable
+        with_load = self._polarisation is not None and load is not False
+
+        def bytes_per_cell():
+            n_el, t = self._cell_mesh.num_cells, self._tensor_size()
+            out = 8 * (4 + t * t + (n_el if values else 0) + (2 * n_el * t if fields else 0)) + 4
+            if with_load and not isinstance(self._polarisation, Expression):
+                out += 8 * n_el * t  # a sampled load
+            return out if self._sampled_on_device() else out + n_el * (1 if self._kind == "poisson" else 2) * 8
+
+        def call(plan, coef, M, P, sub, b):
+            kw = {} if P is None else {"P": P[0], "per_cell": P[1], "eigenstrain": P[2]}
+            return plan.criterion(coef, xi[b:b + len(sub)], crit, M, rows=rows[b:b + len(sub)], points=points, values=values, fields=fields, **kw)
+
+        parts = self._chunks(cells, chunk_cells, bytes_per_cell, call, (lambda sub, kind: self._polarisation_loads(sub, kind)) if with_load else None)
+        return _join(parts, cells=cells)
 
     def _parameter_directions(self) -> tuple[tuple, np.ndarray]:
         """(names, directions[n_dirs, n_el(, n_comp)]) of the parameters of a ``TwoPhase`` or affine ``Separable`` coefficient: the element

@@ -652,6 +652,67 @@ int hommx_second_sensitivity_source_device(hommx_plan* plan, int64_t n_cells, co
                                            const hommx_sens2_args* args, void* stream);
 
 /*
+ * Failure criteria on the reconstructed micro state.  With e_K the gradient / strain and q_K the flux / stress
+ * of micro element K as hommx_reconstruct_batch forms them from xi and the canonical correctors -- and, with a load, the total state
+ * under the macro strain plus the load, e_K + eps(chi_P)_K and q_K + P_K + material(coef_K) eps(chi_P)_K of hommx_loads_source --, one
+ * scalar program is interpreted once per element,
+ *   v_K = program(row of the element),  row = [midpoint (3) | fields (n_fields) | e_K (t) | q_K (t) | coef_K (n_comp)],
+ * and only its statistics come back.  The program is a hommx_coef_program with n_comp == 1 (one STORE 0) in the opcodes of
+ * HOMMX_COEF_PROGRAM, none added: the state is read like a field, `X k` with k = 3 + n_fields + j for e[j], 3 + n_fields + t + j for
+ * q[j] and 3 + n_fields + 2 t + j for coef[j]; `Y i` is coordinate i of the element's centroid, points[K][i].  Every operation is one
+ * separately rounded IEEE operation in program order (value pass only; hommx_amd.expr.Criterion.host_values interprets the same program
+ * with NumPy), and e_K, q_K are formed without contraction, so v_K does not depend on which outputs are asked for.
+ *
+ *   program     n_comp == 1; host memory in the device entry too
+ *   n_fields    0 .. HOMMX_PROGRAM_MAX_FIELDS fields of the criterion's own per macro cell; rows [n_cells][3 + n_fields]
+ *   points      [n_el][dim], shared by all cells; may be NULL if the program has no Y
+ *   xi          [n_cells][t], as hommx_reconstruct_batch
+ *   threshold   the value from which an element counts into crit[3]; not NaN
+ *   has_load    0: the mechanical state alone (per_cell, P and P_source are not read).  Else ONE load (n_loads == 1 of hommx_load_args)
+ *               with the codes and the meaning of hommx_load_args.per_cell, HOMMX_LOADS_EIGENSTRAIN included: HOMMX_LOADS_PER_CELL with
+ *               P[n_cells][n_el][t], or HOMMX_LOADS_PROGRAM with P_source.  HOMMX_LOADS_SHARED is refused (points is the call's one
+ *               shared array: a caller repeats a shared load per cell).  The chunk is then that of a response of hommx_loads_source:
+ *               the load solve on the route hommx_plan_load_kernel_name names, a second corrector block per cell
+ *   crit        [n_cells][4] = [max_K v_K | the smallest K reaching it | sum |K| v_K | sum |K| [v_K >= threshold]], required.  A NaN
+ *               v_K never wins the maximum (-inf and -1 when every element is NaN) and makes the sum NaN
+ *   values      [n_cells][n_el] = v_K, or NULL
+ *   strain, flux [n_cells][n_el][t] = e_K, q_K, the totals the program saw; both or neither
+ *   A_eff, info of the canonical pass, as hommx_solve_batch, or NULL
+ * src, M: as hommx_reconstruct_source.  HOMMX_EINVAL, before the plan's device is made current: a null plan, source, argument struct,
+ * program, rows, xi or crit; one of strain / flux without the other; n_fields out of range; everything a program is refused for
+ * (hommx_coef_program) against n_comp == 1 and a row of 3 + n_fields + 2 t + n_comp entries, on every kind; a Y in the program with
+ * points NULL; a NaN threshold; with has_load the refusals of hommx_loads_source for its code and P / P_source, and
+ * HOMMX_LOADS_SHARED.  HOMMX_EINVAL as well, before any work: has_load on a plan of the frontal mesh route created without
+ * HOMMX_MESH_FLAG_LOADS.  The correctors of one chunk (HOMMX_RECON_MEM_MB) live in plan-owned scratch.  Per workgroup the kernel holds
+ * the field in LDS beside 4 KiB per stack level below the top; a cell for which that exceeds the limit of the reconstruction keeps the
+ * field in a scratch slot, which the chunk rule counts.  The statistics of a cell do not depend on its batch position, the chunking or
+ * which outputs are requested (fixed-order reductions).  A cell whose elimination flags a pivot keeps its info; its outputs may hold
+ * anything, no other cell's change.
+ */
+typedef struct hommx_criterion_args {
+  const hommx_coef_program* program;
+  int32_t n_fields;
+  const double* rows;
+  const double* points;
+  const double* xi;
+  double threshold;
+  int32_t has_load, per_cell;
+  const double* P;
+  const hommx_coef_source* P_source; /* read only when has_load and (per_cell & 3) == HOMMX_LOADS_PROGRAM */
+  double* crit;
+  double* values;
+  double* strain;
+  double* flux;
+  double* A_eff;
+  int32_t* info;
+} hommx_criterion_args;
+#define HOMMX_CRIT_NSTATS 4
+int hommx_criterion_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_criterion_args* args);
+/* Same with DEVICE pointers (in *src, *args and *args->P_source as well; the structs and the programs are host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
+int hommx_criterion_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                  const hommx_criterion_args* args, void* stream);
+
+/*
  * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
  * periodic: the caller folds the mesh vertices into n_nodes independent (periodic) nodes -- cell_problem.py:38-300's slave -> master
  * map -- and passes, per element, the periodic node of every vertex and the UNFOLDED vertex coordinates (gradients and volumes).
