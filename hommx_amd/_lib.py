@@ -35,6 +35,7 @@ DIRS_PARAMETERS_CURVATURE = 3  # HOMMX_DIRS_PARAMETERS_CURVATURE: per_cell of Se
 LOADS_SHARED, LOADS_PER_CELL, LOADS_PROGRAM = 0, 1, 2  # HOMMX_LOADS_*: per_cell of LoadArgs, where the load comes from
 LOADS_EIGENSTRAIN = 4  # HOMMX_LOADS_EIGENSTRAIN: a flag or-ed to them, what arrives is an eigenstrain
 CRIT_NSTATS = 4  # HOMMX_CRIT_NSTATS: max, argmax element, sum |K| v, sum |K| [v >= threshold]
+SECANT_NSTATE = 3  # HOMMX_SECANT_NSTATE: rounds, change, status
 
 
 class PlanDesc(C.Structure):
@@ -187,6 +188,31 @@ class CriterionArgs(C.Structure):
     ]
 
 
+class SecantArgs(C.Structure):
+    """hommx_secant_args: the law of hommx_secant_source[_device], the iteration's limits, an optional start stream and where the
+    outputs of every cell's stopping round go."""
+
+    _fields_ = [
+        ("program", C.POINTER(CoefProgram)),
+        ("n_fields", C.c_int32),
+        ("rows", C.c_void_p),
+        ("points", C.c_void_p),
+        ("xi", C.c_void_p),
+        ("max_iter", C.c_int32),
+        ("tol", C.c_double),
+        ("relax", C.c_double),
+        ("coef_start", C.c_void_p),
+        ("state", C.c_void_p),
+        ("A_eff", C.c_void_p),
+        ("mean_flux", C.c_void_p),
+        ("coef_out", C.c_void_p),
+        ("strain", C.c_void_p),
+        ("flux", C.c_void_p),
+        ("law_values", C.c_void_p),
+        ("info", C.c_void_p),
+    ]
+
+
 def _prototypes() -> dict:
     """name -> (restype, argtypes) of every symbol include/hommx_hip.h declares: ``load()`` declares them from this table, and
     the tests check that the header and the library export exactly these names."""
@@ -239,6 +265,8 @@ def _prototypes() -> dict:
         "hommx_loads_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(LoadArgs), vp]),
         "hommx_criterion_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(CriterionArgs)]),
         "hommx_criterion_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(CriterionArgs), vp]),
+        "hommx_secant_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantArgs)]),
+        "hommx_secant_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantArgs), vp]),
         "hommx_solve_batch_two_phase": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_two_phase_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_separable": (c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),

@@ -224,6 +224,29 @@ class CriterionResult:
     cells: np.ndarray | None = None
 
 
+@dataclass
+class SecantResult:
+    """The secant iteration of a strain-dependent coefficient on macro cells (include/hommx_hip.h, hommx_secant_source),
+    every member that of the cell's STOPPING round: ``A_eff[N, t, t]`` the secant tensor, ``mean_flux[N, t]`` = sum |K| q_K (= A_eff xi
+    up to rounding), ``rounds[N]`` (int), ``change[N]`` = max |w - c| / max |w| of that round, ``status[N]`` (int: 0 converged,
+    1 ``max_iter`` reached, 2 the law gave a value that is not finite, 3 the elimination flagged a pivot -- ``info`` then), ``info[N]``.
+    With ``return_coef`` ``coef[N, n_el(, n_comp)]``, the element stream ``A_eff`` belongs to (pass it to ``reconstruct`` /
+    ``criterion`` for the nonlinear state); with ``fields`` ``strain`` and ``flux`` ``[N, n_el, t]``; with ``values``
+    ``values[N, n_el, n_comp]``, what the law gave.  ``cells``: the macro cells (solver classes).  What was not asked for is None."""
+
+    A_eff: np.ndarray
+    mean_flux: np.ndarray
+    rounds: np.ndarray
+    change: np.ndarray
+    status: np.ndarray
+    info: np.ndarray
+    coef: np.ndarray | None = None
+    strain: np.ndarray | None = None
+    flux: np.ndarray | None = None
+    values: np.ndarray | None = None
+    cells: np.ndarray | None = None
+
+
 REGION_FIELDS = ("region_volume", "region_mean_strain", "region_mean_flux", "region_energy", "region_max_flux", "region_argmax_element")
 
 
@@ -818,6 +841,77 @@ class MicroCellPlan:
         A, info = self._source_call("hommx_criterion_source", nc, M, stream, args)
         return CriterionResult(out[:, 0].copy(), out[:, 1].astype(np.int64), out[:, 2].copy(), out[:, 3].copy(), A, info, vals, strain, flux)
 
+    def _law_program(self, law) -> Program:
+        """The program of a ``hommx_amd.expr.SecantLaw`` on this plan (its component count and index checks against t and n_comp run here)."""
+        ops, consts = law.program(self.t, self.n_comp)
+        if law.n_y > self.dim:
+            raise ValueError(f"the law reads y[{law.n_y - 1}]; the micro mesh has {self.dim} dimensions")
+        return Program(np.ascontiguousarray(ops), np.ascontiguousarray(consts), self.n_comp, int(law.n_params), int(law.n_fields))
+
+    @staticmethod
+    def _secant_limits(max_iter, tol, relax) -> tuple[int, float, float]:
+        max_iter, tol, relax = int(max_iter), float(tol), float(relax)
+        if max_iter < 1:
+            raise ValueError(f"max_iter must be at least 1; got {max_iter}")
+        if not tol >= 0.0:
+            raise ValueError(f"tol must be a number >= 0; got {tol}")
+        if not 0.0 < relax <= 1.0:
+            raise ValueError(f"relax must lie in (0, 1]; got {relax}")
+        return max_iter, tol, relax
+
+    def secant(self, coef, xi: np.ndarray, law, M: np.ndarray | None = None, rows=None, points=None, max_iter: int = 50, tol: float = 1e-10,
+               relax: float = 1.0, coef_start=None, fields: bool = False, values: bool = False, return_coef: bool = False) -> SecantResult:
+        """The secant iteration of a strain-dependent coefficient (hommx_secant_source): ``coef`` an array or a ``CoefStream``, the BASE
+        coefficient ``c`` of the law; xi and M as ``reconstruct`` takes them; ``law`` a ``hommx_amd.expr.SecantLaw`` with the plan's
+        ``n_comp`` components -> ``SecantResult``.  Per cell and round: the correctors of the current stream on the plan's route, the
+        strain and the secant flux of every element, the law on them, the relaxed candidate ``(1 - relax) c + relax v``; the cell stops
+        when the largest change relative to the largest entry is at most ``tol``, after ``max_iter`` rounds, on a value that is not
+        finite or on a flagged pivot, and what comes back is the state of that round.  The element fields never leave the device
+        unless ``fields`` / ``values`` / ``return_coef`` ask for them.  ``rows[N_c, 3 + law.n_fields]``: the macro midpoint and the
+        law's own fields of every cell (required when the law reads ``f``; without them ``x`` is 0); ``points[n_el, dim]``: the
+        element centroids, required when it reads ``y``; ``coef_start[N_c, n_el(, n_comp)]``: the stream the iteration starts from
+        (default: the base stream), e.g. ``SecantResult.coef`` of a neighbouring macro strain.  The batch runs in the chunks of
+        ``reconstruct``; a load beside a law is out of scope."""
+        stream = self._as_stream(coef)
+        nc = self._check_stream(stream)
+        xi = np.ascontiguousarray(xi, dtype=np.float64)
+        if xi.shape != (nc, self.t):
+            raise ValueError(f"xi has shape {xi.shape}; expected ({nc}, {self.t})")
+        max_iter, tol, relax = self._secant_limits(max_iter, tol, relax)
+        prog = self._law_program(law)
+        pstruct = prog.struct()
+        if rows is None:
+            if law.n_fields:
+                raise ValueError(f"the law reads the fields {', '.join(law.field_names)}: pass rows[N_c, 3 + {law.n_fields}]")
+            rows = np.zeros((nc, 3))
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        if rows.shape != (nc, 3 + law.n_fields):
+            raise ValueError(f"rows has shape {rows.shape}; expected ({nc}, 3 + {law.n_fields}): the midpoint, then the law's fields")
+        if points is not None:
+            points = np.ascontiguousarray(points, dtype=np.float64)
+            if points.shape != (self.n_el, self.dim):
+                raise ValueError(f"points has shape {points.shape}; expected ({self.n_el}, {self.dim}): the element centroids")
+        elif law.n_y:
+            raise ValueError(f"the law reads y[{law.n_y - 1}]: pass points[n_el, dim], the element centroids")
+        el = self._el
+        if coef_start is not None:
+            coef_start = np.ascontiguousarray(coef_start, dtype=np.float64)
+            if coef_start.shape != (nc,) + el:
+                raise ValueError(f"coef_start has shape {coef_start.shape}; expected {(nc,) + el}")
+        state = np.empty((nc, _lib.SECANT_NSTATE), dtype=np.float64)
+        mean_flux = np.empty((nc, self.t), dtype=np.float64)
+        out_coef = np.empty((nc,) + el, dtype=np.float64) if return_coef else None
+        strain = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
+        flux = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
+        vals = np.empty((nc, self.n_el, self.n_comp), dtype=np.float64) if values else None
+        addr = lambda a: None if a is None else a.ctypes.data
+        args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows.ctypes.data, addr(points), xi.ctypes.data, max_iter, tol, relax,
+                               addr(coef_start), state.ctypes.data, None, mean_flux.ctypes.data, addr(out_coef), addr(strain), addr(flux),
+                               addr(vals), None)
+        A, info = self._source_call("hommx_secant_source", nc, M, stream, args)
+        return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
+                            strain, flux, vals)
+
     def solve_two_phase(self, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None = None,
                         return_info: bool = False):
         """Two-phase media sampled on the device: mask[n_el] (bool / uint8, phase of every micro element) and
@@ -1002,6 +1096,26 @@ class MicroCellPlan:
                                   flux_ptr or None, A_ptr or None, info_ptr or None)
         _lib.check(self._lib.hommx_criterion_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
                    "hommx_criterion_source_device")
+
+    def secant_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, xi_ptr: int, law, rows_ptr: int, state_ptr: int,
+                      A_ptr: int, points_ptr: int | None = None, max_iter: int = 50, tol: float = 1e-10, relax: float = 1.0,
+                      coef_start_ptr: int | None = None, mean_flux_ptr: int | None = None, coef_ptr: int | None = None,
+                      strain_ptr: int | None = None, flux_ptr: int | None = None, values_ptr: int | None = None, info_ptr: int | None = None,
+                      stream: int | None = None):
+        """Device-pointer form of ``secant`` (hommx_secant_source_device), asynchronous on ``stream``: ``source`` =
+        ``CoefStream.coef_source(upload)`` with device addresses; ``law`` the ``SecantLaw`` (its program is host memory);
+        rows[n_cells, 3 + law.n_fields], points[n_el, dim] (None: the law reads no ``y``) -> state[n_cells, 3] = [rounds | change |
+        status] (doubles), A_eff[n_cells, t, t], mean_flux[n_cells, t], coef[n_cells, n_el, n_comp] (the stream A_eff belongs to),
+        strain / flux[n_cells, n_el, t], values[n_cells, n_el, n_comp].  Exactly ``max_iter`` rounds per chunk are queued and nothing
+        is read back; the bits are those of ``secant``."""
+        max_iter, tol, relax = self._secant_limits(max_iter, tol, relax)
+        prog = self._law_program(law)
+        pstruct = prog.struct()
+        args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows_ptr, points_ptr or None, xi_ptr, max_iter, tol, relax,
+                               coef_start_ptr or None, state_ptr, A_ptr, mean_flux_ptr or None, coef_ptr or None, strain_ptr or None,
+                               flux_ptr or None, values_ptr or None, info_ptr or None)
+        _lib.check(self._lib.hommx_secant_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
+                   "hommx_secant_source_device")
 
     def solve_separable_device(self, n_cells: int, family: str, n_q: int, table_ptr: int, weights_ptr: int | None, params_ptr: int,
                                M_ptr: int | None, out_ptr: int, info_ptr: int | None, stream: int | None = None):

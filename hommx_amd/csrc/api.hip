@@ -117,9 +117,11 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 // B_POLAR: the loads of one chunk of hommx_loads_source that the device forms: the expansion of a program load, [nc][n_el][t]
 //            (derived_call; an eigenstrain becomes the eigenstress in place), or the eigenstresses of an eigenstrain array that is not
 //            the plan's to overwrite, [nc][n_loads][n_el][t] (loads_run; crit_run: the one load of a criterion)
+// B_SECANT: the current and the candidate element stream of one chunk of hommx_secant_source, [chunk][n_el][n_comp] each, and the info
+//            of its eliminations where the caller takes none, [chunk] (secant_run)
 enum {
   B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, B_SENS2, B_TANGENT, B_CURVATURE,
-  B_POLAR, N_BUF
+  B_POLAR, B_SECANT, N_BUF
 };
 
 }  // namespace
@@ -292,8 +294,9 @@ hommx_coef_source source_of_form(const hommx_coef_source& s) {
 // The whole program of a HOMMX_COEF_PROGRAM source against the plan's descriptor, on the host: the kernel then interprets it unchecked.
 // load_comp: 0 for the coefficient; the tensor size t of the plan for the program of a load (HOMMX_LOADS_PROGRAM), which has t
 // components on every kind.  state: 0, or the 2 t + n_comp state entries behind the fields in the row of a criterion
-// (hommx_criterion_args.program): one component on every kind, and of `s` only program and n_fields are read
-int program_check(const hommx_plan* p, const hommx_coef_source* s, int load_comp = 0, int state = 0) {
+// (hommx_criterion_args.program): one component on every kind, and of `s` only program and n_fields are read.  state_comp: the
+// components of a program on that row -- 1 for a criterion, the plan's n_comp for a law (hommx_secant_args.program)
+int program_check(const hommx_plan* p, const hommx_coef_source* s, int load_comp = 0, int state = 0, int state_comp = 1) {
   if (!load_comp && !state && p->desc.kind == HOMMX_KIND_ELASTICITY_VOIGT)
     return fail(HOMMX_EINVAL, "expression coefficients are not supported for the 21-component Voigt kind");
   const hommx_coef_program* g = s->program;
@@ -309,8 +312,8 @@ int program_check(const hommx_plan* p, const hommx_coef_source* s, int load_comp
   if (s->n_fields < 0 || s->n_fields > hommx::PROGRAM_MAX_FIELDS)
     return fail(HOMMX_EINVAL, "program source: n_fields must be 0 .. %d, got %d", hommx::PROGRAM_MAX_FIELDS, s->n_fields);
   const int n_row = hommx::program_row_doubles(s->n_fields) + state;
-  const int n_comp = state ? 1 : load_comp ? load_comp : hommx::kind_sizes(p->desc.dim, p->desc.kind).n_comp;
-  if (g->n_comp != n_comp && state) return fail(HOMMX_EINVAL, "program: n_comp is %d, a criterion has one component", g->n_comp);
+  const int n_comp = state ? state_comp : load_comp ? load_comp : hommx::kind_sizes(p->desc.dim, p->desc.kind).n_comp;
+  if (g->n_comp != n_comp && state && state_comp == 1) return fail(HOMMX_EINVAL, "program: n_comp is %d, a criterion has one component", g->n_comp);
   if (g->n_comp != n_comp && load_comp)
     return fail(HOMMX_EINVAL, "program: n_comp is %d, a load of this plan has t = %d components", g->n_comp, n_comp);
   if (g->n_comp != n_comp) return fail(HOMMX_EINVAL, "program: n_comp is %d, the plan's coefficient has %d components", g->n_comp, n_comp);
@@ -320,7 +323,7 @@ int program_check(const hommx_plan* p, const hommx_coef_source* s, int load_comp
     if (!s->table || !s->weights || !s->params) return fail(HOMMX_EINVAL, "null table / weights / params");
   }
   int depth = 0;
-  bool stored[hommx::PROGRAM_MAX_COMP] = {};
+  bool stored[std::max(hommx::PROGRAM_MAX_COMP, 21)] = {};  // a law stores every entry of the coefficient, 21 on the Voigt kind
   for (int pc = 0; pc < g->n_ops; ++pc) {
     const int op = g->ops[2 * pc], k = g->ops[2 * pc + 1];
     if (op >= hommx::OP_COUNT) return fail(HOMMX_EINVAL, "program: unknown opcode %d at instruction %d", op, pc);
@@ -1659,6 +1662,102 @@ int crit_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const 
                       nullptr, false, program ? &load : nullptr);
 }
 
+// -- strain-dependent coefficients (hommx_secant_source[_device]) --------------------------------------------------------------------------
+// one chunk on the device: the current stream starts as coef_start or the base stream; per round the correctors of the current stream
+// into the plan's scratch, then k_secant_update.  The device entry queues max_iter rounds and reads nothing; the host entry reads the
+// chunk's state after each round and stops when no cell runs -- a stopped cell is frozen, so the bits are the same
+int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_secant_args>& v, bool device, hipStream_t st) {
+  const hommx_secant_args& a = v.a;
+  const int t = p->ks.t, depth = program_depth(*a.program);
+  const bool slot = !crit_in_lds(p, depth);
+  const size_t stream = sizeof(double) * p->n_el * p->ks.n_comp;
+  const size_t bytes[3] = {stream * chunk, stream * chunk, a.info ? 0 : sizeof(int32_t) * chunk};
+  char* at[3];
+  if (int rc = carve(p->buf[B_SECANT], bytes, at)) return rc;
+  double *cur = reinterpret_cast<double*>(at[0]), *cand = reinterpret_cast<double*>(at[1]);
+  int32_t* info = a.info ? a.info : reinterpret_cast<int32_t*>(at[2]);
+  HIP_TRY(hipMemcpyAsync(cur, a.coef_start ? a.coef_start : v.coef, stream * nc, hipMemcpyDeviceToDevice, st));
+  hommx::SecantArgs k;
+  set_geometry(p, k);
+  k.base = v.coef;
+  k.cur = cur;
+  k.cand = cand;
+  k.M = v.M;
+  k.xi = a.xi;
+  k.prog = program_args(*a.program);
+  k.n_fields = a.n_fields;
+  k.rows = a.rows;
+  k.points = a.points;
+  k.max_iter = a.max_iter;
+  k.tol = a.tol;
+  k.relax = a.relax;
+  k.info = info;
+  k.state = a.state;
+  k.mean_flux = a.mean_flux;
+  k.law_values = a.law_values;
+  k.strain = a.strain;
+  k.flux = a.flux;
+  std::vector<double> seen;
+  for (int j = 0; j < a.max_iter; ++j) {
+    double *d_A_eff = a.A_eff, *corr = nullptr;
+    if (int rc = chunk_correctors(p, nc, chunk, cur, v.M, &d_A_eff, info, slot ? 1 : 0, st, &corr)) return rc;
+    k.corr = corr;
+    k.slot = slot ? corr + chunk * t * k.ndof : nullptr;
+    k.round = j;
+    HIP_TRY(hommx::launch_secant(k, depth, nc, st));
+    if (device) continue;
+    seen.resize(HOMMX_SECANT_NSTATE * nc);
+    HIP_TRY(hipMemcpy(seen.data(), a.state, sizeof(double) * seen.size(), hipMemcpyDeviceToHost));
+    bool running = false;
+    for (int64_t c = 0; c < nc; ++c) running |= seen[HOMMX_SECANT_NSTATE * c + 2] == -1.0;
+    if (!running) break;
+  }
+  if (a.coef_out) HIP_TRY(hipMemcpyAsync(a.coef_out, cur, stream * nc, hipMemcpyDeviceToDevice, st));
+  return HOMMX_OK;
+}
+
+// the argument checks of both entry points, then a route that forms correctors
+int secant_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_args* a, bool device) {
+  auto checks = [&] {
+    const hommx::KindSizes ks = hommx::kind_sizes(p->desc.dim, p->desc.kind);
+    if (!a->program) return fail(HOMMX_EINVAL, "null program");
+    if (!a->rows || !a->xi || !a->state || !a->A_eff) return fail(HOMMX_EINVAL, "null rows / xi / state / A_eff");
+    if (!a->strain != !a->flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
+    hommx_coef_source own{};  // what program_check reads of a source
+    own.n_fields = a->n_fields;
+    own.program = a->program;
+    if (int rc = program_check(p, &own, 0, 2 * ks.t + ks.n_comp, ks.n_comp)) return rc;
+    if (!a->points)
+      for (int pc = 0; pc < a->program->n_ops; ++pc)
+        if (a->program->ops[2 * pc] == hommx::OP_Y)
+          return fail(HOMMX_EINVAL, "null points: the program reads y (instruction %d), the centroid of the element", pc);
+    if (a->max_iter < 1) return fail(HOMMX_EINVAL, "max_iter must be at least 1, got %d", a->max_iter);
+    if (!(a->tol >= 0.0)) return fail(HOMMX_EINVAL, "tol must be a number >= 0, got %g", a->tol);
+    if (!(a->relax > 0.0 && a->relax <= 1.0)) return fail(HOMMX_EINVAL, "relax must lie in (0, 1], got %g", a->relax);
+    return HOMMX_OK;
+  };
+  return source_open(p, n_cells, src, a, device, checks);
+}
+
+// The current and the candidate stream of a chunk, the info of its eliminations and the slot of a field that does not fit LDS beside the
+// stack (where the chunk rule of the reconstruction does not count one already) are scratch of the chunk
+int secant_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_secant_args& args, bool device,
+                hipStream_t st) {
+  const int64_t t = p->ks.t, field = p->n_el * t, stream = p->n_el * p->ks.n_comp;
+  Chunk<hommx_secant_args> v{};
+  hommx_secant_args& a = v.a = args;
+  const bool own_slot = !crit_in_lds(p, program_depth(*a.program)) && recon_in_lds(p);
+  const size_t scratch = sizeof(double) * (2 * stream + (own_slot ? plan_ndof(p) : 0)) + sizeof(int32_t);
+  const CellArray in[] = {{&a.rows, hommx::program_row_doubles(a.n_fields)},
+                          {&a.xi, t},
+                          {&a.coef_start, stream},
+                          {&a.points, p->n_el * p->desc.dim, SHARED}};
+  const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE}, {&a.A_eff, t * t, KEPT}, {&a.mean_flux, t},     {&a.coef_out, stream},
+                           {&a.strain, field},              {&a.flux, field},        {&a.law_values, stream}};
+  return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, recon_chunk, device, st,
+                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_secant_args>& c) { return secant_run(p, nc, chunk, c, device, st); });
+}
+
 // -- second derivatives (hommx_second_sensitivity_source[_device]) ------------------------------------------------------------------------
 // bytes per cell of a chunk beside the canonical correctors: the second corrector block and the loads of one direction
 size_t sens2_extra(const hommx_plan* p) { return sizeof(double) * p->ks.t * (plan_ndof(p) + p->n_el * p->ks.t); }
@@ -1817,6 +1916,17 @@ int hommx_criterion_source_device(hommx_plan* p, int64_t n_cells, const hommx_co
 int hommx_criterion_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_criterion_args* args) {
   if (int rc = crit_open(p, n_cells, src, args, false); rc != GO) return rc;
   return crit_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
+}
+
+int hommx_secant_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const hommx_secant_args* args,
+                               void* stream) {
+  if (int rc = secant_open(p, n_cells, src, args, true); rc != GO) return rc;
+  return secant_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream));
+}
+
+int hommx_secant_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_secant_args* args) {
+  if (int rc = secant_open(p, n_cells, src, args, false); rc != GO) return rc;
+  return secant_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
 }
 
 int hommx_second_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,

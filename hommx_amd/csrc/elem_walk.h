@@ -117,6 +117,29 @@ __device__ __forceinline__ void block_argmax(double& mx, double& arg, double (*r
     for (int w = 1; w < kWalkWaves; ++w) take(red[w][0], red[w][1]);
 }
 
+// The N largest-value reductions of a cell in the same order; EVERY thread returns with the totals in v (each reads the wave rows
+// itself), so the workgroup can branch on them without a second barrier.  A NaN never wins
+template <int N>
+__device__ __forceinline__ void block_maxima(double (&v)[N], double (*red)[N], int tid) {
+  auto take = [](double& m, double o) {
+    if (o > m) m = o;
+  };
+#pragma unroll
+  for (int q = 0; q < N; ++q)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) take(v[q], __shfl_xor(v[q], o, 64));
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) red[tid >> 6][q] = v[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    v[q] = red[0][q];
+    for (int w = 1; w < kWalkWaves; ++w) take(v[q], red[w][q]);
+  }
+}
+
 // The kernel that pick(DIM, KIND, MESH) names for the plan of `a` (integral constants; the eight pairs of dispatch_dim_kind times the
 // two geometries), and its launch on nc workgroups of kWalkThreads with `lds` bytes of dynamic LDS
 template <typename Args, typename Pick>

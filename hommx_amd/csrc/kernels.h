@@ -228,6 +228,30 @@ size_t criterion_lds_bytes(long long ndof, int depth);
 // depth: the maximal stack depth of the (validated) program
 hipError_t launch_criterion(const CritArgs& a, int depth, long long nc, hipStream_t stream);
 
+// secant.hip: one round of the secant iteration of a strain-dependent coefficient on `nc` cells (include/hommx_hip.h,
+// hommx_secant_source).  A cell whose state says it has stopped is not touched
+struct SecantArgs : ElemWalk {
+  const double* base = nullptr;      // [nc][n_el][n_comp]: what c[k] reads
+  double* cur = nullptr;             // [nc][n_el][n_comp]: the current stream, the one the correctors belong to; receives the candidate
+  double* cand = nullptr;            // [nc][n_el][n_comp]: the candidate stream w
+  const double* xi = nullptr;        // [nc][t]
+  ProgramArgs prog;                  // n_comp == the plan's; the row of k_criterion
+  int n_fields = 0;
+  const double* rows = nullptr;      // [nc][3 + n_fields]
+  const double* points = nullptr;    // [n_el][dim] element centroids, or null (no Y in the program)
+  int round = 0, max_iter = 1;       // the round j this launch is, of at most max_iter
+  double tol = 0.0, relax = 1.0;
+  const int32_t* info = nullptr;     // [nc]: of the elimination of this round
+  double* state = nullptr;           // [nc][3] = [rounds | change | status], status -1 while the cell runs
+  double* mean_flux = nullptr;       // [nc][t] or null
+  double* law_values = nullptr;      // [nc][n_el][n_comp] or null
+  double* strain = nullptr;          // [nc][n_el][t] or null (then flux is null as well)
+  double* flux = nullptr;
+  double* slot = nullptr;            // [nc][ndof] scratch for the field of cells that do not fit LDS beside the stack (null: LDS)
+};
+// dynamic LDS as k_criterion's (criterion_lds_bytes); depth: the maximal stack depth of the (validated) program
+hipError_t launch_secant(const SecantArgs& a, int depth, long long nc, hipStream_t stream);
+
 // the loads a corrector pass of the blocked family solves for instead of the canonical ones: rows l < n_loads of Brhs from P (device), the
 // rest zero.  P starts at the first cell of the call
 struct LoadOverride {

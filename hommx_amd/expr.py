@@ -39,6 +39,7 @@ MAX_OPS, MAX_CONSTS, MAX_STACK, MAX_COMP = 128, 32, 16, 6
 MAX_POWER = 8
 MAX_PARAMS = 4  # HOMMX_PROGRAM_MAX_PARAMS
 MAX_FIELDS = 4  # HOMMX_PROGRAM_MAX_FIELDS
+MAX_LAW_COMP = 21  # the components of a SecantLaw: the entries of the coefficient of an element, 21 on the 3D Voigt kind
 
 _BINARY = {ast.Add: OP_ADD, ast.Sub: OP_SUB, ast.Mult: OP_MUL, ast.Div: OP_DIV}
 _COMPARE = {ast.Lt: OP_LT, ast.LtE: OP_LE, ast.Gt: OP_GT, ast.GtE: OP_GE}
@@ -817,6 +818,129 @@ class Criterion:
     def max_principal(cls, strength="1", **kw) -> "Criterion":
         """The largest principal stress of 2D elasticity over ``strength``."""
         return cls(f"(0.5*(s[0] + s[1]) + sqrt((0.5*(s[0] - s[1]))**2 + s[2]**2)) / ({strength})", **kw)
+
+
+class SecantLaw:
+    """A strain-dependent coefficient: the entries of an element's coefficient as expressions of its own micro state, iterated on the
+    device as a secant (Kacanov) iteration (include/hommx_hip.h, hommx_secant_source; csrc/secant.hip) and, by
+    ``host_values``, evaluated with NumPy -- the same operations in the same order.
+
+    The component shapes are ``Expression``'s: ``SecantLaw(text)`` one component (scalar Poisson), ``SecantLaw([[a, b], [b, c]])`` a
+    symmetric d x d matrix in the ``poisson_matrix`` order of the ABI, ``SecantLaw(lam=..., mu=...)`` the two Lame entries, and a
+    FLAT list of ``n_comp`` texts the Voigt kind (6 entries in 2D, 21 in 3D).  The grammar is ``Criterion``'s: a law reads
+
+    * ``c[k]``: the BASE coefficient of the element -- what the solver's coefficient ``A`` gives --, so ``where(c[0] > 5, c[0], ...)``
+      tells the phases apart;
+    * ``e[k]``: the gradient / strain of the current iterate (shear doubled);
+    * ``s[k]`` = material(current coefficient) e: the secant flux / stress of the current iterate;
+    * ``x[i]``, ``y[i]`` (the element centroid), ``p[k]`` and ``f[k]`` as a ``Criterion`` does.
+
+    No opcode is added: ``program(t, n_comp)`` is on the row of a criterion, ``[midpoint 3 | fields | e (t) | s (t) | c (n_comp)]``,
+    with one ``STORE k`` per component.  The limits of a program hold for all components together (128 instructions, 32 constants
+    with the parameters first, depth 16), and the number of components must be the plan's ``n_comp``.
+
+    The iteration converges when s -> s a(s) is increasing (a monotone law); the consistent tangent is out of scope."""
+
+    def __init__(self, text=None, *, lam=None, mu=None, p=None, parameter_names=None, fields=None):
+        if (lam is None) != (mu is None) or (text is None) == (lam is None):
+            raise ValueError("SecantLaw(text), SecantLaw([[a, b], [b, c]]), SecantLaw([c0, c1, ...]) or SecantLaw(lam=..., mu=...)")
+        values = _parameter_values(p, None) if p is not None else np.zeros(0)
+        self.n_params = int(values.size)
+        if parameter_names is None:
+            parameter_names = tuple(f"p{k}" for k in range(self.n_params))
+        self.parameter_names = tuple(str(s) for s in parameter_names)
+        if len(self.parameter_names) != self.n_params:
+            raise ValueError(f"law: {len(self.parameter_names)} parameter_names for {self.n_params} parameters")
+        self.n_fields, self.field_names = _field_names(fields)
+        self.dim = None  # the d of a matrix
+        ctx = lambda: _Context(self.n_params if p is not None else None, self.n_fields if fields is not None else None, state=True)
+        if lam is not None:
+            self.shape, texts = "lame", [lam, mu]
+        elif isinstance(text, (list, tuple)) and not any(isinstance(r, (list, tuple)) for r in text):
+            if not 1 <= len(text) <= MAX_LAW_COMP:
+                raise ValueError(f"law: a flat list has 1 .. {MAX_LAW_COMP} components; got {len(text)}")
+            self.shape, texts = "vector", list(text)
+        elif isinstance(text, (list, tuple)):
+            d = len(text)
+            if d not in (2, 3) or any(not isinstance(r, (list, tuple)) or len(r) != d for r in text):
+                raise ValueError("law: a matrix is 2 x 2 or 3 x 3 (nested lists; a flat list of texts is the Voigt kind)")
+            self.shape, self.dim = "matrix", d
+            pairs = [(0, 0), (1, 1), (0, 1)] if d == 2 else [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]  # the component order of the ABI
+            for i, j in pairs:
+                if i != j and _parse(text[i][j], ctx()).key() != _parse(text[j][i], ctx()).key():
+                    raise ValueError(f"law: the matrix must be symmetric; entries [{i}][{j}] and [{j}][{i}] differ")
+            texts = [text[i][j] for i, j in pairs]
+        else:
+            self.shape, texts = "scalar", [text]
+        self.texts = tuple(str(t) for t in texts)
+        self.n_comp = len(texts)
+        ops, consts = [], [float(v) for v in values]
+        for c, t in enumerate(texts):
+            _emit(_parse(t, ctx()), ops, consts, self.n_params)
+            ops.append((OP_STORE, c))
+        if len(ops) > MAX_OPS:
+            raise ValueError(f"law: too long: {len(ops)} instructions, at most {MAX_OPS}")
+        if len(consts) > MAX_CONSTS:
+            raise ValueError(f"law: too many constants: {len(consts)} (the parameters among them), at most {MAX_CONSTS}")
+        self.depth = max(stack_depths(ops))
+        if self.depth > MAX_STACK:
+            raise ValueError(f"law: too deep: stack depth {self.depth}, at most {MAX_STACK}")
+        self._ops = ops  # the operand of a state read is still (name, k)
+        self._consts = np.array(consts, dtype=np.float64)
+        self.n_y = 1 + max([int(k) for op, k in ops if op == OP_Y], default=-1)  # fast-variable components the law reads
+        self.state_indices = {name: 1 + max([k[1] for op, k in ops if op == OP_X and isinstance(k, tuple) and k[0] == name], default=-1)
+                              for name in "esc"}  # entries of e, s and c it reads
+
+    @property
+    def p(self) -> np.ndarray:
+        """The values of the parameters (a copy)."""
+        return self._consts[:self.n_params].copy()
+
+    def with_parameters(self, p) -> "SecantLaw":
+        """The same law at other parameter values: only ``consts[:n_params]`` replaced -- nothing is parsed."""
+        values = _parameter_values(p, self.n_params)
+        other = copy.copy(self)
+        other._consts = self._consts.copy()
+        other._consts[:self.n_params] = values
+        return other
+
+    def program(self, t: int, n_comp: int) -> tuple[np.ndarray, np.ndarray]:
+        """(ops[n_ops, 2] uint8, consts[n_consts] float64) on a plan of tensor size ``t`` whose coefficient has ``n_comp`` entries per
+        element: every component's code followed by its ``STORE k``.  ``ValueError`` when the law has another number of components
+        than ``n_comp`` (naming both), for an index of ``s`` / ``e`` at or above t, of ``c`` at or above n_comp."""
+        if self.n_comp != n_comp:
+            raise ValueError(f"law: it has {self.n_comp} components; the plan's coefficient has n_comp = {n_comp}")
+        base = {"e": 3 + self.n_fields, "s": 3 + self.n_fields + t, "c": 3 + self.n_fields + 2 * t}
+        for name, bound, what in (("e", t, "t"), ("s", t, "t"), ("c", n_comp, "n_comp")):
+            if self.state_indices[name] > bound:
+                raise ValueError(f"law: {name}[{self.state_indices[name] - 1}] is out of range: the plan has {what} = {bound} "
+                                 f"(t = {t}, n_comp = {n_comp})")
+        ops = [(op, base[k[0]] + k[1] if isinstance(k, tuple) else k) for op, k in self._ops]
+        return np.array(ops, dtype=np.uint8).reshape(-1, 2), self._consts.copy()
+
+    def host_values(self, e, s, c, x, y=None, fields=None) -> np.ndarray:
+        """values[N, n_el, n_comp]: the law on every element from e[N, n_el, t] and s[N, n_el, t] (the strain and the secant flux of
+        the current iterate), c[N, n_el(, n_comp)] (the BASE coefficient stream), x[N, 3] (the macro midpoints), y[n_el, d] (the
+        element centroids; may be None when the law reads no ``y``) and fields[N, n_fields] -- ``_run``, value pass, on the rows the
+        device reads.  Bit for bit the device's ``law_values`` wherever the program holds exactly rounded operations only."""
+        e, s = np.asarray(e, dtype=np.float64), np.asarray(s, dtype=np.float64)
+        N, n_el, t = e.shape
+        c = np.asarray(c, dtype=np.float64).reshape(N, n_el, -1)
+        ops, consts = self.program(t, c.shape[2])
+        x = np.asarray(x, dtype=np.float64).reshape(N, -1)
+        x = np.concatenate([x, np.zeros((N, 3 - x.shape[1]))], axis=1) if x.shape[1] < 3 else x[:, :3]
+        if self.n_fields:
+            if fields is None:
+                raise ValueError(f"the law reads the fields {', '.join(self.field_names)}: pass fields[N, {self.n_fields}]")
+            fields = np.asarray(fields, dtype=np.float64).reshape(N, self.n_fields)
+        if self.n_y and (y is None or np.shape(y)[-1] < self.n_y):
+            raise ValueError(f"the law reads y[{self.n_y - 1}]: pass the element centroids y[n_el, d]")
+        rows = [x[:, k, None] for k in range(3)] + [fields[:, k, None] for k in range(self.n_fields)]
+        rows += [a[:, :, k] for a in (e, s, c) for k in range(a.shape[2])]
+        yr = [] if y is None else [np.asarray(y, dtype=np.float64)[None, :, k] for k in range(np.shape(y)[-1])]
+        with np.errstate(all="ignore"):
+            out, _ = _run(ops.tolist(), consts, self.n_comp, rows, yr)
+        return np.stack([np.array(np.broadcast_to(v, (N, n_el))) for v in out], axis=-1)
 
 
 def _field_names(fields) -> tuple[int, tuple]:

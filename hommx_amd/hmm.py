@@ -29,9 +29,9 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import fem
-from .batch import (CoefStream, CriterionResult, LoadResponse, MicroCellPlan, Reconstruction, SecondSensitivities, Sensitivities,
-                    StratSensitivities, region_labels)
-from .expr import Criterion, Expression
+from .batch import (CoefStream, CriterionResult, LoadResponse, MicroCellPlan, Reconstruction, SecantResult, SecondSensitivities,
+                    Sensitivities, StratSensitivities, region_labels)
+from .expr import Criterion, Expression, SecantLaw
 from .mesh import Mesh, micro_cells_per_side
 
 _VOIGT = {2: [(0, 0), (1, 1), (0, 1)], 3: [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]}
@@ -325,6 +325,8 @@ class BaseHMM(ABC):
         self._petsc_options_global_solve = petsc_options_global_solve
         self._petsc_options_prefix = petsc_options_prefix
         self._bcs: list[fem.DirichletBC] = []
+        self.secant: SecantResult | None = None  # solve_nonlinear: the last step's result per cell
+        self.nonlinear_history: list[float] = []  # ... and the relative macro change of every step
         self._Dtheta_t = None
         self._plan: MicroCellPlan | None = None
         self._reserved_cells = 0
@@ -1160,6 +1162,86 @@ class BaseHMM(ABC):
         parts = self._chunks(cells, chunk_cells, bytes_per_cell, call, (lambda sub, kind: self._polarisation_loads(sub, kind)) if with_load else None)
         return _join(parts, cells=cells)
 
+    def _secant_tensors(self, cells: np.ndarray, xi: np.ndarray, law: SecantLaw, rows: np.ndarray, points: np.ndarray, chunk_cells, **kw) -> SecantResult:
+        """``plan.secant`` of ``law`` on ``cells`` under the macro strains ``xi``, chunk by chunk -> one ``SecantResult`` with ``cells``.
+        Under a process group every rank iterates its block and one all-gather of t t + t + 3 numbers per cell (and the info flags)
+        returns the fields to every rank, as ``_effective_polarisation`` does."""
+        t = self._tensor_size()
+
+        def bytes_per_cell():
+            out = 8 * (3 + t * t + t) + 4
+            return out if self._sampled_on_device() else out + self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) * 8
+
+        def local(b, e):
+            call = lambda plan, coef, M, _, sub, at: plan.secant(coef, xi[b + at:b + at + len(sub)], law, M, rows=rows[b + at:b + at + len(sub)],
+                                                                points=points, **kw)
+            return _join(self._chunks(cells[b:e], chunk_cells, bytes_per_cell, call), cells=cells[b:e])
+
+        if not self._sharded():
+            return local(0, len(cells))
+        from .dist import run_sharded
+
+        def block(b, e):
+            r = local(b, e)
+            return np.concatenate([r.A_eff.reshape(e - b, t * t), r.mean_flux, r.rounds[:, None], r.change[:, None], r.status[:, None]], axis=1), r.info
+
+        width = t * t + t + 3
+        packed, info = run_sharded(t, len(cells), block, device=self._shard_device(), shape=(width,))
+        return SecantResult(packed[:, :t * t].reshape(-1, t, t).copy(), packed[:, t * t:t * t + t].copy(), np.rint(packed[:, -3]).astype(np.int64),
+                            packed[:, -2].copy(), np.rint(packed[:, -1]).astype(np.int64), info, cells=cells)
+
+    def solve_nonlinear(self, law: SecantLaw, max_iter: int = 30, tol: float = 1e-8, micro_iter: int = 50, micro_tol: float = 1e-10,
+                        relax: float = 1.0, field_values=None, u0=None, chunk_cells: int | None = None) -> fem.Function:
+        """The two-scale problem with a strain-dependent micro coefficient ``law`` (a ``SecantLaw``: the entries of the coefficient of a
+        micro element as expressions of its own strain ``e``, secant stress ``s`` and base coefficient ``c``, the solver's ``A``), by
+        the Kacanov (secant) iteration on both scales.  u^0 is ``u0`` (a macro ``fem.Function`` or its dof array) or
+        ``solve()``.  Per macro step: the macro strain of u^k on every cell, the secant iteration of every sampling box ON THE DEVICE
+        (hommx_secant_source: at most ``micro_iter`` rounds to ``micro_tol``, relaxed by ``relax``), the macro matrix from the secant
+        tensors, and the macro solve of ``solve()`` on it.  It stops when ``max |u^{k+1} - u^k| <= tol max |u^{k+1}|``, or after
+        ``max_iter`` steps.  ``field_values``: the values of the law's own fields ``f[k]`` per macro cell, in the shapes ``set_fields``
+        takes.  In the law ``x`` is the macro cell midpoint and ``y`` the centroid of the micro element.
+
+        Afterwards ``effective_tensors`` holds the secant tensors of the last step, ``secant`` its ``SecantResult`` (rounds, change,
+        status, info and mean flux per cell), ``nonlinear_history`` the relative macro change of every step; the solver is marked for
+        reassembly, so a later ``solve()`` is the linear one again.  One WARNING when the macro loop or any cell did not converge.
+        ``RuntimeError`` when a polarisation is set (loads beside a law are out of scope) or the law reads fields without
+        ``field_values``.  Out of scope as well: the consistent tangent and a macro Newton method, warm starts of the micro iteration
+        across macro steps (``MicroCellPlan.secant(coef_start=...)`` has them), ``reconstruct()`` / ``criterion()`` of the nonlinear
+        state (``MicroCellPlan.secant(return_coef=True)`` gives the stream to pass to them).  Under a process group every rank
+        iterates its block of the cells, as in ``solve()``."""
+        if self._polarisation is not None:
+            raise RuntimeError("solve_nonlinear() does not take a polarisation or eigenstrain: loads beside a law are out of scope")
+        if law.n_fields and field_values is None:
+            raise RuntimeError(f"the law reads the fields {', '.join(law.field_names)}: pass field_values, their values per macro cell")
+        cells = np.arange(self._msh.num_cells)
+        rows = self._msh.cell_midpoints()[cells]
+        if law.n_fields:
+            rows = np.concatenate([rows, self._field_values(law, field_values)[cells]], axis=1)
+        points = np.ascontiguousarray(self._cell_mesh.cell_midpoints()[:, : self._tdim])
+        u = self._macro_dofs(u0, "u0").copy() if u0 is not None else self.solve().x.array.copy()
+        history, converged, result = [], False, None
+        for _ in range(int(max_iter)):
+            xi = self._macro_strains(cells, u)
+            result = self._secant_tensors(cells, xi, law, rows, points, chunk_cells, max_iter=micro_iter, tol=micro_tol, relax=relax)
+            self._set_macro_matrix(self._local_stiffness_from_tensors(cells, result.A_eff))
+            self.effective_tensors, self.cell_info = result.A_eff, result.info
+            new = self.solve().x.array.copy()
+            change, scale = float(np.abs(new - u).max()), float(np.abs(new).max())
+            history.append(change / scale if scale > 0.0 else 0.0)
+            u = new
+            if change <= tol * scale:
+                converged = True
+                break
+        self.secant, self.nonlinear_history = result, history
+        self._needs_reassembly = True
+        counts = {int(s): int((result.status == s).sum()) for s in np.unique(result.status)} if result is not None else {}
+        if not converged or any(s != 0 for s in counts):
+            self._logger.warning(
+                "solve_nonlinear: %s after %d macro steps (last relative change %.3e, tol %.3e); micro cells by status: %s",
+                "the macro loop did not converge" if not converged else "the macro loop converged, but not every cell did", len(history),
+                history[-1] if history else float("nan"), tol, ", ".join(f"{s}: {n}" for s, n in sorted(counts.items())))
+        return self._u
+
     def _parameter_directions(self) -> tuple[tuple, np.ndarray]:
         """(names, directions[n_dirs, n_el(, n_comp)]) of the parameters of a ``TwoPhase`` or affine ``Separable`` coefficient: the element
         stream is linear in them, so its derivative with respect to each is one direction every macro cell shares.  ``TwoPhase``: the
@@ -1477,6 +1559,12 @@ class PoissonPeriodicHMM:
         self._A_hom = AH[0]
         self._correctors = h._on_micro_mesh(chi[0])
         return self._A_hom
+
+    def solve_nonlinear(self, *args, **kw):
+        """Not offered here: with one periodic cell for the whole domain the secant tensor would still differ from macro cell to
+        macro cell (it depends on the macro strain), which is what ``PoissonHMM.solve_nonlinear`` computes."""
+        raise RuntimeError("PoissonPeriodicHMM has no solve_nonlinear(): the secant tensor depends on the macro strain of every cell; "
+                           "use PoissonHMM.solve_nonlinear")
 
     def solve(self) -> fem.Function:
         """hmm.py:1247-1256: standard P1 FEM with the constant A_hom."""

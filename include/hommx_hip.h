@@ -713,6 +713,69 @@ int hommx_criterion_source_device(hommx_plan* plan, int64_t n_cells, const hommx
                                   const hommx_criterion_args* args, void* stream);
 
 /*
+ * Strain-dependent coefficients: the secant (Kacanov) iteration of a cell, on the device.  A law is a
+ * hommx_coef_program in the opcodes of HOMMX_COEF_PROGRAM, none added, on the row of a criterion,
+ *   row = [midpoint (3) | fields (n_fields) | e_K (t) | s_K (t) | c_K (n_comp)],
+ * with n_comp == the plan's: one STORE k per entry of the element's coefficient, on every kind (the 21 Voigt entries included).
+ * c_K is the BASE coefficient of the element, the stream `src` expands to; e_K the gradient / strain of the current iterate and
+ * s_K = material(current coefficient of K) e_K its secant flux / stress.  `Y i` is coordinate i of the element's centroid.
+ *
+ * Cell T starts from c^0 = coef_start (if given) or the base stream.  Round j = 0, 1, ...:
+ *   1. the correctors and A^j = A_eff(c^j) on the plan's route;
+ *   2. per element e_K, q_K = material(c^j_K) e_K, formed without contraction as hommx_criterion_source forms them;
+ *   3. v_K = law(row), n_comp values; w_K = v_K if relax == 1, else add_rn(mul_rn(1 - relax, c^j_K), mul_rn(relax, v_K));
+ *   4. change^j = max_{K,k} |w - c^j| / max_{K,k} |w| (0 when both are 0), mean_flux^j = sum_K |K| q_K (fixed-order reductions);
+ *   5. the cell stops with a status, tested in this order -- 3: info[T] != 0, the elimination flagged a pivot (change and mean_flux
+ *      are then NaN, the law is not evaluated); 2: some v_K is not finite; 0: change^j <= tol; 1: j + 1 == max_iter -- or goes on
+ *      with c^{j+1} = w.
+ * The outputs are those of the stopping round and belong together: A_eff = A^j, mean_flux, coef_out = c^j (the stream A_eff belongs
+ * to: a stopping round never commits w), state = [rounds = j + 1 | change^j | status], and strain / flux / law_values of that round.
+ * A stopped cell is frozen: its stream is not touched again, so the later eliminations of its chunk reproduce its A_eff and info bit
+ * for bit, and its outputs do not depend on its neighbours, its batch position, the chunking, max_iter beyond its own stopping round,
+ * the outputs asked for or the entry point.
+ *
+ *   program     n_comp == the plan's; host memory in the device entry too
+ *   n_fields    0 .. HOMMX_PROGRAM_MAX_FIELDS fields of the law's own per macro cell; rows [n_cells][3 + n_fields]
+ *   points      [n_el][dim], shared by all cells; may be NULL if the program has no Y
+ *   xi          [n_cells][t]
+ *   max_iter    >= 1;  tol >= 0, not NaN;  relax in (0, 1]
+ *   coef_start  [n_cells][n_el][n_comp] or NULL
+ *   state       [n_cells][3], required;  A_eff [n_cells][t][t], required;  mean_flux [n_cells][t] or NULL
+ *   coef_out    [n_cells][n_el][n_comp] or NULL
+ *   strain, flux [n_cells][n_el][t], both or neither;  law_values [n_cells][n_el][n_comp] = v_K or NULL
+ *   info        as hommx_solve_batch, or NULL
+ * src, M: as hommx_reconstruct_source.  A load is out of scope.  HOMMX_EINVAL, before the plan's device is made current: a null plan,
+ * source, argument struct, program, rows, xi, state or A_eff; one of strain / flux without the other; everything a program is refused
+ * for against n_comp == the plan's and a row of 3 + n_fields + 2 t + n_comp entries; a Y in the program with points NULL; max_iter
+ * < 1; tol negative or NaN; relax outside (0, 1].  The chunk is that of the reconstruction, with the current and the candidate stream
+ * of a chunk (2 n_el n_comp doubles per cell) counted as scratch.  The device entry queues exactly max_iter rounds per chunk and
+ * reads nothing back; the host entry reads the chunk's state after each round and stops when no cell runs.  Both give the same bits.
+ */
+typedef struct hommx_secant_args {
+  const hommx_coef_program* program;
+  int32_t n_fields;
+  const double* rows;
+  const double* points;
+  const double* xi;
+  int32_t max_iter;
+  double tol, relax;
+  const double* coef_start;
+  double* state;
+  double* A_eff;
+  double* mean_flux;
+  double* coef_out;
+  double* strain;
+  double* flux;
+  double* law_values;
+  int32_t* info;
+} hommx_secant_args;
+#define HOMMX_SECANT_NSTATE 3
+int hommx_secant_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_secant_args* args);
+/* Same with DEVICE pointers (in *src and *args; the structs and the program are host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
+int hommx_secant_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                               const hommx_secant_args* args, void* stream);
+
+/*
  * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
  * periodic: the caller folds the mesh vertices into n_nodes independent (periodic) nodes -- cell_problem.py:38-300's slave -> master
  * map -- and passes, per element, the periodic node of every vertex and the UNFOLDED vertex coordinates (gradients and volumes).

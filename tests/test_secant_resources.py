@@ -1,0 +1,96 @@
+"""Scratch, spill and LDS of EVERY instantiation of k_secant_update<DIM, KIND, MESH, OUT> (csrc/secant.hip).
+
+The kernel keeps the top of its stack, the strain, the flux, the running maxima and the flux sums in registers and indexes none of them
+dynamically; on STORE k the value goes straight to the candidate stream, so no array of n_comp values (21 on the Voigt kind) is live.
+It must need no scratch and spill nothing.  The stack rows below the top and the field are DYNAMIC LDS, sized at launch; the static LDS
+is the reduction rows alone, and they are this kernel's own: red[8][t] doubles for the t sums of mean_flux and red_max[8][3] for the two
+maxima of the change and the non-finite flag -- 8 * (t + 3) * 8 bytes, by the tensor size t of the instantiation.  The figures are read
+from the metadata notes of the gfx950 code object inside the built library (clang-offload-bundler, llvm-readelf), in the manner of
+test_criterion_resources.py: metadata only, no instruction is looked at.
+"""
+
+import itertools
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+KERNEL = r"15k_secant_updateILi(\d)ELi(\d)ELb([01])ELb([01])EE"  # <DIM, KIND, MESH, OUT>
+TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
+MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+WALK_WAVES = 8  # kWalkWaves of elem_walk.h
+
+
+def tensor_size(dim, kind):
+    """t of kind_sizes (csrc/kernels.h): dim for the Poisson kinds 0, 1; dim (dim + 1) / 2 for the elasticity kinds 2, 3."""
+    return dim if kind < 2 else dim * (dim + 1) // 2
+
+
+def reduction_rows(dim, kind):
+    """bytes of red[kWalkWaves][t] and red_max[kWalkWaves][3], doubles"""
+    return WALK_WAVES * (tensor_size(dim, kind) + 3) * 8
+
+
+INSTANTIATIONS = list(itertools.product((2, 3), (0, 1, 2, 3), (0, 1), (0, 1)))
+
+
+def _tool(name):
+    for d in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin"), os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")):
+        p = os.path.join(d, name)
+        if os.path.exists(p):
+            return p
+    return shutil.which(name)
+
+
+@pytest.fixture(scope="module")
+def kernels(tmp_path_factory):
+    """{(DIM, KIND, MESH, OUT): metadata} of every k_secant_update of the gfx950 code object that holds them."""
+    from hommx_amd import _lib
+
+    bundler, readelf = _tool("clang-offload-bundler"), _tool("llvm-readelf")
+    if not bundler or not readelf:
+        pytest.skip("clang-offload-bundler / llvm-readelf of the ROCm LLVM not found")
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.fail(f"{_lib.LIB_PATH} is not built")
+    tmp = tmp_path_factory.mktemp("secant_co")
+    data = open(_lib.LIB_PATH, "rb").read()
+    starts = [m.start() for m in re.finditer(MAGIC, data)] + [len(data)]
+    for i, (a, b) in enumerate(zip(starts, starts[1:])):
+        if not re.search(KERNEL.encode(), data[a:b]):
+            continue
+        bundle, co = tmp / f"bundle{i}.bin", tmp / f"bundle{i}.co"
+        bundle.write_bytes(data[a:b])
+        subprocess.run([bundler, "--unbundle", "--type=o", f"--targets={TARGET}", f"--input={bundle}", f"--output={co}"], check=True,
+                       capture_output=True)
+        notes = subprocess.run([readelf, "--notes", str(co)], check=True, capture_output=True, text=True).stdout
+        out = {}
+        for entry in re.split(r"\n  - (?=\.agpr_count:)", notes):
+            name = re.search(r"\n\s+\.name:\s+(\S+)", entry)
+            found = name and not name.group(1).endswith(".kd") and re.search(KERNEL, name.group(1))
+            if found:
+                key = tuple(int(g) for g in found.groups())
+                assert key not in out, name.group(1)
+                out[key] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*(?:\n|$)", entry)}
+        return out
+    pytest.fail("no gfx950 code object of the library holds k_secant_update")
+
+
+def test_the_instantiations_are_the_eight_pairs_times_geometry_and_out(kernels):
+    assert set(kernels) == set(INSTANTIATIONS)
+
+
+@pytest.mark.parametrize("key", INSTANTIATIONS, ids=lambda k: "dim{}_kind{}_mesh{}_out{}".format(*k))
+def test_no_scratch_no_spill_and_static_lds_is_the_reduction_rows(kernels, key):
+    md = kernels[key]
+    print(key, {k: md[k] for k in ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "private_segment_fixed_size",
+                                   "group_segment_fixed_size")})
+    assert md["private_segment_fixed_size"] == 0
+    assert md["vgpr_spill_count"] == 0
+    assert md["group_segment_fixed_size"] == reduction_rows(key[0], key[1])
+    assert -(-md["vgpr_count"] // 8) * 8 + md["agpr_count"] <= 256  # 512 threads are two waves per SIMD: at most 256 registers each
+
+
+def test_the_reduction_rows_by_tensor_size():
+    assert [reduction_rows(d, k) for d, k in ((2, 0), (3, 1), (2, 2), (3, 3))] == [320, 384, 384, 576]
