@@ -213,6 +213,20 @@ class SecantArgs(C.Structure):
     ]
 
 
+class SecantTangentArgs(C.Structure):
+    """hommx_secant_tangent_args: the iteration (a SecantArgs), the sibling plan of the tangent kind and where D, the asymmetry, the
+    tangent stream and the info of the tangent elimination go."""
+
+    _fields_ = [
+        ("secant", C.POINTER(SecantArgs)),
+        ("tangent_plan", C.c_void_p),
+        ("tangent", C.c_void_p),
+        ("asymmetry", C.c_void_p),
+        ("tangent_coef", C.c_void_p),
+        ("tangent_info", C.c_void_p),
+    ]
+
+
 def _prototypes() -> dict:
     """name -> (restype, argtypes) of every symbol include/hommx_hip.h declares: ``load()`` declares them from this table, and
     the tests check that the header and the library export exactly these names."""
@@ -267,6 +281,8 @@ def _prototypes() -> dict:
         "hommx_criterion_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(CriterionArgs), vp]),
         "hommx_secant_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantArgs)]),
         "hommx_secant_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantArgs), vp]),
+        "hommx_secant_tangent_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantTangentArgs)]),
+        "hommx_secant_tangent_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantTangentArgs), vp]),
         "hommx_solve_batch_two_phase": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_two_phase_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_separable": (c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),

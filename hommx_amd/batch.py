@@ -232,7 +232,13 @@ class SecantResult:
     1 ``max_iter`` reached, 2 the law gave a value that is not finite, 3 the elimination flagged a pivot -- ``info`` then), ``info[N]``.
     With ``return_coef`` ``coef[N, n_el(, n_comp)]``, the element stream ``A_eff`` belongs to (pass it to ``reconstruct`` /
     ``criterion`` for the nonlinear state); with ``fields`` ``strain`` and ``flux`` ``[N, n_el, t]``; with ``values``
-    ``values[N, n_el, n_comp]``, what the law gave.  ``cells``: the macro cells (solver classes).  What was not asked for is None."""
+    ``values[N, n_el, n_comp]``, what the law gave.  ``cells``: the macro cells (solver classes).  What was not asked for is None.
+
+    From ``secant_tangent`` (hommx_secant_tangent_source) also ``tangent[N, t, t]`` = D = d mean_flux / d xi at that
+    state (NaN for a cell of status 2 or 3), ``asymmetry[N]`` = max |T - T^T| / max |T| of the element tangents (0 for a law with a
+    potential; D is then exact, otherwise it is the tangent of the symmetrised law; NaN for status 2 or 3), ``tangent_info[N]`` the
+    info of the tangent elimination and, with ``return_tangent_coef``, ``tangent_coef[N, n_el, t (t + 1) / 2]``, the element stream
+    of the tangent kind that was eliminated."""
 
     A_eff: np.ndarray
     mean_flux: np.ndarray
@@ -245,6 +251,10 @@ class SecantResult:
     flux: np.ndarray | None = None
     values: np.ndarray | None = None
     cells: np.ndarray | None = None
+    tangent: np.ndarray | None = None
+    asymmetry: np.ndarray | None = None
+    tangent_info: np.ndarray | None = None
+    tangent_coef: np.ndarray | None = None
 
 
 REGION_FIELDS = ("region_volume", "region_mean_strain", "region_mean_flux", "region_energy", "region_max_flux", "region_argmax_element")
@@ -872,6 +882,45 @@ class MicroCellPlan:
         element centroids, required when it reads ``y``; ``coef_start[N_c, n_el(, n_comp)]``: the stream the iteration starts from
         (default: the base stream), e.g. ``SecantResult.coef`` of a neighbouring macro strain.  The batch runs in the chunks of
         ``reconstruct``; a load beside a law is out of scope."""
+        return self._secant(coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef)
+
+    @property
+    def tangent_kind(self) -> str:
+        """The kind of the sibling plan ``secant_tangent`` eliminates the tangent coefficient on: a full symmetric t x t matrix per
+        element -- "poisson_matrix" for the Poisson kinds, "elasticity_voigt" for the elasticity kinds."""
+        return "poisson_matrix" if self.kind.startswith("poisson") else "elasticity_voigt"
+
+    def _check_tangent(self, law, tangent_plan):
+        """What ``secant_tangent`` and ``secant_tangent_device`` refuse before the library does: an implicit law, a sibling plan of the
+        wrong kind or shape."""
+        if not law.explicit:
+            raise ValueError(f"the law reads s[{law.state_indices['s'] - 1}]: the consistent tangent takes an explicit law, one that reads no "
+                             "s[k]; an implicit law is out of scope")
+        if not isinstance(tangent_plan, MicroCellPlan) or tangent_plan is self:
+            raise ValueError(f"tangent_plan must be another MicroCellPlan, of kind {self.tangent_kind!r} on the same micro mesh")
+        if tangent_plan.kind != self.tangent_kind:
+            raise ValueError(f"tangent_plan has kind {tangent_plan.kind!r}; the tangent kind of a {self.kind!r} plan is {self.tangent_kind!r}")
+        mine, its = (self.dim, self.n_micro, self.n_el, self.n_nodes, self.device), \
+            (tangent_plan.dim, tangent_plan.n_micro, tangent_plan.n_el, tangent_plan.n_nodes, tangent_plan.device)
+        if mine != its:
+            raise ValueError(f"tangent_plan has (dim, n_micro, n_el, n_nodes, device) = {its}; the plan has {mine}")
+
+    def secant_tangent(self, coef, xi: np.ndarray, law, tangent_plan: "MicroCellPlan", M: np.ndarray | None = None, rows=None, points=None,
+                       max_iter: int = 50, tol: float = 1e-10, relax: float = 1.0, coef_start=None, fields: bool = False,
+                       values: bool = False, return_coef: bool = False, return_tangent_coef: bool = False) -> SecantResult:
+        """``secant`` and, at the state every cell stops in, the consistent tangent D = d mean_flux / d xi (hommx_secant_tangent_source;
+        DESIGN 4.16): the arguments of ``secant`` and ``tangent_plan``, a plan of ``self.tangent_kind`` on the same micro mesh and
+        device (``MicroCellPlan(dim, n, plan.tangent_kind)`` or ``from_mesh`` of the same mesh).  Every member ``secant`` returns has
+        its bits; ``tangent``, ``asymmetry``, ``tangent_info`` and, with ``return_tangent_coef``, ``tangent_coef`` come with them.
+        The law must be explicit (``law.explicit``): ``ValueError`` naming the ``s[k]`` it reads otherwise, and for a ``tangent_plan``
+        of the wrong kind or shape."""
+        self._check_tangent(law, tangent_plan)
+        return self._secant(coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef, tangent_plan,
+                            return_tangent_coef)
+
+    def _secant(self, coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef, tangent_plan=None,
+                return_tangent_coef=False) -> SecantResult:
+        """The host call of ``secant`` (``tangent_plan`` None) and ``secant_tangent``."""
         stream = self._as_stream(coef)
         nc = self._check_stream(stream)
         xi = np.ascontiguousarray(xi, dtype=np.float64)
@@ -908,9 +957,24 @@ class MicroCellPlan:
         args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows.ctypes.data, addr(points), xi.ctypes.data, max_iter, tol, relax,
                                addr(coef_start), state.ctypes.data, None, mean_flux.ctypes.data, addr(out_coef), addr(strain), addr(flux),
                                addr(vals), None)
-        A, info = self._source_call("hommx_secant_source", nc, M, stream, args)
+        if tangent_plan is None:
+            A, info = self._source_call("hommx_secant_source", nc, M, stream, args)
+            return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
+                                strain, flux, vals)
+        D = np.empty((nc, self.t, self.t), dtype=np.float64)
+        asym = np.empty(nc, dtype=np.float64)
+        tinfo = np.zeros(nc, dtype=np.int32)
+        tcoef = np.empty((nc, self.n_el, self.t * (self.t + 1) // 2), dtype=np.float64) if return_tangent_coef else None
+        targs = _lib.SecantTangentArgs(C.pointer(args), tangent_plan._h, D.ctypes.data, asym.ctypes.data, addr(tcoef), tinfo.ctypes.data)
+        src = stream.coef_source()
+
+        def call(Mp, o, i):
+            args.A_eff, args.info = o, i
+            return self._lib.hommx_secant_tangent_source(self._h, nc, C.byref(src), Mp, C.byref(targs))
+
+        A, info = self._host_call("hommx_secant_tangent_source", nc, M, call)
         return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
-                            strain, flux, vals)
+                            strain, flux, vals, None, D, asym, tinfo, tcoef)
 
     def solve_two_phase(self, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None = None,
                         return_info: bool = False):
@@ -1116,6 +1180,29 @@ class MicroCellPlan:
                                flux_ptr or None, values_ptr or None, info_ptr or None)
         _lib.check(self._lib.hommx_secant_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
                    "hommx_secant_source_device")
+
+    def secant_tangent_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, xi_ptr: int, law,
+                              tangent_plan: "MicroCellPlan", rows_ptr: int, state_ptr: int, A_ptr: int, tangent_ptr: int, asymmetry_ptr: int,
+                              points_ptr: int | None = None, max_iter: int = 50, tol: float = 1e-10, relax: float = 1.0,
+                              coef_start_ptr: int | None = None, mean_flux_ptr: int | None = None, coef_ptr: int | None = None,
+                              strain_ptr: int | None = None, flux_ptr: int | None = None, values_ptr: int | None = None,
+                              info_ptr: int | None = None, tangent_coef_ptr: int | None = None, tangent_info_ptr: int | None = None,
+                              stream: int | None = None):
+        """Device-pointer form of ``secant_tangent`` (hommx_secant_tangent_source_device), asynchronous on ``stream``: the pointers of
+        ``secant_device`` and tangent[n_cells, t, t], asymmetry[n_cells], tangent_coef[n_cells, n_el, t (t + 1) / 2],
+        tangent_info[n_cells] (int32).  Per chunk ``max_iter`` rounds, one tangent launch and one solve on ``tangent_plan`` are queued
+        and nothing is read back; the bits are those of ``secant_tangent``."""
+        self._check_tangent(law, tangent_plan)
+        max_iter, tol, relax = self._secant_limits(max_iter, tol, relax)
+        prog = self._law_program(law)
+        pstruct = prog.struct()
+        args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows_ptr, points_ptr or None, xi_ptr, max_iter, tol, relax,
+                               coef_start_ptr or None, state_ptr, A_ptr, mean_flux_ptr or None, coef_ptr or None, strain_ptr or None,
+                               flux_ptr or None, values_ptr or None, info_ptr or None)
+        targs = _lib.SecantTangentArgs(C.pointer(args), tangent_plan._h, tangent_ptr, asymmetry_ptr, tangent_coef_ptr or None,
+                                       tangent_info_ptr or None)
+        _lib.check(self._lib.hommx_secant_tangent_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(targs),
+                                                                stream or None), "hommx_secant_tangent_source_device")
 
     def solve_separable_device(self, n_cells: int, family: str, n_q: int, table_ptr: int, weights_ptr: int | None, params_ptr: int,
                                M_ptr: int | None, out_ptr: int, info_ptr: int | None, stream: int | None = None):

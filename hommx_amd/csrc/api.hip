@@ -117,8 +117,9 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 // B_POLAR: the loads of one chunk of hommx_loads_source that the device forms: the expansion of a program load, [nc][n_el][t]
 //            (derived_call; an eigenstrain becomes the eigenstress in place), or the eigenstresses of an eigenstrain array that is not
 //            the plan's to overwrite, [nc][n_loads][n_el][t] (loads_run; crit_run: the one load of a criterion)
-// B_SECANT: the current and the candidate element stream of one chunk of hommx_secant_source, [chunk][n_el][n_comp] each, and the info
-//            of its eliminations where the caller takes none, [chunk] (secant_run)
+// B_SECANT: the current and the candidate element stream of one chunk of hommx_secant_source, [chunk][n_el][n_comp] each, the info
+//            of its eliminations where the caller takes none, [chunk], and the tangent stream of a chunk of hommx_secant_tangent_source
+//            where the caller takes none, [chunk][n_el][t (t + 1) / 2] (secant_run)
 enum {
   B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, B_SENS2, B_TANGENT, B_CURVATURE,
   B_POLAR, B_SECANT, N_BUF
@@ -1666,23 +1667,39 @@ int crit_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const 
 // one chunk on the device: the current stream starts as coef_start or the base stream; per round the correctors of the current stream
 // into the plan's scratch, then k_secant_update.  The device entry queues max_iter rounds and reads nothing; the host entry reads the
 // chunk's state after each round and stops when no cell runs -- a stopped cell is frozen, so the bits are the same
-int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_secant_args>& v, bool device, hipStream_t st) {
-  const hommx_secant_args& a = v.a;
+// tail: what hommx_secant_tangent_source adds behind the last round of a chunk (null: the iteration alone).  After the last queued round
+// the corrector buffer holds the correctors of `cur` for every cell -- a stopped cell's elimination reproduces, a stopping round never
+// commits --, so one launch of k_secant_tangent forms the tangent stream (the caller's tangent_coef, else scratch of the chunk in
+// B_SECANT), solve_source_device eliminates it on the tangent plan, in that plan's own workspace, and the cells of status 2 or 3 get NaN
+struct TangentTail {
+  hommx_plan* plan;
+  double *tangent, *asymmetry, *coef;
+  int32_t* info;
+};
+// the field of the tangent kernel lies in the slot where it does not fit LDS beside the (wider) stack rows of the forward mode
+bool tangent_in_lds(const hommx_plan* p, int depth) {
+  return hommx::secant_tangent_lds_bytes(plan_ndof(p), depth, hommx::secant_tangent_slots(p->ks.t, depth)) <= hommx::recon_lds_limit();
+}
+int64_t tangent_stream_doubles(const hommx_plan* p) { return p->n_el * (p->ks.t * (p->ks.t + 1) / 2); }
+
+int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, const double* M, const hommx_secant_args& a, bool device,
+               hipStream_t st, const TangentTail* tail = nullptr) {
   const int t = p->ks.t, depth = program_depth(*a.program);
-  const bool slot = !crit_in_lds(p, depth);
+  const bool slot = !crit_in_lds(p, depth), tail_slot = tail && !tangent_in_lds(p, depth);
   const size_t stream = sizeof(double) * p->n_el * p->ks.n_comp;
-  const size_t bytes[3] = {stream * chunk, stream * chunk, a.info ? 0 : sizeof(int32_t) * chunk};
-  char* at[3];
+  const size_t bytes[4] = {stream * chunk, stream * chunk, a.info ? 0 : sizeof(int32_t) * chunk,
+                           tail && !tail->coef ? sizeof(double) * tangent_stream_doubles(p) * chunk : 0};
+  char* at[4];
   if (int rc = carve(p->buf[B_SECANT], bytes, at)) return rc;
   double *cur = reinterpret_cast<double*>(at[0]), *cand = reinterpret_cast<double*>(at[1]);
   int32_t* info = a.info ? a.info : reinterpret_cast<int32_t*>(at[2]);
-  HIP_TRY(hipMemcpyAsync(cur, a.coef_start ? a.coef_start : v.coef, stream * nc, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(cur, a.coef_start ? a.coef_start : coef, stream * nc, hipMemcpyDeviceToDevice, st));
   hommx::SecantArgs k;
   set_geometry(p, k);
-  k.base = v.coef;
+  k.base = coef;
   k.cur = cur;
   k.cand = cand;
-  k.M = v.M;
+  k.M = M;
   k.xi = a.xi;
   k.prog = program_args(*a.program);
   k.n_fields = a.n_fields;
@@ -1698,9 +1715,10 @@ int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_secan
   k.strain = a.strain;
   k.flux = a.flux;
   std::vector<double> seen;
+  double* corr = nullptr;
   for (int j = 0; j < a.max_iter; ++j) {
-    double *d_A_eff = a.A_eff, *corr = nullptr;
-    if (int rc = chunk_correctors(p, nc, chunk, cur, v.M, &d_A_eff, info, slot ? 1 : 0, st, &corr)) return rc;
+    double* d_A_eff = a.A_eff;
+    if (int rc = chunk_correctors(p, nc, chunk, cur, M, &d_A_eff, info, slot || tail_slot ? 1 : 0, st, &corr)) return rc;
     k.corr = corr;
     k.slot = slot ? corr + chunk * t * k.ndof : nullptr;
     k.round = j;
@@ -1713,30 +1731,51 @@ int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<hommx_secan
     if (!running) break;
   }
   if (a.coef_out) HIP_TRY(hipMemcpyAsync(a.coef_out, cur, stream * nc, hipMemcpyDeviceToDevice, st));
+  if (!tail) return HOMMX_OK;
+  hommx::SecantTangentArgs g;
+  set_geometry(p, g);
+  g.corr = corr;
+  g.M = M;
+  g.base = coef;
+  g.cur = cur;
+  g.xi = a.xi;
+  g.prog = k.prog;
+  g.n_fields = a.n_fields;
+  g.rows = a.rows;
+  g.points = a.points;
+  g.state = a.state;
+  g.tan = tail->coef ? tail->coef : reinterpret_cast<double*>(at[3]);
+  g.asym = tail->asymmetry;
+  g.slot = tail_slot ? corr + chunk * t * g.ndof : nullptr;
+  HIP_TRY(hommx::launch_secant_tangent(g, depth, nc, st));
+  if (int rc = solve_source_device(tail->plan, nc, sampled_source(g.tan), M, tail->tangent, tail->info, st)) return rc;
+  HIP_TRY(hommx::launch_tangent_mask(a.state, tail->tangent, t * t, nc, st));
+  return HOMMX_OK;
+}
+
+// the checks of hommx_secant_args against the plan's descriptor
+int secant_checks(const hommx_plan* p, const hommx_secant_args* a) {
+  const hommx::KindSizes ks = hommx::kind_sizes(p->desc.dim, p->desc.kind);
+  if (!a->program) return fail(HOMMX_EINVAL, "null program");
+  if (!a->rows || !a->xi || !a->state || !a->A_eff) return fail(HOMMX_EINVAL, "null rows / xi / state / A_eff");
+  if (!a->strain != !a->flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
+  hommx_coef_source own{};  // what program_check reads of a source
+  own.n_fields = a->n_fields;
+  own.program = a->program;
+  if (int rc = program_check(p, &own, 0, 2 * ks.t + ks.n_comp, ks.n_comp)) return rc;
+  if (!a->points)
+    for (int pc = 0; pc < a->program->n_ops; ++pc)
+      if (a->program->ops[2 * pc] == hommx::OP_Y)
+        return fail(HOMMX_EINVAL, "null points: the program reads y (instruction %d), the centroid of the element", pc);
+  if (a->max_iter < 1) return fail(HOMMX_EINVAL, "max_iter must be at least 1, got %d", a->max_iter);
+  if (!(a->tol >= 0.0)) return fail(HOMMX_EINVAL, "tol must be a number >= 0, got %g", a->tol);
+  if (!(a->relax > 0.0 && a->relax <= 1.0)) return fail(HOMMX_EINVAL, "relax must lie in (0, 1], got %g", a->relax);
   return HOMMX_OK;
 }
 
 // the argument checks of both entry points, then a route that forms correctors
 int secant_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_args* a, bool device) {
-  auto checks = [&] {
-    const hommx::KindSizes ks = hommx::kind_sizes(p->desc.dim, p->desc.kind);
-    if (!a->program) return fail(HOMMX_EINVAL, "null program");
-    if (!a->rows || !a->xi || !a->state || !a->A_eff) return fail(HOMMX_EINVAL, "null rows / xi / state / A_eff");
-    if (!a->strain != !a->flux) return fail(HOMMX_EINVAL, "strain and flux: both or neither");
-    hommx_coef_source own{};  // what program_check reads of a source
-    own.n_fields = a->n_fields;
-    own.program = a->program;
-    if (int rc = program_check(p, &own, 0, 2 * ks.t + ks.n_comp, ks.n_comp)) return rc;
-    if (!a->points)
-      for (int pc = 0; pc < a->program->n_ops; ++pc)
-        if (a->program->ops[2 * pc] == hommx::OP_Y)
-          return fail(HOMMX_EINVAL, "null points: the program reads y (instruction %d), the centroid of the element", pc);
-    if (a->max_iter < 1) return fail(HOMMX_EINVAL, "max_iter must be at least 1, got %d", a->max_iter);
-    if (!(a->tol >= 0.0)) return fail(HOMMX_EINVAL, "tol must be a number >= 0, got %g", a->tol);
-    if (!(a->relax > 0.0 && a->relax <= 1.0)) return fail(HOMMX_EINVAL, "relax must lie in (0, 1], got %g", a->relax);
-    return HOMMX_OK;
-  };
-  return source_open(p, n_cells, src, a, device, checks);
+  return source_open(p, n_cells, src, a, device, [&] { return secant_checks(p, a); });
 }
 
 // The current and the candidate stream of a chunk, the info of its eliminations and the slot of a field that does not fit LDS beside the
@@ -1755,7 +1794,75 @@ int secant_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, cons
   const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE}, {&a.A_eff, t * t, KEPT}, {&a.mean_flux, t},     {&a.coef_out, stream},
                            {&a.strain, field},              {&a.flux, field},        {&a.law_values, stream}};
   return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, recon_chunk, device, st,
-                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_secant_args>& c) { return secant_run(p, nc, chunk, c, device, st); });
+                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_secant_args>& c) {
+                        return secant_run(p, nc, chunk, c.coef, c.M, c.a, device, st);
+                      });
+}
+
+// -- the consistent tangent of the secant response (hommx_secant_tangent_source[_device]) -------------------------------------------------
+// the arguments of a call as the chunk driver re-bases them: the iteration's and the tangent's, flat
+struct SecantTangentCall {
+  hommx_secant_args s;
+  hommx_plan* plan;
+  double *tangent, *asymmetry, *coef;
+  int32_t* info;
+};
+
+// everything secant_open checks, then the tangent's own arguments against the descriptors of both plans alone (of a mesh plan, whose
+// descriptor has no size, the element and node counts as well)
+int secant_tangent_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_tangent_args* a, bool device) {
+  auto checks = [&] {
+    if (!a->secant) return fail(HOMMX_EINVAL, "null secant arguments");
+    if (int rc = secant_checks(p, a->secant)) return rc;
+    const hommx_secant_args& s = *a->secant;
+    const hommx::KindSizes ks = hommx::kind_sizes(p->desc.dim, p->desc.kind);
+    if (!a->tangent_plan || !a->tangent || !a->asymmetry) return fail(HOMMX_EINVAL, "null tangent_plan / tangent / asymmetry");
+    const hommx_plan* q = a->tangent_plan;
+    if (q == p) return fail(HOMMX_EINVAL, "tangent_plan is the plan itself: the tangent elimination needs a plan of its own");
+    const int want = hommx::tangent_kind(p->desc.kind);
+    if (q->desc.kind != want)
+      return fail(HOMMX_EINVAL, "tangent_plan has kind %d; the tangent kind of a plan of kind %d is %d", q->desc.kind, p->desc.kind, want);
+    if (q->desc.dim != p->desc.dim) return fail(HOMMX_EINVAL, "tangent_plan has dim %d; the plan has %d", q->desc.dim, p->desc.dim);
+    if (q->desc.n_micro != p->desc.n_micro)
+      return fail(HOMMX_EINVAL, "tangent_plan has n_micro %d; the plan has %d", q->desc.n_micro, p->desc.n_micro);
+    if (q->desc.device != p->desc.device)
+      return fail(HOMMX_EINVAL, "tangent_plan is on device %d; the plan on %d", q->desc.device, p->desc.device);
+    if (p->desc.n_micro == 0 && (q->n_el != p->n_el || plan_ndof(q) / q->ks.bs != plan_ndof(p) / p->ks.bs))
+      return fail(HOMMX_EINVAL, "tangent_plan is a plan of another mesh: %lld elements, the plan has %lld", (long long)q->n_el,
+                  (long long)p->n_el);
+    const int lo = hommx::program_row_doubles(s.n_fields) + ks.t;
+    for (int pc = 0; pc < s.program->n_ops; ++pc) {
+      const int op = s.program->ops[2 * pc], k = s.program->ops[2 * pc + 1];
+      if (op == hommx::OP_X && k >= lo && k < lo + ks.t)
+        return fail(HOMMX_EINVAL, "the law reads s[%d] (instruction %d): the consistent tangent takes an explicit law, one that reads no "
+                                  "s[k]; an implicit law is out of scope", k - lo, pc);
+    }
+    return HOMMX_OK;
+  };
+  return source_open(p, n_cells, src, a, device, checks);
+}
+
+int secant_tangent_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_secant_tangent_args& args,
+                        bool device, hipStream_t st) {
+  const int64_t t = p->ks.t, field = p->n_el * t, stream = p->n_el * p->ks.n_comp, tan = tangent_stream_doubles(p);
+  Chunk<SecantTangentCall> v{};
+  v.a = SecantTangentCall{*args.secant, args.tangent_plan, args.tangent, args.asymmetry, args.tangent_coef, args.tangent_info};
+  hommx_secant_args& a = v.a.s;
+  const int depth = program_depth(*a.program);
+  const bool own_slot = (!crit_in_lds(p, depth) || !tangent_in_lds(p, depth)) && recon_in_lds(p);
+  const size_t scratch = sizeof(double) * (2 * stream + (own_slot ? plan_ndof(p) : 0) + (args.tangent_coef ? 0 : tan)) + sizeof(int32_t);
+  const CellArray in[] = {{&a.rows, hommx::program_row_doubles(a.n_fields)},
+                          {&a.xi, t},
+                          {&a.coef_start, stream},
+                          {&a.points, p->n_el * p->desc.dim, SHARED}};
+  const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE}, {&a.A_eff, t * t, KEPT}, {&a.mean_flux, t},     {&a.coef_out, stream},
+                           {&a.strain, field},              {&a.flux, field},        {&a.law_values, stream}, {&v.a.tangent, t * t},
+                           {&v.a.asymmetry, 1},             {&v.a.coef, tan},        {&v.a.info, 1, PER_CELL, sizeof(int32_t)}};
+  return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, recon_chunk, device, st,
+                      [&](int64_t nc, int64_t chunk, const Chunk<SecantTangentCall>& c) {
+                        const TangentTail tail{c.a.plan, c.a.tangent, c.a.asymmetry, c.a.coef, c.a.info};
+                        return secant_run(p, nc, chunk, c.coef, c.M, c.a.s, device, st, &tail);
+                      });
 }
 
 // -- second derivatives (hommx_second_sensitivity_source[_device]) ------------------------------------------------------------------------
@@ -1927,6 +2034,18 @@ int hommx_secant_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_
 int hommx_secant_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_secant_args* args) {
   if (int rc = secant_open(p, n_cells, src, args, false); rc != GO) return rc;
   return secant_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
+}
+
+int hommx_secant_tangent_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                       const hommx_secant_tangent_args* args, void* stream) {
+  if (int rc = secant_tangent_open(p, n_cells, src, args, true); rc != GO) return rc;
+  return secant_tangent_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream));
+}
+
+int hommx_secant_tangent_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M,
+                                const hommx_secant_tangent_args* args) {
+  if (int rc = secant_tangent_open(p, n_cells, src, args, false); rc != GO) return rc;
+  return secant_tangent_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
 }
 
 int hommx_second_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,

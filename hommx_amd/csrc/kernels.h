@@ -252,6 +252,34 @@ struct SecantArgs : ElemWalk {
 // dynamic LDS as k_criterion's (criterion_lds_bytes); depth: the maximal stack depth of the (validated) program
 hipError_t launch_secant(const SecantArgs& a, int depth, long long nc, hipStream_t stream);
 
+// secant_tangent.hip: the coefficient of the consistent tangent of the secant response on `nc` cells whose iteration has ended
+// (include/hommx_hip.h, hommx_secant_tangent_source): T_K = material(cur_K) + sum_k g_k (dL_k/de)^T, its
+// symmetric part as an element stream of the tangent kind and the asymmetry of the cell
+struct SecantTangentArgs : ElemWalk {
+  const double* base = nullptr;      // [nc][n_el][n_comp]: what c[k] reads
+  const double* cur = nullptr;       // [nc][n_el][n_comp]: the stream the correctors belong to
+  const double* xi = nullptr;        // [nc][t]
+  ProgramArgs prog;                  // the law; it reads no s entry
+  int n_fields = 0;
+  const double* rows = nullptr;      // [nc][3 + n_fields]
+  const double* points = nullptr;    // [n_el][dim] element centroids, or null (no Y in the program)
+  const double* state = nullptr;     // [nc][3]: the status decides between the tangent (0, 1) and the identity material (2, 3)
+  double* tan = nullptr;             // [nc][n_el][t (t + 1) / 2] in the component order of the tangent kind
+  double* asym = nullptr;            // [nc]: max |T - T^T| / max |T|, NaN for a cell of status 2 or 3
+  double* slot = nullptr;            // [nc][ndof] scratch for the field of cells that do not fit LDS beside the stack (null: LDS)
+};
+// the kind of the element stream k_secant_tangent writes for a plan of `kind`: the full symmetric t x t coefficient
+constexpr int tangent_kind(int kind) { return kind < 2 ? HOMMX_KIND_POISSON_MATRIX : HOMMX_KIND_ELASTICITY_VOIGT; }
+// the slots P of one sweep of the forward mode for a program of stack depth `depth` on a plan of tensor size t: t for t <= 3 and 2
+// for t = 6 where the stack rows of that width fit recon_lds_limit(), else 1 (which fits at every depth)
+int secant_tangent_slots(int t, int depth);
+// dynamic LDS of k_secant_tangent<.., P> with the field in it: the field and the stack rows below the top,
+// stack[depth - 1][1 + P][kWalkThreads]
+size_t secant_tangent_lds_bytes(long long ndof, int depth, int slots);
+hipError_t launch_secant_tangent(const SecantTangentArgs& a, int depth, long long nc, hipStream_t stream);
+// tangent[cell][tt] = NaN for every cell whose status (state[cell][2]) is 2 or 3
+hipError_t launch_tangent_mask(const double* state, double* tangent, int tt, long long nc, hipStream_t stream);
+
 // the loads a corrector pass of the blocked family solves for instead of the canonical ones: rows l < n_loads of Brhs from P (device), the
 // rest zero.  P starts at the first cell of the call
 struct LoadOverride {

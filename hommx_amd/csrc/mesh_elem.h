@@ -42,6 +42,73 @@ __device__ __forceinline__ void material(const double* __restrict__ c, double (&
   }
 }
 
+// entry C[m][n] of material(c), n uniform and not a constant (m may be one): the same value as material() gives, read or formed where
+// it is needed, so that a caller holds a few columns instead of the matrix
+template <int DIM, int KIND>
+__device__ __forceinline__ double material_entry(const double* __restrict__ c, int m, int n) {
+  constexpr int T = KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM;
+  if constexpr (KIND == HOMMX_KIND_POISSON_SCALAR) {
+    return m == n ? c[0] : 0.0;
+  } else if constexpr (KIND == HOMMX_KIND_POISSON_MATRIX) {
+    return m == n ? c[m] : c[DIM + (m + n - 1)];  // 01, 02, 12 behind the diagonal
+  } else if constexpr (KIND == HOMMX_KIND_ELASTICITY_ISO) {
+    const double lam = c[0], mu = c[1];
+    return (m < DIM && n < DIM ? lam : 0.0) + (m == n ? (m < DIM ? 2.0 * mu : mu) : 0.0);
+  } else {
+    const int r = m < n ? m : n, s = m < n ? n : m;
+    return c[r * T - r * (r - 1) / 2 + (s - r)];
+  }
+}
+
+// g = material(unit_k) e, the column of the (linear) map c -> material(c) e at entry k of the coefficient; k is uniform over the wave and
+// no register array is indexed with it.  The operation order, which SecantLaw._material_columns (hommx_amd/expr.py) follows: every
+// entry of g is one entry of e, copied, or +0.0, except
+//   the Lame pair: k = 0 (lambda): g[m] = (e[0] + e[1]) (+ e[2], added last) on the normal rows m < DIM, +0.0 on the shear rows;
+//                  k = 1 (mu): g[m] = 2 e[m] (one product) on the normal rows, e[m] on the shear rows.
+// Scalar: g = e.  Matrix (00, 11, [22,] 01 [, 02, 12]) and Voigt (upper triangle, row-major): entry k = (r, c), r <= c, gives
+// g[r] = e[c] and g[c] = e[r]
+template <int DIM, int KIND>
+__device__ __forceinline__ void material_column(int k, const double (&e)[KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM],
+                                                double (&g)[KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM]) {
+#pragma clang fp contract(off)
+  constexpr int T = KIND >= 2 ? DIM * (DIM + 1) / 2 : DIM;
+  if constexpr (KIND == HOMMX_KIND_POISSON_SCALAR) {
+#pragma unroll
+    for (int m = 0; m < T; ++m) g[m] = e[m];
+  } else if constexpr (KIND == HOMMX_KIND_ELASTICITY_ISO) {
+    double tr = e[0] + e[1];
+    if constexpr (DIM == 3) tr = tr + e[2];
+#pragma unroll
+    for (int m = 0; m < T; ++m) g[m] = k == 0 ? (m < DIM ? tr : 0.0) : (m < DIM ? 2.0 * e[m] : e[m]);
+  } else {
+    // (r, c) of entry k: a scan over the constant pairs in the kind's order
+    int r = 0, c = 0;
+    if constexpr (KIND == HOMMX_KIND_POISSON_MATRIX) {
+      const int o = k - DIM;  // the off-diagonal pairs 01, 02, 12
+      r = k < DIM ? k : o == 2 ? 1 : 0;
+      c = k < DIM ? k : o == 0 ? 1 : 2;
+    } else {
+      int q = 0;
+#pragma unroll
+      for (int m = 0; m < T; ++m)
+#pragma unroll
+        for (int n = m; n < T; ++n, ++q)
+          if (q == k) {
+            r = m;
+            c = n;
+          }
+    }
+    double er = e[0], ec = e[0];
+#pragma unroll
+    for (int m = 1; m < T; ++m) {
+      er = m == r ? e[m] : er;
+      ec = m == c ? e[m] : ec;
+    }
+#pragma unroll
+    for (int m = 0; m < T; ++m) g[m] = m == r ? ec : m == c ? er : 0.0;
+  }
+}
+
 // strain of local dof r = a * bs + alpha in the basis of the canonical loads: Poisson M g_a; elasticity sym(e_alpha (x) M g_a) with
 // the off-diagonal components doubled (E^m, m = (k, l), k != l, has 1/2 at kl and lk)
 template <int DIM, int KIND>

@@ -1,11 +1,12 @@
-// state_program.h -- the value-only interpreter of a program on the state of ONE micro element, shared by criterion.hip (one component,
-// kept) and secant.hip (n_comp components, each stored where it is formed).  It is the value pass of coef_program.hip's on one element
-// instead of a quadrature loop: the dispatch is a scalar branch on readfirstlane of the opcode, every operation one separately rounded
-// IEEE operation in program order (hommx_amd.expr.Criterion.host_values / SecantLaw.host_values are its NumPy twins).  The top of the
-// stack is a register; the levels below it are rows of dynamic LDS, stack[depth - 1][kWalkThreads], lane-contiguous (no bank conflict; a
-// thread touches its own column only: no barrier).  The inputs: x and the 2 t state values are selected by switches on the uniform
-// operand over static registers (no register array is indexed dynamically, hence no scratch); a field f[k], y[i] (the element centroid)
-// and c[k] are vector loads where they are read.  What STORE does is the caller's: store(k, value), k uniform.
+// state_program.h -- the interpreter of a program on the state of ONE micro element, shared by criterion.hip (one component, kept),
+// secant.hip (n_comp components, each stored where it is formed) and, in forward mode over the strain, secant_tangent.hip.  It is the
+// value pass of coef_program.hip's on one element instead of a quadrature loop: the dispatch is a scalar branch on readfirstlane of the
+// opcode, every operation one separately rounded IEEE operation in program order (hommx_amd.expr.Criterion.host_values /
+// SecantLaw.host_values are its NumPy twins).  The top of the stack is a register; the levels below it are rows of dynamic LDS,
+// stack[depth - 1][kWalkThreads], lane-contiguous (no bank conflict; a thread touches its own column only: no barrier).  The inputs: x and
+// the 2 t state values are selected by switches on the uniform operand over static registers (no register array is indexed dynamically,
+// hence no scratch); a field f[k], y[i] (the element centroid) and c[k] are vector loads where they are read.  What STORE does is the
+// caller's: store(k, value), k uniform.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,21 +45,67 @@ __device__ __forceinline__ double pick(int j, const double (&a)[T]) {
 // The program on one element.  x: the midpoint; row: the cell's row (the fields behind the midpoint); e, s: strain and flux; ce: the
 // element's coefficient entry, what c[k] reads; yk: its centroid (read by Y only); stk: this thread's column of the stack rows;
 // store(k, v): component k of the element has the value v
-template <int T, typename Store>
+//
+// P > 0: the forward mode over P slots, in the manner of coef_program.hip's expand_body<P, H>.  A stack entry is (v, d_0 .. d_{P-1}),
+// the rows are stack[depth - 1][1 + P][kWalkThreads], and the seeds are the state reads: `X base + n` of the strain entries
+// n = seed0 .. seed0 + P - 1 of the current sweep seeds d_{n - seed0} = 1, every other read seeds 0.  Each case states its value rule
+// and its tangent rule, those of the table in DESIGN.md section 3 (hommx_amd/expr.py, _TANGENT), the dead rule included: d_j of a
+// result is +0.0 where every operand's d_j is 0.0, and the formula is then not evaluated.  The value statements do not read a tangent,
+// so v is the value pass's bit for bit in every sweep.  store(k, v, d) then.  P = 0 declares no tangent and is the value pass
+template <int T, int P = 0, typename Store>
 __device__ __forceinline__ void run_state_program(const ProgramArgs& prog, int n_fields, const double (&x)[3], const double* __restrict__ row,
                                                   const double (&e)[T], const double (&s)[T], const double* __restrict__ ce,
-                                                  const double* __restrict__ yk, double* __restrict__ stk, Store&& store) {
+                                                  const double* __restrict__ yk, double* __restrict__ stk, Store&& store, int seed0 = 0) {
 #pragma clang fp contract(off)
+  constexpr int PN = P ? P : 1, W = 1 + P;  // PN: no array of length zero; W: the doubles of a stack entry
   const int n_ops = prog.n_ops, base = program_row_doubles(n_fields);
-  double t = 0.0;
-  int sp = 0;  // depth: the top is t, the levels below it stk[0 .. sp-2]
+  double t = 0.0, d[PN], da[PN];  // the top; da: the tangents of the popped entry
+#pragma unroll
+  for (int j = 0; j < P; ++j) d[j] = 0.0;
+  int sp = 0;  // depth: the top is (t, d), the levels below it stk[0 .. sp-2]
   auto push = [&] {
-    if (sp > 0) stk[(sp - 1) * kWalkThreads] = t;
+    if (sp > 0) {
+      stk[(sp - 1) * W * kWalkThreads] = t;
+#pragma unroll
+      for (int j = 0; j < P; ++j) stk[((sp - 1) * W + 1 + j) * kWalkThreads] = d[j];
+    }
     ++sp;
   };
-  auto pop = [&]() -> double {
+  auto pop = [&]() -> double {  // the entry below the top: its value, its tangents into da
     --sp;
-    return stk[(sp - 1) * kWalkThreads];
+#pragma unroll
+    for (int j = 0; j < P; ++j) da[j] = stk[((sp - 1) * W + 1 + j) * kWalkThreads];
+    return stk[(sp - 1) * W * kWalkThreads];
+  };
+  auto pop_value = [&]() -> double {  // an operand whose tangent does not count
+    --sp;
+    return stk[(sp - 1) * W * kWalkThreads];
+  };
+  auto flat = [&] {  // a read that seeds nothing, a piecewise constant result
+#pragma unroll
+    for (int j = 0; j < P; ++j) d[j] = 0.0;
+  };
+  auto rule1 = [&](auto f) {  // d_j of a result of one operand, the top
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      double r = 0.0;
+      if (d[j] != 0.0) r = f(j);
+      d[j] = r;
+    }
+  };
+  auto rule2 = [&](auto f) {  // ... of two, the popped entry and the top
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      double r = 0.0;
+      if (da[j] != 0.0 || d[j] != 0.0) r = f(j);
+      d[j] = r;
+    }
+  };
+  auto any_live = [&] {  // does this lane carry a tangent in the top?  (false for P = 0)
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < P; ++j) any = any || d[j] != 0.0;
+    return any;
   };
   for (int pc = 0; pc < n_ops; ++pc) {
     const uint32_t word = prog.code[pc >> 1] >> ((pc & 1) * 16);  // little endian: opcode in the low byte, operand above it
@@ -67,72 +114,154 @@ __device__ __forceinline__ void run_state_program(const ProgramArgs& prog, int n
       case OP_CONST:
         push();
         t = prog.consts[k];
+        flat();
         break;
       case OP_X:
         push();
-        if (k < 3)
+        flat();
+        if (k < 3) {
           t = pick<3>(k, x);
-        else if (k < base)
+        } else if (k < base) {
           t = row[k];
-        else if (k < base + T)
+        } else if (k < base + T) {
           t = pick<T>(k - base, e);
-        else if (k < base + 2 * T)
+#pragma unroll
+          for (int j = 0; j < P; ++j) d[j] = k - base == seed0 + j ? 1.0 : 0.0;
+        } else if (k < base + 2 * T) {
           t = pick<T>(k - base - T, s);
-        else
+        } else {
           t = ce[k - base - 2 * T];
+        }
         break;
       case OP_Y:
         push();
         t = yk[k];
+        flat();
         break;
       case OP_DUP: push(); break;
-      case OP_ADD: t = add_rn(pop(), t); break;
-      case OP_SUB: t = add_rn(pop(), -t); break;
-      case OP_MUL: t = mul_rn(pop(), t); break;
-      case OP_DIV: t = div_rn(pop(), t); break;
-      case OP_NEG: t = -t; break;
-      case OP_ABS: t = __builtin_fabs(t); break;
+      case OP_ADD: {
+        const double a = pop();
+        rule2([&](int j) { return add_rn(da[j], d[j]); });
+        t = add_rn(a, t);
+        break;
+      }
+      case OP_SUB: {
+        const double a = pop();
+        rule2([&](int j) { return add_rn(da[j], -d[j]); });
+        t = add_rn(a, -t);
+        break;
+      }
+      case OP_MUL: {
+        const double a = pop();
+        rule2([&](int j) { return add_rn(mul_rn(a, d[j]), mul_rn(da[j], t)); });
+        t = mul_rn(a, t);
+        break;
+      }
+      case OP_DIV: {
+        const double a = pop(), v = div_rn(a, t);
+        rule2([&](int j) { return div_rn(add_rn(da[j], -mul_rn(v, d[j])), t); });
+        t = v;
+        break;
+      }
+      case OP_NEG:
+        rule1([&](int j) { return -d[j]; });
+        t = -t;
+        break;
+      case OP_ABS:
+        rule1([&](int j) { return t < 0.0 ? -d[j] : d[j]; });
+        t = __builtin_fabs(t);
+        break;
       case OP_MIN: {
         const double a = pop();
-        t = t < a ? t : a;
+        const bool top = t < a;
+        rule2([&](int j) { return top ? d[j] : da[j]; });
+        t = top ? t : a;
         break;
       }
       case OP_MAX: {
         const double a = pop();
-        t = t > a ? t : a;
+        const bool top = t > a;
+        rule2([&](int j) { return top ? d[j] : da[j]; });
+        t = top ? t : a;
         break;
       }
-      case OP_LT: t = pop() < t ? 1.0 : 0.0; break;
-      case OP_LE: t = pop() <= t ? 1.0 : 0.0; break;
-      case OP_GT: t = pop() > t ? 1.0 : 0.0; break;
-      case OP_GE: t = pop() >= t ? 1.0 : 0.0; break;
+      case OP_LT: t = pop_value() < t ? 1.0 : 0.0; flat(); break;
+      case OP_LE: t = pop_value() <= t ? 1.0 : 0.0; flat(); break;
+      case OP_GT: t = pop_value() > t ? 1.0 : 0.0; flat(); break;
+      case OP_GE: t = pop_value() >= t ? 1.0 : 0.0; flat(); break;
       case OP_AND: {
-        const double a = pop();
+        const double a = pop_value();
         t = (a != 0.0 && t != 0.0) ? 1.0 : 0.0;
+        flat();
         break;
       }
       case OP_OR: {
-        const double a = pop();
+        const double a = pop_value();
         t = (a != 0.0 || t != 0.0) ? 1.0 : 0.0;
+        flat();
         break;
       }
-      case OP_NOT: t = t == 0.0 ? 1.0 : 0.0; break;
+      case OP_NOT: t = t == 0.0 ? 1.0 : 0.0; flat(); break;
       case OP_SELECT: {
-        const double a = pop(), c = pop();
-        t = c != 0.0 ? a : t;
+        const double a = pop(), c = pop_value();  // a condition carries no tangent
+        const bool first = c != 0.0;
+        rule2([&](int j) { return first ? da[j] : d[j]; });
+        t = first ? a : t;
         break;
       }
-      case OP_SQRT: t = ::sqrt(t); break;
-      case OP_SIN: t = ::sin(t); break;
-      case OP_COS: t = ::cos(t); break;
-      case OP_TAN: t = ::tan(t); break;
-      case OP_EXP: t = ::exp(t); break;
-      case OP_LOG: t = ::log(t); break;
-      case OP_TANH: t = ::tanh(t); break;
+      case OP_SQRT:
+        t = ::sqrt(t);
+        rule1([&](int j) { return div_rn(d[j], mul_rn(2.0, t)); });
+        break;
+      case OP_SIN: {
+        double c = 0.0;
+        if (any_live()) c = ::cos(t);
+        rule1([&](int j) { return mul_rn(c, d[j]); });
+        t = ::sin(t);
+        break;
+      }
+      case OP_COS: {
+        double c = 0.0;
+        if (any_live()) c = ::sin(t);
+        rule1([&](int j) { return -mul_rn(c, d[j]); });
+        t = ::cos(t);
+        break;
+      }
+      case OP_TAN: {
+        t = ::tan(t);
+        if constexpr (P > 0) {
+          const double g = add_rn(1.0, mul_rn(t, t));
+          rule1([&](int j) { return mul_rn(d[j], g); });
+        }
+        break;
+      }
+      case OP_EXP:
+        t = ::exp(t);
+        rule1([&](int j) { return mul_rn(t, d[j]); });
+        break;
+      case OP_LOG:
+        rule1([&](int j) { return div_rn(d[j], t); });
+        t = ::log(t);
+        break;
+      case OP_TANH: {
+        t = ::tanh(t);
+        if constexpr (P > 0) {
+          const double g = add_rn(1.0, -mul_rn(t, t));
+          rule1([&](int j) { return mul_rn(d[j], g); });
+        }
+        break;
+      }
       default:  // OP_STORE k: the validation admits no other opcode
-        store(k, t);
+        if constexpr (P > 0)
+          store(k, t, d);
+        else
+          store(k, t);
         --sp;
-        if (sp > 0) t = stk[(sp - 1) * kWalkThreads];
+        if (sp > 0) {
+          t = stk[(sp - 1) * W * kWalkThreads];
+#pragma unroll
+          for (int j = 0; j < P; ++j) d[j] = stk[((sp - 1) * W + 1 + j) * kWalkThreads];
+        }
         break;
     }
   }

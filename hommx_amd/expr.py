@@ -382,7 +382,7 @@ def _pairs(n: int) -> tuple:
     return tuple((a, b) for a in range(n) for b in range(a, n))
 
 
-def _run(ops, consts, n_comp: int, x, y, n_params: int = 0, n_fields: int = 0, second: bool = False) -> tuple:
+def _run(ops, consts, n_comp: int, x, y, n_params: int = 0, n_fields: int = 0, second: bool = False, seeds=None) -> tuple:
     """Interpret a program with NumPy on x[3 + n_fields, ...] (the midpoint, then the fields: ``X k`` reads row k) and y[d, ...]
     (broadcast against each other), in forward mode over its P = n_params + n_fields differentiable slots, the parameters, then the
     fields (``CONST k``, k < n_params, seeds slot k; ``X k``, k >= 3, slot ``n_params + k - 3``): (values[n_comp],
@@ -395,8 +395,17 @@ def _run(ops, consts, n_comp: int, x, y, n_params: int = 0, n_fields: int = 0, s
 
     ``second``: the second-order pass, k_expand_program2 -- a stack entry is (v, [d_j], [h_ij for (i, j) in _pairs(P)]), v and d are
     computed by the same statements, and the result is (values, tangents, second[n_comp][n_pairs]).  Its dead rule: h_ij is +0.0
-    (None) where every operand's h_ij is 0.0 and every operand's d_i, or every operand's d_j, is 0.0."""
-    P = n_params + n_fields
+    (None) where every operand's h_ij is 0.0 and every operand's d_i, or every operand's d_j, is 0.0.
+
+    ``seeds``: the rows of ``x`` that seed instead, as {row: slot} -- ``X row`` seeds slot ``seeds[row]``, every other read and every
+    constant seeds nothing, and P = 1 + the largest slot (the forward mode of csrc/state_program.h over the strain rows)."""
+    P = n_params + n_fields if seeds is None else 1 + max(seeds.values())
+    if seeds is None:
+        seed_const = lambda k, j: k == j and k < n_params
+        seed_x = lambda k, j: k >= 3 and j == n_params + k - 3
+    else:
+        seed_const = lambda k, j: False
+        seed_x = lambda k, j: seeds.get(k) == j
     pairs = _pairs(P) if second else ()
     stack, out_v, out_d, out_h = [], [None] * n_comp, [None] * n_comp, [None] * n_comp
     no_h = [None] * len(pairs)
@@ -430,10 +439,9 @@ def _run(ops, consts, n_comp: int, x, y, n_params: int = 0, n_fields: int = 0, s
 
     for op, k in ops:
         if op == OP_CONST:
-            stack.append((np.float64(consts[k]), [_ONE if (k == j and k < n_params) else None for j in range(P)], list(no_h)))
+            stack.append((np.float64(consts[k]), [_ONE if seed_const(k, j) else None for j in range(P)], list(no_h)))
         elif op == OP_X:
-            stack.append((np.asarray(x[k], dtype=np.float64), [_ONE if (k >= 3 and j == n_params + k - 3) else None for j in range(P)],
-                          list(no_h)))
+            stack.append((np.asarray(x[k], dtype=np.float64), [_ONE if seed_x(k, j) else None for j in range(P)], list(no_h)))
         elif op == OP_Y:
             stack.append((np.asarray(y[k], dtype=np.float64), [None] * P, list(no_h)))
         elif op == OP_DUP:
@@ -839,7 +847,10 @@ class SecantLaw:
     with one ``STORE k`` per component.  The limits of a program hold for all components together (128 instructions, 32 constants
     with the parameters first, depth 16), and the number of components must be the plan's ``n_comp``.
 
-    The iteration converges when s -> s a(s) is increasing (a monotone law); the consistent tangent is out of scope."""
+    The iteration converges when s -> s a(s) is increasing (a monotone law).  ``explicit``: the law reads no ``s[k]``; such a law has
+    a consistent tangent d sigma_H / d xi at its converged state (``host_tangent`` is the NumPy twin of the device's
+    tangent coefficient), which ``MicroCellPlan.secant_tangent`` and ``solve_nonlinear(method="newton")`` use.  The tangent of an
+    implicit law (one that reads ``s``) is out of scope."""
 
     def __init__(self, text=None, *, lam=None, mu=None, p=None, parameter_names=None, fields=None):
         if (lam is None) != (mu is None) or (text is None) == (lam is None):
@@ -941,6 +952,103 @@ class SecantLaw:
         with np.errstate(all="ignore"):
             out, _ = _run(ops.tolist(), consts, self.n_comp, rows, yr)
         return np.stack([np.array(np.broadcast_to(v, (N, n_el))) for v in out], axis=-1)
+
+    @property
+    def explicit(self) -> bool:
+        """Whether the law reads no ``s[k]``: its coefficient is then a function of the strain, and it has a consistent tangent."""
+        return self.state_indices["s"] == 0
+
+    def _entries(self, t: int) -> list:
+        """(r, c), r <= c, of every coefficient entry of a matrix (the ABI's order) or a Voigt law (upper triangle, row-major)."""
+        if self.shape == "matrix":
+            return [(0, 0), (1, 1), (0, 1)] if t == 2 else [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)]
+        return [(m, n) for m in range(t) for n in range(m, t)]
+
+    def _material(self, c, t: int) -> np.ndarray:
+        """C[..., t, t] = material(c[..., n_comp]) in the basis of the canonical loads, as csrc/mesh_elem.h forms it."""
+        c = np.asarray(c, dtype=np.float64)
+        C = np.zeros(c.shape[:-1] + (t, t))
+        if self.shape == "scalar":
+            for m in range(t):
+                C[..., m, m] = c[..., 0]
+        elif self.shape == "lame":
+            dim = 2 if t == 3 else 3
+            for m in range(t):
+                for n in range(t):
+                    C[..., m, n] = (c[..., 0] if m < dim and n < dim else 0.0) + ((2.0 * c[..., 1] if m < dim else c[..., 1]) if m == n else 0.0)
+        else:
+            for k, (r, q) in enumerate(self._entries(t)):
+                C[..., r, q] = C[..., q, r] = c[..., k]
+        return C
+
+    def _material_columns(self, e) -> list:
+        """g_k[..., t] = material(unit_k) e for every coefficient entry k, in the operation order of material_column (csrc/mesh_elem.h):
+        copies of entries of e and +0.0, except the Lame pair -- lambda: (e0 + e1) (+ e2, added last) on the normal rows; mu: 2 e[m]
+        on the normal rows, e[m] on the shear rows."""
+        e = np.asarray(e, dtype=np.float64)
+        t = e.shape[-1]
+        if self.shape == "scalar":
+            return [e.copy()]
+        if self.shape == "lame":
+            dim = 2 if t == 3 else 3
+            tr = e[..., 0] + e[..., 1]
+            if dim == 3:
+                tr = tr + e[..., 2]
+            g0, g1 = np.zeros_like(e), e.copy()
+            for m in range(dim):
+                g0[..., m] = tr
+                g1[..., m] = 2.0 * e[..., m]
+            return [g0, g1]
+        out = []
+        for r, q in self._entries(t):
+            g = np.zeros_like(e)
+            g[..., r] = e[..., q]
+            g[..., q] = e[..., r]
+            out.append(g)
+        return out
+
+    def host_tangent(self, e, cur, c, x, y=None, fields=None) -> tuple[np.ndarray, np.ndarray]:
+        """(T_sym[N, n_el, t, t], asymmetry[N]): the coefficient of the consistent tangent as the device forms it (csrc/secant_tangent.hip;
+        DESIGN 4.16) from e[N, n_el, t] (the strain of the stopping round), cur[N, n_el(, n_comp)] (the stream of that round,
+        ``SecantResult.coef``), c (the BASE stream) and x, y, fields as ``host_values`` takes them.  ``_run`` in forward mode with the
+        strain rows as seeds gives d_k[n] = dL_k/de[n]; then, in the order of the program's STOREs,
+        ``T[m][n] = T[m][n] + g_k[m] * d_k[n]`` from ``material(cur)``, the symmetric part ``0.5 * (T[m][n] + T[n][m])`` and
+        ``asymmetry = max |T - T^T| / max |T|`` per cell (0 when both are 0; a NaN never wins).  Bit for bit the device's
+        ``tangent_coef`` wherever the program holds exactly rounded operations only.  ``ValueError`` for a law that reads ``s[k]``."""
+        if not self.explicit:
+            raise ValueError(f"law: it reads s[{self.state_indices['s'] - 1}]: the consistent tangent takes an explicit law, one that "
+                             "reads no s[k]; an implicit law is out of scope")
+        e = np.asarray(e, dtype=np.float64)
+        N, n_el, t = e.shape
+        c = np.asarray(c, dtype=np.float64).reshape(N, n_el, -1)
+        cur = np.asarray(cur, dtype=np.float64).reshape(N, n_el, -1)
+        ops, consts = self.program(t, c.shape[2])
+        x = np.asarray(x, dtype=np.float64).reshape(N, -1)
+        x = np.concatenate([x, np.zeros((N, 3 - x.shape[1]))], axis=1) if x.shape[1] < 3 else x[:, :3]
+        if self.n_fields:
+            if fields is None:
+                raise ValueError(f"the law reads the fields {', '.join(self.field_names)}: pass fields[N, {self.n_fields}]")
+            fields = np.asarray(fields, dtype=np.float64).reshape(N, self.n_fields)
+        if self.n_y and (y is None or np.shape(y)[-1] < self.n_y):
+            raise ValueError(f"the law reads y[{self.n_y - 1}]: pass the element centroids y[n_el, d]")
+        rows = [x[:, k, None] for k in range(3)] + [fields[:, k, None] for k in range(self.n_fields)]
+        rows += [a[:, :, k] for a in (e, np.zeros_like(e), c) for k in range(a.shape[2])]
+        yr = [] if y is None else [np.asarray(y, dtype=np.float64)[None, :, k] for k in range(np.shape(y)[-1])]
+        base = 3 + self.n_fields
+        with np.errstate(all="ignore"):
+            _, dv = _run(ops.tolist(), consts, self.n_comp, rows, yr, seeds={base + n: n for n in range(t)})
+            T = self._material(cur, t)
+            g = self._material_columns(e)
+            for k in [int(k) for op, k in ops if op == OP_STORE]:
+                for n in range(t):
+                    d = np.broadcast_to(np.float64(0.0) if dv[k][n] is None else dv[k][n], (N, n_el))
+                    for m in range(t):
+                        T[:, :, m, n] = T[:, :, m, n] + g[k][:, :, m] * d
+            Tt = T.transpose(0, 1, 3, 2)
+            skew = np.fmax.reduce(np.abs(T - Tt).reshape(N, -1), axis=1, initial=0.0)
+            top = np.fmax.reduce(np.abs(T).reshape(N, -1), axis=1, initial=0.0)
+            asym = np.where((skew == 0.0) & (top == 0.0), 0.0, skew / np.where(top == 0.0, 1.0, top))
+        return 0.5 * (T + Tt), asym
 
 
 def _field_names(fields) -> tuple[int, tuple]:

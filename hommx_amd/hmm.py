@@ -327,6 +327,10 @@ class BaseHMM(ABC):
         self._bcs: list[fem.DirichletBC] = []
         self.secant: SecantResult | None = None  # solve_nonlinear: the last step's result per cell
         self.nonlinear_history: list[float] = []  # ... and the relative macro change of every step
+        self.tangent_tensors = None  # D = d sigma_H / d xi per macro cell of the last solve_nonlinear(method="newton")
+        self._linearisation_load = None  # P_T of the Newton step solve() is serving (solve_nonlinear sets and clears it)
+        self._tangent_plan = None  # the sibling plan of the tangent kind (solve_nonlinear(method="newton") builds and keeps it)
+        self._tangent_reserved = 0  # ... and the cells it is reserved for
         self._Dtheta_t = None
         self._plan: MicroCellPlan | None = None
         self._reserved_cells = 0
@@ -733,6 +737,8 @@ class BaseHMM(ABC):
         if n_cells and n_cells > self._reserved_cells:
             self._plan.reserve(int(n_cells))
             self._reserved_cells = int(n_cells)
+            if self._tangent_plan is not None:  # the sibling of solve_nonlinear(method="newton") follows every reservation
+                self._ensure_tangent_plan(self._plan)
         return self._plan
 
     def _local_cells(self) -> np.ndarray:
@@ -751,13 +757,16 @@ class BaseHMM(ABC):
         """Macro cells this rank solves (hmm.py:307-310)."""
         return len(self._local_cells())
 
-    def prepare(self) -> "BaseHMM":
+    def prepare(self, newton: bool = False) -> "BaseHMM":
         """Create the plan and allocate its device workspace for this rank's share of the macro cells now, so that the first
         ``solve()`` does not pay for it (not in the reference's API: there every PETSc object is made per solve, hmm.py:420-425).
         The kernel family depends on the coefficient's shape, which a plain callable only shows when sampled: one macro cell is
-        sampled for that."""
+        sampled for that.  ``newton``: the sibling plan of ``solve_nonlinear(method="newton")`` as well; once that plan exists
+        (built here or by the first Newton step) it is reserved with the plan, by this call and by ``reserve=True`` alike."""
         kind = self._micro_kind() if self._device_form() else self._element_means(np.array([0]))[1]
-        self._ensure_plan(kind, self._local_cell_count())
+        plan = self._ensure_plan(kind, self._local_cell_count())
+        if newton or self._tangent_plan is not None:
+            self._ensure_tangent_plan(plan)
         return self
 
     def _shard_device(self):
@@ -1015,17 +1024,23 @@ class BaseHMM(ABC):
         self._A = sp.coo_matrix((S.ravel(), (rows, cols)), shape=(N, N)).tocsr()
         self._needs_reassembly = False
 
+    def _add_cell_load(self, b: np.ndarray, P: np.ndarray):
+        """b += b_T = -vol(T)/vol(Y) (macro strains of the basis functions) . P[T] for a constant flux / stress P[N, t] per macro cell:
+        how the effective polarisation and the constant part of a linearised response enter the macro load."""
+        G, Wv = self._strain_basis(np.arange(self._msh.num_cells))
+        bT = -self._volume_ratio()[:, None] * np.einsum("cbm,cm->cb", G if Wv is None else Wv, P)
+        np.add.at(b, self._cell_dofs().ravel(), bT.ravel())
+
     def solve(self) -> fem.Function:
         """Assemble the LHS, RHS and solve the problem (hmm.py:434-491)."""
         self._assemble_stiffness()
         A = self._A.copy()
         b = fem.assemble_load_vector(self._V_macro, self._f, self._rhs_degree)
-        if self._polarisation is not None:  # b_T = -vol(T)/vol(Y) W P_eff[T], before the Dirichlet lifting
-            cells = np.arange(self._msh.num_cells)
-            self.effective_polarisation = self._effective_polarisation(cells)
-            G, Wv = self._strain_basis(cells)
-            bT = -self._volume_ratio()[:, None] * np.einsum("cbm,cm->cb", G if Wv is None else Wv, self.effective_polarisation)
-            np.add.at(b, self._cell_dofs().ravel(), bT.ravel())
+        if self._polarisation is not None:  # b_T of the effective polarisation, before the Dirichlet lifting
+            self.effective_polarisation = self._effective_polarisation(np.arange(self._msh.num_cells))
+            self._add_cell_load(b, self.effective_polarisation)
+        if self._linearisation_load is not None:  # ... and of a Newton step of solve_nonlinear: P_T = sigma_T - D_T xi_T
+            self._add_cell_load(b, self._linearisation_load)
         for bc in self._bcs:  # hmm.py:453-480, bc by bc
             idx, val = bc.unrolled()
             u_bc = np.zeros(self._num_global_dofs)
@@ -1162,19 +1177,42 @@ class BaseHMM(ABC):
         parts = self._chunks(cells, chunk_cells, bytes_per_cell, call, (lambda sub, kind: self._polarisation_loads(sub, kind)) if with_load else None)
         return _join(parts, cells=cells)
 
-    def _secant_tensors(self, cells: np.ndarray, xi: np.ndarray, law: SecantLaw, rows: np.ndarray, points: np.ndarray, chunk_cells, **kw) -> SecantResult:
-        """``plan.secant`` of ``law`` on ``cells`` under the macro strains ``xi``, chunk by chunk -> one ``SecantResult`` with ``cells``.
-        Under a process group every rank iterates its block and one all-gather of t t + t + 3 numbers per cell (and the info flags)
-        returns the fields to every rank, as ``_effective_polarisation`` does."""
+    def _ensure_tangent_plan(self, plan):
+        """The sibling plan of ``plan``'s tangent kind on the same micro mesh and device, built on first use and kept (a stale one
+        is closed), and reserved for as many cells as ``plan`` is: ``_ensure_plan`` passes every later reservation on."""
+        tp = self._tangent_plan
+        if tp is None or tp.kind != plan.tangent_kind:
+            if tp is not None:
+                tp.close()
+            if self._n_micro is None:
+                tp = MicroCellPlan.from_mesh(self._cell_mesh, plan.tangent_kind, device=plan.device)
+            else:
+                tp = MicroCellPlan(self._tdim, self._n_micro, plan.tangent_kind, device=plan.device)
+            self._tangent_plan, self._tangent_reserved = tp, 0
+        if self._reserved_cells > self._tangent_reserved:
+            tp.reserve(self._reserved_cells)
+            self._tangent_reserved = self._reserved_cells
+        return tp
+
+    def _secant_tensors(self, cells: np.ndarray, xi: np.ndarray, law: SecantLaw, rows: np.ndarray, points: np.ndarray, chunk_cells,
+                        tangent: bool = False, **kw) -> SecantResult:
+        """``plan.secant`` of ``law`` on ``cells`` under the macro strains ``xi``, chunk by chunk -> one ``SecantResult`` with ``cells``;
+        ``tangent``: ``plan.secant_tangent`` on the sibling plan instead, with ``tangent`` and ``asymmetry``.  Under a process group
+        every rank iterates its block and one all-gather of t t + t + 3 numbers per cell (2 t t + t + 4 with the tangent; and the info
+        flags) returns the fields to every rank, as ``_effective_polarisation`` does."""
         t = self._tensor_size()
 
         def bytes_per_cell():
-            out = 8 * (3 + t * t + t) + 4
+            out = 8 * (3 + t * t + t + (t * t + 1 if tangent else 0)) + 4
             return out if self._sampled_on_device() else out + self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) * 8
 
         def local(b, e):
-            call = lambda plan, coef, M, _, sub, at: plan.secant(coef, xi[b + at:b + at + len(sub)], law, M, rows=rows[b + at:b + at + len(sub)],
-                                                                points=points, **kw)
+            def call(plan, coef, M, _, sub, at):
+                args = dict(rows=rows[b + at:b + at + len(sub)], points=points, **kw)
+                if not tangent:
+                    return plan.secant(coef, xi[b + at:b + at + len(sub)], law, M, **args)
+                return plan.secant_tangent(coef, xi[b + at:b + at + len(sub)], law, self._ensure_tangent_plan(plan), M, **args)
+
             return _join(self._chunks(cells[b:e], chunk_cells, bytes_per_cell, call), cells=cells[b:e])
 
         if not self._sharded():
@@ -1183,15 +1221,21 @@ class BaseHMM(ABC):
 
         def block(b, e):
             r = local(b, e)
-            return np.concatenate([r.A_eff.reshape(e - b, t * t), r.mean_flux, r.rounds[:, None], r.change[:, None], r.status[:, None]], axis=1), r.info
+            more = [r.tangent.reshape(e - b, t * t), r.asymmetry[:, None]] if tangent else []
+            return np.concatenate([r.A_eff.reshape(e - b, t * t), r.mean_flux, r.rounds[:, None], r.change[:, None], r.status[:, None]] + more,
+                                  axis=1), r.info
 
         width = t * t + t + 3
-        packed, info = run_sharded(t, len(cells), block, device=self._shard_device(), shape=(width,))
-        return SecantResult(packed[:, :t * t].reshape(-1, t, t).copy(), packed[:, t * t:t * t + t].copy(), np.rint(packed[:, -3]).astype(np.int64),
-                            packed[:, -2].copy(), np.rint(packed[:, -1]).astype(np.int64), info, cells=cells)
+        packed, info = run_sharded(t, len(cells), block, device=self._shard_device(), shape=(width + (t * t + 1 if tangent else 0),))
+        out = SecantResult(packed[:, :t * t].reshape(-1, t, t).copy(), packed[:, t * t:t * t + t].copy(),
+                           np.rint(packed[:, width - 3]).astype(np.int64), packed[:, width - 2].copy(),
+                           np.rint(packed[:, width - 1]).astype(np.int64), info, cells=cells)
+        if tangent:
+            out.tangent, out.asymmetry = packed[:, width:width + t * t].reshape(-1, t, t).copy(), packed[:, -1].copy()
+        return out
 
     def solve_nonlinear(self, law: SecantLaw, max_iter: int = 30, tol: float = 1e-8, micro_iter: int = 50, micro_tol: float = 1e-10,
-                        relax: float = 1.0, field_values=None, u0=None, chunk_cells: int | None = None) -> fem.Function:
+                        relax: float = 1.0, field_values=None, u0=None, chunk_cells: int | None = None, method: str = "secant") -> fem.Function:
         """The two-scale problem with a strain-dependent micro coefficient ``law`` (a ``SecantLaw``: the entries of the coefficient of a
         micro element as expressions of its own strain ``e``, secant stress ``s`` and base coefficient ``c``, the solver's ``A``), by
         the Kacanov (secant) iteration on both scales.  u^0 is ``u0`` (a macro ``fem.Function`` or its dof array) or
@@ -1204,8 +1248,19 @@ class BaseHMM(ABC):
         Afterwards ``effective_tensors`` holds the secant tensors of the last step, ``secant`` its ``SecantResult`` (rounds, change,
         status, info and mean flux per cell), ``nonlinear_history`` the relative macro change of every step; the solver is marked for
         reassembly, so a later ``solve()`` is the linear one again.  One WARNING when the macro loop or any cell did not converge.
-        ``RuntimeError`` when a polarisation is set (loads beside a law are out of scope) or the law reads fields without
-        ``field_values``.  Out of scope as well: the consistent tangent and a macro Newton method, warm starts of the micro iteration
+
+        ``method="newton"`` (an explicit law, ``law.explicit``): per step the micro iteration of every box and, at the
+        state it stops in, the consistent tangent D_T = d sigma_T / d xi on a sibling plan of the tangent kind (hommx_secant_tangent_source;
+        the solver builds and keeps that plan); the macro matrix comes from D_T and the load from P_T = sigma_T - D_T xi_T, which enters
+        ``solve()`` where an effective polarisation does, so u^{k+1} solves the linearisation sigma_T + D_T (xi - xi_T): Newton's step,
+        with the same stopping rule and the same ``nonlinear_history``.  ``effective_tensors`` holds the secant tensors,
+        ``tangent_tensors`` D (NaN for a cell of status 2 or 3: such a cell enters the step with its secant tensor and no load, as it
+        does under ``"secant"``, and the status WARNING counts it).  One WARNING when the largest ``asymmetry`` exceeds 1e-8: the law then has no potential and the steps
+        are quasi-Newton steps with the symmetric part of the tangent.
+
+        ``RuntimeError`` when a polarisation is set (loads beside a law are out of scope), the law reads fields without
+        ``field_values``, or ``method="newton"`` meets a law that reads ``s[k]`` (the tangent of an implicit law is out of scope).
+        Out of scope as well: warm starts of the micro iteration
         across macro steps (``MicroCellPlan.secant(coef_start=...)`` has them), ``reconstruct()`` / ``criterion()`` of the nonlinear
         state (``MicroCellPlan.secant(return_coef=True)`` gives the stream to pass to them).  Under a process group every rank
         iterates its block of the cells, as in ``solve()``."""
@@ -1213,6 +1268,12 @@ class BaseHMM(ABC):
             raise RuntimeError("solve_nonlinear() does not take a polarisation or eigenstrain: loads beside a law are out of scope")
         if law.n_fields and field_values is None:
             raise RuntimeError(f"the law reads the fields {', '.join(law.field_names)}: pass field_values, their values per macro cell")
+        if method not in ("secant", "newton"):
+            raise ValueError(f"method must be 'secant' or 'newton'; got {method!r}")
+        newton = method == "newton"
+        if newton and not law.explicit:
+            raise RuntimeError(f"solve_nonlinear(method='newton') takes an explicit law; this one reads s[{law.state_indices['s'] - 1}] "
+                               "(the tangent of an implicit law is out of scope): use method='secant'")
         cells = np.arange(self._msh.num_cells)
         rows = self._msh.cell_midpoints()[cells]
         if law.n_fields:
@@ -1222,10 +1283,20 @@ class BaseHMM(ABC):
         history, converged, result = [], False, None
         for _ in range(int(max_iter)):
             xi = self._macro_strains(cells, u)
-            result = self._secant_tensors(cells, xi, law, rows, points, chunk_cells, max_iter=micro_iter, tol=micro_tol, relax=relax)
-            self._set_macro_matrix(self._local_stiffness_from_tensors(cells, result.A_eff))
+            result = self._secant_tensors(cells, xi, law, rows, points, chunk_cells, tangent=newton, max_iter=micro_iter, tol=micro_tol,
+                                          relax=relax)
+            matrix = result.A_eff
+            if newton:  # a cell without a state to linearise at (status 2, 3: its tangent is NaN) takes the secant step, as "secant" does
+                lost = (result.status >= 2)[:, None, None]
+                matrix = np.where(lost, result.A_eff, result.tangent)
+                self.tangent_tensors = result.tangent
+                self._linearisation_load = np.where(lost[:, :, 0], 0.0, result.mean_flux - np.einsum("cmn,cn->cm", matrix, xi))
+            self._set_macro_matrix(self._local_stiffness_from_tensors(cells, matrix))
             self.effective_tensors, self.cell_info = result.A_eff, result.info
-            new = self.solve().x.array.copy()
+            try:
+                new = self.solve().x.array.copy()
+            finally:
+                self._linearisation_load = None
             change, scale = float(np.abs(new - u).max()), float(np.abs(new).max())
             history.append(change / scale if scale > 0.0 else 0.0)
             u = new
@@ -1240,6 +1311,11 @@ class BaseHMM(ABC):
                 "solve_nonlinear: %s after %d macro steps (last relative change %.3e, tol %.3e); micro cells by status: %s",
                 "the macro loop did not converge" if not converged else "the macro loop converged, but not every cell did", len(history),
                 history[-1] if history else float("nan"), tol, ", ".join(f"{s}: {n}" for s, n in sorted(counts.items())))
+        worst = float(np.nanmax(result.asymmetry, initial=0.0)) if newton and result is not None else 0.0
+        if worst > 1e-8:
+            self._logger.warning(
+                "solve_nonlinear: the element tangents of the law are not symmetric (largest asymmetry %.3e): the law has no potential, "
+                "and the macro steps were quasi-Newton steps with the symmetric part of the tangent", worst)
         return self._u
 
     def _parameter_directions(self) -> tuple[tuple, np.ndarray]:

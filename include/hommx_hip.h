@@ -776,6 +776,48 @@ int hommx_secant_source_device(hommx_plan* plan, int64_t n_cells, const hommx_co
                                const hommx_secant_args* args, void* stream);
 
 /*
+ * The consistent tangent D = d sigma_H / d xi of the secant response, sigma_H(xi) = mean_flux, at the state the iteration stops in
+ * (DESIGN.md section 4.16).  The law must be EXPLICIT: it reads e, c, x, y, p and f but no entry of s (an `X` index in
+ * [3 + n_fields + t, 3 + n_fields + 2 t)).  With b_K the base coefficient and c_K = L(e_K, b_K) the converged one,
+ *   T_K[m][n] = material(c_K)[m][n] + sum_k g_k[m] dL_k/de[n],   g_k = material(unit_k) e_K,
+ * and D is A_eff of the LINEAR cell problem whose element coefficient is T_K, a full symmetric t x t matrix: a coefficient of
+ * HOMMX_KIND_POISSON_MATRIX for the Poisson kinds and of HOMMX_KIND_ELASTICITY_VOIGT for the elasticity kinds (the tangent kind).
+ * dL/de is the forward mode of the law over the strain, by the rules of hommx_expand_tangents, the dead rule included, accumulated
+ * at each STORE k as T[m][n] = add_rn(T[m][n], mul_rn(g_k[m], d_k[n])) from material(c_K).  The elimination needs a symmetric
+ * coefficient, and T_K is symmetric exactly when the law derives from a potential: the device writes the symmetric part
+ * mul_rn(0.5, add_rn(T[m][n], T[n][m])) and reports asymmetry = max_K |T - T^T| / max_K |T| of the cell (0 when both are 0), so a
+ * caller sees when D is the tangent of the symmetrised law only.
+ *
+ * Per chunk: the rounds of hommx_secant_source -- every output named in *secant has its bits --, one launch that forms the tangent
+ * stream of the chunk from the correctors the last round left, and one hommx_solve_batch_device of that stream on tangent_plan with
+ * the same M on the same stream.  A cell of status 2 or 3 gets the identity material in its tangent stream, asymmetry NaN and
+ * tangent NaN.
+ *
+ *   secant        the iteration, exactly as hommx_secant_source takes it
+ *   tangent_plan  a plan of the tangent kind with the dim, the micro mesh (n, or n_el and the nodes) and the device of `plan`; not `plan`
+ *   tangent       [n_cells][t][t], required: D;  asymmetry [n_cells], required
+ *   tangent_coef  [n_cells][n_el][t (t + 1) / 2] or NULL: the tangent stream, in the component order of the tangent kind
+ *   tangent_info  [n_cells] or NULL: info of the tangent elimination
+ * HOMMX_EINVAL, before the plan's device is made current: everything hommx_secant_source refuses; a null tangent_plan, tangent or
+ * asymmetry; a tangent plan of another kind, dim, size or device, or `plan` itself; a program that reads an s entry.  The tangent
+ * stream of a chunk (n_el t (t + 1) / 2 doubles per cell) counts as scratch of the chunk where tangent_coef is NULL.  The device
+ * entry reads nothing back: max_iter rounds, one tangent launch and one solve per chunk; the host entry gives the same bits.
+ */
+typedef struct hommx_secant_tangent_args {
+  const hommx_secant_args* secant;
+  hommx_plan* tangent_plan;
+  double* tangent;
+  double* asymmetry;
+  double* tangent_coef;
+  int32_t* tangent_info;
+} hommx_secant_tangent_args;
+int hommx_secant_tangent_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M,
+                                const hommx_secant_tangent_args* args);
+/* Same with DEVICE pointers (in *src, *args and *args->secant; the structs and the program are host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
+int hommx_secant_tangent_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                       const hommx_secant_tangent_args* args, void* stream);
+
+/*
  * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
  * periodic: the caller folds the mesh vertices into n_nodes independent (periodic) nodes -- cell_problem.py:38-300's slave -> master
  * map -- and passes, per element, the periodic node of every vertex and the UNFOLDED vertex coordinates (gradients and volumes).
