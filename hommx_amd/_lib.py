@@ -36,6 +36,7 @@ LOADS_SHARED, LOADS_PER_CELL, LOADS_PROGRAM = 0, 1, 2  # HOMMX_LOADS_*: per_cell
 LOADS_EIGENSTRAIN = 4  # HOMMX_LOADS_EIGENSTRAIN: a flag or-ed to them, what arrives is an eigenstrain
 CRIT_NSTATS = 4  # HOMMX_CRIT_NSTATS: max, argmax element, sum |K| v, sum |K| [v >= threshold]
 SECANT_NSTATE = 3  # HOMMX_SECANT_NSTATE: rounds, change, status
+SECANT_MAX_HISTORY = 4  # HOMMX_SECANT_MAX_HISTORY: the history variables of a law
 
 
 class PlanDesc(C.Structure):
@@ -227,6 +228,17 @@ class SecantTangentArgs(C.Structure):
     ]
 
 
+class HistoryArgs(C.Structure):
+    """hommx_history_args: the history variables of a law -- their number, the history at the start of the call and where the updates
+    of every cell's stopping round go."""
+
+    _fields_ = [
+        ("n_history", C.c_int32),
+        ("history_in", C.c_void_p),
+        ("history_out", C.c_void_p),
+    ]
+
+
 def _prototypes() -> dict:
     """name -> (restype, argtypes) of every symbol include/hommx_hip.h declares: ``load()`` declares them from this table, and
     the tests check that the header and the library export exactly these names."""
@@ -283,6 +295,12 @@ def _prototypes() -> dict:
         "hommx_secant_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantArgs), vp]),
         "hommx_secant_tangent_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantTangentArgs)]),
         "hommx_secant_tangent_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantTangentArgs), vp]),
+        "hommx_secant_history_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantArgs), C.POINTER(HistoryArgs)]),
+        "hommx_secant_history_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantArgs), C.POINTER(HistoryArgs), vp]),
+        "hommx_secant_tangent_history_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantTangentArgs),
+                                                        C.POINTER(HistoryArgs)]),
+        "hommx_secant_tangent_history_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantTangentArgs),
+                                                               C.POINTER(HistoryArgs), vp]),
         "hommx_solve_batch_two_phase": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_two_phase_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_separable": (c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),

@@ -238,7 +238,10 @@ class SecantResult:
     state (NaN for a cell of status 2 or 3), ``asymmetry[N]`` = max |T - T^T| / max |T| of the element tangents (0 for a law with a
     potential; D is then exact, otherwise it is the tangent of the symmetrised law; NaN for status 2 or 3), ``tangent_info[N]`` the
     info of the tangent elimination and, with ``return_tangent_coef``, ``tangent_coef[N, n_el, t (t + 1) / 2]``, the element stream
-    of the tangent kind that was eliminated."""
+    of the tangent kind that was eliminated.
+
+    For a law with history variables ``history[N, n_el, n_history]``: the updates of the stopping round -- the input's
+    bits for a cell of status 2 or 3 --, what the next load step takes as its ``history`` once the caller commits it."""
 
     A_eff: np.ndarray
     mean_flux: np.ndarray
@@ -255,6 +258,7 @@ class SecantResult:
     asymmetry: np.ndarray | None = None
     tangent_info: np.ndarray | None = None
     tangent_coef: np.ndarray | None = None
+    history: np.ndarray | None = None
 
 
 REGION_FIELDS = ("region_volume", "region_mean_strain", "region_mean_flux", "region_energy", "region_max_flux", "region_argmax_element")
@@ -856,7 +860,29 @@ class MicroCellPlan:
         ops, consts = law.program(self.t, self.n_comp)
         if law.n_y > self.dim:
             raise ValueError(f"the law reads y[{law.n_y - 1}]; the micro mesh has {self.dim} dimensions")
-        return Program(np.ascontiguousarray(ops), np.ascontiguousarray(consts), self.n_comp, int(law.n_params), int(law.n_fields))
+        return Program(np.ascontiguousarray(ops), np.ascontiguousarray(consts), self.n_comp + int(law.n_history), int(law.n_params),
+                       int(law.n_fields))
+
+    def _law_history(self, law, history, nc: int) -> np.ndarray | None:
+        """``history`` of ``secant`` / ``secant_tangent`` as float64[nc, n_el, n_history] (a copy), or None for a law without history
+        variables: [N, n_el, n_history], [N, n_el] for one variable, or a scalar / [n_history] broadcast as an initial state."""
+        nh = int(law.n_history)
+        if not nh:
+            if history is not None:
+                raise ValueError("the law has no history variables: history must be None")
+            return None
+        want = f"history[N_c, n_el, n_history] = ({nc}, {self.n_el}, {nh})" + (f", ({nc}, {self.n_el})" if nh == 1 else "") + \
+            f", a scalar or ({nh},) values as the initial state of every element"
+        if history is None:
+            raise ValueError(f"the law has the history variables {', '.join(law.history_names)}: pass {want}")
+        h = np.asarray(history, dtype=np.float64)
+        if h.shape == (nc, self.n_el) and nh == 1:
+            h = h[:, :, None]
+        elif h.shape in ((), (1,), (nh,)):
+            h = np.broadcast_to(h.reshape(-1), (nc, self.n_el, nh))
+        elif h.shape != (nc, self.n_el, nh):
+            raise ValueError(f"history has shape {h.shape}; expected {want}")
+        return np.array(h, dtype=np.float64, order="C")
 
     @staticmethod
     def _secant_limits(max_iter, tol, relax) -> tuple[int, float, float]:
@@ -870,7 +896,8 @@ class MicroCellPlan:
         return max_iter, tol, relax
 
     def secant(self, coef, xi: np.ndarray, law, M: np.ndarray | None = None, rows=None, points=None, max_iter: int = 50, tol: float = 1e-10,
-               relax: float = 1.0, coef_start=None, fields: bool = False, values: bool = False, return_coef: bool = False) -> SecantResult:
+               relax: float = 1.0, coef_start=None, fields: bool = False, values: bool = False, return_coef: bool = False,
+               history=None) -> SecantResult:
         """The secant iteration of a strain-dependent coefficient (hommx_secant_source): ``coef`` an array or a ``CoefStream``, the BASE
         coefficient ``c`` of the law; xi and M as ``reconstruct`` takes them; ``law`` a ``hommx_amd.expr.SecantLaw`` with the plan's
         ``n_comp`` components -> ``SecantResult``.  Per cell and round: the correctors of the current stream on the plan's route, the
@@ -881,8 +908,13 @@ class MicroCellPlan:
         law's own fields of every cell (required when the law reads ``f``; without them ``x`` is 0); ``points[n_el, dim]``: the
         element centroids, required when it reads ``y``; ``coef_start[N_c, n_el(, n_comp)]``: the stream the iteration starts from
         (default: the base stream), e.g. ``SecantResult.coef`` of a neighbouring macro strain.  The batch runs in the chunks of
-        ``reconstruct``; a load beside a law is out of scope."""
-        return self._secant(coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef)
+        ``reconstruct``; a load beside a law is out of scope.
+
+        ``history``: required for a law with history variables (hommx_secant_history_source) -- what ``h[k]`` reads, the
+        state at the start of the call, frozen for the whole iteration: ``[N_c, n_el, n_history]``, ``[N_c, n_el]`` for one variable,
+        or a scalar / ``[n_history]`` values broadcast as an initial state.  ``SecantResult.history`` is then the update of every
+        element at its cell's stopping round; the argument is not changed.  ``ValueError`` naming the expected shape otherwise."""
+        return self._secant(coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef, history=history)
 
     @property
     def tangent_kind(self) -> str:
@@ -907,20 +939,22 @@ class MicroCellPlan:
 
     def secant_tangent(self, coef, xi: np.ndarray, law, tangent_plan: "MicroCellPlan", M: np.ndarray | None = None, rows=None, points=None,
                        max_iter: int = 50, tol: float = 1e-10, relax: float = 1.0, coef_start=None, fields: bool = False,
-                       values: bool = False, return_coef: bool = False, return_tangent_coef: bool = False) -> SecantResult:
+                       values: bool = False, return_coef: bool = False, return_tangent_coef: bool = False, history=None) -> SecantResult:
         """``secant`` and, at the state every cell stops in, the consistent tangent D = d mean_flux / d xi (hommx_secant_tangent_source;
         DESIGN 4.16): the arguments of ``secant`` and ``tangent_plan``, a plan of ``self.tangent_kind`` on the same micro mesh and
         device (``MicroCellPlan(dim, n, plan.tangent_kind)`` or ``from_mesh`` of the same mesh).  Every member ``secant`` returns has
         its bits; ``tangent``, ``asymmetry``, ``tangent_info`` and, with ``return_tangent_coef``, ``tangent_coef`` come with them.
         The law must be explicit (``law.explicit``): ``ValueError`` naming the ``s[k]`` it reads otherwise, and for a ``tangent_plan``
-        of the wrong kind or shape."""
+        of the wrong kind or shape.  ``history``: as in ``secant`` (hommx_secant_tangent_history_source); the tangent is that of the
+        components at the frozen history, so a cell that unloads has ``tangent`` = ``A_eff``."""
         self._check_tangent(law, tangent_plan)
         return self._secant(coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef, tangent_plan,
-                            return_tangent_coef)
+                            return_tangent_coef, history)
 
     def _secant(self, coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef, tangent_plan=None,
-                return_tangent_coef=False) -> SecantResult:
-        """The host call of ``secant`` (``tangent_plan`` None) and ``secant_tangent``."""
+                return_tangent_coef=False, history=None) -> SecantResult:
+        """The host call of ``secant`` (``tangent_plan`` None) and ``secant_tangent``; with the history entries for a law that has
+        history variables."""
         stream = self._as_stream(coef)
         nc = self._check_stream(stream)
         xi = np.ascontiguousarray(xi, dtype=np.float64)
@@ -929,6 +963,9 @@ class MicroCellPlan:
         max_iter, tol, relax = self._secant_limits(max_iter, tol, relax)
         prog = self._law_program(law)
         pstruct = prog.struct()
+        hist_in = self._law_history(law, history, nc)
+        hist_out = None if hist_in is None else np.empty_like(hist_in)
+        hargs = None if hist_in is None else _lib.HistoryArgs(int(law.n_history), hist_in.ctypes.data, hist_out.ctypes.data)
         if rows is None:
             if law.n_fields:
                 raise ValueError(f"the law reads the fields {', '.join(law.field_names)}: pass rows[N_c, 3 + {law.n_fields}]")
@@ -957,10 +994,20 @@ class MicroCellPlan:
         args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows.ctypes.data, addr(points), xi.ctypes.data, max_iter, tol, relax,
                                addr(coef_start), state.ctypes.data, None, mean_flux.ctypes.data, addr(out_coef), addr(strain), addr(flux),
                                addr(vals), None)
-        if tangent_plan is None:
+        if tangent_plan is None and hargs is None:
             A, info = self._source_call("hommx_secant_source", nc, M, stream, args)
             return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
                                 strain, flux, vals)
+        if tangent_plan is None:
+            src = stream.coef_source()
+
+            def call(Mp, o, i):
+                args.A_eff, args.info = o, i
+                return self._lib.hommx_secant_history_source(self._h, nc, C.byref(src), Mp, C.byref(args), C.byref(hargs))
+
+            A, info = self._host_call("hommx_secant_history_source", nc, M, call)
+            return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
+                                strain, flux, vals, history=hist_out)
         D = np.empty((nc, self.t, self.t), dtype=np.float64)
         asym = np.empty(nc, dtype=np.float64)
         tinfo = np.zeros(nc, dtype=np.int32)
@@ -970,11 +1017,13 @@ class MicroCellPlan:
 
         def call(Mp, o, i):
             args.A_eff, args.info = o, i
+            if hargs is not None:
+                return self._lib.hommx_secant_tangent_history_source(self._h, nc, C.byref(src), Mp, C.byref(targs), C.byref(hargs))
             return self._lib.hommx_secant_tangent_source(self._h, nc, C.byref(src), Mp, C.byref(targs))
 
-        A, info = self._host_call("hommx_secant_tangent_source", nc, M, call)
+        A, info = self._host_call("hommx_secant_tangent_source" if hargs is None else "hommx_secant_tangent_history_source", nc, M, call)
         return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
-                            strain, flux, vals, None, D, asym, tinfo, tcoef)
+                            strain, flux, vals, None, D, asym, tinfo, tcoef, hist_out)
 
     def solve_two_phase(self, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None = None,
                         return_info: bool = False):
@@ -1165,21 +1214,41 @@ class MicroCellPlan:
                       A_ptr: int, points_ptr: int | None = None, max_iter: int = 50, tol: float = 1e-10, relax: float = 1.0,
                       coef_start_ptr: int | None = None, mean_flux_ptr: int | None = None, coef_ptr: int | None = None,
                       strain_ptr: int | None = None, flux_ptr: int | None = None, values_ptr: int | None = None, info_ptr: int | None = None,
-                      stream: int | None = None):
+                      stream: int | None = None, history_in_ptr: int | None = None, history_out_ptr: int | None = None):
         """Device-pointer form of ``secant`` (hommx_secant_source_device), asynchronous on ``stream``: ``source`` =
         ``CoefStream.coef_source(upload)`` with device addresses; ``law`` the ``SecantLaw`` (its program is host memory);
         rows[n_cells, 3 + law.n_fields], points[n_el, dim] (None: the law reads no ``y``) -> state[n_cells, 3] = [rounds | change |
         status] (doubles), A_eff[n_cells, t, t], mean_flux[n_cells, t], coef[n_cells, n_el, n_comp] (the stream A_eff belongs to),
         strain / flux[n_cells, n_el, t], values[n_cells, n_el, n_comp].  Exactly ``max_iter`` rounds per chunk are queued and nothing
-        is read back; the bits are those of ``secant``."""
+        is read back; the bits are those of ``secant``.  A law with history variables (hommx_secant_history_source_device) takes
+        ``history_in_ptr`` and ``history_out_ptr``, two different arrays [n_cells, n_el, n_history] on the device: a caller keeps the
+        history resident by swapping them between load steps."""
+        hargs = self._device_history(law, history_in_ptr, history_out_ptr)
         max_iter, tol, relax = self._secant_limits(max_iter, tol, relax)
         prog = self._law_program(law)
         pstruct = prog.struct()
         args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows_ptr, points_ptr or None, xi_ptr, max_iter, tol, relax,
                                coef_start_ptr or None, state_ptr, A_ptr, mean_flux_ptr or None, coef_ptr or None, strain_ptr or None,
                                flux_ptr or None, values_ptr or None, info_ptr or None)
+        if hargs is not None:
+            _lib.check(self._lib.hommx_secant_history_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
+                                                                    C.byref(hargs), stream or None), "hommx_secant_history_source_device")
+            return
         _lib.check(self._lib.hommx_secant_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
                    "hommx_secant_source_device")
+
+    @staticmethod
+    def _device_history(law, history_in_ptr, history_out_ptr):
+        """The ``HistoryArgs`` of a device call, None for a law without history variables; ``ValueError`` for pointers that do not go
+        with the law."""
+        if not law.n_history:
+            if history_in_ptr or history_out_ptr:
+                raise ValueError("the law has no history variables: history_in_ptr and history_out_ptr must be None")
+            return None
+        if not history_in_ptr or not history_out_ptr or history_in_ptr == history_out_ptr:
+            raise ValueError(f"the law has the history variables {', '.join(law.history_names)}: pass history_in_ptr and history_out_ptr, two "
+                             f"different device arrays [n_cells, n_el, {law.n_history}]")
+        return _lib.HistoryArgs(int(law.n_history), history_in_ptr, history_out_ptr)
 
     def secant_tangent_device(self, n_cells: int, source: "_lib.CoefSource", M_ptr: int | None, xi_ptr: int, law,
                               tangent_plan: "MicroCellPlan", rows_ptr: int, state_ptr: int, A_ptr: int, tangent_ptr: int, asymmetry_ptr: int,
@@ -1187,12 +1256,14 @@ class MicroCellPlan:
                               coef_start_ptr: int | None = None, mean_flux_ptr: int | None = None, coef_ptr: int | None = None,
                               strain_ptr: int | None = None, flux_ptr: int | None = None, values_ptr: int | None = None,
                               info_ptr: int | None = None, tangent_coef_ptr: int | None = None, tangent_info_ptr: int | None = None,
-                              stream: int | None = None):
+                              stream: int | None = None, history_in_ptr: int | None = None, history_out_ptr: int | None = None):
         """Device-pointer form of ``secant_tangent`` (hommx_secant_tangent_source_device), asynchronous on ``stream``: the pointers of
         ``secant_device`` and tangent[n_cells, t, t], asymmetry[n_cells], tangent_coef[n_cells, n_el, t (t + 1) / 2],
         tangent_info[n_cells] (int32).  Per chunk ``max_iter`` rounds, one tangent launch and one solve on ``tangent_plan`` are queued
-        and nothing is read back; the bits are those of ``secant_tangent``."""
+        and nothing is read back; the bits are those of ``secant_tangent``.  ``history_in_ptr`` / ``history_out_ptr``: as in
+        ``secant_device`` (hommx_secant_tangent_history_source_device)."""
         self._check_tangent(law, tangent_plan)
+        hargs = self._device_history(law, history_in_ptr, history_out_ptr)
         max_iter, tol, relax = self._secant_limits(max_iter, tol, relax)
         prog = self._law_program(law)
         pstruct = prog.struct()
@@ -1201,6 +1272,11 @@ class MicroCellPlan:
                                flux_ptr or None, values_ptr or None, info_ptr or None)
         targs = _lib.SecantTangentArgs(C.pointer(args), tangent_plan._h, tangent_ptr, asymmetry_ptr, tangent_coef_ptr or None,
                                        tangent_info_ptr or None)
+        if hargs is not None:
+            _lib.check(self._lib.hommx_secant_tangent_history_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None,
+                                                                            C.byref(targs), C.byref(hargs), stream or None),
+                       "hommx_secant_tangent_history_source_device")
+            return
         _lib.check(self._lib.hommx_secant_tangent_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(targs),
                                                                 stream or None), "hommx_secant_tangent_source_device")
 

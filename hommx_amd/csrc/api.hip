@@ -296,7 +296,8 @@ hommx_coef_source source_of_form(const hommx_coef_source& s) {
 // load_comp: 0 for the coefficient; the tensor size t of the plan for the program of a load (HOMMX_LOADS_PROGRAM), which has t
 // components on every kind.  state: 0, or the 2 t + n_comp state entries behind the fields in the row of a criterion
 // (hommx_criterion_args.program): one component on every kind, and of `s` only program and n_fields are read.  state_comp: the
-// components of a program on that row -- 1 for a criterion, the plan's n_comp for a law (hommx_secant_args.program)
+// components of a program on that row -- 1 for a criterion, the plan's n_comp for a law (hommx_secant_args.program), n_comp +
+// n_history for a law with history variables, whose row (`state`) is longer by n_history as well (hommx_history_args)
 int program_check(const hommx_plan* p, const hommx_coef_source* s, int load_comp = 0, int state = 0, int state_comp = 1) {
   if (!load_comp && !state && p->desc.kind == HOMMX_KIND_ELASTICITY_VOIGT)
     return fail(HOMMX_EINVAL, "expression coefficients are not supported for the 21-component Voigt kind");
@@ -317,6 +318,8 @@ int program_check(const hommx_plan* p, const hommx_coef_source* s, int load_comp
   if (g->n_comp != n_comp && state && state_comp == 1) return fail(HOMMX_EINVAL, "program: n_comp is %d, a criterion has one component", g->n_comp);
   if (g->n_comp != n_comp && load_comp)
     return fail(HOMMX_EINVAL, "program: n_comp is %d, a load of this plan has t = %d components", g->n_comp, n_comp);
+  if (g->n_comp != n_comp && state_comp > hommx::kind_sizes(p->desc.dim, p->desc.kind).n_comp)
+    return fail(HOMMX_EINVAL, "program: n_comp is %d, the plan's coefficient and the history have %d components together", g->n_comp, n_comp);
   if (g->n_comp != n_comp) return fail(HOMMX_EINVAL, "program: n_comp is %d, the plan's coefficient has %d components", g->n_comp, n_comp);
   if (!g->ops || (g->n_consts > 0 && !g->consts)) return fail(HOMMX_EINVAL, "null program ops / consts");
   if (!state) {  // a criterion is interpreted on the element's state: no quadrature rule, and its rows are the call's own argument
@@ -324,13 +327,17 @@ int program_check(const hommx_plan* p, const hommx_coef_source* s, int load_comp
     if (!s->table || !s->weights || !s->params) return fail(HOMMX_EINVAL, "null table / weights / params");
   }
   int depth = 0;
-  bool stored[std::max(hommx::PROGRAM_MAX_COMP, 21)] = {};  // a law stores every entry of the coefficient, 21 on the Voigt kind
+  // a law stores every entry of the coefficient, 21 on the Voigt kind, and the updates of its history variables behind them: 25
+  bool stored[std::max(hommx::PROGRAM_MAX_COMP, 21 + HOMMX_SECANT_MAX_HISTORY)] = {};
   for (int pc = 0; pc < g->n_ops; ++pc) {
     const int op = g->ops[2 * pc], k = g->ops[2 * pc + 1];
     if (op >= hommx::OP_COUNT) return fail(HOMMX_EINVAL, "program: unknown opcode %d at instruction %d", op, pc);
     if (op == hommx::OP_CONST && k >= g->n_consts)
       return fail(HOMMX_EINVAL, "program: constant index %d out of range [0,%d) at instruction %d", k, g->n_consts, pc);
     if (op == hommx::OP_X && k >= n_row) {
+      if (state && state_comp > hommx::kind_sizes(p->desc.dim, p->desc.kind).n_comp)
+        return fail(HOMMX_EINVAL, "program: x index %d out of range [0,%d) (the midpoint, %d fields and the 2 t + n_comp + n_history = %d "
+                                  "state entries) at instruction %d", k, n_row, s->n_fields, state, pc);
       if (state)
         return fail(HOMMX_EINVAL, "program: x index %d out of range [0,%d) (the midpoint, %d fields and the 2 t + n_comp = %d state entries) "
                                   "at instruction %d", k, n_row, s->n_fields, state, pc);
@@ -1682,8 +1689,11 @@ bool tangent_in_lds(const hommx_plan* p, int depth) {
 }
 int64_t tangent_stream_doubles(const hommx_plan* p) { return p->n_el * (p->ks.t * (p->ks.t + 1) / 2); }
 
+// hist: the history variables of the law (null: none, and every launch is the one it was) -- the rounds are k_secant_history's, reading
+// history_in and writing history_out of the chunk, and the tail is k_secant_tangent_history on the law truncated behind the last
+// component's STORE
 int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, const double* M, const hommx_secant_args& a, bool device,
-               hipStream_t st, const TangentTail* tail = nullptr) {
+               hipStream_t st, const TangentTail* tail = nullptr, const hommx_history_args* hist = nullptr) {
   const int t = p->ks.t, depth = program_depth(*a.program);
   const bool slot = !crit_in_lds(p, depth), tail_slot = tail && !tangent_in_lds(p, depth);
   const size_t stream = sizeof(double) * p->n_el * p->ks.n_comp;
@@ -1694,8 +1704,13 @@ int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, con
   double *cur = reinterpret_cast<double*>(at[0]), *cand = reinterpret_cast<double*>(at[1]);
   int32_t* info = a.info ? a.info : reinterpret_cast<int32_t*>(at[2]);
   HIP_TRY(hipMemcpyAsync(cur, a.coef_start ? a.coef_start : coef, stream * nc, hipMemcpyDeviceToDevice, st));
-  hommx::SecantArgs k;
+  hommx::SecantHistoryArgs k;  // without a history its SecantArgs alone is launched
   set_geometry(p, k);
+  if (hist) {
+    k.hist_in = hist->history_in;
+    k.hist_out = hist->history_out;
+    k.n_history = hist->n_history;
+  }
   k.base = coef;
   k.cur = cur;
   k.cand = cand;
@@ -1722,7 +1737,7 @@ int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, con
     k.corr = corr;
     k.slot = slot ? corr + chunk * t * k.ndof : nullptr;
     k.round = j;
-    HIP_TRY(hommx::launch_secant(k, depth, nc, st));
+    HIP_TRY(hist ? hommx::launch_secant_history(k, depth, nc, st) : hommx::launch_secant(k, depth, nc, st));
     if (device) continue;
     seen.resize(HOMMX_SECANT_NSTATE * nc);
     HIP_TRY(hipMemcpy(seen.data(), a.state, sizeof(double) * seen.size(), hipMemcpyDeviceToHost));
@@ -1732,7 +1747,7 @@ int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, con
   }
   if (a.coef_out) HIP_TRY(hipMemcpyAsync(a.coef_out, cur, stream * nc, hipMemcpyDeviceToDevice, st));
   if (!tail) return HOMMX_OK;
-  hommx::SecantTangentArgs g;
+  hommx::SecantTangentHistoryArgs g;  // likewise
   set_geometry(p, g);
   g.corr = corr;
   g.M = M;
@@ -1747,14 +1762,32 @@ int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, con
   g.tan = tail->coef ? tail->coef : reinterpret_cast<double*>(at[3]);
   g.asym = tail->asymmetry;
   g.slot = tail_slot ? corr + chunk * t * g.ndof : nullptr;
-  HIP_TRY(hommx::launch_secant_tangent(g, depth, nc, st));
+  if (hist) {
+    g.hist_in = hist->history_in;
+    g.n_history = hist->n_history;
+    for (int pc = 0; pc < a.program->n_ops; ++pc)  // the updates stand behind the last component's STORE
+      if (a.program->ops[2 * pc] == hommx::OP_STORE && a.program->ops[2 * pc + 1] < p->ks.n_comp) g.prog.n_ops = pc + 1;
+  }
+  HIP_TRY(hist ? hommx::launch_secant_tangent_history(g, depth, nc, st) : hommx::launch_secant_tangent(g, depth, nc, st));
   if (int rc = solve_source_device(tail->plan, nc, sampled_source(g.tan), M, tail->tangent, tail->info, st)) return rc;
   HIP_TRY(hommx::launch_tangent_mask(a.state, tail->tangent, t * t, nc, st));
   return HOMMX_OK;
 }
 
-// the checks of hommx_secant_args against the plan's descriptor
-int secant_checks(const hommx_plan* p, const hommx_secant_args* a) {
+// the checks of hommx_secant_args against the plan's descriptor; hist: the call is one of the history entries, whose struct is checked
+// first and whose program has n_history more components on a row as much longer
+int secant_checks(const hommx_plan* p, const hommx_secant_args* a, const hommx_history_args* const* hist = nullptr) {
+  int n_history = 0;
+  if (hist) {
+    const hommx_history_args* h = *hist;
+    if (!h) return fail(HOMMX_EINVAL, "null history arguments");
+    if (h->n_history < 1 || h->n_history > HOMMX_SECANT_MAX_HISTORY)
+      return fail(HOMMX_EINVAL, "n_history must be 1 .. %d, got %d", HOMMX_SECANT_MAX_HISTORY, h->n_history);
+    if (!h->history_in || !h->history_out) return fail(HOMMX_EINVAL, "null history_in / history_out");
+    if (h->history_in == h->history_out)
+      return fail(HOMMX_EINVAL, "history_in and history_out are the same array: the input is read in every round");
+    n_history = h->n_history;
+  }
   const hommx::KindSizes ks = hommx::kind_sizes(p->desc.dim, p->desc.kind);
   if (!a->program) return fail(HOMMX_EINVAL, "null program");
   if (!a->rows || !a->xi || !a->state || !a->A_eff) return fail(HOMMX_EINVAL, "null rows / xi / state / A_eff");
@@ -1762,7 +1795,7 @@ int secant_checks(const hommx_plan* p, const hommx_secant_args* a) {
   hommx_coef_source own{};  // what program_check reads of a source
   own.n_fields = a->n_fields;
   own.program = a->program;
-  if (int rc = program_check(p, &own, 0, 2 * ks.t + ks.n_comp, ks.n_comp)) return rc;
+  if (int rc = program_check(p, &own, 0, 2 * ks.t + ks.n_comp + n_history, ks.n_comp + n_history)) return rc;
   if (!a->points)
     for (int pc = 0; pc < a->program->n_ops; ++pc)
       if (a->program->ops[2 * pc] == hommx::OP_Y)
@@ -1774,28 +1807,39 @@ int secant_checks(const hommx_plan* p, const hommx_secant_args* a) {
 }
 
 // the argument checks of both entry points, then a route that forms correctors
-int secant_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_args* a, bool device) {
-  return source_open(p, n_cells, src, a, device, [&] { return secant_checks(p, a); });
+int secant_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_args* a, bool device,
+                const hommx_history_args* const* hist = nullptr) {
+  return source_open(p, n_cells, src, a, device, [&] { return secant_checks(p, a, hist); });
 }
+
+// the arguments of a call as the chunk driver re-bases them: the iteration's and the history's (n_history 0, null pointers: none)
+struct SecantCall {
+  hommx_secant_args s;
+  hommx_history_args h;
+};
 
 // The current and the candidate stream of a chunk, the info of its eliminations and the slot of a field that does not fit LDS beside the
 // stack (where the chunk rule of the reconstruction does not count one already) are scratch of the chunk
+// hist: history_in is a per-cell input and history_out a per-cell output of the chunk, counted as coef_start and coef_out are
 int secant_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_secant_args& args, bool device,
-                hipStream_t st) {
+                hipStream_t st, const hommx_history_args* hist = nullptr) {
   const int64_t t = p->ks.t, field = p->n_el * t, stream = p->n_el * p->ks.n_comp;
-  Chunk<hommx_secant_args> v{};
-  hommx_secant_args& a = v.a = args;
+  Chunk<SecantCall> v{};
+  v.a = SecantCall{args, hist ? *hist : hommx_history_args{}};
+  hommx_secant_args& a = v.a.s;
+  hommx_history_args& h = v.a.h;
   const bool own_slot = !crit_in_lds(p, program_depth(*a.program)) && recon_in_lds(p);
   const size_t scratch = sizeof(double) * (2 * stream + (own_slot ? plan_ndof(p) : 0)) + sizeof(int32_t);
   const CellArray in[] = {{&a.rows, hommx::program_row_doubles(a.n_fields)},
                           {&a.xi, t},
                           {&a.coef_start, stream},
+                          {&h.history_in, p->n_el * h.n_history},
                           {&a.points, p->n_el * p->desc.dim, SHARED}};
-  const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE}, {&a.A_eff, t * t, KEPT}, {&a.mean_flux, t},     {&a.coef_out, stream},
-                           {&a.strain, field},              {&a.flux, field},        {&a.law_values, stream}};
+  const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE}, {&a.A_eff, t * t, KEPT}, {&a.mean_flux, t},      {&a.coef_out, stream},
+                           {&a.strain, field},              {&a.flux, field},        {&a.law_values, stream}, {&h.history_out, p->n_el * h.n_history}};
   return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, recon_chunk, device, st,
-                      [&](int64_t nc, int64_t chunk, const Chunk<hommx_secant_args>& c) {
-                        return secant_run(p, nc, chunk, c.coef, c.M, c.a, device, st);
+                      [&](int64_t nc, int64_t chunk, const Chunk<SecantCall>& c) {
+                        return secant_run(p, nc, chunk, c.coef, c.M, c.a.s, device, st, nullptr, c.a.h.n_history ? &c.a.h : nullptr);
                       });
 }
 
@@ -1806,14 +1850,16 @@ struct SecantTangentCall {
   hommx_plan* plan;
   double *tangent, *asymmetry, *coef;
   int32_t* info;
+  hommx_history_args h;  // n_history 0, null pointers: none
 };
 
 // everything secant_open checks, then the tangent's own arguments against the descriptors of both plans alone (of a mesh plan, whose
 // descriptor has no size, the element and node counts as well)
-int secant_tangent_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_tangent_args* a, bool device) {
+int secant_tangent_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_tangent_args* a, bool device,
+                        const hommx_history_args* const* hist = nullptr) {
   auto checks = [&] {
     if (!a->secant) return fail(HOMMX_EINVAL, "null secant arguments");
-    if (int rc = secant_checks(p, a->secant)) return rc;
+    if (int rc = secant_checks(p, a->secant, hist)) return rc;
     const hommx_secant_args& s = *a->secant;
     const hommx::KindSizes ks = hommx::kind_sizes(p->desc.dim, p->desc.kind);
     if (!a->tangent_plan || !a->tangent || !a->asymmetry) return fail(HOMMX_EINVAL, "null tangent_plan / tangent / asymmetry");
@@ -1843,25 +1889,30 @@ int secant_tangent_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source*
 }
 
 int secant_tangent_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_secant_tangent_args& args,
-                        bool device, hipStream_t st) {
+                        bool device, hipStream_t st, const hommx_history_args* hist = nullptr) {
   const int64_t t = p->ks.t, field = p->n_el * t, stream = p->n_el * p->ks.n_comp, tan = tangent_stream_doubles(p);
   Chunk<SecantTangentCall> v{};
-  v.a = SecantTangentCall{*args.secant, args.tangent_plan, args.tangent, args.asymmetry, args.tangent_coef, args.tangent_info};
+  v.a = SecantTangentCall{*args.secant,      args.tangent_plan, args.tangent, args.asymmetry, args.tangent_coef,
+                          args.tangent_info, hist ? *hist : hommx_history_args{}};
   hommx_secant_args& a = v.a.s;
+  hommx_history_args& h = v.a.h;
   const int depth = program_depth(*a.program);
   const bool own_slot = (!crit_in_lds(p, depth) || !tangent_in_lds(p, depth)) && recon_in_lds(p);
   const size_t scratch = sizeof(double) * (2 * stream + (own_slot ? plan_ndof(p) : 0) + (args.tangent_coef ? 0 : tan)) + sizeof(int32_t);
   const CellArray in[] = {{&a.rows, hommx::program_row_doubles(a.n_fields)},
                           {&a.xi, t},
                           {&a.coef_start, stream},
+                          {&h.history_in, p->n_el * h.n_history},
                           {&a.points, p->n_el * p->desc.dim, SHARED}};
-  const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE}, {&a.A_eff, t * t, KEPT}, {&a.mean_flux, t},     {&a.coef_out, stream},
-                           {&a.strain, field},              {&a.flux, field},        {&a.law_values, stream}, {&v.a.tangent, t * t},
-                           {&v.a.asymmetry, 1},             {&v.a.coef, tan},        {&v.a.info, 1, PER_CELL, sizeof(int32_t)}};
+  const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE}, {&a.A_eff, t * t, KEPT}, {&a.mean_flux, t},
+                           {&a.coef_out, stream},           {&a.strain, field},      {&a.flux, field},
+                           {&a.law_values, stream},         {&v.a.tangent, t * t},   {&v.a.asymmetry, 1},
+                           {&v.a.coef, tan},                {&v.a.info, 1, PER_CELL, sizeof(int32_t)},
+                           {&h.history_out, p->n_el * h.n_history}};
   return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, recon_chunk, device, st,
                       [&](int64_t nc, int64_t chunk, const Chunk<SecantTangentCall>& c) {
                         const TangentTail tail{c.a.plan, c.a.tangent, c.a.asymmetry, c.a.coef, c.a.info};
-                        return secant_run(p, nc, chunk, c.coef, c.M, c.a.s, device, st, &tail);
+                        return secant_run(p, nc, chunk, c.coef, c.M, c.a.s, device, st, &tail, c.a.h.n_history ? &c.a.h : nullptr);
                       });
 }
 
@@ -2046,6 +2097,30 @@ int hommx_secant_tangent_source(hommx_plan* p, int64_t n_cells, const hommx_coef
                                 const hommx_secant_tangent_args* args) {
   if (int rc = secant_tangent_open(p, n_cells, src, args, false); rc != GO) return rc;
   return secant_tangent_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
+}
+
+int hommx_secant_history_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                       const hommx_secant_args* args, const hommx_history_args* history, void* stream) {
+  if (int rc = secant_open(p, n_cells, src, args, true, &history); rc != GO) return rc;
+  return secant_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream), history);
+}
+
+int hommx_secant_history_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_secant_args* args,
+                                const hommx_history_args* history) {
+  if (int rc = secant_open(p, n_cells, src, args, false, &history); rc != GO) return rc;
+  return secant_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr, history);
+}
+
+int hommx_secant_tangent_history_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                               const hommx_secant_tangent_args* args, const hommx_history_args* history, void* stream) {
+  if (int rc = secant_tangent_open(p, n_cells, src, args, true, &history); rc != GO) return rc;
+  return secant_tangent_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream), history);
+}
+
+int hommx_secant_tangent_history_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M,
+                                        const hommx_secant_tangent_args* args, const hommx_history_args* history) {
+  if (int rc = secant_tangent_open(p, n_cells, src, args, false, &history); rc != GO) return rc;
+  return secant_tangent_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr, history);
 }
 
 int hommx_second_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,

@@ -251,6 +251,14 @@ struct SecantArgs : ElemWalk {
 };
 // dynamic LDS as k_criterion's (criterion_lds_bytes); depth: the maximal stack depth of the (validated) program
 hipError_t launch_secant(const SecantArgs& a, int depth, long long nc, hipStream_t stream);
+// the same round for a law with history variables (hommx_secant_history_source): prog stores n_comp + n_history
+// values, and its row is longer by the n_history entries h reads
+struct SecantHistoryArgs : SecantArgs {
+  const double* hist_in = nullptr;   // [nc][n_el][n_history]: what h[k] reads in every round, the history at the start of the call
+  double* hist_out = nullptr;        // [nc][n_el][n_history]: the updates of the stopping round; hist_in's bits for status 2 or 3
+  int n_history = 0;                 // 1 .. HOMMX_SECANT_MAX_HISTORY
+};
+hipError_t launch_secant_history(const SecantHistoryArgs& a, int depth, long long nc, hipStream_t stream);
 
 // secant_tangent.hip: the coefficient of the consistent tangent of the secant response on `nc` cells whose iteration has ended
 // (include/hommx_hip.h, hommx_secant_tangent_source): T_K = material(cur_K) + sum_k g_k (dL_k/de)^T, its
@@ -277,6 +285,13 @@ int secant_tangent_slots(int t, int depth);
 // stack[depth - 1][1 + P][kWalkThreads]
 size_t secant_tangent_lds_bytes(long long ndof, int depth, int slots);
 hipError_t launch_secant_tangent(const SecantTangentArgs& a, int depth, long long nc, hipStream_t stream);
+// the same for a law with history variables: prog is the law TRUNCATED behind the last component's STORE (the updates are not
+// differentiated, and nothing is written to a history), and h[k] reads hist_in
+struct SecantTangentHistoryArgs : SecantTangentArgs {
+  const double* hist_in = nullptr;   // [nc][n_el][n_history]
+  int n_history = 0;
+};
+hipError_t launch_secant_tangent_history(const SecantTangentHistoryArgs& a, int depth, long long nc, hipStream_t stream);
 // tangent[cell][tt] = NaN for every cell whose status (state[cell][2]) is 2 or 3
 hipError_t launch_tangent_mask(const double* state, double* tangent, int tt, long long nc, hipStream_t stream);
 

@@ -34,15 +34,18 @@ __device__ constexpr int tangent_entry(int m, int n) {
   return m == n ? m : T + (m + n - 1);
 }
 
-template <int DIM, int KIND, bool MESH, int P>
-__global__ __launch_bounds__(kWalkThreads) void k_secant_tangent(SecantTangentArgs A) {
+// The tangent coefficient of one cell, the body of k_secant_tangent (HIST false: hist_in and n_history are not read) and of
+// k_secant_tangent_history, whose law reads h[k] from hist_in[cell][el][n_history]; the program is then the
+// law truncated behind the last component's STORE, so every STORE is a component's.  lds_dyn: [the field (ndof), unless it lies in
+// the slot | stack[depth - 1][1 + P][kWalkThreads]]; red_max: the reduction rows, the kernel's static LDS
+template <int DIM, int KIND, bool MESH, int P, bool HIST>
+__device__ __forceinline__ void secant_tangent_cell(const SecantTangentArgs& A, double* lds_dyn, double (*red_max)[2],
+                                                    const double* __restrict__ hist_in, int n_history) {
 #pragma clang fp contract(off)
   constexpr KindSizes ks = kind_sizes(DIM, KIND);
   constexpr int T = ks.t, BS = ks.bs, NCOMP = ks.n_comp, NTAN = T * (T + 1) / 2;
   constexpr bool VOIGT = KIND >= 2;
   static_assert(T % P == 0, "the sweeps tile the t strain entries");
-  extern __shared__ double lds_dyn[];  // [the field (ndof), unless it lies in the slot | stack[depth - 1][1 + P][kWalkThreads]]
-  __shared__ double red_max[kWalkWaves][2];
   const int tid = threadIdx.x;
   const long long cell = blockIdx.x;
   const long long ndof = A.ndof;
@@ -114,17 +117,19 @@ __global__ __launch_bounds__(kWalkThreads) void k_secant_tangent(SecantTangentAr
       for (int m = 0; m < T; ++m)
 #pragma unroll
         for (int j = 0; j < P; ++j) col[m][j] = material_entry<DIM, KIND>(cu, m, off + j);
-      run_state_program<T, P>(
-          A.prog, A.n_fields, x, row, e, q, A.base + stream + el * NCOMP, A.points + el * DIM, stk,
-          [&](int k, double, const double(&d)[P]) {
-            double g[T];
-            material_column<DIM, KIND>(k, e, g);
+      auto store = [&](int k, double, const double(&d)[P]) {
+        double g[T];
+        material_column<DIM, KIND>(k, e, g);
 #pragma unroll
-            for (int m = 0; m < T; ++m)
+        for (int m = 0; m < T; ++m)
 #pragma unroll
-              for (int j = 0; j < P; ++j) col[m][j] = add_rn(col[m][j], mul_rn(g[m], d[j]));
-          },
-          off);
+          for (int j = 0; j < P; ++j) col[m][j] = add_rn(col[m][j], mul_rn(g[m], d[j]));
+      };
+      if constexpr (HIST)
+        run_state_program<T, P, true>(A.prog, A.n_fields, x, row, e, q, A.base + stream + el * NCOMP, A.points + el * DIM, stk, store, off,
+                                      hist_in + (cell * A.n_el + el) * n_history, NCOMP);
+      else
+        run_state_program<T, P>(A.prog, A.n_fields, x, row, e, q, A.base + stream + el * NCOMP, A.points + el * DIM, stk, store, off);
       // Column n = off + j against the columns before it.  An entry below the diagonal is parked, raw, in the place of its pair in the
       // stream; when the column of that pair comes -- later in this sweep or in a later one, the same thread either way -- it is read
       // back and the symmetric part takes its place.  col is indexed by constants; what depends on the offset is an address
@@ -152,6 +157,20 @@ __global__ __launch_bounds__(kWalkThreads) void k_secant_tangent(SecantTangentAr
   if (tid == 0) A.asym[cell] = mx[0] == 0.0 && mx[1] == 0.0 ? 0.0 : div_rn(mx[0], mx[1]);
 }
 
+template <int DIM, int KIND, bool MESH, int P>
+__global__ __launch_bounds__(kWalkThreads) void k_secant_tangent(SecantTangentArgs A) {
+  extern __shared__ double lds_dyn[];
+  __shared__ double red_max[kWalkWaves][2];
+  secant_tangent_cell<DIM, KIND, MESH, P, false>(A, lds_dyn, red_max, nullptr, 0);
+}
+
+template <int DIM, int KIND, bool MESH, int P>
+__global__ __launch_bounds__(kWalkThreads) void k_secant_tangent_history(SecantTangentHistoryArgs A) {
+  extern __shared__ double lds_dyn[];
+  __shared__ double red_max[kWalkWaves][2];
+  secant_tangent_cell<DIM, KIND, MESH, P, true>(A, lds_dyn, red_max, A.hist_in, A.n_history);
+}
+
 __global__ void k_tangent_mask(const double* __restrict__ state, double* __restrict__ tangent, int tt, long long total) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
@@ -173,13 +192,11 @@ int secant_tangent_slots(int t, int depth) {
   return secant_tangent_lds_bytes(0, depth, native) <= recon_lds_limit() ? native : 1;
 }
 
-hipError_t launch_secant_tangent(const SecantTangentArgs& a, int depth, long long nc, hipStream_t st) {
-  if (nc <= 0) return hipSuccess;
-  if (depth < 1 || depth > PROGRAM_MAX_STACK) return hipErrorInvalidValue;
-  const int slots = secant_tangent_slots(kind_sizes(a.dim, a.kind).t, depth);
-  const auto kernel =
-      slots > 1 ? walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_secant_tangent<D(), K(), MESH(), native_slots(kind_sizes(D(), K()).t)>; })
-                : walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_secant_tangent<D(), K(), MESH(), 1>; });
+namespace {
+
+// the launch of `kernel`, the instantiation of `slots` slots per sweep
+template <typename Args, typename Kernel>
+hipError_t launch_tangent(const Args& a, Kernel kernel, int slots, int depth, long long nc, hipStream_t st) {
   const size_t lds = secant_tangent_lds_bytes(a.slot ? 0 : a.ndof, depth, slots);
   if (lds > recon_lds_limit()) return hipErrorInvalidValue;  // the caller places the field in the slot where it does not fit
   if (lds > 48 * 1024) {
@@ -187,6 +204,31 @@ hipError_t launch_secant_tangent(const SecantTangentArgs& a, int depth, long lon
     if (e != hipSuccess) return e;
   }
   return launch_walk(a, nc, st, kernel, lds);
+}
+
+}  // namespace
+
+hipError_t launch_secant_tangent(const SecantTangentArgs& a, int depth, long long nc, hipStream_t st) {
+  if (nc <= 0) return hipSuccess;
+  if (depth < 1 || depth > PROGRAM_MAX_STACK) return hipErrorInvalidValue;
+  const int slots = secant_tangent_slots(kind_sizes(a.dim, a.kind).t, depth);
+  const auto kernel =
+      slots > 1 ? walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_secant_tangent<D(), K(), MESH(), native_slots(kind_sizes(D(), K()).t)>; })
+                : walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_secant_tangent<D(), K(), MESH(), 1>; });
+  return launch_tangent(a, kernel, slots, depth, nc, st);
+}
+
+hipError_t launch_secant_tangent_history(const SecantTangentHistoryArgs& a, int depth, long long nc, hipStream_t st) {
+  if (nc <= 0) return hipSuccess;
+  if (depth < 1 || depth > PROGRAM_MAX_STACK || a.n_history < 1 || a.n_history > HOMMX_SECANT_MAX_HISTORY || !a.hist_in)
+    return hipErrorInvalidValue;
+  const int slots = secant_tangent_slots(kind_sizes(a.dim, a.kind).t, depth);
+  const auto kernel =
+      slots > 1 ? walk_kernel(a, [](auto D, auto K, auto MESH) {
+        return &k_secant_tangent_history<D(), K(), MESH(), native_slots(kind_sizes(D(), K()).t)>;
+      })
+                : walk_kernel(a, [](auto D, auto K, auto MESH) { return &k_secant_tangent_history<D(), K(), MESH(), 1>; });
+  return launch_tangent(a, kernel, slots, depth, nc, st);
 }
 
 hipError_t launch_tangent_mask(const double* state, double* tangent, int tt, long long nc, hipStream_t st) {

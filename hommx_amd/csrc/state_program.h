@@ -52,10 +52,16 @@ __device__ __forceinline__ double pick(int j, const double (&a)[T]) {
 // and its tangent rule, those of the table in DESIGN.md section 3 (hommx_amd/expr.py, _TANGENT), the dead rule included: d_j of a
 // result is +0.0 where every operand's d_j is 0.0, and the formula is then not evaluated.  The value statements do not read a tangent,
 // so v is the value pass's bit for bit in every sweep.  store(k, v, d) then.  P = 0 declares no tangent and is the value pass
-template <int T, int P = 0, typename Store>
+//
+// HIST: the law has history variables.  The row is longer by them: an `X` index at or above
+// base + 2 T + n_comp is h[k], a vector load from he, the element's history row, where it is read, as c[k] is; it seeds nothing.
+// n_comp: the entries of ce (uniform).  What a STORE k, k >= n_comp, does is the caller's.  Without HIST neither is read, and the
+// instantiation is the one it was
+template <int T, int P = 0, bool HIST = false, typename Store>
 __device__ __forceinline__ void run_state_program(const ProgramArgs& prog, int n_fields, const double (&x)[3], const double* __restrict__ row,
                                                   const double (&e)[T], const double (&s)[T], const double* __restrict__ ce,
-                                                  const double* __restrict__ yk, double* __restrict__ stk, Store&& store, int seed0 = 0) {
+                                                  const double* __restrict__ yk, double* __restrict__ stk, Store&& store, int seed0 = 0,
+                                                  const double* __restrict__ he = nullptr, int n_comp = 0) {
 #pragma clang fp contract(off)
   constexpr int PN = P ? P : 1, W = 1 + P;  // PN: no array of length zero; W: the doubles of a stack entry
   const int n_ops = prog.n_ops, base = program_row_doubles(n_fields);
@@ -129,8 +135,10 @@ __device__ __forceinline__ void run_state_program(const ProgramArgs& prog, int n
           for (int j = 0; j < P; ++j) d[j] = k - base == seed0 + j ? 1.0 : 0.0;
         } else if (k < base + 2 * T) {
           t = pick<T>(k - base - T, s);
-        } else {
+        } else if (!HIST || k < base + 2 * T + n_comp) {
           t = ce[k - base - 2 * T];
+        } else {
+          if constexpr (HIST) t = he[k - base - 2 * T - n_comp];
         }
         break;
       case OP_Y:

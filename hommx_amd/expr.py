@@ -40,6 +40,7 @@ MAX_POWER = 8
 MAX_PARAMS = 4  # HOMMX_PROGRAM_MAX_PARAMS
 MAX_FIELDS = 4  # HOMMX_PROGRAM_MAX_FIELDS
 MAX_LAW_COMP = 21  # the components of a SecantLaw: the entries of the coefficient of an element, 21 on the 3D Voigt kind
+MAX_HISTORY = 4  # HOMMX_SECANT_MAX_HISTORY: the history variables h[k] of a SecantLaw
 
 _BINARY = {ast.Add: OP_ADD, ast.Sub: OP_SUB, ast.Mult: OP_MUL, ast.Div: OP_DIV}
 _COMPARE = {ast.Lt: OP_LT, ast.LtE: OP_LE, ast.Gt: OP_GT, ast.GtE: OP_GE}
@@ -89,10 +90,11 @@ MAX_STATE_INDEX = 20  # the largest index a state name can have on any plan (c[2
 class _Context:
     """What the components of one Expression share while they are checked: the number of parameters (None: no ``p=``), of fields
     (None: no ``fields=``) and the texts of the comparisons that read one.  ``state``: the text is a ``Criterion``'s, which also
-    reads the element's strain ``e[k]``, flux ``s[k]`` and coefficient ``c[k]``."""
+    reads the element's strain ``e[k]``, flux ``s[k]`` and coefficient ``c[k]``.  ``n_history``: the history variables ``h[k]`` of a
+    ``SecantLaw`` (None: no ``history=``)."""
 
-    def __init__(self, n_params=None, n_fields=None, state=False):
-        self.n_params, self.n_fields, self.compared, self.state = n_params, n_fields, [], state
+    def __init__(self, n_params=None, n_fields=None, state=False, n_history=None):
+        self.n_params, self.n_fields, self.compared, self.state, self.n_history = n_params, n_fields, [], state, n_history
 
 
 def _number(node, value) -> _Node:
@@ -128,6 +130,12 @@ def _check(node, ctx: _Context) -> _Node:
             if not _literal_int(node.slice, 0, MAX_STATE_INDEX):
                 raise _bad(node, f"the index of {node.value.id} is a literal integer 0 .. {MAX_STATE_INDEX}")
             return _Node(_STATE, value=(node.value.id, int(node.slice.value)), degree=1, varying=True)
+        if ctx.state and isinstance(node.value, ast.Name) and node.value.id == "h":
+            if ctx.n_history is None:
+                raise _bad(node, "h[k] needs the updates of the history variables (history=[...])")
+            if not _literal_int(node.slice, 0, ctx.n_history - 1):
+                raise _bad(node, f"the index of h is a literal integer below the number of history variables ({ctx.n_history})")
+            return _Node(_STATE, value=("h", int(node.slice.value)), degree=1, varying=True)
         if not (isinstance(node.value, ast.Name) and node.value.id in ("x", "y")):
             raise _bad(node, "only x and y are indexed")
         if not _literal_int(node.slice, 0, 2):
@@ -850,11 +858,42 @@ class SecantLaw:
     The iteration converges when s -> s a(s) is increasing (a monotone law).  ``explicit``: the law reads no ``s[k]``; such a law has
     a consistent tangent d sigma_H / d xi at its converged state (``host_tangent`` is the NumPy twin of the device's
     tangent coefficient), which ``MicroCellPlan.secant_tangent`` and ``solve_nonlinear(method="newton")`` use.  The tangent of an
-    implicit law (one that reads ``s``) is out of scope."""
+    implicit law (one that reads ``s``) is out of scope.
 
-    def __init__(self, text=None, *, lam=None, mu=None, p=None, parameter_names=None, fields=None):
+    History variables: ``history=[text_0, ...]`` gives the law 1 .. ``MAX_HISTORY`` internal variables per micro
+    element, named ``history_names`` (default ``h0, h1, ...``) and starting from ``history_initial`` (a scalar or one value per
+    variable).  ``h[k]`` is then a state name of every component text and every update text: the element's value at the START of the
+    call, frozen for the whole iteration.  ``history[i]`` is the update, the new value of ``h[i]`` at the state of a round; what the
+    stopping round gives is the call's ``history`` output, and the caller decides when it becomes the state (``commit_history`` of
+    the solver classes).  The row grows by the history, ``[... | c (n_comp) | h (n_history)]``, and the update code stands behind
+    the component code with ``STORE n_comp + i``; the limits hold for everything together.  ``explicit`` counts the updates too; the
+    tangent differentiates the components only, on the program truncated behind the last component's ``STORE`` (``n_law_ops``)."""
+
+    def __init__(self, text=None, *, lam=None, mu=None, p=None, parameter_names=None, fields=None, history=None, history_names=None,
+                 history_initial=0.0):
         if (lam is None) != (mu is None) or (text is None) == (lam is None):
             raise ValueError("SecantLaw(text), SecantLaw([[a, b], [b, c]]), SecantLaw([c0, c1, ...]) or SecantLaw(lam=..., mu=...)")
+        if history is None:
+            if history_names is not None:
+                raise ValueError("law: history_names without history=[...]")
+            updates = []
+        else:
+            updates = [history] if isinstance(history, (str, int, float)) and not isinstance(history, bool) else list(history)
+            if not 1 <= len(updates) <= MAX_HISTORY:
+                raise ValueError(f"law: history has 1 .. {MAX_HISTORY} update texts; got {len(updates)}")
+        self.n_history = len(updates)
+        if history_names is None:
+            history_names = tuple(f"h{k}" for k in range(self.n_history))
+        self.history_names = tuple(str(s) for s in history_names)
+        if len(self.history_names) != self.n_history:
+            raise ValueError(f"law: {len(self.history_names)} history_names for {self.n_history} history variables")
+        try:
+            initial = np.array(history_initial, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            initial = np.zeros(0)
+        if initial.size not in (1, self.n_history) or not np.all(np.isfinite(initial)):
+            raise ValueError(f"law: history_initial is one finite number or one per history variable ({self.n_history}); got {history_initial!r}")
+        self.history_initial = np.broadcast_to(initial, (self.n_history,)).copy()
         values = _parameter_values(p, None) if p is not None else np.zeros(0)
         self.n_params = int(values.size)
         if parameter_names is None:
@@ -864,7 +903,8 @@ class SecantLaw:
             raise ValueError(f"law: {len(self.parameter_names)} parameter_names for {self.n_params} parameters")
         self.n_fields, self.field_names = _field_names(fields)
         self.dim = None  # the d of a matrix
-        ctx = lambda: _Context(self.n_params if p is not None else None, self.n_fields if fields is not None else None, state=True)
+        ctx = lambda: _Context(self.n_params if p is not None else None, self.n_fields if fields is not None else None, state=True,
+                               n_history=self.n_history if history is not None else None)
         if lam is not None:
             self.shape, texts = "lame", [lam, mu]
         elif isinstance(text, (list, tuple)) and not any(isinstance(r, (list, tuple)) for r in text):
@@ -889,6 +929,11 @@ class SecantLaw:
         for c, t in enumerate(texts):
             _emit(_parse(t, ctx()), ops, consts, self.n_params)
             ops.append((OP_STORE, c))
+        self.n_law_ops = len(ops)  # the program of the tangent pass: the components alone
+        self.history_texts = tuple(str(t) for t in updates)
+        for i, t in enumerate(updates):
+            _emit(_parse(t, ctx()), ops, consts, self.n_params)
+            ops.append((OP_STORE, self.n_comp + i))
         if len(ops) > MAX_OPS:
             raise ValueError(f"law: too long: {len(ops)} instructions, at most {MAX_OPS}")
         if len(consts) > MAX_CONSTS:
@@ -900,7 +945,7 @@ class SecantLaw:
         self._consts = np.array(consts, dtype=np.float64)
         self.n_y = 1 + max([int(k) for op, k in ops if op == OP_Y], default=-1)  # fast-variable components the law reads
         self.state_indices = {name: 1 + max([k[1] for op, k in ops if op == OP_X and isinstance(k, tuple) and k[0] == name], default=-1)
-                              for name in "esc"}  # entries of e, s and c it reads
+                              for name in ("esch" if self.n_history else "esc")}  # entries of e, s, c (and h, of a law with history) it reads
 
     @property
     def p(self) -> np.ndarray:
@@ -917,11 +962,12 @@ class SecantLaw:
 
     def program(self, t: int, n_comp: int) -> tuple[np.ndarray, np.ndarray]:
         """(ops[n_ops, 2] uint8, consts[n_consts] float64) on a plan of tensor size ``t`` whose coefficient has ``n_comp`` entries per
-        element: every component's code followed by its ``STORE k``.  ``ValueError`` when the law has another number of components
-        than ``n_comp`` (naming both), for an index of ``s`` / ``e`` at or above t, of ``c`` at or above n_comp."""
+        element: every component's code followed by its ``STORE k``, then every history update's followed by its ``STORE n_comp + i``;
+        ``h[k]`` is ``X 3 + n_fields + 2 t + n_comp + k``.  ``ValueError`` when the law has another number of components than
+        ``n_comp`` (naming both), for an index of ``s`` / ``e`` at or above t, of ``c`` at or above n_comp."""
         if self.n_comp != n_comp:
             raise ValueError(f"law: it has {self.n_comp} components; the plan's coefficient has n_comp = {n_comp}")
-        base = {"e": 3 + self.n_fields, "s": 3 + self.n_fields + t, "c": 3 + self.n_fields + 2 * t}
+        base = {"e": 3 + self.n_fields, "s": 3 + self.n_fields + t, "c": 3 + self.n_fields + 2 * t, "h": 3 + self.n_fields + 2 * t + n_comp}
         for name, bound, what in (("e", t, "t"), ("s", t, "t"), ("c", n_comp, "n_comp")):
             if self.state_indices[name] > bound:
                 raise ValueError(f"law: {name}[{self.state_indices[name] - 1}] is out of range: the plan has {what} = {bound} "
@@ -929,11 +975,9 @@ class SecantLaw:
         ops = [(op, base[k[0]] + k[1] if isinstance(k, tuple) else k) for op, k in self._ops]
         return np.array(ops, dtype=np.uint8).reshape(-1, 2), self._consts.copy()
 
-    def host_values(self, e, s, c, x, y=None, fields=None) -> np.ndarray:
-        """values[N, n_el, n_comp]: the law on every element from e[N, n_el, t] and s[N, n_el, t] (the strain and the secant flux of
-        the current iterate), c[N, n_el(, n_comp)] (the BASE coefficient stream), x[N, 3] (the macro midpoints), y[n_el, d] (the
-        element centroids; may be None when the law reads no ``y``) and fields[N, n_fields] -- ``_run``, value pass, on the rows the
-        device reads.  Bit for bit the device's ``law_values`` wherever the program holds exactly rounded operations only."""
+    def _state_rows(self, e, s, c, x, y, fields, history) -> tuple:
+        """(ops, consts, rows, y rows, N, n_el, t): the program on the plan the arrays belong to and the rows the device reads -- the
+        midpoint, the fields, then e, s, c and the history of the element.  The checks of the three twins."""
         e, s = np.asarray(e, dtype=np.float64), np.asarray(s, dtype=np.float64)
         N, n_el, t = e.shape
         c = np.asarray(c, dtype=np.float64).reshape(N, n_el, -1)
@@ -946,12 +990,40 @@ class SecantLaw:
             fields = np.asarray(fields, dtype=np.float64).reshape(N, self.n_fields)
         if self.n_y and (y is None or np.shape(y)[-1] < self.n_y):
             raise ValueError(f"the law reads y[{self.n_y - 1}]: pass the element centroids y[n_el, d]")
+        state = [e, s, c]
+        if self.n_history:
+            if history is None or np.size(history) != N * n_el * self.n_history:
+                raise ValueError(f"the law has the history variables {', '.join(self.history_names)}: pass "
+                                 f"history[N, n_el, {self.n_history}] = [{N}, {n_el}, {self.n_history}]")
+            state.append(np.asarray(history, dtype=np.float64).reshape(N, n_el, self.n_history))
+        elif history is not None:
+            raise ValueError("the law has no history variables: history must be None")
         rows = [x[:, k, None] for k in range(3)] + [fields[:, k, None] for k in range(self.n_fields)]
-        rows += [a[:, :, k] for a in (e, s, c) for k in range(a.shape[2])]
+        rows += [a[:, :, k] for a in state for k in range(a.shape[2])]
         yr = [] if y is None else [np.asarray(y, dtype=np.float64)[None, :, k] for k in range(np.shape(y)[-1])]
+        return ops.tolist(), consts, rows, yr, N, n_el, t
+
+    def host_values(self, e, s, c, x, y=None, fields=None, history=None) -> np.ndarray:
+        """values[N, n_el, n_comp]: the law on every element from e[N, n_el, t] and s[N, n_el, t] (the strain and the secant flux of
+        the current iterate), c[N, n_el(, n_comp)] (the BASE coefficient stream), x[N, 3] (the macro midpoints), y[n_el, d] (the
+        element centroids; may be None when the law reads no ``y``), fields[N, n_fields] and, for a law with history variables,
+        history[N, n_el, n_history] (what ``h[k]`` reads) -- ``_run``, value pass, on the rows the device reads.  Bit for bit the
+        device's ``law_values`` wherever the program holds exactly rounded operations only."""
+        ops, consts, rows, yr, N, n_el, _ = self._state_rows(e, s, c, x, y, fields, history)
         with np.errstate(all="ignore"):
-            out, _ = _run(ops.tolist(), consts, self.n_comp, rows, yr)
-        return np.stack([np.array(np.broadcast_to(v, (N, n_el))) for v in out], axis=-1)
+            out, _ = _run(ops, consts, self.n_comp + self.n_history, rows, yr)
+        return np.stack([np.array(np.broadcast_to(v, (N, n_el))) for v in out[:self.n_comp]], axis=-1)
+
+    def host_history(self, e, s, c, x, y=None, fields=None, history=None) -> np.ndarray:
+        """history_out[N, n_el, n_history]: the updates of the history variables on every element, from the arguments of
+        ``host_values`` -- the same ``_run`` of the same program, its stores ``n_comp ..``.  Bit for bit the device's ``history``
+        of a cell that stops in this state, wherever the program holds exactly rounded operations only."""
+        if not self.n_history:
+            raise ValueError("the law has no history variables (history=[...])")
+        ops, consts, rows, yr, N, n_el, _ = self._state_rows(e, s, c, x, y, fields, history)
+        with np.errstate(all="ignore"):
+            out, _ = _run(ops, consts, self.n_comp + self.n_history, rows, yr)
+        return np.stack([np.array(np.broadcast_to(v, (N, n_el))) for v in out[self.n_comp:]], axis=-1)
 
     @property
     def explicit(self) -> bool:
@@ -1007,36 +1079,26 @@ class SecantLaw:
             out.append(g)
         return out
 
-    def host_tangent(self, e, cur, c, x, y=None, fields=None) -> tuple[np.ndarray, np.ndarray]:
+    def host_tangent(self, e, cur, c, x, y=None, fields=None, history=None) -> tuple[np.ndarray, np.ndarray]:
         """(T_sym[N, n_el, t, t], asymmetry[N]): the coefficient of the consistent tangent as the device forms it (csrc/secant_tangent.hip;
         DESIGN 4.16) from e[N, n_el, t] (the strain of the stopping round), cur[N, n_el(, n_comp)] (the stream of that round,
         ``SecantResult.coef``), c (the BASE stream) and x, y, fields as ``host_values`` takes them.  ``_run`` in forward mode with the
         strain rows as seeds gives d_k[n] = dL_k/de[n]; then, in the order of the program's STOREs,
         ``T[m][n] = T[m][n] + g_k[m] * d_k[n]`` from ``material(cur)``, the symmetric part ``0.5 * (T[m][n] + T[n][m])`` and
         ``asymmetry = max |T - T^T| / max |T|`` per cell (0 when both are 0; a NaN never wins).  Bit for bit the device's
-        ``tangent_coef`` wherever the program holds exactly rounded operations only.  ``ValueError`` for a law that reads ``s[k]``."""
+        ``tangent_coef`` wherever the program holds exactly rounded operations only.  ``ValueError`` for a law that reads ``s[k]``.
+        ``history[N, n_el, n_history]``: what ``h[k]`` reads, for a law with history variables; the tangent differentiates the
+        components at that frozen history (``max(h[0], ...)`` has the loading and the unloading branch), not the updates."""
         if not self.explicit:
             raise ValueError(f"law: it reads s[{self.state_indices['s'] - 1}]: the consistent tangent takes an explicit law, one that "
                              "reads no s[k]; an implicit law is out of scope")
         e = np.asarray(e, dtype=np.float64)
-        N, n_el, t = e.shape
-        c = np.asarray(c, dtype=np.float64).reshape(N, n_el, -1)
+        ops, consts, rows, yr, N, n_el, t = self._state_rows(e, np.zeros_like(e), c, x, y, fields, history)
+        ops = ops[:self.n_law_ops]  # the components alone: the updates stand behind the last component's STORE
         cur = np.asarray(cur, dtype=np.float64).reshape(N, n_el, -1)
-        ops, consts = self.program(t, c.shape[2])
-        x = np.asarray(x, dtype=np.float64).reshape(N, -1)
-        x = np.concatenate([x, np.zeros((N, 3 - x.shape[1]))], axis=1) if x.shape[1] < 3 else x[:, :3]
-        if self.n_fields:
-            if fields is None:
-                raise ValueError(f"the law reads the fields {', '.join(self.field_names)}: pass fields[N, {self.n_fields}]")
-            fields = np.asarray(fields, dtype=np.float64).reshape(N, self.n_fields)
-        if self.n_y and (y is None or np.shape(y)[-1] < self.n_y):
-            raise ValueError(f"the law reads y[{self.n_y - 1}]: pass the element centroids y[n_el, d]")
-        rows = [x[:, k, None] for k in range(3)] + [fields[:, k, None] for k in range(self.n_fields)]
-        rows += [a[:, :, k] for a in (e, np.zeros_like(e), c) for k in range(a.shape[2])]
-        yr = [] if y is None else [np.asarray(y, dtype=np.float64)[None, :, k] for k in range(np.shape(y)[-1])]
         base = 3 + self.n_fields
         with np.errstate(all="ignore"):
-            _, dv = _run(ops.tolist(), consts, self.n_comp, rows, yr, seeds={base + n: n for n in range(t)})
+            _, dv = _run(ops, consts, self.n_comp, rows, yr, seeds={base + n: n for n in range(t)})
             T = self._material(cur, t)
             g = self._material_columns(e)
             for k in [int(k) for op, k in ops if op == OP_STORE]:

@@ -328,6 +328,8 @@ class BaseHMM(ABC):
         self.secant: SecantResult | None = None  # solve_nonlinear: the last step's result per cell
         self.nonlinear_history: list[float] = []  # ... and the relative macro change of every step
         self.tangent_tensors = None  # D = d sigma_H / d xi per macro cell of the last solve_nonlinear(method="newton")
+        self.history = None  # [cells of this rank, n_el, n_history]: the committed history variables of a law that has some
+        self.history_trial = None  # ... and what the last step of the last solve_nonlinear left: commit_history() makes it the state
         self._linearisation_load = None  # P_T of the Newton step solve() is serving (solve_nonlinear sets and clears it)
         self._tangent_plan = None  # the sibling plan of the tangent kind (solve_nonlinear(method="newton") builds and keeps it)
         self._tangent_reserved = 0  # ... and the cells it is reserved for
@@ -1195,25 +1197,34 @@ class BaseHMM(ABC):
         return tp
 
     def _secant_tensors(self, cells: np.ndarray, xi: np.ndarray, law: SecantLaw, rows: np.ndarray, points: np.ndarray, chunk_cells,
-                        tangent: bool = False, **kw) -> SecantResult:
+                        tangent: bool = False, history: np.ndarray | None = None, **kw) -> SecantResult:
         """``plan.secant`` of ``law`` on ``cells`` under the macro strains ``xi``, chunk by chunk -> one ``SecantResult`` with ``cells``;
         ``tangent``: ``plan.secant_tangent`` on the sibling plan instead, with ``tangent`` and ``asymmetry``.  Under a process group
         every rank iterates its block and one all-gather of t t + t + 3 numbers per cell (2 t t + t + 4 with the tangent; and the info
-        flags) returns the fields to every rank, as ``_effective_polarisation`` does."""
+        flags) returns the fields to every rank, as ``_effective_polarisation`` does.  ``history``: the history variables of THIS
+        RANK'S block of ``cells`` (all of them without a process group), passed to the plan chunk by chunk; what the plan returns for
+        the block goes to ``history_trial`` and is not gathered."""
         t = self._tensor_size()
 
         def bytes_per_cell():
             out = 8 * (3 + t * t + t + (t * t + 1 if tangent else 0)) + 4
+            if history is not None:  # in and out
+                out += 16 * self._cell_mesh.num_cells * history.shape[2]
             return out if self._sampled_on_device() else out + self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) * 8
 
         def local(b, e):
             def call(plan, coef, M, _, sub, at):
                 args = dict(rows=rows[b + at:b + at + len(sub)], points=points, **kw)
+                if history is not None:
+                    args["history"] = history[at:at + len(sub)]
                 if not tangent:
                     return plan.secant(coef, xi[b + at:b + at + len(sub)], law, M, **args)
                 return plan.secant_tangent(coef, xi[b + at:b + at + len(sub)], law, self._ensure_tangent_plan(plan), M, **args)
 
-            return _join(self._chunks(cells[b:e], chunk_cells, bytes_per_cell, call), cells=cells[b:e])
+            r = _join(self._chunks(cells[b:e], chunk_cells, bytes_per_cell, call), cells=cells[b:e])
+            if history is not None:
+                self.history_trial = r.history
+            return r
 
         if not self._sharded():
             return local(0, len(cells))
@@ -1260,6 +1271,17 @@ class BaseHMM(ABC):
 
         ``RuntimeError`` when a polarisation is set (loads beside a law are out of scope), the law reads fields without
         ``field_values``, or ``method="newton"`` meets a law that reads ``s[k]`` (the tangent of an implicit law is out of scope).
+        A law with history variables (``SecantLaw(history=[...])``) reads ``self.history[cells, n_el, n_history]``, created
+        from ``law.history_initial`` on first use: every macro step passes that same frozen state to the plan (``h[k]`` is the state
+        at the start of the LOAD STEP, not of a macro step), and the updates of the last step are left in ``self.history_trial``.
+        ``commit_history()`` makes the trial the state -- call it once a load step is accepted --, ``reset_history()`` clears or sets
+        it; without a commit a second call reproduces the first.  ``RuntimeError`` naming ``reset_history`` when the state belongs to
+        a law with another number of history variables or to another micro mesh.  Both methods are supported.  Under a process group
+        every rank keeps the history of its own block of cells only (``history_cells``, the block rule of ``run_sharded``); nothing
+        of it is gathered.  In this version the solver holds the history on the HOST: ``n_el n_history`` doubles per cell cross the
+        boundary in each direction per macro step (DESIGN 4.17 has the measured cost); ``MicroCellPlan.secant_device`` keeps it
+        resident for callers who drive the plan themselves.
+
         Out of scope as well: warm starts of the micro iteration
         across macro steps (``MicroCellPlan.secant(coef_start=...)`` has them), ``reconstruct()`` / ``criterion()`` of the nonlinear
         state (``MicroCellPlan.secant(return_coef=True)`` gives the stream to pass to them).  Under a process group every rank
@@ -1279,12 +1301,13 @@ class BaseHMM(ABC):
         if law.n_fields:
             rows = np.concatenate([rows, self._field_values(law, field_values)[cells]], axis=1)
         points = np.ascontiguousarray(self._cell_mesh.cell_midpoints()[:, : self._tdim])
+        state = self._history_state(law) if getattr(law, "n_history", 0) else None
         u = self._macro_dofs(u0, "u0").copy() if u0 is not None else self.solve().x.array.copy()
         history, converged, result = [], False, None
         for _ in range(int(max_iter)):
             xi = self._macro_strains(cells, u)
-            result = self._secant_tensors(cells, xi, law, rows, points, chunk_cells, tangent=newton, max_iter=micro_iter, tol=micro_tol,
-                                          relax=relax)
+            result = self._secant_tensors(cells, xi, law, rows, points, chunk_cells, tangent=newton, history=state, max_iter=micro_iter,
+                                          tol=micro_tol, relax=relax)
             matrix = result.A_eff
             if newton:  # a cell without a state to linearise at (status 2, 3: its tangent is NaN) takes the secant step, as "secant" does
                 lost = (result.status >= 2)[:, None, None]
@@ -1317,6 +1340,44 @@ class BaseHMM(ABC):
                 "solve_nonlinear: the element tangents of the law are not symmetric (largest asymmetry %.3e): the law has no potential, "
                 "and the macro steps were quasi-Newton steps with the symmetric part of the tangent", worst)
         return self._u
+
+    # -- the history variables of a law -----------------------------------------------------------------------------------
+    @property
+    def history_cells(self) -> np.ndarray:
+        """The macro cells whose history this rank holds, in the order of ``history``'s first axis: all of them, or this rank's block
+        under a process group (the block rule of ``run_sharded``)."""
+        return self._local_cells()
+
+    def _history_state(self, law: SecantLaw) -> np.ndarray:
+        """``self.history`` for ``law``, created from ``law.history_initial`` on first use."""
+        shape = (self._local_cell_count(), self._cell_mesh.num_cells, int(law.n_history))
+        if self.history is None:
+            self.history = np.ascontiguousarray(np.broadcast_to(law.history_initial, shape))
+        elif self.history.shape != shape:
+            raise RuntimeError(f"the history has shape {self.history.shape}; this law on this micro mesh has (cells, n_el, n_history) = {shape}: "
+                               "reset_history() starts a new one")
+        return self.history
+
+    def commit_history(self):
+        """The history the last ``solve_nonlinear`` left (``history_trial``) becomes the state (``history``): the load step is
+        accepted.  ``RuntimeError`` when there is none."""
+        if self.history_trial is None:
+            raise RuntimeError("commit_history(): no solve_nonlinear() of a law with history variables has run since the last reset_history()")
+        self.history = self.history_trial
+
+    def reset_history(self, values=None):
+        """Forget the history and the trial (the next ``solve_nonlinear`` starts from ``law.history_initial``), or set the state to
+        ``values[len(history_cells), n_el, n_history]`` (``[len(history_cells), n_el]``: one variable)."""
+        self.history = self.history_trial = None
+        if values is None:
+            return
+        v = np.array(values, dtype=np.float64, order="C")
+        if v.ndim == 2:
+            v = v[:, :, None]
+        lead = (self._local_cell_count(), self._cell_mesh.num_cells)
+        if v.ndim != 3 or v.shape[:2] != lead or not 1 <= v.shape[2]:
+            raise ValueError(f"values has shape {np.shape(values)}; expected {lead + ('n_history',)}")
+        self.history = v
 
     def _parameter_directions(self) -> tuple[tuple, np.ndarray]:
         """(names, directions[n_dirs, n_el(, n_comp)]) of the parameters of a ``TwoPhase`` or affine ``Separable`` coefficient: the element

@@ -818,6 +818,48 @@ int hommx_secant_tangent_source_device(hommx_plan* plan, int64_t n_cells, const 
                                        const hommx_secant_tangent_args* args, void* stream);
 
 /*
+ * History variables of a law: 1 .. HOMMX_SECANT_MAX_HISTORY internal variables per micro element that
+ * survive from one call to the next -- a damage driver, the largest field an element has seen.  The row of the law grows by them,
+ *   row = [midpoint (3) | fields (n_fields) | e_K (t) | s_K (t) | c_K (n_comp) | h_K (n_history)],
+ * and its program stores n_comp + n_history values (program->n_comp is that sum): STORE k, k < n_comp, is entry k of the coefficient
+ * as before, STORE n_comp + i the UPDATE of h_i, the value history_out receives.  h_K is history_in of the element: the history at
+ * the START of the call, read in every round and frozen for the whole iteration -- which is why history_in and history_out must not
+ * be the same array.  The rounds are those of hommx_secant_source with these additions: an update that is not finite counts towards
+ * status 2 as a component does; the history does not enter `change`; history_out belongs to the stopping round as A_eff, coef_out and
+ * state do and is frozen with them; a cell that stops with status 2 or 3 gets history_out = history_in bit for bit.  The caller
+ * decides when history_out becomes the state (it passes it as history_in of the next load step).
+ *
+ *   n_history    1 .. HOMMX_SECANT_MAX_HISTORY
+ *   history_in   [n_cells][n_el][n_history], required
+ *   history_out  [n_cells][n_el][n_history], required, not history_in
+ * Every other argument is hommx_secant_source's, resp. hommx_secant_tangent_source's, and so is every output, the struct included.
+ * The tangent entries differentiate the components at the frozen history (max(h, ...) has its loading and its unloading branch) on
+ * the program truncated behind the last component's STORE -- the updates stand behind it and are not differentiated --, and their
+ * law must read no s entry anywhere, the updates included.
+ * HOMMX_EINVAL, before the plan's device is made current: everything the entry without history refuses, with the program checked
+ * against n_comp + n_history components and a row of 3 + n_fields + 2 t + n_comp + n_history entries (its stores must be exactly
+ * 0 .. n_comp + n_history - 1); a null history struct, history_in or history_out; n_history outside 1 .. HOMMX_SECANT_MAX_HISTORY;
+ * history_in == history_out.  Both arrays are per-cell arrays of the chunk, counted as coef_start and coef_out are.  The device
+ * entries read nothing back, so a caller can keep the history resident on the device.
+ */
+#define HOMMX_SECANT_MAX_HISTORY 4
+typedef struct hommx_history_args {
+  int32_t n_history;
+  const double* history_in;
+  double* history_out;
+} hommx_history_args;
+int hommx_secant_history_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M,
+                                const hommx_secant_args* args, const hommx_history_args* history);
+/* Same with DEVICE pointers (in *src, *args and *history; the structs and the program are host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
+int hommx_secant_history_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                       const hommx_secant_args* args, const hommx_history_args* history, void* stream);
+int hommx_secant_tangent_history_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M,
+                                        const hommx_secant_tangent_args* args, const hommx_history_args* history);
+/* Same with DEVICE pointers, asynchronous on `stream`. */
+int hommx_secant_tangent_history_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                               const hommx_secant_tangent_args* args, const hommx_history_args* history, void* stream);
+
+/*
  * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
  * periodic: the caller folds the mesh vertices into n_nodes independent (periodic) nodes -- cell_problem.py:38-300's slave -> master
  * map -- and passes, per element, the periodic node of every vertex and the UNFOLDED vertex coordinates (gradients and volumes).
