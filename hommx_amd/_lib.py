@@ -239,6 +239,17 @@ class HistoryArgs(C.Structure):
     ]
 
 
+class SecantLoadArgs(C.Structure):
+    """hommx_secant_load_args: the one load beside a law -- its code (LOADS_PER_CELL or LOADS_PROGRAM, alone or with
+    LOADS_EIGENSTRAIN), the per-cell array or the program source."""
+
+    _fields_ = [
+        ("per_cell", C.c_int32),
+        ("P", C.c_void_p),
+        ("P_source", C.POINTER(CoefSource)),
+    ]
+
+
 def _prototypes() -> dict:
     """name -> (restype, argtypes) of every symbol include/hommx_hip.h declares: ``load()`` declares them from this table, and
     the tests check that the header and the library export exactly these names."""
@@ -301,6 +312,14 @@ def _prototypes() -> dict:
                                                         C.POINTER(HistoryArgs)]),
         "hommx_secant_tangent_history_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantTangentArgs),
                                                                C.POINTER(HistoryArgs), vp]),
+        "hommx_secant_load_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantArgs), C.POINTER(HistoryArgs),
+                                             C.POINTER(SecantLoadArgs)]),
+        "hommx_secant_load_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantArgs), C.POINTER(HistoryArgs),
+                                                    C.POINTER(SecantLoadArgs), vp]),
+        "hommx_secant_tangent_load_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantTangentArgs),
+                                                     C.POINTER(HistoryArgs), C.POINTER(SecantLoadArgs)]),
+        "hommx_secant_tangent_load_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantTangentArgs),
+                                                            C.POINTER(HistoryArgs), C.POINTER(SecantLoadArgs), vp]),
         "hommx_solve_batch_two_phase": (c_int, [vp, i64, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_two_phase_device": (c_int, [vp, i64, vp, vp, vp, vp, vp, vp]),
         "hommx_solve_batch_separable": (c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),

@@ -827,6 +827,23 @@ class MicroCellPlan:
                 raise ValueError(f"points has shape {points.shape}; expected ({self.n_el}, {self.dim}): the element centroids")
         elif crit.n_y:
             raise ValueError(f"the criterion reads y[{crit.n_y - 1}]: pass points[n_el, dim], the element centroids")
+        P, P_src, P_ptr, code = self._one_load(P, per_cell, eigenstrain, nc)
+        out = np.empty((nc, _lib.CRIT_NSTATS), dtype=np.float64)
+        vals = np.empty((nc, self.n_el), dtype=np.float64) if values else None
+        strain = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
+        flux = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
+        addr = lambda a: None if a is None else a.ctypes.data
+        args = _lib.CriterionArgs(C.pointer(pstruct), int(crit.n_fields), rows.ctypes.data, addr(points), xi.ctypes.data, float(crit.threshold),
+                                  int(P is not None), code, P_ptr, C.pointer(P_src) if P_src is not None else None, out.ctypes.data,
+                                  addr(vals), addr(strain), addr(flux), None, None)
+        A, info = self._source_call("hommx_criterion_source", nc, M, stream, args)
+        return CriterionResult(out[:, 0].copy(), out[:, 1].astype(np.int64), out[:, 2].copy(), out[:, 3].copy(), A, info, vals, strain, flux)
+
+    def _one_load(self, P, per_cell, eigenstrain, nc: int) -> tuple:
+        """ONE load of ``criterion`` / ``secant`` as the library takes it -> (P, P_source, P_ptr, code): a program ``CoefStream`` gives
+        its source and LOADS_PROGRAM; an array -- ``P[n_el, t]`` / ``P[1, n_el, t]`` shared (repeated for every cell: ``points`` is
+        the call's one shared array), ``P[N_c, (1,) n_el, t]`` per cell -- the contiguous ``P[N_c, n_el, t]``, its address and
+        LOADS_PER_CELL; None gives (None, None, None, 0).  ``eigenstrain`` sets the flag of a load that is there."""
         P_src, P_ptr, code = None, None, 0
         if isinstance(P, CoefStream):
             self._check_load_stream(P, nc)
@@ -844,16 +861,7 @@ class MicroCellPlan:
             P_ptr, code = P.ctypes.data, _lib.LOADS_PER_CELL
         if eigenstrain and P is not None:
             code |= _lib.LOADS_EIGENSTRAIN
-        out = np.empty((nc, _lib.CRIT_NSTATS), dtype=np.float64)
-        vals = np.empty((nc, self.n_el), dtype=np.float64) if values else None
-        strain = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
-        flux = np.empty((nc, self.n_el, self.t), dtype=np.float64) if fields else None
-        addr = lambda a: None if a is None else a.ctypes.data
-        args = _lib.CriterionArgs(C.pointer(pstruct), int(crit.n_fields), rows.ctypes.data, addr(points), xi.ctypes.data, float(crit.threshold),
-                                  int(P is not None), code, P_ptr, C.pointer(P_src) if P_src is not None else None, out.ctypes.data,
-                                  addr(vals), addr(strain), addr(flux), None, None)
-        A, info = self._source_call("hommx_criterion_source", nc, M, stream, args)
-        return CriterionResult(out[:, 0].copy(), out[:, 1].astype(np.int64), out[:, 2].copy(), out[:, 3].copy(), A, info, vals, strain, flux)
+        return P, P_src, P_ptr, code
 
     def _law_program(self, law) -> Program:
         """The program of a ``hommx_amd.expr.SecantLaw`` on this plan (its component count and index checks against t and n_comp run here)."""
@@ -897,7 +905,7 @@ class MicroCellPlan:
 
     def secant(self, coef, xi: np.ndarray, law, M: np.ndarray | None = None, rows=None, points=None, max_iter: int = 50, tol: float = 1e-10,
                relax: float = 1.0, coef_start=None, fields: bool = False, values: bool = False, return_coef: bool = False,
-               history=None) -> SecantResult:
+               history=None, P=None, per_cell: bool | None = None, eigenstrain: bool = False) -> SecantResult:
         """The secant iteration of a strain-dependent coefficient (hommx_secant_source): ``coef`` an array or a ``CoefStream``, the BASE
         coefficient ``c`` of the law; xi and M as ``reconstruct`` takes them; ``law`` a ``hommx_amd.expr.SecantLaw`` with the plan's
         ``n_comp`` components -> ``SecantResult``.  Per cell and round: the correctors of the current stream on the plan's route, the
@@ -908,13 +916,22 @@ class MicroCellPlan:
         law's own fields of every cell (required when the law reads ``f``; without them ``x`` is 0); ``points[n_el, dim]``: the
         element centroids, required when it reads ``y``; ``coef_start[N_c, n_el(, n_comp)]``: the stream the iteration starts from
         (default: the base stream), e.g. ``SecantResult.coef`` of a neighbouring macro strain.  The batch runs in the chunks of
-        ``reconstruct``; a load beside a law is out of scope.
+        ``reconstruct``.
 
         ``history``: required for a law with history variables (hommx_secant_history_source) -- what ``h[k]`` reads, the
         state at the start of the call, frozen for the whole iteration: ``[N_c, n_el, n_history]``, ``[N_c, n_el]`` for one variable,
         or a scalar / ``[n_history]`` values broadcast as an initial state.  ``SecantResult.history`` is then the update of every
-        element at its cell's stopping round; the argument is not changed.  ``ValueError`` naming the expected shape otherwise."""
-        return self._secant(coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef, history=history)
+        element at its cell's stopping round; the argument is not changed.  ``ValueError`` naming the expected shape otherwise.
+
+        ``P``: ONE load beside the law (hommx_secant_load_source), with the meaning ``criterion`` gives ``P``,
+        ``per_cell`` and ``eigenstrain``: an array ``[N_c, n_el, t]`` (or one ``[n_el, t]`` for all cells) or a program ``CoefStream``
+        of a vector ``Expression``.  Every round then ends in a load solve on the current stream (the route ``load_kernel`` names;
+        ``load_solve=True`` on the frontal mesh route).  A polarisation: the law reads the total strain in ``e`` and the total flux
+        ``material . e + P`` in ``s``.  An eigenstrain: it reads the elastic strain ``e - E`` and ``material . (e - E)``, the model
+        sigma = c(eps - eps*) (eps - eps*).  ``strain`` / ``flux`` are what the law read, ``mean_flux`` the mean of that flux, and the
+        effective polarisation of the stopping state is ``mean_flux - A_eff xi``.  With ``P=None`` the call is the one it was."""
+        return self._secant(coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef, history=history,
+                            load=(P, per_cell, eigenstrain))
 
     @property
     def tangent_kind(self) -> str:
@@ -939,24 +956,30 @@ class MicroCellPlan:
 
     def secant_tangent(self, coef, xi: np.ndarray, law, tangent_plan: "MicroCellPlan", M: np.ndarray | None = None, rows=None, points=None,
                        max_iter: int = 50, tol: float = 1e-10, relax: float = 1.0, coef_start=None, fields: bool = False,
-                       values: bool = False, return_coef: bool = False, return_tangent_coef: bool = False, history=None) -> SecantResult:
+                       values: bool = False, return_coef: bool = False, return_tangent_coef: bool = False, history=None, P=None,
+                       per_cell: bool | None = None, eigenstrain: bool = False) -> SecantResult:
         """``secant`` and, at the state every cell stops in, the consistent tangent D = d mean_flux / d xi (hommx_secant_tangent_source;
         DESIGN 4.16): the arguments of ``secant`` and ``tangent_plan``, a plan of ``self.tangent_kind`` on the same micro mesh and
         device (``MicroCellPlan(dim, n, plan.tangent_kind)`` or ``from_mesh`` of the same mesh).  Every member ``secant`` returns has
         its bits; ``tangent``, ``asymmetry``, ``tangent_info`` and, with ``return_tangent_coef``, ``tangent_coef`` come with them.
         The law must be explicit (``law.explicit``): ``ValueError`` naming the ``s[k]`` it reads otherwise, and for a ``tangent_plan``
         of the wrong kind or shape.  ``history``: as in ``secant`` (hommx_secant_tangent_history_source); the tangent is that of the
-        components at the frozen history, so a cell that unloads has ``tangent`` = ``A_eff``."""
+        components at the frozen history, so a cell that unloads has ``tangent`` = ``A_eff``.  ``P``, ``per_cell``, ``eigenstrain``:
+        the load of ``secant`` (hommx_secant_tangent_load_source); the element tangents are then evaluated at the strain the law
+        read, total or elastic, and ``tangent`` is still d mean_flux / d xi."""
         self._check_tangent(law, tangent_plan)
         return self._secant(coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef, tangent_plan,
-                            return_tangent_coef, history)
+                            return_tangent_coef, history, (P, per_cell, eigenstrain))
 
     def _secant(self, coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef, tangent_plan=None,
-                return_tangent_coef=False, history=None) -> SecantResult:
+                return_tangent_coef=False, history=None, load=(None, None, False)) -> SecantResult:
         """The host call of ``secant`` (``tangent_plan`` None) and ``secant_tangent``; with the history entries for a law that has
-        history variables."""
+        history variables, and with the load entries (which take the history as an optional argument) for ``load`` = (P, per_cell,
+        eigenstrain) with a P."""
         stream = self._as_stream(coef)
         nc = self._check_stream(stream)
+        P, P_src, P_ptr, code = self._one_load(load[0], load[1], load[2], nc)
+        largs = None if P is None else _lib.SecantLoadArgs(code, P_ptr, C.pointer(P_src) if P_src is not None else None)
         xi = np.ascontiguousarray(xi, dtype=np.float64)
         if xi.shape != (nc, self.t):
             raise ValueError(f"xi has shape {xi.shape}; expected ({nc}, {self.t})")
@@ -994,6 +1017,9 @@ class MicroCellPlan:
         args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows.ctypes.data, addr(points), xi.ctypes.data, max_iter, tol, relax,
                                addr(coef_start), state.ctypes.data, None, mean_flux.ctypes.data, addr(out_coef), addr(strain), addr(flux),
                                addr(vals), None)
+        if largs is not None:
+            return self._secant_load(nc, M, stream, args, hargs, largs, tangent_plan, return_tangent_coef, state, mean_flux, out_coef, strain,
+                                     flux, vals, hist_out)
         if tangent_plan is None and hargs is None:
             A, info = self._source_call("hommx_secant_source", nc, M, stream, args)
             return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
@@ -1024,6 +1050,34 @@ class MicroCellPlan:
         A, info = self._host_call("hommx_secant_tangent_source" if hargs is None else "hommx_secant_tangent_history_source", nc, M, call)
         return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
                             strain, flux, vals, None, D, asym, tinfo, tcoef, hist_out)
+
+    def _secant_load(self, nc, M, stream, args, hargs, largs, tangent_plan, return_tangent_coef, state, mean_flux, out_coef, strain, flux,
+                     vals, hist_out) -> SecantResult:
+        """The host call of ``_secant`` beside a load: hommx_secant_load_source, or with ``tangent_plan`` hommx_secant_tangent_load_source;
+        ``hargs`` None: a law without history variables."""
+        src = stream.coef_source()
+        hp = None if hargs is None else C.byref(hargs)
+        addr = lambda a: None if a is None else a.ctypes.data
+        status = lambda: (state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64))
+        if tangent_plan is None:
+            def call(Mp, o, i):
+                args.A_eff, args.info = o, i
+                return self._lib.hommx_secant_load_source(self._h, nc, C.byref(src), Mp, C.byref(args), hp, C.byref(largs))
+
+            A, info = self._host_call("hommx_secant_load_source", nc, M, call)
+            return SecantResult(A, mean_flux, *status(), info, out_coef, strain, flux, vals, history=hist_out)
+        D = np.empty((nc, self.t, self.t), dtype=np.float64)
+        asym = np.empty(nc, dtype=np.float64)
+        tinfo = np.zeros(nc, dtype=np.int32)
+        tcoef = np.empty((nc, self.n_el, self.t * (self.t + 1) // 2), dtype=np.float64) if return_tangent_coef else None
+        targs = _lib.SecantTangentArgs(C.pointer(args), tangent_plan._h, D.ctypes.data, asym.ctypes.data, addr(tcoef), tinfo.ctypes.data)
+
+        def call(Mp, o, i):
+            args.A_eff, args.info = o, i
+            return self._lib.hommx_secant_tangent_load_source(self._h, nc, C.byref(src), Mp, C.byref(targs), hp, C.byref(largs))
+
+        A, info = self._host_call("hommx_secant_tangent_load_source", nc, M, call)
+        return SecantResult(A, mean_flux, *status(), info, out_coef, strain, flux, vals, None, D, asym, tinfo, tcoef, hist_out)
 
     def solve_two_phase(self, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None = None,
                         return_info: bool = False):
@@ -1214,7 +1268,8 @@ class MicroCellPlan:
                       A_ptr: int, points_ptr: int | None = None, max_iter: int = 50, tol: float = 1e-10, relax: float = 1.0,
                       coef_start_ptr: int | None = None, mean_flux_ptr: int | None = None, coef_ptr: int | None = None,
                       strain_ptr: int | None = None, flux_ptr: int | None = None, values_ptr: int | None = None, info_ptr: int | None = None,
-                      stream: int | None = None, history_in_ptr: int | None = None, history_out_ptr: int | None = None):
+                      stream: int | None = None, history_in_ptr: int | None = None, history_out_ptr: int | None = None,
+                      P_ptr: int | None = None, P_source: "_lib.CoefSource | None" = None, eigenstrain: bool = False):
         """Device-pointer form of ``secant`` (hommx_secant_source_device), asynchronous on ``stream``: ``source`` =
         ``CoefStream.coef_source(upload)`` with device addresses; ``law`` the ``SecantLaw`` (its program is host memory);
         rows[n_cells, 3 + law.n_fields], points[n_el, dim] (None: the law reads no ``y``) -> state[n_cells, 3] = [rounds | change |
@@ -1222,7 +1277,9 @@ class MicroCellPlan:
         strain / flux[n_cells, n_el, t], values[n_cells, n_el, n_comp].  Exactly ``max_iter`` rounds per chunk are queued and nothing
         is read back; the bits are those of ``secant``.  A law with history variables (hommx_secant_history_source_device) takes
         ``history_in_ptr`` and ``history_out_ptr``, two different arrays [n_cells, n_el, n_history] on the device: a caller keeps the
-        history resident by swapping them between load steps."""
+        history resident by swapping them between load steps.  A load beside the law (hommx_secant_load_source_device): ``P_ptr``
+        (P[n_cells, n_el, t], per cell) or ``P_source`` (a program, as in ``loads_device``), ``eigenstrain`` as in ``secant``; an
+        eigenstrain array is read in every round and never written."""
         hargs = self._device_history(law, history_in_ptr, history_out_ptr)
         max_iter, tol, relax = self._secant_limits(max_iter, tol, relax)
         prog = self._law_program(law)
@@ -1230,12 +1287,26 @@ class MicroCellPlan:
         args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows_ptr, points_ptr or None, xi_ptr, max_iter, tol, relax,
                                coef_start_ptr or None, state_ptr, A_ptr, mean_flux_ptr or None, coef_ptr or None, strain_ptr or None,
                                flux_ptr or None, values_ptr or None, info_ptr or None)
+        largs = self._device_load(P_ptr, P_source, eigenstrain)
+        if largs is not None:
+            _lib.check(self._lib.hommx_secant_load_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
+                                                                 None if hargs is None else C.byref(hargs), C.byref(largs), stream or None),
+                       "hommx_secant_load_source_device")
+            return
         if hargs is not None:
             _lib.check(self._lib.hommx_secant_history_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
                                                                     C.byref(hargs), stream or None), "hommx_secant_history_source_device")
             return
         _lib.check(self._lib.hommx_secant_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
                    "hommx_secant_source_device")
+
+    @staticmethod
+    def _device_load(P_ptr, P_source, eigenstrain):
+        """The ``SecantLoadArgs`` of a device call, None without a load."""
+        if P_ptr is None and P_source is None:
+            return None
+        code = (_lib.LOADS_PROGRAM if P_source is not None else _lib.LOADS_PER_CELL) | (_lib.LOADS_EIGENSTRAIN if eigenstrain else 0)
+        return _lib.SecantLoadArgs(code, None if P_source is not None else P_ptr, C.pointer(P_source) if P_source is not None else None)
 
     @staticmethod
     def _device_history(law, history_in_ptr, history_out_ptr):
@@ -1256,12 +1327,14 @@ class MicroCellPlan:
                               coef_start_ptr: int | None = None, mean_flux_ptr: int | None = None, coef_ptr: int | None = None,
                               strain_ptr: int | None = None, flux_ptr: int | None = None, values_ptr: int | None = None,
                               info_ptr: int | None = None, tangent_coef_ptr: int | None = None, tangent_info_ptr: int | None = None,
-                              stream: int | None = None, history_in_ptr: int | None = None, history_out_ptr: int | None = None):
+                              stream: int | None = None, history_in_ptr: int | None = None, history_out_ptr: int | None = None,
+                              P_ptr: int | None = None, P_source: "_lib.CoefSource | None" = None, eigenstrain: bool = False):
         """Device-pointer form of ``secant_tangent`` (hommx_secant_tangent_source_device), asynchronous on ``stream``: the pointers of
         ``secant_device`` and tangent[n_cells, t, t], asymmetry[n_cells], tangent_coef[n_cells, n_el, t (t + 1) / 2],
         tangent_info[n_cells] (int32).  Per chunk ``max_iter`` rounds, one tangent launch and one solve on ``tangent_plan`` are queued
         and nothing is read back; the bits are those of ``secant_tangent``.  ``history_in_ptr`` / ``history_out_ptr``: as in
-        ``secant_device`` (hommx_secant_tangent_history_source_device)."""
+        ``secant_device`` (hommx_secant_tangent_history_source_device); ``P_ptr`` / ``P_source`` / ``eigenstrain``: the load of
+        ``secant_device`` (hommx_secant_tangent_load_source_device)."""
         self._check_tangent(law, tangent_plan)
         hargs = self._device_history(law, history_in_ptr, history_out_ptr)
         max_iter, tol, relax = self._secant_limits(max_iter, tol, relax)
@@ -1272,6 +1345,13 @@ class MicroCellPlan:
                                flux_ptr or None, values_ptr or None, info_ptr or None)
         targs = _lib.SecantTangentArgs(C.pointer(args), tangent_plan._h, tangent_ptr, asymmetry_ptr, tangent_coef_ptr or None,
                                        tangent_info_ptr or None)
+        largs = self._device_load(P_ptr, P_source, eigenstrain)
+        if largs is not None:
+            _lib.check(self._lib.hommx_secant_tangent_load_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None,
+                                                                         C.byref(targs), None if hargs is None else C.byref(hargs),
+                                                                         C.byref(largs), stream or None),
+                       "hommx_secant_tangent_load_source_device")
+            return
         if hargs is not None:
             _lib.check(self._lib.hommx_secant_tangent_history_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None,
                                                                             C.byref(targs), C.byref(hargs), stream or None),

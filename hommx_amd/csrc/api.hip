@@ -119,7 +119,8 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 //            the plan's to overwrite, [nc][n_loads][n_el][t] (loads_run; crit_run: the one load of a criterion)
 // B_SECANT: the current and the candidate element stream of one chunk of hommx_secant_source, [chunk][n_el][n_comp] each, the info
 //            of its eliminations where the caller takes none, [chunk], and the tangent stream of a chunk of hommx_secant_tangent_source
-//            where the caller takes none, [chunk][n_el][t (t + 1) / 2] (secant_run)
+//            where the caller takes none, [chunk][n_el][t (t + 1) / 2], and beside an eigenstrain (hommx_secant_load_source) the
+//            eigenstress of the round, [chunk][n_el][t] (secant_run)
 enum {
   B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, B_SENS2, B_TANGENT, B_CURVATURE,
   B_POLAR, B_SECANT, N_BUF
@@ -1692,19 +1693,30 @@ int64_t tangent_stream_doubles(const hommx_plan* p) { return p->n_el * (p->ks.t 
 // hist: the history variables of the law (null: none, and every launch is the one it was) -- the rounds are k_secant_history's, reading
 // history_in and writing history_out of the chunk, and the tail is k_secant_tangent_history on the law truncated behind the last
 // component's STORE
+// load: the one load of the chunk beside the law (null: none, and every launch is the one it was) -- per round
+// the eigenstress of the current stream where the flag is set (k_eigenstress into scratch of the chunk: the eigenstrain stays as it
+// is, every round and the kernels read it), the canonical correctors, the corrector of the load into the block behind them
+// (load_correctors: the block layout of crit_run), then k_secant_load; the tail is k_secant_tangent_load on the blocks of the last round
+struct SecantLoad {
+  int32_t code;     // HOMMX_LOADS_PER_CELL or HOMMX_LOADS_PROGRAM, alone or with HOMMX_LOADS_EIGENSTRAIN
+  const double* P;  // [nc][n_el][t] of the chunk: the caller's array, its copy in B_IN or the expansion of the program in B_POLAR
+};
 int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, const double* M, const hommx_secant_args& a, bool device,
-               hipStream_t st, const TangentTail* tail = nullptr, const hommx_history_args* hist = nullptr) {
+               hipStream_t st, const TangentTail* tail = nullptr, const hommx_history_args* hist = nullptr, const SecantLoad* load = nullptr) {
   const int t = p->ks.t, depth = program_depth(*a.program);
   const bool slot = !crit_in_lds(p, depth), tail_slot = tail && !tangent_in_lds(p, depth);
+  const bool eigen = load && load_eigenstrain(load->code);
   const size_t stream = sizeof(double) * p->n_el * p->ks.n_comp;
-  const size_t bytes[4] = {stream * chunk, stream * chunk, a.info ? 0 : sizeof(int32_t) * chunk,
-                           tail && !tail->coef ? sizeof(double) * tangent_stream_doubles(p) * chunk : 0};
-  char* at[4];
+  const size_t bytes[5] = {stream * chunk, stream * chunk, a.info ? 0 : sizeof(int32_t) * chunk,
+                           tail && !tail->coef ? sizeof(double) * tangent_stream_doubles(p) * chunk : 0,
+                           eigen ? sizeof(double) * p->n_el * t * chunk : 0};
+  char* at[5];
   if (int rc = carve(p->buf[B_SECANT], bytes, at)) return rc;
   double *cur = reinterpret_cast<double*>(at[0]), *cand = reinterpret_cast<double*>(at[1]);
   int32_t* info = a.info ? a.info : reinterpret_cast<int32_t*>(at[2]);
   HIP_TRY(hipMemcpyAsync(cur, a.coef_start ? a.coef_start : coef, stream * nc, hipMemcpyDeviceToDevice, st));
-  hommx::SecantHistoryArgs k;  // without a history its SecantArgs alone is launched
+  double* stress = reinterpret_cast<double*>(at[4]);  // the eigenstress of the round
+  hommx::SecantLoadArgs k;  // without a load its SecantHistoryArgs alone is launched, without a history its SecantArgs
   set_geometry(p, k);
   if (hist) {
     k.hist_in = hist->history_in;
@@ -1733,11 +1745,23 @@ int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, con
   double* corr = nullptr;
   for (int j = 0; j < a.max_iter; ++j) {
     double* d_A_eff = a.A_eff;
-    if (int rc = chunk_correctors(p, nc, chunk, cur, M, &d_A_eff, info, slot || tail_slot ? 1 : 0, st, &corr)) return rc;
+    if (eigen) HIP_TRY(hommx::launch_eigenstress(p->desc.dim, p->desc.kind, cur, load->P, true, stress, 1, p->n_el, nc, st));
+    if (int rc = chunk_correctors(p, nc, chunk, cur, M, &d_A_eff, info, (load ? t : 0) + (slot || tail_slot ? 1 : 0), st, &corr)) return rc;
     k.corr = corr;
-    k.slot = slot ? corr + chunk * t * k.ndof : nullptr;
+    double* behind = corr + chunk * t * k.ndof;
+    if (load) {
+      const double* P = eigen ? stress : load->P;
+      if (int rc = load_correctors(p, nc, chunk, cur, M, hommx::LoadOverride{P, 1, true}, st, behind)) return rc;
+      k.load.chi = behind;
+      k.load.P = eigen ? nullptr : P;
+      k.load.E = eigen ? load->P : nullptr;
+      behind += chunk * t * k.ndof;
+    }
+    k.slot = slot ? behind : nullptr;
     k.round = j;
-    HIP_TRY(hist ? hommx::launch_secant_history(k, depth, nc, st) : hommx::launch_secant(k, depth, nc, st));
+    HIP_TRY(load   ? hommx::launch_secant_load(k, depth, nc, st)
+            : hist ? hommx::launch_secant_history(k, depth, nc, st)
+                   : hommx::launch_secant(k, depth, nc, st));
     if (device) continue;
     seen.resize(HOMMX_SECANT_NSTATE * nc);
     HIP_TRY(hipMemcpy(seen.data(), a.state, sizeof(double) * seen.size(), hipMemcpyDeviceToHost));
@@ -1747,7 +1771,7 @@ int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, con
   }
   if (a.coef_out) HIP_TRY(hipMemcpyAsync(a.coef_out, cur, stream * nc, hipMemcpyDeviceToDevice, st));
   if (!tail) return HOMMX_OK;
-  hommx::SecantTangentHistoryArgs g;  // likewise
+  hommx::SecantTangentLoadArgs g;  // likewise
   set_geometry(p, g);
   g.corr = corr;
   g.M = M;
@@ -1761,14 +1785,20 @@ int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, con
   g.state = a.state;
   g.tan = tail->coef ? tail->coef : reinterpret_cast<double*>(at[3]);
   g.asym = tail->asymmetry;
-  g.slot = tail_slot ? corr + chunk * t * g.ndof : nullptr;
+  g.slot = tail_slot ? corr + chunk * (load ? 2 : 1) * t * g.ndof : nullptr;
+  if (load) {  // the blocks of the last executed round
+    g.corr_load = k.load.chi;
+    g.E = k.load.E;
+  }
   if (hist) {
     g.hist_in = hist->history_in;
     g.n_history = hist->n_history;
     for (int pc = 0; pc < a.program->n_ops; ++pc)  // the updates stand behind the last component's STORE
       if (a.program->ops[2 * pc] == hommx::OP_STORE && a.program->ops[2 * pc + 1] < p->ks.n_comp) g.prog.n_ops = pc + 1;
   }
-  HIP_TRY(hist ? hommx::launch_secant_tangent_history(g, depth, nc, st) : hommx::launch_secant_tangent(g, depth, nc, st));
+  HIP_TRY(load   ? hommx::launch_secant_tangent_load(g, depth, nc, st)
+          : hist ? hommx::launch_secant_tangent_history(g, depth, nc, st)
+                 : hommx::launch_secant_tangent(g, depth, nc, st));
   if (int rc = solve_source_device(tail->plan, nc, sampled_source(g.tan), M, tail->tangent, tail->info, st)) return rc;
   HIP_TRY(hommx::launch_tangent_mask(a.state, tail->tangent, t * t, nc, st));
   return HOMMX_OK;
@@ -1806,41 +1836,98 @@ int secant_checks(const hommx_plan* p, const hommx_secant_args* a, const hommx_h
   return HOMMX_OK;
 }
 
-// the argument checks of both entry points, then a route that forms correctors
-int secant_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_args* a, bool device,
-                const hommx_history_args* const* hist = nullptr) {
-  return source_open(p, n_cells, src, a, device, [&] { return secant_checks(p, a, hist); });
+// the load of the entries that take one (hommx_secant_load_args), against the plan's descriptor
+int secant_load_checks(const hommx_plan* p, const hommx_secant_load_args* l) {
+  if (!l) return fail(HOMMX_EINVAL, "null load arguments");
+  if (int rc = load_code_check(p, 1, l->per_cell, l->P_source)) return rc;
+  if (load_form(l->per_cell) == HOMMX_LOADS_SHARED)
+    return fail(HOMMX_EINVAL, "a law takes its load per cell (HOMMX_LOADS_PER_CELL) or as a program (HOMMX_LOADS_PROGRAM): points is the "
+                              "one array every cell shares");
+  if (load_form(l->per_cell) == HOMMX_LOADS_PER_CELL && !l->P) return fail(HOMMX_EINVAL, "null P");
+  return HOMMX_OK;
 }
 
-// the arguments of a call as the chunk driver re-bases them: the iteration's and the history's (n_history 0, null pointers: none)
+// what a call with a load needs beside a route that forms correctors: a load solve, as crit_open
+int secant_load_routes(hommx_plan* p) {
+  if (int rc = load_solve_check(p)) return rc;
+  if (int rc = load_workspace(p)) return rc;
+  return GO;
+}
+
+// the argument checks of both entry points, then a route that forms correctors; load: the call is one of the load entries, whose
+// struct *load is checked behind the iteration's and which needs a load solve as well
+int secant_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_args* a, bool device,
+                const hommx_history_args* const* hist = nullptr, const hommx_secant_load_args* const* load = nullptr) {
+  auto checks = [&] {
+    if (int rc = secant_checks(p, a, hist)) return rc;
+    return load ? secant_load_checks(p, *load) : HOMMX_OK;
+  };
+  if (int rc = source_open(p, n_cells, src, a, device, checks); rc != GO) return rc;
+  return load ? secant_load_routes(p) : GO;
+}
+
+// the arguments of a call as the chunk driver re-bases them: the iteration's, the history's (n_history 0, null pointers: none) and
+// the load's (has_load false: none)
 struct SecantCall {
   hommx_secant_args s;
   hommx_history_args h;
+  bool has_load;
+  SecantLoad l;
 };
+
+// what secant_call and secant_tangent_call hold of a load: the program source of its own beside the coefficient's, and the bytes per
+// cell a chunk holds of it beside the caller's array -- the second corrector block, the expansion of a program, the eigenstress
+struct SecantLoadPlan {
+  bool program = false;
+  ProgramLoad prog{};
+  size_t scratch = 0;
+  int64_t field = 0;  // doubles per cell of the load array (0: no load)
+};
+SecantLoadPlan secant_load_plan(const hommx_plan* p, const hommx_secant_load_args* load, SecantLoad* l, bool* has_load) {
+  SecantLoadPlan q;
+  *has_load = load != nullptr;
+  *l = SecantLoad{0, nullptr};
+  if (!load) return q;
+  q.program = load_form(load->per_cell) == HOMMX_LOADS_PROGRAM;
+  *l = SecantLoad{load->per_cell, q.program ? nullptr : load->P};
+  q.field = p->n_el * p->ks.t;
+  if (q.program) {
+    const hommx_coef_source& s = *load->P_source;
+    q.prog = {program_source(s.program, s.n_q, s.table, s.weights, s.params, s.n_fields), &l->P};
+  }
+  q.scratch = sizeof(double) * (plan_ndof(p) * p->ks.t + (q.program ? q.field : 0) + (load_eigenstrain(load->per_cell) ? q.field : 0));
+  return q;
+}
 
 // The current and the candidate stream of a chunk, the info of its eliminations and the slot of a field that does not fit LDS beside the
 // stack (where the chunk rule of the reconstruction does not count one already) are scratch of the chunk
 // hist: history_in is a per-cell input and history_out a per-cell output of the chunk, counted as coef_start and coef_out are
+// load: with it a chunk holds a second corrector block per cell and ends every round in a load solve (load_chunk), and the load array
+// is a per-cell input of the chunk (a program: its expansion, ProgramLoad)
 int secant_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_secant_args& args, bool device,
-                hipStream_t st, const hommx_history_args* hist = nullptr) {
+                hipStream_t st, const hommx_history_args* hist = nullptr, const hommx_secant_load_args* load = nullptr) {
   const int64_t t = p->ks.t, field = p->n_el * t, stream = p->n_el * p->ks.n_comp;
   Chunk<SecantCall> v{};
-  v.a = SecantCall{args, hist ? *hist : hommx_history_args{}};
+  v.a = SecantCall{args, hist ? *hist : hommx_history_args{}, false, {}};
   hommx_secant_args& a = v.a.s;
   hommx_history_args& h = v.a.h;
+  SecantLoadPlan lp = secant_load_plan(p, load, &v.a.l, &v.a.has_load);
   const bool own_slot = !crit_in_lds(p, program_depth(*a.program)) && recon_in_lds(p);
-  const size_t scratch = sizeof(double) * (2 * stream + (own_slot ? plan_ndof(p) : 0)) + sizeof(int32_t);
+  const size_t scratch = sizeof(double) * (2 * stream + (own_slot ? plan_ndof(p) : 0)) + sizeof(int32_t) + lp.scratch;
   const CellArray in[] = {{&a.rows, hommx::program_row_doubles(a.n_fields)},
                           {&a.xi, t},
                           {&a.coef_start, stream},
                           {&h.history_in, p->n_el * h.n_history},
+                          {&v.a.l.P, lp.field},
                           {&a.points, p->n_el * p->desc.dim, SHARED}};
   const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE}, {&a.A_eff, t * t, KEPT}, {&a.mean_flux, t},      {&a.coef_out, stream},
                            {&a.strain, field},              {&a.flux, field},        {&a.law_values, stream}, {&h.history_out, p->n_el * h.n_history}};
-  return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, recon_chunk, device, st,
+  return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, load ? load_chunk : recon_chunk, device, st,
                       [&](int64_t nc, int64_t chunk, const Chunk<SecantCall>& c) {
-                        return secant_run(p, nc, chunk, c.coef, c.M, c.a.s, device, st, nullptr, c.a.h.n_history ? &c.a.h : nullptr);
-                      });
+                        return secant_run(p, nc, chunk, c.coef, c.M, c.a.s, device, st, nullptr, c.a.h.n_history ? &c.a.h : nullptr,
+                                          c.a.has_load ? &c.a.l : nullptr);
+                      },
+                      nullptr, false, lp.program ? &lp.prog : nullptr);
 }
 
 // -- the consistent tangent of the secant response (hommx_secant_tangent_source[_device]) -------------------------------------------------
@@ -1851,15 +1938,19 @@ struct SecantTangentCall {
   double *tangent, *asymmetry, *coef;
   int32_t* info;
   hommx_history_args h;  // n_history 0, null pointers: none
+  bool has_load;         // false: none
+  SecantLoad l;
 };
 
 // everything secant_open checks, then the tangent's own arguments against the descriptors of both plans alone (of a mesh plan, whose
 // descriptor has no size, the element and node counts as well)
 int secant_tangent_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_tangent_args* a, bool device,
-                        const hommx_history_args* const* hist = nullptr) {
+                        const hommx_history_args* const* hist = nullptr, const hommx_secant_load_args* const* load = nullptr) {
   auto checks = [&] {
     if (!a->secant) return fail(HOMMX_EINVAL, "null secant arguments");
     if (int rc = secant_checks(p, a->secant, hist)) return rc;
+    if (load)
+      if (int rc = secant_load_checks(p, *load)) return rc;
     const hommx_secant_args& s = *a->secant;
     const hommx::KindSizes ks = hommx::kind_sizes(p->desc.dim, p->desc.kind);
     if (!a->tangent_plan || !a->tangent || !a->asymmetry) return fail(HOMMX_EINVAL, "null tangent_plan / tangent / asymmetry");
@@ -1885,35 +1976,41 @@ int secant_tangent_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source*
     }
     return HOMMX_OK;
   };
-  return source_open(p, n_cells, src, a, device, checks);
+  if (int rc = source_open(p, n_cells, src, a, device, checks); rc != GO) return rc;
+  return load ? secant_load_routes(p) : GO;
 }
 
 int secant_tangent_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_secant_tangent_args& args,
-                        bool device, hipStream_t st, const hommx_history_args* hist = nullptr) {
+                        bool device, hipStream_t st, const hommx_history_args* hist = nullptr, const hommx_secant_load_args* load = nullptr) {
   const int64_t t = p->ks.t, field = p->n_el * t, stream = p->n_el * p->ks.n_comp, tan = tangent_stream_doubles(p);
   Chunk<SecantTangentCall> v{};
   v.a = SecantTangentCall{*args.secant,      args.tangent_plan, args.tangent, args.asymmetry, args.tangent_coef,
-                          args.tangent_info, hist ? *hist : hommx_history_args{}};
+                          args.tangent_info, hist ? *hist : hommx_history_args{}, false, {}};
   hommx_secant_args& a = v.a.s;
   hommx_history_args& h = v.a.h;
+  SecantLoadPlan lp = secant_load_plan(p, load, &v.a.l, &v.a.has_load);
   const int depth = program_depth(*a.program);
   const bool own_slot = (!crit_in_lds(p, depth) || !tangent_in_lds(p, depth)) && recon_in_lds(p);
-  const size_t scratch = sizeof(double) * (2 * stream + (own_slot ? plan_ndof(p) : 0) + (args.tangent_coef ? 0 : tan)) + sizeof(int32_t);
+  const size_t scratch =
+      sizeof(double) * (2 * stream + (own_slot ? plan_ndof(p) : 0) + (args.tangent_coef ? 0 : tan)) + sizeof(int32_t) + lp.scratch;
   const CellArray in[] = {{&a.rows, hommx::program_row_doubles(a.n_fields)},
                           {&a.xi, t},
                           {&a.coef_start, stream},
                           {&h.history_in, p->n_el * h.n_history},
+                          {&v.a.l.P, lp.field},
                           {&a.points, p->n_el * p->desc.dim, SHARED}};
   const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE}, {&a.A_eff, t * t, KEPT}, {&a.mean_flux, t},
                            {&a.coef_out, stream},           {&a.strain, field},      {&a.flux, field},
                            {&a.law_values, stream},         {&v.a.tangent, t * t},   {&v.a.asymmetry, 1},
                            {&v.a.coef, tan},                {&v.a.info, 1, PER_CELL, sizeof(int32_t)},
                            {&h.history_out, p->n_el * h.n_history}};
-  return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, recon_chunk, device, st,
+  return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, load ? load_chunk : recon_chunk, device, st,
                       [&](int64_t nc, int64_t chunk, const Chunk<SecantTangentCall>& c) {
                         const TangentTail tail{c.a.plan, c.a.tangent, c.a.asymmetry, c.a.coef, c.a.info};
-                        return secant_run(p, nc, chunk, c.coef, c.M, c.a.s, device, st, &tail, c.a.h.n_history ? &c.a.h : nullptr);
-                      });
+                        return secant_run(p, nc, chunk, c.coef, c.M, c.a.s, device, st, &tail, c.a.h.n_history ? &c.a.h : nullptr,
+                                          c.a.has_load ? &c.a.l : nullptr);
+                      },
+                      nullptr, false, lp.program ? &lp.prog : nullptr);
 }
 
 // -- second derivatives (hommx_second_sensitivity_source[_device]) ------------------------------------------------------------------------
@@ -2121,6 +2218,33 @@ int hommx_secant_tangent_history_source(hommx_plan* p, int64_t n_cells, const ho
                                         const hommx_secant_tangent_args* args, const hommx_history_args* history) {
   if (int rc = secant_tangent_open(p, n_cells, src, args, false, &history); rc != GO) return rc;
   return secant_tangent_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr, history);
+}
+
+int hommx_secant_load_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                    const hommx_secant_args* args, const hommx_history_args* history, const hommx_secant_load_args* load,
+                                    void* stream) {
+  if (int rc = secant_open(p, n_cells, src, args, true, history ? &history : nullptr, &load); rc != GO) return rc;
+  return secant_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream), history, load);
+}
+
+int hommx_secant_load_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_secant_args* args,
+                             const hommx_history_args* history, const hommx_secant_load_args* load) {
+  if (int rc = secant_open(p, n_cells, src, args, false, history ? &history : nullptr, &load); rc != GO) return rc;
+  return secant_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr, history, load);
+}
+
+int hommx_secant_tangent_load_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                            const hommx_secant_tangent_args* args, const hommx_history_args* history,
+                                            const hommx_secant_load_args* load, void* stream) {
+  if (int rc = secant_tangent_open(p, n_cells, src, args, true, history ? &history : nullptr, &load); rc != GO) return rc;
+  return secant_tangent_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream), history, load);
+}
+
+int hommx_secant_tangent_load_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M,
+                                     const hommx_secant_tangent_args* args, const hommx_history_args* history,
+                                     const hommx_secant_load_args* load) {
+  if (int rc = secant_tangent_open(p, n_cells, src, args, false, history ? &history : nullptr, &load); rc != GO) return rc;
+  return secant_tangent_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr, history, load);
 }
 
 int hommx_second_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,

@@ -295,6 +295,25 @@ hipError_t launch_secant_tangent_history(const SecantTangentHistoryArgs& a, int 
 // tangent[cell][tt] = NaN for every cell whose status (state[cell][2]) is 2 or 3
 hipError_t launch_tangent_mask(const double* state, double* tangent, int tt, long long nc, hipStream_t stream);
 
+// secant_load.hip: the round and the tangent coefficient beside ONE load per cell (include/hommx_hip.h, hommx_secant_load_source;
+// DESIGN.md section 4.18).  What a loaded round reads beside SecantArgs:
+struct RoundLoad {
+  const double* chi = nullptr;       // [nc][t][ndof]: row 0 of a cell is the corrector of its load on the current stream
+  const double* P = nullptr;         // [nc][n_el][t]: the polarisation, or null (the eigenstrain code)
+  const double* E = nullptr;         // [nc][n_el][t]: the eigenstrain, or null (the polarisation code); exactly one of the two is set
+};
+// n_history == 0: a law without history variables (hist_in and hist_out are then not read)
+struct SecantLoadArgs : SecantHistoryArgs {
+  RoundLoad load;
+};
+hipError_t launch_secant_load(const SecantLoadArgs& a, int depth, long long nc, hipStream_t stream);
+// the tangent at the strain the law saw: the total one beside a polarisation (E null), the elastic one beside an eigenstrain
+struct SecantTangentLoadArgs : SecantTangentHistoryArgs {
+  const double* corr_load = nullptr; // [nc][t][ndof]: row 0 is the corrector of the load on `cur`
+  const double* E = nullptr;         // [nc][n_el][t] or null
+};
+hipError_t launch_secant_tangent_load(const SecantTangentLoadArgs& a, int depth, long long nc, hipStream_t stream);
+
 // the loads a corrector pass of the blocked family solves for instead of the canonical ones: rows l < n_loads of Brhs from P (device), the
 // rest zero.  P starts at the first cell of the call
 struct LoadOverride {

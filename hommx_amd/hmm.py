@@ -330,7 +330,8 @@ class BaseHMM(ABC):
         self.tangent_tensors = None  # D = d sigma_H / d xi per macro cell of the last solve_nonlinear(method="newton")
         self.history = None  # [cells of this rank, n_el, n_history]: the committed history variables of a law that has some
         self.history_trial = None  # ... and what the last step of the last solve_nonlinear left: commit_history() makes it the state
-        self._linearisation_load = None  # P_T of the Newton step solve() is serving (solve_nonlinear sets and clears it)
+        self._linearisation_load = None  # P_T of the macro step solve() is serving (solve_nonlinear sets and clears it)
+        self._nonlinear_load = False  # solve() serves a step of solve_nonlinear(load=True): the load is inside _linearisation_load
         self._tangent_plan = None  # the sibling plan of the tangent kind (solve_nonlinear(method="newton") builds and keeps it)
         self._tangent_reserved = 0  # ... and the cells it is reserved for
         self._Dtheta_t = None
@@ -1038,10 +1039,10 @@ class BaseHMM(ABC):
         self._assemble_stiffness()
         A = self._A.copy()
         b = fem.assemble_load_vector(self._V_macro, self._f, self._rhs_degree)
-        if self._polarisation is not None:  # b_T of the effective polarisation, before the Dirichlet lifting
+        if self._polarisation is not None and not self._nonlinear_load:  # b_T of the effective polarisation, before the Dirichlet lifting
             self.effective_polarisation = self._effective_polarisation(np.arange(self._msh.num_cells))
             self._add_cell_load(b, self.effective_polarisation)
-        if self._linearisation_load is not None:  # ... and of a Newton step of solve_nonlinear: P_T = sigma_T - D_T xi_T
+        if self._linearisation_load is not None:  # ... and of a macro step of solve_nonlinear: P_T = sigma_T - D_T xi_T
             self._add_cell_load(b, self._linearisation_load)
         for bc in self._bcs:  # hmm.py:453-480, bc by bc
             idx, val = bc.unrolled()
@@ -1197,31 +1198,41 @@ class BaseHMM(ABC):
         return tp
 
     def _secant_tensors(self, cells: np.ndarray, xi: np.ndarray, law: SecantLaw, rows: np.ndarray, points: np.ndarray, chunk_cells,
-                        tangent: bool = False, history: np.ndarray | None = None, **kw) -> SecantResult:
+                        tangent: bool = False, history: np.ndarray | None = None, load: bool = False, **kw) -> SecantResult:
         """``plan.secant`` of ``law`` on ``cells`` under the macro strains ``xi``, chunk by chunk -> one ``SecantResult`` with ``cells``;
         ``tangent``: ``plan.secant_tangent`` on the sibling plan instead, with ``tangent`` and ``asymmetry``.  Under a process group
         every rank iterates its block and one all-gather of t t + t + 3 numbers per cell (2 t t + t + 4 with the tangent; and the info
         flags) returns the fields to every rank, as ``_effective_polarisation`` does.  ``history``: the history variables of THIS
         RANK'S block of ``cells`` (all of them without a process group), passed to the plan chunk by chunk; what the plan returns for
-        the block goes to ``history_trial`` and is not gathered."""
+        the block goes to ``history_trial`` and is not gathered.  ``load``: the polarisation or the eigenstrain of the solver enters
+        every round (``plan.secant(P=...)``), sampled chunk by chunk as ``criterion()`` samples it -- an ``Expression`` as
+        its program where the plan takes load sources; an eigenstrain crosses AS IT IS, since its eigenstress belongs to the
+        current stream of every round."""
         t = self._tensor_size()
 
         def bytes_per_cell():
             out = 8 * (3 + t * t + t + (t * t + 1 if tangent else 0)) + 4
+            if load and not isinstance(self._polarisation, Expression):
+                out += 8 * self._cell_mesh.num_cells * t  # a sampled load
             if history is not None:  # in and out
                 out += 16 * self._cell_mesh.num_cells * history.shape[2]
             return out if self._sampled_on_device() else out + self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) * 8
 
+        def sample(sub, kind):  # (P, per_cell, eigenstrain) as plan.secant takes them
+            return self._load_input(sub, self._loads_on_device(kind)) + (self._eigenstrain,)
+
         def local(b, e):
-            def call(plan, coef, M, _, sub, at):
+            def call(plan, coef, M, P, sub, at):
                 args = dict(rows=rows[b + at:b + at + len(sub)], points=points, **kw)
+                if P is not None:
+                    args.update(P=P[0], per_cell=P[1], eigenstrain=P[2])
                 if history is not None:
                     args["history"] = history[at:at + len(sub)]
                 if not tangent:
                     return plan.secant(coef, xi[b + at:b + at + len(sub)], law, M, **args)
                 return plan.secant_tangent(coef, xi[b + at:b + at + len(sub)], law, self._ensure_tangent_plan(plan), M, **args)
 
-            r = _join(self._chunks(cells[b:e], chunk_cells, bytes_per_cell, call), cells=cells[b:e])
+            r = _join(self._chunks(cells[b:e], chunk_cells, bytes_per_cell, call, sample if load else None), cells=cells[b:e])
             if history is not None:
                 self.history_trial = r.history
             return r
@@ -1246,7 +1257,8 @@ class BaseHMM(ABC):
         return out
 
     def solve_nonlinear(self, law: SecantLaw, max_iter: int = 30, tol: float = 1e-8, micro_iter: int = 50, micro_tol: float = 1e-10,
-                        relax: float = 1.0, field_values=None, u0=None, chunk_cells: int | None = None, method: str = "secant") -> fem.Function:
+                        relax: float = 1.0, field_values=None, u0=None, chunk_cells: int | None = None, method: str = "secant",
+                        load: bool = False) -> fem.Function:
         """The two-scale problem with a strain-dependent micro coefficient ``law`` (a ``SecantLaw``: the entries of the coefficient of a
         micro element as expressions of its own strain ``e``, secant stress ``s`` and base coefficient ``c``, the solver's ``A``), by
         the Kacanov (secant) iteration on both scales.  u^0 is ``u0`` (a macro ``fem.Function`` or its dof array) or
@@ -1269,7 +1281,17 @@ class BaseHMM(ABC):
         does under ``"secant"``, and the status WARNING counts it).  One WARNING when the largest ``asymmetry`` exceeds 1e-8: the law then has no potential and the steps
         are quasi-Newton steps with the symmetric part of the tangent.
 
-        ``RuntimeError`` when a polarisation is set (loads beside a law are out of scope), the law reads fields without
+        ``load=True``: the polarisation or the eigenstrain of the solver (``set_polarisation`` / ``set_eigenstrain``, a
+        device-sampled ``Expression`` with its ``set_polarisation_fields`` included) enters every micro iteration
+        (hommx_secant_load_source): every round of every box ends in a load solve on its current stream.  Beside a polarisation the
+        law reads the total strain and the total flux; beside an eigenstrain the elastic strain ``e - E`` and ``material . (e - E)``:
+        thermal damage, swelling, prestress in a softening matrix.  In BOTH methods the macro step then takes its load from
+        P_T = sigma_T - matrix xi_T, as Newton does: for ``"secant"`` the matrix is the secant tensor and P_T the effective
+        polarisation of the secant state.  Afterwards ``effective_polarisation`` holds mean_flux - A_eff xi of the last step.
+        ``RuntimeError`` naming the two setters when nothing is set.  With ``load=False`` and a polarisation set the call raises
+        ``RuntimeError`` (pass ``load=True``): a load is never dropped silently.
+
+        ``RuntimeError`` as well when the law reads fields without
         ``field_values``, or ``method="newton"`` meets a law that reads ``s[k]`` (the tangent of an implicit law is out of scope).
         A law with history variables (``SecantLaw(history=[...])``) reads ``self.history[cells, n_el, n_history]``, created
         from ``law.history_initial`` on first use: every macro step passes that same frozen state to the plan (``h[k]`` is the state
@@ -1282,12 +1304,15 @@ class BaseHMM(ABC):
         boundary in each direction per macro step (DESIGN 4.17 has the measured cost); ``MicroCellPlan.secant_device`` keeps it
         resident for callers who drive the plan themselves.
 
-        Out of scope as well: warm starts of the micro iteration
+        Out of scope: warm starts of the micro iteration
         across macro steps (``MicroCellPlan.secant(coef_start=...)`` has them), ``reconstruct()`` / ``criterion()`` of the nonlinear
         state (``MicroCellPlan.secant(return_coef=True)`` gives the stream to pass to them).  Under a process group every rank
         iterates its block of the cells, as in ``solve()``."""
-        if self._polarisation is not None:
-            raise RuntimeError("solve_nonlinear() does not take a polarisation or eigenstrain: loads beside a law are out of scope")
+        if self._polarisation is not None and not load:
+            raise RuntimeError("solve_nonlinear() does not take the polarisation or eigenstrain that is set unless it is told to: pass "
+                               "load=True to solve with it, or clear it (set_polarisation(None))")
+        if load and self._polarisation is None:
+            raise RuntimeError("solve_nonlinear(load=True) needs a load: call set_polarisation() or set_eigenstrain() first")
         if law.n_fields and field_values is None:
             raise RuntimeError(f"the law reads the fields {', '.join(law.field_names)}: pass field_values, their values per macro cell")
         if method not in ("secant", "newton"):
@@ -1306,20 +1331,24 @@ class BaseHMM(ABC):
         history, converged, result = [], False, None
         for _ in range(int(max_iter)):
             xi = self._macro_strains(cells, u)
-            result = self._secant_tensors(cells, xi, law, rows, points, chunk_cells, tangent=newton, history=state, max_iter=micro_iter,
-                                          tol=micro_tol, relax=relax)
+            result = self._secant_tensors(cells, xi, law, rows, points, chunk_cells, tangent=newton, history=state, load=load,
+                                          max_iter=micro_iter, tol=micro_tol, relax=relax)
             matrix = result.A_eff
+            lost = (result.status >= 2)[:, None, None]
             if newton:  # a cell without a state to linearise at (status 2, 3: its tangent is NaN) takes the secant step, as "secant" does
-                lost = (result.status >= 2)[:, None, None]
                 matrix = np.where(lost, result.A_eff, result.tangent)
                 self.tangent_tensors = result.tangent
+            if newton or load:  # the constant part of the linearised response; beside a load also under "secant": its effective polarisation
                 self._linearisation_load = np.where(lost[:, :, 0], 0.0, result.mean_flux - np.einsum("cmn,cn->cm", matrix, xi))
             self._set_macro_matrix(self._local_stiffness_from_tensors(cells, matrix))
             self.effective_tensors, self.cell_info = result.A_eff, result.info
+            self._nonlinear_load = bool(load)
             try:
                 new = self.solve().x.array.copy()
             finally:
-                self._linearisation_load = None
+                self._linearisation_load, self._nonlinear_load = None, False
+            if load:
+                self.effective_polarisation = result.mean_flux - np.einsum("cmn,cn->cm", result.A_eff, xi)
             change, scale = float(np.abs(new - u).max()), float(np.abs(new).max())
             history.append(change / scale if scale > 0.0 else 0.0)
             u = new

@@ -744,7 +744,7 @@ int hommx_criterion_source_device(hommx_plan* plan, int64_t n_cells, const hommx
  *   coef_out    [n_cells][n_el][n_comp] or NULL
  *   strain, flux [n_cells][n_el][t], both or neither;  law_values [n_cells][n_el][n_comp] = v_K or NULL
  *   info        as hommx_solve_batch, or NULL
- * src, M: as hommx_reconstruct_source.  A load is out of scope.  HOMMX_EINVAL, before the plan's device is made current: a null plan,
+ * src, M: as hommx_reconstruct_source.  A load beside the law: hommx_secant_load_source.  HOMMX_EINVAL, before the plan's device is made current: a null plan,
  * source, argument struct, program, rows, xi, state or A_eff; one of strain / flux without the other; everything a program is refused
  * for against n_comp == the plan's and a row of 3 + n_fields + 2 t + n_comp entries; a Y in the program with points NULL; max_iter
  * < 1; tol negative or NaN; relax outside (0, 1].  The chunk is that of the reconstruction, with the current and the candidate stream
@@ -858,6 +858,56 @@ int hommx_secant_tangent_history_source(hommx_plan* plan, int64_t n_cells, const
 /* Same with DEVICE pointers, asynchronous on `stream`. */
 int hommx_secant_tangent_history_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                                                const hommx_secant_tangent_args* args, const hommx_history_args* history, void* stream);
+
+/*
+ * A load beside a law: the secant iteration with ONE polarisation or eigenstrain per cell (n_loads == 1),
+ * solved for in every round.  The load comes per cell or as a program, in the codes of hommx_load_args.per_cell:
+ *   per_cell    HOMMX_LOADS_PER_CELL (P[n_cells][n_el][t]) or HOMMX_LOADS_PROGRAM (P is not read; the load is sampled on the device
+ *               from P_source, a HOMMX_COEF_PROGRAM source with n_comp == t, as hommx_load_args describes), alone or or-ed with
+ *               HOMMX_LOADS_EIGENSTRAIN.  HOMMX_LOADS_SHARED is refused, as hommx_criterion_source refuses it.
+ *   P           the polarisation P_K[t] (shear not doubled) or, with the flag, the eigenstrain E_K[t] (shear doubled)
+ *   P_source    read only when (per_cell & 3) == HOMMX_LOADS_PROGRAM
+ * Round j of cell T on its current stream c^j:
+ *   1. with the flag only: the eigenstress of the round, P^j = -material(c^j) E, into scratch of the chunk.  The eigenstrain array is
+ *      never overwritten -- every round and the round kernel read it --, a host call's staged array and the expansion of a program
+ *      included; the chunk rule counts the extra field;
+ *   2. the canonical correctors and A^j, as hommx_secant_source forms them;
+ *   3. the corrector chi_P^j of the load on c^j, on the route hommx_plan_load_kernel_name names, behind the canonical block (the
+ *      block layout and the chunk rule of hommx_criterion_source with a load);
+ *   4. the round of hommx_secant_source on X = sum_m xi_m chi_m + chi_P^j, where the law reads
+ *        a polarisation:  e[k] the total strain e_K, s[k] the total flux q_K = material(c^j_K) e_K + P_K, as a criterion sees it;
+ *        an eigenstrain:  e[k] the elastic strain g_K = e_K - E_K (one rounded subtraction per component), s[k] q_K = material(c^j_K) g_K
+ *      -- the model sigma = c(eps - eps*) (eps - eps*), which keeps a strain-driven law explicit.  The `strain` output is what e[k]
+ *      read, `flux` is q_K, and mean_flux = sum |K| q_K.
+ * The effective polarisation of the stopping state needs no output of its own: it is mean_flux - A_eff xi (Levin's identity).  The
+ * tangent entries give D = d mean_flux / d xi unchanged in form, the effective tensor of the element tangents T_K, evaluated at the
+ * strain the law saw (total or elastic).  Everything else is hommx_secant_source's, resp. hommx_secant_tangent_source's: the status
+ * rules and frozen cells, commits on non-stopping rounds only, fixed-order reductions, the independence of chunking, batch position,
+ * max_iter, the outputs asked for and the entry point; the device entries queue exactly max_iter rounds and read nothing back.
+ * history: NULL for a law without history variables, else as the history entries take it.
+ * HOMMX_EINVAL, before the plan's device is made current: everything the entry without a load refuses (with or without history); a
+ * null load struct; an unknown code in per_cell; HOMMX_LOADS_SHARED; a null P for HOMMX_LOADS_PER_CELL; for HOMMX_LOADS_PROGRAM a null
+ * P_source, one of another form, or a program whose n_comp is not t.  HOMMX_EINVAL as well, before any work: a plan of the frontal
+ * mesh route created without HOMMX_MESH_FLAG_LOADS.
+ */
+typedef struct hommx_secant_load_args {
+  int32_t per_cell;
+  const double* P;
+  const hommx_coef_source* P_source;
+} hommx_secant_load_args;
+int hommx_secant_load_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_secant_args* args,
+                             const hommx_history_args* history /* NULL: none */, const hommx_secant_load_args* load);
+/* Same with DEVICE pointers (in *src, *args, *history, *load and *load->P_source; the structs and the programs are host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract). */
+int hommx_secant_load_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                    const hommx_secant_args* args, const hommx_history_args* history, const hommx_secant_load_args* load,
+                                    void* stream);
+int hommx_secant_tangent_load_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M,
+                                     const hommx_secant_tangent_args* args, const hommx_history_args* history /* NULL: none */,
+                                     const hommx_secant_load_args* load);
+/* Same with DEVICE pointers, asynchronous on `stream`. */
+int hommx_secant_tangent_load_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                            const hommx_secant_tangent_args* args, const hommx_history_args* history,
+                                            const hommx_secant_load_args* load, void* stream);
 
 /*
  * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
