@@ -250,6 +250,27 @@ class SecantLoadArgs(C.Structure):
     ]
 
 
+class SecantStateArgs(C.Structure):
+    """hommx_secant_state_args: the tail behind the secant iteration on the state it stopped in -- a criterion (its program on the
+    row ``[.. | c | h | b]``, its own fields and rows, the threshold and where its outputs go) and / or the reconstruction statistics."""
+
+    _fields_ = [
+        ("crit_program", C.POINTER(CoefProgram)),
+        ("crit_n_fields", C.c_int32),
+        ("crit_rows", C.c_void_p),
+        ("threshold", C.c_double),
+        ("crit", C.c_void_p),
+        ("crit_values", C.c_void_p),
+        ("total_strain", C.c_void_p),
+        ("total_flux", C.c_void_p),
+        ("reconstruct", C.c_int32),
+        ("n_regions", C.c_int32),
+        ("region", C.c_void_p),
+        ("stats", C.c_void_p),
+        ("region_stats", C.c_void_p),
+    ]
+
+
 def _prototypes() -> dict:
     """name -> (restype, argtypes) of every symbol include/hommx_hip.h declares: ``load()`` declares them from this table, and
     the tests check that the header and the library export exactly these names."""
@@ -316,6 +337,10 @@ def _prototypes() -> dict:
                                              C.POINTER(SecantLoadArgs)]),
         "hommx_secant_load_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantArgs), C.POINTER(HistoryArgs),
                                                     C.POINTER(SecantLoadArgs), vp]),
+        "hommx_secant_state_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantArgs), C.POINTER(HistoryArgs),
+                                              C.POINTER(SecantLoadArgs), C.POINTER(SecantStateArgs)]),
+        "hommx_secant_state_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantArgs), C.POINTER(HistoryArgs),
+                                                     C.POINTER(SecantLoadArgs), C.POINTER(SecantStateArgs), vp]),
         "hommx_secant_tangent_load_source": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantTangentArgs),
                                                      C.POINTER(HistoryArgs), C.POINTER(SecantLoadArgs)]),
         "hommx_secant_tangent_load_source_device": (c_int, [vp, i64, C.POINTER(CoefSource), vp, C.POINTER(SecantTangentArgs),

@@ -102,6 +102,7 @@ class Reconstruction:
     region_energy: np.ndarray | None = None
     region_max_flux: np.ndarray | None = None
     region_argmax_element: np.ndarray | None = None
+    secant = None  # an attribute, not a field: reconstruct(nonlinear=True) of the solver classes sets the SecantResult of its micro iteration
 
     @classmethod
     def from_stats(cls, xi, stats, A_eff, info, strain=None, flux=None, cells=None, region_stats=None) -> "Reconstruction":
@@ -222,6 +223,7 @@ class CriterionResult:
     strain: np.ndarray | None = None
     flux: np.ndarray | None = None
     cells: np.ndarray | None = None
+    secant = None  # an attribute, not a field: criterion(nonlinear=True) of the solver classes sets the SecantResult of its micro iteration
 
 
 @dataclass
@@ -241,7 +243,11 @@ class SecantResult:
     of the tangent kind that was eliminated.
 
     For a law with history variables ``history[N, n_el, n_history]``: the updates of the stopping round -- the input's
-    bits for a cell of status 2 or 3 --, what the next load step takes as its ``history`` once the caller commits it."""
+    bits for a cell of status 2 or 3 --, what the next load step takes as its ``history`` once the caller commits it.
+
+    With ``secant(criterion=...)`` / ``secant(reconstruct=True)`` (hommx_secant_state_source) ``criterion``, a
+    ``CriterionResult``, and ``reconstruction``, a ``Reconstruction``, of the state the iteration stopped in (their ``A_eff`` and
+    ``info`` are this result's); what a cell of status 3 holds there means nothing."""
 
     A_eff: np.ndarray
     mean_flux: np.ndarray
@@ -259,6 +265,8 @@ class SecantResult:
     tangent_info: np.ndarray | None = None
     tangent_coef: np.ndarray | None = None
     history: np.ndarray | None = None
+    criterion: CriterionResult | None = None
+    reconstruction: Reconstruction | None = None
 
 
 REGION_FIELDS = ("region_volume", "region_mean_strain", "region_mean_flux", "region_energy", "region_max_flux", "region_argmax_element")
@@ -786,9 +794,14 @@ class MicroCellPlan:
             r.argmax_element = stats[:, :, self.t + 1].astype(np.int64)
         return r
 
-    def _criterion_program(self, crit) -> Program:
-        """The program of a ``hommx_amd.expr.Criterion`` on this plan (its index checks against t and n_comp run here)."""
-        ops, consts = crit.program(self.t, self.n_comp)
+    def _criterion_program(self, crit, n_history: int | None = None) -> Program:
+        """The program of a ``hommx_amd.expr.Criterion`` on this plan (its index checks against t and n_comp run here); ``n_history``:
+        the history variables of the law whose state it is evaluated on (None: a criterion of the linear state)."""
+        if n_history is None and crit.reads_state:
+            names = ", ".join(f"{n}[{crit.state_indices[n] - 1}]" for n in "bh" if crit.state_indices[n])
+            raise ValueError(f"the criterion reads {names}, the nonlinear state: it is evaluated behind the secant iteration "
+                             "(secant(criterion=...), criterion(nonlinear=True) of the solver classes)")
+        ops, consts = crit.program(self.t, self.n_comp) if n_history is None else crit.program(self.t, self.n_comp, n_history)
         if crit.n_y > self.dim:
             raise ValueError(f"the criterion reads y[{crit.n_y - 1}]; the micro mesh has {self.dim} dimensions")
         return Program(np.ascontiguousarray(ops), np.ascontiguousarray(consts), 1, int(crit.n_params), int(crit.n_fields))
@@ -905,7 +918,9 @@ class MicroCellPlan:
 
     def secant(self, coef, xi: np.ndarray, law, M: np.ndarray | None = None, rows=None, points=None, max_iter: int = 50, tol: float = 1e-10,
                relax: float = 1.0, coef_start=None, fields: bool = False, values: bool = False, return_coef: bool = False,
-               history=None, P=None, per_cell: bool | None = None, eigenstrain: bool = False) -> SecantResult:
+               history=None, P=None, per_cell: bool | None = None, eigenstrain: bool = False, criterion=None, crit_rows=None,
+               crit_values: bool = False, crit_fields: bool = False, reconstruct: bool = False, regions=None,
+               n_regions: int | None = None) -> SecantResult:
         """The secant iteration of a strain-dependent coefficient (hommx_secant_source): ``coef`` an array or a ``CoefStream``, the BASE
         coefficient ``c`` of the law; xi and M as ``reconstruct`` takes them; ``law`` a ``hommx_amd.expr.SecantLaw`` with the plan's
         ``n_comp`` components -> ``SecantResult``.  Per cell and round: the correctors of the current stream on the plan's route, the
@@ -929,9 +944,82 @@ class MicroCellPlan:
         ``load_solve=True`` on the frontal mesh route).  A polarisation: the law reads the total strain in ``e`` and the total flux
         ``material . e + P`` in ``s``.  An eigenstrain: it reads the elastic strain ``e - E`` and ``material . (e - E)``, the model
         sigma = c(eps - eps*) (eps - eps*).  ``strain`` / ``flux`` are what the law read, ``mean_flux`` the mean of that flux, and the
-        effective polarisation of the stopping state is ``mean_flux - A_eff xi``.  With ``P=None`` the call is the one it was."""
+        effective polarisation of the stopping state is ``mean_flux - A_eff xi``.  With ``P=None`` the call is the one it was.
+
+        ``criterion`` / ``reconstruct``: a tail on the state every cell stops in (hommx_secant_state_source), without
+        another elimination and without the stream leaving the device.  ``criterion``: a ``hommx_amd.expr.Criterion``, which may read
+        ``b[k]`` (the base coefficient) and, declared with ``history=law.n_history``, ``h[k]`` (``history`` of this call) beside what
+        ``MicroCellPlan.criterion`` gives it; ``c[k]`` is the stream the iteration stopped on and ``e`` / ``s`` the TOTAL strain and
+        flux (``material . e + P``, P the polarisation or the eigenstress).  ``crit_rows[N_c, 3 + criterion.n_fields]``: the
+        criterion's own rows (default: the midpoints of ``rows``; required when it reads ``f``); ``crit_values`` / ``crit_fields``:
+        ``values`` / ``strain`` and ``flux`` of the ``CriterionResult``.  ``reconstruct`` (with ``regions`` / ``n_regions`` as
+        ``reconstruct`` takes them; not together with ``P``: the statistics have no load term) -> ``SecantResult.reconstruction``.
+        For a criterion that reads neither ``b`` nor ``h`` the results are bit for bit ``criterion(result.coef, ...)`` /
+        ``reconstruct(result.coef, ...)``.  With none of them the call is the one it was."""
+        tail = None
+        if criterion is not None or reconstruct:
+            tail = (criterion, crit_rows, bool(crit_values), bool(crit_fields), bool(reconstruct), regions, n_regions)
+        elif crit_rows is not None or crit_values or crit_fields or regions is not None:
+            raise ValueError("crit_rows / crit_values / crit_fields belong to criterion=..., regions to reconstruct=True")
         return self._secant(coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef, history=history,
-                            load=(P, per_cell, eigenstrain))
+                            load=(P, per_cell, eigenstrain), tail=tail)
+
+    def _state_tail(self, tail, law, stream, nc: int, rows, points, loaded: bool) -> tuple:
+        """The tail of ``secant`` as the library takes it -> (hommx_secant_state_args, what keeps its arrays alive, finish), where
+        ``finish(xi, A_eff, info)`` gives (``CriterionResult`` or None, ``Reconstruction`` or None) once the call has returned."""
+        crit, crit_rows, want_values, want_fields, recon, regions, n_regions = tail
+        addr = lambda a: None if a is None else a.ctypes.data
+        keep, sargs = [], _lib.SecantStateArgs()
+        out = vals = strain = flux = stats = rstats = None
+        if crit is not None:
+            prog = self._criterion_program(crit, int(law.n_history))
+            pstruct = prog.struct()
+            if crit_rows is None:
+                if crit.n_fields:
+                    raise ValueError(f"the criterion reads the fields {', '.join(crit.field_names)}: pass crit_rows[N_c, 3 + {crit.n_fields}]")
+                crit_rows = rows[:, :3]
+            crit_rows = np.ascontiguousarray(crit_rows, dtype=np.float64)
+            if crit_rows.shape != (nc, 3 + crit.n_fields):
+                raise ValueError(f"crit_rows has shape {crit_rows.shape}; expected ({nc}, 3 + {crit.n_fields}): the midpoint, then the "
+                                 "criterion's fields")
+            if crit.n_y and points is None:
+                raise ValueError(f"the criterion reads y[{crit.n_y - 1}]: pass points[n_el, dim], the element centroids")
+            out = np.empty((nc, _lib.CRIT_NSTATS), dtype=np.float64)
+            vals = np.empty((nc, self.n_el), dtype=np.float64) if want_values else None
+            strain = np.empty((nc, self.n_el, self.t), dtype=np.float64) if want_fields else None
+            flux = np.empty((nc, self.n_el, self.t), dtype=np.float64) if want_fields else None
+            sargs.crit_program, sargs.crit_n_fields, sargs.crit_rows = C.pointer(pstruct), int(crit.n_fields), crit_rows.ctypes.data
+            sargs.threshold, sargs.crit, sargs.crit_values = float(crit.threshold), out.ctypes.data, addr(vals)
+            sargs.total_strain, sargs.total_flux = addr(strain), addr(flux)
+            keep += [prog, pstruct, crit_rows]
+        elif crit_rows is not None or want_values or want_fields:
+            raise ValueError("crit_rows / crit_values / crit_fields belong to criterion=...")
+        if recon:
+            if loaded:
+                raise ValueError("reconstruct=True together with a load P: the reconstruction statistics have no load term; ask for "
+                                 "criterion=..., crit_fields=True, which returns the loaded state")
+            labels, nr = None, 0
+            if regions is True:
+                if stream.method != "solve_two_phase":
+                    raise ValueError("regions=True takes the mask of a two-phase stream as the labels; pass labels for any other coefficient")
+                nr = 2
+            elif regions is not None:
+                labels, nr = region_labels(regions, self.n_el, n_regions)
+            stats = np.empty((nc, 2 * self.t + 3), dtype=np.float64)
+            rstats = np.empty((nc, nr, 2 * self.t + 4), dtype=np.float64) if nr else None
+            sargs.reconstruct, sargs.n_regions, sargs.region = 1, nr, addr(labels)
+            sargs.stats, sargs.region_stats = stats.ctypes.data, addr(rstats)
+            keep += [labels]
+        elif regions is not None:
+            raise ValueError("regions belong to reconstruct=True")
+
+        def finish(xi, A, info):
+            c = None if out is None else CriterionResult(out[:, 0].copy(), out[:, 1].astype(np.int64), out[:, 2].copy(), out[:, 3].copy(),
+                                                         A, info, vals, strain, flux)
+            r = None if stats is None else Reconstruction.from_stats(xi, stats, A, info, region_stats=rstats)
+            return c, r
+
+        return sargs, keep, finish
 
     @property
     def tangent_kind(self) -> str:
@@ -972,10 +1060,11 @@ class MicroCellPlan:
                             return_tangent_coef, history, (P, per_cell, eigenstrain))
 
     def _secant(self, coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef, tangent_plan=None,
-                return_tangent_coef=False, history=None, load=(None, None, False)) -> SecantResult:
+                return_tangent_coef=False, history=None, load=(None, None, False), tail=None) -> SecantResult:
         """The host call of ``secant`` (``tangent_plan`` None) and ``secant_tangent``; with the history entries for a law that has
         history variables, and with the load entries (which take the history as an optional argument) for ``load`` = (P, per_cell,
-        eigenstrain) with a P."""
+        eigenstrain) with a P.  ``tail``: what ``secant`` asks for on the stopped state (hommx_secant_state_source, which takes the
+        history and the load as optional arguments)."""
         stream = self._as_stream(coef)
         nc = self._check_stream(stream)
         P, P_src, P_ptr, code = self._one_load(load[0], load[1], load[2], nc)
@@ -1017,6 +1106,21 @@ class MicroCellPlan:
         args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows.ctypes.data, addr(points), xi.ctypes.data, max_iter, tol, relax,
                                addr(coef_start), state.ctypes.data, None, mean_flux.ctypes.data, addr(out_coef), addr(strain), addr(flux),
                                addr(vals), None)
+        if tail is not None:
+            if tangent_plan is not None:
+                raise ValueError("a tail behind the tangent entries is out of scope: call secant(criterion=...) for the state")
+            sargs, keep, finish = self._state_tail(tail, law, stream, nc, rows, points, largs is not None)
+            src = stream.coef_source()
+
+            def call(Mp, o, i):
+                args.A_eff, args.info = o, i
+                return self._lib.hommx_secant_state_source(self._h, nc, C.byref(src), Mp, C.byref(args), None if hargs is None else C.byref(hargs),
+                                                           None if largs is None else C.byref(largs), C.byref(sargs))
+
+            A, info = self._host_call("hommx_secant_state_source", nc, M, call)
+            crit_result, recon_result = finish(xi, A, info)
+            return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
+                                strain, flux, vals, history=hist_out, criterion=crit_result, reconstruction=recon_result)
         if largs is not None:
             return self._secant_load(nc, M, stream, args, hargs, largs, tangent_plan, return_tangent_coef, state, mean_flux, out_coef, strain,
                                      flux, vals, hist_out)
@@ -1269,7 +1373,10 @@ class MicroCellPlan:
                       coef_start_ptr: int | None = None, mean_flux_ptr: int | None = None, coef_ptr: int | None = None,
                       strain_ptr: int | None = None, flux_ptr: int | None = None, values_ptr: int | None = None, info_ptr: int | None = None,
                       stream: int | None = None, history_in_ptr: int | None = None, history_out_ptr: int | None = None,
-                      P_ptr: int | None = None, P_source: "_lib.CoefSource | None" = None, eigenstrain: bool = False):
+                      P_ptr: int | None = None, P_source: "_lib.CoefSource | None" = None, eigenstrain: bool = False, criterion=None,
+                      crit_rows_ptr: int | None = None, crit_ptr: int | None = None, crit_values_ptr: int | None = None,
+                      total_strain_ptr: int | None = None, total_flux_ptr: int | None = None, stats_ptr: int | None = None,
+                      n_regions: int = 0, regions_ptr: int | None = None, region_stats_ptr: int | None = None):
         """Device-pointer form of ``secant`` (hommx_secant_source_device), asynchronous on ``stream``: ``source`` =
         ``CoefStream.coef_source(upload)`` with device addresses; ``law`` the ``SecantLaw`` (its program is host memory);
         rows[n_cells, 3 + law.n_fields], points[n_el, dim] (None: the law reads no ``y``) -> state[n_cells, 3] = [rounds | change |
@@ -1279,7 +1386,12 @@ class MicroCellPlan:
         ``history_in_ptr`` and ``history_out_ptr``, two different arrays [n_cells, n_el, n_history] on the device: a caller keeps the
         history resident by swapping them between load steps.  A load beside the law (hommx_secant_load_source_device): ``P_ptr``
         (P[n_cells, n_el, t], per cell) or ``P_source`` (a program, as in ``loads_device``), ``eigenstrain`` as in ``secant``; an
-        eigenstrain array is read in every round and never written."""
+        eigenstrain array is read in every round and never written.
+
+        The tail on the stopped state (hommx_secant_state_source_device), queued behind the ``max_iter`` rounds:
+        ``criterion`` (a ``Criterion``, as in ``secant``) with crit_rows[n_cells, 3 + criterion.n_fields] -> crit[n_cells, 4],
+        crit_values[n_cells, n_el], total_strain / total_flux[n_cells, n_el, t]; ``stats_ptr``: the reconstruction statistics
+        stats[n_cells, 2 t + 3] and, with ``n_regions``, regions[n_el] (uint8) -> region_stats[n_cells, n_regions, 2 t + 4]."""
         hargs = self._device_history(law, history_in_ptr, history_out_ptr)
         max_iter, tol, relax = self._secant_limits(max_iter, tol, relax)
         prog = self._law_program(law)
@@ -1288,6 +1400,26 @@ class MicroCellPlan:
                                coef_start_ptr or None, state_ptr, A_ptr, mean_flux_ptr or None, coef_ptr or None, strain_ptr or None,
                                flux_ptr or None, values_ptr or None, info_ptr or None)
         largs = self._device_load(P_ptr, P_source, eigenstrain)
+        if criterion is not None or stats_ptr:
+            sargs = _lib.SecantStateArgs()
+            if criterion is not None:
+                if not crit_rows_ptr or not crit_ptr:
+                    raise ValueError("criterion=... takes crit_rows_ptr and crit_ptr")
+                cprog = self._criterion_program(criterion, int(law.n_history))
+                cstruct = cprog.struct()
+                sargs.crit_program, sargs.crit_n_fields, sargs.crit_rows = C.pointer(cstruct), int(criterion.n_fields), crit_rows_ptr
+                sargs.threshold, sargs.crit, sargs.crit_values = float(criterion.threshold), crit_ptr, crit_values_ptr or None
+                sargs.total_strain, sargs.total_flux = total_strain_ptr or None, total_flux_ptr or None
+            if stats_ptr:
+                sargs.reconstruct, sargs.n_regions, sargs.region = 1, int(n_regions), regions_ptr or None
+                sargs.stats, sargs.region_stats = stats_ptr, region_stats_ptr or None
+            _lib.check(self._lib.hommx_secant_state_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
+                                                                  None if hargs is None else C.byref(hargs),
+                                                                  None if largs is None else C.byref(largs), C.byref(sargs), stream or None),
+                       "hommx_secant_state_source_device")
+            return
+        if crit_rows_ptr or crit_ptr or crit_values_ptr or total_strain_ptr or total_flux_ptr or regions_ptr or region_stats_ptr or n_regions:
+            raise ValueError("the crit_* pointers belong to criterion=..., the regions to stats_ptr")
         if largs is not None:
             _lib.check(self._lib.hommx_secant_load_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
                                                                  None if hargs is None else C.byref(hargs), C.byref(largs), stream or None),

@@ -121,9 +121,10 @@ int carve(Buf& b, const size_t (&bytes)[N], char* (&at)[N], size_t* total = null
 //            of its eliminations where the caller takes none, [chunk], and the tangent stream of a chunk of hommx_secant_tangent_source
 //            where the caller takes none, [chunk][n_el][t (t + 1) / 2], and beside an eigenstrain (hommx_secant_load_source) the
 //            eigenstress of the round, [chunk][n_el][t] (secant_run)
+// B_REGION: the element labels of the reconstruction tail of the host entry hommx_secant_state_source, [n_el] bytes, uploaded once per call
 enum {
   B_IN, B_OUT, B_EXPAND, B_PIN_IN, B_DEV_IN, B_PIN_OUT, B_DEV_OUT, B_RCORR, B_RA, B_FACT, B_LOADS, B_REFINE, B_SENS2, B_TANGENT, B_CURVATURE,
-  B_POLAR, B_SECANT, N_BUF
+  B_POLAR, B_SECANT, B_REGION, N_BUF
 };
 
 }  // namespace
@@ -1701,10 +1702,18 @@ struct SecantLoad {
   int32_t code;     // HOMMX_LOADS_PER_CELL or HOMMX_LOADS_PROGRAM, alone or with HOMMX_LOADS_EIGENSTRAIN
   const double* P;  // [nc][n_el][t] of the chunk: the caller's array, its copy in B_IN or the expansion of the program in B_POLAR
 };
+// state: the second tail, what hommx_secant_state_source adds behind the last round of a chunk (null: none, and every launch is the one
+// it was) -- k_criterion_state and / or k_recon on `cur`, the corrector blocks of the last executed round and
+// its load array or eigenstress, with the field in the slot behind the blocks where it does not fit LDS; no elimination
+bool state_in_lds(const hommx_plan* p, const hommx_secant_state_args* s) {
+  if (s && s->crit_program && !crit_in_lds(p, program_depth(*s->crit_program))) return false;
+  return !(s && s->reconstruct) || recon_in_lds(p);
+}
 int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, const double* M, const hommx_secant_args& a, bool device,
-               hipStream_t st, const TangentTail* tail = nullptr, const hommx_history_args* hist = nullptr, const SecantLoad* load = nullptr) {
+               hipStream_t st, const TangentTail* tail = nullptr, const hommx_history_args* hist = nullptr, const SecantLoad* load = nullptr,
+               const hommx_secant_state_args* state = nullptr) {
   const int t = p->ks.t, depth = program_depth(*a.program);
-  const bool slot = !crit_in_lds(p, depth), tail_slot = tail && !tangent_in_lds(p, depth);
+  const bool slot = !crit_in_lds(p, depth), tail_slot = (tail && !tangent_in_lds(p, depth)) || !state_in_lds(p, state);
   const bool eigen = load && load_eigenstrain(load->code);
   const size_t stream = sizeof(double) * p->n_el * p->ks.n_comp;
   const size_t bytes[5] = {stream * chunk, stream * chunk, a.info ? 0 : sizeof(int32_t) * chunk,
@@ -1770,6 +1779,51 @@ int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, con
     if (!running) break;
   }
   if (a.coef_out) HIP_TRY(hipMemcpyAsync(a.coef_out, cur, stream * nc, hipMemcpyDeviceToDevice, st));
+  if (state) {
+    double* field_slot = corr + chunk * (load ? 2 : 1) * t * k.ndof;  // behind the blocks of the last executed round
+    if (state->crit_program) {
+      const int crit_depth = program_depth(*state->crit_program);
+      hommx::CritStateArgs c;
+      set_geometry(p, c);
+      c.corr = corr;
+      c.coef = cur;
+      c.M = M;
+      c.xi = a.xi;
+      c.prog = program_args(*state->crit_program);
+      c.n_fields = state->crit_n_fields;
+      c.rows = state->crit_rows;
+      c.points = a.points;
+      c.threshold = state->threshold;
+      c.crit = state->crit;
+      c.values = state->crit_values;
+      c.strain = state->total_strain;
+      c.flux = state->total_flux;
+      if (load) {
+        c.corr_load = k.load.chi;
+        c.P = eigen ? stress : load->P;
+        c.per_cell = true;
+      }
+      c.base = coef;
+      c.hist_in = hist ? hist->history_in : nullptr;
+      c.n_history = hist ? hist->n_history : 0;
+      c.slot = crit_in_lds(p, crit_depth) ? nullptr : field_slot;
+      HIP_TRY(hommx::launch_criterion_state(c, crit_depth, nc, st));
+    }
+    if (state->reconstruct) {
+      hommx::ReconArgs r;
+      set_geometry(p, r);
+      r.corr = corr;
+      r.coef = cur;
+      r.M = M;
+      r.xi = a.xi;
+      r.stats = state->stats;
+      r.slot = recon_in_lds(p) ? nullptr : field_slot;
+      r.n_regions = state->n_regions;
+      r.region = state->n_regions ? state->region : nullptr;
+      r.region_stats = state->region_stats;
+      HIP_TRY(hommx::launch_reconstruct(r, nc, st));
+    }
+  }
   if (!tail) return HOMMX_OK;
   hommx::SecantTangentLoadArgs g;  // likewise
   set_geometry(p, g);
@@ -1854,13 +1908,49 @@ int secant_load_routes(hommx_plan* p) {
   return GO;
 }
 
+// the tail of hommx_secant_state_source against the plan's descriptor: the criterion as crit_open checks
+// one, on the row of a state criterion; the reconstruction as recon_open checks its regions.  `a`, `src`, `hist` and `load` have passed
+// their own checks
+int secant_state_checks(const hommx_plan* p, const hommx_coef_source* src, const hommx_secant_args* a, const hommx_history_args* hist,
+                        const hommx_secant_load_args* load, const hommx_secant_state_args* s) {
+  if (!s) return fail(HOMMX_EINVAL, "null state arguments");
+  if (!s->crit_program && !s->reconstruct) return fail(HOMMX_EINVAL, "nothing requested: neither a criterion nor the reconstruction");
+  const hommx::KindSizes ks = hommx::kind_sizes(p->desc.dim, p->desc.kind);
+  if (s->crit_program) {
+    if (!s->crit_rows || !s->crit) return fail(HOMMX_EINVAL, "null crit_rows / crit");
+    if (!s->total_strain != !s->total_flux) return fail(HOMMX_EINVAL, "total_strain and total_flux: both or neither");
+    hommx_coef_source own{};  // what program_check reads of a source
+    own.n_fields = s->crit_n_fields;
+    own.program = s->crit_program;
+    // without a history struct the row ends behind the two coefficient segments: an h index of the criterion is out of range
+    if (int rc = program_check(p, &own, 0, 2 * ks.t + 2 * ks.n_comp + (hist ? hist->n_history : 0))) return rc;
+    if (!a->points)
+      for (int pc = 0; pc < s->crit_program->n_ops; ++pc)
+        if (s->crit_program->ops[2 * pc] == hommx::OP_Y)
+          return fail(HOMMX_EINVAL, "null points: the criterion reads y (instruction %d), the centroid of the element", pc);
+    if (s->threshold != s->threshold) return fail(HOMMX_EINVAL, "the threshold is NaN");
+  }
+  if (s->reconstruct) {
+    if (load)
+      return fail(HOMMX_EINVAL, "reconstruct together with a load: the reconstruction statistics have no load term (ask for the criterion's "
+                                "total_strain / total_flux)");
+    if (!s->stats) return fail(HOMMX_EINVAL, "null stats");
+    if (int rc = regions_check(src, s->n_regions, s->region, s->region_stats)) return rc;
+  }
+  return HOMMX_OK;
+}
+
 // the argument checks of both entry points, then a route that forms correctors; load: the call is one of the load entries, whose
-// struct *load is checked behind the iteration's and which needs a load solve as well
+// struct *load is checked behind the iteration's and which needs a load solve as well; state: the call is hommx_secant_state_source,
+// whose history and load are optional (null pointers behind hist / load) and whose struct *state is checked last
 int secant_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_args* a, bool device,
-                const hommx_history_args* const* hist = nullptr, const hommx_secant_load_args* const* load = nullptr) {
+                const hommx_history_args* const* hist = nullptr, const hommx_secant_load_args* const* load = nullptr,
+                const hommx_secant_state_args* const* state = nullptr) {
   auto checks = [&] {
     if (int rc = secant_checks(p, a, hist)) return rc;
-    return load ? secant_load_checks(p, *load) : HOMMX_OK;
+    if (load)
+      if (int rc = secant_load_checks(p, *load)) return rc;
+    return state ? secant_state_checks(p, src, a, hist ? *hist : nullptr, load ? *load : nullptr, *state) : HOMMX_OK;
   };
   if (int rc = source_open(p, n_cells, src, a, device, checks); rc != GO) return rc;
   return load ? secant_load_routes(p) : GO;
@@ -1873,6 +1963,8 @@ struct SecantCall {
   hommx_history_args h;
   bool has_load;
   SecantLoad l;
+  bool has_state;
+  hommx_secant_state_args t;  // the tail of hommx_secant_state_source (has_state false: none, every pointer null)
 };
 
 // what secant_call and secant_tangent_call hold of a load: the program source of its own beside the coefficient's, and the bytes per
@@ -1904,28 +1996,55 @@ SecantLoadPlan secant_load_plan(const hommx_plan* p, const hommx_secant_load_arg
 // hist: history_in is a per-cell input and history_out a per-cell output of the chunk, counted as coef_start and coef_out are
 // load: with it a chunk holds a second corrector block per cell and ends every round in a load solve (load_chunk), and the load array
 // is a per-cell input of the chunk (a program: its expansion, ProgramLoad)
+// state: the per-cell outputs of the tail and the rows of its criterion are per-cell arrays of the chunk; the labels of a host call
+// travel once, into B_REGION.  The tail holds no scratch beside the round's: the field slot and the corrector blocks are the round's
 int secant_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_secant_args& args, bool device,
-                hipStream_t st, const hommx_history_args* hist = nullptr, const hommx_secant_load_args* load = nullptr) {
+                hipStream_t st, const hommx_history_args* hist = nullptr, const hommx_secant_load_args* load = nullptr,
+                const hommx_secant_state_args* state = nullptr) {
   const int64_t t = p->ks.t, field = p->n_el * t, stream = p->n_el * p->ks.n_comp;
   Chunk<SecantCall> v{};
-  v.a = SecantCall{args, hist ? *hist : hommx_history_args{}, false, {}};
+  v.a = SecantCall{args, hist ? *hist : hommx_history_args{}, false, {}, state != nullptr, state ? *state : hommx_secant_state_args{}};
   hommx_secant_args& a = v.a.s;
   hommx_history_args& h = v.a.h;
+  hommx_secant_state_args& ta = v.a.t;
+  if (state) {  // what the checks have passed: members that belong to the half not asked for are not read
+    if (!ta.crit_program) ta.crit_rows = nullptr, ta.crit = ta.crit_values = ta.total_strain = ta.total_flux = nullptr, ta.crit_n_fields = 0;
+    if (!ta.reconstruct) ta.n_regions = 0, ta.region = nullptr, ta.stats = ta.region_stats = nullptr;
+    if (ta.n_regions && !ta.region) ta.region = s.mask;  // n_regions == 2 of a two-phase source: the mask may be the labels
+    if (ta.n_regions && !device) {
+      if (int rc = grow(p->buf[B_REGION], p->n_el)) return rc;
+      HIP_TRY(hipMemcpy(p->buf[B_REGION].p, ta.region, p->n_el, hipMemcpyHostToDevice));
+      ta.region = static_cast<const uint8_t*>(p->buf[B_REGION].p);
+    }
+  }
   SecantLoadPlan lp = secant_load_plan(p, load, &v.a.l, &v.a.has_load);
-  const bool own_slot = !crit_in_lds(p, program_depth(*a.program)) && recon_in_lds(p);
+  const bool own_slot = !(crit_in_lds(p, program_depth(*a.program)) && state_in_lds(p, state)) && recon_in_lds(p);
   const size_t scratch = sizeof(double) * (2 * stream + (own_slot ? plan_ndof(p) : 0)) + sizeof(int32_t) + lp.scratch;
   const CellArray in[] = {{&a.rows, hommx::program_row_doubles(a.n_fields)},
                           {&a.xi, t},
                           {&a.coef_start, stream},
                           {&h.history_in, p->n_el * h.n_history},
                           {&v.a.l.P, lp.field},
+                          {&ta.crit_rows, hommx::program_row_doubles(ta.crit_n_fields)},
                           {&a.points, p->n_el * p->desc.dim, SHARED}};
-  const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE}, {&a.A_eff, t * t, KEPT}, {&a.mean_flux, t},      {&a.coef_out, stream},
-                           {&a.strain, field},              {&a.flux, field},        {&a.law_values, stream}, {&h.history_out, p->n_el * h.n_history}};
+  const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE},
+                           {&a.A_eff, t * t, KEPT},
+                           {&a.mean_flux, t},
+                           {&a.coef_out, stream},
+                           {&a.strain, field},
+                           {&a.flux, field},
+                           {&a.law_values, stream},
+                           {&h.history_out, p->n_el * h.n_history},
+                           {&ta.crit, HOMMX_CRIT_NSTATS},
+                           {&ta.crit_values, p->n_el},
+                           {&ta.total_strain, field},
+                           {&ta.total_flux, field},
+                           {&ta.stats, HOMMX_RECON_NSTATS(t)},
+                           {&ta.region_stats, ta.n_regions * HOMMX_RECON_NREGION(t)}};
   return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, load ? load_chunk : recon_chunk, device, st,
                       [&](int64_t nc, int64_t chunk, const Chunk<SecantCall>& c) {
                         return secant_run(p, nc, chunk, c.coef, c.M, c.a.s, device, st, nullptr, c.a.h.n_history ? &c.a.h : nullptr,
-                                          c.a.has_load ? &c.a.l : nullptr);
+                                          c.a.has_load ? &c.a.l : nullptr, c.a.has_state ? &c.a.t : nullptr);
                       },
                       nullptr, false, lp.program ? &lp.prog : nullptr);
 }
@@ -2231,6 +2350,19 @@ int hommx_secant_load_source(hommx_plan* p, int64_t n_cells, const hommx_coef_so
                              const hommx_history_args* history, const hommx_secant_load_args* load) {
   if (int rc = secant_open(p, n_cells, src, args, false, history ? &history : nullptr, &load); rc != GO) return rc;
   return secant_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr, history, load);
+}
+
+int hommx_secant_state_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                     const hommx_secant_args* args, const hommx_history_args* history, const hommx_secant_load_args* load,
+                                     const hommx_secant_state_args* state, void* stream) {
+  if (int rc = secant_open(p, n_cells, src, args, true, history ? &history : nullptr, load ? &load : nullptr, &state); rc != GO) return rc;
+  return secant_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream), history, load, state);
+}
+
+int hommx_secant_state_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_secant_args* args,
+                              const hommx_history_args* history, const hommx_secant_load_args* load, const hommx_secant_state_args* state) {
+  if (int rc = secant_open(p, n_cells, src, args, false, history ? &history : nullptr, load ? &load : nullptr, &state); rc != GO) return rc;
+  return secant_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr, history, load, state);
 }
 
 int hommx_secant_tangent_load_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,

@@ -228,6 +228,17 @@ size_t criterion_lds_bytes(long long ndof, int depth);
 // depth: the maximal stack depth of the (validated) program
 hipError_t launch_criterion(const CritArgs& a, int depth, long long nc, hipStream_t stream);
 
+// criterion_state.hip: a criterion of the NONLINEAR state behind the last round of a secant chunk (include/hommx_hip.h,
+// hommx_secant_state_source): k_criterion on the stopped stream (coef: `cur`), whose program may also read the
+// base coefficient and the history at the start of the call
+struct CritStateArgs : CritArgs {
+  const double* base = nullptr;      // [nc][n_el][n_comp]: what b[k] reads
+  const double* hist_in = nullptr;   // [nc][n_el][n_history]: what h[k] reads, or null (n_history == 0)
+  int n_history = 0;                 // 0 .. HOMMX_SECANT_MAX_HISTORY; prog's row is [.. | c (n_comp) | h (n_history) | b (n_comp)]
+};
+// dynamic LDS as k_criterion's (criterion_lds_bytes); depth: the maximal stack depth of the (validated) program
+hipError_t launch_criterion_state(const CritStateArgs& a, int depth, long long nc, hipStream_t stream);
+
 // secant.hip: one round of the secant iteration of a strain-dependent coefficient on `nc` cells (include/hommx_hip.h,
 // hommx_secant_source).  A cell whose state says it has stopped is not touched
 struct SecantArgs : ElemWalk {

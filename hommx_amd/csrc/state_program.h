@@ -57,11 +57,17 @@ __device__ __forceinline__ double pick(int j, const double (&a)[T]) {
 // base + 2 T + n_comp is h[k], a vector load from he, the element's history row, where it is read, as c[k] is; it seeds nothing.
 // n_comp: the entries of ce (uniform).  What a STORE k, k >= n_comp, does is the caller's.  Without HIST neither is read, and the
 // instantiation is the one it was
-template <int T, int P = 0, bool HIST = false, typename Store>
+//
+// BASE (with HIST): a criterion of the nonlinear state (criterion_state.hip).  The row holds a second
+// coefficient segment behind the n_history (uniform, 0: none, and he may be null) history entries: an `X` index at or above
+// base + 2 T + n_comp + n_history is b[k], a vector load from be, the element's entry of the base stream, where it is read.  Without
+// BASE neither is read, and the instantiation is the one it was
+template <int T, int P = 0, bool HIST = false, bool BASE = false, typename Store>
 __device__ __forceinline__ void run_state_program(const ProgramArgs& prog, int n_fields, const double (&x)[3], const double* __restrict__ row,
                                                   const double (&e)[T], const double (&s)[T], const double* __restrict__ ce,
                                                   const double* __restrict__ yk, double* __restrict__ stk, Store&& store, int seed0 = 0,
-                                                  const double* __restrict__ he = nullptr, int n_comp = 0) {
+                                                  const double* __restrict__ he = nullptr, int n_comp = 0,
+                                                  const double* __restrict__ be = nullptr, int n_history = 0) {
 #pragma clang fp contract(off)
   constexpr int PN = P ? P : 1, W = 1 + P;  // PN: no array of length zero; W: the doubles of a stack entry
   const int n_ops = prog.n_ops, base = program_row_doubles(n_fields);
@@ -137,8 +143,10 @@ __device__ __forceinline__ void run_state_program(const ProgramArgs& prog, int n
           t = pick<T>(k - base - T, s);
         } else if (!HIST || k < base + 2 * T + n_comp) {
           t = ce[k - base - 2 * T];
-        } else {
+        } else if (!BASE || k < base + 2 * T + n_comp + n_history) {
           if constexpr (HIST) t = he[k - base - 2 * T - n_comp];
+        } else {
+          if constexpr (BASE) t = be[k - base - 2 * T - n_comp - n_history];
         }
         break;
       case OP_Y:

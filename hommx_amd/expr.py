@@ -91,10 +91,12 @@ class _Context:
     """What the components of one Expression share while they are checked: the number of parameters (None: no ``p=``), of fields
     (None: no ``fields=``) and the texts of the comparisons that read one.  ``state``: the text is a ``Criterion``'s, which also
     reads the element's strain ``e[k]``, flux ``s[k]`` and coefficient ``c[k]``.  ``n_history``: the history variables ``h[k]`` of a
-    ``SecantLaw`` (None: no ``history=``)."""
+    ``SecantLaw`` or of a state ``Criterion`` (None: no ``history=``).  ``base``: the text is a ``Criterion``'s, which may also read
+    the base coefficient ``b[k]``."""
 
-    def __init__(self, n_params=None, n_fields=None, state=False, n_history=None):
+    def __init__(self, n_params=None, n_fields=None, state=False, n_history=None, base=False):
         self.n_params, self.n_fields, self.compared, self.state, self.n_history = n_params, n_fields, [], state, n_history
+        self.base = base
 
 
 def _number(node, value) -> _Node:
@@ -130,6 +132,10 @@ def _check(node, ctx: _Context) -> _Node:
             if not _literal_int(node.slice, 0, MAX_STATE_INDEX):
                 raise _bad(node, f"the index of {node.value.id} is a literal integer 0 .. {MAX_STATE_INDEX}")
             return _Node(_STATE, value=(node.value.id, int(node.slice.value)), degree=1, varying=True)
+        if ctx.state and ctx.base and isinstance(node.value, ast.Name) and node.value.id == "b":
+            if not _literal_int(node.slice, 0, MAX_STATE_INDEX):
+                raise _bad(node, f"the index of b is a literal integer 0 .. {MAX_STATE_INDEX}")
+            return _Node(_STATE, value=("b", int(node.slice.value)), degree=1, varying=True)
         if ctx.state and isinstance(node.value, ast.Name) and node.value.id == "h":
             if ctx.n_history is None:
                 raise _bad(node, "h[k] needs the updates of the history variables (history=[...])")
@@ -724,9 +730,17 @@ class Criterion:
     written, and the indices are checked, when the criterion meets one: ``program(t, n_comp)``.  The limits of a program hold (128
     instructions, 32 constants with the parameters first, depth 16), and it has one component.
 
-    ``threshold``: the value from which an element counts into ``CriterionResult.exceed_volume`` (default 1: an index)."""
+    ``threshold``: the value from which an element counts into ``CriterionResult.exceed_volume`` (default 1: an index).
 
-    def __init__(self, text, p=None, parameter_names=None, fields=None, threshold=1.0):
+    A criterion of the NONLINEAR state (the tail of ``MicroCellPlan.secant``, ``criterion(nonlinear=True)`` of the solver
+    classes) reads two more names: ``b[k]``, k < n_comp, the BASE coefficient of the element -- what the solver's ``A`` gives and a
+    ``SecantLaw`` calls ``c[k]``; ``c[k]`` stays the coefficient the stress was formed with, the softened one --, and, with
+    ``history=n``, ``h[k]``, k < n, the history variable of the element at the start of the load step, the value the law's ``h[k]``
+    reads.  The row is the law's with the base behind it, ``[midpoint 3 | fields | e (t) | s (t) | c (n_comp) | h (n_history) |
+    b (n_comp)]``, so ``h[k]`` has the index it has in a ``SecantLaw``; a criterion that reads neither has the program it had.
+    ``reads_state``: it reads ``b`` or ``h`` and can be evaluated on a nonlinear state only."""
+
+    def __init__(self, text, p=None, parameter_names=None, fields=None, threshold=1.0, history=None):
         values = _parameter_values(p, None) if p is not None else np.zeros(0)
         self.n_params = int(values.size)
         if parameter_names is None:
@@ -738,8 +752,12 @@ class Criterion:
         self.threshold = float(threshold)
         if math.isnan(self.threshold):
             raise ValueError("criterion: the threshold is NaN")
+        if history is not None and (isinstance(history, bool) or not isinstance(history, int) or not 1 <= history <= MAX_HISTORY):
+            raise ValueError(f"criterion: history is the number of history variables, 1 .. {MAX_HISTORY}; got {history!r}")
+        self.n_history = 0 if history is None else int(history)
         self.text = str(text)
-        tree = _parse(text, _Context(self.n_params if p is not None else None, self.n_fields if fields is not None else None, state=True))
+        tree = _parse(text, _Context(self.n_params if p is not None else None, self.n_fields if fields is not None else None, state=True,
+                                     n_history=history, base=True))
         ops, consts = [], [float(v) for v in values]
         _emit(tree, ops, consts, self.n_params)
         ops.append((OP_STORE, 0))
@@ -754,7 +772,8 @@ class Criterion:
         self._consts = np.array(consts, dtype=np.float64)
         self.n_y = 1 + max([int(k) for op, k in ops if op == OP_Y], default=-1)  # fast-variable components the criterion reads
         self.state_indices = {name: 1 + max([k[1] for op, k in ops if op == OP_X and isinstance(k, tuple) and k[0] == name], default=-1)
-                              for name in "esc"}  # entries of e, s and c it reads
+                              for name in "escbh"}  # entries of e, s, c, b and h it reads
+        self.reads_state = bool(self.state_indices["b"] or self.state_indices["h"])
 
     @property
     def p(self) -> np.ndarray:
@@ -769,28 +788,55 @@ class Criterion:
         other._consts[:self.n_params] = values
         return other
 
-    def program(self, t: int, n_comp: int) -> tuple[np.ndarray, np.ndarray]:
+    def program(self, t: int, n_comp: int, n_history: int | None = None) -> tuple[np.ndarray, np.ndarray]:
         """(ops[n_ops, 2] uint8, consts[n_consts] float64) on a plan of tensor size ``t`` whose coefficient has ``n_comp`` entries per
-        element: the one component's code and ``STORE 0``.  ``ValueError`` for an index of ``s`` / ``e`` at or above t, of ``c`` at or
-        above n_comp."""
-        base = {"e": 3 + self.n_fields, "s": 3 + self.n_fields + t, "c": 3 + self.n_fields + 2 * t}
-        for name, bound, what in (("e", t, "t"), ("s", t, "t"), ("c", n_comp, "n_comp")):
+        element: the one component's code and ``STORE 0``.  ``h[k]`` is ``X 3 + n_fields + 2 t + n_comp + k`` and ``b[k]``
+        ``X 3 + n_fields + 2 t + n_comp + n_history + k``.  ``n_history``: the history variables of the row the program runs on, the
+        law's (default: the declared number); a criterion declared without ``history=`` runs on the row of any law, one declared
+        with it on the row of a law with as many -- ``ValueError`` naming both numbers otherwise.  ``ValueError`` as well for an
+        index of ``s`` / ``e`` at or above t, of ``c`` / ``b`` at or above n_comp."""
+        if n_history is None:
+            n_history = self.n_history
+        if self.n_history and int(n_history) != self.n_history:
+            raise ValueError(f"criterion: it declares history={self.n_history}; the law has {int(n_history)} history variables (declare "
+                             f"Criterion(..., history={int(n_history) or None}))")
+        base = {"e": 3 + self.n_fields, "s": 3 + self.n_fields + t, "c": 3 + self.n_fields + 2 * t,
+                "h": 3 + self.n_fields + 2 * t + n_comp, "b": 3 + self.n_fields + 2 * t + n_comp + int(n_history)}
+        for name, bound, what in (("e", t, "t"), ("s", t, "t"), ("c", n_comp, "n_comp"), ("b", n_comp, "n_comp")):
             if self.state_indices[name] > bound:
                 raise ValueError(f"criterion: {name}[{self.state_indices[name] - 1}] is out of range: the plan has {what} = {bound} "
                                  f"(t = {t}, n_comp = {n_comp})")
         ops = [(op, base[k[0]] + k[1] if isinstance(k, tuple) else k) for op, k in self._ops]
         return np.array(ops, dtype=np.uint8).reshape(-1, 2), self._consts.copy()
 
-    def host_values(self, e, s, c, x, y=None, fields=None) -> np.ndarray:
+    def host_values(self, e, s, c, x, y=None, fields=None, base=None, history=None) -> np.ndarray:
         """values[N, n_el]: the criterion of every element from e[N, n_el, t] and s[N, n_el, t] (``CriterionResult.strain`` / ``flux``),
         c[N, n_el(, n_comp)] (the coefficient stream), x[N, 3] (the macro midpoints), y[n_el, d] (the element centroids; may be None
         when the criterion reads no ``y``) and fields[N, n_fields] -- ``_run``, value pass, on the rows the device reads: the
-        midpoint, the fields, then e, s and c of the element.  Bit for bit the device's values wherever the program holds exactly
-        rounded operations only."""
+        midpoint, the fields, then e, s and c of the element.  A state criterion: base[N, n_el(, n_comp)] is what ``b[k]`` reads
+        and history[N, n_el, n_history] what ``h[k]`` reads, behind c on the row; ``ValueError`` when the criterion reads a name
+        whose array is missing.  Bit for bit the device's values wherever the program holds exactly rounded operations only."""
         e, s = np.asarray(e, dtype=np.float64), np.asarray(s, dtype=np.float64)
         N, n_el, t = e.shape
         c = np.asarray(c, dtype=np.float64).reshape(N, n_el, -1)
-        ops, consts = self.program(t, c.shape[2])
+        state = [e, s, c]
+        if self.state_indices["h"] and history is None:
+            raise ValueError(f"the criterion reads h[{self.state_indices['h'] - 1}]: pass history[N, n_el, {self.n_history}]")
+        if history is not None:  # the row of the law the state belongs to: its history, read or not, stands between c and b
+            history = np.asarray(history, dtype=np.float64)
+            if history.ndim == 2:
+                history = history[:, :, None]
+            if history.ndim != 3 or history.shape[:2] != (N, n_el):
+                raise ValueError(f"history must be [N, n_el, n_history] = [{N}, {n_el}, n_history]; got shape {history.shape}")
+            state.append(history)
+        ops, consts = self.program(t, c.shape[2], 0 if history is None else history.shape[2])
+        if self.state_indices["b"]:
+            if base is None:
+                raise ValueError(f"the criterion reads b[{self.state_indices['b'] - 1}]: pass the base coefficient stream "
+                                 f"base[N, n_el, {c.shape[2]}]")
+            if np.size(base) != c.size:
+                raise ValueError(f"base must have the shape of c, [{N}, {n_el}, {c.shape[2]}]; got shape {np.shape(base)}")
+            state.append(np.asarray(base, dtype=np.float64).reshape(c.shape))
         x = np.asarray(x, dtype=np.float64).reshape(N, -1)
         x = np.concatenate([x, np.zeros((N, 3 - x.shape[1]))], axis=1) if x.shape[1] < 3 else x[:, :3]
         if self.n_fields:
@@ -800,7 +846,7 @@ class Criterion:
         if self.n_y and (y is None or np.shape(y)[-1] < self.n_y):
             raise ValueError(f"the criterion reads y[{self.n_y - 1}]: pass the element centroids y[n_el, d]")
         rows = [x[:, k, None] for k in range(3)] + [fields[:, k, None] for k in range(self.n_fields)]
-        rows += [a[:, :, k] for a in (e, s, c) for k in range(a.shape[2])]
+        rows += [a[:, :, k] for a in state for k in range(a.shape[2])]
         yr = [] if y is None else [np.asarray(y, dtype=np.float64)[None, :, k] for k in range(np.shape(y)[-1])]
         with np.errstate(all="ignore"):
             out, _ = _run(ops.tolist(), consts, 1, rows, yr)

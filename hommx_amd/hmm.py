@@ -40,7 +40,14 @@ _VOIGT = {2: [(0, 0), (1, 1), (0, 1)], 3: [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2
 def _join(parts: list, **override):
     """The results of the chunks of a batch (one of the result dataclasses of ``batch``) as one: every field concatenated along the
     cells, a field that is None staying None, the fields of ``override`` as given (what the chunks do not know: ``cells``, ``names``)."""
-    cat = lambda name: None if getattr(parts[0], name) is None else np.concatenate([getattr(r, name) for r in parts])
+    def cat(name):
+        first = getattr(parts[0], name)
+        if first is None:
+            return None
+        if dataclasses.is_dataclass(first):  # a result inside a result: the tail of a SecantResult
+            return _join([getattr(r, name) for r in parts])
+        return np.concatenate([getattr(r, name) for r in parts])
+
     return type(parts[0])(**{f.name: override[f.name] if f.name in override else cat(f.name) for f in dataclasses.fields(parts[0])})
 
 
@@ -330,6 +337,7 @@ class BaseHMM(ABC):
         self.tangent_tensors = None  # D = d sigma_H / d xi per macro cell of the last solve_nonlinear(method="newton")
         self.history = None  # [cells of this rank, n_el, n_history]: the committed history variables of a law that has some
         self.history_trial = None  # ... and what the last step of the last solve_nonlinear left: commit_history() makes it the state
+        self._nonlinear_state = None  # what defines the state the last solve_nonlinear ended in (criterion / reconstruct(nonlinear=True))
         self._linearisation_load = None  # P_T of the macro step solve() is serving (solve_nonlinear sets and clears it)
         self._nonlinear_load = False  # solve() serves a step of solve_nonlinear(load=True): the load is inside _linearisation_load
         self._tangent_plan = None  # the sibling plan of the tangent kind (solve_nonlinear(method="newton") builds and keeps it)
@@ -1083,7 +1091,62 @@ class BaseHMM(ABC):
             return region_labels(np.asarray(self._coeff.indicator(mid), dtype=bool), mid.shape[1], 2)
         return region_labels(regions(mid) if callable(regions) else regions, mid.shape[1])
 
-    def reconstruct(self, u=None, cells=None, fields: bool = False, chunk_cells: int | None = None, regions=None) -> Reconstruction:
+    def _nonlinear_tail(self, method: str, u, cells, chunk_cells, tail_bytes: int, tail) -> SecantResult:
+        """The micro iteration of ``cells`` at ``u`` with what the last ``solve_nonlinear`` kept -- its law, limits, rows, load and the
+        history it started from -- and ``tail(b, n)``, the tail arguments of ``plan.secant`` for the n cells from position b, chunk by
+        chunk -> the joined ``SecantResult`` with ``cells`` (its ``criterion`` / ``reconstruction`` hold the tail).  One WARNING with
+        the counts per status when a cell did not stop with status 0."""
+        st = self._nonlinear_state
+        if st is None:
+            raise RuntimeError(f"{method}(nonlinear=True) evaluates the state a nonlinear solve ended in: call solve_nonlinear() first")
+        law = st["law"]
+        x = self._macro_dofs(self._or_last_solve(u, method))
+        cells = self._cells_argument(cells, method, local=False)
+        history = None
+        if law.n_history:
+            own = self.history_cells
+            at = np.searchsorted(own, cells)
+            inside = (at < len(own)) & (own[np.minimum(at, len(own) - 1)] == cells)
+            if not inside.all():
+                raise ValueError(f"{method}(nonlinear=True): the law has history variables and this rank holds the history of the cells "
+                                 f"{own[0]} .. {own[-1]} (history_cells) only; cell {int(cells[~inside][0])} is not among them")
+            history = st["history"][at]
+        xi = self._macro_strains(cells, x)
+        rows = st["rows"][cells]
+        points = np.ascontiguousarray(self._cell_mesh.cell_midpoints()[:, : self._tdim])
+        t, n_el = self._tensor_size(), self._cell_mesh.num_cells
+
+        def bytes_per_cell():
+            out = 8 * (3 + t * t + t) + 4 + tail_bytes
+            if st["load"] and not isinstance(self._polarisation, Expression):
+                out += 8 * n_el * t  # a sampled load
+            if history is not None:  # in and out
+                out += 16 * n_el * history.shape[2]
+            return out if self._sampled_on_device() else out + n_el * (1 if self._kind == "poisson" else 2) * 8
+
+        def sample(sub, kind):  # (P, per_cell, eigenstrain) as plan.secant takes them
+            return self._load_input(sub, self._loads_on_device(kind)) + (self._eigenstrain,)
+
+        def call(plan, coef, M, P, sub, b):
+            args = dict(rows=rows[b:b + len(sub)], points=points, max_iter=st["micro_iter"], tol=st["micro_tol"], relax=st["relax"],
+                        **tail(b, len(sub)))
+            if P is not None:
+                args.update(P=P[0], per_cell=P[1], eigenstrain=P[2])
+            if history is not None:
+                args["history"] = history[b:b + len(sub)]
+            return plan.secant(coef, xi[b:b + len(sub)], law, M, **args)
+
+        if st["load"] and self._polarisation is None:
+            raise RuntimeError(f"{method}(nonlinear=True): solve_nonlinear ran with load=True and the load has been cleared since: set it again")
+        r = _join(self._chunks(cells, chunk_cells, bytes_per_cell, call, sample if st["load"] else None), cells=cells)
+        counts = {int(k): int((r.status == k).sum()) for k in np.unique(r.status)}
+        if any(k != 0 for k in counts):
+            self._logger.warning("%s(nonlinear=True): not every micro iteration converged; micro cells by status: %s", method,
+                                 ", ".join(f"{k}: {n}" for k, n in sorted(counts.items())))
+        return r
+
+    def reconstruct(self, u=None, cells=None, fields: bool = False, chunk_cells: int | None = None, regions=None,
+                    nonlinear: bool = False) -> Reconstruction:
         """HMM reconstruction of the micro fields in the sampling boxes of ``cells`` (default: every macro cell) from the macro solution
         ``u`` (a macro ``fem.Function`` or its dof array; default: the last ``solve()`` result): R = u_H + corrector of xi_T, with xi_T the
         macro gradient / strain of u on the cell (hommx_reconstruct_source).  Returns a ``Reconstruction`` with ``cells``:
@@ -1098,7 +1161,30 @@ class BaseHMM(ABC):
 
         The cells are reconstructed in chunks of ``chunk_cells`` (default: about 256 MB of coefficient stream when it is sampled on the
         host, of outputs when it is sampled on the device).  Under a process group this runs on the calling rank alone, for the cells it
-        is given: there is no collective."""
+        is given: there is no collective.
+
+        ``nonlinear=True`` (after ``solve_nonlinear``): the statistics of the NONLINEAR state -- the micro iteration of
+        the asked cells at ``u`` (default: the last result, which after ``solve_nonlinear`` is the nonlinear solution) with that
+        call's law, limits and starting history, and the reconstruction of the stream every cell stops on, on the device
+        (hommx_secant_state_source).  The result also carries ``secant`` (rounds, change, status per cell).  ``fields`` is not
+        offered there (``criterion(crit, nonlinear=True, fields=True)`` returns the state), and a solver that ran
+        ``solve_nonlinear(load=True)`` raises ``RuntimeError``: the statistics have no load term.  Without it the call is the linear
+        one it was, for the coefficient ``A``."""
+        if nonlinear:
+            if self._nonlinear_state is not None and self._nonlinear_state["load"]:
+                raise RuntimeError("reconstruct(nonlinear=True): solve_nonlinear ran with load=True, and the reconstruction statistics have "
+                                   "no load term; criterion(crit, nonlinear=True, fields=True) returns the loaded state")
+            if fields:
+                raise ValueError("reconstruct(nonlinear=True) returns the statistics; criterion(crit, nonlinear=True, fields=True) returns "
+                                 "the strain and the flux of the nonlinear state")
+            labels = self._region_labels(regions)
+            kw = dict(reconstruct=True, **({} if labels is None else {"regions": labels[0], "n_regions": labels[1]}))
+            t = self._tensor_size()
+            r = self._nonlinear_tail("reconstruct", u, cells, chunk_cells, 8 * (2 * t + 3 + (labels[1] * (2 * t + 4) if labels else 0)),
+                                     lambda b, n: kw)
+            out = dataclasses.replace(r.reconstruction, cells=r.cells)
+            out.secant = dataclasses.replace(r, criterion=None, reconstruction=None)
+            return out
         x = self._macro_dofs(self._or_last_solve(u, "reconstruct"))
         cells = self._cells_argument(cells, "reconstruct", local=False)
         xi = self._macro_strains(cells, x)
@@ -1138,7 +1224,7 @@ class BaseHMM(ABC):
         return _join(self._load_blocks(cells, chunk_cells, bytes_per_cell, response=True, fields=fields, return_correctors=correctors), cells=cells)
 
     def criterion(self, crit: Criterion, u=None, cells=None, field_values=None, values: bool = False, fields: bool = False, load=None,
-                  chunk_cells: int | None = None) -> CriterionResult:
+                  chunk_cells: int | None = None, nonlinear: bool = False) -> CriterionResult:
         """A failure criterion ``crit`` (a ``Criterion``: von Mises against a phase-dependent yield stress, a largest principal stress, a
         critical flux, ...) on the micro state ``reconstruct`` forms in the sampling boxes of ``cells`` (default: every macro cell) from
         the macro solution ``u`` (default: the last ``solve()`` result), evaluated ON THE DEVICE where the stress is formed
@@ -1152,7 +1238,40 @@ class BaseHMM(ABC):
         ``field_values``: the values of the criterion's own fields ``f[k]`` per macro cell, in the shapes ``set_fields`` takes;
         ``RuntimeError`` when the criterion reads fields and they are missing.  In the criterion ``x`` is the macro cell midpoint and
         ``y`` the centroid of the micro element.  The cells run in chunks of ``chunk_cells`` (default: about 256 MB of what crosses the
-        boundary).  Under a process group this runs on the calling rank alone, for the cells it is given: there is no collective."""
+        boundary).  Under a process group this runs on the calling rank alone, for the cells it is given: there is no collective.
+
+        ``nonlinear=True`` (after ``solve_nonlinear``): the criterion on the NONLINEAR state -- the micro iteration of the
+        asked cells at ``u`` (default: the last result, which after ``solve_nonlinear`` is the nonlinear solution) with that call's
+        law, limits, starting history and, where it ran with ``load=True``, the solver's load, and the criterion on the stream every
+        cell stops on, on the device (hommx_secant_state_source): no stream crosses the boundary.  There ``c[k]`` is the softened
+        coefficient, ``b[k]`` the base one (the solver's ``A``) and ``h[k]`` the history at the start of the load step
+        (``Criterion(..., history=law.n_history)``), before or after ``commit_history()``.  The result also carries ``secant``
+        (rounds, change, status per cell); one WARNING when a cell did not stop with status 0.  ``load`` must stay None: the load of
+        the nonlinear run is part of its state.  A criterion that reads ``b`` or ``h`` needs ``nonlinear=True``.  Under a process
+        group the cells of a law with history must be among ``history_cells``."""
+        if nonlinear:
+            if load is not None:
+                raise ValueError("criterion(nonlinear=True) takes no load=: the load of the nonlinear run is part of its state "
+                                 "(solve_nonlinear(load=True) decides it)")
+            if crit.n_fields and field_values is None:
+                raise RuntimeError(f"the criterion reads the fields {', '.join(crit.field_names)}: pass field_values, their values per macro cell")
+            if self._nonlinear_state is not None and crit.n_history and crit.n_history != self._nonlinear_state["law"].n_history:
+                raise ValueError(f"the criterion declares history={crit.n_history}; the law of solve_nonlinear has "
+                                 f"{self._nonlinear_state['law'].n_history} history variables")
+            crit_rows = self._msh.cell_midpoints()
+            if crit.n_fields:
+                crit_rows = np.concatenate([crit_rows, self._field_values(crit, field_values)], axis=1)
+            n_el, t = self._cell_mesh.num_cells, self._tensor_size()
+            picked = self._cells_argument(cells, "criterion", local=False)
+            r = self._nonlinear_tail("criterion", u, picked, chunk_cells, 8 * (4 + (n_el if values else 0) + (2 * n_el * t if fields else 0)),
+                                     lambda b, n: dict(criterion=crit, crit_rows=crit_rows[picked[b:b + n]], crit_values=values,
+                                                       crit_fields=fields))
+            out = dataclasses.replace(r.criterion, cells=r.cells)
+            out.secant = dataclasses.replace(r, criterion=None, reconstruction=None)
+            return out
+        if crit.reads_state:
+            names = ", ".join(f"{n}[{crit.state_indices[n] - 1}]" for n in "bh" if crit.state_indices[n])
+            raise ValueError(f"the criterion reads {names}, the nonlinear state: pass nonlinear=True (after solve_nonlinear)")
         if load is True and self._polarisation is None:
             raise RuntimeError("criterion(load=True) needs a polarisation: call set_polarisation() or set_eigenstrain() first")
         if crit.n_fields and field_values is None:
@@ -1304,9 +1423,12 @@ class BaseHMM(ABC):
         boundary in each direction per macro step (DESIGN 4.17 has the measured cost); ``MicroCellPlan.secant_device`` keeps it
         resident for callers who drive the plan themselves.
 
+        ``criterion(crit, nonlinear=True)`` and ``reconstruct(nonlinear=True)`` evaluate the state this call ended in:
+        the solver keeps the law, the micro limits, the law's field rows, ``load`` and a reference to the history the step started
+        from.
+
         Out of scope: warm starts of the micro iteration
-        across macro steps (``MicroCellPlan.secant(coef_start=...)`` has them), ``reconstruct()`` / ``criterion()`` of the nonlinear
-        state (``MicroCellPlan.secant(return_coef=True)`` gives the stream to pass to them).  Under a process group every rank
+        across macro steps (``MicroCellPlan.secant(coef_start=...)`` has them).  Under a process group every rank
         iterates its block of the cells, as in ``solve()``."""
         if self._polarisation is not None and not load:
             raise RuntimeError("solve_nonlinear() does not take the polarisation or eigenstrain that is set unless it is told to: pass "
@@ -1356,6 +1478,9 @@ class BaseHMM(ABC):
                 converged = True
                 break
         self.secant, self.nonlinear_history = result, history
+        # `state` is the array the step started from: commit_history() rebinds self.history and mutates nothing, so the reference
+        # survives a commit and costs no copy
+        self._nonlinear_state = dict(law=law, micro_iter=micro_iter, micro_tol=micro_tol, relax=relax, rows=rows, load=bool(load), history=state)
         self._needs_reassembly = True
         counts = {int(s): int((result.status == s).sum()) for s in np.unique(result.status)} if result is not None else {}
         if not converged or any(s != 0 for s in counts):
@@ -1725,6 +1850,17 @@ class PoissonPeriodicHMM:
         self._A_hom = AH[0]
         self._correctors = h._on_micro_mesh(chi[0])
         return self._A_hom
+
+    def criterion(self, *args, nonlinear: bool = False, **kw):
+        """Not offered here: the nonlinear state belongs to ``PoissonHMM.solve_nonlinear`` (see ``solve_nonlinear``), and the linear
+        state of the one periodic cell is ``correctors`` and ``A_hom``."""
+        raise RuntimeError("PoissonPeriodicHMM has no criterion(): " + ("the nonlinear state is that of PoissonHMM.solve_nonlinear; " if nonlinear else "")
+                           + "use PoissonHMM.criterion")
+
+    def reconstruct(self, *args, nonlinear: bool = False, **kw):
+        """Not offered here, as ``criterion``."""
+        raise RuntimeError("PoissonPeriodicHMM has no reconstruct(): " + ("the nonlinear state is that of PoissonHMM.solve_nonlinear; " if nonlinear else "")
+                           + "use PoissonHMM.reconstruct")
 
     def solve_nonlinear(self, *args, **kw):
         """Not offered here: with one periodic cell for the whole domain the secant tensor would still differ from macro cell to

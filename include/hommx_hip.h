@@ -910,6 +910,59 @@ int hommx_secant_tangent_load_source_device(hommx_plan* plan, int64_t n_cells, c
                                             const hommx_secant_load_args* load, void* stream);
 
 /*
+ * Criteria and reconstruction statistics of the NONLINEAR state: a second tail behind the secant iteration.
+ * The rounds are exactly those of hommx_secant_load_source -- of hommx_secant_history_source or hommx_secant_source where `load` resp.
+ * `history` is NULL --, and every output named in *args and *history has its bits.  After the last round of a chunk the tail runs,
+ * per cell, on the stream coef_out describes, the corrector blocks of the last executed round (a stopped cell's elimination reproduces
+ * them), the load array or the eigenstress of that round, the base stream and history_in.  It adds no elimination.
+ *   crit_program  NULL: no criterion.  Else ONE component (n_comp == 1) on the row
+ *                   [midpoint (3) | fields (crit_n_fields) | e_K (t) | s_K (t) | c_K (n_comp) | h_K (n_history) | b_K (n_comp)],
+ *                 the row of a law with history with the base behind it: e_K the total strain, s_K = material(c_K) e_K + P_K the total
+ *                 flux (P the polarisation or the eigenstress of the round), c_K the stream the iteration stopped on, h_K history_in
+ *                 of the element (n_history == 0 without a history struct), b_K the base stream, what the law calls c[k].  `Y i`
+ *                 reads args->points.
+ *   crit_n_fields, crit_rows   the criterion's OWN fields, [n_cells][3 + crit_n_fields] (the law's rows stay args->rows)
+ *   threshold, crit, crit_values   as hommx_criterion_args.threshold, .crit ([n_cells][HOMMX_CRIT_NSTATS], required with a program)
+ *                 and .values ([n_cells][n_el] or NULL)
+ *   total_strain, total_flux   [n_cells][n_el][t], both or neither: what the criterion saw
+ *   reconstruct   != 0: stats [n_cells][HOMMX_RECON_NSTATS(t)] (required) and, with n_regions > 0, region / region_stats: the
+ *                 statistics of hommx_reconstruct_source on the stopped state
+ * For a program that reads neither b nor h, crit, crit_values, total_strain and total_flux are bit for bit what
+ * hommx_criterion_source returns for coef_out as a per-cell stream with the same xi, M, rows, points and load; stats and region_stats
+ * are bit for bit hommx_reconstruct_source's for coef_out.  A cell of status 0, 1 or 2 is evaluated on its c^j; a cell of status 3 keeps
+ * its info, its tail outputs may hold anything, and no other cell's outputs change.  The tail outputs of a cell do not depend on its
+ * batch position, the chunking, max_iter beyond its stopping round, the outputs asked for, or the entry point.  The chunk rule is the
+ * underlying entry's with the per-cell tail outputs and crit_rows counted; the tail holds no scratch of its own.
+ * HOMMX_EINVAL, before the plan's device is made current: everything the underlying entry refuses; a null state struct; neither a
+ * program nor reconstruct; with a program everything hommx_criterion_source refuses for program, fields, rows, threshold, crit and one
+ * of strain / flux alone, the program checked against a row of 3 + crit_n_fields + 2 t + 2 n_comp + n_history entries (an h index
+ * without a history struct is out of that row's h segment); with reconstruct a null stats, the region refusals of
+ * hommx_reconstruct_source, and reconstruct together with a load (the statistics have no load term: refused, not computed wrongly).
+ */
+typedef struct hommx_secant_state_args {
+  const hommx_coef_program* crit_program;
+  int32_t crit_n_fields;
+  const double* crit_rows;
+  double threshold;
+  double* crit;
+  double* crit_values;
+  double* total_strain;
+  double* total_flux;
+  int32_t reconstruct;
+  int32_t n_regions;
+  const uint8_t* region;
+  double* stats;
+  double* region_stats;
+} hommx_secant_state_args;
+int hommx_secant_state_source(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_secant_args* args,
+                              const hommx_history_args* history /* NULL: none */, const hommx_secant_load_args* load /* NULL: none */,
+                              const hommx_secant_state_args* state);
+/* Same with DEVICE pointers (in *src, *args, *history, *load, *load->P_source and *state; the structs and the programs are host memory), asynchronous on `stream` (hommx_solve_batch_device: the stream-order contract): max_iter rounds and the tail are queued, nothing is read back. */
+int hommx_secant_state_source_device(hommx_plan* plan, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
+                                     const hommx_secant_args* args, const hommx_history_args* history, const hommx_secant_load_args* load,
+                                     const hommx_secant_state_args* state, void* stream);
+
+/*
  * Unstructured periodic micro meshes.  Any simplicial mesh of the unit square / cube whose boundary is
  * periodic: the caller folds the mesh vertices into n_nodes independent (periodic) nodes -- cell_problem.py:38-300's slave -> master
  * map -- and passes, per element, the periodic node of every vertex and the UNFOLDED vertex coordinates (gradients and volumes).
