@@ -269,6 +269,30 @@ class SecantResult:
     reconstruction: Reconstruction | None = None
 
 
+# The host entries of the nonlinear family (include/hommx_hip.h), by (tangent, the last part of history < load < state that is there),
+# and what an entry of that part takes behind its argument struct: the parts before the last are optional there (None: NULL).  The
+# device form of an entry has the suffix and takes the stream last.  There is no tangent entry with a state tail.
+_SECANT_ENTRIES = {
+    (False, None): "hommx_secant_source",
+    (False, "history"): "hommx_secant_history_source",
+    (False, "load"): "hommx_secant_load_source",
+    (False, "state"): "hommx_secant_state_source",
+    (True, None): "hommx_secant_tangent_source",
+    (True, "history"): "hommx_secant_tangent_history_source",
+    (True, "load"): "hommx_secant_tangent_load_source",
+}
+_SECANT_TAKES = {None: (), "history": ("history",), "load": ("history", "load"), "state": ("history", "load", "state")}
+
+
+def _secant_entry(tangent: bool, hargs, largs, sargs, device: bool) -> tuple[str, tuple]:
+    """The entry a call of the nonlinear family goes to -> (its name, its arguments behind the argument struct): ``hargs`` / ``largs`` /
+    ``sargs`` the ``HistoryArgs`` / ``SecantLoadArgs`` / ``SecantStateArgs`` of the call, None for a part it does not have."""
+    parts = {"history": hargs, "load": largs, "state": sargs}
+    last = next((k for k in ("state", "load", "history") if parts[k] is not None), None)
+    name = _SECANT_ENTRIES[bool(tangent), last] + ("_device" if device else "")
+    return name, tuple(None if parts[k] is None else C.byref(parts[k]) for k in _SECANT_TAKES[last])
+
+
 REGION_FIELDS = ("region_volume", "region_mean_strain", "region_mean_flux", "region_energy", "region_max_flux", "region_argmax_element")
 
 
@@ -1061,10 +1085,9 @@ class MicroCellPlan:
 
     def _secant(self, coef, xi, law, M, rows, points, max_iter, tol, relax, coef_start, fields, values, return_coef, tangent_plan=None,
                 return_tangent_coef=False, history=None, load=(None, None, False), tail=None) -> SecantResult:
-        """The host call of ``secant`` (``tangent_plan`` None) and ``secant_tangent``; with the history entries for a law that has
-        history variables, and with the load entries (which take the history as an optional argument) for ``load`` = (P, per_cell,
-        eigenstrain) with a P.  ``tail``: what ``secant`` asks for on the stopped state (hommx_secant_state_source, which takes the
-        history and the load as optional arguments)."""
+        """The host call of ``secant`` (``tangent_plan`` None) and ``secant_tangent``, on the entry ``_secant_entry`` names for what the
+        call has: a history (a law with history variables), a load (``load`` = (P, per_cell, eigenstrain) with a P), a tail (``tail``:
+        what ``secant`` asks for on the stopped state)."""
         stream = self._as_stream(coef)
         nc = self._check_stream(stream)
         P, P_src, P_ptr, code = self._one_load(load[0], load[1], load[2], nc)
@@ -1106,82 +1129,31 @@ class MicroCellPlan:
         args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows.ctypes.data, addr(points), xi.ctypes.data, max_iter, tol, relax,
                                addr(coef_start), state.ctypes.data, None, mean_flux.ctypes.data, addr(out_coef), addr(strain), addr(flux),
                                addr(vals), None)
+        sargs = finish = None
         if tail is not None:
             if tangent_plan is not None:
                 raise ValueError("a tail behind the tangent entries is out of scope: call secant(criterion=...) for the state")
             sargs, keep, finish = self._state_tail(tail, law, stream, nc, rows, points, largs is not None)
-            src = stream.coef_source()
-
-            def call(Mp, o, i):
-                args.A_eff, args.info = o, i
-                return self._lib.hommx_secant_state_source(self._h, nc, C.byref(src), Mp, C.byref(args), None if hargs is None else C.byref(hargs),
-                                                           None if largs is None else C.byref(largs), C.byref(sargs))
-
-            A, info = self._host_call("hommx_secant_state_source", nc, M, call)
-            crit_result, recon_result = finish(xi, A, info)
-            return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
-                                strain, flux, vals, history=hist_out, criterion=crit_result, reconstruction=recon_result)
-        if largs is not None:
-            return self._secant_load(nc, M, stream, args, hargs, largs, tangent_plan, return_tangent_coef, state, mean_flux, out_coef, strain,
-                                     flux, vals, hist_out)
-        if tangent_plan is None and hargs is None:
-            A, info = self._source_call("hommx_secant_source", nc, M, stream, args)
-            return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
-                                strain, flux, vals)
-        if tangent_plan is None:
-            src = stream.coef_source()
-
-            def call(Mp, o, i):
-                args.A_eff, args.info = o, i
-                return self._lib.hommx_secant_history_source(self._h, nc, C.byref(src), Mp, C.byref(args), C.byref(hargs))
-
-            A, info = self._host_call("hommx_secant_history_source", nc, M, call)
-            return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
-                                strain, flux, vals, history=hist_out)
-        D = np.empty((nc, self.t, self.t), dtype=np.float64)
-        asym = np.empty(nc, dtype=np.float64)
-        tinfo = np.zeros(nc, dtype=np.int32)
-        tcoef = np.empty((nc, self.n_el, self.t * (self.t + 1) // 2), dtype=np.float64) if return_tangent_coef else None
-        targs = _lib.SecantTangentArgs(C.pointer(args), tangent_plan._h, D.ctypes.data, asym.ctypes.data, addr(tcoef), tinfo.ctypes.data)
+        struct, D, asym, tinfo, tcoef = args, None, None, None, None
+        if tangent_plan is not None:
+            D = np.empty((nc, self.t, self.t), dtype=np.float64)
+            asym = np.empty(nc, dtype=np.float64)
+            tinfo = np.zeros(nc, dtype=np.int32)
+            tcoef = np.empty((nc, self.n_el, self.t * (self.t + 1) // 2), dtype=np.float64) if return_tangent_coef else None
+            struct = _lib.SecantTangentArgs(C.pointer(args), tangent_plan._h, D.ctypes.data, asym.ctypes.data, addr(tcoef), tinfo.ctypes.data)
+        what, more = _secant_entry(tangent_plan is not None, hargs, largs, sargs, device=False)
         src = stream.coef_source()
 
         def call(Mp, o, i):
             args.A_eff, args.info = o, i
-            if hargs is not None:
-                return self._lib.hommx_secant_tangent_history_source(self._h, nc, C.byref(src), Mp, C.byref(targs), C.byref(hargs))
-            return self._lib.hommx_secant_tangent_source(self._h, nc, C.byref(src), Mp, C.byref(targs))
+            return getattr(self._lib, what)(self._h, nc, C.byref(src), Mp, C.byref(struct), *more)
 
-        A, info = self._host_call("hommx_secant_tangent_source" if hargs is None else "hommx_secant_tangent_history_source", nc, M, call)
-        return SecantResult(A, mean_flux, state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64), info, out_coef,
-                            strain, flux, vals, None, D, asym, tinfo, tcoef, hist_out)
-
-    def _secant_load(self, nc, M, stream, args, hargs, largs, tangent_plan, return_tangent_coef, state, mean_flux, out_coef, strain, flux,
-                     vals, hist_out) -> SecantResult:
-        """The host call of ``_secant`` beside a load: hommx_secant_load_source, or with ``tangent_plan`` hommx_secant_tangent_load_source;
-        ``hargs`` None: a law without history variables."""
-        src = stream.coef_source()
-        hp = None if hargs is None else C.byref(hargs)
-        addr = lambda a: None if a is None else a.ctypes.data
-        status = lambda: (state[:, 0].astype(np.int64), state[:, 1].copy(), state[:, 2].astype(np.int64))
-        if tangent_plan is None:
-            def call(Mp, o, i):
-                args.A_eff, args.info = o, i
-                return self._lib.hommx_secant_load_source(self._h, nc, C.byref(src), Mp, C.byref(args), hp, C.byref(largs))
-
-            A, info = self._host_call("hommx_secant_load_source", nc, M, call)
-            return SecantResult(A, mean_flux, *status(), info, out_coef, strain, flux, vals, history=hist_out)
-        D = np.empty((nc, self.t, self.t), dtype=np.float64)
-        asym = np.empty(nc, dtype=np.float64)
-        tinfo = np.zeros(nc, dtype=np.int32)
-        tcoef = np.empty((nc, self.n_el, self.t * (self.t + 1) // 2), dtype=np.float64) if return_tangent_coef else None
-        targs = _lib.SecantTangentArgs(C.pointer(args), tangent_plan._h, D.ctypes.data, asym.ctypes.data, addr(tcoef), tinfo.ctypes.data)
-
-        def call(Mp, o, i):
-            args.A_eff, args.info = o, i
-            return self._lib.hommx_secant_tangent_load_source(self._h, nc, C.byref(src), Mp, C.byref(targs), hp, C.byref(largs))
-
-        A, info = self._host_call("hommx_secant_tangent_load_source", nc, M, call)
-        return SecantResult(A, mean_flux, *status(), info, out_coef, strain, flux, vals, None, D, asym, tinfo, tcoef, hist_out)
+        A, info = self._host_call(what, nc, M, call)
+        crit_result, recon_result = (None, None) if finish is None else finish(xi, A, info)
+        return SecantResult(A_eff=A, mean_flux=mean_flux, rounds=state[:, 0].astype(np.int64), change=state[:, 1].copy(),
+                            status=state[:, 2].astype(np.int64), info=info, coef=out_coef, strain=strain, flux=flux, values=vals, tangent=D,
+                            asymmetry=asym, tangent_info=tinfo, tangent_coef=tcoef, history=hist_out, criterion=crit_result,
+                            reconstruction=recon_result)
 
     def solve_two_phase(self, mask: np.ndarray, values: np.ndarray, M: np.ndarray | None = None,
                         return_info: bool = False):
@@ -1392,14 +1364,10 @@ class MicroCellPlan:
         ``criterion`` (a ``Criterion``, as in ``secant``) with crit_rows[n_cells, 3 + criterion.n_fields] -> crit[n_cells, 4],
         crit_values[n_cells, n_el], total_strain / total_flux[n_cells, n_el, t]; ``stats_ptr``: the reconstruction statistics
         stats[n_cells, 2 t + 3] and, with ``n_regions``, regions[n_el] (uint8) -> region_stats[n_cells, n_regions, 2 t + 4]."""
-        hargs = self._device_history(law, history_in_ptr, history_out_ptr)
-        max_iter, tol, relax = self._secant_limits(max_iter, tol, relax)
-        prog = self._law_program(law)
-        pstruct = prog.struct()
-        args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows_ptr, points_ptr or None, xi_ptr, max_iter, tol, relax,
-                               coef_start_ptr or None, state_ptr, A_ptr, mean_flux_ptr or None, coef_ptr or None, strain_ptr or None,
-                               flux_ptr or None, values_ptr or None, info_ptr or None)
-        largs = self._device_load(P_ptr, P_source, eigenstrain)
+        args, hargs, largs, keep = self._device_args(law, (max_iter, tol, relax), (history_in_ptr, history_out_ptr),
+                                                     (P_ptr, P_source, eigenstrain), rows_ptr, points_ptr, xi_ptr, coef_start_ptr, state_ptr,
+                                                     A_ptr, mean_flux_ptr, coef_ptr, strain_ptr, flux_ptr, values_ptr, info_ptr)
+        sargs = None
         if criterion is not None or stats_ptr:
             sargs = _lib.SecantStateArgs()
             if criterion is not None:
@@ -1413,24 +1381,26 @@ class MicroCellPlan:
             if stats_ptr:
                 sargs.reconstruct, sargs.n_regions, sargs.region = 1, int(n_regions), regions_ptr or None
                 sargs.stats, sargs.region_stats = stats_ptr, region_stats_ptr or None
-            _lib.check(self._lib.hommx_secant_state_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
-                                                                  None if hargs is None else C.byref(hargs),
-                                                                  None if largs is None else C.byref(largs), C.byref(sargs), stream or None),
-                       "hommx_secant_state_source_device")
-            return
-        if crit_rows_ptr or crit_ptr or crit_values_ptr or total_strain_ptr or total_flux_ptr or regions_ptr or region_stats_ptr or n_regions:
+        elif crit_rows_ptr or crit_ptr or crit_values_ptr or total_strain_ptr or total_flux_ptr or regions_ptr or region_stats_ptr or n_regions:
             raise ValueError("the crit_* pointers belong to criterion=..., the regions to stats_ptr")
-        if largs is not None:
-            _lib.check(self._lib.hommx_secant_load_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
-                                                                 None if hargs is None else C.byref(hargs), C.byref(largs), stream or None),
-                       "hommx_secant_load_source_device")
-            return
-        if hargs is not None:
-            _lib.check(self._lib.hommx_secant_history_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args),
-                                                                    C.byref(hargs), stream or None), "hommx_secant_history_source_device")
-            return
-        _lib.check(self._lib.hommx_secant_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(args), stream or None),
-                   "hommx_secant_source_device")
+        self._secant_device_call(n_cells, source, M_ptr, args, False, hargs, largs, sargs, stream)
+
+    def _device_args(self, law, limits, history, load, rows_ptr, points_ptr, xi_ptr, coef_start_ptr, state_ptr, A_ptr, *optional) -> tuple:
+        """What ``secant_device`` and ``secant_tangent_device`` build alike -> (``SecantArgs``, ``HistoryArgs`` or None,
+        ``SecantLoadArgs`` or None, what keeps the program alive): ``limits`` = (max_iter, tol, relax), ``history`` = (history_in_ptr,
+        history_out_ptr), ``load`` = (P_ptr, P_source, eigenstrain), ``optional`` = the pointers behind A_eff in the struct's order."""
+        hargs = self._device_history(law, *history)
+        max_iter, tol, relax = self._secant_limits(*limits)
+        prog = self._law_program(law)
+        pstruct = prog.struct()
+        args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows_ptr, points_ptr or None, xi_ptr, max_iter, tol, relax,
+                               coef_start_ptr or None, state_ptr, A_ptr, *(q or None for q in optional))
+        return args, hargs, self._device_load(*load), (prog, pstruct)
+
+    def _secant_device_call(self, n_cells, source, M_ptr, struct, tangent: bool, hargs, largs, sargs, stream):
+        """The device entry of the combination (``_secant_entry``) on ``struct``, the ``SecantArgs`` or ``SecantTangentArgs`` of the call."""
+        what, more = _secant_entry(tangent, hargs, largs, sargs, device=True)
+        _lib.check(getattr(self._lib, what)(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(struct), *more, stream or None), what)
 
     @staticmethod
     def _device_load(P_ptr, P_source, eigenstrain):
@@ -1468,29 +1438,12 @@ class MicroCellPlan:
         ``secant_device`` (hommx_secant_tangent_history_source_device); ``P_ptr`` / ``P_source`` / ``eigenstrain``: the load of
         ``secant_device`` (hommx_secant_tangent_load_source_device)."""
         self._check_tangent(law, tangent_plan)
-        hargs = self._device_history(law, history_in_ptr, history_out_ptr)
-        max_iter, tol, relax = self._secant_limits(max_iter, tol, relax)
-        prog = self._law_program(law)
-        pstruct = prog.struct()
-        args = _lib.SecantArgs(C.pointer(pstruct), int(law.n_fields), rows_ptr, points_ptr or None, xi_ptr, max_iter, tol, relax,
-                               coef_start_ptr or None, state_ptr, A_ptr, mean_flux_ptr or None, coef_ptr or None, strain_ptr or None,
-                               flux_ptr or None, values_ptr or None, info_ptr or None)
+        args, hargs, largs, keep = self._device_args(law, (max_iter, tol, relax), (history_in_ptr, history_out_ptr),
+                                                     (P_ptr, P_source, eigenstrain), rows_ptr, points_ptr, xi_ptr, coef_start_ptr, state_ptr,
+                                                     A_ptr, mean_flux_ptr, coef_ptr, strain_ptr, flux_ptr, values_ptr, info_ptr)
         targs = _lib.SecantTangentArgs(C.pointer(args), tangent_plan._h, tangent_ptr, asymmetry_ptr, tangent_coef_ptr or None,
                                        tangent_info_ptr or None)
-        largs = self._device_load(P_ptr, P_source, eigenstrain)
-        if largs is not None:
-            _lib.check(self._lib.hommx_secant_tangent_load_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None,
-                                                                         C.byref(targs), None if hargs is None else C.byref(hargs),
-                                                                         C.byref(largs), stream or None),
-                       "hommx_secant_tangent_load_source_device")
-            return
-        if hargs is not None:
-            _lib.check(self._lib.hommx_secant_tangent_history_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None,
-                                                                            C.byref(targs), C.byref(hargs), stream or None),
-                       "hommx_secant_tangent_history_source_device")
-            return
-        _lib.check(self._lib.hommx_secant_tangent_source_device(self._h, int(n_cells), C.byref(source), M_ptr or None, C.byref(targs),
-                                                                stream or None), "hommx_secant_tangent_source_device")
+        self._secant_device_call(n_cells, source, M_ptr, targs, True, hargs, largs, None, stream)
 
     def solve_separable_device(self, n_cells: int, family: str, n_q: int, table_ptr: int, weights_ptr: int | None, params_ptr: int,
                                M_ptr: int | None, out_ptr: int, info_ptr: int | None, stream: int | None = None):

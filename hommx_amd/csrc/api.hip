@@ -1672,70 +1672,90 @@ int crit_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const 
                       nullptr, false, program ? &load : nullptr);
 }
 
-// -- strain-dependent coefficients (hommx_secant_source[_device]) --------------------------------------------------------------------------
-// one chunk on the device: the current stream starts as coef_start or the base stream; per round the correctors of the current stream
-// into the plan's scratch, then k_secant_update.  The device entry queues max_iter rounds and reads nothing; the host entry reads the
-// chunk's state after each round and stops when no cell runs -- a stopped cell is frozen, so the bits are the same
-// tail: what hommx_secant_tangent_source adds behind the last round of a chunk (null: the iteration alone).  After the last queued round
-// the corrector buffer holds the correctors of `cur` for every cell -- a stopped cell's elimination reproduces, a stopping round never
-// commits --, so one launch of k_secant_tangent forms the tangent stream (the caller's tangent_coef, else scratch of the chunk in
-// B_SECANT), solve_source_device eliminates it on the tangent plan, in that plan's own workspace, and the cells of status 2 or 3 get NaN
-struct TangentTail {
-  hommx_plan* plan;
-  double *tangent, *asymmetry, *coef;
-  int32_t* info;
+// -- the nonlinear family: strain-dependent coefficients (hommx_secant*_source[_device]; DESIGN.md sections 4.15 - 4.19) ------------------
+// One request describes a call of any of the fourteen entries: the iteration's arguments and what the entry takes beside them -- the
+// tangent's struct (the tangent entries), a history, a load, a state tail.  A part the entry requires (`need`) must be there; any other
+// part that is null is absent
+enum : unsigned { NEED_HISTORY = 1, NEED_LOAD = 2, NEED_STATE = 4 };
+struct SecantRequest {
+  const void* given;                         // the entry's own argument struct: `secant` or, of a tangent entry, `tangent`
+  const hommx_secant_args* secant;           // the iteration's: the entry's own struct, or the one the tangent's struct points to
+  const hommx_secant_tangent_args* tangent;  // null: no tangent tail
+  const hommx_history_args* hist;
+  const hommx_secant_load_args* load;
+  const hommx_secant_state_args* state;
+  unsigned need;
 };
-// the field of the tangent kernel lies in the slot where it does not fit LDS beside the (wider) stack rows of the forward mode
-bool tangent_in_lds(const hommx_plan* p, int depth) {
-  return hommx::secant_tangent_lds_bytes(plan_ndof(p), depth, hommx::secant_tangent_slots(p->ks.t, depth)) <= hommx::recon_lds_limit();
+SecantRequest secant_request(const hommx_secant_args* a, unsigned need = 0, const hommx_history_args* hist = nullptr,
+                             const hommx_secant_load_args* load = nullptr, const hommx_secant_state_args* state = nullptr) {
+  return {a, a, nullptr, hist, load, state, need};
 }
+SecantRequest secant_request(const hommx_secant_tangent_args* a, unsigned need = 0, const hommx_history_args* hist = nullptr,
+                             const hommx_secant_load_args* load = nullptr) {
+  return {a, a ? a->secant : nullptr, a, hist, load, nullptr, need};
+}
+
+// The request as the chunk driver re-bases it: a copy of every struct that is there (h.n_history 0 and null pointers: no history).
+// l.P is the load array of the chunk, [nc][n_el][t]: the caller's, its copy in B_IN or the expansion of the program in B_POLAR;
+// l.P_source and g.secant are not read
+struct SecantCall {
+  hommx_secant_args s;
+  hommx_history_args h;
+  bool has_load, has_state, has_tangent;
+  hommx_secant_load_args l;
+  hommx_secant_state_args t;
+  hommx_secant_tangent_args g;
+};
+
+// Where the field of a kernel of the call lives: in LDS beside the interpreter's stack, or, where it does not fit there, in the slot of
+// global scratch behind the corrector blocks.  The one definition under the scratch a chunk holds and under every launch
+enum SecantKernel { K_ROUND, K_TANGENT, K_CRITERION, K_RECON };
+bool secant_field_in_slot(const hommx_plan* p, const SecantCall& c, SecantKernel k) {
+  const int depth = program_depth(*c.s.program);
+  switch (k) {
+    case K_ROUND: return !crit_in_lds(p, depth);
+    case K_TANGENT:  // the stack rows of the forward mode are (1 + P) wide
+      return c.has_tangent &&
+             hommx::secant_tangent_lds_bytes(plan_ndof(p), depth, hommx::secant_tangent_slots(p->ks.t, depth)) > hommx::recon_lds_limit();
+    case K_CRITERION: return c.has_state && c.t.crit_program && !crit_in_lds(p, program_depth(*c.t.crit_program));
+    case K_RECON: return c.has_state && c.t.reconstruct && !recon_in_lds(p);
+  }
+  return false;
+}
+bool secant_slot_used(const hommx_plan* p, const SecantCall& c) {
+  const SecantKernel all[] = {K_ROUND, K_TANGENT, K_CRITERION, K_RECON};
+  return std::any_of(all, all + 4, [&](SecantKernel k) { return secant_field_in_slot(p, c, k); });
+}
+// ... and where it is addressed: `corr` holds [canonical blocks | with a load, as many for its corrector | slot] per chunk
+double* secant_slot(const hommx_plan* p, const SecantCall& c, SecantKernel k, double* corr, int64_t chunk) {
+  return secant_field_in_slot(p, c, k) ? corr + chunk * (c.has_load ? 2 : 1) * p->ks.t * plan_ndof(p) : nullptr;
+}
+
 int64_t tangent_stream_doubles(const hommx_plan* p) { return p->n_el * (p->ks.t * (p->ks.t + 1) / 2); }
 
-// hist: the history variables of the law (null: none, and every launch is the one it was) -- the rounds are k_secant_history's, reading
-// history_in and writing history_out of the chunk, and the tail is k_secant_tangent_history on the law truncated behind the last
-// component's STORE
-// load: the one load of the chunk beside the law (null: none, and every launch is the one it was) -- per round
-// the eigenstress of the current stream where the flag is set (k_eigenstress into scratch of the chunk: the eigenstrain stays as it
-// is, every round and the kernels read it), the canonical correctors, the corrector of the load into the block behind them
-// (load_correctors: the block layout of crit_run), then k_secant_load; the tail is k_secant_tangent_load on the blocks of the last round
-struct SecantLoad {
-  int32_t code;     // HOMMX_LOADS_PER_CELL or HOMMX_LOADS_PROGRAM, alone or with HOMMX_LOADS_EIGENSTRAIN
-  const double* P;  // [nc][n_el][t] of the chunk: the caller's array, its copy in B_IN or the expansion of the program in B_POLAR
+// what the rounds of a chunk leave for the tails: the blocks are those of the last executed round
+struct SecantRounds {
+  double* cur;      // the stream the iteration stands on
+  double* corr;     // the corrector buffer: the canonical blocks, the load's block, the slot
+  double* chi;      // the load's block (null: no load)
+  const double* P;  // what that block was solved for: the load array or, of an eigenstrain, the eigenstress of the round (null: no load)
+  const double* E;  // the eigenstrain (null: none)
+  double* tan;      // scratch of the chunk for the tangent stream (null: the caller takes tangent_coef, or no tangent tail)
 };
-// state: the second tail, what hommx_secant_state_source adds behind the last round of a chunk (null: none, and every launch is the one
-// it was) -- k_criterion_state and / or k_recon on `cur`, the corrector blocks of the last executed round and
-// its load array or eigenstress, with the field in the slot behind the blocks where it does not fit LDS; no elimination
-bool state_in_lds(const hommx_plan* p, const hommx_secant_state_args* s) {
-  if (s && s->crit_program && !crit_in_lds(p, program_depth(*s->crit_program))) return false;
-  return !(s && s->reconstruct) || recon_in_lds(p);
-}
-int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, const double* M, const hommx_secant_args& a, bool device,
-               hipStream_t st, const TangentTail* tail = nullptr, const hommx_history_args* hist = nullptr, const SecantLoad* load = nullptr,
-               const hommx_secant_state_args* state = nullptr) {
-  const int t = p->ks.t, depth = program_depth(*a.program);
-  const bool slot = !crit_in_lds(p, depth), tail_slot = (tail && !tangent_in_lds(p, depth)) || !state_in_lds(p, state);
-  const bool eigen = load && load_eigenstrain(load->code);
-  const size_t stream = sizeof(double) * p->n_el * p->ks.n_comp;
-  const size_t bytes[5] = {stream * chunk, stream * chunk, a.info ? 0 : sizeof(int32_t) * chunk,
-                           tail && !tail->coef ? sizeof(double) * tangent_stream_doubles(p) * chunk : 0,
-                           eigen ? sizeof(double) * p->n_el * t * chunk : 0};
-  char* at[5];
-  if (int rc = carve(p->buf[B_SECANT], bytes, at)) return rc;
-  double *cur = reinterpret_cast<double*>(at[0]), *cand = reinterpret_cast<double*>(at[1]);
-  int32_t* info = a.info ? a.info : reinterpret_cast<int32_t*>(at[2]);
-  HIP_TRY(hipMemcpyAsync(cur, a.coef_start ? a.coef_start : coef, stream * nc, hipMemcpyDeviceToDevice, st));
-  double* stress = reinterpret_cast<double*>(at[4]);  // the eigenstress of the round
-  hommx::SecantLoadArgs k;  // without a load its SecantHistoryArgs alone is launched, without a history its SecantArgs
+
+// the arguments of every round of a chunk but the round's own (corr, load, slot, round).  Without a load its SecantHistoryArgs alone is
+// launched, without a history its SecantArgs
+hommx::SecantLoadArgs secant_round_args(const hommx_plan* p, const Chunk<SecantCall>& v, double* cur, double* cand, int32_t* info) {
+  const hommx_secant_args& a = v.a.s;
+  hommx::SecantLoadArgs k;
   set_geometry(p, k);
-  if (hist) {
-    k.hist_in = hist->history_in;
-    k.hist_out = hist->history_out;
-    k.n_history = hist->n_history;
-  }
-  k.base = coef;
+  k.hist_in = v.a.h.history_in;
+  k.hist_out = v.a.h.history_out;
+  k.n_history = v.a.h.n_history;
+  k.base = v.coef;
   k.cur = cur;
   k.cand = cand;
-  k.M = M;
+  k.M = v.M;
   k.xi = a.xi;
   k.prog = program_args(*a.program);
   k.n_fields = a.n_fields;
@@ -1750,27 +1770,47 @@ int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, con
   k.law_values = a.law_values;
   k.strain = a.strain;
   k.flux = a.flux;
+  return k;
+}
+
+// The rounds of one chunk: the current stream starts as coef_start or the base stream; per round the eigenstress of the current stream
+// (an eigenstrain: k_eigenstress into scratch of the chunk), the canonical correctors, with a load its corrector into the block behind
+// them (load_correctors: the block layout of crit_run), then k_secant_load, k_secant_history or k_secant_update.  The device entry
+// queues max_iter rounds and reads nothing; the host entry reads the chunk's state after each round and stops when no cell runs -- a
+// stopped cell is frozen, so the bits are the same
+int secant_rounds(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<SecantCall>& v, bool device, hipStream_t st, SecantRounds* out) {
+  const hommx_secant_args& a = v.a.s;
+  const int t = p->ks.t, depth = program_depth(*a.program);
+  const bool load = v.a.has_load, eigen = load && load_eigenstrain(v.a.l.per_cell);
+  const size_t stream = sizeof(double) * p->n_el * p->ks.n_comp;
+  const size_t bytes[5] = {stream * chunk, stream * chunk, a.info ? 0 : sizeof(int32_t) * chunk,
+                           v.a.has_tangent && !v.a.g.tangent_coef ? sizeof(double) * tangent_stream_doubles(p) * chunk : 0,
+                           eigen ? sizeof(double) * p->n_el * t * chunk : 0};
+  char* at[5];
+  if (int rc = carve(p->buf[B_SECANT], bytes, at)) return rc;
+  double *cur = reinterpret_cast<double*>(at[0]), *stress = reinterpret_cast<double*>(at[4]);  // stress: the eigenstress of the round
+  int32_t* info = a.info ? a.info : reinterpret_cast<int32_t*>(at[2]);
+  HIP_TRY(hipMemcpyAsync(cur, a.coef_start ? a.coef_start : v.coef, stream * nc, hipMemcpyDeviceToDevice, st));
+  hommx::SecantLoadArgs k = secant_round_args(p, v, cur, reinterpret_cast<double*>(at[1]), info);
+  *out = SecantRounds{cur, nullptr, nullptr, nullptr, eigen ? v.a.l.P : nullptr, reinterpret_cast<double*>(at[3])};
   std::vector<double> seen;
-  double* corr = nullptr;
   for (int j = 0; j < a.max_iter; ++j) {
     double* d_A_eff = a.A_eff;
-    if (eigen) HIP_TRY(hommx::launch_eigenstress(p->desc.dim, p->desc.kind, cur, load->P, true, stress, 1, p->n_el, nc, st));
-    if (int rc = chunk_correctors(p, nc, chunk, cur, M, &d_A_eff, info, (load ? t : 0) + (slot || tail_slot ? 1 : 0), st, &corr)) return rc;
-    k.corr = corr;
-    double* behind = corr + chunk * t * k.ndof;
+    if (eigen) HIP_TRY(hommx::launch_eigenstress(p->desc.dim, p->desc.kind, cur, v.a.l.P, true, stress, 1, p->n_el, nc, st));
+    if (int rc = chunk_correctors(p, nc, chunk, cur, v.M, &d_A_eff, info, (load ? t : 0) + (secant_slot_used(p, v.a) ? 1 : 0), st, &out->corr))
+      return rc;
+    k.corr = out->corr;
     if (load) {
-      const double* P = eigen ? stress : load->P;
-      if (int rc = load_correctors(p, nc, chunk, cur, M, hommx::LoadOverride{P, 1, true}, st, behind)) return rc;
-      k.load.chi = behind;
-      k.load.P = eigen ? nullptr : P;
-      k.load.E = eigen ? load->P : nullptr;
-      behind += chunk * t * k.ndof;
+      out->chi = out->corr + chunk * t * k.ndof;
+      out->P = eigen ? stress : v.a.l.P;
+      if (int rc = load_correctors(p, nc, chunk, cur, v.M, hommx::LoadOverride{out->P, 1, true}, st, out->chi)) return rc;
+      k.load = hommx::RoundLoad{out->chi, eigen ? nullptr : out->P, out->E};
     }
-    k.slot = slot ? behind : nullptr;
+    k.slot = secant_slot(p, v.a, K_ROUND, out->corr, chunk);
     k.round = j;
-    HIP_TRY(load   ? hommx::launch_secant_load(k, depth, nc, st)
-            : hist ? hommx::launch_secant_history(k, depth, nc, st)
-                   : hommx::launch_secant(k, depth, nc, st));
+    HIP_TRY(load          ? hommx::launch_secant_load(k, depth, nc, st)
+            : k.n_history ? hommx::launch_secant_history(k, depth, nc, st)
+                          : hommx::launch_secant(k, depth, nc, st));
     if (device) continue;
     seen.resize(HOMMX_SECANT_NSTATE * nc);
     HIP_TRY(hipMemcpy(seen.data(), a.state, sizeof(double) * seen.size(), hipMemcpyDeviceToHost));
@@ -1779,91 +1819,116 @@ int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const double* coef, con
     if (!running) break;
   }
   if (a.coef_out) HIP_TRY(hipMemcpyAsync(a.coef_out, cur, stream * nc, hipMemcpyDeviceToDevice, st));
-  if (state) {
-    double* field_slot = corr + chunk * (load ? 2 : 1) * t * k.ndof;  // behind the blocks of the last executed round
-    if (state->crit_program) {
-      const int crit_depth = program_depth(*state->crit_program);
-      hommx::CritStateArgs c;
-      set_geometry(p, c);
-      c.corr = corr;
-      c.coef = cur;
-      c.M = M;
-      c.xi = a.xi;
-      c.prog = program_args(*state->crit_program);
-      c.n_fields = state->crit_n_fields;
-      c.rows = state->crit_rows;
-      c.points = a.points;
-      c.threshold = state->threshold;
-      c.crit = state->crit;
-      c.values = state->crit_values;
-      c.strain = state->total_strain;
-      c.flux = state->total_flux;
-      if (load) {
-        c.corr_load = k.load.chi;
-        c.P = eigen ? stress : load->P;
-        c.per_cell = true;
-      }
-      c.base = coef;
-      c.hist_in = hist ? hist->history_in : nullptr;
-      c.n_history = hist ? hist->n_history : 0;
-      c.slot = crit_in_lds(p, crit_depth) ? nullptr : field_slot;
-      HIP_TRY(hommx::launch_criterion_state(c, crit_depth, nc, st));
-    }
-    if (state->reconstruct) {
-      hommx::ReconArgs r;
-      set_geometry(p, r);
-      r.corr = corr;
-      r.coef = cur;
-      r.M = M;
-      r.xi = a.xi;
-      r.stats = state->stats;
-      r.slot = recon_in_lds(p) ? nullptr : field_slot;
-      r.n_regions = state->n_regions;
-      r.region = state->n_regions ? state->region : nullptr;
-      r.region_stats = state->region_stats;
-      HIP_TRY(hommx::launch_reconstruct(r, nc, st));
-    }
-  }
-  if (!tail) return HOMMX_OK;
-  hommx::SecantTangentLoadArgs g;  // likewise
+  return HOMMX_OK;
+}
+
+// the state tail (hommx_secant_state_source): k_criterion_state and / or k_recon on `cur`, the corrector blocks
+// of the last executed round and its load array or eigenstress; no elimination
+hommx::CritStateArgs state_criterion_args(const hommx_plan* p, int64_t chunk, const Chunk<SecantCall>& v, const SecantRounds& r) {
+  const hommx_secant_state_args& s = v.a.t;
+  hommx::CritStateArgs c;
+  set_geometry(p, c);
+  c.corr = r.corr;
+  c.coef = r.cur;
+  c.M = v.M;
+  c.xi = v.a.s.xi;
+  c.prog = program_args(*s.crit_program);
+  c.n_fields = s.crit_n_fields;
+  c.rows = s.crit_rows;
+  c.points = v.a.s.points;
+  c.threshold = s.threshold;
+  c.crit = s.crit;
+  c.values = s.crit_values;
+  c.strain = s.total_strain;
+  c.flux = s.total_flux;
+  c.corr_load = r.chi;
+  c.P = r.P;
+  c.per_cell = v.a.has_load;
+  c.base = v.coef;
+  c.hist_in = v.a.h.history_in;
+  c.n_history = v.a.h.n_history;
+  c.slot = secant_slot(p, v.a, K_CRITERION, r.corr, chunk);
+  return c;
+}
+hommx::ReconArgs state_recon_args(const hommx_plan* p, int64_t chunk, const Chunk<SecantCall>& v, const SecantRounds& r) {
+  const hommx_secant_state_args& s = v.a.t;
+  hommx::ReconArgs a;
+  set_geometry(p, a);
+  a.corr = r.corr;
+  a.coef = r.cur;
+  a.M = v.M;
+  a.xi = v.a.s.xi;
+  a.stats = s.stats;
+  a.slot = secant_slot(p, v.a, K_RECON, r.corr, chunk);
+  a.n_regions = s.n_regions;
+  a.region = s.n_regions ? s.region : nullptr;
+  a.region_stats = s.region_stats;
+  return a;
+}
+int state_tail(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<SecantCall>& v, const SecantRounds& r, hipStream_t st) {
+  if (v.a.t.crit_program)
+    HIP_TRY(hommx::launch_criterion_state(state_criterion_args(p, chunk, v, r), program_depth(*v.a.t.crit_program), nc, st));
+  if (v.a.t.reconstruct) HIP_TRY(hommx::launch_reconstruct(state_recon_args(p, chunk, v, r), nc, st));
+  return HOMMX_OK;
+}
+
+// the tangent tail (hommx_secant_tangent_source).  After the last queued round the corrector buffer holds the
+// correctors of `cur` for every cell -- a stopped cell's elimination reproduces, a stopping round never commits --, so one launch of
+// k_secant_tangent[_history | _load] forms the tangent stream, solve_source_device eliminates it on the tangent plan, in that plan's
+// own workspace, and the cells of status 2 or 3 get NaN.  Of the argument struct the base of the kernel that is launched is read, as in a round
+hommx::SecantTangentLoadArgs tangent_args(const hommx_plan* p, int64_t chunk, const Chunk<SecantCall>& v, const SecantRounds& r) {
+  const hommx_secant_args& a = v.a.s;
+  hommx::SecantTangentLoadArgs g;
   set_geometry(p, g);
-  g.corr = corr;
-  g.M = M;
-  g.base = coef;
-  g.cur = cur;
+  g.corr = r.corr;
+  g.M = v.M;
+  g.base = v.coef;
+  g.cur = r.cur;
   g.xi = a.xi;
-  g.prog = k.prog;
+  g.prog = program_args(*a.program);
   g.n_fields = a.n_fields;
   g.rows = a.rows;
   g.points = a.points;
   g.state = a.state;
-  g.tan = tail->coef ? tail->coef : reinterpret_cast<double*>(at[3]);
-  g.asym = tail->asymmetry;
-  g.slot = tail_slot ? corr + chunk * (load ? 2 : 1) * t * g.ndof : nullptr;
-  if (load) {  // the blocks of the last executed round
-    g.corr_load = k.load.chi;
-    g.E = k.load.E;
-  }
-  if (hist) {
-    g.hist_in = hist->history_in;
-    g.n_history = hist->n_history;
+  g.tan = v.a.g.tangent_coef ? v.a.g.tangent_coef : r.tan;
+  g.asym = v.a.g.asymmetry;
+  g.slot = secant_slot(p, v.a, K_TANGENT, r.corr, chunk);
+  g.corr_load = r.chi;
+  g.E = r.E;
+  g.hist_in = v.a.h.history_in;
+  g.n_history = v.a.h.n_history;
+  if (g.n_history)
     for (int pc = 0; pc < a.program->n_ops; ++pc)  // the updates stand behind the last component's STORE
       if (a.program->ops[2 * pc] == hommx::OP_STORE && a.program->ops[2 * pc + 1] < p->ks.n_comp) g.prog.n_ops = pc + 1;
-  }
-  HIP_TRY(load   ? hommx::launch_secant_tangent_load(g, depth, nc, st)
-          : hist ? hommx::launch_secant_tangent_history(g, depth, nc, st)
-                 : hommx::launch_secant_tangent(g, depth, nc, st));
-  if (int rc = solve_source_device(tail->plan, nc, sampled_source(g.tan), M, tail->tangent, tail->info, st)) return rc;
-  HIP_TRY(hommx::launch_tangent_mask(a.state, tail->tangent, t * t, nc, st));
+  return g;
+}
+int tangent_tail(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<SecantCall>& v, const SecantRounds& r, hipStream_t st) {
+  const hommx::SecantTangentLoadArgs g = tangent_args(p, chunk, v, r);
+  const int depth = program_depth(*v.a.s.program);
+  HIP_TRY(v.a.has_load  ? hommx::launch_secant_tangent_load(g, depth, nc, st)
+          : g.n_history ? hommx::launch_secant_tangent_history(g, depth, nc, st)
+                        : hommx::launch_secant_tangent(g, depth, nc, st));
+  if (int rc = solve_source_device(v.a.g.tangent_plan, nc, sampled_source(g.tan), v.M, v.a.g.tangent, v.a.g.tangent_info, st)) return rc;
+  HIP_TRY(hommx::launch_tangent_mask(v.a.s.state, v.a.g.tangent, p->ks.t * p->ks.t, nc, st));
   return HOMMX_OK;
 }
 
-// the checks of hommx_secant_args against the plan's descriptor; hist: the call is one of the history entries, whose struct is checked
-// first and whose program has n_history more components on a row as much longer
-int secant_checks(const hommx_plan* p, const hommx_secant_args* a, const hommx_history_args* const* hist = nullptr) {
+// one chunk on the device: the rounds, then the tails the call has on what the rounds left
+int secant_run(hommx_plan* p, int64_t nc, int64_t chunk, const Chunk<SecantCall>& v, bool device, hipStream_t st) {
+  SecantRounds r;
+  if (int rc = secant_rounds(p, nc, chunk, v, device, st, &r)) return rc;
+  if (v.a.has_state)
+    if (int rc = state_tail(p, nc, chunk, v, r, st)) return rc;
+  return v.a.has_tangent ? tangent_tail(p, nc, chunk, v, r, st) : HOMMX_OK;
+}
+
+// the checks of a history struct, then of hommx_secant_args, against the plan's descriptor: the program of a call with a history has
+// n_history more components on a row as much longer
+int secant_checks(const hommx_plan* p, const SecantRequest& r) {
+  const hommx_secant_args* a = r.secant;
   int n_history = 0;
-  if (hist) {
-    const hommx_history_args* h = *hist;
+  if (r.hist || (r.need & NEED_HISTORY)) {
+    const hommx_history_args* h = r.hist;
     if (!h) return fail(HOMMX_EINVAL, "null history arguments");
     if (h->n_history < 1 || h->n_history > HOMMX_SECANT_MAX_HISTORY)
       return fail(HOMMX_EINVAL, "n_history must be 1 .. %d, got %d", HOMMX_SECANT_MAX_HISTORY, h->n_history);
@@ -1890,7 +1955,7 @@ int secant_checks(const hommx_plan* p, const hommx_secant_args* a, const hommx_h
   return HOMMX_OK;
 }
 
-// the load of the entries that take one (hommx_secant_load_args), against the plan's descriptor
+// the load (hommx_secant_load_args) against the plan's descriptor
 int secant_load_checks(const hommx_plan* p, const hommx_secant_load_args* l) {
   if (!l) return fail(HOMMX_EINVAL, "null load arguments");
   if (int rc = load_code_check(p, 1, l->per_cell, l->P_source)) return rc;
@@ -1908,11 +1973,40 @@ int secant_load_routes(hommx_plan* p) {
   return GO;
 }
 
+// the tangent's own arguments against the descriptors of both plans alone (of a mesh plan, whose descriptor has no size, the element
+// and node counts as well); the iteration's have passed secant_checks
+int secant_tangent_checks(const hommx_plan* p, const hommx_secant_tangent_args* a) {
+  const hommx_secant_args& s = *a->secant;
+  const hommx::KindSizes ks = hommx::kind_sizes(p->desc.dim, p->desc.kind);
+  if (!a->tangent_plan || !a->tangent || !a->asymmetry) return fail(HOMMX_EINVAL, "null tangent_plan / tangent / asymmetry");
+  const hommx_plan* q = a->tangent_plan;
+  if (q == p) return fail(HOMMX_EINVAL, "tangent_plan is the plan itself: the tangent elimination needs a plan of its own");
+  const int want = hommx::tangent_kind(p->desc.kind);
+  if (q->desc.kind != want)
+    return fail(HOMMX_EINVAL, "tangent_plan has kind %d; the tangent kind of a plan of kind %d is %d", q->desc.kind, p->desc.kind, want);
+  if (q->desc.dim != p->desc.dim) return fail(HOMMX_EINVAL, "tangent_plan has dim %d; the plan has %d", q->desc.dim, p->desc.dim);
+  if (q->desc.n_micro != p->desc.n_micro)
+    return fail(HOMMX_EINVAL, "tangent_plan has n_micro %d; the plan has %d", q->desc.n_micro, p->desc.n_micro);
+  if (q->desc.device != p->desc.device)
+    return fail(HOMMX_EINVAL, "tangent_plan is on device %d; the plan on %d", q->desc.device, p->desc.device);
+  if (p->desc.n_micro == 0 && (q->n_el != p->n_el || plan_ndof(q) / q->ks.bs != plan_ndof(p) / p->ks.bs))
+    return fail(HOMMX_EINVAL, "tangent_plan is a plan of another mesh: %lld elements, the plan has %lld", (long long)q->n_el,
+                (long long)p->n_el);
+  const int lo = hommx::program_row_doubles(s.n_fields) + ks.t;
+  for (int pc = 0; pc < s.program->n_ops; ++pc) {
+    const int op = s.program->ops[2 * pc], k = s.program->ops[2 * pc + 1];
+    if (op == hommx::OP_X && k >= lo && k < lo + ks.t)
+      return fail(HOMMX_EINVAL, "the law reads s[%d] (instruction %d): the consistent tangent takes an explicit law, one that reads no "
+                                "s[k]; an implicit law is out of scope", k - lo, pc);
+  }
+  return HOMMX_OK;
+}
+
 // the tail of hommx_secant_state_source against the plan's descriptor: the criterion as crit_open checks
-// one, on the row of a state criterion; the reconstruction as recon_open checks its regions.  `a`, `src`, `hist` and `load` have passed
-// their own checks
-int secant_state_checks(const hommx_plan* p, const hommx_coef_source* src, const hommx_secant_args* a, const hommx_history_args* hist,
-                        const hommx_secant_load_args* load, const hommx_secant_state_args* s) {
+// one, on the row of a state criterion; the reconstruction as recon_open checks its regions.  The other parts of the request have
+// passed their own checks
+int secant_state_checks(const hommx_plan* p, const hommx_coef_source* src, const SecantRequest& r) {
+  const hommx_secant_state_args* s = r.state;
   if (!s) return fail(HOMMX_EINVAL, "null state arguments");
   if (!s->crit_program && !s->reconstruct) return fail(HOMMX_EINVAL, "nothing requested: neither a criterion nor the reconstruction");
   const hommx::KindSizes ks = hommx::kind_sizes(p->desc.dim, p->desc.kind);
@@ -1923,15 +2017,15 @@ int secant_state_checks(const hommx_plan* p, const hommx_coef_source* src, const
     own.n_fields = s->crit_n_fields;
     own.program = s->crit_program;
     // without a history struct the row ends behind the two coefficient segments: an h index of the criterion is out of range
-    if (int rc = program_check(p, &own, 0, 2 * ks.t + 2 * ks.n_comp + (hist ? hist->n_history : 0))) return rc;
-    if (!a->points)
+    if (int rc = program_check(p, &own, 0, 2 * ks.t + 2 * ks.n_comp + (r.hist ? r.hist->n_history : 0))) return rc;
+    if (!r.secant->points)
       for (int pc = 0; pc < s->crit_program->n_ops; ++pc)
         if (s->crit_program->ops[2 * pc] == hommx::OP_Y)
           return fail(HOMMX_EINVAL, "null points: the criterion reads y (instruction %d), the centroid of the element", pc);
     if (s->threshold != s->threshold) return fail(HOMMX_EINVAL, "the threshold is NaN");
   }
   if (s->reconstruct) {
-    if (load)
+    if (r.load)
       return fail(HOMMX_EINVAL, "reconstruct together with a load: the reconstruction statistics have no load term (ask for the criterion's "
                                 "total_strain / total_flux)");
     if (!s->stats) return fail(HOMMX_EINVAL, "null stats");
@@ -1940,74 +2034,64 @@ int secant_state_checks(const hommx_plan* p, const hommx_coef_source* src, const
   return HOMMX_OK;
 }
 
-// the argument checks of both entry points, then a route that forms correctors; load: the call is one of the load entries, whose
-// struct *load is checked behind the iteration's and which needs a load solve as well; state: the call is hommx_secant_state_source,
-// whose history and load are optional (null pointers behind hist / load) and whose struct *state is checked last
-int secant_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_args* a, bool device,
-                const hommx_history_args* const* hist = nullptr, const hommx_secant_load_args* const* load = nullptr,
-                const hommx_secant_state_args* const* state = nullptr) {
+// the argument checks of every entry, in this order: the source, the entry's struct, of a tangent entry the iteration's struct behind
+// it, the history, the iteration, the load, the tangent's own or the state's; then a route that forms correctors and, with a load, a
+// load solve
+int secant_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const SecantRequest& r, bool device) {
   auto checks = [&] {
-    if (int rc = secant_checks(p, a, hist)) return rc;
-    if (load)
-      if (int rc = secant_load_checks(p, *load)) return rc;
-    return state ? secant_state_checks(p, src, a, hist ? *hist : nullptr, load ? *load : nullptr, *state) : HOMMX_OK;
+    if (!r.secant) return fail(HOMMX_EINVAL, "null secant arguments");  // a tangent entry's; a null `given` is source_open's
+    if (int rc = secant_checks(p, r)) return rc;
+    if (r.load || (r.need & NEED_LOAD))
+      if (int rc = secant_load_checks(p, r.load)) return rc;
+    if (r.tangent)
+      if (int rc = secant_tangent_checks(p, r.tangent)) return rc;
+    return r.state || (r.need & NEED_STATE) ? secant_state_checks(p, src, r) : HOMMX_OK;
   };
-  if (int rc = source_open(p, n_cells, src, a, device, checks); rc != GO) return rc;
-  return load ? secant_load_routes(p) : GO;
+  if (int rc = source_open(p, n_cells, src, r.given, device, checks); rc != GO) return rc;
+  return r.load ? secant_load_routes(p) : GO;
 }
 
-// the arguments of a call as the chunk driver re-bases them: the iteration's, the history's (n_history 0, null pointers: none) and
-// the load's (has_load false: none)
-struct SecantCall {
-  hommx_secant_args s;
-  hommx_history_args h;
-  bool has_load;
-  SecantLoad l;
-  bool has_state;
-  hommx_secant_state_args t;  // the tail of hommx_secant_state_source (has_state false: none, every pointer null)
-};
-
-// what secant_call and secant_tangent_call hold of a load: the program source of its own beside the coefficient's, and the bytes per
-// cell a chunk holds of it beside the caller's array -- the second corrector block, the expansion of a program, the eigenstress
+// what a call holds of a load: the program source of its own beside the coefficient's, and the bytes per cell a chunk holds of it
+// beside the caller's array -- the second corrector block, the expansion of a program, the eigenstress
 struct SecantLoadPlan {
   bool program = false;
   ProgramLoad prog{};
   size_t scratch = 0;
-  int64_t field = 0;  // doubles per cell of the load array (0: no load)
 };
-SecantLoadPlan secant_load_plan(const hommx_plan* p, const hommx_secant_load_args* load, SecantLoad* l, bool* has_load) {
+SecantLoadPlan secant_load_plan(const hommx_plan* p, const hommx_secant_load_args* load, hommx_secant_load_args* l) {
   SecantLoadPlan q;
-  *has_load = load != nullptr;
-  *l = SecantLoad{0, nullptr};
   if (!load) return q;
+  const int64_t field = p->n_el * p->ks.t;
   q.program = load_form(load->per_cell) == HOMMX_LOADS_PROGRAM;
-  *l = SecantLoad{load->per_cell, q.program ? nullptr : load->P};
-  q.field = p->n_el * p->ks.t;
+  *l = *load;
   if (q.program) {
+    l->P = nullptr;
     const hommx_coef_source& s = *load->P_source;
     q.prog = {program_source(s.program, s.n_q, s.table, s.weights, s.params, s.n_fields), &l->P};
   }
-  q.scratch = sizeof(double) * (plan_ndof(p) * p->ks.t + (q.program ? q.field : 0) + (load_eigenstrain(load->per_cell) ? q.field : 0));
+  q.scratch = sizeof(double) * (plan_ndof(p) * p->ks.t + (q.program ? field : 0) + (load_eigenstrain(load->per_cell) ? field : 0));
   return q;
 }
 
-// The current and the candidate stream of a chunk, the info of its eliminations and the slot of a field that does not fit LDS beside the
-// stack (where the chunk rule of the reconstruction does not count one already) are scratch of the chunk
-// hist: history_in is a per-cell input and history_out a per-cell output of the chunk, counted as coef_start and coef_out are
-// load: with it a chunk holds a second corrector block per cell and ends every round in a load solve (load_chunk), and the load array
-// is a per-cell input of the chunk (a program: its expansion, ProgramLoad)
-// state: the per-cell outputs of the tail and the rows of its criterion are per-cell arrays of the chunk; the labels of a host call
-// travel once, into B_REGION.  The tail holds no scratch beside the round's: the field slot and the corrector blocks are the round's
-int secant_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_secant_args& args, bool device,
-                hipStream_t st, const hommx_history_args* hist = nullptr, const hommx_secant_load_args* load = nullptr,
-                const hommx_secant_state_args* state = nullptr) {
-  const int64_t t = p->ks.t, field = p->n_el * t, stream = p->n_el * p->ks.n_comp;
+// The chunk loop of a request that has passed secant_open.  Scratch of a chunk: the current and the candidate stream, the info of its
+// eliminations, the slot of a field that does not fit LDS beside the stack (where the chunk rule of the reconstruction does not count
+// one already), the tangent stream the caller does not take, and what secant_load_plan counts of a load -- with one the rule is
+// load_chunk, since every round ends in a load solve.  Per-cell arrays of the chunk: coef_start / coef_out, history_in / history_out,
+// the load array (a program: its expansion, ProgramLoad), the rows of the state's criterion and every output; an absent part's arrays
+// are null and take no room.  The labels of a host call travel once, into B_REGION
+int secant_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const SecantRequest& r, bool device,
+                hipStream_t st) {
+  const int64_t t = p->ks.t, field = p->n_el * t, stream = p->n_el * p->ks.n_comp, tan = tangent_stream_doubles(p);
   Chunk<SecantCall> v{};
-  v.a = SecantCall{args, hist ? *hist : hommx_history_args{}, false, {}, state != nullptr, state ? *state : hommx_secant_state_args{}};
-  hommx_secant_args& a = v.a.s;
+  hommx_secant_args& a = v.a.s = *r.secant;
   hommx_history_args& h = v.a.h;
   hommx_secant_state_args& ta = v.a.t;
-  if (state) {  // what the checks have passed: members that belong to the half not asked for are not read
+  hommx_secant_tangent_args& g = v.a.g;
+  if (r.hist) h = *r.hist;
+  if (r.tangent) v.a.has_tangent = true, g = *r.tangent;
+  if (r.state) {  // what the checks have passed: members that belong to the half not asked for are not read
+    v.a.has_state = true;
+    ta = *r.state;
     if (!ta.crit_program) ta.crit_rows = nullptr, ta.crit = ta.crit_values = ta.total_strain = ta.total_flux = nullptr, ta.crit_n_fields = 0;
     if (!ta.reconstruct) ta.n_regions = 0, ta.region = nullptr, ta.stats = ta.region_stats = nullptr;
     if (ta.n_regions && !ta.region) ta.region = s.mask;  // n_regions == 2 of a two-phase source: the mask may be the labels
@@ -2017,14 +2101,16 @@ int secant_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, cons
       ta.region = static_cast<const uint8_t*>(p->buf[B_REGION].p);
     }
   }
-  SecantLoadPlan lp = secant_load_plan(p, load, &v.a.l, &v.a.has_load);
-  const bool own_slot = !(crit_in_lds(p, program_depth(*a.program)) && state_in_lds(p, state)) && recon_in_lds(p);
-  const size_t scratch = sizeof(double) * (2 * stream + (own_slot ? plan_ndof(p) : 0)) + sizeof(int32_t) + lp.scratch;
+  v.a.has_load = r.load != nullptr;
+  SecantLoadPlan lp = secant_load_plan(p, r.load, &v.a.l);
+  const bool own_slot = secant_slot_used(p, v.a) && recon_in_lds(p);
+  const size_t scratch = sizeof(double) * (2 * stream + (own_slot ? plan_ndof(p) : 0) + (v.a.has_tangent && !g.tangent_coef ? tan : 0)) +
+                         sizeof(int32_t) + lp.scratch;
   const CellArray in[] = {{&a.rows, hommx::program_row_doubles(a.n_fields)},
                           {&a.xi, t},
                           {&a.coef_start, stream},
                           {&h.history_in, p->n_el * h.n_history},
-                          {&v.a.l.P, lp.field},
+                          {&v.a.l.P, r.load ? field : 0},
                           {&ta.crit_rows, hommx::program_row_doubles(ta.crit_n_fields)},
                           {&a.points, p->n_el * p->desc.dim, SHARED}};
   const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE},
@@ -2034,6 +2120,10 @@ int secant_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, cons
                            {&a.strain, field},
                            {&a.flux, field},
                            {&a.law_values, stream},
+                           {&g.tangent, t * t},
+                           {&g.asymmetry, 1},
+                           {&g.tangent_coef, tan},
+                           {&g.tangent_info, 1, PER_CELL, sizeof(int32_t)},
                            {&h.history_out, p->n_el * h.n_history},
                            {&ta.crit, HOMMX_CRIT_NSTATS},
                            {&ta.crit_values, p->n_el},
@@ -2041,96 +2131,18 @@ int secant_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, cons
                            {&ta.total_flux, field},
                            {&ta.stats, HOMMX_RECON_NSTATS(t)},
                            {&ta.region_stats, ta.n_regions * HOMMX_RECON_NREGION(t)}};
-  return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, load ? load_chunk : recon_chunk, device, st,
-                      [&](int64_t nc, int64_t chunk, const Chunk<SecantCall>& c) {
-                        return secant_run(p, nc, chunk, c.coef, c.M, c.a.s, device, st, nullptr, c.a.h.n_history ? &c.a.h : nullptr,
-                                          c.a.has_load ? &c.a.l : nullptr, c.a.has_state ? &c.a.t : nullptr);
-                      },
+  return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, r.load ? load_chunk : recon_chunk, device, st,
+                      [&](int64_t nc, int64_t chunk, const Chunk<SecantCall>& c) { return secant_run(p, nc, chunk, c, device, st); },
                       nullptr, false, lp.program ? &lp.prog : nullptr);
 }
 
-// -- the consistent tangent of the secant response (hommx_secant_tangent_source[_device]) -------------------------------------------------
-// the arguments of a call as the chunk driver re-bases them: the iteration's and the tangent's, flat
-struct SecantTangentCall {
-  hommx_secant_args s;
-  hommx_plan* plan;
-  double *tangent, *asymmetry, *coef;
-  int32_t* info;
-  hommx_history_args h;  // n_history 0, null pointers: none
-  bool has_load;         // false: none
-  SecantLoad l;
-};
-
-// everything secant_open checks, then the tangent's own arguments against the descriptors of both plans alone (of a mesh plan, whose
-// descriptor has no size, the element and node counts as well)
-int secant_tangent_open(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const hommx_secant_tangent_args* a, bool device,
-                        const hommx_history_args* const* hist = nullptr, const hommx_secant_load_args* const* load = nullptr) {
-  auto checks = [&] {
-    if (!a->secant) return fail(HOMMX_EINVAL, "null secant arguments");
-    if (int rc = secant_checks(p, a->secant, hist)) return rc;
-    if (load)
-      if (int rc = secant_load_checks(p, *load)) return rc;
-    const hommx_secant_args& s = *a->secant;
-    const hommx::KindSizes ks = hommx::kind_sizes(p->desc.dim, p->desc.kind);
-    if (!a->tangent_plan || !a->tangent || !a->asymmetry) return fail(HOMMX_EINVAL, "null tangent_plan / tangent / asymmetry");
-    const hommx_plan* q = a->tangent_plan;
-    if (q == p) return fail(HOMMX_EINVAL, "tangent_plan is the plan itself: the tangent elimination needs a plan of its own");
-    const int want = hommx::tangent_kind(p->desc.kind);
-    if (q->desc.kind != want)
-      return fail(HOMMX_EINVAL, "tangent_plan has kind %d; the tangent kind of a plan of kind %d is %d", q->desc.kind, p->desc.kind, want);
-    if (q->desc.dim != p->desc.dim) return fail(HOMMX_EINVAL, "tangent_plan has dim %d; the plan has %d", q->desc.dim, p->desc.dim);
-    if (q->desc.n_micro != p->desc.n_micro)
-      return fail(HOMMX_EINVAL, "tangent_plan has n_micro %d; the plan has %d", q->desc.n_micro, p->desc.n_micro);
-    if (q->desc.device != p->desc.device)
-      return fail(HOMMX_EINVAL, "tangent_plan is on device %d; the plan on %d", q->desc.device, p->desc.device);
-    if (p->desc.n_micro == 0 && (q->n_el != p->n_el || plan_ndof(q) / q->ks.bs != plan_ndof(p) / p->ks.bs))
-      return fail(HOMMX_EINVAL, "tangent_plan is a plan of another mesh: %lld elements, the plan has %lld", (long long)q->n_el,
-                  (long long)p->n_el);
-    const int lo = hommx::program_row_doubles(s.n_fields) + ks.t;
-    for (int pc = 0; pc < s.program->n_ops; ++pc) {
-      const int op = s.program->ops[2 * pc], k = s.program->ops[2 * pc + 1];
-      if (op == hommx::OP_X && k >= lo && k < lo + ks.t)
-        return fail(HOMMX_EINVAL, "the law reads s[%d] (instruction %d): the consistent tangent takes an explicit law, one that reads no "
-                                  "s[k]; an implicit law is out of scope", k - lo, pc);
-    }
-    return HOMMX_OK;
-  };
-  if (int rc = source_open(p, n_cells, src, a, device, checks); rc != GO) return rc;
-  return load ? secant_load_routes(p) : GO;
+// what every entry of the family is: open the request, then run it
+int secant_entry(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const SecantRequest& r, bool device,
+                 void* stream = nullptr) {
+  if (int rc = secant_open(p, n_cells, src, r, device); rc != GO) return rc;
+  return secant_call(p, n_cells, source_of_form(*src), M, r, device, reinterpret_cast<hipStream_t>(stream));
 }
 
-int secant_tangent_call(hommx_plan* p, int64_t n_cells, const hommx_coef_source& s, const double* M, const hommx_secant_tangent_args& args,
-                        bool device, hipStream_t st, const hommx_history_args* hist = nullptr, const hommx_secant_load_args* load = nullptr) {
-  const int64_t t = p->ks.t, field = p->n_el * t, stream = p->n_el * p->ks.n_comp, tan = tangent_stream_doubles(p);
-  Chunk<SecantTangentCall> v{};
-  v.a = SecantTangentCall{*args.secant,      args.tangent_plan, args.tangent, args.asymmetry, args.tangent_coef,
-                          args.tangent_info, hist ? *hist : hommx_history_args{}, false, {}};
-  hommx_secant_args& a = v.a.s;
-  hommx_history_args& h = v.a.h;
-  SecantLoadPlan lp = secant_load_plan(p, load, &v.a.l, &v.a.has_load);
-  const int depth = program_depth(*a.program);
-  const bool own_slot = (!crit_in_lds(p, depth) || !tangent_in_lds(p, depth)) && recon_in_lds(p);
-  const size_t scratch =
-      sizeof(double) * (2 * stream + (own_slot ? plan_ndof(p) : 0) + (args.tangent_coef ? 0 : tan)) + sizeof(int32_t) + lp.scratch;
-  const CellArray in[] = {{&a.rows, hommx::program_row_doubles(a.n_fields)},
-                          {&a.xi, t},
-                          {&a.coef_start, stream},
-                          {&h.history_in, p->n_el * h.n_history},
-                          {&v.a.l.P, lp.field},
-                          {&a.points, p->n_el * p->desc.dim, SHARED}};
-  const CellArray out[] = {{&a.state, HOMMX_SECANT_NSTATE}, {&a.A_eff, t * t, KEPT}, {&a.mean_flux, t},
-                           {&a.coef_out, stream},           {&a.strain, field},      {&a.flux, field},
-                           {&a.law_values, stream},         {&v.a.tangent, t * t},   {&v.a.asymmetry, 1},
-                           {&v.a.coef, tan},                {&v.a.info, 1, PER_CELL, sizeof(int32_t)},
-                           {&h.history_out, p->n_el * h.n_history}};
-  return derived_call(p, n_cells, s, M, v, in, out, &a.info, scratch, load ? load_chunk : recon_chunk, device, st,
-                      [&](int64_t nc, int64_t chunk, const Chunk<SecantTangentCall>& c) {
-                        const TangentTail tail{c.a.plan, c.a.tangent, c.a.asymmetry, c.a.coef, c.a.info};
-                        return secant_run(p, nc, chunk, c.coef, c.M, c.a.s, device, st, &tail, c.a.h.n_history ? &c.a.h : nullptr,
-                                          c.a.has_load ? &c.a.l : nullptr);
-                      },
-                      nullptr, false, lp.program ? &lp.prog : nullptr);
-}
 
 // -- second derivatives (hommx_second_sensitivity_source[_device]) ------------------------------------------------------------------------
 // bytes per cell of a chunk beside the canonical correctors: the second corrector block and the loads of one direction
@@ -2294,90 +2306,77 @@ int hommx_criterion_source(hommx_plan* p, int64_t n_cells, const hommx_coef_sour
 
 int hommx_secant_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M, const hommx_secant_args* args,
                                void* stream) {
-  if (int rc = secant_open(p, n_cells, src, args, true); rc != GO) return rc;
-  return secant_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream));
+  return secant_entry(p, n_cells, src, d_M, secant_request(args), true, stream);
 }
 
 int hommx_secant_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_secant_args* args) {
-  if (int rc = secant_open(p, n_cells, src, args, false); rc != GO) return rc;
-  return secant_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
+  return secant_entry(p, n_cells, src, M, secant_request(args), false);
 }
 
 int hommx_secant_tangent_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                                        const hommx_secant_tangent_args* args, void* stream) {
-  if (int rc = secant_tangent_open(p, n_cells, src, args, true); rc != GO) return rc;
-  return secant_tangent_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream));
+  return secant_entry(p, n_cells, src, d_M, secant_request(args), true, stream);
 }
 
 int hommx_secant_tangent_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M,
                                 const hommx_secant_tangent_args* args) {
-  if (int rc = secant_tangent_open(p, n_cells, src, args, false); rc != GO) return rc;
-  return secant_tangent_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr);
+  return secant_entry(p, n_cells, src, M, secant_request(args), false);
 }
 
 int hommx_secant_history_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                                        const hommx_secant_args* args, const hommx_history_args* history, void* stream) {
-  if (int rc = secant_open(p, n_cells, src, args, true, &history); rc != GO) return rc;
-  return secant_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream), history);
+  return secant_entry(p, n_cells, src, d_M, secant_request(args, NEED_HISTORY, history), true, stream);
 }
 
 int hommx_secant_history_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_secant_args* args,
                                 const hommx_history_args* history) {
-  if (int rc = secant_open(p, n_cells, src, args, false, &history); rc != GO) return rc;
-  return secant_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr, history);
+  return secant_entry(p, n_cells, src, M, secant_request(args, NEED_HISTORY, history), false);
 }
 
 int hommx_secant_tangent_history_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                                                const hommx_secant_tangent_args* args, const hommx_history_args* history, void* stream) {
-  if (int rc = secant_tangent_open(p, n_cells, src, args, true, &history); rc != GO) return rc;
-  return secant_tangent_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream), history);
+  return secant_entry(p, n_cells, src, d_M, secant_request(args, NEED_HISTORY, history), true, stream);
 }
 
 int hommx_secant_tangent_history_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M,
                                         const hommx_secant_tangent_args* args, const hommx_history_args* history) {
-  if (int rc = secant_tangent_open(p, n_cells, src, args, false, &history); rc != GO) return rc;
-  return secant_tangent_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr, history);
+  return secant_entry(p, n_cells, src, M, secant_request(args, NEED_HISTORY, history), false);
 }
 
 int hommx_secant_load_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                                     const hommx_secant_args* args, const hommx_history_args* history, const hommx_secant_load_args* load,
                                     void* stream) {
-  if (int rc = secant_open(p, n_cells, src, args, true, history ? &history : nullptr, &load); rc != GO) return rc;
-  return secant_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream), history, load);
+  return secant_entry(p, n_cells, src, d_M, secant_request(args, NEED_LOAD, history, load), true, stream);
 }
 
 int hommx_secant_load_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_secant_args* args,
                              const hommx_history_args* history, const hommx_secant_load_args* load) {
-  if (int rc = secant_open(p, n_cells, src, args, false, history ? &history : nullptr, &load); rc != GO) return rc;
-  return secant_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr, history, load);
+  return secant_entry(p, n_cells, src, M, secant_request(args, NEED_LOAD, history, load), false);
 }
 
 int hommx_secant_state_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                                      const hommx_secant_args* args, const hommx_history_args* history, const hommx_secant_load_args* load,
                                      const hommx_secant_state_args* state, void* stream) {
-  if (int rc = secant_open(p, n_cells, src, args, true, history ? &history : nullptr, load ? &load : nullptr, &state); rc != GO) return rc;
-  return secant_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream), history, load, state);
+  return secant_entry(p, n_cells, src, d_M, secant_request(args, NEED_STATE, history, load, state), true, stream);
 }
 
 int hommx_secant_state_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M, const hommx_secant_args* args,
                               const hommx_history_args* history, const hommx_secant_load_args* load, const hommx_secant_state_args* state) {
-  if (int rc = secant_open(p, n_cells, src, args, false, history ? &history : nullptr, load ? &load : nullptr, &state); rc != GO) return rc;
-  return secant_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr, history, load, state);
+  return secant_entry(p, n_cells, src, M, secant_request(args, NEED_STATE, history, load, state), false);
 }
 
 int hommx_secant_tangent_load_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                                             const hommx_secant_tangent_args* args, const hommx_history_args* history,
                                             const hommx_secant_load_args* load, void* stream) {
-  if (int rc = secant_tangent_open(p, n_cells, src, args, true, history ? &history : nullptr, &load); rc != GO) return rc;
-  return secant_tangent_call(p, n_cells, source_of_form(*src), d_M, *args, true, reinterpret_cast<hipStream_t>(stream), history, load);
+  return secant_entry(p, n_cells, src, d_M, secant_request(args, NEED_LOAD, history, load), true, stream);
 }
 
 int hommx_secant_tangent_load_source(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* M,
                                      const hommx_secant_tangent_args* args, const hommx_history_args* history,
                                      const hommx_secant_load_args* load) {
-  if (int rc = secant_tangent_open(p, n_cells, src, args, false, history ? &history : nullptr, &load); rc != GO) return rc;
-  return secant_tangent_call(p, n_cells, source_of_form(*src), M, *args, false, nullptr, history, load);
+  return secant_entry(p, n_cells, src, M, secant_request(args, NEED_LOAD, history, load), false);
 }
+
 
 int hommx_second_sensitivity_source_device(hommx_plan* p, int64_t n_cells, const hommx_coef_source* src, const double* d_M,
                                            const hommx_sens2_args* args, void* stream) {

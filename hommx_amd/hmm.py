@@ -1091,6 +1091,39 @@ class BaseHMM(ABC):
             return region_labels(np.asarray(self._coeff.indicator(mid), dtype=bool), mid.shape[1], 2)
         return region_labels(regions(mid) if callable(regions) else regions, mid.shape[1])
 
+    def _secant_chunks(self, cells: np.ndarray, xi: np.ndarray, law: SecantLaw, rows: np.ndarray, points: np.ndarray, chunk_cells,
+                       history: np.ndarray | None, load: bool, extra: int, kw, tangent: bool = False) -> SecantResult:
+        """``plan.secant`` of ``law`` on ``cells``, chunk by chunk -> the joined ``SecantResult`` with ``cells``; ``tangent``:
+        ``plan.secant_tangent`` on the sibling plan instead.  ``xi``, ``rows`` and ``history`` (None: a law without history variables)
+        lie along ``cells`` and are sliced per chunk; ``kw(b, n)``: the other keyword arguments of the n cells from position b.
+        ``load``: the solver's polarisation or eigenstrain, sampled chunk by chunk.  A chunk streams the iteration's own outputs, a
+        sampled load, the history in and out, a sampled coefficient, and ``extra`` bytes per cell for what the caller adds."""
+        t, n_el = self._tensor_size(), self._cell_mesh.num_cells
+
+        def bytes_per_cell():
+            out = 8 * (3 + t * t + t) + 4 + extra
+            if load and not isinstance(self._polarisation, Expression):
+                out += 8 * n_el * t  # a sampled load
+            if history is not None:  # in and out
+                out += 16 * n_el * history.shape[2]
+            return out if self._sampled_on_device() else out + n_el * (1 if self._kind == "poisson" else 2) * 8
+
+        def sample(sub, kind):  # (P, per_cell, eigenstrain) as plan.secant takes them
+            return self._load_input(sub, self._loads_on_device(kind)) + (self._eigenstrain,)
+
+        def call(plan, coef, M, P, sub, b):
+            at = slice(b, b + len(sub))
+            args = dict(rows=rows[at], points=points, **kw(b, len(sub)))
+            if P is not None:
+                args.update(P=P[0], per_cell=P[1], eigenstrain=P[2])
+            if history is not None:
+                args["history"] = history[at]
+            if not tangent:
+                return plan.secant(coef, xi[at], law, M, **args)
+            return plan.secant_tangent(coef, xi[at], law, self._ensure_tangent_plan(plan), M, **args)
+
+        return _join(self._chunks(cells, chunk_cells, bytes_per_cell, call, sample if load else None), cells=cells)
+
     def _nonlinear_tail(self, method: str, u, cells, chunk_cells, tail_bytes: int, tail) -> SecantResult:
         """The micro iteration of ``cells`` at ``u`` with what the last ``solve_nonlinear`` kept -- its law, limits, rows, load and the
         history it started from -- and ``tail(b, n)``, the tail arguments of ``plan.secant`` for the n cells from position b, chunk by
@@ -1114,31 +1147,10 @@ class BaseHMM(ABC):
         xi = self._macro_strains(cells, x)
         rows = st["rows"][cells]
         points = np.ascontiguousarray(self._cell_mesh.cell_midpoints()[:, : self._tdim])
-        t, n_el = self._tensor_size(), self._cell_mesh.num_cells
-
-        def bytes_per_cell():
-            out = 8 * (3 + t * t + t) + 4 + tail_bytes
-            if st["load"] and not isinstance(self._polarisation, Expression):
-                out += 8 * n_el * t  # a sampled load
-            if history is not None:  # in and out
-                out += 16 * n_el * history.shape[2]
-            return out if self._sampled_on_device() else out + n_el * (1 if self._kind == "poisson" else 2) * 8
-
-        def sample(sub, kind):  # (P, per_cell, eigenstrain) as plan.secant takes them
-            return self._load_input(sub, self._loads_on_device(kind)) + (self._eigenstrain,)
-
-        def call(plan, coef, M, P, sub, b):
-            args = dict(rows=rows[b:b + len(sub)], points=points, max_iter=st["micro_iter"], tol=st["micro_tol"], relax=st["relax"],
-                        **tail(b, len(sub)))
-            if P is not None:
-                args.update(P=P[0], per_cell=P[1], eigenstrain=P[2])
-            if history is not None:
-                args["history"] = history[b:b + len(sub)]
-            return plan.secant(coef, xi[b:b + len(sub)], law, M, **args)
-
         if st["load"] and self._polarisation is None:
             raise RuntimeError(f"{method}(nonlinear=True): solve_nonlinear ran with load=True and the load has been cleared since: set it again")
-        r = _join(self._chunks(cells, chunk_cells, bytes_per_cell, call, sample if st["load"] else None), cells=cells)
+        limits = dict(max_iter=st["micro_iter"], tol=st["micro_tol"], relax=st["relax"])
+        r = self._secant_chunks(cells, xi, law, rows, points, chunk_cells, history, st["load"], tail_bytes, lambda b, n: dict(limits, **tail(b, n)))
         counts = {int(k): int((r.status == k).sum()) for k in np.unique(r.status)}
         if any(k != 0 for k in counts):
             self._logger.warning("%s(nonlinear=True): not every micro iteration converged; micro cells by status: %s", method,
@@ -1329,29 +1341,9 @@ class BaseHMM(ABC):
         current stream of every round."""
         t = self._tensor_size()
 
-        def bytes_per_cell():
-            out = 8 * (3 + t * t + t + (t * t + 1 if tangent else 0)) + 4
-            if load and not isinstance(self._polarisation, Expression):
-                out += 8 * self._cell_mesh.num_cells * t  # a sampled load
-            if history is not None:  # in and out
-                out += 16 * self._cell_mesh.num_cells * history.shape[2]
-            return out if self._sampled_on_device() else out + self._cell_mesh.num_cells * (1 if self._kind == "poisson" else 2) * 8
-
-        def sample(sub, kind):  # (P, per_cell, eigenstrain) as plan.secant takes them
-            return self._load_input(sub, self._loads_on_device(kind)) + (self._eigenstrain,)
-
         def local(b, e):
-            def call(plan, coef, M, P, sub, at):
-                args = dict(rows=rows[b + at:b + at + len(sub)], points=points, **kw)
-                if P is not None:
-                    args.update(P=P[0], per_cell=P[1], eigenstrain=P[2])
-                if history is not None:
-                    args["history"] = history[at:at + len(sub)]
-                if not tangent:
-                    return plan.secant(coef, xi[b + at:b + at + len(sub)], law, M, **args)
-                return plan.secant_tangent(coef, xi[b + at:b + at + len(sub)], law, self._ensure_tangent_plan(plan), M, **args)
-
-            r = _join(self._chunks(cells[b:e], chunk_cells, bytes_per_cell, call, sample if load else None), cells=cells[b:e])
+            r = self._secant_chunks(cells[b:e], xi[b:e], law, rows[b:e], points, chunk_cells, history, load, 8 * (t * t + 1) if tangent else 0,
+                                    lambda at, n: kw, tangent)
             if history is not None:
                 self.history_trial = r.history
             return r

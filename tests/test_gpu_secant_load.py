@@ -396,3 +396,84 @@ def test_elasticity_hmm_with_a_thermal_expression_solves_its_own_secant_system()
     print(f"thermal elasticity: {len(h.nonlinear_history)} macro steps, |u - solve(secant tensors, effective polarisations)| = {dev:.3e}")
     assert dev <= 10 * tol
     assert np.abs(h.effective_polarisation).max() > 0.01  # the thermal strain loads the macro problem
+
+
+# -- j. the slot path: the field behind TWO corrector blocks, and under the tangent kernel ------------------------------------------------
+LOADS = [None, False, True]  # no load, a polarisation, an eigenstrain
+LOAD_IDS = ["none", "P", "E"]
+
+
+@functools.lru_cache(maxsize=None)
+def _large_cell():
+    """The cell of test_slot_path_and_lds_path_on_a_large_cell (test_gpu_secant.py) with its two laws and one seeded load: n = 112, so
+    that the field of 8 n n bytes = 98 KiB fits the 150 KiB of LDS beside the stack rows of the shallow law and not beside those of
+    the depth-16 law -- fifteen rows of 4096 bytes (512 threads) under the round kernel, fifteen of (1 + P) times that under the
+    tangent kernel."""
+    from hommx_amd import MicroCellPlan
+
+    from test_gpu_secant import _law
+
+    n = 112
+    p = MicroCellPlan(2, n, "poisson")
+    rng = np.random.default_rng(12)
+    d = {"coef": np.exp(rng.uniform(-1, 1, (1, p.n_el))), "xi": rng.standard_normal((1, 2)), "M": None,
+         "rows": rng.integers(-8, 9, (1, 4)) / 8.0, "points": rng.integers(0, 17, (p.n_el, 2)) / 16.0}
+    d["load"] = 0.3 * rng.standard_normal((1, p.n_el, p.t)) + 0.2 * rng.standard_normal((1, 1, p.t))
+    for a in d.values():
+        if a is not None:
+            a.setflags(write=False)
+    text = "e[0]**2"
+    for _ in range(13):
+        text = f"(1 + {text})"
+    deep, shallow = _law([f"c[0]/{text}"]), _law(["c[0]/(1 + e[0]**2)"])
+    assert deep.depth == 16 and shallow.depth <= 4
+    return p, d, (("slot", deep), ("lds", shallow))
+
+
+@pytest.mark.parametrize("eigenstrain", CODES, ids=IDS)
+def test_slot_path_and_lds_path_beside_a_load_on_a_large_cell(eigenstrain):
+    """The rounds of k_secant_load with the field in global scratch: the slot lies behind the canonical corrector blocks AND the block
+    of the load's corrector.  The assertions are those of the unloaded test, on the strain and flux the law read."""
+    p, d, laws = _large_cell()
+    n = p.n_micro
+    assert 8 * n * n + 4096 * 15 > 150 * 1024 >= 8 * n * n + 4096 * 3  # the branch of the round kernel, as in the unloaded test
+    for name, law in laws:
+        r = _run(p, d, law, d["load"], eigenstrain, max_iter=2, tol=0.0, fields=True, values=True, return_coef=True)
+        assert not r.info.any() and r.rounds[0] == 2 and r.status[0] == 1
+        first = _run(p, d, law, d["load"], eigenstrain, max_iter=1, fields=True, values=True)
+        assert np.array_equal(first.values, law.host_values(first.strain, first.flux, d["coef"], d["rows"][:, :3])), name
+        assert np.array_equal(r.coef, first.values[..., 0]), name
+        assert np.array_equal(r.values, law.host_values(r.strain, r.flux, d["coef"], d["rows"][:, :3])), name
+        A = p.solve(r.coef)
+        assert np.abs(A - r.A_eff).max() <= 1e-12 * np.abs(A).max(), name
+
+
+@pytest.mark.parametrize("eigenstrain", LOADS, ids=LOAD_IDS)
+def test_tangent_tail_on_the_slot_path_and_the_lds_path_of_a_large_cell(eigenstrain):
+    """k_secant_tangent / k_secant_tangent_load with the field in global scratch, behind one corrector block set or two.  Which branch a
+    law takes follows from secant_tangent_lds_bytes = 8 (ndof + 512 (1 + P) (depth - 1)) against the 150 KiB limit, P from
+    secant_tangent_slots: t = 2 strain entries per sweep where the stack rows of that width fit the limit on their own, else 1."""
+    from hommx_amd import MicroCellPlan
+
+    p, d, laws = _large_cell()
+    n, row, limit = p.n_micro, 4096, 150 * 1024
+    assert 3 * row * 15 > limit >= 2 * row * 15  # depth 16: rows three doubles wide do not fit even without a field, so P = 1 ...
+    assert 8 * n * n + 2 * row * 15 > limit  # ... and beside those rows the field does not fit: the slot
+    assert 8 * n * n + 3 * row * 3 <= limit  # depth <= 4: P = 2 and the field in LDS
+    sib = MicroCellPlan(2, n, p.tangent_kind)
+    # the flux c e0 / (1 + e0^2) of the shallow law has a positive tangent for |e0| < 1 only, and the sibling plan eliminates a
+    # definite stream: a quarter of the seeded macro strain and load keeps every element there (tangent_info == 0 below says so)
+    xi, load = 0.25 * d["xi"], None if eigenstrain is None else 0.25 * d["load"]
+    for name, law in laws:
+        got = p.secant_tangent(d["coef"], xi, law, sib, None, rows=d["rows"][:, :3], points=d["points"], P=load,
+                               eigenstrain=bool(eigenstrain), max_iter=2, tol=0.0, fields=True, return_coef=True, return_tangent_coef=True)
+        assert not got.info.any() and got.rounds[0] == 2 and got.status[0] == 1, name
+        T, asym = law.host_tangent(got.strain, got.coef, d["coef"], d["rows"][:, :3], d["points"])
+        want = np.stack([TR.tangent_stream("poisson", 2, T[c]) for c in range(len(T))])
+        assert np.array_equal(got.tangent_coef, want) and np.array_equal(got.asymmetry, asym), name
+        D, info = sib.solve(got.tangent_coef, return_info=True)
+        assert np.array_equal(info, got.tangent_info) and not info.any(), name
+        dev = np.abs(D - got.tangent).max() / np.abs(D).max()
+        print(f"{name} {LOAD_IDS[LOADS.index(eigenstrain)]}: tangent against solve(tangent_coef): {dev:.3e}")
+        assert dev <= 1e-12, name
+    sib.close()
