@@ -1,6 +1,6 @@
 """GPU side of the accuracy and pivot-contract tests: runs the case groups of tests/accuracy_ref.py through the plans and returns raw
 results.  Nothing here computes a bound.  Environment knobs are read when a plan is created, so the forced groups run this module as a
-child process:  python accuracy_gpu.py <accuracy|pivot|derived> <group> <out.npz>  (the derived outputs: the default group, and blocked_loads for the second load route of the fused plans)."""
+child process:  python accuracy_gpu.py <accuracy|pivot|derived|nonlinear> <group> <out.npz>  (the derived outputs: the default group, and blocked_loads for the second load route of the fused plans; nonlinear: the load cases of tests/nonlinear_truth.py, the same two groups)."""
 
 from __future__ import annotations
 
@@ -356,7 +356,96 @@ def run_pivot_sens2_group(group: str = "default") -> dict:
     return out
 
 
-RUNNERS = {"accuracy": run_accuracy_group, "pivot": run_pivot_group, "derived": run_derived_group, "pivot_sens2": run_pivot_sens2_group}
+def secant_law(law):
+    """The ``SecantLaw`` of the texts of a ``nonlinear_truth.Law``, in the shape the kind takes (for the device and the float64 references)."""
+    from hommx_amd.expr import SecantLaw
+
+    a, n = law.texts, len(law.texts)
+    kw = {} if law.history_texts is None else {"history": list(law.history_texts)}
+    if n == 1:
+        return SecantLaw(a[0], **kw)
+    if n == 2:
+        return SecantLaw(lam=a[0], mu=a[1], **kw)
+    if n == 3:
+        return SecantLaw([[a[0], a[2]], [a[2], a[1]]], **kw)
+    if n == 6 and law.kind == "poisson_matrix":
+        return SecantLaw([[a[0], a[3], a[4]], [a[3], a[1], a[5]], [a[4], a[5], a[2]]], **kw)
+    return SecantLaw(list(a), **kw)
+
+
+def criterion(crit):
+    """The ``Criterion`` of the text of a ``nonlinear_truth.Crit``."""
+    from hommx_amd.expr import Criterion
+
+    return Criterion(crit.text, threshold=crit.threshold, **({"history": 1} if crit.with_history else {}))
+
+
+# the load route of every load shape of nonlinear_truth: one case per route (group 'blocked_loads': the fused plan on the blocked one)
+NONLINEAR_LOAD_ROUTES = {"p2": "fused2d_subst", "e3": "blocked", "mesh_ev3": "mesh_front_subst"}
+
+
+def nonlinear_plan(shape, n=None, load_solve=True):
+    """The plan of a shape of tests/nonlinear_truth.py (those of test_gpu_elem_walk_bits.py; ``n``: another size of the structured cell)."""
+    import nonlinear_truth as NT
+    from hommx_amd import MicroCellPlan
+
+    dim, kind, n0 = NT.SHAPES[shape]
+    if n or n0:
+        return MicroCellPlan(dim, n or n0, kind)
+    return MicroCellPlan.from_mesh(R.mesh_of(*NT.MESHES[dim]), kind, route="front", load_solve=load_solve)
+
+
+def nonlinear_sibling(shape, p):
+    import nonlinear_truth as NT
+    from hommx_amd import MicroCellPlan
+
+    dim, _, n = NT.SHAPES[shape]
+    return MicroCellPlan(dim, n, p.tangent_kind) if n else MicroCellPlan.from_mesh(R.mesh_of(*NT.MESHES[dim]), p.tangent_kind, route="front")
+
+
+SECANT_OUTPUTS = {"coef": "coef", "A": "A_eff", "mean_flux": "mean_flux", "strain": "strain", "flux": "flux", "values": "values",
+                  "history": "history", "D": "tangent", "tangent_coef": "tangent_coef", "asymmetry": "asymmetry", "status": "status",
+                  "info": "info", "tangent_info": "tangent_info", "rounds": "rounds"}
+
+
+def secant_outputs(r) -> dict:
+    """Cell 0 of a SecantResult under the names of nonlinear_truth."""
+    return {k: np.asarray(getattr(r, a)[0]) for k, a in SECANT_OUTPUTS.items() if getattr(r, a) is not None}
+
+
+def run_nonlinear_group(group: str = "default") -> dict:
+    """The load cases of nonlinear_truth on the device: a potential law beside a polarisation and an eigenstrain, ``secant_tangent`` with
+    max_iter = the round count of the truth and tol = 0, one cell per call (keys nl|shape|cell|E|name).  group 'blocked_loads' (a child
+    process with HOMMX_FUSED_LOADS=0): the fused shape alone, its load route asserted."""
+    import nonlinear_truth as NT
+
+    out = {}
+    for shape in NT.LOAD_SHAPES:
+        p = nonlinear_plan(shape)
+        if group == "blocked_loads":
+            if p.kernel != "fused2d":
+                p.close()
+                continue
+            assert p.load_kernel == "blocked", p.load_kernel
+        else:
+            assert p.load_kernel == NONLINEAR_LOAD_ROUTES[shape], (shape, p.load_kernel)
+        sib = nonlinear_sibling(shape, p)
+        law = secant_law(NT.potential_law(p.kind, p.dim))
+        coef, M, xi = NT.inputs(shape, 0, NT.tangent_xi(shape))
+        load = NT.load_of(shape, 0)
+        for c in range(NT.cells_of(shape)):
+            for eig in (False, True):
+                rounds = NT.load_reference(shape, c, eig)[0]["rounds"]
+                r = p.secant_tangent(coef[c:c + 1], xi[c:c + 1], law, sib, None if M is None else M[c:c + 1], max_iter=rounds, tol=0.0,
+                                     fields=True, values=True, return_coef=True, return_tangent_coef=True, P=load[c:c + 1], eigenstrain=eig)
+                for name, v in secant_outputs(r).items():
+                    out[f"nl|{shape}|{c}|{int(eig)}|{name}"] = v
+        sib.close()
+        p.close()
+    return out
+
+
+RUNNERS = {"nonlinear": run_nonlinear_group, "accuracy": run_accuracy_group, "pivot": run_pivot_group, "derived": run_derived_group, "pivot_sens2": run_pivot_sens2_group}
 
 
 def run_in_child(what: str, group: str, tmp_path) -> dict:

@@ -57,8 +57,10 @@ def unit_strains(dim: int, dtype=LD) -> np.ndarray:
 
 
 def material_tensor(kind: str, coef: np.ndarray, dim: int, dtype=LD) -> np.ndarray:
-    """A[e, d, d] (Poisson kinds) or C[e, d, d, d, d] (elasticity kinds) in ``dtype`` from the float64 coefficient stream of the C ABI."""
-    coef = np.asarray(coef, dtype=np.float64).astype(dtype)
+    """A[e, d, d] (Poisson kinds) or C[e, d, d, d, d] (elasticity kinds) in ``dtype`` from the float64 coefficient stream of the C ABI.
+    A stream that is long double already keeps its digits: the iterates of tests/nonlinear_truth.py, which float64 cannot hold."""
+    coef = np.asarray(coef)
+    coef = coef.astype(dtype) if coef.dtype == LD else coef.astype(np.float64).astype(dtype)
     ne = coef.shape[0]
     I = np.eye(dim, dtype=dtype)
     if kind == "poisson":

@@ -12,6 +12,12 @@ tests/test_gpu_accuracy_derived.py against their own float64 yardsticks (accurac
 The derived outputs come from DIR/derived_default.npz (`python tests/accuracy_gpu.py derived default DIR/derived_default.npz`) and, for the
 second load route of the fused plans, DIR/derived_blocked_loads.npz (the same with `blocked_loads` and HOMMX_FUSED_LOADS=0).
 
+    python tools/accuracy_table.py --nonlinear [--out profiles/accuracy_nonlinear.json]
+
+--nonlinear: the nonlinear family instead (tests/test_gpu_accuracy_nonlinear.py against the long-double truth of tests/nonlinear_truth.py):
+every test of that file is run here as a function, and every comparison it makes -- case, quantity, e, the float64 yardstick, the bound and
+the ratio e / (bound / 32) -- is written per group (iteration, tangent, history, load, state, magnitude, slot) with the group's worst ratio.
+
 "second_derivatives": the ratio of d2A per (case, family, cell, load route) -- the largest over the cell's blocks, each block against its own
 yardstick (accuracy_ref.block_rel).
 """
@@ -35,11 +41,58 @@ DERIVED_GROUPS = {"tensor": ("A",), "fields": ("strain", "flux"), "statistics": 
                   "loads": tuple(q for q in R.LOAD_QUANTITIES if q != "load_chi"), "load correctors": ("load_chi",)}
 
 
+NONLINEAR_GROUPS = {"iteration": ("test_fourth_round", "test_fixed_point", "test_laminate_against_mpmath"), "tangent": ("test_tangent", "test_asymmetry_of_a_law_without_a_potential"),
+                    "history": ("test_history_over_three_load_steps", "test_tangent_at_frozen_history"),
+                    "load": ("test_loads_beside_a_law", "test_loads_of_the_fused_plan_on_the_blocked_route"), "state": ("test_state_tail",),
+                    "magnitude": ("test_magnitude",), "slot": ("test_slot_path_and_lds_path",)}
+
+
+def nonlinear(out):
+    """Runs the tests of tests/test_gpu_accuracy_nonlinear.py as functions, over their own parameters, and writes what they compared."""
+    import time
+
+    import nonlinear_truth as NT
+    import test_gpu_accuracy_nonlinear as N
+
+    class Tmp:
+        def mktemp(self, name):
+            return tempfile.mkdtemp(prefix=name)
+
+    loads = G.run_nonlinear_group()
+    params = {"test_fourth_round": NT.ITERATION_CASES, "test_fixed_point": NT.ITERATION_CASES, "test_laminate_against_mpmath": [()],
+              "test_tangent": NT.TANGENT_CASES,
+              "test_asymmetry_of_a_law_without_a_potential": [()], "test_history_over_three_load_steps": [(s,) for s in NT.HISTORY_SHAPES],
+              "test_tangent_at_frozen_history": [(s,) for s in NT.HISTORY_TANGENT_SHAPES], "test_loads_beside_a_law": [(loads, s) for s in NT.LOAD_SHAPES],
+              "test_loads_of_the_fused_plan_on_the_blocked_route": [(Tmp(),)], "test_state_tail": [(s,) for s in NT.STATE_CASES],
+              "test_magnitude": [(s,) for s in NT.MAGNITUDE_SHAPES], "test_slot_path_and_lds_path": [(None,), (True,)]}
+    groups, t0 = {}, time.perf_counter()
+    for group, tests in NONLINEAR_GROUPS.items():
+        first = len(N.Held.LOG)
+        for name in tests:
+            for a in params[name]:
+                getattr(N, name)(*a)
+        records = N.Held.LOG[first:]
+        worst = max(records, key=lambda r: r["worst_ratio"])
+        groups[group] = {"worst_ratio": worst["worst_ratio"], "worst_case": f"{worst['test']}: {worst['worst_at']}", "tests": records}
+    with open(out, "w") as f:
+        # three significant digits and one test per line: the record is a thousand comparisons
+        doc = {"bound_factor": R.FACTOR, "floor_eps": R.FLOOR_EPS, "wall_time_s": round(time.perf_counter() - t0, 1), "groups": groups}
+        text = json.dumps(json.loads(json.dumps(doc), parse_float=lambda v: float(f"{float(v):.3g}")), separators=(",", ":"))
+        f.write(text.replace('{"test":', '\n{"test":') + "\n")
+    print("| Group | worst ratio | at |\n|---|---|---|")
+    for group, g in groups.items():
+        print(f"| {group} | {g['worst_ratio']:.2f} | {g['worst_case']} |")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dumps")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "accuracy.json"))
+    ap.add_argument("--nonlinear", action="store_true")
+    ap.add_argument("--out")
     args = ap.parse_args()
+    if args.nonlinear:
+        return nonlinear(args.out or os.path.join(ROOT, "profiles", "accuracy_nonlinear.json"))
+    args.out = args.out or os.path.join(ROOT, "profiles", "accuracy.json")
 
     def results(group, tmp):
         if args.dumps:
