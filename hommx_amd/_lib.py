@@ -21,6 +21,7 @@ SAMPLER_RECIPROCAL = 1
 MESH_MAX_FRONT = 192  # HOMMX_MESH_MAX_FRONT
 MESH_FLAG_TREE = 1  # HOMMX_MESH_FLAG_TREE
 MESH_FLAG_LOADS = 2  # HOMMX_MESH_FLAG_LOADS
+FLAG_TREE_LOADS = 4  # HOMMX_FLAG_TREE_LOADS == HOMMX_MESH_FLAG_TREE_LOADS: load solves of a tree plan substitute on its kept fronts
 COEF_SAMPLED = 0  # HOMMX_COEF_*: the form of a hommx_coef_source
 COEF_TWO_PHASE = 1
 COEF_SEPARABLE = 2

@@ -432,18 +432,22 @@ class MicroCellPlan:
 
     load_sources = True  # loads() takes a program CoefStream as P and eigenstrain=True (what the solver classes ask a plan before they send either)
 
-    def __init__(self, dim: int, n_micro: int, kind: str = "poisson", device: int = 0, flags: int = 0):
+    def __init__(self, dim: int, n_micro: int, kind: str = "poisson", device: int = 0, flags: int = 0, tree_loads: bool = False):
+        """``tree_loads``: a plan of the nested-dissection route ("multifrontal") does the load solves of ``loads(response=True)``,
+        ``criterion``, ``secant`` with a load and ``second_sensitivities`` by substitution on the fronts its canonical pass has just left
+        (HOMMX_FLAG_TREE_LOADS; ``load_kernel`` is then "multifrontal_subst") instead of a second elimination.  Off by default; without
+        effect on every other route."""
         if kind not in KINDS:
             raise ValueError(f"unknown kind {kind!r}; expected one of {sorted(KINDS)}")
         self._lib = _lib.load()
-        desc = _lib.PlanDesc(int(dim), int(n_micro), KINDS[kind], int(device), int(flags))
+        desc = _lib.PlanDesc(int(dim), int(n_micro), KINDS[kind], int(device), int(flags) | (_lib.FLAG_TREE_LOADS if tree_loads else 0))
         h = C.c_void_p()
         _lib.check(self._lib.hommx_plan_create(C.byref(h), C.byref(desc)), "hommx_plan_create")
         self._adopt(h, int(dim), int(n_micro), kind, device, int(n_micro) ** int(dim), None)
 
     @classmethod
     def from_mesh(cls, msh, kind: str = "poisson", device: int = 0, order=None, constraint=None, route: str | None = None,
-                  load_solve: bool = False) -> "MicroCellPlan":
+                  load_solve: bool = False, tree_loads: bool = False) -> "MicroCellPlan":
         """Plan of the mesh route for ANY periodic simplicial mesh of the unit cell (include/hommx_hip.h, hommx_plan_create_mesh).
 
         The periodic nodes are those of ``create_periodic_boundary_conditions`` (or of ``constraint``, when given); ``to_periodic``
@@ -458,12 +462,17 @@ class MicroCellPlan:
         ``load_solve``: a plan of the frontal route gets a load solve (HOMMX_MESH_FLAG_LOADS; ``load_kernel`` is then
         "mesh_front_subst": substitution on the pivot columns of its corrector arena) and with it the response outputs of ``loads`` and
         ``second_sensitivities``; without it such a plan refuses them.  Meaningless on the tree route, which has a load solve of its own:
-        the flag is ignored there.  ``solve`` and the correctors do not depend on it."""
+        the flag is ignored there.  ``solve`` and the correctors do not depend on it.
+
+        ``tree_loads``: a plan of the tree route does its load solves by substitution on the fronts its canonical pass has just left
+        (HOMMX_MESH_FLAG_TREE_LOADS; ``load_kernel`` is then "mesh_multifrontal_subst") instead of a second elimination.  Off by
+        default; without effect on the frontal route."""
         if kind not in KINDS:
             raise ValueError(f"unknown kind {kind!r}; expected one of {sorted(KINDS)}")
         if route not in (None, "front", "tree"):
             raise ValueError(f"unknown route {route!r}; expected None, 'front' or 'tree'")
-        flags = (_lib.MESH_FLAG_TREE if route == "tree" else 0) | (_lib.MESH_FLAG_LOADS if load_solve else 0)
+        flags = ((_lib.MESH_FLAG_TREE if route == "tree" else 0) | (_lib.MESH_FLAG_LOADS if load_solve else 0)
+                 | (_lib.FLAG_TREE_LOADS if tree_loads else 0))
         desc, keep = mesh_desc(msh, kind, device, order, constraint, flags=flags)
         self = cls.__new__(cls)
         self._lib = _lib.load()

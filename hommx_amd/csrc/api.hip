@@ -203,6 +203,9 @@ bool fused_loads(const hommx_plan* p) { return fused_subst(p) && p->fused_loads;
 // a frontal mesh plan created with HOMMX_MESH_FLAG_LOADS: its load solve substitutes on the pivot columns of the corrector arena
 // (k_mesh_front_rhs)
 bool mesh_loads(const hommx_plan* p) { return p->family == FAM_MESH && (p->desc.flags & HOMMX_MESH_FLAG_LOADS) != 0; }
+// a plan of a nested-dissection route created with HOMMX_FLAG_TREE_LOADS / HOMMX_MESH_FLAG_TREE_LOADS whose correctors stay on the tree:
+// its load solve substitutes on the fronts the canonical pass of the chunk has left in the corrector plan's arena (mf_load_correctors)
+bool tree_loads(const hommx_plan* p) { return p->family == FAM_BLOCKED && hommx::blocked_tree_loads(p->ws); }
 // bytes of factor record per cell of that route (0 on every other)
 size_t fact_bytes(const hommx_plan* p) { return fused_subst(p) ? sizeof(double) * hommx::fused_fact_doubles(p->desc.n_micro) : 0; }
 // ... and of the scratch of its refinement step: the canonical flux field (8 n^2 doubles) and the correction (2 n^2)
@@ -602,6 +605,7 @@ int hommx_plan_create(hommx_plan** out, const hommx_plan_desc* d) {
       delete p;
       return prefix_error(rc, "blocked path: ");
     }
+    if (d->flags & HOMMX_FLAG_TREE_LOADS) hommx::blocked_enable_tree_loads(p->ws);
   }
   *out = p;
   return HOMMX_OK;
@@ -671,7 +675,7 @@ const char* hommx_plan_load_kernel_name(const hommx_plan* p) {
   switch (p->family) {
     case FAM_FUSED2D: return fused_loads(p) ? "fused2d_subst" : "blocked";
     case FAM_MESH: return mesh_loads(p) ? "mesh_front_subst" : "none";
-    default: return hommx::blocked_corrector_route_name(p->ws);
+    default: return hommx::blocked_load_route_name(p->ws);  // "multifrontal_subst" / "mesh_multifrontal_subst" with the flag on a tree plan
   }
 }
 
@@ -738,6 +742,7 @@ int hommx_plan_create_mesh(hommx_plan** out, const hommx_mesh_desc* d) {
   if (!rc) rc = hommx::mesh_geom_upload(d, geo, &p->geo);
   if (!rc) rc = m ? hommx::mesh_upload(m, p->geo) : hommx::mesh_tree_workspace(mt, p->geo, &p->ws);
   hommx::mesh_tree_destroy(mt);  // host analysis only: the workspace holds what the tree route needs
+  if (!rc && !m && (d->flags & HOMMX_MESH_FLAG_TREE_LOADS)) hommx::blocked_enable_tree_loads(p->ws);
   if (rc) {
     hommx_plan_destroy(p);
     return prefix_error(rc, "mesh route: ");
@@ -1033,8 +1038,14 @@ int64_t recon_chunk(const hommx_plan* p, int64_t n_cells, size_t extra) {
 
 // cells per chunk of an entry point whose chunks end in a load solve (load_correctors): the chunk rule of the reconstruction, and on a
 // flagged frontal mesh plan the pivot columns of the arena as well, at most one arena chunk of them -- mesh_solve then runs the chunk as
-// one arena chunk and its columns are still there when the load pass reads them
+// one arena chunk and its columns are still there when the load pass reads them; on a flagged plan of a tree route likewise at most one
+// arena chunk of its corrector plan (reserved here for the chunk the reconstruction's rule gives, as the first solve would), whose fronts
+// mf_solve then leaves whole
 int64_t load_chunk(const hommx_plan* p, int64_t n_cells, size_t extra) {
+  if (tree_loads(p)) {
+    const int64_t chunk = recon_chunk(p, n_cells, extra), arena = hommx::blocked_tree_load_chunk(p->ws, chunk);
+    return arena > 0 ? std::min(chunk, arena) : chunk;
+  }
   if (!mesh_loads(p)) return recon_chunk(p, n_cells, extra);
   return std::min<int64_t>(recon_chunk(p, n_cells, extra + hommx::mesh_arena_bytes_per_cell(p->mesh)), hommx::mesh_arena_chunk(p->mesh, n_cells));
 }
@@ -1422,7 +1433,8 @@ bool eigenstress_scratch(int32_t code, bool device) {
 // The correctors of the loads `lo` of nc cells of a chunk into corr_l[nc][t][ndof] (rows l < n_loads), on the route
 // hommx_plan_load_kernel_name names: fused 2D plans substitute on the records the canonical pass of this chunk has just left in B_FACT
 // (k_fused2d_subst_rhs), flagged frontal mesh plans on the pivot columns it has left in the arena (k_mesh_front_rhs; load_chunk keeps
-// them resident); every other plan runs a corrector pass of the blocked family on the overridden load rows
+// them resident), flagged plans of the tree routes on the fronts it has left in the corrector plan's arena (mf_load_correctors); every
+// other plan runs a corrector pass of the blocked family on the overridden load rows
 int load_correctors(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_coef, const double* d_M, const hommx::LoadOverride& lo, hipStream_t st,
                     double* corr_l) {
   if (fused_loads(p)) {
@@ -1433,6 +1445,10 @@ int load_correctors(hommx_plan* p, int64_t nc, int64_t chunk, const double* d_co
   if (mesh_loads(p)) {
     const int rc = hommx::mesh_load_correctors(p->mesh, nc, lo, d_M, corr_l, st);
     return rc ? route_fail(p, rc) : HOMMX_OK;
+  }
+  if (tree_loads(p)) {
+    const int rc = hommx::blocked_load_correctors(p->ws, nc, lo, d_M, corr_l, st);
+    return rc ? prefix_error(rc, p->desc.n_micro ? "multifrontal_subst: " : "mesh_multifrontal_subst: ") : HOMMX_OK;
   }
   const int t = p->ks.t;
   if (int rc = grow(p->buf[B_LOADS], sizeof(double) * chunk * t * t)) return rc;

@@ -134,6 +134,34 @@ const char* blocked_route_name(const BlockedWorkspace* ws) {
 
 const char* blocked_corrector_route_name(const BlockedWorkspace* ws) { return ws && ws_corr_on_tree(ws) ? blocked_route_name(ws) : "blocked"; }
 
+// Load solves on the kept fronts of the corrector plan (multifrontal.hip: mf_load_correctors).  Asked for before the corrector plan exists
+// (it sizes the row block of the forward pass); a workspace whose correctors do not stay on the tree ignores the request
+void blocked_enable_tree_loads(BlockedWorkspace* ws) {
+  if (ws && !ws->mf_keep) ws->tree_loads = ws_corr_on_tree(ws);
+}
+
+bool blocked_tree_loads(const BlockedWorkspace* ws) { return ws && ws->tree_loads; }
+
+const char* blocked_load_route_name(const BlockedWorkspace* ws) {
+  if (!blocked_tree_loads(ws)) return blocked_corrector_route_name(ws);
+  return ws->route == Route::MeshTree ? "mesh_multifrontal_subst" : "multifrontal_subst";
+}
+
+// the corrector plan of a tree route, created by the first call that needs it
+static int ws_keep_plan(BlockedWorkspace* ws) { return ws->mf_keep ? 0 : mf_plan_from_tree(ws, true, &ws->mf_keep); }
+
+long long blocked_tree_load_chunk(BlockedWorkspace* ws, long long n_cells) {
+  if (!blocked_tree_loads(ws) || n_cells <= 0) return 0;
+  if (ws_keep_plan(ws) || mf_reserve(ws, ws->mf_keep, n_cells, false)) return 0;
+  return mf_chunk(ws->mf_keep);
+}
+
+int blocked_load_correctors(BlockedWorkspace* ws, long long nc, const LoadOverride& lo, const double* d_M, double* d_corr_l, hipStream_t st) {
+  if (!blocked_tree_loads(ws) || !ws->mf_keep)
+    return fail(HOMMX_EINVAL, "%s: no corrector solve has left fronts to substitute on", blocked_load_route_name(ws));
+  return mf_load_correctors(ws, ws->mf_keep, nc, lo, d_M, d_corr_l, st);
+}
+
 // one line for reports (bench.py's roofline.kernel): what the route launches, derived from the plan itself
 const char* blocked_route_detail(BlockedWorkspace* ws) {
   if (!ws) return "";
@@ -191,8 +219,7 @@ int blocked_solve(BlockedWorkspace* ws, long long ncells, const double* d_coef, 
   if (ws_on_tree(ws) && !d_corr) return mf_solve(ws, ws->mf, ncells, d_coef, d_M, d_out, d_info, st);  // nested dissection (multifrontal.hip)
   // correctors on the same route: a second plan whose fronts keep their factors for the back substitution
   if (ws_corr_on_tree(ws)) {
-    if (!ws->mf_keep)
-      if (int rc = mf_plan_from_tree(ws, true, &ws->mf_keep)) return rc;
+    if (int rc = ws_keep_plan(ws)) return rc;
     return mf_solve(ws, ws->mf_keep, ncells, d_coef, d_M, d_out, d_info, st, d_corr, loads);
   }
   if (int rc = plane_reserve(ws, ncells, d_corr != nullptr)) return rc;

@@ -59,6 +59,7 @@ struct BlockedWorkspace {
   MfPlan* mf = nullptr;
   MfPlan* mf_keep = nullptr;   // corrector plan of the same route (fronts keep their factors), created by the first corrector call
   bool mf_corr = true;         // HOMMX_MF_CORR=0: correctors of structured multifrontal plans take the plane elimination (A/B runs)
+  bool tree_loads = false;     // load solves substitute on the kept fronts of mf_keep (blocked_enable_tree_loads; only where correctors stay on the tree)
   // mesh plans of the tree route (blocked_workspace_create_mesh): K1 is the mesh assembly on these tables, one device block owned here
   MeshAsm mesh{};
   void* mesh_tables = nullptr;  // non-null marks a mesh workspace
@@ -126,8 +127,8 @@ int mf_split_depth();
 // multifrontal.hip: the plan of ws->tree on the current device (keep: the corrector plan, every front keeps its factors)
 int mf_plan_from_tree(BlockedWorkspace* ws, bool keep, MfPlan** out);
 // its host half on any tree: boundaries, heights, groups, arena, flop model and the index tables (no GPU); the gauge is the node of highest
-// elimination rank in the root.  G supplies nn, bs, ncode.
-int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep);
+// elimination rank in the root.  G supplies nn, bs, ncode.  loads (with keep): the row block of mf_load_correctors is sized as well.
+int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep, bool loads = false);
 // what the host analysis found: fronts, groups, the largest front (s + r, unknowns), the largest (s, r) pair, arena doubles per cell, groups on
 // k_mf_front
 struct MfStats {
@@ -143,6 +144,11 @@ int mf_reserve(BlockedWorkspace* ws, MfPlan* P, long long ncells, bool ahead);
 // effective tensors, and with the corrector plan (keep = true) and d_corr != nullptr the correctors [cell][t][n^d bs] as well
 int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
              hipStream_t st, double* d_corr = nullptr, const LoadOverride* loads = nullptr);
+// The correctors of the loads `lo` of the nc cells whose factors the last corrector solve of the corrector plan P (of a workspace with
+// tree_loads) left in its arena: forward substitution up the tree on a row block of all fronts, then mf_solve's back substitution and
+// centring.  HOMMX_EINVAL unless that solve ran exactly these nc cells as one chunk (its halves and streams are taken over)
+int mf_load_correctors(BlockedWorkspace* ws, MfPlan* P, long long nc, const LoadOverride& lo, const double* d_M, double* d_corr_l, hipStream_t st);
+long long mf_chunk(const MfPlan* P);  // cells per chunk of the plan's buffers (0 before the first reservation)
 // loads.hip: Brhs of `nc` cells (the layout K1 writes) from the loads of cells [cell0, cell0 + nc) of `lo`, on the geometry of the workspace
 hipError_t launch_assemble_loads(const BlockedWorkspace* ws, const LoadOverride& lo, long long cell0, const double* Mm, long long nc,
                                  hipStream_t st, double* Brhs);

@@ -355,6 +355,20 @@ const char* blocked_route_name(const BlockedWorkspace* ws);
 const char* blocked_route_detail(BlockedWorkspace* ws);
 // the route blocked_solve takes when correctors are asked for: the tree route's name where they stay on it, else "blocked"
 const char* blocked_corrector_route_name(const BlockedWorkspace* ws);
+// Load solves by substitution on the kept fronts (HOMMX_FLAG_TREE_LOADS / HOMMX_MESH_FLAG_TREE_LOADS; multifrontal.hip, mf_load_correctors).
+// blocked_enable_tree_loads: ask for it when the plan is created -- it takes effect where the correctors stay on the tree, nowhere else;
+// blocked_tree_loads: whether it did; blocked_load_route_name: "multifrontal_subst" / "mesh_multifrontal_subst" then, else the name
+// blocked_corrector_route_name returns
+void blocked_enable_tree_loads(BlockedWorkspace* ws);
+bool blocked_tree_loads(const BlockedWorkspace* ws);
+const char* blocked_load_route_name(const BlockedWorkspace* ws);
+// cells per arena chunk of the corrector plan for batches of n_cells: builds and reserves that plan if need be, so that the rule "a chunk
+// that ends in a load solve is at most one arena chunk" has its answer before the first solve; 0: the reservation failed (the solve
+// that follows reports why)
+long long blocked_tree_load_chunk(BlockedWorkspace* ws, long long n_cells);
+// the correctors [cell][t][ndof] of the loads `lo` (rows l < n_loads, the rest zero) of the nc cells whose canonical corrector pass was the
+// last call of blocked_solve with correctors: nothing is eliminated again; HOMMX_EINVAL when the arena does not hold exactly these cells
+int blocked_load_correctors(BlockedWorkspace* ws, long long nc, const LoadOverride& lo, const double* d_M, double* d_corr_l, hipStream_t stream);
 // dense flops one micro-cell solve executes on this route, by the route's own model (multifrontal: sum over the fronts of
 // s^3 + 2 s^2 r + s r^2 on the padded sizes; plane elimination: (6 (n - 1) + 2) b^3)
 double blocked_flops_per_cell(const BlockedWorkspace* ws);

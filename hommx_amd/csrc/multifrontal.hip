@@ -61,6 +61,9 @@ struct MfGroup {
   int32_t* d_cpos = nullptr;        // [nf][2][nloc]   position of local node in child c's boundary list, -1: not there
   int32_t* d_dpos = nullptr;        // [nf][2][rp]     unknown of child c's boundary block for boundary unknown p of this front, -1: none
   MfChild* d_child = nullptr;       // [nf][2]
+  // load solves on the kept fronts (MfPlan::loads): the group's place in the per-cell row block R [nf][MF_BORDER][L] of the forward pass
+  long long offR = 0;
+  long long* d_croff = nullptr;     // [nf][2]         offR of child c's group
   // register-resident route of the group (mf_front.h: k_mf_front), when the whole front fits the registers of one workgroup
   bool front = false;
   int s16 = 0, T = 0, P = 0, ntiles = 0;   // 16-granular padded s, tiles per dimension, panels, upper tiles
@@ -72,6 +75,7 @@ struct MfGroup {
   std::vector<int32_t> h_nodes, h_cpos, h_dpos, h_upos;
   std::vector<int8_t> h_code;
   std::vector<MfChild> h_child;
+  std::vector<long long> h_croff;
   std::vector<uint16_t> h_tilemap;
 };
 
@@ -86,9 +90,15 @@ struct MfPlan {
   int front_max_t = MFF_MAX_T;      // HOMMX_MF_FRONT: most 16-tiles per dimension of a front that takes k_mf_front (0: never; at most MFF_MAX_T)
   bool keep = false;                // corrector plan: every front keeps its own place in the arena (the back substitution reads N and X of all of them)
   long long vbuf_per_cell = 0;      // doubles: solution vectors of the largest group, [nf][MF_BORDER][L] (corrector plan)
+  bool loads = false;               // corrector plan of a workspace with tree_loads: load solves substitute on the kept fronts (mf_load_correctors)
+  long long rbuf_per_cell = 0;      // doubles: the row blocks of ALL fronts, sum of nf MF_BORDER L (loads; else 0)
+  // what the last corrector solve left in the arena (loads): the cells of its only chunk (0: nothing a load solve may read) and its pieces
+  long long kept_cells = 0;
+  int kept_nh = 0;
+  long long kept_a[4] = {0, 0, 0, 0}, kept_n[4] = {0, 0, 0, 0};  // first cell and cells of piece k
   // chunk buffers
   long long chunk = 0;
-  double *arena = nullptr, *scratch = nullptr, *vbuf = nullptr;
+  double *arena = nullptr, *scratch = nullptr, *vbuf = nullptr, *rbuf = nullptr;
   double *Kst = nullptr, *Brhs = nullptr, *C0 = nullptr;  // K1 output of this route's chunks (the plane elimination keeps its own)
   double* Cn = nullptr;    // magnitude normalisation (blocked_internal.h): the scaled coefficient stream of the chunk
   int32_t* Esh = nullptr;  // and the exponent of every cell
@@ -252,10 +262,11 @@ void mf_plan_destroy(MfPlan* p) {
     if (g.d_cpos) (void)hipFree(g.d_cpos);
     if (g.d_dpos) (void)hipFree(g.d_dpos);
     if (g.d_child) (void)hipFree(g.d_child);
+    if (g.d_croff) (void)hipFree(g.d_croff);
     if (g.d_upos) (void)hipFree(g.d_upos);
     if (g.d_tilemap) (void)hipFree(g.d_tilemap);
   }
-  for (double* q : {p->arena, p->scratch, p->vbuf, p->Kst, p->Brhs, p->C0, p->Cn})
+  for (double* q : {p->arena, p->scratch, p->vbuf, p->rbuf, p->Kst, p->Brhs, p->C0, p->Cn})
     if (q) (void)hipFree(q);
   if (p->Esh) (void)hipFree(p->Esh);
   for (int k = 0; k < 3; ++k) {
@@ -339,11 +350,12 @@ void mf_tree_structured(const Geo& G, MfTree* T) {
   }
 }
 
-int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep) {
+int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep, bool loads) {
   *out = nullptr;
   MfPlan* P = new MfPlan();
   P->G = G;
   P->keep = keep;
+  P->loads = keep && loads;
   const int bs = G.bs, nn = G.nn;
   if (const char* e = getenv("HOMMX_MF_STAGE")) P->stage = atoi(e);
   if (const char* e = getenv("HOMMX_MF_STREAMS")) P->streams = atoi(e);
@@ -488,6 +500,10 @@ int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep) {
       mg.offF = place((long long)mg.nf * mg.L * mg.L, expiry[t], t);
       P->scratch_per_cell = std::max(P->scratch_per_cell, (long long)mg.nf * mg.sp * mg.sp);
       if (keep) P->vbuf_per_cell = std::max(P->vbuf_per_cell, (long long)mg.nf * MF_BORDER * mg.L);
+      if (P->loads) {  // every front keeps its rows: the back substitution of a load solve reads z_i of all of them
+        mg.offR = P->rbuf_per_cell;
+        P->rbuf_per_cell += (long long)mg.nf * MF_BORDER * mg.L;
+      }
       if (mg.front) {  // k_mf_front: per panel p of 16 pivots the sweep, T - 1 - p products Y'_a and (T - 1 - p)(T - p) / 2 tile updates of 4 MFMAs
         double f = 0.0;
         for (int pp = 0; pp < mg.P; ++pp) {
@@ -526,6 +542,7 @@ int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep) {
     dpos.assign((size_t)mg.nf * 2 * mg.rp, -1);
     code.assign((size_t)mg.nf * nloc * mg.ns + 4, (int8_t)-1);  // + 4: k_mf_front stages the tables word by word
     child.assign((size_t)mg.nf * 2, MfChild{});
+    mg.h_croff.assign(P->loads ? (size_t)mg.nf * 2 : 0, 0);
     const int NUf = 16 * mg.T;
     upos.assign(mg.front ? (size_t)mg.nf * 2 * NUf : 0, -1);
     for (int f = 0; f < mg.nf; ++f) {
@@ -553,6 +570,7 @@ int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep) {
         ch.sp = cg.sp;
         ch.rb = cg.rb;
         ch.valid = 1;
+        if (P->loads) mg.h_croff[(size_t)f * 2 + slot] = cg.offR;
         for (int q = 0; q < (int)cs.bnd.size(); ++q) {
           const int i = local[cs.bnd[q]];
           if (i < 0) {
@@ -602,10 +620,10 @@ int mf_plan_build(MfPlan** out, const Geo& G, const MfTree& T, bool keep) {
 int mf_plan_from_tree(BlockedWorkspace* ws, bool keep, MfPlan** out) {
   *out = nullptr;
   MfPlan* P = nullptr;
-  if (int rc = mf_plan_build(&P, ws->G, ws->tree, keep)) return rc;
+  if (int rc = mf_plan_build(&P, ws->G, ws->tree, keep, ws->tree_loads)) return rc;
   for (MfGroup& mg : P->groups)
     if (upload(&mg.d_nodes, mg.h_nodes) || upload(&mg.d_code, mg.h_code) || upload(&mg.d_cpos, mg.h_cpos) || upload(&mg.d_dpos, mg.h_dpos) ||
-        upload(&mg.d_child, mg.h_child) || upload(&mg.d_upos, mg.h_upos) || upload(&mg.d_tilemap, mg.h_tilemap)) {
+        upload(&mg.d_child, mg.h_child) || upload(&mg.d_croff, mg.h_croff) || upload(&mg.d_upos, mg.h_upos) || upload(&mg.d_tilemap, mg.h_tilemap)) {
       mf_plan_destroy(P);
       return HOMMX_EHIP;
     }
@@ -807,10 +825,13 @@ __global__ void k_mf_finalize(const double* __restrict__ C0, const double* __res
 //     v[stage i]   = X_i[:, border m] - X_i[:, later stages and boundary] v[later stages and boundary]     (last stage first)
 //   X_i = N_i E_i^T, and border column m of X_i is N_i times the forward-eliminated load vector (the border rows took part in the
 //   elimination).  The products run as thin batched GEMMs (k_gemm_tile, M = 8 load rows); V is [front][8][L].
+//   Z (a load solve on the kept fronts, mf_load_correctors): the rows [front][8][L] of the group whose eliminated part holds
+//   z_i = N_i y_i of the forward pass, read in place of the border columns; null: the canonical loads.
 // ---------------------------------------------------------------------------------------------------------------
 template <int BS>
 __global__ __launch_bounds__(256) void k_mf_bs_init(MfGroupDev g, const double* __restrict__ arena, double* __restrict__ V,
-                                                    const double* __restrict__ corr, long long nc, int t, long long ndof) {
+                                                    const double* __restrict__ corr, long long nc, int t, long long ndof,
+                                                    const double* __restrict__ Z) {
   const long long nb = nc * g.nf;
   for (long long batch = blockIdx.x; batch < nb; batch += gridDim.x) {
     const long long cell = batch / g.nf;
@@ -821,7 +842,7 @@ __global__ __launch_bounds__(256) void k_mf_bs_init(MfGroupDev g, const double* 
     for (int w = threadIdx.x; w < MF_BORDER * g.L; w += 256) {
       const int m = w / g.L, q = w % g.L;
       double x = 0.0;
-      if (q < g.sp) x = F[(long long)q * g.L + g.sp + g.rb + m];
+      if (q < g.sp) x = Z ? Z[batch * (long long)MF_BORDER * g.L + w] : F[(long long)q * g.L + g.sp + g.rb + m];
       else if (q < g.sp + g.rb && m < t) {
         const int p = q - g.sp;
         x = corr[(cell * t + m) * ndof + (long long)nodes[g.ns + p / BS] * BS + p % BS];
@@ -849,12 +870,74 @@ __global__ __launch_bounds__(256) void k_mf_bs_store(MfGroupDev g, const double*
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// load solves on the kept fronts: forward substitution up the tree (mf_load_correctors).  The border rows of the elimination carry the
+// canonical loads through exactly this pass; a load that was not in them when the fronts were built takes it on a row block
+// R [front][8][L] of its own, one per front of the cell and all of them resident (the back substitution reads every front's):
+//     R[:, eliminated]  = the assembled load at the front's own unknowns + the children's boundary parts
+//     R[:, boundary]    = the children's boundary parts
+//   then per stage i, in elimination order, with y_i = R[:, stage i]:
+//     R[:, later stages and boundary] -= y_i X_i[:, later stages and boundary]      (X_i = N_i E_i^T as the elimination left it)
+//     R[:, stage i]                    = z_i = y_i N_i                              (through V: a product does not run in place)
+//   z_i is what k_mf_bs_init reads as "border column m of X_i".
+// ---------------------------------------------------------------------------------------------------------------
+// rows of every (cell, front) of the group before its stages: one thread per entry (m, q); zero in the identity padding, at the pinned
+// gauge unknowns (k_mf_pad clears the load rows there) and behind the boundary; the children's rows are complete (lower groups first).
+// croff [nf][2]: the row-block offset of each child's group
+template <int BS>
+__global__ __launch_bounds__(256) void k_mf_fw_init(MfGroupDev g, const long long* __restrict__ croff, const double* __restrict__ Brhs,
+                                                    double* __restrict__ R, long long offR, long long nc, int nn, int t, int pinpos) {
+  const long long nb = nc * g.nf;
+  for (long long batch = blockIdx.x; batch < nb; batch += gridDim.x) {
+    const long long cell = batch / g.nf;
+    const int f = (int)(batch % g.nf);
+    const int32_t* nodes = g.nodes + (long long)f * g.nloc;
+    const MfChild ch0 = g.child[f * 2], ch1 = g.child[f * 2 + 1];
+    const int32_t* cp0 = g.cpos + ((long long)f * 2) * g.nloc;
+    const int32_t* cp1 = cp0 + g.nloc;
+    const double* R0 = R + nc * croff[f * 2] + (cell * ch0.nf + ch0.fidx) * (long long)MF_BORDER * ch0.L + ch0.sp;
+    const double* R1 = R + nc * croff[f * 2 + 1] + (cell * ch1.nf + ch1.fidx) * (long long)MF_BORDER * ch1.L + ch1.sp;
+    double* r = R + nc * offR + batch * (long long)MF_BORDER * g.L;
+    for (int w = threadIdx.x; w < MF_BORDER * g.L; w += 256) {
+      const int m = w / g.L, q = w % g.L;
+      int i = -1, b = 0;  // local node and component of unknown q
+      if (q < g.ns * BS) {
+        i = q / BS;
+        b = q - i * BS;
+      } else if (q >= g.sp && q < g.sp + g.rb) {
+        i = g.ns + (q - g.sp) / BS;
+        b = (q - g.sp) % BS;
+      }
+      double x = 0.0;
+      if (i >= 0 && i != pinpos) {
+        if (i < g.ns && m < t) x = Brhs[cell * (long long)t * BS * nn + ((long long)m * BS + b) * nn + nodes[i]];
+        const int c0 = ch0.valid ? cp0[i] : -1, c1 = ch1.valid ? cp1[i] : -1;
+        if (c0 >= 0) x += R0[(long long)m * ch0.L + c0 * BS + b];
+        if (c1 >= 0) x += R1[(long long)m * ch1.L + c1 * BS + b];
+      }
+      r[w] = x;
+    }
+  }
+}
+
+// z_i of every stage from V into the eliminated part of the group's rows
+__global__ __launch_bounds__(256) void k_mf_fw_keep(const double* __restrict__ V, double* __restrict__ R, int L, int sp, long long nb) {
+  for (long long batch = blockIdx.x; batch < nb; batch += gridDim.x) {
+    const double* v = V + batch * (long long)MF_BORDER * L;
+    double* r = R + batch * (long long)MF_BORDER * L;
+    for (int w = threadIdx.x; w < MF_BORDER * sp; w += 256) {
+      const int m = w / sp, q = w % sp;
+      r[m * L + q] = v[m * L + q];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------------------------------
 int mf_reserve(BlockedWorkspace* ws, MfPlan* P, long long ncells, bool ahead) {
   const Geo& G = ws->G;
   const long long stencil = (long long)G.ncode * G.bs * G.bs * G.nn + (long long)G.t * G.bs * G.nn + 36 + (long long)G.n_el * G.ncomp + 1;
-  const long long per_cell = 8ll * (P->arena_per_cell + P->scratch_per_cell + P->vbuf_per_cell + stencil);
+  const long long per_cell = 8ll * (P->arena_per_cell + P->scratch_per_cell + P->vbuf_per_cell + P->rbuf_per_cell + stencil);
   // Fronts are big (C4 / C5: 0.2 GB per cell) and the card has 288 GB, but a call pays for what it allocates (2.5 - 3 s per 64 GB
   // measured) and the throughput is nearly flat from 256 cells per chunk (C4: 2,390 / 2,510 / 2,580 / 2,655 / 2,654 solves/s at 64 / 128 /
   // 192 / 256 / 384 cells; all of C5: 2,590 with 64 GB, 2,640 with 128).  A solve that has to allocate takes 64 GB (more, to 128 GB, only
@@ -880,7 +963,8 @@ int mf_reserve(BlockedWorkspace* ws, MfPlan* P, long long ncells, bool ahead) {
         if (mn > 0 && ty >= 2 * ws->tile_sb) (void)ensure_tilemap(ws, ty);
       }
   if (chunk <= P->chunk) return 0;
-  for (double** p : {&P->arena, &P->scratch, &P->vbuf, &P->Kst, &P->Brhs, &P->C0, &P->Cn}) {
+  P->kept_cells = 0;  // the arena goes: no load solve may read it
+  for (double** p : {&P->arena, &P->scratch, &P->vbuf, &P->rbuf, &P->Kst, &P->Brhs, &P->C0, &P->Cn}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
@@ -890,6 +974,7 @@ int mf_reserve(BlockedWorkspace* ws, MfPlan* P, long long ncells, bool ahead) {
   HIP_TRY(hipMalloc(&P->arena, 8ll * chunk * P->arena_per_cell));
   HIP_TRY(hipMalloc(&P->scratch, 8ll * chunk * P->scratch_per_cell));
   if (P->vbuf_per_cell) HIP_TRY(hipMalloc(&P->vbuf, 8ll * chunk * P->vbuf_per_cell));
+  if (P->rbuf_per_cell) HIP_TRY(hipMalloc(&P->rbuf, 8ll * chunk * P->rbuf_per_cell));
   HIP_TRY(hipMalloc(&P->Kst, 8ll * chunk * G.ncode * G.bs * G.bs * G.nn));
   HIP_TRY(hipMalloc(&P->Brhs, 8ll * chunk * G.t * G.bs * G.nn));
   HIP_TRY(hipMalloc(&P->C0, 8ll * chunk * 36));
@@ -997,7 +1082,8 @@ void mf_group_step(BlockedWorkspace* ws, MfPlan* P, const MfHalf& h, const MfGro
 }
 
 // back substitution of one group of fronts for one half (corrector plan): the unknowns the group eliminates, for every load case
-void mf_backsub_step(BlockedWorkspace* ws, MfPlan* P, const MfHalf& h, const MfGroup& mg, double* d_corr) {
+// rows: the piece's row block of a load solve (mf_load_correctors) in place of the border columns of the fronts; null: the canonical loads
+void mf_backsub_step(BlockedWorkspace* ws, MfPlan* P, const MfHalf& h, const MfGroup& mg, double* d_corr, const double* rows = nullptr) {
   const Geo& G = ws->G;
   const int bs = G.bs;
   const long long nc = h.nc, nb = nc * mg.nf, ndof = (long long)G.nn * bs;
@@ -1013,7 +1099,7 @@ void mf_backsub_step(BlockedWorkspace* ws, MfPlan* P, const MfHalf& h, const MfG
     else if (bs == 2) hipLaunchKernelGGL((KERN<2>), dim3(blocks), dim3(256), 0, st, __VA_ARGS__);        \
     else hipLaunchKernelGGL((KERN<3>), dim3(blocks), dim3(256), 0, st, __VA_ARGS__);                     \
   } while (0)
-  HOMMX_MF_BS(k_mf_bs_init, gd, arena, V, corr, nc, G.t, ndof);
+  HOMMX_MF_BS(k_mf_bs_init, gd, arena, V, corr, nc, G.t, ndof, rows ? rows + nc * mg.offR : nullptr);
   const double* F = arena + nc * mg.offF;
   const long long sF = (long long)mg.L * mg.L, sV = (long long)MF_BORDER * mg.L;
   Ctx c{ws, nb, st, nullptr, 0};
@@ -1031,13 +1117,94 @@ void mf_backsub_step(BlockedWorkspace* ws, MfPlan* P, const MfHalf& h, const MfG
 #undef HOMMX_MF_BS
 }
 
+// forward substitution of one group of fronts for one half (a load solve on the kept fronts): rows of the group from the assembled loads
+// and the children's rows, then stage by stage
+void mf_forward_step(BlockedWorkspace* ws, MfPlan* P, const MfHalf& h, const MfGroup& mg) {
+  const Geo& G = ws->G;
+  const int bs = G.bs;
+  const long long nc = h.nc, nb = nc * mg.nf;
+  hipStream_t st = h.st;
+  const double* arena = P->arena + h.base * P->arena_per_cell;
+  double* V = P->vbuf + h.base * P->vbuf_per_cell;
+  double* Rh = P->rbuf + h.base * P->rbuf_per_cell;
+  const double* Brhs = P->Brhs + h.base * G.t * bs * G.nn;
+  MfGroupDev gd{mg.ns, mg.ns + mg.nr, mg.sp, mg.rb, mg.L, mg.nf, mg.offF, mg.d_nodes, mg.d_code, mg.d_cpos, mg.d_child};
+  const unsigned blocks = (unsigned)std::min(nb, 1ll << 22);
+  if (bs == 1) hipLaunchKernelGGL((k_mf_fw_init<1>), dim3(blocks), dim3(256), 0, st, gd, mg.d_croff, Brhs, Rh, mg.offR, nc, G.nn, G.t, mg.pinpos);
+  else if (bs == 2) hipLaunchKernelGGL((k_mf_fw_init<2>), dim3(blocks), dim3(256), 0, st, gd, mg.d_croff, Brhs, Rh, mg.offR, nc, G.nn, G.t, mg.pinpos);
+  else hipLaunchKernelGGL((k_mf_fw_init<3>), dim3(blocks), dim3(256), 0, st, gd, mg.d_croff, Brhs, Rh, mg.offR, nc, G.nn, G.t, mg.pinpos);
+  const double* F = arena + nc * mg.offF;
+  double* R = Rh + nc * mg.offR;
+  const long long sF = (long long)mg.L * mg.L, sV = (long long)MF_BORDER * mg.L;
+  Ctx c{ws, nb, st, nullptr, 0};
+  const int nst = mf_stages(mg.sp, P->stage);
+  int off = 0;
+  for (int i = 0; i < nst; ++i) {
+    const int si = mf_stage_size(mg.sp, nst, i);
+    const int rest = mg.sp + mg.rb - (off + si);
+    if (rest > 0)  // R[:, later stages and boundary] -= y_i X_i: C (8 x rest) -= A (8 x si) B (B = X_i: si x rest)
+      gemm(c, false, false, MF_BORDER, rest, si, -1.0, R + off, mg.L, sV, F + (long long)off * mg.L + off + si, mg.L, sF, 1.0, R + off + si, mg.L, sV);
+    gemm(c, false, false, MF_BORDER, si, si, 1.0, R + off, mg.L, sV, F + (long long)off * mg.L + off, mg.L, sF, 0.0, V + off, mg.L, sV);  // z_i = y_i N_i
+    off += si;
+  }
+  hipLaunchKernelGGL(k_mf_fw_keep, dim3(blocks), dim3(256), 0, st, V, R, mg.L, mg.sp, nb);
+}
+
 }  // namespace
+
+long long mf_chunk(const MfPlan* P) { return P ? P->chunk : 0; }
+
+int mf_load_correctors(BlockedWorkspace* ws, MfPlan* P, long long nc, const LoadOverride& lo, const double* d_M, double* d_corr_l, hipStream_t st) {
+  const Geo& G = ws->G;
+  const int bs = G.bs;
+  if (nc <= 0) return 0;
+  if (!P->loads) return fail(HOMMX_EINVAL, "load solve on the kept fronts: the corrector plan was built without its row block");
+  if (lo.n_loads < 1 || lo.n_loads > G.t || lo.n_loads > MF_BORDER || !lo.P)
+    return fail(HOMMX_EINVAL, "load solve on the kept fronts: n_loads must be 1 .. %d with loads given", G.t);
+  if (nc != P->kept_cells)
+    return fail(HOMMX_EINVAL, "load solve of %lld cells on the kept fronts, but the arena holds the factors of %lld: the corrector solve before "
+                              "it must run exactly these cells as one arena chunk",
+                nc, P->kept_cells);
+  // the pieces and streams of the solve that left the factors (mf_solve): every buffer of a piece starts where it did
+  const int nh = P->kept_nh;
+  MfHalf halves[4];
+  for (int k = 0; k < nh; ++k) halves[k] = MfHalf{P->kept_a[k], P->kept_n[k], P->kept_a[k], k == 0 ? st : P->side[k - 1]};
+  int forked = 0;
+  auto join = [&]() {
+    for (int k = 1; k < forked; ++k) (void)hipStreamSynchronize(P->side[k - 1]);
+  };
+  if (nh > 1) {
+    HIP_TRY(hipEventRecord(P->ev_fork, st));
+    for (int k = 1; k < nh; ++k) {
+      forked = k + 1;
+      HIP_TRY_OR(join(), hipStreamWaitEvent(P->side[k - 1], P->ev_fork, 0));
+    }
+  }
+  for (int k = 0; k < nh; ++k) {  // the loads in the layout K1 writes, at the magnitude the cell was eliminated at (the plan keeps Esh)
+    const MfHalf& h = halves[k];
+    double* Brhs = P->Brhs + h.base * G.t * bs * G.nn;
+    HIP_TRY_OR(join(), launch_assemble_loads(ws, lo, h.c0, d_M ? d_M + h.c0 * G.dim * G.dim : nullptr, h.nc, h.st, Brhs));
+    launch_scale_cells(Brhs, (long long)G.t * bs * G.nn, P->Esh + h.base, -1, h.nc, h.st);
+  }
+  for (const MfGroup& mg : P->groups)
+    for (int k = 0; k < nh; ++k) mf_forward_step(ws, P, halves[k], mg);
+  for (auto it = P->groups.rbegin(); it != P->groups.rend(); ++it)
+    for (int k = 0; k < nh; ++k) mf_backsub_step(ws, P, halves[k], *it, d_corr_l, P->rbuf + halves[k].base * P->rbuf_per_cell);
+  for (int k = 0; k < nh; ++k) launch_center_corr(ws, d_corr_l + halves[k].c0 * G.t * (long long)G.nn * bs, halves[k].nc, halves[k].st);
+  for (int k = 1; k < nh; ++k) {
+    HIP_TRY_OR(join(), hipEventRecord(P->ev_join[k - 1], P->side[k - 1]));
+    HIP_TRY_OR(join(), hipStreamWaitEvent(st, P->ev_join[k - 1], 0));
+  }
+  HIP_TRY_OR(join(), hipGetLastError());
+  return 0;
+}
 
 int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_coef, const double* d_M, double* d_out, int32_t* d_info,
              hipStream_t st, double* d_corr, const LoadOverride* loads) {
   const Geo& G = ws->G;
   if (d_corr && !P->keep) return fail(HOMMX_EINVAL, "mf_solve: correctors need the corrector plan");
   if (int rc = mf_reserve(ws, P, ncells, false)) return rc;
+  P->kept_cells = 0;  // the arena is rewritten: a load solve may read it again once this call has left the factors of one whole chunk
   if (d_info) HIP_TRY(hipMemsetAsync(d_info, 0, sizeof(int32_t) * ncells, st));
   long long step_cells = P->chunk;
   {
@@ -1122,6 +1289,14 @@ int mf_solve(BlockedWorkspace* ws, MfPlan* P, long long ncells, const double* d_
     }
     HIP_TRY_OR(join(), hipGetLastError());
     forked = 0;
+    if (P->loads && d_corr && nc == ncells) {  // the only chunk: what mf_load_correctors may substitute on, and how it was cut
+      P->kept_nh = nh;
+      for (int k = 0; k < nh; ++k) {
+        P->kept_a[k] = halves[k].base;
+        P->kept_n[k] = halves[k].nc;
+      }
+      P->kept_cells = ncells;
+    }
   }
   return 0;
 }

@@ -266,6 +266,7 @@ class BaseHMM(ABC):
         rhs_quadrature_degree: int = 6,
         device: int | None = None,
         reserve: bool = False,
+        tree_loads: bool = False,
     ):
         """``quadrature_degree``: degree of the micro quadrature rule that samples ``A(x, .)``.  The reference lets UFL estimate it
         from the expression (hmm.py:190-198 + fem.form at :644-647): 0 for a ``conditional`` between constants, 3 for one
@@ -283,7 +284,10 @@ class BaseHMM(ABC):
         ``reserve``: create the plan and allocate its device workspace for this rank's share of the macro cells NOW (``prepare()``)
         instead of inside the first ``solve()`` -- the nested-dissection route of the C4 / C5 size holds 0.2 GB of fronts per cell
         of a chunk, 0.5 - 3 s of ``hipMalloc`` that the first assembly would otherwise hide.  Resolves the device at construction
-        time, so leave it off when the solver is built before ``init_process_group``; ``prepare()`` can be called later."""
+        time, so leave it off when the solver is built before ``init_process_group``; ``prepare()`` can be called later.
+        ``tree_loads``: the plan is created with ``tree_loads=True`` (``MicroCellPlan``): where it takes a nested-dissection route, the
+        load solves of ``load_response()``, ``criterion()``, ``solve_nonlinear(load=True)`` and the second derivatives substitute on
+        the kept fronts instead of eliminating again.  Off by default; the sibling plan of ``method="newton"`` never needs it."""
         self._logger = logging.getLogger(__name__)
         self._msh = msh
         self._comm = msh.comm
@@ -317,6 +321,7 @@ class BaseHMM(ABC):
         self._rhs_degree = rhs_quadrature_degree
         self._device = device  # None: resolved lazily in _ensure_plan (the solver may be built before init_process_group)
         self._reserve_at_construction = bool(reserve)
+        self._plan_options = {"tree_loads": True} if tree_loads else {}  # what both kinds of plan are asked for beside the defaults
 
         self._V_macro = self._setup_macro_function_space()
         self._macro_coordinates = self._V_macro.tabulate_dof_coordinates()
@@ -741,9 +746,9 @@ class BaseHMM(ABC):
                 self._device = default_device()
             if self._n_micro is None:
                 # load_solve: the frontal route serves load_response() and the second derivatives as every other route does
-                self._plan = MicroCellPlan.from_mesh(self._cell_mesh, kind, device=self._device, load_solve=True)
+                self._plan = MicroCellPlan.from_mesh(self._cell_mesh, kind, device=self._device, load_solve=True, **self._plan_options)
             else:
-                self._plan = MicroCellPlan(self._tdim, self._n_micro, kind, device=self._device)
+                self._plan = MicroCellPlan(self._tdim, self._n_micro, kind, device=self._device, **self._plan_options)
             self._reserved_cells = 0
         if n_cells and n_cells > self._reserved_cells:
             self._plan.reserve(int(n_cells))

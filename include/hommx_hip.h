@@ -41,6 +41,11 @@ extern "C" {
                                            the t x t matrix  E^m : A : E^n  (tensorial unit strains), row-major */
 
 #define HOMMX_FLAG_FORCE_BLOCKED 1     /* use the generic blocked kernel family even where the fused 2D kernel applies */
+#define HOMMX_FLAG_TREE_LOADS 4        /* a plan of the nested-dissection route ("multifrontal") does its load solves by substitution on
+                                          the fronts the canonical pass of the chunk has just left in the corrector plan's arena
+                                          ("multifrontal_subst", hommx_plan_load_kernel_name) instead of a second elimination; a chunk is
+                                          then at most one arena chunk of that plan.  Off by default; accepted and without effect on every
+                                          other route (and with HOMMX_MF_CORR=0).  Same bit as HOMMX_MESH_FLAG_TREE_LOADS */
 
 /* Environment knobs (development / tuning; read once, when a plan is created):
  *   HOMMX_BLOCKED_MEM_GB   workspace budget of the blocked family in GB (default: plane elimination min(64, half of the free HBM),
@@ -58,7 +63,8 @@ extern "C" {
  *   HOMMX_MF_STREAMS       1: the nested-dissection route runs on the caller's stream alone (default 4: every chunk as two to four pieces side
  *                          by side on the caller's stream and plan-owned ones; the caller's stream waits for all, results are bitwise equal)
  *   HOMMX_MF_CORR          0: hommx_solve_batch_correctors of a nested-dissection plan runs the plane elimination (default: back substitution
- *                          down the elimination tree on a second plan whose fronts all stay resident)
+ *                          down the elimination tree on a second plan whose fronts all stay resident); HOMMX_FLAG_TREE_LOADS then has
+ *                          no effect: there are no kept fronts to substitute on
  *   HOMMX_MF_LEAF, HOMMX_MF_SPLIT_DEPTH, HOMMX_MF_VERBOSE   tuning / A-B knobs of that route
  *   HOMMX_SMALL_WAVES      2 / 4: plane blocks b <= 48 take the LDS-resident multi-wave kernel (that many waves per macro cell)
  *                          instead of the one-wave-per-cell register kernel; for 48 < b <= 64 it sets that kernel's wave count
@@ -118,8 +124,10 @@ const char* hommx_plan_kernel_name(const hommx_plan* plan);
 const char* hommx_plan_corrector_kernel_name(const hommx_plan* plan);
 /* The route the load solve of hommx_loads_source[_device] takes (the response outputs; P_eff alone needs none): "fused2d_subst" (fused 2D
  * plans; "blocked" with HOMMX_FUSED_LOADS=0 or HOMMX_FUSED_CORR=0), "mesh_front_subst" (frontal mesh plans created with HOMMX_MESH_FLAG_LOADS:
- * substitution on the pivot columns of the corrector arena), "none" (frontal mesh plans without the flag: the response is refused), else
- * the name hommx_plan_corrector_kernel_name returns. */
+ * substitution on the pivot columns of the corrector arena), "none" (frontal mesh plans without the flag: the response is refused),
+ * "multifrontal_subst" / "mesh_multifrontal_subst" (nested-dissection plans created with HOMMX_FLAG_TREE_LOADS / HOMMX_MESH_FLAG_TREE_LOADS
+ * whose correctors stay on the tree: forward and backward substitution on the kept fronts of the chunk's canonical pass), else the name
+ * hommx_plan_corrector_kernel_name returns. */
 const char* hommx_plan_load_kernel_name(const hommx_plan* plan);
 /* One line describing what that route launches for THIS plan (kernel names with their tile sizes, tree shape of the nested dissection,
  * stage size, streams): for reports -- bench.py's roofline.kernel label is this string, so it cannot drift from the code. */
@@ -530,6 +538,9 @@ int hommx_stratification_sensitivity_source_device(hommx_plan* plan, int64_t n_c
  * HOMMX_FUSED_LOADS=0 it gets a blocked workspace on the first such call instead), every other plan runs one more corrector pass of the
  * blocked family with the load rows replaced (a mesh plan of the tree route among them); a frontal mesh plan substitutes on the pivot
  * columns its canonical pass has just left in the corrector arena (k_mesh_front_rhs) when it was created with HOMMX_MESH_FLAG_LOADS.
+ * A plan of a nested-dissection route created with HOMMX_FLAG_TREE_LOADS / HOMMX_MESH_FLAG_TREE_LOADS substitutes on the fronts its
+ * canonical pass has just left in the corrector plan's arena instead (forwards up the tree on a row block of all fronts, backwards by
+ * the back substitution of the canonical correctors); a chunk is then at most one arena chunk of that plan (HOMMX_BLOCKED_MEM_GB).
  *
  *   n_loads     1 .. t of the plan (callers loop for more)
  *   per_cell    a code: where the load comes from, alone or or-ed with the flag HOMMX_LOADS_EIGENSTRAIN
@@ -987,6 +998,9 @@ int hommx_secant_state_source_device(hommx_plan* plan, int64_t n_cells, const ho
 #define HOMMX_MESH_FLAG_LOADS 2   /* hommx_mesh_desc.flags: a plan of the frontal route gets a load solve ("mesh_front_subst": the
                                    * response outputs of hommx_loads_source, hommx_second_sensitivity_source); without it such a plan
                                    * refuses them.  Ignored on the tree route, which has its own; the plan's descriptor keeps the bit */
+/* hommx_mesh_desc.flags, value 4: a plan of the tree route does its load solves by substitution on the kept fronts of the chunk's canonical
+ * pass ("mesh_multifrontal_subst") instead of a second elimination; accepted and without effect on the frontal route.  Off by default */
+#define HOMMX_MESH_FLAG_TREE_LOADS HOMMX_FLAG_TREE_LOADS
 
 typedef struct hommx_mesh_desc {
   int32_t dim, kind, device, flags;   /* as hommx_plan_desc; flags: 0 or HOMMX_MESH_FLAG_* or'ed                  */
